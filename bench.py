@@ -2,7 +2,7 @@
 """Headline benchmark of the hot path (BASELINE.json): batched greedy HNSW search on
 1M x 768 f32 vectors, queries/sec at recall@10 >= 0.95, one process per GPU.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = one pass of the search path over one batch of --queries synthetic queries per GPU
@@ -10,12 +10,19 @@ A step = one pass of the search path over one batch of --queries synthetic queri
 (search replicates, north_star) and searches its own query batch: weak scaling, no data-path
 collective; index construction is sharded over the ranks.  Rank 0 prints ONE JSON line.
 
+A plain run does what the headline needs: one index build, the calibration sweep that picks the
+search parameters, W + K steps, the recall of the timed batches, and a compact line.  --full adds
+everything else: the second build, the one-stream timing, per-dispatch times and the roofline, the
+batch sweeps, CPU baseline, PQ, host path, sharded build, the other datasets and the counter passes.
+--dump-outputs DIR writes what the last timed step handed its caller (ids, distances, lengths,
+counters, status) as .npy files; the inputs are seeded, so two builds can be compared file by file.
+
 Processes.  Started plainly (no RANK in the environment) this file is a driver that never touches
 the GPU: it starts the measuring worker(s) as child processes -- N of them for --gpus N, with the
-torchrun environment -- and, at N = 1, two short `rocprofv3 --pmc` passes over the SAME index (the
-worker serialises it) whose memory-side byte counters become `roofline.traffic`.  Under torchrun
-(RANK set) or with --role worker the file is the worker itself; profile that form
-(`rocprofv3 --kernel-trace --stats -- python3 bench.py --role worker ...`).
+torchrun environment -- and, at N = 1 with --full, two short `rocprofv3 --pmc` passes over the SAME
+index (the worker serialises it) whose memory-side byte counters become `roofline.traffic`.  Under
+torchrun (RANK set) or with --role worker the file is the worker itself; profile that form
+(`rocprofv3 --kernel-trace --stats -- python3 bench.py --role worker --full ...`).
 """
 import argparse
 import csv
@@ -69,10 +76,17 @@ def parse_args(argv=None):
                     help="N > 1: do not measure the sharded index build after the search measurement")
     ap.add_argument("--sharded-timeout", type=int, default=300, help="N > 1: watchdog of the sharded build, seconds")
     ap.add_argument("--keep-pmc", default="", help="driver: copy the counter CSVs of the passes into this directory")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well (see the module docstring)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the outputs of the last timed step to DIR/<name>.npy")
     ap.add_argument("--role", default="", choices=["", "driver", "worker", "pmc", "pmc_build"])
     ap.add_argument("--dump-index", default="", help="worker: serialise the headline index + parameters here")
     ap.add_argument("--index-dir", default="", help="pmc: directory written by --dump-index")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def host_threads():
@@ -124,6 +138,29 @@ DATASET_TEXT = {
     "tight": "clustered synthetic, round 1: 1000 unit centres + uniform noise of norm 1.0, normalised",
     "iid": "iid uniform(-1,1) normalised (bigvec.rs:59-65)",
 }
+
+DUMP_BYTES = 64_000_000  # --dump-outputs writes at most this much
+
+
+def dump_outputs(out_dir, ids, dist, lens, stats, status):
+    """the arrays one search_batch_device call handed its caller (host copies: u32 ids [nq, ef], f32 distances
+    [nq, ef], u32 lengths, i32 (distance evaluations, hops) per query, i32 status) as float64 / float32 .npy files.
+    Rows past a query's length hold the kernel's padding (PH_EMPTY32, FLT_MAX).  A batch larger than DUMP_BYTES is cut
+    to a fixed, seeded sample of its queries; rows.npy holds the query numbers written."""
+    nq, ef = ids.shape
+    per_query = ef * (8 + 4) + 8 * 5  # ids f64 + distances f32; length, 2 counters, status, row number as f64
+    keep = min(nq, (DUMP_BYTES - 4096) // per_query)  # 4096: the .npy headers
+    rows = np.arange(nq) if keep == nq else np.sort(np.random.default_rng(0).choice(nq, keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"rows": rows.astype(np.float64),
+              "ids": ids[rows].view(np.uint32).astype(np.float64),
+              "distances": np.ascontiguousarray(dist[rows], dtype=np.float32),
+              "lengths": lens[rows].view(np.uint32).astype(np.float64),
+              "stats": stats[rows].astype(np.float64),
+              "status": status[rows].astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 # --------------------------------------------------------------------------------------- worker
@@ -226,7 +263,7 @@ def worker(args):
         if world > 1:
             dist.barrier()
         runs = [round(build_s, 3)]
-        if world == 1 and kind == "survey" and not args.single_build:
+        if world == 1 and kind == "survey" and args.full and not args.single_build:
             # the same build once more (deterministic: the same graph): a box's first build has come out up to 25 %
             # slower than its second; both times are printed, the figure is the faster one
             first = index._layer(index.layer_count() - 1).neighbors.copy()
@@ -246,8 +283,9 @@ def worker(args):
         log("%s: index built in %.1f s (%.0f vectors/s), layers %s" % (kind, build_s, store.n / build_s, layers))
         log("  build runs %s s; device allocation inside them (hipMalloc + hipFree, host time): %s" % (runs, allocs))
         info = {"build_s": build_s, "build_runs_s": runs, "build_alloc": allocs, "build_mode": mode, "layers": layers,
-                "build_self_recall": round(index.stochastic_recall(), 5),  # the reference's own estimator, lib.rs:1463-1499
                 "build_distance_evals": b_dist, "build_hops": b_hops}
+        if args.full:
+            info["build_self_recall"] = round(index.stochastic_recall(), 5)  # the reference's own estimator, lib.rs:1463-1499
         return index, info
 
     def sharded_probe(store, index, emit):
@@ -403,8 +441,10 @@ def worker(args):
             waited = time.perf_counter() - t0
             torch.cuda.synchronize()
             return waited < 0.8e-3
-        lanes_ok = side_by_side(stream2)
-        log("second lane: phnsw_stream_create_beside; runs beside the first: %s" % lanes_ok)
+        lanes_ok = None
+        if args.full:
+            lanes_ok = side_by_side(stream2)
+            log("second lane: phnsw_stream_create_beside; runs beside the first: %s" % lanes_ok)
         lanes = [(run, stream), (run2, stream2)]
         torch.cuda.synchronize()
 
@@ -438,6 +478,23 @@ def worker(args):
         # runs under the tail of the launch before it (the last queries drawn run one per CU): the fixed 1.6 ms of a
         # launch is hidden by the caller, which no arrangement inside one launch achieved.
         elapsed = timed(lambda i: i & 1)
+        if args.dump_outputs and rank == 0:
+            r_ = lanes[(args.steps - 1) & 1][0]  # the lane of the last timed step
+            n_ = r_.q.n
+            names = dump_outputs(args.dump_outputs, r_.result_ids(ef).cpu().numpy(),
+                                 r_.d.view(-1)[: n_ * ef].view(n_, ef).cpu().numpy(), r_.len.cpu().numpy(),
+                                 r_.stats.cpu().numpy(), r_.status.cpu().numpy())
+            log("outputs of the last timed step written to %s: %s" % (args.dump_outputs, ", ".join(names)))
+        # lane 1 has run when at least two steps (warm-up or timed) have
+        rec2 = recall_at_10(run2.result_ids(ef), gt2) if max(args.warmup, args.steps) >= 2 else None
+        assert rec2 is None or int(run2.status.abs().sum()) == 0, "search reported per-query errors (second batch)"
+        del run2, qstore2, gt2
+        if not args.full:
+            rec = recall_at_10(run.result_ids(ef), gt)
+            assert int(run.status.abs().sum()) == 0, "search reported per-query errors"
+            res = dict(binfo, dataset=kind, ef=ef, upper=up, probe_depth=pd, recall_target_met=met, recall_at_10=round(rec, 4),
+                       recall_at_10_second_batch=None if rec2 is None else round(rec2, 4), elapsed=elapsed)
+            return res, store, index, qstore, run, sp, gt
         # ---- the same K steps on ONE stream (a step's period is then never shorter than its kernels): reported beside
         elapsed_one = timed(lambda i: 0)
         one_stream = {"ms_per_step": round(elapsed_one / args.steps * 1e3, 3),
@@ -445,9 +502,6 @@ def worker(args):
                       "how": "the same K steps over one batch on one stream, nothing overlapping"}
         log("two batches in flight: %.3f ms per step; one stream: %.3f ms per step" % (
             elapsed / args.steps * 1e3, elapsed_one / args.steps * 1e3))
-        rec2 = recall_at_10(run2.result_ids(ef), gt2)
-        assert int(run2.status.abs().sum()) == 0, "search reported per-query errors (second batch)"
-        del run2, qstore2, gt2
         # ---- per-launch kernel time from HIP events on the launch stream, dispatch by dispatch
         kms, disp = [], None
         for _ in range(min(args.steps, 10)):
@@ -529,7 +583,8 @@ def worker(args):
                    elapsed=elapsed, kernel_ms=float(np.mean(kms)), alg_bytes=alg_bytes, gathered_bytes=gathered_bytes,
                    n_table=n_table, search_ms=search_ms, table_ms=table_ms, n_dist_per_query=n_dist / args.nq,
                    n_hops_per_query=n_hops / args.nq, sweep=sweep, batch_sweep=batch_sweep, dispatches=dispatches,
-                   batch_100k=big, one_stream=one_stream, recall_at_10_second_batch=round(rec2, 4),
+                   batch_100k=big, one_stream=one_stream,
+                   recall_at_10_second_batch=None if rec2 is None else round(rec2, 4),
                    lanes_side_by_side=bool(lanes_ok),
                    build_roofline={"bound": "hbm", "distance_evals": binfo["build_distance_evals"], "hops": binfo["build_hops"],
                                    "evals_equivalent_bytes": build_bytes,
@@ -577,23 +632,23 @@ def worker(args):
     value = world * args.nq * args.steps / res["elapsed"]
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         cpu = cpu_baseline(args, log, ph, torch, store, index, qstore, run, sp, gt, recall_at_10, dev)
 
     pq = None
-    if rank == 0 and world == 1 and not args.no_pq and not args.ef:
+    if args.full and rank == 0 and world == 1 and not args.no_pq and not args.ef:
         pq = pq_cells(args, log, ph, torch, store, index, qstore, gt, recall_at_10, dev, stream)
 
     host_path = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         host_path = host_path_cells(args, log, ph, torch, index, qstore, run, sp)
 
     sharded_model = None
-    if rank == 0 and world == 1 and not args.no_sharded_build and not args.ef:
+    if args.full and rank == 0 and world == 1 and not args.no_sharded_build and not args.ef:
         sharded_model = sharded_build_model(args, log, ph, store, index, res["build_s"])
 
     extras = {}
-    if rank == 0 and world == 1 and not args.ef:
+    if args.full and rank == 0 and world == 1 and not args.ef:
         del run, gt, qstore, index, store
         torch.cuda.empty_cache()
         if not args.no_tight and args.dataset != "tight":
@@ -603,7 +658,39 @@ def worker(args):
         if not args.no_iid and args.dataset != "iid":
             extras["iid"] = secondary("iid", LITERAL)
 
-    if rank == 0:
+    if rank == 0 and not args.full:
+        line = {
+            "metric": "queries/sec at recall@10≥0.95 on 1M×768 f32",
+            "value": round(value, 1),
+            "unit": "queries/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(res["elapsed"] / args.steps * 1e3, 3),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "config": {
+                "workload": "configs[1]: %dx%d f32 cosine (1-dot)/2, batched greedy search, %d queries/step/GPU"
+                            % (args.n, args.dim, args.nq),
+                "dataset": DATASET_TEXT[res["dataset"]],
+                "number_of_candidates": res["ef"], "upper_layer_candidate_count": res["upper"],
+                "probe_depth": res["probe_depth"],
+                "parallelism": "replicated index, queries sharded x%d; per GPU the K steps keep TWO batches in flight: two query "
+                               "batches alternate, each on its own stream" % world,
+                "in_flight": 2,
+            },
+            "recall_at_10": res["recall_at_10"],
+            "recall_at_10_second_batch": res["recall_at_10_second_batch"],
+            "recall_target_met": res["recall_target_met"],
+            "build_runs_s": res["build_runs_s"],
+            "layers": res["layers"],
+            "queries_per_step_per_gpu": args.nq, "argv": " ".join(sys.argv[1:]),
+            "full": False,
+        }
+    elif rank == 0:
         ktime = res["kernel_ms"] * 1e-3
         line = {
             # BASELINE.json's metric, first clause (the second, index-build vectors/sec, is build_vectors_per_sec below)
@@ -695,6 +782,7 @@ def worker(args):
             "build_roofline": res["build_roofline"],
             "build_self_recall": res["build_self_recall"],
             "sweep": res["sweep"],
+            "full": True,
         }
         line.update(extras)
         if world > 1:
@@ -719,7 +807,7 @@ def worker(args):
                     line["all_gather"] = sharded["all_gather"]
             print(json.dumps(line), flush=True)
 
-    if world > 1 and not args.no_sharded_build:
+    if world > 1 and args.full and not args.no_sharded_build:
         emit(sharded_probe(store, index, emit))
     else:
         emit()
@@ -1208,6 +1296,9 @@ def passthrough(args):
         if isinstance(v, bool):
             if v:
                 out.append(flag)
+        elif k == "dump_outputs":
+            if v:
+                out += [flag, os.path.abspath(v)]
         else:
             out += [flag, str(v)]
     return out
@@ -1234,7 +1325,7 @@ def driver(args):
     try:
         env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
         cmd = [sys.executable, me, "--role", "worker"] + passthrough(args)
-        want_pmc = not args.no_pmc and shutil.which("rocprofv3") is not None
+        want_pmc = args.full and not args.no_pmc and shutil.which("rocprofv3") is not None
         if want_pmc:
             cmd += ["--dump-index", tmp]
         r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, text=True)
@@ -1242,6 +1333,9 @@ def driver(args):
         if r.returncode != 0 or not lines:
             sys.stdout.write(r.stdout)
             return r.returncode or 1
+        if not args.full:
+            print(lines[-1], flush=True)
+            return 0
         line = json.loads(lines[-1])
         roof = line["roofline"]
         if want_pmc:

@@ -1,7 +1,7 @@
 """profiles/r02/search_kernel_summary.json from
   <dir>/trace/**kernel_trace.csv + kernel_stats.csv   rocprofv3 --kernel-trace --stats -- python3 bench.py --role worker ...
   <dir>/bench_trace.json                              the JSON line that worker printed
-  <dir>/bench_full.json                               the JSON line of the plain `python bench.py` run (with PMC)
+  <dir>/bench_full.json                               the JSON line of the `python bench.py --full` run (with PMC)
 The worker's last `isolated` launches (one per HIP-event reading) are the unit; a launch of the headline batch is
 ph_tiny_prep_kernel + 2 x ph_tiny_pack_kernel + ph_tiny_table_mfma_kernel + ph_search_kernel (or prep + ph_tiny_table_kernel +
 search when the store is not one the matrix-core table takes)."""

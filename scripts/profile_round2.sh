@@ -6,11 +6,11 @@ OUT=$ROOT/gpurun_out/prof_r02
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # (a) kernel trace + stats of the measuring worker itself (headline only)
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o t -- python3 $ROOT/bench.py --role worker --steps 20 --skip-iid --skip-tight --skip-pq --cpu-seconds 0 > $OUT/bench_trace.json 2> $OUT/bench_trace.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o t -- python3 $ROOT/bench.py --role worker --full --steps 20 --skip-iid --skip-tight --skip-pq --cpu-seconds 0 > $OUT/bench_trace.json 2> $OUT/bench_trace.err
 echo "trace pass done"
-# (b) the plain run: driver + worker + its own two --pmc passes; counter CSVs kept
-python3 $ROOT/bench.py --keep-pmc $OUT/pmc > $OUT/bench_full.json 2> $OUT/bench_full.err
-echo "plain run done"
+# (b) the full run: driver + worker + its own two --pmc passes; counter CSVs kept
+python3 $ROOT/bench.py --full --keep-pmc $OUT/pmc > $OUT/bench_full.json 2> $OUT/bench_full.err
+echo "full run done"
 python3 $ROOT/scripts/make_profile_summary_r2.py $OUT $OUT/summary
 # (c) index construction alone (1M x 768, SURVEY clustered variant, single GPU): per-kernel totals
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/build -o b -- python3 $ROOT/scripts/probe_plain_build.py > $OUT/build.log 2>&1
