@@ -748,6 +748,33 @@ int ph_search_device(const phnsw_index *ix, const float *queries_dev, uint32_t l
     }
   }
 #endif
+#ifdef PH_VISITED_PROBE
+  {
+    static unsigned long long *vprobe_dev = nullptr;
+    if (!vprobe_dev) {
+      PH_HIP(hipMalloc(&vprobe_dev, 130 * sizeof(unsigned long long)));
+      PH_HIP(hipMemset(vprobe_dev, 0, 130 * sizeof(unsigned long long)));
+    } else {
+      unsigned long long h[130];
+      PH_HIP(hipDeviceSynchronize());
+      PH_HIP(hipMemcpy(h, vprobe_dev, sizeof(h), hipMemcpyDeviceToHost));
+      for (int k = 0; k < 2; k++) {
+        unsigned long long n = 0, sum = 0, run = 0;
+        for (int b = 0; b < 64; b++) n += h[64 * k + b], sum += h[64 * k + b] * (64ull * b + 32ull);
+        if (!n) continue;
+        fprintf(stderr, "[visited probe] %s: %llu walks, mean ~%.0f ids, past the LDS load limit: %.4f; ids < 64*(b+1) for",
+                k ? "bottom layer" : "upper gathered layers", n, (double)sum / (double)n, (double)h[128 + k] / (double)n);
+        for (int b = 0; b < 64; b++) {
+          run += h[64 * k + b];
+          if (h[64 * k + b]) fprintf(stderr, " b%d:%.4f", b, (double)run / (double)n);
+        }
+        fprintf(stderr, "\n");
+      }
+      PH_HIP(hipMemset(vprobe_dev, 0, 130 * sizeof(unsigned long long)));
+    }
+    a.vprobe_out = vprobe_dev;
+  }
+#endif
   rc = ph_search_begin(ws, stream);
   if (rc) return rc;
   // The dense top layers (tiny.hip) keep one table row per launch position; a query list longer

@@ -261,8 +261,9 @@ template <int NV, int U>
 __device__ __forceinline__ float batch_distances(const float *__restrict__ vecs, uint32_t ld, uint32_t nv4, int metric,
                                                  bool l2, const float4 (&qv)[NV], uint64_t mask, uint32_t vid,
                                                  uint32_t lane) {
-  // U rows in flight per wave: 4 for throughput (8 was measured: 183 VGPRs, 2 waves/SIMD, no faster on full
-  // batches); the latency kernels of small batches take 12 (one load round per hop instead of four)
+  // U rows in flight per wave: 4 for throughput, 8 (191 VGPRs, 2 waves/SIMD) where the queues of ef <= 256 leave the
+  // LDS visited table room in a third of the waves (search.hip; on its own, 8 rows were no faster on full batches);
+  // the latency kernels of small batches take 12 (one load round per hop instead of four)
   float myd = 0.f;
   const uint32_t m = __popcll(mask);
   if (m == 0) return myd;

@@ -245,6 +245,14 @@ struct PhSearchArgs {
   const uint32_t *probe_pos;
   unsigned long long *probe_out;  // [12]: evaluations within 0,1,2,4,...,256 ranks; [10] all; [11] queries
 #endif
+#ifdef PH_VISITED_PROBE
+  // experiment: ids visited per gathered layer walk, in buckets of 64 ([0, 64) upper layers, [64, 128) the
+  // bottom layer; the last bucket holds everything above); [128 + k]: walks that passed the LDS table's load limit
+  unsigned long long *vprobe_out;
+#endif
+  // visited set of the gathered layers in LDS (search.hip): a table of vis_slots NodeIds at word vis_off of the
+  // dynamic LDS, at most vis_limit of them live (the rest of the layer then runs on the bitmap); 0 slots = bitmap
+  uint32_t vis_slots, vis_limit, vis_off;
   const uint32_t *order;  // nullable: processing order (a permutation of 0..nq-1), see search.hip
   uint32_t seg;           // order != nullptr: positions per XCD segment
   uint32_t *out_hit;    // nullable: 1 when a Stored query found itself (stochastic_recall lib.rs:1492)
@@ -335,7 +343,9 @@ void ph_workspace_order_free(PhWorkspace &ws);                                  
 #define PH_TWO_LAUNCH_MIN 32768u  // batches at least this large descend in two launches
 int ph_workspace_ensure(const phnsw_index *ix, PhWorkspace &ws, uint32_t ef, uint32_t ovf_cap);
 void ph_workspace_free(PhWorkspace &ws);
-uint32_t ph_search_slots(uint32_t ef, uint32_t nv4, bool pq, size_t pq_lds, int pqr_m = 0);
+// resident waves of a search launch; grows: threshold_nn (the queue may double); vis_slots: the LDS visited table
+uint32_t ph_search_slots(uint32_t ef, uint32_t nv4, bool pq, size_t pq_lds, int pqr_m = 0, bool grows = false,
+                         uint32_t *vis_slots = nullptr);
 static inline PhDistArgs ph_dist_args(const phnsw_store *s) {
   PhDistArgs d;
   d.vecs = s->rows;

@@ -12,7 +12,8 @@
 //    (persistent grid, no tail of idle CUs);
 //  * the query vector lives in registers (NV float4 per lane); a candidate row is read as
 //    NV fully coalesced 1 KiB wave-loads (global_load_dwordx4), 4 rows in flight per wave
-//    (4 / 12 / 24 in the small-batch kernels), fma-accumulated per lane and reduced with an xor
+//    (8 at ef <= 256 and 768 dimensions, 4 / 12 / 24 in the small-batch kernels), fma-accumulated
+//    per lane and reduced with an xor
 //    butterfly -- this fixed order is the oracle's ORC_SUM_BLOCKED64, so results are bit-comparable;
 //  * the small top layers are not gathered at all: their distances come from a table built per
 //    launch on the matrix cores (tiny.hip) and the walk there runs in table ids, visited set in LDS;
@@ -27,8 +28,12 @@
 //    + an append-only spill list in HBM for entries that fell out of / never entered the
 //    queue.  All spilled entries are worse than every queue entry, so pop = first
 //    unexpanded queue entry, else the minimum unexpanded spill entry (rare, linear scan);
-//  * `visited` (HashSet) is a per-wave bitmap in HBM driven by returning atomicOr
-//    (test-and-set in one L2 round trip), cleared after each layer by walking queue+spill.
+//  * `visited` (HashSet) of a gathered layer is an open-addressed table of NodeIds in the wave's
+//    LDS (multiplicative hash, linear probing, test-and-insert = ds_cmpst), wiped after the layer
+//    with LDS stores.  A walk that would fill it past its load limit moves its ids into the
+//    per-wave bitmap in HBM and finishes the layer there: returning atomicOr (test-and-set in one
+//    L2 round trip), cleared afterwards by walking queue+spill.  PHNSW_VISITED=global: the bitmap
+//    throughout, as on the latency, threshold_nn big-queue, PQ and _instr kernels.
 //
 // Hand-written for CDNA4: wave64 ballots/readlane, LDS queue, no portability layer.
 #include <hip/hip_runtime.h>
@@ -36,6 +41,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #include "phnsw_internal.h"
 
@@ -68,6 +74,45 @@ template <bool BIG>
 __device__ __forceinline__ void queue_sync() {
   if constexpr (BIG) __threadfence();
   __syncthreads();
+}
+
+// The f32 throughput kernels whose walks can get an LDS visited table (vis_table_slots: what the CU's LDS leaves a
+// resident wave beside its queues, at least max(1024, 4 ef) slots): queues of 128 slots; of 256 except at <= 256
+// dimensions (16 waves per CU leave under 1024 slots); of 512 at 1536 dimensions (8 waves per CU).  Every other
+// kernel compiles none of the table code, which would only cost it registers (<8, DistF32<1,4>>: 125 -> 129 VGPRs,
+// 4 -> 3 waves per SIMD).  The one-wave-per-SIMD latency kernels (U = 0) measured 2 % slower with the table for
+// batches of 1, 64 and 1024 and keep the bitmap too.
+__host__ __device__ constexpr bool vis_lds_shape(int capc, int nv) {
+  return capc == 2 || (capc == 4 && nv != 1) || (capc == 8 && nv == 6);
+}
+template <int CAPC, class D>
+struct vis_lds_policy : std::false_type {};
+template <int CAPC, int NV, int U>
+struct vis_lds_policy<CAPC, DistF32<NV, U>> : std::integral_constant<bool, U != 0 && vis_lds_shape(CAPC, NV)> {};
+
+// The LDS visited set: slot of a NodeId (multiplicative hash, scaled to any table size)
+__device__ __forceinline__ uint32_t vis_slot(uint32_t id, uint32_t slots) {
+  return (uint32_t)(((uint64_t)(id * 0x9E3779B1u) * slots) >> 32);
+}
+
+// test-and-insert of one id per lane (valid lanes): true when the id was not in the table.  EMPTY = fresh,
+// equal = visited, anything else = the next slot; the loop runs until every lane has resolved.  The load limit
+// keeps the table from filling, so every probe sequence ends.
+__device__ __forceinline__ bool vis_insert(uint32_t *H, uint32_t slots, uint32_t id, bool valid) {
+  bool fresh = false, pending = valid;
+  uint32_t s = valid ? vis_slot(id, slots) : 0u;
+  while (__ballot(pending)) {
+    if (pending) {
+      const uint32_t old = atomicCAS(&H[s], PH_EMPTY32, id);
+      if (old == PH_EMPTY32 || old == id) {
+        fresh = old == PH_EMPTY32;
+        pending = false;
+      } else {
+        s = s + 1u == slots ? 0u : s + 1u;
+      }
+    }
+  }
+  return fresh;
 }
 
 template <int CAPC, class Dist, bool INSTR = false, bool BIG = false>
@@ -105,6 +150,10 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
   const uint32_t ovf_cap = DENSE_ONLY ? a.dense_ovf_cap : a.ovf_cap;
   uint32_t *const Qs = S;
   uint32_t *const ovf_s = INSTR ? a.ovf_s + (uint64_t)blockIdx.x * a.ovf_cap : nullptr;
+  // visited set of the gathered layers in LDS (vis_slots = 0: the bitmap in HBM); empty between layers
+  uint32_t *const H = smem + a.vis_off;
+  const uint32_t hslots = (BIG || INSTR || !vis_lds_policy<CAPC, Dist>::value) ? 0u : a.vis_slots;
+  for (uint32_t i = lane; i < hslots; i += 64) H[i] = PH_EMPTY32;
 
   // locality schedule: with an `order` the query list is cut into 8 consecutive segments, one
   // per XCD, so that the queries one L2 serves together are neighbours in `order`; a wave
@@ -225,6 +274,31 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
         L.neighbors = a.tiny_nbr + a.tiny_off[li];
       }
       const bool identity = L.vec2node == nullptr;
+      bool hv = hslots && !tl;  // this layer's visited set is the LDS table (until it would pass its load limit)
+      uint32_t hn = 0;          // ids in the table
+      // test-and-set of one id per valid lane in the layer's visited set: true when it was not in it.  A batch that
+      // could take the table past vis_limit first moves the table into the bitmap, where the layer then goes on.
+      auto visit = [&](uint32_t id, bool valid) -> bool {
+        if (hv && hn + (uint32_t)__popcll(__ballot(valid)) > a.vis_limit) {
+          for (uint32_t i = lane; i < hslots; i += 64) {
+            const uint32_t o = H[i];
+            if (o != PH_EMPTY32) {
+              atomicOr(&vis[o >> 5], 1u << (o & 31));
+              H[i] = PH_EMPTY32;
+            }
+          }
+          wait_vm0();
+          hv = false;
+        }
+        if (hv) {
+          const bool f = vis_insert(H, hslots, id, valid);
+          hn += (uint32_t)__popcll(__ballot(f));
+          return f;
+        }
+        if (!valid) return false;
+        const uint32_t bit = 1u << (id & 31);
+        return !(atomicOr(&vis[id >> 5], bit) & bit);
+      };
       // ---- closest_vectors: VectorId -> NodeId, queue = new(cap); merge_pairs  lib.rs:258-266
       uint32_t qlen;
       if (a.knn_mode) {
@@ -232,8 +306,8 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
         if (lane == 0) {
           Qid[0] = qnode;
           Qd[0] = 0.0f;
-          atomicOr(&vis[qnode >> 5], 1u << (qnode & 31));
         }
+        visit(qnode, lane == 0);
         qlen = 1;
       } else {
         bool miss = false;
@@ -259,12 +333,10 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
 #pragma unroll
         for (int c = 0; c < CAPC; c++) {
           uint32_t i = lane + 64u * c;
-          if (i < clen) {
-            uint32_t nid = Qid[i];
-            if (tl)
-              atomicOr(&Vl[nid >> 5], 1u << (nid & 31));
-            else
-              atomicOr(&vis[nid >> 5], 1u << (nid & 31));
+          if (tl) {
+            if (i < clen) atomicOr(&Vl[Qid[i] >> 5], 1u << (Qid[i] & 31));
+          } else if (64u * c < clen) {
+            visit(i < clen ? Qid[i] : 0u, i < clen);
           }
         }
         qlen = clen;
@@ -284,11 +356,12 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
 #pragma unroll
           for (int c = 0; c < (BIG ? (int)((qlen + 63u) >> 6) : CAPC); c++) {
             uint32_t i = lane + 64u * c;
+            uint32_t nid = 0;
             if (i < qlen) {
-              uint32_t nid = Qid[i] & IDM;
+              nid = Qid[i] & IDM;
               Qid[i] = nid;
-              atomicOr(&vis[nid >> 5], 1u << (nid & 31));
             }
+            if (64u * c < qlen) visit(nid, i < qlen);
           }
           queue_sync<BIG>();
         }
@@ -383,10 +456,13 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
         }
         PH_TICK(1)
         bool fresh = false;
-        if (nb < L.n_nodes) {
-          uint32_t bit = 1u << (nb & 31);
-          uint32_t old = tl ? atomicOr(&Vl[nb >> 5], bit) : atomicOr(&vis[nb >> 5], bit);
-          fresh = !(old & bit);
+        if (tl) {
+          if (nb < L.n_nodes) {
+            uint32_t bit = 1u << (nb & 31);
+            fresh = !(atomicOr(&Vl[nb >> 5], bit) & bit);
+          }
+        } else {
+          fresh = visit(nb, nb < L.n_nodes);
         }
         const uint64_t fm = __ballot(fresh);
         const uint32_t m = __popcll(fm);
@@ -605,9 +681,18 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
                tprof[3] * 0.01, tprof[4] * 0.01, tprof[5] * 0.01, tprof[6] * 0.01);
 #endif
 
-      // ---- clear this layer's visited bits (queue + spill hold every evaluated node)
+#ifdef PH_VISITED_PROBE
+      if (!tl && lane == 0) {  // every visited id is in the queue or the spill list
+        const uint32_t k = li == last_layer ? 1u : 0u;
+        atomicAdd(&a.vprobe_out[k * 64u + min((qlen + ovf_n) >> 6, 63u)], 1ull);
+        if (!hv && hslots) atomicAdd(&a.vprobe_out[128u + k], 1ull);
+      }
+#endif
+      // ---- clear this layer's visited set (queue + spill hold every evaluated node)
       if (tl) {
         for (uint32_t i = lane; i < tiny_words; i += 64) Vl[i] = 0u;
+      } else if (hv) {
+        for (uint32_t i = lane; i < hslots; i += 64) H[i] = PH_EMPTY32;
       } else {
 #pragma unroll
         for (int c = 0; c < (BIG ? (int)((qlen + 63u) >> 6) : CAPC); c++) {
@@ -623,6 +708,8 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
         }
       }
       wait_vm0();
+      hv = hslots && !tl;
+      hn = 0;
       if (a.knn_mode != 2) break;
       thr_last = Qd[qlen - 1];  // pq.last().1  lib.rs:948
       if (thr_last < a.threshold && qlen == ef) {  // pq.resize_capacity(capacity * 2)  lib.rs:949-951
@@ -754,6 +841,7 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
       // leave the slot clean for the next query: wipe the whole bitmap (rare path; a dense-only launch has none)
       if (!DENSE_ONLY)
         for (uint64_t w = lane; w < a.visited_words; w += 64) vis[w] = 0u;
+      for (uint32_t i = lane; i < hslots; i += 64) H[i] = PH_EMPTY32;
       wait_vm0();
       clen = 0;
     }
@@ -863,6 +951,17 @@ __global__ __launch_bounds__(64, 2) void ph_search_kernel_pqr(PhSearchArgs a) {
 typedef void (*ph_search_fn)(PhSearchArgs);
 
 static int pick_capc(uint32_t ef) { return ef <= 128 ? 2 : (ef <= 512 ? 8 : (ef <= 1024 ? 16 : 0)); }
+
+// PHNSW_VISITED=global: the visited sets of the gathered layers stay in the HBM bitmap (A/B runs, tests)
+static bool vis_lds_on() {
+  const char *e = getenv("PHNSW_VISITED");
+  return !(e && !strcmp(e, "global"));
+}
+// the f32 throughput kernel at 128 < ef <= 256 with the LDS visited set: queues of 256 slots instead of 512 leave a
+// wave room for the table (threshold_nn keeps 512: its queue may double past ef)
+static int pick_capc_f32(uint32_t ef, bool grows, int nv) {
+  return (!grows && ef > 128 && ef <= 256 && vis_lds_on() && vis_lds_shape(4, nv)) ? 4 : pick_capc(ef);
+}
 static int pick_capc_dense(uint32_t ef) { return ef <= 128 ? 2 : (ef <= 256 ? 4 : (ef <= 512 ? 8 : (ef <= 1024 ? 16 : 0))); }
 static int pick_nv(uint32_t nv4) { return nv4 <= 64 ? 1 : (nv4 <= 192 ? 3 : (nv4 <= 384 ? 6 : 0)); }
 
@@ -926,6 +1025,10 @@ static ph_search_fn pick_kernel(int capc, int nv) {
   if (capc == C && nv == 0)   \
     return ph_pq_global_tables() ? (ph_search_fn)ph_search_kernel<C, DistPQG> : (ph_search_fn)ph_search_kernel<C, DistPQ>;
   PH_K(2, 1) PH_K(2, 3) PH_K(2, 6)
+  // ef <= 256 at 768 dimensions (the headline): 8 rows in flight at 2 waves per SIMD, whose LDS share holds a visited
+  // table of 3 520 slots -- 1.04 M q/s against 1.01 M for 4 rows at 3 waves per SIMD with 1 792 slots
+  if (capc == 4 && nv == 3) return (ph_search_fn)ph_search_kernel<4, DistF32<3, 8>>;
+  PH_K(4, 6)
   PH_K(8, 1) PH_K(8, 3) PH_K(8, 6)
   PH_K(16, 1) PH_K(16, 3) PH_K(16, 6)
   PH_KQ(2) PH_KQ(8) PH_KQ(16)
@@ -937,8 +1040,39 @@ static ph_search_fn pick_kernel(int capc, int nv) {
 // pq_lds: bytes behind the queues -- the PQ lookup table, or the dense-top-layer table row + visited bits
 static size_t lds_bytes(int capc, size_t pq_lds) { return (size_t)(5 * capc * 64 + 64) * 4 + pq_lds; }
 
-uint32_t ph_search_slots(uint32_t ef, uint32_t nv4, bool pq, size_t pq_lds, int pqr_m) {
-  int capc = pick_capc(ef), nv = pq ? 0 : pick_nv(nv4);
+// a table of fewer slots than max(PH_VIS_SLOTS_MIN, 4 ef) sends most walks to the bitmap part-way: the move costs
+// more than the table saves (measured: 512 slots at ef 320-512 made those launches 7-9 % slower)
+#define PH_VIS_SLOTS_MIN 1024u
+#define PH_VIS_SLOTS_MAX 4096u
+
+// Slots of the LDS visited table of kernel fn, whose other LDS is `lds` bytes, at per_cu resident waves per CU: what
+// the CU's LDS holds beside them without costing a resident wave (0 = the bitmap in HBM).  PHNSW_VISITED_LDS_SLOTS=n
+// forces n slots (tests: a small table sends every walk to the bitmap part-way through a layer).
+static uint32_t vis_table_slots(ph_search_fn fn, size_t lds, int per_cu, size_t lds_cu, uint32_t ef) {
+  if (!vis_lds_on() || per_cu <= 0) return 0;
+  if (const char *e = getenv("PHNSW_VISITED_LDS_SLOTS")) {
+    const long n = atol(e);
+    if (n > 0) return lds + (size_t)n * 4u <= 64u * 1024u ? (uint32_t)n : 0u;
+  }
+  const size_t room = std::min<size_t>(lds_cu / (size_t)per_cu, 64u * 1024u);
+  if (room <= lds) return 0;
+  const uint32_t least = std::max<uint32_t>(PH_VIS_SLOTS_MIN, 4u * ef);
+  for (uint32_t n = std::min<uint32_t>(PH_VIS_SLOTS_MAX, (uint32_t)((room - lds) / 4u) & ~63u); n >= least; n -= 64u) {
+    int got = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&got, (const void *)fn, 64, lds + (size_t)n * 4u) == hipSuccess &&
+        got >= per_cu)
+      return n;
+  }
+  return 0;
+}
+
+// the kernels whose body runs the LDS visited set (vis_lds_policy)
+static bool vis_table_kernel(bool pq, int pqr_m, int capc, int nv) { return !pq && pqr_m == 0 && vis_lds_shape(capc, nv); }
+
+uint32_t ph_search_slots(uint32_t ef, uint32_t nv4, bool pq, size_t pq_lds, int pqr_m, bool grows, uint32_t *vis_slots) {
+  if (vis_slots) *vis_slots = 0;
+  const int nv = pq ? 0 : pick_nv(nv4);
+  int capc = (!pq && pqr_m == 0) ? pick_capc_f32(ef, grows, nv) : pick_capc(ef);
   if (!capc || (!pq && !nv)) return 0;
   ph_search_fn fn = pqr_m == -1 ? pick_kernel_pqs(capc, nv) : (pqr_m ? pick_kernel_pqr(capc, pqr_m) : pick_kernel(capc, nv));
   if (pqr_m == -2) fn = pick_kernel_lat(capc, nv);
@@ -965,6 +1099,11 @@ uint32_t ph_search_slots(uint32_t ef, uint32_t nv4, bool pq, size_t pq_lds, int 
     if (atoi(e) > 0) per_cu = atoi(e);
     if (getenv("PHNSW_VERBOSE")) fprintf(stderr, "[phnsw] search grid: %d waves per CU (forced), lds %zu\n", per_cu, lds);
   }
+  if (vis_slots && vis_table_kernel(pq, pqr_m, capc, nv))
+    *vis_slots = vis_table_slots(fn, lds, per_cu, prop.maxSharedMemoryPerMultiProcessor, ef);
+  if (vis_slots && getenv("PHNSW_VERBOSE"))
+    fprintf(stderr, "[phnsw] search grid: %d waves per CU, lds %zu + visited table %u slots (of %zu per CU)\n", per_cu, lds,
+            *vis_slots, (size_t)prop.maxSharedMemoryPerMultiProcessor);
   return (uint32_t)(per_cu * prop.multiProcessorCount);
 }
 
@@ -992,8 +1131,11 @@ int ph_workspace_ensure(const phnsw_index *ix, PhWorkspace &ws, uint32_t ef, uin
   uint64_t words = (max_nodes + 31) / 32 + 1;
   const int pqr = ix->store->codes16 ? -1 : pick_pqr(ix->store, pick_capc(ef));  // -1: shared-codebook store
   const bool pqg = ix->store->codes != nullptr && (ph_pq_global_tables() || pqr);  // (the register policy stages its table there)
-  uint32_t slots = ph_search_slots(ef, ix->store->ld / 4, ix->store->codes != nullptr,
-                                   pqg ? 0 : ph_pq_lds_bytes(ix->store), pqr);
+  // the grid of every kernel a launch at this ef may pick: threshold_nn keeps queues of 512 at ef <= 256
+  uint32_t slots = 0;
+  for (bool grows : {false, true})
+    slots = std::max(slots, ph_search_slots(ef, ix->store->ld / 4, ix->store->codes != nullptr,
+                                            pqg ? 0 : ph_pq_lds_bytes(ix->store), pqr, grows));
   if (slots == 0) {
     ph_set_error("unsupported search shape: ef=%u dim=%u (ef <= 1024, dim <= 1536; PQ table + queue <= 160 KB LDS)", ef,
                  ix->store->dim);
@@ -1086,6 +1228,7 @@ static int search_launch_dense(PhWorkspace &ws, PhSearchArgs &a, hipStream_t str
   a.dense_ovf = ws.dense_ovf;
   a.visited = ws.visited;  // never touched: the visited set of a dense layer is in LDS
   a.visited_words = 0;
+  a.vis_slots = a.vis_limit = a.vis_off = 0;
   a.ovf = ws.ovf;
   a.ovf_cap = ws.ovf_cap;
   a.counter = ws.counter;
@@ -1123,6 +1266,7 @@ int ph_search_launch_big(const phnsw_index *ix, PhSearchArgs &a, uint32_t grid, 
   a.pq_table_bytes = 0;
   a.seg = 0;
   a.order = nullptr;
+  a.vis_slots = a.vis_limit = a.vis_off = 0;
   PH_HIP(hipMemsetAsync(a.counter, 0, 512, stream));
   hipLaunchKernelGGL(fn, dim3(grid), dim3(64), lds, stream, a);
   PH_HIP(hipGetLastError());
@@ -1132,12 +1276,14 @@ int ph_search_launch_big(const phnsw_index *ix, PhSearchArgs &a, uint32_t grid, 
 int ph_search_launch(const phnsw_index *ix, PhWorkspace &ws, PhSearchArgs &a, hipStream_t stream, bool mark_end) {
   if (a.dense_only) return search_launch_dense(ws, a, stream);
   const bool pq = ix->store->codes != nullptr;
-  int capc = pick_capc(std::max(a.ef, a.cap_max)), nv = pq ? 0 : pick_nv(a.dist.nv4);
+  const uint32_t ef_max = std::max(a.ef, a.cap_max);
+  int capc = pick_capc(ef_max), nv = pq ? 0 : pick_nv(a.dist.nv4);
   const int pqr = ix->store->codes16 ? -1 : pick_pqr(ix->store, capc);
+  const int capc_f32 = (!pq && !pqr) ? pick_capc_f32(ef_max, a.knn_mode == 2, nv) : capc;  // the throughput kernel's
   a.pq_tables = ws.pq_tables;
   a.pq_table_bytes = (uint32_t)ph_pq_lds_bytes(ix->store);
   ph_search_fn fn = nullptr;
-  if (capc && (pq || nv)) fn = pqr == -1 ? pick_kernel_pqs(capc, nv) : (pqr ? pick_kernel_pqr(capc, pqr) : pick_kernel(capc, nv));
+  if (capc && (pq || nv)) fn = pqr == -1 ? pick_kernel_pqs(capc, nv) : (pqr ? pick_kernel_pqr(capc, pqr) : pick_kernel(capc_f32, nv));
   // small batches of f32 queries: the latency kernels, when the shape has one
   int lat = 0;
   if (!pq && !pqr && a.nq <= PH_LATENCY_MAX && !getenv("PHNSW_NO_LAT") && pick_kernel_lat(capc, nv)) {
@@ -1149,6 +1295,8 @@ int ph_search_launch(const phnsw_index *ix, PhWorkspace &ws, PhSearchArgs &a, hi
     if (a.tiny_layers && a.tiny_n > a.tiny_lds_nodes && !getenv("PHNSW_NO_LAT_LDS_ROW") &&
         lds_bytes(capc, (size_t)a.tiny_stride * 4u + (size_t)((a.tiny_n + 31u) / 32u + 1u) * 4u) <= (160u * 1024u) / 3u)
       a.tiny_lds_nodes = a.tiny_n;
+  } else {
+    capc = capc_f32;
   }
   const size_t pq_lds = pq ? ((pqr || ph_pq_global_tables()) ? 0 : ph_pq_lds_bytes(ix->store)) : ph_tiny_lds_bytes(a);
   if (a.out_index) {  // Hnsw::search_instrumented
@@ -1177,12 +1325,18 @@ int ph_search_launch(const phnsw_index *ix, PhWorkspace &ws, PhSearchArgs &a, hi
   a.ovf = ws.ovf;
   a.ovf_cap = ws.ovf_cap;
   a.counter = ws.counter;
-  uint32_t slots = std::min<uint32_t>(ph_search_slots(std::max(a.ef, a.cap_max), a.dist.nv4, pq, pq_lds, lat ? lat : pqr), ws.n_slots);
+  uint32_t vis_slots = 0;
+  uint32_t slots = std::min<uint32_t>(
+      ph_search_slots(ef_max, a.dist.nv4, pq, pq_lds, lat ? lat : pqr, a.knn_mode == 2, &vis_slots), ws.n_slots);
   uint32_t grid = (uint32_t)std::min<uint64_t>(slots, a.nq);
   if (grid == 0) return 0;
+  // the LDS visited table sits behind everything else the kernel keeps in LDS
+  a.vis_slots = vis_slots;
+  a.vis_limit = vis_slots - vis_slots / 4u;
+  a.vis_off = (uint32_t)(lds_bytes(capc, pq_lds) / 4u);
   PH_HIP(hipMemsetAsync(ws.counter, 0, 512, stream));
   a.seg = a.order ? (a.nq + 7u) / 8u : 0u;
-  hipLaunchKernelGGL(fn, dim3(grid), dim3(64), lds_bytes(capc, pq_lds), stream, a);
+  hipLaunchKernelGGL(fn, dim3(grid), dim3(64), lds_bytes(capc, pq_lds) + (size_t)vis_slots * 4u, stream, a);
   PH_HIP(hipGetLastError());
   if (mark_end) {
     PH_HIP(hipEventRecord(ws.ev1, stream));
