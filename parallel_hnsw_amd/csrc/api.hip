@@ -885,6 +885,35 @@ extern "C" int phnsw_search_batch_device(const phnsw_index *ix, const float *que
                           out_len_dev, out_stats_dev, status_dev, 0, 0, (hipStream_t)stream);
 } catch (...) { return ph_caught(); }
 
+// tests: the raw distance table of the last launch's dense top layers ([positions][stride] f32, the last chunk's) and
+// the staging depth G of the matrix-core kernel that made it (0: the vector-unit kernel).  out_host may be NULL.
+extern "C" int phnsw_debug_last_tiny_table(const phnsw_index *ix, float *out_host, uint64_t cap_floats, uint32_t *npos,
+                                           uint32_t *tn, uint32_t *stride, int *g) try {
+  if (!ix) return PHNSW_E_INVALID;
+  phnsw_index *mix = const_cast<phnsw_index *>(ix);
+  std::lock_guard<std::mutex> lock(mix->ws_mutex);
+  PhWorkspace &ws = mix->ws[mix->ws_last];
+  if (!ws.timed || !ws.d_tiny || !ws.tiny_d) {
+    ph_set_error("the last search on this index made no dense table");
+    return PHNSW_E_INVALID;
+  }
+  const uint64_t need = (uint64_t)ws.tiny_last_npos * ws.tiny_last_stride;
+  if (npos) *npos = ws.tiny_last_npos;
+  if (tn) *tn = ws.tiny_last_tn;
+  if (stride) *stride = ws.tiny_last_stride;
+  if (g) *g = ws.tiny_table_g;
+  if (out_host) {
+    if (cap_floats < need) {
+      ph_set_error("phnsw_debug_last_tiny_table: %llu floats needed", (unsigned long long)need);
+      return PHNSW_E_INVALID;
+    }
+    PH_HIP(hipSetDevice(ix->store->device));
+    PH_HIP(hipEventSynchronize(ws.ev1));
+    PH_HIP(hipMemcpy(out_host, ws.tiny_d, need * 4u, hipMemcpyDeviceToHost));
+  }
+  return 0;
+} catch (...) { return ph_caught(); }
+
 extern "C" int phnsw_debug_layer_pos(phnsw_index *ix, uint32_t lft, uint32_t *out_host) try {
   if (lft >= ix->layers.size() || !ix->layers[lft].pos) return PHNSW_E_INVALID;
   PH_HIP(hipMemcpy(out_host, ix->layers[lft].pos, (size_t)ix->layers[lft].n_nodes * 4, hipMemcpyDeviceToHost));

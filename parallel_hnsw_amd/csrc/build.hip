@@ -497,6 +497,7 @@ static uint32_t wave_grid(uint32_t n) {
 static int apply_proposals(PhLayerHost &L, const uint32_t *tgt, const float *d, uint32_t S, uint64_t *out_added) {
   uint32_t n = L.n_nodes;
   PhTimer tm(" apply_proposals(K5)", n);
+  L.links_epoch++;  // rows are rewritten in place: what a search workspace derived from them is void (tiny.hip)
   uint64_t nslots = (uint64_t)n * S;
   DevBuf<uint32_t> cnt, start, cursor, inc_src;
   DevBuf<float> inc_d;

@@ -47,6 +47,7 @@ struct PhLayerHost {
   uint32_t *nodes = nullptr;
   uint32_t *neighbors = nullptr;
   float *nbr_dist = nullptr;  // [n_nodes * W] distance of each occupant to the row owner (build only)
+  uint64_t links_epoch = 0;   // bumped whenever rows of `neighbors` are rewritten in place (build.hip: apply_proposals)
   uint32_t *vec2node = nullptr;
   bool identity = false;
   uint32_t *recall_q = nullptr;  // cached stochastic_recall_at sample (build.hip), recall_n entries
@@ -95,6 +96,24 @@ struct phnsw_store {
   int refcount = 1;
 };
 
+// identity of the inputs of ph_tiny_prep_kernel (the dense layers' node lists and neighbour rows) and of the node-side
+// ph_tiny_pack_kernel (the table layer's node list and the stored rows): pointers, sizes and the epochs that say
+// whether what they point at has been rewritten
+struct PhTinyPrepKey {
+  bool valid = false;
+  uint64_t nodes_epoch = 0;
+  uint32_t T = 0, tn = 0;
+  const void *nodes[PH_TINY_MAX_LAYERS] = {}, *nbrs[PH_TINY_MAX_LAYERS] = {}, *vec2node = nullptr;
+  uint32_t n[PH_TINY_MAX_LAYERS] = {}, W[PH_TINY_MAX_LAYERS] = {};
+  uint64_t links[PH_TINY_MAX_LAYERS] = {};
+};
+struct PhTinyPackKey {
+  bool valid = false;
+  uint64_t nodes_epoch = 0;
+  const void *vecs = nullptr, *tnodes = nullptr;
+  uint32_t ld = 0, tn = 0, nv = 0;
+};
+
 struct PhWorkspace {
   // per resident-wave search state: visited bitmap + overflow (frontier spill) list
   uint32_t *visited = nullptr;
@@ -123,6 +142,11 @@ struct PhWorkspace {
   size_t tiny_member_bytes = 0;
   float4 *tiny_pq = nullptr, *tiny_pn = nullptr;  // matrix-core operands: packed positions / nodes (tiny.hip)
   size_t tiny_pq_bytes = 0, tiny_pn_bytes = 0;
+  // what tiny_nbr / tiny_member and tiny_pn were made from: a launch whose key matches skips the kernels (tiny.hip)
+  PhTinyPrepKey tiny_prep_key;
+  PhTinyPackKey tiny_pack_key;
+  int tiny_table_g = 0;  // staging depth of the last matrix-core table kernel on this workspace (0: none ran)
+  uint32_t tiny_last_npos = 0, tiny_last_tn = 0, tiny_last_stride = 0;  // shape of the last per-launch table in tiny_d
   uint2 *dense_ovf = nullptr;  // spill lists of the dense-only launch: [its resident waves][table nodes]
   size_t dense_ovf_bytes = 0;
   uint32_t *ovf_s = nullptr;  // search_instrumented: index sums of the spilled entries, [n_slots][ovf_cap]
@@ -344,8 +368,9 @@ void ph_workspace_order_free(PhWorkspace &ws);                                  
 int ph_workspace_ensure(const phnsw_index *ix, PhWorkspace &ws, uint32_t ef, uint32_t ovf_cap);
 void ph_workspace_free(PhWorkspace &ws);
 // resident waves of a search launch; grows: threshold_nn (the queue may double); vis_slots: the LDS visited table
+size_t ph_tiny_beside_lds(const phnsw_index *ix, const PhSearchArgs &a);  // LDS of one table block that runs beside a search (0: none)
 uint32_t ph_search_slots(uint32_t ef, uint32_t nv4, bool pq, size_t pq_lds, int pqr_m = 0, bool grows = false,
-                         uint32_t *vis_slots = nullptr);
+                         uint32_t *vis_slots = nullptr, size_t hole = 0);
 static inline PhDistArgs ph_dist_args(const phnsw_store *s) {
   PhDistArgs d;
   d.vecs = s->rows;

@@ -1044,19 +1044,30 @@ static size_t lds_bytes(int capc, size_t pq_lds) { return (size_t)(5 * capc * 64
 // more than the table saves (measured: 512 slots at ef 320-512 made those launches 7-9 % slower)
 #define PH_VIS_SLOTS_MIN 1024u
 #define PH_VIS_SLOTS_MAX 4096u
+#define PH_LDS_GRANULE 1280u
 
 // Slots of the LDS visited table of kernel fn, whose other LDS is `lds` bytes, at per_cu resident waves per CU: what
 // the CU's LDS holds beside them without costing a resident wave (0 = the bitmap in HBM).  PHNSW_VISITED_LDS_SLOTS=n
 // forces n slots (tests: a small table sends every walk to the bitmap part-way through a layer).
-static uint32_t vis_table_slots(ph_search_fn fn, size_t lds, int per_cu, size_t lds_cu, uint32_t ef) {
+// `hole`: bytes of the CU's LDS the resident waves leave free together, for one block of the next launch's table kernel
+// (tiny.hip: the table pass of the other workspace's launch runs beside this kernel instead of waiting for its tail).
+// The table never shrinks below its floor for the hole's sake: a kernel that cannot afford both keeps its table.
+static uint32_t vis_table_slots(ph_search_fn fn, size_t lds, int per_cu, size_t lds_cu, uint32_t ef, size_t hole) {
   if (!vis_lds_on() || per_cu <= 0) return 0;
   if (const char *e = getenv("PHNSW_VISITED_LDS_SLOTS")) {
     const long n = atol(e);
     if (n > 0) return lds + (size_t)n * 4u <= 64u * 1024u ? (uint32_t)n : 0u;
   }
-  const size_t room = std::min<size_t>(lds_cu / (size_t)per_cu, 64u * 1024u);
-  if (room <= lds) return 0;
   const uint32_t least = std::max<uint32_t>(PH_VIS_SLOTS_MIN, 4u * ef);
+  size_t share = lds_cu / (size_t)per_cu;
+  if (hole) {
+    // gfx950 hands out LDS in blocks of 320 dwords: the hole and every wave's share are whole blocks
+    const size_t G = PH_LDS_GRANULE, hole_blocks = (hole + G - 1u) / G;
+    const size_t with_hole = lds_cu / G > hole_blocks ? (lds_cu / G - hole_blocks) / (size_t)per_cu * G : 0u;
+    if (with_hole >= lds + (size_t)least * 4u) share = with_hole;
+  }
+  const size_t room = std::min<size_t>(share, 64u * 1024u);
+  if (room <= lds) return 0;
   for (uint32_t n = std::min<uint32_t>(PH_VIS_SLOTS_MAX, (uint32_t)((room - lds) / 4u) & ~63u); n >= least; n -= 64u) {
     int got = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&got, (const void *)fn, 64, lds + (size_t)n * 4u) == hipSuccess &&
@@ -1069,7 +1080,8 @@ static uint32_t vis_table_slots(ph_search_fn fn, size_t lds, int per_cu, size_t 
 // the kernels whose body runs the LDS visited set (vis_lds_policy)
 static bool vis_table_kernel(bool pq, int pqr_m, int capc, int nv) { return !pq && pqr_m == 0 && vis_lds_shape(capc, nv); }
 
-uint32_t ph_search_slots(uint32_t ef, uint32_t nv4, bool pq, size_t pq_lds, int pqr_m, bool grows, uint32_t *vis_slots) {
+uint32_t ph_search_slots(uint32_t ef, uint32_t nv4, bool pq, size_t pq_lds, int pqr_m, bool grows, uint32_t *vis_slots,
+                         size_t hole) {
   if (vis_slots) *vis_slots = 0;
   const int nv = pq ? 0 : pick_nv(nv4);
   int capc = (!pq && pqr_m == 0) ? pick_capc_f32(ef, grows, nv) : pick_capc(ef);
@@ -1100,10 +1112,10 @@ uint32_t ph_search_slots(uint32_t ef, uint32_t nv4, bool pq, size_t pq_lds, int 
     if (getenv("PHNSW_VERBOSE")) fprintf(stderr, "[phnsw] search grid: %d waves per CU (forced), lds %zu\n", per_cu, lds);
   }
   if (vis_slots && vis_table_kernel(pq, pqr_m, capc, nv))
-    *vis_slots = vis_table_slots(fn, lds, per_cu, prop.maxSharedMemoryPerMultiProcessor, ef);
+    *vis_slots = vis_table_slots(fn, lds, per_cu, prop.maxSharedMemoryPerMultiProcessor, ef, hole);
   if (vis_slots && getenv("PHNSW_VERBOSE"))
-    fprintf(stderr, "[phnsw] search grid: %d waves per CU, lds %zu + visited table %u slots (of %zu per CU)\n", per_cu, lds,
-            *vis_slots, (size_t)prop.maxSharedMemoryPerMultiProcessor);
+    fprintf(stderr, "[phnsw] search grid: %d waves per CU, lds %zu + visited table %u slots (of %zu per CU, %zu left to a table block)\n",
+            per_cu, lds, *vis_slots, (size_t)prop.maxSharedMemoryPerMultiProcessor, hole);
   return (uint32_t)(per_cu * prop.multiProcessorCount);
 }
 
@@ -1326,8 +1338,12 @@ int ph_search_launch(const phnsw_index *ix, PhWorkspace &ws, PhSearchArgs &a, hi
   a.ovf_cap = ws.ovf_cap;
   a.counter = ws.counter;
   uint32_t vis_slots = 0;
+  // per_cu (hence the grid) comes from the kernel without its visited table, as before: the hole is not handed to
+  // one more search wave
   uint32_t slots = std::min<uint32_t>(
-      ph_search_slots(ef_max, a.dist.nv4, pq, pq_lds, lat ? lat : pqr, a.knn_mode == 2, &vis_slots), ws.n_slots);
+      ph_search_slots(ef_max, a.dist.nv4, pq, pq_lds, lat ? lat : pqr, a.knn_mode == 2, &vis_slots,
+                      lat ? 0 : ph_tiny_beside_lds(ix, a)),
+      ws.n_slots);
   uint32_t grid = (uint32_t)std::min<uint64_t>(slots, a.nq);
   if (grid == 0) return 0;
   // the LDS visited table sits behind everything else the kernel keeps in LDS

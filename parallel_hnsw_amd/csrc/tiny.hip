@@ -354,8 +354,14 @@ struct PhMfmaTile {
   }
 };
 
+//
+// G = 2 is the form of a launch that has the chip to itself.  G = 1 is the form that runs BESIDE the other workspace's
+// search kernel (ph_tiny_prepare): half the LDS (24 KiB at NV = 3, the hole the search waves of a CU leave together,
+// search.hip: vis_table_slots) and at most 128 registers, which is what two resident search waves of 192 leave of a
+// SIMD's 512.  The staging depth changes neither the order of the leaves nor anything inside one, so both forms give
+// the same bits.
 template <int NV, int G>
-__global__ __launch_bounds__(256) void ph_tiny_table_mfma_kernel(PhTinyMfmaArgs a) {
+__global__ __launch_bounds__(256, G == 1 ? 4 : 1) void ph_tiny_table_mfma_kernel(PhTinyMfmaArgs a) {
   extern __shared__ float4 sm4[];
   using Tile = PhMfmaTile<NV, G>;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
@@ -391,6 +397,8 @@ __global__ __launch_bounds__(256) void ph_tiny_table_mfma_kernel(PhTinyMfmaArgs 
 // ------------------------------------------------------------------ host side
 
 void ph_tiny_free(PhWorkspace &ws) {
+  ws.tiny_prep_key = PhTinyPrepKey();
+  ws.tiny_pack_key = PhTinyPackKey();
   if (ws.tiny_d) hipFree(ws.tiny_d);
   if (ws.tiny_nbr) hipFree(ws.tiny_nbr);
   if (ws.tiny_member) hipFree(ws.tiny_member);
@@ -407,6 +415,16 @@ void ph_tiny_free(PhWorkspace &ws) {
 static bool tiny_mfma_shape(int metric, uint32_t ld) {
   return metric != PHNSW_METRIC_L2 && (ld == 256u || ld == 768u || ld == 1536u) && !getenv("PHNSW_TINY_VALU");
 }
+
+// PHNSW_TABLE_BESIDE = 0: the table pass never runs beside a search kernel (G = 2 always, no hole in the search
+// kernel's LDS); 1: always the G = 1 form; auto (default): G = 1 when the index's other workspace has a launch in flight
+static int table_beside_mode() {
+  const char *e = getenv("PHNSW_TABLE_BESIDE");
+  if (!e || !strcmp(e, "auto")) return 2;
+  return atoi(e) > 0 ? 1 : 0;
+}
+static bool tiny_keep_off() { return getenv("PHNSW_NO_TINY_KEEP") != nullptr; }  // tests: prep and node pack every launch
+static size_t tiny_mfma_lds(int nv, int g) { return (size_t)2 * 4 * g * nv * 64 * sizeof(float4); }
 
 bool ph_tiny_matrix_cores(const phnsw_index *ix) { return tiny_mfma_shape(ix->store->metric, ix->store->ld); }
 
@@ -442,6 +460,15 @@ uint64_t ph_tiny_max_positions(const phnsw_index *ix, uint32_t n_layers, uint32_
   return std::max<uint64_t>(64, budget / ((uint64_t)tiny_stride_of(ix->layers[T - 1].n_nodes) * 4u));
 }
 
+// what a search launch leaves free of a CU's LDS: one block of the G = 1 table kernel, when the launches of this index
+// get their table from that kernel (per launch, on the matrix cores)
+size_t ph_tiny_beside_lds(const phnsw_index *ix, const PhSearchArgs &a) {
+  if (!a.tiny_layers || a.tiny_rows || !table_beside_mode()) return 0;
+  const uint32_t nv4 = a.dist.nv4;
+  if (!tiny_mfma_shape(ix->store->metric, nv4 * 4u)) return 0;
+  return tiny_mfma_lds((int)(nv4 / 64u), 1);
+}
+
 size_t ph_tiny_lds_bytes(const PhSearchArgs &a) {
   if (!a.tiny_layers) return 0;
   return (a.tiny_n <= a.tiny_lds_nodes ? (size_t)a.tiny_stride * 4u : 0u) + (size_t)((a.tiny_n + 31u) / 32u + 1u) * 4u;
@@ -458,25 +485,55 @@ static hipError_t grow(T **p, size_t *have, size_t need) {
   return e;
 }
 
-// the neighbour rows of the dense layers rewritten in table ids + the membership mask (per launch: the rows change
-// between build rounds)
-static int tiny_prep_graph(PhWorkspace &ws, PhSearchArgs &a, uint32_t T, uint32_t tn, hipStream_t stream) {
+static bool same_key(const PhTinyPrepKey &a, const PhTinyPrepKey &b) {
+  if (!a.valid || !b.valid || a.nodes_epoch != b.nodes_epoch || a.T != b.T || a.tn != b.tn || a.vec2node != b.vec2node) return false;
+  for (uint32_t l = 0; l < a.T; l++)
+    if (a.nodes[l] != b.nodes[l] || a.nbrs[l] != b.nbrs[l] || a.n[l] != b.n[l] || a.W[l] != b.W[l] || a.links[l] != b.links[l])
+      return false;
+  return true;
+}
+
+// the neighbour rows of the dense layers rewritten in table ids + the membership mask.  The rows change between build
+// rounds (links_epoch) and the lists with every promotion (nodes_epoch); between the searches of a finished index
+// neither does, and the workspace keeps what the last launch made (the launches of a workspace are ordered by
+// ph_search_begin, so the kept rows are complete before this launch's kernels read them)
+static int tiny_prep_graph(const phnsw_index *ix, PhWorkspace &ws, PhSearchArgs &a, uint32_t T, uint32_t tn, hipStream_t stream,
+                           bool *kept = nullptr) {
+  if (kept) *kept = false;
   PhTinyPrepArgs p;
   memset(&p, 0, sizeof(p));
   p.T = T;
   p.tiny_n = tn;
+  PhTinyPrepKey key;
+  key.valid = !tiny_keep_off();
+  key.nodes_epoch = ix->nodes_epoch;
+  key.T = T;
+  key.tn = tn;
+  key.vec2node = a.layers[T - 1].vec2node;
   size_t nbr_words = 0;
   for (uint32_t l = 0; l < T; l++) {
     p.layers[l] = a.layers[l];
     p.off[l] = (uint32_t)nbr_words;
     a.tiny_off[l] = (uint32_t)nbr_words;
     nbr_words += (size_t)tn * a.layers[l].W;
+    key.nodes[l] = a.layers[l].nodes;
+    key.nbrs[l] = a.layers[l].neighbors;
+    key.n[l] = a.layers[l].n_nodes;
+    key.W[l] = a.layers[l].W;
+    key.links[l] = ix->layers[l].links_epoch;
   }
+  const uint32_t *nbr_was = ws.tiny_nbr, *member_was = ws.tiny_member;
   if (grow(&ws.tiny_nbr, &ws.tiny_nbr_bytes, nbr_words * 4u) != hipSuccess ||
       grow(&ws.tiny_member, &ws.tiny_member_bytes, (size_t)(PH_TINY_MAX_NODES + 1u) * 4u) != hipSuccess) {
     (void)hipGetLastError();
+    ws.tiny_prep_key.valid = false;
     return 1;  // not an error: the launch walks every layer on the per-hop path
   }
+  if (ws.tiny_nbr == nbr_was && ws.tiny_member == member_was && same_key(key, ws.tiny_prep_key)) {
+    if (kept) *kept = true;
+    return 0;
+  }
+  ws.tiny_prep_key = key;
   p.nbr = ws.tiny_nbr;
   p.member = ws.tiny_member;
   PH_HIP(hipMemsetAsync(ws.tiny_nbr, 0xFF, nbr_words * 4u, stream));
@@ -489,9 +546,13 @@ static int tiny_prep_graph(PhWorkspace &ws, PhSearchArgs &a, uint32_t T, uint32_
 // D[p][t] = compare_vec(query of position p, Stored(tnodes[t])) for npos positions (position p = query order[p], or p
 // itself; raw queries or Stored ids), the per-hop path's bits: the matrix-core kernel where it applies, else the
 // vector-unit tile pass.  returns 1 (no error set) when its operand buffers cannot be allocated.
-static int tiny_table(PhWorkspace &ws, const PhDistArgs &dist, const float *queries, uint32_t ldq, const uint32_t *qids,
-                      const uint32_t *order, uint32_t npos, const uint32_t *tnodes, uint32_t tn, uint32_t stride, float *D,
-                      hipStream_t stream) {
+// g: staging depth of the matrix-core kernel, 1 = the form that fits beside a running search kernel.  The packed node
+// operand depends on the table layer's node list and the stored rows alone and is kept like the prepared graph.
+static int tiny_table(const phnsw_index *ix, PhWorkspace &ws, const PhDistArgs &dist, const float *queries, uint32_t ldq,
+                      const uint32_t *qids, const uint32_t *order, uint32_t npos, const uint32_t *tnodes, uint32_t tn,
+                      uint32_t stride, float *D, hipStream_t stream, int g = 2, bool *kept = nullptr) {
+  if (kept) *kept = false;
+  ws.tiny_table_g = 0;
   PhTinyTableArgs t;
   memset(&t, 0, sizeof(t));
   t.dist = dist;
@@ -514,11 +575,27 @@ static int tiny_table(PhWorkspace &ws, const PhDistArgs &dist, const float *quer
   if (mfma) {
     const uint32_t qtiles = (npos + 63u) / 64u, ntiles = (tn + 63u) / 64u;
     const size_t row_bytes = (size_t)nv * 64u * sizeof(float4);
+    const float4 *pn_was = ws.tiny_pn;
     if (grow(&ws.tiny_pq, &ws.tiny_pq_bytes, (size_t)qtiles * 64u * row_bytes) != hipSuccess ||
         grow(&ws.tiny_pn, &ws.tiny_pn_bytes, (size_t)ntiles * 64u * row_bytes) != hipSuccess) {
       (void)hipGetLastError();
+      ws.tiny_pack_key.valid = false;
       return 1;
     }
+    PhTinyPackKey key;
+    key.valid = !tiny_keep_off();
+    key.nodes_epoch = ix->nodes_epoch;
+    key.vecs = dist.vecs;
+    key.tnodes = tnodes;
+    key.ld = dist.ld;
+    key.tn = tn;
+    key.nv = (uint32_t)nv;
+    const PhTinyPackKey &have = ws.tiny_pack_key;
+    const bool pn_kept = ws.tiny_pn == pn_was && key.valid && have.valid && have.nodes_epoch == key.nodes_epoch &&
+                         have.vecs == key.vecs && have.tnodes == key.tnodes && have.ld == key.ld && have.tn == key.tn &&
+                         have.nv == key.nv;
+    ws.tiny_pack_key = key;
+    if (kept) *kept = pn_kept;
     PhTinyPackArgs k;
     memset(&k, 0, sizeof(k));
     k.vecs = dist.vecs;
@@ -538,7 +615,7 @@ static int tiny_table(PhWorkspace &ws, const PhDistArgs &dist, const float *quer
     k.n = tn;
     k.n_pad = ntiles * 64u;
     k.out = ws.tiny_pn;
-    hipLaunchKernelGGL(ph_tiny_pack_kernel, dim3(k.n_pad / 32u, 8u * (uint32_t)nv), dim3(32, 8), 0, stream, k);
+    if (!pn_kept) hipLaunchKernelGGL(ph_tiny_pack_kernel, dim3(k.n_pad / 32u, 8u * (uint32_t)nv), dim3(32, 8), 0, stream, k);
     PH_HIP(hipGetLastError());
     PhTinyMfmaArgs m;
     memset(&m, 0, sizeof(m));
@@ -553,15 +630,22 @@ static int tiny_table(PhWorkspace &ws, const PhDistArgs &dist, const float *quer
     m.D = D;
     const uint32_t supers = ((qtiles + 7u) / 8u) * ((ntiles + 7u) / 8u);
     const uint32_t blocks = (supers + 7u) / 8u * 8u * 64u;
-    constexpr int G = 2;
-    const size_t lds = (size_t)2 * 4 * G * nv * 64 * sizeof(float4);
-    if (nv == 1) {
-      hipLaunchKernelGGL((ph_tiny_table_mfma_kernel<1, G>), dim3(blocks), dim3(256), lds, stream, m);
+    const size_t lds = tiny_mfma_lds(nv, g == 1 ? 1 : 2);
+    ws.tiny_table_g = g == 1 ? 1 : 2;
+    if (g == 1) {
+      if (nv == 1)
+        hipLaunchKernelGGL((ph_tiny_table_mfma_kernel<1, 1>), dim3(blocks), dim3(256), lds, stream, m);
+      else if (nv == 3)
+        hipLaunchKernelGGL((ph_tiny_table_mfma_kernel<3, 1>), dim3(blocks), dim3(256), lds, stream, m);
+      else
+        hipLaunchKernelGGL((ph_tiny_table_mfma_kernel<6, 1>), dim3(blocks), dim3(256), lds, stream, m);
+    } else if (nv == 1) {
+      hipLaunchKernelGGL((ph_tiny_table_mfma_kernel<1, 2>), dim3(blocks), dim3(256), lds, stream, m);
     } else if (nv == 3) {
-      hipLaunchKernelGGL((ph_tiny_table_mfma_kernel<3, G>), dim3(blocks), dim3(256), lds, stream, m);
+      hipLaunchKernelGGL((ph_tiny_table_mfma_kernel<3, 2>), dim3(blocks), dim3(256), lds, stream, m);
     } else {
-      PH_HIP(hipFuncSetAttribute((const void *)ph_tiny_table_mfma_kernel<6, G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL((ph_tiny_table_mfma_kernel<6, G>), dim3(blocks), dim3(256), lds, stream, m);
+      PH_HIP(hipFuncSetAttribute((const void *)ph_tiny_table_mfma_kernel<6, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      hipLaunchKernelGGL((ph_tiny_table_mfma_kernel<6, 2>), dim3(blocks), dim3(256), lds, stream, m);
     }
   } else {
     const uint32_t qt = nv == 6 ? 4u : 8u;
@@ -596,10 +680,37 @@ int ph_tiny_prepare(const phnsw_index *ix, PhWorkspace &ws, PhSearchArgs &a, uin
     (void)hipGetLastError();
     return 0;
   }
-  int rc = tiny_prep_graph(ws, a, T, tn, stream);
+  // The form of the table kernel: a caller that keeps two batches in flight (the index's two workspaces, a stream
+  // each) finds the other workspace's search kernel running or queued when it launches -- its end event has not
+  // come -- and this launch's table pass, which wants the matrix cores the search kernel leaves idle, takes the
+  // form that fits on the CUs beside it.  A lone launch keeps the faster G = 2 form.  A query, never a wait.
+  const int mode = table_beside_mode();
+  bool beside = mode == 1;
+  if (mode == 2) {
+    const PhWorkspace &other = &ws == &ix->ws[0] ? ix->ws[1] : ix->ws[0];
+    if ((&ws == &ix->ws[0] || &ws == &ix->ws[1]) && other.timed && other.ev1) {
+      beside = hipEventQuery(other.ev1) == hipErrorNotReady;
+      (void)hipGetLastError();
+    }
+  }
+  bool prep_kept = false, pack_kept = false;
+  int rc = tiny_prep_graph(ix, ws, a, T, tn, stream, &prep_kept);
   if (rc) return rc < 0 ? rc : 0;
-  rc = tiny_table(ws, a.dist, a.queries, a.ldq, a.qids, a.order, npos, a.layers[T - 1].nodes, tn, stride, ws.tiny_d, stream);
+  rc = tiny_table(ix, ws, a.dist, a.queries, a.ldq, a.qids, a.order, npos, a.layers[T - 1].nodes, tn, stride, ws.tiny_d, stream,
+                  beside ? 1 : 2, &pack_kept);
   if (rc) return rc < 0 ? rc : 0;
+  if (getenv("PHNSW_VERBOSE")) {
+    if (ws.tiny_table_g)
+      fprintf(stderr, "[phnsw] dense table: %u positions x %u nodes on the matrix cores, G = %d (%s), graph %s, node operand %s\n",
+              npos, tn, ws.tiny_table_g, beside ? "beside the other workspace's launch" : "alone",
+              prep_kept ? "kept" : "prepared", pack_kept ? "kept" : "packed");
+    else
+      fprintf(stderr, "[phnsw] dense table: %u positions x %u nodes on the vector units, graph %s\n", npos, tn,
+              prep_kept ? "kept" : "prepared");
+  }
+  ws.tiny_last_npos = npos;
+  ws.tiny_last_tn = tn;
+  ws.tiny_last_stride = stride;
   a.tiny_layers = T;
   a.tiny_n = tn;
   a.tiny_lds_nodes = PH_TINY_LDS_NODES;
@@ -724,7 +835,7 @@ int ph_build_table_prepare(phnsw_index *ix, PhWorkspace &ws, PhSearchArgs &a, co
     const uint32_t PIECE = 131072u;  // bounds the packed-operand buffer (400 MB at 768 floats)
     for (uint32_t at = lo; at < hi; at += PIECE) {
       const uint32_t cnt = std::min(PIECE, hi - at);
-      int rc = tiny_table(ws, a.dist, nullptr, 0, h.qnodes + at, nullptr, cnt, tnodes, tn, stride,
+      int rc = tiny_table(ix, ws, a.dist, nullptr, 0, h.qnodes + at, nullptr, cnt, tnodes, tn, stride,
                           B.D + (size_t)(at - B.lo_alloc) * stride, stream);
       if (rc) return rc;
     }
@@ -745,7 +856,7 @@ int ph_build_table_prepare(phnsw_index *ix, PhWorkspace &ws, PhSearchArgs &a, co
     }
   }
   if (rc) return rc < 0 ? rc : 0;
-  rc = tiny_prep_graph(ws, a, T, tn, stream);
+  rc = tiny_prep_graph(ix, ws, a, T, tn, stream);
   if (rc) return rc < 0 ? rc : 0;
   a.tiny_layers = T;
   a.tiny_n = tn;
