@@ -468,6 +468,29 @@ int phnsw_pq_search_batch_device(const phnsw_index *ix, const phnsw_store *full,
                                  uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
                                  uint32_t *out_stats_dev, uint32_t *status_dev, void *stream);
 
+/* ---- half-precision row store (f16.hip) ----
+ * The rows of the f32 store `full`, rounded to IEEE binary16 (round to nearest even) by a device kernel: half the
+ * bytes per stored vector and per gathered candidate.  n, dim, metric and device are those of `full`; a component
+ * that is NaN or rounds to infinity in binary16 is PHNSW_E_INVALID.  A distance on the store widens the halves to f32
+ * (exact) and runs the f32 store's arithmetic, so every result equals, bit for bit, the f32 search over the widened
+ * rows -- which phnsw_store_read returns (phnsw_store_info reports rows_dev NULL).  The store is SEARCH-ONLY:
+ * phnsw_distance_batch, phnsw_index_from_layers (adopt a graph built over the f32 store), phnsw_search_batch,
+ * _stored, _topk, _device, phnsw_index_layer_*, the phnsw_last_search_* / phnsw_dense_top_layers queries and the
+ * destroy calls work on it and on an index over it; every other entry point returns PHNSW_E_UNSUPPORTED. */
+int phnsw_store_create_f16(const phnsw_store *full, phnsw_store **out);
+/* search the index over the f16 store with `sp`, recompute the distance of every returned id against the f32 store
+ * `full` (the bits of phnsw_distance_batch on it), sort by (distance, id), keep the best k <= number_of_candidates.
+ * out_ids / out_d are [nq][k], out_len[q] = min(results of query q, k). */
+int phnsw_f16_search_batch(const phnsw_index *ix, const phnsw_store *full, const float *queries, uint64_t nq,
+                           const phnsw_search_params *sp, uint64_t k, uint64_t *out_ids, float *out_d,
+                           uint64_t *out_len);
+/* zero-copy form: search, re-rank and cut enqueued on `stream`, u32 ids; rows keep the search's stride
+ * (number_of_candidates entries per query), the first out_len[q] <= k are live, the rest empty */
+int phnsw_f16_search_batch_device(const phnsw_index *ix, const phnsw_store *full, const float *queries_dev,
+                                  uint32_t ldq, uint64_t nq, const phnsw_search_params *sp, uint64_t k,
+                                  uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                  uint32_t *out_stats_dev, uint32_t *status_dev, void *stream);
+
 /* ---- on-disk interchange with the Rust crate: serialize_hnsw / deserialize_hnsw
  * (src/serialize.rs:33-209): <dir>/meta (JSON HNSWMeta), <dir>/comparator/ (this library's
  * store; a crate user substitutes their own Serializable comparator), layer.meta.N (JSON),

@@ -101,6 +101,13 @@ class Comparator {
         if (ids[q * k + j] != EMPTY) r[q].push_back({ids[q * k + j], d[q * k + j]});
     return r;
   }
+  // the same vectors as IEEE half rows (phnsw_store_create_f16): search-only -- adopt a graph built over this
+  // comparator with Hnsw::from_layers(half, layers) and re-rank with Hnsw::search_many_reranked(*this, ...)
+  phnsw_store *make_f16() const {
+    phnsw_store *h = nullptr;
+    check(phnsw_store_create_f16(s_, &h));
+    return h;  // wrap it: Comparator half(full.make_f16());
+  }
   uint32_t dim() const { return dim_; }
   uint64_t len() const { return n_; }
   phnsw_store *handle() const { return s_; }
@@ -185,6 +192,19 @@ class Hnsw {
   // Hnsw::search_upto(v, sp, upto_layer_from_top)  lib.rs:654-661 (0 = all layers)
   SearchResult search_upto(const AbstractVector &v, const SearchParameters &sp, uint32_t upto) const {
     return search_many({v}, sp, upto)[0];
+  }
+  // an index over an f16 comparator: search, recompute the results' distances on the f32 comparator `full`, sort by
+  // (distance, id), keep the best k  (phnsw_f16_search_batch); queries = nq * dim floats
+  std::vector<SearchResult> search_many_reranked(const Comparator &full, const std::vector<float> &queries,
+                                                 const SearchParameters &sp, uint64_t k) const {
+    const uint64_t nq = queries.size() / c_->dim();
+    std::vector<uint64_t> ids(nq * k), len(nq);
+    std::vector<float> d(nq * k);
+    check(phnsw_f16_search_batch(ix_, full.handle(), queries.data(), nq, &sp, k, ids.data(), d.data(), len.data()));
+    std::vector<SearchResult> out(nq);
+    for (uint64_t i = 0; i < nq; i++)
+      for (uint64_t j = 0; j < len[i]; j++) out[i].push_back({ids[i * k + j], d[i * k + j]});
+    return out;
   }
   // the batched form every GPU caller should use
   std::vector<SearchResult> search_many(const std::vector<AbstractVector> &vs, const SearchParameters &sp,

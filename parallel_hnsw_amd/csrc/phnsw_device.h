@@ -112,37 +112,69 @@ __device__ __forceinline__ void chain_partial2(const float4 (&x)[NV], const ph_f
   }
 }
 
-template <int NV, int U, bool EXACT, bool L2>
-__device__ __forceinline__ void rows_partial_impl(const float4 *const (&row)[U], const float4 (&q)[NV], uint32_t nv4,
-                                                  uint32_t lane, float (&acc)[U]) {
-  float4 x[U][NV];
+// How a stored row reaches the chain: a lane's chunk lane + 64k is four components -- 16 bytes of an f32 row, 8 bytes
+// of a half-precision row (f16 store).  Halves widen to f32 with v_cvt_f32_f16, which is exact (subnormals included:
+// the kernels run with f16 denormals on, the compiler's default), so the chain sees the f32 values a row of the
+// widened store would hold and everything behind the load is shared.  The raw chunks of all U rows are requested
+// before the first use and widened row by row: a half row in flight costs half the registers.
+struct RowF32 {
+  typedef float4 chunk;
+  static constexpr uint32_t ELT = 4;  // bytes per component
+  static __device__ __forceinline__ float4 widen(const float4 &v) { return v; }
+  static __device__ __forceinline__ const chunk *row(const PhDistArgs &d, uint32_t vid) {
+    return (const chunk *)(d.vecs + (uint64_t)vid * d.ld);
+  }
+};
+struct RowF16 {
+  typedef uint2 chunk;
+  static constexpr uint32_t ELT = 2;
+  static __device__ __forceinline__ const chunk *row(const PhDistArgs &d, uint32_t vid) {
+    return (const chunk *)(d.half + (uint64_t)vid * d.ldh);
+  }
+  static __device__ __forceinline__ float4 widen(const uint2 &v) {
+    return make_float4(__half2float(__ushort_as_half((unsigned short)(v.x & 0xFFFFu))),
+                       __half2float(__ushort_as_half((unsigned short)(v.x >> 16))),
+                       __half2float(__ushort_as_half((unsigned short)(v.y & 0xFFFFu))),
+                       __half2float(__ushort_as_half((unsigned short)(v.y >> 16))));
+  }
+};
+
+template <int NV, int U, bool EXACT, bool L2, class R>
+__device__ __forceinline__ void rows_partial_impl(const typename R::chunk *const (&row)[U], const float4 (&q)[NV],
+                                                  uint32_t nv4, uint32_t lane, float (&acc)[U]) {
+  typename R::chunk raw[U][NV];
 #pragma unroll
   for (int u = 0; u < U; u++) {
 #pragma unroll
     for (int k = 0; k < NV; k++) {
       uint32_t c = lane + 64u * k;
       if (!EXACT) c = c < nv4 ? c : nv4 - 1;
-      x[u][k] = row[u][c];
+      raw[u][k] = row[u][c];
     }
   }
 #pragma unroll
-  for (int u = 0; u < U; u++) acc[u] = chain_partial<NV, EXACT, L2>(x[u], q, nv4, lane);
+  for (int u = 0; u < U; u++) {
+    float4 x[NV];
+#pragma unroll
+    for (int k = 0; k < NV; k++) x[k] = R::widen(raw[u][k]);
+    acc[u] = chain_partial<NV, EXACT, L2>(x, q, nv4, lane);
+  }
 }
 
-template <int NV, int U>
-__device__ __forceinline__ void rows_partial(const float4 *const (&row)[U], const float4 (&q)[NV], uint32_t nv4,
+template <int NV, int U, class R = RowF32>
+__device__ __forceinline__ void rows_partial(const typename R::chunk *const (&row)[U], const float4 (&q)[NV], uint32_t nv4,
                                              uint32_t lane, bool l2, float (&acc)[U]) {
   const bool exact = nv4 == 64u * NV;  // wave-uniform
   if (exact) {
     if (l2)
-      rows_partial_impl<NV, U, true, true>(row, q, nv4, lane, acc);
+      rows_partial_impl<NV, U, true, true, R>(row, q, nv4, lane, acc);
     else
-      rows_partial_impl<NV, U, true, false>(row, q, nv4, lane, acc);
+      rows_partial_impl<NV, U, true, false, R>(row, q, nv4, lane, acc);
   } else {
     if (l2)
-      rows_partial_impl<NV, U, false, true>(row, q, nv4, lane, acc);
+      rows_partial_impl<NV, U, false, true, R>(row, q, nv4, lane, acc);
     else
-      rows_partial_impl<NV, U, false, false>(row, q, nv4, lane, acc);
+      rows_partial_impl<NV, U, false, false, R>(row, q, nv4, lane, acc);
   }
 }
 
@@ -151,14 +183,14 @@ __device__ __forceinline__ float row_partial(const float4 *__restrict__ row, con
                                              uint32_t lane, bool l2) {
   const float4 *const r[1] = {row};
   float acc[1];
-  rows_partial<NV, 1>(r, q, nv4, lane, l2, acc);
+  rows_partial<NV, 1, RowF32>(r, q, nv4, lane, l2, acc);
   return acc[0];
 }
 
 // distances of the query to the (up to 64) rows whose ids sit in the lanes flagged by
 // `mask`; 4 rows in flight; the result lands in the lane that held the id
-template <int NV, int U>
-__device__ __forceinline__ float batch_distances(const float *__restrict__ vecs, uint32_t ld, uint32_t nv4, int metric,
+template <int NV, int U, class R = RowF32>
+__device__ __forceinline__ float batch_distances(const void *__restrict__ vecs, uint32_t ld, uint32_t nv4, int metric,
                                                  bool l2, const float4 (&qv)[NV], uint64_t mask, uint32_t vid,
                                                  uint32_t lane);
 
@@ -223,19 +255,19 @@ __device__ __forceinline__ float wave_sum4(float p0, float p1, float p2, float p
 }
 
 // one round of batch_distances: candidates base .. base+U-1 (in lane order) of the compacted list
-template <int NV, int U>
-__device__ __forceinline__ void distance_round(const float *__restrict__ vecs, uint32_t nv4, int metric, bool l2,
+template <int NV, int U, class R>
+__device__ __forceinline__ void distance_round(const void *__restrict__ vecs, uint32_t nv4, int metric, bool l2,
                                                const float4 (&qv)[NV], uint32_t olo, uint32_t ohi, uint32_t m, uint32_t base,
                                                bool cand, uint32_t myrank, uint32_t lane, float &myd) {
-    const float4 *r[U];
+    const typename R::chunk *r[U];
 #pragma unroll
     for (int u = 0; u < U; u++) {
       const uint32_t k = min(base + (uint32_t)u, m - 1u);  // short tail: the last row again (same value, unused)
       const uint64_t o = ((uint64_t)rl32(ohi, (int)k) << 32) | rl32(olo, (int)k);
-      r[u] = (const float4 *)((const char *)vecs + o);
+      r[u] = (const typename R::chunk *)((const char *)vecs + o);
     }
     float p[U];
-    rows_partial<NV, U>(r, qv, nv4, lane, l2, p);
+    rows_partial<NV, U, R>(r, qv, nv4, lane, l2, p);
     const uint32_t mine = myrank - base;  // < U when this is the lane's round
     if constexpr (U % 4 == 0) {
       // row u of a group of four ends in lanes {0, 32, 16, 48}[u] + 0..15 (wave_sum4): every candidate lane
@@ -257,8 +289,8 @@ __device__ __forceinline__ void distance_round(const float *__restrict__ vecs, u
     }
 }
 
-template <int NV, int U>
-__device__ __forceinline__ float batch_distances(const float *__restrict__ vecs, uint32_t ld, uint32_t nv4, int metric,
+template <int NV, int U, class R>
+__device__ __forceinline__ float batch_distances(const void *__restrict__ vecs, uint32_t ld, uint32_t nv4, int metric,
                                                  bool l2, const float4 (&qv)[NV], uint64_t mask, uint32_t vid,
                                                  uint32_t lane) {
   // U rows in flight per wave: 4 for throughput, 8 (191 VGPRs, 2 waves/SIMD) where the queues of ef <= 256 leave the
@@ -272,7 +304,7 @@ __device__ __forceinline__ float batch_distances(const float *__restrict__ vecs,
   // address arithmetic of a row is one v_mad_u64_u32 per lane instead of scalar multiplies per row.
   const bool cand = (mask >> lane) & 1ull;
   const uint32_t myrank = __popcll(mask & lanemask_lt(lane));
-  const uint64_t off = (uint64_t)vid * ((uint64_t)ld * 4u);
+  const uint64_t off = (uint64_t)vid * ((uint64_t)ld * R::ELT);
   const int dst = (int)((cand ? myrank : 63u) << 2);  // non-candidates park in lane 63 (never read: m <= 63 there)
   uint32_t olo = (uint32_t)__builtin_amdgcn_ds_permute(dst, (int)(uint32_t)off);
   uint32_t ohi = (uint32_t)__builtin_amdgcn_ds_permute(dst, (int)(uint32_t)(off >> 32));
@@ -288,19 +320,19 @@ __device__ __forceinline__ float batch_distances(const float *__restrict__ vecs,
       const uint32_t left = m - base;
       constexpr int UBIG = NV <= 3 ? 24 : 12;  // 24 rows of 6 float4 per lane would not fit the register file
       if (left > 12u && UBIG > 12) {
-        distance_round<NV, UBIG>(vecs, nv4, metric, l2, qv, olo, ohi, m, base, cand, myrank, lane, myd);
+        distance_round<NV, UBIG, R>(vecs, nv4, metric, l2, qv, olo, ohi, m, base, cand, myrank, lane, myd);
         base += (uint32_t)UBIG;
       } else if (left > 4u) {
-        distance_round<NV, 12>(vecs, nv4, metric, l2, qv, olo, ohi, m, base, cand, myrank, lane, myd);
+        distance_round<NV, 12, R>(vecs, nv4, metric, l2, qv, olo, ohi, m, base, cand, myrank, lane, myd);
         base += 12u;
       } else {
-        distance_round<NV, 4>(vecs, nv4, metric, l2, qv, olo, ohi, m, base, cand, myrank, lane, myd);
+        distance_round<NV, 4, R>(vecs, nv4, metric, l2, qv, olo, ohi, m, base, cand, myrank, lane, myd);
         base += 4u;
       }
     }
   } else {
     for (uint32_t base = 0; base < m; base += U)
-      distance_round<NV, U>(vecs, nv4, metric, l2, qv, olo, ohi, m, base, cand, myrank, lane, myd);
+      distance_round<NV, U, R>(vecs, nv4, metric, l2, qv, olo, ohi, m, base, cand, myrank, lane, myd);
   }
   return myd;
 }
@@ -345,6 +377,34 @@ struct DistF32 {
   }
   __device__ __forceinline__ float batch(const PhDistArgs &d, uint64_t mask, uint32_t vid, uint32_t lane) const {
     return batch_distances<NV, U>(d.vecs, d.ld, d.nv4, d.metric, d.metric == PHNSW_METRIC_L2, qv, mask, vid, lane);
+  }
+};
+
+// DistF16<NV, U>: DistF32 over a half-precision row store.  The query stays f32 in registers; a stored query is its
+// widened row; a candidate's chunk is 8 bytes, widened in registers (RowF16).  Same chain, same butterfly, same
+// compaction: the bits are those of DistF32 on the store of widened rows.
+template <int NV, int U = 4>
+struct DistF16 {
+  static constexpr bool GLOBAL_TABLE = false;
+  static constexpr bool EARLY = false;
+  float4 qv[NV];
+  __device__ __forceinline__ void prepare_raw(const PhDistArgs &d, const float *q, float *, uint32_t lane) {
+#pragma unroll
+    for (int k = 0; k < NV; k++) {
+      uint32_t c = lane + 64u * k;
+      qv[k] = (c < d.nv4) ? ((const float4 *)q)[c] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+  __device__ __forceinline__ void prepare_stored(const PhDistArgs &d, uint32_t vid, float *, uint32_t lane) {
+    const uint2 *row = (const uint2 *)(d.half + (uint64_t)vid * d.ldh);
+#pragma unroll
+    for (int k = 0; k < NV; k++) {
+      uint32_t c = lane + 64u * k;
+      qv[k] = (c < d.nv4) ? RowF16::widen(row[c]) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+  __device__ __forceinline__ float batch(const PhDistArgs &d, uint64_t mask, uint32_t vid, uint32_t lane) const {
+    return batch_distances<NV, U, RowF16>(d.half, d.ldh, d.nv4, d.metric, d.metric == PHNSW_METRIC_L2, qv, mask, vid, lane);
   }
 };
 

@@ -70,6 +70,8 @@ struct PhDistArgs {
   const float *codebook;  // [m][ksub][dsub]
   uint32_t m, ksub, dsub;
   uint32_t table_f16;  // 1: the per-query table holds IEEE half values (2 bytes per entry)
+  const uint16_t *half;  // [n][ldh] IEEE binary16 rows in component order (f16 store, f16.hip); vecs == nullptr then
+  uint32_t ldh;          // halves per row (== ld: rows start on 8-byte boundaries)
 };
 
 struct phnsw_store {
@@ -85,6 +87,10 @@ struct phnsw_store {
   float *codebook = nullptr;
   uint32_t pq_m = 0, pq_ksub = 0, pq_dsub = 0;
   uint32_t pq_table_f16 = 0;
+  // half-precision store (phnsw_store_create_f16, f16.hip): rows == nullptr, half = [n][ldh] binary16 rows; a distance
+  // widens them to f32 (exact) and runs the f32 chain.  Search-only: see ph_f16_unsupported.
+  uint16_t *half = nullptr;
+  uint32_t ldh = 0;
   // coarse cells of the locality schedule (bruteforce.hip): anchor rows + their chain ranks
   float *anchors = nullptr;
   uint32_t *anchor_rank = nullptr;
@@ -329,10 +335,10 @@ int ph_search_device(const phnsw_index *ix, const float *queries_dev, uint32_t l
 // a layer whose vector rows do not fit one XCD's L2 (4 MiB) gets a launch of its own in a split
 // descent, its queries sorted by the cell they arrive in (PHNSW_SPLIT_BYTES overrides: tuning knob)
 #define PH_SPLIT_BYTES (4ull << 20)
-static inline bool ph_layer_own_launch(uint64_t n_nodes, uint32_t ld) {
+static inline bool ph_layer_own_launch(uint64_t n_nodes, uint32_t row_bytes) {
   const char *e = getenv("PHNSW_SPLIT_BYTES");  // read per call: the tests switch it
   const uint64_t limit = (e && atoll(e) > 0) ? (uint64_t)atoll(e) : (uint64_t)PH_SPLIT_BYTES;
-  return n_nodes * (uint64_t)ld * 4u > limit;
+  return n_nodes * (uint64_t)row_bytes > limit;
 }
 int ph_layer_anchor_pos(const phnsw_store *s, PhLayerHost &L);  // bruteforce.hip
 bool ph_layer_wants_cells(const phnsw_store *s, uint32_t n_nodes);
@@ -340,6 +346,11 @@ int ph_layer_cells_range(const phnsw_store *s, const PhLayerHost &L, uint32_t fi
 void ph_store_anchors_free(phnsw_store *s);
 int ph_order_by_keys_device(const uint32_t *keys, uint32_t n, uint32_t *order_out, hipStream_t st);
 int ph_layer_range_order(PhLayerHost &L, uint32_t first, uint32_t count, const uint32_t **out);
+
+// f16 store (f16.hip): rows of `ids_dev` (nullptr: rows first .. first + cnt) widened into [cnt][ld] f32 rows; a
+// range of the store widened into a dense host array
+int ph_f16_gather_rows(const phnsw_store *s, const uint32_t *ids_dev, uint32_t first, uint32_t cnt, float *out_dev);
+int ph_f16_store_read(const phnsw_store *s, uint64_t first, uint64_t count, float *out);
 
 // dense top layers (tiny.hip): decides how many leading layers of the launch described by `a` run
 // against a distance table, fills a.tiny_* and enqueues the table kernels for launch positions
@@ -384,7 +395,17 @@ static inline PhDistArgs ph_dist_args(const phnsw_store *s) {
   d.ksub = s->pq_ksub;
   d.dsub = s->pq_dsub;
   d.table_f16 = s->pq_table_f16;
+  d.half = s->half;
+  d.ldh = s->ldh;
   return d;
+}
+// bytes of one stored row as the search gathers it
+static inline uint32_t ph_row_bytes(const phnsw_store *s) { return s->half ? s->ldh * 2u : s->ld * 4u; }
+// an f16 store serves searches only: every other entry point refuses it by name
+static inline int ph_f16_unsupported(const phnsw_store *s, const char *call) {
+  if (!s || !s->half) return 0;
+  ph_set_error("%s: not supported on an f16 store or an index over one (search-only; use the f32 store)", call);
+  return PHNSW_E_UNSUPPORTED;
 }
 // the batched search keeps PQ tables in global memory unless PHNSW_PQ_TABLE=lds
 static inline bool ph_pq_global_tables() {

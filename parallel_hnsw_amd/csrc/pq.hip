@@ -216,6 +216,7 @@ static int pq_encode_sharded(const phnsw_comm *comm, uint64_t n, uint64_t row_by
 extern "C" int phnsw_store_create_pq_sharded(phnsw_store *full, uint32_t m, uint32_t ksub, uint64_t seed,
                                              uint32_t kmeans_iters, uint64_t sample, const phnsw_comm *comm,
                                              phnsw_store **out) try {
+  if (int rc = ph_f16_unsupported(full, "phnsw_store_create_pq")) return rc;
   if (!full || !out || full->codes || !full->rows || m == 0 || ksub == 0 || ksub > 256 || (m % 4) ||
       (full->dim % m) || ksub > full->n) {
     ph_set_error("phnsw_store_create_pq: need an f32 store, m %% 4 == 0, dim %% m == 0, 1 <= ksub <= min(256, n)");
@@ -373,6 +374,7 @@ extern "C" int phnsw_store_create_pq_shared_sharded(phnsw_store *full, uint32_t 
                                                     const phnsw_build_params *centroid_bp,
                                                     const phnsw_search_params *quantized_search, int centroid_metric,
                                                     const phnsw_comm *comm, phnsw_store **out) try {
+  if (int rc = ph_f16_unsupported(full, "phnsw_store_create_pq_shared")) return rc;
   if (!full || !out || !full->rows || !centroid_bp || !quantized_search || dsub == 0 || (dsub % 4) || (full->dim % dsub) ||
       full->ld != full->dim || n_centroids == 0 || n_centroids > 65535 || n_centroids > full->n ||
       quantized_search->number_of_candidates == 0 || quantized_search->number_of_candidates > 1024 ||
@@ -767,4 +769,146 @@ extern "C" int phnsw_pq_search_batch_device(const phnsw_index *ix, const phnsw_s
   }
   PH_HIP(hipGetLastError());
   return 0;
+} catch (...) { return ph_caught(); }
+
+// ------------------------------------------------------------------ f16 store: search + f32 re-rank
+//
+// The f16 index finds the candidates (distances of the widened half rows); the f32 store then gives every returned
+// id its full-precision distance (ph_pq_rerank_kernel: the bits of phnsw_distance_batch on `full`), the row is
+// sorted by (distance, id) and the best k are kept.
+
+// the sorted rows [nq][ef] cut to k entries each, in place: entries k .. ef - 1 become empty, len = min(len, k)
+__global__ void ph_f16_trim_kernel(uint32_t *ids, float *d, uint32_t *len, uint32_t ef, uint32_t k, uint64_t nq) {
+  const uint64_t total = nq * ef;
+  for (uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; x < total; x += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t r = x / ef;
+    const uint32_t c = (uint32_t)(x - r * ef);
+    if (c >= k) {
+      ids[x] = PH_EMPTY32;
+      d[x] = PH_FMAX;
+    }
+    if (c == 0) len[r] = min(len[r], k);
+  }
+}
+// ... and the leading k of each row as u64 ids + distances, [nq][k]
+__global__ void ph_f16_take_kernel(const uint32_t *ids, const float *d, uint32_t ef, uint32_t k, uint64_t nq, uint64_t *ids64,
+                                   float *dk) {
+  const uint64_t total = nq * k;
+  for (uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; x < total; x += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t r = x / k, c = x - r * k;
+    const uint32_t id = ids[r * ef + c];
+    ids64[x] = id == PH_EMPTY32 ? PHNSW_EMPTY : (uint64_t)id;
+    dk[x] = d[r * ef + c];
+  }
+}
+
+static int f16_rerank_check(const char *call, const phnsw_index *ix, const phnsw_store *full, const phnsw_search_params *sp,
+                            uint64_t nq, uint64_t k) {
+  if (!ix || !full || !sp || !ix->store->half || !full->rows || full->n != ix->store->n || full->dim != ix->store->dim ||
+      full->metric != ix->store->metric || full->device != ix->store->device || nq > 0xFFFFFFFFull ||
+      sp->number_of_candidates == 0 || sp->number_of_candidates > 1024 || sp->probe_depth == 0 || k == 0 ||
+      k > sp->number_of_candidates) {
+    ph_set_error("%s: need an index over an f16 store, the f32 store of the same n / dim / metric / device, valid "
+                 "parameters and 1 <= k <= number_of_candidates", call);
+    return PHNSW_E_INVALID;
+  }
+  return 0;
+}
+
+static int f16_rerank_launch(const phnsw_store *full, const float *queries_dev, uint32_t ldq, uint64_t nq, uint32_t ef,
+                             uint32_t k, uint32_t *len, uint32_t *ids, float *d, hipStream_t st) {
+  PhDistArgs fa = ph_dist_args(full);
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(nq, 256u * 16u);
+  const size_t lds = (size_t)ef * 16;
+  const uint32_t nv4 = full->ld / 4;
+  if (nv4 <= 64)
+    hipLaunchKernelGGL(ph_pq_rerank_kernel<1>, dim3(grid), dim3(64), lds, st, fa, queries_dev, ldq, (uint32_t)nq, ef, len, ids, d);
+  else if (nv4 <= 192)
+    hipLaunchKernelGGL(ph_pq_rerank_kernel<3>, dim3(grid), dim3(64), lds, st, fa, queries_dev, ldq, (uint32_t)nq, ef, len, ids, d);
+  else if (nv4 <= 384)
+    hipLaunchKernelGGL(ph_pq_rerank_kernel<6>, dim3(grid), dim3(64), lds, st, fa, queries_dev, ldq, (uint32_t)nq, ef, len, ids, d);
+  else {
+    ph_set_error("dim %u unsupported (max 1536)", full->dim);
+    return PHNSW_E_UNSUPPORTED;
+  }
+  PH_HIP(hipGetLastError());
+  if (k < ef) {
+    hipLaunchKernelGGL(ph_f16_trim_kernel, dim3((uint32_t)std::min<uint64_t>((nq * ef + 255) / 256, 4096)), dim3(256), 0, st, ids,
+                       d, len, ef, k, nq);
+    PH_HIP(hipGetLastError());
+  }
+  return 0;
+}
+
+// zero-copy form: the search launches, the re-rank and the cut to k enqueued on `stream`, no synchronisation.  The
+// result rows keep the search's stride (number_of_candidates entries per query): the first min(len, k) are live.
+extern "C" int phnsw_f16_search_batch_device(const phnsw_index *ix, const phnsw_store *full, const float *queries_dev,
+                                             uint32_t ldq, uint64_t nq, const phnsw_search_params *sp, uint64_t k,
+                                             uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                             uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) try {
+  PH_TRYQ(f16_rerank_check("phnsw_f16_search_batch_device", ix, full, sp, nq, k));
+  if (!queries_dev || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev || ldq < full->ld || (ldq % 4) ||
+      ((uintptr_t)queries_dev % 16)) {
+    ph_set_error("phnsw_f16_search_batch_device: invalid argument (queries need ldq >= store ld, multiple of 4, 16-byte base)");
+    return PHNSW_E_INVALID;
+  }
+  if (nq == 0) return 0;
+  PH_HIP(hipSetDevice(full->device));
+  PH_TRYQ(ph_search_device(ix, queries_dev, ldq, nullptr, nq, sp, 0, nullptr, out_ids_dev, out_d_dev, out_len_dev,
+                           out_stats_dev, status_dev, 0, 0, (hipStream_t)stream));
+  return f16_rerank_launch(full, queries_dev, ldq, nq, (uint32_t)sp->number_of_candidates, (uint32_t)k, out_len_dev,
+                           out_ids_dev, out_d_dev, (hipStream_t)stream);
+} catch (...) { return ph_caught(); }
+
+// host form: out_ids / out_d are [nq][k], out_len[q] = min(results of query q, k)
+extern "C" int phnsw_f16_search_batch(const phnsw_index *ix, const phnsw_store *full, const float *queries, uint64_t nq,
+                                      const phnsw_search_params *sp, uint64_t k, uint64_t *out_ids, float *out_d,
+                                      uint64_t *out_len) try {
+  PH_TRYQ(f16_rerank_check("phnsw_f16_search_batch", ix, full, sp, nq, k));
+  if ((!queries || !out_ids || !out_d || !out_len) && nq) {
+    ph_set_error("phnsw_f16_search_batch: queries and outputs must not be NULL");
+    return PHNSW_E_INVALID;
+  }
+  if (nq == 0) return 0;
+  PH_HIP(hipSetDevice(full->device));
+  const uint32_t ef = (uint32_t)sp->number_of_candidates;
+  float *qd = nullptr, *od = nullptr, *dk = nullptr;
+  uint32_t *oid = nullptr, *olen = nullptr, *ostat = nullptr;
+  uint64_t *ids64 = nullptr;
+  int rc = 0;
+  hipError_t e = hipMalloc(&qd, (size_t)nq * full->ld * 4);
+  if (e == hipSuccess && full->ld != full->dim) e = hipMemset(qd, 0, (size_t)nq * full->ld * 4);
+  if (e == hipSuccess)
+    e = hipMemcpy2D(qd, (size_t)full->ld * 4, queries, (size_t)full->dim * 4, (size_t)full->dim * 4, nq, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMalloc(&oid, (size_t)nq * ef * 4);
+  if (e == hipSuccess) e = hipMalloc(&od, (size_t)nq * ef * 4);
+  if (e == hipSuccess) e = hipMalloc(&olen, nq * 4);
+  if (e == hipSuccess) e = hipMalloc(&ostat, nq * 4);
+  if (e == hipSuccess) e = hipMalloc(&ids64, (size_t)nq * k * 8);
+  if (e == hipSuccess) e = hipMalloc(&dk, (size_t)nq * k * 4);
+  if (e != hipSuccess) rc = ph_hip_fail(e, "f16 search staging", __FILE__, __LINE__);
+  if (!rc) rc = ph_search_device(ix, qd, full->ld, nullptr, nq, sp, 0, nullptr, oid, od, olen, nullptr, ostat, 0, 0, 0);
+  if (!rc) rc = f16_rerank_launch(full, qd, full->ld, nq, ef, (uint32_t)k, olen, oid, od, 0);
+  if (!rc) {
+    hipLaunchKernelGGL(ph_f16_take_kernel, dim3((uint32_t)std::min<uint64_t>((nq * k + 255) / 256, 4096)), dim3(256), 0, 0, oid,
+                       od, ef, (uint32_t)k, nq, ids64, dk);
+    e = hipGetLastError();
+    std::vector<uint32_t> h_status(nq), h_len(nq);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(h_status.data(), ostat, nq * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(h_len.data(), olen, nq * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_ids, ids64, (size_t)nq * k * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_d, dk, (size_t)nq * k * 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = ph_hip_fail(e, "f16 search", __FILE__, __LINE__);
+    for (uint64_t i = 0; !rc && i < nq; i++) {
+      if (h_status[i]) {
+        ph_set_error("f16 search: query %llu failed with status %u", (unsigned long long)i, h_status[i]);
+        rc = h_status[i] == 4 ? PHNSW_E_MISSING_NODE : PHNSW_E_OVERFLOW;
+      }
+      out_len[i] = std::min<uint64_t>(h_len[i], k);
+    }
+  }
+  for (void *p : {(void *)qd, (void *)od, (void *)dk, (void *)oid, (void *)olen, (void *)ostat, (void *)ids64})
+    if (p) hipFree(p);
+  return rc;
 } catch (...) { return ph_caught(); }

@@ -157,7 +157,9 @@ __device__ __forceinline__ void tiny_tile(const float4 *lds, const ph_f2 (&qv)[Q
   if constexpr (QT == 4) V += __shfl_xor(V, 1);
 }
 
-template <int NV, int QT>
+// R: how the stored rows are read (RowF32, or RowF16: the halves of an f16 store widened as they are staged, so the
+// tile pass below sees the f32 operands it always saw)
+template <int NV, int QT, class R = RowF32>
 __global__ __launch_bounds__(256) void ph_tiny_table_kernel(PhTinyTableArgs a) {
   __shared__ float4 rows_lds[8 * NV * 64];
   const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
@@ -171,13 +173,17 @@ __global__ __launch_bounds__(256) void ph_tiny_table_kernel(PhTinyTableArgs a) {
     const bool valid = p < a.npos;
     const uint32_t q = valid ? (a.order ? a.order[p] : p) : 0u;
     const float4 *src = nullptr;
-    if (valid)
-      src = a.queries ? (const float4 *)(a.queries + (uint64_t)q * a.ldq)
-                      : (const float4 *)(a.dist.vecs + (uint64_t)a.qids[q] * a.dist.ld);
+    const typename R::chunk *srcs = nullptr;  // a stored query
+    if (valid) {
+      if (a.queries)
+        src = (const float4 *)(a.queries + (uint64_t)q * a.ldq);
+      else
+        srcs = R::row(a.dist, a.qids[q]);
+    }
 #pragma unroll
     for (int k = 0; k < NV; k++) {
       const uint32_t c = lane + 64u * k;
-      const float4 v = (valid && c < nv4) ? src[c] : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 v = (valid && c < nv4) ? (src ? src[c] : R::widen(srcs[c])) : make_float4(0.f, 0.f, 0.f, 0.f);
       qv[j / 2][k][0][j & 1] = v.x;
       qv[j / 2][k][1][j & 1] = v.y;
       qv[j / 2][k][2][j & 1] = v.z;
@@ -194,12 +200,12 @@ __global__ __launch_bounds__(256) void ph_tiny_table_kernel(PhTinyTableArgs a) {
     for (int u = 0; u < 2; u++) {
       const uint32_t slot = 2u * w + u;
       const uint32_t rr = min(r0 + slot, a.tiny_n - 1u);
-      const float4 *src = (const float4 *)(a.dist.vecs + (uint64_t)a.tnodes[rr] * a.dist.ld);
+      const typename R::chunk *src = R::row(a.dist, a.tnodes[rr]);
 #pragma unroll
       for (int k = 0; k < NV; k++) {
         uint32_t c = lane + 64u * k;
         c = c < nv4 ? c : nv4 - 1u;
-        rows_lds[(slot * NV + k) * 64 + lane] = src[c];
+        rows_lds[(slot * NV + k) * 64 + lane] = R::widen(src[c]);
       }
     }
     __syncthreads();
@@ -251,6 +257,7 @@ __host__ __device__ constexpr uint32_t ph_rev5(uint32_t t) {
 
 struct PhTinyPackArgs {
   const float *vecs;     // stored rows
+  const uint16_t *half;  // ... of an f16 store (vecs == nullptr): widened here, the packed operand is f32 either way
   uint32_t ld;
   const float *queries;  // raw query rows, or nullptr: rows are stored vectors
   uint32_t ldq;
@@ -268,9 +275,13 @@ __global__ void ph_tiny_pack_kernel(PhTinyPackArgs p) {
   float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
   if (r < p.n) {
     const uint32_t e = p.order ? p.order[r] : r;
-    const float4 *src = p.queries ? (const float4 *)(p.queries + (uint64_t)e * p.ldq)
-                                  : (const float4 *)(p.vecs + (uint64_t)p.ids[e] * p.ld);
-    v = src[c];
+    if (!p.queries && p.half) {
+      v = RowF16::widen(((const uint2 *)(p.half + (uint64_t)p.ids[e] * p.ld))[c]);
+    } else {
+      const float4 *src = p.queries ? (const float4 *)(p.queries + (uint64_t)e * p.ldq)
+                                    : (const float4 *)(p.vecs + (uint64_t)p.ids[e] * p.ld);
+      v = src[c];
+    }
   }
   const uint32_t t = ph_rev5(c & 31u), b = (c >> 5) & 1u, k = c >> 6;
   p.out[(((((uint64_t)(r >> 5) * 32u + t) * p.nv + k) * 2u + b) << 5) + (r & 31u)] = v;
@@ -437,7 +448,7 @@ bool ph_tiny_matrix_cores(const phnsw_index *ix) { return tiny_mfma_shape(ix->st
 // ef 300) it is tabulated either way.  PHNSW_TINY_MAX overrides.
 uint32_t ph_tiny_layer_count(const phnsw_index *ix, uint32_t n_layers, uint32_t ef) {
   const bool off = getenv("PHNSW_NO_TINY") != nullptr;  // tests compare both paths
-  if (off || !ix->store->rows || ix->store->ld / 4 > 384) return 0;
+  if (off || (!ix->store->rows && !ix->store->half) || ix->store->ld / 4 > 384) return 0;
   const uint64_t per_ef = tiny_mfma_shape(ix->store->metric, ix->store->ld) ? 80ull : 48ull;
   uint64_t cap = std::min<uint64_t>(PH_TINY_MAX_NODES, per_ef * ef);
   if (const char *e = getenv("PHNSW_TINY_MAX"))
@@ -585,7 +596,7 @@ static int tiny_table(const phnsw_index *ix, PhWorkspace &ws, const PhDistArgs &
     PhTinyPackKey key;
     key.valid = !tiny_keep_off();
     key.nodes_epoch = ix->nodes_epoch;
-    key.vecs = dist.vecs;
+    key.vecs = dist.half ? (const void *)dist.half : (const void *)dist.vecs;
     key.tnodes = tnodes;
     key.ld = dist.ld;
     key.tn = tn;
@@ -599,6 +610,7 @@ static int tiny_table(const phnsw_index *ix, PhWorkspace &ws, const PhDistArgs &
     PhTinyPackArgs k;
     memset(&k, 0, sizeof(k));
     k.vecs = dist.vecs;
+    k.half = dist.half;
     k.ld = dist.ld;
     k.nv = (uint32_t)nv;
     k.queries = queries;
@@ -655,7 +667,14 @@ static int tiny_table(const phnsw_index *ix, PhWorkspace &ws, const PhDistArgs &
     t.rows_per_slice = (tiles + slices - 1u) / slices * 8u;
     slices = (tn + t.rows_per_slice - 1u) / t.rows_per_slice;
     dim3 grid(gx, slices);
-    if (nv == 1)
+    if (dist.half) {
+      if (nv == 1)
+        hipLaunchKernelGGL((ph_tiny_table_kernel<1, 8, RowF16>), grid, dim3(256), 0, stream, t);
+      else if (nv == 3)
+        hipLaunchKernelGGL((ph_tiny_table_kernel<3, 8, RowF16>), grid, dim3(256), 0, stream, t);
+      else
+        hipLaunchKernelGGL((ph_tiny_table_kernel<6, 4, RowF16>), grid, dim3(256), 0, stream, t);
+    } else if (nv == 1)
       hipLaunchKernelGGL((ph_tiny_table_kernel<1, 8>), grid, dim3(256), 0, stream, t);
     else if (nv == 3)
       hipLaunchKernelGGL((ph_tiny_table_kernel<3, 8>), grid, dim3(256), 0, stream, t);

@@ -217,6 +217,22 @@ class PqStore(VectorStore):
         return out
 
 
+class F16Store(VectorStore):
+    """half-precision view of an f32 VectorStore (phnsw_store_create_f16): the rows rounded to IEEE binary16, half the
+    bytes per vector.  Distances widen the halves and run the f32 arithmetic, so read() returns exactly the rows the
+    searches see.  Search-only: adopt a graph built over the f32 store with Hnsw.from_layers(f16_store, ...)"""
+
+    def __init__(self, full):
+        h = C.c_void_p()
+        check(lib().phnsw_store_create_f16(full._h, C.byref(h)))
+        VectorStore.__init__(self, _handle=h, device=full.device)
+        self.full = full
+
+    @classmethod
+    def from_full(cls, store):
+        return cls(store)
+
+
 class SharedPqStore(VectorStore):
     """the reference's quantizer shape (pq.rs:19-27, 61-81, 261-285): ONE codebook of up to 65535 centroid
     sub-vectors shared by all sub-spaces, u16 codes, quantize = top-1 of an HNSW search over the centroids"""
@@ -540,6 +556,27 @@ class Hnsw:
             check(lib().phnsw_search_batch_stored(self._h, _p(qi), nq, C.byref(sp), upto, _p(ex), _p(ids), _p(d),
                                                   _p(ln), _p(st)))
         return (ids, d, ln, st) if stats else (ids, d, ln)
+
+    def search_batch_reranked(self, full, queries, sp=None, k=10):
+        """an index over an F16Store: search it, recompute every result's distance on the f32 store `full`, sort by
+        (distance, id), keep the best k (phnsw_f16_search_batch) -> ids[nq, k] u64, d[nq, k] f32, len[nq]"""
+        sp = sp or SearchParameters()
+        q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+        assert q.shape[1] == self.store.dim
+        nq, k = q.shape[0], int(k)
+        ids = np.empty((nq, k), dtype=np.uint64)
+        d = np.empty((nq, k), dtype=np.float32)
+        ln = np.zeros(nq, dtype=np.uint64)
+        check(lib().phnsw_f16_search_batch(self._h, full._h, _p(q), nq, C.byref(sp), k, _p(ids), _p(d), _p(ln)))
+        return ids, d, ln
+
+    def search_batch_reranked_device(self, full, nq, sp, k, queries, ldq, out_ids, out_d, out_len, status, out_stats=0,
+                                     stream=0):
+        """zero-copy form of search_batch_reranked (device pointers as ints, u32 ids, rows of number_of_candidates)"""
+        check(lib().phnsw_f16_search_batch_device(self._h, full._h, C.c_void_p(queries), ldq, nq, C.byref(sp), int(k),
+                                                  C.c_void_p(out_ids), C.c_void_p(out_d), C.c_void_p(out_len),
+                                                  C.c_void_p(out_stats or None), C.c_void_p(status),
+                                                  C.c_void_p(stream or None)))
 
     def search_instrumented_batch(self, queries=None, qids=None, sp=None):
         """Hnsw::search_instrumented (lib.rs:667-673) for many queries -> ids, d, len, index_distance[nq] u64"""

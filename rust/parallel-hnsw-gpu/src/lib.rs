@@ -89,6 +89,15 @@ impl GpuComparator {
         GpuComparator { host: data, store: Arc::new(StoreHandle(s)) }
     }
 
+    /// The same vectors with their HBM rows rounded to IEEE half floats (`phnsw_store_create_f16`): half the bytes per
+    /// gathered candidate.  Search-only -- adopt a graph built over the f32 comparator with `GpuHnsw::from_layers`
+    /// and re-rank with `GpuHnsw::search_many_reranked`.  The host copy (and `compare_raw`) stays f32.
+    pub fn to_f16(&self) -> Self {
+        let mut s = std::ptr::null_mut();
+        check(unsafe { sys::phnsw_store_create_f16(self.store.0, &mut s) });
+        GpuComparator { host: self.host.clone(), store: Arc::new(StoreHandle(s)) }
+    }
+
     /// `compare_vec(v, Stored(id))` for a whole candidate list in one launch (lib.rs:69-73)
     pub fn compare_batch(&self, v: AbstractVector<Vec<f32>>, ids: &[VectorId]) -> Vec<f32> {
         let raw: Vec<u64> = ids.iter().map(|i| i.0 as u64).collect();
@@ -325,6 +334,24 @@ impl GpuHnsw {
         check(unsafe {
             sys::phnsw_search_batch_topk(self.ix, q.as_ptr(), std::ptr::null(), nq as u64, &psp, 0, std::ptr::null(), k as u64,
                                          ids.as_mut_ptr(), d.as_mut_ptr(), len.as_mut_ptr())
+        });
+        (0..nq).map(|i| (0..len[i] as usize).map(|j| (VectorId(ids[i * k + j] as usize), d[i * k + j])).collect()).collect()
+    }
+
+    /// an index over a `to_f16()` comparator: search it, recompute every result's distance on the f32 comparator
+    /// `full`, sort by (distance, id), keep the best `k` (`phnsw_f16_search_batch`)
+    pub fn search_many_reranked(&self, full: &GpuComparator, queries: &[Vec<f32>], sp: SearchParameters, k: usize)
+                                -> Vec<Vec<(VectorId, f32)>> {
+        let nq = queries.len();
+        let psp = sp_c(sp);
+        let mut q: Vec<f32> = Vec::with_capacity(nq * queries.first().map_or(0, |x| x.len()));
+        for x in queries {
+            q.extend_from_slice(x);
+        }
+        let (mut ids, mut d, mut len) = (vec![0u64; nq * k], vec![0f32; nq * k], vec![0u64; nq]);
+        check(unsafe {
+            sys::phnsw_f16_search_batch(self.ix, full.store.0, q.as_ptr(), nq as u64, &psp, k as u64, ids.as_mut_ptr(),
+                                        d.as_mut_ptr(), len.as_mut_ptr())
         });
         (0..nq).map(|i| (0..len[i] as usize).map(|j| (VectorId(ids[i * k + j] as usize), d[i * k + j])).collect()).collect()
     }
