@@ -520,7 +520,10 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
         const bool full = qlen == ef;
         const float dtail = full ? Qd[ef - 1] : PH_FMAX;
         const uint64_t tailkey = full ? mkkey(dtail, Qid[ef - 1]) : KEY_NONE;
-        const bool ins = fresh && key < tailkey;
+        // a distance above f32::MAX (an L2 sum that overflowed to +inf) never enters `candidates`: insert's and merge's
+        // partition point lies past the f32::MAX fill of the empty slots (priority_queue.rs:102-107, 132-135); the
+        // visit_queue still holds it (lib.rs:211-220), so it goes to the spill list like an entry past a full queue
+        const bool ins = fresh && key < tailkey && myd <= PH_FMAX;
         const uint64_t im = __ballot(ins);
         uint32_t pos = 0, pos_min = 0xFFFFFFFFu, newpos = 0xFFFFFFFFu;
         // merge()'s return value (priority_queue.rs:109-144), closed form for a sorted,
@@ -655,7 +658,7 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
           if constexpr (INSTR)  // current_best != candidates.first(): a new entry took slot 0  lib.rs:225-231
             if (__ballot(fresh && newpos == 0u)) highest = cur_s;
         }
-        qlen = min(ef, qlen + m);
+        qlen = min(ef, qlen + (uint32_t)__popcll(im));  // every entering element of a queue that is not full; a full one stays full
         scan_from = min(pop >= 0 ? (uint32_t)pop + 1u : scan_from, pos_min);
         queue_sync<BIG>();
         PH_TICK(4)
