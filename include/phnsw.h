@@ -491,6 +491,31 @@ int phnsw_f16_search_batch_device(const phnsw_index *ix, const phnsw_store *full
                                   uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
                                   uint32_t *out_stats_dev, uint32_t *status_dev, void *stream);
 
+/* ---- int8 row store (i8.hip) ----
+ * The rows of the f32 store `full`, scalar-quantised per row and symmetrically by a device kernel:
+ *   scale = maxabs(row) / 127.0f,  code_j = (int8) clamp(rintf(x_j / scale), -127, 127)   (IEEE f32 divisions),
+ * a scale of 0 (a row of zeros, or a maxabs whose quotient underflows) gives codes 0.  A stored row is its f32 scale
+ * and its code bytes: a quarter of the bytes per stored vector and per gathered candidate.  n, dim, metric and device
+ * are those of `full`; a NaN or infinite component is PHNSW_E_INVALID, and so is a source that is not an f32 store.
+ * A distance on the store dequantises (scale * (float)code, one f32 multiply) and runs the f32 store's arithmetic, so
+ * every result equals, bit for bit, the f32 search over the dequantised rows -- which phnsw_store_read returns
+ * (phnsw_store_info reports rows_dev NULL).  The store is SEARCH-ONLY with the supported list of the f16 store:
+ * phnsw_distance_batch, phnsw_index_from_layers, phnsw_search_batch, _stored, _topk, _device, phnsw_index_layer_*,
+ * the phnsw_last_search_* / phnsw_dense_top_layers queries and the destroy calls; every other entry point returns
+ * PHNSW_E_UNSUPPORTED. */
+int phnsw_store_create_i8(const phnsw_store *full, phnsw_store **out);
+/* the stored codes [n][dim] and scales [n] of an i8 store */
+int phnsw_i8_read(const phnsw_store *s, int8_t *codes, float *scales);
+/* phnsw_f16_search_batch / _device over an index on an i8 store: search, recompute every returned id on `full`,
+ * sort by (distance, id), keep the best k <= number_of_candidates; same outputs */
+int phnsw_i8_search_batch(const phnsw_index *ix, const phnsw_store *full, const float *queries, uint64_t nq,
+                          const phnsw_search_params *sp, uint64_t k, uint64_t *out_ids, float *out_d,
+                          uint64_t *out_len);
+int phnsw_i8_search_batch_device(const phnsw_index *ix, const phnsw_store *full, const float *queries_dev,
+                                 uint32_t ldq, uint64_t nq, const phnsw_search_params *sp, uint64_t k,
+                                 uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                 uint32_t *out_stats_dev, uint32_t *status_dev, void *stream);
+
 /* ---- on-disk interchange with the Rust crate: serialize_hnsw / deserialize_hnsw
  * (src/serialize.rs:33-209): <dir>/meta (JSON HNSWMeta), <dir>/comparator/ (this library's
  * store; a crate user substitutes their own Serializable comparator), layer.meta.N (JSON),

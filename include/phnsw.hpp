@@ -108,6 +108,19 @@ class Comparator {
     check(phnsw_store_create_f16(s_, &h));
     return h;  // wrap it: Comparator half(full.make_f16());
   }
+  // the same vectors as int8 rows with one f32 scale per row (phnsw_store_create_i8): search-only as well; re-rank
+  // with Hnsw::search_many_reranked_i8(*this, ...)
+  phnsw_store *make_i8() const {
+    phnsw_store *h = nullptr;
+    check(phnsw_store_create_i8(s_, &h));
+    return h;  // wrap it: Comparator q8(full.make_i8());
+  }
+  // codes [n][dim] and scales [n] of a comparator made by make_i8 (phnsw_i8_read)
+  void read_i8(std::vector<int8_t> &codes, std::vector<float> &scales) const {
+    codes.resize(n_ * dim_);
+    scales.resize(n_);
+    check(phnsw_i8_read(s_, codes.data(), scales.data()));
+  }
   uint32_t dim() const { return dim_; }
   uint64_t len() const { return n_; }
   phnsw_store *handle() const { return s_; }
@@ -205,6 +218,25 @@ class Hnsw {
     for (uint64_t i = 0; i < nq; i++)
       for (uint64_t j = 0; j < len[i]; j++) out[i].push_back({ids[i * k + j], d[i * k + j]});
     return out;
+  }
+  // the same over an i8 comparator (phnsw_i8_search_batch)
+  std::vector<SearchResult> search_many_reranked_i8(const Comparator &full, const std::vector<float> &queries,
+                                                    const SearchParameters &sp, uint64_t k) const {
+    const uint64_t nq = queries.size() / c_->dim();
+    std::vector<uint64_t> ids(nq * k), len(nq);
+    std::vector<float> d(nq * k);
+    check(phnsw_i8_search_batch(ix_, full.handle(), queries.data(), nq, &sp, k, ids.data(), d.data(), len.data()));
+    std::vector<SearchResult> out(nq);
+    for (uint64_t i = 0; i < nq; i++)
+      for (uint64_t j = 0; j < len[i]; j++) out[i].push_back({ids[i * k + j], d[i * k + j]});
+    return out;
+  }
+  // zero-copy form: device pointers of the caller, enqueued on `stream` (phnsw_i8_search_batch_device)
+  void search_reranked_i8_device(const Comparator &full, const float *queries_dev, uint32_t ldq, uint64_t nq,
+                                 const SearchParameters &sp, uint64_t k, uint32_t *out_ids_dev, float *out_d_dev,
+                                 uint32_t *out_len_dev, uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) const {
+    check(phnsw_i8_search_batch_device(ix_, full.handle(), queries_dev, ldq, nq, &sp, k, out_ids_dev, out_d_dev, out_len_dev,
+                                       out_stats_dev, status_dev, stream));
   }
   // the batched form every GPU caller should use
   std::vector<SearchResult> search_many(const std::vector<AbstractVector> &vs, const SearchParameters &sp,

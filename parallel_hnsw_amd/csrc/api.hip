@@ -163,7 +163,7 @@ extern "C" int phnsw_store_create(const float *rows, uint64_t n, uint32_t dim, i
 // comparator and calls generate / extend on the new ids): the array is reallocated, so no search
 // or build may be running on an index over this store; existing VectorIds keep their rows
 extern "C" int phnsw_store_append(phnsw_store *s, const float *rows, uint64_t count, uint64_t *out_first_id) try {
-  if (int rc = ph_f16_unsupported(s, "phnsw_store_append")) return rc;
+  if (int rc = ph_search_only_unsupported(s, "phnsw_store_append")) return rc;
   if (!s || !rows || !s->rows || !s->owns_rows || s->n + count >= 0x7FFFFFFFull) {
     ph_set_error("phnsw_store_append: needs an f32 store created by phnsw_store_create* that owns its rows, n < 2^31");
     return PHNSW_E_INVALID;
@@ -299,9 +299,10 @@ extern "C" int phnsw_store_info(const phnsw_store *s, uint64_t *n, uint32_t *dim
 } catch (...) { return ph_caught(); }
 
 extern "C" int phnsw_store_read(const phnsw_store *s, uint64_t first, uint64_t count, float *out) try {
-  if (s && out && s->half && first + count <= s->n) {  // f16 store: the widened values, as the distance kernels see them
+  if (s && out && ph_store_converted(s) && first + count <= s->n) {  // f16 / i8 store: the values the distance kernels see
     PH_HIP(hipSetDevice(s->device));
-    return count ? ph_f16_store_read(s, first, count, out) : 0;
+    if (!count) return 0;
+    return s->half ? ph_f16_store_read(s, first, count, out) : ph_i8_store_read(s, first, count, out);
   }
   if (!s || !out || !s->rows || first + count > s->n) {
     ph_set_error("phnsw_store_read: range out of bounds (or a product-quantised store: use phnsw_pq_read)");
@@ -321,6 +322,7 @@ extern "C" void phnsw_store_destroy(phnsw_store *s) {
   if (s->owns_rows && s->rows) hipFree(s->rows);
   if (s->codes) hipFree(s->codes);
   if (s->half) hipFree(s->half);
+  if (s->i8) hipFree(s->i8);
   if (s->codes16) hipFree(s->codes16);
   if (s->centroid_index) phnsw_index_destroy(s->centroid_index);  // (releases its reference to centroid_store)
   if (s->centroid_store) phnsw_store_destroy(s->centroid_store);
@@ -662,9 +664,9 @@ int ph_search_device(const phnsw_index *ix, const float *queries_dev, uint32_t l
                      uint32_t *out_hit, float threshold, uint32_t first_node, float hit_eps, const uint32_t *order,
                      uint32_t *out_index, const PhRowHint *hint) {
   phnsw_index *mix = const_cast<phnsw_index *>(ix);
-  if (ix->store->half && (knn_mode || out_index || hint || out_hit)) {
-    // an f16 store is searched, never built over: knn / threshold_nn / search_instrumented / the build's rounds
-    return ph_f16_unsupported(ix->store, knn_mode ? "knn / threshold_nn" : (out_index ? "search_instrumented" : "build search"));
+  if (ph_store_converted(ix->store) && (knn_mode || out_index || hint || out_hit)) {
+    // an f16 / i8 store is searched, never built over: knn / threshold_nn / search_instrumented / the build's rounds
+    return ph_search_only_unsupported(ix->store, knn_mode ? "knn / threshold_nn" : (out_index ? "search_instrumented" : "build search"));
   }
   PhSearchArgs a;
   fill_args(ix, sp, upto, a);
@@ -722,7 +724,7 @@ int ph_search_device(const phnsw_index *ix, const float *queries_dev, uint32_t l
   }
   // (not for PQ stores: their searches are not bound by where rows come from, and every launch
   // would build the per-query table again)
-  const bool split = (ix->store->rows || ix->store->half) && !a.order && !knn_mode && !out_stride && !out_index && first_big < a.n_layers &&
+  const bool split = (ix->store->rows || ph_store_converted(ix->store)) && !a.order && !knn_mode && !out_stride && !out_index && first_big < a.n_layers &&
                      nq >= two_launch_min() &&
                      !getenv("PHNSW_NO_LOCALITY");
   if (split) {
@@ -1050,7 +1052,7 @@ static int search_host(const phnsw_index *ix, const float *queries, const uint64
 extern "C" int phnsw_knn(const phnsw_index *ix, uint64_t k, uint64_t probe_depth, uint64_t *out_ids, float *out_d,
                          uint64_t *out_len) try {
   if (ix)
-    if (int rc = ph_f16_unsupported(ix->store, "phnsw_knn")) return rc;
+    if (int rc = ph_search_only_unsupported(ix->store, "phnsw_knn")) return rc;
   if (!ix || ix->layers.empty() || k == 0 || k * 3 > 1024) {
     ph_set_error("phnsw_knn: k must be 1..341");
     return PHNSW_E_INVALID;
@@ -1237,7 +1239,7 @@ extern "C" int phnsw_threshold_nn(const phnsw_index *ix, float threshold, uint64
                                   uint64_t initial_search_depth, uint64_t max_out, uint64_t *out_ids, float *out_d,
                                   uint64_t *out_len) try {
   if (ix)
-    if (int rc = ph_f16_unsupported(ix->store, "phnsw_threshold_nn")) return rc;
+    if (int rc = ph_search_only_unsupported(ix->store, "phnsw_threshold_nn")) return rc;
   if (!ix || ix->layers.empty() || !out_ids || !out_d || !out_len || initial_search_depth == 0 ||
       initial_search_depth > 0x40000000ull || probe_depth == 0 || max_out == 0) {
     ph_set_error("phnsw_threshold_nn: initial_search_depth and probe_depth must be >= 1");

@@ -162,7 +162,7 @@ static thread_local float g_bf_gemm_ms = 0.f;
 // everything on the device: queries_dev [nq][ldq], outputs [nq][k] (u32 ids, f32 distances)
 extern "C" int phnsw_bruteforce_topk_device(const phnsw_store *s, const float *queries_dev, uint32_t ldq, uint64_t nq,
                                             uint32_t k, uint32_t *out_ids_dev, float *out_d_dev, void *stream) try {
-  if (int rc = ph_f16_unsupported(s, "phnsw_bruteforce_topk")) return rc;
+  if (int rc = ph_search_only_unsupported(s, "phnsw_bruteforce_topk")) return rc;
   if (!s || !s->rows || !queries_dev || !out_ids_dev || !out_d_dev || k == 0 || k > BF_KMAX || k > s->n ||
       nq == 0 || nq > 0xFFFFFFFFull || ldq < s->ld || (ldq % 4) || s->metric == PHNSW_METRIC_L2) {
     ph_set_error("phnsw_bruteforce_topk: need an f32 store with a dot-product metric, 1 <= k <= %d, ldq %% 4 == 0",
@@ -341,8 +341,8 @@ static int ph_store_anchors(phnsw_store *s) {
   if (e == hipSuccess) e = hipMalloc(&ids, (size_t)A * 4);
   if (e == hipSuccess) e = hipMemcpy(ids, h.data(), (size_t)A * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
-    if (s->half)  // f16 store: the anchors are its widened rows
-      (void)ph_f16_gather_rows(s, ids, 0, A, anchors);
+    if (ph_store_converted(s))  // f16 / i8 store: the anchors are its widened / dequantised rows
+      (void)ph_converted_gather_rows(s, ids, 0, A, anchors);
     else
       hipLaunchKernelGGL(ph_gather_rows_f32_kernel, dim3((A + 3) / 4), dim3(256), 0, 0, s->rows, ld, ids, 1u, A, anchors);
     dim3 grid((A + BF_TN - 1) / BF_TN, (A + BF_TM - 1) / BF_TM);
@@ -374,7 +374,7 @@ void ph_store_anchors_free(phnsw_store *s) {
 // whether a layer carries cells at all: not the small ones, not PQ stores, not the L2 metric (the GEMM scores dot
 // products)
 bool ph_layer_wants_cells(const phnsw_store *s, uint32_t n_nodes) {
-  return n_nodes >= PH_POS_MIN && (s->rows || s->half) && s->n >= 65536 && s->metric != PHNSW_METRIC_L2 && !getenv("PHNSW_NO_LOCALITY");
+  return n_nodes >= PH_POS_MIN && (s->rows || ph_store_converted(s)) && s->n >= 65536 && s->metric != PHNSW_METRIC_L2 && !getenv("PHNSW_NO_LOCALITY");
 }
 
 // out_pos[i] = chain rank of the nearest anchor of node first + i, for count nodes of the layer (the sharded build
@@ -388,13 +388,13 @@ int ph_layer_cells_range(const phnsw_store *cs, const PhLayerHost &L, uint32_t f
   const uint32_t QC = 65536;  // layer vectors per GEMM pass
   float *qrows = nullptr, *scores = nullptr;
   hipError_t e = hipMalloc(&scores, (size_t)std::min(QC, count) * A * 4);
-  if (e == hipSuccess && (!L.identity || s->half)) e = hipMalloc(&qrows, (size_t)std::min(QC, count) * ld * 4);
+  if (e == hipSuccess && (!L.identity || ph_store_converted(s))) e = hipMalloc(&qrows, (size_t)std::min(QC, count) * ld * 4);
   if (e == hipSuccess) {
     for (uint32_t at = 0; at < count; at += QC) {
       const uint32_t cnt = std::min(QC, count - at);
       const float *Q = s->rows ? s->rows + (uint64_t)(first + at) * ld : nullptr;  // identity layer: node i is row i
-      if (s->half) {  // f16 store: the layer's rows widened (a copy even for an identity layer)
-        (void)ph_f16_gather_rows(s, L.identity ? nullptr : L.nodes + first + at, first + at, cnt, qrows);
+      if (ph_store_converted(s)) {  // f16 / i8 store: the layer's rows as f32 (a copy even for an identity layer)
+        (void)ph_converted_gather_rows(s, L.identity ? nullptr : L.nodes + first + at, first + at, cnt, qrows);
         Q = qrows;
       } else if (!L.identity) {
         hipLaunchKernelGGL(ph_gather_rows_f32_kernel, dim3((cnt + 3) / 4), dim3(256), 0, 0, s->rows, ld, L.nodes + first + at,
@@ -438,7 +438,7 @@ extern "C" float phnsw_bruteforce_last_gemm_ms(void) { return g_bf_gemm_ms; }
 
 extern "C" int phnsw_bruteforce_topk(const phnsw_store *s, const float *queries, uint64_t nq, uint32_t k,
                                      uint64_t *out_ids, float *out_d) try {
-  if (int rc = ph_f16_unsupported(s, "phnsw_bruteforce_topk")) return rc;
+  if (int rc = ph_search_only_unsupported(s, "phnsw_bruteforce_topk")) return rc;
   if (!s || !queries || !out_ids || !out_d || nq == 0) {
     ph_set_error("phnsw_bruteforce_topk: invalid argument");
     return PHNSW_E_INVALID;

@@ -1556,7 +1556,7 @@ static int enter(const phnsw_index *ix, const char *call = __builtin_FUNCTION())
     ph_set_error("null index");
     return PHNSW_E_INVALID;
   }
-  if (int rc = ph_f16_unsupported(ix->store, call)) return rc;
+  if (int rc = ph_search_only_unsupported(ix->store, call)) return rc;
   PH_HIP(hipSetDevice(ix->store->device));
   return 0;
 }
@@ -1669,7 +1669,7 @@ extern "C" int phnsw_recall_hits(phnsw_index *ix, uint32_t layer_from_top, const
 } catch (...) { return ph_caught(); }
 extern "C" int phnsw_index_create(phnsw_store *s, const phnsw_build_params *bp, phnsw_index **out) try {
   if (!s || !out) return PHNSW_E_INVALID;
-  if (int rc = ph_f16_unsupported(s, "phnsw_index_create")) return rc;
+  if (int rc = ph_search_only_unsupported(s, "phnsw_index_create")) return rc;
   PH_HIP(hipSetDevice(s->device));
   phnsw_index *ix = new phnsw_index();
   ix->store = s;
@@ -1748,7 +1748,7 @@ static int build_impl(phnsw_store *s, const uint64_t *vids, uint64_t n, const ph
 
 extern "C" int phnsw_build(phnsw_store *s, const uint64_t *vids, uint64_t n, const phnsw_build_params *bp,
                            phnsw_progress_cb cb, void *user, phnsw_index **out) try {
-  if (int rc = ph_f16_unsupported(s, "phnsw_build")) return rc;
+  if (int rc = ph_search_only_unsupported(s, "phnsw_build")) return rc;
   int rc = build_impl(s, vids, n, bp, cb, user, out);
   ph_pool_trim();  // scratch of the rounds goes back to the driver
   return rc;

@@ -4,7 +4,7 @@
 //
 // The contract: a distance on this store is the f32 chain on the WIDENED rows -- widening is exact -- so a search
 // equals, bit for bit, the f32 search over the store phnsw_store_read returns.  The store serves searches and
-// distance batches only (ph_f16_unsupported names everything else).
+// distance batches only (ph_search_only_unsupported names everything else).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

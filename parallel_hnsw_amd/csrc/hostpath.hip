@@ -427,7 +427,7 @@ extern "C" int phnsw_search_instrumented(const phnsw_index *ix, const float *que
                                          const phnsw_search_params *sp, uint64_t *out_ids, float *out_d,
                                          uint64_t *out_len, uint64_t *out_index_distance) try {
   if (ix)
-    if (int rc = ph_f16_unsupported(ix->store, "phnsw_search_instrumented")) return rc;
+    if (int rc = ph_search_only_unsupported(ix->store, "phnsw_search_instrumented")) return rc;
   if ((((!queries) == (!qids)) && nq) || !out_index_distance) {
     ph_set_error("phnsw_search_instrumented: pass queries or qids (exactly one) and out_index_distance");
     return PHNSW_E_INVALID;

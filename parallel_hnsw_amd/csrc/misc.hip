@@ -63,6 +63,23 @@ int ph_distance_batch(const phnsw_store *st, const float *q_dev, uint32_t query_
       return PHNSW_E_UNSUPPORTED;
     }
 #undef PH_LAUNCH_H
+  } else if (st->i8) {  // i8 store: the same chain over dequantised int8 rows
+    uint32_t nv4 = st->ld / 4;
+    uint32_t blocks = std::min<uint32_t>((k + 63) / 64, 4096);
+#define PH_LAUNCH_B(NV)                                                                                          \
+  hipLaunchKernelGGL(ph_distance_batch_kernel<DistI8<NV>>, dim3(blocks), dim3(64), 0, s, da, q_dev, query_id,   \
+                     ids_dev, k, st->n, out_dev)
+    if (nv4 <= 64)
+      PH_LAUNCH_B(1);
+    else if (nv4 <= 192)
+      PH_LAUNCH_B(3);
+    else if (nv4 <= 384)
+      PH_LAUNCH_B(6);
+    else {
+      ph_set_error("dim %u unsupported (max 1536)", st->dim);
+      return PHNSW_E_UNSUPPORTED;
+    }
+#undef PH_LAUNCH_B
   } else {
     uint32_t nv4 = st->ld / 4;
     uint32_t blocks = std::min<uint32_t>((k + 63) / 64, 4096);

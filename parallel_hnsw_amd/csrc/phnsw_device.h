@@ -113,29 +113,61 @@ __device__ __forceinline__ void chain_partial2(const float4 (&x)[NV], const ph_f
 }
 
 // How a stored row reaches the chain: a lane's chunk lane + 64k is four components -- 16 bytes of an f32 row, 8 bytes
-// of a half-precision row (f16 store).  Halves widen to f32 with v_cvt_f32_f16, which is exact (subnormals included:
-// the kernels run with f16 denormals on, the compiler's default), so the chain sees the f32 values a row of the
-// widened store would hold and everything behind the load is shared.  The raw chunks of all U rows are requested
-// before the first use and widened row by row: a half row in flight costs half the registers.
+// of a half-precision row (f16 store), 4 bytes of an int8 row (i8 store).  Halves widen to f32 with v_cvt_f32_f16, which
+// is exact (subnormals included: the kernels run with f16 denormals on, the compiler's default); an int8 code becomes
+// scale * (float)code with the row's scale (ph_i8_dequant: one rounding, the value phnsw_store_read returns).  Either
+// way the chain sees the f32 values a row of the converted store would hold and everything behind the load is shared.
+// A policy names its chunk, what widen needs beside the chunk (aux: nothing, or the row's scale), and how both are
+// read from a row.  The raw chunks (and aux) of all U rows are requested before the first use and widened row by row:
+// a half row in flight costs half the registers, an int8 row a quarter.
+struct RowNoAux {};
 struct RowF32 {
   typedef float4 chunk;
+  typedef RowNoAux aux;
   static constexpr uint32_t ELT = 4;  // bytes per component
   static __device__ __forceinline__ float4 widen(const float4 &v) { return v; }
+  static __device__ __forceinline__ float4 widen(const float4 &v, const aux &) { return v; }
+  static __device__ __forceinline__ aux row_aux(const chunk *) { return aux(); }
+  static __device__ __forceinline__ chunk load(const chunk *row, uint32_t c) { return row[c]; }
   static __device__ __forceinline__ const chunk *row(const PhDistArgs &d, uint32_t vid) {
     return (const chunk *)(d.vecs + (uint64_t)vid * d.ld);
   }
 };
 struct RowF16 {
   typedef uint2 chunk;
+  typedef RowNoAux aux;
   static constexpr uint32_t ELT = 2;
   static __device__ __forceinline__ const chunk *row(const PhDistArgs &d, uint32_t vid) {
     return (const chunk *)(d.half + (uint64_t)vid * d.ldh);
   }
+  static __device__ __forceinline__ aux row_aux(const chunk *) { return aux(); }
+  static __device__ __forceinline__ chunk load(const chunk *row, uint32_t c) { return row[c]; }
   static __device__ __forceinline__ float4 widen(const uint2 &v) {
     return make_float4(__half2float(__ushort_as_half((unsigned short)(v.x & 0xFFFFu))),
                        __half2float(__ushort_as_half((unsigned short)(v.x >> 16))),
                        __half2float(__ushort_as_half((unsigned short)(v.y & 0xFFFFu))),
                        __half2float(__ushort_as_half((unsigned short)(v.y >> 16))));
+  }
+  static __device__ __forceinline__ float4 widen(const uint2 &v, const aux &) { return widen(v); }
+};
+// THE dequantised component of an i8 store: one IEEE f32 multiply (never contracted into the chain's fma).  The
+// distance kernels, phnsw_store_read, the dense table's pack and staging steps and the cells' row gather all call it.
+__device__ __forceinline__ float ph_i8_dequant(float scale, int code) { return __fmul_rn(scale, (float)code); }
+// A stored row is ldb bytes (a multiple of 16): its f32 scale, then ld int8 codes, then padding.  The scale sits at
+// the head, in the 128-byte line the row's first chunks come from; the row pointer is wave-uniform in the distance
+// kernels, so the scale is one same-address (scalar) load per row, not one request per lane.
+struct RowI8 {
+  typedef uint32_t chunk;  // four codes
+  typedef float aux;       // the row's scale
+  static constexpr uint32_t ELT = 1;  // batch_distances is handed the row's byte stride
+  static __device__ __forceinline__ const chunk *row(const PhDistArgs &d, uint32_t vid) {
+    return (const chunk *)(d.i8 + (uint64_t)vid * d.ldb);
+  }
+  static __device__ __forceinline__ aux row_aux(const chunk *row) { return __uint_as_float(row[0]); }
+  static __device__ __forceinline__ chunk load(const chunk *row, uint32_t c) { return row[1u + c]; }
+  static __device__ __forceinline__ float4 widen(const uint32_t &v, const aux &s) {
+    return make_float4(ph_i8_dequant(s, (int)(int8_t)(v & 0xFFu)), ph_i8_dequant(s, (int)(int8_t)((v >> 8) & 0xFFu)),
+                       ph_i8_dequant(s, (int)(int8_t)((v >> 16) & 0xFFu)), ph_i8_dequant(s, (int)v >> 24));
   }
 };
 
@@ -143,20 +175,22 @@ template <int NV, int U, bool EXACT, bool L2, class R>
 __device__ __forceinline__ void rows_partial_impl(const typename R::chunk *const (&row)[U], const float4 (&q)[NV],
                                                   uint32_t nv4, uint32_t lane, float (&acc)[U]) {
   typename R::chunk raw[U][NV];
+  typename R::aux ax[U];
 #pragma unroll
   for (int u = 0; u < U; u++) {
+    ax[u] = R::row_aux(row[u]);
 #pragma unroll
     for (int k = 0; k < NV; k++) {
       uint32_t c = lane + 64u * k;
       if (!EXACT) c = c < nv4 ? c : nv4 - 1;
-      raw[u][k] = row[u][c];
+      raw[u][k] = R::load(row[u], c);
     }
   }
 #pragma unroll
   for (int u = 0; u < U; u++) {
     float4 x[NV];
 #pragma unroll
-    for (int k = 0; k < NV; k++) x[k] = R::widen(raw[u][k]);
+    for (int k = 0; k < NV; k++) x[k] = R::widen(raw[u][k], ax[u]);
     acc[u] = chain_partial<NV, EXACT, L2>(x, q, nv4, lane);
   }
 }
@@ -405,6 +439,35 @@ struct DistF16 {
   }
   __device__ __forceinline__ float batch(const PhDistArgs &d, uint64_t mask, uint32_t vid, uint32_t lane) const {
     return batch_distances<NV, U, RowF16>(d.half, d.ldh, d.nv4, d.metric, d.metric == PHNSW_METRIC_L2, qv, mask, vid, lane);
+  }
+};
+
+// DistI8<NV, U>: DistF32 over an int8 row store with one f32 scale per row.  The query stays f32 in registers; a stored
+// query is its dequantised row; a candidate's chunk is 4 bytes, dequantised in registers (RowI8).  Same chain, same
+// butterfly, same compaction: the bits are those of DistF32 on the store of dequantised rows.
+template <int NV, int U = 4>
+struct DistI8 {
+  static constexpr bool GLOBAL_TABLE = false;
+  static constexpr bool EARLY = false;
+  float4 qv[NV];
+  __device__ __forceinline__ void prepare_raw(const PhDistArgs &d, const float *q, float *, uint32_t lane) {
+#pragma unroll
+    for (int k = 0; k < NV; k++) {
+      uint32_t c = lane + 64u * k;
+      qv[k] = (c < d.nv4) ? ((const float4 *)q)[c] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+  __device__ __forceinline__ void prepare_stored(const PhDistArgs &d, uint32_t vid, float *, uint32_t lane) {
+    const RowI8::chunk *row = RowI8::row(d, vid);
+    const float s = RowI8::row_aux(row);
+#pragma unroll
+    for (int k = 0; k < NV; k++) {
+      uint32_t c = lane + 64u * k;
+      qv[k] = (c < d.nv4) ? RowI8::widen(RowI8::load(row, c), s) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  }
+  __device__ __forceinline__ float batch(const PhDistArgs &d, uint64_t mask, uint32_t vid, uint32_t lane) const {
+    return batch_distances<NV, U, RowI8>(d.i8, d.ldb, d.nv4, d.metric, d.metric == PHNSW_METRIC_L2, qv, mask, vid, lane);
   }
 };
 

@@ -72,6 +72,8 @@ struct PhDistArgs {
   uint32_t table_f16;  // 1: the per-query table holds IEEE half values (2 bytes per entry)
   const uint16_t *half;  // [n][ldh] IEEE binary16 rows in component order (f16 store, f16.hip); vecs == nullptr then
   uint32_t ldh;          // halves per row (== ld: rows start on 8-byte boundaries)
+  const uint8_t *i8;     // [n] rows of ldb bytes: f32 scale, then ld int8 codes (i8 store, i8.hip); vecs == nullptr then
+  uint32_t ldb;          // bytes per row: 4 + ld rounded up to a multiple of 16
 };
 
 struct phnsw_store {
@@ -88,9 +90,13 @@ struct phnsw_store {
   uint32_t pq_m = 0, pq_ksub = 0, pq_dsub = 0;
   uint32_t pq_table_f16 = 0;
   // half-precision store (phnsw_store_create_f16, f16.hip): rows == nullptr, half = [n][ldh] binary16 rows; a distance
-  // widens them to f32 (exact) and runs the f32 chain.  Search-only: see ph_f16_unsupported.
+  // widens them to f32 (exact) and runs the f32 chain.  Search-only: see ph_search_only_unsupported.
   uint16_t *half = nullptr;
   uint32_t ldh = 0;
+  // int8 store (phnsw_store_create_i8, i8.hip): rows == nullptr, i8 = n rows of ldb bytes, each its f32 scale followed
+  // by ld int8 codes; a distance dequantises them (scale * code) and runs the f32 chain.  Search-only as well.
+  uint8_t *i8 = nullptr;
+  uint32_t ldb = 0;
   // coarse cells of the locality schedule (bruteforce.hip): anchor rows + their chain ranks
   float *anchors = nullptr;
   uint32_t *anchor_rank = nullptr;
@@ -351,6 +357,15 @@ int ph_layer_range_order(PhLayerHost &L, uint32_t first, uint32_t count, const u
 // range of the store widened into a dense host array
 int ph_f16_gather_rows(const phnsw_store *s, const uint32_t *ids_dev, uint32_t first, uint32_t cnt, float *out_dev);
 int ph_f16_store_read(const phnsw_store *s, uint64_t first, uint64_t count, float *out);
+// i8 store (i8.hip): the same two, dequantising
+int ph_i8_gather_rows(const phnsw_store *s, const uint32_t *ids_dev, uint32_t first, uint32_t cnt, float *out_dev);
+int ph_i8_store_read(const phnsw_store *s, uint64_t first, uint64_t count, float *out);
+// a search-only row store (f16 or i8): searched like the f32 store, its rows converted to f32 where a GEMM or a host reads them
+static inline bool ph_store_converted(const phnsw_store *s) { return s->half || s->i8; }
+static inline int ph_converted_gather_rows(const phnsw_store *s, const uint32_t *ids_dev, uint32_t first, uint32_t cnt,
+                                           float *out_dev) {
+  return s->half ? ph_f16_gather_rows(s, ids_dev, first, cnt, out_dev) : ph_i8_gather_rows(s, ids_dev, first, cnt, out_dev);
+}
 
 // dense top layers (tiny.hip): decides how many leading layers of the launch described by `a` run
 // against a distance table, fills a.tiny_* and enqueues the table kernels for launch positions
@@ -397,14 +412,17 @@ static inline PhDistArgs ph_dist_args(const phnsw_store *s) {
   d.table_f16 = s->pq_table_f16;
   d.half = s->half;
   d.ldh = s->ldh;
+  d.i8 = s->i8;
+  d.ldb = s->ldb;
   return d;
 }
 // bytes of one stored row as the search gathers it
-static inline uint32_t ph_row_bytes(const phnsw_store *s) { return s->half ? s->ldh * 2u : s->ld * 4u; }
-// an f16 store serves searches only: every other entry point refuses it by name
-static inline int ph_f16_unsupported(const phnsw_store *s, const char *call) {
-  if (!s || !s->half) return 0;
-  ph_set_error("%s: not supported on an f16 store or an index over one (search-only; use the f32 store)", call);
+static inline uint32_t ph_row_bytes(const phnsw_store *s) { return s->i8 ? s->ldb : (s->half ? s->ldh * 2u : s->ld * 4u); }
+// an f16 or i8 store serves searches only: every other entry point refuses it by name
+static inline int ph_search_only_unsupported(const phnsw_store *s, const char *call) {
+  if (!s || !ph_store_converted(s)) return 0;
+  ph_set_error("%s: not supported on an %s store or an index over one (search-only; use the f32 store)", call,
+               s->half ? "f16" : "i8");
   return PHNSW_E_UNSUPPORTED;
 }
 // the batched search keeps PQ tables in global memory unless PHNSW_PQ_TABLE=lds

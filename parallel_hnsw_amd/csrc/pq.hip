@@ -216,7 +216,7 @@ static int pq_encode_sharded(const phnsw_comm *comm, uint64_t n, uint64_t row_by
 extern "C" int phnsw_store_create_pq_sharded(phnsw_store *full, uint32_t m, uint32_t ksub, uint64_t seed,
                                              uint32_t kmeans_iters, uint64_t sample, const phnsw_comm *comm,
                                              phnsw_store **out) try {
-  if (int rc = ph_f16_unsupported(full, "phnsw_store_create_pq")) return rc;
+  if (int rc = ph_search_only_unsupported(full, "phnsw_store_create_pq")) return rc;
   if (!full || !out || full->codes || !full->rows || m == 0 || ksub == 0 || ksub > 256 || (m % 4) ||
       (full->dim % m) || ksub > full->n) {
     ph_set_error("phnsw_store_create_pq: need an f32 store, m %% 4 == 0, dim %% m == 0, 1 <= ksub <= min(256, n)");
@@ -374,7 +374,7 @@ extern "C" int phnsw_store_create_pq_shared_sharded(phnsw_store *full, uint32_t 
                                                     const phnsw_build_params *centroid_bp,
                                                     const phnsw_search_params *quantized_search, int centroid_metric,
                                                     const phnsw_comm *comm, phnsw_store **out) try {
-  if (int rc = ph_f16_unsupported(full, "phnsw_store_create_pq_shared")) return rc;
+  if (int rc = ph_search_only_unsupported(full, "phnsw_store_create_pq_shared")) return rc;
   if (!full || !out || !full->rows || !centroid_bp || !quantized_search || dsub == 0 || (dsub % 4) || (full->dim % dsub) ||
       full->ld != full->dim || n_centroids == 0 || n_centroids > 65535 || n_centroids > full->n ||
       quantized_search->number_of_candidates == 0 || quantized_search->number_of_candidates > 1024 ||
@@ -771,9 +771,9 @@ extern "C" int phnsw_pq_search_batch_device(const phnsw_index *ix, const phnsw_s
   return 0;
 } catch (...) { return ph_caught(); }
 
-// ------------------------------------------------------------------ f16 store: search + f32 re-rank
+// ------------------------------------------------------------------ f16 / i8 store: search + f32 re-rank
 //
-// The f16 index finds the candidates (distances of the widened half rows); the f32 store then gives every returned
+// The f16 or i8 index finds the candidates (distances of the widened / dequantised rows); the f32 store then gives every returned
 // id its full-precision distance (ph_pq_rerank_kernel: the bits of phnsw_distance_batch on `full`), the row is
 // sorted by (distance, id) and the best k are kept.
 
@@ -802,20 +802,21 @@ __global__ void ph_f16_take_kernel(const uint32_t *ids, const float *d, uint32_t
   }
 }
 
-static int f16_rerank_check(const char *call, const phnsw_index *ix, const phnsw_store *full, const phnsw_search_params *sp,
-                            uint64_t nq, uint64_t k) {
-  if (!ix || !full || !sp || !ix->store->half || !full->rows || full->n != ix->store->n || full->dim != ix->store->dim ||
+// `i8`: which of the two stores the entry point serves (the f16 calls refuse an i8 index and the other way round)
+static int rerank_check(const char *call, bool i8, const phnsw_index *ix, const phnsw_store *full,
+                        const phnsw_search_params *sp, uint64_t nq, uint64_t k) {
+  if (!ix || !full || !sp || !(i8 ? (const void *)ix->store->i8 : (const void *)ix->store->half) || !full->rows || full->n != ix->store->n || full->dim != ix->store->dim ||
       full->metric != ix->store->metric || full->device != ix->store->device || nq > 0xFFFFFFFFull ||
       sp->number_of_candidates == 0 || sp->number_of_candidates > 1024 || sp->probe_depth == 0 || k == 0 ||
       k > sp->number_of_candidates) {
-    ph_set_error("%s: need an index over an f16 store, the f32 store of the same n / dim / metric / device, valid "
-                 "parameters and 1 <= k <= number_of_candidates", call);
+    ph_set_error("%s: need an index over an %s store, the f32 store of the same n / dim / metric / device, valid "
+                 "parameters and 1 <= k <= number_of_candidates", call, i8 ? "i8" : "f16");
     return PHNSW_E_INVALID;
   }
   return 0;
 }
 
-static int f16_rerank_launch(const phnsw_store *full, const float *queries_dev, uint32_t ldq, uint64_t nq, uint32_t ef,
+static int rerank_launch(const phnsw_store *full, const float *queries_dev, uint32_t ldq, uint64_t nq, uint32_t ef,
                              uint32_t k, uint32_t *len, uint32_t *ids, float *d, hipStream_t st) {
   PhDistArgs fa = ph_dist_args(full);
   const uint32_t grid = (uint32_t)std::min<uint64_t>(nq, 256u * 16u);
@@ -842,31 +843,31 @@ static int f16_rerank_launch(const phnsw_store *full, const float *queries_dev, 
 
 // zero-copy form: the search launches, the re-rank and the cut to k enqueued on `stream`, no synchronisation.  The
 // result rows keep the search's stride (number_of_candidates entries per query): the first min(len, k) are live.
-extern "C" int phnsw_f16_search_batch_device(const phnsw_index *ix, const phnsw_store *full, const float *queries_dev,
-                                             uint32_t ldq, uint64_t nq, const phnsw_search_params *sp, uint64_t k,
-                                             uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
-                                             uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) try {
-  PH_TRYQ(f16_rerank_check("phnsw_f16_search_batch_device", ix, full, sp, nq, k));
+static int reranked_search_device(const char *call, bool i8, const phnsw_index *ix, const phnsw_store *full,
+                                  const float *queries_dev, uint32_t ldq, uint64_t nq, const phnsw_search_params *sp,
+                                  uint64_t k, uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                  uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) {
+  PH_TRYQ(rerank_check(call, i8, ix, full, sp, nq, k));
   if (!queries_dev || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev || ldq < full->ld || (ldq % 4) ||
       ((uintptr_t)queries_dev % 16)) {
-    ph_set_error("phnsw_f16_search_batch_device: invalid argument (queries need ldq >= store ld, multiple of 4, 16-byte base)");
+    ph_set_error("%s: invalid argument (queries need ldq >= store ld, multiple of 4, 16-byte base)", call);
     return PHNSW_E_INVALID;
   }
   if (nq == 0) return 0;
   PH_HIP(hipSetDevice(full->device));
   PH_TRYQ(ph_search_device(ix, queries_dev, ldq, nullptr, nq, sp, 0, nullptr, out_ids_dev, out_d_dev, out_len_dev,
                            out_stats_dev, status_dev, 0, 0, (hipStream_t)stream));
-  return f16_rerank_launch(full, queries_dev, ldq, nq, (uint32_t)sp->number_of_candidates, (uint32_t)k, out_len_dev,
+  return rerank_launch(full, queries_dev, ldq, nq, (uint32_t)sp->number_of_candidates, (uint32_t)k, out_len_dev,
                            out_ids_dev, out_d_dev, (hipStream_t)stream);
-} catch (...) { return ph_caught(); }
+}
 
 // host form: out_ids / out_d are [nq][k], out_len[q] = min(results of query q, k)
-extern "C" int phnsw_f16_search_batch(const phnsw_index *ix, const phnsw_store *full, const float *queries, uint64_t nq,
-                                      const phnsw_search_params *sp, uint64_t k, uint64_t *out_ids, float *out_d,
-                                      uint64_t *out_len) try {
-  PH_TRYQ(f16_rerank_check("phnsw_f16_search_batch", ix, full, sp, nq, k));
+static int reranked_search_host(const char *call, bool i8, const phnsw_index *ix, const phnsw_store *full,
+                                const float *queries, uint64_t nq, const phnsw_search_params *sp, uint64_t k,
+                                uint64_t *out_ids, float *out_d, uint64_t *out_len) {
+  PH_TRYQ(rerank_check(call, i8, ix, full, sp, nq, k));
   if ((!queries || !out_ids || !out_d || !out_len) && nq) {
-    ph_set_error("phnsw_f16_search_batch: queries and outputs must not be NULL");
+    ph_set_error("%s: queries and outputs must not be NULL", call);
     return PHNSW_E_INVALID;
   }
   if (nq == 0) return 0;
@@ -886,9 +887,9 @@ extern "C" int phnsw_f16_search_batch(const phnsw_index *ix, const phnsw_store *
   if (e == hipSuccess) e = hipMalloc(&ostat, nq * 4);
   if (e == hipSuccess) e = hipMalloc(&ids64, (size_t)nq * k * 8);
   if (e == hipSuccess) e = hipMalloc(&dk, (size_t)nq * k * 4);
-  if (e != hipSuccess) rc = ph_hip_fail(e, "f16 search staging", __FILE__, __LINE__);
+  if (e != hipSuccess) rc = ph_hip_fail(e, "re-ranked search staging", __FILE__, __LINE__);
   if (!rc) rc = ph_search_device(ix, qd, full->ld, nullptr, nq, sp, 0, nullptr, oid, od, olen, nullptr, ostat, 0, 0, 0);
-  if (!rc) rc = f16_rerank_launch(full, qd, full->ld, nq, ef, (uint32_t)k, olen, oid, od, 0);
+  if (!rc) rc = rerank_launch(full, qd, full->ld, nq, ef, (uint32_t)k, olen, oid, od, 0);
   if (!rc) {
     hipLaunchKernelGGL(ph_f16_take_kernel, dim3((uint32_t)std::min<uint64_t>((nq * k + 255) / 256, 4096)), dim3(256), 0, 0, oid,
                        od, ef, (uint32_t)k, nq, ids64, dk);
@@ -899,10 +900,10 @@ extern "C" int phnsw_f16_search_batch(const phnsw_index *ix, const phnsw_store *
     if (e == hipSuccess) e = hipMemcpy(h_len.data(), olen, nq * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(out_ids, ids64, (size_t)nq * k * 8, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(out_d, dk, (size_t)nq * k * 4, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = ph_hip_fail(e, "f16 search", __FILE__, __LINE__);
+    if (e != hipSuccess) rc = ph_hip_fail(e, "re-ranked search", __FILE__, __LINE__);
     for (uint64_t i = 0; !rc && i < nq; i++) {
       if (h_status[i]) {
-        ph_set_error("f16 search: query %llu failed with status %u", (unsigned long long)i, h_status[i]);
+        ph_set_error("%s: query %llu failed with status %u", call, (unsigned long long)i, h_status[i]);
         rc = h_status[i] == 4 ? PHNSW_E_MISSING_NODE : PHNSW_E_OVERFLOW;
       }
       out_len[i] = std::min<uint64_t>(h_len[i], k);
@@ -911,4 +912,30 @@ extern "C" int phnsw_f16_search_batch(const phnsw_index *ix, const phnsw_store *
   for (void *p : {(void *)qd, (void *)od, (void *)dk, (void *)oid, (void *)olen, (void *)ostat, (void *)ids64})
     if (p) hipFree(p);
   return rc;
+}
+
+extern "C" int phnsw_f16_search_batch_device(const phnsw_index *ix, const phnsw_store *full, const float *queries_dev,
+                                             uint32_t ldq, uint64_t nq, const phnsw_search_params *sp, uint64_t k,
+                                             uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                             uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) try {
+  return reranked_search_device("phnsw_f16_search_batch_device", false, ix, full, queries_dev, ldq, nq, sp, k, out_ids_dev,
+                                out_d_dev, out_len_dev, out_stats_dev, status_dev, stream);
+} catch (...) { return ph_caught(); }
+extern "C" int phnsw_f16_search_batch(const phnsw_index *ix, const phnsw_store *full, const float *queries, uint64_t nq,
+                                      const phnsw_search_params *sp, uint64_t k, uint64_t *out_ids, float *out_d,
+                                      uint64_t *out_len) try {
+  return reranked_search_host("phnsw_f16_search_batch", false, ix, full, queries, nq, sp, k, out_ids, out_d, out_len);
+} catch (...) { return ph_caught(); }
+// the same two over an index on an i8 store
+extern "C" int phnsw_i8_search_batch_device(const phnsw_index *ix, const phnsw_store *full, const float *queries_dev,
+                                            uint32_t ldq, uint64_t nq, const phnsw_search_params *sp, uint64_t k,
+                                            uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                            uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) try {
+  return reranked_search_device("phnsw_i8_search_batch_device", true, ix, full, queries_dev, ldq, nq, sp, k, out_ids_dev,
+                                out_d_dev, out_len_dev, out_stats_dev, status_dev, stream);
+} catch (...) { return ph_caught(); }
+extern "C" int phnsw_i8_search_batch(const phnsw_index *ix, const phnsw_store *full, const float *queries, uint64_t nq,
+                                     const phnsw_search_params *sp, uint64_t k, uint64_t *out_ids, float *out_d,
+                                     uint64_t *out_len) try {
+  return reranked_search_host("phnsw_i8_search_batch", true, ix, full, queries, nq, sp, k, out_ids, out_d, out_len);
 } catch (...) { return ph_caught(); }

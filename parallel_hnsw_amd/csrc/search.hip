@@ -91,6 +91,8 @@ template <int CAPC, int NV, int U>
 struct vis_lds_policy<CAPC, DistF32<NV, U>> : std::integral_constant<bool, U != 0 && vis_lds_shape(CAPC, NV)> {};
 template <int CAPC, int NV, int U>
 struct vis_lds_policy<CAPC, DistF16<NV, U>> : std::integral_constant<bool, U != 0 && vis_lds_shape(CAPC, NV)> {};
+template <int CAPC, int NV, int U>
+struct vis_lds_policy<CAPC, DistI8<NV, U>> : std::integral_constant<bool, U != 0 && vis_lds_shape(CAPC, NV)> {};
 
 // The LDS visited set: slot of a NodeId (multiplicative hash, scaled to any table size)
 __device__ __forceinline__ uint32_t vis_slot(uint32_t id, uint32_t slots) {
@@ -1057,6 +1059,19 @@ static ph_search_fn pick_kernel_f16(int capc, int nv) {
   return nullptr;
 }
 
+// i8 stores (DistI8): the same set once more, over int8 rows with a per-row scale
+static ph_search_fn pick_kernel_i8(int capc, int nv) {
+#define PH_KB(C, N) \
+  if (capc == C && nv == N) return (ph_search_fn)ph_search_kernel<C, DistI8<N>>;
+  PH_KB(2, 1) PH_KB(2, 3) PH_KB(2, 6)
+  if (capc == 4 && nv == 3) return (ph_search_fn)ph_search_kernel<4, DistI8<3, 8>>;
+  PH_KB(4, 6)
+  PH_KB(8, 1) PH_KB(8, 3) PH_KB(8, 6)
+  PH_KB(16, 1) PH_KB(16, 3) PH_KB(16, 6)
+#undef PH_KB
+  return nullptr;
+}
+
 // pq_lds: bytes behind the queues -- the PQ lookup table, or the dense-top-layer table row + visited bits
 static size_t lds_bytes(int capc, size_t pq_lds) { return (size_t)(5 * capc * 64 + 64) * 4 + pq_lds; }
 
@@ -1099,18 +1114,19 @@ static uint32_t vis_table_slots(ph_search_fn fn, size_t lds, int per_cu, size_t 
 
 // the kernels whose body runs the LDS visited set (vis_lds_policy)
 static bool vis_table_kernel(bool pq, int pqr_m, int capc, int nv) {
-  return !pq && (pqr_m == 0 || pqr_m == -4) && vis_lds_shape(capc, nv);
+  return !pq && (pqr_m == 0 || pqr_m == -4 || pqr_m == -5) && vis_lds_shape(capc, nv);
 }
 
 uint32_t ph_search_slots(uint32_t ef, uint32_t nv4, bool pq, size_t pq_lds, int pqr_m, bool grows, uint32_t *vis_slots,
                          size_t hole) {
   if (vis_slots) *vis_slots = 0;
   const int nv = pq ? 0 : pick_nv(nv4);
-  int capc = (!pq && (pqr_m == 0 || pqr_m == -4)) ? pick_capc_f32(ef, grows, nv) : pick_capc(ef);
+  int capc = (!pq && (pqr_m == 0 || pqr_m == -4 || pqr_m == -5)) ? pick_capc_f32(ef, grows, nv) : pick_capc(ef);
   if (!capc || (!pq && !nv)) return 0;
   ph_search_fn fn = pqr_m == -1 ? pick_kernel_pqs(capc, nv) : (pqr_m ? pick_kernel_pqr(capc, pqr_m) : pick_kernel(capc, nv));
   if (pqr_m == -2) fn = pick_kernel_lat(capc, nv);
   if (pqr_m == -4) fn = pick_kernel_f16(capc, nv);  // f16 store
+  if (pqr_m == -5) fn = pick_kernel_i8(capc, nv);   // i8 store
   if (pqr_m == -3) {
     capc = std::max(capc, 8);
     fn = pick_kernel_instr(capc, nv);
@@ -1164,7 +1180,8 @@ int ph_workspace_ensure(const phnsw_index *ix, PhWorkspace &ws, uint32_t ef, uin
   uint64_t max_nodes = 0;
   for (auto &l : ix->layers) max_nodes = std::max<uint64_t>(max_nodes, l.n_nodes);
   uint64_t words = (max_nodes + 31) / 32 + 1;
-  const int pqr = ix->store->half ? -4 : (ix->store->codes16 ? -1 : pick_pqr(ix->store, pick_capc(ef)));  // -1: shared-codebook store, -4: f16 store
+  // -1: shared-codebook store, -4: f16 store, -5: i8 store
+  const int pqr = ix->store->half ? -4 : (ix->store->i8 ? -5 : (ix->store->codes16 ? -1 : pick_pqr(ix->store, pick_capc(ef))));
   const bool pqg = ix->store->codes != nullptr && (ph_pq_global_tables() || pqr);  // (the register policy stages its table there)
   // the grid of every kernel a launch at this ef may pick: threshold_nn keeps queues of 512 at ef <= 256
   uint32_t slots = 0;
@@ -1313,18 +1330,18 @@ int ph_search_launch(const phnsw_index *ix, PhWorkspace &ws, PhSearchArgs &a, hi
   const bool pq = ix->store->codes != nullptr;
   const uint32_t ef_max = std::max(a.ef, a.cap_max);
   int capc = pick_capc(ef_max), nv = pq ? 0 : pick_nv(a.dist.nv4);
-  const bool f16 = ix->store->half != nullptr;
-  if (f16 && (a.knn_mode || a.out_index)) return ph_f16_unsupported(ix->store, "knn / threshold_nn / search_instrumented");
-  const int pqr = f16 ? 0 : (ix->store->codes16 ? -1 : pick_pqr(ix->store, capc));
+  const int conv = ix->store->half ? -4 : (ix->store->i8 ? -5 : 0);  // f16 / i8 store (the codes of ph_search_slots)
+  if (conv && (a.knn_mode || a.out_index)) return ph_search_only_unsupported(ix->store, "knn / threshold_nn / search_instrumented");
+  const int pqr = conv ? 0 : (ix->store->codes16 ? -1 : pick_pqr(ix->store, capc));
   const int capc_f32 = (!pq && !pqr) ? pick_capc_f32(ef_max, a.knn_mode == 2, nv) : capc;  // the throughput kernel's
   a.pq_tables = ws.pq_tables;
   a.pq_table_bytes = (uint32_t)ph_pq_lds_bytes(ix->store);
   ph_search_fn fn = nullptr;
   if (capc && (pq || nv)) fn = pqr == -1 ? pick_kernel_pqs(capc, nv) : (pqr ? pick_kernel_pqr(capc, pqr) : pick_kernel(capc_f32, nv));
-  if (f16) fn = (capc && nv) ? pick_kernel_f16(capc_f32, nv) : nullptr;
+  if (conv) fn = !(capc && nv) ? nullptr : (conv == -4 ? pick_kernel_f16(capc_f32, nv) : pick_kernel_i8(capc_f32, nv));
   // small batches of f32 queries: the latency kernels, when the shape has one
   int lat = 0;
-  if (!pq && !pqr && !f16 && a.nq <= PH_LATENCY_MAX && !getenv("PHNSW_NO_LAT") && pick_kernel_lat(capc, nv)) {
+  if (!pq && !pqr && !conv && a.nq <= PH_LATENCY_MAX && !getenv("PHNSW_NO_LAT") && pick_kernel_lat(capc, nv)) {
     fn = pick_kernel_lat(capc, nv);
     lat = -2;
     // one wave per SIMD leaves each wave a quarter of the CU's LDS: room for the table row of a far larger table layer
@@ -1367,7 +1384,7 @@ int ph_search_launch(const phnsw_index *ix, PhWorkspace &ws, PhSearchArgs &a, hi
   // per_cu (hence the grid) comes from the kernel without its visited table, as before: the hole is not handed to
   // one more search wave
   uint32_t slots = std::min<uint32_t>(
-      ph_search_slots(ef_max, a.dist.nv4, pq, pq_lds, lat ? lat : (f16 ? -4 : pqr), a.knn_mode == 2, &vis_slots,
+      ph_search_slots(ef_max, a.dist.nv4, pq, pq_lds, lat ? lat : (conv ? conv : pqr), a.knn_mode == 2, &vis_slots,
                       lat ? 0 : ph_tiny_beside_lds(ix, a)),
       ws.n_slots);
   uint32_t grid = (uint32_t)std::min<uint64_t>(slots, a.nq);

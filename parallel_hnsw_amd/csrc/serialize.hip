@@ -130,7 +130,7 @@ static bool parse_sp(const std::string &s, size_t from, phnsw_search_params *p) 
 
 extern "C" int phnsw_index_serialize(const phnsw_index *ix, const char *path) try {
   if (ix)
-    if (int rc = ph_f16_unsupported(ix->store, "phnsw_index_serialize")) return rc;
+    if (int rc = ph_search_only_unsupported(ix->store, "phnsw_index_serialize")) return rc;
   if (!ix || !path) {
     ph_set_error("phnsw_index_serialize: invalid argument");
     return PHNSW_E_INVALID;
@@ -195,7 +195,7 @@ extern "C" int phnsw_index_serialize(const phnsw_index *ix, const char *path) tr
 
 // deserialize_hnsw  serialize.rs:126-209 against an existing store (the C::Params role)
 extern "C" int phnsw_index_deserialize(phnsw_store *s, const char *path, phnsw_index **out) try {
-  if (int rc = ph_f16_unsupported(s, "phnsw_index_deserialize")) return rc;
+  if (int rc = ph_search_only_unsupported(s, "phnsw_index_deserialize")) return rc;
   if (!s || !path || !out) {
     ph_set_error("phnsw_index_deserialize: invalid argument");
     return PHNSW_E_INVALID;

@@ -693,7 +693,7 @@ extern "C" int phnsw_build_sharded_engine(const phnsw_shard_engine *e, const uin
 extern "C" int phnsw_build_sharded(phnsw_store *s, const uint64_t *vids, uint64_t n, const phnsw_build_params *bp,
                                    const phnsw_comm *comm, phnsw_progress_cb cb, void *user, phnsw_index **out,
                                    phnsw_sharded_stats *stats) try {
-  if (int rc = ph_f16_unsupported(s, "phnsw_build_sharded")) return rc;
+  if (int rc = ph_search_only_unsupported(s, "phnsw_build_sharded")) return rc;
   if (!s || !vids || !bp || !out || n == 0 || bp->order < 2) {
     ph_set_error("phnsw_build_sharded: invalid argument (need n > 0, order >= 2)");
     return PHNSW_E_INVALID;
@@ -737,7 +737,7 @@ extern "C" int phnsw_build_sharded(phnsw_store *s, const uint64_t *vids, uint64_
 extern "C" int phnsw_improve_index_sharded(phnsw_index *ix, const phnsw_build_params *bp, float last_recall,
                                            const phnsw_comm *comm, float *out_recall, phnsw_sharded_stats *stats) try {
   if (ix)
-    if (int rc = ph_f16_unsupported(ix->store, "phnsw_improve_index_sharded")) return rc;
+    if (int rc = ph_search_only_unsupported(ix->store, "phnsw_improve_index_sharded")) return rc;
   if (!ix || !bp) {
     ph_set_error("phnsw_improve_index_sharded: null index or parameters");
     return PHNSW_E_INVALID;

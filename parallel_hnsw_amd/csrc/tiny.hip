@@ -157,8 +157,8 @@ __device__ __forceinline__ void tiny_tile(const float4 *lds, const ph_f2 (&qv)[Q
   if constexpr (QT == 4) V += __shfl_xor(V, 1);
 }
 
-// R: how the stored rows are read (RowF32, or RowF16: the halves of an f16 store widened as they are staged, so the
-// tile pass below sees the f32 operands it always saw)
+// R: how the stored rows are read (RowF32, or RowF16 / RowI8: the halves of an f16 store widened, the codes of an i8
+// store dequantised, as they are staged, so the tile pass below sees the f32 operands it always saw)
 template <int NV, int QT, class R = RowF32>
 __global__ __launch_bounds__(256) void ph_tiny_table_kernel(PhTinyTableArgs a) {
   __shared__ float4 rows_lds[8 * NV * 64];
@@ -174,16 +174,19 @@ __global__ __launch_bounds__(256) void ph_tiny_table_kernel(PhTinyTableArgs a) {
     const uint32_t q = valid ? (a.order ? a.order[p] : p) : 0u;
     const float4 *src = nullptr;
     const typename R::chunk *srcs = nullptr;  // a stored query
+    typename R::aux sax = typename R::aux();
     if (valid) {
       if (a.queries)
         src = (const float4 *)(a.queries + (uint64_t)q * a.ldq);
-      else
+      else {
         srcs = R::row(a.dist, a.qids[q]);
+        sax = R::row_aux(srcs);
+      }
     }
 #pragma unroll
     for (int k = 0; k < NV; k++) {
       const uint32_t c = lane + 64u * k;
-      const float4 v = (valid && c < nv4) ? (src ? src[c] : R::widen(srcs[c])) : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 v = (valid && c < nv4) ? (src ? src[c] : R::widen(R::load(srcs, c), sax)) : make_float4(0.f, 0.f, 0.f, 0.f);
       qv[j / 2][k][0][j & 1] = v.x;
       qv[j / 2][k][1][j & 1] = v.y;
       qv[j / 2][k][2][j & 1] = v.z;
@@ -201,11 +204,12 @@ __global__ __launch_bounds__(256) void ph_tiny_table_kernel(PhTinyTableArgs a) {
       const uint32_t slot = 2u * w + u;
       const uint32_t rr = min(r0 + slot, a.tiny_n - 1u);
       const typename R::chunk *src = R::row(a.dist, a.tnodes[rr]);
+      const typename R::aux ax = R::row_aux(src);
 #pragma unroll
       for (int k = 0; k < NV; k++) {
         uint32_t c = lane + 64u * k;
         c = c < nv4 ? c : nv4 - 1u;
-        rows_lds[(slot * NV + k) * 64 + lane] = R::widen(src[c]);
+        rows_lds[(slot * NV + k) * 64 + lane] = R::widen(R::load(src, c), ax);
       }
     }
     __syncthreads();
@@ -258,6 +262,8 @@ __host__ __device__ constexpr uint32_t ph_rev5(uint32_t t) {
 struct PhTinyPackArgs {
   const float *vecs;     // stored rows
   const uint16_t *half;  // ... of an f16 store (vecs == nullptr): widened here, the packed operand is f32 either way
+  const uint8_t *i8;     // ... of an i8 store (vecs == nullptr): dequantised here
+  uint32_t ldb;
   uint32_t ld;
   const float *queries;  // raw query rows, or nullptr: rows are stored vectors
   uint32_t ldq;
@@ -277,6 +283,9 @@ __global__ void ph_tiny_pack_kernel(PhTinyPackArgs p) {
     const uint32_t e = p.order ? p.order[r] : r;
     if (!p.queries && p.half) {
       v = RowF16::widen(((const uint2 *)(p.half + (uint64_t)p.ids[e] * p.ld))[c]);
+    } else if (!p.queries && p.i8) {
+      const RowI8::chunk *src = (const RowI8::chunk *)(p.i8 + (uint64_t)p.ids[e] * p.ldb);
+      v = RowI8::widen(RowI8::load(src, c), RowI8::row_aux(src));
     } else {
       const float4 *src = p.queries ? (const float4 *)(p.queries + (uint64_t)e * p.ldq)
                                     : (const float4 *)(p.vecs + (uint64_t)p.ids[e] * p.ld);
@@ -448,7 +457,7 @@ bool ph_tiny_matrix_cores(const phnsw_index *ix) { return tiny_mfma_shape(ix->st
 // ef 300) it is tabulated either way.  PHNSW_TINY_MAX overrides.
 uint32_t ph_tiny_layer_count(const phnsw_index *ix, uint32_t n_layers, uint32_t ef) {
   const bool off = getenv("PHNSW_NO_TINY") != nullptr;  // tests compare both paths
-  if (off || (!ix->store->rows && !ix->store->half) || ix->store->ld / 4 > 384) return 0;
+  if (off || (!ix->store->rows && !ph_store_converted(ix->store)) || ix->store->ld / 4 > 384) return 0;
   const uint64_t per_ef = tiny_mfma_shape(ix->store->metric, ix->store->ld) ? 80ull : 48ull;
   uint64_t cap = std::min<uint64_t>(PH_TINY_MAX_NODES, per_ef * ef);
   if (const char *e = getenv("PHNSW_TINY_MAX"))
@@ -596,7 +605,7 @@ static int tiny_table(const phnsw_index *ix, PhWorkspace &ws, const PhDistArgs &
     PhTinyPackKey key;
     key.valid = !tiny_keep_off();
     key.nodes_epoch = ix->nodes_epoch;
-    key.vecs = dist.half ? (const void *)dist.half : (const void *)dist.vecs;
+    key.vecs = dist.half ? (const void *)dist.half : (dist.i8 ? (const void *)dist.i8 : (const void *)dist.vecs);
     key.tnodes = tnodes;
     key.ld = dist.ld;
     key.tn = tn;
@@ -611,6 +620,8 @@ static int tiny_table(const phnsw_index *ix, PhWorkspace &ws, const PhDistArgs &
     memset(&k, 0, sizeof(k));
     k.vecs = dist.vecs;
     k.half = dist.half;
+    k.i8 = dist.i8;
+    k.ldb = dist.ldb;
     k.ld = dist.ld;
     k.nv = (uint32_t)nv;
     k.queries = queries;
@@ -674,6 +685,13 @@ static int tiny_table(const phnsw_index *ix, PhWorkspace &ws, const PhDistArgs &
         hipLaunchKernelGGL((ph_tiny_table_kernel<3, 8, RowF16>), grid, dim3(256), 0, stream, t);
       else
         hipLaunchKernelGGL((ph_tiny_table_kernel<6, 4, RowF16>), grid, dim3(256), 0, stream, t);
+    } else if (dist.i8) {
+      if (nv == 1)
+        hipLaunchKernelGGL((ph_tiny_table_kernel<1, 8, RowI8>), grid, dim3(256), 0, stream, t);
+      else if (nv == 3)
+        hipLaunchKernelGGL((ph_tiny_table_kernel<3, 8, RowI8>), grid, dim3(256), 0, stream, t);
+      else
+        hipLaunchKernelGGL((ph_tiny_table_kernel<6, 4, RowI8>), grid, dim3(256), 0, stream, t);
     } else if (nv == 1)
       hipLaunchKernelGGL((ph_tiny_table_kernel<1, 8>), grid, dim3(256), 0, stream, t);
     else if (nv == 3)

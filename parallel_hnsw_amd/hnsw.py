@@ -233,6 +233,36 @@ class F16Store(VectorStore):
         return cls(store)
 
 
+class I8Store(VectorStore):
+    """int8 view of an f32 VectorStore (phnsw_store_create_i8): every row scalar-quantised with its own scale
+    (maxabs / 127), a quarter of the bytes per vector.  Distances dequantise (scale * code) and run the f32
+    arithmetic, so read() returns exactly the rows the searches see.  Search-only, like F16Store"""
+
+    def __init__(self, full):
+        h = C.c_void_p()
+        check(lib().phnsw_store_create_i8(full._h, C.byref(h)))
+        VectorStore.__init__(self, _handle=h, device=full.device)
+        self.full = full
+
+    @classmethod
+    def from_full(cls, store):
+        return cls(store)
+
+    def _read_i8(self):
+        codes = np.empty((self.n, self.dim), dtype=np.int8)
+        scales = np.empty(self.n, dtype=np.float32)
+        check(lib().phnsw_i8_read(self._h, _p(codes), _p(scales)))
+        return codes, scales
+
+    def codes(self):
+        """the stored codes [n, dim] int8"""
+        return self._read_i8()[0]
+
+    def scales(self):
+        """the rows' scales [n] f32"""
+        return self._read_i8()[1]
+
+
 class SharedPqStore(VectorStore):
     """the reference's quantizer shape (pq.rs:19-27, 61-81, 261-285): ONE codebook of up to 65535 centroid
     sub-vectors shared by all sub-spaces, u16 codes, quantize = top-1 of an HNSW search over the centroids"""
@@ -558,8 +588,9 @@ class Hnsw:
         return (ids, d, ln, st) if stats else (ids, d, ln)
 
     def search_batch_reranked(self, full, queries, sp=None, k=10):
-        """an index over an F16Store: search it, recompute every result's distance on the f32 store `full`, sort by
-        (distance, id), keep the best k (phnsw_f16_search_batch) -> ids[nq, k] u64, d[nq, k] f32, len[nq]"""
+        """an index over an F16Store or I8Store: search it, recompute every result's distance on the f32 store `full`,
+        sort by (distance, id), keep the best k (phnsw_f16_search_batch / phnsw_i8_search_batch)
+        -> ids[nq, k] u64, d[nq, k] f32, len[nq]"""
         sp = sp or SearchParameters()
         q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
         assert q.shape[1] == self.store.dim
@@ -567,16 +598,17 @@ class Hnsw:
         ids = np.empty((nq, k), dtype=np.uint64)
         d = np.empty((nq, k), dtype=np.float32)
         ln = np.zeros(nq, dtype=np.uint64)
-        check(lib().phnsw_f16_search_batch(self._h, full._h, _p(q), nq, C.byref(sp), k, _p(ids), _p(d), _p(ln)))
+        fn = lib().phnsw_i8_search_batch if isinstance(self.store, I8Store) else lib().phnsw_f16_search_batch
+        check(fn(self._h, full._h, _p(q), nq, C.byref(sp), k, _p(ids), _p(d), _p(ln)))
         return ids, d, ln
 
     def search_batch_reranked_device(self, full, nq, sp, k, queries, ldq, out_ids, out_d, out_len, status, out_stats=0,
                                      stream=0):
         """zero-copy form of search_batch_reranked (device pointers as ints, u32 ids, rows of number_of_candidates)"""
-        check(lib().phnsw_f16_search_batch_device(self._h, full._h, C.c_void_p(queries), ldq, nq, C.byref(sp), int(k),
-                                                  C.c_void_p(out_ids), C.c_void_p(out_d), C.c_void_p(out_len),
-                                                  C.c_void_p(out_stats or None), C.c_void_p(status),
-                                                  C.c_void_p(stream or None)))
+        fn = lib().phnsw_i8_search_batch_device if isinstance(self.store, I8Store) else lib().phnsw_f16_search_batch_device
+        check(fn(self._h, full._h, C.c_void_p(queries), ldq, nq, C.byref(sp), int(k), C.c_void_p(out_ids),
+                 C.c_void_p(out_d), C.c_void_p(out_len), C.c_void_p(out_stats or None), C.c_void_p(status),
+                 C.c_void_p(stream or None)))
 
     def search_instrumented_batch(self, queries=None, qids=None, sp=None):
         """Hnsw::search_instrumented (lib.rs:667-673) for many queries -> ids, d, len, index_distance[nq] u64"""

@@ -147,6 +147,10 @@ pub struct phnsw_shard_engine {
     pub layer_set_cells: Option<unsafe extern "C" fn(ctx: *mut c_void, pos: *const c_void) -> c_int>,
 }
 
+/// C's `int8_t` under its own name (the codes of an i8 store), as the `libc` crate spells it
+#[allow(non_camel_case_types)]
+pub type int8_t = i8;
+
 extern "C" {
     pub fn phnsw_default_search_params(sp: *mut phnsw_search_params);
     pub fn phnsw_default_build_params(bp: *mut phnsw_build_params);
@@ -320,6 +324,18 @@ extern "C" {
                                          sp: *const phnsw_search_params, k: u64, out_ids_dev: *mut u32,
                                          out_d_dev: *mut c_float, out_len_dev: *mut u32, out_stats_dev: *mut u32,
                                          status_dev: *mut u32, stream: *mut c_void) -> c_int;
+
+    // ---- int8 row store with a per-row scale: search over dequantised rows, re-rank on the f32 store
+    pub fn phnsw_store_create_i8(full: *const phnsw_store, out: *mut *mut phnsw_store) -> c_int;
+    pub fn phnsw_i8_read(s: *const phnsw_store, codes: *mut int8_t, scales: *mut c_float) -> c_int;
+    pub fn phnsw_i8_search_batch(ix: *const phnsw_index, full: *const phnsw_store, queries: *const c_float,
+                                 nq: u64, sp: *const phnsw_search_params, k: u64, out_ids: *mut u64,
+                                 out_d: *mut c_float, out_len: *mut u64) -> c_int;
+    pub fn phnsw_i8_search_batch_device(ix: *const phnsw_index, full: *const phnsw_store,
+                                        queries_dev: *const c_float, ldq: u32, nq: u64,
+                                        sp: *const phnsw_search_params, k: u64, out_ids_dev: *mut u32,
+                                        out_d_dev: *mut c_float, out_len_dev: *mut u32, out_stats_dev: *mut u32,
+                                        status_dev: *mut u32, stream: *mut c_void) -> c_int;
 
     // ---- on-disk interchange (serialize.rs:33-209)
     pub fn phnsw_index_serialize(ix: *const phnsw_index, path: *const c_char) -> c_int;

@@ -1,11 +1,11 @@
-"""f32 search against f16 search (and f16 search + f32 re-rank) on the plain bench.py workload: the 1M x 768
+"""f32 search against f16 and i8 search (and each + f32 re-rank) on the plain bench.py workload: the 1M x 768
 clustered "survey" set, the same seeds and build, ef 256 / probe_depth 8, 10 000-query batches, one stream and two
 streams (two batches in flight).  Every mode reports ms per step from device events after warm-up, recall@10
 against the exact top 10 of the f32 store, and the dispatches of its last descent.  One JSON line per mode.
 
-  python scripts/bench_f16.py --modes f32,f16,f16_rerank [--steps 20 --warmup 3] [--out FILE]
+  python scripts/bench_f16.py --modes f32,f16,f16_rerank,i8,i8_rerank [--steps 20 --warmup 3] [--out FILE]
 
-Mode f32 uses only calls that exist without the f16 store, so this file copied onto an older checkout gives the
+Mode f32 uses only calls that exist without the f16 and i8 stores, so this file copied onto an older checkout gives the
 baseline of the same run (pass --modes f32 there)."""
 import argparse
 import ctypes as C
@@ -21,7 +21,7 @@ sys.path.insert(0, ROOT)
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--modes", default="f32,f16,f16_rerank")
+    ap.add_argument("--modes", default="f32,f16,f16_rerank,i8,i8_rerank")
     ap.add_argument("--vectors", dest="n", type=int, default=1_000_000)
     ap.add_argument("--dim", type=int, default=768)
     ap.add_argument("--queries", dest="nq", type=int, default=10_000)
@@ -67,17 +67,19 @@ def main():
             self.status = torch.empty(nq, dtype=torch.int32, device=dev)
 
     lanes = [Lane(), Lane()]
-    f16_index = None
+    converted = {}  # "f16" / "i8" -> the index over that store, made when the first mode asks for it
+    row_bytes = {"f32": 4 * int(store.ld), "f16": 2 * int(store.ld), "i8": (4 + int(store.ld) + 15) // 16 * 16}
     out_lines = []
     for mode in args.modes.split(","):
-        if mode != "f32" and f16_index is None:
-            f16 = ph.F16Store.from_full(store)
-            f16_index = ph.Hnsw.from_layers(f16, [(l.nodes, l.neighbors) for l in index.layers], index.build_parameters)
-        ix = index if mode == "f32" else f16_index
+        kind = mode.split("_")[0]
+        if kind != "f32" and kind not in converted:
+            low = (ph.F16Store if kind == "f16" else ph.I8Store).from_full(store)
+            converted[kind] = ph.Hnsw.from_layers(low, [(l.nodes, l.neighbors) for l in index.layers], index.build_parameters)
+        ix = index if kind == "f32" else converted[kind]
 
         def launch(b, stream):
             ln, qs = lanes[b], qstores[b]
-            if mode == "f16_rerank":
+            if mode.endswith("_rerank"):
                 ix.search_batch_reranked_device(store, nq, sp, 10, qs.rows_dev, qs.ld, ln.ids.data_ptr(), ln.d.data_ptr(),
                                                 ln.len.data_ptr(), ln.status.data_ptr(), stream=stream.cuda_stream)
             else:
@@ -123,7 +125,7 @@ def main():
                 "one_stream_ms_per_step": {"runs": one, "median": float(np.median(one)), "spread": round(max(one) - min(one), 4)},
                 "two_streams_ms_per_step": {"runs": two, "median": float(np.median(two)), "spread": round(max(two) - min(two), 4)},
                 "recall_at_10": [round(r, 4) for r in recalls], "last_search_dispatches": disp,
-                "store_bytes": int(n) * int(store.ld) * (4 if mode == "f32" else 2),
+                "store_bytes": int(n) * row_bytes[kind],
                 "layers": [int(l.node_count()) for l in index.layers]}
         print(json.dumps(line), flush=True)
         out_lines.append(json.dumps(line))
