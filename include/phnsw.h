@@ -468,7 +468,7 @@ int phnsw_pq_search_batch_device(const phnsw_index *ix, const phnsw_store *full,
                                  uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
                                  uint32_t *out_stats_dev, uint32_t *status_dev, void *stream);
 
-/* ---- half-precision row store (f16.hip) ----
+/* ---- half-precision row store (rowstore.hip) ----
  * The rows of the f32 store `full`, rounded to IEEE binary16 (round to nearest even) by a device kernel: half the
  * bytes per stored vector and per gathered candidate.  n, dim, metric and device are those of `full`; a component
  * that is NaN or rounds to infinity in binary16 is PHNSW_E_INVALID.  A distance on the store widens the halves to f32
@@ -491,7 +491,7 @@ int phnsw_f16_search_batch_device(const phnsw_index *ix, const phnsw_store *full
                                   uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
                                   uint32_t *out_stats_dev, uint32_t *status_dev, void *stream);
 
-/* ---- int8 row store (i8.hip) ----
+/* ---- int8 row store (rowstore.hip) ----
  * The rows of the f32 store `full`, scalar-quantised per row and symmetrically by a device kernel:
  *   scale = maxabs(row) / 127.0f,  code_j = (int8) clamp(rintf(x_j / scale), -127, 127)   (IEEE f32 divisions),
  * a scale of 0 (a row of zeros, or a maxabs whose quotient underflows) gives codes 0.  A stored row is its f32 scale

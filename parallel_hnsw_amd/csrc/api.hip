@@ -302,7 +302,7 @@ extern "C" int phnsw_store_read(const phnsw_store *s, uint64_t first, uint64_t c
   if (s && out && ph_store_converted(s) && first + count <= s->n) {  // f16 / i8 store: the values the distance kernels see
     PH_HIP(hipSetDevice(s->device));
     if (!count) return 0;
-    return s->half ? ph_f16_store_read(s, first, count, out) : ph_i8_store_read(s, first, count, out);
+    return ph_converted_store_read(s, first, count, out);
   }
   if (!s || !out || !s->rows || first + count > s->n) {
     ph_set_error("phnsw_store_read: range out of bounds (or a product-quantised store: use phnsw_pq_read)");
@@ -321,8 +321,7 @@ extern "C" void phnsw_store_destroy(phnsw_store *s) {
   hipSetDevice(s->device);
   if (s->owns_rows && s->rows) hipFree(s->rows);
   if (s->codes) hipFree(s->codes);
-  if (s->half) hipFree(s->half);
-  if (s->i8) hipFree(s->i8);
+  if (s->packed) hipFree(s->packed);
   if (s->codes16) hipFree(s->codes16);
   if (s->centroid_index) phnsw_index_destroy(s->centroid_index);  // (releases its reference to centroid_store)
   if (s->centroid_store) phnsw_store_destroy(s->centroid_store);

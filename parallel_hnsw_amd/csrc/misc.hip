@@ -30,6 +30,29 @@ __global__ __launch_bounds__(64) void ph_distance_batch_kernel(PhDistArgs da, co
   }
 }
 
+// the row stores: one kernel per chunk count, whatever the row policy
+template <template <int, int> class D>
+static int distance_batch_rows(const phnsw_store *st, const PhDistArgs &da, const float *q_dev, uint32_t query_id,
+                               const uint32_t *ids_dev, uint32_t k, float *out_dev, hipStream_t s) {
+  const uint32_t nv4 = st->ld / 4;
+  const uint32_t blocks = std::min<uint32_t>((k + 63) / 64, 4096);
+#define PH_LAUNCH(NV)                                                                                               \
+  hipLaunchKernelGGL((ph_distance_batch_kernel<D<NV, 4>>), dim3(blocks), dim3(64), 0, s, da, q_dev, query_id, ids_dev, \
+                     k, st->n, out_dev)
+  if (nv4 <= 64)
+    PH_LAUNCH(1);
+  else if (nv4 <= 192)
+    PH_LAUNCH(3);
+  else if (nv4 <= 384)
+    PH_LAUNCH(6);
+  else {
+    ph_set_error("dim %u unsupported (max 1536)", st->dim);
+    return PHNSW_E_UNSUPPORTED;
+  }
+#undef PH_LAUNCH
+  return 0;
+}
+
 int ph_distance_batch(const phnsw_store *st, const float *q_dev, uint32_t query_id, const uint32_t *ids_dev, uint32_t k,
                       float *out_dev, hipStream_t s) {
   if (k == 0) return 0;
@@ -46,57 +69,14 @@ int ph_distance_batch(const phnsw_store *st, const float *q_dev, uint32_t query_
     uint32_t blocks = std::min<uint32_t>((k + 63) / 64, 256);
     hipLaunchKernelGGL(ph_distance_batch_kernel<DistPQ>, dim3(blocks), dim3(64), lds, s, da, q_dev, query_id, ids_dev,
                        k, st->n, out_dev);
-  } else if (st->half) {  // f16 store: the same chain over widened half rows
-    uint32_t nv4 = st->ld / 4;
-    uint32_t blocks = std::min<uint32_t>((k + 63) / 64, 4096);
-#define PH_LAUNCH_H(NV)                                                                                           \
-  hipLaunchKernelGGL(ph_distance_batch_kernel<DistF16<NV>>, dim3(blocks), dim3(64), 0, s, da, q_dev, query_id,   \
-                     ids_dev, k, st->n, out_dev)
-    if (nv4 <= 64)
-      PH_LAUNCH_H(1);
-    else if (nv4 <= 192)
-      PH_LAUNCH_H(3);
-    else if (nv4 <= 384)
-      PH_LAUNCH_H(6);
-    else {
-      ph_set_error("dim %u unsupported (max 1536)", st->dim);
-      return PHNSW_E_UNSUPPORTED;
-    }
-#undef PH_LAUNCH_H
-  } else if (st->i8) {  // i8 store: the same chain over dequantised int8 rows
-    uint32_t nv4 = st->ld / 4;
-    uint32_t blocks = std::min<uint32_t>((k + 63) / 64, 4096);
-#define PH_LAUNCH_B(NV)                                                                                          \
-  hipLaunchKernelGGL(ph_distance_batch_kernel<DistI8<NV>>, dim3(blocks), dim3(64), 0, s, da, q_dev, query_id,   \
-                     ids_dev, k, st->n, out_dev)
-    if (nv4 <= 64)
-      PH_LAUNCH_B(1);
-    else if (nv4 <= 192)
-      PH_LAUNCH_B(3);
-    else if (nv4 <= 384)
-      PH_LAUNCH_B(6);
-    else {
-      ph_set_error("dim %u unsupported (max 1536)", st->dim);
-      return PHNSW_E_UNSUPPORTED;
-    }
-#undef PH_LAUNCH_B
   } else {
-    uint32_t nv4 = st->ld / 4;
-    uint32_t blocks = std::min<uint32_t>((k + 63) / 64, 4096);
-#define PH_LAUNCH(NV)                                                                                             \
-  hipLaunchKernelGGL(ph_distance_batch_kernel<DistF32<NV>>, dim3(blocks), dim3(64), 0, s, da, q_dev, query_id,   \
-                     ids_dev, k, st->n, out_dev)
-    if (nv4 <= 64)
-      PH_LAUNCH(1);
-    else if (nv4 <= 192)
-      PH_LAUNCH(3);
-    else if (nv4 <= 384)
-      PH_LAUNCH(6);
-    else {
-      ph_set_error("dim %u unsupported (max 1536)", st->dim);
-      return PHNSW_E_UNSUPPORTED;
+    int rc = 0;
+    switch (st->kind) {  // the same chain over f32 rows, widened half rows, dequantised int8 rows
+      case PH_ROWS_F16: rc = distance_batch_rows<DistF16>(st, da, q_dev, query_id, ids_dev, k, out_dev, s); break;
+      case PH_ROWS_I8: rc = distance_batch_rows<DistI8>(st, da, q_dev, query_id, ids_dev, k, out_dev, s); break;
+      default: rc = distance_batch_rows<DistF32>(st, da, q_dev, query_id, ids_dev, k, out_dev, s); break;
     }
-#undef PH_LAUNCH
+    if (rc) return rc;
   }
   PH_HIP(hipGetLastError());
   return 0;

@@ -118,51 +118,50 @@ __device__ __forceinline__ void chain_partial2(const float4 (&x)[NV], const ph_f
 // scale * (float)code with the row's scale (ph_i8_dequant: one rounding, the value phnsw_store_read returns).  Either
 // way the chain sees the f32 values a row of the converted store would hold and everything behind the load is shared.
 // A policy names its chunk, what widen needs beside the chunk (aux: nothing, or the row's scale), and how both are
-// read from a row.  The raw chunks (and aux) of all U rows are requested before the first use and widened row by row:
-// a half row in flight costs half the registers, an int8 row a quarter.
+// read from a row; where the rows are (base, byte stride) is PhRows, the same for every kind.  The raw chunks (and
+// aux) of all U rows are requested before the first use and widened row by row: a half row in flight costs half the
+// registers, an int8 row a quarter.  A new row format is one more of these structs.
 struct RowNoAux {};
-struct RowF32 {
-  typedef float4 chunk;
-  typedef RowNoAux aux;
-  static constexpr uint32_t ELT = 4;  // bytes per component
-  static __device__ __forceinline__ float4 widen(const float4 &v) { return v; }
-  static __device__ __forceinline__ float4 widen(const float4 &v, const aux &) { return v; }
-  static __device__ __forceinline__ aux row_aux(const chunk *) { return aux(); }
-  static __device__ __forceinline__ chunk load(const chunk *row, uint32_t c) { return row[c]; }
-  static __device__ __forceinline__ const chunk *row(const PhDistArgs &d, uint32_t vid) {
-    return (const chunk *)(d.vecs + (uint64_t)vid * d.ld);
+template <class C>
+struct RowBase {
+  typedef C chunk;
+  static __device__ __forceinline__ const C *row(const PhRows &r, uint32_t vid) {
+    return (const C *)((const char *)r.base + (uint64_t)vid * r.stride);
   }
 };
-struct RowF16 {
-  typedef uint2 chunk;
+struct RowF32 : RowBase<float4> {
   typedef RowNoAux aux;
-  static constexpr uint32_t ELT = 2;
-  static __device__ __forceinline__ const chunk *row(const PhDistArgs &d, uint32_t vid) {
-    return (const chunk *)(d.half + (uint64_t)vid * d.ldh);
-  }
+  static constexpr int KIND = PH_ROWS_F32;
   static __device__ __forceinline__ aux row_aux(const chunk *) { return aux(); }
   static __device__ __forceinline__ chunk load(const chunk *row, uint32_t c) { return row[c]; }
-  static __device__ __forceinline__ float4 widen(const uint2 &v) {
+  static __device__ __forceinline__ float4 widen(const float4 &v, const aux &) { return v; }
+  // the same address counted in components, the way a raw query is addressed: the search kernels then keep one load
+  // for both kinds of query (in bytes, <8, DistF32<1,4>> took 129 VGPRs instead of 125 and lost a wave per SIMD)
+  static __device__ __forceinline__ const chunk *row(const PhRows &r, uint32_t vid) {
+    return (const chunk *)((const float *)r.base + (uint64_t)vid * (r.stride / 4u));
+  }
+};
+struct RowF16 : RowBase<uint2> {
+  typedef RowNoAux aux;
+  static constexpr int KIND = PH_ROWS_F16;
+  static __device__ __forceinline__ aux row_aux(const chunk *) { return aux(); }
+  static __device__ __forceinline__ chunk load(const chunk *row, uint32_t c) { return row[c]; }
+  static __device__ __forceinline__ float4 widen(const uint2 &v, const aux &) {
     return make_float4(__half2float(__ushort_as_half((unsigned short)(v.x & 0xFFFFu))),
                        __half2float(__ushort_as_half((unsigned short)(v.x >> 16))),
                        __half2float(__ushort_as_half((unsigned short)(v.y & 0xFFFFu))),
                        __half2float(__ushort_as_half((unsigned short)(v.y >> 16))));
   }
-  static __device__ __forceinline__ float4 widen(const uint2 &v, const aux &) { return widen(v); }
 };
 // THE dequantised component of an i8 store: one IEEE f32 multiply (never contracted into the chain's fma).  The
 // distance kernels, phnsw_store_read, the dense table's pack and staging steps and the cells' row gather all call it.
 __device__ __forceinline__ float ph_i8_dequant(float scale, int code) { return __fmul_rn(scale, (float)code); }
-// A stored row is ldb bytes (a multiple of 16): its f32 scale, then ld int8 codes, then padding.  The scale sits at
+// A stored row is a multiple of 16 bytes: its f32 scale, then ld int8 codes, then padding.  The scale sits at
 // the head, in the 128-byte line the row's first chunks come from; the row pointer is wave-uniform in the distance
 // kernels, so the scale is one same-address (scalar) load per row, not one request per lane.
-struct RowI8 {
-  typedef uint32_t chunk;  // four codes
-  typedef float aux;       // the row's scale
-  static constexpr uint32_t ELT = 1;  // batch_distances is handed the row's byte stride
-  static __device__ __forceinline__ const chunk *row(const PhDistArgs &d, uint32_t vid) {
-    return (const chunk *)(d.i8 + (uint64_t)vid * d.ldb);
-  }
+struct RowI8 : RowBase<uint32_t> {  // four codes
+  typedef float aux;                // the row's scale
+  static constexpr int KIND = PH_ROWS_I8;
   static __device__ __forceinline__ aux row_aux(const chunk *row) { return __uint_as_float(row[0]); }
   static __device__ __forceinline__ chunk load(const chunk *row, uint32_t c) { return row[1u + c]; }
   static __device__ __forceinline__ float4 widen(const uint32_t &v, const aux &s) {
@@ -224,9 +223,9 @@ __device__ __forceinline__ float row_partial(const float4 *__restrict__ row, con
 // distances of the query to the (up to 64) rows whose ids sit in the lanes flagged by
 // `mask`; 4 rows in flight; the result lands in the lane that held the id
 template <int NV, int U, class R = RowF32>
-__device__ __forceinline__ float batch_distances(const void *__restrict__ vecs, uint32_t ld, uint32_t nv4, int metric,
+__device__ __forceinline__ float batch_distances(const void *__restrict__ vecs, uint32_t stride, uint32_t nv4, int metric,
                                                  bool l2, const float4 (&qv)[NV], uint64_t mask, uint32_t vid,
-                                                 uint32_t lane);
+                                                 uint32_t lane);  // stride: bytes per row
 
 __device__ __forceinline__ float finalize_metric(float r, int metric) {
   if (metric == PHNSW_METRIC_COSINE_HALF) return (1.0f - r) / 2.0f;  // bigvec.rs:52
@@ -324,7 +323,7 @@ __device__ __forceinline__ void distance_round(const void *__restrict__ vecs, ui
 }
 
 template <int NV, int U, class R>
-__device__ __forceinline__ float batch_distances(const void *__restrict__ vecs, uint32_t ld, uint32_t nv4, int metric,
+__device__ __forceinline__ float batch_distances(const void *__restrict__ vecs, uint32_t stride, uint32_t nv4, int metric,
                                                  bool l2, const float4 (&qv)[NV], uint64_t mask, uint32_t vid,
                                                  uint32_t lane) {
   // U rows in flight per wave: 4 for throughput, 8 (191 VGPRs, 2 waves/SIMD) where the queues of ef <= 256 leave the
@@ -338,7 +337,7 @@ __device__ __forceinline__ float batch_distances(const void *__restrict__ vecs, 
   // address arithmetic of a row is one v_mad_u64_u32 per lane instead of scalar multiplies per row.
   const bool cand = (mask >> lane) & 1ull;
   const uint32_t myrank = __popcll(mask & lanemask_lt(lane));
-  const uint64_t off = (uint64_t)vid * ((uint64_t)ld * R::ELT);
+  const uint64_t off = (uint64_t)vid * (uint64_t)stride;
   const int dst = (int)((cand ? myrank : 63u) << 2);  // non-candidates park in lane 63 (never read: m <= 63 there)
   uint32_t olo = (uint32_t)__builtin_amdgcn_ds_permute(dst, (int)(uint32_t)off);
   uint32_t ohi = (uint32_t)__builtin_amdgcn_ds_permute(dst, (int)(uint32_t)(off >> 32));
@@ -373,7 +372,7 @@ __device__ __forceinline__ float batch_distances(const void *__restrict__ vecs, 
 
 // ------------------------------------------------------------------ distance policies
 // The traversal kernels are written once and instantiated per policy:
-//   DistF32<NV>: the query in registers, candidates = f32 rows (wave per row, 4 in flight)
+//   DistF32 / DistF16 / DistI8<NV>: the query in registers, candidates = stored rows (wave per row, 4 in flight)
 //   DistPQ:      product-quantised store: a per-query table T[m][ksub] in LDS
 //                (T[j][k] = <q_sub_j, c_jk> or |q_sub_j - c_jk|^2), candidates = u8 code
 //                rows, one LANE per candidate, distance = sum_j T[j][code_j] added in j order.
@@ -394,33 +393,16 @@ struct dist_is_none<DistNone> {
   static constexpr bool value = true;
 };
 
-template <int NV, int U = 4>
-struct DistF32 {
+// DistRows<NV, U, R>: the query in registers, candidates = stored rows read through the row policy R (wave per row,
+// U in flight).  A stored query is its widened / dequantised row; a candidate's chunk is widened in registers.  Same
+// chain, same butterfly, same compaction for every R: the bits are those of the f32 search over the rows
+// phnsw_store_read returns.
+template <int NV, int U, class R>
+struct DistRows {
   static constexpr bool GLOBAL_TABLE = false;
   static constexpr bool EARLY = false;
-  float4 qv[NV];
-  __device__ __forceinline__ void prepare_raw(const PhDistArgs &d, const float *q, float *, uint32_t lane) {
-#pragma unroll
-    for (int k = 0; k < NV; k++) {
-      uint32_t c = lane + 64u * k;
-      qv[k] = (c < d.nv4) ? ((const float4 *)q)[c] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  }
-  __device__ __forceinline__ void prepare_stored(const PhDistArgs &d, uint32_t vid, float *lds, uint32_t lane) {
-    prepare_raw(d, d.vecs + (uint64_t)vid * d.ld, lds, lane);
-  }
-  __device__ __forceinline__ float batch(const PhDistArgs &d, uint64_t mask, uint32_t vid, uint32_t lane) const {
-    return batch_distances<NV, U>(d.vecs, d.ld, d.nv4, d.metric, d.metric == PHNSW_METRIC_L2, qv, mask, vid, lane);
-  }
-};
-
-// DistF16<NV, U>: DistF32 over a half-precision row store.  The query stays f32 in registers; a stored query is its
-// widened row; a candidate's chunk is 8 bytes, widened in registers (RowF16).  Same chain, same butterfly, same
-// compaction: the bits are those of DistF32 on the store of widened rows.
-template <int NV, int U = 4>
-struct DistF16 {
-  static constexpr bool GLOBAL_TABLE = false;
-  static constexpr bool EARLY = false;
+  static constexpr bool ROW_STORE = true;
+  static constexpr int CHUNKS = NV, ROWS_IN_FLIGHT = U;
   float4 qv[NV];
   __device__ __forceinline__ void prepare_raw(const PhDistArgs &d, const float *q, float *, uint32_t lane) {
 #pragma unroll
@@ -430,46 +412,27 @@ struct DistF16 {
     }
   }
   __device__ __forceinline__ void prepare_stored(const PhDistArgs &d, uint32_t vid, float *, uint32_t lane) {
-    const uint2 *row = (const uint2 *)(d.half + (uint64_t)vid * d.ldh);
+    const typename R::chunk *row = R::row(d.rows, vid);
+    const typename R::aux ax = R::row_aux(row);
 #pragma unroll
     for (int k = 0; k < NV; k++) {
       uint32_t c = lane + 64u * k;
-      qv[k] = (c < d.nv4) ? RowF16::widen(row[c]) : make_float4(0.f, 0.f, 0.f, 0.f);
+      qv[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (c < d.nv4) qv[k] = R::widen(R::load(row, c), ax);  // (a store, not a select: see RowF32::row)
     }
   }
   __device__ __forceinline__ float batch(const PhDistArgs &d, uint64_t mask, uint32_t vid, uint32_t lane) const {
-    return batch_distances<NV, U, RowF16>(d.half, d.ldh, d.nv4, d.metric, d.metric == PHNSW_METRIC_L2, qv, mask, vid, lane);
+    return batch_distances<NV, U, R>(d.rows.base, d.rows.stride, d.nv4, d.metric, d.metric == PHNSW_METRIC_L2, qv, mask, vid,
+                                     lane);
   }
 };
-
-// DistI8<NV, U>: DistF32 over an int8 row store with one f32 scale per row.  The query stays f32 in registers; a stored
-// query is its dequantised row; a candidate's chunk is 4 bytes, dequantised in registers (RowI8).  Same chain, same
-// butterfly, same compaction: the bits are those of DistF32 on the store of dequantised rows.
+// the three row stores: derived structs, not aliases, so that the kernels keep the names they are profiled under
 template <int NV, int U = 4>
-struct DistI8 {
-  static constexpr bool GLOBAL_TABLE = false;
-  static constexpr bool EARLY = false;
-  float4 qv[NV];
-  __device__ __forceinline__ void prepare_raw(const PhDistArgs &d, const float *q, float *, uint32_t lane) {
-#pragma unroll
-    for (int k = 0; k < NV; k++) {
-      uint32_t c = lane + 64u * k;
-      qv[k] = (c < d.nv4) ? ((const float4 *)q)[c] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  }
-  __device__ __forceinline__ void prepare_stored(const PhDistArgs &d, uint32_t vid, float *, uint32_t lane) {
-    const RowI8::chunk *row = RowI8::row(d, vid);
-    const float s = RowI8::row_aux(row);
-#pragma unroll
-    for (int k = 0; k < NV; k++) {
-      uint32_t c = lane + 64u * k;
-      qv[k] = (c < d.nv4) ? RowI8::widen(RowI8::load(row, c), s) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  }
-  __device__ __forceinline__ float batch(const PhDistArgs &d, uint64_t mask, uint32_t vid, uint32_t lane) const {
-    return batch_distances<NV, U, RowI8>(d.i8, d.ldb, d.nv4, d.metric, d.metric == PHNSW_METRIC_L2, qv, mask, vid, lane);
-  }
-};
+struct DistF32 : DistRows<NV, U, RowF32> {};
+template <int NV, int U = 4>
+struct DistF16 : DistRows<NV, U, RowF16> {};
+template <int NV, int U = 4>
+struct DistI8 : DistRows<NV, U, RowI8> {};
 
 // f32 -> IEEE binary16 bits, round to nearest even, written with integer operations so that
 // the oracle's C version produces the same bits (no dependence on a denormal mode)

@@ -59,26 +59,44 @@ struct PhLayerHost {
   uint32_t ord_first = 0, ord_count = 0;
 };
 
-// what a distance evaluation needs: the f32 store, or -- for a product-quantised store --
+// How a store keeps its vectors.  The three row kinds are searched by the same kernels through a row policy
+// (RowF32 / RowF16 / RowI8, phnsw_device.h); f16 and i8 are the converted, search-only stores of rowstore.hip.
+enum PhRowKind : int {
+  PH_ROWS_F32 = 0,    // [n][ld] f32
+  PH_ROWS_F16,        // [n][ld] IEEE binary16 in component order: rows start on 8-byte boundaries
+  PH_ROWS_I8,         // n rows of 4 + ld bytes rounded up to a multiple of 16: the f32 scale, then ld int8 codes
+  PH_ROWS_PQ,         // u8 codes over per-sub-space codebooks (pq.hip)
+  PH_ROWS_PQ_SHARED,  // u16 codes over one shared codebook (pq.hip)
+};
+static inline bool ph_rows_converted(int kind) { return kind == PH_ROWS_F16 || kind == PH_ROWS_I8; }
+static inline const char *ph_rows_name(int kind) {
+  static const char *const names[] = {"f32", "f16", "i8", "product-quantised", "shared-codebook product-quantised"};
+  return names[kind];
+}
+// where the rows of a row kind are: one base pointer, one stride in bytes
+struct PhRows {
+  const void *base;  // nullptr for a PQ store
+  uint32_t stride;   // bytes from one row to the next
+  int kind;          // PhRowKind
+};
+
+// what a distance evaluation needs: the rows of an f32, f16 or i8 store, or -- for a product-quantised store --
 // code rows + per-subspace codebooks (pq.hip)
 struct PhDistArgs {
-  const float *vecs;  // [n][ld] f32 rows (nullptr for a PQ store)
-  uint32_t ld, nv4;
+  PhRows rows;
+  uint32_t ld, nv4;  // components per row (padded), float4 chunks per row
   int metric;
   const uint8_t *codes;   // [n][m] u8 codes (PQ store)
   const uint16_t *codes16;  // [n][m] u16 codes over ONE shared codebook [ksub][dsub] (the reference's shape, pq.rs:19-27)
   const float *codebook;  // [m][ksub][dsub]
   uint32_t m, ksub, dsub;
   uint32_t table_f16;  // 1: the per-query table holds IEEE half values (2 bytes per entry)
-  const uint16_t *half;  // [n][ldh] IEEE binary16 rows in component order (f16 store, f16.hip); vecs == nullptr then
-  uint32_t ldh;          // halves per row (== ld: rows start on 8-byte boundaries)
-  const uint8_t *i8;     // [n] rows of ldb bytes: f32 scale, then ld int8 codes (i8 store, i8.hip); vecs == nullptr then
-  uint32_t ldb;          // bytes per row: 4 + ld rounded up to a multiple of 16
 };
 
 struct phnsw_store {
   int device = 0;
-  float *rows = nullptr;  // [n][ld] flat, HBM
+  int kind = PH_ROWS_F32;  // PhRowKind: what the store is, whatever its size (an empty store has no allocation to test)
+  float *rows = nullptr;   // [n][ld] flat, HBM: the f32 rows, nullptr for every other kind
   // product-quantised store (phnsw_store_create_pq): rows == nullptr, dim/ld describe the
   // full vectors a query has
   uint8_t *codes = nullptr;
@@ -89,14 +107,11 @@ struct phnsw_store {
   float *codebook = nullptr;
   uint32_t pq_m = 0, pq_ksub = 0, pq_dsub = 0;
   uint32_t pq_table_f16 = 0;
-  // half-precision store (phnsw_store_create_f16, f16.hip): rows == nullptr, half = [n][ldh] binary16 rows; a distance
-  // widens them to f32 (exact) and runs the f32 chain.  Search-only: see ph_search_only_unsupported.
-  uint16_t *half = nullptr;
-  uint32_t ldh = 0;
-  // int8 store (phnsw_store_create_i8, i8.hip): rows == nullptr, i8 = n rows of ldb bytes, each its f32 scale followed
-  // by ld int8 codes; a distance dequantises them (scale * code) and runs the f32 chain.  Search-only as well.
-  uint8_t *i8 = nullptr;
-  uint32_t ldb = 0;
+  // converted store (phnsw_store_create_f16 / _i8, rowstore.hip): rows == nullptr, packed = n rows of packed_stride
+  // bytes in the layout of its kind; a distance widens / dequantises them to f32 and runs the f32 chain.  Search-only:
+  // see ph_search_only_unsupported.
+  void *packed = nullptr;
+  uint32_t packed_stride = 0;
   // coarse cells of the locality schedule (bruteforce.hip): anchor rows + their chain ranks
   float *anchors = nullptr;
   uint32_t *anchor_rank = nullptr;
@@ -122,7 +137,7 @@ struct PhTinyPrepKey {
 struct PhTinyPackKey {
   bool valid = false;
   uint64_t nodes_epoch = 0;
-  const void *vecs = nullptr, *tnodes = nullptr;
+  const void *vecs = nullptr, *tnodes = nullptr;  // vecs: the base pointer of the stored rows (PhRows::base)
   uint32_t ld = 0, tn = 0, nv = 0;
 };
 
@@ -353,19 +368,12 @@ void ph_store_anchors_free(phnsw_store *s);
 int ph_order_by_keys_device(const uint32_t *keys, uint32_t n, uint32_t *order_out, hipStream_t st);
 int ph_layer_range_order(PhLayerHost &L, uint32_t first, uint32_t count, const uint32_t **out);
 
-// f16 store (f16.hip): rows of `ids_dev` (nullptr: rows first .. first + cnt) widened into [cnt][ld] f32 rows; a
-// range of the store widened into a dense host array
-int ph_f16_gather_rows(const phnsw_store *s, const uint32_t *ids_dev, uint32_t first, uint32_t cnt, float *out_dev);
-int ph_f16_store_read(const phnsw_store *s, uint64_t first, uint64_t count, float *out);
-// i8 store (i8.hip): the same two, dequantising
-int ph_i8_gather_rows(const phnsw_store *s, const uint32_t *ids_dev, uint32_t first, uint32_t cnt, float *out_dev);
-int ph_i8_store_read(const phnsw_store *s, uint64_t first, uint64_t count, float *out);
 // a search-only row store (f16 or i8): searched like the f32 store, its rows converted to f32 where a GEMM or a host reads them
-static inline bool ph_store_converted(const phnsw_store *s) { return s->half || s->i8; }
-static inline int ph_converted_gather_rows(const phnsw_store *s, const uint32_t *ids_dev, uint32_t first, uint32_t cnt,
-                                           float *out_dev) {
-  return s->half ? ph_f16_gather_rows(s, ids_dev, first, cnt, out_dev) : ph_i8_gather_rows(s, ids_dev, first, cnt, out_dev);
-}
+static inline bool ph_store_converted(const phnsw_store *s) { return ph_rows_converted(s->kind); }
+// converted stores (rowstore.hip): rows of `ids_dev` (nullptr: rows first .. first + cnt) widened / dequantised into
+// [cnt][ld] f32 rows; a range of the store converted into a dense host array
+int ph_converted_gather_rows(const phnsw_store *s, const uint32_t *ids_dev, uint32_t first, uint32_t cnt, float *out_dev);
+int ph_converted_store_read(const phnsw_store *s, uint64_t first, uint64_t count, float *out);
 
 // dense top layers (tiny.hip): decides how many leading layers of the launch described by `a` run
 // against a distance table, fills a.tiny_* and enqueues the table kernels for launch positions
@@ -393,13 +401,17 @@ void ph_workspace_order_free(PhWorkspace &ws);                                  
 #define PH_TWO_LAUNCH_MIN 32768u  // batches at least this large descend in two launches
 int ph_workspace_ensure(const phnsw_index *ix, PhWorkspace &ws, uint32_t ef, uint32_t ovf_cap);
 void ph_workspace_free(PhWorkspace &ws);
-// resident waves of a search launch; grows: threshold_nn (the queue may double); vis_slots: the LDS visited table
 size_t ph_tiny_beside_lds(const phnsw_index *ix, const PhSearchArgs &a);  // LDS of one table block that runs beside a search (0: none)
-uint32_t ph_search_slots(uint32_t ef, uint32_t nv4, bool pq, size_t pq_lds, int pqr_m = 0, bool grows = false,
-                         uint32_t *vis_slots = nullptr, size_t hole = 0);
+static inline PhRows ph_store_rows(const phnsw_store *s) {
+  PhRows r;
+  r.base = ph_store_converted(s) ? (const void *)s->packed : (const void *)s->rows;
+  r.stride = ph_store_converted(s) ? s->packed_stride : s->ld * 4u;
+  r.kind = s->kind;
+  return r;
+}
 static inline PhDistArgs ph_dist_args(const phnsw_store *s) {
   PhDistArgs d;
-  d.vecs = s->rows;
+  d.rows = ph_store_rows(s);
   d.ld = s->ld;
   d.nv4 = s->ld / 4;
   d.metric = s->metric;
@@ -410,19 +422,15 @@ static inline PhDistArgs ph_dist_args(const phnsw_store *s) {
   d.ksub = s->pq_ksub;
   d.dsub = s->pq_dsub;
   d.table_f16 = s->pq_table_f16;
-  d.half = s->half;
-  d.ldh = s->ldh;
-  d.i8 = s->i8;
-  d.ldb = s->ldb;
   return d;
 }
 // bytes of one stored row as the search gathers it
-static inline uint32_t ph_row_bytes(const phnsw_store *s) { return s->i8 ? s->ldb : (s->half ? s->ldh * 2u : s->ld * 4u); }
+static inline uint32_t ph_row_bytes(const phnsw_store *s) { return ph_store_rows(s).stride; }
 // an f16 or i8 store serves searches only: every other entry point refuses it by name
 static inline int ph_search_only_unsupported(const phnsw_store *s, const char *call) {
   if (!s || !ph_store_converted(s)) return 0;
   ph_set_error("%s: not supported on an %s store or an index over one (search-only; use the f32 store)", call,
-               s->half ? "f16" : "i8");
+               ph_rows_name(s->kind));
   return PHNSW_E_UNSUPPORTED;
 }
 // the batched search keeps PQ tables in global memory unless PHNSW_PQ_TABLE=lds

@@ -239,6 +239,7 @@ extern "C" int phnsw_store_create_pq_sharded(phnsw_store *full, uint32_t m, uint
   s->dim = full->dim;
   s->ld = full->ld;
   s->metric = full->metric;
+  s->kind = PH_ROWS_PQ;
   s->rows = nullptr;
   s->pq_m = m;
   s->pq_ksub = ksub;
@@ -434,6 +435,7 @@ extern "C" int phnsw_store_create_pq_shared_sharded(phnsw_store *full, uint32_t 
   s->dim = full->dim;
   s->ld = full->ld;
   s->metric = full->metric;
+  s->kind = PH_ROWS_PQ_SHARED;
   s->rows = nullptr;
   s->pq_m = m;
   s->pq_ksub = C;
@@ -778,7 +780,7 @@ extern "C" int phnsw_pq_search_batch_device(const phnsw_index *ix, const phnsw_s
 // sorted by (distance, id) and the best k are kept.
 
 // the sorted rows [nq][ef] cut to k entries each, in place: entries k .. ef - 1 become empty, len = min(len, k)
-__global__ void ph_f16_trim_kernel(uint32_t *ids, float *d, uint32_t *len, uint32_t ef, uint32_t k, uint64_t nq) {
+__global__ void ph_rerank_trim_kernel(uint32_t *ids, float *d, uint32_t *len, uint32_t ef, uint32_t k, uint64_t nq) {
   const uint64_t total = nq * ef;
   for (uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; x < total; x += (uint64_t)gridDim.x * blockDim.x) {
     const uint64_t r = x / ef;
@@ -791,7 +793,7 @@ __global__ void ph_f16_trim_kernel(uint32_t *ids, float *d, uint32_t *len, uint3
   }
 }
 // ... and the leading k of each row as u64 ids + distances, [nq][k]
-__global__ void ph_f16_take_kernel(const uint32_t *ids, const float *d, uint32_t ef, uint32_t k, uint64_t nq, uint64_t *ids64,
+__global__ void ph_rerank_take_kernel(const uint32_t *ids, const float *d, uint32_t ef, uint32_t k, uint64_t nq, uint64_t *ids64,
                                    float *dk) {
   const uint64_t total = nq * k;
   for (uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; x < total; x += (uint64_t)gridDim.x * blockDim.x) {
@@ -802,15 +804,15 @@ __global__ void ph_f16_take_kernel(const uint32_t *ids, const float *d, uint32_t
   }
 }
 
-// `i8`: which of the two stores the entry point serves (the f16 calls refuse an i8 index and the other way round)
-static int rerank_check(const char *call, bool i8, const phnsw_index *ix, const phnsw_store *full,
+// `kind`: the converted store the entry point serves (the f16 calls refuse an i8 index and the other way round)
+static int rerank_check(const char *call, int kind, const phnsw_index *ix, const phnsw_store *full,
                         const phnsw_search_params *sp, uint64_t nq, uint64_t k) {
-  if (!ix || !full || !sp || !(i8 ? (const void *)ix->store->i8 : (const void *)ix->store->half) || !full->rows || full->n != ix->store->n || full->dim != ix->store->dim ||
+  if (!ix || !full || !sp || ix->store->kind != kind || !full->rows || full->n != ix->store->n || full->dim != ix->store->dim ||
       full->metric != ix->store->metric || full->device != ix->store->device || nq > 0xFFFFFFFFull ||
       sp->number_of_candidates == 0 || sp->number_of_candidates > 1024 || sp->probe_depth == 0 || k == 0 ||
       k > sp->number_of_candidates) {
     ph_set_error("%s: need an index over an %s store, the f32 store of the same n / dim / metric / device, valid "
-                 "parameters and 1 <= k <= number_of_candidates", call, i8 ? "i8" : "f16");
+                 "parameters and 1 <= k <= number_of_candidates", call, ph_rows_name(kind));
     return PHNSW_E_INVALID;
   }
   return 0;
@@ -834,7 +836,7 @@ static int rerank_launch(const phnsw_store *full, const float *queries_dev, uint
   }
   PH_HIP(hipGetLastError());
   if (k < ef) {
-    hipLaunchKernelGGL(ph_f16_trim_kernel, dim3((uint32_t)std::min<uint64_t>((nq * ef + 255) / 256, 4096)), dim3(256), 0, st, ids,
+    hipLaunchKernelGGL(ph_rerank_trim_kernel, dim3((uint32_t)std::min<uint64_t>((nq * ef + 255) / 256, 4096)), dim3(256), 0, st, ids,
                        d, len, ef, k, nq);
     PH_HIP(hipGetLastError());
   }
@@ -843,11 +845,11 @@ static int rerank_launch(const phnsw_store *full, const float *queries_dev, uint
 
 // zero-copy form: the search launches, the re-rank and the cut to k enqueued on `stream`, no synchronisation.  The
 // result rows keep the search's stride (number_of_candidates entries per query): the first min(len, k) are live.
-static int reranked_search_device(const char *call, bool i8, const phnsw_index *ix, const phnsw_store *full,
+static int reranked_search_device(const char *call, int kind, const phnsw_index *ix, const phnsw_store *full,
                                   const float *queries_dev, uint32_t ldq, uint64_t nq, const phnsw_search_params *sp,
                                   uint64_t k, uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
                                   uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) {
-  PH_TRYQ(rerank_check(call, i8, ix, full, sp, nq, k));
+  PH_TRYQ(rerank_check(call, kind, ix, full, sp, nq, k));
   if (!queries_dev || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev || ldq < full->ld || (ldq % 4) ||
       ((uintptr_t)queries_dev % 16)) {
     ph_set_error("%s: invalid argument (queries need ldq >= store ld, multiple of 4, 16-byte base)", call);
@@ -862,10 +864,10 @@ static int reranked_search_device(const char *call, bool i8, const phnsw_index *
 }
 
 // host form: out_ids / out_d are [nq][k], out_len[q] = min(results of query q, k)
-static int reranked_search_host(const char *call, bool i8, const phnsw_index *ix, const phnsw_store *full,
+static int reranked_search_host(const char *call, int kind, const phnsw_index *ix, const phnsw_store *full,
                                 const float *queries, uint64_t nq, const phnsw_search_params *sp, uint64_t k,
                                 uint64_t *out_ids, float *out_d, uint64_t *out_len) {
-  PH_TRYQ(rerank_check(call, i8, ix, full, sp, nq, k));
+  PH_TRYQ(rerank_check(call, kind, ix, full, sp, nq, k));
   if ((!queries || !out_ids || !out_d || !out_len) && nq) {
     ph_set_error("%s: queries and outputs must not be NULL", call);
     return PHNSW_E_INVALID;
@@ -891,7 +893,7 @@ static int reranked_search_host(const char *call, bool i8, const phnsw_index *ix
   if (!rc) rc = ph_search_device(ix, qd, full->ld, nullptr, nq, sp, 0, nullptr, oid, od, olen, nullptr, ostat, 0, 0, 0);
   if (!rc) rc = rerank_launch(full, qd, full->ld, nq, ef, (uint32_t)k, olen, oid, od, 0);
   if (!rc) {
-    hipLaunchKernelGGL(ph_f16_take_kernel, dim3((uint32_t)std::min<uint64_t>((nq * k + 255) / 256, 4096)), dim3(256), 0, 0, oid,
+    hipLaunchKernelGGL(ph_rerank_take_kernel, dim3((uint32_t)std::min<uint64_t>((nq * k + 255) / 256, 4096)), dim3(256), 0, 0, oid,
                        od, ef, (uint32_t)k, nq, ids64, dk);
     e = hipGetLastError();
     std::vector<uint32_t> h_status(nq), h_len(nq);
@@ -918,24 +920,24 @@ extern "C" int phnsw_f16_search_batch_device(const phnsw_index *ix, const phnsw_
                                              uint32_t ldq, uint64_t nq, const phnsw_search_params *sp, uint64_t k,
                                              uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
                                              uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) try {
-  return reranked_search_device("phnsw_f16_search_batch_device", false, ix, full, queries_dev, ldq, nq, sp, k, out_ids_dev,
+  return reranked_search_device("phnsw_f16_search_batch_device", PH_ROWS_F16, ix, full, queries_dev, ldq, nq, sp, k, out_ids_dev,
                                 out_d_dev, out_len_dev, out_stats_dev, status_dev, stream);
 } catch (...) { return ph_caught(); }
 extern "C" int phnsw_f16_search_batch(const phnsw_index *ix, const phnsw_store *full, const float *queries, uint64_t nq,
                                       const phnsw_search_params *sp, uint64_t k, uint64_t *out_ids, float *out_d,
                                       uint64_t *out_len) try {
-  return reranked_search_host("phnsw_f16_search_batch", false, ix, full, queries, nq, sp, k, out_ids, out_d, out_len);
+  return reranked_search_host("phnsw_f16_search_batch", PH_ROWS_F16, ix, full, queries, nq, sp, k, out_ids, out_d, out_len);
 } catch (...) { return ph_caught(); }
 // the same two over an index on an i8 store
 extern "C" int phnsw_i8_search_batch_device(const phnsw_index *ix, const phnsw_store *full, const float *queries_dev,
                                             uint32_t ldq, uint64_t nq, const phnsw_search_params *sp, uint64_t k,
                                             uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
                                             uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) try {
-  return reranked_search_device("phnsw_i8_search_batch_device", true, ix, full, queries_dev, ldq, nq, sp, k, out_ids_dev,
+  return reranked_search_device("phnsw_i8_search_batch_device", PH_ROWS_I8, ix, full, queries_dev, ldq, nq, sp, k, out_ids_dev,
                                 out_d_dev, out_len_dev, out_stats_dev, status_dev, stream);
 } catch (...) { return ph_caught(); }
 extern "C" int phnsw_i8_search_batch(const phnsw_index *ix, const phnsw_store *full, const float *queries, uint64_t nq,
                                      const phnsw_search_params *sp, uint64_t k, uint64_t *out_ids, float *out_d,
                                      uint64_t *out_len) try {
-  return reranked_search_host("phnsw_i8_search_batch", true, ix, full, queries, nq, sp, k, out_ids, out_d, out_len);
+  return reranked_search_host("phnsw_i8_search_batch", PH_ROWS_I8, ix, full, queries, nq, sp, k, out_ids, out_d, out_len);
 } catch (...) { return ph_caught(); }

@@ -179,7 +179,7 @@ __global__ __launch_bounds__(256) void ph_tiny_table_kernel(PhTinyTableArgs a) {
       if (a.queries)
         src = (const float4 *)(a.queries + (uint64_t)q * a.ldq);
       else {
-        srcs = R::row(a.dist, a.qids[q]);
+        srcs = R::row(a.dist.rows, a.qids[q]);
         sax = R::row_aux(srcs);
       }
     }
@@ -203,7 +203,7 @@ __global__ __launch_bounds__(256) void ph_tiny_table_kernel(PhTinyTableArgs a) {
     for (int u = 0; u < 2; u++) {
       const uint32_t slot = 2u * w + u;
       const uint32_t rr = min(r0 + slot, a.tiny_n - 1u);
-      const typename R::chunk *src = R::row(a.dist, a.tnodes[rr]);
+      const typename R::chunk *src = R::row(a.dist.rows, a.tnodes[rr]);
       const typename R::aux ax = R::row_aux(src);
 #pragma unroll
       for (int k = 0; k < NV; k++) {
@@ -260,11 +260,7 @@ __host__ __device__ constexpr uint32_t ph_rev5(uint32_t t) {
 }
 
 struct PhTinyPackArgs {
-  const float *vecs;     // stored rows
-  const uint16_t *half;  // ... of an f16 store (vecs == nullptr): widened here, the packed operand is f32 either way
-  const uint8_t *i8;     // ... of an i8 store (vecs == nullptr): dequantised here
-  uint32_t ldb;
-  uint32_t ld;
+  PhRows rows;  // stored rows: widened / dequantised here, the packed operand is f32 whatever their kind
   const float *queries;  // raw query rows, or nullptr: rows are stored vectors
   uint32_t ldq;
   const uint32_t *ids;    // row -> VectorId of a stored vector (when queries == nullptr)
@@ -274,6 +270,11 @@ struct PhTinyPackArgs {
   float4 *out;
 };
 
+template <class R>
+__device__ __forceinline__ float4 tiny_pack_stored(const PhRows &rows, uint32_t vid, uint32_t c) {
+  const typename R::chunk *src = R::row(rows, vid);
+  return R::widen(R::load(src, c), R::row_aux(src));
+}
 // blockDim (32 rows, 8 chunks): a row's 8 chunks are one 128-byte read, a chunk's 32 rows one 512-byte write
 __global__ void ph_tiny_pack_kernel(PhTinyPackArgs p) {
   const uint32_t r = blockIdx.x * 32u + threadIdx.x;
@@ -281,15 +282,14 @@ __global__ void ph_tiny_pack_kernel(PhTinyPackArgs p) {
   float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
   if (r < p.n) {
     const uint32_t e = p.order ? p.order[r] : r;
-    if (!p.queries && p.half) {
-      v = RowF16::widen(((const uint2 *)(p.half + (uint64_t)p.ids[e] * p.ld))[c]);
-    } else if (!p.queries && p.i8) {
-      const RowI8::chunk *src = (const RowI8::chunk *)(p.i8 + (uint64_t)p.ids[e] * p.ldb);
-      v = RowI8::widen(RowI8::load(src, c), RowI8::row_aux(src));
+    if (p.queries) {
+      v = ((const float4 *)(p.queries + (uint64_t)e * p.ldq))[c];
     } else {
-      const float4 *src = p.queries ? (const float4 *)(p.queries + (uint64_t)e * p.ldq)
-                                    : (const float4 *)(p.vecs + (uint64_t)p.ids[e] * p.ld);
-      v = src[c];
+      switch (p.rows.kind) {
+        case PH_ROWS_F16: v = tiny_pack_stored<RowF16>(p.rows, p.ids[e], c); break;
+        case PH_ROWS_I8: v = tiny_pack_stored<RowI8>(p.rows, p.ids[e], c); break;
+        default: v = tiny_pack_stored<RowF32>(p.rows, p.ids[e], c); break;
+      }
     }
   }
   const uint32_t t = ph_rev5(c & 31u), b = (c >> 5) & 1u, k = c >> 6;
@@ -563,6 +563,17 @@ static int tiny_prep_graph(const phnsw_index *ix, PhWorkspace &ws, PhSearchArgs 
   return 0;
 }
 
+// the vector-unit tile pass over the rows of one kind
+template <class R>
+static void tiny_table_valu(int nv, dim3 grid, hipStream_t stream, const PhTinyTableArgs &t) {
+  if (nv == 1)
+    hipLaunchKernelGGL((ph_tiny_table_kernel<1, 8, R>), grid, dim3(256), 0, stream, t);
+  else if (nv == 3)
+    hipLaunchKernelGGL((ph_tiny_table_kernel<3, 8, R>), grid, dim3(256), 0, stream, t);
+  else
+    hipLaunchKernelGGL((ph_tiny_table_kernel<6, 4, R>), grid, dim3(256), 0, stream, t);
+}
+
 // D[p][t] = compare_vec(query of position p, Stored(tnodes[t])) for npos positions (position p = query order[p], or p
 // itself; raw queries or Stored ids), the per-hop path's bits: the matrix-core kernel where it applies, else the
 // vector-unit tile pass.  returns 1 (no error set) when its operand buffers cannot be allocated.
@@ -605,7 +616,7 @@ static int tiny_table(const phnsw_index *ix, PhWorkspace &ws, const PhDistArgs &
     PhTinyPackKey key;
     key.valid = !tiny_keep_off();
     key.nodes_epoch = ix->nodes_epoch;
-    key.vecs = dist.half ? (const void *)dist.half : (dist.i8 ? (const void *)dist.i8 : (const void *)dist.vecs);
+    key.vecs = dist.rows.base;
     key.tnodes = tnodes;
     key.ld = dist.ld;
     key.tn = tn;
@@ -618,11 +629,7 @@ static int tiny_table(const phnsw_index *ix, PhWorkspace &ws, const PhDistArgs &
     if (kept) *kept = pn_kept;
     PhTinyPackArgs k;
     memset(&k, 0, sizeof(k));
-    k.vecs = dist.vecs;
-    k.half = dist.half;
-    k.i8 = dist.i8;
-    k.ldb = dist.ldb;
-    k.ld = dist.ld;
+    k.rows = dist.rows;
     k.nv = (uint32_t)nv;
     k.queries = queries;
     k.ldq = ldq;
@@ -678,26 +685,11 @@ static int tiny_table(const phnsw_index *ix, PhWorkspace &ws, const PhDistArgs &
     t.rows_per_slice = (tiles + slices - 1u) / slices * 8u;
     slices = (tn + t.rows_per_slice - 1u) / t.rows_per_slice;
     dim3 grid(gx, slices);
-    if (dist.half) {
-      if (nv == 1)
-        hipLaunchKernelGGL((ph_tiny_table_kernel<1, 8, RowF16>), grid, dim3(256), 0, stream, t);
-      else if (nv == 3)
-        hipLaunchKernelGGL((ph_tiny_table_kernel<3, 8, RowF16>), grid, dim3(256), 0, stream, t);
-      else
-        hipLaunchKernelGGL((ph_tiny_table_kernel<6, 4, RowF16>), grid, dim3(256), 0, stream, t);
-    } else if (dist.i8) {
-      if (nv == 1)
-        hipLaunchKernelGGL((ph_tiny_table_kernel<1, 8, RowI8>), grid, dim3(256), 0, stream, t);
-      else if (nv == 3)
-        hipLaunchKernelGGL((ph_tiny_table_kernel<3, 8, RowI8>), grid, dim3(256), 0, stream, t);
-      else
-        hipLaunchKernelGGL((ph_tiny_table_kernel<6, 4, RowI8>), grid, dim3(256), 0, stream, t);
-    } else if (nv == 1)
-      hipLaunchKernelGGL((ph_tiny_table_kernel<1, 8>), grid, dim3(256), 0, stream, t);
-    else if (nv == 3)
-      hipLaunchKernelGGL((ph_tiny_table_kernel<3, 8>), grid, dim3(256), 0, stream, t);
-    else
-      hipLaunchKernelGGL((ph_tiny_table_kernel<6, 4>), grid, dim3(256), 0, stream, t);
+    switch (dist.rows.kind) {
+      case PH_ROWS_F16: tiny_table_valu<RowF16>(nv, grid, stream, t); break;
+      case PH_ROWS_I8: tiny_table_valu<RowI8>(nv, grid, stream, t); break;
+      default: tiny_table_valu<RowF32>(nv, grid, stream, t); break;
+    }
   }
   PH_HIP(hipGetLastError());
   return 0;
