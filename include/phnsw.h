@@ -504,7 +504,7 @@ int phnsw_f16_search_batch_device(const phnsw_index *ix, const phnsw_store *full
  * the phnsw_last_search_* / phnsw_dense_top_layers queries and the destroy calls; every other entry point returns
  * PHNSW_E_UNSUPPORTED. */
 int phnsw_store_create_i8(const phnsw_store *full, phnsw_store **out);
-/* the stored codes [n][dim] and scales [n] of an i8 store */
+/* the stored codes [n][dim] and scales [n] of an i8 (or i8q) store */
 int phnsw_i8_read(const phnsw_store *s, int8_t *codes, float *scales);
 /* phnsw_f16_search_batch / _device over an index on an i8 store: search, recompute every returned id on `full`,
  * sort by (distance, id), keep the best k <= number_of_candidates; same outputs */
@@ -515,6 +515,28 @@ int phnsw_i8_search_batch_device(const phnsw_index *ix, const phnsw_store *full,
                                  uint32_t ldq, uint64_t nq, const phnsw_search_params *sp, uint64_t k,
                                  uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
                                  uint32_t *out_stats_dev, uint32_t *status_dev, void *stream);
+
+/* ---- int8 row store searched symmetrically: int8 query, integer dot products (rowstore.hip) ----
+ * The rows are exactly those of phnsw_store_create_i8 (same quantiser, same layout; phnsw_i8_read and phnsw_store_read
+ * return the same values).  A distance quantises the query too -- a raw query with the rows' own quantiser
+ *   sq = maxabs(query) / 127.0f,  cq_j = clamp(rintf(q_j / sq), -127, 127)   (sq == 0: codes 0),
+ * a Stored query as its row's codes and scale, never requantised -- and is
+ *   dot = (sq * sr) * (float)idot,  idot = sum_j cq_j * cr_j  in int32 (exact),
+ * two IEEE f32 multiplies in that order and a round-to-nearest-even conversion, put through the metric like any dot
+ * product (tests/i8q_reference.py restates it in numpy).  A non-finite raw query is outside the contract.  The two
+ * dot-product metrics only: an L2 `full` is PHNSW_E_UNSUPPORTED (the Euclidean distance would need the rows' norms).
+ * A source that is not an f32 store, or a NaN or infinite component, is PHNSW_E_INVALID.  SEARCH-ONLY, with the
+ * supported list of the i8 store; every other entry point returns PHNSW_E_UNSUPPORTED. */
+int phnsw_store_create_i8q(const phnsw_store *full, phnsw_store **out);
+/* phnsw_i8_search_batch / _device over an index on an i8q store (the i8 calls refuse an i8q index and the other way
+ * round): search, recompute every returned id on `full`, sort by (distance, id), keep the best k; same outputs */
+int phnsw_i8q_search_batch(const phnsw_index *ix, const phnsw_store *full, const float *queries, uint64_t nq,
+                           const phnsw_search_params *sp, uint64_t k, uint64_t *out_ids, float *out_d,
+                           uint64_t *out_len);
+int phnsw_i8q_search_batch_device(const phnsw_index *ix, const phnsw_store *full, const float *queries_dev,
+                                  uint32_t ldq, uint64_t nq, const phnsw_search_params *sp, uint64_t k,
+                                  uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                  uint32_t *out_stats_dev, uint32_t *status_dev, void *stream);
 
 /* ---- on-disk interchange with the Rust crate: serialize_hnsw / deserialize_hnsw
  * (src/serialize.rs:33-209): <dir>/meta (JSON HNSWMeta), <dir>/comparator/ (this library's

@@ -186,6 +186,10 @@ SYMBOLS = {
     "phnsw_i8_search_batch": (_i32, [_vp, _vp, _vp, _u64, C.POINTER(SearchParams), _u64, _vp, _vp, _vp]),
     "phnsw_i8_search_batch_device": (_i32, [_vp, _vp, _vp, _u32, _u64, C.POINTER(SearchParams), _u64, _vp, _vp, _vp,
                                             _vp, _vp, _vp]),
+    "phnsw_store_create_i8q": (_i32, [_vp, _pp]),
+    "phnsw_i8q_search_batch": (_i32, [_vp, _vp, _vp, _u64, C.POINTER(SearchParams), _u64, _vp, _vp, _vp]),
+    "phnsw_i8q_search_batch_device": (_i32, [_vp, _vp, _vp, _u32, _u64, C.POINTER(SearchParams), _u64, _vp, _vp, _vp,
+                                             _vp, _vp, _vp]),
     "phnsw_index_serialize": (_i32, [_vp, C.c_char_p]),
     "phnsw_index_deserialize": (_i32, [_vp, C.c_char_p, _pp]),
     "phnsw_index_build_params": (_i32, [_vp, C.POINTER(BuildParams)]),

@@ -74,6 +74,7 @@ int ph_distance_batch(const phnsw_store *st, const float *q_dev, uint32_t query_
     switch (st->kind) {  // the same chain over f32 rows, widened half rows, dequantised int8 rows
       case PH_ROWS_F16: rc = distance_batch_rows<DistF16>(st, da, q_dev, query_id, ids_dev, k, out_dev, s); break;
       case PH_ROWS_I8: rc = distance_batch_rows<DistI8>(st, da, q_dev, query_id, ids_dev, k, out_dev, s); break;
+      case PH_ROWS_I8Q: rc = distance_batch_rows<DistI8Q>(st, da, q_dev, query_id, ids_dev, k, out_dev, s); break;  // integer dots
       default: rc = distance_batch_rows<DistF32>(st, da, q_dev, query_id, ids_dev, k, out_dev, s); break;
     }
     if (rc) return rc;

@@ -170,6 +170,28 @@ struct RowI8 : RowBase<uint32_t> {  // four codes
   }
 };
 
+// THE quantiser of the i8 and i8q stores, for a row (ph_i8_convert_kernel) and for a raw query of an i8q store alike:
+//   scale = maxabs / 127.0f, code = clamp(rintf(x / scale), -127, 127)   (IEEE f32 divisions), scale 0 -> code 0
+__device__ __forceinline__ float ph_i8_scale(float maxabs) { return __fdiv_rn(maxabs, 127.0f); }
+__device__ __forceinline__ int ph_i8_quant(float x, float scale) {
+  if (scale == 0.f) return 0;
+  const float t = rintf(__fdiv_rn(x, scale));
+  return (int)fminf(fmaxf(t, -127.f), 127.f);
+}
+// four components -> the code word of their chunk, component order = byte order (the layout RowI8::load reads)
+__device__ __forceinline__ uint32_t ph_i8_quant4(const float4 &v, float scale) {
+  return ((uint32_t)ph_i8_quant(v.x, scale) & 0xFFu) | (((uint32_t)ph_i8_quant(v.y, scale) & 0xFFu) << 8) |
+         (((uint32_t)ph_i8_quant(v.z, scale) & 0xFFu) << 16) | (((uint32_t)ph_i8_quant(v.w, scale) & 0xFFu) << 24);
+}
+__device__ __forceinline__ float ph_maxabs4(float m, const float4 &v) {
+  return fmaxf(fmaxf(fmaxf(m, fabsf(v.x)), fmaxf(fabsf(v.y), fabsf(v.z))), fabsf(v.w));
+}
+__device__ __forceinline__ float wave_max(float m) {
+#pragma unroll
+  for (int sft = 32; sft >= 1; sft >>= 1) m = fmaxf(m, __shfl_xor(m, sft));
+  return m;
+}
+
 template <int NV, int U, bool EXACT, bool L2, class R>
 __device__ __forceinline__ void rows_partial_impl(const typename R::chunk *const (&row)[U], const float4 (&q)[NV],
                                                   uint32_t nv4, uint32_t lane, float (&acc)[U]) {
@@ -373,6 +395,7 @@ __device__ __forceinline__ float batch_distances(const void *__restrict__ vecs, 
 // ------------------------------------------------------------------ distance policies
 // The traversal kernels are written once and instantiated per policy:
 //   DistF32 / DistF16 / DistI8<NV>: the query in registers, candidates = stored rows (wave per row, 4 in flight)
+//   DistI8Q<NV>: the query as int8 codes in registers, candidates = int8 rows, integer dot products
 //   DistPQ:      product-quantised store: a per-query table T[m][ksub] in LDS
 //                (T[j][k] = <q_sub_j, c_jk> or |q_sub_j - c_jk|^2), candidates = u8 code
 //                rows, one LANE per candidate, distance = sum_j T[j][code_j] added in j order.
@@ -433,6 +456,137 @@ template <int NV, int U = 4>
 struct DistF16 : DistRows<NV, U, RowF16> {};
 template <int NV, int U = 4>
 struct DistI8 : DistRows<NV, U, RowI8> {};
+
+// ------------------------------------------------------------------ i8q: int8 rows, int8 query, integer dot products
+// THE distance of an i8q store: the two scales multiplied first, then the exact integer dot product (converted with
+// round to nearest even, exact below 2^24), two roundings in all, never contracted.  The per-hop policy below, the
+// distance batch and the dense table's epilogue (tiny.hip) all call it.
+__device__ __forceinline__ float ph_i8q_distance(float sq, float sr, int idot, int metric) {
+  return finalize_metric(__fmul_rn(__fmul_rn(sq, sr), (float)idot), metric);
+}
+
+// wave_sum4 over int32: an integer sum has the same bits in any tree, so this one is simply the cheapest (two
+// permlane swaps, five DPP moves).  Afterwards lanes 0-15 hold row 0's sum, 16-31 row 2's, 32-47 row 1's, 48-63 row 3's.
+__device__ __forceinline__ int wave_isum4(int p0, int p1, int p2, int p3) {
+  auto a = __builtin_amdgcn_permlane32_swap((uint32_t)p0, (uint32_t)p1, false, false);
+  auto b = __builtin_amdgcn_permlane32_swap((uint32_t)p2, (uint32_t)p3, false, false);
+  const uint32_t f0 = a[0] + a[1], f1 = b[0] + b[1];  // lanes < 32: rows 0 / 2, >= 32: rows 1 / 3
+  auto c = __builtin_amdgcn_permlane16_swap(f0, f1, false, false);
+  int v = (int)(c[0] + c[1]);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x128, 0xF, 0xF, true);  // row_ror:8
+  int t = __builtin_amdgcn_update_dpp(v, v, 0x114, 0xF, 0xA, false);  // row_shr:4 into lanes 4-7, 12-15
+  t = __builtin_amdgcn_update_dpp(t, v, 0x104, 0xF, 0x5, false);      // row_shl:4 into lanes 0-3, 8-11
+  v += t;
+  v += __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xF, 0xF, true);  // quad_perm [2,3,0,1]
+  v += __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xF, 0xF, true);  // quad_perm [1,0,3,2]
+  return v;
+}
+
+// four wave-uniform values to the lanes wave_isum4 leaves their rows' sums in, by the same three swaps (a select per
+// lane would do, but the compiler turns a select among loaded values into an indexed array that it keeps in LDS)
+__device__ __forceinline__ float wave_route4(float s0, float s1, float s2, float s3) {
+  auto a = __builtin_amdgcn_permlane32_swap(__float_as_uint(s0), __float_as_uint(s1), false, false);
+  auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(s2), __float_as_uint(s3), false, false);
+  auto c = __builtin_amdgcn_permlane16_swap(a[0], b[0], false, false);  // a[0]: s0 | s1 by halves, b[0]: s2 | s3
+  return __uint_as_float(c[0]);
+}
+
+// DistI8Q<NV, U>: the rows of an i8 store, the query as int8 codes too -- NV dwords and one scale per lane instead of
+// NV float4.  Not a DistRows: there is no f32 chain.  Lane l keeps the code words of chunks l, l + 64, ... (RowI8's
+// mapping, four codes per dword) of the query; a candidate row is NV v_dot4_i32_i8 per lane into one int32, an integer
+// wave sum and one ph_i8q_distance.  Chunks past the row (dim not a multiple of 256) read a clamped address against a
+// query word of 0, which adds nothing: one code path for every dimension.  The candidate compaction and the
+// fetch of a candidate's result are batch_distances' (ds_permute of row offsets, one ds_bpermute per group of four).
+template <int NV, int U = 4>
+struct DistI8Q {
+  static_assert(U > 0 && U % 4 == 0, "rows are reduced four at a time");
+  static constexpr bool GLOBAL_TABLE = false;
+  static constexpr bool EARLY = false;
+  static constexpr bool ROW_STORE = true;
+  static constexpr int CHUNKS = NV, ROWS_IN_FLIGHT = U;
+  uint32_t qc[NV];
+  float sq;
+  __device__ __forceinline__ void prepare_raw(const PhDistArgs &d, const float *q, float *, uint32_t lane) {
+    float4 v[NV];
+    float m = 0.f;
+#pragma unroll
+    for (int k = 0; k < NV; k++) {
+      const uint32_t c = lane + 64u * k;
+      v[k] = (c < d.nv4) ? ((const float4 *)q)[c] : make_float4(0.f, 0.f, 0.f, 0.f);
+      m = ph_maxabs4(m, v[k]);
+    }
+    sq = ph_i8_scale(wave_max(m));
+#pragma unroll
+    for (int k = 0; k < NV; k++) qc[k] = ph_i8_quant4(v[k], sq);
+  }
+  // a stored query is its row's codes and scale as they are
+  __device__ __forceinline__ void prepare_stored(const PhDistArgs &d, uint32_t vid, float *, uint32_t lane) {
+    const uint32_t *row = RowI8::row(d.rows, vid);
+    sq = RowI8::row_aux(row);
+#pragma unroll
+    for (int k = 0; k < NV; k++) {
+      const uint32_t c = lane + 64u * k;
+      qc[k] = 0u;
+      if (c < d.nv4) qc[k] = RowI8::load(row, c);
+    }
+  }
+  // one round: candidates base .. base + U - 1 (in lane order) of the compacted list
+  __device__ __forceinline__ void round(const PhDistArgs &d, uint32_t olo, uint32_t ohi, uint32_t m, uint32_t base, bool cand,
+                                        uint32_t myrank, uint32_t lane, float &myd) const {
+    const uint32_t *r[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      const uint32_t k = min(base + (uint32_t)u, m - 1u);  // short tail: the last row again (same value, unused)
+      const uint64_t o = ((uint64_t)rl32(ohi, (int)k) << 32) | rl32(olo, (int)k);
+      r[u] = (const uint32_t *)((const char *)d.rows.base + o);
+    }
+    uint32_t raw[U][NV];
+    float sr[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      sr[u] = RowI8::row_aux(r[u]);
+#pragma unroll
+      for (int k = 0; k < NV; k++) raw[u][k] = RowI8::load(r[u], min(lane + 64u * k, d.nv4 - 1u));
+    }
+    int p[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      p[u] = 0;
+#pragma unroll
+      for (int k = 0; k < NV; k++) p[u] = __builtin_amdgcn_sdot4((int)qc[k], (int)raw[u][k], p[u], false);
+    }
+    const uint32_t mine = myrank - base;  // < U when this is the lane's round
+#pragma unroll
+    for (int g = 0; g < U; g += 4) {
+      // row u of the group ends in lanes {0, 32, 16, 48}[u] + 0..15 (wave_isum4); those lanes finish it with its scale
+      const int idot = wave_isum4(p[g], p[g + 1], p[g + 2], p[g + 3]);
+      const float s4 = wave_route4(sr[g], sr[g + 1], sr[g + 2], sr[g + 3]);
+      const float d4 = ph_i8q_distance(sq, s4, idot, d.metric);
+      const uint32_t u = (mine - g) & 3u;
+      const uint32_t src = ((u & 1u) << 5) | ((u & 2u) << 3);  // 0, 32, 16, 48
+      const float got = __uint_as_float((uint32_t)__builtin_amdgcn_ds_bpermute((int)(src << 2), (int)__float_as_uint(d4)));
+      if (cand && mine >= (uint32_t)g && mine < (uint32_t)g + 4u) myd = got;
+    }
+  }
+  __device__ __forceinline__ float batch(const PhDistArgs &d, uint64_t mask, uint32_t vid, uint32_t lane) const {
+    float myd = 0.f;
+    const uint32_t m = __popcll(mask);
+    if (m == 0) return myd;
+    // candidate number k (in lane order) leaves the byte offset of its row in lane k: see batch_distances
+    const bool cand = (mask >> lane) & 1ull;
+    const uint32_t myrank = __popcll(mask & lanemask_lt(lane));
+    const uint64_t off = (uint64_t)vid * (uint64_t)d.rows.stride;
+    const int dst = (int)((cand ? myrank : 63u) << 2);
+    uint32_t olo = (uint32_t)__builtin_amdgcn_ds_permute(dst, (int)(uint32_t)off);
+    uint32_t ohi = (uint32_t)__builtin_amdgcn_ds_permute(dst, (int)(uint32_t)(off >> 32));
+    if (m == 64) {
+      olo = (uint32_t)off;
+      ohi = (uint32_t)(off >> 32);
+    }
+    for (uint32_t base = 0; base < m; base += U) round(d, olo, ohi, m, base, cand, myrank, lane, myd);
+    return myd;
+  }
+};
 
 // f32 -> IEEE binary16 bits, round to nearest even, written with integer operations so that
 // the oracle's C version produces the same bits (no dependence on a denormal mode)

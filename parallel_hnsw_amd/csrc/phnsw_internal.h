@@ -60,17 +60,19 @@ struct PhLayerHost {
 };
 
 // How a store keeps its vectors.  The three row kinds are searched by the same kernels through a row policy
-// (RowF32 / RowF16 / RowI8, phnsw_device.h); f16 and i8 are the converted, search-only stores of rowstore.hip.
+// (RowF32 / RowF16 / RowI8, phnsw_device.h); f16, i8 and i8q are the converted, search-only stores of rowstore.hip.
 enum PhRowKind : int {
   PH_ROWS_F32 = 0,    // [n][ld] f32
   PH_ROWS_F16,        // [n][ld] IEEE binary16 in component order: rows start on 8-byte boundaries
   PH_ROWS_I8,         // n rows of 4 + ld bytes rounded up to a multiple of 16: the f32 scale, then ld int8 codes
   PH_ROWS_PQ,         // u8 codes over per-sub-space codebooks (pq.hip)
   PH_ROWS_PQ_SHARED,  // u16 codes over one shared codebook (pq.hip)
+  PH_ROWS_I8Q,        // the bytes of PH_ROWS_I8; a distance quantises the query too and takes integer dot products (DistI8Q)
 };
-static inline bool ph_rows_converted(int kind) { return kind == PH_ROWS_F16 || kind == PH_ROWS_I8; }
+static inline bool ph_rows_converted(int kind) { return kind == PH_ROWS_F16 || kind == PH_ROWS_I8 || kind == PH_ROWS_I8Q; }
+static inline bool ph_rows_i8_layout(int kind) { return kind == PH_ROWS_I8 || kind == PH_ROWS_I8Q; }  // scale + int8 codes
 static inline const char *ph_rows_name(int kind) {
-  static const char *const names[] = {"f32", "f16", "i8", "product-quantised", "shared-codebook product-quantised"};
+  static const char *const names[] = {"f32", "f16", "i8", "product-quantised", "shared-codebook product-quantised", "i8q"};
   return names[kind];
 }
 // where the rows of a row kind are: one base pointer, one stride in bytes
@@ -107,9 +109,9 @@ struct phnsw_store {
   float *codebook = nullptr;
   uint32_t pq_m = 0, pq_ksub = 0, pq_dsub = 0;
   uint32_t pq_table_f16 = 0;
-  // converted store (phnsw_store_create_f16 / _i8, rowstore.hip): rows == nullptr, packed = n rows of packed_stride
-  // bytes in the layout of its kind; a distance widens / dequantises them to f32 and runs the f32 chain.  Search-only:
-  // see ph_search_only_unsupported.
+  // converted store (phnsw_store_create_f16 / _i8 / _i8q, rowstore.hip): rows == nullptr, packed = n rows of
+  // packed_stride bytes in the layout of its kind; a distance widens / dequantises them to f32 and runs the f32 chain
+  // (i8q: integer dot products of the codes, DistI8Q).  Search-only: see ph_search_only_unsupported.
   void *packed = nullptr;
   uint32_t packed_stride = 0;
   // coarse cells of the locality schedule (bruteforce.hip): anchor rows + their chain ranks
@@ -368,7 +370,7 @@ void ph_store_anchors_free(phnsw_store *s);
 int ph_order_by_keys_device(const uint32_t *keys, uint32_t n, uint32_t *order_out, hipStream_t st);
 int ph_layer_range_order(PhLayerHost &L, uint32_t first, uint32_t count, const uint32_t **out);
 
-// a search-only row store (f16 or i8): searched like the f32 store, its rows converted to f32 where a GEMM or a host reads them
+// a search-only row store (f16, i8 or i8q): searched like the f32 store, its rows converted to f32 where a GEMM or a host reads them
 static inline bool ph_store_converted(const phnsw_store *s) { return ph_rows_converted(s->kind); }
 // converted stores (rowstore.hip): rows of `ids_dev` (nullptr: rows first .. first + cnt) widened / dequantised into
 // [cnt][ld] f32 rows; a range of the store converted into a dense host array
@@ -426,7 +428,7 @@ static inline PhDistArgs ph_dist_args(const phnsw_store *s) {
 }
 // bytes of one stored row as the search gathers it
 static inline uint32_t ph_row_bytes(const phnsw_store *s) { return ph_store_rows(s).stride; }
-// an f16 or i8 store serves searches only: every other entry point refuses it by name
+// an f16, i8 or i8q store serves searches only: every other entry point refuses it by name
 static inline int ph_search_only_unsupported(const phnsw_store *s, const char *call) {
   if (!s || !ph_store_converted(s)) return 0;
   ph_set_error("%s: not supported on an %s store or an index over one (search-only; use the f32 store)", call,

@@ -773,9 +773,9 @@ extern "C" int phnsw_pq_search_batch_device(const phnsw_index *ix, const phnsw_s
   return 0;
 } catch (...) { return ph_caught(); }
 
-// ------------------------------------------------------------------ f16 / i8 store: search + f32 re-rank
+// ------------------------------------------------------------------ f16 / i8 / i8q store: search + f32 re-rank
 //
-// The f16 or i8 index finds the candidates (distances of the widened / dequantised rows); the f32 store then gives every returned
+// The f16, i8 or i8q index finds the candidates (distances of the widened / dequantised rows); the f32 store then gives every returned
 // id its full-precision distance (ph_pq_rerank_kernel: the bits of phnsw_distance_batch on `full`), the row is
 // sorted by (distance, id) and the best k are kept.
 
@@ -804,7 +804,7 @@ __global__ void ph_rerank_take_kernel(const uint32_t *ids, const float *d, uint3
   }
 }
 
-// `kind`: the converted store the entry point serves (the f16 calls refuse an i8 index and the other way round)
+// `kind`: the converted store the entry point serves (a call of one kind refuses an index over another)
 static int rerank_check(const char *call, int kind, const phnsw_index *ix, const phnsw_store *full,
                         const phnsw_search_params *sp, uint64_t nq, uint64_t k) {
   if (!ix || !full || !sp || ix->store->kind != kind || !full->rows || full->n != ix->store->n || full->dim != ix->store->dim ||
@@ -940,4 +940,17 @@ extern "C" int phnsw_i8_search_batch(const phnsw_index *ix, const phnsw_store *f
                                      const phnsw_search_params *sp, uint64_t k, uint64_t *out_ids, float *out_d,
                                      uint64_t *out_len) try {
   return reranked_search_host("phnsw_i8_search_batch", PH_ROWS_I8, ix, full, queries, nq, sp, k, out_ids, out_d, out_len);
+} catch (...) { return ph_caught(); }
+// ... and on an i8q store
+extern "C" int phnsw_i8q_search_batch_device(const phnsw_index *ix, const phnsw_store *full, const float *queries_dev,
+                                             uint32_t ldq, uint64_t nq, const phnsw_search_params *sp, uint64_t k,
+                                             uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                             uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) try {
+  return reranked_search_device("phnsw_i8q_search_batch_device", PH_ROWS_I8Q, ix, full, queries_dev, ldq, nq, sp, k, out_ids_dev,
+                                out_d_dev, out_len_dev, out_stats_dev, status_dev, stream);
+} catch (...) { return ph_caught(); }
+extern "C" int phnsw_i8q_search_batch(const phnsw_index *ix, const phnsw_store *full, const float *queries, uint64_t nq,
+                                      const phnsw_search_params *sp, uint64_t k, uint64_t *out_ids, float *out_d,
+                                      uint64_t *out_len) try {
+  return reranked_search_host("phnsw_i8q_search_batch", PH_ROWS_I8Q, ix, full, queries, nq, sp, k, out_ids, out_d, out_len);
 } catch (...) { return ph_caught(); }

@@ -17,6 +17,10 @@
 // rows of 4 + ld bytes rounded up to a multiple of 16: the f32 scale, the ld code bytes in component order (padding
 // components: code 0), padding.  A lane's chunk of four components is one 4-byte load; a component dequantises to
 // scale * (float)code with one rounding (ph_i8_dequant).
+//
+// i8q: the rows of an i8 store, byte for byte (same kernel, same layout, same phnsw_i8_read and phnsw_store_read); what
+// differs is the distance, which quantises the query with the rows' own quantiser and takes integer dot products
+// (DistI8Q, phnsw_device.h).  Dot-product metrics only: the Euclidean distance would need the rows' norms.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -42,12 +46,6 @@ __global__ void ph_f16_convert_kernel(const float *__restrict__ rows, uint32_t l
   if (mine) atomicOr(bad, 1u);
 }
 
-__device__ __forceinline__ int ph_i8_quant(float x, float scale) {
-  if (scale == 0.f) return 0;
-  const float t = rintf(__fdiv_rn(x, scale));
-  return (int)fminf(fmaxf(t, -127.f), 127.f);
-}
-
 // one wave per row: max-abs reduction over the wave, then the row's scale and its codes, four to a word; a NaN or an
 // infinite component raises the flag
 __global__ void ph_i8_convert_kernel(const float *__restrict__ rows, uint32_t ld, uint32_t dim, uint64_t n,
@@ -64,7 +62,7 @@ __global__ void ph_i8_convert_kernel(const float *__restrict__ rows, uint32_t ld
     }
 #pragma unroll
     for (int sft = 32; sft >= 1; sft >>= 1) m = fmaxf(m, __shfl_xor(m, sft));
-    const float scale = __fdiv_rn(m, 127.0f);
+    const float scale = ph_i8_scale(m);
     uint32_t *dst = (uint32_t *)(out + r * stride);
     if (lane == 0) dst[0] = __float_as_uint(scale);
     for (uint32_t w = 1u + lane; w < stride / 4u; w += 64u) {
@@ -161,6 +159,10 @@ static int create_converted(const char *name, const phnsw_store *full, int kind,
     ph_set_error("%s: the source must be an f32 store", name);
     return PHNSW_E_INVALID;
   }
+  if (kind == PH_ROWS_I8Q && full->metric == PHNSW_METRIC_L2) {
+    ph_set_error("%s: the Euclidean metric is not supported on an i8q store (dot-product metrics only)", name);
+    return PHNSW_E_UNSUPPORTED;
+  }
   PH_HIP(hipSetDevice(full->device));
   phnsw_store *s = new phnsw_store();
   s->device = full->device;
@@ -214,11 +216,14 @@ extern "C" int phnsw_store_create_f16(const phnsw_store *full, phnsw_store **out
 extern "C" int phnsw_store_create_i8(const phnsw_store *full, phnsw_store **out) try {
   return create_converted("phnsw_store_create_i8", full, PH_ROWS_I8, out);
 } catch (...) { return ph_caught(); }
+extern "C" int phnsw_store_create_i8q(const phnsw_store *full, phnsw_store **out) try {
+  return create_converted("phnsw_store_create_i8q", full, PH_ROWS_I8Q, out);
+} catch (...) { return ph_caught(); }
 
 // the stored codes [n][dim] and scales [n], as they lie in the rows
 extern "C" int phnsw_i8_read(const phnsw_store *s, int8_t *codes, float *scales) try {
-  if (!s || s->kind != PH_ROWS_I8 || !codes || !scales) {
-    ph_set_error("phnsw_i8_read: needs an i8 store and both outputs");
+  if (!s || !ph_rows_i8_layout(s->kind) || !codes || !scales) {
+    ph_set_error("phnsw_i8_read: needs an i8 or i8q store and both outputs");
     return PHNSW_E_INVALID;
   }
   if (s->n == 0) return 0;

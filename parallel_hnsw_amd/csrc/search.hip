@@ -1021,8 +1021,9 @@ static ph_search_fn pick_kernel_lat(int capc, int nv) {
   return nullptr;
 }
 
-// The throughput kernels of a row store, D = DistF32 / DistF16 / DistI8: the same set shape for shape -- same queues,
-// same LDS visited table, same rows in flight.  (There are no latency (U == 0), instrumented or big-queue kernels over
+// The throughput kernels of a row store, D = DistF32 / DistF16 / DistI8 / DistI8Q: the same set shape for shape -- same
+// queues, same LDS visited table, same rows in flight (DistI8Q too: 16 rows in flight would cost its headline kernel a
+// wave per SIMD, 144 VGPRs against 112, profiles/i8q).  (There are no latency (U == 0), instrumented or big-queue kernels over
 // converted rows: batches of any size run these, and the calls behind the others refuse a converted store.)
 template <template <int, int> class D>
 static ph_search_fn pick_kernel_rows(int capc, int nv) {
@@ -1094,6 +1095,7 @@ enum PhKernelFamily {
   PH_KF_ROWS_F32,   // throughput kernels over f32 rows
   PH_KF_ROWS_F16,   // ... f16 rows
   PH_KF_ROWS_I8,    // ... i8 rows
+  PH_KF_ROWS_I8Q,   // ... i8 rows against an int8 query (integer dot products)
   PH_KF_PQ_TABLE,   // per-sub-space PQ, the query's table in LDS or global memory
   PH_KF_PQ_REG,     // ... the 8-bit table in registers (pqr_m sub-spaces)
   PH_KF_PQ_SHARED,  // shared-codebook PQ
@@ -1111,7 +1113,9 @@ struct PhKernelChoice {
   bool lat_shape = false;  // the shape has a latency kernel and the batch is small enough for it (the instrumented
                            // kernel overrides it, as it always has: after the latency path made its LDS arrangements)
 };
-static bool kf_rows(PhKernelFamily f) { return f == PH_KF_ROWS_F32 || f == PH_KF_ROWS_F16 || f == PH_KF_ROWS_I8; }
+static bool kf_rows(PhKernelFamily f) {
+  return f == PH_KF_ROWS_F32 || f == PH_KF_ROWS_F16 || f == PH_KF_ROWS_I8 || f == PH_KF_ROWS_I8Q;
+}
 
 // grows: threshold_nn (the queue may double, so it keeps 512 slots at ef <= 256); instr: out_index is set.  Reads
 // PHNSW_VISITED, PHNSW_PQ_TABLE and PHNSW_NO_LAT.
@@ -1157,6 +1161,7 @@ static PhKernelChoice pick_search_kernel(const phnsw_store *s, uint32_t ef_max, 
   switch (s->kind) {
     case PH_ROWS_F16: k.family = PH_KF_ROWS_F16; k.fn = pick_kernel_rows<DistF16>(k.capc, k.nv); break;
     case PH_ROWS_I8: k.family = PH_KF_ROWS_I8; k.fn = pick_kernel_rows<DistI8>(k.capc, k.nv); break;
+    case PH_ROWS_I8Q: k.family = PH_KF_ROWS_I8Q; k.fn = pick_kernel_rows<DistI8Q>(k.capc, k.nv); break;
     default: k.family = PH_KF_ROWS_F32; k.fn = pick_kernel_rows<DistF32>(k.capc, k.nv); break;
   }
   return k;

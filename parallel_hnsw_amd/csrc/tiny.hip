@@ -414,6 +414,121 @@ __global__ __launch_bounds__(256, G == 1 ? 4 : 1) void ph_tiny_table_mfma_kernel
   }
 }
 
+// ------------------------------------------------------------------ the table of an i8q store: an int8 GEMM
+//
+// D[p][t] = ph_i8q_distance(sq[p], sr[t], idot, metric) with idot = sum_j cq[p][j] * cr[t][j] in int32.  An integer
+// sum has the same bits in any order, so the table needs neither the packed operand layout nor the butterfly-order
+// recursion of the f32 kernel above: the operands are plain row-major code matrices [rows_pad][K_pad] with one scale
+// per row, K zero-padded to a whole staging step (zeros add nothing, so ragged dimensions and launches of a few
+// queries take the same kernel), and the kernel is a textbook tiled GEMM on v_mfma_i32_32x32x32_i8.
+//
+// ph_tiny_quant_kernel makes an operand: one wave per row.  A raw query goes through the quantiser of the rows
+// (ph_i8_scale / ph_i8_quant4, the functions DistI8Q::prepare_raw calls); a stored vector -- a stored query or a node
+// of the table layer -- is its row's codes and scale copied as they are.
+#define PH_I8T_KS 128u                 // code bytes of a row staged per step (four MFMAs deep)
+#define PH_I8T_ROW (PH_I8T_KS + 16u)   // LDS bytes per staged row: the 16-byte pad spreads a 16-lane read over all banks
+#define PH_I8T_LDS (2u * 64u * PH_I8T_ROW)  // 18 KiB: fits the hole a running search kernel leaves (24 KiB, search.hip)
+
+struct PhTinyQuantArgs {
+  PhRows rows;
+  const float *queries;   // raw query rows, or nullptr: rows are stored vectors
+  uint32_t ldq, nv4;      // nv4: float4 chunks (= code words) of a vector
+  const uint32_t *ids;    // row -> VectorId of a stored vector (when queries == nullptr)
+  const uint32_t *order;  // nullable: row r reads entry order[r]
+  uint32_t n, n_pad;      // rows, rows rounded up to the block tile (the rest: codes 0, scale 0)
+  uint32_t kw;            // K_pad / 4: code words per operand row
+  uint32_t *codes;        // [n_pad][kw]
+  float *scales;          // [n_pad]
+};
+
+__global__ __launch_bounds__(256) void ph_tiny_quant_kernel(PhTinyQuantArgs p) {
+  const uint32_t lane = threadIdx.x & 63u, r = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (r >= p.n_pad) return;
+  uint32_t *dst = p.codes + (uint64_t)r * p.kw;
+  float scale = 0.f;
+  if (r >= p.n) {
+    for (uint32_t c = lane; c < p.kw; c += 64u) dst[c] = 0u;
+  } else {
+    const uint32_t e = p.order ? p.order[r] : r;
+    if (p.queries) {
+      const float4 *q = (const float4 *)(p.queries + (uint64_t)e * p.ldq);
+      float m = 0.f;
+      for (uint32_t c = lane; c < p.nv4; c += 64u) m = ph_maxabs4(m, q[c]);
+      scale = ph_i8_scale(wave_max(m));
+      for (uint32_t c = lane; c < p.kw; c += 64u) dst[c] = c < p.nv4 ? ph_i8_quant4(q[c], scale) : 0u;
+    } else {
+      const uint32_t *row = RowI8::row(p.rows, p.ids[e]);
+      scale = RowI8::row_aux(row);
+      for (uint32_t c = lane; c < p.kw; c += 64u) dst[c] = c < p.nv4 ? RowI8::load(row, c) : 0u;
+    }
+  }
+  if (lane == 0) p.scales[r] = scale;
+}
+
+typedef int ph_i32x4 __attribute__((ext_vector_type(4)));
+typedef int ph_i32x16 __attribute__((ext_vector_type(16)));
+
+struct PhTinyI8Args {
+  const ph_i32x4 *cq, *cn;  // code matrices of the positions / the nodes, [rows_pad][k16] runs of 16 codes
+  const float *sq, *sn;    // their scales
+  uint32_t npos, tiny_n, stride;
+  uint32_t k16;            // K_pad / 16 (a multiple of PH_I8T_KS / 16)
+  int metric;
+  float *D;
+};
+
+// 256 threads = 4 waves, block tile 64 positions x 64 nodes, wave w: positions half w & 1, nodes half w >> 1 (as
+// the f32 kernel).  Per step, PH_I8T_KS code bytes of the 64 + 64 rows are staged in LDS (the next step's global loads
+// are in flight while the matrix cores work on this one) and every wave issues four MFMAs: lane l feeds row l % 32 with
+// the 16 codes at byte 16 * (l / 32) of each 32-byte K slab -- whichever K positions the instruction assigns to a
+// lane's 16 bytes, it assigns them alike on both operands, and the sum does not care.  One form: 18 KiB of LDS and 4
+// blocks per CU, so it always fits beside a running search kernel and PHNSW_TABLE_BESIDE has nothing to choose.
+__global__ __launch_bounds__(256, 4) void ph_tiny_table_i8_kernel(PhTinyI8Args a) {
+  __shared__ ph_i32x4 sm[PH_I8T_LDS / 16u];
+  constexpr uint32_t ROW16 = PH_I8T_ROW / 16u, KS16 = PH_I8T_KS / 16u;  // 16-byte runs per staged row / of it that are codes
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
+  const uint32_t qt = blockIdx.x, nt = blockIdx.y;
+  // staging: thread t moves run t % 8 of rows t / 8 and t / 8 + 32, for both operands
+  const uint32_t srow = tid / KS16, scol = tid % KS16;
+  const ph_i32x4 *gq = a.cq + ((uint64_t)qt * 64u + srow) * a.k16 + scol;
+  const ph_i32x4 *gn = a.cn + ((uint64_t)nt * 64u + srow) * a.k16 + scol;
+  ph_i32x4 *lq = sm + srow * ROW16 + scol, *ln = sm + (64u + srow) * ROW16 + scol;
+  const ph_i32x4 *A = sm + ((w & 1u) * 32u + (lane & 31u)) * ROW16 + (lane >> 5);
+  const ph_i32x4 *B = sm + (64u + (w >> 1) * 32u + (lane & 31u)) * ROW16 + (lane >> 5);
+  ph_i32x16 acc;
+#pragma unroll
+  for (int v = 0; v < 16; v++) acc[v] = 0;
+  const uint64_t half = (uint64_t)32u * a.k16;  // 32 operand rows on
+  ph_i32x4 q0 = gq[0], q1 = gq[half], n0 = gn[0], n1 = gn[half];
+  const uint32_t steps = a.k16 / KS16;
+  for (uint32_t s = 0; s < steps; s++) {
+    __syncthreads();  // the previous step has been consumed
+    lq[0] = q0;
+    lq[32u * ROW16] = q1;
+    ln[0] = n0;
+    ln[32u * ROW16] = n1;
+    __syncthreads();
+    if (s + 1u < steps) {
+      const uint32_t o = (s + 1u) * KS16;
+      q0 = gq[o];
+      q1 = gq[half + o];
+      n0 = gn[o];
+      n1 = gn[half + o];
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < KS16 / 2u; j++) acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(A[2u * j], B[2u * j], acc, 0, 0, 0);
+  }
+  // 32x32 accumulator layout: register v of lane L holds row 8 * (v / 4) + 4 * (L / 32) + v % 4, column L % 32;
+  // rows are the A operand's (positions), columns the B operand's (nodes)
+  const uint32_t r = (2u * nt + (w >> 1)) * 32u + (lane & 31u);
+  const float sr = a.sn[r];  // (padded to the tile)
+#pragma unroll
+  for (int v = 0; v < 16; v++) {
+    const uint32_t p = (2u * qt + (w & 1u)) * 32u + 8u * (v / 4) + 4u * (lane >> 5) + (v & 3);
+    if (p < a.npos && r < a.tiny_n) a.D[(uint64_t)p * a.stride + r] = ph_i8q_distance(a.sq[p], sr, acc[v], a.metric);
+  }
+}
+
 // ------------------------------------------------------------------ host side
 
 void ph_tiny_free(PhWorkspace &ws) {
@@ -446,7 +561,10 @@ static int table_beside_mode() {
 static bool tiny_keep_off() { return getenv("PHNSW_NO_TINY_KEEP") != nullptr; }  // tests: prep and node pack every launch
 static size_t tiny_mfma_lds(int nv, int g) { return (size_t)2 * 4 * g * nv * 64 * sizeof(float4); }
 
-bool ph_tiny_matrix_cores(const phnsw_index *ix) { return tiny_mfma_shape(ix->store->metric, ix->store->ld); }
+// an i8q store's table always comes from the int8 matrix-core kernel (PHNSW_TINY_VALU means nothing to it)
+bool ph_tiny_matrix_cores(const phnsw_index *ix) {
+  return ix->store->kind == PH_ROWS_I8Q || tiny_mfma_shape(ix->store->metric, ix->store->ld);
+}
 
 // Which leading layers run densely.  Measured at 1M x 768 (100 000 queries): the vector-unit tile pass costs
 // 0.030 us per (query, node), the matrix-core one 0.016 us, a table lookup on the walk 0.08 us, a gathered
@@ -458,7 +576,7 @@ bool ph_tiny_matrix_cores(const phnsw_index *ix) { return tiny_mfma_shape(ix->st
 uint32_t ph_tiny_layer_count(const phnsw_index *ix, uint32_t n_layers, uint32_t ef) {
   const bool off = getenv("PHNSW_NO_TINY") != nullptr;  // tests compare both paths
   if (off || (!ix->store->rows && !ph_store_converted(ix->store)) || ix->store->ld / 4 > 384) return 0;
-  const uint64_t per_ef = tiny_mfma_shape(ix->store->metric, ix->store->ld) ? 80ull : 48ull;
+  const uint64_t per_ef = ph_tiny_matrix_cores(ix) ? 80ull : 48ull;
   uint64_t cap = std::min<uint64_t>(PH_TINY_MAX_NODES, per_ef * ef);
   if (const char *e = getenv("PHNSW_TINY_MAX"))
     if (atoi(e) > 0) cap = std::min<uint64_t>(PH_TINY_MAX_NODES, (uint64_t)atoi(e));
@@ -484,6 +602,7 @@ uint64_t ph_tiny_max_positions(const phnsw_index *ix, uint32_t n_layers, uint32_
 // get their table from that kernel (per launch, on the matrix cores)
 size_t ph_tiny_beside_lds(const phnsw_index *ix, const PhSearchArgs &a) {
   if (!a.tiny_layers || a.tiny_rows || !table_beside_mode()) return 0;
+  if (ix->store->kind == PH_ROWS_I8Q) return PH_I8T_LDS;  // its one form
   const uint32_t nv4 = a.dist.nv4;
   if (!tiny_mfma_shape(ix->store->metric, nv4 * 4u)) return 0;
   return tiny_mfma_lds((int)(nv4 / 64u), 1);
@@ -574,6 +693,77 @@ static void tiny_table_valu(int nv, dim3 grid, hipStream_t stream, const PhTinyT
     hipLaunchKernelGGL((ph_tiny_table_kernel<6, 4, R>), grid, dim3(256), 0, stream, t);
 }
 
+// the table of an i8q store: both operands as code matrices + scales (the node side kept under the pack key, like the
+// packed f32 operand), then the int8 GEMM.  The buffers are the workspace's operand buffers, which an index over an i8q
+// store uses for nothing else.
+static int tiny_table_i8q(const phnsw_index *ix, PhWorkspace &ws, const PhDistArgs &dist, const float *queries, uint32_t ldq,
+                          const uint32_t *qids, const uint32_t *order, uint32_t npos, const uint32_t *tnodes, uint32_t tn,
+                          uint32_t stride, float *D, hipStream_t stream, bool *kept) {
+  const uint32_t qtiles = (npos + 63u) / 64u, ntiles = (tn + 63u) / 64u;
+  const uint32_t kpad = (dist.ld + PH_I8T_KS - 1u) / PH_I8T_KS * PH_I8T_KS;
+  const size_t row_bytes = (size_t)kpad + 4u;  // codes, and the row's scale behind the code matrix
+  const float4 *pn_was = ws.tiny_pn;
+  if (grow(&ws.tiny_pq, &ws.tiny_pq_bytes, (size_t)qtiles * 64u * row_bytes) != hipSuccess ||
+      grow(&ws.tiny_pn, &ws.tiny_pn_bytes, (size_t)ntiles * 64u * row_bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    ws.tiny_pack_key.valid = false;
+    return 1;
+  }
+  PhTinyPackKey key;
+  key.valid = !tiny_keep_off();
+  key.nodes_epoch = ix->nodes_epoch;
+  key.vecs = dist.rows.base;
+  key.tnodes = tnodes;
+  key.ld = dist.ld;
+  key.tn = tn;
+  key.nv = kpad;
+  const PhTinyPackKey &have = ws.tiny_pack_key;
+  const bool pn_kept = ws.tiny_pn == pn_was && key.valid && have.valid && have.nodes_epoch == key.nodes_epoch &&
+                       have.vecs == key.vecs && have.tnodes == key.tnodes && have.ld == key.ld && have.tn == key.tn &&
+                       have.nv == key.nv;
+  ws.tiny_pack_key = key;
+  if (kept) *kept = pn_kept;
+  PhTinyQuantArgs k;
+  memset(&k, 0, sizeof(k));
+  k.rows = dist.rows;
+  k.nv4 = dist.nv4;
+  k.kw = kpad / 4u;
+  k.queries = queries;
+  k.ldq = ldq;
+  k.ids = qids;
+  k.order = order;
+  k.n = npos;
+  k.n_pad = qtiles * 64u;
+  k.codes = (uint32_t *)ws.tiny_pq;
+  k.scales = (float *)((char *)ws.tiny_pq + (size_t)k.n_pad * kpad);
+  hipLaunchKernelGGL(ph_tiny_quant_kernel, dim3(k.n_pad / 4u), dim3(256), 0, stream, k);
+  PhTinyI8Args m;
+  memset(&m, 0, sizeof(m));
+  m.cq = (const ph_i32x4 *)k.codes;
+  m.sq = k.scales;
+  k.queries = nullptr;
+  k.ids = tnodes;
+  k.order = nullptr;
+  k.n = tn;
+  k.n_pad = ntiles * 64u;
+  k.codes = (uint32_t *)ws.tiny_pn;
+  k.scales = (float *)((char *)ws.tiny_pn + (size_t)k.n_pad * kpad);
+  if (!pn_kept) hipLaunchKernelGGL(ph_tiny_quant_kernel, dim3(k.n_pad / 4u), dim3(256), 0, stream, k);
+  PH_HIP(hipGetLastError());
+  m.cn = (const ph_i32x4 *)k.codes;
+  m.sn = k.scales;
+  m.npos = npos;
+  m.tiny_n = tn;
+  m.stride = stride;
+  m.k16 = kpad / 16u;
+  m.metric = dist.metric;
+  m.D = D;
+  ws.tiny_table_g = 1;
+  hipLaunchKernelGGL(ph_tiny_table_i8_kernel, dim3(qtiles, ntiles), dim3(256), 0, stream, m);
+  PH_HIP(hipGetLastError());
+  return 0;
+}
+
 // D[p][t] = compare_vec(query of position p, Stored(tnodes[t])) for npos positions (position p = query order[p], or p
 // itself; raw queries or Stored ids), the per-hop path's bits: the matrix-core kernel where it applies, else the
 // vector-unit tile pass.  returns 1 (no error set) when its operand buffers cannot be allocated.
@@ -599,6 +789,7 @@ static int tiny_table(const phnsw_index *ix, PhWorkspace &ws, const PhDistArgs &
   if (const char *e = getenv("PHNSW_TINY_DBG")) t.dbg = (uint32_t)atoi(e);
   const uint32_t nv4 = dist.nv4;
   const int nv = nv4 <= 64 ? 1 : (nv4 <= 192 ? 3 : 6);
+  if (dist.rows.kind == PH_ROWS_I8Q) return tiny_table_i8q(ix, ws, dist, queries, ldq, qids, order, npos, tnodes, tn, stride, D, stream, kept);
   // dot-product metrics over whole 64-chunk rows go to the matrix cores (same bits, see above); the Euclidean
   // chain (fma(d, d, acc) of a difference) is not a product of the two operands and stays on the vector units, as
   // do ragged rows and launches of a handful of queries.  PHNSW_TINY_VALU=1 forces the vector kernel (tests).

@@ -233,14 +233,14 @@ class F16Store(VectorStore):
         return cls(store)
 
 
-class I8Store(VectorStore):
-    """int8 view of an f32 VectorStore (phnsw_store_create_i8): every row scalar-quantised with its own scale
-    (maxabs / 127), a quarter of the bytes per vector.  Distances dequantise (scale * code) and run the f32
-    arithmetic, so read() returns exactly the rows the searches see.  Search-only, like F16Store"""
+class _Int8Rows(VectorStore):
+    """what I8Store and I8QStore share: the rows of an f32 store as int8 codes with one f32 scale per row"""
+
+    _create = None  # the constructor of the kind
 
     def __init__(self, full):
         h = C.c_void_p()
-        check(lib().phnsw_store_create_i8(full._h, C.byref(h)))
+        check(getattr(lib(), self._create)(full._h, C.byref(h)))
         VectorStore.__init__(self, _handle=h, device=full.device)
         self.full = full
 
@@ -261,6 +261,28 @@ class I8Store(VectorStore):
     def scales(self):
         """the rows' scales [n] f32"""
         return self._read_i8()[1]
+
+
+class I8Store(_Int8Rows):
+    """int8 view of an f32 VectorStore (phnsw_store_create_i8): every row scalar-quantised with its own scale
+    (maxabs / 127), a quarter of the bytes per vector.  Distances dequantise (scale * code) and run the f32
+    arithmetic, so read() returns exactly the rows the searches see.  Search-only, like F16Store"""
+
+    _create = "phnsw_store_create_i8"
+
+
+class I8QStore(_Int8Rows):
+    """the rows of an I8Store, byte for byte (phnsw_store_create_i8q: same codes(), scales() and read()), searched
+    symmetrically: a distance quantises the query the way the rows were quantised and is
+    (scale_q * scale_r) * (integer dot product of the codes), put through the metric -- tests/i8q_reference.py restates
+    it.  Dot-product metrics only (an L2 store is refused).  Search-only, like I8Store"""
+
+    _create = "phnsw_store_create_i8q"
+
+
+def _reranked_kind(store):
+    """the name a converted store's re-ranked search calls carry"""
+    return "i8q" if isinstance(store, I8QStore) else ("i8" if isinstance(store, I8Store) else "f16")
 
 
 class SharedPqStore(VectorStore):
@@ -588,8 +610,9 @@ class Hnsw:
         return (ids, d, ln, st) if stats else (ids, d, ln)
 
     def search_batch_reranked(self, full, queries, sp=None, k=10):
-        """an index over an F16Store or I8Store: search it, recompute every result's distance on the f32 store `full`,
-        sort by (distance, id), keep the best k (phnsw_f16_search_batch / phnsw_i8_search_batch)
+        """an index over an F16Store, I8Store or I8QStore: search it, recompute every result's distance on the f32 store
+        `full`, sort by (distance, id), keep the best k (phnsw_f16_search_batch / phnsw_i8_search_batch /
+        phnsw_i8q_search_batch)
         -> ids[nq, k] u64, d[nq, k] f32, len[nq]"""
         sp = sp or SearchParameters()
         q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
@@ -598,14 +621,14 @@ class Hnsw:
         ids = np.empty((nq, k), dtype=np.uint64)
         d = np.empty((nq, k), dtype=np.float32)
         ln = np.zeros(nq, dtype=np.uint64)
-        fn = lib().phnsw_i8_search_batch if isinstance(self.store, I8Store) else lib().phnsw_f16_search_batch
+        fn = getattr(lib(), "phnsw_%s_search_batch" % _reranked_kind(self.store))
         check(fn(self._h, full._h, _p(q), nq, C.byref(sp), k, _p(ids), _p(d), _p(ln)))
         return ids, d, ln
 
     def search_batch_reranked_device(self, full, nq, sp, k, queries, ldq, out_ids, out_d, out_len, status, out_stats=0,
                                      stream=0):
         """zero-copy form of search_batch_reranked (device pointers as ints, u32 ids, rows of number_of_candidates)"""
-        fn = lib().phnsw_i8_search_batch_device if isinstance(self.store, I8Store) else lib().phnsw_f16_search_batch_device
+        fn = getattr(lib(), "phnsw_%s_search_batch_device" % _reranked_kind(self.store))
         check(fn(self._h, full._h, C.c_void_p(queries), ldq, nq, C.byref(sp), int(k), C.c_void_p(out_ids),
                  C.c_void_p(out_d), C.c_void_p(out_len), C.c_void_p(out_stats or None), C.c_void_p(status),
                  C.c_void_p(stream or None)))

@@ -337,6 +337,17 @@ extern "C" {
                                         out_d_dev: *mut c_float, out_len_dev: *mut u32, out_stats_dev: *mut u32,
                                         status_dev: *mut u32, stream: *mut c_void) -> c_int;
 
+    // ---- the same int8 rows against an int8 query: integer dot products, dot-product metrics only
+    pub fn phnsw_store_create_i8q(full: *const phnsw_store, out: *mut *mut phnsw_store) -> c_int;
+    pub fn phnsw_i8q_search_batch(ix: *const phnsw_index, full: *const phnsw_store, queries: *const c_float,
+                                  nq: u64, sp: *const phnsw_search_params, k: u64, out_ids: *mut u64,
+                                  out_d: *mut c_float, out_len: *mut u64) -> c_int;
+    pub fn phnsw_i8q_search_batch_device(ix: *const phnsw_index, full: *const phnsw_store,
+                                         queries_dev: *const c_float, ldq: u32, nq: u64,
+                                         sp: *const phnsw_search_params, k: u64, out_ids_dev: *mut u32,
+                                         out_d_dev: *mut c_float, out_len_dev: *mut u32, out_stats_dev: *mut u32,
+                                         status_dev: *mut u32, stream: *mut c_void) -> c_int;
+
     // ---- on-disk interchange (serialize.rs:33-209)
     pub fn phnsw_index_serialize(ix: *const phnsw_index, path: *const c_char) -> c_int;
     pub fn phnsw_index_deserialize(s: *mut phnsw_store, path: *const c_char, out: *mut *mut phnsw_index) -> c_int;

@@ -1,9 +1,9 @@
-"""f32 search against f16 and i8 search (and each + f32 re-rank) on the plain bench.py workload: the 1M x 768
+"""f32 search against f16, i8 and i8q search (and each + f32 re-rank) on the plain bench.py workload: the 1M x 768
 clustered "survey" set, the same seeds and build, ef 256 / probe_depth 8, 10 000-query batches, one stream and two
 streams (two batches in flight).  Every mode reports ms per step from device events after warm-up, recall@10
 against the exact top 10 of the f32 store, and the dispatches of its last descent.  One JSON line per mode.
 
-  python scripts/bench_f16.py --modes f32,f16,f16_rerank,i8,i8_rerank [--steps 20 --warmup 3] [--out FILE]
+  python scripts/bench_f16.py --modes f32,f16,f16_rerank,i8,i8_rerank,i8q,i8q_rerank [--steps 20 --warmup 3] [--out FILE]
 
 Mode f32 uses only calls that exist without the f16 and i8 stores, so this file copied onto an older checkout gives the
 baseline of the same run (pass --modes f32 there)."""
@@ -21,7 +21,7 @@ sys.path.insert(0, ROOT)
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--modes", default="f32,f16,f16_rerank,i8,i8_rerank")
+    ap.add_argument("--modes", default="f32,f16,f16_rerank,i8,i8_rerank,i8q,i8q_rerank")
     ap.add_argument("--vectors", dest="n", type=int, default=1_000_000)
     ap.add_argument("--dim", type=int, default=768)
     ap.add_argument("--queries", dest="nq", type=int, default=10_000)
@@ -67,13 +67,14 @@ def main():
             self.status = torch.empty(nq, dtype=torch.int32, device=dev)
 
     lanes = [Lane(), Lane()]
-    converted = {}  # "f16" / "i8" -> the index over that store, made when the first mode asks for it
+    converted = {}  # "f16" / "i8" / "i8q" -> the index over that store, made when the first mode asks for it
     row_bytes = {"f32": 4 * int(store.ld), "f16": 2 * int(store.ld), "i8": (4 + int(store.ld) + 15) // 16 * 16}
+    row_bytes["i8q"] = row_bytes["i8"]
     out_lines = []
     for mode in args.modes.split(","):
         kind = mode.split("_")[0]
         if kind != "f32" and kind not in converted:
-            low = (ph.F16Store if kind == "f16" else ph.I8Store).from_full(store)
+            low = {"f16": ph.F16Store, "i8": ph.I8Store, "i8q": ph.I8QStore}[kind].from_full(store)
             converted[kind] = ph.Hnsw.from_layers(low, [(l.nodes, l.neighbors) for l in index.layers], index.build_parameters)
         ix = index if kind == "f32" else converted[kind]
 
