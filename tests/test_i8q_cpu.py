@@ -69,6 +69,103 @@ def test_reference_distance_on_hand_made_values():
     np.testing.assert_array_equal(z, np.full(3, 0.5, dtype=np.float32))  # a query of zeros: scale 0, dot 0
 
 
+# ---------------------------------------------------------------- the inputs of tests/test_gpu_i8q_exhaustive.py
+# can tell a wrong kernel from a right one
+@pytest.mark.parametrize("dim", [1536, 1532])
+def test_saturated_rows_have_dot_products_past_2_to_the_24_that_tell_the_roundings_apart(dim):
+    rng = np.random.default_rng(dim)
+    rows, c, k = i8q_reference.saturated(200, dim, rng)
+    queries, cq, kq = i8q_reference.saturated(65, dim, rng)
+    for x, cx, kx in ((rows, c, k), (queries, cq, kq)):
+        codes, scales = quantize(x)
+        np.testing.assert_array_equal(codes, cx)
+        np.testing.assert_array_equal(bits(scales), bits(np.exp2(kx.astype(np.float64)).astype(np.float32)))
+    idot = i8q_reference.idots(cq, c)
+    i8q_reference.assert_saturated(idot)
+    rne = idot.astype(np.float32).astype(np.int64)  # numpy converts int64 -> f32 with round to nearest even
+    big = np.abs(idot) > 2 ** 24
+    odd = big & (idot % 2 != 0)
+    assert (rne[odd] % 4 == 0).all() and (np.abs(rne - idot)[odd] == 1).all()  # ties went to the even mantissa
+    trunc = np.sign(idot) * (np.abs(idot) // 2 * 2)          # toward zero: what a truncating conversion gives past 2^24
+    away = np.sign(idot) * ((np.abs(idot) + 1) // 2 * 2)     # half away from zero
+    assert int((rne != trunc)[big].sum()) >= 50 and int((rne != away)[big].sum()) >= 50
+    # an f32 running sum of the 1536 products loses what the integer sum keeps
+    run = np.zeros(idot.shape, dtype=np.float32)
+    for j in range(dim):
+        run += (cq[:, j].astype(np.float32)[:, None] * c[:, j].astype(np.float32)[None, :])
+    assert int((run != idot.astype(np.float32)).sum()) >= 50
+    # and the distance keeps every bit of the converted sum: two dot products a float apart never share a distance
+    for metric in (oracle.METRIC_COSINE_HALF, oracle.METRIC_ONE_MINUS_DOT):
+        d = i8q_reference.distance_codes(cq[0], np.exp2(np.float32(kq[0])), c, np.exp2(k.astype(np.float32)), metric)
+        half = np.float32(2.0) if metric == oracle.METRIC_COSINE_HALF else np.float32(1.0)
+        back = -(d * half) / (np.exp2(np.float32(kq[0])) * np.exp2(k.astype(np.float32)))
+        np.testing.assert_array_equal(back[big[0]].astype(np.int64), rne[0][big[0]])
+
+
+@pytest.mark.parametrize("dim", [4, 6, 100, 132, 260, 1536])
+def test_quantiser_edge_queries_quantise_to_their_hand_written_codes_and_scales(dim):
+    edges = i8q_reference.quantiser_edges(dim)
+    assert [e[0] for e in edges] == ["ties", "max_negative", "max_first", "max_last", "all_equal", "one_component",
+                                     "subnormal", "huge", "zeros"]
+    for name, q, want_codes, want_scale, row_scale in edges:
+        codes, scales = quantize(q[None, :])
+        np.testing.assert_array_equal(codes[0], want_codes, err_msg=name)
+        np.testing.assert_array_equal(bits(scales), bits(want_scale), err_msg=name)
+    by = {e[0]: e for e in edges}
+    tiny = np.finfo(np.float32).tiny
+    assert 0 < np.abs(by["subnormal"][1]).max() < tiny and 0 < by["subnormal"][3] < tiny
+    assert np.abs(by["huge"][1]).max() > 1.0e18
+    assert by["max_negative"][1].min() == -np.abs(by["max_negative"][1]).max() and by["max_negative"][2].min() == -127
+    assert by["max_first"][2][0] == 127 and by["max_last"][2][dim - 1] == 127
+    assert set(by["ties"][2].tolist()) >= {0, 2, -2}  # k + 1/2 for even k, odd k and a negative one, at the least
+    # over general rows times the case's power of two: every distance finite, no product of scales lost to underflow, and
+    # the query's codes in the distance bits -- rows with different dot products get different distances
+    rows = oracle.synth_rows(0, 200, dim)[:, :dim]
+    for name, q, want_codes, want_scale, row_scale in edges:
+        codes, scales = quantize(rows * np.float32(row_scale))
+        prod = (want_scale * scales).astype(np.float32)
+        for metric in (oracle.METRIC_COSINE_HALF, oracle.METRIC_ONE_MINUS_DOT):
+            d = i8q_reference.distance(q, codes, scales, metric)
+            assert np.isfinite(d).all(), name
+            if name == "zeros":
+                assert (prod == 0).all() and (d == (0.5 if metric == oracle.METRIC_COSINE_HALF else 1.0)).all()
+                continue
+            assert (prod >= tiny).all(), name + ": sq * sr is a normal number"
+            idot = i8q_reference.idots(want_codes[None, :], codes)[0]
+            assert len(np.unique(bits(d))) >= 0.9 * len(np.unique(idot)), name
+
+
+RING_SHAPES = [(3, 6, 1), (33, 100, 1), (65, 128, 1), (129, 132, 1), (200, 1536, 1), (300, 768, 1), (200, 100, 12), (200, 6, 32)]
+
+
+@pytest.mark.parametrize("n,dim,reach", RING_SHAPES)
+def test_a_ring_searched_with_ef_n_evaluates_and_returns_every_node(n, dim, reach):
+    """the premise of the exhaustive GPU test, against the unchanged oracle on lattice rows (where its f32 arithmetic is
+    the i8q distance): length n, n evaluations, and ids and distance bits those of i8q_reference.all_pairs"""
+    rng = np.random.default_rng(n + dim)
+    rows, c, k = i8q_reference.lattice(n, dim, rng)
+    q, cq, kq = i8q_reference.lattice(7, dim, rng)
+    assert int(np.abs(c.astype(np.int64)).sum(axis=1).max()) * 127 < 2 ** 24
+    codes, scales = quantize(rows)
+    ix = oracle.Index(rows, sum_mode=oracle.SUM_BLOCKED64)
+    for nodes, nb in i8q_reference.circulant(n, reach):
+        ix.push_layer(nodes, nb, nb.shape[1])
+    qids = np.arange(0, n, max(1, n // 5), dtype=np.uint64)  # the first is the entry vector, which exclude does not drop
+    pd = 2 if reach == 1 else n + 1
+    for kw in (dict(queries=q), dict(qids=qids), dict(qids=qids, exclude=qids)):
+        ci, cd, cl, cs = ix.search(sp=(n, n, pd), stats=True, **kw)
+        wi, wd = i8q_reference.ranked(i8q_reference.matrix(q, codes, scales, oracle.METRIC_COSINE_HALF, kw.get("qids")),
+                                      kw.get("exclude"))
+        assert (cs[:, 0] == n).all()
+        if reach == 1:
+            assert (cs[:, 1] == n).all()  # n - 2 hops that find a node, then two that find none
+        for i in range(len(cl)):
+            w = len(wi[i])
+            assert w == (n - 1 if "exclude" in kw and i > 0 else n) and cl[i] == w
+            np.testing.assert_array_equal(ci[i, :w].astype(np.int64), wi[i])
+            np.testing.assert_array_equal(bits(cd[i, :w]), bits(wd[i]))
+
+
 def test_new_prototypes_are_declared_everywhere_with_matching_argument_counts():
     strip = lambda s: re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", s, flags=re.S))
     header = strip(open(os.path.join(ROOT, "include", "phnsw.h")).read())
