@@ -164,7 +164,7 @@ extern "C" int phnsw_store_create(const float *rows, uint64_t n, uint32_t dim, i
 // or build may be running on an index over this store; existing VectorIds keep their rows
 extern "C" int phnsw_store_append(phnsw_store *s, const float *rows, uint64_t count, uint64_t *out_first_id) try {
   if (int rc = ph_search_only_unsupported(s, "phnsw_store_append")) return rc;
-  if (!s || !rows || !s->rows || !s->owns_rows || s->n + count >= 0x7FFFFFFFull) {
+  if (!s || !rows || !ph_store_f32(s) || !s->owns_rows || s->n + count >= 0x7FFFFFFFull) {
     ph_set_error("phnsw_store_append: needs an f32 store created by phnsw_store_create* that owns its rows, n < 2^31");
     return PHNSW_E_INVALID;
   }
@@ -304,7 +304,7 @@ extern "C" int phnsw_store_read(const phnsw_store *s, uint64_t first, uint64_t c
     if (!count) return 0;
     return ph_converted_store_read(s, first, count, out);
   }
-  if (!s || !out || !s->rows || first + count > s->n) {
+  if (!s || !out || !ph_store_f32(s) || first + count > s->n) {
     ph_set_error("phnsw_store_read: range out of bounds (or a product-quantised store: use phnsw_pq_read)");
     return PHNSW_E_INVALID;
   }
@@ -723,7 +723,7 @@ int ph_search_device(const phnsw_index *ix, const float *queries_dev, uint32_t l
   }
   // (not for PQ stores: their searches are not bound by where rows come from, and every launch
   // would build the per-query table again)
-  const bool split = (ix->store->rows || ph_store_converted(ix->store)) && !a.order && !knn_mode && !out_stride && !out_index && first_big < a.n_layers &&
+  const bool split = (ph_store_f32(ix->store) || ph_store_converted(ix->store)) && !a.order && !knn_mode && !out_stride && !out_index && first_big < a.n_layers &&
                      nq >= two_launch_min() &&
                      !getenv("PHNSW_NO_LOCALITY");
   if (split) {
@@ -752,7 +752,7 @@ int ph_search_device(const phnsw_index *ix, const float *queries_dev, uint32_t l
     }
     a.probe_out = probe_dev;
     a.probe_pos = nullptr;
-    if (!knn_mode && ix->store->rows && nq >= 1000) {
+    if (!knn_mode && ph_store_f32(ix->store) && nq >= 1000) {
       rc = ph_layer_anchor_pos(ix->store, mix->layers[a.n_layers - 1]);
       if (rc) return rc;
       a.probe_pos = ix->layers[a.n_layers - 1].pos;

@@ -163,7 +163,7 @@ static thread_local float g_bf_gemm_ms = 0.f;
 extern "C" int phnsw_bruteforce_topk_device(const phnsw_store *s, const float *queries_dev, uint32_t ldq, uint64_t nq,
                                             uint32_t k, uint32_t *out_ids_dev, float *out_d_dev, void *stream) try {
   if (int rc = ph_search_only_unsupported(s, "phnsw_bruteforce_topk")) return rc;
-  if (!s || !s->rows || !queries_dev || !out_ids_dev || !out_d_dev || k == 0 || k > BF_KMAX || k > s->n ||
+  if (!s || !ph_store_f32(s) || !queries_dev || !out_ids_dev || !out_d_dev || k == 0 || k > BF_KMAX || k > s->n ||
       nq == 0 || nq > 0xFFFFFFFFull || ldq < s->ld || (ldq % 4) || s->metric == PHNSW_METRIC_L2) {
     ph_set_error("phnsw_bruteforce_topk: need an f32 store with a dot-product metric, 1 <= k <= %d, ldq %% 4 == 0",
                  BF_KMAX);
@@ -374,7 +374,7 @@ void ph_store_anchors_free(phnsw_store *s) {
 // whether a layer carries cells at all: not the small ones, not PQ stores, not the L2 metric (the GEMM scores dot
 // products)
 bool ph_layer_wants_cells(const phnsw_store *s, uint32_t n_nodes) {
-  return n_nodes >= PH_POS_MIN && (s->rows || ph_store_converted(s)) && s->n >= 65536 && s->metric != PHNSW_METRIC_L2 && !getenv("PHNSW_NO_LOCALITY");
+  return n_nodes >= PH_POS_MIN && (ph_store_f32(s) || ph_store_converted(s)) && s->n >= 65536 && s->metric != PHNSW_METRIC_L2 && !getenv("PHNSW_NO_LOCALITY");
 }
 
 // out_pos[i] = chain rank of the nearest anchor of node first + i, for count nodes of the layer (the sharded build
@@ -392,7 +392,7 @@ int ph_layer_cells_range(const phnsw_store *cs, const PhLayerHost &L, uint32_t f
   if (e == hipSuccess) {
     for (uint32_t at = 0; at < count; at += QC) {
       const uint32_t cnt = std::min(QC, count - at);
-      const float *Q = s->rows ? s->rows + (uint64_t)(first + at) * ld : nullptr;  // identity layer: node i is row i
+      const float *Q = ph_store_f32(s) ? s->rows + (uint64_t)(first + at) * ld : nullptr;  // identity layer: node i is row i
       if (ph_store_converted(s)) {  // f16 / i8 store: the layer's rows as f32 (a copy even for an identity layer)
         (void)ph_converted_gather_rows(s, L.identity ? nullptr : L.nodes + first + at, first + at, cnt, qrows);
         Q = qrows;

@@ -451,8 +451,7 @@ __global__ void ph_link_targets_kernel(const uint32_t *nodes, uint32_t n, const 
 
 // ------------------------------------------------------------------ host: shared steps
 
-static int nv_for(uint32_t nv4) { return nv4 <= 64 ? 1 : (nv4 <= 192 ? 3 : (nv4 <= 384 ? 6 : 0)); }
-static bool store_supported(const phnsw_store *s) { return s->codes ? true : nv_for(s->ld / 4) != 0; }
+static bool store_supported(const phnsw_store *s) { return ph_store_pq(s) || ph_chunk_count(s->ld / 4) != 0; }
 // resident one-wave blocks a PQ kernel can have per chip: the lookup table dominates the LDS
 static uint32_t pq_grid(const phnsw_store *s, uint32_t want) {
   size_t per = ph_pq_lds_bytes(s) + 8 * 1024;
@@ -462,7 +461,7 @@ static uint32_t pq_grid(const phnsw_store *s, uint32_t want) {
 
 template <typename K1, typename K3, typename K6, typename KQ, typename... Args>
 static int launch_by_policy(const phnsw_store *s, dim3 g, K1 k1, K3 k3, K6 k6, KQ kq, Args... args) {
-  if (s->codes) {
+  if (ph_store_pq(s)) {
     size_t lds = ph_pq_lds_bytes(s);
     if (lds > 48 * 1024) {
       hipError_t e = hipFuncSetAttribute((const void *)kq, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -470,7 +469,7 @@ static int launch_by_policy(const phnsw_store *s, dim3 g, K1 k1, K3 k3, K6 k6, K
     }
     hipLaunchKernelGGL(kq, g, dim3(64), lds, 0, args...);
   } else {
-    switch (nv_for(s->ld / 4)) {
+    switch (ph_chunk_count(s->ld / 4)) {
       case 1:
         hipLaunchKernelGGL(k1, g, dim3(64), 0, 0, args...);
         break;
@@ -481,8 +480,7 @@ static int launch_by_policy(const phnsw_store *s, dim3 g, K1 k1, K3 k3, K6 k6, K
         hipLaunchKernelGGL(k6, g, dim3(64), 0, 0, args...);
         break;
       default:
-        ph_set_error("dim %u unsupported (max 1536)", s->dim);
-        return PHNSW_E_UNSUPPORTED;
+        return ph_dim_unsupported(s->dim);
     }
   }
   PH_HIP(hipGetLastError());
@@ -533,7 +531,7 @@ static int ensure_row_dist(phnsw_index *ix, PhLayerHost &L) {
   const phnsw_store *s = ix->store;
   PH_HIP(hipMalloc(&L.nbr_dist, (size_t)L.n_nodes * L.W * 4));
   // a PQ table takes most of a CU's LDS: one resident wave per CU is all that fits
-  dim3 g(s->codes ? pq_grid(s, L.n_nodes) : wave_grid(L.n_nodes));
+  dim3 g(ph_store_pq(s) ? pq_grid(s, L.n_nodes) : wave_grid(L.n_nodes));
   return launch_by_policy(s, g, ph_row_dist_kernel<DistF32<1>>, ph_row_dist_kernel<DistF32<3>>,
                           ph_row_dist_kernel<DistF32<6>>, ph_row_dist_kernel<DistPQ>, ph_dist_args(s), L.nodes, L.n_nodes,
                           L.W, L.neighbors, L.nbr_dist);
@@ -730,12 +728,12 @@ void ph_pending_free(phnsw_index *ix) { pending_drop(ix); }
 // proposals by (distance, id): that needs d(a, b) == d(b, a) bit for bit.  The 8-bit PQ table
 // scales by the QUERY's table, so it is for searching a graph built in mode 0 or 1.
 static int symmetric_store(const phnsw_store *s) {
-  if (s->codes16) {
+  if (ph_store_pq_shared(s)) {
     ph_set_error("a shared-codebook PQ store is searched, not built on: build the index over "
                  "phnsw_pq_shared_reconstruct_store (identical distances) and adopt it with phnsw_index_from_layers");
     return PHNSW_E_UNSUPPORTED;
   }
-  if (s->codes && s->pq_table_f16 == 2) {
+  if (ph_store_pq(s) && s->pq_table_f16 == 2) {
     ph_set_error("8-bit PQ tables (phnsw_pq_set_table_mode 2) are asymmetric: build / link in mode 0 or 1, then switch");
     return PHNSW_E_UNSUPPORTED;
   }
@@ -754,10 +752,7 @@ static int layer_begin_impl(phnsw_index *ix, const uint64_t *vids, uint64_t n64,
     ph_set_error("generate_layer: more than %d layers", PH_MAX_LAYERS);
     return PHNSW_E_UNSUPPORTED;
   }
-  if (!store_supported(s)) {
-    ph_set_error("dim %u unsupported (max 1536)", s->dim);
-    return PHNSW_E_UNSUPPORTED;
-  }
+  if (!store_supported(s)) return ph_dim_unsupported(s->dim);
   const uint32_t K = (uint32_t)bp->initial_partition_search.number_of_candidates;
   if (!ix->layers.empty() && (K == 0 || K > 64)) {
     ph_set_error("initial_partition_search.number_of_candidates must be 1..64 (got %u)", K);
@@ -919,7 +914,7 @@ static int layer_seed_impl(phnsw_index *ix, const phnsw_build_params *bp, const 
   PH_TRY(ph_layer_range_order(P->L, first, count, &a.order));
   a.rows = out_rows;
   a.rows_d = out_rows_d;
-  dim3 g(s->codes ? pq_grid(s, count) : wave_grid(count));
+  dim3 g(ph_store_pq(s) ? pq_grid(s, count) : wave_grid(count));
   PH_TRY(launch_by_policy(s, g, ph_seed_rows_kernel<DistF32<1>>, ph_seed_rows_kernel<DistF32<3>>,
                           ph_seed_rows_kernel<DistF32<6>>, ph_seed_rows_kernel<DistPQ>, a));
   PH_HIP(hipDeviceSynchronize());
@@ -1374,7 +1369,7 @@ static int filter_promotion_candidates_impl(phnsw_index *ix, uint32_t lft, const
     const uint32_t bc = std::min(B, H - c0);
     const size_t prev = sel.size();
     PH_TRY(search_stored(ix, cand_d.p + c0, bc, sp, lft, nullptr, r_id.p, r_d.p, r_len.p, 1, nullptr));
-    dim3 g(s->codes ? pq_grid(s, bc) : wave_grid(bc));
+    dim3 g(ph_store_pq(s) ? pq_grid(s, bc) : wave_grid(bc));
     if (prev)
       PH_TRY(launch_by_policy(s, g, ph_cover_kernel<DistF32<1>>, ph_cover_kernel<DistF32<3>>, ph_cover_kernel<DistF32<6>>,
                               ph_cover_kernel<DistPQ>, ph_dist_args(s), cand_d.p + c0, bc, (const uint32_t *)sel_d.p,

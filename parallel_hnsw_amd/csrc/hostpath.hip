@@ -207,6 +207,14 @@ void plan_chunks(uint64_t nq, std::vector<uint64_t> &bounds) {
 
 }  // namespace
 
+int ph_take_launch(const uint32_t *ids, const float *d, uint32_t ef, uint32_t k, uint64_t n, uint64_t *ids64, float *dk,
+                   hipStream_t s) {
+  hipLaunchKernelGGL(ph_take_kernel, dim3((uint32_t)std::min<uint64_t>((n * k + 255) / 256, 4096)), dim3(256), 0, s, ids, d, ef,
+                     k, n, ids64, dk);
+  PH_HIP(hipGetLastError());
+  return 0;
+}
+
 void ph_host_stages_free(phnsw_index *ix) {
   for (PhHostStage *st : ix->stages) {
     slot_free(st->slot[0]);
@@ -261,9 +269,7 @@ int ph_search_host(const phnsw_index *ix, const float *queries, const uint64_t *
     if (!sl.busy) return 0;
     sl.busy = false;
     const uint64_t c0 = sl.c0, cnt = sl.cnt, N = sl.cnt;  // the per-query words are laid out [7][cnt]
-    hipLaunchKernelGGL(ph_take_kernel, dim3((uint32_t)std::min<uint64_t>((cnt * k + 255) / 256, 4096)), dim3(256), 0, sl.stream,
-                       sl.ids, sl.d, ef, k, cnt, sl.ids64, sl.dk);
-    PH_HIP(hipGetLastError());
+    PH_TRY(ph_take_launch(sl.ids, sl.d, ef, k, cnt, sl.ids64, sl.dk, sl.stream));
     // len | status | index | stats sit contiguously at rows 2..6 of `small`
     PH_HIP(hipMemcpyAsync(sl.h_small + 2 * N, sl.small + 2 * N, 5 * N * 4, hipMemcpyDeviceToHost, sl.stream));
     PH_HIP(hipMemcpyAsync(out_ids + c0 * k, sl.ids64, (size_t)cnt * k * 8, hipMemcpyDeviceToHost, sl.stream));

@@ -34,34 +34,34 @@ __global__ __launch_bounds__(64) void ph_distance_batch_kernel(PhDistArgs da, co
 template <template <int, int> class D>
 static int distance_batch_rows(const phnsw_store *st, const PhDistArgs &da, const float *q_dev, uint32_t query_id,
                                const uint32_t *ids_dev, uint32_t k, float *out_dev, hipStream_t s) {
-  const uint32_t nv4 = st->ld / 4;
   const uint32_t blocks = std::min<uint32_t>((k + 63) / 64, 4096);
 #define PH_LAUNCH(NV)                                                                                               \
   hipLaunchKernelGGL((ph_distance_batch_kernel<D<NV, 4>>), dim3(blocks), dim3(64), 0, s, da, q_dev, query_id, ids_dev, \
                      k, st->n, out_dev)
-  if (nv4 <= 64)
-    PH_LAUNCH(1);
-  else if (nv4 <= 192)
-    PH_LAUNCH(3);
-  else if (nv4 <= 384)
-    PH_LAUNCH(6);
-  else {
-    ph_set_error("dim %u unsupported (max 1536)", st->dim);
-    return PHNSW_E_UNSUPPORTED;
+  switch (ph_chunk_count(st->ld / 4)) {
+    case 1: PH_LAUNCH(1); break;
+    case 3: PH_LAUNCH(3); break;
+    case 6: PH_LAUNCH(6); break;
+    default: return ph_dim_unsupported(st->dim);
   }
 #undef PH_LAUNCH
   return 0;
 }
 
+int ph_dim_unsupported(uint32_t dim) {
+  ph_set_error("dim %u unsupported (max 1536)", dim);
+  return PHNSW_E_UNSUPPORTED;
+}
+
 int ph_distance_batch(const phnsw_store *st, const float *q_dev, uint32_t query_id, const uint32_t *ids_dev, uint32_t k,
                       float *out_dev, hipStream_t s) {
   if (k == 0) return 0;
-  if (st->codes16) {
+  if (ph_store_pq_shared(st)) {
     ph_set_error("distance batches over a shared-codebook PQ store are not supported; use its reconstruction store");
     return PHNSW_E_UNSUPPORTED;
   }
   PhDistArgs da = ph_dist_args(st);
-  if (st->codes) {
+  if (ph_store_pq(st)) {
     size_t lds = ph_pq_lds_bytes(st);
     if (lds > 48 * 1024)
       PH_HIP(hipFuncSetAttribute((const void *)ph_distance_batch_kernel<DistPQ>,

@@ -75,6 +75,10 @@ static inline const char *ph_rows_name(int kind) {
   static const char *const names[] = {"f32", "f16", "i8", "product-quantised", "shared-codebook product-quantised", "i8q"};
   return names[kind];
 }
+// float4 chunks a lane holds of a row of nv4 float4s: the three shapes the row kernels are instantiated for (0: none;
+// a launch switches on this value, one case per instance)
+static inline int ph_chunk_count(uint32_t nv4) { return nv4 <= 64 ? 1 : (nv4 <= 192 ? 3 : (nv4 <= 384 ? 6 : 0)); }
+int ph_dim_unsupported(uint32_t dim);  // sets "dim unsupported (max 1536)", returns PHNSW_E_UNSUPPORTED (misc.hip)
 // where the rows of a row kind are: one base pointer, one stride in bytes
 struct PhRows {
   const void *base;  // nullptr for a PQ store
@@ -372,6 +376,11 @@ int ph_layer_range_order(PhLayerHost &L, uint32_t first, uint32_t count, const u
 
 // a search-only row store (f16, i8 or i8q): searched like the f32 store, its rows converted to f32 where a GEMM or a host reads them
 static inline bool ph_store_converted(const phnsw_store *s) { return ph_rows_converted(s->kind); }
+// the other kinds.  `rows` / `codes` / `codes16` are non-null exactly on an f32 / PQ / shared-codebook PQ store (every
+// creator allocates n > 0 rows); a pointer is still what a hipFree or an ownership rule asks
+static inline bool ph_store_f32(const phnsw_store *s) { return s->kind == PH_ROWS_F32; }
+static inline bool ph_store_pq(const phnsw_store *s) { return s->kind == PH_ROWS_PQ; }
+static inline bool ph_store_pq_shared(const phnsw_store *s) { return s->kind == PH_ROWS_PQ_SHARED; }
 // converted stores (rowstore.hip): rows of `ids_dev` (nullptr: rows first .. first + cnt) widened / dequantised into
 // [cnt][ld] f32 rows; a range of the store converted into a dense host array
 int ph_converted_gather_rows(const phnsw_store *s, const uint32_t *ids_dev, uint32_t first, uint32_t cnt, float *out_dev);
@@ -441,7 +450,7 @@ static inline bool ph_pq_global_tables() {
   return !(e && e[0] == 'l');
 }
 static inline size_t ph_pq_lds_bytes(const phnsw_store *s) {
-  return s->codes ? (size_t)s->pq_m * s->pq_ksub * (s->pq_table_f16 == 2 ? 1 : (s->pq_table_f16 ? 2 : 4)) : 0;
+  return ph_store_pq(s) ? (size_t)s->pq_m * s->pq_ksub * (s->pq_table_f16 == 2 ? 1 : (s->pq_table_f16 ? 2 : 4)) : 0;
 }
 
 // sharded.hip: rank r's share of n items, and a synchronous all-gather of device blocks over any transport
@@ -457,6 +466,10 @@ int ph_synth_clustered_rows(float *rows_dev, uint64_t first, uint64_t count, uin
 int ph_distance_batch(const phnsw_store *st, const float *q_dev, uint32_t query_id, const uint32_t *ids_dev,
                       uint32_t k, float *out_dev, hipStream_t s);
 int ph_fill_u32(uint32_t *p, uint32_t v, uint64_t n, hipStream_t s);
+// rows of `ef` results -> the leading k of each of the n rows as u64 ids (PH_EMPTY32 -> PHNSW_EMPTY) + distances,
+// [n][k] (ph_take_kernel, hostpath.hip)
+int ph_take_launch(const uint32_t *ids, const float *d, uint32_t ef, uint32_t k, uint64_t n, uint64_t *ids64, float *dk,
+                   hipStream_t s);
 int ph_scatter_vec2node(const uint32_t *nodes, uint32_t n, uint32_t *vec2node, hipStream_t s);
 int ph_count_nan(const float *rows, uint64_t n_floats, uint32_t *out_count_dev, hipStream_t s);
 

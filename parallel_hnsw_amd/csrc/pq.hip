@@ -19,7 +19,8 @@
 //   ph_pq_gather_codebook_kernel   random_centroids, per sub-space
 //   ph_pq_encode_kernel            Quantizer::quantize for every vector, one wave per vector
 //   ph_pq_reconstruct_kernel       Quantizer::reconstruct
-//   ph_pq_rerank_kernel            the re-rank + sort tail of QuantizedHnsw::search
+//   ph_pq_rerank_kernel            the re-rank + sort tail of QuantizedHnsw::search, and of the f16 / i8 / i8q re-ranked
+//                                  searches: one launch (rerank_launch), one host form (reranked_search_host)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -217,7 +218,7 @@ extern "C" int phnsw_store_create_pq_sharded(phnsw_store *full, uint32_t m, uint
                                              uint32_t kmeans_iters, uint64_t sample, const phnsw_comm *comm,
                                              phnsw_store **out) try {
   if (int rc = ph_search_only_unsupported(full, "phnsw_store_create_pq")) return rc;
-  if (!full || !out || full->codes || !full->rows || m == 0 || ksub == 0 || ksub > 256 || (m % 4) ||
+  if (!full || !out || !ph_store_f32(full) || m == 0 || ksub == 0 || ksub > 256 || (m % 4) ||
       (full->dim % m) || ksub > full->n) {
     ph_set_error("phnsw_store_create_pq: need an f32 store, m %% 4 == 0, dim %% m == 0, 1 <= ksub <= min(256, n)");
     return PHNSW_E_INVALID;
@@ -376,7 +377,7 @@ extern "C" int phnsw_store_create_pq_shared_sharded(phnsw_store *full, uint32_t 
                                                     const phnsw_search_params *quantized_search, int centroid_metric,
                                                     const phnsw_comm *comm, phnsw_store **out) try {
   if (int rc = ph_search_only_unsupported(full, "phnsw_store_create_pq_shared")) return rc;
-  if (!full || !out || !full->rows || !centroid_bp || !quantized_search || dsub == 0 || (dsub % 4) || (full->dim % dsub) ||
+  if (!full || !out || !ph_store_f32(full) || !centroid_bp || !quantized_search || dsub == 0 || (dsub % 4) || (full->dim % dsub) ||
       full->ld != full->dim || n_centroids == 0 || n_centroids > 65535 || n_centroids > full->n ||
       quantized_search->number_of_candidates == 0 || quantized_search->number_of_candidates > 1024 ||
       quantized_search->probe_depth == 0 || centroid_metric < 0 || centroid_metric > 2) {
@@ -480,7 +481,7 @@ extern "C" int phnsw_store_create_pq_shared(phnsw_store *full, uint32_t dsub, ui
 } catch (...) { return ph_caught(); }
 
 extern "C" int phnsw_pq_shared_read(const phnsw_store *s, uint16_t *codes, float *codebook) try {
-  if (!s || !s->codes16) {
+  if (!s || !ph_store_pq_shared(s)) {
     ph_set_error("not a shared-codebook product-quantised store");
     return PHNSW_E_INVALID;
   }
@@ -494,7 +495,7 @@ extern "C" int phnsw_pq_shared_read(const phnsw_store *s, uint16_t *codes, float
 // bits as over the codes (DistPQS), so the Hnsw over the quantised vectors (pq.rs:336-338) is built on it with
 // the full-precision kernels and adopted over the codes (phnsw_index_from_layers); destroy it afterwards
 extern "C" int phnsw_pq_shared_reconstruct_store(const phnsw_store *s, phnsw_store **out) try {
-  if (!s || !s->codes16 || !out) {
+  if (!s || !ph_store_pq_shared(s) || !out) {
     ph_set_error("phnsw_pq_shared_reconstruct_store: needs a shared-codebook product-quantised store");
     return PHNSW_E_INVALID;
   }
@@ -528,7 +529,7 @@ extern "C" int phnsw_pq_shared_reconstruct_store(const phnsw_store *s, phnsw_sto
 // quantised distances; a graph must be built and searched in the same mode.  The oracle mirrors
 // every mode bit for bit.
 extern "C" int phnsw_pq_set_table_mode(phnsw_store *s, int mode) try {
-  if (!s || !s->codes || mode < 0 || mode > 2) {
+  if (!s || !ph_store_pq(s) || mode < 0 || mode > 2) {
     ph_set_error("phnsw_pq_set_table_mode: needs a product-quantised store and mode 0 (f32), 1 (f16) or 2 (8-bit)");
     return PHNSW_E_INVALID;
   }
@@ -544,7 +545,7 @@ extern "C" int phnsw_pq_set_table_f16(phnsw_store *s, int on) try { return phnsw
 // Quantizer::quantize  pq.rs:61-71 for arbitrary vectors (exact nearest centroid per sub-space,
 // ties to the smaller centroid id) and Quantizer::reconstruct  pq.rs:73-81
 extern "C" int phnsw_pq_quantize(const phnsw_store *s, const float *rows, uint64_t n, uint8_t *out_codes) try {
-  if (!s || !s->codes || !rows || !out_codes) {
+  if (!s || !ph_store_pq(s) || !rows || !out_codes) {
     ph_set_error("phnsw_pq_quantize: needs a product-quantised store, rows and an output buffer");
     return PHNSW_E_INVALID;
   }
@@ -570,7 +571,7 @@ extern "C" int phnsw_pq_quantize(const phnsw_store *s, const float *rows, uint64
 } catch (...) { return ph_caught(); }
 
 extern "C" int phnsw_pq_reconstruct(const phnsw_store *s, const uint8_t *codes, uint64_t n, float *out_rows) try {
-  if (!s || !s->codes || !codes || !out_rows) {
+  if (!s || !ph_store_pq(s) || !codes || !out_rows) {
     ph_set_error("phnsw_pq_reconstruct: needs a product-quantised store, codes and an output buffer");
     return PHNSW_E_INVALID;
   }
@@ -596,7 +597,7 @@ extern "C" int phnsw_pq_reconstruct(const phnsw_store *s, const uint8_t *codes, 
 } catch (...) { return ph_caught(); }
 
 extern "C" int phnsw_pq_info(const phnsw_store *s, uint32_t *m, uint32_t *ksub, uint32_t *dsub) try {
-  if (!s || (!s->codes && !s->codes16)) {
+  if (!s || (!ph_store_pq(s) && !ph_store_pq_shared(s))) {
     ph_set_error("not a product-quantised store");
     return PHNSW_E_INVALID;
   }
@@ -607,7 +608,7 @@ extern "C" int phnsw_pq_info(const phnsw_store *s, uint32_t *m, uint32_t *ksub, 
 } catch (...) { return ph_caught(); }
 
 extern "C" int phnsw_pq_read(const phnsw_store *s, uint8_t *codes, float *codebook) try {
-  if (!s || !s->codes) {
+  if (!s || !ph_store_pq(s)) {
     ph_set_error("not a product-quantised store");
     return PHNSW_E_INVALID;
   }
@@ -618,166 +619,11 @@ extern "C" int phnsw_pq_read(const phnsw_store *s, uint8_t *codes, float *codebo
   return 0;
 } catch (...) { return ph_caught(); }
 
-// QuantizedHnsw::search  pq.rs:346-364 for a batch: (optionally quantise the query like the
-// reference :351-352, default = asymmetric: the raw query meets the codes), search the graph
-// over the code rows, re-rank with the full-precision store, sort by (d, id).
-extern "C" int phnsw_pq_search_batch(const phnsw_index *ix, const phnsw_store *full, const float *queries, uint64_t nq,
-                                     const phnsw_search_params *sp, int quantize_query, uint64_t *out_ids,
-                                     float *out_d, uint64_t *out_len, uint64_t *out_stats) try {
-  if (!ix || !full || !queries || !sp || !out_ids || !out_d || !out_len || (!ix->store->codes && !ix->store->codes16) || !full->rows ||
-      full->n != ix->store->n || full->dim != ix->store->dim || nq > 0xFFFFFFFFull || sp->number_of_candidates == 0 ||
-      sp->number_of_candidates > 1024 || sp->probe_depth == 0) {
-    ph_set_error("phnsw_pq_search_batch: need an index over a PQ store, its full-precision store and valid parameters");
-    return PHNSW_E_INVALID;
-  }
-  if (nq == 0) return 0;
-  const phnsw_store *ps = ix->store;
-  PH_HIP(hipSetDevice(ps->device));
-  const uint32_t ef = (uint32_t)sp->number_of_candidates;
-  float *qd = nullptr, *qq = nullptr, *od = nullptr;
-  uint32_t *oid = nullptr, *olen = nullptr, *ost = nullptr, *ostat = nullptr;
-  uint8_t *qcodes = nullptr;
-  int rc = 0;
-  hipError_t e = hipMalloc(&qd, (size_t)nq * full->ld * 4);
-  if (e == hipSuccess && full->ld != full->dim) e = hipMemset(qd, 0, (size_t)nq * full->ld * 4);
-  if (e == hipSuccess)
-    e = hipMemcpy2D(qd, (size_t)full->ld * 4, queries, (size_t)full->dim * 4, (size_t)full->dim * 4, nq,
-                    hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc(&oid, (size_t)nq * ef * 4);
-  if (e == hipSuccess) e = hipMalloc(&od, (size_t)nq * ef * 4);
-  if (e == hipSuccess) e = hipMalloc(&olen, nq * 4);
-  if (e == hipSuccess) e = hipMalloc(&ost, nq * 8);
-  if (e == hipSuccess) e = hipMalloc(&ostat, nq * 4);
-  const float *qsearch = qd;
-  if (e == hipSuccess && quantize_query && ps->codes16) {
-    // quantizer.quantize(&raw_v) through the HNSW over the centroids, then its reconstruction  pq.rs:351-353
-    uint16_t *qc16 = nullptr;
-    e = hipMalloc(&qc16, (size_t)nq * ps->pq_m * 2);
-    if (e == hipSuccess) e = hipMalloc(&qq, (size_t)nq * full->ld * 4);
-    if (e == hipSuccess) {
-      rc = pq_shared_encode_device(ps, qd, nq, qc16);
-      if (!rc) {
-        hipLaunchKernelGGL(ph_pq_shared_reconstruct_kernel, dim3(1024), dim3(256), 0, 0, qc16, nq, ps->pq_m, ps->pq_dsub,
-                           ps->codebook, qq, full->ld);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipDeviceSynchronize();
-        qsearch = qq;
-      }
-    }
-    if (qc16) hipFree(qc16);
-  } else if (e == hipSuccess && quantize_query) {
-    e = hipMalloc(&qcodes, (size_t)nq * ps->pq_m);
-    if (e == hipSuccess) e = hipMalloc(&qq, (size_t)nq * full->ld * 4);
-    if (e == hipSuccess) e = hipMemset(qq, 0, (size_t)nq * full->ld * 4);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(ph_pq_encode_kernel, dim3((uint32_t)std::min<uint64_t>(nq, 8192)), dim3(64), 0, 0, qd,
-                         full->ld, nq, ps->pq_m, ps->pq_ksub, ps->pq_dsub, ps->codebook, qcodes, (uint64_t)ps->pq_m,
-                         (uint64_t)1);
-      uint64_t tot = nq * full->dim;
-      hipLaunchKernelGGL(ph_pq_reconstruct_kernel, dim3((uint32_t)((tot + 255) / 256)), dim3(256), 0, 0, qcodes, nq,
-                         ps->pq_m, ps->pq_ksub, ps->pq_dsub, ps->codebook, qq, full->ld);
-      e = hipGetLastError();
-      qsearch = qq;
-    }
-  }
-  if (e != hipSuccess && !rc) rc = ph_hip_fail(e, "pq search staging", __FILE__, __LINE__);
-  if (!rc)
-    rc = ph_search_device(ix, qsearch, full->ld, nullptr, nq, sp, 0, nullptr, oid, od, olen, ost, ostat, 0, 0, 0);
-  std::vector<uint32_t> h_status(nq);
-  if (!rc) {
-    e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(h_status.data(), ostat, nq * 4, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = ph_hip_fail(e, "pq search", __FILE__, __LINE__);
-    for (uint64_t i = 0; !rc && i < nq; i++)
-      if (h_status[i]) {
-        ph_set_error("pq search: query %llu failed with status %u", (unsigned long long)i, h_status[i]);
-        rc = h_status[i] == 4 ? PHNSW_E_MISSING_NODE : PHNSW_E_OVERFLOW;
-      }
-  }
-  if (!rc) {
-    // full_comparator().compare_vec(Stored(id), v) for every result, sort_by_key (d, id)
-    PhDistArgs fa = ph_dist_args(full);
-    uint32_t grid = (uint32_t)std::min<uint64_t>(nq, 256u * 16u);
-    size_t lds = (size_t)ef * 16;
-    uint32_t nv4 = full->ld / 4;
-    if (nv4 <= 64)
-      hipLaunchKernelGGL(ph_pq_rerank_kernel<1>, dim3(grid), dim3(64), lds, 0, fa, qd, full->ld, (uint32_t)nq, ef, olen, oid, od);
-    else if (nv4 <= 192)
-      hipLaunchKernelGGL(ph_pq_rerank_kernel<3>, dim3(grid), dim3(64), lds, 0, fa, qd, full->ld, (uint32_t)nq, ef, olen, oid, od);
-    else if (nv4 <= 384)
-      hipLaunchKernelGGL(ph_pq_rerank_kernel<6>, dim3(grid), dim3(64), lds, 0, fa, qd, full->ld, (uint32_t)nq, ef, olen, oid, od);
-    else {
-      ph_set_error("dim %u unsupported (max 1536)", full->dim);
-      rc = PHNSW_E_UNSUPPORTED;
-    }
-    if (!rc) {
-      e = hipGetLastError();
-      if (e == hipSuccess) e = hipDeviceSynchronize();
-      if (e != hipSuccess) rc = ph_hip_fail(e, "pq rerank", __FILE__, __LINE__);
-    }
-  }
-  if (!rc) {
-    std::vector<uint32_t> h_ids((size_t)nq * ef), h_len(nq), h_st(2 * nq);
-    e = hipMemcpy(h_ids.data(), oid, h_ids.size() * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(out_d, od, (size_t)nq * ef * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(h_len.data(), olen, nq * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(h_st.data(), ost, nq * 8, hipMemcpyDeviceToHost);
-    if (e != hipSuccess)
-      rc = ph_hip_fail(e, "pq readback", __FILE__, __LINE__);
-    else {
-      for (size_t i = 0; i < h_ids.size(); i++) out_ids[i] = h_ids[i] == PH_EMPTY32 ? PHNSW_EMPTY : h_ids[i];
-      for (uint64_t i = 0; i < nq; i++) out_len[i] = h_len[i];
-      if (out_stats)
-        for (uint64_t i = 0; i < 2 * nq; i++) out_stats[i] = h_st[i];
-    }
-  }
-  for (void *p : {(void *)qd, (void *)qq, (void *)od, (void *)oid, (void *)olen, (void *)ost, (void *)ostat, (void *)qcodes})
-    if (p) hipFree(p);
-  return rc;
-} catch (...) { return ph_caught(); }
-
-// zero-copy form of phnsw_pq_search_batch (asymmetric queries): search kernel + re-rank
-// kernel enqueued on `stream`, u32 ids, no synchronisation.
-extern "C" int phnsw_pq_search_batch_device(const phnsw_index *ix, const phnsw_store *full, const float *queries_dev,
-                                            uint32_t ldq, uint64_t nq, const phnsw_search_params *sp,
-                                            uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
-                                            uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) try {
-  if (!ix || !full || !queries_dev || !sp || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev ||
-      (!ix->store->codes && !ix->store->codes16) || !full->rows || full->n != ix->store->n || full->dim != ix->store->dim ||
-      nq > 0xFFFFFFFFull || sp->number_of_candidates == 0 || sp->number_of_candidates > 1024 || sp->probe_depth == 0 ||
-      ldq < full->ld || (ldq % 4)) {
-    ph_set_error("phnsw_pq_search_batch_device: invalid argument");
-    return PHNSW_E_INVALID;
-  }
-  if (nq == 0) return 0;
-  PH_HIP(hipSetDevice(full->device));
-  const uint32_t ef = (uint32_t)sp->number_of_candidates;
-  PH_TRYQ(ph_search_device(ix, queries_dev, ldq, nullptr, nq, sp, 0, nullptr, out_ids_dev, out_d_dev, out_len_dev,
-                           out_stats_dev, status_dev, 0, 0, (hipStream_t)stream));
-  PhDistArgs fa = ph_dist_args(full);
-  uint32_t grid = (uint32_t)std::min<uint64_t>(nq, 256u * 16u);
-  size_t lds = (size_t)ef * 16;
-  uint32_t nv4 = full->ld / 4;
-  hipStream_t st = (hipStream_t)stream;
-  if (nv4 <= 64)
-    hipLaunchKernelGGL(ph_pq_rerank_kernel<1>, dim3(grid), dim3(64), lds, st, fa, queries_dev, ldq, (uint32_t)nq, ef, out_len_dev, out_ids_dev, out_d_dev);
-  else if (nv4 <= 192)
-    hipLaunchKernelGGL(ph_pq_rerank_kernel<3>, dim3(grid), dim3(64), lds, st, fa, queries_dev, ldq, (uint32_t)nq, ef, out_len_dev, out_ids_dev, out_d_dev);
-  else if (nv4 <= 384)
-    hipLaunchKernelGGL(ph_pq_rerank_kernel<6>, dim3(grid), dim3(64), lds, st, fa, queries_dev, ldq, (uint32_t)nq, ef, out_len_dev, out_ids_dev, out_d_dev);
-  else {
-    ph_set_error("dim %u unsupported (max 1536)", full->dim);
-    return PHNSW_E_UNSUPPORTED;
-  }
-  PH_HIP(hipGetLastError());
-  return 0;
-} catch (...) { return ph_caught(); }
-
-// ------------------------------------------------------------------ f16 / i8 / i8q store: search + f32 re-rank
+// ------------------------------------------------------------------ search + f32 re-rank
 //
-// The f16, i8 or i8q index finds the candidates (distances of the widened / dequantised rows); the f32 store then gives every returned
-// id its full-precision distance (ph_pq_rerank_kernel: the bits of phnsw_distance_batch on `full`), the row is
-// sorted by (distance, id) and the best k are kept.
+// An index over a PQ, f16, i8 or i8q store finds the candidates; the f32 store `full` then gives every returned id its
+// full-precision distance (ph_pq_rerank_kernel: the bits of phnsw_distance_batch on `full`), the row is sorted by
+// (distance, id) and the best k are kept.  QuantizedHnsw::search (pq.rs:346-364) is this with k = number_of_candidates.
 
 // the sorted rows [nq][ef] cut to k entries each, in place: entries k .. ef - 1 become empty, len = min(len, k)
 __global__ void ph_rerank_trim_kernel(uint32_t *ids, float *d, uint32_t *len, uint32_t ef, uint32_t k, uint64_t nq) {
@@ -792,48 +638,36 @@ __global__ void ph_rerank_trim_kernel(uint32_t *ids, float *d, uint32_t *len, ui
     if (c == 0) len[r] = min(len[r], k);
   }
 }
-// ... and the leading k of each row as u64 ids + distances, [nq][k]
-__global__ void ph_rerank_take_kernel(const uint32_t *ids, const float *d, uint32_t ef, uint32_t k, uint64_t nq, uint64_t *ids64,
-                                   float *dk) {
-  const uint64_t total = nq * k;
-  for (uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; x < total; x += (uint64_t)gridDim.x * blockDim.x) {
-    const uint64_t r = x / k, c = x - r * k;
-    const uint32_t id = ids[r * ef + c];
-    ids64[x] = id == PH_EMPTY32 ? PHNSW_EMPTY : (uint64_t)id;
-    dk[x] = d[r * ef + c];
-  }
+
+// What every re-ranked search asks of its arguments.  `kinds`: the row kinds the entry point serves, one bit per
+// PhRowKind (a call of one kind refuses an index over another).  A converted store was made from `full` and shares its
+// metric and device; a PQ index and its full-precision store have never been held to that.
+static const uint32_t PH_KINDS_PQ = (1u << PH_ROWS_PQ) | (1u << PH_ROWS_PQ_SHARED);
+static bool rerank_check(uint32_t kinds, const phnsw_index *ix, const phnsw_store *full, const phnsw_search_params *sp,
+                         uint64_t nq, uint64_t k) {
+  if (!ix || !full || !sp) return false;
+  const phnsw_store *s = ix->store;
+  return ((kinds >> s->kind) & 1u) && ph_store_f32(full) && full->n == s->n && full->dim == s->dim &&
+         (!ph_store_converted(s) || (full->metric == s->metric && full->device == s->device)) && nq <= 0xFFFFFFFFull &&
+         sp->number_of_candidates != 0 && sp->number_of_candidates <= 1024 && sp->probe_depth != 0 && k != 0 &&
+         k <= sp->number_of_candidates;
 }
 
-// `kind`: the converted store the entry point serves (a call of one kind refuses an index over another)
-static int rerank_check(const char *call, int kind, const phnsw_index *ix, const phnsw_store *full,
-                        const phnsw_search_params *sp, uint64_t nq, uint64_t k) {
-  if (!ix || !full || !sp || ix->store->kind != kind || !full->rows || full->n != ix->store->n || full->dim != ix->store->dim ||
-      full->metric != ix->store->metric || full->device != ix->store->device || nq > 0xFFFFFFFFull ||
-      sp->number_of_candidates == 0 || sp->number_of_candidates > 1024 || sp->probe_depth == 0 || k == 0 ||
-      k > sp->number_of_candidates) {
-    ph_set_error("%s: need an index over an %s store, the f32 store of the same n / dim / metric / device, valid "
-                 "parameters and 1 <= k <= number_of_candidates", call, ph_rows_name(kind));
-    return PHNSW_E_INVALID;
-  }
-  return 0;
-}
-
+// the re-rank of rows [nq][ef] in place, then the cut to k: the only launch of ph_pq_rerank_kernel
 static int rerank_launch(const phnsw_store *full, const float *queries_dev, uint32_t ldq, uint64_t nq, uint32_t ef,
-                             uint32_t k, uint32_t *len, uint32_t *ids, float *d, hipStream_t st) {
+                         uint32_t k, uint32_t *len, uint32_t *ids, float *d, hipStream_t st) {
   PhDistArgs fa = ph_dist_args(full);
   const uint32_t grid = (uint32_t)std::min<uint64_t>(nq, 256u * 16u);
   const size_t lds = (size_t)ef * 16;
-  const uint32_t nv4 = full->ld / 4;
-  if (nv4 <= 64)
-    hipLaunchKernelGGL(ph_pq_rerank_kernel<1>, dim3(grid), dim3(64), lds, st, fa, queries_dev, ldq, (uint32_t)nq, ef, len, ids, d);
-  else if (nv4 <= 192)
-    hipLaunchKernelGGL(ph_pq_rerank_kernel<3>, dim3(grid), dim3(64), lds, st, fa, queries_dev, ldq, (uint32_t)nq, ef, len, ids, d);
-  else if (nv4 <= 384)
-    hipLaunchKernelGGL(ph_pq_rerank_kernel<6>, dim3(grid), dim3(64), lds, st, fa, queries_dev, ldq, (uint32_t)nq, ef, len, ids, d);
-  else {
-    ph_set_error("dim %u unsupported (max 1536)", full->dim);
-    return PHNSW_E_UNSUPPORTED;
+#define PH_RERANK(NV) \
+  hipLaunchKernelGGL(ph_pq_rerank_kernel<NV>, dim3(grid), dim3(64), lds, st, fa, queries_dev, ldq, (uint32_t)nq, ef, len, ids, d)
+  switch (ph_chunk_count(full->ld / 4)) {
+    case 1: PH_RERANK(1); break;
+    case 3: PH_RERANK(3); break;
+    case 6: PH_RERANK(6); break;
+    default: return ph_dim_unsupported(full->dim);
   }
+#undef PH_RERANK
   PH_HIP(hipGetLastError());
   if (k < ef) {
     hipLaunchKernelGGL(ph_rerank_trim_kernel, dim3((uint32_t)std::min<uint64_t>((nq * ef + 255) / 256, 4096)), dim3(256), 0, st, ids,
@@ -843,63 +677,60 @@ static int rerank_launch(const phnsw_store *full, const float *queries_dev, uint
   return 0;
 }
 
-// zero-copy form: the search launches, the re-rank and the cut to k enqueued on `stream`, no synchronisation.  The
-// result rows keep the search's stride (number_of_candidates entries per query): the first min(len, k) are live.
-static int reranked_search_device(const char *call, int kind, const phnsw_index *ix, const phnsw_store *full,
-                                  const float *queries_dev, uint32_t ldq, uint64_t nq, const phnsw_search_params *sp,
-                                  uint64_t k, uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
-                                  uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) {
-  PH_TRYQ(rerank_check(call, kind, ix, full, sp, nq, k));
-  if (!queries_dev || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev || ldq < full->ld || (ldq % 4) ||
-      ((uintptr_t)queries_dev % 16)) {
-    ph_set_error("%s: invalid argument (queries need ldq >= store ld, multiple of 4, 16-byte base)", call);
-    return PHNSW_E_INVALID;
-  }
+// zero-copy form (arguments checked by the caller): the search launches, the re-rank and the cut to k enqueued on
+// `stream`, u32 ids, no synchronisation.  The result rows keep the search's stride (number_of_candidates entries per
+// query): the first min(len, k) are live.
+static int reranked_search_device(const phnsw_index *ix, const phnsw_store *full, const float *queries_dev, uint32_t ldq,
+                                  uint64_t nq, const phnsw_search_params *sp, uint64_t k, uint32_t *out_ids_dev,
+                                  float *out_d_dev, uint32_t *out_len_dev, uint32_t *out_stats_dev, uint32_t *status_dev,
+                                  void *stream) {
   if (nq == 0) return 0;
   PH_HIP(hipSetDevice(full->device));
   PH_TRYQ(ph_search_device(ix, queries_dev, ldq, nullptr, nq, sp, 0, nullptr, out_ids_dev, out_d_dev, out_len_dev,
                            out_stats_dev, status_dev, 0, 0, (hipStream_t)stream));
-  return rerank_launch(full, queries_dev, ldq, nq, (uint32_t)sp->number_of_candidates, (uint32_t)k, out_len_dev,
-                           out_ids_dev, out_d_dev, (hipStream_t)stream);
+  return rerank_launch(full, queries_dev, ldq, nq, (uint32_t)sp->number_of_candidates, (uint32_t)k, out_len_dev, out_ids_dev,
+                       out_d_dev, (hipStream_t)stream);
 }
 
-// host form: out_ids / out_d are [nq][k], out_len[q] = min(results of query q, k)
-static int reranked_search_host(const char *call, int kind, const phnsw_index *ix, const phnsw_store *full,
-                                const float *queries, uint64_t nq, const phnsw_search_params *sp, uint64_t k,
-                                uint64_t *out_ids, float *out_d, uint64_t *out_len) {
-  PH_TRYQ(rerank_check(call, kind, ix, full, sp, nq, k));
-  if ((!queries || !out_ids || !out_d || !out_len) && nq) {
-    ph_set_error("%s: queries and outputs must not be NULL", call);
-    return PHNSW_E_INVALID;
-  }
-  if (nq == 0) return 0;
-  PH_HIP(hipSetDevice(full->device));
+// host queries [nq][dim] as device rows of the f32 store's padded length
+static hipError_t upload_queries(const phnsw_store *full, const float *queries, uint64_t nq, float **qd) {
+  hipError_t e = hipMalloc(qd, (size_t)nq * full->ld * 4);
+  if (e == hipSuccess && full->ld != full->dim) e = hipMemset(*qd, 0, (size_t)nq * full->ld * 4);
+  if (e == hipSuccess)
+    e = hipMemcpy2D(*qd, (size_t)full->ld * 4, queries, (size_t)full->dim * 4, (size_t)full->dim * 4, nq, hipMemcpyHostToDevice);
+  return e;
+}
+
+// host form (arguments checked, device selected by the caller): out_ids / out_d are [nq][k], out_len[q] = min(results
+// of query q, k), out_stats [nq][2] or nullptr.  The index is searched with the device rows `qsearch` (nullptr: the
+// queries as they are); the re-rank always takes the queries as they are.
+static int reranked_search_host(const char *call, const phnsw_index *ix, const phnsw_store *full, const float *queries,
+                                const float *qsearch, uint64_t nq, const phnsw_search_params *sp, uint64_t k,
+                                uint64_t *out_ids, float *out_d, uint64_t *out_len, uint64_t *out_stats) {
   const uint32_t ef = (uint32_t)sp->number_of_candidates;
   float *qd = nullptr, *od = nullptr, *dk = nullptr;
-  uint32_t *oid = nullptr, *olen = nullptr, *ostat = nullptr;
+  uint32_t *oid = nullptr, *olen = nullptr, *ostat = nullptr, *ost = nullptr;
   uint64_t *ids64 = nullptr;
   int rc = 0;
-  hipError_t e = hipMalloc(&qd, (size_t)nq * full->ld * 4);
-  if (e == hipSuccess && full->ld != full->dim) e = hipMemset(qd, 0, (size_t)nq * full->ld * 4);
-  if (e == hipSuccess)
-    e = hipMemcpy2D(qd, (size_t)full->ld * 4, queries, (size_t)full->dim * 4, (size_t)full->dim * 4, nq, hipMemcpyHostToDevice);
+  hipError_t e = upload_queries(full, queries, nq, &qd);
   if (e == hipSuccess) e = hipMalloc(&oid, (size_t)nq * ef * 4);
   if (e == hipSuccess) e = hipMalloc(&od, (size_t)nq * ef * 4);
   if (e == hipSuccess) e = hipMalloc(&olen, nq * 4);
   if (e == hipSuccess) e = hipMalloc(&ostat, nq * 4);
+  if (e == hipSuccess && out_stats) e = hipMalloc(&ost, nq * 8);
   if (e == hipSuccess) e = hipMalloc(&ids64, (size_t)nq * k * 8);
   if (e == hipSuccess) e = hipMalloc(&dk, (size_t)nq * k * 4);
   if (e != hipSuccess) rc = ph_hip_fail(e, "re-ranked search staging", __FILE__, __LINE__);
-  if (!rc) rc = ph_search_device(ix, qd, full->ld, nullptr, nq, sp, 0, nullptr, oid, od, olen, nullptr, ostat, 0, 0, 0);
+  if (!rc)
+    rc = ph_search_device(ix, qsearch ? qsearch : qd, full->ld, nullptr, nq, sp, 0, nullptr, oid, od, olen, ost, ostat, 0, 0, 0);
   if (!rc) rc = rerank_launch(full, qd, full->ld, nq, ef, (uint32_t)k, olen, oid, od, 0);
+  if (!rc) rc = ph_take_launch(oid, od, ef, (uint32_t)k, nq, ids64, dk, 0);
   if (!rc) {
-    hipLaunchKernelGGL(ph_rerank_take_kernel, dim3((uint32_t)std::min<uint64_t>((nq * k + 255) / 256, 4096)), dim3(256), 0, 0, oid,
-                       od, ef, (uint32_t)k, nq, ids64, dk);
-    e = hipGetLastError();
-    std::vector<uint32_t> h_status(nq), h_len(nq);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
+    std::vector<uint32_t> h_status(nq), h_len(nq), h_st(out_stats ? 2 * nq : 0);
+    e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(h_status.data(), ostat, nq * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(h_len.data(), olen, nq * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_stats) e = hipMemcpy(h_st.data(), ost, nq * 8, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(out_ids, ids64, (size_t)nq * k * 8, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(out_d, dk, (size_t)nq * k * 4, hipMemcpyDeviceToHost);
     if (e != hipSuccess) rc = ph_hip_fail(e, "re-ranked search", __FILE__, __LINE__);
@@ -910,47 +741,154 @@ static int reranked_search_host(const char *call, int kind, const phnsw_index *i
       }
       out_len[i] = std::min<uint64_t>(h_len[i], k);
     }
+    for (size_t i = 0; !rc && i < h_st.size(); i++) out_stats[i] = h_st[i];
   }
-  for (void *p : {(void *)qd, (void *)od, (void *)dk, (void *)oid, (void *)olen, (void *)ostat, (void *)ids64})
+  for (void *p : {(void *)qd, (void *)od, (void *)dk, (void *)oid, (void *)olen, (void *)ostat, (void *)ost, (void *)ids64})
     if (p) hipFree(p);
   return rc;
+}
+
+// quantizer.quantize(&raw_v) and its reconstruction (pq.rs:351-353) for nq host queries: *out = device rows
+// [nq][full->ld], the caller's to free.  A shared-codebook store quantises through the HNSW over its centroids.
+static int pq_quantized_queries(const phnsw_store *ps, const phnsw_store *full, const float *queries, uint64_t nq, float **out) {
+  const bool shared = ph_store_pq_shared(ps);
+  float *qd = nullptr, *qq = nullptr;
+  void *qcodes = nullptr;
+  int rc = 0;
+  hipError_t e = upload_queries(full, queries, nq, &qd);
+  if (e == hipSuccess) e = hipMalloc(&qcodes, (size_t)nq * ps->pq_m * (shared ? 2 : 1));
+  if (e == hipSuccess) e = hipMalloc(&qq, (size_t)nq * full->ld * 4);
+  if (e == hipSuccess && shared) {
+    rc = pq_shared_encode_device(ps, qd, nq, (uint16_t *)qcodes);
+    if (!rc) {
+      hipLaunchKernelGGL(ph_pq_shared_reconstruct_kernel, dim3(1024), dim3(256), 0, 0, (const uint16_t *)qcodes, nq, ps->pq_m,
+                         ps->pq_dsub, ps->codebook, qq, full->ld);
+      e = hipGetLastError();
+    }
+  } else if (e == hipSuccess) {
+    e = hipMemset(qq, 0, (size_t)nq * full->ld * 4);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(ph_pq_encode_kernel, dim3((uint32_t)std::min<uint64_t>(nq, 8192)), dim3(64), 0, 0, qd, full->ld, nq,
+                         ps->pq_m, ps->pq_ksub, ps->pq_dsub, ps->codebook, (uint8_t *)qcodes, (uint64_t)ps->pq_m, (uint64_t)1);
+      const uint64_t tot = nq * full->dim;
+      hipLaunchKernelGGL(ph_pq_reconstruct_kernel, dim3((uint32_t)((tot + 255) / 256)), dim3(256), 0, 0,
+                         (const uint8_t *)qcodes, nq, ps->pq_m, ps->pq_ksub, ps->pq_dsub, ps->codebook, qq, full->ld);
+      e = hipGetLastError();
+    }
+  }
+  if (e == hipSuccess && !rc) e = hipDeviceSynchronize();  // before the codes and the upload go
+  if (e != hipSuccess && !rc) rc = ph_hip_fail(e, "pq query quantisation", __FILE__, __LINE__);
+  if (qd) hipFree(qd);
+  if (qcodes) hipFree(qcodes);
+  if (rc && qq) hipFree(qq);
+  if (!rc) *out = qq;
+  return rc;
+}
+
+// QuantizedHnsw::search  pq.rs:346-364 for a batch: (optionally quantise the query like the
+// reference :351-352, default = asymmetric: the raw query meets the codes), search the graph
+// over the code rows, re-rank with the full-precision store, sort by (d, id).
+extern "C" int phnsw_pq_search_batch(const phnsw_index *ix, const phnsw_store *full, const float *queries, uint64_t nq,
+                                     const phnsw_search_params *sp, int quantize_query, uint64_t *out_ids,
+                                     float *out_d, uint64_t *out_len, uint64_t *out_stats) try {
+  const uint64_t ef = sp ? sp->number_of_candidates : 0;
+  if (!rerank_check(PH_KINDS_PQ, ix, full, sp, nq, ef) || !queries || !out_ids || !out_d || !out_len) {
+    ph_set_error("phnsw_pq_search_batch: need an index over a PQ store, its full-precision store and valid parameters");
+    return PHNSW_E_INVALID;
+  }
+  if (nq == 0) return 0;
+  PH_HIP(hipSetDevice(ix->store->device));
+  float *qq = nullptr;
+  if (quantize_query) PH_TRYQ(pq_quantized_queries(ix->store, full, queries, nq, &qq));
+  const int rc = reranked_search_host("phnsw_pq_search_batch", ix, full, queries, qq, nq, sp, ef, out_ids, out_d, out_len, out_stats);
+  if (qq) hipFree(qq);
+  return rc;
+} catch (...) { return ph_caught(); }
+
+// zero-copy form of phnsw_pq_search_batch (asymmetric queries)
+extern "C" int phnsw_pq_search_batch_device(const phnsw_index *ix, const phnsw_store *full, const float *queries_dev,
+                                            uint32_t ldq, uint64_t nq, const phnsw_search_params *sp,
+                                            uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                            uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) try {
+  const uint64_t ef = sp ? sp->number_of_candidates : 0;
+  if (!rerank_check(PH_KINDS_PQ, ix, full, sp, nq, ef) || !queries_dev || !out_ids_dev || !out_d_dev || !out_len_dev ||
+      !status_dev || ldq < full->ld || (ldq % 4)) {
+    ph_set_error("phnsw_pq_search_batch_device: invalid argument");
+    return PHNSW_E_INVALID;
+  }
+  return reranked_search_device(ix, full, queries_dev, ldq, nq, sp, ef, out_ids_dev, out_d_dev, out_len_dev, out_stats_dev,
+                                status_dev, stream);
+} catch (...) { return ph_caught(); }
+
+// the f16 / i8 / i8q entry points: `kind` is the converted store the call serves
+static int converted_check(const char *call, int kind, const phnsw_index *ix, const phnsw_store *full,
+                           const phnsw_search_params *sp, uint64_t nq, uint64_t k) {
+  if (rerank_check(1u << kind, ix, full, sp, nq, k)) return 0;
+  ph_set_error("%s: need an index over an %s store, the f32 store of the same n / dim / metric / device, valid "
+               "parameters and 1 <= k <= number_of_candidates", call, ph_rows_name(kind));
+  return PHNSW_E_INVALID;
+}
+static int converted_search_device(const char *call, int kind, const phnsw_index *ix, const phnsw_store *full,
+                                   const float *queries_dev, uint32_t ldq, uint64_t nq, const phnsw_search_params *sp,
+                                   uint64_t k, uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                   uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) {
+  PH_TRYQ(converted_check(call, kind, ix, full, sp, nq, k));
+  if (!queries_dev || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev || ldq < full->ld || (ldq % 4) ||
+      ((uintptr_t)queries_dev % 16)) {
+    ph_set_error("%s: invalid argument (queries need ldq >= store ld, multiple of 4, 16-byte base)", call);
+    return PHNSW_E_INVALID;
+  }
+  return reranked_search_device(ix, full, queries_dev, ldq, nq, sp, k, out_ids_dev, out_d_dev, out_len_dev, out_stats_dev,
+                                status_dev, stream);
+}
+static int converted_search_host(const char *call, int kind, const phnsw_index *ix, const phnsw_store *full,
+                                 const float *queries, uint64_t nq, const phnsw_search_params *sp, uint64_t k,
+                                 uint64_t *out_ids, float *out_d, uint64_t *out_len) {
+  PH_TRYQ(converted_check(call, kind, ix, full, sp, nq, k));
+  if ((!queries || !out_ids || !out_d || !out_len) && nq) {
+    ph_set_error("%s: queries and outputs must not be NULL", call);
+    return PHNSW_E_INVALID;
+  }
+  if (nq == 0) return 0;
+  PH_HIP(hipSetDevice(full->device));
+  return reranked_search_host(call, ix, full, queries, nullptr, nq, sp, k, out_ids, out_d, out_len, nullptr);
 }
 
 extern "C" int phnsw_f16_search_batch_device(const phnsw_index *ix, const phnsw_store *full, const float *queries_dev,
                                              uint32_t ldq, uint64_t nq, const phnsw_search_params *sp, uint64_t k,
                                              uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
                                              uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) try {
-  return reranked_search_device("phnsw_f16_search_batch_device", PH_ROWS_F16, ix, full, queries_dev, ldq, nq, sp, k, out_ids_dev,
+  return converted_search_device("phnsw_f16_search_batch_device", PH_ROWS_F16, ix, full, queries_dev, ldq, nq, sp, k, out_ids_dev,
                                 out_d_dev, out_len_dev, out_stats_dev, status_dev, stream);
 } catch (...) { return ph_caught(); }
 extern "C" int phnsw_f16_search_batch(const phnsw_index *ix, const phnsw_store *full, const float *queries, uint64_t nq,
                                       const phnsw_search_params *sp, uint64_t k, uint64_t *out_ids, float *out_d,
                                       uint64_t *out_len) try {
-  return reranked_search_host("phnsw_f16_search_batch", PH_ROWS_F16, ix, full, queries, nq, sp, k, out_ids, out_d, out_len);
+  return converted_search_host("phnsw_f16_search_batch", PH_ROWS_F16, ix, full, queries, nq, sp, k, out_ids, out_d, out_len);
 } catch (...) { return ph_caught(); }
 // the same two over an index on an i8 store
 extern "C" int phnsw_i8_search_batch_device(const phnsw_index *ix, const phnsw_store *full, const float *queries_dev,
                                             uint32_t ldq, uint64_t nq, const phnsw_search_params *sp, uint64_t k,
                                             uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
                                             uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) try {
-  return reranked_search_device("phnsw_i8_search_batch_device", PH_ROWS_I8, ix, full, queries_dev, ldq, nq, sp, k, out_ids_dev,
+  return converted_search_device("phnsw_i8_search_batch_device", PH_ROWS_I8, ix, full, queries_dev, ldq, nq, sp, k, out_ids_dev,
                                 out_d_dev, out_len_dev, out_stats_dev, status_dev, stream);
 } catch (...) { return ph_caught(); }
 extern "C" int phnsw_i8_search_batch(const phnsw_index *ix, const phnsw_store *full, const float *queries, uint64_t nq,
                                      const phnsw_search_params *sp, uint64_t k, uint64_t *out_ids, float *out_d,
                                      uint64_t *out_len) try {
-  return reranked_search_host("phnsw_i8_search_batch", PH_ROWS_I8, ix, full, queries, nq, sp, k, out_ids, out_d, out_len);
+  return converted_search_host("phnsw_i8_search_batch", PH_ROWS_I8, ix, full, queries, nq, sp, k, out_ids, out_d, out_len);
 } catch (...) { return ph_caught(); }
 // ... and on an i8q store
 extern "C" int phnsw_i8q_search_batch_device(const phnsw_index *ix, const phnsw_store *full, const float *queries_dev,
                                              uint32_t ldq, uint64_t nq, const phnsw_search_params *sp, uint64_t k,
                                              uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
                                              uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) try {
-  return reranked_search_device("phnsw_i8q_search_batch_device", PH_ROWS_I8Q, ix, full, queries_dev, ldq, nq, sp, k, out_ids_dev,
+  return converted_search_device("phnsw_i8q_search_batch_device", PH_ROWS_I8Q, ix, full, queries_dev, ldq, nq, sp, k, out_ids_dev,
                                 out_d_dev, out_len_dev, out_stats_dev, status_dev, stream);
 } catch (...) { return ph_caught(); }
 extern "C" int phnsw_i8q_search_batch(const phnsw_index *ix, const phnsw_store *full, const float *queries, uint64_t nq,
                                       const phnsw_search_params *sp, uint64_t k, uint64_t *out_ids, float *out_d,
                                       uint64_t *out_len) try {
-  return reranked_search_host("phnsw_i8q_search_batch", PH_ROWS_I8Q, ix, full, queries, nq, sp, k, out_ids, out_d, out_len);
+  return converted_search_host("phnsw_i8q_search_batch", PH_ROWS_I8Q, ix, full, queries, nq, sp, k, out_ids, out_d, out_len);
 } catch (...) { return ph_caught(); }

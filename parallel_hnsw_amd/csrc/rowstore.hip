@@ -155,7 +155,7 @@ static int create_converted(const char *name, const phnsw_store *full, int kind,
     ph_set_error("no HIP device available (libphnsw has no CPU fallback)");
     return PHNSW_E_NO_DEVICE;
   }
-  if (!full->rows) {
+  if (!ph_store_f32(full)) {
     ph_set_error("%s: the source must be an f32 store", name);
     return PHNSW_E_INVALID;
   }

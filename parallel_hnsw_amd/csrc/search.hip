@@ -967,12 +967,11 @@ static int pick_capc_f32(uint32_t ef, bool grows, int nv) {
   return (!grows && ef > 128 && ef <= 256 && vis_lds_on() && vis_lds_shape(4, nv)) ? 4 : pick_capc(ef);
 }
 static int pick_capc_dense(uint32_t ef) { return ef <= 128 ? 2 : (ef <= 256 ? 4 : (ef <= 512 ? 8 : (ef <= 1024 ? 16 : 0))); }
-static int pick_nv(uint32_t nv4) { return nv4 <= 64 ? 1 : (nv4 <= 192 ? 3 : (nv4 <= 384 ? 6 : 0)); }
 
 // the register-table policy serves 8-bit tables (mode 2) of exactly 32 / 64 / 96 / 128 sub-spaces with at most
 // 256 centroids and queues of up to 512 entries; PHNSW_PQ_TABLE=lds|global selects the older table placements
 static int pick_pqr(const phnsw_store *s, int capc) {
-  if (!s->codes || s->pq_table_f16 != 2 || (capc != 2 && capc != 8) || getenv("PHNSW_PQ_TABLE")) return 0;
+  if (!ph_store_pq(s) || s->pq_table_f16 != 2 || (capc != 2 && capc != 8) || getenv("PHNSW_PQ_TABLE")) return 0;
   const uint32_t m = s->pq_m;
   return (s->pq_ksub == 256 && (m == 32 || m == 64 || m == 96 || m == 128)) ? (int)m : 0;
 }
@@ -1138,12 +1137,12 @@ static PhKernelChoice pick_search_kernel(const phnsw_store *s, uint32_t ef_max, 
       return k;
     case PH_ROWS_PQ_SHARED:
       k.family = PH_KF_PQ_SHARED;
-      k.nv = pick_nv(nv4);
+      k.nv = ph_chunk_count(nv4);
       k.fn = pick_kernel_pqs(capc, k.nv);
       return k;
     default: break;
   }
-  k.nv = pick_nv(nv4);
+  k.nv = ph_chunk_count(nv4);
   if (s->kind == PH_ROWS_F32 && !instr && nq <= PH_LATENCY_MAX && !getenv("PHNSW_NO_LAT") && pick_kernel_lat(capc, k.nv)) {
     k.family = PH_KF_LATENCY;
     k.fn = pick_kernel_lat(capc, k.nv);
@@ -1337,7 +1336,7 @@ static int search_launch_dense(PhWorkspace &ws, PhSearchArgs &a, hipStream_t str
 
 int ph_search_launch_big(const phnsw_index *ix, PhSearchArgs &a, uint32_t grid, hipStream_t stream) {
   const phnsw_store *s = ix->store;
-  const int nv = s->kind == PH_ROWS_PQ ? 0 : pick_nv(a.dist.nv4);
+  const int nv = s->kind == PH_ROWS_PQ ? 0 : ph_chunk_count(a.dist.nv4);
   ph_search_fn fn = nullptr;
   size_t pq_lds = 0;
   if (s->kind == PH_ROWS_PQ_SHARED) {

@@ -153,13 +153,13 @@ extern "C" int phnsw_index_serialize(const phnsw_index *ix, const char *path) tr
     mkdir(cdir.c_str(), 0777);
     std::ostringstream cm;
     cm << "{\"n\":" << s->n << ",\"dim\":" << s->dim << ",\"metric\":" << s->metric
-       << ",\"kind\":\"" << (s->codes ? "pq" : "f32") << "\"";
-    if (s->codes) cm << ",\"m\":" << s->pq_m << ",\"ksub\":" << s->pq_ksub << ",\"dsub\":" << s->pq_dsub;
+       << ",\"kind\":\"" << (ph_store_pq(s) ? "pq" : "f32") << "\"";
+    if (ph_store_pq(s)) cm << ",\"m\":" << s->pq_m << ",\"ksub\":" << s->pq_ksub << ",\"dsub\":" << s->pq_dsub;
     cm << "}";
     std::string cms = cm.str();
     rc = write_file(cdir + "/meta.json", cms.data(), cms.size());
     if (rc) return rc;
-    if (s->codes) {
+    if (ph_store_pq(s)) {
       std::vector<uint8_t> codes((size_t)s->n * s->pq_m);
       std::vector<float> cb((size_t)s->pq_m * s->pq_ksub * s->pq_dsub);
       PH_HIP(hipMemcpy(codes.data(), s->codes, codes.size(), hipMemcpyDeviceToHost));

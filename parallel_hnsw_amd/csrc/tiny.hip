@@ -575,7 +575,7 @@ bool ph_tiny_matrix_cores(const phnsw_index *ix) {
 // ef 300) it is tabulated either way.  PHNSW_TINY_MAX overrides.
 uint32_t ph_tiny_layer_count(const phnsw_index *ix, uint32_t n_layers, uint32_t ef) {
   const bool off = getenv("PHNSW_NO_TINY") != nullptr;  // tests compare both paths
-  if (off || (!ix->store->rows && !ph_store_converted(ix->store)) || ix->store->ld / 4 > 384) return 0;
+  if (off || (!ph_store_f32(ix->store) && !ph_store_converted(ix->store)) || !ph_chunk_count(ix->store->ld / 4)) return 0;
   const uint64_t per_ef = ph_tiny_matrix_cores(ix) ? 80ull : 48ull;
   uint64_t cap = std::min<uint64_t>(PH_TINY_MAX_NODES, per_ef * ef);
   if (const char *e = getenv("PHNSW_TINY_MAX"))
@@ -685,12 +685,11 @@ static int tiny_prep_graph(const phnsw_index *ix, PhWorkspace &ws, PhSearchArgs 
 // the vector-unit tile pass over the rows of one kind
 template <class R>
 static void tiny_table_valu(int nv, dim3 grid, hipStream_t stream, const PhTinyTableArgs &t) {
-  if (nv == 1)
-    hipLaunchKernelGGL((ph_tiny_table_kernel<1, 8, R>), grid, dim3(256), 0, stream, t);
-  else if (nv == 3)
-    hipLaunchKernelGGL((ph_tiny_table_kernel<3, 8, R>), grid, dim3(256), 0, stream, t);
-  else
-    hipLaunchKernelGGL((ph_tiny_table_kernel<6, 4, R>), grid, dim3(256), 0, stream, t);
+  switch (nv) {
+    case 1: hipLaunchKernelGGL((ph_tiny_table_kernel<1, 8, R>), grid, dim3(256), 0, stream, t); break;
+    case 3: hipLaunchKernelGGL((ph_tiny_table_kernel<3, 8, R>), grid, dim3(256), 0, stream, t); break;
+    default: hipLaunchKernelGGL((ph_tiny_table_kernel<6, 4, R>), grid, dim3(256), 0, stream, t); break;
+  }
 }
 
 // the table of an i8q store: both operands as code matrices + scales (the node side kept under the pack key, like the
@@ -788,7 +787,7 @@ static int tiny_table(const phnsw_index *ix, PhWorkspace &ws, const PhDistArgs &
   t.D = D;
   if (const char *e = getenv("PHNSW_TINY_DBG")) t.dbg = (uint32_t)atoi(e);
   const uint32_t nv4 = dist.nv4;
-  const int nv = nv4 <= 64 ? 1 : (nv4 <= 192 ? 3 : 6);
+  const int nv = ph_chunk_count(nv4);  // 1, 3 or 6: ph_tiny_layer_count gives longer rows no dense layer
   if (dist.rows.kind == PH_ROWS_I8Q) return tiny_table_i8q(ix, ws, dist, queries, ldq, qids, order, npos, tnodes, tn, stride, D, stream, kept);
   // dot-product metrics over whole 64-chunk rows go to the matrix cores (same bits, see above); the Euclidean
   // chain (fma(d, d, acc) of a difference) is not a product of the two operands and stays on the vector units, as
@@ -853,21 +852,23 @@ static int tiny_table(const phnsw_index *ix, PhWorkspace &ws, const PhDistArgs &
     const uint32_t blocks = (supers + 7u) / 8u * 8u * 64u;
     const size_t lds = tiny_mfma_lds(nv, g == 1 ? 1 : 2);
     ws.tiny_table_g = g == 1 ? 1 : 2;
-    if (g == 1) {
-      if (nv == 1)
-        hipLaunchKernelGGL((ph_tiny_table_mfma_kernel<1, 1>), dim3(blocks), dim3(256), lds, stream, m);
-      else if (nv == 3)
-        hipLaunchKernelGGL((ph_tiny_table_mfma_kernel<3, 1>), dim3(blocks), dim3(256), lds, stream, m);
-      else
-        hipLaunchKernelGGL((ph_tiny_table_mfma_kernel<6, 1>), dim3(blocks), dim3(256), lds, stream, m);
-    } else if (nv == 1) {
-      hipLaunchKernelGGL((ph_tiny_table_mfma_kernel<1, 2>), dim3(blocks), dim3(256), lds, stream, m);
-    } else if (nv == 3) {
-      hipLaunchKernelGGL((ph_tiny_table_mfma_kernel<3, 2>), dim3(blocks), dim3(256), lds, stream, m);
-    } else {
+    if (g != 1 && nv == 6)
       PH_HIP(hipFuncSetAttribute((const void *)ph_tiny_table_mfma_kernel<6, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      hipLaunchKernelGGL((ph_tiny_table_mfma_kernel<6, 2>), dim3(blocks), dim3(256), lds, stream, m);
+#define PH_MFMA(NV, G) hipLaunchKernelGGL((ph_tiny_table_mfma_kernel<NV, G>), dim3(blocks), dim3(256), lds, stream, m)
+    if (g == 1) {
+      switch (nv) {
+        case 1: PH_MFMA(1, 1); break;
+        case 3: PH_MFMA(3, 1); break;
+        default: PH_MFMA(6, 1); break;
+      }
+    } else {
+      switch (nv) {
+        case 1: PH_MFMA(1, 2); break;
+        case 3: PH_MFMA(3, 2); break;
+        default: PH_MFMA(6, 2); break;
+      }
     }
+#undef PH_MFMA
   } else {
     const uint32_t qt = nv == 6 ? 4u : 8u;
     const uint32_t gx = (npos + 4u * qt - 1u) / (4u * qt);

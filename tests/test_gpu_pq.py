@@ -386,3 +386,41 @@ def test_sharded_encode_equals_single_gpu_encode(world, rank):
     b = ph.SharedPqStore(f2, 16, 300, seed=3, comm=comm, **kw)
     np.testing.assert_array_equal(a.codes(), b.codes())
     np.testing.assert_array_equal(a.codebook().view(np.uint32), b.codebook().view(np.uint32))
+
+
+@pytest.mark.parametrize("n,ksub,short", [(2000, 64, False), (40, 16, True)])
+def test_pq_host_search_short_rows_hold_empty_and_the_float_maximum(n, ksub, short):
+    """QuantizedHnsw.search_batch widens its ids where the re-ranked rows are: a slot at or past out_len is PHNSW_EMPTY
+    and the float maximum (never a widened 0xFFFFFFFF), the leading slots are the oracle's pq_search, and the counters
+    are those of the plain search over the code rows.  64 candidates from 40 vectors leave every row short; 2000
+    vectors fill every row."""
+    dim, m, ef = 32, 8, 64
+    rows, full, pq, ocodes, ocb = make(n, dim, m, ksub, seed=1)
+    oix = oracle.Index(rows, dim=dim, sum_mode=oracle.SUM_BLOCKED64)
+    oix.set_pq(ocodes, ocb, table_f16=0)
+    obp = oracle.default_build_params(seed=2, promote=0)
+    vs = oracle.shuffle(np.arange(n), obp.seed)
+    sizes = oracle.calculate_partitions(n, obp.order)
+    for i, sz in enumerate(sizes):
+        oix.generate_layer(vs[:sz], 48 if i == len(sizes) - 1 else 24, obp)
+        oix.improve_index(obp)
+    ofull = oracle.Index(rows, dim=dim, sum_mode=oracle.SUM_BLOCKED64)
+    ofull.set_sum_mode(oracle.SUM_BLOCKED64)  # what Index.store() hands pq_search: the constructor's mode is the handle's alone
+    qh = ph.QuantizedHnsw.__new__(ph.QuantizedHnsw)
+    qh.full, qh.store = full, pq
+    qh.hnsw = ph.Hnsw.from_layers(pq, [oix.layer(l) for l in range(oix.layer_count)])
+    q = oracle.synth_rows(2 ** 32, 96, dim)[:, :dim]
+    sp = (ef, ef, 1)
+    plain = qh.hnsw.search_batch(queries=q, sp=ph.SearchParameters(*sp), stats=True)
+    for quant in (False, True):
+        ri, rd, rl, rs = qh.search_batch(q, ph.SearchParameters(*sp), quantize_query=quant, stats=True)
+        oi, od, ol = oix.pq_search(ofull, q, sp, quantize_query=quant)
+        np.testing.assert_array_equal(rl, ol)
+        assert bool((rl < ef).all()) == short and bool((rl == ef).all()) != short
+        live = np.arange(ef)[None, :] < rl[:, None].astype(np.int64)
+        assert (ri[~live] == ph.EMPTY).all() and (rd[~live].view(np.uint32) == oracle.FMAX.view(np.uint32)).all()
+        assert (ri[live] < n).all()
+        np.testing.assert_array_equal(ri[live], oi[live])
+        np.testing.assert_array_equal(rd[live].view(np.uint32), od[live].view(np.uint32))
+        if not quant:  # the raw query is what the plain search walks with
+            np.testing.assert_array_equal(rs, plain[3])
