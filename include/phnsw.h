@@ -207,6 +207,39 @@ int phnsw_search_batch_device(const phnsw_index *ix, const float *queries_dev, u
                               uint32_t upto_layers, const uint32_t *exclude_dev,
                               uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
                               uint32_t *out_stats_dev, uint32_t *status_dev, void *stream);
+/* ---- searches restricted to an allow-list of VectorIds: Layer::closest_vectors' `include` closure
+ * (src/lib.rs:250-277) as a bitmap instead of the one instantiation `|v| Some(v) != exclude` (src/search.rs:128-134).
+ * A layer's result keeps v iff v != exclude[q] and the bit of v is set; take(candidate_count) counts kept entries only.
+ * It is a POST-filter on each layer's queue: the traversal is the unfiltered one, so a filter of density p leaves about
+ * p * number_of_candidates results -- selective filters want a larger number_of_candidates.
+ * The entry vector (layers[0].nodes[0]) enters the candidates before any filter runs (search.rs:102-111) and can be
+ * returned although it is disallowed, exactly as it can be returned although excluded; PHNSW_FILTER_STRICT removes
+ * disallowed ids from the final rows (lengths shrink, padding PHNSW_EMPTY / f32::MAX).
+ * Every store kind phnsw_search_batch accepts (f32, f16, i8, i8q, PQ).  The re-ranked calls (phnsw_f16_ / phnsw_i8_ /
+ * phnsw_i8q_search_batch[_device], phnsw_pq_search_batch*) take no filter. */
+enum { PHNSW_FILTER_STRICT = 1 };
+/* phnsw_search_batch_topk restricted to allowed VectorIds.  filter: bitmap words, bit v%32 of word v/32 set = allowed;
+ * filter_stride_words 0 = one bitmap of ceil(n/32) words for all queries, else nq bitmaps that far apart (>= ceil(n/32)):
+ * `filter` then holds nq * filter_stride_words words, the last bitmap a whole stride like the others (the host form
+ * copies whole strides).  Bits at or past n are ignored.  filter NULL = the index's default filter
+ * (phnsw_index_set_filter_device), else none.
+ * k 0 = number_of_candidates (the shape of phnsw_search_batch): out_ids / out_d hold nq rows of k entries, of
+ * number_of_candidates entries when k is 0.  out_stats nullable.  Exactly one of queries / qids. */
+int phnsw_search_batch_filtered(const phnsw_index *ix, const float *queries, const uint64_t *qids, uint64_t nq,
+                                const phnsw_search_params *sp, uint32_t upto_layers, const uint64_t *exclude,
+                                const uint32_t *filter, uint32_t filter_stride_words, uint32_t flags, uint64_t k,
+                                uint64_t *out_ids, float *out_d, uint64_t *out_len, uint64_t *out_stats);
+/* phnsw_search_batch_device with the same filter, its words resident in HBM (rows of number_of_candidates entries) */
+int phnsw_search_batch_filtered_device(const phnsw_index *ix, const float *queries_dev, uint32_t ldq,
+                                       const uint32_t *qids_dev, uint64_t nq, const phnsw_search_params *sp,
+                                       uint32_t upto_layers, const uint32_t *exclude_dev, const uint32_t *filter_dev,
+                                       uint32_t filter_stride_words, uint32_t flags, uint32_t *out_ids_dev,
+                                       float *out_d_dev, uint32_t *out_len_dev, uint32_t *out_stats_dev,
+                                       uint32_t *status_dev, void *stream);
+/* tombstones: a shared device bitmap of ceil(n/32) words, kept alive by the caller, becomes the filter of every
+ * FILTERED call on this index that passes filter == NULL (NULL here clears it).  The other entry points never see it.
+ * Not to be called while searches on the index are in flight. */
+int phnsw_index_set_filter_device(phnsw_index *ix, const uint32_t *filter_dev);
 /* Throughput callers keep TWO batches in flight: phnsw_search_batch_device calls issued alternately on two streams
  * overlap (an index holds two search workspaces) -- if the two streams sit on different hardware queues.  HIP maps a
  * process's streams onto a few of them (GPU_MAX_HW_QUEUES, 4 by default) and two streams that share one run in issue

@@ -298,6 +298,44 @@ class Hnsw {
       for (uint64_t j = 0; j < len[i]; j++) out[i].push_back({ids[i * k + j], d[i * k + j]});
     return out;
   }
+  // search_many_topk restricted to an allow bitmap over VectorIds (bit v % 32 of word v / 32 set = v may be returned):
+  // Layer::closest_vectors' `include` (lib.rs:250-277).  stride_words 0 = one bitmap for all queries, else one per
+  // query that far apart; an empty `allow` = the default of set_filter_device.  A post-filter on each layer's queue:
+  // expect about density * number_of_candidates results.  strict also removes a disallowed entry vector.  k 0 = all
+  // number_of_candidates entries of a row.  Throws on k > number_of_candidates and on an `allow` shorter than its
+  // bitmaps: ceil(n / 32) words shared, nq * stride_words words per query
+  std::vector<SearchResult> search_many_filtered(const std::vector<const float *> &queries, const SearchParameters &sp,
+                                                 uint64_t k, const std::vector<uint32_t> &allow, uint32_t stride_words = 0,
+                                                 bool strict = false) const {
+    const uint64_t nq = queries.size(), dim = c_->dim(), words = (c_->len() + 31) / 32;
+    if (k == 0) k = sp.number_of_candidates;  // the C call's "whole row"; the buffers below are sized by it
+    if (k > sp.number_of_candidates) throw Error(PHNSW_E_INVALID, "search_many_filtered: k exceeds number_of_candidates");
+    if (!allow.empty() && (stride_words ? stride_words < words || allow.size() < nq * stride_words : allow.size() < words))
+      throw Error(PHNSW_E_INVALID, "search_many_filtered: allow is shorter than its bitmaps (ceil(n / 32) words shared, "
+                                   "nq * stride_words per query, stride_words >= ceil(n / 32))");
+    std::vector<float> q(nq * dim);
+    for (uint64_t i = 0; i < nq; i++) std::copy(queries[i], queries[i] + dim, q.begin() + i * dim);
+    std::vector<uint64_t> ids(nq * k), len(nq);
+    std::vector<float> d(nq * k);
+    check(phnsw_search_batch_filtered(ix_, q.data(), nullptr, nq, &sp, 0, nullptr, allow.empty() ? nullptr : allow.data(),
+                                      stride_words, strict ? PHNSW_FILTER_STRICT : 0u, k, ids.data(), d.data(), len.data(),
+                                      nullptr));
+    std::vector<SearchResult> out(nq);
+    for (uint64_t i = 0; i < nq; i++)
+      for (uint64_t j = 0; j < len[i]; j++) out[i].push_back({ids[i * k + j], d[i * k + j]});
+    return out;
+  }
+  // zero-copy form (phnsw_search_batch_filtered_device): device pointers of the caller, enqueued on `stream`
+  void search_filtered_device(const float *queries_dev, uint32_t ldq, const uint32_t *qids_dev, uint64_t nq,
+                              const SearchParameters &sp, uint32_t upto, const uint32_t *exclude_dev, const uint32_t *filter_dev,
+                              uint32_t stride_words, bool strict, uint32_t *out_ids_dev, float *out_d_dev,
+                              uint32_t *out_len_dev, uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) const {
+    check(phnsw_search_batch_filtered_device(ix_, queries_dev, ldq, qids_dev, nq, &sp, upto, exclude_dev, filter_dev,
+                                             stride_words, strict ? PHNSW_FILTER_STRICT : 0u, out_ids_dev, out_d_dev,
+                                             out_len_dev, out_stats_dev, status_dev, stream));
+  }
+  // tombstones (phnsw_index_set_filter_device): the default bitmap of the filtered calls; nullptr clears it
+  void set_filter_device(const uint32_t *filter_dev) { check(phnsw_index_set_filter_device(ix_, filter_dev)); }
   // Hnsw::search_instrumented(v, sp) -> (results, index_distance)  lib.rs:667-673
   std::pair<SearchResult, uint64_t> search_instrumented(const AbstractVector &v, const SearchParameters &sp) const {
     const uint64_t ef = sp.number_of_candidates;

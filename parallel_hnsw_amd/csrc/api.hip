@@ -661,7 +661,7 @@ int ph_search_device(const phnsw_index *ix, const float *queries_dev, uint32_t l
                      uint32_t *out_ids, float *out_d, uint32_t *out_len, uint32_t *out_stats, uint32_t *status,
                      uint32_t ovf_cap, uint32_t knn_mode, hipStream_t stream, uint32_t out_stride,
                      uint32_t *out_hit, float threshold, uint32_t first_node, float hit_eps, const uint32_t *order,
-                     uint32_t *out_index, const PhRowHint *hint) {
+                     uint32_t *out_index, const PhRowHint *hint, const PhFilter *filter) {
   phnsw_index *mix = const_cast<phnsw_index *>(ix);
   if (ph_store_converted(ix->store) && (knn_mode || out_index || hint || out_hit)) {
     // an f16 / i8 store is searched, never built over: knn / threshold_nn / search_instrumented / the build's rounds
@@ -673,6 +673,11 @@ int ph_search_device(const phnsw_index *ix, const float *queries_dev, uint32_t l
   a.ldq = ldq;
   a.qids = qids_dev;
   a.exclude = exclude_dev;
+  if (filter && filter->words) {
+    a.filter = filter->words;
+    a.filter_stride = filter->stride;
+    a.filter_flags = filter->flags;
+  }
   a.nq = (uint32_t)nq;
   a.out_ids = out_ids;
   a.out_d = out_d;
@@ -810,6 +815,7 @@ int ph_search_device(const phnsw_index *ix, const float *queries_dev, uint32_t l
       if (b.queries) b.queries += c0 * ldq;
       if (b.qids) b.qids += c0;
       if (b.exclude) b.exclude += c0;
+      if (b.filter) b.filter += c0 * b.filter_stride;  // per-query bitmaps follow the chunk; a shared one (stride 0) stays
       b.out_ids += c0 * ostride;
       b.out_d += c0 * ostride;
       b.out_len += c0;
@@ -894,6 +900,60 @@ extern "C" int phnsw_search_batch_device(const phnsw_index *ix, const float *que
   PH_HIP(hipSetDevice(ix->store->device));
   return ph_search_device(ix, queries_dev, ldq, qids_dev, nq, sp, upto_layers, exclude_dev, out_ids_dev, out_d_dev,
                           out_len_dev, out_stats_dev, status_dev, 0, 0, (hipStream_t)stream);
+} catch (...) { return ph_caught(); }
+
+// ---- searches restricted to an allow-list of VectorIds: closest_vectors' `include` (lib.rs:250-277) as a bitmap
+
+// the argument checks the host and the device form share; *f = what the launch gets (nullptr words: no filter)
+int ph_filter_check(const phnsw_index *ix, const uint32_t *filter, uint32_t stride, uint32_t flags, const char *call,
+                    PhFilter *f) {
+  const uint64_t words = (ix->store->n + 31u) / 32u;
+  if (flags & ~(uint32_t)PHNSW_FILTER_STRICT) {
+    ph_set_error("%s: unknown flag bits 0x%x", call, flags);
+    return PHNSW_E_INVALID;
+  }
+  if (stride && stride < words) {
+    ph_set_error("%s: filter_stride_words %u is below the %llu words of one bitmap (0 = one shared bitmap)", call, stride,
+                 (unsigned long long)words);
+    return PHNSW_E_INVALID;
+  }
+  f->words = filter;
+  f->stride = filter ? stride : 0u;
+  f->flags = flags;
+  return 0;
+}
+
+extern "C" int phnsw_search_batch_filtered_device(const phnsw_index *ix, const float *queries_dev, uint32_t ldq,
+                                                  const uint32_t *qids_dev, uint64_t nq, const phnsw_search_params *sp,
+                                                  uint32_t upto_layers, const uint32_t *exclude_dev,
+                                                  const uint32_t *filter_dev, uint32_t filter_stride_words, uint32_t flags,
+                                                  uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                                  uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) try {
+  int rc = check_sp(ix, sp);
+  if (rc) return rc;
+  if ((!queries_dev && !qids_dev) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev ||
+      nq > 0xFFFFFFFFull || (queries_dev && (ldq < ix->store->ld || (ldq % 4) || ((uintptr_t)queries_dev % 16)))) {
+    ph_set_error("phnsw_search_batch_filtered_device: invalid argument (queries need ldq >= store ld, multiple of 4, 16-byte base)");
+    return PHNSW_E_INVALID;
+  }
+  PhFilter f;
+  rc = ph_filter_check(ix, filter_dev, filter_stride_words, flags, "phnsw_search_batch_filtered_device", &f);
+  if (rc) return rc;
+  if (!f.words) f.words = ix->default_filter;  // phnsw_index_set_filter_device
+  if (nq == 0) return 0;
+  PH_HIP(hipSetDevice(ix->store->device));
+  return ph_search_device(ix, queries_dev, ldq, qids_dev, nq, sp, upto_layers, exclude_dev, out_ids_dev, out_d_dev,
+                          out_len_dev, out_stats_dev, status_dev, 0, 0, (hipStream_t)stream, 0, nullptr, 0.f, 0, 0.f, nullptr,
+                          nullptr, nullptr, &f);
+} catch (...) { return ph_caught(); }
+
+extern "C" int phnsw_index_set_filter_device(phnsw_index *ix, const uint32_t *filter_dev) try {
+  if (!ix) {
+    ph_set_error("phnsw_index_set_filter_device: null index");
+    return PHNSW_E_INVALID;
+  }
+  ix->default_filter = filter_dev;
+  return 0;
 } catch (...) { return ph_caught(); }
 
 // tests: the raw distance table of the last launch's dense top layers ([positions][stride] f32, the last chunk's) and
@@ -1035,11 +1095,7 @@ extern "C" int phnsw_dense_top_layers(const phnsw_index *ix, uint64_t number_of_
   return 0;
 } catch (...) { return ph_caught(); }
 
-// host-pointer searches live in hostpath.hip (persistent staging, pipelined chunks)
-int ph_search_host(const phnsw_index *ix, const float *queries, const uint64_t *qids, uint64_t nq,
-                   const phnsw_search_params *sp, uint32_t upto, const uint64_t *exclude, uint64_t out_k,
-                   uint64_t *out_ids, float *out_d, uint64_t *out_len, uint64_t *out_stats, uint32_t knn_mode,
-                   uint64_t *out_index);
+// host-pointer searches live in hostpath.hip (persistent staging, pipelined chunks): ph_search_host
 static int search_host(const phnsw_index *ix, const float *queries, const uint64_t *qids, uint64_t nq,
                        const phnsw_search_params *sp, uint32_t upto, const uint64_t *exclude, uint64_t *out_ids,
                        float *out_d, uint64_t *out_len, uint64_t *out_stats, uint32_t knn_mode) {

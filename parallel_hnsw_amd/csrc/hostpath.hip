@@ -45,6 +45,8 @@ struct Slot {
   size_t take_cap = 0;
   uint32_t *h_small = nullptr;  // pinned mirror of `small`
   size_t h_cap = 0;
+  uint32_t *filt = nullptr;  // device: the chunk's per-query allow bitmaps [cnt][stride] (filtered searches)
+  size_t filt_bytes = 0;
   uint64_t c0 = 0, cnt = 0;  // the chunk in flight
   bool busy = false;
 };
@@ -53,6 +55,8 @@ struct Slot {
 
 struct PhHostStage {
   Slot slot[2];
+  uint32_t *filt = nullptr;  // device: a call's shared allow bitmap, staged once per call
+  size_t filt_bytes = 0;
   bool in_use = false;
   bool streams_checked = false;  // the two slots' streams were seen to run side by side (pair_streams)
 };
@@ -66,6 +70,7 @@ void slot_free(Slot &s) {
   if (s.d) hipFree(s.d);
   if (s.ids64) hipFree(s.ids64);
   if (s.dk) hipFree(s.dk);
+  if (s.filt) hipFree(s.filt);
   if (s.h_small) hipHostFree(s.h_small);
   if (s.done) hipEventDestroy(s.done);
   if (s.stream) hipStreamDestroy(s.stream);
@@ -219,6 +224,7 @@ void ph_host_stages_free(phnsw_index *ix) {
   for (PhHostStage *st : ix->stages) {
     slot_free(st->slot[0]);
     slot_free(st->slot[1]);
+    if (st->filt) hipFree(st->filt);
     delete st;
   }
   ix->stages.clear();
@@ -228,7 +234,7 @@ void ph_host_stages_free(phnsw_index *ix) {
 int ph_search_host(const phnsw_index *ix, const float *queries, const uint64_t *qids, uint64_t nq,
                    const phnsw_search_params *sp, uint32_t upto, const uint64_t *exclude, uint64_t out_k,
                    uint64_t *out_ids, float *out_d, uint64_t *out_len, uint64_t *out_stats, uint32_t knn_mode,
-                   uint64_t *out_index) {
+                   uint64_t *out_index, const PhFilter *filter, bool filter_on_device) {
   if (!ix || !sp || ix->layers.empty()) {
     ph_set_error("search: null index/params or index without layers");
     return PHNSW_E_INVALID;
@@ -292,6 +298,23 @@ int ph_search_host(const phnsw_index *ix, const float *queries, const uint64_t *
     return 0;
   };
 
+  // the allow-list: a shared bitmap goes to the device once per call, per-query bitmaps travel with their chunk
+  const bool filtered = filter && filter->words;
+  const bool per_query = filtered && filter->stride != 0;
+  const uint64_t filter_words = (s->n + 31u) / 32u;
+  PhFilter fdev = {nullptr, 0u, filtered ? filter->flags : 0u};
+  if (filtered && filter_on_device) fdev.words = filter->words;
+  if (filtered && !filter_on_device && !per_query) {
+    Slot &s0 = st->slot[0];
+    if (!s0.stream) {
+      PH_HIP(hipStreamCreateWithFlags(&s0.stream, hipStreamNonBlocking));
+      PH_HIP(hipEventCreateWithFlags(&s0.done, hipEventDisableTiming));
+    }
+    PH_TRY(grow(&st->filt, &st->filt_bytes, (size_t)filter_words * 4, "host path: filter staging"));
+    PH_HIP(hipMemcpyAsync(st->filt, filter->words, (size_t)filter_words * 4, hipMemcpyHostToDevice, s0.stream));
+    PH_HIP(hipStreamSynchronize(s0.stream));  // both slots' streams read it
+    fdev.words = st->filt;
+  }
   if (n_chunks >= 2 && !st->streams_checked) {  // the first pipelined call of this staging set: see pair_streams
     for (Slot &sl : st->slot)
       if (!sl.stream) {
@@ -326,9 +349,17 @@ int ph_search_host(const phnsw_index *ix, const float *queries, const uint64_t *
         for (uint64_t i = 0; i < cnt; i++) sl.h_small[N + i] = exclude[c0 + i] >= s->n ? PH_EMPTY32 : (uint32_t)exclude[c0 + i];
       PH_HIP(hipMemcpyAsync(sl.small, sl.h_small, 2 * N * 4, hipMemcpyHostToDevice, sl.stream));
     }
+    if (per_query) {
+      const size_t bytes = (size_t)cnt * filter->stride * 4;
+      rc = grow(&sl.filt, &sl.filt_bytes, bytes, "host path: per-query filter staging");
+      if (rc) break;
+      PH_HIP(hipMemcpyAsync(sl.filt, filter->words + c0 * filter->stride, bytes, hipMemcpyHostToDevice, sl.stream));
+      fdev.words = sl.filt;
+      fdev.stride = filter->stride;
+    }
     rc = ph_search_device(ix, queries ? sl.q : nullptr, s->ld, qids ? d_qid : nullptr, cnt, sp, upto, exclude ? d_excl : nullptr,
                           sl.ids, sl.d, d_len, d_stats, d_status, 0, knn_mode, sl.stream, 0, nullptr, 0.f, (uint32_t)c0, 0.f,
-                          nullptr, out_index ? d_index : nullptr);
+                          nullptr, out_index ? d_index : nullptr, nullptr, filtered ? &fdev : nullptr);
     if (rc) break;
     sl.c0 = c0;
     sl.cnt = cnt;
@@ -376,9 +407,16 @@ int ph_search_host(const phnsw_index *ix, const float *queries, const uint64_t *
       sl.h_small[0] = qids ? (uint32_t)qids[qi] : 0u;
       sl.h_small[N] = (exclude && exclude[qi] < s->n) ? (uint32_t)exclude[qi] : PH_EMPTY32;
       PH_HIP(hipMemcpyAsync(sl.small, sl.h_small, 2 * N * 4, hipMemcpyHostToDevice, sl.stream));
+      if (per_query) {  // (slot 0 holds at least one bitmap: it staged a chunk)
+        PH_HIP(hipMemcpyAsync(sl.filt, filter->words + (uint64_t)qi * filter->stride, (size_t)filter->stride * 4,
+                              hipMemcpyHostToDevice, sl.stream));
+        fdev.words = sl.filt;
+        fdev.stride = filter->stride;
+      }
       PH_TRY(ph_search_device(ix, queries ? sl.q : nullptr, s->ld, qids ? sl.small : nullptr, 1, sp, upto,
                               exclude ? sl.small + N : nullptr, sl.ids, sl.d, sl.small + 2 * N, sl.small + 5 * N, sl.small + 3 * N,
-                              ovf_cap, 0, sl.stream, 0, nullptr, 0.f, 0, 0.f, nullptr, out_index ? sl.small + 4 * N : nullptr));
+                              ovf_cap, 0, sl.stream, 0, nullptr, 0.f, 0, 0.f, nullptr, out_index ? sl.small + 4 * N : nullptr,
+                              nullptr, filtered ? &fdev : nullptr));
       sl.c0 = qi;
       sl.cnt = 1;
       sl.busy = true;
@@ -439,4 +477,25 @@ extern "C" int phnsw_search_instrumented(const phnsw_index *ix, const float *que
     return PHNSW_E_INVALID;
   }
   return ph_search_host(ix, queries, qids, nq, sp, 0, nullptr, 0, out_ids, out_d, out_len, nullptr, 0, out_index_distance);
+} catch (...) { return ph_caught(); }
+
+// Hnsw::search with closest_vectors' `include` (lib.rs:250-277) as an allow bitmap over VectorIds
+extern "C" int phnsw_search_batch_filtered(const phnsw_index *ix, const float *queries, const uint64_t *qids, uint64_t nq,
+                                           const phnsw_search_params *sp, uint32_t upto_layers, const uint64_t *exclude,
+                                           const uint32_t *filter, uint32_t filter_stride_words, uint32_t flags, uint64_t k,
+                                           uint64_t *out_ids, float *out_d, uint64_t *out_len, uint64_t *out_stats) try {
+  if (((!queries) == (!qids)) && nq) {
+    ph_set_error("phnsw_search_batch_filtered: pass queries or qids (exactly one)");
+    return PHNSW_E_INVALID;
+  }
+  if (!ix || ix->layers.empty()) {
+    ph_set_error("search: null index/params or index without layers");
+    return PHNSW_E_INVALID;
+  }
+  PhFilter f;
+  PH_TRY(ph_filter_check(ix, filter, filter_stride_words, flags, "phnsw_search_batch_filtered", &f));
+  const bool use_default = !f.words && ix->default_filter;  // phnsw_index_set_filter_device: device words
+  if (use_default) f.words = ix->default_filter;
+  return ph_search_host(ix, queries, qids, nq, sp, upto_layers, exclude, k, out_ids, out_d, out_len, out_stats, 0, nullptr, &f,
+                        use_default);
 } catch (...) { return ph_caught(); }

@@ -218,6 +218,12 @@ struct PhRowHint {
   bool contiguous;           // false: any nodes of X (a recall sample)
 };
 
+// the allow-list of a filtered search as ph_search_device takes it (device words; PhSearchArgs::filter*)
+struct PhFilter {
+  const uint32_t *words;
+  uint32_t stride, flags;
+};
+
 struct PhPendingLayer;
 struct PhHostStage;  // hostpath.hip: persistent staging of the host-pointer search entry points
 struct phnsw_index {
@@ -241,6 +247,7 @@ struct phnsw_index {
   float last_kernel_ms = 0.f;
   unsigned long long *totals = nullptr;  // device [2]: distance evaluations, hops of every launch on this index
   const uint32_t *dbg_order = nullptr;  // experiment hook
+  const uint32_t *default_filter = nullptr;  // phnsw_index_set_filter_device: the caller's shared bitmap, filtered calls only
   uint64_t dbg_order_n = 0;
 };
 
@@ -251,6 +258,11 @@ struct PhSearchArgs {
   uint32_t ldq;
   const uint32_t *qids;     // or nullptr
   const uint32_t *exclude;  // or nullptr
+  // allow-list of closest_vectors' `include` (lib.rs:250-277): bit v & 31 of word v >> 5 set = VectorId v may be
+  // returned; nullptr = no filter.  filter_stride: words from one query's bitmap to the next, 0 = one bitmap for the
+  // whole launch.  filter_flags: PHNSW_FILTER_STRICT also drops disallowed ids from the final output row (search.hip)
+  const uint32_t *filter;
+  uint32_t filter_stride, filter_flags;
   uint32_t nq;
   uint32_t n_layers;
   PhLayerDev layers[PH_MAX_LAYERS];
@@ -355,7 +367,15 @@ int ph_search_device(const phnsw_index *ix, const float *queries_dev, uint32_t l
                      uint32_t ovf_cap, uint32_t knn_mode, hipStream_t stream, uint32_t out_stride = 0,
                      uint32_t *out_hit = nullptr, float threshold = 0.f, uint32_t first_node = 0,
                      float hit_eps = 0.f, const uint32_t *order = nullptr, uint32_t *out_index = nullptr,
-                     const PhRowHint *hint = nullptr);
+                     const PhRowHint *hint = nullptr, const PhFilter *filter = nullptr);
+// argument checks of the filtered entry points (api.hip): flags, stride; *f = the triple a launch gets
+int ph_filter_check(const phnsw_index *ix, const uint32_t *filter, uint32_t stride, uint32_t flags, const char *call,
+                    PhFilter *f);
+// host-pointer searches (hostpath.hip).  filter: host words (or, filter_on_device, device words of a shared bitmap)
+int ph_search_host(const phnsw_index *ix, const float *queries, const uint64_t *qids, uint64_t nq,
+                   const phnsw_search_params *sp, uint32_t upto, const uint64_t *exclude, uint64_t out_k,
+                   uint64_t *out_ids, float *out_d, uint64_t *out_len, uint64_t *out_stats, uint32_t knn_mode,
+                   uint64_t *out_index, const PhFilter *filter = nullptr, bool filter_on_device = false);
 // locality schedule helpers (group.hip / api.hip)
 #define PH_ORDER_MIN 16384u  // shorter query lists run in natural order
 #define PH_POS_MIN 256u     // smaller layers carry no cells (their node id is the key)

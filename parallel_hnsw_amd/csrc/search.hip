@@ -36,923 +36,9 @@
 //    throughout, as on the latency, threshold_nn big-queue, PQ and _instr kernels.
 //
 // Hand-written for CDNA4: wave64 ballots/readlane, LDS queue, no portability layer.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-
-#include "phnsw_internal.h"
-
-#include "phnsw_device.h"
-
-// -DPH_HOP_PROFILE: a debugging build that prints, per layer of every query, where the hops' time went
-// (100 MHz ticks of s_memrealtime; each phase ends with a forced wait).  Never part of libphnsw.so proper.
-#ifdef PH_HOP_PROFILE
-#define PH_TICK(k)                                   \
-  {                                                  \
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)");   \
-    const uint64_t t_now = wall_clock64();           \
-    tprof[k] += t_now - t_last;                      \
-    t_last = t_now;                                  \
-  }
-#else
-#define PH_TICK(k)
-#endif
-
-// INSTR: Hnsw::search_instrumented (lib.rs:667-673).  Every visit_queue entry of the reference carries the
-// index_sum of its discovery path (lib.rs:211-220: parent's sum + 1-based rank in the parent's sorted batch); the
-// value returned is the index_sum of the node expanded at the last hop of the bottom layer that changed
-// candidates.first() (lib.rs:225-231).  The sums ride along in a third queue array (the prefix scratch S, idle
-// during the hops) and a parallel spill array; the plain kernels compile none of it.
-// BIG (threshold_nn only, ph_search_kernel_big): the layer queue lives in global memory with a capacity chosen at
-// launch (a.cap_max), so resize_capacity can go on doubling past what LDS holds.  The queue is then shared between
-// the lanes of the wave through L2: every barrier of the body also orders and invalidates (queue_sync), and the loops
-// over the queue's 64-entry chunks run to the live length instead of being unrolled CAPC times.
-template <bool BIG>
-__device__ __forceinline__ void queue_sync() {
-  if constexpr (BIG) __threadfence();
-  __syncthreads();
-}
-
-// The row-store throughput kernels (f32, f16, i8 rows alike) whose walks can get an LDS visited table (vis_table_slots: what the CU's LDS leaves a
-// resident wave beside its queues, at least max(1024, 4 ef) slots): queues of 128 slots; of 256 except at <= 256
-// dimensions (16 waves per CU leave under 1024 slots); of 512 at 1536 dimensions (8 waves per CU).  Every other
-// kernel compiles none of the table code, which would only cost it registers (<8, DistF32<1,4>>: 125 -> 129 VGPRs,
-// 4 -> 3 waves per SIMD).  The one-wave-per-SIMD latency kernels (U = 0) measured 2 % slower with the table for
-// batches of 1, 64 and 1024 and keep the bitmap too.
-__host__ __device__ constexpr bool vis_lds_shape(int capc, int nv) {
-  return capc == 2 || (capc == 4 && nv != 1) || (capc == 8 && nv == 6);
-}
-template <int CAPC, class D, class = void>
-struct vis_lds_policy : std::false_type {};
-template <int CAPC, class D>
-struct vis_lds_policy<CAPC, D, std::enable_if_t<D::ROW_STORE>>
-    : std::integral_constant<bool, D::ROWS_IN_FLIGHT != 0 && vis_lds_shape(CAPC, D::CHUNKS)> {};
-
-// The LDS visited set: slot of a NodeId (multiplicative hash, scaled to any table size)
-__device__ __forceinline__ uint32_t vis_slot(uint32_t id, uint32_t slots) {
-  return (uint32_t)(((uint64_t)(id * 0x9E3779B1u) * slots) >> 32);
-}
-
-// test-and-insert of one id per lane (valid lanes): true when the id was not in the table.  EMPTY = fresh,
-// equal = visited, anything else = the next slot; the loop runs until every lane has resolved.  The load limit
-// keeps the table from filling, so every probe sequence ends.
-__device__ __forceinline__ bool vis_insert(uint32_t *H, uint32_t slots, uint32_t id, bool valid) {
-  bool fresh = false, pending = valid;
-  uint32_t s = valid ? vis_slot(id, slots) : 0u;
-  while (__ballot(pending)) {
-    if (pending) {
-      const uint32_t old = atomicCAS(&H[s], PH_EMPTY32, id);
-      if (old == PH_EMPTY32 || old == id) {
-        fresh = old == PH_EMPTY32;
-        pending = false;
-      } else {
-        s = s + 1u == slots ? 0u : s + 1u;
-      }
-    }
-  }
-  return fresh;
-}
-
-template <int CAPC, class Dist, bool INSTR = false, bool BIG = false>
-__device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
-  extern __shared__ uint32_t smem[];
-  constexpr int CAP = CAPC * 64;
-  uint32_t *Cid = smem;                    // running candidates: VectorIds (search.rs:110)
-  float *Cd = (float *)(smem + CAP);       //
-  uint32_t *Qid = smem + 2 * CAP;          // layer queue: NodeIds | EXPF (lib.rs:264)
-  float *Qd = (float *)(smem + 3 * CAP);   //
-  if constexpr (BIG) {
-    Qid = a.big_q + (uint64_t)blockIdx.x * 2u * a.cap_max;
-    Qd = (float *)(Qid + a.cap_max);
-  }
-  uint32_t *S = smem + 4 * CAP;            // prefix scratch [CAP + 64]
-  float *dist_lds = (float *)(smem + 5 * CAP + 64);  // DistPQ: the query's lookup table
-  if (Dist::GLOBAL_TABLE) dist_lds = (float *)((char *)a.pq_tables + (size_t)blockIdx.x * a.pq_table_bytes);
-  // dense top layers (tiny.hip): this query's row of the distance table and the visited bits of the
-  // table ids, both in LDS; T = 0 when the launch has none (or its layers turned out not to be nested)
-  const uint32_t T = (a.tiny_layers && a.tiny_member[a.tiny_n] == 0u) ? a.tiny_layers : 0u;
-  const bool tiny_lds_row = a.tiny_n <= a.tiny_lds_nodes;
-  float *Dl = (float *)(smem + 5 * CAP + 64);
-  uint32_t *Vl = smem + 5 * CAP + 64 + (tiny_lds_row ? a.tiny_stride : 0u);
-  const uint32_t tiny_words = (a.tiny_n + 31u) / 32u;
-
-  const uint32_t lane = threadIdx.x;
-  const uint64_t lt = lanemask_lt(lane);
-  constexpr bool DENSE_ONLY = dist_is_none<Dist>::value;
-  // the dense-only launch and its follow-up agree through the table's device-side "usable" flag (phnsw_internal.h)
-  const bool table_ok = (a.dense_only || a.after_dense) ? a.dense_flag[0] == 0u : true;
-  if (DENSE_ONLY && !table_ok) return;  // layers not nested: the follow-up launch walks everything per hop
-  const uint32_t layer_lo = a.after_dense ? (table_ok ? a.after_dense : 0u) : a.layer_lo;
-  uint32_t *vis = a.visited + (uint64_t)blockIdx.x * a.visited_words;
-  uint2 *ovf = DENSE_ONLY ? a.dense_ovf + (uint64_t)blockIdx.x * a.dense_ovf_cap : a.ovf + (uint64_t)blockIdx.x * a.ovf_cap;
-  const uint32_t ovf_cap = DENSE_ONLY ? a.dense_ovf_cap : a.ovf_cap;
-  uint32_t *const Qs = S;
-  uint32_t *const ovf_s = INSTR ? a.ovf_s + (uint64_t)blockIdx.x * a.ovf_cap : nullptr;
-  // visited set of the gathered layers in LDS (vis_slots = 0: the bitmap in HBM); empty between layers
-  uint32_t *const H = smem + a.vis_off;
-  const uint32_t hslots = (BIG || INSTR || !vis_lds_policy<CAPC, Dist>::value) ? 0u : a.vis_slots;
-  for (uint32_t i = lane; i < hslots; i += 64) H[i] = PH_EMPTY32;
-
-  // locality schedule: with an `order` the query list is cut into 8 consecutive segments, one
-  // per XCD, so that the queries one L2 serves together are neighbours in `order`; a wave
-  // whose segment is exhausted moves on to the next one (no idle tail)
-  uint32_t seg_cur = 0, seg_done = 0;
-  if (a.order) {
-    uint32_t xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    seg_cur = (xcc & 15u) & 7u;
-  }
-
-  for (;;) {
-    uint32_t q = 0, qpos = 0;  // qpos: position in the launch's processing order (row of the dense table)
-    if (!a.order) {
-      if (lane == 0) q = atomicAdd(a.counter, 1u);
-      q = rfl32(q);
-      if (q >= a.nq) break;
-      qpos = q;
-    } else {
-      for (;;) {
-        uint32_t p = 0;
-        if (lane == 0) p = atomicAdd(a.counter + seg_cur * 16u, 1u);
-        p = rfl32(p);
-        const uint32_t base = seg_cur * a.seg;
-        const uint32_t len = base >= a.nq ? 0u : min(a.seg, a.nq - base);
-        if (p < len) {
-          qpos = base + p;
-          q = a.order[qpos];
-          break;
-        }
-        seg_cur = (seg_cur + 1u) & 7u;
-        if (++seg_done == 8u) {
-          q = PH_EMPTY32;
-          break;
-        }
-      }
-      if (q == PH_EMPTY32) break;
-    }
-
-    const uint32_t last_layer = a.n_layers - 1;
-    // a descent may run as two launches (upper layers; then the bottom layer with the queries
-    // re-ordered by where they landed): layers [layer_lo, layer_hi) of this launch, the running
-    // candidates parked in the output rows in between
-    const uint32_t layer_hi = a.layer_hi ? a.layer_hi : a.n_layers;
-    if (layer_lo && a.status[q] != ST_OK) continue;  // failed in the first launch: keep its status
-    // knn modes: the query is a node of the bottom layer
-    const uint32_t qnode = (BIG && a.knn_nodes) ? a.knn_nodes[q] : a.first_node + q;
-    uint32_t qvec = a.knn_mode ? a.layers[last_layer].nodes[qnode] : (a.qids ? a.qids[q] : 0u);
-    // row of this query in the dense table: its launch position, or (the build's kept table) its NodeId in layer X
-    uint64_t trow = qpos;
-    if (a.tiny_rows) trow = (uint64_t)((a.tiny_row_map ? a.tiny_row_map[qvec] : qvec) - a.tiny_row_first);
-    Dist dist;
-    if (a.queries && !a.knn_mode)
-      dist.prepare_raw(a.dist, a.queries + (uint64_t)q * a.ldq, dist_lds, lane);
-    else
-      dist.prepare_stored(a.dist, qvec, dist_lds, lane);
-    const uint32_t excl = a.exclude ? a.exclude[q] : PH_EMPTY32;
-    uint32_t n_dist = 0, n_hops = 0, err = ST_OK;
-    uint32_t index_distance = 0xFFFFFFFFu;  // usize::MAX until a layer has run  search.rs:112
-    uint32_t n_tab = 0;  // of n_dist: evaluations served by the dense tables (measurement: the rest are gathered rows)
-    uint32_t n_dist0 = 0, n_hops0 = 0;  // counters a split descent brought in from its earlier launches
-    uint32_t clen = 0;
-    uint32_t ef = a.ef;  // queue capacity; grows in threshold_nn mode (resize_capacity)
-    bool big_written = false;
-
-    if (layer_lo) {
-      clen = a.out_len[q];
-#pragma unroll
-      for (int c = 0; c < CAPC; c++) {
-        uint32_t i = lane + 64u * c;
-        if (i < clen) {
-          Cid[i] = a.out_ids[(uint64_t)q * a.ef + i];
-          Cd[i] = a.out_d[(uint64_t)q * a.ef + i];
-        }
-      }
-      if (a.out_stats) {
-        n_dist = a.out_stats[2 * (uint64_t)q];
-        n_hops = a.out_stats[2 * (uint64_t)q + 1];
-      }
-      n_dist0 = n_dist;
-      n_hops0 = n_hops;
-    } else if (!a.knn_mode) {
-      // entry_vector + distance_from_entry  search.rs:101-111
-      uint32_t entry = a.layers[0].nodes[0];
-      float d0;
-      if constexpr (DENSE_ONLY) {  // the table holds it
-        const PhLayerDev TLy = a.layers[a.tiny_layers - 1];
-        const uint32_t tid = TLy.vec2node ? TLy.vec2node[entry] : entry;
-        d0 = (a.tiny_d + trow * a.tiny_stride)[tid < a.tiny_n ? tid : 0u];
-      } else {
-        d0 = dist.batch(a.dist, 1ull, entry, lane);
-      }
-      d0 = __uint_as_float(rl32(__float_as_uint(d0), 0));
-      n_dist = 1;
-      if (lane == 0) {
-        Cid[0] = entry;
-        Cd[0] = d0;
-      }
-      clen = 1;
-    }
-    const float *Dg = a.tiny_d + trow * a.tiny_stride;  // this query's row of the table
-    if (T) {
-      if (tiny_lds_row)
-        for (uint32_t i = lane; i < a.tiny_n; i += 64) Dl[i] = Dg[i];
-      for (uint32_t i = lane; i < tiny_words; i += 64) Vl[i] = 0u;
-    }
-    queue_sync<BIG>();
-
-    for (uint32_t li = a.knn_mode ? last_layer : layer_lo; li < layer_hi && err == ST_OK; li++) {
-      PhLayerDev L = a.layers[li];
-      // a dense top layer is walked in table ids: ids, id maps and neighbour rows of the table layer
-      const bool tl = li < T;
-      if (tl) {
-        const PhLayerDev TLy = a.layers[T - 1];
-        L.n_nodes = a.tiny_n;
-        L.nodes = TLy.nodes;
-        L.vec2node = TLy.vec2node;
-        L.neighbors = a.tiny_nbr + a.tiny_off[li];
-      }
-      const bool identity = L.vec2node == nullptr;
-      bool hv = hslots && !tl;  // this layer's visited set is the LDS table (until it would pass its load limit)
-      uint32_t hn = 0;          // ids in the table
-      // test-and-set of one id per valid lane in the layer's visited set: true when it was not in it.  A batch that
-      // could take the table past vis_limit first moves the table into the bitmap, where the layer then goes on.
-      auto visit = [&](uint32_t id, bool valid) -> bool {
-        if (hv && hn + (uint32_t)__popcll(__ballot(valid)) > a.vis_limit) {
-          for (uint32_t i = lane; i < hslots; i += 64) {
-            const uint32_t o = H[i];
-            if (o != PH_EMPTY32) {
-              atomicOr(&vis[o >> 5], 1u << (o & 31));
-              H[i] = PH_EMPTY32;
-            }
-          }
-          wait_vm0();
-          hv = false;
-        }
-        if (hv) {
-          const bool f = vis_insert(H, hslots, id, valid);
-          hn += (uint32_t)__popcll(__ballot(f));
-          return f;
-        }
-        if (!valid) return false;
-        const uint32_t bit = 1u << (id & 31);
-        return !(atomicOr(&vis[id >> 5], bit) & bit);
-      };
-      // ---- closest_vectors: VectorId -> NodeId, queue = new(cap); merge_pairs  lib.rs:258-266
-      uint32_t qlen;
-      if (a.knn_mode) {
-        // pq.merge_pairs(&[(node, 0.0)])  lib.rs:917-918
-        if (lane == 0) {
-          Qid[0] = qnode;
-          Qd[0] = 0.0f;
-        }
-        visit(qnode, lane == 0);
-        qlen = 1;
-      } else {
-        bool miss = false;
-#pragma unroll
-        for (int c = 0; c < CAPC; c++) {
-          uint32_t i = lane + 64u * c;
-          if (i < clen) {
-            uint32_t vid = Cid[i];
-            uint32_t nid = identity ? vid : L.vec2node[vid];
-            if (nid >= L.n_nodes || (tl && !((a.tiny_member[nid] >> li) & 1u))) {  // get_node(v).unwrap() would panic  lib.rs:261
-              miss = true;
-              nid = 0;
-            }
-            Qid[i] = nid;
-            Qd[i] = Cd[i];
-          }
-        }
-        if (__ballot(miss)) {
-          err = ST_MISSING;
-          break;
-        }
-        // visited = candidates ids  lib.rs:187
-#pragma unroll
-        for (int c = 0; c < CAPC; c++) {
-          uint32_t i = lane + 64u * c;
-          if (tl) {
-            if (i < clen) atomicOr(&Vl[Qid[i] >> 5], 1u << (Qid[i] & 31));
-          } else if (64u * c < clen) {
-            visit(i < clen ? Qid[i] : 0u, i < clen);
-          }
-        }
-        qlen = clen;
-      }
-      queue_sync<BIG>();
-
-      // Hnsw::threshold_nn (lib.rs:930-962, knn_mode == 2) calls closest_nodes repeatedly on a
-      // growing queue; everything else runs this block once
-      float thr_last = 0.0f;
-      uint32_t thr_last_size = 0;
-      for (;;) {
-      if (a.knn_mode == 2) {
-        if (!(thr_last < a.threshold && qlen > thr_last_size)) break;  // lib.rs:945
-        thr_last_size = qlen;
-        if (thr_last_size > 1 || n_hops > 0) {
-          // a fresh closest_nodes call: every queue entry is a seed again (lib.rs:182-187)
-#pragma unroll
-          for (int c = 0; c < (BIG ? (int)((qlen + 63u) >> 6) : CAPC); c++) {
-            uint32_t i = lane + 64u * c;
-            uint32_t nid = 0;
-            if (i < qlen) {
-              nid = Qid[i] & IDM;
-              Qid[i] = nid;
-            }
-            if (64u * c < qlen) visit(nid, i < qlen);
-          }
-          queue_sync<BIG>();
-        }
-      }
-      // ---- closest_nodes  lib.rs:175-248
-      uint32_t ovf_n = 0;
-      uint32_t pd = a.probe_depth;
-      uint32_t highest = 0;  // highest_improvement  lib.rs:190
-      if constexpr (INSTR) {
-#pragma unroll
-        for (int c = 0; c < CAPC; c++)
-          if (lane + 64u * c < qlen) Qs[lane + 64u * c] = 0u;  // seeds: NodeDistance::ZERO  lib.rs:182-185
-        queue_sync<BIG>();
-      }
-      // every queue entry below scan_from has been expanded: the pop scan starts at its 64-entry chunk,
-      // and a hop's merge touches only the chunks from its first insertion point on
-      uint32_t scan_from = 0;
-#ifdef PH_CELL_PROBE
-      const bool probing = a.probe_pos && li == last_layer && !tl;
-      uint32_t probe_p0 = 0, probe_cnt[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-      if (probing) probe_p0 = a.probe_pos[Qid[0] & IDM];
-#endif
-#ifdef PH_HOP_PROFILE
-      uint64_t tprof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      uint64_t t_last = wall_clock64();
-      const uint32_t hops_before = n_hops, dist_before = n_dist;
-#endif
-      for (;;) {
-        // visit_queue.pop(): smallest (d,id) among not yet expanded nodes  lib.rs:191,243-244
-        int pop = -1;
-        uint32_t cur = 0;
-        for (uint32_t c = scan_from >> 6; 64u * c < qlen; c++) {
-          const uint32_t i = lane + 64u * c;
-          const uint32_t e = i < qlen ? Qid[i] : EXPF;
-          const uint64_t b = __ballot(!(e & EXPF));
-          if (b) {
-            const int pl = __builtin_ctzll(b);
-            pop = (int)(64u * c) + pl;
-            cur = rl32(e, pl);
-            break;
-          }
-        }
-        if (pop >= 0) {
-          if (lane == 0) Qid[pop] = cur | EXPF;
-          if constexpr (BIG) __threadfence();  // the merge below reads the slot back from another lane
-        } else {
-          if (ovf_n == 0) break;
-          wait_vm0();  // spill stores of this wave have reached L2
-          uint64_t best = KEY_NONE;
-          uint32_t bi = 0;
-          for (uint32_t i = lane; i < ovf_n; i += 64) {
-            uint32_t id = __hip_atomic_load(&ovf[i].x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (!(id & EXPF)) {
-              uint32_t db = __hip_atomic_load(&ovf[i].y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              uint64_t k = mkkey(__uint_as_float(db), id);
-              if (k < best) {
-                best = k;
-                bi = i;
-              }
-            }
-          }
-#pragma unroll
-          for (int s = 32; s >= 1; s >>= 1) {
-            uint64_t o = ((uint64_t)__shfl_xor((uint32_t)(best >> 32), s) << 32) | __shfl_xor((uint32_t)best, s);
-            uint32_t oi = __shfl_xor(bi, s);
-            if (o < best) {
-              best = o;
-              bi = oi;
-            }
-          }
-          if (best == KEY_NONE) break;  // frontier exhausted
-          cur = (uint32_t)best & IDM;
-          if (lane == 0)
-            __hip_atomic_store(&ovf[bi].x, cur | EXPF, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          pop = -1 - (int)bi;  // INSTR reads the spilled entry's index_sum below
-        }
-        uint32_t cur_s = 0;
-        if constexpr (INSTR) cur_s = pop >= 0 ? Qs[pop] : ovf_s[(uint32_t)(-1 - pop)];
-        cur &= IDM;
-        n_hops++;
-        PH_TICK(0)
-
-        // get_neighbors(next) + filter(!visited)  lib.rs:195-198
-        uint32_t nb = PH_EMPTY32;
-        if (lane < L.W) nb = L.neighbors[(uint64_t)cur * L.W + lane];
-        if constexpr (Dist::EARLY) {
-          // the candidates' rows are requested before the visited test-and-set below returns
-          const bool valid = nb < L.n_nodes;
-          uint32_t v = 0;
-          if (valid) v = identity ? nb : L.nodes[nb];
-          dist.prefetch(a.dist, valid, v, lane);
-        }
-        PH_TICK(1)
-        bool fresh = false;
-        if (tl) {
-          if (nb < L.n_nodes) {
-            uint32_t bit = 1u << (nb & 31);
-            fresh = !(atomicOr(&Vl[nb >> 5], bit) & bit);
-          }
-        } else {
-          fresh = visit(nb, nb < L.n_nodes);
-        }
-        const uint64_t fm = __ballot(fresh);
-        const uint32_t m = __popcll(fm);
-        n_dist += m;
-        if (tl) n_tab += m;
-#ifdef PH_CELL_PROBE
-        if (probing) {
-          uint32_t dd = 0xFFFFFFFFu;
-          if (fresh) {
-            const int d0 = (int)a.probe_pos[nb] - (int)probe_p0;
-            dd = (uint32_t)(d0 < 0 ? -d0 : d0);
-          }
-#pragma unroll
-          for (int k = 0; k < 10; k++) probe_cnt[k] += __popcll(__ballot(fresh && dd <= (k ? (1u << (k - 1)) : 0u)));
-          probe_cnt[10] += m;
-        }
-#endif
-        PH_TICK(2)
-
-        // distance batch: compare_vec(v, Stored(get_vector(n)))  lib.rs:200-202 -- in a dense top
-        // layer the value was computed by the tile pass (same bits) and is looked up
-        float myd;
-        if (tl) {
-          myd = 0.f;
-          if (fresh) myd = tiny_lds_row ? Dl[nb] : Dg[nb];
-        } else if constexpr (Dist::EARLY) {
-          myd = dist.finish(a.dist, fm, lane);
-        } else {
-          uint32_t vid = 0;
-          if (fresh) vid = identity ? nb : L.nodes[nb];
-          myd = dist.batch(a.dist, fm, vid, lane);
-        }
-
-        PH_TICK(3)
-        // candidates.merge_pairs(sorted batch)  lib.rs:206,226 / priority_queue.rs:109-144,
-        // as one parallel rank-merge.  Batch keys are distinct and absent from the queue
-        // (visited), so final slot = (#queue keys below) + (#batch keys below).
-        const uint64_t key = fresh ? mkkey(myd, nb) : KEY_NONE;
-        uint32_t my_s = 0;
-        if constexpr (INSTR) {  // (ix, (n, d)) of the sorted batch: index_sum + ix + 1  lib.rs:211-220
-          uint32_t rank_all = 0;
-          uint64_t remf = fm;
-          while (remf) {
-            const int j = __builtin_ctzll(remf);
-            remf &= remf - 1;
-            rank_all += (rl64(key, j) < key) ? 1u : 0u;
-          }
-          my_s = cur_s + rank_all + 1u;
-        }
-        // An element that is worse than the tail of a FULL queue cannot enter it: it goes straight to
-        // the spill list and takes no part in the merge.  Late in a layer most hops bring nothing
-        // else; those skip the merge altogether.
-        const bool full = qlen == ef;
-        const float dtail = full ? Qd[ef - 1] : PH_FMAX;
-        const uint64_t tailkey = full ? mkkey(dtail, Qid[ef - 1]) : KEY_NONE;
-        // a distance above f32::MAX (an L2 sum that overflowed to +inf) never enters `candidates`: insert's and merge's
-        // partition point lies past the f32::MAX fill of the empty slots (priority_queue.rs:102-107, 132-135); the
-        // visit_queue still holds it (lib.rs:211-220), so it goes to the spill list like an entry past a full queue
-        const bool ins = fresh && key < tailkey && myd <= PH_FMAX;
-        const uint64_t im = __ballot(ins);
-        uint32_t pos = 0, pos_min = 0xFFFFFFFFu, newpos = 0xFFFFFFFFu;
-        // merge()'s return value (priority_queue.rs:109-144), closed form for a sorted,
-        // duplicate-free batch e_0 < e_1 < ...: the first element decides.  It is inserted
-        // (true) unless it ranks past a full queue; then Err(i>=cap) => break => false,
-        // except when its priority ties the queue's tail (Ok branch returns cap, false) and
-        // a second element follows (Err(0) on the empty slice => true without writing).
-        // e_0 enters the queue exactly when some element does (im != 0); otherwise every distance is
-        // >= the tail's, so e_0 ties the tail exactly when some element's distance equals it.
-        bool did = im != 0;
-        if (!im && m >= 2) did = __ballot(fresh && myd == dtail) != 0;
-        if (im) {
-          // One pass handles two 64-entry chunks of the queue, TOP chunks first.  For every entering key k_j (a
-          // scalar loop over the bits of `im`) the pass counts, per queue slot, the entering keys below it (the
-          // distance the slot's entry moves up: into its own chunk or the one above, both already in registers
-          // or already rewritten -- a wave's LDS reads and writes execute in program order) and, per entering
-          // key, the processed slots holding a greater key (s_bcnt1 of the same compare mask), which gives its
-          // insertion point without a search.  The first pass also ranks the entering keys among themselves.
-          // The passes stop at the first chunk whose head is below every entering key: everything under it
-          // stays where it is and is neither read nor rewritten.  What falls past `ef` is spilled.
-          uint32_t rank = 0, greater = 0;
-          bool first_pass = true;
-          const int c_top = (int)((qlen - 1u) >> 6);
-          int c = c_top, c_low;
-          for (;;) {
-            const bool two = c > 0;  // chunk c-1 belongs to this pass (it is a full chunk)
-            const uint32_t i1 = lane + 64u * (uint32_t)c, i0 = i1 - 64u;
-            const bool has1 = i1 < qlen;
-            const uint32_t qi1 = has1 ? Qid[i1] : PH_EMPTY32;
-            const float qd1 = has1 ? Qd[i1] : PH_FMAX;
-            const uint64_t qk1 = has1 ? mkkey(qd1, qi1) : KEY_NONE;
-            uint32_t qi0 = PH_EMPTY32;
-            float qd0 = PH_FMAX;
-            if (two) {
-              qi0 = Qid[i0];
-              qd0 = Qd[i0];
-            }
-            const uint64_t qk0 = two ? mkkey(qd0, qi0) : KEY_NONE;
-            uint32_t qs1 = 0, qs0 = 0;
-            if constexpr (INSTR) {
-              qs1 = has1 ? Qs[i1] : 0u;
-              qs0 = two ? Qs[i0] : 0u;
-            }
-            uint32_t sh1 = 0, sh0 = 0;
-            uint64_t rem = im;
-            if (first_pass) {
-              while (rem) {
-                const int j = __builtin_ctzll(rem);
-                rem &= rem - 1;
-                const uint64_t kj = rl64(key, j);
-                rank += (kj < key) ? 1u : 0u;
-                const bool g1 = kj < qk1, g0 = two && kj < qk0;
-                sh1 += g1 ? 1u : 0u;
-                sh0 += g0 ? 1u : 0u;
-                const uint32_t g = (uint32_t)__popcll(__ballot(g1)) + (uint32_t)__popcll(__ballot(g0));
-                greater += lane == (uint32_t)j ? g : 0u;
-              }
-              first_pass = false;
-            } else {
-              while (rem) {
-                const int j = __builtin_ctzll(rem);
-                rem &= rem - 1;
-                const uint64_t kj = rl64(key, j);
-                const bool g1 = kj < qk1, g0 = two && kj < qk0;
-                sh1 += g1 ? 1u : 0u;
-                sh0 += g0 ? 1u : 0u;
-                const uint32_t g = (uint32_t)__popcll(__ballot(g1)) + (uint32_t)__popcll(__ballot(g0));
-                greater += lane == (uint32_t)j ? g : 0u;
-              }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // both chunks are in registers before either is overwritten
-            if constexpr (BIG) wait_vm0();
-            const uint32_t np1 = i1 + sh1, np0 = i0 + sh0;
-            if (has1 && np1 < ef) {
-              Qid[np1] = qi1;
-              Qd[np1] = qd1;
-              if constexpr (INSTR) Qs[np1] = qs1;
-            }
-            if (two && np0 < ef) {
-              Qid[np0] = qi0;
-              Qd[np0] = qd0;
-              if constexpr (INSTR) Qs[np0] = qs0;
-            }
-            if (qlen + 64u > ef) {  // only a queue within 64 entries of its capacity can push anything out
-              const bool spill1 = has1 && np1 >= ef;
-              const uint64_t sm1 = __ballot(spill1);
-              if (sm1) {
-                const uint32_t at = ovf_n + __popcll(sm1 & lt);
-                if (spill1 && at < ovf_cap) ovf[at] = make_uint2(qi1, __float_as_uint(qd1));
-                if constexpr (INSTR)
-                  if (spill1 && at < ovf_cap) ovf_s[at] = qs1;
-                ovf_n += __popcll(sm1);
-              }
-              const bool spill0 = two && np0 >= ef;
-              const uint64_t sm0 = __ballot(spill0);
-              if (sm0) {
-                const uint32_t at = ovf_n + __popcll(sm0 & lt);
-                if (spill0 && at < ovf_cap) ovf[at] = make_uint2(qi0, __float_as_uint(qd0));
-                if constexpr (INSTR)
-                  if (spill0 && at < ovf_cap) ovf_s[at] = qs0;
-                ovf_n += __popcll(sm0);
-              }
-            }
-            c_low = two ? c - 1 : c;
-            // the head of the lowest chunk done (its lane 0) is below every entering key: so is all the rest
-            if (c_low == 0 || rl32(two ? sh0 : sh1, 0) == 0u) break;
-            c -= 2;
-          }
-          // slots of the chunks done (the empty ones of the top chunk count as greater) + all of the chunks below
-          pos = 64u * (uint32_t)(c_top + 1) - greater;
-          if (ins) newpos = pos + rank;
-          pos_min = rl32(pos, __builtin_ctzll(__ballot(ins && rank == 0u)));  // the smallest entering key's
-          PH_TICK(5)
-          queue_sync<BIG>();
-          PH_TICK(6)
-        }
-        {
-          if (fresh && newpos < ef) {
-            Qid[newpos] = nb;
-            Qd[newpos] = myd;
-            if constexpr (INSTR) Qs[newpos] = my_s;
-          }
-          bool spill = fresh && newpos >= ef;
-          uint64_t sm = __ballot(spill);
-          if (sm) {
-            uint32_t at = ovf_n + __popcll(sm & lt);
-            if (spill && at < ovf_cap) ovf[at] = make_uint2(nb, __float_as_uint(myd));
-            if constexpr (INSTR)
-              if (spill && at < ovf_cap) ovf_s[at] = my_s;
-            ovf_n += __popcll(sm);
-          }
-          if constexpr (INSTR)  // current_best != candidates.first(): a new entry took slot 0  lib.rs:225-231
-            if (__ballot(fresh && newpos == 0u)) highest = cur_s;
-        }
-        qlen = min(ef, qlen + (uint32_t)__popcll(im));  // every entering element of a queue that is not full; a full one stays full
-        scan_from = min(pop >= 0 ? (uint32_t)pop + 1u : scan_from, pos_min);
-        queue_sync<BIG>();
-        PH_TICK(4)
-        if (ovf_n > ovf_cap) {
-          err = ST_OVERFLOW;
-          break;
-        }
-        if (!did) {  // lib.rs:233-238
-          pd -= 1;
-          if (pd == 0) break;
-        }
-      }
-      if (err != ST_OK) break;
-      if constexpr (INSTR) index_distance = highest;  // last_index_distance = index_distance  search.rs:135
-#ifdef PH_CELL_PROBE
-      if (probing && lane == 0) {
-        for (int k = 0; k < 11; k++) atomicAdd(&a.probe_out[k], (unsigned long long)probe_cnt[k]);
-        atomicAdd(&a.probe_out[11], 1ull);
-      }
-#endif
-#ifdef PH_HOP_PROFILE
-      if (lane == 0 && q == 0)
-        printf("hop profile q0 layer %u%s: hops %u evals %u | us: pop %.1f nbr %.1f visited %.1f dist %.1f merge %.1f (+ search/rank %.1f, shift %.1f)\n", li,
-               tl ? " (dense)" : "", n_hops - hops_before, n_dist - dist_before, tprof[0] * 0.01, tprof[1] * 0.01, tprof[2] * 0.01,
-               tprof[3] * 0.01, tprof[4] * 0.01, tprof[5] * 0.01, tprof[6] * 0.01);
-#endif
-
-#ifdef PH_VISITED_PROBE
-      if (!tl && lane == 0) {  // every visited id is in the queue or the spill list
-        const uint32_t k = li == last_layer ? 1u : 0u;
-        atomicAdd(&a.vprobe_out[k * 64u + min((qlen + ovf_n) >> 6, 63u)], 1ull);
-        if (!hv && hslots) atomicAdd(&a.vprobe_out[128u + k], 1ull);
-      }
-#endif
-      // ---- clear this layer's visited set (queue + spill hold every evaluated node)
-      if (tl) {
-        for (uint32_t i = lane; i < tiny_words; i += 64) Vl[i] = 0u;
-      } else if (hv) {
-        for (uint32_t i = lane; i < hslots; i += 64) H[i] = PH_EMPTY32;
-      } else {
-#pragma unroll
-        for (int c = 0; c < (BIG ? (int)((qlen + 63u) >> 6) : CAPC); c++) {
-          uint32_t i = lane + 64u * c;
-          if (i < qlen) vis[(Qid[i] & IDM) >> 5] = 0u;
-        }
-        if (ovf_n) {
-          wait_vm0();
-          for (uint32_t i = lane; i < ovf_n; i += 64) {
-            uint32_t id = __hip_atomic_load(&ovf[i].x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & IDM;
-            vis[id >> 5] = 0u;
-          }
-        }
-      }
-      wait_vm0();
-      hv = hslots && !tl;
-      hn = 0;
-      if (a.knn_mode != 2) break;
-      thr_last = Qd[qlen - 1];  // pq.last().1  lib.rs:948
-      if (thr_last < a.threshold && qlen == ef) {  // pq.resize_capacity(capacity * 2)  lib.rs:949-951
-        if (ef * 2 > (BIG ? a.cap_max : (uint32_t)CAP)) {
-          err = ST_CAPACITY;
-          break;
-        }
-        ef *= 2;
-      }
-      }  // closest_nodes call loop
-      if (err != ST_OK) break;
-
-      if constexpr (BIG) {
-        // the knn modes start from no running candidates, so closest_vectors' tail (lib.rs:268-276) followed by
-        // candidates.merge_pairs (search.rs:136) is the queue itself: it goes straight to the output row, of which
-        // the caller reads out_stride entries at most
-        const uint32_t os = a.out_stride ? a.out_stride : a.ef;
-        uint32_t kept = 0;
-        for (uint32_t base = 0; base < qlen && kept < os; base += 64) {
-          const uint32_t i = base + lane;
-          const bool has = i < qlen;
-          const uint32_t nid = has ? (Qid[i] & IDM) : 0u;
-          const uint32_t v = has ? (identity ? nid : L.nodes[nid]) : PH_EMPTY32;
-          const bool keep = has && v != excl;
-          const uint64_t km = __ballot(keep);
-          const uint32_t at = kept + __popcll(km & lt);
-          if (keep && at < os) {
-            a.out_ids[(uint64_t)q * os + at] = v;
-            a.out_d[(uint64_t)q * os + at] = Qd[i];
-          }
-          kept += __popcll(km);
-        }
-        clen = min(kept, os);
-        for (uint32_t i = clen + lane; i < os; i += 64) {
-          a.out_ids[(uint64_t)q * os + i] = PH_EMPTY32;
-          a.out_d[(uint64_t)q * os + i] = PH_FMAX;
-        }
-        big_written = true;
-        continue;
-      }
-      // ---- closest_vectors tail: NodeId -> VectorId, filter(include), take(count)  lib.rs:268-276
-      const uint32_t candidate_count = (a.n_layers == 1 || li == last_layer) ? ef : a.upper;  // search.rs:122-126
-      uint32_t bv[CAPC];
-      float bd[CAPC];
-      uint32_t bpos[CAPC];
-      uint32_t kept = 0;
-#pragma unroll
-      for (int c = 0; c < CAPC; c++) {
-        uint32_t i = lane + 64u * c;
-        bool has = i < qlen;
-        uint32_t nid = has ? (Qid[i] & IDM) : 0u;
-        bd[c] = has ? Qd[i] : PH_FMAX;
-        bv[c] = has ? (identity ? nid : L.nodes[nid]) : PH_EMPTY32;
-        bool keep = has && bv[c] != excl;
-        uint64_t km = __ballot(keep);
-        uint32_t at = kept + __popcll(km & lt);
-        bpos[c] = (keep && at < candidate_count) ? at : PH_EMPTY32;
-        kept += __popcll(km);
-      }
-      const uint32_t blen = min(kept, candidate_count);
-      queue_sync<BIG>();
-#pragma unroll
-      for (int c = 0; c < CAPC; c++) {
-        if (bpos[c] != PH_EMPTY32) {
-          Qid[bpos[c]] = bv[c];
-          Qd[bpos[c]] = bd[c];
-        }
-      }
-      queue_sync<BIG>();
-
-      // ---- candidates.merge_pairs(&closest)  search.rs:136 : sorted set union, cap ef.
-      // An element present in both lists (same id => same distance) is kept once.
-      uint32_t ci[CAPC];
-      float cd[CAPC];
-      uint32_t cpos[CAPC];
-      uint32_t dups = 0;
-#pragma unroll
-      for (int c = 0; c < CAPC; c++) {
-        uint32_t i = lane + 64u * c;
-        bool has = i < clen;
-        ci[c] = has ? Cid[i] : PH_EMPTY32;
-        cd[c] = has ? Cd[i] : PH_FMAX;
-        bool dup = false;
-        uint32_t lb = 0;
-        if (has) {
-          uint64_t k = mkkey(cd[c], ci[c]);
-          lb = lds_lower_bound(Qid, Qd, blen, k);
-          dup = lb < blen && mkkey(Qd[lb], Qid[lb]) == k;
-        }
-        uint64_t dm = __ballot(dup);
-        uint32_t pre = dups + __popcll(dm & lt);  // duplicates among C[0..i)
-        S[i] = pre;
-        cpos[c] = (has && !dup) ? (i - pre) + lb : PH_EMPTY32;
-        dups += __popcll(dm);
-      }
-      if (lane == 0) S[CAP] = dups;
-      queue_sync<BIG>();
-#pragma unroll
-      for (int c = 0; c < CAPC; c++) {
-        uint32_t j = lane + 64u * c;
-        bool has = j < blen;
-        bv[c] = has ? Qid[j] : PH_EMPTY32;
-        bd[c] = has ? Qd[j] : PH_FMAX;
-        bpos[c] = PH_EMPTY32;
-        if (has) {
-          uint32_t la = lds_lower_bound(Cid, Cd, clen, mkkey(bd[c], bv[c]));
-          uint32_t dupb = la < clen ? S[la] : S[CAP];  // S[clen] when la == clen
-          if (la == clen) dupb = dups;
-          bpos[c] = j + (la - dupb);
-        }
-      }
-      queue_sync<BIG>();
-#pragma unroll
-      for (int c = 0; c < CAPC; c++) {
-        if (cpos[c] < ef) {
-          Cid[cpos[c]] = ci[c];
-          Cd[cpos[c]] = cd[c];
-        }
-        if (bpos[c] < ef) {
-          Cid[bpos[c]] = bv[c];
-          Cd[bpos[c]] = bd[c];
-        }
-      }
-      clen = min(ef, clen - dups + blen);
-      queue_sync<BIG>();
-    }
-
-    if (err != ST_OK) {
-      // leave the slot clean for the next query: wipe the whole bitmap (rare path; a dense-only launch has none)
-      if (!DENSE_ONLY)
-        for (uint64_t w = lane; w < a.visited_words; w += 64) vis[w] = 0u;
-      for (uint32_t i = lane; i < hslots; i += 64) H[i] = PH_EMPTY32;
-      wait_vm0();
-      clen = 0;
-    }
-    // (candidates.iter().collect(), ..)  search.rs:139
-    const uint32_t ostride = a.out_stride ? a.out_stride : a.ef;
-    for (uint32_t i = lane; i < ostride && !big_written; i += 64) {
-      a.out_ids[(uint64_t)q * ostride + i] = i < clen ? Cid[i] : PH_EMPTY32;
-      a.out_d[(uint64_t)q * ostride + i] = i < clen ? Cd[i] : PH_FMAX;
-    }
-    if (a.out_hit) {
-      // res.iter().any(|v| v == *vid)  lib.rs:1492
-      // hit_eps > 0: match_within_epsilon (search.rs:173-187): only the leading results with
-      // |d| < eps count
-      uint32_t cut = clen;
-      if (a.hit_eps > 0.f) {
-#pragma unroll
-        for (int c = 0; c < CAPC; c++) {
-          uint32_t i = lane + 64u * c;
-          bool far = i < clen && !(fabsf(Cd[i]) < a.hit_eps);
-          uint64_t fmk = __ballot(far);
-          if (fmk && cut == clen) cut = 64u * c + __builtin_ctzll(fmk);
-        }
-      }
-      bool hit = false;
-#pragma unroll
-      for (int c = 0; c < CAPC; c++) {
-        uint32_t i = lane + 64u * c;
-        hit |= (i < cut && Cid[i] == qvec);
-      }
-      uint64_t hm = __ballot(hit);
-      if (lane == 0) a.out_hit[q] = hm ? 1u : 0u;
-    }
-    if (a.out_key && lane == 0) {
-      // where the query landed: the cell (or node) of its best candidate in the last layer done
-      uint32_t key = PH_EMPTY32;
-      if (clen) {
-        const PhLayerDev KL = a.layers[layer_hi - 1];
-        uint32_t nid = KL.vec2node ? KL.vec2node[Cid[0]] : Cid[0];
-        if (nid < KL.n_nodes) key = a.key_pos ? a.key_pos[nid] : nid;
-      }
-      a.out_key[q] = key;
-    }
-    if (lane == 0 && a.totals) {
-      atomicAdd(&a.totals[0], (unsigned long long)(n_dist - n_dist0));
-      atomicAdd(&a.totals[1], (unsigned long long)(n_hops - n_hops0));
-    }
-    if (lane == 0 && a.launch_totals) {
-      atomicAdd(&a.launch_totals[0], (unsigned long long)(n_dist - n_dist0));
-      atomicAdd(&a.launch_totals[1], (unsigned long long)(n_hops - n_hops0));
-      if (a.launch_tab && n_tab) atomicAdd(a.launch_tab, (unsigned long long)n_tab);
-    }
-    if constexpr (INSTR)
-      if (lane == 0) a.out_index[q] = index_distance;
-    if (lane == 0) {
-      a.out_len[q] = clen;
-      a.status[q] = err;
-      if (a.out_stats) {
-        a.out_stats[2 * (uint64_t)q] = n_dist;
-        a.out_stats[2 * (uint64_t)q + 1] = n_hops;
-      }
-    }
-    queue_sync<BIG>();
-  }
-}
-
-template <int CAPC, class Dist>
-__global__ __launch_bounds__(64) void ph_search_kernel(PhSearchArgs a) {
-  ph_search_body<CAPC, Dist>(a);
-}
-
-// The dense top layers in a launch of their own: no distance policy state, so half the registers and (queues of
-// ef <= 256 in 256 slots) half the LDS of the full kernel -- twice the resident waves on a walk that is pure
-// latency and instruction issue.  The running candidates are parked in the output rows for the follow-up launch.
-template <int CAPC>
-__global__ __launch_bounds__(64) void ph_search_kernel_dense(PhSearchArgs a) {
-  ph_search_body<CAPC, DistNone>(a);
-}
-
-// Small batches leave most of the chip idle and finish with their slowest query: their kernels keep up to 24
-// rows in flight per wave (one load round per hop instead of up to twelve) at one wave per SIMD.  Same
-// arithmetic per row, so the same results.
-template <int CAPC, int NV>
-__global__ __launch_bounds__(64, 1) void ph_search_kernel_lat(PhSearchArgs a) {
-  ph_search_body<CAPC, DistF32<NV, 0>>(a);
-}
-
-// Hnsw::search_instrumented: the same body carrying index sums (f32 stores; queues of 512 or 1024 slots)
-template <int CAPC, int NV>
-__global__ __launch_bounds__(64) void ph_search_kernel_instr(PhSearchArgs a) {
-  ph_search_body<CAPC, DistF32<NV>, true>(a);
-}
-
-// Hnsw::threshold_nn past the LDS queues: the BIG body (queue in global memory, capacity a.cap_max)
-template <class Dist>
-__global__ __launch_bounds__(64) void ph_search_kernel_big(PhSearchArgs a) {
-  ph_search_body<2, Dist, false, true>(a);
-}
-
-// the register-table policy keeps a whole lookup table in VGPRs: two waves per SIMD is its register budget
-template <int CAPC, int M>
-__global__ __launch_bounds__(64, 2) void ph_search_kernel_pqr(PhSearchArgs a) {
-  ph_search_body<CAPC, DistPQR<M>>(a);
-}
+#include "search_kernels.h"
 
 // ------------------------------------------------------------------ host side
-
-typedef void (*ph_search_fn)(PhSearchArgs);
 
 static int pick_capc(uint32_t ef) { return ef <= 128 ? 2 : (ef <= 512 ? 8 : (ef <= 1024 ? 16 : 0)); }
 
@@ -975,34 +61,6 @@ static int pick_pqr(const phnsw_store *s, int capc) {
   const uint32_t m = s->pq_m;
   return (s->pq_ksub == 256 && (m == 32 || m == 64 || m == 96 || m == 128)) ? (int)m : 0;
 }
-static ph_search_fn pick_kernel_pqr(int capc, int m) {
-#define PH_KR(C, M) \
-  if (capc == C && m == M) return (ph_search_fn)ph_search_kernel_pqr<C, M>;
-  PH_KR(2, 32) PH_KR(2, 64) PH_KR(2, 96) PH_KR(2, 128)
-  PH_KR(8, 32) PH_KR(8, 64) PH_KR(8, 96) PH_KR(8, 128)
-#undef PH_KR
-  return nullptr;
-}
-
-// shared-codebook PQ stores (u16 codes): the query layout is DistF32's, the candidate rows come through the codes
-static ph_search_fn pick_kernel_pqs(int capc, int nv) {
-#define PH_KS(C, N) \
-  if (capc == C && nv == N) return (ph_search_fn)ph_search_kernel<C, DistPQS<N>>;
-  PH_KS(2, 1) PH_KS(2, 3) PH_KS(2, 6) PH_KS(8, 1) PH_KS(8, 3) PH_KS(8, 6) PH_KS(16, 1) PH_KS(16, 3) PH_KS(16, 6)
-#undef PH_KS
-  return nullptr;
-}
-
-static ph_search_fn pick_kernel_dense(int capc) {
-  switch (capc) {
-    case 2: return (ph_search_fn)ph_search_kernel_dense<2>;
-    case 4: return (ph_search_fn)ph_search_kernel_dense<4>;
-    case 8: return (ph_search_fn)ph_search_kernel_dense<8>;
-    case 16: return (ph_search_fn)ph_search_kernel_dense<16>;
-  }
-  return nullptr;
-}
-
 static ph_search_fn pick_kernel_instr(int capc, int nv) {
 #define PH_KI(C, N) \
   if (capc == C && nv == N) return (ph_search_fn)ph_search_kernel_instr<C, N>;
@@ -1012,42 +70,6 @@ static ph_search_fn pick_kernel_instr(int capc, int nv) {
 }
 
 #define PH_LATENCY_MAX 1024u  // batches up to this many queries run the latency kernels (PHNSW_NO_LAT=1: never)
-static ph_search_fn pick_kernel_lat(int capc, int nv) {
-#define PH_KL(C, N) \
-  if (capc == C && nv == N) return (ph_search_fn)ph_search_kernel_lat<C, N>;
-  PH_KL(2, 1) PH_KL(2, 3) PH_KL(8, 1) PH_KL(8, 3)
-#undef PH_KL
-  return nullptr;
-}
-
-// The throughput kernels of a row store, D = DistF32 / DistF16 / DistI8 / DistI8Q: the same set shape for shape -- same
-// queues, same LDS visited table, same rows in flight (DistI8Q too: 16 rows in flight would cost its headline kernel a
-// wave per SIMD, 144 VGPRs against 112, profiles/i8q).  (There are no latency (U == 0), instrumented or big-queue kernels over
-// converted rows: batches of any size run these, and the calls behind the others refuse a converted store.)
-template <template <int, int> class D>
-static ph_search_fn pick_kernel_rows(int capc, int nv) {
-#define PH_K(C, N) \
-  if (capc == C && nv == N) return (ph_search_fn)ph_search_kernel<C, D<N, 4>>;
-  PH_K(2, 1) PH_K(2, 3) PH_K(2, 6)
-  // ef <= 256 at 768 dimensions (the headline): 8 rows in flight at 2 waves per SIMD, whose LDS share holds a visited
-  // table of 3 520 slots -- 1.04 M q/s against 1.01 M for 4 rows at 3 waves per SIMD with 1 792 slots
-  if (capc == 4 && nv == 3) return (ph_search_fn)ph_search_kernel<4, D<3, 8>>;
-  PH_K(4, 6)
-  PH_K(8, 1) PH_K(8, 3) PH_K(8, 6)
-  PH_K(16, 1) PH_K(16, 3) PH_K(16, 6)
-#undef PH_K
-  return nullptr;
-}
-
-// the per-sub-space PQ policy with its table in LDS or in global memory (PHNSW_PQ_TABLE)
-static ph_search_fn pick_kernel_pqt(int capc, bool global) {
-#define PH_KQ(C) \
-  if (capc == C) return global ? (ph_search_fn)ph_search_kernel<C, DistPQG> : (ph_search_fn)ph_search_kernel<C, DistPQ>;
-  PH_KQ(2) PH_KQ(8) PH_KQ(16)
-#undef PH_KQ
-  return nullptr;
-}
-
 // pq_lds: bytes behind the queues -- the PQ lookup table, or the dense-top-layer table row + visited bits
 static size_t lds_bytes(int capc, size_t pq_lds) { return (size_t)(5 * capc * 64 + 64) * 4 + pq_lds; }
 
@@ -1090,17 +112,6 @@ static uint32_t vis_table_slots(ph_search_fn fn, size_t lds, int per_cu, size_t 
 
 // Which search kernel a launch runs: THE one place that decides it.  ph_workspace_ensure sizes the workspace from
 // the choices a launch at that ef may get, ph_search_launch launches the one it got, ph_search_slots measures it.
-enum PhKernelFamily {
-  PH_KF_ROWS_F32,   // throughput kernels over f32 rows
-  PH_KF_ROWS_F16,   // ... f16 rows
-  PH_KF_ROWS_I8,    // ... i8 rows
-  PH_KF_ROWS_I8Q,   // ... i8 rows against an int8 query (integer dot products)
-  PH_KF_PQ_TABLE,   // per-sub-space PQ, the query's table in LDS or global memory
-  PH_KF_PQ_REG,     // ... the 8-bit table in registers (pqr_m sub-spaces)
-  PH_KF_PQ_SHARED,  // shared-codebook PQ
-  PH_KF_LATENCY,    // small batches over f32 rows
-  PH_KF_INSTR,      // Hnsw::search_instrumented over f32 rows
-};
 struct PhKernelChoice {
   ph_search_fn fn = nullptr;  // nullptr: no kernel for this shape
   PhKernelFamily family = PH_KF_ROWS_F32;
@@ -1118,8 +129,8 @@ static bool kf_rows(PhKernelFamily f) {
 
 // grows: threshold_nn (the queue may double, so it keeps 512 slots at ef <= 256); instr: out_index is set.  Reads
 // PHNSW_VISITED, PHNSW_PQ_TABLE and PHNSW_NO_LAT.
-static PhKernelChoice pick_search_kernel(const phnsw_store *s, uint32_t ef_max, uint32_t nv4, bool grows, uint64_t nq,
-                                         bool instr) {
+static PhKernelChoice pick_unfiltered_kernel(const phnsw_store *s, uint32_t ef_max, uint32_t nv4, bool grows, uint64_t nq,
+                                             bool instr) {
   PhKernelChoice k;
   const int capc = pick_capc(ef_max);
   k.capc = capc;
@@ -1129,23 +140,23 @@ static PhKernelChoice pick_search_kernel(const phnsw_store *s, uint32_t ef_max, 
       k.pqr_m = pick_pqr(s, capc);
       k.family = k.pqr_m ? PH_KF_PQ_REG : PH_KF_PQ_TABLE;
       if (k.pqr_m) {
-        k.fn = pick_kernel_pqr(capc, k.pqr_m);
+        k.fn = pick_kernel_pqr<false>(capc, k.pqr_m);
       } else {
-        k.fn = pick_kernel_pqt(capc, ph_pq_global_tables());
+        k.fn = pick_kernel_pqt<false>(capc, ph_pq_global_tables());
         k.pq_lds = ph_pq_global_tables() ? 0 : ph_pq_lds_bytes(s);  // (the register policy stages its table in global memory)
       }
       return k;
     case PH_ROWS_PQ_SHARED:
       k.family = PH_KF_PQ_SHARED;
       k.nv = ph_chunk_count(nv4);
-      k.fn = pick_kernel_pqs(capc, k.nv);
+      k.fn = pick_kernel_pqs<false>(capc, k.nv);
       return k;
     default: break;
   }
   k.nv = ph_chunk_count(nv4);
-  if (s->kind == PH_ROWS_F32 && !instr && nq <= PH_LATENCY_MAX && !getenv("PHNSW_NO_LAT") && pick_kernel_lat(capc, k.nv)) {
+  if (s->kind == PH_ROWS_F32 && !instr && nq <= PH_LATENCY_MAX && !getenv("PHNSW_NO_LAT") && pick_kernel_lat<false>(capc, k.nv)) {
     k.family = PH_KF_LATENCY;
-    k.fn = pick_kernel_lat(capc, k.nv);
+    k.fn = pick_kernel_lat<false>(capc, k.nv);
     k.lat_shape = true;
     return k;
   }
@@ -1153,16 +164,25 @@ static PhKernelChoice pick_search_kernel(const phnsw_store *s, uint32_t ef_max, 
     k.family = PH_KF_INSTR;
     k.capc = std::max(capc, 8);
     k.fn = pick_kernel_instr(k.capc, k.nv);
-    k.lat_shape = nq <= PH_LATENCY_MAX && !getenv("PHNSW_NO_LAT") && pick_kernel_lat(capc, k.nv);
+    k.lat_shape = nq <= PH_LATENCY_MAX && !getenv("PHNSW_NO_LAT") && pick_kernel_lat<false>(capc, k.nv);
     return k;
   }
   k.capc = pick_capc_f32(ef_max, grows, k.nv);
   switch (s->kind) {
-    case PH_ROWS_F16: k.family = PH_KF_ROWS_F16; k.fn = pick_kernel_rows<DistF16>(k.capc, k.nv); break;
-    case PH_ROWS_I8: k.family = PH_KF_ROWS_I8; k.fn = pick_kernel_rows<DistI8>(k.capc, k.nv); break;
-    case PH_ROWS_I8Q: k.family = PH_KF_ROWS_I8Q; k.fn = pick_kernel_rows<DistI8Q>(k.capc, k.nv); break;
-    default: k.family = PH_KF_ROWS_F32; k.fn = pick_kernel_rows<DistF32>(k.capc, k.nv); break;
+    case PH_ROWS_F16: k.family = PH_KF_ROWS_F16; k.fn = pick_kernel_rows<DistF16, false>(k.capc, k.nv); break;
+    case PH_ROWS_I8: k.family = PH_KF_ROWS_I8; k.fn = pick_kernel_rows<DistI8, false>(k.capc, k.nv); break;
+    case PH_ROWS_I8Q: k.family = PH_KF_ROWS_I8Q; k.fn = pick_kernel_rows<DistI8Q, false>(k.capc, k.nv); break;
+    default: k.family = PH_KF_ROWS_F32; k.fn = pick_kernel_rows<DistF32, false>(k.capc, k.nv); break;
   }
+  return k;
+}
+
+// filt: the launch carries an allow-list and runs the FILT twin of the kernel it would run without one (same family,
+// same queues, same LDS; search_filtered.hip).  Never with instr, which ph_search_launch refuses.
+static PhKernelChoice pick_search_kernel(const phnsw_store *s, uint32_t ef_max, uint32_t nv4, bool grows, uint64_t nq,
+                                         bool instr, bool filt = false) {
+  PhKernelChoice k = pick_unfiltered_kernel(s, ef_max, nv4, grows, nq, instr);
+  if (filt && k.fn) k.fn = ph_pick_filtered_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
   return k;
 }
 
@@ -1223,6 +243,8 @@ int ph_workspace_ensure(const phnsw_index *ix, PhWorkspace &ws, uint32_t ef, uin
   // the grid of every kernel a launch at this ef may pick: threshold_nn keeps queues of 512 at ef <= 256.  The
   // throughput kernel of a large batch stands for the latency and instrumented kernels of the same ef, which hold
   // fewer waves (one per SIMD; wider queues), and for a launch over rows, whose dense-layer LDS only lowers the count.
+  // It stands for its FILT twin too, whatever that twin's own occupancy: ph_search_launch never launches more waves
+  // than the slots sized here (its grid is min(ph_search_slots of the kernel it runs, ws.n_slots)).
   uint32_t slots = 0;
   PhKernelFamily family = PH_KF_ROWS_F32;
   for (bool grows : {false, true}) {
@@ -1298,7 +320,7 @@ static hipError_t grow_buf(T **p, size_t *have, size_t need) {
 // the dense-only launch of a descent (PhSearchArgs::dense_only): its own kernel, grid and spill lists
 static int search_launch_dense(PhWorkspace &ws, PhSearchArgs &a, hipStream_t stream) {
   const int capc = pick_capc_dense(a.ef);
-  ph_search_fn fn = pick_kernel_dense(capc);
+  ph_search_fn fn = a.filter ? ph_pick_filtered_dense(capc) : pick_kernel_dense<false>(capc);
   if (!fn) {
     ph_set_error("unsupported search shape: ef=%u", a.ef);
     return PHNSW_E_UNSUPPORTED;
@@ -1377,7 +399,11 @@ int ph_search_launch(const phnsw_index *ix, PhWorkspace &ws, PhSearchArgs &a, hi
     ph_set_error("search_instrumented: f32 stores only");
     return PHNSW_E_UNSUPPORTED;
   }
-  PhKernelChoice k = pick_search_kernel(st, ef_max, a.dist.nv4, a.knn_mode == 2, a.nq, a.out_index != nullptr);
+  if (a.filter && (a.knn_mode || a.out_index)) {  // only the plain searches have filtered kernels
+    ph_set_error("knn / threshold_nn / search_instrumented take no filter");
+    return PHNSW_E_UNSUPPORTED;
+  }
+  PhKernelChoice k = pick_search_kernel(st, ef_max, a.dist.nv4, a.knn_mode == 2, a.nq, a.out_index != nullptr, a.filter != nullptr);
   a.pq_tables = ws.pq_tables;
   a.pq_table_bytes = (uint32_t)ph_pq_lds_bytes(st);
   // one wave per SIMD leaves each wave a quarter of the CU's LDS: room for the table row of a far larger table layer

@@ -37,6 +37,32 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+FILTER_STRICT = 1  # PHNSW_FILTER_STRICT
+
+
+def pack_allow(allow, n, nq):
+    """the allow-list of a filtered search as phnsw.h wants it -> (u32 words or None, filter_stride_words): bit v % 32 of
+    word v // 32 set = VectorId v may be returned.  A bool array [n] is one bitmap for all queries (stride 0), [nq, n] one
+    per query (stride ceil(n/32)); u32 arrays are taken as already packed ([>= ceil(n/32)] or [nq, stride])"""
+    if allow is None:
+        return None, 0
+    a = np.asarray(allow)
+    nw = (int(n) + 31) // 32
+    if a.dtype == np.bool_:
+        if a.ndim not in (1, 2) or a.shape[-1] != n or (a.ndim == 2 and a.shape[0] != nq):
+            raise ValueError("allow: a bool array of shape [n] or [nq, n] (n = %d, nq = %d), got %r" % (n, nq, a.shape))
+        rows = np.zeros((a.shape[0] if a.ndim == 2 else 1, nw * 32), dtype=np.bool_)  # bits at or past n stay clear
+        rows[:, :n] = a
+        words = np.ascontiguousarray(np.packbits(rows, axis=1, bitorder="little")).view("<u4")
+        return (words, nw) if a.ndim == 2 else (words.reshape(-1), 0)
+    if a.dtype != np.uint32:
+        raise TypeError("allow: a bool mask or packed uint32 words, got %s" % a.dtype)
+    if a.ndim not in (1, 2) or a.shape[-1] < nw or (a.ndim == 2 and a.shape[0] != nq):
+        raise ValueError("allow: packed words of shape [>= %d] or [%d, >= %d], got %r" % (nw, nq, nw, a.shape))
+    a = np.ascontiguousarray(a)
+    return (a, a.shape[1]) if a.ndim == 2 else (a, 0)
+
+
 def SearchParameters(number_of_candidates=300, upper_layer_candidate_count=300, probe_depth=2):
     return SearchParams(number_of_candidates, upper_layer_candidate_count, probe_depth)
 
@@ -608,6 +634,54 @@ class Hnsw:
             check(lib().phnsw_search_batch_stored(self._h, _p(qi), nq, C.byref(sp), upto, _p(ex), _p(ids), _p(d),
                                                   _p(ln), _p(st)))
         return (ids, d, ln, st) if stats else (ids, d, ln)
+
+    def search_batch_filtered(self, queries=None, qids=None, sp=None, allow=None, strict=False, exclude=None, upto=0,
+                              stats=False, k=None):
+        """search_batch restricted to allowed VectorIds (phnsw_search_batch_filtered): closest_vectors' `include`
+        (lib.rs:250-277) as a bitmap.  allow: a bool array [n] (one filter for all queries) or [nq, n] (one per query), or
+        the packed u32 words themselves ([ceil(n/32)] or [nq, stride]); None = the default of set_filter, else no
+        filter.  A post-filter on each layer's queue: about density * number_of_candidates results come back, so
+        selective filters want a larger number_of_candidates.  The entry vector may be returned although it is
+        disallowed (as the reference returns it although excluded); strict=True removes it.
+        Returns (ids[nq, k or ef] u64, d f32, len[nq]) and the stats with stats=True"""
+        sp = sp or SearchParameters()
+        ef = sp.number_of_candidates
+        q = qi = None
+        if queries is not None:
+            q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+            assert q.shape[1] == self.store.dim
+            nq = q.shape[0]
+        else:
+            qi = np.ascontiguousarray(qids, dtype=np.uint64)
+            nq = len(qi)
+        words, stride = pack_allow(allow, self.store.n, nq)
+        w = ef if k is None else int(k)
+        ids = np.empty((nq, w), dtype=np.uint64)
+        d = np.empty((nq, w), dtype=np.float32)
+        ln = np.zeros(nq, dtype=np.uint64)
+        st = np.zeros((nq, 2), dtype=np.uint64) if stats else None
+        ex = None if exclude is None else np.ascontiguousarray(exclude, dtype=np.uint64)
+        check(lib().phnsw_search_batch_filtered(self._h, _p(q), _p(qi), nq, C.byref(sp), upto, _p(ex), _p(words), stride,
+                                                FILTER_STRICT if strict else 0, 0 if k is None else w, _p(ids), _p(d),
+                                                _p(ln), _p(st)))
+        return (ids, d, ln, st) if stats else (ids, d, ln)
+
+    def search_batch_filtered_device(self, nq, sp, out_ids, out_d, out_len, status, queries=0, ldq=0, qids=0, exclude=0,
+                                     allow=0, allow_stride=0, strict=False, out_stats=0, upto=0, stream=0):
+        """zero-copy form (phnsw_search_batch_filtered_device): search_batch_device with `allow`, a device pointer to
+        the packed words -- one bitmap (allow_stride 0) or nq bitmaps allow_stride words apart; 0 = the default of
+        set_filter"""
+        check(lib().phnsw_search_batch_filtered_device(
+            self._h, C.c_void_p(queries or None), ldq, C.c_void_p(qids or None), nq, C.byref(sp), upto,
+            C.c_void_p(exclude or None), C.c_void_p(allow or None), int(allow_stride), FILTER_STRICT if strict else 0,
+            C.c_void_p(out_ids), C.c_void_p(out_d), C.c_void_p(out_len), C.c_void_p(out_stats or None), C.c_void_p(status),
+            C.c_void_p(stream or None)))
+
+    def set_filter(self, allow_dev=0):
+        """tombstones (phnsw_index_set_filter_device): a device pointer to one packed bitmap of ceil(n/32) words, kept
+        alive by the caller, becomes the filter of every filtered call that passes none; 0 clears it.  search_batch and
+        the other unfiltered calls never see it.  Not while searches on the index are in flight"""
+        check(lib().phnsw_index_set_filter_device(self._h, C.c_void_p(allow_dev or None)))
 
     def search_batch_reranked(self, full, queries, sp=None, k=10):
         """an index over an F16Store, I8Store or I8QStore: search it, recompute every result's distance on the f32 store

@@ -363,6 +363,69 @@ impl GpuHnsw {
         (0..nq).map(|i| (0..len[i] as usize).map(|j| (VectorId(ids[i * k + j] as usize), d[i * k + j])).collect()).collect()
     }
 
+    /// `search_many_topk` restricted to the VectorIds `include` accepts: `Layer::closest_vectors`' closure
+    /// (lib.rs:250-277) evaluated once per id into an allow bitmap shared by the batch (`phnsw_search_batch_filtered`).
+    /// A post-filter on each layer's queue: expect about density * number_of_candidates results.  The entry vector can
+    /// come back although `include` rejects it, as in the reference; `strict` removes it.  `k` 0 = all
+    /// `number_of_candidates` entries of a row; panics on `k > number_of_candidates`
+    pub fn search_many_filtered<F: Fn(VectorId) -> bool>(&self, queries: &[Vec<f32>], sp: SearchParameters, k: usize,
+                                                         include: F, strict: bool) -> Vec<Vec<(VectorId, f32)>> {
+        let nq = queries.len();
+        // the C call reads k 0 as "the whole row": the buffers below are sized by the k it will write
+        let k = if k == 0 { sp.number_of_candidates } else { k };
+        assert!(k <= sp.number_of_candidates, "search_many_filtered: k exceeds number_of_candidates");
+        let psp = sp_c(sp);
+        let mut n64 = 0u64;
+        check(unsafe {
+            sys::phnsw_store_info(self.comparator.store.0, &mut n64, std::ptr::null_mut(), std::ptr::null_mut(),
+                                  std::ptr::null_mut(), std::ptr::null_mut())
+        });
+        let n = n64 as usize; // the bitmap covers every VectorId of the store
+        let mut words = vec![0u32; (n + 31) / 32];
+        for v in 0..n {
+            if include(VectorId(v)) {
+                words[v >> 5] |= 1u32 << (v & 31);
+            }
+        }
+        let mut q: Vec<f32> = Vec::with_capacity(nq * queries.first().map_or(0, |x| x.len()));
+        for x in queries {
+            q.extend_from_slice(x);
+        }
+        let (mut ids, mut d, mut len) = (vec![0u64; nq * k], vec![0f32; nq * k], vec![0u64; nq]);
+        check(unsafe {
+            sys::phnsw_search_batch_filtered(self.ix, q.as_ptr(), std::ptr::null(), nq as u64, &psp, 0, std::ptr::null(),
+                                             words.as_ptr(), 0, if strict { sys::PHNSW_FILTER_STRICT } else { 0 }, k as u64,
+                                             ids.as_mut_ptr(), d.as_mut_ptr(), len.as_mut_ptr(), std::ptr::null_mut())
+        });
+        (0..nq).map(|i| (0..len[i] as usize).map(|j| (VectorId(ids[i * k + j] as usize), d[i * k + j])).collect()).collect()
+    }
+
+    /// zero-copy form (`phnsw_search_batch_filtered_device`): `filter_dev` holds one bitmap (`filter_stride_words` 0)
+    /// or one per query; null = the default set with `set_filter_device`
+    ///
+    /// # Safety
+    /// the pointers must be valid device allocations of the sizes `phnsw.h` documents for the call
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn search_filtered_device(&self, queries_dev: *const f32, ldq: u32, qids_dev: *const u32, nq: u64,
+                                         sp: SearchParameters, upto: u32, exclude_dev: *const u32, filter_dev: *const u32,
+                                         filter_stride_words: u32, strict: bool, out_ids_dev: *mut u32, out_d_dev: *mut f32,
+                                         out_len_dev: *mut u32, out_stats_dev: *mut u32, status_dev: *mut u32,
+                                         stream: *mut c_void) {
+        let psp = sp_c(sp);
+        check(sys::phnsw_search_batch_filtered_device(self.ix, queries_dev, ldq, qids_dev, nq, &psp, upto, exclude_dev, filter_dev,
+                                                      filter_stride_words, if strict { sys::PHNSW_FILTER_STRICT } else { 0 },
+                                                      out_ids_dev, out_d_dev, out_len_dev, out_stats_dev, status_dev, stream));
+    }
+
+    /// tombstones (`phnsw_index_set_filter_device`): a shared device bitmap the caller keeps alive becomes the filter
+    /// of every filtered call that passes none; null clears it.  Not while searches are in flight
+    ///
+    /// # Safety
+    /// `filter_dev` must stay a valid device allocation of ceil(n / 32) words until it is cleared
+    pub unsafe fn set_filter_device(&mut self, filter_dev: *const u32) {
+        check(sys::phnsw_index_set_filter_device(self.ix, filter_dev));
+    }
+
     /// an index over a `to_f16()` comparator: search it, recompute every result's distance on the f32 comparator
     /// `full`, sort by (distance, id), keep the best `k` (`phnsw_f16_search_batch`)
     pub fn search_many_reranked(&self, full: &GpuComparator, queries: &[Vec<f32>], sp: SearchParameters, k: usize)

@@ -22,6 +22,8 @@ pub const PHNSW_E_NAN: c_int = -6;
 pub const PHNSW_E_UNSUPPORTED: c_int = -7;
 pub const PHNSW_E_NOMEM: c_int = -8;
 
+pub const PHNSW_FILTER_STRICT: u32 = 1; // also drop disallowed ids (the entry vector) from the final rows
+
 pub const PHNSW_METRIC_COSINE_HALF: c_int = 0; // (1 - dot)/2   bigvec.rs:47-53
 pub const PHNSW_METRIC_ONE_MINUS_DOT: c_int = 1; // 1 - dot       lib.rs:1985-1991
 pub const PHNSW_METRIC_L2: c_int = 2; // sqrt(sum (a-b)^2)  lib.rs:2431-2437
@@ -223,6 +225,19 @@ extern "C" {
                                      upto_layers: u32, exclude_dev: *const u32, out_ids_dev: *mut u32,
                                      out_d_dev: *mut c_float, out_len_dev: *mut u32, out_stats_dev: *mut u32,
                                      status_dev: *mut u32, stream: *mut c_void) -> c_int;
+    // searches restricted to an allow bitmap over VectorIds: closest_vectors' `include` (lib.rs:250-277)
+    pub fn phnsw_search_batch_filtered(ix: *const phnsw_index, queries: *const c_float, qids: *const u64, nq: u64,
+                                       sp: *const phnsw_search_params, upto_layers: u32, exclude: *const u64,
+                                       filter: *const u32, filter_stride_words: u32, flags: u32, k: u64,
+                                       out_ids: *mut u64, out_d: *mut c_float, out_len: *mut u64,
+                                       out_stats: *mut u64) -> c_int;
+    pub fn phnsw_search_batch_filtered_device(ix: *const phnsw_index, queries_dev: *const c_float, ldq: u32,
+                                              qids_dev: *const u32, nq: u64, sp: *const phnsw_search_params,
+                                              upto_layers: u32, exclude_dev: *const u32, filter_dev: *const u32,
+                                              filter_stride_words: u32, flags: u32, out_ids_dev: *mut u32,
+                                              out_d_dev: *mut c_float, out_len_dev: *mut u32, out_stats_dev: *mut u32,
+                                              status_dev: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn phnsw_index_set_filter_device(ix: *mut phnsw_index, filter_dev: *const u32) -> c_int;
     pub fn phnsw_index_counters(ix: *const phnsw_index, n_dist: *mut u64, n_hops: *mut u64) -> c_int;
     pub fn phnsw_last_search_kernel_ms(ix: *const phnsw_index, ms: *mut c_float) -> c_int;
     pub fn phnsw_last_search_dispatches(ix: *const phnsw_index, cap: u32, count: *mut u32, ms: *mut c_float,
