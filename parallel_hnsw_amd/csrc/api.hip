@@ -590,7 +590,7 @@ extern "C" int phnsw_index_layer_read(const phnsw_index *ix, uint32_t lft, uint6
 
 // ------------------------------------------------------------------ search
 
-static int check_sp(const phnsw_index *ix, const phnsw_search_params *sp) {
+int ph_check_sp(const phnsw_index *ix, const phnsw_search_params *sp) {
   if (!ix || !sp || ix->layers.empty()) {
     ph_set_error("search: null index/params or index without layers");
     return PHNSW_E_INVALID;
@@ -604,11 +604,12 @@ static int check_sp(const phnsw_index *ix, const phnsw_search_params *sp) {
   return 0;
 }
 
-static void fill_args(const phnsw_index *ix, const phnsw_search_params *sp, uint32_t upto, PhSearchArgs &a) {
+// the kernel argument block of a request: the index's layers and store, the search parameters, the caller's buffers
+static void fill_args(const phnsw_index *ix, const PhSearchCall &c, PhSearchArgs &a) {
   memset(&a, 0, sizeof(a));
   const phnsw_store *s = ix->store;
   a.dist = ph_dist_args(s);
-  uint32_t nl = (upto == 0 || upto > ix->layers.size()) ? (uint32_t)ix->layers.size() : upto;
+  uint32_t nl = (c.upto == 0 || c.upto > ix->layers.size()) ? (uint32_t)ix->layers.size() : c.upto;
   a.n_layers = nl;
   for (uint32_t l = 0; l < nl; l++) {
     const PhLayerHost &h = ix->layers[l];
@@ -618,9 +619,33 @@ static void fill_args(const phnsw_index *ix, const phnsw_search_params *sp, uint
     a.layers[l].neighbors = h.neighbors;
     a.layers[l].vec2node = h.identity ? nullptr : h.vec2node;
   }
-  a.ef = (uint32_t)sp->number_of_candidates;
-  a.upper = (uint32_t)std::min<uint64_t>(sp->upper_layer_candidate_count, 0xFFFFFFFFull);
-  a.probe_depth = (uint32_t)sp->probe_depth;
+  a.ef = (uint32_t)c.sp->number_of_candidates;
+  a.upper = (uint32_t)std::min<uint64_t>(c.sp->upper_layer_candidate_count, 0xFFFFFFFFull);
+  a.probe_depth = (uint32_t)c.sp->probe_depth;
+  a.queries = c.queries;
+  a.ldq = c.ldq;
+  a.qids = c.qids;
+  a.exclude = c.exclude;
+  if (c.filter.words) {
+    a.filter = c.filter.words;
+    a.filter_stride = c.filter.stride;
+    a.filter_flags = c.filter.flags;
+  }
+  a.nq = (uint32_t)c.nq;
+  a.out_ids = c.out_ids;
+  a.out_d = c.out_d;
+  a.out_len = c.out_len;
+  a.out_stats = c.out_stats;
+  a.status = c.status;
+  a.knn_mode = c.knn_mode;
+  a.out_stride = c.out_stride;
+  a.out_hit = c.out_hit;
+  a.threshold = c.threshold;
+  a.first_node = c.first_node;
+  a.hit_eps = c.hit_eps;
+  a.cap_max = c.knn_mode == 2 ? c.out_stride : 0;
+  a.out_index = c.out_index;  // Hnsw::search_instrumented: the INSTR kernels, every layer on the per-hop path, one launch
+  a.order = c.order;
 }
 
 // spill-list entries per resident wave; PHNSW_OVF_CAP (tests) forces a small list so that the
@@ -655,91 +680,12 @@ extern "C" int phnsw_stream_create_beside(int device, void *other_stream, void *
   return 0;
 } catch (...) { return ph_caught(); }
 
-// enqueue one search launch; caller owns all device buffers
-int ph_search_device(const phnsw_index *ix, const float *queries_dev, uint32_t ldq, const uint32_t *qids_dev,
-                     uint64_t nq, const phnsw_search_params *sp, uint32_t upto, const uint32_t *exclude_dev,
-                     uint32_t *out_ids, float *out_d, uint32_t *out_len, uint32_t *out_stats, uint32_t *status,
-                     uint32_t ovf_cap, uint32_t knn_mode, hipStream_t stream, uint32_t out_stride,
-                     uint32_t *out_hit, float threshold, uint32_t first_node, float hit_eps, const uint32_t *order,
-                     uint32_t *out_index, const PhRowHint *hint, const PhFilter *filter) {
-  phnsw_index *mix = const_cast<phnsw_index *>(ix);
-  if (ph_store_converted(ix->store) && (knn_mode || out_index || hint || out_hit)) {
-    // an f16 / i8 store is searched, never built over: knn / threshold_nn / search_instrumented / the build's rounds
-    return ph_search_only_unsupported(ix->store, knn_mode ? "knn / threshold_nn" : (out_index ? "search_instrumented" : "build search"));
-  }
-  PhSearchArgs a;
-  fill_args(ix, sp, upto, a);
-  a.queries = queries_dev;
-  a.ldq = ldq;
-  a.qids = qids_dev;
-  a.exclude = exclude_dev;
-  if (filter && filter->words) {
-    a.filter = filter->words;
-    a.filter_stride = filter->stride;
-    a.filter_flags = filter->flags;
-  }
-  a.nq = (uint32_t)nq;
-  a.out_ids = out_ids;
-  a.out_d = out_d;
-  a.out_len = out_len;
-  a.out_stats = out_stats;
-  a.status = status;
-  a.knn_mode = knn_mode;
-  a.out_stride = out_stride;
-  a.out_hit = out_hit;
-  a.threshold = threshold;
-  a.first_node = first_node;
-  a.hit_eps = hit_eps;
-  a.cap_max = knn_mode == 2 ? out_stride : 0;
-  a.out_index = out_index;  // Hnsw::search_instrumented: the INSTR kernels, every layer on the per-hop path, one launch
-  a.order = (ix->dbg_order && ix->dbg_order_n == nq) ? ix->dbg_order : order;
-  std::lock_guard<std::mutex> g(mix->ws_mutex);
-  if (!mix->totals) {
-    PH_HIP(hipMalloc(&mix->totals, 16));
-    PH_HIP(hipMemset(mix->totals, 0, 16));
-  }
-  a.totals = mix->totals;
-  PhWorkspace &ws = mix->ws[mix->ws_next & 1];
-  mix->ws_last = mix->ws_next & 1;
-  mix->ws_next++;
-  int rc = ph_workspace_ensure(ix, ws, std::max(a.ef, a.cap_max), ovf_cap ? ovf_cap : default_ovf_cap(a.ef));
-  if (rc) return rc;
-  // Large batches of independent queries descend in several launches: the small top layers in
-  // the caller's order, then every layer whose rows exceed one XCD's L2 in a launch of its own with
-  // the queries sorted by where they landed in the layer above (cell of the best candidate), one
-  // contiguous eighth of that order per XCD.  Same arithmetic per query, so the results are
-  // identical; neighbouring queries now share rows in L2 / the Infinity Cache.  Between launches
-  // the running candidates are parked in the output rows.
-  // (layers evaluated densely, tiny.hip, never read a vector row during the traversal: they stay in
-  // the first launch whatever their size)
-  const uint32_t T = (knn_mode || out_index) ? 0u : ph_tiny_layer_count(ix, a.n_layers, a.ef);
-  uint32_t first_big = a.n_layers;
-  for (uint32_t l = std::max(1u, T); l < a.n_layers; l++)
-    if (ph_layer_own_launch(ix->layers[l].n_nodes, ph_row_bytes(ix->store))) {
-      first_big = l;
-      break;
-    }
-  if (!a.order && knn_mode && nq >= PH_ORDER_MIN) {
-    // knn / threshold_nn: the queries are the bottom layer's nodes first_node .. first_node + nq
-    PhLayerHost &B = mix->layers[a.n_layers - 1];
-    rc = ph_layer_anchor_pos(ix->store, B);
-    if (!rc && first_node + nq <= B.n_nodes) rc = ph_layer_range_order(B, first_node, (uint32_t)nq, &a.order);
-    if (rc) return rc;
-  }
-  // (not for PQ stores: their searches are not bound by where rows come from, and every launch
-  // would build the per-query table again)
-  const bool split = (ph_store_f32(ix->store) || ph_store_converted(ix->store)) && !a.order && !knn_mode && !out_stride && !out_index && first_big < a.n_layers &&
-                     nq >= two_launch_min() &&
-                     !getenv("PHNSW_NO_LOCALITY");
-  if (split) {
-    g_two_launch_count++;
-    rc = ph_workspace_order_ensure(ws, a.nq);
-    for (uint32_t l = first_big; l < a.n_layers && !rc; l++)
-      rc = ph_layer_anchor_pos(ix->store, mix->layers[l - 1]);  // first use on a loaded index; no-op afterwards
-    if (rc) return rc;
-  }
+// the two experiment probes: each reports what the launches since the last call counted, clears
+// its counters and points the launch at them.  Without either macro this does nothing.
+static int attach_probes(phnsw_index *mix, const PhSearchCall &c, PhSearchArgs &a) {
+  (void)mix, (void)c, (void)a;
 #ifdef PH_CELL_PROBE
-  {
+  {  // DESIGN 12
     static unsigned long long *probe_dev = nullptr;
     if (!probe_dev) {
       PH_HIP(hipMalloc(&probe_dev, 12 * sizeof(unsigned long long)));
@@ -757,10 +703,10 @@ int ph_search_device(const phnsw_index *ix, const float *queries_dev, uint32_t l
     }
     a.probe_out = probe_dev;
     a.probe_pos = nullptr;
-    if (!knn_mode && ph_store_f32(ix->store) && nq >= 1000) {
-      rc = ph_layer_anchor_pos(ix->store, mix->layers[a.n_layers - 1]);
+    if (!c.knn_mode && ph_store_f32(mix->store) && c.nq >= 1000) {
+      int rc = ph_layer_anchor_pos(mix->store, mix->layers[a.n_layers - 1]);
       if (rc) return rc;
-      a.probe_pos = ix->layers[a.n_layers - 1].pos;
+      a.probe_pos = mix->layers[a.n_layers - 1].pos;
     }
   }
 #endif
@@ -791,14 +737,78 @@ int ph_search_device(const phnsw_index *ix, const float *queries_dev, uint32_t l
     a.vprobe_out = vprobe_dev;
   }
 #endif
+  return 0;
+}
+
+// enqueue one search launch; caller owns all device buffers
+int ph_search_device(const phnsw_index *ix, const PhSearchCall &c) {
+  phnsw_index *mix = const_cast<phnsw_index *>(ix);
+  const uint64_t nq = c.nq;
+  const uint32_t knn_mode = c.knn_mode, out_stride = c.out_stride;
+  uint32_t *const out_index = c.out_index;
+  const hipStream_t stream = c.stream;
+  if (ph_store_converted(ix->store) && (knn_mode || out_index || c.hint || c.out_hit)) {
+    // an f16 / i8 store is searched, never built over: knn / threshold_nn / search_instrumented / the build's rounds
+    return ph_search_only_unsupported(ix->store, knn_mode ? "knn / threshold_nn" : (out_index ? "search_instrumented" : "build search"));
+  }
+  PhSearchArgs a;
+  fill_args(ix, c, a);
+  if (ix->dbg_order && ix->dbg_order_n == nq) a.order = ix->dbg_order;
+  std::lock_guard<std::mutex> g(mix->ws_mutex);
+  if (!mix->totals) {
+    PH_HIP(hipMalloc(&mix->totals, 16));
+    PH_HIP(hipMemset(mix->totals, 0, 16));
+  }
+  a.totals = mix->totals;
+  PhWorkspace &ws = mix->ws[mix->ws_next & 1];
+  mix->ws_last = mix->ws_next & 1;
+  mix->ws_next++;
+  int rc = ph_workspace_ensure(ix, ws, std::max(a.ef, a.cap_max), c.ovf_cap ? c.ovf_cap : default_ovf_cap(a.ef));
+  if (rc) return rc;
+  // Large batches of independent queries descend in several launches: the small top layers in
+  // the caller's order, then every layer whose rows exceed one XCD's L2 in a launch of its own with
+  // the queries sorted by where they landed in the layer above (cell of the best candidate), one
+  // contiguous eighth of that order per XCD.  Same arithmetic per query, so the results are
+  // identical; neighbouring queries now share rows in L2 / the Infinity Cache.  Between launches
+  // the running candidates are parked in the output rows.
+  // (layers evaluated densely, tiny.hip, never read a vector row during the traversal: they stay in
+  // the first launch whatever their size)
+  const uint32_t T = (knn_mode || out_index) ? 0u : ph_tiny_layer_count(ix, a.n_layers, a.ef);
+  uint32_t first_big = a.n_layers;
+  for (uint32_t l = std::max(1u, T); l < a.n_layers; l++)
+    if (ph_layer_own_launch(ix->layers[l].n_nodes, ph_row_bytes(ix->store))) {
+      first_big = l;
+      break;
+    }
+  if (!a.order && knn_mode && nq >= PH_ORDER_MIN) {
+    // knn / threshold_nn: the queries are the bottom layer's nodes first_node .. first_node + nq
+    PhLayerHost &B = mix->layers[a.n_layers - 1];
+    rc = ph_layer_anchor_pos(ix->store, B);
+    if (!rc && c.first_node + nq <= B.n_nodes) rc = ph_layer_range_order(B, c.first_node, (uint32_t)nq, &a.order);
+    if (rc) return rc;
+  }
+  // (not for PQ stores: their searches are not bound by where rows come from, and every launch
+  // would build the per-query table again)
+  const bool split = (ph_store_f32(ix->store) || ph_store_converted(ix->store)) && !a.order && !knn_mode && !out_stride && !out_index && first_big < a.n_layers &&
+                     nq >= two_launch_min() &&
+                     !getenv("PHNSW_NO_LOCALITY");
+  if (split) {
+    g_two_launch_count++;
+    rc = ph_workspace_order_ensure(ws, a.nq);
+    for (uint32_t l = first_big; l < a.n_layers && !rc; l++)
+      rc = ph_layer_anchor_pos(ix->store, mix->layers[l - 1]);  // first use on a loaded index; no-op afterwards
+    if (rc) return rc;
+  }
+  rc = attach_probes(mix, c, a);
+  if (rc) return rc;
   rc = ph_search_begin(ws, stream);
   if (rc) return rc;
   // The dense top layers (tiny.hip) keep one table row per launch position; a query list longer
   // than the table may hold runs in consecutive chunks of the list (same workspace, same stream).
   // a build's searches first try the table kept across its rounds (tiny.hip): no table pass, and no chunking either
   bool kept_table = false;
-  if (hint && T && !split) {
-    rc = ph_build_table_prepare(mix, ws, a, *hint, T, stream, &kept_table);
+  if (c.hint && T && !split) {
+    rc = ph_build_table_prepare(mix, ws, a, *c.hint, T, stream, &kept_table);
     if (rc) return rc;
   }
   const uint64_t tmax = (T && !kept_table) ? ph_tiny_max_positions(ix, a.n_layers, a.ef) : 0;
@@ -812,7 +822,7 @@ int ph_search_device(const phnsw_index *ix, const float *queries_dev, uint32_t l
       b.order += c0;  // positions [c0, c0 + cnt) of the processing order; query indices stay global
     } else if (c0) {
       const uint32_t ostride = out_stride ? out_stride : b.ef;
-      if (b.queries) b.queries += c0 * ldq;
+      if (b.queries) b.queries += c0 * c.ldq;
       if (b.qids) b.qids += c0;
       if (b.exclude) b.exclude += c0;
       if (b.filter) b.filter += c0 * b.filter_stride;  // per-query bitmaps follow the chunk; a shared one (stride 0) stays
@@ -884,22 +894,44 @@ int ph_search_device(const phnsw_index *ix, const float *queries_dev, uint32_t l
   return 0;
 }
 
+// the argument test the two device entry points share; `call` names the entry point in the message
+static int check_device_call(const char *call, const phnsw_index *ix, const PhSearchCall &c) {
+  int rc = ph_check_sp(ix, c.sp);
+  if (rc) return rc;
+  if ((!c.queries && !c.qids) || !c.out_ids || !c.out_d || !c.out_len || !c.status || c.nq > 0xFFFFFFFFull ||
+      (c.queries && (c.ldq < ix->store->ld || (c.ldq % 4) || ((uintptr_t)c.queries % 16)))) {
+    ph_set_error("%s: invalid argument (queries need ldq >= store ld, multiple of 4, 16-byte base)", call);
+    return PHNSW_E_INVALID;
+  }
+  return 0;
+}
+
+// the request both device entry points make of their arguments
+static PhSearchCall device_call(const float *queries_dev, uint32_t ldq, const uint32_t *qids_dev, uint64_t nq,
+                                const phnsw_search_params *sp, uint32_t upto_layers, const uint32_t *exclude_dev,
+                                uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev, uint32_t *out_stats_dev,
+                                uint32_t *status_dev, void *stream) {
+  PhSearchCall c = {};
+  c.queries = queries_dev, c.ldq = ldq, c.qids = qids_dev, c.exclude = exclude_dev, c.nq = nq;
+  c.sp = sp, c.upto = upto_layers;
+  c.out_ids = out_ids_dev, c.out_d = out_d_dev, c.out_len = out_len_dev, c.status = status_dev;
+  c.out_stats = out_stats_dev;
+  c.stream = (hipStream_t)stream;
+  return c;
+}
+
 extern "C" int phnsw_search_batch_device(const phnsw_index *ix, const float *queries_dev, uint32_t ldq,
                                          const uint32_t *qids_dev, uint64_t nq, const phnsw_search_params *sp,
                                          uint32_t upto_layers, const uint32_t *exclude_dev, uint32_t *out_ids_dev,
                                          float *out_d_dev, uint32_t *out_len_dev, uint32_t *out_stats_dev,
                                          uint32_t *status_dev, void *stream) try {
-  int rc = check_sp(ix, sp);
+  const PhSearchCall c = device_call(queries_dev, ldq, qids_dev, nq, sp, upto_layers, exclude_dev, out_ids_dev, out_d_dev,
+                                     out_len_dev, out_stats_dev, status_dev, stream);
+  int rc = check_device_call("phnsw_search_batch_device", ix, c);
   if (rc) return rc;
-  if ((!queries_dev && !qids_dev) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev ||
-      nq > 0xFFFFFFFFull || (queries_dev && (ldq < ix->store->ld || (ldq % 4) || ((uintptr_t)queries_dev % 16)))) {
-    ph_set_error("phnsw_search_batch_device: invalid argument (queries need ldq >= store ld, multiple of 4, 16-byte base)");
-    return PHNSW_E_INVALID;
-  }
   if (nq == 0) return 0;
   PH_HIP(hipSetDevice(ix->store->device));
-  return ph_search_device(ix, queries_dev, ldq, qids_dev, nq, sp, upto_layers, exclude_dev, out_ids_dev, out_d_dev,
-                          out_len_dev, out_stats_dev, status_dev, 0, 0, (hipStream_t)stream);
+  return ph_search_device(ix, c);
 } catch (...) { return ph_caught(); }
 
 // ---- searches restricted to an allow-list of VectorIds: closest_vectors' `include` (lib.rs:250-277) as a bitmap
@@ -929,22 +961,16 @@ extern "C" int phnsw_search_batch_filtered_device(const phnsw_index *ix, const f
                                                   const uint32_t *filter_dev, uint32_t filter_stride_words, uint32_t flags,
                                                   uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
                                                   uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) try {
-  int rc = check_sp(ix, sp);
+  PhSearchCall c = device_call(queries_dev, ldq, qids_dev, nq, sp, upto_layers, exclude_dev, out_ids_dev, out_d_dev,
+                               out_len_dev, out_stats_dev, status_dev, stream);
+  int rc = check_device_call("phnsw_search_batch_filtered_device", ix, c);
   if (rc) return rc;
-  if ((!queries_dev && !qids_dev) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev ||
-      nq > 0xFFFFFFFFull || (queries_dev && (ldq < ix->store->ld || (ldq % 4) || ((uintptr_t)queries_dev % 16)))) {
-    ph_set_error("phnsw_search_batch_filtered_device: invalid argument (queries need ldq >= store ld, multiple of 4, 16-byte base)");
-    return PHNSW_E_INVALID;
-  }
-  PhFilter f;
-  rc = ph_filter_check(ix, filter_dev, filter_stride_words, flags, "phnsw_search_batch_filtered_device", &f);
+  rc = ph_filter_check(ix, filter_dev, filter_stride_words, flags, "phnsw_search_batch_filtered_device", &c.filter);
   if (rc) return rc;
-  if (!f.words) f.words = ix->default_filter;  // phnsw_index_set_filter_device
+  if (!c.filter.words) c.filter.words = ix->default_filter;  // phnsw_index_set_filter_device
   if (nq == 0) return 0;
   PH_HIP(hipSetDevice(ix->store->device));
-  return ph_search_device(ix, queries_dev, ldq, qids_dev, nq, sp, upto_layers, exclude_dev, out_ids_dev, out_d_dev,
-                          out_len_dev, out_stats_dev, status_dev, 0, 0, (hipStream_t)stream, 0, nullptr, 0.f, 0, 0.f, nullptr,
-                          nullptr, nullptr, &f);
+  return ph_search_device(ix, c);
 } catch (...) { return ph_caught(); }
 
 extern "C" int phnsw_index_set_filter_device(phnsw_index *ix, const uint32_t *filter_dev) try {
@@ -1095,15 +1121,8 @@ extern "C" int phnsw_dense_top_layers(const phnsw_index *ix, uint64_t number_of_
   return 0;
 } catch (...) { return ph_caught(); }
 
-// host-pointer searches live in hostpath.hip (persistent staging, pipelined chunks): ph_search_host
-static int search_host(const phnsw_index *ix, const float *queries, const uint64_t *qids, uint64_t nq,
-                       const phnsw_search_params *sp, uint32_t upto, const uint64_t *exclude, uint64_t *out_ids,
-                       float *out_d, uint64_t *out_len, uint64_t *out_stats, uint32_t knn_mode) {
-  return ph_search_host(ix, queries, qids, nq, sp, upto, exclude, 0, out_ids, out_d, out_len, out_stats, knn_mode, nullptr);
-}
-
 // Hnsw::knn  src/lib.rs:905-928: queue of 3k seeded with (self, 0.0), closest_nodes on the
-// bottom layer, drop self, take k
+// bottom layer, drop self, take k (a host-pointer search: ph_search_host, hostpath.hip)
 extern "C" int phnsw_knn(const phnsw_index *ix, uint64_t k, uint64_t probe_depth, uint64_t *out_ids, float *out_d,
                          uint64_t *out_len) try {
   if (ix)
@@ -1117,7 +1136,10 @@ extern "C" int phnsw_knn(const phnsw_index *ix, uint64_t k, uint64_t probe_depth
   uint64_t n = L.n_nodes, cap = k * 3;
   std::vector<uint64_t> ids(n * cap), len(n);
   std::vector<float> d(n * cap);
-  int rc = search_host(ix, nullptr, nullptr, n, &sp, 0, nullptr, ids.data(), d.data(), len.data(), nullptr, 1);
+  PhHostSearch h = {};
+  h.nq = n, h.sp = &sp, h.knn_mode = 1;
+  h.out_ids = ids.data(), h.out_d = d.data(), h.out_len = len.data();
+  int rc = ph_search_host(ix, h);
   if (rc) return rc;
   std::vector<uint64_t> nodes(n);
   rc = phnsw_index_layer_read(ix, (uint32_t)ix->layers.size() - 1, nodes.data(), nullptr);
@@ -1218,16 +1240,12 @@ static int threshold_nn_big(const phnsw_index *ix, const phnsw_search_params *sp
     PH_TRY_(d_q.alloc((size_t)grid * 2 * cap));
     PH_HIP(hipMemset(d_vis.p, 0, (size_t)grid * words * 4));
     PH_HIP(hipMemcpy(d_nodes.p, nodes.data(), cnt * 4, hipMemcpyHostToDevice));
+    PhSearchCall c = {};
+    c.nq = cnt, c.sp = sp;
+    c.out_ids = d_oid.p, c.out_d = d_od.p, c.out_len = d_len.p, c.status = d_status.p;
+    c.knn_mode = 2, c.threshold = threshold, c.out_stride = os;
     PhSearchArgs a;
-    fill_args(ix, sp, 0, a);
-    a.nq = (uint32_t)cnt;
-    a.out_ids = d_oid.p;
-    a.out_d = d_od.p;
-    a.out_len = d_len.p;
-    a.status = d_status.p;
-    a.knn_mode = 2;
-    a.threshold = threshold;
-    a.out_stride = os;
+    fill_args(ix, c, a);
     a.cap_max = (uint32_t)cap;
     a.knn_nodes = d_nodes.p;
     a.big_q = d_q.p;
@@ -1325,8 +1343,11 @@ extern "C" int phnsw_threshold_nn(const phnsw_index *ix, float threshold, uint64
   std::vector<float> h_d((size_t)cn * CAPMAX);
   for (uint32_t first = 0; !rc && first < n; first += CHUNK) {
     uint32_t cnt = std::min(CHUNK, n - first);
-    rc = ph_search_device(ix, nullptr, 0, nullptr, cnt, &sp, 0, nullptr, oid, od, olen, nullptr, ostat, 0, 2, 0, CAPMAX,
-                          nullptr, threshold, first);
+    PhSearchCall c = {};
+    c.nq = cnt, c.sp = &sp;
+    c.out_ids = oid, c.out_d = od, c.out_len = olen, c.status = ostat;
+    c.knn_mode = 2, c.threshold = threshold, c.out_stride = CAPMAX, c.first_node = first;
+    rc = ph_search_device(ix, c);
     if (rc) break;
     e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(h_ids.data(), oid, (size_t)cnt * CAPMAX * 4, hipMemcpyDeviceToHost);

@@ -559,10 +559,15 @@ static int search_stored(const phnsw_index *ix, const uint32_t *qids_dev, uint32
   }
   DevBuf<uint32_t> status;
   PH_TRY(status.alloc(nq));
-  uint32_t ovf_cap = ph_default_ovf_cap((uint32_t)sp->number_of_candidates);
+  PhSearchCall c = {};
+  c.qids = qids_dev, c.exclude = exclude_dev, c.nq = nq;
+  c.sp = sp, c.upto = upto;
+  c.out_ids = out_ids, c.out_d = out_d, c.out_len = out_len, c.status = status.p;
+  c.ovf_cap = ph_default_ovf_cap((uint32_t)sp->number_of_candidates);
+  c.out_stride = out_stride, c.out_hit = out_hit;
+  c.order = order, c.hint = hint;
   for (int attempt = 0; attempt < 3; attempt++) {
-    PH_TRY(ph_search_device(ix, nullptr, 0, qids_dev, nq, sp, upto, exclude_dev, out_ids, out_d, out_len, nullptr,
-                            status.p, ovf_cap, 0, 0, out_stride, out_hit, 0.f, 0, 0.f, order, nullptr, hint));
+    PH_TRY(ph_search_device(ix, c));
     PH_HIP(hipDeviceSynchronize());
     std::vector<uint32_t> h(nq);
     PH_HIP(hipMemcpy(h.data(), status.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
@@ -575,9 +580,9 @@ static int search_stored(const phnsw_index *ix, const uint32_t *qids_dev, uint32
       overflow |= (h[i] == 5);
     }
     if (!overflow) return 0;
-    ovf_cap *= 8;  // rare: rerun the whole batch with more spill room (results are deterministic)
+    c.ovf_cap *= 8;  // rare: rerun the whole batch with more spill room (results are deterministic)
   }
-  ph_set_error("build: frontier spill exceeded %u entries", ovf_cap);
+  ph_set_error("build: frontier spill exceeded %u entries", c.ovf_cap);
   return PHNSW_E_OVERFLOW;
 }
 
@@ -1166,13 +1171,17 @@ static int discover_hits_impl(phnsw_index *ix, uint32_t lft, const phnsw_search_
   PH_TRY(d.alloc(count));
   PH_TRY(len.alloc(count));
   PH_TRY(status.alloc(count));
-  uint32_t ovf_cap = ph_default_ovf_cap((uint32_t)sp->number_of_candidates);
-  const uint32_t *order = nullptr;
-  PH_TRY(ph_layer_range_order(L, first, count, &order));
+  const PhRowHint hint = row_hint(L, first, count, true);
+  PhSearchCall c = {};
+  c.qids = L.nodes + first, c.nq = count;
+  c.sp = sp, c.upto = lft + 1;
+  c.out_ids = ids.p, c.out_d = d.p, c.out_len = len.p, c.status = status.p;
+  c.ovf_cap = ph_default_ovf_cap((uint32_t)sp->number_of_candidates);
+  c.out_stride = 1, c.out_hit = hit_dev, c.hit_eps = 1e-5f;
+  c.hint = &hint;
+  PH_TRY(ph_layer_range_order(L, first, count, &c.order));
   for (int attempt = 0; attempt < 3; attempt++) {
-    const PhRowHint hint = row_hint(L, first, count, true);
-    PH_TRY(ph_search_device(ix, nullptr, 0, L.nodes + first, count, sp, lft + 1, nullptr, ids.p, d.p, len.p, nullptr,
-                            status.p, ovf_cap, 0, 0, 1, hit_dev, 0.f, 0, 1e-5f, order, nullptr, &hint));
+    PH_TRY(ph_search_device(ix, c));
     PH_HIP(hipDeviceSynchronize());
     std::vector<uint32_t> hs(count);
     PH_HIP(hipMemcpy(hs.data(), status.p, (size_t)count * 4, hipMemcpyDeviceToHost));
@@ -1185,7 +1194,7 @@ static int discover_hits_impl(phnsw_index *ix, uint32_t lft, const phnsw_search_
       overflow |= x == 5;
     }
     if (!overflow) return 0;
-    ovf_cap *= 8;
+    c.ovf_cap *= 8;
   }
   ph_set_error("discover_unreachable: frontier spill overflow");
   return PHNSW_E_OVERFLOW;

@@ -230,23 +230,15 @@ void ph_host_stages_free(phnsw_index *ix) {
   ix->stages.clear();
 }
 
-// out_k == 0: the whole queue (number_of_candidates entries per query)
-int ph_search_host(const phnsw_index *ix, const float *queries, const uint64_t *qids, uint64_t nq,
-                   const phnsw_search_params *sp, uint32_t upto, const uint64_t *exclude, uint64_t out_k,
-                   uint64_t *out_ids, float *out_d, uint64_t *out_len, uint64_t *out_stats, uint32_t knn_mode,
-                   uint64_t *out_index, const PhFilter *filter, bool filter_on_device) {
-  if (!ix || !sp || ix->layers.empty()) {
-    ph_set_error("search: null index/params or index without layers");
-    return PHNSW_E_INVALID;
-  }
-  if (sp->number_of_candidates == 0 || sp->number_of_candidates > 1024 || sp->probe_depth == 0 ||
-      sp->probe_depth > 0xFFFFFFFFull) {
-    ph_set_error("search: number_of_candidates must be 1..1024 and probe_depth >= 1 (got %llu, %llu)",
-                 (unsigned long long)sp->number_of_candidates, (unsigned long long)sp->probe_depth);
-    return PHNSW_E_INVALID;
-  }
-  const uint32_t ef = (uint32_t)sp->number_of_candidates;
-  if ((!queries && !qids && !knn_mode) || !out_ids || !out_d || !out_len || nq > 0xFFFFFFFFull || out_k > ef) {
+int ph_search_host(const phnsw_index *ix, const PhHostSearch &h) {
+  PH_TRY(ph_check_sp(ix, h.sp));
+  const float *const queries = h.queries;
+  const uint64_t *const qids = h.qids, *const exclude = h.exclude;
+  const uint64_t nq = h.nq, out_k = h.out_k;
+  uint64_t *const out_ids = h.out_ids, *const out_len = h.out_len, *const out_stats = h.out_stats, *const out_index = h.out_index;
+  float *const out_d = h.out_d;
+  const uint32_t ef = (uint32_t)h.sp->number_of_candidates;
+  if ((!queries && !qids && !h.knn_mode) || !out_ids || !out_d || !out_len || nq > 0xFFFFFFFFull || out_k > ef) {
     ph_set_error("search: invalid argument (queries or ids, outputs, k <= number_of_candidates)");
     return PHNSW_E_INVALID;
   }
@@ -299,19 +291,20 @@ int ph_search_host(const phnsw_index *ix, const float *queries, const uint64_t *
   };
 
   // the allow-list: a shared bitmap goes to the device once per call, per-query bitmaps travel with their chunk
-  const bool filtered = filter && filter->words;
-  const bool per_query = filtered && filter->stride != 0;
+  const PhFilter &filter = h.filter;
+  const bool filtered = filter.words != nullptr;
+  const bool per_query = filtered && filter.stride != 0;
   const uint64_t filter_words = (s->n + 31u) / 32u;
-  PhFilter fdev = {nullptr, 0u, filtered ? filter->flags : 0u};
-  if (filtered && filter_on_device) fdev.words = filter->words;
-  if (filtered && !filter_on_device && !per_query) {
+  PhFilter fdev = {nullptr, 0u, filtered ? filter.flags : 0u};
+  if (filtered && h.filter_on_device) fdev.words = filter.words;
+  if (filtered && !h.filter_on_device && !per_query) {
     Slot &s0 = st->slot[0];
     if (!s0.stream) {
       PH_HIP(hipStreamCreateWithFlags(&s0.stream, hipStreamNonBlocking));
       PH_HIP(hipEventCreateWithFlags(&s0.done, hipEventDisableTiming));
     }
     PH_TRY(grow(&st->filt, &st->filt_bytes, (size_t)filter_words * 4, "host path: filter staging"));
-    PH_HIP(hipMemcpyAsync(st->filt, filter->words, (size_t)filter_words * 4, hipMemcpyHostToDevice, s0.stream));
+    PH_HIP(hipMemcpyAsync(st->filt, filter.words, (size_t)filter_words * 4, hipMemcpyHostToDevice, s0.stream));
     PH_HIP(hipStreamSynchronize(s0.stream));  // both slots' streams read it
     fdev.words = st->filt;
   }
@@ -323,47 +316,68 @@ int ph_search_host(const phnsw_index *ix, const float *queries, const uint64_t *
       }
     rc = pair_streams(*st);
   }
-  for (size_t c = 0; c < n_chunks && !rc; c++) {
-    Slot &sl = st->slot[c & 1];
-    rc = finish(sl);  // the slot's previous chunk (two chunks back) comes home first
-    if (rc) break;
-    const uint64_t c0 = bounds[c], cnt = bounds[c + 1] - c0;
-    rc = slot_ensure(sl, cnt, s->ld, queries != nullptr, ef, k);
-    if (rc) break;
-    const uint64_t N = cnt;
-    uint32_t *d_qid = sl.small, *d_excl = sl.small + N, *d_len = sl.small + 2 * N, *d_status = sl.small + 3 * N,
-             *d_index = sl.small + 4 * N, *d_stats = sl.small + 5 * N;
+  // queries [first, first + cnt) into a slot and onto its stream: the query rows (padded to the store's row length), the
+  // id and exclude words, the per-query bitmaps, then the search.  A failed upload leaves the chunk loop at once, the
+  // step's other failures drain the slots first, and the re-run loop returns at once on both: as before the step was
+  // written once (which paths should drain is a question of its own)
+  bool upload_failed = false;
+#define PH_STAGE_HIP(x)                               \
+  do {                                                \
+    hipError_t e__ = (x);                             \
+    if (e__ != hipSuccess) {                          \
+      upload_failed = true;                           \
+      return ph_hip_fail(e__, #x, __FILE__, __LINE__); \
+    }                                                 \
+  } while (0)
+  auto stage_and_launch = [&](Slot &sl, uint64_t first, uint64_t cnt, uint32_t ovf_cap) -> int {
+    PH_TRY(slot_ensure(sl, cnt, s->ld, queries != nullptr, ef, k));
+    const uint64_t N = cnt;  // the per-query words are laid out [7][cnt]: qid | excl | len | status | index | stats(2)
     if (queries) {
       if (s->ld != s->dim) {
-        PH_HIP(hipMemsetAsync(sl.q, 0, (size_t)cnt * s->ld * 4, sl.stream));
-        PH_HIP(hipMemcpy2DAsync(sl.q, (size_t)s->ld * 4, queries + c0 * s->dim, (size_t)s->dim * 4, (size_t)s->dim * 4, cnt,
+        PH_STAGE_HIP(hipMemsetAsync(sl.q, 0, (size_t)cnt * s->ld * 4, sl.stream));
+        PH_STAGE_HIP(hipMemcpy2DAsync(sl.q, (size_t)s->ld * 4, queries + first * s->dim, (size_t)s->dim * 4, (size_t)s->dim * 4, cnt,
                                 hipMemcpyHostToDevice, sl.stream));
       } else {
-        PH_HIP(hipMemcpyAsync(sl.q, queries + c0 * s->dim, (size_t)cnt * s->dim * 4, hipMemcpyHostToDevice, sl.stream));
+        PH_STAGE_HIP(hipMemcpyAsync(sl.q, queries + first * s->dim, (size_t)cnt * s->dim * 4, hipMemcpyHostToDevice, sl.stream));
       }
     }
     if (qids || exclude) {
       if (qids)
-        for (uint64_t i = 0; i < cnt; i++) sl.h_small[i] = (uint32_t)qids[c0 + i];
+        for (uint64_t i = 0; i < cnt; i++) sl.h_small[i] = (uint32_t)qids[first + i];
       if (exclude)
-        for (uint64_t i = 0; i < cnt; i++) sl.h_small[N + i] = exclude[c0 + i] >= s->n ? PH_EMPTY32 : (uint32_t)exclude[c0 + i];
-      PH_HIP(hipMemcpyAsync(sl.small, sl.h_small, 2 * N * 4, hipMemcpyHostToDevice, sl.stream));
+        for (uint64_t i = 0; i < cnt; i++) sl.h_small[N + i] = exclude[first + i] >= s->n ? PH_EMPTY32 : (uint32_t)exclude[first + i];
+      PH_STAGE_HIP(hipMemcpyAsync(sl.small, sl.h_small, 2 * N * 4, hipMemcpyHostToDevice, sl.stream));
     }
     if (per_query) {
-      const size_t bytes = (size_t)cnt * filter->stride * 4;
-      rc = grow(&sl.filt, &sl.filt_bytes, bytes, "host path: per-query filter staging");
-      if (rc) break;
-      PH_HIP(hipMemcpyAsync(sl.filt, filter->words + c0 * filter->stride, bytes, hipMemcpyHostToDevice, sl.stream));
+      const size_t bytes = (size_t)cnt * filter.stride * 4;
+      PH_TRY(grow(&sl.filt, &sl.filt_bytes, bytes, "host path: per-query filter staging"));
+      PH_STAGE_HIP(hipMemcpyAsync(sl.filt, filter.words + first * filter.stride, bytes, hipMemcpyHostToDevice, sl.stream));
       fdev.words = sl.filt;
-      fdev.stride = filter->stride;
+      fdev.stride = filter.stride;
     }
-    rc = ph_search_device(ix, queries ? sl.q : nullptr, s->ld, qids ? d_qid : nullptr, cnt, sp, upto, exclude ? d_excl : nullptr,
-                          sl.ids, sl.d, d_len, d_stats, d_status, 0, knn_mode, sl.stream, 0, nullptr, 0.f, (uint32_t)c0, 0.f,
-                          nullptr, out_index ? d_index : nullptr, nullptr, filtered ? &fdev : nullptr);
-    if (rc) break;
-    sl.c0 = c0;
+    PhSearchCall c = {};
+    if (queries) c.queries = sl.q;
+    if (qids) c.qids = sl.small;
+    if (exclude) c.exclude = sl.small + N;
+    if (filtered) c.filter = fdev;
+    c.ldq = s->ld, c.nq = cnt, c.sp = h.sp, c.upto = h.upto;
+    c.out_ids = sl.ids, c.out_d = sl.d, c.out_len = sl.small + 2 * N, c.status = sl.small + 3 * N;
+    if (out_index) c.out_index = sl.small + 4 * N;
+    c.out_stats = sl.small + 5 * N;
+    c.ovf_cap = ovf_cap, c.stream = sl.stream;
+    c.knn_mode = h.knn_mode, c.first_node = (uint32_t)first;  // first_node: read in the knn modes only
+    PH_TRY(ph_search_device(ix, c));
+    sl.c0 = first;
     sl.cnt = cnt;
     sl.busy = true;
+    return 0;
+  };
+#undef PH_STAGE_HIP
+  for (size_t c = 0; c < n_chunks && !rc; c++) {
+    Slot &sl = st->slot[c & 1];
+    rc = finish(sl);  // the slot's previous chunk (two chunks back) comes home first
+    if (!rc) rc = stage_and_launch(sl, bounds[c], bounds[c + 1] - bounds[c], 0);
+    if (upload_failed) return rc;
   }
   // the (up to two) chunks still in flight, oldest first
   if (n_chunks >= 2) {
@@ -385,7 +399,7 @@ int ph_search_host(const phnsw_index *ix, const float *queries, const uint64_t *
   // queries whose frontier spill outgrew the workspace: rerun them alone with 8x the room (rare)
   uint32_t ovf_cap = ph_default_ovf_cap(ef);
   for (int attempt = 0; !redo.empty(); attempt++) {
-    if (knn_mode) {
+    if (h.knn_mode) {
       ph_set_error("knn: frontier spill exceeded %u entries", ovf_cap);
       return PHNSW_E_OVERFLOW;
     }
@@ -398,28 +412,7 @@ int ph_search_host(const phnsw_index *ix, const float *queries, const uint64_t *
     todo.swap(redo);
     Slot &sl = st->slot[0];
     for (uint32_t qi : todo) {
-      PH_TRY(slot_ensure(sl, 1, s->ld, queries != nullptr, ef, k));
-      const uint64_t N = 1;
-      if (queries) {
-        PH_HIP(hipMemsetAsync(sl.q, 0, (size_t)s->ld * 4, sl.stream));
-        PH_HIP(hipMemcpyAsync(sl.q, queries + (uint64_t)qi * s->dim, (size_t)s->dim * 4, hipMemcpyHostToDevice, sl.stream));
-      }
-      sl.h_small[0] = qids ? (uint32_t)qids[qi] : 0u;
-      sl.h_small[N] = (exclude && exclude[qi] < s->n) ? (uint32_t)exclude[qi] : PH_EMPTY32;
-      PH_HIP(hipMemcpyAsync(sl.small, sl.h_small, 2 * N * 4, hipMemcpyHostToDevice, sl.stream));
-      if (per_query) {  // (slot 0 holds at least one bitmap: it staged a chunk)
-        PH_HIP(hipMemcpyAsync(sl.filt, filter->words + (uint64_t)qi * filter->stride, (size_t)filter->stride * 4,
-                              hipMemcpyHostToDevice, sl.stream));
-        fdev.words = sl.filt;
-        fdev.stride = filter->stride;
-      }
-      PH_TRY(ph_search_device(ix, queries ? sl.q : nullptr, s->ld, qids ? sl.small : nullptr, 1, sp, upto,
-                              exclude ? sl.small + N : nullptr, sl.ids, sl.d, sl.small + 2 * N, sl.small + 5 * N, sl.small + 3 * N,
-                              ovf_cap, 0, sl.stream, 0, nullptr, 0.f, 0, 0.f, nullptr, out_index ? sl.small + 4 * N : nullptr,
-                              nullptr, filtered ? &fdev : nullptr));
-      sl.c0 = qi;
-      sl.cnt = 1;
-      sl.busy = true;
+      PH_TRY(stage_and_launch(sl, qi, 1, ovf_cap));
       PH_TRY(finish(sl));
     }
   }
@@ -427,6 +420,15 @@ int ph_search_host(const phnsw_index *ix, const float *queries, const uint64_t *
 }
 
 // ------------------------------------------------------------------ C ABI
+
+// what every host entry point below asks for: queries or ids, the parameters, the three result arrays
+static PhHostSearch host_call(const float *queries, const uint64_t *qids, uint64_t nq, const phnsw_search_params *sp,
+                              uint64_t *out_ids, float *out_d, uint64_t *out_len) {
+  PhHostSearch h = {};
+  h.queries = queries, h.qids = qids, h.nq = nq, h.sp = sp;
+  h.out_ids = out_ids, h.out_d = out_d, h.out_len = out_len;
+  return h;
+}
 
 // Hnsw::search for a batch of AbstractVector::Unstored queries  lib.rs:663-665
 extern "C" int phnsw_search_batch(const phnsw_index *ix, const float *queries, uint64_t nq,
@@ -436,7 +438,9 @@ extern "C" int phnsw_search_batch(const phnsw_index *ix, const float *queries, u
     ph_set_error("phnsw_search_batch: queries is NULL");
     return PHNSW_E_INVALID;
   }
-  return ph_search_host(ix, queries, nullptr, nq, sp, upto_layers, exclude, 0, out_ids, out_d, out_len, out_stats, 0, nullptr);
+  PhHostSearch h = host_call(queries, nullptr, nq, sp, out_ids, out_d, out_len);
+  h.upto = upto_layers, h.exclude = exclude, h.out_stats = out_stats;
+  return ph_search_host(ix, h);
 } catch (...) { return ph_caught(); }
 
 extern "C" int phnsw_search_batch_stored(const phnsw_index *ix, const uint64_t *qids, uint64_t nq,
@@ -446,7 +450,9 @@ extern "C" int phnsw_search_batch_stored(const phnsw_index *ix, const uint64_t *
     ph_set_error("phnsw_search_batch_stored: qids is NULL");
     return PHNSW_E_INVALID;
   }
-  return ph_search_host(ix, nullptr, qids, nq, sp, upto_layers, exclude, 0, out_ids, out_d, out_len, out_stats, 0, nullptr);
+  PhHostSearch h = host_call(nullptr, qids, nq, sp, out_ids, out_d, out_len);
+  h.upto = upto_layers, h.exclude = exclude, h.out_stats = out_stats;
+  return ph_search_host(ix, h);
 } catch (...) { return ph_caught(); }
 
 // the same keeping only the best k results of every query: the truncation callers of Hnsw::search do themselves
@@ -462,7 +468,9 @@ extern "C" int phnsw_search_batch_topk(const phnsw_index *ix, const float *queri
     ph_set_error("phnsw_search_batch_topk: k must be 1..number_of_candidates");
     return PHNSW_E_INVALID;
   }
-  return ph_search_host(ix, queries, qids, nq, sp, upto_layers, exclude, k, out_ids, out_d, out_len, nullptr, 0, nullptr);
+  PhHostSearch h = host_call(queries, qids, nq, sp, out_ids, out_d, out_len);
+  h.upto = upto_layers, h.exclude = exclude, h.out_k = k;
+  return ph_search_host(ix, h);
 } catch (...) { return ph_caught(); }
 
 // Hnsw::search_instrumented  lib.rs:667-673: results + the index_distance of search_layers_instrumented
@@ -476,7 +484,9 @@ extern "C" int phnsw_search_instrumented(const phnsw_index *ix, const float *que
     ph_set_error("phnsw_search_instrumented: pass queries or qids (exactly one) and out_index_distance");
     return PHNSW_E_INVALID;
   }
-  return ph_search_host(ix, queries, qids, nq, sp, 0, nullptr, 0, out_ids, out_d, out_len, nullptr, 0, out_index_distance);
+  PhHostSearch h = host_call(queries, qids, nq, sp, out_ids, out_d, out_len);
+  h.out_index = out_index_distance;
+  return ph_search_host(ix, h);
 } catch (...) { return ph_caught(); }
 
 // Hnsw::search with closest_vectors' `include` (lib.rs:250-277) as an allow bitmap over VectorIds
@@ -492,10 +502,10 @@ extern "C" int phnsw_search_batch_filtered(const phnsw_index *ix, const float *q
     ph_set_error("search: null index/params or index without layers");
     return PHNSW_E_INVALID;
   }
-  PhFilter f;
-  PH_TRY(ph_filter_check(ix, filter, filter_stride_words, flags, "phnsw_search_batch_filtered", &f));
-  const bool use_default = !f.words && ix->default_filter;  // phnsw_index_set_filter_device: device words
-  if (use_default) f.words = ix->default_filter;
-  return ph_search_host(ix, queries, qids, nq, sp, upto_layers, exclude, k, out_ids, out_d, out_len, out_stats, 0, nullptr, &f,
-                        use_default);
+  PhHostSearch h = host_call(queries, qids, nq, sp, out_ids, out_d, out_len);
+  h.upto = upto_layers, h.exclude = exclude, h.out_k = k, h.out_stats = out_stats;
+  PH_TRY(ph_filter_check(ix, filter, filter_stride_words, flags, "phnsw_search_batch_filtered", &h.filter));
+  h.filter_on_device = !h.filter.words && ix->default_filter;  // phnsw_index_set_filter_device: device words
+  if (h.filter_on_device) h.filter.words = ix->default_filter;
+  return ph_search_host(ix, h);
 } catch (...) { return ph_caught(); }

@@ -361,21 +361,51 @@ void ph_pending_free(phnsw_index *ix);
 void ph_host_stages_free(phnsw_index *ix);  // hostpath.hip
 int ph_layer_upload(phnsw_index *ix, const uint32_t *nodes, const uint32_t *neighbors, uint32_t n, uint32_t W,
                     PhLayerHost *out);
-int ph_search_device(const phnsw_index *ix, const float *queries_dev, uint32_t ldq, const uint32_t *qids_dev,
-                     uint64_t nq, const phnsw_search_params *sp, uint32_t upto, const uint32_t *exclude_dev,
-                     uint32_t *out_ids, float *out_d, uint32_t *out_len, uint32_t *out_stats, uint32_t *status,
-                     uint32_t ovf_cap, uint32_t knn_mode, hipStream_t stream, uint32_t out_stride = 0,
-                     uint32_t *out_hit = nullptr, float threshold = 0.f, uint32_t first_node = 0,
-                     float hit_eps = 0.f, const uint32_t *order = nullptr, uint32_t *out_index = nullptr,
-                     const PhRowHint *hint = nullptr, const PhFilter *filter = nullptr);
-// argument checks of the filtered entry points (api.hip): flags, stride; *f = the triple a launch gets
+// The request of one device search (ph_search_device).  All pointers are device memory owned by the caller; the
+// value-initialised struct means "absent" for every optional field, so a call site names only what it uses.
+struct PhSearchCall {
+  const float *queries;  // [nq][ldq], or nullptr: Stored queries (qids) or a knn mode
+  uint32_t ldq;
+  const uint32_t *qids, *exclude;  // [nq] or nullptr
+  uint64_t nq;
+  const phnsw_search_params *sp;
+  uint32_t upto;    // layers searched, 0 = all
+  PhFilter filter;  // words == nullptr: none
+  uint32_t *out_ids;  // [nq][out_stride ? out_stride : number_of_candidates]
+  float *out_d;
+  uint32_t *out_len, *status;  // [nq]
+  uint32_t *out_stats;         // [nq][2] or nullptr
+  uint32_t ovf_cap;            // spill-list entries per resident wave, 0 = ph_default_ovf_cap
+  hipStream_t stream;
+  // the rest as PhSearchArgs describes it; out_stride: threshold_nn's largest queue capacity as well
+  uint32_t knn_mode, first_node, out_stride;
+  float threshold, hit_eps;
+  uint32_t *out_hit, *out_index;  // [nq] or nullptr
+  const uint32_t *order;
+  const PhRowHint *hint;  // a build's searches: the kept table (tiny.hip)
+};
+int ph_search_device(const phnsw_index *ix, const PhSearchCall &c);
+// argument checks the search entry points share (api.hip): index and parameters; the device forms' pointers (`call`
+// names the entry point in the message); a filtered call's flags and stride, *f = the triple a launch gets
+int ph_check_sp(const phnsw_index *ix, const phnsw_search_params *sp);
 int ph_filter_check(const phnsw_index *ix, const uint32_t *filter, uint32_t stride, uint32_t flags, const char *call,
                     PhFilter *f);
-// host-pointer searches (hostpath.hip).  filter: host words (or, filter_on_device, device words of a shared bitmap)
-int ph_search_host(const phnsw_index *ix, const float *queries, const uint64_t *qids, uint64_t nq,
-                   const phnsw_search_params *sp, uint32_t upto, const uint64_t *exclude, uint64_t out_k,
-                   uint64_t *out_ids, float *out_d, uint64_t *out_len, uint64_t *out_stats, uint32_t knn_mode,
-                   uint64_t *out_index, const PhFilter *filter = nullptr, bool filter_on_device = false);
+// The request of one host-pointer search (ph_search_host, hostpath.hip): host arrays, ids as u64.
+struct PhHostSearch {
+  const float *queries;            // [nq][dim] or nullptr
+  const uint64_t *qids, *exclude;  // [nq] or nullptr
+  uint64_t nq;
+  const phnsw_search_params *sp;
+  uint32_t upto, knn_mode;
+  uint64_t out_k;  // results kept per query, 0 = the whole queue (number_of_candidates entries)
+  uint64_t *out_ids;  // [nq][k]
+  float *out_d;
+  uint64_t *out_len;
+  uint64_t *out_stats, *out_index;  // [nq][2], [nq] or nullptr
+  PhFilter filter;                  // host words; words == nullptr: none
+  bool filter_on_device;            // filter.words is a shared bitmap in device memory (phnsw_index_set_filter_device)
+};
+int ph_search_host(const phnsw_index *ix, const PhHostSearch &h);
 // locality schedule helpers (group.hip / api.hip)
 #define PH_ORDER_MIN 16384u  // shorter query lists run in natural order
 #define PH_POS_MIN 256u     // smaller layers carry no cells (their node id is the key)

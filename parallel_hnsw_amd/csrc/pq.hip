@@ -354,8 +354,12 @@ static int pq_shared_encode_device(const phnsw_store *s, const float *rows_dev, 
   std::vector<uint32_t> h_status;
   for (uint64_t c0 = 0; !rc && c0 < total; c0 += CH) {
     const uint64_t cnt = std::min(CH, total - c0);
-    rc = ph_search_device(s->centroid_index, rows_dev + c0 * s->pq_dsub, s->pq_dsub, nullptr, cnt, &s->quantized_search, 0,
-                          nullptr, oid, od, olen, nullptr, ostat, 0, 0, 0, /*out_stride=*/1);
+    PhSearchCall c = {};
+    c.queries = rows_dev + c0 * s->pq_dsub, c.ldq = s->pq_dsub, c.nq = cnt;
+    c.sp = &s->quantized_search;
+    c.out_ids = oid, c.out_d = od, c.out_len = olen, c.status = ostat;
+    c.out_stride = 1;
+    rc = ph_search_device(s->centroid_index, c);
     if (rc) break;
     hipLaunchKernelGGL(ph_ids_to_u16_kernel, dim3(1024), dim3(256), 0, 0, oid, cnt, codes_dev + c0);
     h_status.resize(cnt);
@@ -686,8 +690,13 @@ static int reranked_search_device(const phnsw_index *ix, const phnsw_store *full
                                   void *stream) {
   if (nq == 0) return 0;
   PH_HIP(hipSetDevice(full->device));
-  PH_TRYQ(ph_search_device(ix, queries_dev, ldq, nullptr, nq, sp, 0, nullptr, out_ids_dev, out_d_dev, out_len_dev,
-                           out_stats_dev, status_dev, 0, 0, (hipStream_t)stream));
+  PhSearchCall c = {};
+  c.queries = queries_dev, c.ldq = ldq, c.nq = nq;
+  c.sp = sp;
+  c.out_ids = out_ids_dev, c.out_d = out_d_dev, c.out_len = out_len_dev, c.status = status_dev;
+  c.out_stats = out_stats_dev;
+  c.stream = (hipStream_t)stream;
+  PH_TRYQ(ph_search_device(ix, c));
   return rerank_launch(full, queries_dev, ldq, nq, (uint32_t)sp->number_of_candidates, (uint32_t)k, out_len_dev, out_ids_dev,
                        out_d_dev, (hipStream_t)stream);
 }
@@ -721,8 +730,12 @@ static int reranked_search_host(const char *call, const phnsw_index *ix, const p
   if (e == hipSuccess) e = hipMalloc(&ids64, (size_t)nq * k * 8);
   if (e == hipSuccess) e = hipMalloc(&dk, (size_t)nq * k * 4);
   if (e != hipSuccess) rc = ph_hip_fail(e, "re-ranked search staging", __FILE__, __LINE__);
-  if (!rc)
-    rc = ph_search_device(ix, qsearch ? qsearch : qd, full->ld, nullptr, nq, sp, 0, nullptr, oid, od, olen, ost, ostat, 0, 0, 0);
+  PhSearchCall c = {};
+  c.queries = qsearch ? qsearch : qd, c.ldq = full->ld, c.nq = nq;
+  c.sp = sp;
+  c.out_ids = oid, c.out_d = od, c.out_len = olen, c.status = ostat;
+  c.out_stats = ost;
+  if (!rc) rc = ph_search_device(ix, c);
   if (!rc) rc = rerank_launch(full, qd, full->ld, nq, ef, (uint32_t)k, olen, oid, od, 0);
   if (!rc) rc = ph_take_launch(oid, od, ef, (uint32_t)k, nq, ids64, dk, 0);
   if (!rc) {

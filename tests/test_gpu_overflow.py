@@ -2,6 +2,7 @@
 the LDS queue, lib.rs:182-191) has a fixed capacity per resident wave; a query that outgrows it is
 flagged and re-run with more room.  PHNSW_OVF_CAP forces a tiny list so that these paths run:
 results must still equal the oracle's."""
+import functools
 import os
 
 import numpy as np
@@ -9,6 +10,9 @@ import pytest
 
 import oracle
 import parallel_hnsw_amd as ph
+
+import filter_reference as fr
+from test_gpu_filter import device_search
 
 pytestmark = pytest.mark.gpu
 
@@ -57,6 +61,73 @@ def test_search_reruns_overflowing_queries():
     np.testing.assert_array_equal(gd.view(np.uint32), cd.view(np.uint32))
     np.testing.assert_array_equal(gl, cl)
     np.testing.assert_array_equal(gs, cs)
+
+
+# ---- the host path's re-run of single queries with every staged field present: query rows that need padding (dim 30 in
+# rows of 32), stored ids, exclude words, per-query bitmaps, counters, the instrumented index.  Expected values are
+# the CPU side's throughout.
+N30, DIM30, SP30, CAP30 = 3000, 30, (16, 16, 8), 8
+
+
+@functools.lru_cache(maxsize=None)
+def world30():
+    """(oracle index, f32 store over the same rows, the graph's layers); made once, changed by no test"""
+    rows = oracle.synth_rows(0, N30, DIM30)
+    oix = oracle.Index.generate(rows, np.arange(N30), oracle.default_build_params(seed=1), dim=DIM30,
+                                sum_mode=oracle.SUM_BLOCKED64)
+    store = ph.VectorStore(rows[:, :DIM30])
+    assert store.ld == 32
+    return oix, store, [oix.layer(l) for l in range(oix.layer_count)]
+
+
+def fresh(store, layers):
+    """a workspace keeps the largest spill list it ever had: every call that must overflow gets a new index"""
+    return ph.Hnsw.from_layers(store, layers)
+
+
+def same_rows(got, want):
+    np.testing.assert_array_equal(got[2], want[2])
+    np.testing.assert_array_equal(got[0], want[0])
+    np.testing.assert_array_equal(got[1].view(np.uint32), want[1].view(np.uint32))
+    np.testing.assert_array_equal(got[3], want[3])
+
+
+def test_rerun_stages_stored_queries_exclude_filter_and_counters(monkeypatch):
+    oix, store, layers = world30()
+    sp = ph.SearchParameters(*SP30)
+    qids = np.arange(7, N30, N30 // 300, dtype=np.uint64)[:300]
+    assert len(qids) == 300
+    allow = np.random.default_rng(2024).random((300, N30)) < 0.5
+    D = fr.distance_rows(oix, qids=qids, mode=oracle.SUM_BLOCKED64)
+    want_filtered = fr.search(oix, D, SP30, allow=allow, exclude=qids)
+    want_plain = oix.search(qids=qids, sp=SP30, exclude=qids, stats=True)
+    same_rows(fr.search(oix, D, SP30, allow=None, exclude=qids), want_plain)  # the restatement, on these very inputs
+    with tiny_spill(CAP30):
+        # the re-run loop runs: under this cap the device forms report overflow (status 5) and retry nothing
+        for a in (allow, None):
+            st = device_search(fresh(store, layers), sp, qids=qids, allow=a, exclude=qids)[4]
+            assert (st == 5).sum() > 0 and set(st.tolist()) <= {0, 5}
+        for chunks in (None, "64,16,100"):  # whole; then 16 + pieces of <= 100: re-run entries from both slots
+            if chunks:
+                monkeypatch.setenv("PHNSW_HOST_CHUNKS", chunks)
+            same_rows(fresh(store, layers).search_batch_filtered(qids=qids, sp=sp, allow=allow, exclude=qids, stats=True),
+                      want_filtered)
+            same_rows(fresh(store, layers).search_batch(qids=qids, sp=sp, exclude=qids, stats=True), want_plain)
+
+
+def test_rerun_stages_padded_raw_queries_for_the_instrumented_search():
+    oix, store, layers = world30()
+    sp = ph.SearchParameters(*SP30)
+    q = oracle.synth_rows(2 ** 32, 300, DIM30)[:, :DIM30]
+    ci, cd, cl, cx = oix.search_instrumented(queries=q, sp=SP30)
+    with tiny_spill(CAP30):
+        st = device_search(fresh(store, layers), sp, queries=q)[4]
+        assert (st == 5).sum() > 0 and set(st.tolist()) <= {0, 5}
+        gi, gd, gl, gx = fresh(store, layers).search_instrumented_batch(queries=q, sp=sp)
+    np.testing.assert_array_equal(gl, cl)
+    np.testing.assert_array_equal(gi, ci)
+    np.testing.assert_array_equal(gd.view(np.uint32), cd.view(np.uint32))
+    np.testing.assert_array_equal(gx, cx)
 
 
 def test_build_reruns_overflowing_rounds():
