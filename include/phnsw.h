@@ -211,7 +211,8 @@ int phnsw_search_batch_device(const phnsw_index *ix, const float *queries_dev, u
  * (src/lib.rs:250-277) as a bitmap instead of the one instantiation `|v| Some(v) != exclude` (src/search.rs:128-134).
  * A layer's result keeps v iff v != exclude[q] and the bit of v is set; take(candidate_count) counts kept entries only.
  * It is a POST-filter on each layer's queue: the traversal is the unfiltered one, so a filter of density p leaves about
- * p * number_of_candidates results -- selective filters want a larger number_of_candidates.
+ * p * number_of_candidates results -- selective filters want a larger number_of_candidates, and below some density no
+ * number_of_candidates is large enough: there phnsw_search_exact_filtered (below) scans the allowed rows instead.
  * The entry vector (layers[0].nodes[0]) enters the candidates before any filter runs (search.rs:102-111) and can be
  * returned although it is disallowed, exactly as it can be returned although excluded; PHNSW_FILTER_STRICT removes
  * disallowed ids from the final rows (lengths shrink, padding PHNSW_EMPTY / f32::MAX).
@@ -240,6 +241,40 @@ int phnsw_search_batch_filtered_device(const phnsw_index *ix, const float *queri
  * FILTERED call on this index that passes filter == NULL (NULL here clears it).  The other entry points never see it.
  * Not to be called while searches on the index are in flight. */
 int phnsw_index_set_filter_device(phnsw_index *ix, const uint32_t *filter_dev);
+/* ---- exact top-k over the allow-list: the call for SELECTIVE filters.  No traversal: the allowed rows are scanned, so
+ * the recall is 1 and the cost is one distance per candidate -- cheaper than the graph walk when few rows are allowed,
+ * and the only form that answers at all when density * number_of_candidates falls below k.
+ * A VectorId v is a candidate of query q iff v < n, its bit is set in q's bitmap, v != exclude[q] and v is a vector of
+ * the index's bottom layer (an index may cover only part of its store).  Bitmap layout, stride rule and the default
+ * filter (filter NULL) as phnsw_search_batch_filtered; no filter at all = every vector of the index; bits at or past n
+ * are ignored.  There is no entry-vector quirk: a disallowed id is never returned.
+ * Result: the k candidates with the smallest (distance, id), ascending; out_len[q] = min(k, candidates of q); rows of k
+ * entries padded with PHNSW_EMPTY / f32::MAX.  The distance of (q, v) has exactly the bits phnsw_distance_batch returns
+ * for it on the same store; equal distances are ordered by id.  1 <= k <= 1024, else PHNSW_E_INVALID.  nq == 0 is a
+ * no-op.  Exactly one of queries / qids.  Every store kind phnsw_distance_batch accepts (f32, f16, i8, i8q, PQ); a
+ * shared-codebook PQ store is PHNSW_E_UNSUPPORTED, and so is a PQ store whose lookup table plus the scan's own LDS
+ * (16 * k + 8704 bytes) exceed a workgroup's 160 KiB.
+ * Choosing between this call and phnsw_search_batch_filtered is the caller's job: phnsw_filter_count_device gives the
+ * number of candidates to choose by.  Guidance (measured on 1M x 768 f32 rows, 10 000-query batches, k = 10;
+ * profiles/filter_exact/README.md): the scan is the faster call below roughly 13 000 candidates per query with a shared
+ * bitmap and about 10 000 with per-query bitmaps, and the only one that returns k results once density * 1024 < k.
+ * No existing call switches by itself. */
+int phnsw_search_exact_filtered(const phnsw_index *ix, const float *queries, const uint64_t *qids, uint64_t nq,
+                                const uint64_t *exclude, const uint32_t *filter, uint32_t filter_stride_words,
+                                uint64_t k, uint64_t *out_ids, float *out_d, uint64_t *out_len);
+/* zero-copy form: device pointers, u32 ids [nq][k] padded with 0xFFFFFFFF / f32::MAX, enqueued on `stream` without
+ * synchronising; queries [nq][ldq] as for phnsw_search_batch_device.  status_dev[q]: 0 = ok, 4 = a Stored query id at
+ * or past n (the row is then empty). */
+int phnsw_search_exact_filtered_device(const phnsw_index *ix, const float *queries_dev, uint32_t ldq,
+                                       const uint32_t *qids_dev, uint64_t nq, const uint32_t *exclude_dev,
+                                       const uint32_t *filter_dev, uint32_t filter_stride_words, uint64_t k,
+                                       uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                       uint32_t *status_dev, void *stream);
+/* the number of candidates of each of nbitmaps bitmaps (filter_stride_words apart; 0 = the one shared bitmap, counted
+ * nbitmaps times): set bits below n whose vector is in the index, no exclude.  filter_dev NULL = the default filter,
+ * else every vector of the index.  out_count_dev [nbitmaps] u32, device memory; enqueued on `stream`. */
+int phnsw_filter_count_device(const phnsw_index *ix, const uint32_t *filter_dev, uint32_t filter_stride_words,
+                              uint64_t nbitmaps, uint32_t *out_count_dev, void *stream);
 /* Throughput callers keep TWO batches in flight: phnsw_search_batch_device calls issued alternately on two streams
  * overlap (an index holds two search workspaces) -- if the two streams sit on different hardware queues.  HIP maps a
  * process's streams onto a few of them (GPU_MAX_HW_QUEUES, 4 by default) and two streams that share one run in issue

@@ -334,6 +334,41 @@ class Hnsw {
                                              stride_words, strict ? PHNSW_FILTER_STRICT : 0u, out_ids_dev, out_d_dev,
                                              out_len_dev, out_stats_dev, status_dev, stream));
   }
+  // the exact k nearest among the allowed VectorIds (phnsw_search_exact_filtered): a scan of the allow-list instead of
+  // the graph walk, recall 1 -- the call for selective filters.  `allow` as for search_many_filtered (empty = the default
+  // of set_filter_device, else every vector of the index).  Only vectors of the index are candidates; a disallowed id is
+  // never returned; results ascend by (distance, id).  Throws unless 1 <= k <= 1024 and on a short `allow`
+  std::vector<SearchResult> search_many_exact_filtered(const std::vector<const float *> &queries, uint64_t k,
+                                                       const std::vector<uint32_t> &allow, uint32_t stride_words = 0) const {
+    const uint64_t nq = queries.size(), dim = c_->dim(), words = (c_->len() + 31) / 32;
+    if (k == 0 || k > 1024) throw Error(PHNSW_E_INVALID, "search_many_exact_filtered: k must be 1..1024");
+    if (!allow.empty() && (stride_words ? stride_words < words || allow.size() < nq * stride_words : allow.size() < words))
+      throw Error(PHNSW_E_INVALID, "search_many_exact_filtered: allow is shorter than its bitmaps (ceil(n / 32) words "
+                                   "shared, nq * stride_words per query, stride_words >= ceil(n / 32))");
+    std::vector<float> q(nq * dim);
+    for (uint64_t i = 0; i < nq; i++) std::copy(queries[i], queries[i] + dim, q.begin() + i * dim);
+    std::vector<uint64_t> ids(nq * k), len(nq);
+    std::vector<float> d(nq * k);
+    check(phnsw_search_exact_filtered(ix_, q.data(), nullptr, nq, nullptr, allow.empty() ? nullptr : allow.data(),
+                                      stride_words, k, ids.data(), d.data(), len.data()));
+    std::vector<SearchResult> out(nq);
+    for (uint64_t i = 0; i < nq; i++)
+      for (uint64_t j = 0; j < len[i]; j++) out[i].push_back({ids[i * k + j], d[i * k + j]});
+    return out;
+  }
+  // zero-copy form (phnsw_search_exact_filtered_device): u32 ids [nq][k], enqueued on `stream`
+  void search_exact_filtered_device(const float *queries_dev, uint32_t ldq, const uint32_t *qids_dev, uint64_t nq,
+                                    const uint32_t *exclude_dev, const uint32_t *filter_dev, uint32_t stride_words, uint64_t k,
+                                    uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev, uint32_t *status_dev,
+                                    void *stream) const {
+    check(phnsw_search_exact_filtered_device(ix_, queries_dev, ldq, qids_dev, nq, exclude_dev, filter_dev, stride_words, k,
+                                             out_ids_dev, out_d_dev, out_len_dev, status_dev, stream));
+  }
+  // candidates of each of nbitmaps device bitmaps (phnsw_filter_count_device): what to choose the search call by
+  void filter_count_device(const uint32_t *filter_dev, uint32_t stride_words, uint64_t nbitmaps, uint32_t *out_count_dev,
+                           void *stream) const {
+    check(phnsw_filter_count_device(ix_, filter_dev, stride_words, nbitmaps, out_count_dev, stream));
+  }
   // tombstones (phnsw_index_set_filter_device): the default bitmap of the filtered calls; nullptr clears it
   void set_filter_device(const uint32_t *filter_dev) { check(phnsw_index_set_filter_device(ix_, filter_dev)); }
   // Hnsw::search_instrumented(v, sp) -> (results, index_distance)  lib.rs:667-673

@@ -12,6 +12,7 @@
 #include <stdexcept>
 #include <vector>
 
+#include "exact_slices.h"
 #include "phnsw_internal.h"
 
 static thread_local std::string g_err;
@@ -549,6 +550,7 @@ extern "C" void phnsw_index_destroy(phnsw_index *ix) {
   ph_workspace_free(ix->ws[0]);
   ph_workspace_free(ix->ws[1]);
   ph_host_stages_free(ix);
+  ph_exact_free(ix);
   ph_build_table_free(ix);
   if (ix->totals) hipFree(ix->totals);
   phnsw_store_destroy(ix->store);
@@ -980,6 +982,65 @@ extern "C" int phnsw_index_set_filter_device(phnsw_index *ix, const uint32_t *fi
   }
   ix->default_filter = filter_dev;
   return 0;
+} catch (...) { return ph_caught(); }
+
+// ---- exact top-k over the allow-list (filter_exact.hip): the call for SELECTIVE filters
+
+int ph_exact_check(const phnsw_index *ix, uint64_t k, const char *call) {
+  if (!ix || ix->layers.empty()) {
+    ph_set_error("%s: null index or index without layers", call);
+    return PHNSW_E_INVALID;
+  }
+  if (!ph_exact_k_valid(k)) {
+    ph_set_error("%s: k must be 1..1024 (got %llu)", call, (unsigned long long)k);
+    return PHNSW_E_INVALID;
+  }
+  if (ph_store_pq_shared(ix->store)) {  // as for the distance batch, whose arithmetic the scan runs
+    ph_set_error("%s: not supported over a shared-codebook PQ store; use its reconstruction store", call);
+    return PHNSW_E_UNSUPPORTED;
+  }
+  return 0;
+}
+
+extern "C" int phnsw_search_exact_filtered_device(const phnsw_index *ix, const float *queries_dev, uint32_t ldq,
+                                                  const uint32_t *qids_dev, uint64_t nq, const uint32_t *exclude_dev,
+                                                  const uint32_t *filter_dev, uint32_t filter_stride_words, uint64_t k,
+                                                  uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                                  uint32_t *status_dev, void *stream) try {
+  const char *const call = "phnsw_search_exact_filtered_device";
+  int rc = ph_exact_check(ix, k, call);
+  if (rc) return rc;
+  if (nq == 0) return 0;
+  if (((!queries_dev) == (!qids_dev)) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev || nq > 0xFFFFFFFFull ||
+      (queries_dev && (ldq < ix->store->ld || (ldq % 4) || ((uintptr_t)queries_dev % 16)))) {
+    ph_set_error("%s: invalid argument (queries or qids, exactly one; outputs; queries need ldq >= store ld, multiple of 4, "
+                 "16-byte base)", call);
+    return PHNSW_E_INVALID;
+  }
+  PhExactCall c = {};
+  rc = ph_filter_check(ix, filter_dev, filter_stride_words, 0u, call, &c.filter);
+  if (rc) return rc;
+  if (!c.filter.words) c.filter.words = ix->default_filter;  // phnsw_index_set_filter_device
+  c.queries = queries_dev, c.ldq = ldq, c.qids = qids_dev, c.exclude = exclude_dev, c.nq = nq, c.k = (uint32_t)k;
+  c.out_ids = out_ids_dev, c.out_d = out_d_dev, c.out_len = out_len_dev, c.status = status_dev;
+  c.stream = (hipStream_t)stream;
+  PH_HIP(hipSetDevice(ix->store->device));
+  return ph_exact_device(ix, c);
+} catch (...) { return ph_caught(); }
+
+extern "C" int phnsw_filter_count_device(const phnsw_index *ix, const uint32_t *filter_dev, uint32_t filter_stride_words,
+                                         uint64_t nbitmaps, uint32_t *out_count_dev, void *stream) try {
+  const char *const call = "phnsw_filter_count_device";
+  if (!ix || ix->layers.empty() || (!out_count_dev && nbitmaps)) {
+    ph_set_error("%s: null index, index without layers or null output", call);
+    return PHNSW_E_INVALID;
+  }
+  PhFilter f;
+  int rc = ph_filter_check(ix, filter_dev, filter_stride_words, 0u, call, &f);
+  if (rc) return rc;
+  if (!f.words) f.words = ix->default_filter;
+  PH_HIP(hipSetDevice(ix->store->device));
+  return ph_filter_count(ix, f, nbitmaps, out_count_dev, (hipStream_t)stream);
 } catch (...) { return ph_caught(); }
 
 // tests: the raw distance table of the last launch's dense top layers ([positions][stride] f32, the last chunk's) and

@@ -1,0 +1,354 @@
+// Exact top-k over an allow-list (phnsw_search_exact_filtered[_device], phnsw_filter_count_device): the answer to a
+// SELECTIVE filter, where the graph search -- a post-filter on each layer's queue -- returns about density *
+// number_of_candidates results and, at a density of 0.001, nothing.  No traversal: a wave walks its query's bitmap,
+// expands the set bits to VectorIds in id order, evaluates them 64 at a time with the very call the distance batch
+// makes (dist.batch of the store's policy, misc.hip: the bits are phnsw_distance_batch's by construction) and keeps a
+// running top-k of (distance, id) keys in LDS.
+//
+//   candidates of query q = { v : v < n, bit v of q's bitmap set, v != exclude[q], v a vector of the bottom layer }
+//   result                = the k candidates with the smallest (distance, id), ascending; len = min(k, candidates)
+//
+// The keys are distinct (the id is part of the key), so the k smallest are one set in one order: the result does not
+// depend on how the bitmap is cut into slices (exact_slices.h), nor on the order in which candidates arrive.
+//
+// Kernels of this file only: no existing kernel, and no translation unit that holds one, is touched
+// (profiles/filter_exact/).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+
+#include "exact_slices.h"
+#include "phnsw_device.h"
+
+struct PhExactArgs {
+  PhDistArgs dist;
+  const float *queries;  // [nq][ldq] or nullptr
+  uint32_t ldq;
+  const uint32_t *qids, *exclude;  // [nq] or nullptr
+  const uint32_t *filter;          // nullptr: every vector of the index
+  uint32_t filter_stride;          // words from one query's bitmap to the next, 0 = one for all
+  uint32_t nq, n, nwords, k, slices;
+  uint64_t passes;
+  // the index's bottom layer: a candidate is one of its vectors
+  uint32_t n_nodes;
+  const uint32_t *nodes, *vec2node;  // vec2node == nullptr: identity, the vectors are 0 .. n_nodes - 1
+  uint32_t pq_lds;                   // bytes of dynamic LDS in front of the scan's own: a PQ store's table (16-byte multiple)
+  uint64_t *scratch;                 // slices > 1: [nq][slices][k] keys, each list ascending, KEY_NONE padded
+  uint32_t *out_ids;                 // [nq][k]
+  float *out_d;
+  uint32_t *out_len, *status;  // [nq]
+};
+
+// VectorIds of the bottom layer lie below this: an identity layer holds 0 .. n_nodes - 1, any other layer's largest
+// vector is its last node (nodes ascend), and vec2node has an entry for every id up to that one
+__device__ __forceinline__ uint32_t ph_exact_id_limit(uint32_t n, uint32_t n_nodes, const uint32_t *nodes,
+                                                      const uint32_t *vec2node) {
+  if (n_nodes == 0) return 0u;
+  return min(n, vec2node ? nodes[n_nodes - 1u] + 1u : n_nodes);
+}
+
+// word `widx` of a bitmap reduced to candidates: bits at or past the limit cleared, then the bits of vectors the
+// bottom layer does not hold.  bitmap == nullptr: every bit set.  The one candidate test of the scan and of the count.
+__device__ __forceinline__ uint32_t ph_exact_word(const uint32_t *bitmap, uint32_t widx, uint32_t nwords, uint32_t nlim,
+                                                  const uint32_t *vec2node) {
+  if (widx >= nwords) return 0u;
+  const uint32_t first = widx * 32u;  // widx < nwords <= 2^26
+  if (first >= nlim) return 0u;
+  uint32_t w = bitmap ? bitmap[widx] : 0xFFFFFFFFu;
+  if (nlim - first < 32u) w &= (1u << (nlim - first)) - 1u;
+  if (vec2node)
+    for (uint32_t t = w; t; t &= t - 1u) {
+      const uint32_t b = (uint32_t)__ffs((int)t) - 1u;
+      if (vec2node[first + b] == PH_EMPTY32) w &= ~(1u << b);  // first + b < nlim
+    }
+  return w;
+}
+
+// partition_point over an ascending key list in LDS; len is wave-uniform, every lane may call it
+__device__ __forceinline__ uint32_t ph_keys_lower_bound(const uint64_t *keys, uint32_t len, uint64_t key) {
+  if (len == 0) return 0;
+  uint32_t base = 0, n = len;
+  while (n > 1) {
+    const uint32_t half = n >> 1;
+    base = keys[base + half - 1] < key ? base + half : base;
+    n -= half;
+  }
+  return base + (keys[base] < key ? 1u : 0u);
+}
+
+// The running top-k of one wave: an ascending list of at most k keys in LDS and a second list it is merged into.
+struct PhExactTopK {
+  uint64_t *cur, *nxt;  // [k] each
+  uint64_t *sv;         // [64]: a batch's survivors, ascending
+  uint32_t len, k;      // wave-uniform
+
+  // One key per lane (KEY_NONE: none).  A batch is first tested against the current k-th key with one ballot -- once
+  // the list is full most batches end there.  Survivors are rank-merged: a survivor lands at (entries of the list below
+  // it) + (survivors below it), a list entry moves up by the survivors below it; whatever lands at or past k is dropped.
+  // Returns whether the batch had a survivor.  Called by the whole wave in uniform control flow.
+  __device__ __forceinline__ bool insert(uint64_t key, uint32_t lane) {
+    const uint64_t kth = len == k ? cur[k - 1u] : KEY_NONE;
+    const bool surv = key < kth;
+    const uint64_t sm = __ballot(surv);
+    if (!sm) return false;
+    const uint32_t ns = (uint32_t)__popcll(sm);
+    uint32_t rank = 0;
+    for (uint64_t t = sm; t; t &= t - 1ull) rank += rl64(key, __ffsll((unsigned long long)t) - 1) < key ? 1u : 0u;
+    const uint32_t below = ph_keys_lower_bound(cur, len, key);
+    if (surv) {
+      sv[rank] = key;  // rank < ns <= 64
+      if (below + rank < k) nxt[below + rank] = key;
+    }
+    __syncthreads();
+    for (uint32_t base = 0; base < len; base += 64u) {
+      const uint32_t i = base + lane;
+      const uint64_t e = i < len ? cur[i] : KEY_NONE;
+      const uint32_t to = i + ph_keys_lower_bound(sv, ns, e);
+      if (i < len && to < k) nxt[to] = e;
+    }
+    __syncthreads();
+    uint64_t *t = cur;
+    cur = nxt;
+    nxt = t;
+    len = min(k, len + ns);
+    return true;
+  }
+};
+
+// row q of the result from an ascending key list
+__device__ __forceinline__ void ph_exact_write_row(const PhExactArgs &a, uint32_t q, const uint64_t *keys, uint32_t len,
+                                                   bool bad_query, uint32_t lane) {
+  for (uint32_t i = lane; i < a.k; i += 64u) {
+    const uint64_t key = i < len ? keys[i] : KEY_NONE;
+    a.out_ids[(uint64_t)q * a.k + i] = key == KEY_NONE ? PH_EMPTY32 : ((uint32_t)key & IDM);
+    a.out_d[(uint64_t)q * a.k + i] = key == KEY_NONE ? PH_FMAX : unfkey((uint32_t)(key >> 32));
+  }
+  if (lane == 0) {
+    a.out_len[q] = len;
+    a.status[q] = bad_query ? ST_MISSING : ST_OK;  // a Stored query id at or past n (device form; the host form checks)
+  }
+}
+
+__device__ __forceinline__ uint32_t ph_wave_inclusive_sum(uint32_t v, uint32_t lane) {
+#pragma unroll
+  for (uint32_t d = 1; d < 64u; d <<= 1) {
+    const uint32_t t = __shfl_up(v, d);
+    if (lane >= d) v += t;
+  }
+  return v;
+}
+
+// One wave64 per (query, slice of the bitmap); work item = slice * nq + q (slice-major, query-minor): the waves resident
+// together walk the same part of the id range, so with a shared bitmap they read the same rows and L2 can serve them.
+template <class Dist>
+__global__ __launch_bounds__(64) void ph_exact_scan_kernel(PhExactArgs a) {
+  extern __shared__ float exact_lds[];
+  const uint32_t lane = threadIdx.x;
+  uint64_t *const keys = (uint64_t *)((char *)exact_lds + a.pq_lds);
+  uint32_t *const stage = (uint32_t *)(keys + 2u * a.k + 64u);  // [PH_EXACT_PASS_IDS]
+  const uint32_t nlim = ph_exact_id_limit(a.n, a.n_nodes, a.nodes, a.vec2node);
+  const uint64_t items = (uint64_t)a.nq * a.slices;
+  for (uint64_t item = blockIdx.x; item < items; item += gridDim.x) {
+    const uint32_t q = (uint32_t)(item % a.nq), slice = (uint32_t)(item / a.nq);
+    __syncthreads();  // the previous item's LDS (table, lists) is done with
+    const bool bad_query = !a.queries && a.qids[q] >= a.n;
+    Dist dist;
+    if (a.queries)
+      dist.prepare_raw(a.dist, a.queries + (uint64_t)q * a.ldq, exact_lds, lane);
+    else if (!bad_query)
+      dist.prepare_stored(a.dist, a.qids[q], exact_lds, lane);
+    PhExactTopK top;
+    top.cur = keys, top.nxt = keys + a.k, top.sv = keys + 2u * a.k, top.len = 0, top.k = a.k;
+    const uint32_t *const bitmap = a.filter ? a.filter + (uint64_t)q * a.filter_stride : nullptr;
+    const uint32_t ex = a.exclude ? a.exclude[q] : PH_EMPTY32;
+    uint64_t p0, p1;
+    ph_exact_slice_range(slice, a.slices, a.passes, &p0, &p1);
+    if (bad_query) p1 = p0;
+    for (uint64_t p = p0; p < p1; p++) {
+      const uint32_t widx = (uint32_t)(p * PH_EXACT_PASS_WORDS) + lane;  // p < passes <= 2^20
+      uint32_t w = ph_exact_word(bitmap, widx, a.nwords, nlim, a.vec2node);
+      if (ex != PH_EMPTY32 && (ex >> 5) == widx) w &= ~(1u << (ex & 31u));
+      if (!__ballot(w != 0u)) continue;
+      // set bits -> ids in id order: lane l's ids follow those of the lanes below it
+      const uint32_t cnt = (uint32_t)__popc(w);
+      const uint32_t incl = ph_wave_inclusive_sum(cnt, lane);
+      const uint32_t total = rl32(incl, 63);  // <= PH_EXACT_PASS_IDS
+      uint32_t o = incl - cnt;
+      for (uint32_t t = w; t; t &= t - 1u) stage[o++] = widx * 32u + (uint32_t)__ffs((int)t) - 1u;  // o < incl <= total
+      __syncthreads();
+      for (uint32_t b = 0; b < total; b += 64u) {
+        const bool ok = b + lane < total;
+        const uint32_t id = ok ? stage[b + lane] : 0u;  // id < nlim <= n: a row of the store
+        const float d = dist.batch(a.dist, __ballot(ok), id, lane);
+        top.insert(ok ? mkkey(d, id) : KEY_NONE, lane);
+      }
+      __syncthreads();  // the next pass overwrites the staged ids
+    }
+    if (a.slices == 1u) {
+      ph_exact_write_row(a, q, top.cur, top.len, bad_query, lane);
+    } else {
+      uint64_t *const out = a.scratch + ((uint64_t)q * a.slices + slice) * a.k;
+      for (uint32_t i = lane; i < a.k; i += 64u) out[i] = i < top.len ? top.cur[i] : KEY_NONE;
+    }
+  }
+}
+
+// One wave per query: the slices' ascending lists merged through the same running top-k.  A list is fed 64 keys at a
+// time and left at the first batch without a survivor -- whatever follows in it is larger still.
+__global__ __launch_bounds__(64) void ph_exact_merge_kernel(PhExactArgs a) {
+  extern __shared__ float exact_lds[];
+  const uint32_t lane = threadIdx.x;
+  uint64_t *const keys = (uint64_t *)exact_lds;
+  for (uint32_t q = blockIdx.x; q < a.nq; q += gridDim.x) {
+    __syncthreads();
+    PhExactTopK top;
+    top.cur = keys, top.nxt = keys + a.k, top.sv = keys + 2u * a.k, top.len = 0, top.k = a.k;
+    for (uint32_t s = 0; s < a.slices; s++) {
+      const uint64_t *const list = a.scratch + ((uint64_t)q * a.slices + s) * a.k;
+      for (uint32_t b = 0; b < a.k; b += 64u)
+        if (!top.insert(b + lane < a.k ? list[b + lane] : KEY_NONE, lane)) break;
+    }
+    ph_exact_write_row(a, q, top.cur, top.len, !a.queries && a.qids[q] >= a.n, lane);
+  }
+}
+
+// candidates of each bitmap (no exclude): one block per bitmap, a popcount over the scan's candidate test
+__global__ __launch_bounds__(256) void ph_filter_count_kernel(const uint32_t *filter, uint32_t stride, uint64_t nbitmaps,
+                                                              uint32_t n, uint32_t nwords, uint32_t n_nodes,
+                                                              const uint32_t *nodes, const uint32_t *vec2node,
+                                                              uint32_t *out_count) {
+  __shared__ uint32_t part[4];
+  const uint32_t nlim = ph_exact_id_limit(n, n_nodes, nodes, vec2node);
+  for (uint64_t b = blockIdx.x; b < nbitmaps; b += gridDim.x) {
+    const uint32_t *const bitmap = filter ? filter + b * stride : nullptr;
+    uint32_t c = 0;
+    for (uint32_t widx = threadIdx.x; widx < nwords; widx += 256u)
+      c += (uint32_t)__popc(ph_exact_word(bitmap, widx, nwords, nlim, vec2node));
+#pragma unroll
+    for (int sft = 32; sft >= 1; sft >>= 1) c += __shfl_xor(c, sft);
+    __syncthreads();  // part[] of the previous bitmap has been read
+    if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) out_count[b] = part[0] + part[1] + part[2] + part[3];
+  }
+}
+
+// ------------------------------------------------------------------ launchers
+
+typedef void (*PhExactFn)(PhExactArgs);
+template <template <int, int> class D>
+static PhExactFn exact_rows_fn(uint32_t nv4) {
+  switch (ph_chunk_count(nv4)) {
+    case 1: return ph_exact_scan_kernel<D<1, 4>>;
+    case 3: return ph_exact_scan_kernel<D<3, 4>>;
+    case 6: return ph_exact_scan_kernel<D<6, 4>>;
+    default: return nullptr;
+  }
+}
+static PhExactFn exact_fn(const phnsw_store *s) {
+  switch (s->kind) {
+    case PH_ROWS_PQ: return ph_exact_scan_kernel<DistPQ>;
+    case PH_ROWS_F16: return exact_rows_fn<DistF16>(s->ld / 4);
+    case PH_ROWS_I8: return exact_rows_fn<DistI8>(s->ld / 4);
+    case PH_ROWS_I8Q: return exact_rows_fn<DistI8Q>(s->ld / 4);
+    default: return exact_rows_fn<DistF32>(s->ld / 4);
+  }
+}
+
+static const size_t PH_EXACT_LDS_MAX = 160 * 1024;  // a workgroup's LDS on gfx950
+
+// the bottom layer of the index into the argument block
+static void exact_bottom_layer(const phnsw_index *ix, uint32_t *n_nodes, const uint32_t **nodes, const uint32_t **vec2node) {
+  const PhLayerHost &B = ix->layers.back();
+  *n_nodes = B.n_nodes;
+  *nodes = B.nodes;
+  *vec2node = B.identity ? nullptr : B.vec2node;
+}
+
+void ph_exact_free(phnsw_index *ix) {
+  for (PhExactScratch &x : ix->exact) {
+    if (x.done) {
+      hipEventSynchronize(x.done);
+      hipEventDestroy(x.done);
+    }
+    if (x.keys) ph_pool_free(x.keys);
+    x = PhExactScratch();
+  }
+}
+
+int ph_exact_device(const phnsw_index *ix, const PhExactCall &c) {
+  phnsw_index *mix = const_cast<phnsw_index *>(ix);
+  const phnsw_store *s = ix->store;
+  if (c.nq == 0) return 0;
+  const PhExactFn fn = exact_fn(s);
+  if (!fn) return ph_dim_unsupported(s->dim);
+  const size_t pq_lds = (ph_pq_lds_bytes(s) + 15u) & ~(size_t)15u, own_lds = (size_t)ph_exact_own_lds(c.k);
+  const size_t lds = pq_lds + own_lds;
+  if (lds > PH_EXACT_LDS_MAX) {
+    ph_set_error("exact filtered search: the PQ tables (%zu bytes) plus the scan's own %zu bytes of LDS at k = %u do not fit a "
+                 "workgroup's %zu bytes",
+                 pq_lds, own_lds, c.k, PH_EXACT_LDS_MAX);
+    return PHNSW_E_UNSUPPORTED;
+  }
+  if (lds > 48 * 1024)
+    PH_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  // waves of the scan the device holds at once
+  int per_cu = 0, cus = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)fn, 64, lds) != hipSuccess || per_cu <= 0) per_cu = 1;
+  PH_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device));
+  const uint64_t resident = (uint64_t)per_cu * (uint64_t)std::max(cus, 1);
+  const char *e = getenv("PHNSW_EXACT_SLICES");  // tests and tuning: forces the slice count, changes no result
+  PhExactArgs a = {};
+  a.dist = ph_dist_args(s);
+  a.queries = c.queries, a.ldq = c.ldq, a.qids = c.qids, a.exclude = c.exclude;
+  a.filter = c.filter.words, a.filter_stride = c.filter.words ? c.filter.stride : 0u;
+  a.nq = (uint32_t)c.nq, a.n = (uint32_t)s->n, a.nwords = (uint32_t)ph_exact_words(s->n), a.k = c.k;
+  a.passes = ph_exact_passes(s->n);
+  a.slices = ph_exact_slice_count(c.nq, resident, a.passes, e ? atoll(e) : 0);
+  exact_bottom_layer(ix, &a.n_nodes, &a.nodes, &a.vec2node);
+  a.pq_lds = (uint32_t)pq_lds;
+  a.out_ids = c.out_ids, a.out_d = c.out_d, a.out_len = c.out_len, a.status = c.status;
+  const uint64_t items = c.nq * (uint64_t)a.slices;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(items, 1u << 20);  // the kernels stride over what is left
+  if (a.slices == 1u) {
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(64), lds, c.stream, a);
+    PH_HIP(hipGetLastError());
+    return 0;
+  }
+  // per-slice lists: one of the index's two scratch blocks, behind its previous user
+  std::lock_guard<std::mutex> g(mix->exact_mutex);
+  PhExactScratch &x = mix->exact[mix->exact_next++ & 1u];
+  const size_t bytes = (size_t)items * c.k * 8u;
+  if (!x.done) PH_HIP(hipEventCreateWithFlags(&x.done, hipEventDisableTiming));
+  if (x.bytes < bytes) {
+    if (x.keys) {
+      PH_HIP(hipEventSynchronize(x.done));  // the block goes back to the pool: nothing may still write it
+      ph_pool_free(x.keys);
+      x.keys = nullptr, x.bytes = 0;
+    }
+    PH_HIP(ph_pool_alloc((void **)&x.keys, bytes));
+    x.bytes = bytes;
+  } else {
+    PH_HIP(hipStreamWaitEvent(c.stream, x.done, 0));
+  }
+  a.scratch = x.keys;
+  hipLaunchKernelGGL(fn, dim3(grid), dim3(64), lds, c.stream, a);
+  hipLaunchKernelGGL(ph_exact_merge_kernel, dim3((uint32_t)std::min<uint64_t>(c.nq, 1u << 20)), dim3(64), own_lds, c.stream, a);
+  PH_HIP(hipGetLastError());
+  PH_HIP(hipEventRecord(x.done, c.stream));
+  return 0;
+}
+
+int ph_filter_count(const phnsw_index *ix, const PhFilter &f, uint64_t nbitmaps, uint32_t *out_count_dev, hipStream_t stream) {
+  if (nbitmaps == 0) return 0;
+  const phnsw_store *s = ix->store;
+  uint32_t n_nodes;
+  const uint32_t *nodes, *vec2node;
+  exact_bottom_layer(ix, &n_nodes, &nodes, &vec2node);
+  hipLaunchKernelGGL(ph_filter_count_kernel, dim3((uint32_t)std::min<uint64_t>(nbitmaps, 1u << 20)), dim3(256), 0, stream,
+                     f.words, f.words ? f.stride : 0u, nbitmaps, (uint32_t)s->n, (uint32_t)ph_exact_words(s->n), n_nodes, nodes,
+                     vec2node, out_count_dev);
+  PH_HIP(hipGetLastError());
+  return 0;
+}

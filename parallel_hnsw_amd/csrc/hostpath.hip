@@ -231,13 +231,13 @@ void ph_host_stages_free(phnsw_index *ix) {
 }
 
 int ph_search_host(const phnsw_index *ix, const PhHostSearch &h) {
-  PH_TRY(ph_check_sp(ix, h.sp));
+  if (!h.exact) PH_TRY(ph_check_sp(ix, h.sp));  // (the exact scan has no search parameters: ph_exact_check ran)
   const float *const queries = h.queries;
   const uint64_t *const qids = h.qids, *const exclude = h.exclude;
   const uint64_t nq = h.nq, out_k = h.out_k;
   uint64_t *const out_ids = h.out_ids, *const out_len = h.out_len, *const out_stats = h.out_stats, *const out_index = h.out_index;
   float *const out_d = h.out_d;
-  const uint32_t ef = (uint32_t)h.sp->number_of_candidates;
+  const uint32_t ef = h.exact ? (uint32_t)h.out_k : (uint32_t)h.sp->number_of_candidates;  // entries of a staged result row
   if ((!queries && !qids && !h.knn_mode) || !out_ids || !out_d || !out_len || nq > 0xFFFFFFFFull || out_k > ef) {
     ph_set_error("search: invalid argument (queries or ids, outputs, k <= number_of_candidates)");
     return PHNSW_E_INVALID;
@@ -354,6 +354,21 @@ int ph_search_host(const phnsw_index *ix, const PhHostSearch &h) {
       PH_STAGE_HIP(hipMemcpyAsync(sl.filt, filter.words + first * filter.stride, bytes, hipMemcpyHostToDevice, sl.stream));
       fdev.words = sl.filt;
       fdev.stride = filter.stride;
+    }
+    if (h.exact) {  // the scan over the allow-list (filter_exact.hip) on the same staging: rows of k entries
+      PhExactCall x = {};
+      if (queries) x.queries = sl.q;
+      if (qids) x.qids = sl.small;
+      if (exclude) x.exclude = sl.small + N;
+      if (filtered) x.filter = fdev;
+      x.ldq = s->ld, x.nq = cnt, x.k = k;
+      x.out_ids = sl.ids, x.out_d = sl.d, x.out_len = sl.small + 2 * N, x.status = sl.small + 3 * N;
+      x.stream = sl.stream;
+      PH_TRY(ph_exact_device(ix, x));
+      sl.c0 = first;
+      sl.cnt = cnt;
+      sl.busy = true;
+      return 0;
     }
     PhSearchCall c = {};
     if (queries) c.queries = sl.q;
@@ -505,6 +520,24 @@ extern "C" int phnsw_search_batch_filtered(const phnsw_index *ix, const float *q
   PhHostSearch h = host_call(queries, qids, nq, sp, out_ids, out_d, out_len);
   h.upto = upto_layers, h.exclude = exclude, h.out_k = k, h.out_stats = out_stats;
   PH_TRY(ph_filter_check(ix, filter, filter_stride_words, flags, "phnsw_search_batch_filtered", &h.filter));
+  h.filter_on_device = !h.filter.words && ix->default_filter;  // phnsw_index_set_filter_device: device words
+  if (h.filter_on_device) h.filter.words = ix->default_filter;
+  return ph_search_host(ix, h);
+} catch (...) { return ph_caught(); }
+
+// the exact top-k of the allowed vectors, by a scan instead of the graph search: the call for selective filters
+extern "C" int phnsw_search_exact_filtered(const phnsw_index *ix, const float *queries, const uint64_t *qids, uint64_t nq,
+                                           const uint64_t *exclude, const uint32_t *filter, uint32_t filter_stride_words,
+                                           uint64_t k, uint64_t *out_ids, float *out_d, uint64_t *out_len) try {
+  PH_TRY(ph_exact_check(ix, k, "phnsw_search_exact_filtered"));
+  if (nq == 0) return 0;
+  if ((!queries) == (!qids)) {
+    ph_set_error("phnsw_search_exact_filtered: pass queries or qids (exactly one)");
+    return PHNSW_E_INVALID;
+  }
+  PhHostSearch h = host_call(queries, qids, nq, nullptr, out_ids, out_d, out_len);
+  h.exclude = exclude, h.out_k = k, h.exact = true;
+  PH_TRY(ph_filter_check(ix, filter, filter_stride_words, 0u, "phnsw_search_exact_filtered", &h.filter));
   h.filter_on_device = !h.filter.words && ix->default_filter;  // phnsw_index_set_filter_device: device words
   if (h.filter_on_device) h.filter.words = ix->default_filter;
   return ph_search_host(ix, h);

@@ -19,6 +19,10 @@ __device__ __forceinline__ uint32_t fkey(float d) {
   uint32_t u = __float_as_uint(d);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
+// fkey's inverse: the distance a key's upper word was made from (bit for bit; a -0.0 went in as +0.0)
+__device__ __forceinline__ float unfkey(uint32_t fk) {
+  return __uint_as_float((fk & 0x80000000u) ? (fk ^ 0x80000000u) : ~fk);
+}
 // total order of the reference: (OrderedFloat(d), id) ascending (src/lib.rs:206)
 __device__ __forceinline__ uint64_t mkkey(float d, uint32_t id) {
   return ((uint64_t)fkey(d) << 32) | (uint64_t)(id & IDM);

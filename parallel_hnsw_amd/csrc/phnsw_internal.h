@@ -224,6 +224,15 @@ struct PhFilter {
   uint32_t stride, flags;
 };
 
+// per-slice results of an exact scan that was cut into slices (filter_exact.hip): [nq][slices][k] keys from
+// ph_pool_alloc, kept with the index.  Two of them, used alternately like the search workspaces, so that scans on two
+// streams may overlap; `done` closes the last launch that used one, and the next user's stream waits for it.
+struct PhExactScratch {
+  uint64_t *keys = nullptr;
+  size_t bytes = 0;
+  hipEvent_t done = nullptr;
+};
+
 struct PhPendingLayer;
 struct PhHostStage;  // hostpath.hip: persistent staging of the host-pointer search entry points
 struct phnsw_index {
@@ -249,6 +258,9 @@ struct phnsw_index {
   const uint32_t *dbg_order = nullptr;  // experiment hook
   const uint32_t *default_filter = nullptr;  // phnsw_index_set_filter_device: the caller's shared bitmap, filtered calls only
   uint64_t dbg_order_n = 0;
+  std::mutex exact_mutex;  // filter_exact.hip
+  PhExactScratch exact[2];
+  uint32_t exact_next = 0;
 };
 
 // ---- kernel argument block for the batched greedy search ----
@@ -404,8 +416,29 @@ struct PhHostSearch {
   uint64_t *out_stats, *out_index;  // [nq][2], [nq] or nullptr
   PhFilter filter;                  // host words; words == nullptr: none
   bool filter_on_device;            // filter.words is a shared bitmap in device memory (phnsw_index_set_filter_device)
+  bool exact;  // the exact scan over the allow-list instead of the graph search (ph_exact_device): sp unused, out_k = k >= 1
 };
 int ph_search_host(const phnsw_index *ix, const PhHostSearch &h);
+// The request of one exact top-k scan over an allow-list (ph_exact_device, filter_exact.hip).  Device pointers of the
+// caller, enqueued on `stream`; rows of k entries, PH_EMPTY32 / PH_FMAX padded.
+struct PhExactCall {
+  const float *queries;  // [nq][ldq], or nullptr: Stored queries (qids)
+  uint32_t ldq;
+  const uint32_t *qids, *exclude;  // [nq] or nullptr
+  uint64_t nq;
+  PhFilter filter;  // words == nullptr: every vector of the index
+  uint32_t k;       // 1..PH_EXACT_KMAX
+  uint32_t *out_ids;  // [nq][k]
+  float *out_d;
+  uint32_t *out_len, *status;  // [nq]
+  hipStream_t stream;
+};
+int ph_exact_device(const phnsw_index *ix, const PhExactCall &c);
+int ph_filter_count(const phnsw_index *ix, const PhFilter &f, uint64_t nbitmaps, uint32_t *out_count_dev, hipStream_t stream);
+void ph_exact_free(phnsw_index *ix);
+// the argument checks the exact entry points share (api.hip): index with layers, 1 <= k <= 1024, a store kind the
+// distance batch accepts
+int ph_exact_check(const phnsw_index *ix, uint64_t k, const char *call);
 // locality schedule helpers (group.hip / api.hip)
 #define PH_ORDER_MIN 16384u  // shorter query lists run in natural order
 #define PH_POS_MIN 256u     // smaller layers carry no cells (their node id is the key)

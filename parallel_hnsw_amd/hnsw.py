@@ -641,7 +641,8 @@ class Hnsw:
         (lib.rs:250-277) as a bitmap.  allow: a bool array [n] (one filter for all queries) or [nq, n] (one per query), or
         the packed u32 words themselves ([ceil(n/32)] or [nq, stride]); None = the default of set_filter, else no
         filter.  A post-filter on each layer's queue: about density * number_of_candidates results come back, so
-        selective filters want a larger number_of_candidates.  The entry vector may be returned although it is
+        selective filters want a larger number_of_candidates (or search_exact_filtered, which scans the allowed rows
+        instead; filter_count tells how many there are).  The entry vector may be returned although it is
         disallowed (as the reference returns it although excluded); strict=True removes it.
         Returns (ids[nq, k or ef] u64, d f32, len[nq]) and the stats with stats=True"""
         sp = sp or SearchParameters()
@@ -682,6 +683,66 @@ class Hnsw:
         alive by the caller, becomes the filter of every filtered call that passes none; 0 clears it.  search_batch and
         the other unfiltered calls never see it.  Not while searches on the index are in flight"""
         check(lib().phnsw_index_set_filter_device(self._h, C.c_void_p(allow_dev or None)))
+
+    def search_exact_filtered(self, queries=None, qids=None, allow=None, exclude=None, k=10):
+        """the exact top-k of the allowed vectors (phnsw_search_exact_filtered): a scan of the allow-list instead of the
+        graph search -- the call for selective filters, where search_batch_filtered returns about density *
+        number_of_candidates results.  Candidates: ids below n whose bit is set (allow as for search_batch_filtered;
+        None = the default of set_filter, else every vector), that are not exclude[q] and that the index holds.  A
+        disallowed id is never returned.  1 <= k <= 1024.  filter_count(allow) tells how many candidates there are.
+        Returns (ids[nq, k] u64, d[nq, k] f32, len[nq]): ascending (distance, id), the distance bits of compare_vec,
+        padded with EMPTY / f32::MAX"""
+        q = qi = None
+        if queries is not None:
+            q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+            assert q.shape[1] == self.store.dim
+            nq = q.shape[0]
+        else:
+            qi = np.ascontiguousarray(qids, dtype=np.uint64)
+            nq = len(qi)
+        words, stride = pack_allow(allow, self.store.n, nq)
+        w = max(int(k), 0)
+        ids = np.empty((nq, w), dtype=np.uint64)
+        d = np.empty((nq, w), dtype=np.float32)
+        ln = np.zeros(nq, dtype=np.uint64)
+        ex = None if exclude is None else np.ascontiguousarray(exclude, dtype=np.uint64)
+        check(lib().phnsw_search_exact_filtered(self._h, _p(q), _p(qi), nq, _p(ex), _p(words), stride, int(k), _p(ids), _p(d),
+                                                _p(ln)))
+        return ids, d, ln
+
+    def search_exact_filtered_device(self, nq, k, out_ids, out_d, out_len, status, queries=0, ldq=0, qids=0, exclude=0,
+                                     allow=0, allow_stride=0, stream=0):
+        """zero-copy form (phnsw_search_exact_filtered_device): device pointers as integers, u32 ids [nq, k] padded with
+        0xFFFFFFFF, enqueued on `stream`; allow = one packed bitmap (allow_stride 0) or nq bitmaps allow_stride words
+        apart, 0 = the default of set_filter"""
+        check(lib().phnsw_search_exact_filtered_device(
+            self._h, C.c_void_p(queries or None), ldq, C.c_void_p(qids or None), nq, C.c_void_p(exclude or None),
+            C.c_void_p(allow or None), int(allow_stride), int(k), C.c_void_p(out_ids), C.c_void_p(out_d), C.c_void_p(out_len),
+            C.c_void_p(status), C.c_void_p(stream or None)))
+
+    def filter_count_device(self, nbitmaps, out_count, allow=0, allow_stride=0, stream=0):
+        """phnsw_filter_count_device: the number of candidates of each of nbitmaps device bitmaps into out_count (u32
+        [nbitmaps], a device pointer)"""
+        check(lib().phnsw_filter_count_device(self._h, C.c_void_p(allow or None), int(allow_stride), int(nbitmaps),
+                                              C.c_void_p(out_count), C.c_void_p(stream or None)))
+
+    def filter_count(self, allow=None):
+        """how many candidates search_exact_filtered would choose among: allowed ids below n that the index holds (no
+        exclude).  allow: a bool mask [n] or [nq, n] or packed words, None = the default of set_filter, else every
+        vector of the index.  Host convenience over filter_count_device (needs torch for the device buffers); returns
+        an int for one bitmap, a u32 array [nq] for one per query.  What to choose the search call by"""
+        import torch
+        a = None if allow is None else np.asarray(allow)
+        nb = a.shape[0] if a is not None and a.ndim == 2 else 1
+        words, stride = pack_allow(a, self.store.n, nb)
+        dev = torch.device("cuda", getattr(self.store, "device", 0))
+        wd = None if words is None else torch.from_numpy(words.view(np.int32)).to(dev)
+        out = torch.zeros(nb, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.filter_count_device(nb, out.data_ptr(), allow=0 if wd is None else wd.data_ptr(), allow_stride=stride)
+        torch.cuda.synchronize(dev)
+        counts = out.cpu().numpy().view(np.uint32)
+        return counts if a is not None and a.ndim == 2 else int(counts[0])
 
     def search_batch_reranked(self, full, queries, sp=None, k=10):
         """an index over an F16Store, I8Store or I8QStore: search it, recompute every result's distance on the f32 store

@@ -426,6 +426,62 @@ impl GpuHnsw {
         check(sys::phnsw_index_set_filter_device(self.ix, filter_dev));
     }
 
+    /// the exact `k` nearest among the VectorIds `include` accepts (`phnsw_search_exact_filtered`): the allowed rows are
+    /// scanned instead of the graph walked, so the recall is 1 -- the call for selective filters, where
+    /// `search_many_filtered` returns about density * number_of_candidates results.  Only vectors of the index are
+    /// candidates, a rejected id is never returned, results ascend by (distance, id).  Panics unless 1 <= k <= 1024
+    pub fn search_many_exact_filtered<F: Fn(VectorId) -> bool>(&self, queries: &[Vec<f32>], k: usize, include: F)
+                                                               -> Vec<Vec<(VectorId, f32)>> {
+        assert!((1..=1024).contains(&k), "search_many_exact_filtered: k must be 1..1024");
+        let nq = queries.len();
+        let mut n64 = 0u64;
+        check(unsafe {
+            sys::phnsw_store_info(self.comparator.store.0, &mut n64, std::ptr::null_mut(), std::ptr::null_mut(),
+                                  std::ptr::null_mut(), std::ptr::null_mut())
+        });
+        let n = n64 as usize;
+        let mut words = vec![0u32; (n + 31) / 32];
+        for v in 0..n {
+            if include(VectorId(v)) {
+                words[v >> 5] |= 1u32 << (v & 31);
+            }
+        }
+        let mut q: Vec<f32> = Vec::with_capacity(nq * queries.first().map_or(0, |x| x.len()));
+        for x in queries {
+            q.extend_from_slice(x);
+        }
+        let (mut ids, mut d, mut len) = (vec![0u64; nq * k], vec![0f32; nq * k], vec![0u64; nq]);
+        check(unsafe {
+            sys::phnsw_search_exact_filtered(self.ix, q.as_ptr(), std::ptr::null(), nq as u64, std::ptr::null(), words.as_ptr(),
+                                             0, k as u64, ids.as_mut_ptr(), d.as_mut_ptr(), len.as_mut_ptr())
+        });
+        (0..nq).map(|i| (0..len[i] as usize).map(|j| (VectorId(ids[i * k + j] as usize), d[i * k + j])).collect()).collect()
+    }
+
+    /// zero-copy form (`phnsw_search_exact_filtered_device`): u32 ids `[nq][k]`, enqueued on `stream`
+    ///
+    /// # Safety
+    /// the pointers must be valid device allocations of the sizes `phnsw.h` documents for the call
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn search_exact_filtered_device(&self, queries_dev: *const f32, ldq: u32, qids_dev: *const u32, nq: u64,
+                                               exclude_dev: *const u32, filter_dev: *const u32, filter_stride_words: u32,
+                                               k: u64, out_ids_dev: *mut u32, out_d_dev: *mut f32, out_len_dev: *mut u32,
+                                               status_dev: *mut u32, stream: *mut c_void) {
+        check(sys::phnsw_search_exact_filtered_device(self.ix, queries_dev, ldq, qids_dev, nq, exclude_dev, filter_dev,
+                                                      filter_stride_words, k, out_ids_dev, out_d_dev, out_len_dev, status_dev,
+                                                      stream));
+    }
+
+    /// candidates of each of `nbitmaps` device bitmaps (`phnsw_filter_count_device`): what to choose between
+    /// `search_many_filtered` and `search_many_exact_filtered` by
+    ///
+    /// # Safety
+    /// `filter_dev` (or null: the default filter) and `out_count_dev` (`nbitmaps` u32) must be valid device allocations
+    pub unsafe fn filter_count_device(&self, filter_dev: *const u32, filter_stride_words: u32, nbitmaps: u64,
+                                      out_count_dev: *mut u32, stream: *mut c_void) {
+        check(sys::phnsw_filter_count_device(self.ix, filter_dev, filter_stride_words, nbitmaps, out_count_dev, stream));
+    }
+
     /// an index over a `to_f16()` comparator: search it, recompute every result's distance on the f32 comparator
     /// `full`, sort by (distance, id), keep the best `k` (`phnsw_f16_search_batch`)
     pub fn search_many_reranked(&self, full: &GpuComparator, queries: &[Vec<f32>], sp: SearchParameters, k: usize)

@@ -238,6 +238,17 @@ extern "C" {
                                               out_d_dev: *mut c_float, out_len_dev: *mut u32, out_stats_dev: *mut u32,
                                               status_dev: *mut u32, stream: *mut c_void) -> c_int;
     pub fn phnsw_index_set_filter_device(ix: *mut phnsw_index, filter_dev: *const u32) -> c_int;
+    // exact top-k over the allow-list (a scan, no traversal): the call for selective filters, and the candidate count
+    pub fn phnsw_search_exact_filtered(ix: *const phnsw_index, queries: *const c_float, qids: *const u64, nq: u64,
+                                       exclude: *const u64, filter: *const u32, filter_stride_words: u32, k: u64,
+                                       out_ids: *mut u64, out_d: *mut c_float, out_len: *mut u64) -> c_int;
+    pub fn phnsw_search_exact_filtered_device(ix: *const phnsw_index, queries_dev: *const c_float, ldq: u32,
+                                              qids_dev: *const u32, nq: u64, exclude_dev: *const u32,
+                                              filter_dev: *const u32, filter_stride_words: u32, k: u64,
+                                              out_ids_dev: *mut u32, out_d_dev: *mut c_float, out_len_dev: *mut u32,
+                                              status_dev: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn phnsw_filter_count_device(ix: *const phnsw_index, filter_dev: *const u32, filter_stride_words: u32,
+                                     nbitmaps: u64, out_count_dev: *mut u32, stream: *mut c_void) -> c_int;
     pub fn phnsw_index_counters(ix: *const phnsw_index, n_dist: *mut u64, n_hops: *mut u64) -> c_int;
     pub fn phnsw_last_search_kernel_ms(ix: *const phnsw_index, ms: *mut c_float) -> c_int;
     pub fn phnsw_last_search_dispatches(ix: *const phnsw_index, cap: u32, count: *mut u32, ms: *mut c_float,
