@@ -258,7 +258,7 @@ int phnsw_index_set_filter_device(phnsw_index *ix, const uint32_t *filter_dev);
  * number of candidates to choose by.  Guidance (measured on 1M x 768 f32 rows, 10 000-query batches, k = 10;
  * profiles/filter_exact/README.md): the scan is the faster call below roughly 13 000 candidates per query with a shared
  * bitmap and about 10 000 with per-query bitmaps, and the only one that returns k results once density * 1024 < k.
- * No existing call switches by itself. */
+ * phnsw_search_filtered_auto (below) makes this choice per query. */
 int phnsw_search_exact_filtered(const phnsw_index *ix, const float *queries, const uint64_t *qids, uint64_t nq,
                                 const uint64_t *exclude, const uint32_t *filter, uint32_t filter_stride_words,
                                 uint64_t k, uint64_t *out_ids, float *out_d, uint64_t *out_len);
@@ -275,6 +275,55 @@ int phnsw_search_exact_filtered_device(const phnsw_index *ix, const float *queri
  * else every vector of the index.  out_count_dev [nbitmaps] u32, device memory; enqueued on `stream`. */
 int phnsw_filter_count_device(const phnsw_index *ix, const uint32_t *filter_dev, uint32_t filter_stride_words,
                               uint64_t nbitmaps, uint32_t *out_count_dev, void *stream);
+/* ---- one filtered call that picks scan or graph walk per query, and rescans what the walk left short.  For batches
+ * whose bitmaps differ widely (tenants, ACLs, tombstones plus a predicate): the caller neither counts nor splits.
+ * Candidates: exactly those of phnsw_search_exact_filtered -- v < n, its bit set in q's bitmap, v != exclude[q], v a
+ * vector of the index's bottom layer.  Bitmap layout, stride rule, the default filter (filter NULL) and "no filter at
+ * all = every vector of the index" as there.  Exactly one of queries / qids; nq == 0 is a no-op.  Every store kind both
+ * underlying calls accept (f32, f16, i8, i8q, PQ); what either refuses (a shared-codebook PQ store, a PQ table that
+ * does not fit beside the scan's LDS) is refused here with the same code.  1 <= k <= sp->number_of_candidates (<= 1024),
+ * else PHNSW_E_INVALID.  All layers are searched (there is no upto).
+ * Rows: k entries, ascending by (distance, id), padded with PHNSW_EMPTY / f32::MAX.  out_len[q] == min(k, candidates of
+ * q) for EVERY query, and an id that is not a candidate is never returned: not the disallowed entry vector, and not the
+ * excluded one either (both can come back from phnsw_search_batch_filtered).
+ * Route: let c_q be what phnsw_filter_count_device reports for q's bitmap, N the bottom layer's node count and
+ * ef = sp->number_of_candidates.  Query q is SCANNED iff c_q <= scan_below or c_q * ef < k * N (the walk's post-filter
+ * is then expected to keep fewer than k of its queue); otherwise it WALKS THE GRAPH.  A Stored query id at or past n
+ * (device form) is scanned whatever its count, which reports it.
+ * scan_below 0 = the library default, the measured crossover of profiles/filter_exact/README.md: 13 000 with a shared
+ * bitmap, 10 000 with per-query bitmaps -- measured on 1M x 768 f32 rows, k = 10, batches of 10 000 queries; other store
+ * kinds, dimensions and batch sizes are unmeasured, pass your own.  UINT64_MAX = always scan.  No value never scans:
+ * the second rule and the fallback below always hold.
+ * A scanned row is, bit for bit, the row phnsw_search_exact_filtered returns.  A graph row is the PHNSW_FILTER_STRICT
+ * row of phnsw_search_batch_filtered with the same sp, with exclude[q] removed if present, cut to k.  If that leaves
+ * fewer than min(k, c_q - e_q) entries (e_q = 1 iff exclude[q] is itself a candidate by bitmap and index membership),
+ * or the walk overflowed its spill list, the query is scanned: its row is then the scan's and its route reads
+ * PHNSW_ROUTE_GRAPH_THEN_SCAN.
+ * A graph-routed row is an APPROXIMATE result: its recall is that of the walk at this sp (the README's cells show
+ * 0.45-0.67 at the minimal number_of_candidates).  The guarantee of this call is completeness -- the full
+ * min(k, candidates) entries, candidates only -- not recall; scanned rows are exact.
+ * Cost: the call adds a count, a routing pass and up to two stream synchronisations to the method it picks; it has not
+ * been timed against the two calls (profiles/filter_auto/README.md).  A caller whose whole batch sits on one side of the
+ * crossover loses nothing by calling that method directly.
+ * out_route: nullable; per query one of the three values.  Thread safe like the other search calls. */
+enum { PHNSW_ROUTE_GRAPH = 0, PHNSW_ROUTE_SCAN = 1, PHNSW_ROUTE_GRAPH_THEN_SCAN = 2 };
+int phnsw_search_filtered_auto(const phnsw_index *ix, const float *queries, const uint64_t *qids, uint64_t nq,
+                               const phnsw_search_params *sp, const uint64_t *exclude,
+                               const uint32_t *filter, uint32_t filter_stride_words,
+                               uint64_t k, uint64_t scan_below,
+                               uint64_t *out_ids, float *out_d, uint64_t *out_len, uint32_t *out_route);
+/* device form: device pointers, u32 ids [nq][k] padded with 0xFFFFFFFF / f32::MAX; queries [nq][ldq] as for
+ * phnsw_search_batch_device.  status_dev[q] is 0, or what the underlying call reports for that query (4 = a Stored
+ * query id at or past n, or a vector missing from a lower layer; the row is then empty).  Unlike the other _device
+ * calls this one SYNCHRONISES `stream`, at most twice, to read list lengths back: after counting and routing, and --
+ * only when some query walks the graph -- after the graph rows are finished and the short ones are known.  The scan is
+ * enqueued after that; the call returns without waiting for it. */
+int phnsw_search_filtered_auto_device(const phnsw_index *ix, const float *queries_dev, uint32_t ldq,
+                                      const uint32_t *qids_dev, uint64_t nq, const phnsw_search_params *sp,
+                                      const uint32_t *exclude_dev, const uint32_t *filter_dev,
+                                      uint32_t filter_stride_words, uint64_t k, uint64_t scan_below,
+                                      uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                      uint32_t *out_route_dev, uint32_t *status_dev, void *stream);
 /* Throughput callers keep TWO batches in flight: phnsw_search_batch_device calls issued alternately on two streams
  * overlap (an index holds two search workspaces) -- if the two streams sit on different hardware queues.  HIP maps a
  * process's streams onto a few of them (GPU_MAX_HW_QUEUES, 4 by default) and two streams that share one run in issue

@@ -369,6 +369,42 @@ class Hnsw {
                            void *stream) const {
     check(phnsw_filter_count_device(ix_, filter_dev, stride_words, nbitmaps, out_count_dev, stream));
   }
+  // one filtered call that picks the scan or the graph walk per query and rescans what the walk left short
+  // (phnsw_search_filtered_auto): every result holds min(k, candidates) entries, candidates only.  `allow` as for
+  // search_many_filtered (empty = the default of set_filter_device, else every vector of the index); scan_below 0 = the
+  // library's threshold, UINT64_MAX = always scan.  A graph-routed result is approximate (phnsw.h); routes, when given,
+  // receives one PHNSW_ROUTE_* per query.  Throws unless 1 <= k <= number_of_candidates and on a short `allow`
+  std::vector<SearchResult> search_many_filtered_auto(const std::vector<const float *> &queries, const SearchParameters &sp,
+                                                      uint64_t k, const std::vector<uint32_t> &allow, uint32_t stride_words = 0,
+                                                      uint64_t scan_below = 0, std::vector<uint32_t> *routes = nullptr) const {
+    const uint64_t nq = queries.size(), dim = c_->dim(), words = (c_->len() + 31) / 32;
+    if (k == 0 || k > sp.number_of_candidates)
+      throw Error(PHNSW_E_INVALID, "search_many_filtered_auto: k must be 1..number_of_candidates");
+    if (!allow.empty() && (stride_words ? stride_words < words || allow.size() < nq * stride_words : allow.size() < words))
+      throw Error(PHNSW_E_INVALID, "search_many_filtered_auto: allow is shorter than its bitmaps (ceil(n / 32) words "
+                                   "shared, nq * stride_words per query, stride_words >= ceil(n / 32))");
+    std::vector<float> q(nq * dim);
+    for (uint64_t i = 0; i < nq; i++) std::copy(queries[i], queries[i] + dim, q.begin() + i * dim);
+    std::vector<uint64_t> ids(nq * k), len(nq);
+    std::vector<float> d(nq * k);
+    if (routes) routes->assign(nq, 0u);
+    check(phnsw_search_filtered_auto(ix_, q.data(), nullptr, nq, &sp, nullptr, allow.empty() ? nullptr : allow.data(),
+                                     stride_words, k, scan_below, ids.data(), d.data(), len.data(),
+                                     routes ? routes->data() : nullptr));
+    std::vector<SearchResult> out(nq);
+    for (uint64_t i = 0; i < nq; i++)
+      for (uint64_t j = 0; j < len[i]; j++) out[i].push_back({ids[i * k + j], d[i * k + j]});
+    return out;
+  }
+  // device form (phnsw_search_filtered_auto_device): u32 ids [nq][k]; synchronises `stream` up to twice (phnsw.h)
+  void search_filtered_auto_device(const float *queries_dev, uint32_t ldq, const uint32_t *qids_dev, uint64_t nq,
+                                   const SearchParameters &sp, const uint32_t *exclude_dev, const uint32_t *filter_dev,
+                                   uint32_t stride_words, uint64_t k, uint64_t scan_below, uint32_t *out_ids_dev,
+                                   float *out_d_dev, uint32_t *out_len_dev, uint32_t *out_route_dev, uint32_t *status_dev,
+                                   void *stream) const {
+    check(phnsw_search_filtered_auto_device(ix_, queries_dev, ldq, qids_dev, nq, &sp, exclude_dev, filter_dev, stride_words, k,
+                                            scan_below, out_ids_dev, out_d_dev, out_len_dev, out_route_dev, status_dev, stream));
+  }
   // tombstones (phnsw_index_set_filter_device): the default bitmap of the filtered calls; nullptr clears it
   void set_filter_device(const uint32_t *filter_dev) { check(phnsw_index_set_filter_device(ix_, filter_dev)); }
   // Hnsw::search_instrumented(v, sp) -> (results, index_distance)  lib.rs:667-673

@@ -136,6 +136,9 @@ SYMBOLS = {
     "phnsw_search_exact_filtered": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _u32, _u64, _vp, _vp, _vp]),
     "phnsw_search_exact_filtered_device": (_i32, [_vp, _vp, _u32, _vp, _u64, _vp, _vp, _u32, _u64, _vp, _vp, _vp, _vp, _vp]),
     "phnsw_filter_count_device": (_i32, [_vp, _vp, _u32, _u64, _vp, _vp]),
+    "phnsw_search_filtered_auto": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _u32, _u64, _u64, _vp, _vp, _vp, _vp]),
+    "phnsw_search_filtered_auto_device": (_i32, [_vp, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _u32, _u64, _u64, _vp, _vp, _vp,
+                                                 _vp, _vp, _vp]),
     "phnsw_index_counters": (_i32, [_vp, _vp, _vp]),
     "phnsw_last_search_kernel_ms": (_i32, [_vp, C.POINTER(_f32)]),
     "phnsw_last_search_dispatches": (_i32, [_vp, _u32, C.POINTER(_u32), _vp, _vp, _vp, _vp, _vp]),

@@ -1,0 +1,434 @@
+// One filtered search that picks its method per query (phnsw_search_filtered_auto[_device]): the exact scan of the
+// allow-list (filter_exact.hip) where few rows are allowed, the graph walk with a strict post-filter (search.hip) where
+// many are, and the scan again for every query whose walk came back short.  Every row then holds exactly
+// min(k, candidates) entries and never an id that is not a candidate.  The rule is filter_route.h's.
+//
+//   1. ph_filter_count          candidates per bitmap
+//   2. ph_auto_route_kernel     route[q]; the graph list and the scan list, ascending, their lengths in device words
+//      -- the host reads the two lengths (first synchronisation)
+//   3. ph_search_device         order = the graph list: strict rows [nq][ef] in scratch, addressed by the original q
+//   4. ph_auto_finish_kernel    exclude[q] dropped, k entries copied out; short rows appended to the scan list
+//      -- the host reads the scan list's length (second synchronisation; neither happens without a graph list)
+//   5. ph_exact_device          list = the scan list: routed and short queries in ONE launch, after the walk
+//
+// The search kernels and the scan's arithmetic are untouched: a scanned row is phnsw_search_exact_filtered's row bit
+// for bit, a graph row is the strict row of phnsw_search_batch_filtered.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "filter_candidate.h"
+#include "filter_route.h"
+#include "phnsw_device.h"
+
+static_assert(PH_ROUTE_GRAPH == PHNSW_ROUTE_GRAPH && PH_ROUTE_SCAN == PHNSW_ROUTE_SCAN &&
+                  PH_ROUTE_GRAPH_THEN_SCAN == PHNSW_ROUTE_GRAPH_THEN_SCAN,
+              "filter_route.h and phnsw.h name the same routes");
+
+#define PH_TRY(x)          \
+  do {                     \
+    int rc__ = (x);        \
+    if (rc__) return rc__; \
+  } while (0)
+
+struct PhAutoArgs {
+  uint32_t nq, n, k, ef;
+  uint64_t scan_below;
+  const uint32_t *qids, *exclude;  // [nq] or nullptr
+  const uint32_t *filter;          // nullptr: every vector of the index
+  uint32_t filter_stride;          // 0 = one bitmap for all
+  uint32_t per_query;              // counts holds nq entries, else one
+  // the index's bottom layer, as the candidate test takes it
+  uint32_t n_nodes;
+  const uint32_t *nodes, *vec2node;
+  // the call's scratch (filter_route.h)
+  uint32_t *head;          // [0] length of the graph list, [1] of the scan list
+  const uint32_t *counts;  // candidates per bitmap
+  uint32_t *glist, *slist, *route;
+  const uint32_t *walk_ids;  // [nq][ef]: the strict rows of the graph list's queries
+  const float *walk_d;
+  const uint32_t *walk_len;
+  uint32_t *out_ids;  // [nq][k]
+  float *out_d;
+  uint32_t *out_len, *status;
+};
+
+// One workgroup walks the batch 256 queries at a time: the rule per query, a ballot per wave and a scan over the four
+// waves' counts give every query its place, so both lists come out ascending.
+__global__ __launch_bounds__(256) void ph_auto_route_kernel(PhAutoArgs a) {
+  __shared__ uint32_t wave_g[4], wave_s[4];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint64_t lt = lanemask_lt(lane);
+  uint32_t gbase = 0, sbase = 0;  // entries of the two lists so far: the same in every thread
+  for (uint64_t base = 0; base < a.nq; base += 256u) {
+    const uint64_t q64 = base + threadIdx.x;
+    const bool valid = q64 < a.nq;
+    const uint32_t q = (uint32_t)q64;
+    uint32_t r = PH_ROUTE_SCAN;
+    if (valid) {
+      r = ph_auto_route(a.counts[a.per_query ? q : 0u], a.scan_below, a.ef, a.k, a.n_nodes);
+      // a Stored query id at or past n has no row to walk from: the scan reports it (status 4, an empty row)
+      if (a.qids && a.qids[q] >= a.n) r = PH_ROUTE_SCAN;
+      a.route[q] = r;
+    }
+    const uint64_t gm = __ballot(valid && r == PH_ROUTE_GRAPH), sm = __ballot(valid && r == PH_ROUTE_SCAN);
+    if (lane == 0) wave_g[wave] = (uint32_t)__popcll(gm), wave_s[wave] = (uint32_t)__popcll(sm);
+    __syncthreads();
+    uint32_t goff = gbase, soff = sbase, gtot = 0, stot = 0;
+    for (uint32_t w = 0; w < 4u; w++) {
+      if (w < wave) goff += wave_g[w], soff += wave_s[w];
+      gtot += wave_g[w], stot += wave_s[w];
+    }
+    if (valid) {  // goff + rank < gbase + gtot <= nq, and so for the scan list
+      if (r == PH_ROUTE_GRAPH)
+        a.glist[goff + (uint32_t)__popcll(gm & lt)] = q;
+      else
+        a.slist[soff + (uint32_t)__popcll(sm & lt)] = q;
+    }
+    gbase += gtot, sbase += stot;
+    __syncthreads();  // the counts are rewritten by the next 256
+  }
+  if (threadIdx.x == 0) a.head[0] = gbase, a.head[1] = sbase;
+}
+
+// One wave per query of the graph list: its strict row without exclude[q], cut to k and padded, into the caller's
+// row; a row shorter than the candidates allow moves its query to the scan list (route 2), and so does a walk whose
+// spill list overflowed (status 5: the scan needs none).  Any other status stays, with an empty row.
+__global__ __launch_bounds__(64) void ph_auto_finish_kernel(PhAutoArgs a) {
+  const uint32_t lane = threadIdx.x;
+  const uint64_t lt = lanemask_lt(lane);
+  const uint32_t nlim = ph_exact_id_limit(a.n, a.n_nodes, a.nodes, a.vec2node);
+  const uint32_t glen = min(a.head[0], a.nq);
+  for (uint32_t i = blockIdx.x; i < glen; i += gridDim.x) {
+    const uint32_t q = a.glist[i];  // < nq: the route kernel wrote it
+    const uint32_t st = a.status[q];
+    const uint32_t len = st == ST_OK ? min(a.walk_len[q], a.ef) : 0u;
+    const uint32_t ex = a.exclude ? a.exclude[q] : PH_EMPTY32;
+    uint32_t kept = 0;
+    for (uint32_t b = 0; b < len && kept < a.k; b += 64u) {
+      const uint32_t j = b + lane;
+      const uint32_t id = j < len ? a.walk_ids[(uint64_t)q * a.ef + j] : PH_EMPTY32;
+      const bool keep = id != PH_EMPTY32 && id != ex;
+      const uint64_t km = __ballot(keep);
+      const uint32_t to = kept + (uint32_t)__popcll(km & lt);
+      if (keep && to < a.k) {
+        a.out_ids[(uint64_t)q * a.k + to] = id;
+        a.out_d[(uint64_t)q * a.k + to] = a.walk_d[(uint64_t)q * a.ef + j];
+      }
+      kept += (uint32_t)__popcll(km);
+    }
+    kept = min(kept, a.k);
+    for (uint32_t j = kept + lane; j < a.k; j += 64u) {
+      a.out_ids[(uint64_t)q * a.k + j] = PH_EMPTY32;
+      a.out_d[(uint64_t)q * a.k + j] = PH_FMAX;
+    }
+    if (lane == 0) {
+      const uint32_t *const bitmap = a.filter ? a.filter + (uint64_t)q * a.filter_stride : nullptr;
+      const uint32_t e = (ex != PH_EMPTY32 && ph_exact_is_candidate(bitmap, ex, nlim, a.vec2node)) ? 1u : 0u;
+      const uint32_t full = ph_auto_full_len(a.counts[a.per_query ? q : 0u], e, a.k);
+      if (st == ST_OVERFLOW || (st == ST_OK && kept < full)) {
+        const uint32_t at = atomicAdd(&a.head[1], 1u);  // < nq: q was in the graph list, not in this one
+        if (at < a.nq) a.slist[at] = q;
+        a.route[q] = PH_ROUTE_GRAPH_THEN_SCAN;  // the scan writes the row, its length and the status
+      } else {
+        a.out_len[q] = kept;
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------ a call's scratch
+
+// Kept with the index, one set per call in flight: nothing goes back to the pool while work that uses it may still be
+// enqueued, whichever way a call ends.  `done` closes the last call that used the set; the next one's stream waits.
+struct PhAutoSet {
+  uint32_t *block = nullptr;
+  size_t words = 0;
+  hipEvent_t done = nullptr;
+  uint32_t *h_head = nullptr;    // pinned: the list lengths as the host reads them
+  hipStream_t stream = nullptr;  // the host form's
+  bool in_use = false;
+};
+
+namespace {
+
+PhAutoSet *set_acquire(phnsw_index *ix) {
+  std::lock_guard<std::mutex> g(ix->auto_mutex);
+  for (PhAutoSet *s : ix->autos)
+    if (!s->in_use) {
+      s->in_use = true;
+      return s;
+    }
+  PhAutoSet *s = new PhAutoSet();
+  s->in_use = true;
+  ix->autos.push_back(s);
+  return s;
+}
+struct SetGuard {
+  phnsw_index *ix;
+  PhAutoSet *set;
+  hipStream_t stream;
+  ~SetGuard() {
+    if (set->done) hipEventRecord(set->done, stream);
+    std::lock_guard<std::mutex> g(ix->auto_mutex);
+    set->in_use = false;
+  }
+};
+
+int set_ensure(PhAutoSet &s, size_t words, hipStream_t stream) {
+  if (!s.done) PH_HIP(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
+  if (!s.h_head) PH_HIP(hipHostMalloc((void **)&s.h_head, PH_AUTO_HEAD_WORDS * 4u, hipHostMallocDefault));
+  if (s.words < words) {
+    if (s.block) {
+      PH_HIP(hipEventSynchronize(s.done));  // the block goes back to the pool: nothing may still use it
+      ph_pool_free(s.block);
+      s.block = nullptr, s.words = 0;
+    }
+    PH_HIP(ph_pool_alloc((void **)&s.block, words * 4u));
+    s.words = words;
+  } else {
+    PH_HIP(hipStreamWaitEvent(stream, s.done, 0));
+  }
+  return 0;
+}
+
+// the orchestration on a set the caller holds; c is checked
+int auto_run(const phnsw_index *ix, const PhAutoCall &c, PhAutoSet &set) {
+  const phnsw_store *s = ix->store;
+  const uint64_t nq = c.nq;
+  const uint32_t ef = (uint32_t)c.sp->number_of_candidates;
+  const bool per_query = c.filter.words && c.filter.stride != 0u;
+  PH_TRY(set_ensure(set, (size_t)ph_auto_scratch_words(nq, per_query, ef), c.stream));
+  const uint64_t nb = ph_auto_bitmaps(nq, per_query);
+  uint32_t *const head = set.block, *const counts = head + PH_AUTO_HEAD_WORDS, *const glist = counts + nb;
+  uint32_t *const slist = glist + ph_auto_list_words(nq), *const route_own = slist + ph_auto_list_words(nq);
+  uint32_t *const walk_len = route_own + nq, *const walk_ids = walk_len + nq;
+  float *const walk_d = (float *)(walk_ids + nq * ef);
+
+  PH_TRY(ph_filter_count(ix, c.filter, nb, counts, c.stream));
+  PhAutoArgs a = {};
+  a.nq = (uint32_t)nq, a.n = (uint32_t)s->n, a.k = c.k, a.ef = ef;
+  a.scan_below = ph_auto_scan_below(c.scan_below, per_query);
+  a.qids = c.qids, a.exclude = c.exclude;
+  a.filter = c.filter.words, a.filter_stride = c.filter.words ? c.filter.stride : 0u, a.per_query = per_query ? 1u : 0u;
+  ph_exact_bottom_layer(ix, &a.n_nodes, &a.nodes, &a.vec2node);
+  a.head = head, a.counts = counts, a.glist = glist, a.slist = slist, a.route = c.out_route ? c.out_route : route_own;
+  a.walk_ids = walk_ids, a.walk_d = walk_d, a.walk_len = walk_len;
+  a.out_ids = c.out_ids, a.out_d = c.out_d, a.out_len = c.out_len, a.status = c.status;
+  hipLaunchKernelGGL(ph_auto_route_kernel, dim3(1), dim3(256), 0, c.stream, a);
+  PH_HIP(hipGetLastError());
+  PH_HIP(hipMemcpyAsync(set.h_head, head, 8, hipMemcpyDeviceToHost, c.stream));
+  PH_HIP(hipStreamSynchronize(c.stream));
+  const uint64_t glen = std::min<uint64_t>(set.h_head[0], nq);
+  uint64_t slen = std::min<uint64_t>(set.h_head[1], nq);
+
+  if (glen) {
+    PhSearchCall w = {};
+    w.queries = c.queries, w.ldq = c.ldq, w.qids = c.qids, w.exclude = c.exclude;
+    w.nq = glen, w.order = glist;  // positions of the list; the kernels address everything by the query index it holds
+    w.sp = c.sp;
+    w.filter = c.filter, w.filter.flags = PHNSW_FILTER_STRICT;
+    w.out_ids = walk_ids, w.out_d = walk_d, w.out_len = walk_len, w.status = c.status;
+    w.stream = c.stream;
+    PH_TRY(ph_search_device(ix, w));
+    hipLaunchKernelGGL(ph_auto_finish_kernel, dim3((uint32_t)std::min<uint64_t>(glen, 1u << 16)), dim3(64), 0, c.stream, a);
+    PH_HIP(hipGetLastError());
+    PH_HIP(hipMemcpyAsync(set.h_head + 1, head + 1, 4, hipMemcpyDeviceToHost, c.stream));
+    PH_HIP(hipStreamSynchronize(c.stream));
+    slen = std::min<uint64_t>(set.h_head[1], nq);
+  }
+  if (slen) {
+    PhExactCall x = {};
+    x.queries = c.queries, x.ldq = c.ldq, x.qids = c.qids, x.exclude = c.exclude;
+    x.nq = slen, x.list = slist;
+    x.filter = c.filter, x.filter.flags = 0u;
+    x.k = c.k;
+    x.out_ids = c.out_ids, x.out_d = c.out_d, x.out_len = c.out_len, x.status = c.status;
+    x.stream = c.stream;
+    PH_TRY(ph_exact_device(ix, x));
+  }
+  return 0;
+}
+
+// the checks both entry points make before they look at a pointer: index, parameters, k, store kind
+int auto_check(const phnsw_index *ix, const phnsw_search_params *sp, uint64_t k, const char *call) {
+  PH_TRY(ph_check_sp(ix, sp));
+  if (!ph_auto_k_valid(k, sp->number_of_candidates)) {
+    ph_set_error("%s: k must be 1..number_of_candidates (got %llu, number_of_candidates %llu)", call, (unsigned long long)k,
+                 (unsigned long long)sp->number_of_candidates);
+    return PHNSW_E_INVALID;
+  }
+  PH_TRY(ph_exact_check(ix, k, call));  // a shared-codebook PQ store
+  return ph_exact_supported(ix, (uint32_t)k);
+}
+
+// device blocks of one host call: handed back only after the stream they were used on has drained, whichever way the
+// call ends
+struct HostBlocks {
+  hipStream_t stream;
+  std::vector<void *> blocks;
+  template <class T>
+  int alloc(T **p, size_t bytes) {
+    void *v = nullptr;
+    PH_HIP(ph_pool_alloc(&v, std::max<size_t>(bytes, 4)));
+    blocks.push_back(v);
+    *p = (T *)v;
+    return 0;
+  }
+  ~HostBlocks() {
+    hipStreamSynchronize(stream);
+    for (void *b : blocks) ph_pool_free(b);
+  }
+};
+
+}  // namespace
+
+void ph_auto_free(phnsw_index *ix) {
+  for (PhAutoSet *s : ix->autos) {
+    if (s->done) {
+      hipEventSynchronize(s->done);
+      hipEventDestroy(s->done);
+    }
+    if (s->block) ph_pool_free(s->block);
+    if (s->h_head) hipHostFree(s->h_head);
+    if (s->stream) hipStreamDestroy(s->stream);
+    delete s;
+  }
+  ix->autos.clear();
+}
+
+int ph_auto_device(const phnsw_index *ix, const PhAutoCall &c) {
+  if (c.nq == 0) return 0;
+  phnsw_index *mix = const_cast<phnsw_index *>(ix);
+  PhAutoSet *set = set_acquire(mix);
+  SetGuard guard{mix, set, c.stream};
+  return auto_run(ix, c, *set);
+}
+
+// ------------------------------------------------------------------ C ABI
+
+extern "C" int phnsw_search_filtered_auto_device(const phnsw_index *ix, const float *queries_dev, uint32_t ldq,
+                                                 const uint32_t *qids_dev, uint64_t nq, const phnsw_search_params *sp,
+                                                 const uint32_t *exclude_dev, const uint32_t *filter_dev,
+                                                 uint32_t filter_stride_words, uint64_t k, uint64_t scan_below,
+                                                 uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                                 uint32_t *out_route_dev, uint32_t *status_dev, void *stream) try {
+  const char *const call = "phnsw_search_filtered_auto_device";
+  PH_TRY(auto_check(ix, sp, k, call));
+  if (nq == 0) return 0;
+  if (!ph_auto_queries_valid(queries_dev != nullptr, qids_dev != nullptr) || !out_ids_dev || !out_d_dev || !out_len_dev ||
+      !status_dev || !ph_auto_nq_valid(nq) ||
+      (queries_dev && (ldq < ix->store->ld || (ldq % 4) || ((uintptr_t)queries_dev % 16)))) {
+    ph_set_error("%s: invalid argument (queries or qids, exactly one; outputs; queries need ldq >= store ld, multiple of 4, "
+                 "16-byte base)", call);
+    return PHNSW_E_INVALID;
+  }
+  PhAutoCall c = {};
+  PH_TRY(ph_filter_check(ix, filter_dev, filter_stride_words, 0u, call, &c.filter));
+  if (!c.filter.words) c.filter.words = ix->default_filter;  // phnsw_index_set_filter_device
+  c.queries = queries_dev, c.ldq = ldq, c.qids = qids_dev, c.exclude = exclude_dev, c.nq = nq, c.sp = sp;
+  c.k = (uint32_t)k, c.scan_below = scan_below;
+  c.out_ids = out_ids_dev, c.out_d = out_d_dev, c.out_len = out_len_dev, c.out_route = out_route_dev, c.status = status_dev;
+  c.stream = (hipStream_t)stream;
+  PH_HIP(hipSetDevice(ix->store->device));
+  return ph_auto_device(ix, c);
+} catch (...) { return ph_caught(); }
+
+extern "C" int phnsw_search_filtered_auto(const phnsw_index *ix, const float *queries, const uint64_t *qids, uint64_t nq,
+                                          const phnsw_search_params *sp, const uint64_t *exclude, const uint32_t *filter,
+                                          uint32_t filter_stride_words, uint64_t k, uint64_t scan_below, uint64_t *out_ids,
+                                          float *out_d, uint64_t *out_len, uint32_t *out_route) try {
+  const char *const call = "phnsw_search_filtered_auto";
+  PH_TRY(auto_check(ix, sp, k, call));
+  if (nq == 0) return 0;
+  if (!ph_auto_queries_valid(queries != nullptr, qids != nullptr) || !out_ids || !out_d || !out_len || !ph_auto_nq_valid(nq)) {
+    ph_set_error("%s: invalid argument (queries or qids, exactly one; outputs)", call);
+    return PHNSW_E_INVALID;
+  }
+  PhFilter hf;
+  PH_TRY(ph_filter_check(ix, filter, filter_stride_words, 0u, call, &hf));
+  const phnsw_store *s = ix->store;
+  if (qids)
+    for (uint64_t i = 0; i < nq; i++)
+      if (qids[i] >= s->n) {
+        ph_set_error("search: stored query id %llu out of range", (unsigned long long)qids[i]);
+        return PHNSW_E_INVALID;
+      }
+  PH_HIP(hipSetDevice(s->device));
+  // host words of the per-query ids, alive until the stream has drained (HostBlocks is declared after them)
+  std::vector<uint32_t> h_in, h_out(3u * nq);
+  phnsw_index *mix = const_cast<phnsw_index *>(ix);
+  PhAutoSet *set = set_acquire(mix);
+  if (!set->stream) {
+    hipError_t e = hipStreamCreateWithFlags(&set->stream, hipStreamNonBlocking);
+    if (e != hipSuccess) {
+      SetGuard g{mix, set, nullptr};
+      return ph_hip_fail(e, "host path: stream", __FILE__, __LINE__);
+    }
+  }
+  const hipStream_t st = set->stream;
+  SetGuard guard{mix, set, st};
+  HostBlocks hb{st, {}};
+
+  PhAutoCall c = {};
+  const uint32_t ld = s->ld, kk = (uint32_t)k;
+  if (queries) {  // rows padded to the store's row length
+    float *q = nullptr;
+    PH_TRY(hb.alloc(&q, (size_t)nq * ld * 4u));
+    if (ld != s->dim) {
+      PH_HIP(hipMemsetAsync(q, 0, (size_t)nq * ld * 4u, st));
+      PH_HIP(hipMemcpy2DAsync(q, (size_t)ld * 4u, queries, (size_t)s->dim * 4u, (size_t)s->dim * 4u, nq, hipMemcpyHostToDevice, st));
+    } else {
+      PH_HIP(hipMemcpyAsync(q, queries, (size_t)nq * ld * 4u, hipMemcpyHostToDevice, st));
+    }
+    c.queries = q, c.ldq = ld;
+  }
+  uint32_t *small = nullptr;  // qid | exclude | len | status | route   [5][nq]
+  PH_TRY(hb.alloc(&small, (size_t)nq * 5u * 4u));
+  if (qids || exclude) {
+    h_in.resize(2u * nq);
+    if (qids)
+      for (uint64_t i = 0; i < nq; i++) h_in[i] = (uint32_t)qids[i];
+    if (exclude)
+      for (uint64_t i = 0; i < nq; i++) h_in[nq + i] = exclude[i] >= s->n ? PH_EMPTY32 : (uint32_t)exclude[i];
+    PH_HIP(hipMemcpyAsync(small, h_in.data(), (size_t)nq * 2u * 4u, hipMemcpyHostToDevice, st));
+    if (qids) c.qids = small;
+    if (exclude) c.exclude = small + nq;
+  }
+  c.filter = hf;
+  if (hf.words) {  // whole strides, as phnsw_search_batch_filtered copies them
+    const size_t words = hf.stride ? (size_t)nq * hf.stride : (size_t)((s->n + 31u) / 32u);
+    uint32_t *f = nullptr;
+    PH_TRY(hb.alloc(&f, words * 4u));
+    PH_HIP(hipMemcpyAsync(f, hf.words, words * 4u, hipMemcpyHostToDevice, st));
+    c.filter.words = f;
+  } else {
+    c.filter.words = ix->default_filter;  // phnsw_index_set_filter_device: device words
+  }
+  uint32_t *ids = nullptr;
+  float *d = nullptr, *dk = nullptr;
+  uint64_t *ids64 = nullptr;
+  PH_TRY(hb.alloc(&ids, (size_t)nq * kk * 4u));
+  PH_TRY(hb.alloc(&d, (size_t)nq * kk * 4u));
+  PH_TRY(hb.alloc(&ids64, (size_t)nq * kk * 8u));
+  PH_TRY(hb.alloc(&dk, (size_t)nq * kk * 4u));
+  c.nq = nq, c.sp = sp, c.k = kk, c.scan_below = scan_below;
+  c.out_ids = ids, c.out_d = d, c.out_len = small + 2u * nq, c.status = small + 3u * nq, c.out_route = small + 4u * nq;
+  c.stream = st;
+  PH_TRY(auto_run(ix, c, *set));
+  PH_TRY(ph_take_launch(ids, d, kk, kk, nq, ids64, dk, st));  // u32 -> u64 ids, 0xFFFFFFFF -> PHNSW_EMPTY
+  PH_HIP(hipMemcpyAsync(h_out.data(), small + 2u * nq, (size_t)nq * 3u * 4u, hipMemcpyDeviceToHost, st));
+  PH_HIP(hipMemcpyAsync(out_ids, ids64, (size_t)nq * kk * 8u, hipMemcpyDeviceToHost, st));
+  PH_HIP(hipMemcpyAsync(out_d, dk, (size_t)nq * kk * 4u, hipMemcpyDeviceToHost, st));
+  PH_HIP(hipStreamSynchronize(st));
+  for (uint64_t i = 0; i < nq; i++) {
+    if (h_out[nq + i] != 0u) {  // the ids were checked: what is left is the walk's own failure
+      ph_set_error("search: a candidate vector is missing from a lower layer (layers not nested, lib.rs:261)");
+      return PHNSW_E_MISSING_NODE;
+    }
+    out_len[i] = h_out[i];
+    if (out_route) out_route[i] = h_out[2u * nq + i];
+  }
+  return 0;
+} catch (...) { return ph_caught(); }

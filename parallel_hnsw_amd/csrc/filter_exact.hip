@@ -12,13 +12,15 @@
 // depend on how the bitmap is cut into slices (exact_slices.h), nor on the order in which candidates arrive.
 //
 // Kernels of this file only: no existing kernel, and no translation unit that holds one, is touched
-// (profiles/filter_exact/).
+// (profiles/filter_exact/).  The candidate test lives in filter_candidate.h, shared with filter_auto.hip, whose routed
+// call also scans a LIST of queries (PhExactCall::list): work goes by list position, everything else by the query index.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdlib>
 
 #include "exact_slices.h"
+#include "filter_candidate.h"
 #include "phnsw_device.h"
 
 struct PhExactArgs {
@@ -29,41 +31,17 @@ struct PhExactArgs {
   const uint32_t *filter;          // nullptr: every vector of the index
   uint32_t filter_stride;          // words from one query's bitmap to the next, 0 = one for all
   uint32_t nq, n, nwords, k, slices;
+  const uint32_t *list;  // nullable: work position i is query list[i] (nq positions); scratch goes by position
   uint64_t passes;
   // the index's bottom layer: a candidate is one of its vectors
   uint32_t n_nodes;
   const uint32_t *nodes, *vec2node;  // vec2node == nullptr: identity, the vectors are 0 .. n_nodes - 1
   uint32_t pq_lds;                   // bytes of dynamic LDS in front of the scan's own: a PQ store's table (16-byte multiple)
-  uint64_t *scratch;                 // slices > 1: [nq][slices][k] keys, each list ascending, KEY_NONE padded
+  uint64_t *scratch;                 // slices > 1: [nq positions][slices][k] keys, each list ascending, KEY_NONE padded
   uint32_t *out_ids;                 // [nq][k]
   float *out_d;
   uint32_t *out_len, *status;  // [nq]
 };
-
-// VectorIds of the bottom layer lie below this: an identity layer holds 0 .. n_nodes - 1, any other layer's largest
-// vector is its last node (nodes ascend), and vec2node has an entry for every id up to that one
-__device__ __forceinline__ uint32_t ph_exact_id_limit(uint32_t n, uint32_t n_nodes, const uint32_t *nodes,
-                                                      const uint32_t *vec2node) {
-  if (n_nodes == 0) return 0u;
-  return min(n, vec2node ? nodes[n_nodes - 1u] + 1u : n_nodes);
-}
-
-// word `widx` of a bitmap reduced to candidates: bits at or past the limit cleared, then the bits of vectors the
-// bottom layer does not hold.  bitmap == nullptr: every bit set.  The one candidate test of the scan and of the count.
-__device__ __forceinline__ uint32_t ph_exact_word(const uint32_t *bitmap, uint32_t widx, uint32_t nwords, uint32_t nlim,
-                                                  const uint32_t *vec2node) {
-  if (widx >= nwords) return 0u;
-  const uint32_t first = widx * 32u;  // widx < nwords <= 2^26
-  if (first >= nlim) return 0u;
-  uint32_t w = bitmap ? bitmap[widx] : 0xFFFFFFFFu;
-  if (nlim - first < 32u) w &= (1u << (nlim - first)) - 1u;
-  if (vec2node)
-    for (uint32_t t = w; t; t &= t - 1u) {
-      const uint32_t b = (uint32_t)__ffs((int)t) - 1u;
-      if (vec2node[first + b] == PH_EMPTY32) w &= ~(1u << b);  // first + b < nlim
-    }
-  return w;
-}
 
 // partition_point over an ascending key list in LDS; len is wave-uniform, every lane may call it
 __device__ __forceinline__ uint32_t ph_keys_lower_bound(const uint64_t *keys, uint32_t len, uint64_t key) {
@@ -150,7 +128,8 @@ __global__ __launch_bounds__(64) void ph_exact_scan_kernel(PhExactArgs a) {
   const uint32_t nlim = ph_exact_id_limit(a.n, a.n_nodes, a.nodes, a.vec2node);
   const uint64_t items = (uint64_t)a.nq * a.slices;
   for (uint64_t item = blockIdx.x; item < items; item += gridDim.x) {
-    const uint32_t q = (uint32_t)(item % a.nq), slice = (uint32_t)(item / a.nq);
+    const uint32_t pos = (uint32_t)(item % a.nq), slice = (uint32_t)(item / a.nq);
+    const uint32_t q = a.list ? a.list[pos] : pos;
     __syncthreads();  // the previous item's LDS (table, lists) is done with
     const bool bad_query = !a.queries && a.qids[q] >= a.n;
     Dist dist;
@@ -188,7 +167,7 @@ __global__ __launch_bounds__(64) void ph_exact_scan_kernel(PhExactArgs a) {
     if (a.slices == 1u) {
       ph_exact_write_row(a, q, top.cur, top.len, bad_query, lane);
     } else {
-      uint64_t *const out = a.scratch + ((uint64_t)q * a.slices + slice) * a.k;
+      uint64_t *const out = a.scratch + ((uint64_t)pos * a.slices + slice) * a.k;
       for (uint32_t i = lane; i < a.k; i += 64u) out[i] = i < top.len ? top.cur[i] : KEY_NONE;
     }
   }
@@ -200,12 +179,13 @@ __global__ __launch_bounds__(64) void ph_exact_merge_kernel(PhExactArgs a) {
   extern __shared__ float exact_lds[];
   const uint32_t lane = threadIdx.x;
   uint64_t *const keys = (uint64_t *)exact_lds;
-  for (uint32_t q = blockIdx.x; q < a.nq; q += gridDim.x) {
+  for (uint32_t pos = blockIdx.x; pos < a.nq; pos += gridDim.x) {
+    const uint32_t q = a.list ? a.list[pos] : pos;
     __syncthreads();
     PhExactTopK top;
     top.cur = keys, top.nxt = keys + a.k, top.sv = keys + 2u * a.k, top.len = 0, top.k = a.k;
     for (uint32_t s = 0; s < a.slices; s++) {
-      const uint64_t *const list = a.scratch + ((uint64_t)q * a.slices + s) * a.k;
+      const uint64_t *const list = a.scratch + ((uint64_t)pos * a.slices + s) * a.k;
       for (uint32_t b = 0; b < a.k; b += 64u)
         if (!top.insert(b + lane < a.k ? list[b + lane] : KEY_NONE, lane)) break;
     }
@@ -259,7 +239,7 @@ static PhExactFn exact_fn(const phnsw_store *s) {
 static const size_t PH_EXACT_LDS_MAX = 160 * 1024;  // a workgroup's LDS on gfx950
 
 // the bottom layer of the index into the argument block
-static void exact_bottom_layer(const phnsw_index *ix, uint32_t *n_nodes, const uint32_t **nodes, const uint32_t **vec2node) {
+void ph_exact_bottom_layer(const phnsw_index *ix, uint32_t *n_nodes, const uint32_t **nodes, const uint32_t **vec2node) {
   const PhLayerHost &B = ix->layers.back();
   *n_nodes = B.n_nodes;
   *nodes = B.nodes;
@@ -277,20 +257,27 @@ void ph_exact_free(phnsw_index *ix) {
   }
 }
 
+int ph_exact_supported(const phnsw_index *ix, uint32_t k) {
+  const phnsw_store *s = ix->store;
+  if (!exact_fn(s)) return ph_dim_unsupported(s->dim);
+  const size_t pq_lds = (ph_pq_lds_bytes(s) + 15u) & ~(size_t)15u, own_lds = (size_t)ph_exact_own_lds(k);
+  if (pq_lds + own_lds > PH_EXACT_LDS_MAX) {
+    ph_set_error("exact filtered search: the PQ tables (%zu bytes) plus the scan's own %zu bytes of LDS at k = %u do not fit a "
+                 "workgroup's %zu bytes",
+                 pq_lds, own_lds, k, PH_EXACT_LDS_MAX);
+    return PHNSW_E_UNSUPPORTED;
+  }
+  return 0;
+}
+
 int ph_exact_device(const phnsw_index *ix, const PhExactCall &c) {
   phnsw_index *mix = const_cast<phnsw_index *>(ix);
   const phnsw_store *s = ix->store;
   if (c.nq == 0) return 0;
+  if (int rc = ph_exact_supported(ix, c.k)) return rc;
   const PhExactFn fn = exact_fn(s);
-  if (!fn) return ph_dim_unsupported(s->dim);
   const size_t pq_lds = (ph_pq_lds_bytes(s) + 15u) & ~(size_t)15u, own_lds = (size_t)ph_exact_own_lds(c.k);
   const size_t lds = pq_lds + own_lds;
-  if (lds > PH_EXACT_LDS_MAX) {
-    ph_set_error("exact filtered search: the PQ tables (%zu bytes) plus the scan's own %zu bytes of LDS at k = %u do not fit a "
-                 "workgroup's %zu bytes",
-                 pq_lds, own_lds, c.k, PH_EXACT_LDS_MAX);
-    return PHNSW_E_UNSUPPORTED;
-  }
   if (lds > 48 * 1024)
     PH_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   // waves of the scan the device holds at once
@@ -303,10 +290,10 @@ int ph_exact_device(const phnsw_index *ix, const PhExactCall &c) {
   a.dist = ph_dist_args(s);
   a.queries = c.queries, a.ldq = c.ldq, a.qids = c.qids, a.exclude = c.exclude;
   a.filter = c.filter.words, a.filter_stride = c.filter.words ? c.filter.stride : 0u;
-  a.nq = (uint32_t)c.nq, a.n = (uint32_t)s->n, a.nwords = (uint32_t)ph_exact_words(s->n), a.k = c.k;
+  a.nq = (uint32_t)c.nq, a.list = c.list, a.n = (uint32_t)s->n, a.nwords = (uint32_t)ph_exact_words(s->n), a.k = c.k;
   a.passes = ph_exact_passes(s->n);
   a.slices = ph_exact_slice_count(c.nq, resident, a.passes, e ? atoll(e) : 0);
-  exact_bottom_layer(ix, &a.n_nodes, &a.nodes, &a.vec2node);
+  ph_exact_bottom_layer(ix, &a.n_nodes, &a.nodes, &a.vec2node);
   a.pq_lds = (uint32_t)pq_lds;
   a.out_ids = c.out_ids, a.out_d = c.out_d, a.out_len = c.out_len, a.status = c.status;
   const uint64_t items = c.nq * (uint64_t)a.slices;
@@ -345,7 +332,7 @@ int ph_filter_count(const phnsw_index *ix, const PhFilter &f, uint64_t nbitmaps,
   const phnsw_store *s = ix->store;
   uint32_t n_nodes;
   const uint32_t *nodes, *vec2node;
-  exact_bottom_layer(ix, &n_nodes, &nodes, &vec2node);
+  ph_exact_bottom_layer(ix, &n_nodes, &nodes, &vec2node);
   hipLaunchKernelGGL(ph_filter_count_kernel, dim3((uint32_t)std::min<uint64_t>(nbitmaps, 1u << 20)), dim3(256), 0, stream,
                      f.words, f.words ? f.stride : 0u, nbitmaps, (uint32_t)s->n, (uint32_t)ph_exact_words(s->n), n_nodes, nodes,
                      vec2node, out_count_dev);

@@ -1,0 +1,68 @@
+// How the routed filtered search (filter_auto.hip, phnsw_search_filtered_auto) decides: pure integer rules without a
+// pointer, shared by the entry points, the kernels and tests/cpp/test_filter_route.cpp (which runs them under the host
+// sanitizers, no GPU).
+//
+// Per query, with c = its candidates as phnsw_filter_count_device counts them, N = nodes of the bottom layer,
+// ef = number_of_candidates:
+//   scan   iff  c <= scan_below  or  c * ef < k * N   (the walk's post-filter keeps about ef * c / N of its queue:
+//               fewer than k of them are expected to survive)
+//   graph  otherwise; a graph row that comes back with fewer than min(k, c - e) entries is scanned after all
+//               (e = 1 iff exclude[q] is itself among the c)
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define PH_ROUTE_HD __host__ __device__
+#else
+#define PH_ROUTE_HD
+#endif
+
+// the values of phnsw.h's PHNSW_ROUTE_* (filter_auto.hip asserts that they agree)
+#define PH_ROUTE_GRAPH 0u
+#define PH_ROUTE_SCAN 1u
+#define PH_ROUTE_GRAPH_THEN_SCAN 2u
+
+#define PH_AUTO_EF_MAX 1024u  // largest number_of_candidates of a search, hence the largest k
+// scan_below == 0: the measured crossover of the two calls (profiles/filter_exact/README.md: 1M x 768 f32 rows, k = 10,
+// batches of 10 000 queries; other store kinds and shapes are unmeasured)
+#define PH_AUTO_SCAN_BELOW_SHARED 13000u     // one bitmap for the batch
+#define PH_AUTO_SCAN_BELOW_PER_QUERY 10000u  // a bitmap per query
+
+// the threshold a call runs with.  UINT64_MAX stays what it is: no count exceeds it, every query is scanned
+PH_ROUTE_HD static inline uint64_t ph_auto_scan_below(uint64_t scan_below, bool per_query) {
+  if (scan_below != 0u) return scan_below;
+  return per_query ? PH_AUTO_SCAN_BELOW_PER_QUERY : PH_AUTO_SCAN_BELOW_SHARED;
+}
+
+// the route of a query with c candidates.  c and n_nodes are 32-bit counts, ef and k at most 1024: the two products
+// stay below 2^42 and cannot wrap
+PH_ROUTE_HD static inline uint32_t ph_auto_route(uint32_t c, uint64_t scan_below, uint32_t ef, uint32_t k, uint32_t n_nodes) {
+  if ((uint64_t)c <= scan_below) return PH_ROUTE_SCAN;
+  return (uint64_t)c * (uint64_t)ef < (uint64_t)k * (uint64_t)n_nodes ? PH_ROUTE_SCAN : PH_ROUTE_GRAPH;
+}
+
+// entries a complete row of a query holds: min(k, c - e); excluded is 1 only when exclude[q] is one of the c
+PH_ROUTE_HD static inline uint32_t ph_auto_full_len(uint32_t c, uint32_t excluded, uint32_t k) {
+  const uint32_t left = c - (excluded && c ? 1u : 0u);
+  return left < k ? left : k;
+}
+
+// ---- argument checks
+static inline bool ph_auto_ef_valid(uint64_t ef) { return ef >= 1u && ef <= PH_AUTO_EF_MAX; }
+static inline bool ph_auto_k_valid(uint64_t k, uint64_t ef) { return ph_auto_ef_valid(ef) && k >= 1u && k <= ef; }
+// exactly one of queries / qids
+static inline bool ph_auto_queries_valid(bool has_queries, bool has_qids) { return has_queries != has_qids; }
+// 0 = one shared bitmap, else at least the ceil(n / 32) words of one bitmap
+static inline bool ph_auto_stride_valid(uint64_t stride_words, uint64_t n) { return stride_words == 0u || stride_words >= (n + 31u) / 32u; }
+static inline bool ph_auto_nq_valid(uint64_t nq) { return nq <= 0xFFFFFFFFull; }
+
+// ---- capacities of a call's device scratch, in 32-bit words.  One block:
+//   head[PH_AUTO_HEAD_WORDS] | counts[bitmaps] | graph list[nq] | scan list[nq] | route[nq] | walk len[nq] |
+//   walk ids[nq][ef] | walk distances[nq][ef]
+// Every query is in at most one of the two lists at a time (a short graph row moves over), so nq entries hold either.
+#define PH_AUTO_HEAD_WORDS 4u  // [0] length of the graph list, [1] of the scan list
+static inline uint64_t ph_auto_bitmaps(uint64_t nq, bool per_query) { return per_query ? nq : 1u; }
+static inline uint64_t ph_auto_list_words(uint64_t nq) { return nq; }
+static inline uint64_t ph_auto_scratch_words(uint64_t nq, bool per_query, uint64_t ef) {
+  return PH_AUTO_HEAD_WORDS + ph_auto_bitmaps(nq, per_query) + 2u * ph_auto_list_words(nq) + 2u * nq + 2u * nq * ef;
+}

@@ -233,6 +233,7 @@ struct PhExactScratch {
   hipEvent_t done = nullptr;
 };
 
+struct PhAutoSet;  // filter_auto.hip: the scratch of one routed filtered search, one per concurrent call
 struct PhPendingLayer;
 struct PhHostStage;  // hostpath.hip: persistent staging of the host-pointer search entry points
 struct phnsw_index {
@@ -261,6 +262,8 @@ struct phnsw_index {
   std::mutex exact_mutex;  // filter_exact.hip
   PhExactScratch exact[2];
   uint32_t exact_next = 0;
+  std::vector<PhAutoSet *> autos;  // filter_auto.hip: handed out under auto_mutex
+  std::mutex auto_mutex;
 };
 
 // ---- kernel argument block for the batched greedy search ----
@@ -432,10 +435,36 @@ struct PhExactCall {
   float *out_d;
   uint32_t *out_len, *status;  // [nq]
   hipStream_t stream;
+  // nullable: the scan covers queries list[0 .. nq) only (device words; filter_auto.hip).  nq is then the list's length;
+  // queries, qids, exclude, per-query bitmaps and every output stay addressed by the query index the list holds
+  const uint32_t *list;
 };
 int ph_exact_device(const phnsw_index *ix, const PhExactCall &c);
+// what ph_exact_device would refuse for this store and k (the row length, a PQ table beside the scan's LDS): 0 or the code
+int ph_exact_supported(const phnsw_index *ix, uint32_t k);
+// the bottom layer as the candidate test takes it (filter_candidate.h): *vec2node == nullptr for an identity layer
+void ph_exact_bottom_layer(const phnsw_index *ix, uint32_t *n_nodes, const uint32_t **nodes, const uint32_t **vec2node);
 int ph_filter_count(const phnsw_index *ix, const PhFilter &f, uint64_t nbitmaps, uint32_t *out_count_dev, hipStream_t stream);
 void ph_exact_free(phnsw_index *ix);
+// The request of one routed filtered search (ph_auto_device, filter_auto.hip): per query the exact scan or the graph
+// walk, and the scan again for whatever the walk left short.  Device pointers of the caller; rows of k entries.
+struct PhAutoCall {
+  const float *queries;  // [nq][ldq], or nullptr: Stored queries (qids)
+  uint32_t ldq;
+  const uint32_t *qids, *exclude;  // [nq] or nullptr
+  uint64_t nq;
+  const phnsw_search_params *sp;
+  PhFilter filter;  // words == nullptr: every vector of the index
+  uint32_t k;
+  uint64_t scan_below;  // 0 = the library default, UINT64_MAX = always scan (filter_route.h)
+  uint32_t *out_ids;    // [nq][k]
+  float *out_d;
+  uint32_t *out_len, *status;  // [nq]
+  uint32_t *out_route;         // [nq] or nullptr
+  hipStream_t stream;
+};
+int ph_auto_device(const phnsw_index *ix, const PhAutoCall &c);
+void ph_auto_free(phnsw_index *ix);
 // the argument checks the exact entry points share (api.hip): index with layers, 1 <= k <= 1024, a store kind the
 // distance batch accepts
 int ph_exact_check(const phnsw_index *ix, uint64_t k, const char *call);

@@ -38,6 +38,7 @@ def _p(a):
 
 
 FILTER_STRICT = 1  # PHNSW_FILTER_STRICT
+ROUTE_GRAPH, ROUTE_SCAN, ROUTE_GRAPH_THEN_SCAN = 0, 1, 2  # PHNSW_ROUTE_*
 
 
 def pack_allow(allow, n, nq):
@@ -743,6 +744,48 @@ class Hnsw:
         torch.cuda.synchronize(dev)
         counts = out.cpu().numpy().view(np.uint32)
         return counts if a is not None and a.ndim == 2 else int(counts[0])
+
+    def search_filtered(self, queries=None, qids=None, sp=None, allow=None, exclude=None, k=10, scan_below=0, route=False):
+        """one filtered call that picks its method per query (phnsw_search_filtered_auto): the exact scan where few rows
+        are allowed (candidates <= scan_below, or candidates * number_of_candidates < k * vector_count), the graph walk
+        with a strict filter otherwise, and the scan again for every query whose walk came back short.  Every row holds
+        exactly min(k, candidates) entries and only candidates (as search_exact_filtered defines them; allow and exclude
+        as there).  scan_below 0 = the library's threshold (13 000 shared / 10 000 per query, measured on 1M x 768 f32
+        rows), 2**64 - 1 = always scan.  A graph-routed row is approximate: the guarantee is completeness, not recall.
+        1 <= k <= sp.number_of_candidates.
+        Returns (ids[nq, k] u64, d[nq, k] f32, len[nq]) and, with route=True, route[nq] u32: ROUTE_GRAPH, ROUTE_SCAN or
+        ROUTE_GRAPH_THEN_SCAN"""
+        sp = sp or SearchParameters()
+        q = qi = None
+        if queries is not None:
+            q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+            assert q.shape[1] == self.store.dim
+            nq = q.shape[0]
+        if qids is not None:
+            qi = np.ascontiguousarray(qids, dtype=np.uint64)
+            nq = len(qi)
+        if q is None and qi is None:
+            raise ValueError("search_filtered: pass queries or qids")
+        words, stride = pack_allow(allow, self.store.n, nq)
+        w = max(int(k), 0)
+        ids = np.empty((nq, w), dtype=np.uint64)
+        d = np.empty((nq, w), dtype=np.float32)
+        ln = np.zeros(nq, dtype=np.uint64)
+        rt = np.zeros(nq, dtype=np.uint32) if route else None
+        ex = None if exclude is None else np.ascontiguousarray(exclude, dtype=np.uint64)
+        check(lib().phnsw_search_filtered_auto(self._h, _p(q), _p(qi), nq, C.byref(sp), _p(ex), _p(words), stride, int(k),
+                                               int(scan_below), _p(ids), _p(d), _p(ln), _p(rt)))
+        return (ids, d, ln, rt) if route else (ids, d, ln)
+
+    def search_filtered_device(self, nq, sp, k, out_ids, out_d, out_len, status, queries=0, ldq=0, qids=0, exclude=0,
+                               allow=0, allow_stride=0, scan_below=0, out_route=0, stream=0):
+        """device form (phnsw_search_filtered_auto_device): device pointers as integers, u32 ids [nq, k] padded with
+        0xFFFFFFFF; allow = one packed bitmap (allow_stride 0) or nq bitmaps allow_stride words apart, 0 = the default
+        of set_filter; out_route u32 [nq] or 0.  Unlike the other _device calls it synchronises `stream`, up to twice"""
+        check(lib().phnsw_search_filtered_auto_device(
+            self._h, C.c_void_p(queries or None), ldq, C.c_void_p(qids or None), nq, C.byref(sp), C.c_void_p(exclude or None),
+            C.c_void_p(allow or None), int(allow_stride), int(k), int(scan_below), C.c_void_p(out_ids), C.c_void_p(out_d),
+            C.c_void_p(out_len), C.c_void_p(out_route or None), C.c_void_p(status), C.c_void_p(stream or None)))
 
     def search_batch_reranked(self, full, queries, sp=None, k=10):
         """an index over an F16Store, I8Store or I8QStore: search it, recompute every result's distance on the f32 store

@@ -482,6 +482,59 @@ impl GpuHnsw {
         check(sys::phnsw_filter_count_device(self.ix, filter_dev, filter_stride_words, nbitmaps, out_count_dev, stream));
     }
 
+    /// one filtered call that picks the scan or the graph walk per query and rescans what the walk left short
+    /// (`phnsw_search_filtered_auto`): every result holds min(k, candidates) entries and only ids `include` accepts.
+    /// `scan_below` 0 = the library's threshold, `u64::MAX` = always scan.  A graph-routed result is approximate
+    /// (`phnsw.h`).  Returns the results and one route per query.  Panics unless 1 <= k <= number_of_candidates
+    pub fn search_many_filtered_auto<F: Fn(VectorId) -> bool>(&self, queries: &[Vec<f32>], sp: SearchParameters, k: usize,
+                                                              scan_below: u64, include: F)
+                                                              -> (Vec<Vec<(VectorId, f32)>>, Vec<u32>) {
+        assert!(k >= 1 && k <= sp.number_of_candidates, "search_many_filtered_auto: k must be 1..number_of_candidates");
+        let psp = sp_c(sp);
+        let nq = queries.len();
+        let mut n64 = 0u64;
+        check(unsafe {
+            sys::phnsw_store_info(self.comparator.store.0, &mut n64, std::ptr::null_mut(), std::ptr::null_mut(),
+                                  std::ptr::null_mut(), std::ptr::null_mut())
+        });
+        let n = n64 as usize;
+        let mut words = vec![0u32; (n + 31) / 32];
+        for v in 0..n {
+            if include(VectorId(v)) {
+                words[v >> 5] |= 1u32 << (v & 31);
+            }
+        }
+        let mut q: Vec<f32> = Vec::with_capacity(nq * queries.first().map_or(0, |x| x.len()));
+        for x in queries {
+            q.extend_from_slice(x);
+        }
+        let (mut ids, mut d, mut len) = (vec![0u64; nq * k], vec![0f32; nq * k], vec![0u64; nq]);
+        let mut route = vec![0u32; nq];
+        check(unsafe {
+            sys::phnsw_search_filtered_auto(self.ix, q.as_ptr(), std::ptr::null(), nq as u64, &psp, std::ptr::null(), words.as_ptr(),
+                                            0, k as u64, scan_below, ids.as_mut_ptr(), d.as_mut_ptr(), len.as_mut_ptr(),
+                                            route.as_mut_ptr())
+        });
+        let rows = (0..nq).map(|i| (0..len[i] as usize).map(|j| (VectorId(ids[i * k + j] as usize), d[i * k + j])).collect()).collect();
+        (rows, route)
+    }
+
+    /// device form (`phnsw_search_filtered_auto_device`): u32 ids `[nq][k]`; synchronises `stream` up to twice
+    ///
+    /// # Safety
+    /// the pointers must be valid device allocations of the sizes `phnsw.h` documents for the call
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn search_filtered_auto_device(&self, queries_dev: *const f32, ldq: u32, qids_dev: *const u32, nq: u64,
+                                              sp: SearchParameters, exclude_dev: *const u32, filter_dev: *const u32,
+                                              filter_stride_words: u32, k: u64, scan_below: u64, out_ids_dev: *mut u32,
+                                              out_d_dev: *mut f32, out_len_dev: *mut u32, out_route_dev: *mut u32,
+                                              status_dev: *mut u32, stream: *mut c_void) {
+        let psp = sp_c(sp);
+        check(sys::phnsw_search_filtered_auto_device(self.ix, queries_dev, ldq, qids_dev, nq, &psp, exclude_dev, filter_dev,
+                                                     filter_stride_words, k, scan_below, out_ids_dev, out_d_dev, out_len_dev,
+                                                     out_route_dev, status_dev, stream));
+    }
+
     /// an index over a `to_f16()` comparator: search it, recompute every result's distance on the f32 comparator
     /// `full`, sort by (distance, id), keep the best `k` (`phnsw_f16_search_batch`)
     pub fn search_many_reranked(&self, full: &GpuComparator, queries: &[Vec<f32>], sp: SearchParameters, k: usize)

@@ -249,6 +249,17 @@ extern "C" {
                                               status_dev: *mut u32, stream: *mut c_void) -> c_int;
     pub fn phnsw_filter_count_device(ix: *const phnsw_index, filter_dev: *const u32, filter_stride_words: u32,
                                      nbitmaps: u64, out_count_dev: *mut u32, stream: *mut c_void) -> c_int;
+    // per query the scan or the graph walk, the scan again for short rows: min(k, candidates) entries, candidates only
+    pub fn phnsw_search_filtered_auto(ix: *const phnsw_index, queries: *const c_float, qids: *const u64, nq: u64,
+                                      sp: *const phnsw_search_params, exclude: *const u64, filter: *const u32,
+                                      filter_stride_words: u32, k: u64, scan_below: u64, out_ids: *mut u64,
+                                      out_d: *mut c_float, out_len: *mut u64, out_route: *mut u32) -> c_int;
+    pub fn phnsw_search_filtered_auto_device(ix: *const phnsw_index, queries_dev: *const c_float, ldq: u32,
+                                             qids_dev: *const u32, nq: u64, sp: *const phnsw_search_params,
+                                             exclude_dev: *const u32, filter_dev: *const u32, filter_stride_words: u32,
+                                             k: u64, scan_below: u64, out_ids_dev: *mut u32, out_d_dev: *mut c_float,
+                                             out_len_dev: *mut u32, out_route_dev: *mut u32, status_dev: *mut u32,
+                                             stream: *mut c_void) -> c_int;
     pub fn phnsw_index_counters(ix: *const phnsw_index, n_dist: *mut u64, n_hops: *mut u64) -> c_int;
     pub fn phnsw_last_search_kernel_ms(ix: *const phnsw_index, ms: *mut c_float) -> c_int;
     pub fn phnsw_last_search_dispatches(ix: *const phnsw_index, cap: u32, count: *mut u32, ms: *mut c_float,
