@@ -275,6 +275,51 @@ int phnsw_search_exact_filtered_device(const phnsw_index *ix, const float *queri
  * else every vector of the index.  out_count_dev [nbitmaps] u32, device memory; enqueued on `stream`. */
 int phnsw_filter_count_device(const phnsw_index *ix, const uint32_t *filter_dev, uint32_t filter_stride_words,
                               uint64_t nbitmaps, uint32_t *out_count_dev, void *stream);
+/* ---- exact top-k for ONE allow-list shared by the whole batch, as a distance table.  With a shared bitmap (tombstones,
+ * a category predicate, a tenant's bulk job) every query meets the same candidate rows: the call expands the bitmap to
+ * the ascending list of its candidates and computes queries x candidates distance tables with the kernels of the dense
+ * top layers (the f32 matrix cores for dot-product metrics at 256 / 768 / 1536 floats, the int8 matrix cores on an i8q
+ * store, the vector-unit tile pass for L2, ragged dimensions and fewer than 32 queries; PHNSW_TINY_VALU=1 forces the
+ * last), then selects the top k per query over the table.
+ * Arguments: those of phnsw_search_exact_filtered[_device] without filter_stride_words -- `filter` is one bitmap of
+ * ceil(n/32) words; NULL = the index's default filter (phnsw_index_set_filter_device), else every vector of the index.
+ * Candidates: exactly those of phnsw_search_exact_filtered -- v < n, bit set, v != exclude[q], v a vector of the bottom
+ * layer.  Result: the k candidates with the smallest (distance, id), ascending; out_len[q] = min(k, candidates of q);
+ * rows of k entries padded with PHNSW_EMPTY / f32::MAX; 1 <= k <= 1024.
+ * EQUALITY: the row of every query equals, in ids, distance bits, length and status, the row
+ * phnsw_search_exact_filtered returns for the same arguments with filter_stride_words 0; the distance has the bits of
+ * phnsw_distance_batch.  The result does not depend on the chunk sizes below.
+ * Checks, in this order: a null index or one without layers, then k outside 1..1024 (PHNSW_E_INVALID); then the store:
+ * f32, f16, i8 and i8q stores with rows of at most 1536 floats, every metric the store kind has -- a PQ store of either
+ * form and longer rows are PHNSW_E_UNSUPPORTED (phnsw_search_exact_filtered scans those); then nq == 0, a no-op; then
+ * exactly one of queries / qids and the outputs (PHNSW_E_INVALID); the host form then refuses a Stored query id at or
+ * past n as phnsw_search_exact_filtered does (PHNSW_E_INVALID).  phnsw_exact_shared_supported returns what the first
+ * three checks return, without running anything.
+ * Knobs (environment, read per call): PHNSW_DENSE_NODES, candidates per table (rounded up to a multiple of 64, default
+ * 8192); PHNSW_DENSE_TABLE_BYTES, the bytes of one table (default 1 GiB, below 4 GiB), which bounds the queries per table.
+ * Guidance (measured on 1M x 768 f32 rows, cosine, 10 000-query batches, k = 10, the three calls alternating in one
+ * run; profiles/filter_dense/README.md): against phnsw_search_exact_filtered with the same shared bitmap this call was
+ * the faster one in every cell, 6 x at 1 037 candidates rising to 18 x at 300 322, and no crossover was found (fewer
+ * candidates were not measured).  Against the strict graph walk of phnsw_search_batch_filtered at the minimal
+ * number_of_candidates (an APPROXIMATE result, recall@10 0.10-0.65) it was faster at 1 037, 9 988 and 20 043 candidates
+ * (146 x, 22 x, 7 x) and SLOWER at 99 217 (18.3 ms against 13.2 ms) and 300 322 (55.0 ms against 8.7 ms): the crossover
+ * lies between 20 000 and 99 000 candidates, and above it this call stands on its exact, bit-equal contract alone.
+ * f16, i8 and i8q stores, L2 and ragged dimensions (the vector-unit pass), other k and batch sizes: not measured.
+ * No other call routes here: phnsw_search_exact_filtered keeps scanning. */
+int phnsw_exact_shared_supported(const phnsw_index *ix, uint64_t k);
+int phnsw_search_exact_shared(const phnsw_index *ix, const float *queries, const uint64_t *qids, uint64_t nq,
+                              const uint64_t *exclude, const uint32_t *filter, uint64_t k, uint64_t *out_ids, float *out_d,
+                              uint64_t *out_len);
+/* device form: device pointers, u32 ids [nq][k] padded with 0xFFFFFFFF / f32::MAX; queries [nq][ldq] as for
+ * phnsw_search_batch_device.  status_dev[q]: 0 = ok, 4 = a Stored query id at or past n (the row is then empty, the
+ * other rows unaffected).  Unlike phnsw_search_exact_filtered_device this call SYNCHRONISES `stream`, once, to read the
+ * candidate count back (the tables' shape depends on it); the tables and the selection are enqueued after that and the
+ * call returns without waiting for them.  Thread safe like the other search calls: every call in flight has a scratch
+ * set of its own. */
+int phnsw_search_exact_shared_device(const phnsw_index *ix, const float *queries_dev, uint32_t ldq,
+                                     const uint32_t *qids_dev, uint64_t nq, const uint32_t *exclude_dev,
+                                     const uint32_t *filter_dev, uint64_t k, uint32_t *out_ids_dev, float *out_d_dev,
+                                     uint32_t *out_len_dev, uint32_t *status_dev, void *stream);
 /* ---- one filtered call that picks scan or graph walk per query, and rescans what the walk left short.  For batches
  * whose bitmaps differ widely (tenants, ACLs, tombstones plus a predicate): the caller neither counts nor splits.
  * Candidates: exactly those of phnsw_search_exact_filtered -- v < n, its bit set in q's bitmap, v != exclude[q], v a

@@ -364,6 +364,35 @@ class Hnsw {
     check(phnsw_search_exact_filtered_device(ix_, queries_dev, ldq, qids_dev, nq, exclude_dev, filter_dev, stride_words, k,
                                              out_ids_dev, out_d_dev, out_len_dev, status_dev, stream));
   }
+  // search_many_exact_filtered for ONE bitmap shared by all queries, computed as a queries x candidates distance table
+  // (phnsw_search_exact_shared): the same results, bit for bit.  `allow`: ceil(n / 32) words, empty = the default of
+  // set_filter_device, else every vector of the index.  f32, f16, i8 and i8q stores with rows up to 1536 floats
+  std::vector<SearchResult> search_many_exact_shared(const std::vector<const float *> &queries, uint64_t k,
+                                                     const std::vector<uint32_t> &allow) const {
+    const uint64_t nq = queries.size(), dim = c_->dim(), words = (c_->len() + 31) / 32;
+    if (k == 0 || k > 1024) throw Error(PHNSW_E_INVALID, "search_many_exact_shared: k must be 1..1024");
+    if (!allow.empty() && allow.size() < words)
+      throw Error(PHNSW_E_INVALID, "search_many_exact_shared: allow is shorter than one bitmap (ceil(n / 32) words)");
+    std::vector<float> q(nq * dim);
+    for (uint64_t i = 0; i < nq; i++) std::copy(queries[i], queries[i] + dim, q.begin() + i * dim);
+    std::vector<uint64_t> ids(nq * k), len(nq);
+    std::vector<float> d(nq * k);
+    check(phnsw_search_exact_shared(ix_, q.data(), nullptr, nq, nullptr, allow.empty() ? nullptr : allow.data(), k, ids.data(),
+                                    d.data(), len.data()));
+    std::vector<SearchResult> out(nq);
+    for (uint64_t i = 0; i < nq; i++)
+      for (uint64_t j = 0; j < len[i]; j++) out[i].push_back({ids[i * k + j], d[i * k + j]});
+    return out;
+  }
+  // zero-copy form (phnsw_search_exact_shared_device): u32 ids [nq][k]; synchronises `stream` once
+  void search_exact_shared_device(const float *queries_dev, uint32_t ldq, const uint32_t *qids_dev, uint64_t nq,
+                                  const uint32_t *exclude_dev, const uint32_t *filter_dev, uint64_t k, uint32_t *out_ids_dev,
+                                  float *out_d_dev, uint32_t *out_len_dev, uint32_t *status_dev, void *stream) const {
+    check(phnsw_search_exact_shared_device(ix_, queries_dev, ldq, qids_dev, nq, exclude_dev, filter_dev, k, out_ids_dev,
+                                           out_d_dev, out_len_dev, status_dev, stream));
+  }
+  // 0, or the code search_many_exact_shared would refuse this index and k with (phnsw_exact_shared_supported)
+  int exact_shared_supported(uint64_t k) const { return phnsw_exact_shared_supported(ix_, k); }
   // candidates of each of nbitmaps device bitmaps (phnsw_filter_count_device): what to choose the search call by
   void filter_count_device(const uint32_t *filter_dev, uint32_t stride_words, uint64_t nbitmaps, uint32_t *out_count_dev,
                            void *stream) const {

@@ -234,6 +234,7 @@ struct PhExactScratch {
 };
 
 struct PhAutoSet;  // filter_auto.hip: the scratch of one routed filtered search, one per concurrent call
+struct PhDenseSet;  // filter_dense.hip: the scratch of one exact search for a shared allow-list, one per concurrent call
 struct PhPendingLayer;
 struct PhHostStage;  // hostpath.hip: persistent staging of the host-pointer search entry points
 struct phnsw_index {
@@ -264,6 +265,8 @@ struct phnsw_index {
   uint32_t exact_next = 0;
   std::vector<PhAutoSet *> autos;  // filter_auto.hip: handed out under auto_mutex
   std::mutex auto_mutex;
+  std::vector<PhDenseSet *> denses;  // filter_dense.hip: handed out under dense_mutex
+  std::mutex dense_mutex;
 };
 
 // ---- kernel argument block for the batched greedy search ----
@@ -465,6 +468,7 @@ struct PhAutoCall {
 };
 int ph_auto_device(const phnsw_index *ix, const PhAutoCall &c);
 void ph_auto_free(phnsw_index *ix);
+void ph_dense_free(phnsw_index *ix);  // filter_dense.hip
 // the argument checks the exact entry points share (api.hip): index with layers, 1 <= k <= 1024, a store kind the
 // distance batch accepts
 int ph_exact_check(const phnsw_index *ix, uint64_t k, const char *call);
@@ -512,6 +516,10 @@ bool ph_tiny_matrix_cores(const phnsw_index *ix);  // the table of this index's 
 uint32_t ph_tiny_layer_count(const phnsw_index *ix, uint32_t n_layers, uint32_t ef);  // leading layers a launch may run densely
 uint64_t ph_tiny_max_positions(const phnsw_index *ix, uint32_t n_layers, uint32_t ef);  // 0 = no dense layers for this launch shape
 void ph_tiny_free(PhWorkspace &ws);
+// one table call of the exact search for a shared allow-list (filter_dense.hip) on a workspace of its own: D[p][t] for
+// positions [0, npos) and the VectorIds tnodes[0 .. tn), stride = tn rounded up to 64
+int ph_tiny_table_chunk(const phnsw_index *ix, PhWorkspace &ws, const float *queries, uint32_t ldq, const uint32_t *qids,
+                        uint32_t npos, const uint32_t *tnodes, uint32_t tn, float *D, hipStream_t stream, bool *kept);
 
 // launchers (search.hip)
 int ph_search_begin(PhWorkspace &ws, hipStream_t stream);

@@ -472,6 +472,55 @@ impl GpuHnsw {
                                                       stream));
     }
 
+    /// `search_many_exact_filtered` computed as a queries x candidates distance table (`phnsw_search_exact_shared`):
+    /// `include` is one predicate for the whole batch, so every query meets the same rows.  The same results, bit for
+    /// bit.  f32, f16, i8 and i8q stores with rows up to 1536 floats.  Panics unless 1 <= k <= 1024
+    pub fn search_many_exact_shared<F: Fn(VectorId) -> bool>(&self, queries: &[Vec<f32>], k: usize, include: F)
+                                                             -> Vec<Vec<(VectorId, f32)>> {
+        assert!((1..=1024).contains(&k), "search_many_exact_shared: k must be 1..1024");
+        let nq = queries.len();
+        let mut n64 = 0u64;
+        check(unsafe {
+            sys::phnsw_store_info(self.comparator.store.0, &mut n64, std::ptr::null_mut(), std::ptr::null_mut(),
+                                  std::ptr::null_mut(), std::ptr::null_mut())
+        });
+        let n = n64 as usize;
+        let mut words = vec![0u32; (n + 31) / 32];
+        for v in 0..n {
+            if include(VectorId(v)) {
+                words[v >> 5] |= 1u32 << (v & 31);
+            }
+        }
+        let mut q: Vec<f32> = Vec::with_capacity(nq * queries.first().map_or(0, |x| x.len()));
+        for x in queries {
+            q.extend_from_slice(x);
+        }
+        let (mut ids, mut d, mut len) = (vec![0u64; nq * k], vec![0f32; nq * k], vec![0u64; nq]);
+        check(unsafe {
+            sys::phnsw_search_exact_shared(self.ix, q.as_ptr(), std::ptr::null(), nq as u64, std::ptr::null(), words.as_ptr(),
+                                           k as u64, ids.as_mut_ptr(), d.as_mut_ptr(), len.as_mut_ptr())
+        });
+        (0..nq).map(|i| (0..len[i] as usize).map(|j| (VectorId(ids[i * k + j] as usize), d[i * k + j])).collect()).collect()
+    }
+
+    /// zero-copy form (`phnsw_search_exact_shared_device`): u32 ids `[nq][k]`; synchronises `stream` once
+    ///
+    /// # Safety
+    /// the pointers must be valid device allocations of the sizes `phnsw.h` documents for the call
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn search_exact_shared_device(&self, queries_dev: *const f32, ldq: u32, qids_dev: *const u32, nq: u64,
+                                             exclude_dev: *const u32, filter_dev: *const u32, k: u64,
+                                             out_ids_dev: *mut u32, out_d_dev: *mut f32, out_len_dev: *mut u32,
+                                             status_dev: *mut u32, stream: *mut c_void) {
+        check(sys::phnsw_search_exact_shared_device(self.ix, queries_dev, ldq, qids_dev, nq, exclude_dev, filter_dev, k,
+                                                    out_ids_dev, out_d_dev, out_len_dev, status_dev, stream));
+    }
+
+    /// 0, or the code `search_many_exact_shared` would be refused with (`phnsw_exact_shared_supported`)
+    pub fn exact_shared_supported(&self, k: usize) -> i32 {
+        unsafe { sys::phnsw_exact_shared_supported(self.ix, k as u64) }
+    }
+
     /// candidates of each of `nbitmaps` device bitmaps (`phnsw_filter_count_device`): what to choose between
     /// `search_many_filtered` and `search_many_exact_filtered` by
     ///

@@ -247,6 +247,16 @@ extern "C" {
                                               filter_dev: *const u32, filter_stride_words: u32, k: u64,
                                               out_ids_dev: *mut u32, out_d_dev: *mut c_float, out_len_dev: *mut u32,
                                               status_dev: *mut u32, stream: *mut c_void) -> c_int;
+    // the same exact top-k for ONE bitmap shared by the batch, as a distance table on the dense-layer table kernels
+    pub fn phnsw_exact_shared_supported(ix: *const phnsw_index, k: u64) -> c_int;
+    pub fn phnsw_search_exact_shared(ix: *const phnsw_index, queries: *const c_float, qids: *const u64, nq: u64,
+                                     exclude: *const u64, filter: *const u32, k: u64, out_ids: *mut u64,
+                                     out_d: *mut c_float, out_len: *mut u64) -> c_int;
+    pub fn phnsw_search_exact_shared_device(ix: *const phnsw_index, queries_dev: *const c_float, ldq: u32,
+                                            qids_dev: *const u32, nq: u64, exclude_dev: *const u32,
+                                            filter_dev: *const u32, k: u64, out_ids_dev: *mut u32,
+                                            out_d_dev: *mut c_float, out_len_dev: *mut u32, status_dev: *mut u32,
+                                            stream: *mut c_void) -> c_int;
     pub fn phnsw_filter_count_device(ix: *const phnsw_index, filter_dev: *const u32, filter_stride_words: u32,
                                      nbitmaps: u64, out_count_dev: *mut u32, stream: *mut c_void) -> c_int;
     // per query the scan or the graph walk, the scan again for short rows: min(k, candidates) entries, candidates only
