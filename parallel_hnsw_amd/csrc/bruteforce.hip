@@ -174,6 +174,10 @@ extern "C" int phnsw_bruteforce_topk_device(const phnsw_store *s, const float *q
   // chunk of base rows whose score matrix stays around 2.5 GB
   uint64_t chunk = std::max<uint64_t>(BF_TN, std::min<uint64_t>(s->n, (uint64_t)(640ull << 20) / nq / BF_TN * BF_TN));
   chunk = std::min<uint64_t>(chunk, 1u << 20);
+  if (const char *e = getenv("PHNSW_BF_CHUNK_ROWS")) {  // tuning knob (tests force many chunks), changes no result
+    const long long v = atoll(e);
+    if (v > 0) chunk = std::min<uint64_t>(((uint64_t)v + BF_TN - 1) / BF_TN * BF_TN, 1u << 20);
+  }
   float *scores = nullptr;
   uint64_t *best = nullptr;
   hipError_t e = hipMalloc(&scores, (size_t)nq * chunk * 4);
