@@ -250,7 +250,13 @@ int phnsw_index_set_filter_device(phnsw_index *ix, const uint32_t *filter_dev);
  * are ignored.  There is no entry-vector quirk: a disallowed id is never returned.
  * Result: the k candidates with the smallest (distance, id), ascending; out_len[q] = min(k, candidates of q); rows of k
  * entries padded with PHNSW_EMPTY / f32::MAX.  The distance of (q, v) has exactly the bits phnsw_distance_batch returns
- * for it on the same store; equal distances are ordered by id.  1 <= k <= 1024, else PHNSW_E_INVALID.  nq == 0 is a
+ * for it on the same store; equal distances are ordered by id.
+ * +inf (an L2 sum of squares past f32::MAX): a candidate at +inf is a candidate like any other and is returned, behind
+ * every finite one and in id order among its like, with the distance bits 0x7F800000; it counts in out_len.  The padding
+ * value f32::MAX therefore compares BELOW such entries: tell padding by out_len (or PHNSW_EMPTY), not by the distance.
+ * The graph walk (phnsw_search_batch[_filtered]) never returns a candidate at +inf -- the reference's queue never holds
+ * one -- so on such data this call and the walk differ by design; phnsw_search_exact_shared follows this call.
+ * 1 <= k <= 1024, else PHNSW_E_INVALID.  nq == 0 is a
  * no-op.  Exactly one of queries / qids.  Every store kind phnsw_distance_batch accepts (f32, f16, i8, i8q, PQ); a
  * shared-codebook PQ store is PHNSW_E_UNSUPPORTED, and so is a PQ store whose lookup table plus the scan's own LDS
  * (16 * k + 8704 bytes) exceed a workgroup's 160 KiB.
@@ -344,6 +350,11 @@ int phnsw_search_exact_shared_device(const phnsw_index *ix, const float *queries
  * fewer than min(k, c_q - e_q) entries (e_q = 1 iff exclude[q] is itself a candidate by bitmap and index membership),
  * or the walk overflowed its spill list, the query is scanned: its row is then the scan's and its route reads
  * PHNSW_ROUTE_GRAPH_THEN_SCAN.
+ * +inf: the walk never returns a candidate at +inf (an L2 sum past f32::MAX) while the scan returns it behind every
+ * finite one, in id order (see phnsw_search_exact_filtered; f32::MAX, the padding, compares below such entries).  A
+ * graph-routed query whose FINITE candidates number fewer than min(k, c_q - e_q) is therefore always left short by the
+ * walk and scanned: its route reads PHNSW_ROUTE_GRAPH_THEN_SCAN and its row ends in entries at +inf.  A query at +inf
+ * from the entry vector is outside the walk's contract, here as in phnsw_search_batch.
  * A graph-routed row is an APPROXIMATE result: its recall is that of the walk at this sp (the README's cells show
  * 0.45-0.67 at the minimal number_of_candidates).  The guarantee of this call is completeness -- the full
  * min(k, candidates) entries, candidates only -- not recall; scanned rows are exact.
