@@ -326,6 +326,61 @@ int phnsw_search_exact_shared_device(const phnsw_index *ix, const float *queries
                                      const uint32_t *qids_dev, uint64_t nq, const uint32_t *exclude_dev,
                                      const uint32_t *filter_dev, uint64_t k, uint32_t *out_ids_dev, float *out_d_dev,
                                      uint32_t *out_len_dev, uint32_t *status_dev, void *stream);
+/* ---- exact top-k for a TABLE of allow-lists with a selector per query, grouped by bitmap: a handful of distinct
+ * bitmaps (tenants, ACL classes), each shared by many queries of the batch.  The call groups the batch by bitmap on the
+ * device and runs every group as phnsw_search_exact_shared runs its batch -- the candidate list of the group's bitmap,
+ * queries x candidates distance tables on the table kernels, a select per query -- with one stream synchronisation for
+ * the whole call.  The caller neither replicates a bitmap per query (phnsw_search_exact_filtered's layout) nor splits
+ * the batch by bitmap on the host (one phnsw_search_exact_shared call per bitmap).
+ * Table: `filters` holds nfilters bitmaps, filter_stride_words apart; the stride is >= ceil(n/32) and REQUIRED (0 is
+ * PHNSW_E_INVALID); bit layout as everywhere; bits at or past n, and the words between ceil(n/32) and the stride, are
+ * ignored whatever they hold.  1 <= nfilters <= 0xFFFFFFFE.  filter_of[q] names the bitmap of query q, or is
+ * PHNSW_FILTER_ALL: no bitmap, every vector of the index.  filters and filter_of must not be NULL; the index's default
+ * filter (phnsw_index_set_filter_device) is NOT consulted: the caller passed a filter.
+ * Candidates of q: exactly those of phnsw_search_exact_filtered when q's bitmap is filters[filter_of[q]] -- v < n, bit
+ * set, v != exclude[q], v a vector of the bottom layer.
+ * EQUALITY: the row of every query equals, in ids, distance bits, length and status, the row
+ * phnsw_search_exact_filtered returns for that query with that bitmap (hence also phnsw_search_exact_shared's row for a
+ * group run alone); +inf, tie order by id and padding (PHNSW_EMPTY / f32::MAX) as there.  The result does not depend on
+ * how the queries are spread over the bitmaps, on their order in the batch, or on any knob below.
+ * Checks, in this order (as phnsw_search_exact_shared): a null index or one without layers, then k outside 1..1024
+ * (PHNSW_E_INVALID); then the store: f32, f16, i8 and i8q stores with rows of at most 1536 floats, else
+ * PHNSW_E_UNSUPPORTED (phnsw_exact_shared_supported answers for this call too); then nq == 0, a no-op; then exactly one
+ * of queries / qids, the outputs, the table arguments above and nq <= 2^31 - 2 (PHNSW_E_INVALID).  The host form then
+ * refuses, before any device work, a Stored query id at or past n and a selector that is neither below nfilters nor
+ * PHNSW_FILTER_ALL (PHNSW_E_INVALID; the message names the query).
+ * Knobs (environment, read per call): PHNSW_DENSE_NODES and PHNSW_DENSE_TABLE_BYTES as for phnsw_search_exact_shared,
+ * applied per group; PHNSW_GROUP_LIST_BYTES, the bytes of candidate lists and per-word offsets built at a time
+ * (default 256 MiB, at most 16 GiB): groups are taken in ascending bitmap order in rounds that fit it, a round always
+ * taking at least one group, so the scratch never grows as nfilters x n beyond it.  PHNSW_GROUP_TIMES=1 prints the
+ * steps' times of a call on stderr.
+ * Guidance (measured on 1M x 768 f32 rows, cosine, 10 000-query batches spread evenly over the bitmaps, k = 10, the
+ * variants alternating in one run; profiles/filter_grouped/README.md): against phnsw_search_exact_filtered with the
+ * table replicated per query this call was 8.3 x, 4.1 x and 1.8 x faster at 1, 8 and 64 bitmaps of 10 000 candidates,
+ * 3.7 x and 11.7 x at 8 bitmaps of 1 000 and 100 000 candidates, and FOUR TIMES SLOWER at 1000 bitmaps (groups of 10
+ * queries: 166 ms against 42 ms) -- every group pays its own table and select launches, and groups below 32 queries run
+ * on the vector units.  The crossover lies between 156 and 10 queries per group; below it the scan is the call.  Against
+ * one phnsw_search_exact_shared call per bitmap over queries gathered on the host (gather and scatter not timed) it was
+ * never slower and 1.2 x to 1.75 x faster from 8 bitmaps on.  Other store kinds, L2, ragged dimensions, other k, uneven
+ * groups and the host form: not measured.  No other call routes here. */
+enum { PHNSW_FILTER_ALL = 0xFFFFFFFFu }; /* filter_of[q]: no bitmap, every vector of the index */
+int phnsw_search_exact_grouped(const phnsw_index *ix, const float *queries, const uint64_t *qids, uint64_t nq,
+                               const uint64_t *exclude, const uint32_t *filters, uint32_t filter_stride_words,
+                               uint64_t nfilters, const uint32_t *filter_of, uint64_t k,
+                               uint64_t *out_ids, float *out_d, uint64_t *out_len);
+/* device form: device pointers, u32 ids [nq][k] padded with 0xFFFFFFFF / f32::MAX; queries [nq][ldq] as for
+ * phnsw_search_batch_device.  status_dev[q]: 0 = ok; 4 = a Stored query id at or past n; 6 = a selector that is neither
+ * below nfilters nor PHNSW_FILTER_ALL; 7 = the bitmap of q changed while the call read it (its candidate list no longer
+ * had the counted length).  With 4, 6 and 7 the row is empty and out_len[q] is 0; every other query is unaffected, and
+ * no bitmap word outside the table is ever read.  The host form reports 7 as PHNSW_E_INVALID.
+ * The call SYNCHRONISES `stream` once: that read fetches the groups and the candidate count of every bitmap in use
+ * together.  Everything after is enqueued and the call returns without waiting.  Selectors that change during that
+ * read are PHNSW_E_INVALID.  Thread safe like the other exact calls: every call in flight has a scratch set of its own. */
+int phnsw_search_exact_grouped_device(const phnsw_index *ix, const float *queries_dev, uint32_t ldq,
+                               const uint32_t *qids_dev, uint64_t nq, const uint32_t *exclude_dev,
+                               const uint32_t *filters_dev, uint32_t filter_stride_words, uint64_t nfilters,
+                               const uint32_t *filter_of_dev, uint64_t k, uint32_t *out_ids_dev, float *out_d_dev,
+                               uint32_t *out_len_dev, uint32_t *status_dev, void *stream);
 /* ---- one filtered call that picks scan or graph walk per query, and rescans what the walk left short.  For batches
  * whose bitmaps differ widely (tenants, ACLs, tombstones plus a predicate): the caller neither counts nor splits.
  * Candidates: exactly those of phnsw_search_exact_filtered -- v < n, its bit set in q's bitmap, v != exclude[q], v a

@@ -391,6 +391,43 @@ class Hnsw {
     check(phnsw_search_exact_shared_device(ix_, queries_dev, ldq, qids_dev, nq, exclude_dev, filter_dev, k, out_ids_dev,
                                            out_d_dev, out_len_dev, status_dev, stream));
   }
+  // search_many_exact_filtered for a TABLE of bitmaps and a selector per query (phnsw_search_exact_grouped): query i may
+  // return the vectors of bitmap allow_of[i] (PHNSW_FILTER_ALL: every vector of the index).  The batch is grouped by
+  // bitmap on the device and every group runs as search_many_exact_shared runs its batch: the same results, bit for
+  // bit.  `allows`: nfilters bitmaps stride_words apart, stride_words >= ceil(n / 32).  Throws on a bad k, table or
+  // selector before the library is called
+  std::vector<SearchResult> search_many_exact_grouped(const std::vector<const float *> &queries, uint64_t k,
+                                                      const std::vector<uint32_t> &allows, uint32_t stride_words,
+                                                      const std::vector<uint32_t> &allow_of) const {
+    const uint64_t nq = queries.size(), dim = c_->dim(), words = (c_->len() + 31) / 32;
+    if (k == 0 || k > 1024) throw Error(PHNSW_E_INVALID, "search_many_exact_grouped: k must be 1..1024");
+    if (stride_words == 0 || stride_words < words || allows.size() < stride_words || allows.size() % stride_words)
+      throw Error(PHNSW_E_INVALID, "search_many_exact_grouped: allows holds whole bitmaps stride_words apart, at least one, "
+                                   "stride_words >= ceil(n / 32)");
+    const uint64_t nfilters = allows.size() / stride_words;
+    if (allow_of.size() != nq) throw Error(PHNSW_E_INVALID, "search_many_exact_grouped: one selector per query");
+    for (uint32_t f : allow_of)
+      if (f != PHNSW_FILTER_ALL && f >= nfilters)
+        throw Error(PHNSW_E_INVALID, "search_many_exact_grouped: a selector outside the table");
+    std::vector<float> q(nq * dim);
+    for (uint64_t i = 0; i < nq; i++) std::copy(queries[i], queries[i] + dim, q.begin() + i * dim);
+    std::vector<uint64_t> ids(nq * k), len(nq);
+    std::vector<float> d(nq * k);
+    check(phnsw_search_exact_grouped(ix_, q.data(), nullptr, nq, nullptr, allows.data(), stride_words, nfilters, allow_of.data(),
+                                     k, ids.data(), d.data(), len.data()));
+    std::vector<SearchResult> out(nq);
+    for (uint64_t i = 0; i < nq; i++)
+      for (uint64_t j = 0; j < len[i]; j++) out[i].push_back({ids[i * k + j], d[i * k + j]});
+    return out;
+  }
+  // zero-copy form (phnsw_search_exact_grouped_device): u32 ids [nq][k]; synchronises `stream` once
+  void search_exact_grouped_device(const float *queries_dev, uint32_t ldq, const uint32_t *qids_dev, uint64_t nq,
+                                   const uint32_t *exclude_dev, const uint32_t *filters_dev, uint32_t stride_words,
+                                   uint64_t nfilters, const uint32_t *filter_of_dev, uint64_t k, uint32_t *out_ids_dev,
+                                   float *out_d_dev, uint32_t *out_len_dev, uint32_t *status_dev, void *stream) const {
+    check(phnsw_search_exact_grouped_device(ix_, queries_dev, ldq, qids_dev, nq, exclude_dev, filters_dev, stride_words, nfilters,
+                                            filter_of_dev, k, out_ids_dev, out_d_dev, out_len_dev, status_dev, stream));
+  }
   // 0, or the code search_many_exact_shared would refuse this index and k with (phnsw_exact_shared_supported)
   int exact_shared_supported(uint64_t k) const { return phnsw_exact_shared_supported(ix_, k); }
   // candidates of each of nbitmaps device bitmaps (phnsw_filter_count_device): what to choose the search call by

@@ -553,6 +553,7 @@ extern "C" void phnsw_index_destroy(phnsw_index *ix) {
   ph_exact_free(ix);
   ph_auto_free(ix);
   ph_dense_free(ix);
+  ph_grouped_free(ix);
   ph_build_table_free(ix);
   if (ix->totals) hipFree(ix->totals);
   phnsw_store_destroy(ix->store);

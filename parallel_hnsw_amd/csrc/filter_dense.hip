@@ -412,8 +412,10 @@ struct HostBlocks {
   }
 };
 
-// the checks every entry point makes before it looks at another argument: index, k, store kind and row length
-int dense_check(const phnsw_index *ix, uint64_t k, const char *call) {
+}  // namespace
+
+// the checks every entry point makes (filter_grouped.hip's too) before it looks at another argument: index, k, store kind and row length
+int ph_dense_check(const phnsw_index *ix, uint64_t k, const char *call) {
   if (!ix || ix->layers.empty()) {
     ph_set_error("%s: null index or index without layers", call);
     return PHNSW_E_INVALID;
@@ -436,8 +438,6 @@ int dense_check(const phnsw_index *ix, uint64_t k, const char *call) {
   return 0;
 }
 
-}  // namespace
-
 void ph_dense_free(phnsw_index *ix) {
   for (PhDenseSet *s : ix->denses) {
     if (s->done) {
@@ -457,7 +457,7 @@ void ph_dense_free(phnsw_index *ix) {
 // ------------------------------------------------------------------ C ABI
 
 extern "C" int phnsw_exact_shared_supported(const phnsw_index *ix, uint64_t k) try {
-  return dense_check(ix, k, "phnsw_exact_shared_supported");
+  return ph_dense_check(ix, k, "phnsw_exact_shared_supported");
 } catch (...) { return ph_caught(); }
 
 extern "C" int phnsw_search_exact_shared_device(const phnsw_index *ix, const float *queries_dev, uint32_t ldq,
@@ -466,7 +466,7 @@ extern "C" int phnsw_search_exact_shared_device(const phnsw_index *ix, const flo
                                                 float *out_d_dev, uint32_t *out_len_dev, uint32_t *status_dev,
                                                 void *stream) try {
   const char *const call = "phnsw_search_exact_shared_device";
-  PH_TRY(dense_check(ix, k, call));
+  PH_TRY(ph_dense_check(ix, k, call));
   if (nq == 0) return 0;
   if (((!queries_dev) == (!qids_dev)) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev || nq > 0xFFFFFFFFull ||
       (queries_dev && (ldq < ix->store->ld || (ldq % 4) || ((uintptr_t)queries_dev % 16)))) {
@@ -491,7 +491,7 @@ extern "C" int phnsw_search_exact_shared(const phnsw_index *ix, const float *que
                                          const uint64_t *exclude, const uint32_t *filter, uint64_t k, uint64_t *out_ids,
                                          float *out_d, uint64_t *out_len) try {
   const char *const call = "phnsw_search_exact_shared";
-  PH_TRY(dense_check(ix, k, call));
+  PH_TRY(ph_dense_check(ix, k, call));
   if (nq == 0) return 0;
   if ((!queries) == (!qids)) {
     ph_set_error("%s: pass queries or qids (exactly one)", call);

@@ -235,6 +235,7 @@ struct PhExactScratch {
 
 struct PhAutoSet;  // filter_auto.hip: the scratch of one routed filtered search, one per concurrent call
 struct PhDenseSet;  // filter_dense.hip: the scratch of one exact search for a shared allow-list, one per concurrent call
+struct PhGroupedSet;  // filter_grouped.hip: the scratch of one exact search over a table of allow-lists, one per concurrent call
 struct PhPendingLayer;
 struct PhHostStage;  // hostpath.hip: persistent staging of the host-pointer search entry points
 struct phnsw_index {
@@ -267,6 +268,8 @@ struct phnsw_index {
   std::mutex auto_mutex;
   std::vector<PhDenseSet *> denses;  // filter_dense.hip: handed out under dense_mutex
   std::mutex dense_mutex;
+  std::vector<PhGroupedSet *> groupeds;  // filter_grouped.hip: handed out under grouped_mutex
+  std::mutex grouped_mutex;
 };
 
 // ---- kernel argument block for the batched greedy search ----
@@ -469,6 +472,9 @@ struct PhAutoCall {
 int ph_auto_device(const phnsw_index *ix, const PhAutoCall &c);
 void ph_auto_free(phnsw_index *ix);
 void ph_dense_free(phnsw_index *ix);  // filter_dense.hip
+// the checks the table calls make before they look at another argument: index, k, store kind and row length
+int ph_dense_check(const phnsw_index *ix, uint64_t k, const char *call);  // filter_dense.hip
+void ph_grouped_free(phnsw_index *ix);  // filter_grouped.hip
 // the argument checks the exact entry points share (api.hip): index with layers, 1 <= k <= 1024, a store kind the
 // distance batch accepts
 int ph_exact_check(const phnsw_index *ix, uint64_t k, const char *call);
@@ -520,6 +526,10 @@ void ph_tiny_free(PhWorkspace &ws);
 // positions [0, npos) and the VectorIds tnodes[0 .. tn), stride = tn rounded up to 64
 int ph_tiny_table_chunk(const phnsw_index *ix, PhWorkspace &ws, const float *queries, uint32_t ldq, const uint32_t *qids,
                         uint32_t npos, const uint32_t *tnodes, uint32_t tn, float *D, hipStream_t stream, bool *kept);
+// ... and of the exact search over a table of allow-lists (filter_grouped.hip): position p is query order[p]
+int ph_tiny_table_chunk_ordered(const phnsw_index *ix, PhWorkspace &ws, const float *queries, uint32_t ldq,
+                                const uint32_t *qids, const uint32_t *order, uint32_t npos, const uint32_t *tnodes,
+                                uint32_t tn, float *D, hipStream_t stream, bool *kept);
 
 // launchers (search.hip)
 int ph_search_begin(PhWorkspace &ws, hipStream_t stream);

@@ -897,6 +897,15 @@ int ph_tiny_table_chunk(const phnsw_index *ix, PhWorkspace &ws, const float *que
                     2, kept);
 }
 
+// the same for a group of the exact call over a table of allow-lists (filter_grouped.hip): position p is query order[p]
+// of the whole batch's queries / checked Stored ids
+int ph_tiny_table_chunk_ordered(const phnsw_index *ix, PhWorkspace &ws, const float *queries, uint32_t ldq,
+                                const uint32_t *qids, const uint32_t *order, uint32_t npos, const uint32_t *tnodes,
+                                uint32_t tn, float *D, hipStream_t stream, bool *kept) {
+  return tiny_table(ix, ws, ph_dist_args(ix->store), queries, ldq, qids, order, npos, tnodes, tn, tiny_stride_of(tn), D, stream,
+                    2, kept);
+}
+
 int ph_tiny_prepare(const phnsw_index *ix, PhWorkspace &ws, PhSearchArgs &a, uint32_t max_layers, hipStream_t stream) {
   a.tiny_layers = 0;
   a.tiny_rows = 0;

@@ -516,6 +516,64 @@ impl GpuHnsw {
                                                     out_ids_dev, out_d_dev, out_len_dev, status_dev, stream));
     }
 
+    /// `search_many_exact_filtered` for a table of predicates and a selector per query (`phnsw_search_exact_grouped`):
+    /// query i may return the vectors `includes[include_of[i]]` accepts, every vector of the index when `include_of[i]`
+    /// is `None`.  The batch is grouped by predicate on the device and every group runs as `search_many_exact_shared`
+    /// runs its batch: the same results, bit for bit.  Panics unless 1 <= k <= 1024, `includes` is not empty,
+    /// `include_of` has one entry per query and every selector names a predicate
+    pub fn search_many_exact_grouped<F: Fn(VectorId) -> bool>(&self, queries: &[Vec<f32>], k: usize, includes: &[F],
+                                                              include_of: &[Option<usize>])
+                                                              -> Vec<Vec<(VectorId, f32)>> {
+        assert!((1..=1024).contains(&k), "search_many_exact_grouped: k must be 1..1024");
+        assert!(!includes.is_empty(), "search_many_exact_grouped: an empty table of predicates");
+        let nq = queries.len();
+        assert!(include_of.len() == nq, "search_many_exact_grouped: one selector per query");
+        assert!(include_of.iter().all(|s| s.map_or(true, |i| i < includes.len())),
+                "search_many_exact_grouped: a selector outside the table");
+        let mut n64 = 0u64;
+        check(unsafe {
+            sys::phnsw_store_info(self.comparator.store.0, &mut n64, std::ptr::null_mut(), std::ptr::null_mut(),
+                                  std::ptr::null_mut(), std::ptr::null_mut())
+        });
+        let n = n64 as usize;
+        let stride = (n + 31) / 32;
+        let mut words = vec![0u32; includes.len() * stride];
+        for (f, include) in includes.iter().enumerate() {
+            for v in 0..n {
+                if include(VectorId(v)) {
+                    words[f * stride + (v >> 5)] |= 1u32 << (v & 31);
+                }
+            }
+        }
+        let of: Vec<u32> = include_of.iter().map(|s| s.map_or(sys::PHNSW_FILTER_ALL, |i| i as u32)).collect();
+        let mut q: Vec<f32> = Vec::with_capacity(nq * queries.first().map_or(0, |x| x.len()));
+        for x in queries {
+            q.extend_from_slice(x);
+        }
+        let (mut ids, mut d, mut len) = (vec![0u64; nq * k], vec![0f32; nq * k], vec![0u64; nq]);
+        check(unsafe {
+            sys::phnsw_search_exact_grouped(self.ix, q.as_ptr(), std::ptr::null(), nq as u64, std::ptr::null(), words.as_ptr(),
+                                            stride as u32, includes.len() as u64, of.as_ptr(), k as u64, ids.as_mut_ptr(),
+                                            d.as_mut_ptr(), len.as_mut_ptr())
+        });
+        (0..nq).map(|i| (0..len[i] as usize).map(|j| (VectorId(ids[i * k + j] as usize), d[i * k + j])).collect()).collect()
+    }
+
+    /// zero-copy form (`phnsw_search_exact_grouped_device`): u32 ids `[nq][k]`; synchronises `stream` once
+    ///
+    /// # Safety
+    /// the pointers must be valid device allocations of the sizes `phnsw.h` documents for the call
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn search_exact_grouped_device(&self, queries_dev: *const f32, ldq: u32, qids_dev: *const u32, nq: u64,
+                                              exclude_dev: *const u32, filters_dev: *const u32, filter_stride_words: u32,
+                                              nfilters: u64, filter_of_dev: *const u32, k: u64, out_ids_dev: *mut u32,
+                                              out_d_dev: *mut f32, out_len_dev: *mut u32, status_dev: *mut u32,
+                                              stream: *mut c_void) {
+        check(sys::phnsw_search_exact_grouped_device(self.ix, queries_dev, ldq, qids_dev, nq, exclude_dev, filters_dev,
+                                                     filter_stride_words, nfilters, filter_of_dev, k, out_ids_dev, out_d_dev,
+                                                     out_len_dev, status_dev, stream));
+    }
+
     /// 0, or the code `search_many_exact_shared` would be refused with (`phnsw_exact_shared_supported`)
     pub fn exact_shared_supported(&self, k: usize) -> i32 {
         unsafe { sys::phnsw_exact_shared_supported(self.ix, k as u64) }

@@ -23,6 +23,7 @@ pub const PHNSW_E_UNSUPPORTED: c_int = -7;
 pub const PHNSW_E_NOMEM: c_int = -8;
 
 pub const PHNSW_FILTER_STRICT: u32 = 1; // also drop disallowed ids (the entry vector) from the final rows
+pub const PHNSW_FILTER_ALL: u32 = 0xFFFF_FFFF; // filter_of[q] of phnsw_search_exact_grouped: no bitmap, every vector of the index
 
 pub const PHNSW_METRIC_COSINE_HALF: c_int = 0; // (1 - dot)/2   bigvec.rs:47-53
 pub const PHNSW_METRIC_ONE_MINUS_DOT: c_int = 1; // 1 - dot       lib.rs:1985-1991
@@ -257,6 +258,17 @@ extern "C" {
                                             filter_dev: *const u32, k: u64, out_ids_dev: *mut u32,
                                             out_d_dev: *mut c_float, out_len_dev: *mut u32, status_dev: *mut u32,
                                             stream: *mut c_void) -> c_int;
+    // ... and for a table of bitmaps with a selector per query (PHNSW_FILTER_ALL: no bitmap), grouped on the device
+    pub fn phnsw_search_exact_grouped(ix: *const phnsw_index, queries: *const c_float, qids: *const u64, nq: u64,
+                                      exclude: *const u64, filters: *const u32, filter_stride_words: u32, nfilters: u64,
+                                      filter_of: *const u32, k: u64, out_ids: *mut u64, out_d: *mut c_float,
+                                      out_len: *mut u64) -> c_int;
+    pub fn phnsw_search_exact_grouped_device(ix: *const phnsw_index, queries_dev: *const c_float, ldq: u32,
+                                             qids_dev: *const u32, nq: u64, exclude_dev: *const u32,
+                                             filters_dev: *const u32, filter_stride_words: u32, nfilters: u64,
+                                             filter_of_dev: *const u32, k: u64, out_ids_dev: *mut u32,
+                                             out_d_dev: *mut c_float, out_len_dev: *mut u32, status_dev: *mut u32,
+                                             stream: *mut c_void) -> c_int;
     pub fn phnsw_filter_count_device(ix: *const phnsw_index, filter_dev: *const u32, filter_stride_words: u32,
                                      nbitmaps: u64, out_count_dev: *mut u32, stream: *mut c_void) -> c_int;
     // per query the scan or the graph walk, the scan again for short rows: min(k, candidates) entries, candidates only
