@@ -381,6 +381,75 @@ int phnsw_search_exact_grouped_device(const phnsw_index *ix, const float *querie
                                const uint32_t *filters_dev, uint32_t filter_stride_words, uint64_t nfilters,
                                const uint32_t *filter_of_dev, uint64_t k, uint32_t *out_ids_dev, float *out_d_dev,
                                uint32_t *out_len_dev, uint32_t *status_dev, void *stream);
+/* ---- exact top-k by ROW LABEL, posting lists instead of bitmaps: the filter of a partition (a tenant, a collection,
+ * an ACL class).  Every vector carries one u32 label and a query wants the rows of one label.  A phnsw_labels handle
+ * turns the label column once into posting lists -- the ascending VectorIds of every label, CSR -- on the device; a
+ * search derives nothing from a bitmap and reads nothing back.  A label column is 4 bytes per vector whatever the
+ * number of labels (1000 bitmaps over 1M rows are 125 MB, 100 000 are 12.5 GB).
+ * Listed: vector v is listed under labels[v] iff v < n, labels[v] != PHNSW_LABEL_NONE and v is a vector of the index's
+ * bottom layer (the candidate test of the other exact calls, without a bitmap).  Labels are arbitrary 32-bit values,
+ * neither dense nor small.  n must equal the store's vector count, else PHNSW_E_INVALID.
+ * The handle is a SNAPSHOT: it remembers the index, the store's n and the bottom layer's node count.  A search with a
+ * handle made for another index, or after either count has changed, is PHNSW_E_INVALID ("the labels are stale"); make a
+ * new handle.  The check cannot see more than that: an index destroyed and another created at the same address with the
+ * same two counts but other vectors in its bottom layer passes it -- destroy the handle with its index.  Creation synchronises (the null stream, or `stream` of the device form, whose labels_dev is device
+ * memory read before the call returns).  phnsw_labels_info: the n it was made for, the distinct labels that list a
+ * vector, the listed vectors, the longest list; any output may be NULL.  phnsw_labels_count_device writes, per query,
+ * the length of the list of want_dev[q], 0 for a label nobody carries and for PHNSW_LABEL_NONE: phnsw_filter_count_device's
+ * figure for the equivalent bitmap; enqueued on `stream`.  phnsw_labels_destroy waits for the calls in flight that use
+ * the handle; NULL is a no-op.  The handle does not own the index and must not outlive it in use.
+ * Candidates of q: the listed vectors of label want[q], except exclude[q].  want[q] == PHNSW_LABEL_NONE, or a label
+ * nobody carries, is no error: the row is empty, the length 0, the status 0.
+ * EQUALITY: the row of every query equals, in ids, distance bits, length and status, the row
+ * phnsw_search_exact_filtered returns for that query with the bitmap {v : labels[v] == want[q]}: ascending (distance,
+ * id), the distances with phnsw_distance_batch's bits, +inf and tie order as there, rows of k entries padded with
+ * PHNSW_EMPTY / f32::MAX, 1 <= k <= 1024.  The result does not depend on how the batch is spread over the labels, on its
+ * order, or on any knob below.
+ * Checks, in this order: a null index or one without layers, then k outside 1..1024, then a null or stale `lb`
+ * (PHNSW_E_INVALID); then the store: every kind phnsw_search_exact_filtered scans (f32, f16, i8, i8q, PQ), with its
+ * limits -- a shared-codebook PQ store, rows above 1536 floats and a PQ table that does not fit beside the scan's LDS
+ * are PHNSW_E_UNSUPPORTED; then nq == 0, a no-op; then exactly one of queries / qids, the outputs, `want` and
+ * nq <= 2^31 - 2 (PHNSW_E_INVALID).  The host form then refuses a Stored query id at or past n (PHNSW_E_INVALID).
+ * Every message names the call.
+ * How: per query a binary search of its label; the batch sorted by label; on f32 / f16 / i8 row stores a wave then takes
+ * a TILE of up to T queries of one label and reads every row of (a slice of) that label's list once for the whole tile;
+ * i8q and PQ stores, and T = 1, scan the list per query.  Knobs (environment, read per call, none changes a result):
+ * PHNSW_LABEL_TILE, 1 = the per-query scan only, N = a cap on T (default 16; T also shrinks with k and the row length
+ * so that a CU holds four tile waves); PHNSW_LABEL_SLICES forces the number of slices a list is cut into.
+ * Guidance (measured on 1M x 768 f32 rows, cosine, 10 000-query batches spread evenly over the labels, k = 10, the
+ * variants alternating in one run; profiles/filter_labeled/README.md): against phnsw_search_exact_filtered with per-query
+ * bitmaps this call was 1.4 x to 3.8 x faster in every cell (1, 8, 64 labels of 10 000 rows, 1000 labels of 1000 rows, 8
+ * labels of 1000 and of 100 000 rows).  Against phnsw_search_exact_grouped it was SLOWER wherever groups are large --
+ * 0.26 x and 0.36 x at 1 and 8 labels of 10 000 rows, 0.69 x and 0.29 x at 8 labels of 1000 and 100 000 rows -- and faster
+ * at 64 labels (1.5 x) and at 1000 labels of 1000 rows (1.24 ms against 42.9 ms).  The tile path was 2.2 x to 3.6 x faster
+ * than PHNSW_LABEL_TILE=1 except where a label has one query or a short list (0.94 x, 0.64 x).  Other store kinds, L2,
+ * other k, uneven labels and the host form: not measured. */
+typedef struct phnsw_labels phnsw_labels;
+#define PHNSW_LABEL_NONE 0xFFFFFFFFu /* labels[v]: v is not listed; want[q]: an empty row */
+int phnsw_labels_create(const phnsw_index *ix, const uint32_t *labels, uint64_t n, phnsw_labels **out); /* host labels [n] */
+int phnsw_labels_create_device(const phnsw_index *ix, const uint32_t *labels_dev, uint64_t n, void *stream,
+                               phnsw_labels **out);
+int phnsw_labels_info(const phnsw_labels *lb, uint64_t *n, uint64_t *nlabels, uint64_t *listed, uint64_t *longest);
+int phnsw_labels_count_device(const phnsw_labels *lb, const uint32_t *want_dev, uint64_t nq, uint32_t *out_count_dev,
+                              void *stream);
+void phnsw_labels_destroy(phnsw_labels *lb); /* waits for the calls in flight that use it */
+int phnsw_search_exact_labeled(const phnsw_index *ix, const phnsw_labels *lb, const float *queries, const uint64_t *qids,
+                               uint64_t nq, const uint64_t *exclude, const uint32_t *want, uint64_t k, uint64_t *out_ids,
+                               float *out_d, uint64_t *out_len);
+/* device form: device pointers, u32 ids [nq][k] padded with 0xFFFFFFFF / f32::MAX; queries [nq][ldq] as for
+ * phnsw_search_batch_device.  status_dev[q]: 0 = ok, 4 = a Stored query id at or past n (the row is then empty, the
+ * other rows unaffected).  The call ENQUEUES AND RETURNS: it never synchronises `stream`; where a label's list lies and
+ * how the batch falls into tiles stay on the device.  One exception to "returns at once": scratch is kept with the handle
+ * and grows with the largest call; a call that needs MORE scratch than the set it was given holds waits on the host for
+ * that set's previous call to finish before the old block goes back to the pool (calls of one size, or shrinking ones,
+ * never wait).  Thread safe like the other exact calls: every call in flight has a scratch set of its own.  Calls on one
+ * stream share one set; calls on different streams get sets of their own (four per handle before they share one behind
+ * its event), so they may overlap.  The sets -- grouping arrays of 28 bytes per query, the sort's temporaries, nq x slices
+ * x k keys -- stay with the handle until phnsw_labels_destroy. */
+int phnsw_search_exact_labeled_device(const phnsw_index *ix, const phnsw_labels *lb, const float *queries_dev, uint32_t ldq,
+                                      const uint32_t *qids_dev, uint64_t nq, const uint32_t *exclude_dev,
+                                      const uint32_t *want_dev, uint64_t k, uint32_t *out_ids_dev, float *out_d_dev,
+                                      uint32_t *out_len_dev, uint32_t *status_dev, void *stream);
 /* ---- one filtered call that picks scan or graph walk per query, and rescans what the walk left short.  For batches
  * whose bitmaps differ widely (tenants, ACLs, tombstones plus a predicate): the caller neither counts nor splits.
  * Candidates: exactly those of phnsw_search_exact_filtered -- v < n, its bit set in q's bitmap, v != exclude[q], v a

@@ -158,6 +158,8 @@ struct Layer {
 
 using SearchResult = std::vector<std::pair<VectorId, float>>;
 
+class Labels;
+
 class Hnsw {
  public:
   BuildParameters build_parameters;
@@ -428,6 +430,17 @@ class Hnsw {
     check(phnsw_search_exact_grouped_device(ix_, queries_dev, ldq, qids_dev, nq, exclude_dev, filters_dev, stride_words, nfilters,
                                             filter_of_dev, k, out_ids_dev, out_d_dev, out_len_dev, status_dev, stream));
   }
+  // search_many_exact_filtered by row label (phnsw_search_exact_labeled): query i may return the vectors `labels` lists
+  // under want[i]; PHNSW_LABEL_NONE or a label nobody carries gives an empty result.  The same results, bit for bit, as
+  // the bitmaps {v : label of v == want[i]} give, from posting lists.  Throws on a bad k and on want.size() != queries
+  // before the library is called, and on a handle made for another index (defined below, after Labels)
+  inline std::vector<SearchResult> search_many_exact_labeled(const std::vector<const float *> &queries, uint64_t k,
+                                                             const Labels &labels, const std::vector<uint32_t> &want) const;
+  // zero-copy form (phnsw_search_exact_labeled_device): u32 ids [nq][k]; enqueued on `stream`, never synchronises it
+  inline void search_exact_labeled_device(const Labels &labels, const float *queries_dev, uint32_t ldq, const uint32_t *qids_dev,
+                                          uint64_t nq, const uint32_t *exclude_dev, const uint32_t *want_dev, uint64_t k,
+                                          uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev, uint32_t *status_dev,
+                                          void *stream) const;
   // 0, or the code search_many_exact_shared would refuse this index and k with (phnsw_exact_shared_supported)
   int exact_shared_supported(uint64_t k) const { return phnsw_exact_shared_supported(ix_, k); }
   // candidates of each of nbitmaps device bitmaps (phnsw_filter_count_device): what to choose the search call by
@@ -570,6 +583,63 @@ class Hnsw {
   phnsw_index *ix_ = nullptr;
   const Comparator *c_ = nullptr;
 };
+
+// phnsw_labels: one u32 label per vector of the index's store, turned once into posting lists on the device.  A snapshot:
+// after the store or the index has changed a search refuses it as stale.  The Hnsw must outlive its use
+class Labels {
+ public:
+  static constexpr uint32_t NONE = PHNSW_LABEL_NONE;  // a vector that is not listed; a wanted label with an empty result
+  Labels(const Hnsw &hnsw, const std::vector<uint32_t> &labels) {
+    check(phnsw_labels_create(hnsw.handle(), labels.data(), labels.size(), &lb_));
+  }
+  // labels_dev: u32 [store n] in device memory, read on `stream`, which is synchronised
+  Labels(const Hnsw &hnsw, const uint32_t *labels_dev, uint64_t n, void *stream) {
+    check(phnsw_labels_create_device(hnsw.handle(), labels_dev, n, stream, &lb_));
+  }
+  Labels(const Labels &) = delete;
+  Labels &operator=(const Labels &) = delete;
+  Labels(Labels &&o) noexcept : lb_(o.lb_) { o.lb_ = nullptr; }
+  ~Labels() { phnsw_labels_destroy(lb_); }
+  uint64_t label_count() const { return info(1); }
+  uint64_t listed() const { return info(2); }
+  uint64_t longest() const { return info(3); }
+  void count_device(const uint32_t *want_dev, uint64_t nq, uint32_t *out_count_dev, void *stream) const {
+    check(phnsw_labels_count_device(lb_, want_dev, nq, out_count_dev, stream));
+  }
+  phnsw_labels *handle() const { return lb_; }
+
+ private:
+  uint64_t info(int which) const {
+    uint64_t v[4] = {0, 0, 0, 0};
+    check(phnsw_labels_info(lb_, &v[0], &v[1], &v[2], &v[3]));
+    return v[which];
+  }
+  phnsw_labels *lb_ = nullptr;
+};
+
+inline std::vector<SearchResult> Hnsw::search_many_exact_labeled(const std::vector<const float *> &queries, uint64_t k,
+                                                                 const Labels &labels, const std::vector<uint32_t> &want) const {
+  const uint64_t nq = queries.size(), dim = c_->dim();
+  if (k == 0 || k > 1024) throw Error(PHNSW_E_INVALID, "search_many_exact_labeled: k must be 1..1024");
+  if (want.size() != nq) throw Error(PHNSW_E_INVALID, "search_many_exact_labeled: one wanted label per query");
+  std::vector<float> q(nq * dim);
+  for (uint64_t i = 0; i < nq; i++) std::copy(queries[i], queries[i] + dim, q.begin() + i * dim);
+  std::vector<uint64_t> ids(nq * k), len(nq);
+  std::vector<float> d(nq * k);
+  check(phnsw_search_exact_labeled(ix_, labels.handle(), q.data(), nullptr, nq, nullptr, want.data(), k, ids.data(), d.data(),
+                                   len.data()));
+  std::vector<SearchResult> out(nq);
+  for (uint64_t i = 0; i < nq; i++)
+    for (uint64_t j = 0; j < len[i]; j++) out[i].push_back({ids[i * k + j], d[i * k + j]});
+  return out;
+}
+inline void Hnsw::search_exact_labeled_device(const Labels &labels, const float *queries_dev, uint32_t ldq,
+                                              const uint32_t *qids_dev, uint64_t nq, const uint32_t *exclude_dev,
+                                              const uint32_t *want_dev, uint64_t k, uint32_t *out_ids_dev, float *out_d_dev,
+                                              uint32_t *out_len_dev, uint32_t *status_dev, void *stream) const {
+  check(phnsw_search_exact_labeled_device(ix_, labels.handle(), queries_dev, ldq, qids_dev, nq, exclude_dev, want_dev, k,
+                                          out_ids_dev, out_d_dev, out_len_dev, status_dev, stream));
+}
 
 // QuantizedHnsw  pq.rs:120-131, 287-364 (per-sub-space codebooks, u8 codes)
 class QuantizedHnsw {

@@ -1,7 +1,8 @@
 """parallel_hnsw_amd: MI355X-native HNSW build + search behind the public surface of the
 Rust crate terminusdb-labs/parallel-hnsw (hot path only)."""
 from ._lib import BuildParams, OptimizationParams, PhnswError, SearchParams, build_lib, lib  # noqa: F401
-from .hnsw import (EMPTY, FILTER_ALL, METRIC_COSINE_HALF, METRIC_L2, METRIC_ONE_MINUS_DOT, BuildParameters, Hnsw, Layer,  # noqa: F401
+from .hnsw import (EMPTY, FILTER_ALL, LABEL_NONE, Labels, METRIC_COSINE_HALF, METRIC_L2, METRIC_ONE_MINUS_DOT, BuildParameters,  # noqa: F401
+                   Hnsw, Layer,
                    SearchParameters, Stored, Unstored, VectorStore, PqStore, SharedPqStore, F16Store, I8Store, I8QStore,
                    QuantizedHnsw, stream_create_beside)
 from .sharded import (EmulatedComm, GpuEngine, PythonEngine, ShardedBuilder, TorchComm, build_sharded,  # noqa: F401,E402

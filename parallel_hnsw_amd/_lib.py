@@ -141,6 +141,13 @@ SYMBOLS = {
     "phnsw_search_exact_grouped": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _u32, _u64, _vp, _u64, _vp, _vp, _vp]),
     "phnsw_search_exact_grouped_device": (_i32, [_vp, _vp, _u32, _vp, _u64, _vp, _vp, _u32, _u64, _vp, _u64, _vp, _vp, _vp,
                                                  _vp, _vp]),
+    "phnsw_labels_create": (_i32, [_vp, _vp, _u64, _pp]),
+    "phnsw_labels_create_device": (_i32, [_vp, _vp, _u64, _vp, _pp]),
+    "phnsw_labels_info": (_i32, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "phnsw_labels_count_device": (_i32, [_vp, _vp, _u64, _vp, _vp]),
+    "phnsw_labels_destroy": (None, [_vp]),
+    "phnsw_search_exact_labeled": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "phnsw_search_exact_labeled_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "phnsw_filter_count_device": (_i32, [_vp, _vp, _u32, _u64, _vp, _vp]),
     "phnsw_search_filtered_auto": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _u32, _u64, _u64, _vp, _vp, _vp, _vp]),
     "phnsw_search_filtered_auto_device": (_i32, [_vp, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _u32, _u64, _u64, _vp, _vp, _vp,

@@ -1,0 +1,931 @@
+// Exact top-k by ROW LABEL (phnsw_labels_*, phnsw_search_exact_labeled[_device]): the filter of a partition -- a tenant,
+// a collection, an ACL class.  Every vector carries one u32 label and a query wants the rows of one label.  The
+// candidate lists are a property of the data: posting lists in CSR form, built once per handle; a call derives nothing
+// from a bitmap and reads nothing back.
+//
+//   listed under labels[v]  iff  v < n, labels[v] != PHNSW_LABEL_NONE, v a vector of the bottom layer
+//   candidates of query q   =    the listed vectors of want[q], except exclude[q]
+//   result                  =    the k candidates with the smallest (distance, id), ascending
+//
+//   construction  ph_label_key_kernel (the label, or NONE where the vector is not listed), stable radix sort of
+//                 (label, id), ph_label_flags_kernel, exclusive sum, ph_label_heads_kernel: values, first, ids
+//   a call     1. ph_labeled_lookup_kernel: per query the slot of its label (label_plan.h), radix sort of (slot, query):
+//                 the queries of one label are adjacent positions; ph_labeled_tileflag_kernel, exclusive sum,
+//                 ph_labeled_tiles_kernel: the tile table and its count, on the device
+//              2. ph_labeled_scan_kernel: one wave64 per (position, slice of its list); ids 64 at a time from the
+//                 posting list into dist.batch of the store's policy -- every store kind, and T = 1
+//              3. ph_labeled_tile_kernel (f32 / f16 / i8 row stores, T > 1): one wave64 per (tile of up to T queries of
+//                 ONE label, slice of that label's list); every candidate row is read once for the whole tile
+//                 ph_labeled_merge_kernel: the slices' lists of a position through the same running top-k
+//
+// Equality with phnsw_search_exact_filtered over the bitmap {v : labels[v] == want[q]}: the candidate sets are equal by
+// the definition above, the keys are distinct, so the k smallest are one set in one order however the list is cut; the
+// distances of path 2 are dist.batch's, and those of path 3 go through the same functions with the same operands in the
+// same order (chain_partial with the row as x and the query as q, wave_sum4, finalize_metric), four rows at a time as
+// batch_distances takes them.  What filter_exact.hip has beyond the shared headers is restated here; no existing
+// kernel is touched (profiles/filter_labeled/).
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cstdlib>
+#include <vector>
+
+#include "exact_slices.h"
+#include "exact_topk.h"
+#include "filter_candidate.h"
+#include "label_plan.h"
+#include "phnsw_device.h"
+
+#define PH_TRY(x)          \
+  do {                     \
+    int rc__ = (x);        \
+    if (rc__) return rc__; \
+  } while (0)
+
+struct PhLabeledSet;
+struct PhLabelResident {  // resident waves of one kernel at one dynamic LDS size
+  const void *fn;
+  size_t lds;
+  uint64_t waves;
+};
+struct phnsw_labels {
+  const phnsw_index *ix = nullptr;  // the index the lists were made for, and what it looked like then
+  uint64_t n = 0;
+  uint32_t n_nodes = 0;
+  int device = 0;
+  uint64_t nlabels = 0, listed = 0, longest = 0;
+  uint32_t *values = nullptr;  // [nlabels] ascending
+  uint32_t *first = nullptr;   // [nlabels + 1]
+  uint32_t *ids = nullptr;     // [listed] (allocated [n]): ascending within a label
+  std::mutex mutex;
+  std::vector<PhLabeledSet *> sets;  // handed out under mutex, one per call in flight
+  std::vector<PhLabelResident> resident;  // under mutex
+  int cus = 0;                            // compute units of the device, 0 = not asked yet
+};
+
+// ------------------------------------------------------------------ construction
+
+__global__ __launch_bounds__(256) void ph_label_key_kernel(const uint32_t *labels, uint32_t n, uint32_t n_nodes,
+                                                           const uint32_t *nodes, const uint32_t *vec2node, uint32_t *keys,
+                                                           uint32_t *iota) {
+  const uint32_t nlim = ph_exact_id_limit(n, n_nodes, nodes, vec2node);
+  for (uint64_t v = (uint64_t)blockIdx.x * 256u + threadIdx.x; v < n; v += (uint64_t)gridDim.x * 256u) {
+    const bool listed = v < nlim && (!vec2node || vec2node[v] != PH_EMPTY32);
+    keys[v] = listed ? labels[v] : PHNSW_LABEL_NONE;
+    iota[v] = (uint32_t)v;
+  }
+}
+
+// flags [n + 1]: 1 where a label starts (NONE sorts last and starts nothing); head[1] = listed, the first NONE position
+__global__ __launch_bounds__(256) void ph_label_flags_kernel(const uint32_t *skeys, uint32_t n, uint32_t *flags, uint32_t *head) {
+  for (uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x; p <= n; p += (uint64_t)gridDim.x * 256u) {
+    const bool none = p == n || skeys[p] == PHNSW_LABEL_NONE;
+    const bool none_before = p > 0 && skeys[p - 1u] == PHNSW_LABEL_NONE;
+    flags[p] = !none && (p == 0 || skeys[p] != skeys[p - 1u]) ? 1u : 0u;
+    if (none && !none_before) head[1] = (uint32_t)p;
+  }
+}
+
+__global__ __launch_bounds__(256) void ph_label_heads_kernel(const uint32_t *skeys, const uint32_t *flags, const uint32_t *slots,
+                                                             uint32_t n, uint32_t nlabels, uint32_t listed, uint32_t *values,
+                                                             uint32_t *first) {
+  for (uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x; p <= n; p += (uint64_t)gridDim.x * 256u) {
+    if (p == n) {
+      first[nlabels] = listed;
+    } else if (flags[p]) {
+      const uint32_t s = slots[p];
+      if (s < nlabels) values[s] = skeys[p], first[s] = (uint32_t)p;
+    }
+  }
+}
+
+// ------------------------------------------------------------------ a call: lookup, grouping, tiles
+
+struct PhLabeledArgs {
+  PhDistArgs dist;
+  const float *queries;  // [nq][ldq] or nullptr
+  uint32_t ldq;
+  const uint32_t *qids, *exclude, *want;  // [nq]; qids, exclude nullable
+  uint32_t nq, n, k, slices, T;
+  // the posting lists
+  const uint32_t *values, *first, *ids;
+  uint32_t nlabels;
+  // the grouping (label_plan.h)
+  uint32_t *slot, *iota;            // [nq] by query
+  const uint32_t *sslot, *order;    // [nq] by position: its slot, its query
+  uint32_t *flags;                  // [nq + 1]
+  const uint32_t *tidx;             // [nq + 1]: exclusive sum of flags
+  uint32_t *tile_first, *head;      // [nq]; head[0] = tiles
+  uint32_t pq_lds;                  // bytes of dynamic LDS in front of the scan's own: a PQ store's table
+  uint64_t *scratch;                // slices > 1: [nq positions][slices][k] keys, each list ascending, KEY_NONE padded
+  uint32_t *out_ids;                // [nq][k]
+  float *out_d;
+  uint32_t *out_len, *status;  // [nq]
+};
+
+__global__ __launch_bounds__(256) void ph_labeled_lookup_kernel(PhLabeledArgs a) {
+  for (uint64_t q = (uint64_t)blockIdx.x * 256u + threadIdx.x; q < a.nq; q += (uint64_t)gridDim.x * 256u) {
+    const bool bad_query = !a.queries && a.qids[q] >= a.n;
+    a.slot[q] = bad_query ? PH_LABEL_SLOT_NONE : ph_label_slot(a.values, a.nlabels, a.want[q], PHNSW_LABEL_NONE);
+    a.iota[q] = (uint32_t)q;
+  }
+}
+
+__global__ __launch_bounds__(256) void ph_labeled_tileflag_kernel(PhLabeledArgs a) {
+  for (uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x; p <= a.nq; p += (uint64_t)gridDim.x * 256u)
+    a.flags[p] = p < a.nq && ph_label_tile_head(a.sslot, p, a.T) ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(256) void ph_labeled_tiles_kernel(PhLabeledArgs a) {
+  for (uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x; p <= a.nq; p += (uint64_t)gridDim.x * 256u) {
+    if (p == a.nq)
+      a.head[0] = a.tidx[p];
+    else if (a.flags[p])
+      a.tile_first[a.tidx[p]] = (uint32_t)p;  // tidx[p] < tiles <= nq
+  }
+}
+
+__global__ __launch_bounds__(256) void ph_labeled_count_kernel(const uint32_t *values, const uint32_t *first, uint32_t nlabels,
+                                                               const uint32_t *want, uint64_t nq, uint32_t *out_count) {
+  for (uint64_t q = (uint64_t)blockIdx.x * 256u + threadIdx.x; q < nq; q += (uint64_t)gridDim.x * 256u) {
+    const uint32_t s = ph_label_slot(values, nlabels, want[q], PHNSW_LABEL_NONE);
+    out_count[q] = s == PH_LABEL_SLOT_NONE ? 0u : first[s + 1u] - first[s];
+  }
+}
+
+// ------------------------------------------------------------------ path 2: the per-query list scan
+
+// One wave64 per (position, slice of its list); work item = slice * nq + position (slice-major, position-minor, the
+// positions label-major): the waves resident together read the same rows.
+template <class Dist>
+__global__ __launch_bounds__(64) void ph_labeled_scan_kernel(PhLabeledArgs a) {
+  extern __shared__ float labeled_lds[];
+  const uint32_t lane = threadIdx.x;
+  uint64_t *const keys = (uint64_t *)((char *)labeled_lds + a.pq_lds);
+  const uint64_t items = (uint64_t)a.nq * a.slices;
+  for (uint64_t item = blockIdx.x; item < items; item += gridDim.x) {
+    const uint32_t pos = (uint32_t)(item % a.nq), slice = (uint32_t)(item / a.nq);
+    const uint32_t q = a.order[pos], s = a.sslot[pos];
+    __syncthreads();  // the previous item's LDS (table, lists) is done with
+    const bool bad_query = !a.queries && a.qids[q] >= a.n;
+    Dist dist;
+    if (a.queries)
+      dist.prepare_raw(a.dist, a.queries + (uint64_t)q * a.ldq, labeled_lds, lane);
+    else if (!bad_query)
+      dist.prepare_stored(a.dist, a.qids[q], labeled_lds, lane);
+    PhExactTopK top;
+    top.cur = keys, top.nxt = keys + a.k, top.sv = keys + 2u * a.k, top.len = 0, top.k = a.k;
+    const uint32_t ex = a.exclude ? a.exclude[q] : PH_EMPTY32;
+    const uint32_t at = s == PH_LABEL_SLOT_NONE ? 0u : a.first[s];
+    const uint32_t len = s == PH_LABEL_SLOT_NONE ? 0u : a.first[s + 1u] - at;  // a bad query's slot is NONE
+    const uint32_t *const list = a.ids + at;
+    uint64_t b0, b1;
+    ph_label_slice_range(slice, a.slices, len, &b0, &b1);
+    for (uint64_t b = b0; b < b1; b++) {
+      const uint32_t j = (uint32_t)b * PH_LABEL_BATCH + lane;
+      const bool ok = j < len;
+      const uint32_t id = ok ? list[j] : 0u;  // a listed id: a row of the store
+      const float d = dist.batch(a.dist, __ballot(ok), id, lane);
+      top.insert(ok && id != ex ? mkkey(d, id) : KEY_NONE, lane);
+    }
+    if (a.slices == 1u) {
+      ph_exact_write_row(a, q, top.cur, top.len, bad_query, lane);
+    } else {
+      uint64_t *const out = a.scratch + ((uint64_t)pos * a.slices + slice) * a.k;
+      for (uint32_t i = lane; i < a.k; i += 64u) out[i] = i < top.len ? top.cur[i] : KEY_NONE;
+    }
+  }
+}
+
+// One wave per position: the slices' ascending lists merged through the same running top-k (as ph_exact_merge_kernel).
+__global__ __launch_bounds__(64) void ph_labeled_merge_kernel(PhLabeledArgs a) {
+  extern __shared__ float labeled_lds[];
+  const uint32_t lane = threadIdx.x;
+  uint64_t *const keys = (uint64_t *)labeled_lds;
+  for (uint32_t pos = blockIdx.x; pos < a.nq; pos += gridDim.x) {
+    const uint32_t q = a.order[pos];
+    __syncthreads();
+    PhExactTopK top;
+    top.cur = keys, top.nxt = keys + a.k, top.sv = keys + 2u * a.k, top.len = 0, top.k = a.k;
+    for (uint32_t s = 0; s < a.slices; s++) {
+      const uint64_t *const list = a.scratch + ((uint64_t)pos * a.slices + s) * a.k;
+      for (uint32_t b = 0; b < a.k; b += 64u)
+        if (!top.insert(b + lane < a.k ? list[b + lane] : KEY_NONE, lane)) break;
+    }
+    ph_exact_write_row(a, q, top.cur, top.len, !a.queries && a.qids[q] >= a.n, lane);
+  }
+}
+
+// ------------------------------------------------------------------ path 3: the tile scan
+
+// LDS of a tile wave: [T][ld] query values (what prepare_raw / prepare_stored would hold), then per query the scan's
+// lists [2k + 64] keys, then [T][64] collected distances, then [T][4] state words {len, list in use, query, exclude}.
+struct PhTileLds {
+  float *qrow;
+  uint64_t *keys;
+  float *dbuf;
+  uint32_t *state;
+};
+
+// Batches [b0, b1) of the list for the tsz queries of the tile.  The ids of a batch sit one per lane; with every lane
+// below m a candidate, candidate g is lane g: batch_distances' compaction is the identity.  Four rows are in flight, as
+// rows_partial loads them; each (row, query) pair then goes through chain_partial, wave_sum4 and finalize_metric with
+// the operands batch_distances gives them.
+template <int NV, class R, bool EXACT, bool L2>
+__device__ __forceinline__ void ph_labeled_tile_batches(const PhLabeledArgs &a, const PhTileLds &l, uint32_t tsz,
+                                                        const uint32_t *list, uint32_t len, uint64_t b0, uint64_t b1,
+                                                        uint32_t lane) {
+  const uint32_t nv4 = a.dist.nv4, keys_per = 2u * a.k + 64u;
+  for (uint64_t b = b0; b < b1; b++) {
+    const uint32_t j0 = (uint32_t)b * PH_LABEL_BATCH, j = j0 + lane;
+    const uint32_t m = min(PH_LABEL_BATCH, len - j0);  // >= 1: b < batches of len
+    const bool ok = lane < m;
+    const uint32_t id = ok ? list[j] : 0u;  // a listed id: a row of the store
+    const uint64_t off = (uint64_t)id * (uint64_t)a.dist.rows.stride;
+    const uint32_t olo = (uint32_t)off, ohi = (uint32_t)(off >> 32);
+    __syncthreads();  // the previous batch's distances have been taken
+    for (uint32_t g = 0; g < m; g += 4u) {
+      const typename R::chunk *r[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const uint32_t c = min(g + (uint32_t)u, m - 1u);  // short tail: the last row again (same value, unused)
+        const uint64_t o = ((uint64_t)rl32(ohi, (int)c) << 32) | rl32(olo, (int)c);
+        r[u] = (const typename R::chunk *)((const char *)a.dist.rows.base + o);
+      }
+      typename R::chunk raw[4][NV];
+      typename R::aux ax[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        ax[u] = R::row_aux(r[u]);
+#pragma unroll
+        for (int k = 0; k < NV; k++) {
+          uint32_t c = lane + 64u * k;
+          if (!EXACT) c = c < nv4 ? c : nv4 - 1;
+          raw[u][k] = R::load(r[u], c);
+        }
+      }
+      float4 x[4][NV];
+#pragma unroll
+      for (int u = 0; u < 4; u++)
+#pragma unroll
+        for (int k = 0; k < NV; k++) x[u][k] = R::widen(raw[u][k], ax[u]);
+      // where wave_sum4 leaves row u: lanes {0, 32, 16, 48}[u] + 0..15
+      const uint32_t u_mine = (((lane >> 4) & 1u) << 1) | (lane >> 5);
+      const bool writer = (lane & 15u) == 0u && g + u_mine < m;
+      for (uint32_t t = 0; t < tsz; t++) {
+        const float4 *const qr = (const float4 *)(l.qrow + (uint64_t)t * a.dist.ld);
+        float4 qv[NV];
+#pragma unroll
+        for (int k = 0; k < NV; k++) {
+          const uint32_t c = lane + 64u * k;
+          qv[k] = (EXACT || c < nv4) ? qr[EXACT ? c : min(c, nv4 - 1u)] : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+        float p[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) p[u] = chain_partial<NV, EXACT, L2>(x[u], qv, nv4, lane);
+        const float d4 = finalize_metric(wave_sum4(p[0], p[1], p[2], p[3]), a.dist.metric);
+        if (writer) l.dbuf[t * 64u + g + u_mine] = d4;
+      }
+    }
+    __syncthreads();  // the batch's distances are there
+    for (uint32_t t = 0; t < tsz; t++) {
+      uint32_t *const st = l.state + 4u * t;
+      uint64_t *const kb = l.keys + (uint64_t)t * keys_per;
+      const uint32_t flip = rfl32(st[1]), ex = rfl32(st[3]);
+      PhExactTopK top;
+      top.cur = flip ? kb + a.k : kb, top.nxt = flip ? kb : kb + a.k, top.sv = kb + 2u * a.k, top.len = rfl32(st[0]), top.k = a.k;
+      const float d = l.dbuf[t * 64u + lane];
+      top.insert(ok && id != ex ? mkkey(d, id) : KEY_NONE, lane);
+      __syncthreads();
+      if (lane == 0) st[0] = top.len, st[1] = top.cur == kb ? 0u : 1u;
+    }
+  }
+}
+
+// One wave64 per (tile, slice of the tile's list); work item = slice * nq + tile (nq bounds the tiles; the count is a
+// device word), tiles label-major.
+template <int NV, class R>
+__global__ __launch_bounds__(64) void ph_labeled_tile_kernel(PhLabeledArgs a) {
+  extern __shared__ float labeled_lds[];
+  const uint32_t lane = threadIdx.x;
+  const uint32_t keys_per = 2u * a.k + 64u;
+  PhTileLds l;
+  l.qrow = labeled_lds;
+  l.keys = (uint64_t *)(l.qrow + (uint64_t)a.T * a.dist.ld);  // ld % 4 == 0: 16-byte aligned
+  l.dbuf = (float *)(l.keys + (uint64_t)a.T * keys_per);
+  l.state = (uint32_t *)(l.dbuf + a.T * 64u);
+  const uint32_t ntiles = min(a.head[0], a.nq);
+  const uint64_t items = (uint64_t)a.nq * a.slices;
+  for (uint64_t item = blockIdx.x; item < items; item += gridDim.x) {
+    const uint32_t ti = (uint32_t)(item % a.nq), slice = (uint32_t)(item / a.nq);
+    if (ti >= ntiles) continue;  // uniform over the wave
+    const uint32_t p0 = a.tile_first[ti];  // < nq
+    const uint32_t s = a.sslot[p0];
+    const uint32_t tsz = ph_label_tile_size(a.sslot, a.nq, p0, a.T);
+    __syncthreads();  // the previous item's LDS is done with
+    for (uint32_t t = 0; t < tsz; t++) {
+      const uint32_t q = a.order[p0 + t];
+      float4 *const qr = (float4 *)(l.qrow + (uint64_t)t * a.dist.ld);
+      const bool bad_query = !a.queries && a.qids[q] >= a.n;
+      if (a.queries) {
+        const float4 *const src = (const float4 *)(a.queries + (uint64_t)q * a.ldq);
+        for (uint32_t c = lane; c < a.dist.nv4; c += 64u) qr[c] = src[c];
+      } else if (!bad_query) {
+        const typename R::chunk *row = R::row(a.dist.rows, a.qids[q]);
+        const typename R::aux ax = R::row_aux(row);
+        for (uint32_t c = lane; c < a.dist.nv4; c += 64u) qr[c] = R::widen(R::load(row, c), ax);
+      }
+      if (lane == 0) {
+        uint32_t *const st = l.state + 4u * t;
+        st[0] = 0u, st[1] = 0u, st[2] = q, st[3] = a.exclude ? a.exclude[q] : PH_EMPTY32;
+      }
+    }
+    __syncthreads();
+    const uint32_t at = s == PH_LABEL_SLOT_NONE ? 0u : a.first[s];
+    const uint32_t len = s == PH_LABEL_SLOT_NONE ? 0u : a.first[s + 1u] - at;  // a bad query's slot is NONE
+    const uint32_t *const list = a.ids + at;
+    uint64_t b0, b1;
+    ph_label_slice_range(slice, a.slices, len, &b0, &b1);
+    const bool exact = a.dist.nv4 == 64u * NV, l2 = a.dist.metric == PHNSW_METRIC_L2;  // wave-uniform
+    if (exact) {
+      if (l2)
+        ph_labeled_tile_batches<NV, R, true, true>(a, l, tsz, list, len, b0, b1, lane);
+      else
+        ph_labeled_tile_batches<NV, R, true, false>(a, l, tsz, list, len, b0, b1, lane);
+    } else {
+      if (l2)
+        ph_labeled_tile_batches<NV, R, false, true>(a, l, tsz, list, len, b0, b1, lane);
+      else
+        ph_labeled_tile_batches<NV, R, false, false>(a, l, tsz, list, len, b0, b1, lane);
+    }
+    __syncthreads();
+    for (uint32_t t = 0; t < tsz; t++) {
+      const uint32_t *const st = l.state + 4u * t;
+      const uint32_t tlen = rfl32(st[0]), q = rfl32(st[2]);
+      const uint64_t *const cur = l.keys + (uint64_t)t * keys_per + (rfl32(st[1]) ? a.k : 0u);
+      if (a.slices == 1u) {
+        ph_exact_write_row(a, q, cur, tlen, !a.queries && a.qids[q] >= a.n, lane);
+      } else {
+        uint64_t *const out = a.scratch + ((uint64_t)(p0 + t) * a.slices + slice) * a.k;
+        for (uint32_t i = lane; i < a.k; i += 64u) out[i] = i < tlen ? cur[i] : KEY_NONE;
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------ launchers
+
+typedef void (*PhLabeledFn)(PhLabeledArgs);
+template <template <int, int> class D>
+static PhLabeledFn labeled_rows_fn(uint32_t nv4) {
+  switch (ph_chunk_count(nv4)) {
+    case 1: return ph_labeled_scan_kernel<D<1, 4>>;
+    case 3: return ph_labeled_scan_kernel<D<3, 4>>;
+    case 6: return ph_labeled_scan_kernel<D<6, 4>>;
+    default: return nullptr;
+  }
+}
+static PhLabeledFn labeled_scan_fn(const phnsw_store *s) {
+  switch (s->kind) {
+    case PH_ROWS_PQ: return ph_labeled_scan_kernel<DistPQ>;
+    case PH_ROWS_F16: return labeled_rows_fn<DistF16>(s->ld / 4);
+    case PH_ROWS_I8: return labeled_rows_fn<DistI8>(s->ld / 4);
+    case PH_ROWS_I8Q: return labeled_rows_fn<DistI8Q>(s->ld / 4);
+    default: return labeled_rows_fn<DistF32>(s->ld / 4);
+  }
+}
+template <class R>
+static PhLabeledFn labeled_tile_rows_fn(uint32_t nv4) {
+  switch (ph_chunk_count(nv4)) {
+    case 1: return ph_labeled_tile_kernel<1, R>;
+    case 3: return ph_labeled_tile_kernel<3, R>;
+    case 6: return ph_labeled_tile_kernel<6, R>;
+    default: return nullptr;
+  }
+}
+// the tile kernel of a store, nullptr where only the per-query scan serves it (i8q, PQ)
+static PhLabeledFn labeled_tile_fn(const phnsw_store *s) {
+  switch (s->kind) {
+    case PH_ROWS_F32: return labeled_tile_rows_fn<RowF32>(s->ld / 4);
+    case PH_ROWS_F16: return labeled_tile_rows_fn<RowF16>(s->ld / 4);
+    case PH_ROWS_I8: return labeled_tile_rows_fn<RowI8>(s->ld / 4);
+    default: return nullptr;
+  }
+}
+
+// A call's scratch, kept with the HANDLE, one set per call in flight, after the pattern of PhGroupedSet: nothing goes
+// back to the pool while work that uses it may still be enqueued.  `done` closes the last call that used the set; the
+// next one's stream waits.
+struct PhLabeledSet {
+  void *pre = nullptr, *tmp = nullptr, *keys = nullptr;
+  size_t pre_bytes = 0, tmp_bytes = 0, keys_bytes = 0;
+  hipEvent_t done = nullptr;
+  hipStream_t stream = nullptr;  // the host form's
+  hipStream_t last = nullptr;    // the stream of the last call that used the set; has_last: there was one
+  bool has_last = false;
+  uint64_t tmp_nq = 0;           // the batch size tmp_need was asked of hipCUB for (0: none yet)
+  size_t tmp_need = 0;
+  bool in_use = false;
+};
+
+struct PhLabeledCall {
+  const float *queries;
+  uint32_t ldq;
+  const uint32_t *qids, *exclude, *want;
+  uint64_t nq;
+  uint32_t k;
+  uint32_t *out_ids;
+  float *out_d;
+  uint32_t *out_len, *status;
+  hipStream_t stream;
+};
+
+namespace {
+
+const size_t PH_LABEL_SETS = 4;  // scratch sets a handle makes before calls share one behind its event
+
+// own_stream: the host form, which runs on the set's own stream (`stream` is then ignored)
+PhLabeledSet *set_acquire(phnsw_labels *lb, hipStream_t stream, bool own_stream) {
+  // First a set whose last call ran on this very stream: stream order already protects it, so back-to-back calls on one
+  // stream share one set however far the device is behind.  Then a set whose last call has finished.  Then, while fewer
+  // than PH_LABEL_SETS exist, a new one, so that calls on different streams overlap; past that a free set whose event
+  // the call's stream waits for.  A handle so holds at most max(PH_LABEL_SETS, calls inside the library at once) sets,
+  // each as large as the largest call it served, until phnsw_labels_destroy.
+  std::lock_guard<std::mutex> g(lb->mutex);
+  if (!own_stream)
+    for (PhLabeledSet *s : lb->sets)
+      if (!s->in_use && !s->stream && s->has_last && s->last == stream) {
+        s->in_use = true;
+        return s;
+      }
+  PhLabeledSet *busy = nullptr;
+  for (PhLabeledSet *s : lb->sets) {
+    if (s->in_use) continue;
+    if (!s->done || hipEventQuery(s->done) == hipSuccess) {
+      s->in_use = true;
+      return s;
+    }
+    busy = s;
+  }
+  (void)hipGetLastError();  // hipErrorNotReady of the query is no error of the call
+  if (busy && lb->sets.size() >= PH_LABEL_SETS) {
+    busy->in_use = true;
+    return busy;
+  }
+  PhLabeledSet *s = new PhLabeledSet();
+  s->in_use = true;
+  lb->sets.push_back(s);
+  return s;
+}
+// the one drain of every return path: the set's event closes what the call enqueued, then the set is handed back
+struct SetGuard {
+  phnsw_labels *lb;
+  PhLabeledSet *set;
+  hipStream_t stream;
+  ~SetGuard() {
+    if (set->done) hipEventRecord(set->done, stream);
+    std::lock_guard<std::mutex> g(lb->mutex);
+    set->last = stream, set->has_last = true;
+    set->in_use = false;
+  }
+};
+
+int block_ensure(PhLabeledSet &s, void **block, size_t *have, size_t need, hipStream_t stream) {
+  if (*have < need) {
+    if (*block) {
+      PH_HIP(hipEventSynchronize(s.done));  // the block goes back to the pool: nothing may still use it
+      ph_pool_free(*block);
+      *block = nullptr, *have = 0;
+    }
+    PH_HIP(ph_pool_alloc(block, need));
+    *have = need;
+  } else {
+    PH_HIP(hipStreamWaitEvent(stream, s.done, 0));
+  }
+  return 0;
+}
+
+long long env_ll(const char *name) {
+  const char *e = getenv(name);  // read per call: the tests switch them
+  return e ? atoll(e) : 0;
+}
+
+uint32_t grid1(uint64_t items) { return (uint32_t)std::min<uint64_t>((items + 255u) / 256u, 1u << 16); }
+
+// index, k, handle, store: the checks every search form makes before it looks at another argument, in this order
+int labeled_check(const phnsw_index *ix, const phnsw_labels *lb, uint64_t k, const char *call) {
+  if (!ix || ix->layers.empty()) {
+    ph_set_error("%s: null index or index without layers", call);
+    return PHNSW_E_INVALID;
+  }
+  if (!ph_exact_k_valid(k)) {
+    ph_set_error("%s: k must be 1..1024 (got %llu)", call, (unsigned long long)k);
+    return PHNSW_E_INVALID;
+  }
+  if (!lb) {
+    ph_set_error("%s: null labels", call);
+    return PHNSW_E_INVALID;
+  }
+  if (lb->ix != ix || lb->n != ix->store->n || lb->n_nodes != ix->layers.back().n_nodes) {
+    ph_set_error("%s: the labels are stale: made for %s (%llu vectors, %u bottom-layer nodes then; %llu and %u now); make a "
+                 "new handle", call, lb->ix != ix ? "another index" : "this index before it changed", (unsigned long long)lb->n,
+                 lb->n_nodes, (unsigned long long)ix->store->n, ix->layers.back().n_nodes);
+    return PHNSW_E_INVALID;
+  }
+  if (ph_store_pq_shared(ix->store)) {  // as for the distance batch, whose arithmetic the scan runs
+    ph_set_error("%s: not supported over a shared-codebook PQ store; use its reconstruction store", call);
+    return PHNSW_E_UNSUPPORTED;
+  }
+  return ph_exact_supported(ix, (uint32_t)k);  // the row length, a PQ table beside the scan's LDS
+}
+
+// the orchestration on a set the caller holds; c is checked, 0 < nq <= PH_LABEL_NQ_MAX.  Enqueues and returns.
+int labeled_run(const phnsw_index *ix, const phnsw_labels *lb, const PhLabeledCall &c, PhLabeledSet &set) {
+  const phnsw_store *s = ix->store;
+  const uint64_t nq = c.nq;
+  const PhLabelPre lay = ph_label_pre(nq);
+  if (!set.done) PH_HIP(hipEventCreateWithFlags(&set.done, hipEventDisableTiming));
+  PH_TRY(block_ensure(set, &set.pre, &set.pre_bytes, (size_t)lay.words * 4u, c.stream));
+  uint32_t *const pre = (uint32_t *)set.pre;
+  PhLabeledArgs a = {};
+  a.dist = ph_dist_args(s);
+  a.queries = c.queries, a.ldq = c.ldq, a.qids = c.qids, a.exclude = c.exclude, a.want = c.want;
+  a.nq = (uint32_t)nq, a.n = (uint32_t)s->n, a.k = c.k;
+  a.values = lb->values, a.first = lb->first, a.ids = lb->ids, a.nlabels = (uint32_t)lb->nlabels;
+  a.slot = pre + lay.slot, a.iota = pre + lay.iota, a.sslot = pre + lay.sslot, a.order = pre + lay.order;
+  a.flags = pre + lay.flags, a.tidx = pre + lay.tidx, a.tile_first = pre + lay.tile_first, a.head = pre + lay.head;
+  a.out_ids = c.out_ids, a.out_d = c.out_d, a.out_len = c.out_len, a.status = c.status;
+
+  // T and the kernel: the tile kernel for T > 1 on a row store, else the per-query scan
+  const size_t pq_lds = (ph_pq_lds_bytes(s) + 15u) & ~(size_t)15u;
+  PhLabeledFn fn = labeled_scan_fn(s);
+  size_t lds = pq_lds + (size_t)ph_label_scan_lds(c.k);
+  a.T = 1u, a.pq_lds = (uint32_t)pq_lds;
+  if (PhLabeledFn tile = labeled_tile_fn(s)) {
+    const uint32_t T = ph_label_tile(c.k, s->ld, PH_LABEL_LDS_BYTES, env_ll("PHNSW_LABEL_TILE"));
+    if (T > 1u && ph_label_tile_lds(T, c.k, s->ld) <= PH_LABEL_LDS_BYTES) {
+      fn = tile, a.T = T, lds = (size_t)ph_label_tile_lds(T, c.k, s->ld);
+    }
+  }
+  if (lds > 48 * 1024) PH_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  // resident waves of this kernel at this LDS size: asked of the runtime once per (kernel, LDS) and kept with the handle
+  uint64_t resident = 0;
+  {
+    phnsw_labels *mlb = const_cast<phnsw_labels *>(lb);
+    std::lock_guard<std::mutex> g(mlb->mutex);
+    for (const PhLabelResident &r : mlb->resident)
+      if (r.fn == (const void *)fn && r.lds == lds) resident = r.waves;
+    if (!resident) {
+      int per_cu = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)fn, 64, lds) != hipSuccess || per_cu <= 0) per_cu = 1;
+      if (!mlb->cus) PH_HIP(hipDeviceGetAttribute(&mlb->cus, hipDeviceAttributeMultiprocessorCount, s->device));
+      resident = (uint64_t)per_cu * (uint64_t)std::max(mlb->cus, 1);
+      mlb->resident.push_back(PhLabelResident{(const void *)fn, lds, resident});
+    }
+  }
+  // work items the host can count on: the queries, or at least ceil(nq / T) tiles
+  a.slices = ph_label_slice_count((nq + a.T - 1u) / a.T, resident, lb->longest, env_ll("PHNSW_LABEL_SLICES"));
+
+  if (set.tmp_nq != nq) {  // hipCUB's temporaries depend on the batch size alone
+    size_t sort_bytes = 0, scan_bytes = 0;
+    PH_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, a.slot, pre + lay.sslot, a.iota, pre + lay.order, (int)nq, 0,
+                                              32, c.stream));
+    PH_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, a.flags, pre + lay.tidx, (int)(nq + 1u), c.stream));
+    set.tmp_need = std::max<size_t>(std::max(sort_bytes, scan_bytes), 16), set.tmp_nq = nq;
+  }
+  PH_TRY(block_ensure(set, &set.tmp, &set.tmp_bytes, set.tmp_need, c.stream));
+  if (a.slices > 1u) {
+    uint64_t bytes = 0;
+    if (!ph_label_key_bytes(nq, a.slices, c.k, &bytes)) {
+      ph_set_error("exact labeled search: %llu queries in %u slices at k = %u need more scratch than can be addressed",
+                   (unsigned long long)nq, a.slices, c.k);
+      return PHNSW_E_INVALID;
+    }
+    PH_TRY(block_ensure(set, &set.keys, &set.keys_bytes, (size_t)bytes, c.stream));
+    a.scratch = (uint64_t *)set.keys;
+  }
+
+  hipLaunchKernelGGL(ph_labeled_lookup_kernel, dim3(grid1(nq)), dim3(256), 0, c.stream, a);
+  PH_HIP(hipGetLastError());
+  size_t bytes = set.tmp_bytes;
+  PH_HIP(hipcub::DeviceRadixSort::SortPairs(set.tmp, bytes, a.slot, pre + lay.sslot, a.iota, pre + lay.order, (int)nq, 0, 32,
+                                            c.stream));
+  if (a.T > 1u) {
+    hipLaunchKernelGGL(ph_labeled_tileflag_kernel, dim3(grid1(nq + 1u)), dim3(256), 0, c.stream, a);
+    PH_HIP(hipGetLastError());
+    bytes = set.tmp_bytes;
+    PH_HIP(hipcub::DeviceScan::ExclusiveSum(set.tmp, bytes, a.flags, pre + lay.tidx, (int)(nq + 1u), c.stream));
+    hipLaunchKernelGGL(ph_labeled_tiles_kernel, dim3(grid1(nq + 1u)), dim3(256), 0, c.stream, a);
+    PH_HIP(hipGetLastError());
+  }
+  const uint64_t items = nq * (uint64_t)a.slices;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(items, 1u << 20);  // the kernels stride over what is left
+  hipLaunchKernelGGL(fn, dim3(grid), dim3(64), lds, c.stream, a);
+  PH_HIP(hipGetLastError());
+  if (a.slices > 1u) {
+    hipLaunchKernelGGL(ph_labeled_merge_kernel, dim3((uint32_t)std::min<uint64_t>(nq, 1u << 20)), dim3(64),
+                       (size_t)ph_label_scan_lds(c.k), c.stream, a);
+    PH_HIP(hipGetLastError());
+  }
+  return 0;
+}
+
+// device blocks of one host call: handed back only after the stream they were used on has drained
+struct HostBlocks {
+  hipStream_t stream;
+  std::vector<void *> blocks;
+  template <class T>
+  int alloc(T **p, size_t bytes) {
+    void *v = nullptr;
+    PH_HIP(ph_pool_alloc(&v, std::max<size_t>(bytes, 4)));
+    blocks.push_back(v);
+    *p = (T *)v;
+    return 0;
+  }
+  ~HostBlocks() {
+    hipStreamSynchronize(stream);
+    for (void *b : blocks) ph_pool_free(b);
+  }
+};
+
+void labels_free(phnsw_labels *lb) {
+  for (PhLabeledSet *s : lb->sets) {
+    if (s->done) {
+      hipEventSynchronize(s->done);
+      hipEventDestroy(s->done);
+    }
+    if (s->pre) ph_pool_free(s->pre);
+    if (s->tmp) ph_pool_free(s->tmp);
+    if (s->keys) ph_pool_free(s->keys);
+    if (s->stream) hipStreamDestroy(s->stream);
+    delete s;
+  }
+  if (lb->values) hipFree(lb->values);
+  if (lb->first) hipFree(lb->first);
+  if (lb->ids) hipFree(lb->ids);
+  delete lb;
+}
+
+// the lists of labels_dev [n] on `stream`; synchronises it
+int labels_build(const phnsw_index *ix, const uint32_t *labels_dev, uint64_t n, hipStream_t stream, const char *call,
+                 phnsw_labels **out) {
+  const phnsw_store *s = ix->store;
+  phnsw_labels *lb = new phnsw_labels();
+  lb->ix = ix, lb->n = n, lb->n_nodes = ix->layers.back().n_nodes, lb->device = s->device;
+  struct Drop {
+    phnsw_labels *lb;
+    ~Drop() {
+      if (lb) labels_free(lb);
+    }
+  } drop{lb};
+  if (n == 0) {
+    PH_HIP(hipMalloc(&lb->first, 4));
+    PH_HIP(hipMemsetAsync(lb->first, 0, 4, stream));
+    PH_HIP(hipStreamSynchronize(stream));
+    *out = lb, drop.lb = nullptr;
+    return 0;
+  }
+  uint32_t n_nodes;
+  const uint32_t *nodes, *vec2node;
+  ph_exact_bottom_layer(ix, &n_nodes, &nodes, &vec2node);
+  HostBlocks hb{stream, {}};
+  uint32_t *keys = nullptr, *skeys = nullptr, *iota = nullptr, *flags = nullptr, *slots = nullptr, *head = nullptr;
+  void *tmp = nullptr;
+  PH_TRY(hb.alloc(&keys, (size_t)n * 4u));
+  PH_TRY(hb.alloc(&skeys, (size_t)n * 4u));
+  PH_TRY(hb.alloc(&iota, (size_t)n * 4u));
+  PH_TRY(hb.alloc(&flags, (size_t)(n + 1u) * 4u));
+  PH_TRY(hb.alloc(&slots, (size_t)(n + 1u) * 4u));
+  PH_TRY(hb.alloc(&head, 16));
+  PH_HIP(hipMalloc(&lb->ids, (size_t)n * 4u));
+  size_t sort_bytes = 0, scan_bytes = 0;
+  PH_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, keys, skeys, iota, lb->ids, (int)n, 0, 32, stream));
+  PH_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, flags, slots, (int)(n + 1u), stream));
+  size_t tmp_bytes = std::max<size_t>(std::max(sort_bytes, scan_bytes), 16);
+  PH_TRY(hb.alloc(&tmp, tmp_bytes));
+  hipLaunchKernelGGL(ph_label_key_kernel, dim3(grid1(n)), dim3(256), 0, stream, labels_dev, (uint32_t)n, n_nodes, nodes, vec2node,
+                     keys, iota);
+  PH_HIP(hipGetLastError());
+  size_t bytes = tmp_bytes;
+  PH_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, bytes, keys, skeys, iota, lb->ids, (int)n, 0, 32, stream));
+  hipLaunchKernelGGL(ph_label_flags_kernel, dim3(grid1(n + 1u)), dim3(256), 0, stream, skeys, (uint32_t)n, flags, head);
+  PH_HIP(hipGetLastError());
+  bytes = tmp_bytes;
+  PH_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, bytes, flags, slots, (int)(n + 1u), stream));
+  uint32_t h[2] = {0, 0};
+  PH_HIP(hipMemcpyAsync(&h[0], slots + n, 4, hipMemcpyDeviceToHost, stream));
+  PH_HIP(hipMemcpyAsync(&h[1], head + 1, 4, hipMemcpyDeviceToHost, stream));
+  PH_HIP(hipStreamSynchronize(stream));
+  lb->nlabels = h[0], lb->listed = h[1];
+  if (lb->listed > n || lb->nlabels > lb->listed) {
+    ph_set_error("%s: the labels changed while the lists were made", call);
+    return PHNSW_E_INVALID;
+  }
+  PH_HIP(hipMalloc(&lb->values, std::max<size_t>((size_t)lb->nlabels * 4u, 4)));
+  PH_HIP(hipMalloc(&lb->first, (size_t)(lb->nlabels + 1u) * 4u));
+  hipLaunchKernelGGL(ph_label_heads_kernel, dim3(grid1(n + 1u)), dim3(256), 0, stream, skeys, flags, slots, (uint32_t)n,
+                     (uint32_t)lb->nlabels, (uint32_t)lb->listed, lb->values, lb->first);
+  PH_HIP(hipGetLastError());
+  std::vector<uint32_t> hfirst(lb->nlabels + 1u);
+  PH_HIP(hipMemcpyAsync(hfirst.data(), lb->first, hfirst.size() * 4u, hipMemcpyDeviceToHost, stream));
+  PH_HIP(hipStreamSynchronize(stream));
+  for (uint64_t i = 0; i < lb->nlabels; i++) {
+    if (hfirst[i + 1u] <= hfirst[i] || hfirst[i + 1u] > lb->listed) {
+      ph_set_error("%s: the labels changed while the lists were made", call);
+      return PHNSW_E_INVALID;
+    }
+    lb->longest = std::max<uint64_t>(lb->longest, hfirst[i + 1u] - hfirst[i]);
+  }
+  *out = lb, drop.lb = nullptr;
+  return 0;
+}
+
+int labels_create_check(const phnsw_index *ix, const void *labels, uint64_t n, phnsw_labels **out, const char *call) {
+  if (!ix || ix->layers.empty()) {
+    ph_set_error("%s: null index or index without layers", call);
+    return PHNSW_E_INVALID;
+  }
+  if (!out || (!labels && n)) {
+    ph_set_error("%s: null labels or null output", call);
+    return PHNSW_E_INVALID;
+  }
+  if (n != ix->store->n) {
+    ph_set_error("%s: %llu labels for a store of %llu vectors (one label per vector)", call, (unsigned long long)n,
+                 (unsigned long long)ix->store->n);
+    return PHNSW_E_INVALID;
+  }
+  return 0;
+}
+
+}  // namespace
+
+// ------------------------------------------------------------------ C ABI
+
+extern "C" int phnsw_labels_create_device(const phnsw_index *ix, const uint32_t *labels_dev, uint64_t n, void *stream,
+                                          phnsw_labels **out) try {
+  const char *const call = "phnsw_labels_create_device";
+  PH_TRY(labels_create_check(ix, labels_dev, n, out, call));
+  PH_HIP(hipSetDevice(ix->store->device));
+  return labels_build(ix, labels_dev, n, (hipStream_t)stream, call, out);
+} catch (...) { return ph_caught(); }
+
+extern "C" int phnsw_labels_create(const phnsw_index *ix, const uint32_t *labels, uint64_t n, phnsw_labels **out) try {
+  const char *const call = "phnsw_labels_create";
+  PH_TRY(labels_create_check(ix, labels, n, out, call));
+  PH_HIP(hipSetDevice(ix->store->device));
+  HostBlocks hb{nullptr, {}};
+  uint32_t *dev = nullptr;
+  PH_TRY(hb.alloc(&dev, (size_t)n * 4u));
+  if (n) PH_HIP(hipMemcpy(dev, labels, (size_t)n * 4u, hipMemcpyHostToDevice));
+  return labels_build(ix, dev, n, nullptr, call, out);
+} catch (...) { return ph_caught(); }
+
+extern "C" int phnsw_labels_info(const phnsw_labels *lb, uint64_t *n, uint64_t *nlabels, uint64_t *listed, uint64_t *longest) try {
+  if (!lb) {
+    ph_set_error("phnsw_labels_info: null labels");
+    return PHNSW_E_INVALID;
+  }
+  if (n) *n = lb->n;
+  if (nlabels) *nlabels = lb->nlabels;
+  if (listed) *listed = lb->listed;
+  if (longest) *longest = lb->longest;
+  return 0;
+} catch (...) { return ph_caught(); }
+
+extern "C" int phnsw_labels_count_device(const phnsw_labels *lb, const uint32_t *want_dev, uint64_t nq, uint32_t *out_count_dev,
+                                         void *stream) try {
+  const char *const call = "phnsw_labels_count_device";
+  if (!lb) {
+    ph_set_error("%s: null labels", call);
+    return PHNSW_E_INVALID;
+  }
+  if (nq == 0) return 0;
+  if (!want_dev || !out_count_dev) {
+    ph_set_error("%s: null want or null output", call);
+    return PHNSW_E_INVALID;
+  }
+  PH_HIP(hipSetDevice(lb->device));
+  hipLaunchKernelGGL(ph_labeled_count_kernel, dim3(grid1(nq)), dim3(256), 0, (hipStream_t)stream, lb->values, lb->first,
+                     (uint32_t)lb->nlabels, want_dev, nq, out_count_dev);
+  PH_HIP(hipGetLastError());
+  return 0;
+} catch (...) { return ph_caught(); }
+
+extern "C" void phnsw_labels_destroy(phnsw_labels *lb) {
+  if (!lb) return;
+  try {
+    hipSetDevice(lb->device);
+    labels_free(lb);  // waits for the events that close the calls in flight
+  } catch (...) {
+  }
+}
+
+extern "C" int phnsw_search_exact_labeled_device(const phnsw_index *ix, const phnsw_labels *lb, const float *queries_dev,
+                                                 uint32_t ldq, const uint32_t *qids_dev, uint64_t nq, const uint32_t *exclude_dev,
+                                                 const uint32_t *want_dev, uint64_t k, uint32_t *out_ids_dev, float *out_d_dev,
+                                                 uint32_t *out_len_dev, uint32_t *status_dev, void *stream) try {
+  const char *const call = "phnsw_search_exact_labeled_device";
+  PH_TRY(labeled_check(ix, lb, k, call));
+  if (nq == 0) return 0;
+  if (((!queries_dev) == (!qids_dev)) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev || !want_dev ||
+      nq > PH_LABEL_NQ_MAX || (queries_dev && (ldq < ix->store->ld || (ldq % 4) || ((uintptr_t)queries_dev % 16)))) {
+    ph_set_error("%s: invalid argument (queries or qids, exactly one; outputs; want; nq < 2^31 - 1; queries need ldq >= store "
+                 "ld, multiple of 4, 16-byte base)", call);
+    return PHNSW_E_INVALID;
+  }
+  PhLabeledCall c = {};
+  c.queries = queries_dev, c.ldq = ldq, c.qids = qids_dev, c.exclude = exclude_dev, c.want = want_dev, c.nq = nq;
+  c.k = (uint32_t)k;
+  c.out_ids = out_ids_dev, c.out_d = out_d_dev, c.out_len = out_len_dev, c.status = status_dev;
+  c.stream = (hipStream_t)stream;
+  PH_HIP(hipSetDevice(ix->store->device));
+  phnsw_labels *mlb = const_cast<phnsw_labels *>(lb);
+  PhLabeledSet *set = set_acquire(mlb, c.stream, false);
+  SetGuard guard{mlb, set, c.stream};
+  return labeled_run(ix, lb, c, *set);
+} catch (...) { return ph_caught(); }
+
+extern "C" int phnsw_search_exact_labeled(const phnsw_index *ix, const phnsw_labels *lb, const float *queries, const uint64_t *qids,
+                                          uint64_t nq, const uint64_t *exclude, const uint32_t *want, uint64_t k,
+                                          uint64_t *out_ids, float *out_d, uint64_t *out_len) try {
+  const char *const call = "phnsw_search_exact_labeled";
+  PH_TRY(labeled_check(ix, lb, k, call));
+  if (nq == 0) return 0;
+  if ((!queries) == (!qids)) {
+    ph_set_error("%s: pass queries or qids (exactly one)", call);
+    return PHNSW_E_INVALID;
+  }
+  if (!out_ids || !out_d || !out_len || !want || nq > PH_LABEL_NQ_MAX) {
+    ph_set_error("%s: invalid argument (outputs; want; nq < 2^31 - 1)", call);
+    return PHNSW_E_INVALID;
+  }
+  const phnsw_store *s = ix->store;
+  PH_HIP(hipSetDevice(s->device));
+  if (qids)
+    for (uint64_t i = 0; i < nq; i++)
+      if (qids[i] >= s->n) {
+        ph_set_error("%s: stored query id %llu out of range", call, (unsigned long long)qids[i]);
+        return PHNSW_E_INVALID;
+      }
+  // host words of the per-query ids, alive until the stream has drained (HostBlocks is declared after them)
+  std::vector<uint32_t> h_in, h_len(nq);
+  phnsw_labels *mlb = const_cast<phnsw_labels *>(lb);
+  PhLabeledSet *set = set_acquire(mlb, nullptr, true);
+  if (!set->stream) {
+    hipError_t e = hipStreamCreateWithFlags(&set->stream, hipStreamNonBlocking);
+    if (e != hipSuccess) {
+      SetGuard g{mlb, set, nullptr};
+      return ph_hip_fail(e, "host path: stream", __FILE__, __LINE__);
+    }
+  }
+  const hipStream_t st = set->stream;
+  SetGuard guard{mlb, set, st};
+  HostBlocks hb{st, {}};
+
+  PhLabeledCall c = {};
+  const uint32_t ld = s->ld, kk = (uint32_t)k;
+  if (queries) {  // rows padded to the store's row length
+    float *q = nullptr;
+    PH_TRY(hb.alloc(&q, (size_t)nq * ld * 4u));
+    if (ld != s->dim) {
+      PH_HIP(hipMemsetAsync(q, 0, (size_t)nq * ld * 4u, st));
+      PH_HIP(hipMemcpy2DAsync(q, (size_t)ld * 4u, queries, (size_t)s->dim * 4u, (size_t)s->dim * 4u, nq, hipMemcpyHostToDevice, st));
+    } else {
+      PH_HIP(hipMemcpyAsync(q, queries, (size_t)nq * ld * 4u, hipMemcpyHostToDevice, st));
+    }
+    c.queries = q, c.ldq = ld;
+  }
+  uint32_t *small = nullptr;  // qid | exclude | len | status | want   [5][nq]
+  PH_TRY(hb.alloc(&small, (size_t)nq * 5u * 4u));
+  if (qids || exclude) {
+    h_in.resize(2u * nq);
+    if (qids)
+      for (uint64_t i = 0; i < nq; i++) h_in[i] = (uint32_t)qids[i];
+    if (exclude)
+      for (uint64_t i = 0; i < nq; i++) h_in[nq + i] = exclude[i] >= s->n ? PH_EMPTY32 : (uint32_t)exclude[i];
+    PH_HIP(hipMemcpyAsync(small, h_in.data(), (size_t)nq * 2u * 4u, hipMemcpyHostToDevice, st));
+    if (qids) c.qids = small;
+    if (exclude) c.exclude = small + nq;
+  }
+  PH_HIP(hipMemcpyAsync(small + 4u * nq, want, (size_t)nq * 4u, hipMemcpyHostToDevice, st));
+  c.want = small + 4u * nq;
+  uint32_t *ids = nullptr;
+  float *d = nullptr, *dk = nullptr;
+  uint64_t *ids64 = nullptr;
+  PH_TRY(hb.alloc(&ids, (size_t)nq * kk * 4u));
+  PH_TRY(hb.alloc(&d, (size_t)nq * kk * 4u));
+  PH_TRY(hb.alloc(&ids64, (size_t)nq * kk * 8u));
+  PH_TRY(hb.alloc(&dk, (size_t)nq * kk * 4u));
+  c.nq = nq, c.k = kk;
+  c.out_ids = ids, c.out_d = d, c.out_len = small + 2u * nq, c.status = small + 3u * nq;
+  c.stream = st;
+  PH_TRY(labeled_run(ix, lb, c, *set));
+  PH_TRY(ph_take_launch(ids, d, kk, kk, nq, ids64, dk, st));  // u32 -> u64 ids, 0xFFFFFFFF -> PHNSW_EMPTY
+  PH_HIP(hipMemcpyAsync(h_len.data(), small + 2u * nq, (size_t)nq * 4u, hipMemcpyDeviceToHost, st));
+  PH_HIP(hipMemcpyAsync(out_ids, ids64, (size_t)nq * kk * 8u, hipMemcpyDeviceToHost, st));
+  PH_HIP(hipMemcpyAsync(out_d, dk, (size_t)nq * kk * 4u, hipMemcpyDeviceToHost, st));
+  PH_HIP(hipStreamSynchronize(st));
+  for (uint64_t i = 0; i < nq; i++) out_len[i] = h_len[i];
+  return 0;
+} catch (...) { return ph_caught(); }

@@ -40,6 +40,7 @@ def _p(a):
 FILTER_STRICT = 1  # PHNSW_FILTER_STRICT
 FILTER_ALL = 0xFFFFFFFF  # PHNSW_FILTER_ALL: a selector of search_exact_grouped that names no bitmap
 ROUTE_GRAPH, ROUTE_SCAN, ROUTE_GRAPH_THEN_SCAN = 0, 1, 2  # PHNSW_ROUTE_*
+LABEL_NONE = 0xFFFFFFFF  # PHNSW_LABEL_NONE: a vector that is not listed; a wanted label with an empty row
 
 
 def pack_allow(allow, n, nq):
@@ -101,6 +102,98 @@ def pack_allow_of(allow_of, nq):
         raise ValueError("allow_of: selectors are bitmap numbers, -1 or FILTER_ALL")
     a[a == -1] = FILTER_ALL
     return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def pack_labels(values, count, what):
+    """labels of Labels / wanted labels of search_exact_labeled -> u32 [count]: integers within u32, -1 or LABEL_NONE =
+    none"""
+    if values is None:
+        raise ValueError("%s: an integer array of shape [%d] is required" % (what, count))
+    a = np.asarray(values)
+    if a.dtype.kind not in "iu":
+        raise TypeError("%s: an integer array, got %s" % (what, a.dtype))
+    if a.ndim != 1 or a.shape[0] != count:
+        raise ValueError("%s: an integer array of shape [%d], got %r" % (what, count, a.shape))
+    if a.dtype != np.uint32:
+        if a.dtype == np.uint64:
+            if (a > LABEL_NONE).any():
+                raise ValueError("%s: labels are 32-bit values, -1 or LABEL_NONE" % what)
+        else:
+            a = a.astype(np.int64)
+            if ((a < -1) | (a > LABEL_NONE)).any():
+                raise ValueError("%s: labels are 32-bit values, -1 or LABEL_NONE" % what)
+            a[a == -1] = LABEL_NONE
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+class Labels:
+    """phnsw_labels: one label per vector of `hnsw`'s store, turned once into posting lists on the device (the ascending
+    VectorIds of every label).  labels: an integer array [n] within u32; -1 or LABEL_NONE = the vector is not listed.  A
+    vector is listed iff the index's bottom layer holds it.  The handle is a snapshot: after store.append, or with
+    another index, search_exact_labeled refuses it as stale -- make a new one.  Keep `hnsw` alive while it is used."""
+
+    def __init__(self, hnsw, labels):
+        self._h = None
+        if not isinstance(hnsw, Hnsw):
+            raise TypeError("Labels: hnsw must be an Hnsw")
+        lab = pack_labels(labels, int(hnsw.store.n), "labels")
+        h = C.c_void_p()
+        check(lib().phnsw_labels_create(hnsw._h, _p(lab), len(lab), C.byref(h)))
+        self._h, self.hnsw = h, hnsw
+
+    @classmethod
+    def from_device(cls, hnsw, ptr, stream=0):
+        """phnsw_labels_create_device: ptr = u32 labels [store n] in device memory (an integer), read on `stream`, which
+        is synchronised"""
+        if not isinstance(hnsw, Hnsw):
+            raise TypeError("Labels.from_device: hnsw must be an Hnsw")
+        self = cls.__new__(cls)
+        self._h = None
+        h = C.c_void_p()
+        check(lib().phnsw_labels_create_device(hnsw._h, C.c_void_p(ptr or None), int(hnsw.store.n), C.c_void_p(stream or None),
+                                               C.byref(h)))
+        self._h, self.hnsw = h, hnsw
+        return self
+
+    def info(self):
+        """(n, nlabels, listed, longest): the vector count the handle was made for, the distinct labels that list a
+        vector, the listed vectors, the longest list"""
+        v = [C.c_uint64() for _ in range(4)]
+        check(lib().phnsw_labels_info(self._h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+    nlabels = property(lambda self: self.info()[1])
+    listed = property(lambda self: self.info()[2])
+    longest = property(lambda self: self.info()[3])
+
+    def count_device(self, nq, want, out_count, stream=0):
+        """phnsw_labels_count_device: device pointers as integers, u32 [nq] each"""
+        check(lib().phnsw_labels_count_device(self._h, C.c_void_p(want or None), int(nq), C.c_void_p(out_count or None),
+                                              C.c_void_p(stream or None)))
+
+    def count(self, want):
+        """the length of the list of every wanted label, u32 [nq] (0 for a label nobody carries and for LABEL_NONE):
+        filter_count's figure for the equivalent bitmaps.  Host convenience over count_device (needs torch)"""
+        import torch
+        w = pack_labels(np.atleast_1d(want), len(np.atleast_1d(want)), "want")
+        dev = torch.device("cuda", getattr(self.hnsw.store, "device", 0))
+        wd = torch.from_numpy(w.view(np.int32)).to(dev)
+        out = torch.zeros(max(len(w), 1), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.count_device(len(w), wd.data_ptr(), out.data_ptr())
+        torch.cuda.synchronize(dev)
+        return out.cpu().numpy().view(np.uint32)[:len(w)]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().phnsw_labels_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def SearchParameters(number_of_candidates=300, upper_layer_candidate_count=300, probe_depth=2):
@@ -849,6 +942,49 @@ class Hnsw:
             self._h, C.c_void_p(queries or None), ldq, C.c_void_p(qids or None), nq, C.c_void_p(exclude or None),
             C.c_void_p(allows or None), int(allow_stride), int(nallows), C.c_void_p(allow_of or None), int(k),
             C.c_void_p(out_ids), C.c_void_p(out_d), C.c_void_p(out_len), C.c_void_p(status), C.c_void_p(stream or None)))
+
+    def search_exact_labeled(self, queries=None, qids=None, labels=None, want=None, exclude=None, k=10):
+        """search_exact_filtered by row label (phnsw_search_exact_labeled): query i may return the vectors `labels` lists
+        under want[i] -- the same rows as search_exact_filtered(allow=(label column == want[i])), bit for bit, from
+        posting lists instead of bitmaps.  labels: a Labels made for this index; want: integers [nq] within u32, -1 or
+        LABEL_NONE (or a label nobody carries) = an empty row.  Exactly one of queries / qids.  Every store kind the
+        scan takes.  Measured on 1M x 768 f32 rows, 10 000 queries, k = 10: 1.4 to 3.8 times faster than the scan with
+        per-query bitmaps; 0.26 to 0.69 times as fast as search_exact_grouped at 1 and 8 labels (it LOSES there), 1.5 and 35
+        times faster at 64 and 1000 labels (profiles/filter_labeled/README.md).
+        Returns (ids[nq, k] u64, d[nq, k] f32, len[nq])"""
+        if (queries is None) == (qids is None):
+            raise ValueError("search_exact_labeled: pass queries or qids (exactly one)")
+        if not isinstance(labels, Labels):
+            raise TypeError("search_exact_labeled: labels must be a Labels made for this index")
+        q = qi = None
+        if queries is not None:
+            q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+            assert q.shape[1] == self.store.dim
+            nq = q.shape[0]
+        else:
+            qi = np.ascontiguousarray(qids, dtype=np.uint64)
+            nq = len(qi)
+        w32 = pack_labels(want, nq, "want")
+        w = max(int(k), 0)
+        ids = np.empty((nq, w), dtype=np.uint64)
+        d = np.empty((nq, w), dtype=np.float32)
+        ln = np.zeros(nq, dtype=np.uint64)
+        ex = None if exclude is None else np.ascontiguousarray(exclude, dtype=np.uint64)
+        check(lib().phnsw_search_exact_labeled(self._h, labels._h, _p(q), _p(qi), nq, _p(ex), _p(w32), int(k), _p(ids), _p(d),
+                                               _p(ln)))
+        return ids, d, ln
+
+    def search_exact_labeled_device(self, labels, nq, k, out_ids, out_d, out_len, status, queries=0, ldq=0, qids=0, exclude=0,
+                                    want=0, stream=0):
+        """zero-copy form (phnsw_search_exact_labeled_device): device pointers as integers, u32 ids [nq, k] padded with
+        0xFFFFFFFF; want = u32 labels [nq].  status 4 = a stored query id at or past n (an empty row).  Enqueued on
+        `stream`; never synchronises it"""
+        if not isinstance(labels, Labels):
+            raise TypeError("search_exact_labeled_device: labels must be a Labels made for this index")
+        check(lib().phnsw_search_exact_labeled_device(
+            self._h, labels._h, C.c_void_p(queries or None), ldq, C.c_void_p(qids or None), nq, C.c_void_p(exclude or None),
+            C.c_void_p(want or None), int(k), C.c_void_p(out_ids), C.c_void_p(out_d), C.c_void_p(out_len), C.c_void_p(status),
+            C.c_void_p(stream or None)))
 
     def filter_count_device(self, nbitmaps, out_count, allow=0, allow_stride=0, stream=0):
         """phnsw_filter_count_device: the number of candidates of each of nbitmaps device bitmaps into out_count (u32

@@ -223,6 +223,36 @@ impl Drop for GpuHnsw {
     }
 }
 
+/// `phnsw_labels`: the posting lists of a label column (`GpuHnsw::labels`).  Must not be used after its index is dropped
+pub struct GpuLabels {
+    lb: *mut sys::phnsw_labels,
+}
+unsafe impl Send for GpuLabels {}
+unsafe impl Sync for GpuLabels {} // the search calls keep a scratch set per call in flight with the handle (phnsw.h)
+
+impl Drop for GpuLabels {
+    fn drop(&mut self) {
+        unsafe { sys::phnsw_labels_destroy(self.lb) } // waits for the calls in flight that use it
+    }
+}
+
+impl GpuLabels {
+    /// (distinct labels that list a vector, listed vectors, the longest list)
+    pub fn info(&self) -> (u64, u64, u64) {
+        let (mut n, mut nlabels, mut listed, mut longest) = (0u64, 0u64, 0u64, 0u64);
+        check(unsafe { sys::phnsw_labels_info(self.lb, &mut n, &mut nlabels, &mut listed, &mut longest) });
+        (nlabels, listed, longest)
+    }
+
+    /// per query the length of the list of `want_dev[q]` (`phnsw_labels_count_device`)
+    ///
+    /// # Safety
+    /// `want_dev` and `out_count_dev` (`nq` u32 each) must be valid device allocations
+    pub unsafe fn count_device(&self, want_dev: *const u32, nq: u64, out_count_dev: *mut u32, stream: *mut c_void) {
+        check(sys::phnsw_labels_count_device(self.lb, want_dev, nq, out_count_dev, stream));
+    }
+}
+
 impl GpuHnsw {
     /// `Hnsw::generate(c, vs, bp, progress)`  lib.rs:825-830
     pub fn generate(c: GpuComparator, vs: Vec<VectorId>, bp: BuildParameters, progress: &mut dyn ProgressMonitor) -> Self {
@@ -572,6 +602,51 @@ impl GpuHnsw {
         check(sys::phnsw_search_exact_grouped_device(self.ix, queries_dev, ldq, qids_dev, nq, exclude_dev, filters_dev,
                                                      filter_stride_words, nfilters, filter_of_dev, k, out_ids_dev, out_d_dev,
                                                      out_len_dev, status_dev, stream));
+    }
+
+    /// one label per vector of the store, turned once into posting lists on the device (`phnsw_labels_create`):
+    /// `labels[v]` is the label of vector v, `None` = not listed.  A snapshot: after the store or the index has changed
+    /// `search_many_exact_labeled` refuses it as stale.  Panics unless `labels` has one entry per vector
+    pub fn labels(&self, labels: &[Option<u32>]) -> GpuLabels {
+        let col: Vec<u32> = labels.iter().map(|l| l.unwrap_or(sys::PHNSW_LABEL_NONE)).collect();
+        let mut lb: *mut sys::phnsw_labels = std::ptr::null_mut();
+        check(unsafe { sys::phnsw_labels_create(self.ix, col.as_ptr(), col.len() as u64, &mut lb) });
+        GpuLabels { lb }
+    }
+
+    /// `search_many_exact_filtered` by row label (`phnsw_search_exact_labeled`): query i may return the vectors `labels`
+    /// lists under `want[i]`; `None`, or a label nobody carries, gives an empty result.  The same results, bit for bit,
+    /// as the predicates `label of v == want[i]` give, from posting lists instead of bitmaps.  Panics unless
+    /// 1 <= k <= 1024 and `want` has one entry per query
+    pub fn search_many_exact_labeled(&self, queries: &[Vec<f32>], k: usize, labels: &GpuLabels, want: &[Option<u32>])
+                                     -> Vec<Vec<(VectorId, f32)>> {
+        assert!((1..=1024).contains(&k), "search_many_exact_labeled: k must be 1..1024");
+        let nq = queries.len();
+        assert!(want.len() == nq, "search_many_exact_labeled: one wanted label per query");
+        let w: Vec<u32> = want.iter().map(|l| l.unwrap_or(sys::PHNSW_LABEL_NONE)).collect();
+        let mut q: Vec<f32> = Vec::with_capacity(nq * queries.first().map_or(0, |x| x.len()));
+        for x in queries {
+            q.extend_from_slice(x);
+        }
+        let (mut ids, mut d, mut len) = (vec![0u64; nq * k], vec![0f32; nq * k], vec![0u64; nq]);
+        check(unsafe {
+            sys::phnsw_search_exact_labeled(self.ix, labels.lb, q.as_ptr(), std::ptr::null(), nq as u64, std::ptr::null(),
+                                            w.as_ptr(), k as u64, ids.as_mut_ptr(), d.as_mut_ptr(), len.as_mut_ptr())
+        });
+        (0..nq).map(|i| (0..len[i] as usize).map(|j| (VectorId(ids[i * k + j] as usize), d[i * k + j])).collect()).collect()
+    }
+
+    /// zero-copy form (`phnsw_search_exact_labeled_device`): u32 ids `[nq][k]`; enqueued on `stream`, never synchronises it
+    ///
+    /// # Safety
+    /// the pointers must be valid device allocations of the sizes `phnsw.h` documents for the call
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn search_exact_labeled_device(&self, labels: &GpuLabels, queries_dev: *const f32, ldq: u32,
+                                              qids_dev: *const u32, nq: u64, exclude_dev: *const u32, want_dev: *const u32,
+                                              k: u64, out_ids_dev: *mut u32, out_d_dev: *mut f32, out_len_dev: *mut u32,
+                                              status_dev: *mut u32, stream: *mut c_void) {
+        check(sys::phnsw_search_exact_labeled_device(self.ix, labels.lb, queries_dev, ldq, qids_dev, nq, exclude_dev, want_dev, k,
+                                                     out_ids_dev, out_d_dev, out_len_dev, status_dev, stream));
     }
 
     /// 0, or the code `search_many_exact_shared` would be refused with (`phnsw_exact_shared_supported`)

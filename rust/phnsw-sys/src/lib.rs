@@ -24,6 +24,7 @@ pub const PHNSW_E_NOMEM: c_int = -8;
 
 pub const PHNSW_FILTER_STRICT: u32 = 1; // also drop disallowed ids (the entry vector) from the final rows
 pub const PHNSW_FILTER_ALL: u32 = 0xFFFF_FFFF; // filter_of[q] of phnsw_search_exact_grouped: no bitmap, every vector of the index
+pub const PHNSW_LABEL_NONE: u32 = 0xFFFF_FFFF; // labels[v]: v is not listed; want[q]: an empty row
 
 pub const PHNSW_METRIC_COSINE_HALF: c_int = 0; // (1 - dot)/2   bigvec.rs:47-53
 pub const PHNSW_METRIC_ONE_MINUS_DOT: c_int = 1; // 1 - dot       lib.rs:1985-1991
@@ -69,6 +70,10 @@ pub struct phnsw_store {
 }
 #[repr(C)]
 pub struct phnsw_index {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct phnsw_labels {
     _private: [u8; 0],
 }
 
@@ -269,6 +274,22 @@ extern "C" {
                                              filter_of_dev: *const u32, k: u64, out_ids_dev: *mut u32,
                                              out_d_dev: *mut c_float, out_len_dev: *mut u32, status_dev: *mut u32,
                                              stream: *mut c_void) -> c_int;
+    // the same exact top-k by row label: posting lists made once per handle, no bitmap, nothing read back
+    pub fn phnsw_labels_create(ix: *const phnsw_index, labels: *const u32, n: u64, out: *mut *mut phnsw_labels) -> c_int;
+    pub fn phnsw_labels_create_device(ix: *const phnsw_index, labels_dev: *const u32, n: u64, stream: *mut c_void,
+                                      out: *mut *mut phnsw_labels) -> c_int;
+    pub fn phnsw_labels_info(lb: *const phnsw_labels, n: *mut u64, nlabels: *mut u64, listed: *mut u64,
+                             longest: *mut u64) -> c_int;
+    pub fn phnsw_labels_count_device(lb: *const phnsw_labels, want_dev: *const u32, nq: u64, out_count_dev: *mut u32,
+                                     stream: *mut c_void) -> c_int;
+    pub fn phnsw_labels_destroy(lb: *mut phnsw_labels);
+    pub fn phnsw_search_exact_labeled(ix: *const phnsw_index, lb: *const phnsw_labels, queries: *const c_float,
+                                      qids: *const u64, nq: u64, exclude: *const u64, want: *const u32, k: u64,
+                                      out_ids: *mut u64, out_d: *mut c_float, out_len: *mut u64) -> c_int;
+    pub fn phnsw_search_exact_labeled_device(ix: *const phnsw_index, lb: *const phnsw_labels, queries_dev: *const c_float,
+                                             ldq: u32, qids_dev: *const u32, nq: u64, exclude_dev: *const u32,
+                                             want_dev: *const u32, k: u64, out_ids_dev: *mut u32, out_d_dev: *mut c_float,
+                                             out_len_dev: *mut u32, status_dev: *mut u32, stream: *mut c_void) -> c_int;
     pub fn phnsw_filter_count_device(ix: *const phnsw_index, filter_dev: *const u32, filter_stride_words: u32,
                                      nbitmaps: u64, out_count_dev: *mut u32, stream: *mut c_void) -> c_int;
     // per query the scan or the graph walk, the scan again for short rows: min(k, candidates) entries, candidates only
