@@ -386,6 +386,9 @@ int phnsw_search_exact_grouped_device(const phnsw_index *ix, const float *querie
  * turns the label column once into posting lists -- the ascending VectorIds of every label, CSR -- on the device; a
  * search derives nothing from a bitmap and reads nothing back.  A label column is 4 bytes per vector whatever the
  * number of labels (1000 bitmaps over 1M rows are 125 MB, 100 000 are 12.5 GB).
+ * The handle also keeps the column itself on the device, label_of[n] -- the label of every listed vector, PHNSW_LABEL_NONE
+ * for one that is not listed --, for the graph walk by label (phnsw_search_batch_labeled, below): 4 * n bytes more than the
+ * posting lists.
  * Listed: vector v is listed under labels[v] iff v < n, labels[v] != PHNSW_LABEL_NONE and v is a vector of the index's
  * bottom layer (the candidate test of the other exact calls, without a bitmap).  Labels are arbitrary 32-bit values,
  * neither dense nor small.  n must equal the store's vector count, else PHNSW_E_INVALID.
@@ -504,6 +507,62 @@ int phnsw_search_filtered_auto_device(const phnsw_index *ix, const float *querie
                                       uint32_t filter_stride_words, uint64_t k, uint64_t scan_below,
                                       uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
                                       uint32_t *out_route_dev, uint32_t *status_dev, void *stream);
+/* ---- the graph walk restricted by ROW LABEL: phnsw_search_batch_filtered without a bitmap per query.  The handle keeps
+ * the label column it was made from on the device, label_of[n] -- the label of every listed vector, PHNSW_LABEL_NONE for
+ * one that is not listed; this costs a handle 4 * n more bytes than its posting lists -- and the search kernels test
+ * label_of[v] == want[q] where the bitmap form tests bit v: one 4-byte load per kept queue entry instead of one word.
+ * A batch of nq queries sends nq labels, not nq bitmaps of ceil(n / 32) words.
+ * Arguments as phnsw_search_batch_filtered[_device] with (lb, want) in place of (filter, filter_stride_words): sp,
+ * upto_layers, exclude, flags (PHNSW_FILTER_STRICT or 0), k (host form; 0 = the whole queue), out_stats.
+ * ROW EQUALITY: the rows, lengths, stats and statuses are those of phnsw_search_batch_filtered[_device] called with the
+ * per-query bitmaps {v : v listed under want[q]}, bit for bit.  It is the same post-filter: a query gets about
+ * number_of_candidates * (list length) / N results, not k of them -- phnsw_search_labeled_auto (below) completes rows.
+ * The entry vector may appear although its label differs (and although it is not listed), unless flags has
+ * PHNSW_FILTER_STRICT.  want[q] == PHNSW_LABEL_NONE, or a label nobody carries, gives the row an all-zero bitmap gives.
+ * The default filter of phnsw_index_set_filter_device is NOT consulted, as in phnsw_search_exact_labeled.
+ * Checks: index and sp as phnsw_search_batch; then a null or stale `lb`, refused exactly as phnsw_search_exact_labeled
+ * refuses it (PHNSW_E_INVALID, "the labels are stale"); unknown flag bits; exactly one of queries / qids, the outputs and
+ * `want` (PHNSW_E_INVALID); nq == 0 is a no-op.  Every store kind phnsw_search_batch_filtered walks.
+ * The host form stages its arrays once per call (queries, ids, want: 4 bytes per query where the bitmap form uploads
+ * ceil(n / 32) words per query) and runs on a stream of its own; a query whose frontier spill overflowed is re-run
+ * with more room, as in phnsw_search_batch.  Timing against the bitmap call: profiles/labeled_walk/README.md. */
+int phnsw_search_batch_labeled(const phnsw_index *ix, const phnsw_labels *lb, const float *queries, const uint64_t *qids,
+                               uint64_t nq, const phnsw_search_params *sp, uint32_t upto_layers, const uint64_t *exclude,
+                               const uint32_t *want, uint32_t flags, uint64_t k, uint64_t *out_ids, float *out_d,
+                               uint64_t *out_len, uint64_t *out_stats);
+/* device form: device pointers, rows of number_of_candidates entries as phnsw_search_batch_filtered_device writes them,
+ * status_dev as there.  ENQUEUED on `stream`; never synchronises.  want_dev [nq] is read by the kernels: keep it alive
+ * and unchanged until the work on `stream` is done. */
+int phnsw_search_batch_labeled_device(const phnsw_index *ix, const phnsw_labels *lb, const float *queries_dev, uint32_t ldq,
+                                      const uint32_t *qids_dev, uint64_t nq, const phnsw_search_params *sp,
+                                      uint32_t upto_layers, const uint32_t *exclude_dev, const uint32_t *want_dev,
+                                      uint32_t flags, uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                      uint32_t *out_stats_dev, uint32_t *status_dev, void *stream);
+/* ---- one call by label that routes: phnsw_search_filtered_auto with (lb, want) for the bitmaps.  Same arguments
+ * otherwise, same three routes, same promise: every row holds exactly min(k, c_q - e_q) entries and only candidates,
+ * where c_q is the length of the list of want[q] (what phnsw_labels_count_device writes) and e_q is 1 iff exclude[q] is
+ * listed under want[q].  The counts come from the posting lists -- no bitmap is made or counted --, the rule is the
+ * one above (filter_route.h), the walk is the PHNSW_FILTER_STRICT walk of phnsw_search_batch_labeled, and a scanned
+ * row is phnsw_search_exact_labeled's row bit for bit, routed and short queries in ONE scan launch.  Hence every row
+ * equals the row of phnsw_search_filtered_auto with the per-query bitmaps {v : v listed under want[q]} and the same
+ * scan_below.
+ * scan_below 0 = the library default for labels (filter_route.h, PH_AUTO_SCAN_BELOW_LABELED): 20 000, the measured
+ * crossover of phnsw_search_exact_labeled and the label walk (profiles/labeled_walk/README.md: at 20 000 rows per label the
+ * scan took 17.8 ms against the walk's 22.0, at 25 000 rows 22.0 against 21.5) -- measured on 1M x 768 f32 rows, ef 256 /
+ * probe_depth 8, k = 10, batches of 10 000 queries; other store kinds, dimensions, parameters and batch sizes are
+ * unmeasured, pass your own.  UINT64_MAX = always scan.
+ * Checks: those of phnsw_search_filtered_auto (sp, then 1 <= k <= number_of_candidates, then the store), then the handle
+ * as phnsw_search_exact_labeled checks it, then the pointers.  The default filter is not consulted.  The device form
+ * synchronises `stream` at most twice, like phnsw_search_filtered_auto_device. */
+int phnsw_search_labeled_auto(const phnsw_index *ix, const phnsw_labels *lb, const float *queries, const uint64_t *qids,
+                              uint64_t nq, const phnsw_search_params *sp, const uint64_t *exclude, const uint32_t *want,
+                              uint64_t k, uint64_t scan_below, uint64_t *out_ids, float *out_d, uint64_t *out_len,
+                              uint32_t *out_route);
+int phnsw_search_labeled_auto_device(const phnsw_index *ix, const phnsw_labels *lb, const float *queries_dev, uint32_t ldq,
+                                     const uint32_t *qids_dev, uint64_t nq, const phnsw_search_params *sp,
+                                     const uint32_t *exclude_dev, const uint32_t *want_dev, uint64_t k, uint64_t scan_below,
+                                     uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                     uint32_t *out_route_dev, uint32_t *status_dev, void *stream);
 /* Throughput callers keep TWO batches in flight: phnsw_search_batch_device calls issued alternately on two streams
  * overlap (an index holds two search workspaces) -- if the two streams sit on different hardware queues.  HIP maps a
  * process's streams onto a few of them (GPU_MAX_HW_QUEUES, 4 by default) and two streams that share one run in issue

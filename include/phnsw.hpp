@@ -441,6 +441,34 @@ class Hnsw {
                                           uint64_t nq, const uint32_t *exclude_dev, const uint32_t *want_dev, uint64_t k,
                                           uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev, uint32_t *status_dev,
                                           void *stream) const;
+  // search_many_filtered by row label (phnsw_search_batch_labeled): the graph walk of query i restricted to the vectors
+  // `labels` lists under want[i], read from the handle's label column instead of a bitmap per query -- the results
+  // search_many_filtered gives with the equivalent bitmaps, bit for bit.  A post-filter: about number_of_candidates *
+  // list length / N results; strict also removes an entry vector whose label differs.  k = 0: the whole queue.  Throws on
+  // want.size() != queries and k > number_of_candidates before the library is called (defined below, after Labels)
+  inline std::vector<SearchResult> search_many_labeled(const std::vector<const float *> &queries, const SearchParameters &sp,
+                                                       const Labels &labels, const std::vector<uint32_t> &want,
+                                                       bool strict = false, uint64_t k = 0) const;
+  // zero-copy form (phnsw_search_batch_labeled_device): rows of number_of_candidates u32 ids; enqueued on `stream`,
+  // never synchronises it
+  inline void search_batch_labeled_device(const Labels &labels, const float *queries_dev, uint32_t ldq, const uint32_t *qids_dev,
+                                          uint64_t nq, const SearchParameters &sp, uint32_t upto_layers,
+                                          const uint32_t *exclude_dev, const uint32_t *want_dev, uint32_t flags,
+                                          uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                          uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) const;
+  // search_many_filtered_auto by row label (phnsw_search_labeled_auto): per query the posting-list scan or the strict
+  // walk by label, the scan again for short rows; every result holds min(k, list length) entries, listed vectors of
+  // want[i] only.  scan_below 0 = the library's threshold for labels (20 000, phnsw.h), UINT64_MAX = always scan.
+  // Throws unless 1 <= k <= number_of_candidates and want.size() == queries
+  inline std::vector<SearchResult> search_many_labeled_auto(const std::vector<const float *> &queries, const SearchParameters &sp,
+                                                            uint64_t k, const Labels &labels, const std::vector<uint32_t> &want,
+                                                            uint64_t scan_below = 0, std::vector<uint32_t> *routes = nullptr) const;
+  // device form (phnsw_search_labeled_auto_device): u32 ids [nq][k]; synchronises `stream` up to twice (phnsw.h)
+  inline void search_labeled_auto_device(const Labels &labels, const float *queries_dev, uint32_t ldq, const uint32_t *qids_dev,
+                                         uint64_t nq, const SearchParameters &sp, const uint32_t *exclude_dev,
+                                         const uint32_t *want_dev, uint64_t k, uint64_t scan_below, uint32_t *out_ids_dev,
+                                         float *out_d_dev, uint32_t *out_len_dev, uint32_t *out_route_dev, uint32_t *status_dev,
+                                         void *stream) const;
   // 0, or the code search_many_exact_shared would refuse this index and k with (phnsw_exact_shared_supported)
   int exact_shared_supported(uint64_t k) const { return phnsw_exact_shared_supported(ix_, k); }
   // candidates of each of nbitmaps device bitmaps (phnsw_filter_count_device): what to choose the search call by
@@ -639,6 +667,61 @@ inline void Hnsw::search_exact_labeled_device(const Labels &labels, const float 
                                               uint32_t *out_len_dev, uint32_t *status_dev, void *stream) const {
   check(phnsw_search_exact_labeled_device(ix_, labels.handle(), queries_dev, ldq, qids_dev, nq, exclude_dev, want_dev, k,
                                           out_ids_dev, out_d_dev, out_len_dev, status_dev, stream));
+}
+
+inline std::vector<SearchResult> Hnsw::search_many_labeled(const std::vector<const float *> &queries, const SearchParameters &sp,
+                                                           const Labels &labels, const std::vector<uint32_t> &want, bool strict,
+                                                           uint64_t k) const {
+  const uint64_t nq = queries.size(), dim = c_->dim(), ef = sp.number_of_candidates;
+  if (k > ef) throw Error(PHNSW_E_INVALID, "search_many_labeled: k must be 0 or 1..number_of_candidates");
+  if (want.size() != nq) throw Error(PHNSW_E_INVALID, "search_many_labeled: one wanted label per query");
+  const uint64_t w = k ? k : ef;
+  std::vector<float> q(nq * dim);
+  for (uint64_t i = 0; i < nq; i++) std::copy(queries[i], queries[i] + dim, q.begin() + i * dim);
+  std::vector<uint64_t> ids(nq * w), len(nq);
+  std::vector<float> d(nq * w);
+  check(phnsw_search_batch_labeled(ix_, labels.handle(), q.data(), nullptr, nq, &sp, 0, nullptr, want.data(),
+                                   strict ? PHNSW_FILTER_STRICT : 0u, k, ids.data(), d.data(), len.data(), nullptr));
+  std::vector<SearchResult> out(nq);
+  for (uint64_t i = 0; i < nq; i++)
+    for (uint64_t j = 0; j < len[i]; j++) out[i].push_back({ids[i * w + j], d[i * w + j]});
+  return out;
+}
+inline void Hnsw::search_batch_labeled_device(const Labels &labels, const float *queries_dev, uint32_t ldq,
+                                              const uint32_t *qids_dev, uint64_t nq, const SearchParameters &sp,
+                                              uint32_t upto_layers, const uint32_t *exclude_dev, const uint32_t *want_dev,
+                                              uint32_t flags, uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                              uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) const {
+  check(phnsw_search_batch_labeled_device(ix_, labels.handle(), queries_dev, ldq, qids_dev, nq, &sp, upto_layers, exclude_dev,
+                                          want_dev, flags, out_ids_dev, out_d_dev, out_len_dev, out_stats_dev, status_dev, stream));
+}
+inline std::vector<SearchResult> Hnsw::search_many_labeled_auto(const std::vector<const float *> &queries,
+                                                                const SearchParameters &sp, uint64_t k, const Labels &labels,
+                                                                const std::vector<uint32_t> &want, uint64_t scan_below,
+                                                                std::vector<uint32_t> *routes) const {
+  const uint64_t nq = queries.size(), dim = c_->dim();
+  if (k == 0 || k > sp.number_of_candidates)
+    throw Error(PHNSW_E_INVALID, "search_many_labeled_auto: k must be 1..number_of_candidates");
+  if (want.size() != nq) throw Error(PHNSW_E_INVALID, "search_many_labeled_auto: one wanted label per query");
+  std::vector<float> q(nq * dim);
+  for (uint64_t i = 0; i < nq; i++) std::copy(queries[i], queries[i] + dim, q.begin() + i * dim);
+  std::vector<uint64_t> ids(nq * k), len(nq);
+  std::vector<float> d(nq * k);
+  if (routes) routes->assign(nq, 0u);
+  check(phnsw_search_labeled_auto(ix_, labels.handle(), q.data(), nullptr, nq, &sp, nullptr, want.data(), k, scan_below,
+                                  ids.data(), d.data(), len.data(), routes ? routes->data() : nullptr));
+  std::vector<SearchResult> out(nq);
+  for (uint64_t i = 0; i < nq; i++)
+    for (uint64_t j = 0; j < len[i]; j++) out[i].push_back({ids[i * k + j], d[i * k + j]});
+  return out;
+}
+inline void Hnsw::search_labeled_auto_device(const Labels &labels, const float *queries_dev, uint32_t ldq,
+                                             const uint32_t *qids_dev, uint64_t nq, const SearchParameters &sp,
+                                             const uint32_t *exclude_dev, const uint32_t *want_dev, uint64_t k,
+                                             uint64_t scan_below, uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                             uint32_t *out_route_dev, uint32_t *status_dev, void *stream) const {
+  check(phnsw_search_labeled_auto_device(ix_, labels.handle(), queries_dev, ldq, qids_dev, nq, &sp, exclude_dev, want_dev, k,
+                                         scan_below, out_ids_dev, out_d_dev, out_len_dev, out_route_dev, status_dev, stream));
 }
 
 // QuantizedHnsw  pq.rs:120-131, 287-364 (per-sub-space codebooks, u8 codes)

@@ -636,6 +636,12 @@ static void fill_args(const phnsw_index *ix, const PhSearchCall &c, PhSearchArgs
     a.filter_stride = c.filter.stride;
     a.filter_flags = c.filter.flags;
   }
+  if (c.filter.label_of) {  // the label form of the filter: never both
+    a.filter = nullptr, a.filter_stride = 0u;
+    a.label_of = c.filter.label_of;
+    a.label_want = c.filter.want;
+    a.filter_flags = c.filter.flags;
+  }
   a.nq = (uint32_t)c.nq;
   a.out_ids = c.out_ids;
   a.out_d = c.out_d;
@@ -831,6 +837,7 @@ int ph_search_device(const phnsw_index *ix, const PhSearchCall &c) {
       if (b.qids) b.qids += c0;
       if (b.exclude) b.exclude += c0;
       if (b.filter) b.filter += c0 * b.filter_stride;  // per-query bitmaps follow the chunk; a shared one (stride 0) stays
+      if (b.label_want) b.label_want += c0;  // ... and so do the wanted labels; the column is indexed by VectorId
       b.out_ids += c0 * ostride;
       b.out_d += c0 * ostride;
       b.out_len += c0;

@@ -13,6 +13,13 @@
 //
 // The search kernels and the scan's arithmetic are untouched: a scanned row is phnsw_search_exact_filtered's row bit
 // for bit, a graph row is the strict row of phnsw_search_batch_filtered.
+//
+// A call describes its candidates by bitmaps or BY LABEL (phnsw_search_labeled_auto[_device]: a phnsw_labels handle and
+// want[q]).  The five steps and the two kernels are the same; only where a step gets its facts differs:
+//   1. the counts are the lengths of the posting lists (ph_labels_count), no bitmap is counted
+//   3. the walk is the search kernels' label mode over the handle's column
+//   4. "exclude[q] is a candidate" is label_of[exclude[q]] == want[q]
+//   5. the scan is filter_labeled.hip's, over the scan list (PhLabeledCall::list)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -39,6 +46,7 @@ struct PhAutoArgs {
   const uint32_t *filter;          // nullptr: every vector of the index
   uint32_t filter_stride;          // 0 = one bitmap for all
   uint32_t per_query;              // counts holds nq entries, else one
+  const uint32_t *label_of, *want;  // a call by label: the handle's column [n] and want [nq]; else nullptr
   // the index's bottom layer, as the candidate test takes it
   uint32_t n_nodes;
   const uint32_t *nodes, *vec2node;
@@ -125,7 +133,9 @@ __global__ __launch_bounds__(64) void ph_auto_finish_kernel(PhAutoArgs a) {
     }
     if (lane == 0) {
       const uint32_t *const bitmap = a.filter ? a.filter + (uint64_t)q * a.filter_stride : nullptr;
-      const uint32_t e = (ex != PH_EMPTY32 && ph_exact_is_candidate(bitmap, ex, nlim, a.vec2node)) ? 1u : 0u;
+      const bool ex_cand = a.label_of ? ph_auto_label_candidate(a.label_of, a.n, a.want[q], ex, PHNSW_LABEL_NONE)
+                                      : ph_exact_is_candidate(bitmap, ex, nlim, a.vec2node);
+      const uint32_t e = (ex != PH_EMPTY32 && ex_cand) ? 1u : 0u;
       const uint32_t full = ph_auto_full_len(a.counts[a.per_query ? q : 0u], e, a.k);
       if (st == ST_OVERFLOW || (st == ST_OK && kept < full)) {
         const uint32_t at = atomicAdd(&a.head[1], 1u);  // < nq: q was in the graph list, not in this one
@@ -198,7 +208,8 @@ int auto_run(const phnsw_index *ix, const PhAutoCall &c, PhAutoSet &set) {
   const phnsw_store *s = ix->store;
   const uint64_t nq = c.nq;
   const uint32_t ef = (uint32_t)c.sp->number_of_candidates;
-  const bool per_query = c.filter.words && c.filter.stride != 0u;
+  const bool by_label = c.labels != nullptr;
+  const bool per_query = by_label || (c.filter.words && c.filter.stride != 0u);
   PH_TRY(set_ensure(set, (size_t)ph_auto_scratch_words(nq, per_query, ef), c.stream));
   const uint64_t nb = ph_auto_bitmaps(nq, per_query);
   uint32_t *const head = set.block, *const counts = head + PH_AUTO_HEAD_WORDS, *const glist = counts + nb;
@@ -206,12 +217,20 @@ int auto_run(const phnsw_index *ix, const PhAutoCall &c, PhAutoSet &set) {
   uint32_t *const walk_len = route_own + nq, *const walk_ids = walk_len + nq;
   float *const walk_d = (float *)(walk_ids + nq * ef);
 
-  PH_TRY(ph_filter_count(ix, c.filter, nb, counts, c.stream));
+  if (by_label)
+    PH_TRY(ph_labels_count(c.labels, c.want, nq, counts, c.stream));
+  else
+    PH_TRY(ph_filter_count(ix, c.filter, nb, counts, c.stream));
   PhAutoArgs a = {};
   a.nq = (uint32_t)nq, a.n = (uint32_t)s->n, a.k = c.k, a.ef = ef;
-  a.scan_below = ph_auto_scan_below(c.scan_below, per_query);
+  a.scan_below = by_label ? ph_auto_scan_below_labeled(c.scan_below) : ph_auto_scan_below(c.scan_below, per_query);
   a.qids = c.qids, a.exclude = c.exclude;
-  a.filter = c.filter.words, a.filter_stride = c.filter.words ? c.filter.stride : 0u, a.per_query = per_query ? 1u : 0u;
+  PhFilter filter = c.filter;  // what the walk gets
+  if (by_label) {
+    filter = PhFilter{};
+    filter.label_of = a.label_of = ph_labels_column(c.labels), filter.want = a.want = c.want;
+  }
+  a.filter = filter.words, a.filter_stride = filter.words ? filter.stride : 0u, a.per_query = per_query ? 1u : 0u;
   ph_exact_bottom_layer(ix, &a.n_nodes, &a.nodes, &a.vec2node);
   a.head = head, a.counts = counts, a.glist = glist, a.slist = slist, a.route = c.out_route ? c.out_route : route_own;
   a.walk_ids = walk_ids, a.walk_d = walk_d, a.walk_len = walk_len;
@@ -228,7 +247,7 @@ int auto_run(const phnsw_index *ix, const PhAutoCall &c, PhAutoSet &set) {
     w.queries = c.queries, w.ldq = c.ldq, w.qids = c.qids, w.exclude = c.exclude;
     w.nq = glen, w.order = glist;  // positions of the list; the kernels address everything by the query index it holds
     w.sp = c.sp;
-    w.filter = c.filter, w.filter.flags = PHNSW_FILTER_STRICT;
+    w.filter = filter, w.filter.flags = PHNSW_FILTER_STRICT;
     w.out_ids = walk_ids, w.out_d = walk_d, w.out_len = walk_len, w.status = c.status;
     w.stream = c.stream;
     PH_TRY(ph_search_device(ix, w));
@@ -238,7 +257,15 @@ int auto_run(const phnsw_index *ix, const PhAutoCall &c, PhAutoSet &set) {
     PH_HIP(hipStreamSynchronize(c.stream));
     slen = std::min<uint64_t>(set.h_head[1], nq);
   }
-  if (slen) {
+  if (slen && by_label) {
+    PhLabeledCall x = {};
+    x.queries = c.queries, x.ldq = c.ldq, x.qids = c.qids, x.exclude = c.exclude, x.want = c.want;
+    x.nq = slen, x.list = slist;
+    x.k = c.k;
+    x.out_ids = c.out_ids, x.out_d = c.out_d, x.out_len = c.out_len, x.status = c.status;
+    x.stream = c.stream;
+    PH_TRY(ph_labeled_device(ix, c.labels, x));
+  } else if (slen) {
     PhExactCall x = {};
     x.queries = c.queries, x.ldq = c.ldq, x.qids = c.qids, x.exclude = c.exclude;
     x.nq = slen, x.list = slist;
@@ -335,19 +362,18 @@ extern "C" int phnsw_search_filtered_auto_device(const phnsw_index *ix, const fl
   return ph_auto_device(ix, c);
 } catch (...) { return ph_caught(); }
 
-extern "C" int phnsw_search_filtered_auto(const phnsw_index *ix, const float *queries, const uint64_t *qids, uint64_t nq,
-                                          const phnsw_search_params *sp, const uint64_t *exclude, const uint32_t *filter,
-                                          uint32_t filter_stride_words, uint64_t k, uint64_t scan_below, uint64_t *out_ids,
-                                          float *out_d, uint64_t *out_len, uint32_t *out_route) try {
-  const char *const call = "phnsw_search_filtered_auto";
-  PH_TRY(auto_check(ix, sp, k, call));
-  if (nq == 0) return 0;
-  if (!ph_auto_queries_valid(queries != nullptr, qids != nullptr) || !out_ids || !out_d || !out_len || !ph_auto_nq_valid(nq)) {
-    ph_set_error("%s: invalid argument (queries or qids, exactly one; outputs)", call);
+// the host form of both descriptions; lb != nullptr: by label (want: host words [nq]; filter unused), else by bitmap
+static int auto_host(const char *call, const phnsw_index *ix, const phnsw_labels *lb, const float *queries, const uint64_t *qids,
+                     uint64_t nq, const phnsw_search_params *sp, const uint64_t *exclude, const uint32_t *filter,
+                     uint32_t filter_stride_words, const uint32_t *want, uint64_t k, uint64_t scan_below, uint64_t *out_ids,
+                     float *out_d, uint64_t *out_len, uint32_t *out_route) {
+  if (!ph_auto_queries_valid(queries != nullptr, qids != nullptr) || !out_ids || !out_d || !out_len || !ph_auto_nq_valid(nq) ||
+      (lb && (!want || nq > 0x7FFFFFFEull))) {
+    ph_set_error("%s: invalid argument (queries or qids, exactly one; outputs%s)", call, lb ? "; want; nq < 2^31 - 1" : "");
     return PHNSW_E_INVALID;
   }
-  PhFilter hf;
-  PH_TRY(ph_filter_check(ix, filter, filter_stride_words, 0u, call, &hf));
+  PhFilter hf = {};
+  if (!lb) PH_TRY(ph_filter_check(ix, filter, filter_stride_words, 0u, call, &hf));
   const phnsw_store *s = ix->store;
   if (qids)
     for (uint64_t i = 0; i < nq; i++)
@@ -384,8 +410,8 @@ extern "C" int phnsw_search_filtered_auto(const phnsw_index *ix, const float *qu
     }
     c.queries = q, c.ldq = ld;
   }
-  uint32_t *small = nullptr;  // qid | exclude | len | status | route   [5][nq]
-  PH_TRY(hb.alloc(&small, (size_t)nq * 5u * 4u));
+  uint32_t *small = nullptr;  // qid | exclude | len | status | route | want   [6][nq]
+  PH_TRY(hb.alloc(&small, (size_t)nq * 6u * 4u));
   if (qids || exclude) {
     h_in.resize(2u * nq);
     if (qids)
@@ -397,7 +423,10 @@ extern "C" int phnsw_search_filtered_auto(const phnsw_index *ix, const float *qu
     if (exclude) c.exclude = small + nq;
   }
   c.filter = hf;
-  if (hf.words) {  // whole strides, as phnsw_search_batch_filtered copies them
+  if (lb) {  // the description of a call by label: 4 bytes per query
+    PH_HIP(hipMemcpyAsync(small + 5u * nq, want, (size_t)nq * 4u, hipMemcpyHostToDevice, st));
+    c.labels = lb, c.want = small + 5u * nq;
+  } else if (hf.words) {  // whole strides, as phnsw_search_batch_filtered copies them
     const size_t words = hf.stride ? (size_t)nq * hf.stride : (size_t)((s->n + 31u) / 32u);
     uint32_t *f = nullptr;
     PH_TRY(hb.alloc(&f, words * 4u));
@@ -431,4 +460,56 @@ extern "C" int phnsw_search_filtered_auto(const phnsw_index *ix, const float *qu
     if (out_route) out_route[i] = h_out[2u * nq + i];
   }
   return 0;
+}
+
+extern "C" int phnsw_search_filtered_auto(const phnsw_index *ix, const float *queries, const uint64_t *qids, uint64_t nq,
+                                          const phnsw_search_params *sp, const uint64_t *exclude, const uint32_t *filter,
+                                          uint32_t filter_stride_words, uint64_t k, uint64_t scan_below, uint64_t *out_ids,
+                                          float *out_d, uint64_t *out_len, uint32_t *out_route) try {
+  const char *const call = "phnsw_search_filtered_auto";
+  PH_TRY(auto_check(ix, sp, k, call));
+  if (nq == 0) return 0;
+  return auto_host(call, ix, nullptr, queries, qids, nq, sp, exclude, filter, filter_stride_words, nullptr, k, scan_below,
+                   out_ids, out_d, out_len, out_route);
+} catch (...) { return ph_caught(); }
+
+// ---- by label
+
+extern "C" int phnsw_search_labeled_auto(const phnsw_index *ix, const phnsw_labels *lb, const float *queries, const uint64_t *qids,
+                                         uint64_t nq, const phnsw_search_params *sp, const uint64_t *exclude,
+                                         const uint32_t *want, uint64_t k, uint64_t scan_below, uint64_t *out_ids, float *out_d,
+                                         uint64_t *out_len, uint32_t *out_route) try {
+  const char *const call = "phnsw_search_labeled_auto";
+  PH_TRY(auto_check(ix, sp, k, call));
+  PH_TRY(ph_labeled_check(ix, lb, k, call));
+  if (nq == 0) return 0;
+  return auto_host(call, ix, lb, queries, qids, nq, sp, exclude, nullptr, 0u, want, k, scan_below, out_ids, out_d, out_len,
+                   out_route);
+} catch (...) { return ph_caught(); }
+
+extern "C" int phnsw_search_labeled_auto_device(const phnsw_index *ix, const phnsw_labels *lb, const float *queries_dev,
+                                                uint32_t ldq, const uint32_t *qids_dev, uint64_t nq,
+                                                const phnsw_search_params *sp, const uint32_t *exclude_dev,
+                                                const uint32_t *want_dev, uint64_t k, uint64_t scan_below, uint32_t *out_ids_dev,
+                                                float *out_d_dev, uint32_t *out_len_dev, uint32_t *out_route_dev,
+                                                uint32_t *status_dev, void *stream) try {
+  const char *const call = "phnsw_search_labeled_auto_device";
+  PH_TRY(auto_check(ix, sp, k, call));
+  PH_TRY(ph_labeled_check(ix, lb, k, call));
+  if (nq == 0) return 0;
+  if (!ph_auto_queries_valid(queries_dev != nullptr, qids_dev != nullptr) || !out_ids_dev || !out_d_dev || !out_len_dev ||
+      !status_dev || !want_dev || !ph_auto_nq_valid(nq) || nq > 0x7FFFFFFEull ||
+      (queries_dev && (ldq < ix->store->ld || (ldq % 4) || ((uintptr_t)queries_dev % 16)))) {
+    ph_set_error("%s: invalid argument (queries or qids, exactly one; outputs; want; queries need ldq >= store ld, multiple "
+                 "of 4, 16-byte base)", call);
+    return PHNSW_E_INVALID;
+  }
+  PhAutoCall c = {};
+  c.labels = lb, c.want = want_dev;
+  c.queries = queries_dev, c.ldq = ldq, c.qids = qids_dev, c.exclude = exclude_dev, c.nq = nq, c.sp = sp;
+  c.k = (uint32_t)k, c.scan_below = scan_below;
+  c.out_ids = out_ids_dev, c.out_d = out_d_dev, c.out_len = out_len_dev, c.out_route = out_route_dev, c.status = status_dev;
+  c.stream = (hipStream_t)stream;
+  PH_HIP(hipSetDevice(ix->store->device));
+  return ph_auto_device(ix, c);
 } catch (...) { return ph_caught(); }

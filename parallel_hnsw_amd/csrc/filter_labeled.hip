@@ -7,8 +7,9 @@
 //   candidates of query q   =    the listed vectors of want[q], except exclude[q]
 //   result                  =    the k candidates with the smallest (distance, id), ascending
 //
-//   construction  ph_label_key_kernel (the label, or NONE where the vector is not listed), stable radix sort of
-//                 (label, id), ph_label_flags_kernel, exclusive sum, ph_label_heads_kernel: values, first, ids
+//   construction  ph_label_key_kernel (the label, or NONE where the vector is not listed: label_of, kept with the
+//                 handle for the label walk), stable radix sort of (label, id), ph_label_flags_kernel, exclusive sum,
+//                 ph_label_heads_kernel: values, first, ids
 //   a call     1. ph_labeled_lookup_kernel: per query the slot of its label (label_plan.h), radix sort of (slot, query):
 //                 the queries of one label are adjacent positions; ph_labeled_tileflag_kernel, exclusive sum,
 //                 ph_labeled_tiles_kernel: the tile table and its count, on the device
@@ -24,6 +25,10 @@
 // same order (chain_partial with the row as x and the query as q, wave_sum4, finalize_metric), four rows at a time as
 // batch_distances takes them.  What filter_exact.hip has beyond the shared headers is restated here; no existing
 // kernel is touched (profiles/filter_labeled/).
+//
+// The graph walk by label (phnsw_search_batch_labeled[_device], at the end of this file) is the search kernels' own
+// label mode (search_labeled.hip) over label_of; the routed call (phnsw_search_labeled_auto) is filter_auto.hip's and
+// takes its scan from here through the subset form of a call (PhLabeledCall::list).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -58,6 +63,7 @@ struct phnsw_labels {
   uint32_t *values = nullptr;  // [nlabels] ascending
   uint32_t *first = nullptr;   // [nlabels + 1]
   uint32_t *ids = nullptr;     // [listed] (allocated [n]): ascending within a label
+  uint32_t *label_of = nullptr;  // [n]: the label of a listed vector, PHNSW_LABEL_NONE elsewhere (the label walk's column)
   std::mutex mutex;
   std::vector<PhLabeledSet *> sets;  // handed out under mutex, one per call in flight
   std::vector<PhLabelResident> resident;  // under mutex
@@ -107,12 +113,13 @@ struct PhLabeledArgs {
   const float *queries;  // [nq][ldq] or nullptr
   uint32_t ldq;
   const uint32_t *qids, *exclude, *want;  // [nq]; qids, exclude nullable
+  const uint32_t *list;                   // nullable: the subset form -- position p of the lookup is query list[p]
   uint32_t nq, n, k, slices, T;
   // the posting lists
   const uint32_t *values, *first, *ids;
   uint32_t nlabels;
   // the grouping (label_plan.h)
-  uint32_t *slot, *iota;            // [nq] by query
+  uint32_t *slot, *iota;            // [nq] by lookup position: its slot, its query (the position itself without a list)
   const uint32_t *sslot, *order;    // [nq] by position: its slot, its query
   uint32_t *flags;                  // [nq + 1]
   const uint32_t *tidx;             // [nq + 1]: exclusive sum of flags
@@ -125,10 +132,11 @@ struct PhLabeledArgs {
 };
 
 __global__ __launch_bounds__(256) void ph_labeled_lookup_kernel(PhLabeledArgs a) {
-  for (uint64_t q = (uint64_t)blockIdx.x * 256u + threadIdx.x; q < a.nq; q += (uint64_t)gridDim.x * 256u) {
+  for (uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x; p < a.nq; p += (uint64_t)gridDim.x * 256u) {
+    const uint32_t q = ph_label_seed(a.list, (uint32_t)p);  // every kernel after the sort addresses by order[pos]
     const bool bad_query = !a.queries && a.qids[q] >= a.n;
-    a.slot[q] = bad_query ? PH_LABEL_SLOT_NONE : ph_label_slot(a.values, a.nlabels, a.want[q], PHNSW_LABEL_NONE);
-    a.iota[q] = (uint32_t)q;
+    a.slot[p] = bad_query ? PH_LABEL_SLOT_NONE : ph_label_slot(a.values, a.nlabels, a.want[q], PHNSW_LABEL_NONE);
+    a.iota[p] = q;
   }
 }
 
@@ -429,18 +437,6 @@ struct PhLabeledSet {
   bool in_use = false;
 };
 
-struct PhLabeledCall {
-  const float *queries;
-  uint32_t ldq;
-  const uint32_t *qids, *exclude, *want;
-  uint64_t nq;
-  uint32_t k;
-  uint32_t *out_ids;
-  float *out_d;
-  uint32_t *out_len, *status;
-  hipStream_t stream;
-};
-
 namespace {
 
 const size_t PH_LABEL_SETS = 4;  // scratch sets a handle makes before calls share one behind its event
@@ -513,16 +509,10 @@ long long env_ll(const char *name) {
 
 uint32_t grid1(uint64_t items) { return (uint32_t)std::min<uint64_t>((items + 255u) / 256u, 1u << 16); }
 
-// index, k, handle, store: the checks every search form makes before it looks at another argument, in this order
-int labeled_check(const phnsw_index *ix, const phnsw_labels *lb, uint64_t k, const char *call) {
-  if (!ix || ix->layers.empty()) {
-    ph_set_error("%s: null index or index without layers", call);
-    return PHNSW_E_INVALID;
-  }
-  if (!ph_exact_k_valid(k)) {
-    ph_set_error("%s: k must be 1..1024 (got %llu)", call, (unsigned long long)k);
-    return PHNSW_E_INVALID;
-  }
+}  // namespace
+
+// the handle test every call by label makes (ix has layers)
+int ph_labels_fresh(const phnsw_index *ix, const phnsw_labels *lb, const char *call) {
   if (!lb) {
     ph_set_error("%s: null labels", call);
     return PHNSW_E_INVALID;
@@ -533,6 +523,20 @@ int labeled_check(const phnsw_index *ix, const phnsw_labels *lb, uint64_t k, con
                  lb->n_nodes, (unsigned long long)ix->store->n, ix->layers.back().n_nodes);
     return PHNSW_E_INVALID;
   }
+  return 0;
+}
+
+// index, k, handle, store: the checks every exact form makes before it looks at another argument, in this order
+int ph_labeled_check(const phnsw_index *ix, const phnsw_labels *lb, uint64_t k, const char *call) {
+  if (!ix || ix->layers.empty()) {
+    ph_set_error("%s: null index or index without layers", call);
+    return PHNSW_E_INVALID;
+  }
+  if (!ph_exact_k_valid(k)) {
+    ph_set_error("%s: k must be 1..1024 (got %llu)", call, (unsigned long long)k);
+    return PHNSW_E_INVALID;
+  }
+  PH_TRY(ph_labels_fresh(ix, lb, call));
   if (ph_store_pq_shared(ix->store)) {  // as for the distance batch, whose arithmetic the scan runs
     ph_set_error("%s: not supported over a shared-codebook PQ store; use its reconstruction store", call);
     return PHNSW_E_UNSUPPORTED;
@@ -540,7 +544,12 @@ int labeled_check(const phnsw_index *ix, const phnsw_labels *lb, uint64_t k, con
   return ph_exact_supported(ix, (uint32_t)k);  // the row length, a PQ table beside the scan's LDS
 }
 
-// the orchestration on a set the caller holds; c is checked, 0 < nq <= PH_LABEL_NQ_MAX.  Enqueues and returns.
+const uint32_t *ph_labels_column(const phnsw_labels *lb) { return lb->label_of; }
+
+namespace {
+
+// the orchestration on a set the caller holds; c is checked, 0 < nq <= PH_LABEL_NQ_MAX (with a list: its length).
+// Enqueues and returns.
 int labeled_run(const phnsw_index *ix, const phnsw_labels *lb, const PhLabeledCall &c, PhLabeledSet &set) {
   const phnsw_store *s = ix->store;
   const uint64_t nq = c.nq;
@@ -550,7 +559,7 @@ int labeled_run(const phnsw_index *ix, const phnsw_labels *lb, const PhLabeledCa
   uint32_t *const pre = (uint32_t *)set.pre;
   PhLabeledArgs a = {};
   a.dist = ph_dist_args(s);
-  a.queries = c.queries, a.ldq = c.ldq, a.qids = c.qids, a.exclude = c.exclude, a.want = c.want;
+  a.queries = c.queries, a.ldq = c.ldq, a.qids = c.qids, a.exclude = c.exclude, a.want = c.want, a.list = c.list;
   a.nq = (uint32_t)nq, a.n = (uint32_t)s->n, a.k = c.k;
   a.values = lb->values, a.first = lb->first, a.ids = lb->ids, a.nlabels = (uint32_t)lb->nlabels;
   a.slot = pre + lay.slot, a.iota = pre + lay.iota, a.sslot = pre + lay.sslot, a.order = pre + lay.order;
@@ -664,6 +673,7 @@ void labels_free(phnsw_labels *lb) {
   if (lb->values) hipFree(lb->values);
   if (lb->first) hipFree(lb->first);
   if (lb->ids) hipFree(lb->ids);
+  if (lb->label_of) hipFree(lb->label_of);
   delete lb;
 }
 
@@ -682,6 +692,8 @@ int labels_build(const phnsw_index *ix, const uint32_t *labels_dev, uint64_t n, 
   if (n == 0) {
     PH_HIP(hipMalloc(&lb->first, 4));
     PH_HIP(hipMemsetAsync(lb->first, 0, 4, stream));
+    PH_HIP(hipMalloc(&lb->label_of, 4));  // never null: a null column would read as "no label filter"
+    PH_HIP(hipMemsetAsync(lb->label_of, 0xFF, 4, stream));
     PH_HIP(hipStreamSynchronize(stream));
     *out = lb, drop.lb = nullptr;
     return 0;
@@ -690,9 +702,10 @@ int labels_build(const phnsw_index *ix, const uint32_t *labels_dev, uint64_t n, 
   const uint32_t *nodes, *vec2node;
   ph_exact_bottom_layer(ix, &n_nodes, &nodes, &vec2node);
   HostBlocks hb{stream, {}};
-  uint32_t *keys = nullptr, *skeys = nullptr, *iota = nullptr, *flags = nullptr, *slots = nullptr, *head = nullptr;
+  uint32_t *skeys = nullptr, *iota = nullptr, *flags = nullptr, *slots = nullptr, *head = nullptr;
   void *tmp = nullptr;
-  PH_TRY(hb.alloc(&keys, (size_t)n * 4u));
+  PH_HIP(hipMalloc(&lb->label_of, (size_t)n * 4u));  // the sort's keys, which it leaves as they are: kept
+  uint32_t *const keys = lb->label_of;
   PH_TRY(hb.alloc(&skeys, (size_t)n * 4u));
   PH_TRY(hb.alloc(&iota, (size_t)n * 4u));
   PH_TRY(hb.alloc(&flags, (size_t)(n + 1u) * 4u));
@@ -760,6 +773,21 @@ int labels_create_check(const phnsw_index *ix, const void *labels, uint64_t n, p
 
 }  // namespace
 
+int ph_labels_count(const phnsw_labels *lb, const uint32_t *want_dev, uint64_t nq, uint32_t *out_count_dev, hipStream_t stream) {
+  hipLaunchKernelGGL(ph_labeled_count_kernel, dim3(grid1(nq)), dim3(256), 0, stream, lb->values, lb->first, (uint32_t)lb->nlabels,
+                     want_dev, nq, out_count_dev);
+  PH_HIP(hipGetLastError());
+  return 0;
+}
+
+int ph_labeled_device(const phnsw_index *ix, const phnsw_labels *lb, const PhLabeledCall &c) {
+  if (c.nq == 0) return 0;
+  phnsw_labels *mlb = const_cast<phnsw_labels *>(lb);
+  PhLabeledSet *set = set_acquire(mlb, c.stream, false);
+  SetGuard guard{mlb, set, c.stream};
+  return labeled_run(ix, lb, c, *set);
+}
+
 // ------------------------------------------------------------------ C ABI
 
 extern "C" int phnsw_labels_create_device(const phnsw_index *ix, const uint32_t *labels_dev, uint64_t n, void *stream,
@@ -806,10 +834,7 @@ extern "C" int phnsw_labels_count_device(const phnsw_labels *lb, const uint32_t 
     return PHNSW_E_INVALID;
   }
   PH_HIP(hipSetDevice(lb->device));
-  hipLaunchKernelGGL(ph_labeled_count_kernel, dim3(grid1(nq)), dim3(256), 0, (hipStream_t)stream, lb->values, lb->first,
-                     (uint32_t)lb->nlabels, want_dev, nq, out_count_dev);
-  PH_HIP(hipGetLastError());
-  return 0;
+  return ph_labels_count(lb, want_dev, nq, out_count_dev, (hipStream_t)stream);
 } catch (...) { return ph_caught(); }
 
 extern "C" void phnsw_labels_destroy(phnsw_labels *lb) {
@@ -826,7 +851,7 @@ extern "C" int phnsw_search_exact_labeled_device(const phnsw_index *ix, const ph
                                                  const uint32_t *want_dev, uint64_t k, uint32_t *out_ids_dev, float *out_d_dev,
                                                  uint32_t *out_len_dev, uint32_t *status_dev, void *stream) try {
   const char *const call = "phnsw_search_exact_labeled_device";
-  PH_TRY(labeled_check(ix, lb, k, call));
+  PH_TRY(ph_labeled_check(ix, lb, k, call));
   if (nq == 0) return 0;
   if (((!queries_dev) == (!qids_dev)) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev || !want_dev ||
       nq > PH_LABEL_NQ_MAX || (queries_dev && (ldq < ix->store->ld || (ldq % 4) || ((uintptr_t)queries_dev % 16)))) {
@@ -840,17 +865,14 @@ extern "C" int phnsw_search_exact_labeled_device(const phnsw_index *ix, const ph
   c.out_ids = out_ids_dev, c.out_d = out_d_dev, c.out_len = out_len_dev, c.status = status_dev;
   c.stream = (hipStream_t)stream;
   PH_HIP(hipSetDevice(ix->store->device));
-  phnsw_labels *mlb = const_cast<phnsw_labels *>(lb);
-  PhLabeledSet *set = set_acquire(mlb, c.stream, false);
-  SetGuard guard{mlb, set, c.stream};
-  return labeled_run(ix, lb, c, *set);
+  return ph_labeled_device(ix, lb, c);
 } catch (...) { return ph_caught(); }
 
 extern "C" int phnsw_search_exact_labeled(const phnsw_index *ix, const phnsw_labels *lb, const float *queries, const uint64_t *qids,
                                           uint64_t nq, const uint64_t *exclude, const uint32_t *want, uint64_t k,
                                           uint64_t *out_ids, float *out_d, uint64_t *out_len) try {
   const char *const call = "phnsw_search_exact_labeled";
-  PH_TRY(labeled_check(ix, lb, k, call));
+  PH_TRY(ph_labeled_check(ix, lb, k, call));
   if (nq == 0) return 0;
   if ((!queries) == (!qids)) {
     ph_set_error("%s: pass queries or qids (exactly one)", call);
@@ -927,5 +949,162 @@ extern "C" int phnsw_search_exact_labeled(const phnsw_index *ix, const phnsw_lab
   PH_HIP(hipMemcpyAsync(out_d, dk, (size_t)nq * kk * 4u, hipMemcpyDeviceToHost, st));
   PH_HIP(hipStreamSynchronize(st));
   for (uint64_t i = 0; i < nq; i++) out_len[i] = h_len[i];
+  return 0;
+} catch (...) { return ph_caught(); }
+
+// ------------------------------------------------------------------ the graph walk by label
+
+namespace {
+
+// what both forms of the walk check before they look at a pointer: index and parameters, the handle, the flags
+int walk_check(const phnsw_index *ix, const phnsw_labels *lb, const phnsw_search_params *sp, uint32_t flags, const char *call) {
+  PH_TRY(ph_check_sp(ix, sp));
+  PH_TRY(ph_labels_fresh(ix, lb, call));
+  if (flags & ~(uint32_t)PHNSW_FILTER_STRICT) {
+    ph_set_error("%s: unknown flag bits 0x%x", call, flags);
+    return PHNSW_E_INVALID;
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int phnsw_search_batch_labeled_device(const phnsw_index *ix, const phnsw_labels *lb, const float *queries_dev,
+                                                 uint32_t ldq, const uint32_t *qids_dev, uint64_t nq,
+                                                 const phnsw_search_params *sp, uint32_t upto_layers, const uint32_t *exclude_dev,
+                                                 const uint32_t *want_dev, uint32_t flags, uint32_t *out_ids_dev, float *out_d_dev,
+                                                 uint32_t *out_len_dev, uint32_t *out_stats_dev, uint32_t *status_dev,
+                                                 void *stream) try {
+  const char *const call = "phnsw_search_batch_labeled_device";
+  PH_TRY(walk_check(ix, lb, sp, flags, call));
+  if (nq == 0) return 0;
+  if (((!queries_dev) == (!qids_dev)) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev || !want_dev ||
+      nq > 0xFFFFFFFFull || (queries_dev && (ldq < ix->store->ld || (ldq % 4) || ((uintptr_t)queries_dev % 16)))) {
+    ph_set_error("%s: invalid argument (queries or qids, exactly one; outputs; want; queries need ldq >= store ld, multiple of "
+                 "4, 16-byte base)", call);
+    return PHNSW_E_INVALID;
+  }
+  PhSearchCall c = {};
+  c.queries = queries_dev, c.ldq = ldq, c.qids = qids_dev, c.exclude = exclude_dev, c.nq = nq;
+  c.sp = sp, c.upto = upto_layers;
+  c.filter.label_of = lb->label_of, c.filter.want = want_dev, c.filter.flags = flags;
+  c.out_ids = out_ids_dev, c.out_d = out_d_dev, c.out_len = out_len_dev, c.status = status_dev, c.out_stats = out_stats_dev;
+  c.stream = (hipStream_t)stream;
+  PH_HIP(hipSetDevice(ix->store->device));
+  return ph_search_device(ix, c);
+} catch (...) { return ph_caught(); }
+
+// The host form stages everything once, on the stream of a scratch set of the handle: query rows, the id words, want.
+// Queries whose frontier spill overflowed (status 5) are re-run from a device list with 8x the room, as ph_search_host
+// re-runs them.
+extern "C" int phnsw_search_batch_labeled(const phnsw_index *ix, const phnsw_labels *lb, const float *queries,
+                                          const uint64_t *qids, uint64_t nq, const phnsw_search_params *sp, uint32_t upto_layers,
+                                          const uint64_t *exclude, const uint32_t *want, uint32_t flags, uint64_t k,
+                                          uint64_t *out_ids, float *out_d, uint64_t *out_len, uint64_t *out_stats) try {
+  const char *const call = "phnsw_search_batch_labeled";
+  PH_TRY(walk_check(ix, lb, sp, flags, call));
+  const uint32_t ef = (uint32_t)sp->number_of_candidates;
+  if (k > ef) {
+    ph_set_error("%s: k must be 0 (the whole queue) or 1..number_of_candidates (got %llu, number_of_candidates %u)", call,
+                 (unsigned long long)k, ef);
+    return PHNSW_E_INVALID;
+  }
+  if (nq == 0) return 0;
+  if ((!queries) == (!qids)) {
+    ph_set_error("%s: pass queries or qids (exactly one)", call);
+    return PHNSW_E_INVALID;
+  }
+  if (!out_ids || !out_d || !out_len || !want || nq > 0xFFFFFFFFull) {
+    ph_set_error("%s: invalid argument (outputs; want; nq < 2^32)", call);
+    return PHNSW_E_INVALID;
+  }
+  const phnsw_store *s = ix->store;
+  PH_HIP(hipSetDevice(s->device));
+  if (qids)
+    for (uint64_t i = 0; i < nq; i++)
+      if (qids[i] >= s->n) {
+        ph_set_error("%s: stored query id %llu out of range", call, (unsigned long long)qids[i]);
+        return PHNSW_E_INVALID;
+      }
+  // host words of the per-query ids, alive until the stream has drained (HostBlocks is declared after them)
+  std::vector<uint32_t> h_in, h_out(4u * nq), redo;
+  phnsw_labels *mlb = const_cast<phnsw_labels *>(lb);
+  PhLabeledSet *set = set_acquire(mlb, nullptr, true);
+  if (!set->stream) {
+    hipError_t e = hipStreamCreateWithFlags(&set->stream, hipStreamNonBlocking);
+    if (e != hipSuccess) {
+      SetGuard g{mlb, set, nullptr};
+      return ph_hip_fail(e, "host path: stream", __FILE__, __LINE__);
+    }
+  }
+  const hipStream_t st = set->stream;
+  SetGuard guard{mlb, set, st};
+  HostBlocks hb{st, {}};
+
+  PhSearchCall c = {};
+  const uint32_t ld = s->ld, kk = k ? (uint32_t)k : ef;
+  if (queries) {  // rows padded to the store's row length
+    float *q = nullptr;
+    PH_TRY(hb.alloc(&q, (size_t)nq * ld * 4u));
+    if (ld != s->dim) {
+      PH_HIP(hipMemsetAsync(q, 0, (size_t)nq * ld * 4u, st));
+      PH_HIP(hipMemcpy2DAsync(q, (size_t)ld * 4u, queries, (size_t)s->dim * 4u, (size_t)s->dim * 4u, nq, hipMemcpyHostToDevice, st));
+    } else {
+      PH_HIP(hipMemcpyAsync(q, queries, (size_t)nq * ld * 4u, hipMemcpyHostToDevice, st));
+    }
+    c.queries = q, c.ldq = ld;
+  }
+  uint32_t *small = nullptr;  // qid | exclude | want | redo list | len | status | stats(2)   [8][nq]
+  PH_TRY(hb.alloc(&small, (size_t)nq * 8u * 4u));
+  h_in.resize(3u * nq);
+  if (qids)
+    for (uint64_t i = 0; i < nq; i++) h_in[i] = (uint32_t)qids[i];
+  if (exclude)
+    for (uint64_t i = 0; i < nq; i++) h_in[nq + i] = exclude[i] >= s->n ? PH_EMPTY32 : (uint32_t)exclude[i];
+  for (uint64_t i = 0; i < nq; i++) h_in[2u * nq + i] = want[i];
+  PH_HIP(hipMemcpyAsync(small, h_in.data(), (size_t)nq * 3u * 4u, hipMemcpyHostToDevice, st));
+  if (qids) c.qids = small;
+  if (exclude) c.exclude = small + nq;
+  c.filter.label_of = lb->label_of, c.filter.want = small + 2u * nq, c.filter.flags = flags;
+  uint32_t *ids = nullptr;
+  float *d = nullptr, *dk = nullptr;
+  uint64_t *ids64 = nullptr;
+  PH_TRY(hb.alloc(&ids, (size_t)nq * ef * 4u));
+  PH_TRY(hb.alloc(&d, (size_t)nq * ef * 4u));
+  PH_TRY(hb.alloc(&ids64, (size_t)nq * kk * 8u));
+  PH_TRY(hb.alloc(&dk, (size_t)nq * kk * 4u));
+  c.nq = nq, c.sp = sp, c.upto = upto_layers;
+  c.out_ids = ids, c.out_d = d, c.out_len = small + 4u * nq, c.status = small + 5u * nq, c.out_stats = small + 6u * nq;
+  c.stream = st;
+  uint32_t ovf_cap = ph_default_ovf_cap(ef);
+  for (int attempt = 0;; attempt++) {
+    PH_TRY(ph_search_device(ix, c));
+    PH_HIP(hipMemcpyAsync(h_out.data(), small + 4u * nq, (size_t)nq * 4u * 4u, hipMemcpyDeviceToHost, st));
+    PH_HIP(hipStreamSynchronize(st));
+    redo.clear();
+    for (uint64_t i = 0; i < nq; i++) {
+      if (h_out[nq + i] == 4u) {
+        ph_set_error("search: a candidate vector is missing from a lower layer (layers not nested, lib.rs:261)");
+        return PHNSW_E_MISSING_NODE;
+      }
+      if (h_out[nq + i] == 5u) redo.push_back((uint32_t)i);
+    }
+    if (redo.empty()) break;
+    if (attempt == 3) {
+      ph_set_error("search: frontier spill exceeded %u entries for %zu queries", ovf_cap, redo.size());
+      return PHNSW_E_OVERFLOW;
+    }
+    // the overflowed queries alone, from a device list, with 8x the room: everything stays addressed by the query index
+    ovf_cap *= 8;
+    PH_HIP(hipMemcpyAsync(small + 3u * nq, redo.data(), redo.size() * 4u, hipMemcpyHostToDevice, st));
+    c.order = small + 3u * nq, c.nq = redo.size(), c.ovf_cap = ovf_cap;
+  }
+  PH_TRY(ph_take_launch(ids, d, ef, kk, nq, ids64, dk, st));  // u32 -> u64 ids, 0xFFFFFFFF -> PHNSW_EMPTY
+  PH_HIP(hipMemcpyAsync(out_ids, ids64, (size_t)nq * kk * 8u, hipMemcpyDeviceToHost, st));
+  PH_HIP(hipMemcpyAsync(out_d, dk, (size_t)nq * kk * 4u, hipMemcpyDeviceToHost, st));
+  PH_HIP(hipStreamSynchronize(st));
+  for (uint64_t i = 0; i < nq; i++) out_len[i] = std::min<uint32_t>(h_out[i], kk);
+  if (out_stats)
+    for (uint64_t i = 0; i < 2u * nq; i++) out_stats[i] = h_out[2u * nq + i];
   return 0;
 } catch (...) { return ph_caught(); }

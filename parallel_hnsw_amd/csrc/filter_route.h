@@ -27,11 +27,26 @@
 // batches of 10 000 queries; other store kinds and shapes are unmeasured)
 #define PH_AUTO_SCAN_BELOW_SHARED 13000u     // one bitmap for the batch
 #define PH_AUTO_SCAN_BELOW_PER_QUERY 10000u  // a bitmap per query
+// a label per query (phnsw_search_labeled_auto): the measured crossover of phnsw_search_exact_labeled and the label walk
+// (profiles/labeled_walk/README.md, "Crossover": at 20 000 rows per label the scan took 17.8 ms against the walk's 22.0,
+// at 25 000 rows 22.0 against 21.5 -- 1M x 768 f32 rows, ef 256 / probe_depth 8, k = 10, 10 000 queries; other shapes
+// are unmeasured)
+#define PH_AUTO_SCAN_BELOW_LABELED 20000u
 
 // the threshold a call runs with.  UINT64_MAX stays what it is: no count exceeds it, every query is scanned
 PH_ROUTE_HD static inline uint64_t ph_auto_scan_below(uint64_t scan_below, bool per_query) {
   if (scan_below != 0u) return scan_below;
   return per_query ? PH_AUTO_SCAN_BELOW_PER_QUERY : PH_AUTO_SCAN_BELOW_SHARED;
+}
+// ... of a call by label
+PH_ROUTE_HD static inline uint64_t ph_auto_scan_below_labeled(uint64_t scan_below) {
+  return scan_below != 0u ? scan_below : PH_AUTO_SCAN_BELOW_LABELED;
+}
+// e of ph_auto_full_len for a call by label: exclude[q] is a candidate iff it is listed under want[q].  label_of [n]
+// holds none_label for a vector that is not listed, and a query that wants none_label has no candidates
+PH_ROUTE_HD static inline bool ph_auto_label_candidate(const uint32_t *label_of, uint32_t n, uint32_t want, uint32_t v,
+                                                       uint32_t none_label) {
+  return v < n && want != none_label && label_of[v] == want;
 }
 
 // the route of a query with c candidates.  c and n_nodes are 32-bit counts, ef and k at most 1024: the two products

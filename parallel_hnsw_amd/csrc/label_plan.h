@@ -42,6 +42,10 @@ PH_EXACT_HD static inline uint32_t ph_label_slot(const uint32_t *values, uint64_
   return i < nlabels && values[i] == want ? (uint32_t)i : PH_LABEL_SLOT_NONE;
 }
 
+// the query a lookup position stands for: the position itself, or -- the subset form of a call -- the entry of the
+// caller's list; the sort then carries it and every later kernel addresses by order[pos]
+PH_EXACT_HD static inline uint32_t ph_label_seed(const uint32_t *list, uint32_t p) { return list ? list[p] : p; }
+
 // LDS of the per-query scan besides a PQ store's table: two key lists of k entries and 64 sorted survivor keys
 PH_EXACT_HD static inline uint64_t ph_label_scan_lds(uint64_t k) { return 2u * k * 8u + 64u * 8u; }
 // LDS one query of a tile takes: its row of ld f32 values, the scan's lists, 64 collected distances, four state words

@@ -219,9 +219,12 @@ struct PhRowHint {
 };
 
 // the allow-list of a filtered search as ph_search_device takes it (device words; PhSearchArgs::filter*)
+// ... or its label form: label_of != nullptr, the column [n] of a phnsw_labels handle (PHNSW_LABEL_NONE where a vector
+// is not listed) and want [nq], the label each query wants; words is then unused, flags mean the same
 struct PhFilter {
   const uint32_t *words;
   uint32_t stride, flags;
+  const uint32_t *label_of, *want;
 };
 
 // per-slice results of an exact scan that was cut into slices (filter_exact.hip): [nq][slices][k] keys from
@@ -361,6 +364,10 @@ struct PhSearchArgs {
   uint32_t tiny_rows, tiny_row_first;
   const uint32_t *tiny_row_map;
   uint32_t tiny_off[PH_TINY_MAX_LAYERS];
+  // the filter by row label (search_labeled.hip): label_of [n], the label of every listed vector and PHNSW_LABEL_NONE
+  // elsewhere; label_want [nq], what each query wants.  nullptr = not a label launch.  filter_flags as for the bitmap.
+  // (At the end: the argument offsets of every other kernel stay what they were.)
+  const uint32_t *label_of, *label_want;
 };
 
 uint32_t ph_default_ovf_cap(uint32_t ef);
@@ -391,7 +398,7 @@ struct PhSearchCall {
   uint64_t nq;
   const phnsw_search_params *sp;
   uint32_t upto;    // layers searched, 0 = all
-  PhFilter filter;  // words == nullptr: none
+  PhFilter filter;  // words == nullptr and label_of == nullptr: none
   uint32_t *out_ids;  // [nq][out_stride ? out_stride : number_of_candidates]
   float *out_d;
   uint32_t *out_len, *status;  // [nq]
@@ -461,6 +468,9 @@ struct PhAutoCall {
   uint64_t nq;
   const phnsw_search_params *sp;
   PhFilter filter;  // words == nullptr: every vector of the index
+  // the label form (phnsw_search_labeled_auto): candidates = the listed vectors of want[q]; filter is then unused
+  const phnsw_labels *labels;
+  const uint32_t *want;  // [nq]
   uint32_t k;
   uint64_t scan_below;  // 0 = the library default, UINT64_MAX = always scan (filter_route.h)
   uint32_t *out_ids;    // [nq][k]
@@ -470,6 +480,31 @@ struct PhAutoCall {
   hipStream_t stream;
 };
 int ph_auto_device(const phnsw_index *ix, const PhAutoCall &c);
+// The request of one exact top-k scan over posting lists (ph_labeled_device, filter_labeled.hip).  Device pointers of
+// the caller, enqueued on `stream`; rows of k entries, PH_EMPTY32 / PH_FMAX padded.
+struct PhLabeledCall {
+  const float *queries;
+  uint32_t ldq;
+  const uint32_t *qids, *exclude, *want;
+  uint64_t nq;
+  uint32_t k;
+  uint32_t *out_ids;
+  float *out_d;
+  uint32_t *out_len, *status;
+  hipStream_t stream;
+  // nullable: the subset form, as PhExactCall::list -- the scan covers queries list[0 .. nq) only (device words); nq is
+  // the list's length; queries, qids, exclude, want and every output stay addressed by the query index the list holds
+  const uint32_t *list;
+};
+int ph_labeled_device(const phnsw_index *ix, const phnsw_labels *lb, const PhLabeledCall &c);
+// a null handle, one made for another index or before the index changed: PHNSW_E_INVALID ("the labels are stale")
+int ph_labels_fresh(const phnsw_index *ix, const phnsw_labels *lb, const char *call);
+// the index, k, handle and store checks of phnsw_search_exact_labeled, in its order
+int ph_labeled_check(const phnsw_index *ix, const phnsw_labels *lb, uint64_t k, const char *call);
+// label_of [n] of a handle: the label of every listed vector, PHNSW_LABEL_NONE elsewhere (device words)
+const uint32_t *ph_labels_column(const phnsw_labels *lb);
+// out_count_dev[q] = the length of the list of want_dev[q] (phnsw_labels_count_device without its checks)
+int ph_labels_count(const phnsw_labels *lb, const uint32_t *want_dev, uint64_t nq, uint32_t *out_count_dev, hipStream_t stream);
 void ph_auto_free(phnsw_index *ix);
 void ph_dense_free(phnsw_index *ix);  // filter_dense.hip
 // the checks the table calls make before they look at another argument: index, k, store kind and row length

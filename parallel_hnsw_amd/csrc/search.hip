@@ -177,12 +177,14 @@ static PhKernelChoice pick_unfiltered_kernel(const phnsw_store *s, uint32_t ef_m
   return k;
 }
 
-// filt: the launch carries an allow-list and runs the FILT twin of the kernel it would run without one (same family,
-// same queues, same LDS; search_filtered.hip).  Never with instr, which ph_search_launch refuses.
+// mode: the launch carries an allow-list or a label column and runs that twin of the kernel it would run without one
+// (same family, same queues, same LDS; search_filtered.hip, search_labeled.hip).  Never with instr, which
+// ph_search_launch refuses.
 static PhKernelChoice pick_search_kernel(const phnsw_store *s, uint32_t ef_max, uint32_t nv4, bool grows, uint64_t nq,
-                                         bool instr, bool filt = false) {
+                                         bool instr, int mode = PH_FM_NONE) {
   PhKernelChoice k = pick_unfiltered_kernel(s, ef_max, nv4, grows, nq, instr);
-  if (filt && k.fn) k.fn = ph_pick_filtered_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
+  if (mode == PH_FM_BITMAP && k.fn) k.fn = ph_pick_filtered_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
+  if (mode == PH_FM_LABEL && k.fn) k.fn = ph_pick_labeled_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
   return k;
 }
 
@@ -320,7 +322,9 @@ static hipError_t grow_buf(T **p, size_t *have, size_t need) {
 // the dense-only launch of a descent (PhSearchArgs::dense_only): its own kernel, grid and spill lists
 static int search_launch_dense(PhWorkspace &ws, PhSearchArgs &a, hipStream_t stream) {
   const int capc = pick_capc_dense(a.ef);
-  ph_search_fn fn = a.filter ? ph_pick_filtered_dense(capc) : pick_kernel_dense<false>(capc);
+  const int mode = ph_filter_mode(a);
+  ph_search_fn fn = mode == PH_FM_LABEL ? ph_pick_labeled_dense(capc)
+                                        : (mode == PH_FM_BITMAP ? ph_pick_filtered_dense(capc) : pick_kernel_dense<PH_FM_NONE>(capc));
   if (!fn) {
     ph_set_error("unsupported search shape: ef=%u", a.ef);
     return PHNSW_E_UNSUPPORTED;
@@ -399,11 +403,12 @@ int ph_search_launch(const phnsw_index *ix, PhWorkspace &ws, PhSearchArgs &a, hi
     ph_set_error("search_instrumented: f32 stores only");
     return PHNSW_E_UNSUPPORTED;
   }
-  if (a.filter && (a.knn_mode || a.out_index)) {  // only the plain searches have filtered kernels
+  const int mode = ph_filter_mode(a);
+  if (mode != PH_FM_NONE && (a.knn_mode || a.out_index)) {  // only the plain searches have filtered kernels
     ph_set_error("knn / threshold_nn / search_instrumented take no filter");
     return PHNSW_E_UNSUPPORTED;
   }
-  PhKernelChoice k = pick_search_kernel(st, ef_max, a.dist.nv4, a.knn_mode == 2, a.nq, a.out_index != nullptr, a.filter != nullptr);
+  PhKernelChoice k = pick_search_kernel(st, ef_max, a.dist.nv4, a.knn_mode == 2, a.nq, a.out_index != nullptr, mode);
   a.pq_tables = ws.pq_tables;
   a.pq_table_bytes = (uint32_t)ph_pq_lds_bytes(st);
   // one wave per SIMD leaves each wave a quarter of the CU's LDS: room for the table row of a far larger table layer

@@ -1,6 +1,7 @@
 // The search kernels (search.hip has the long form) and the functions that name their instances, for the two
-// translation units that instantiate them: search.hip the kernels as they always were, search_filtered.hip their FILT
-// twins, the kernels of a search restricted to an allow-list of VectorIds.  Two units so that they compile side by side.
+// translation units that instantiate them: search.hip the kernels as they always were, search_filtered.hip their bitmap
+// twins, the kernels of a search restricted to an allow-list of VectorIds, search_labeled.hip their label twins, the same
+// restriction read from a label column.  Three units so that they compile side by side.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -82,10 +83,20 @@ __device__ __forceinline__ bool vis_insert(uint32_t *H, uint32_t slots, uint32_t
   return fresh;
 }
 
-// FILT: the launch carries an allow-list (a.filter), tested where closest_vectors applies `include`.  A flag of the
-// body and not a run-time test of the pointer: the test alone cost 19 of the 88 kernels scratch (profiles/filter), so
-// the filtered instances exist beside the others and are picked only when a filter is given.
-template <int CAPC, class Dist, bool INSTR = false, bool BIG = false, bool FILT = false>
+// FILT: the filter mode of the launch, tested where closest_vectors applies `include`.
+//   PH_FM_NONE    no filter
+//   PH_FM_BITMAP  an allow-list (a.filter): bit v of the query's bitmap
+//   PH_FM_LABEL   a label column (a.label_of) and one wanted label per query (a.label_want): VectorId v passes iff
+//                 want != PHNSW_LABEL_NONE && label_of[v] == want -- one 4-byte load where the bitmap mode loads a word.
+//                 Written per lane as label_of[v] == want && label_of[v] != NONE: the same predicate, and the scalar
+//                 test of `want` cost seven twins a wave per SIMD (profiles/labeled_walk)
+// A mode of the body and not a run-time test of the pointers: the test alone cost 19 of the 88 kernels scratch
+// (profiles/filter), so the filtered instances exist beside the others and are picked only when a filter is given.
+enum : int { PH_FM_NONE = 0, PH_FM_BITMAP = 1, PH_FM_LABEL = 2 };
+// the mode a launch's arguments ask for
+static inline int ph_filter_mode(const PhSearchArgs &a) { return a.label_of ? PH_FM_LABEL : (a.filter ? PH_FM_BITMAP : PH_FM_NONE); }
+
+template <int CAPC, class Dist, bool INSTR = false, bool BIG = false, int FILT = PH_FM_NONE>
 __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
   extern __shared__ uint32_t smem[];
   constexpr int CAP = CAPC * 64;
@@ -182,7 +193,9 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
       dist.prepare_stored(a.dist, qvec, dist_lds, lane);
     const uint32_t excl = a.exclude ? a.exclude[q] : PH_EMPTY32;
     // the allow-list of this query (wave-uniform): `include` of lib.rs:250-277
-    const uint32_t *const allow = FILT ? a.filter + (uint64_t)q * a.filter_stride : nullptr;
+    const uint32_t *const allow = FILT == PH_FM_BITMAP ? a.filter + (uint64_t)q * a.filter_stride : nullptr;
+    // ... or the label it wants (wave-uniform); NONE matches nothing, not even the unlisted vectors that carry it
+    const uint32_t want = FILT == PH_FM_LABEL ? rfl32(a.label_want[q]) : PHNSW_LABEL_NONE;
     uint32_t n_dist = 0, n_hops = 0, err = ST_OK;
     uint32_t index_distance = 0xFFFFFFFFu;  // usize::MAX until a layer has run  search.rs:112
     uint32_t n_tab = 0;  // of n_dist: evaluations served by the dense tables (measurement: the rest are gathered rows)
@@ -739,8 +752,13 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
         bd[c] = has ? Qd[i] : PH_FMAX;
         bv[c] = has ? (identity ? nid : L.nodes[nid]) : PH_EMPTY32;
         bool keep = has && bv[c] != excl;
-        if constexpr (FILT)
+        if constexpr (FILT == PH_FM_BITMAP)
           if (keep) keep = (allow[bv[c] >> 5] >> (bv[c] & 31)) & 1u;  // (only lanes holding an id read a word)
+        if constexpr (FILT == PH_FM_LABEL)
+          if (keep) {  // (... or a label)
+            const uint32_t lbl = a.label_of[bv[c]];
+            keep = lbl == want && lbl != PHNSW_LABEL_NONE;
+          }
         uint64_t km = __ballot(keep);
         uint32_t at = kept + __popcll(km & lt);
         bpos[c] = (keep && at < candidate_count) ? at : PH_EMPTY32;
@@ -836,7 +854,14 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
         sv[c] = has ? Cid[i] : 0u;
         sd[c] = has ? Cd[i] : PH_FMAX;
         bool keep = false;
-        if (has) keep = (allow[sv[c] >> 5] >> (sv[c] & 31)) & 1u;
+        if constexpr (FILT == PH_FM_LABEL) {
+          if (has) {
+            const uint32_t lbl = a.label_of[sv[c]];
+            keep = lbl == want && lbl != PHNSW_LABEL_NONE;
+          }
+        } else {
+          if (has) keep = (allow[sv[c] >> 5] >> (sv[c] & 31)) & 1u;
+        }
         const uint64_t km = __ballot(keep);
         spos[c] = keep ? kept + __popcll(km & lt) : PH_EMPTY32;
         kept += __popcll(km);
@@ -914,7 +939,7 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
   }
 }
 
-template <int CAPC, class Dist, bool FILT = false>
+template <int CAPC, class Dist, int FILT = PH_FM_NONE>
 __global__ __launch_bounds__(64) void ph_search_kernel(PhSearchArgs a) {
   ph_search_body<CAPC, Dist, false, false, FILT>(a);
 }
@@ -922,7 +947,7 @@ __global__ __launch_bounds__(64) void ph_search_kernel(PhSearchArgs a) {
 // The dense top layers in a launch of their own: no distance policy state, so half the registers and (queues of
 // ef <= 256 in 256 slots) half the LDS of the full kernel -- twice the resident waves on a walk that is pure
 // latency and instruction issue.  The running candidates are parked in the output rows for the follow-up launch.
-template <int CAPC, bool FILT = false>
+template <int CAPC, int FILT = PH_FM_NONE>
 __global__ __launch_bounds__(64) void ph_search_kernel_dense(PhSearchArgs a) {
   ph_search_body<CAPC, DistNone, false, false, FILT>(a);
 }
@@ -930,7 +955,7 @@ __global__ __launch_bounds__(64) void ph_search_kernel_dense(PhSearchArgs a) {
 // Small batches leave most of the chip idle and finish with their slowest query: their kernels keep up to 24
 // rows in flight per wave (one load round per hop instead of up to twelve) at one wave per SIMD.  Same
 // arithmetic per row, so the same results.
-template <int CAPC, int NV, bool FILT = false>
+template <int CAPC, int NV, int FILT = PH_FM_NONE>
 __global__ __launch_bounds__(64, 1) void ph_search_kernel_lat(PhSearchArgs a) {
   ph_search_body<CAPC, DistF32<NV, 0>, false, false, FILT>(a);
 }
@@ -948,7 +973,7 @@ __global__ __launch_bounds__(64) void ph_search_kernel_big(PhSearchArgs a) {
 }
 
 // the register-table policy keeps a whole lookup table in VGPRs: two waves per SIMD is its register budget
-template <int CAPC, int M, bool FILT = false>
+template <int CAPC, int M, int FILT = PH_FM_NONE>
 __global__ __launch_bounds__(64, 2) void ph_search_kernel_pqr(PhSearchArgs a) {
   ph_search_body<CAPC, DistPQR<M>, false, false, FILT>(a);
 }
@@ -970,7 +995,7 @@ enum PhKernelFamily {
 };
 
 // the register-table PQ policy (pick_pqr): 32 / 64 / 96 / 128 sub-spaces, queues of up to 512 entries
-template <bool FILT>
+template <int FILT>
 static ph_search_fn pick_kernel_pqr(int capc, int m) {
 #define PH_KR(C, M) \
   if (capc == C && m == M) return (ph_search_fn)ph_search_kernel_pqr<C, M, FILT>;
@@ -981,7 +1006,7 @@ static ph_search_fn pick_kernel_pqr(int capc, int m) {
 }
 
 // shared-codebook PQ stores (u16 codes): the query layout is DistF32's, the candidate rows come through the codes
-template <bool FILT>
+template <int FILT>
 static ph_search_fn pick_kernel_pqs(int capc, int nv) {
 #define PH_KS(C, N) \
   if (capc == C && nv == N) return (ph_search_fn)ph_search_kernel<C, DistPQS<N>, FILT>;
@@ -990,7 +1015,7 @@ static ph_search_fn pick_kernel_pqs(int capc, int nv) {
   return nullptr;
 }
 
-template <bool FILT>
+template <int FILT>
 static ph_search_fn pick_kernel_dense(int capc) {
   switch (capc) {
     case 2: return (ph_search_fn)ph_search_kernel_dense<2, FILT>;
@@ -1001,7 +1026,7 @@ static ph_search_fn pick_kernel_dense(int capc) {
   return nullptr;
 }
 
-template <bool FILT>
+template <int FILT>
 static ph_search_fn pick_kernel_lat(int capc, int nv) {
 #define PH_KL(C, N) \
   if (capc == C && nv == N) return (ph_search_fn)ph_search_kernel_lat<C, N, FILT>;
@@ -1014,7 +1039,7 @@ static ph_search_fn pick_kernel_lat(int capc, int nv) {
 // queues, same LDS visited table, same rows in flight (DistI8Q too: 16 rows in flight would cost its headline kernel a
 // wave per SIMD, 144 VGPRs against 112, profiles/i8q).  (There are no latency (U == 0), instrumented or big-queue kernels over
 // converted rows: batches of any size run these, and the calls behind the others refuse a converted store.)
-template <template <int, int> class D, bool FILT>
+template <template <int, int> class D, int FILT>
 static ph_search_fn pick_kernel_rows(int capc, int nv) {
 #define PH_K(C, N) \
   if (capc == C && nv == N) return (ph_search_fn)ph_search_kernel<C, D<N, 4>, FILT>;
@@ -1030,7 +1055,7 @@ static ph_search_fn pick_kernel_rows(int capc, int nv) {
 }
 
 // the per-sub-space PQ policy with its table in LDS or in global memory (PHNSW_PQ_TABLE)
-template <bool FILT>
+template <int FILT>
 static ph_search_fn pick_kernel_pqt(int capc, bool global) {
 #define PH_KQ(C) \
   if (capc == C) return global ? (ph_search_fn)ph_search_kernel<C, DistPQG, FILT> : (ph_search_fn)ph_search_kernel<C, DistPQ, FILT>;
@@ -1039,8 +1064,8 @@ static ph_search_fn pick_kernel_pqt(int capc, bool global) {
   return nullptr;
 }
 
-// the kernel of a plain search by family and shape (nullptr: none); FILT: its twin with the allow-list test
-template <bool FILT>
+// the kernel of a plain search by family and shape (nullptr: none); FILT: its twin with the test of that filter mode
+template <int FILT>
 static ph_search_fn pick_kernel_family(int family, int capc, int nv, int pqr_m, bool pq_global) {
   switch (family) {
     case PH_KF_ROWS_F32: return pick_kernel_rows<DistF32, FILT>(capc, nv);
@@ -1055,6 +1080,9 @@ static ph_search_fn pick_kernel_family(int family, int capc, int nv, int pqr_m, 
   }
 }
 
-// the FILT instances live in search_filtered.hip; the launchers of search.hip get them here
+// the bitmap twins live in search_filtered.hip, the label twins in search_labeled.hip; the launchers of search.hip get
+// them here
 ph_search_fn ph_pick_filtered_kernel(int family, int capc, int nv, int pqr_m, bool pq_global);
 ph_search_fn ph_pick_filtered_dense(int capc);
+ph_search_fn ph_pick_labeled_kernel(int family, int capc, int nv, int pqr_m, bool pq_global);
+ph_search_fn ph_pick_labeled_dense(int capc);

@@ -130,7 +130,9 @@ class Labels:
     """phnsw_labels: one label per vector of `hnsw`'s store, turned once into posting lists on the device (the ascending
     VectorIds of every label).  labels: an integer array [n] within u32; -1 or LABEL_NONE = the vector is not listed.  A
     vector is listed iff the index's bottom layer holds it.  The handle is a snapshot: after store.append, or with
-    another index, search_exact_labeled refuses it as stale -- make a new one.  Keep `hnsw` alive while it is used."""
+    another index, search_exact_labeled refuses it as stale -- make a new one.  Keep `hnsw` alive while it is used.
+    The handle also keeps the label column itself on the device (4 bytes per vector beside the lists): the graph walk by
+    label, search_batch_labeled, and the routed search_labeled read it."""
 
     def __init__(self, hnsw, labels):
         self._h = None
@@ -984,6 +986,104 @@ class Hnsw:
         check(lib().phnsw_search_exact_labeled_device(
             self._h, labels._h, C.c_void_p(queries or None), ldq, C.c_void_p(qids or None), nq, C.c_void_p(exclude or None),
             C.c_void_p(want or None), int(k), C.c_void_p(out_ids), C.c_void_p(out_d), C.c_void_p(out_len), C.c_void_p(status),
+            C.c_void_p(stream or None)))
+
+    def _labeled_args(self, call, queries, qids, labels, want):
+        """the checks the calls by label make before they reach the library: a Labels, exactly one of queries / qids,
+        want as pack_labels takes it.  Returns (q, qi, nq, want u32 [nq])"""
+        if not isinstance(labels, Labels):
+            raise TypeError("%s: labels must be a Labels made for this index" % call)
+        if (queries is None) == (qids is None):
+            raise ValueError("%s: pass queries or qids (exactly one)" % call)
+        q = qi = None
+        if queries is not None:
+            q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+            if q.shape[1] != self.store.dim:
+                raise ValueError("%s: queries of shape [nq, %d], got %r" % (call, self.store.dim, q.shape))
+            nq = q.shape[0]
+        else:
+            qi = np.ascontiguousarray(qids, dtype=np.uint64)
+            nq = len(qi)
+        return q, qi, nq, pack_labels(want, nq, "want")
+
+    def search_batch_labeled(self, queries=None, qids=None, sp=None, labels=None, want=None, strict=False, exclude=None,
+                             upto=0, stats=False, k=None):
+        """search_batch_filtered by row label (phnsw_search_batch_labeled): the graph walk of query i restricted to the
+        vectors `labels` lists under want[i] -- the rows, lengths and stats of search_batch_filtered(allow=(the vectors
+        listed under want[i])), bit for bit, without a bitmap per query: the kernels test the handle's label column.
+        labels: a Labels made for this index; want: integers [nq] within u32, -1 or LABEL_NONE (or a label nobody carries)
+        = the row an all-zero bitmap gives.  A post-filter like search_batch_filtered: about number_of_candidates * list
+        length / vector_count results come back (search_labeled completes rows).  The entry vector may be returned
+        although its label differs; strict=True removes it.  set_filter's default is not consulted.  Measured on 1M x 768
+        f32 rows, ef 256 / probe_depth 8, 10 000 queries, 2 to 1000 labels: the device form took 0.990 to 0.997 of the
+        bitmap call's kernel time (run-to-run spread of either: under 1 %) and 0.36 to 0.54 of it with the bitmaps' upload
+        counted (profiles/labeled_walk/README.md); the host forms were not timed.
+        Returns (ids[nq, k or ef] u64, d f32, len[nq]) and the stats with stats=True"""
+        q, qi, nq, w32 = self._labeled_args("search_batch_labeled", queries, qids, labels, want)
+        sp = sp or SearchParameters()
+        ef = sp.number_of_candidates
+        w = ef if k is None else int(k)
+        if w < 0:
+            raise ValueError("search_batch_labeled: k must not be negative")
+        ids = np.empty((nq, w), dtype=np.uint64)
+        d = np.empty((nq, w), dtype=np.float32)
+        ln = np.zeros(nq, dtype=np.uint64)
+        st = np.zeros((nq, 2), dtype=np.uint64) if stats else None
+        ex = None if exclude is None else np.ascontiguousarray(exclude, dtype=np.uint64)
+        check(lib().phnsw_search_batch_labeled(self._h, labels._h, _p(q), _p(qi), nq, C.byref(sp), upto, _p(ex), _p(w32),
+                                               FILTER_STRICT if strict else 0, 0 if k is None else w, _p(ids), _p(d), _p(ln),
+                                               _p(st)))
+        return (ids, d, ln, st) if stats else (ids, d, ln)
+
+    def search_batch_labeled_device(self, labels, nq, sp, out_ids, out_d, out_len, status, queries=0, ldq=0, qids=0, exclude=0,
+                                    want=0, strict=False, out_stats=0, upto=0, stream=0):
+        """zero-copy form (phnsw_search_batch_labeled_device): search_batch_filtered_device with want = u32 labels [nq] (a
+        device pointer, alive until the work on `stream` is done) in place of the bitmaps.  Enqueued on `stream`; never
+        synchronises it"""
+        if not isinstance(labels, Labels):
+            raise TypeError("search_batch_labeled_device: labels must be a Labels made for this index")
+        check(lib().phnsw_search_batch_labeled_device(
+            self._h, labels._h, C.c_void_p(queries or None), ldq, C.c_void_p(qids or None), nq, C.byref(sp), upto,
+            C.c_void_p(exclude or None), C.c_void_p(want or None), FILTER_STRICT if strict else 0, C.c_void_p(out_ids),
+            C.c_void_p(out_d), C.c_void_p(out_len), C.c_void_p(out_stats or None), C.c_void_p(status),
+            C.c_void_p(stream or None)))
+
+    def search_labeled(self, queries=None, qids=None, sp=None, labels=None, want=None, exclude=None, k=10, scan_below=0,
+                       route=False):
+        """search_filtered by row label (phnsw_search_labeled_auto): per query the posting-list scan
+        (search_exact_labeled) where the list of want[i] is short (length <= scan_below, or length *
+        number_of_candidates < k * vector_count), the strict graph walk by label otherwise, and the scan again for every
+        query whose walk came back short.  Every row holds exactly min(k, list length - e) entries and only listed vectors
+        of want[i] (e = 1 iff exclude[i] is one of them): the rows of search_filtered with the equivalent per-query
+        bitmaps, bit for bit.  scan_below 0 = the library's threshold for labels, 20 000: the measured crossover of the two
+        calls on 1M x 768 f32 rows, ef 256, k = 10 (scan 17.8 ms against the walk's 22.0 at 20 000 rows per label, 22.0
+        against 21.5 at 25 000; profiles/labeled_walk/README.md), other shapes unmeasured; 2**64 - 1 = always scan.
+        1 <= k <= sp.number_of_candidates.
+        Returns (ids[nq, k] u64, d[nq, k] f32, len[nq]) and, with route=True, route[nq] u32: ROUTE_GRAPH, ROUTE_SCAN or
+        ROUTE_GRAPH_THEN_SCAN"""
+        q, qi, nq, w32 = self._labeled_args("search_labeled", queries, qids, labels, want)
+        sp = sp or SearchParameters()
+        w = max(int(k), 0)
+        ids = np.empty((nq, w), dtype=np.uint64)
+        d = np.empty((nq, w), dtype=np.float32)
+        ln = np.zeros(nq, dtype=np.uint64)
+        rt = np.zeros(nq, dtype=np.uint32) if route else None
+        ex = None if exclude is None else np.ascontiguousarray(exclude, dtype=np.uint64)
+        check(lib().phnsw_search_labeled_auto(self._h, labels._h, _p(q), _p(qi), nq, C.byref(sp), _p(ex), _p(w32), int(k),
+                                              int(scan_below), _p(ids), _p(d), _p(ln), _p(rt)))
+        return (ids, d, ln, rt) if route else (ids, d, ln)
+
+    def search_labeled_device(self, labels, nq, sp, k, out_ids, out_d, out_len, status, queries=0, ldq=0, qids=0, exclude=0,
+                              want=0, scan_below=0, out_route=0, stream=0):
+        """device form (phnsw_search_labeled_auto_device): device pointers as integers, u32 ids [nq, k] padded with
+        0xFFFFFFFF; want = u32 labels [nq]; out_route u32 [nq] or 0.  Like search_filtered_device it synchronises
+        `stream`, up to twice"""
+        if not isinstance(labels, Labels):
+            raise TypeError("search_labeled_device: labels must be a Labels made for this index")
+        check(lib().phnsw_search_labeled_auto_device(
+            self._h, labels._h, C.c_void_p(queries or None), ldq, C.c_void_p(qids or None), nq, C.byref(sp),
+            C.c_void_p(exclude or None), C.c_void_p(want or None), int(k), int(scan_below), C.c_void_p(out_ids),
+            C.c_void_p(out_d), C.c_void_p(out_len), C.c_void_p(out_route or None), C.c_void_p(status),
             C.c_void_p(stream or None)))
 
     def filter_count_device(self, nbitmaps, out_count, allow=0, allow_stride=0, stream=0):

@@ -649,6 +649,91 @@ impl GpuHnsw {
                                                      out_ids_dev, out_d_dev, out_len_dev, status_dev, stream));
     }
 
+    /// `search_many_filtered` by row label (`phnsw_search_batch_labeled`): the graph walk of query i restricted to the
+    /// vectors `labels` lists under `want[i]`, read from the handle's label column instead of a bitmap per query -- the
+    /// results `search_many_filtered` gives with the equivalent predicates, bit for bit.  A post-filter: about
+    /// number_of_candidates * list length / N results; `strict` also removes an entry vector whose label differs.
+    /// Panics unless `want` has one entry per query
+    pub fn search_many_labeled(&self, queries: &[Vec<f32>], sp: SearchParameters, labels: &GpuLabels, want: &[Option<u32>],
+                               strict: bool) -> Vec<Vec<(VectorId, f32)>> {
+        let nq = queries.len();
+        assert!(want.len() == nq, "search_many_labeled: one wanted label per query");
+        let ef = sp.number_of_candidates;
+        let psp = sp_c(sp);
+        let w: Vec<u32> = want.iter().map(|l| l.unwrap_or(sys::PHNSW_LABEL_NONE)).collect();
+        let mut q: Vec<f32> = Vec::with_capacity(nq * queries.first().map_or(0, |x| x.len()));
+        for x in queries {
+            q.extend_from_slice(x);
+        }
+        let (mut ids, mut d, mut len) = (vec![0u64; nq * ef], vec![0f32; nq * ef], vec![0u64; nq]);
+        check(unsafe {
+            sys::phnsw_search_batch_labeled(self.ix, labels.lb, q.as_ptr(), std::ptr::null(), nq as u64, &psp, 0, std::ptr::null(),
+                                            w.as_ptr(), if strict { 1 } else { 0 }, 0, ids.as_mut_ptr(), d.as_mut_ptr(),
+                                            len.as_mut_ptr(), std::ptr::null_mut())
+        });
+        (0..nq).map(|i| (0..len[i] as usize).map(|j| (VectorId(ids[i * ef + j] as usize), d[i * ef + j])).collect()).collect()
+    }
+
+    /// zero-copy form (`phnsw_search_batch_labeled_device`): rows of number_of_candidates u32 ids; enqueued on `stream`,
+    /// never synchronises it
+    ///
+    /// # Safety
+    /// the pointers must be valid device allocations of the sizes `phnsw.h` documents for the call
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn search_batch_labeled_device(&self, labels: &GpuLabels, queries_dev: *const f32, ldq: u32,
+                                              qids_dev: *const u32, nq: u64, sp: SearchParameters, upto_layers: u32,
+                                              exclude_dev: *const u32, want_dev: *const u32, flags: u32,
+                                              out_ids_dev: *mut u32, out_d_dev: *mut f32, out_len_dev: *mut u32,
+                                              out_stats_dev: *mut u32, status_dev: *mut u32, stream: *mut c_void) {
+        let psp = sp_c(sp);
+        check(sys::phnsw_search_batch_labeled_device(self.ix, labels.lb, queries_dev, ldq, qids_dev, nq, &psp, upto_layers,
+                                                     exclude_dev, want_dev, flags, out_ids_dev, out_d_dev, out_len_dev,
+                                                     out_stats_dev, status_dev, stream));
+    }
+
+    /// `search_many_filtered_auto` by row label (`phnsw_search_labeled_auto`): per query the posting-list scan or the
+    /// strict walk by label, the scan again for short rows; every result holds min(k, list length) entries, listed
+    /// vectors of `want[i]` only.  `scan_below` 0 = the library's threshold for labels (20 000, `phnsw.h`),
+    /// `u64::MAX` = always scan.  Returns the results and one route per query.  Panics unless
+    /// 1 <= k <= number_of_candidates and `want` has one entry per query
+    pub fn search_many_labeled_auto(&self, queries: &[Vec<f32>], sp: SearchParameters, k: usize, scan_below: u64,
+                                    labels: &GpuLabels, want: &[Option<u32>]) -> (Vec<Vec<(VectorId, f32)>>, Vec<u32>) {
+        assert!(k >= 1 && k <= sp.number_of_candidates, "search_many_labeled_auto: k must be 1..number_of_candidates");
+        let nq = queries.len();
+        assert!(want.len() == nq, "search_many_labeled_auto: one wanted label per query");
+        let psp = sp_c(sp);
+        let w: Vec<u32> = want.iter().map(|l| l.unwrap_or(sys::PHNSW_LABEL_NONE)).collect();
+        let mut q: Vec<f32> = Vec::with_capacity(nq * queries.first().map_or(0, |x| x.len()));
+        for x in queries {
+            q.extend_from_slice(x);
+        }
+        let (mut ids, mut d, mut len) = (vec![0u64; nq * k], vec![0f32; nq * k], vec![0u64; nq]);
+        let mut route = vec![0u32; nq];
+        check(unsafe {
+            sys::phnsw_search_labeled_auto(self.ix, labels.lb, q.as_ptr(), std::ptr::null(), nq as u64, &psp, std::ptr::null(),
+                                           w.as_ptr(), k as u64, scan_below, ids.as_mut_ptr(), d.as_mut_ptr(), len.as_mut_ptr(),
+                                           route.as_mut_ptr())
+        });
+        let rows = (0..nq).map(|i| (0..len[i] as usize).map(|j| (VectorId(ids[i * k + j] as usize), d[i * k + j])).collect()).collect();
+        (rows, route)
+    }
+
+    /// device form (`phnsw_search_labeled_auto_device`): u32 ids `[nq][k]`; synchronises `stream` up to twice
+    ///
+    /// # Safety
+    /// the pointers must be valid device allocations of the sizes `phnsw.h` documents for the call
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn search_labeled_auto_device(&self, labels: &GpuLabels, queries_dev: *const f32, ldq: u32,
+                                             qids_dev: *const u32, nq: u64, sp: SearchParameters, exclude_dev: *const u32,
+                                             want_dev: *const u32, k: u64, scan_below: u64, out_ids_dev: *mut u32,
+                                             out_d_dev: *mut f32, out_len_dev: *mut u32, out_route_dev: *mut u32,
+                                             status_dev: *mut u32, stream: *mut c_void) {
+        let psp = sp_c(sp);
+        check(sys::phnsw_search_labeled_auto_device(self.ix, labels.lb, queries_dev, ldq, qids_dev, nq, &psp, exclude_dev,
+                                                    want_dev, k, scan_below, out_ids_dev, out_d_dev, out_len_dev, out_route_dev,
+                                                    status_dev, stream));
+    }
+
     /// 0, or the code `search_many_exact_shared` would be refused with (`phnsw_exact_shared_supported`)
     pub fn exact_shared_supported(&self, k: usize) -> i32 {
         unsafe { sys::phnsw_exact_shared_supported(self.ix, k as u64) }

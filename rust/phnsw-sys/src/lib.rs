@@ -290,6 +290,26 @@ extern "C" {
                                              ldq: u32, qids_dev: *const u32, nq: u64, exclude_dev: *const u32,
                                              want_dev: *const u32, k: u64, out_ids_dev: *mut u32, out_d_dev: *mut c_float,
                                              out_len_dev: *mut u32, status_dev: *mut u32, stream: *mut c_void) -> c_int;
+    // the graph walk by row label: the kernels test the handle's label column, no bitmap per query
+    pub fn phnsw_search_batch_labeled(ix: *const phnsw_index, lb: *const phnsw_labels, queries: *const c_float,
+                                      qids: *const u64, nq: u64, sp: *const phnsw_search_params, upto_layers: u32,
+                                      exclude: *const u64, want: *const u32, flags: u32, k: u64, out_ids: *mut u64,
+                                      out_d: *mut c_float, out_len: *mut u64, out_stats: *mut u64) -> c_int;
+    pub fn phnsw_search_batch_labeled_device(ix: *const phnsw_index, lb: *const phnsw_labels, queries_dev: *const c_float,
+                                             ldq: u32, qids_dev: *const u32, nq: u64, sp: *const phnsw_search_params,
+                                             upto_layers: u32, exclude_dev: *const u32, want_dev: *const u32, flags: u32,
+                                             out_ids_dev: *mut u32, out_d_dev: *mut c_float, out_len_dev: *mut u32,
+                                             out_stats_dev: *mut u32, status_dev: *mut u32, stream: *mut c_void) -> c_int;
+    // ... and the routed call by label: posting-list scan or label walk per query, the scan again for short rows
+    pub fn phnsw_search_labeled_auto(ix: *const phnsw_index, lb: *const phnsw_labels, queries: *const c_float,
+                                     qids: *const u64, nq: u64, sp: *const phnsw_search_params, exclude: *const u64,
+                                     want: *const u32, k: u64, scan_below: u64, out_ids: *mut u64, out_d: *mut c_float,
+                                     out_len: *mut u64, out_route: *mut u32) -> c_int;
+    pub fn phnsw_search_labeled_auto_device(ix: *const phnsw_index, lb: *const phnsw_labels, queries_dev: *const c_float,
+                                            ldq: u32, qids_dev: *const u32, nq: u64, sp: *const phnsw_search_params,
+                                            exclude_dev: *const u32, want_dev: *const u32, k: u64, scan_below: u64,
+                                            out_ids_dev: *mut u32, out_d_dev: *mut c_float, out_len_dev: *mut u32,
+                                            out_route_dev: *mut u32, status_dev: *mut u32, stream: *mut c_void) -> c_int;
     pub fn phnsw_filter_count_device(ix: *const phnsw_index, filter_dev: *const u32, filter_stride_words: u32,
                                      nbitmaps: u64, out_count_dev: *mut u32, stream: *mut c_void) -> c_int;
     // per query the scan or the graph walk, the scan again for short rows: min(k, candidates) entries, candidates only
