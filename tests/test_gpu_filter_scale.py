@@ -82,7 +82,8 @@ def full_store(lattice, dim):
 @functools.lru_cache(maxsize=None)
 def store_of(kind, dim):
     full = full_store(kind == "i8q", dim)
-    return {"f32": lambda f: f, "i8q": ph.I8QStore.from_full, "pq": lambda f: ph.PqStore(f, PQ_M)}[kind](full)
+    return {"f32": lambda f: f, "f16": ph.F16Store.from_full, "i8": ph.I8Store.from_full, "i8q": ph.I8QStore.from_full,
+            "pq": lambda f: ph.PqStore(f, PQ_M)}[kind](full)
 
 
 def stored_ids(n, dups, count):
