@@ -563,6 +563,76 @@ int phnsw_search_labeled_auto_device(const phnsw_index *ix, const phnsw_labels *
                                      const uint32_t *exclude_dev, const uint32_t *want_dev, uint64_t k, uint64_t scan_below,
                                      uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
                                      uint32_t *out_route_dev, uint32_t *status_dev, void *stream);
+/* ---- the COLLECTING search: the graph walk that remembers the best ALLOWED rows it evaluates.  The filtered walks above
+ * are post-filters: they keep the best number_of_candidates rows, allowed or not, and filter that queue when the layer
+ * ends, so a filter of density p leaves about p * number_of_candidates results although the walk evaluated several
+ * times as many rows.  A collecting search of query q with result size k (1 <= k <= 64) IS the plain search
+ * phnsw_search_batch with the same sp, upto_layers and exclude -- split descents included --, and only the walk of the
+ * LAST LAYER IT RUNS is extended:
+ *  - beside the layer's queue there is a second queue `kept`, a PriorityQueue of capacity k ordered by (distance, id)
+ *    like every queue here;
+ *  - a node with vector v QUALIFIES iff v passes the filter (bit v of the query's bitmap; or
+ *    label_of[v] == want[q] && want[q] != PHNSW_LABEL_NONE), v != exclude[q], and its distance is <= f32::MAX (the walk
+ *    never returns +inf, and neither does this);
+ *  - `kept` is seeded with the qualifying entries of the queue the layer starts with (the running candidates).  There is
+ *    no entry-vector quirk: a row that does not qualify is never returned;
+ *  - at every hop the qualifying members of that hop's evaluated batch are merged into `kept` -- the batch the layer's
+ *    queue is merged with, including the members that are too far away for that queue;
+ *  - without flags NOTHING ELSE changes: the traversal, the visited sets, the per-query evaluation and hop counters are
+ *    the plain search's, bit for bit, so out_stats equals phnsw_search_batch's for any filter;
+ *  - with PHNSW_COLLECT_EXTEND a hop additionally "did something" when it changed `kept`.  This is the only change to the
+ *    walk: probe_depth then counts the hops that improve NEITHER queue, so hops that find better allowed rows no longer
+ *    use up the budget.  probe_depth idle hops IN ALL (the budget is never refilled) still end the walk, however many
+ *    allowed rows lie further out and however few `kept` holds: the flag does not make the walk exhaust its
+ *    frontier, and a row shorter than k does not mean that fewer than k allowed rows are reachable;
+ *  - upper layers run exactly as in the plain search, unfiltered apart from exclude: a selective filter cannot starve
+ *    the descent.
+ * Result row: the entries of `kept`, ascending by (distance, id); out_len[q] = its length; rows of k entries padded with
+ * PHNSW_EMPTY / f32::MAX; the distance has the bits the walk computed, which are phnsw_distance_batch's for that store
+ * (a -0.0 comes back as +0.0, as from the exact calls); out_stats as phnsw_search_batch (evaluations, hops).
+ * Consequences: with every row allowed, no exclude and k <= number_of_candidates the row is the first k entries of
+ * phnsw_search_batch's row, with or without the flag.  With any filter the row holds the first k of the ALLOWED entries
+ * of phnsw_search_batch's row (same sp, upto_layers, exclude) -- the strict post-filter of the plain search -- or better
+ * ones: every allowed entry of that row is in `kept` or behind its tail.  The same holds against the
+ * PHNSW_FILTER_STRICT row of phnsw_search_batch_filtered ONLY where the two descents coincide (one layer walked:
+ * upto_layers 1 or a one-layer index): that call filters the queue of every layer, descends from other candidates below
+ * the top layer and may return rows this walk never evaluates, as this walk may return rows that one never does.  It is
+ * an APPROXIMATE result: it holds only rows the walk evaluated.
+ * Arguments as phnsw_search_batch_filtered[_device] / phnsw_search_batch_labeled[_device]; flags: PHNSW_COLLECT_EXTEND
+ * or 0; k follows the flags in the device forms too, whose rows hold k entries.  `filter` NULL = the index's default
+ * filter (phnsw_index_set_filter_device), else every row is allowed.  The label forms do not consult the default filter.
+ * Checks, in this order: index and sp as phnsw_search_batch; unknown flag bits; k == 0 or k > 64; a stride below the
+ * words of one bitmap; (label forms) a null or stale `lb`; all PHNSW_E_INVALID.  Then nq == 0, a no-op.  Then exactly
+ * one of queries / qids and the other pointers (PHNSW_E_INVALID).  Every store kind the filtered walk accepts.
+ * The host forms stage like phnsw_search_batch_filtered (per-query bitmaps travel with their chunk, u64 ids out, a query
+ * whose frontier spill overflowed is re-run with 8x the room, else PHNSW_E_OVERFLOW).  The device forms are ENQUEUED on
+ * `stream` and never synchronise it, with two exceptions that allocate and therefore wait for the device: the first call
+ * without any filter on an index makes that index's all-ones bitmap, once; and a call that descends in several launches
+ * (phnsw_search_batch_device's split descent of large batches) parks its running candidates in rows of
+ * number_of_candidates entries kept with the index's workspace, which grow -- free and allocate -- when a call needs more
+ * than any before it (calls of one size, or smaller ones, never wait): status_dev per query as phnsw_search_batch_device, u32 ids padded with 0xFFFFFFFF, rows of k.
+ * want_dev and the handle's column are read by the kernels: keep both alive until the work on `stream` is done.
+ * Cost and yield: profiles/collect/README.md.  The routed calls (phnsw_search_filtered_auto, phnsw_search_labeled_auto)
+ * do not use this walk. */
+enum { PHNSW_COLLECT_EXTEND = 1 };
+int phnsw_search_collect(const phnsw_index *ix, const float *queries, const uint64_t *qids, uint64_t nq,
+                         const phnsw_search_params *sp, uint32_t upto_layers, const uint64_t *exclude,
+                         const uint32_t *filter, uint32_t filter_stride_words, uint32_t flags, uint64_t k,
+                         uint64_t *out_ids, float *out_d, uint64_t *out_len, uint64_t *out_stats);
+int phnsw_search_collect_device(const phnsw_index *ix, const float *queries_dev, uint32_t ldq, const uint32_t *qids_dev,
+                                uint64_t nq, const phnsw_search_params *sp, uint32_t upto_layers,
+                                const uint32_t *exclude_dev, const uint32_t *filter_dev, uint32_t filter_stride_words,
+                                uint32_t flags, uint64_t k, uint32_t *out_ids_dev, float *out_d_dev,
+                                uint32_t *out_len_dev, uint32_t *out_stats_dev, uint32_t *status_dev, void *stream);
+int phnsw_search_collect_labeled(const phnsw_index *ix, const phnsw_labels *lb, const float *queries, const uint64_t *qids,
+                                 uint64_t nq, const phnsw_search_params *sp, uint32_t upto_layers, const uint64_t *exclude,
+                                 const uint32_t *want, uint32_t flags, uint64_t k, uint64_t *out_ids, float *out_d,
+                                 uint64_t *out_len, uint64_t *out_stats);
+int phnsw_search_collect_labeled_device(const phnsw_index *ix, const phnsw_labels *lb, const float *queries_dev,
+                                        uint32_t ldq, const uint32_t *qids_dev, uint64_t nq, const phnsw_search_params *sp,
+                                        uint32_t upto_layers, const uint32_t *exclude_dev, const uint32_t *want_dev,
+                                        uint32_t flags, uint64_t k, uint32_t *out_ids_dev, float *out_d_dev,
+                                        uint32_t *out_len_dev, uint32_t *out_stats_dev, uint32_t *status_dev, void *stream);
 /* Throughput callers keep TWO batches in flight: phnsw_search_batch_device calls issued alternately on two streams
  * overlap (an index holds two search workspaces) -- if the two streams sit on different hardware queues.  HIP maps a
  * process's streams onto a few of them (GPU_MAX_HW_QUEUES, 4 by default) and two streams that share one run in issue

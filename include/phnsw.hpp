@@ -336,6 +336,39 @@ class Hnsw {
                                              stride_words, strict ? PHNSW_FILTER_STRICT : 0u, out_ids_dev, out_d_dev,
                                              out_len_dev, out_stats_dev, status_dev, stream));
   }
+  // the collecting search (phnsw_search_collect): search_many_topk whose walk of the last layer also keeps the best k
+  // ALLOWED rows it evaluates and returns those, where search_many_filtered filters the queue afterwards.  `allow` and
+  // stride_words as for search_many_filtered (empty = the default of set_filter_device, else every row).  extend: a hop
+  // that improved the kept rows counts as one that did something (PHNSW_COLLECT_EXTEND).  1 <= k <= 64; k may exceed
+  // number_of_candidates.  Throws on an `allow` shorter than its bitmaps
+  std::vector<SearchResult> search_many_collect(const std::vector<const float *> &queries, const SearchParameters &sp,
+                                                uint64_t k, const std::vector<uint32_t> &allow, uint32_t stride_words = 0,
+                                                bool extend = false) const {
+    const uint64_t nq = queries.size(), dim = c_->dim(), words = (c_->len() + 31) / 32;
+    if (k == 0 || k > 64) throw Error(PHNSW_E_INVALID, "search_many_collect: k must be 1..64");
+    if (!allow.empty() && (stride_words ? stride_words < words || allow.size() < nq * stride_words : allow.size() < words))
+      throw Error(PHNSW_E_INVALID, "search_many_collect: allow is shorter than its bitmaps (ceil(n / 32) words shared, "
+                                   "nq * stride_words per query, stride_words >= ceil(n / 32))");
+    std::vector<float> q(nq * dim);
+    for (uint64_t i = 0; i < nq; i++) std::copy(queries[i], queries[i] + dim, q.begin() + i * dim);
+    std::vector<uint64_t> ids(nq * k), len(nq);
+    std::vector<float> d(nq * k);
+    check(phnsw_search_collect(ix_, q.data(), nullptr, nq, &sp, 0, nullptr, allow.empty() ? nullptr : allow.data(),
+                               stride_words, extend ? PHNSW_COLLECT_EXTEND : 0u, k, ids.data(), d.data(), len.data(), nullptr));
+    std::vector<SearchResult> out(nq);
+    for (uint64_t i = 0; i < nq; i++)
+      for (uint64_t j = 0; j < len[i]; j++) out[i].push_back({ids[i * k + j], d[i * k + j]});
+    return out;
+  }
+  // zero-copy form (phnsw_search_collect_device): rows of k u32 ids; enqueued on `stream`, never synchronises it
+  void search_collect_device(const float *queries_dev, uint32_t ldq, const uint32_t *qids_dev, uint64_t nq,
+                             const SearchParameters &sp, uint32_t upto, const uint32_t *exclude_dev, const uint32_t *filter_dev,
+                             uint32_t stride_words, bool extend, uint64_t k, uint32_t *out_ids_dev, float *out_d_dev,
+                             uint32_t *out_len_dev, uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) const {
+    check(phnsw_search_collect_device(ix_, queries_dev, ldq, qids_dev, nq, &sp, upto, exclude_dev, filter_dev, stride_words,
+                                      extend ? PHNSW_COLLECT_EXTEND : 0u, k, out_ids_dev, out_d_dev, out_len_dev,
+                                      out_stats_dev, status_dev, stream));
+  }
   // the exact k nearest among the allowed VectorIds (phnsw_search_exact_filtered): a scan of the allow-list instead of
   // the graph walk, recall 1 -- the call for selective filters.  `allow` as for search_many_filtered (empty = the default
   // of set_filter_device, else every vector of the index).  Only vectors of the index are candidates; a disallowed id is
@@ -456,6 +489,18 @@ class Hnsw {
                                           const uint32_t *exclude_dev, const uint32_t *want_dev, uint32_t flags,
                                           uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
                                           uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) const;
+  // search_many_collect by row label (phnsw_search_collect_labeled): the rows search_many_collect gives with the
+  // equivalent per-query bitmaps, bit for bit, read from the handle's label column
+  inline std::vector<SearchResult> search_many_collect_labeled(const std::vector<const float *> &queries,
+                                                               const SearchParameters &sp, uint64_t k, const Labels &labels,
+                                                               const std::vector<uint32_t> &want, bool extend = false) const;
+  // zero-copy form (phnsw_search_collect_labeled_device): rows of k u32 ids; enqueued on `stream`, never synchronises it
+  inline void search_collect_labeled_device(const Labels &labels, const float *queries_dev, uint32_t ldq,
+                                            const uint32_t *qids_dev, uint64_t nq, const SearchParameters &sp,
+                                            uint32_t upto_layers, const uint32_t *exclude_dev, const uint32_t *want_dev,
+                                            bool extend, uint64_t k, uint32_t *out_ids_dev, float *out_d_dev,
+                                            uint32_t *out_len_dev, uint32_t *out_stats_dev, uint32_t *status_dev,
+                                            void *stream) const;
   // search_many_filtered_auto by row label (phnsw_search_labeled_auto): per query the posting-list scan or the strict
   // walk by label, the scan again for short rows; every result holds min(k, list length) entries, listed vectors of
   // want[i] only.  scan_below 0 = the library's threshold for labels (20 000, phnsw.h), UINT64_MAX = always scan.
@@ -694,6 +739,34 @@ inline void Hnsw::search_batch_labeled_device(const Labels &labels, const float 
                                               uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) const {
   check(phnsw_search_batch_labeled_device(ix_, labels.handle(), queries_dev, ldq, qids_dev, nq, &sp, upto_layers, exclude_dev,
                                           want_dev, flags, out_ids_dev, out_d_dev, out_len_dev, out_stats_dev, status_dev, stream));
+}
+inline std::vector<SearchResult> Hnsw::search_many_collect_labeled(const std::vector<const float *> &queries,
+                                                                   const SearchParameters &sp, uint64_t k,
+                                                                   const Labels &labels, const std::vector<uint32_t> &want,
+                                                                   bool extend) const {
+  const uint64_t nq = queries.size(), dim = c_->dim();
+  if (k == 0 || k > 64) throw Error(PHNSW_E_INVALID, "search_many_collect_labeled: k must be 1..64");
+  if (want.size() != nq) throw Error(PHNSW_E_INVALID, "search_many_collect_labeled: one wanted label per query");
+  std::vector<float> q(nq * dim);
+  for (uint64_t i = 0; i < nq; i++) std::copy(queries[i], queries[i] + dim, q.begin() + i * dim);
+  std::vector<uint64_t> ids(nq * k), len(nq);
+  std::vector<float> d(nq * k);
+  check(phnsw_search_collect_labeled(ix_, labels.handle(), q.data(), nullptr, nq, &sp, 0, nullptr, want.data(),
+                                     extend ? PHNSW_COLLECT_EXTEND : 0u, k, ids.data(), d.data(), len.data(), nullptr));
+  std::vector<SearchResult> out(nq);
+  for (uint64_t i = 0; i < nq; i++)
+    for (uint64_t j = 0; j < len[i]; j++) out[i].push_back({ids[i * k + j], d[i * k + j]});
+  return out;
+}
+inline void Hnsw::search_collect_labeled_device(const Labels &labels, const float *queries_dev, uint32_t ldq,
+                                                const uint32_t *qids_dev, uint64_t nq, const SearchParameters &sp,
+                                                uint32_t upto_layers, const uint32_t *exclude_dev, const uint32_t *want_dev,
+                                                bool extend, uint64_t k, uint32_t *out_ids_dev, float *out_d_dev,
+                                                uint32_t *out_len_dev, uint32_t *out_stats_dev, uint32_t *status_dev,
+                                                void *stream) const {
+  check(phnsw_search_collect_labeled_device(ix_, labels.handle(), queries_dev, ldq, qids_dev, nq, &sp, upto_layers, exclude_dev,
+                                            want_dev, extend ? PHNSW_COLLECT_EXTEND : 0u, k, out_ids_dev, out_d_dev,
+                                            out_len_dev, out_stats_dev, status_dev, stream));
 }
 inline std::vector<SearchResult> Hnsw::search_many_labeled_auto(const std::vector<const float *> &queries,
                                                                 const SearchParameters &sp, uint64_t k, const Labels &labels,

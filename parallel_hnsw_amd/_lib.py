@@ -154,6 +154,14 @@ SYMBOLS = {
     "phnsw_search_labeled_auto": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
     "phnsw_search_labeled_auto_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp,
                                                 _vp, _vp, _vp]),
+    "phnsw_search_collect": (_i32, [_vp, _vp, _vp, _u64, C.POINTER(SearchParams), _u32, _vp, _vp, _u32, _u32, _u64, _vp, _vp,
+                                    _vp, _vp]),
+    "phnsw_search_collect_device": (_i32, [_vp, _vp, _u32, _vp, _u64, C.POINTER(SearchParams), _u32, _vp, _vp, _u32, _u32,
+                                           _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "phnsw_search_collect_labeled": (_i32, [_vp, _vp, _vp, _vp, _u64, C.POINTER(SearchParams), _u32, _vp, _vp, _u32, _u64,
+                                            _vp, _vp, _vp, _vp]),
+    "phnsw_search_collect_labeled_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, C.POINTER(SearchParams), _u32, _vp, _vp,
+                                                   _u32, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "phnsw_filter_count_device": (_i32, [_vp, _vp, _u32, _u64, _vp, _vp]),
     "phnsw_search_filtered_auto": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _u32, _u64, _u64, _vp, _vp, _vp, _vp]),
     "phnsw_search_filtered_auto_device": (_i32, [_vp, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _u32, _u64, _u64, _vp, _vp, _vp,

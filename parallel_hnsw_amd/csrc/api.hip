@@ -556,6 +556,7 @@ extern "C" void phnsw_index_destroy(phnsw_index *ix) {
   ph_grouped_free(ix);
   ph_build_table_free(ix);
   if (ix->totals) hipFree(ix->totals);
+  if (ix->all_ones) hipFree(ix->all_ones);
   phnsw_store_destroy(ix->store);
   delete ix;
   ph_pool_trim();
@@ -657,6 +658,15 @@ static void fill_args(const phnsw_index *ix, const PhSearchCall &c, PhSearchArgs
   a.cap_max = c.knn_mode == 2 ? c.out_stride : 0;
   a.out_index = c.out_index;  // Hnsw::search_instrumented: the INSTR kernels, every layer on the per-hop path, one launch
   a.order = c.order;
+  if (c.collect_k) {  // the caller's rows hold collect_k entries; out_ids / out_d: only a split descent's parking (below)
+    a.collect_k = c.collect_k;
+    a.collect_flags = c.collect_flags;
+    a.collect_ids = c.out_ids;
+    a.collect_d = c.out_d;
+    a.out_ids = nullptr;
+    a.out_d = nullptr;
+    a.filter_flags = 0u;
+  }
 }
 
 // spill-list entries per resident wave; PHNSW_OVF_CAP (tests) forces a small list so that the
@@ -809,6 +819,23 @@ int ph_search_device(const phnsw_index *ix, const PhSearchCall &c) {
     for (uint32_t l = first_big; l < a.n_layers && !rc; l++)
       rc = ph_layer_anchor_pos(ix->store, mix->layers[l - 1]);  // first use on a loaded index; no-op afterwards
     if (rc) return rc;
+    if (a.collect_k) {  // rows of collect_k entries cannot park number_of_candidates running candidates: the workspace does
+      const size_t need = (size_t)nq * a.ef * 4u;
+      if (ws.park_ids_bytes < need) {
+        if (ws.park_ids) PH_HIP(hipFree(ws.park_ids));
+        ws.park_ids = nullptr, ws.park_ids_bytes = 0;
+        PH_HIP(hipMalloc(&ws.park_ids, need));
+        ws.park_ids_bytes = need;
+      }
+      if (ws.park_d_bytes < need) {
+        if (ws.park_d) PH_HIP(hipFree(ws.park_d));
+        ws.park_d = nullptr, ws.park_d_bytes = 0;
+        PH_HIP(hipMalloc(&ws.park_d, need));
+        ws.park_d_bytes = need;
+      }
+      a.out_ids = ws.park_ids;
+      a.out_d = ws.park_d;
+    }
   }
   rc = attach_probes(mix, c, a);
   if (rc) return rc;
@@ -838,8 +865,8 @@ int ph_search_device(const phnsw_index *ix, const PhSearchCall &c) {
       if (b.exclude) b.exclude += c0;
       if (b.filter) b.filter += c0 * b.filter_stride;  // per-query bitmaps follow the chunk; a shared one (stride 0) stays
       if (b.label_want) b.label_want += c0;  // ... and so do the wanted labels; the column is indexed by VectorId
-      b.out_ids += c0 * ostride;
-      b.out_d += c0 * ostride;
+      if (b.out_ids) b.out_ids += c0 * ostride, b.out_d += c0 * ostride;
+      if (b.collect_k) b.collect_ids += c0 * b.collect_k, b.collect_d += c0 * b.collect_k;
       b.out_len += c0;
       if (b.out_stats) b.out_stats += 2 * c0;
       b.status += c0;
@@ -887,6 +914,12 @@ int ph_search_device(const phnsw_index *ix, const PhSearchCall &c) {
       if (dense_first) {
         p.dense_only = lo == 0 ? 1u : 0u;
         p.after_dense = lo == Td ? Td : 0u;
+      }
+      if (!last && p.collect_k) {
+        // the upper layers of a collecting search are the plain search's: no filter, the candidates parked in ef-rows
+        p.collect_k = p.collect_flags = 0u;
+        p.filter = nullptr, p.filter_stride = 0u;
+        p.label_of = p.label_want = nullptr;
       }
       p.order = lo ? ws.oorder : nullptr;
       p.out_hit = last ? out_hit_final : nullptr;
@@ -981,6 +1014,88 @@ extern "C" int phnsw_search_batch_filtered_device(const phnsw_index *ix, const f
   if (rc) return rc;
   if (!c.filter.words) c.filter.words = ix->default_filter;  // phnsw_index_set_filter_device
   if (nq == 0) return 0;
+  PH_HIP(hipSetDevice(ix->store->device));
+  return ph_search_device(ix, c);
+} catch (...) { return ph_caught(); }
+
+// ---- the collecting search: device forms (the host forms: hostpath.hip)
+
+int ph_collect_filter(const phnsw_index *ix, PhFilter *f, bool *on_device) {
+  *on_device = false;
+  f->flags = 0u;
+  if (f->words) return 0;  // the caller's
+  f->stride = 0u;
+  *on_device = true;
+  if (ix->default_filter) {  // phnsw_index_set_filter_device
+    f->words = ix->default_filter;
+    return 0;
+  }
+  // no filter at all = every row allowed: the collecting kernels read a bitmap, so the index keeps one of all ones
+  phnsw_index *mix = const_cast<phnsw_index *>(ix);
+  std::lock_guard<std::mutex> g(mix->ws_mutex);
+  const uint64_t words = (ix->store->n + 31u) / 32u;
+  if (mix->all_ones_words < words) {
+    PH_HIP(hipSetDevice(ix->store->device));
+    if (mix->all_ones) PH_HIP(hipFree(mix->all_ones));
+    mix->all_ones = nullptr, mix->all_ones_words = 0;
+    PH_HIP(hipMalloc(&mix->all_ones, (size_t)words * 4u));
+    PH_HIP(hipMemset(mix->all_ones, 0xFF, (size_t)words * 4u));
+    PH_HIP(hipStreamSynchronize(nullptr));  // once per index: the callers' streams do not wait for the null stream
+    mix->all_ones_words = words;
+  }
+  f->words = mix->all_ones;
+  return 0;
+}
+
+extern "C" int phnsw_search_collect_device(const phnsw_index *ix, const float *queries_dev, uint32_t ldq,
+                                           const uint32_t *qids_dev, uint64_t nq, const phnsw_search_params *sp,
+                                           uint32_t upto_layers, const uint32_t *exclude_dev, const uint32_t *filter_dev,
+                                           uint32_t filter_stride_words, uint32_t flags, uint64_t k, uint32_t *out_ids_dev,
+                                           float *out_d_dev, uint32_t *out_len_dev, uint32_t *out_stats_dev,
+                                           uint32_t *status_dev, void *stream) try {
+  const char *const call = "phnsw_search_collect_device";
+  int rc = ph_collect_check(ix, sp, filter_stride_words, flags, k, call);
+  if (rc) return rc;
+  if (nq == 0) return 0;
+  PhSearchCall c = device_call(queries_dev, ldq, qids_dev, nq, sp, upto_layers, exclude_dev, out_ids_dev, out_d_dev,
+                               out_len_dev, out_stats_dev, status_dev, stream);
+  if ((!queries_dev) == (!qids_dev)) {
+    ph_set_error("%s: pass queries or qids (exactly one)", call);
+    return PHNSW_E_INVALID;
+  }
+  rc = check_device_call(call, ix, c);
+  if (rc) return rc;
+  c.collect_k = (uint32_t)k, c.collect_flags = flags;
+  c.filter.words = filter_dev, c.filter.stride = filter_dev ? filter_stride_words : 0u;
+  bool on_device = false;
+  rc = ph_collect_filter(ix, &c.filter, &on_device);
+  if (rc) return rc;
+  PH_HIP(hipSetDevice(ix->store->device));
+  return ph_search_device(ix, c);
+} catch (...) { return ph_caught(); }
+
+extern "C" int phnsw_search_collect_labeled_device(const phnsw_index *ix, const phnsw_labels *lb, const float *queries_dev,
+                                                   uint32_t ldq, const uint32_t *qids_dev, uint64_t nq,
+                                                   const phnsw_search_params *sp, uint32_t upto_layers,
+                                                   const uint32_t *exclude_dev, const uint32_t *want_dev, uint32_t flags,
+                                                   uint64_t k, uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                                   uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) try {
+  const char *const call = "phnsw_search_collect_labeled_device";
+  int rc = ph_collect_check(ix, sp, 0u, flags, k, call);
+  if (rc) return rc;
+  rc = ph_labels_fresh(ix, lb, call);
+  if (rc) return rc;
+  if (nq == 0) return 0;
+  PhSearchCall c = device_call(queries_dev, ldq, qids_dev, nq, sp, upto_layers, exclude_dev, out_ids_dev, out_d_dev,
+                               out_len_dev, out_stats_dev, status_dev, stream);
+  if (((!queries_dev) == (!qids_dev)) || !want_dev) {
+    ph_set_error("%s: invalid argument (queries or qids, exactly one; want)", call);
+    return PHNSW_E_INVALID;
+  }
+  rc = check_device_call(call, ix, c);
+  if (rc) return rc;
+  c.collect_k = (uint32_t)k, c.collect_flags = flags;
+  c.filter.label_of = ph_labels_column(lb), c.filter.want = want_dev;
   PH_HIP(hipSetDevice(ix->store->device));
   return ph_search_device(ix, c);
 } catch (...) { return ph_caught(); }

@@ -36,6 +36,7 @@ struct Slot {
   float *q = nullptr;
   size_t q_bytes = 0;
   uint32_t *small = nullptr;  // device: qid | excl | len | status | index | stats(2)   [7][n_cap]
+                              // (a collecting search by label has no index row: it stages `want` there)
   size_t n_cap = 0;
   uint32_t *ids = nullptr;  // device [cnt][ef]
   float *d = nullptr;
@@ -237,7 +238,8 @@ int ph_search_host(const phnsw_index *ix, const PhHostSearch &h) {
   const uint64_t nq = h.nq, out_k = h.out_k;
   uint64_t *const out_ids = h.out_ids, *const out_len = h.out_len, *const out_stats = h.out_stats, *const out_index = h.out_index;
   float *const out_d = h.out_d;
-  const uint32_t ef = h.exact ? (uint32_t)h.out_k : (uint32_t)h.sp->number_of_candidates;  // entries of a staged result row
+  // entries of a staged result row (a collecting search writes rows of k, whatever number_of_candidates is)
+  const uint32_t ef = (h.exact || h.collect) ? (uint32_t)h.out_k : (uint32_t)h.sp->number_of_candidates;
   if ((!queries && !qids && !h.knn_mode) || !out_ids || !out_d || !out_len || nq > 0xFFFFFFFFull || out_k > ef) {
     ph_set_error("search: invalid argument (queries or ids, outputs, k <= number_of_candidates)");
     return PHNSW_E_INVALID;
@@ -294,6 +296,7 @@ int ph_search_host(const phnsw_index *ix, const PhHostSearch &h) {
   const PhFilter &filter = h.filter;
   const bool filtered = filter.words != nullptr;
   const bool per_query = filtered && filter.stride != 0;
+  const bool labeled = filter.label_of != nullptr;  // the collecting search by label: the column is on the device, want [nq] here
   const uint64_t filter_words = (s->n + 31u) / 32u;
   PhFilter fdev = {nullptr, 0u, filtered ? filter.flags : 0u};
   if (filtered && h.filter_on_device) fdev.words = filter.words;
@@ -355,6 +358,10 @@ int ph_search_host(const phnsw_index *ix, const PhHostSearch &h) {
       fdev.words = sl.filt;
       fdev.stride = filter.stride;
     }
+    if (labeled) {  // the wanted labels travel with their chunk, in the (unused) index row of the per-query words
+      for (uint64_t i = 0; i < cnt; i++) sl.h_small[4 * N + i] = filter.want[first + i];
+      PH_STAGE_HIP(hipMemcpyAsync(sl.small + 4 * N, sl.h_small + 4 * N, N * 4, hipMemcpyHostToDevice, sl.stream));
+    }
     if (h.exact) {  // the scan over the allow-list (filter_exact.hip) on the same staging: rows of k entries
       PhExactCall x = {};
       if (queries) x.queries = sl.q;
@@ -375,6 +382,8 @@ int ph_search_host(const phnsw_index *ix, const PhHostSearch &h) {
     if (qids) c.qids = sl.small;
     if (exclude) c.exclude = sl.small + N;
     if (filtered) c.filter = fdev;
+    if (labeled) c.filter.label_of = filter.label_of, c.filter.want = sl.small + 4 * N;
+    if (h.collect) c.collect_k = k, c.collect_flags = h.collect_flags;
     c.ldq = s->ld, c.nq = cnt, c.sp = h.sp, c.upto = h.upto;
     c.out_ids = sl.ids, c.out_d = sl.d, c.out_len = sl.small + 2 * N, c.status = sl.small + 3 * N;
     if (out_index) c.out_index = sl.small + 4 * N;
@@ -412,7 +421,7 @@ int ph_search_host(const phnsw_index *ix, const PhHostSearch &h) {
   }
 
   // queries whose frontier spill outgrew the workspace: rerun them alone with 8x the room (rare)
-  uint32_t ovf_cap = ph_default_ovf_cap(ef);
+  uint32_t ovf_cap = ph_default_ovf_cap(h.collect ? (uint32_t)h.sp->number_of_candidates : ef);
   for (int attempt = 0; !redo.empty(); attempt++) {
     if (h.knn_mode) {
       ph_set_error("knn: frontier spill exceeded %u entries", ovf_cap);
@@ -540,5 +549,71 @@ extern "C" int phnsw_search_exact_filtered(const phnsw_index *ix, const float *q
   PH_TRY(ph_filter_check(ix, filter, filter_stride_words, 0u, "phnsw_search_exact_filtered", &h.filter));
   h.filter_on_device = !h.filter.words && ix->default_filter;  // phnsw_index_set_filter_device: device words
   if (h.filter_on_device) h.filter.words = ix->default_filter;
+  return ph_search_host(ix, h);
+} catch (...) { return ph_caught(); }
+
+// ---- the collecting search: the plain search whose last layer keeps the best ALLOWED rows it evaluates (phnsw.h)
+
+// what the four collecting entry points check first, in this order: index and parameters, the flags, k, the stride
+int ph_collect_check(const phnsw_index *ix, const phnsw_search_params *sp, uint32_t stride, uint32_t flags, uint64_t k,
+                     const char *call) {
+  PH_TRY(ph_check_sp(ix, sp));
+  if (flags & ~(uint32_t)PHNSW_COLLECT_EXTEND) {
+    ph_set_error("%s: unknown flag bits 0x%x", call, flags);
+    return PHNSW_E_INVALID;
+  }
+  if (k == 0 || k > PH_COLLECT_KMAX) {
+    ph_set_error("%s: k must be 1..%u (got %llu)", call, PH_COLLECT_KMAX, (unsigned long long)k);
+    return PHNSW_E_INVALID;
+  }
+  const uint64_t words = (ix->store->n + 31u) / 32u;
+  if (stride && stride < words) {
+    ph_set_error("%s: filter_stride_words %u is below the %llu words of one bitmap (0 = one shared bitmap)", call, stride,
+                 (unsigned long long)words);
+    return PHNSW_E_INVALID;
+  }
+  return 0;
+}
+
+extern "C" int phnsw_search_collect(const phnsw_index *ix, const float *queries, const uint64_t *qids, uint64_t nq,
+                                    const phnsw_search_params *sp, uint32_t upto_layers, const uint64_t *exclude,
+                                    const uint32_t *filter, uint32_t filter_stride_words, uint32_t flags, uint64_t k,
+                                    uint64_t *out_ids, float *out_d, uint64_t *out_len, uint64_t *out_stats) try {
+  const char *const call = "phnsw_search_collect";
+  PH_TRY(ph_collect_check(ix, sp, filter_stride_words, flags, k, call));
+  if (nq == 0) return 0;
+  if ((!queries) == (!qids)) {
+    ph_set_error("%s: pass queries or qids (exactly one)", call);
+    return PHNSW_E_INVALID;
+  }
+  PhHostSearch h = host_call(queries, qids, nq, sp, out_ids, out_d, out_len);
+  h.upto = upto_layers, h.exclude = exclude, h.out_k = k, h.out_stats = out_stats;
+  h.collect = true, h.collect_flags = flags;
+  h.filter.words = filter, h.filter.stride = filter ? filter_stride_words : 0u;
+  PH_TRY(ph_collect_filter(ix, &h.filter, &h.filter_on_device));
+  return ph_search_host(ix, h);
+} catch (...) { return ph_caught(); }
+
+extern "C" int phnsw_search_collect_labeled(const phnsw_index *ix, const phnsw_labels *lb, const float *queries,
+                                            const uint64_t *qids, uint64_t nq, const phnsw_search_params *sp,
+                                            uint32_t upto_layers, const uint64_t *exclude, const uint32_t *want, uint32_t flags,
+                                            uint64_t k, uint64_t *out_ids, float *out_d, uint64_t *out_len,
+                                            uint64_t *out_stats) try {
+  const char *const call = "phnsw_search_collect_labeled";
+  PH_TRY(ph_collect_check(ix, sp, 0u, flags, k, call));
+  PH_TRY(ph_labels_fresh(ix, lb, call));
+  if (nq == 0) return 0;
+  if ((!queries) == (!qids)) {
+    ph_set_error("%s: pass queries or qids (exactly one)", call);
+    return PHNSW_E_INVALID;
+  }
+  if (!want) {
+    ph_set_error("%s: invalid argument (want is NULL)", call);
+    return PHNSW_E_INVALID;
+  }
+  PhHostSearch h = host_call(queries, qids, nq, sp, out_ids, out_d, out_len);
+  h.upto = upto_layers, h.exclude = exclude, h.out_k = k, h.out_stats = out_stats;
+  h.collect = true, h.collect_flags = flags;
+  h.filter.label_of = ph_labels_column(lb), h.filter.want = want;
   return ph_search_host(ix, h);
 } catch (...) { return ph_caught(); }

@@ -184,6 +184,11 @@ struct PhWorkspace {
   size_t dense_ovf_bytes = 0;
   uint32_t *ovf_s = nullptr;  // search_instrumented: index sums of the spilled entries, [n_slots][ovf_cap]
   size_t ovf_s_cap = 0;
+  // a collecting search in a split descent: its output rows hold collect_k entries, so the running candidates are
+  // parked here between the launches, [nq][ef]
+  uint32_t *park_ids = nullptr;
+  float *park_d = nullptr;
+  size_t park_ids_bytes = 0, park_d_bytes = 0;
   // per-dispatch bookkeeping of the last descent (phnsw_last_search_dispatches): evd[0] closes the
   // dense-top-layer kernels, evd[1 + i] search launch i; dtotals[i] = {distance evaluations, hops}
   hipEvent_t evd[PH_MAX_DISPATCH + 1] = {};
@@ -263,6 +268,8 @@ struct phnsw_index {
   unsigned long long *totals = nullptr;  // device [2]: distance evaluations, hops of every launch on this index
   const uint32_t *dbg_order = nullptr;  // experiment hook
   const uint32_t *default_filter = nullptr;  // phnsw_index_set_filter_device: the caller's shared bitmap, filtered calls only
+  uint32_t *all_ones = nullptr;  // a bitmap that allows every vector of the store, for collecting calls without a filter
+  uint64_t all_ones_words = 0;   // (made on first use under ws_mutex, remade when the store has grown)
   uint64_t dbg_order_n = 0;
   std::mutex exact_mutex;  // filter_exact.hip
   PhExactScratch exact[2];
@@ -368,6 +375,13 @@ struct PhSearchArgs {
   // elsewhere; label_want [nq], what each query wants.  nullptr = not a label launch.  filter_flags as for the bitmap.
   // (At the end: the argument offsets of every other kernel stay what they were.)
   const uint32_t *label_of, *label_want;
+  // the collecting walk (phnsw_search_collect*, search_collect.hip): collect_k != 0 selects the PH_FM_COLLECT twins for
+  // the LAST launch of a descent, which writes rows of collect_k entries to collect_ids / collect_d (and their lengths to
+  // out_len); out_ids / out_d are then only where a split descent parked its candidates.  collect_flags:
+  // PHNSW_COLLECT_EXTEND.  (At the end, like the label pair.)
+  uint32_t collect_k, collect_flags;
+  uint32_t *collect_ids;
+  float *collect_d;
 };
 
 uint32_t ph_default_ovf_cap(uint32_t ef);
@@ -411,6 +425,10 @@ struct PhSearchCall {
   uint32_t *out_hit, *out_index;  // [nq] or nullptr
   const uint32_t *order;
   const PhRowHint *hint;  // a build's searches: the kept table (tiny.hip)
+  // the collecting search (phnsw_search_collect*): collect_k = 1..64 results per query, and out_ids / out_d are then
+  // rows of collect_k entries; `filter` is what the last layer's walk collects by (never STRICT: the descent itself is
+  // the plain search's).  collect_flags: PHNSW_COLLECT_EXTEND
+  uint32_t collect_k, collect_flags;
 };
 int ph_search_device(const phnsw_index *ix, const PhSearchCall &c);
 // argument checks the search entry points share (api.hip): index and parameters; the device forms' pointers (`call`
@@ -418,6 +436,13 @@ int ph_search_device(const phnsw_index *ix, const PhSearchCall &c);
 int ph_check_sp(const phnsw_index *ix, const phnsw_search_params *sp);
 int ph_filter_check(const phnsw_index *ix, const uint32_t *filter, uint32_t stride, uint32_t flags, const char *call,
                     PhFilter *f);
+// the filter of a collecting call by bitmap: the caller's, else the index's default filter, else a bitmap of all ones
+// kept with the index (the collecting kernels exist over a bitmap and over a label column; api.hip)
+int ph_collect_filter(const phnsw_index *ix, PhFilter *f, bool *on_device);
+// what the collecting entry points check first, in this order: index and parameters, the flags, k in 1..64, the stride
+int ph_collect_check(const phnsw_index *ix, const phnsw_search_params *sp, uint32_t stride, uint32_t flags, uint64_t k,
+                     const char *call);
+#define PH_COLLECT_KMAX 64u
 // The request of one host-pointer search (ph_search_host, hostpath.hip): host arrays, ids as u64.
 struct PhHostSearch {
   const float *queries;            // [nq][dim] or nullptr
@@ -433,6 +458,10 @@ struct PhHostSearch {
   PhFilter filter;                  // host words; words == nullptr: none
   bool filter_on_device;            // filter.words is a shared bitmap in device memory (phnsw_index_set_filter_device)
   bool exact;  // the exact scan over the allow-list instead of the graph search (ph_exact_device): sp unused, out_k = k >= 1
+  // the collecting search: out_k = k = 1..64, rows of k entries.  Its label form: filter.label_of = the handle's column
+  // (device), filter.want = HOST labels [nq], staged with their chunk
+  bool collect;
+  uint32_t collect_flags;
 };
 int ph_search_host(const phnsw_index *ix, const PhHostSearch &h);
 // The request of one exact top-k scan over an allow-list (ph_exact_device, filter_exact.hip).  Device pointers of the

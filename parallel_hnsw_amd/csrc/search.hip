@@ -185,6 +185,11 @@ static PhKernelChoice pick_search_kernel(const phnsw_store *s, uint32_t ef_max, 
   PhKernelChoice k = pick_unfiltered_kernel(s, ef_max, nv4, grows, nq, instr);
   if (mode == PH_FM_BITMAP && k.fn) k.fn = ph_pick_filtered_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
   if (mode == PH_FM_LABEL && k.fn) k.fn = ph_pick_labeled_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
+  // the collecting twins: the new calls only (PhSearchArgs::collect_k), and only the last launch of their descent
+  if (mode == (PH_FM_BITMAP | PH_FM_COLLECT) && k.fn)
+    k.fn = ph_pick_collect_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
+  if (mode == (PH_FM_LABEL | PH_FM_COLLECT) && k.fn)
+    k.fn = ph_pick_collect_labeled_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
   return k;
 }
 
@@ -232,6 +237,8 @@ void ph_workspace_free(PhWorkspace &ws) {
   if (ws.dtotals) hipFree(ws.dtotals);
   if (ws.dense_ovf) hipFree(ws.dense_ovf);
   if (ws.ovf_s) hipFree(ws.ovf_s);
+  if (ws.park_ids) hipFree(ws.park_ids);
+  if (ws.park_d) hipFree(ws.park_d);
   ph_workspace_order_free(ws);
   ph_tiny_free(ws);
   ws = PhWorkspace();
@@ -323,6 +330,10 @@ static hipError_t grow_buf(T **p, size_t *have, size_t need) {
 static int search_launch_dense(PhWorkspace &ws, PhSearchArgs &a, hipStream_t stream) {
   const int capc = pick_capc_dense(a.ef);
   const int mode = ph_filter_mode(a);
+  if (mode & PH_FM_COLLECT) {  // (api.hip launches the upper layers of a collecting descent without its filter)
+    ph_set_error("a collecting search has no dense-only launch");
+    return PHNSW_E_UNSUPPORTED;
+  }
   ph_search_fn fn = mode == PH_FM_LABEL ? ph_pick_labeled_dense(capc)
                                         : (mode == PH_FM_BITMAP ? ph_pick_filtered_dense(capc) : pick_kernel_dense<PH_FM_NONE>(capc));
   if (!fn) {
@@ -406,6 +417,12 @@ int ph_search_launch(const phnsw_index *ix, PhWorkspace &ws, PhSearchArgs &a, hi
   const int mode = ph_filter_mode(a);
   if (mode != PH_FM_NONE && (a.knn_mode || a.out_index)) {  // only the plain searches have filtered kernels
     ph_set_error("knn / threshold_nn / search_instrumented take no filter");
+    return PHNSW_E_UNSUPPORTED;
+  }
+  if ((mode & PH_FM_COLLECT) &&
+      (mode == PH_FM_COLLECT || (a.layer_hi && a.layer_hi != a.n_layers) || !a.collect_ids || !a.collect_d ||
+       a.collect_k > PH_COLLECT_KMAX)) {
+    ph_set_error("a collecting launch is the last of its descent, over a bitmap or a label column, with rows of 1..64 entries");
     return PHNSW_E_UNSUPPORTED;
   }
   PhKernelChoice k = pick_search_kernel(st, ef_max, a.dist.nv4, a.knn_mode == 2, a.nq, a.out_index != nullptr, mode);

@@ -1,0 +1,8 @@
+// The collecting twins of the search kernels over an allow-list (PH_FM_BITMAP | PH_FM_COLLECT: the last layer's walk
+// keeps the best allowed rows it evaluates, phnsw_search_collect[_device]) and the function that hands them to the
+// launchers of search.hip: a translation unit of their own, compiled beside the other search units.
+#include "search_kernels.h"
+
+ph_search_fn ph_pick_collect_kernel(int family, int capc, int nv, int pqr_m, bool pq_global) {
+  return pick_kernel_family<PH_FM_BITMAP | PH_FM_COLLECT>(family, capc, nv, pqr_m, pq_global);
+}

@@ -1,7 +1,8 @@
 // The search kernels (search.hip has the long form) and the functions that name their instances, for the two
 // translation units that instantiate them: search.hip the kernels as they always were, search_filtered.hip their bitmap
 // twins, the kernels of a search restricted to an allow-list of VectorIds, search_labeled.hip their label twins, the same
-// restriction read from a label column.  Three units so that they compile side by side.
+// restriction read from a label column; search_collect.hip and search_collect_labeled.hip the collecting twins of those
+// two (PH_FM_COLLECT).  Five units so that they compile side by side.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -92,14 +93,23 @@ __device__ __forceinline__ bool vis_insert(uint32_t *H, uint32_t slots, uint32_t
 //                 test of `want` cost seven twins a wave per SIMD (profiles/labeled_walk)
 // A mode of the body and not a run-time test of the pointers: the test alone cost 19 of the 88 kernels scratch
 // (profiles/filter), so the filtered instances exist beside the others and are picked only when a filter is given.
-enum : int { PH_FM_NONE = 0, PH_FM_BITMAP = 1, PH_FM_LABEL = 2 };
+//   PH_FM_COLLECT  a bit on top of PH_FM_BITMAP / PH_FM_LABEL: the collecting walk (phnsw_search_collect*, search_collect.hip,
+//                  search_collect_labeled.hip).  The descent is the PLAIN search's -- the layer tails apply `exclude` only --
+//                  and the walk of the last layer keeps, beside the layer's queue, the a.collect_k best evaluated rows
+//                  that pass the filter (`kq`, below); those are the result row.  Only ever the last launch of a descent.
+enum : int { PH_FM_NONE = 0, PH_FM_BITMAP = 1, PH_FM_LABEL = 2, PH_FM_COLLECT = 4 };
 // the mode a launch's arguments ask for
-static inline int ph_filter_mode(const PhSearchArgs &a) { return a.label_of ? PH_FM_LABEL : (a.filter ? PH_FM_BITMAP : PH_FM_NONE); }
+static inline int ph_filter_mode(const PhSearchArgs &a) {
+  return (a.label_of ? PH_FM_LABEL : (a.filter ? PH_FM_BITMAP : PH_FM_NONE)) | (a.collect_k ? PH_FM_COLLECT : PH_FM_NONE);
+}
 
 template <int CAPC, class Dist, bool INSTR = false, bool BIG = false, int FILT = PH_FM_NONE>
 __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
   extern __shared__ uint32_t smem[];
   constexpr int CAP = CAPC * 64;
+  constexpr int FM = FILT & (PH_FM_BITMAP | PH_FM_LABEL);  // where the filter is read from
+  constexpr bool COLLECT = (FILT & PH_FM_COLLECT) != 0;
+  constexpr int TAILF = COLLECT ? PH_FM_NONE : FM;  // closest_vectors' `include` beyond `exclude`: none in a collecting walk
   uint32_t *Cid = smem;                    // running candidates: VectorIds (search.rs:110)
   float *Cd = (float *)(smem + CAP);       //
   uint32_t *Qid = smem + 2 * CAP;          // layer queue: NodeIds | EXPF (lib.rs:264)
@@ -193,9 +203,56 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
       dist.prepare_stored(a.dist, qvec, dist_lds, lane);
     const uint32_t excl = a.exclude ? a.exclude[q] : PH_EMPTY32;
     // the allow-list of this query (wave-uniform): `include` of lib.rs:250-277
-    const uint32_t *const allow = FILT == PH_FM_BITMAP ? a.filter + (uint64_t)q * a.filter_stride : nullptr;
+    const uint32_t *const allow = FM == PH_FM_BITMAP ? a.filter + (uint64_t)q * a.filter_stride : nullptr;
     // ... or the label it wants (wave-uniform); NONE matches nothing, not even the unlisted vectors that carry it
-    const uint32_t want = FILT == PH_FM_LABEL ? rfl32(a.label_want[q]) : PHNSW_LABEL_NONE;
+    const uint32_t want = FM == PH_FM_LABEL ? rfl32(a.label_want[q]) : PHNSW_LABEL_NONE;
+    // the filter test of VectorId v, written once for the layer tail, the strict pass and the collecting walk (callers
+    // guard it: only lanes holding an id read a word or a label)
+    auto passes = [&](uint32_t v) -> bool {
+      if constexpr (FM == PH_FM_BITMAP) {
+        return (allow[v >> 5] >> (v & 31)) & 1u;
+      } else if constexpr (FM == PH_FM_LABEL) {
+        const uint32_t lbl = a.label_of[v];
+        return lbl == want && lbl != PHNSW_LABEL_NONE;
+      } else {
+        return true;
+      }
+    };
+    // COLLECT: `kq`, the contract's `kept` (phnsw.h; named apart from the `kept` counters of the tails below): a
+    // PriorityQueue of capacity a.collect_k ordered by (distance, id) like every queue here, in registers: lane i holds
+    // the 64-bit key of slot i (VectorId in the low word), KEY_NONE in empty slots and in slots >= collect_k.  No LDS:
+    // the LDS budget decides occupancy and the size of the visited table.
+    uint64_t kq = KEY_NONE;
+    uint32_t klen = 0;
+    // merge of one batch into `kq`: ckey = the lane's key when its row qualifies, else KEY_NONE.  Returns whether
+    // `kq` changed.  One ballot of the lanes that can enter (below the tail of a full `kq`, any while it is not
+    // full); empty = nothing else to do, the common case late in a layer.  Otherwise a scalar loop over the entering
+    // bits (v_readlane + 64-bit compare, the idiom of the main merge): keys are distinct and absent from `kq` (the
+    // nodes are fresh), so the final slot of an entering key = (kq keys below) + (entering keys below), two s_bcnt1 of
+    // compare masks, and the lane of that slot takes it; every other slot s pulls the kq entry s - (entering keys
+    // placed under s) with one ds_bpermute per half.  What lands at slot >= collect_k drops out.
+    auto collect = [&](uint64_t ckey) -> bool {
+      const uint32_t kk = a.collect_k;
+      const uint64_t tail = klen == kk ? rl64(kq, (int)kk - 1) : KEY_NONE;
+      const bool ent = ckey < tail;
+      const uint64_t em = __ballot(ent);
+      if (!em) return false;
+      uint64_t in = KEY_NONE;
+      uint32_t under = 0;
+      for (uint64_t rem = em; rem; rem &= rem - 1) {
+        const uint64_t kj = rl64(ckey, __builtin_ctzll(rem));
+        const uint32_t p = (uint32_t)__popcll(__ballot(kq < kj)) + (uint32_t)__popcll(__ballot(ent && ckey < kj));
+        under += p < lane ? 1u : 0u;
+        if (p == lane) in = kj;
+      }
+      const int src = (int)((lane - under) << 2);  // under <= lane: the slots below hold `under` entering keys
+      const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)(uint32_t)kq);
+      const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)(uint32_t)(kq >> 32));
+      kq = in != KEY_NONE ? in : (((uint64_t)hi << 32) | lo);
+      if (lane >= kk) kq = KEY_NONE;
+      klen = min(kk, klen + (uint32_t)__popcll(em));
+      return true;
+    };
     uint32_t n_dist = 0, n_hops = 0, err = ST_OK;
     uint32_t index_distance = 0xFFFFFFFFu;  // usize::MAX until a layer has run  search.rs:112
     uint32_t n_tab = 0;  // of n_dist: evaluations served by the dense tables (measurement: the rest are gathered rows)
@@ -327,6 +384,23 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
         qlen = clen;
       }
       queue_sync<BIG>();
+      if constexpr (COLLECT) {
+        // `kq` starts from the qualifying entries of the queue the last layer starts with (the `pairs` of
+        // closest_vectors: the running candidates, still in C as VectorIds): allowed, not excluded, at most f32::MAX away
+        if (li == last_layer) {
+#pragma unroll
+          for (int c = 0; c < CAPC; c++) {
+            if (64u * c >= clen) break;
+            const uint32_t i = lane + 64u * c;
+            const bool has = i < clen;
+            const uint32_t v = has ? Cid[i] : 0u;
+            const float d = has ? Cd[i] : PH_FMAX;
+            bool ok = has && v != excl && d <= PH_FMAX;
+            if (ok) ok = passes(v);
+            collect(ok ? mkkey(d, v) : KEY_NONE);
+          }
+        }
+      }
 
       // Hnsw::threshold_nn (lib.rs:930-962, knn_mode == 2) calls closest_nodes repeatedly on a
       // growing queue; everything else runs this block once
@@ -466,6 +540,15 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
         }
 #endif
         PH_TICK(2)
+        // COLLECT: the filter test of the fresh lanes' vectors, one word or one label each, issued with the row requests
+        uint32_t cvec = 0;
+        bool cq = false;
+        if constexpr (COLLECT) {
+          if (li == last_layer && fresh) {
+            cvec = identity ? nb : L.nodes[nb];  // (a dense layer walks table ids: its node list maps them too)
+            cq = cvec != excl && passes(cvec);
+          }
+        }
 
         // distance batch: compare_vec(v, Stored(get_vector(n)))  lib.rs:200-202 -- in a dense top
         // layer the value was computed by the tile pass (same bits) and is looked up
@@ -645,6 +728,14 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
         scan_from = min(pop >= 0 ? (uint32_t)pop + 1u : scan_from, pos_min);
         queue_sync<BIG>();
         PH_TICK(4)
+        if constexpr (COLLECT) {
+          // every qualifying member of the batch merge_pairs sees, those bound for the spill list included: their
+          // distances are still in registers (after the main merge: its keys and ranks are dead by now).  PHNSW_COLLECT_EXTEND: a hop that changed `kq` did something.
+          if (li == last_layer) {
+            const bool changed = collect((cq && myd <= PH_FMAX) ? mkkey(myd, cvec) : KEY_NONE);
+            if (a.collect_flags & PHNSW_COLLECT_EXTEND) did = did || changed;
+          }
+        }
         if (ovf_n > ovf_cap) {
           err = ST_OVERFLOW;
           break;
@@ -752,13 +843,8 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
         bd[c] = has ? Qd[i] : PH_FMAX;
         bv[c] = has ? (identity ? nid : L.nodes[nid]) : PH_EMPTY32;
         bool keep = has && bv[c] != excl;
-        if constexpr (FILT == PH_FM_BITMAP)
-          if (keep) keep = (allow[bv[c] >> 5] >> (bv[c] & 31)) & 1u;  // (only lanes holding an id read a word)
-        if constexpr (FILT == PH_FM_LABEL)
-          if (keep) {  // (... or a label)
-            const uint32_t lbl = a.label_of[bv[c]];
-            keep = lbl == want && lbl != PHNSW_LABEL_NONE;
-          }
+        if constexpr (TAILF != PH_FM_NONE)
+          if (keep) keep = passes(bv[c]);  // (only lanes holding an id read a word or a label)
         uint64_t km = __ballot(keep);
         uint32_t at = kept + __popcll(km & lt);
         bpos[c] = (keep && at < candidate_count) ? at : PH_EMPTY32;
@@ -839,10 +925,12 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
       for (uint32_t i = lane; i < hslots; i += 64) H[i] = PH_EMPTY32;
       wait_vm0();
       clen = 0;
+      kq = KEY_NONE;
+      klen = 0;
     }
     // PHNSW_FILTER_STRICT: the entry vector enters `candidates` before any filter runs (search.rs:102-111) and may
     // sit in the row although it is disallowed; the last launch of a descent takes such ids out, in order
-    if (FILT && (a.filter_flags & PHNSW_FILTER_STRICT) && layer_hi == a.n_layers && !big_written) {
+    if (TAILF && (a.filter_flags & PHNSW_FILTER_STRICT) && layer_hi == a.n_layers && !big_written) {
       uint32_t sv[CAPC];
       float sd[CAPC];
       uint32_t spos[CAPC];
@@ -854,14 +942,7 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
         sv[c] = has ? Cid[i] : 0u;
         sd[c] = has ? Cd[i] : PH_FMAX;
         bool keep = false;
-        if constexpr (FILT == PH_FM_LABEL) {
-          if (has) {
-            const uint32_t lbl = a.label_of[sv[c]];
-            keep = lbl == want && lbl != PHNSW_LABEL_NONE;
-          }
-        } else {
-          if (has) keep = (allow[sv[c] >> 5] >> (sv[c] & 31)) & 1u;
-        }
+        if (has) keep = passes(sv[c]);
         const uint64_t km = __ballot(keep);
         spos[c] = keep ? kept + __popcll(km & lt) : PH_EMPTY32;
         kept += __popcll(km);
@@ -878,10 +959,20 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
       queue_sync<BIG>();
     }
     // (candidates.iter().collect(), ..)  search.rs:139
+    if constexpr (COLLECT) {
+      // the row of a collecting search is `kq`: rows of collect_k entries, the distance from the key's upper word
+      // (unfkey: the walk's bits; a -0.0 comes back as +0.0, as from the exact calls)
+      const uint32_t kk = a.collect_k;
+      if (lane < kk) {
+        a.collect_ids[(uint64_t)q * kk + lane] = lane < klen ? (uint32_t)kq : PH_EMPTY32;
+        a.collect_d[(uint64_t)q * kk + lane] = lane < klen ? unfkey((uint32_t)(kq >> 32)) : PH_FMAX;
+      }
+    } else {
     const uint32_t ostride = a.out_stride ? a.out_stride : a.ef;
     for (uint32_t i = lane; i < ostride && !big_written; i += 64) {
       a.out_ids[(uint64_t)q * ostride + i] = i < clen ? Cid[i] : PH_EMPTY32;
       a.out_d[(uint64_t)q * ostride + i] = i < clen ? Cd[i] : PH_FMAX;
+    }
     }
     if (a.out_hit) {
       // res.iter().any(|v| v == *vid)  lib.rs:1492
@@ -928,7 +1019,7 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
     if constexpr (INSTR)
       if (lane == 0) a.out_index[q] = index_distance;
     if (lane == 0) {
-      a.out_len[q] = clen;
+      a.out_len[q] = COLLECT ? klen : clen;
       a.status[q] = err;
       if (a.out_stats) {
         a.out_stats[2 * (uint64_t)q] = n_dist;
@@ -1086,3 +1177,8 @@ ph_search_fn ph_pick_filtered_kernel(int family, int capc, int nv, int pqr_m, bo
 ph_search_fn ph_pick_filtered_dense(int capc);
 ph_search_fn ph_pick_labeled_kernel(int family, int capc, int nv, int pqr_m, bool pq_global);
 ph_search_fn ph_pick_labeled_dense(int capc);
+// the collecting twins (PH_FM_COLLECT over the bitmap and over the label column): search_collect.hip and
+// search_collect_labeled.hip.  No dense-only twin: a collecting kernel runs the last layer of a descent, and the
+// dense-only launch of a split descent never holds it (api.hip)
+ph_search_fn ph_pick_collect_kernel(int family, int capc, int nv, int pqr_m, bool pq_global);
+ph_search_fn ph_pick_collect_labeled_kernel(int family, int capc, int nv, int pqr_m, bool pq_global);

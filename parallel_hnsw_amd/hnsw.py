@@ -41,6 +41,7 @@ FILTER_STRICT = 1  # PHNSW_FILTER_STRICT
 FILTER_ALL = 0xFFFFFFFF  # PHNSW_FILTER_ALL: a selector of search_exact_grouped that names no bitmap
 ROUTE_GRAPH, ROUTE_SCAN, ROUTE_GRAPH_THEN_SCAN = 0, 1, 2  # PHNSW_ROUTE_*
 LABEL_NONE = 0xFFFFFFFF  # PHNSW_LABEL_NONE: a vector that is not listed; a wanted label with an empty row
+COLLECT_EXTEND = 1  # PHNSW_COLLECT_EXTEND: a hop that improved the kept rows counts as one that did something
 
 
 def pack_allow(allow, n, nq):
@@ -1084,6 +1085,83 @@ class Hnsw:
             self._h, labels._h, C.c_void_p(queries or None), ldq, C.c_void_p(qids or None), nq, C.byref(sp),
             C.c_void_p(exclude or None), C.c_void_p(want or None), int(k), int(scan_below), C.c_void_p(out_ids),
             C.c_void_p(out_d), C.c_void_p(out_len), C.c_void_p(out_route or None), C.c_void_p(status),
+            C.c_void_p(stream or None)))
+
+    def search_collect(self, queries=None, qids=None, sp=None, allow=None, exclude=None, upto=0, stats=False, k=10,
+                       extend=False):
+        """the collecting search (phnsw_search_collect): search_batch with the same sp, upto and exclude, whose walk of the
+        last layer also keeps the best k ALLOWED rows it evaluates (allowed, not excluded, distance <= f32::MAX) and
+        returns those -- where search_batch_filtered filters the layer's queue afterwards and comes back with about
+        density * number_of_candidates results.  allow as in search_batch_filtered (None = the default of set_filter,
+        else every row).  Without extend the traversal and its stats are search_batch's, bit for bit; extend=True lets a
+        hop that improved the kept rows count as one that did something, so probe_depth counts the hops that improve
+        neither queue; probe_depth idle hops in all (not in a row) still end the walk, so a short row does not mean that fewer than k
+        allowed rows are reachable.  The row holds the first k allowed entries of search_batch's row or better ones (not
+        of search_batch_filtered's, whose descent differs below the top layer).  1 <= k <= 64; k may exceed
+        number_of_candidates.  An approximate result: only rows the walk evaluated.  profiles/collect/README.md.
+        Returns (ids[nq, k] u64, d[nq, k] f32, len[nq]) and the stats with stats=True"""
+        if (queries is None) == (qids is None):
+            raise ValueError("search_collect: pass queries or qids (exactly one)")
+        sp = sp or SearchParameters()
+        q = qi = None
+        if queries is not None:
+            q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+            assert q.shape[1] == self.store.dim
+            nq = q.shape[0]
+        else:
+            qi = np.ascontiguousarray(qids, dtype=np.uint64)
+            nq = len(qi)
+        words, stride = pack_allow(allow, self.store.n, nq)
+        w = max(int(k), 0)
+        ids = np.empty((nq, w), dtype=np.uint64)
+        d = np.empty((nq, w), dtype=np.float32)
+        ln = np.zeros(nq, dtype=np.uint64)
+        st = np.zeros((nq, 2), dtype=np.uint64) if stats else None
+        ex = None if exclude is None else np.ascontiguousarray(exclude, dtype=np.uint64)
+        check(lib().phnsw_search_collect(self._h, _p(q), _p(qi), nq, C.byref(sp), upto, _p(ex), _p(words), stride,
+                                         COLLECT_EXTEND if extend else 0, int(k), _p(ids), _p(d), _p(ln), _p(st)))
+        return (ids, d, ln, st) if stats else (ids, d, ln)
+
+    def search_collect_device(self, nq, sp, k, out_ids, out_d, out_len, status, queries=0, ldq=0, qids=0, exclude=0,
+                              allow=0, allow_stride=0, extend=False, out_stats=0, upto=0, stream=0):
+        """zero-copy form (phnsw_search_collect_device): device pointers as integers, u32 ids [nq, k] padded with
+        0xFFFFFFFF; allow as in search_batch_filtered_device.  Enqueued on `stream`; never synchronises it"""
+        check(lib().phnsw_search_collect_device(
+            self._h, C.c_void_p(queries or None), ldq, C.c_void_p(qids or None), nq, C.byref(sp), upto,
+            C.c_void_p(exclude or None), C.c_void_p(allow or None), int(allow_stride), COLLECT_EXTEND if extend else 0, int(k),
+            C.c_void_p(out_ids), C.c_void_p(out_d), C.c_void_p(out_len), C.c_void_p(out_stats or None), C.c_void_p(status),
+            C.c_void_p(stream or None)))
+
+    def search_collect_labeled(self, queries=None, qids=None, sp=None, labels=None, want=None, exclude=None, upto=0,
+                               stats=False, k=10, extend=False):
+        """search_collect by row label (phnsw_search_collect_labeled): the rows, lengths and stats of
+        search_collect(allow=(the vectors listed under want[i])), bit for bit, without a bitmap per query.  labels: a
+        Labels made for this index; want: integers [nq] within u32, -1 or LABEL_NONE (or a label nobody carries) = an empty
+        row.  set_filter's default is not consulted.
+        Returns (ids[nq, k] u64, d[nq, k] f32, len[nq]) and the stats with stats=True"""
+        q, qi, nq, w32 = self._labeled_args("search_collect_labeled", queries, qids, labels, want)
+        sp = sp or SearchParameters()
+        w = max(int(k), 0)
+        ids = np.empty((nq, w), dtype=np.uint64)
+        d = np.empty((nq, w), dtype=np.float32)
+        ln = np.zeros(nq, dtype=np.uint64)
+        st = np.zeros((nq, 2), dtype=np.uint64) if stats else None
+        ex = None if exclude is None else np.ascontiguousarray(exclude, dtype=np.uint64)
+        check(lib().phnsw_search_collect_labeled(self._h, labels._h, _p(q), _p(qi), nq, C.byref(sp), upto, _p(ex), _p(w32),
+                                                 COLLECT_EXTEND if extend else 0, int(k), _p(ids), _p(d), _p(ln), _p(st)))
+        return (ids, d, ln, st) if stats else (ids, d, ln)
+
+    def search_collect_labeled_device(self, labels, nq, sp, k, out_ids, out_d, out_len, status, queries=0, ldq=0, qids=0,
+                                      exclude=0, want=0, extend=False, out_stats=0, upto=0, stream=0):
+        """zero-copy form (phnsw_search_collect_labeled_device): search_collect_device with want = u32 labels [nq] (a
+        device pointer, alive until the work on `stream` is done) in place of the bitmaps.  Enqueued on `stream`; never
+        synchronises it"""
+        if not isinstance(labels, Labels):
+            raise TypeError("search_collect_labeled_device: labels must be a Labels made for this index")
+        check(lib().phnsw_search_collect_labeled_device(
+            self._h, labels._h, C.c_void_p(queries or None), ldq, C.c_void_p(qids or None), nq, C.byref(sp), upto,
+            C.c_void_p(exclude or None), C.c_void_p(want or None), COLLECT_EXTEND if extend else 0, int(k),
+            C.c_void_p(out_ids), C.c_void_p(out_d), C.c_void_p(out_len), C.c_void_p(out_stats or None), C.c_void_p(status),
             C.c_void_p(stream or None)))
 
     def filter_count_device(self, nbitmaps, out_count, allow=0, allow_stride=0, stream=0):

@@ -691,6 +691,96 @@ impl GpuHnsw {
                                                      out_stats_dev, status_dev, stream));
     }
 
+    /// the collecting search (`phnsw_search_collect`): `search_many_topk` whose walk of the last layer also keeps the best
+    /// `k` rows `include` accepts among those it evaluates, and returns them -- where `search_many_filtered` filters the
+    /// queue afterwards.  `extend`: a hop that improved the kept rows counts as one that did something.  Panics unless
+    /// 1 <= k <= 64 (k may exceed number_of_candidates)
+    pub fn search_many_collect<F: Fn(VectorId) -> bool>(&self, queries: &[Vec<f32>], sp: SearchParameters, k: usize,
+                                                        include: F, extend: bool) -> Vec<Vec<(VectorId, f32)>> {
+        assert!(k >= 1 && k <= 64, "search_many_collect: k must be 1..64");
+        let nq = queries.len();
+        let psp = sp_c(sp);
+        let mut n64 = 0u64;
+        check(unsafe {
+            sys::phnsw_store_info(self.comparator.store.0, &mut n64, std::ptr::null_mut(), std::ptr::null_mut(),
+                                  std::ptr::null_mut(), std::ptr::null_mut())
+        });
+        let n = n64 as usize;
+        let mut words = vec![0u32; (n + 31) / 32];
+        for v in 0..n {
+            if include(VectorId(v)) {
+                words[v >> 5] |= 1u32 << (v & 31);
+            }
+        }
+        let mut q: Vec<f32> = Vec::with_capacity(nq * queries.first().map_or(0, |x| x.len()));
+        for x in queries {
+            q.extend_from_slice(x);
+        }
+        let (mut ids, mut d, mut len) = (vec![0u64; nq * k], vec![0f32; nq * k], vec![0u64; nq]);
+        check(unsafe {
+            sys::phnsw_search_collect(self.ix, q.as_ptr(), std::ptr::null(), nq as u64, &psp, 0, std::ptr::null(), words.as_ptr(), 0,
+                                      if extend { sys::PHNSW_COLLECT_EXTEND } else { 0 }, k as u64, ids.as_mut_ptr(),
+                                      d.as_mut_ptr(), len.as_mut_ptr(), std::ptr::null_mut())
+        });
+        (0..nq).map(|i| (0..len[i] as usize).map(|j| (VectorId(ids[i * k + j] as usize), d[i * k + j])).collect()).collect()
+    }
+
+    /// zero-copy form (`phnsw_search_collect_device`): rows of `k` u32 ids; enqueued on `stream`, never synchronises it
+    ///
+    /// # Safety
+    /// the pointers must be valid device allocations of the sizes `phnsw.h` documents for the call
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn search_collect_device(&self, queries_dev: *const f32, ldq: u32, qids_dev: *const u32, nq: u64,
+                                        sp: SearchParameters, upto: u32, exclude_dev: *const u32, filter_dev: *const u32,
+                                        filter_stride_words: u32, extend: bool, k: u64, out_ids_dev: *mut u32,
+                                        out_d_dev: *mut f32, out_len_dev: *mut u32, out_stats_dev: *mut u32,
+                                        status_dev: *mut u32, stream: *mut c_void) {
+        let psp = sp_c(sp);
+        check(sys::phnsw_search_collect_device(self.ix, queries_dev, ldq, qids_dev, nq, &psp, upto, exclude_dev, filter_dev,
+                                               filter_stride_words, if extend { sys::PHNSW_COLLECT_EXTEND } else { 0 }, k,
+                                               out_ids_dev, out_d_dev, out_len_dev, out_stats_dev, status_dev, stream));
+    }
+
+    /// `search_many_collect` by row label (`phnsw_search_collect_labeled`): the results `search_many_collect` gives with
+    /// the equivalent predicates, bit for bit, read from the handle's label column.  Panics unless 1 <= k <= 64 and
+    /// `want` has one entry per query
+    pub fn search_many_collect_labeled(&self, queries: &[Vec<f32>], sp: SearchParameters, k: usize, labels: &GpuLabels,
+                                       want: &[Option<u32>], extend: bool) -> Vec<Vec<(VectorId, f32)>> {
+        assert!(k >= 1 && k <= 64, "search_many_collect_labeled: k must be 1..64");
+        let nq = queries.len();
+        assert!(want.len() == nq, "search_many_collect_labeled: one wanted label per query");
+        let psp = sp_c(sp);
+        let w: Vec<u32> = want.iter().map(|l| l.unwrap_or(sys::PHNSW_LABEL_NONE)).collect();
+        let mut q: Vec<f32> = Vec::with_capacity(nq * queries.first().map_or(0, |x| x.len()));
+        for x in queries {
+            q.extend_from_slice(x);
+        }
+        let (mut ids, mut d, mut len) = (vec![0u64; nq * k], vec![0f32; nq * k], vec![0u64; nq]);
+        check(unsafe {
+            sys::phnsw_search_collect_labeled(self.ix, labels.lb, q.as_ptr(), std::ptr::null(), nq as u64, &psp, 0,
+                                              std::ptr::null(), w.as_ptr(), if extend { sys::PHNSW_COLLECT_EXTEND } else { 0 },
+                                              k as u64, ids.as_mut_ptr(), d.as_mut_ptr(), len.as_mut_ptr(), std::ptr::null_mut())
+        });
+        (0..nq).map(|i| (0..len[i] as usize).map(|j| (VectorId(ids[i * k + j] as usize), d[i * k + j])).collect()).collect()
+    }
+
+    /// zero-copy form (`phnsw_search_collect_labeled_device`): rows of `k` u32 ids; enqueued on `stream`, never
+    /// synchronises it
+    ///
+    /// # Safety
+    /// the pointers must be valid device allocations of the sizes `phnsw.h` documents for the call
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn search_collect_labeled_device(&self, labels: &GpuLabels, queries_dev: *const f32, ldq: u32,
+                                                qids_dev: *const u32, nq: u64, sp: SearchParameters, upto_layers: u32,
+                                                exclude_dev: *const u32, want_dev: *const u32, extend: bool, k: u64,
+                                                out_ids_dev: *mut u32, out_d_dev: *mut f32, out_len_dev: *mut u32,
+                                                out_stats_dev: *mut u32, status_dev: *mut u32, stream: *mut c_void) {
+        let psp = sp_c(sp);
+        check(sys::phnsw_search_collect_labeled_device(self.ix, labels.lb, queries_dev, ldq, qids_dev, nq, &psp, upto_layers,
+                                                       exclude_dev, want_dev, if extend { sys::PHNSW_COLLECT_EXTEND } else { 0 },
+                                                       k, out_ids_dev, out_d_dev, out_len_dev, out_stats_dev, status_dev, stream));
+    }
+
     /// `search_many_filtered_auto` by row label (`phnsw_search_labeled_auto`): per query the posting-list scan or the
     /// strict walk by label, the scan again for short rows; every result holds min(k, list length) entries, listed
     /// vectors of `want[i]` only.  `scan_below` 0 = the library's threshold for labels (20 000, `phnsw.h`),

@@ -24,6 +24,7 @@ pub const PHNSW_E_NOMEM: c_int = -8;
 
 pub const PHNSW_FILTER_STRICT: u32 = 1; // also drop disallowed ids (the entry vector) from the final rows
 pub const PHNSW_FILTER_ALL: u32 = 0xFFFF_FFFF; // filter_of[q] of phnsw_search_exact_grouped: no bitmap, every vector of the index
+pub const PHNSW_COLLECT_EXTEND: u32 = 1; // collecting search: a hop that improved the kept rows did something
 pub const PHNSW_LABEL_NONE: u32 = 0xFFFF_FFFF; // labels[v]: v is not listed; want[q]: an empty row
 
 pub const PHNSW_METRIC_COSINE_HALF: c_int = 0; // (1 - dot)/2   bigvec.rs:47-53
@@ -310,6 +311,25 @@ extern "C" {
                                             exclude_dev: *const u32, want_dev: *const u32, k: u64, scan_below: u64,
                                             out_ids_dev: *mut u32, out_d_dev: *mut c_float, out_len_dev: *mut u32,
                                             out_route_dev: *mut u32, status_dev: *mut u32, stream: *mut c_void) -> c_int;
+    // the collecting search: the plain walk whose last layer keeps the best k allowed rows it evaluates (k <= 64)
+    pub fn phnsw_search_collect(ix: *const phnsw_index, queries: *const c_float, qids: *const u64, nq: u64,
+                                sp: *const phnsw_search_params, upto_layers: u32, exclude: *const u64, filter: *const u32,
+                                filter_stride_words: u32, flags: u32, k: u64, out_ids: *mut u64, out_d: *mut c_float,
+                                out_len: *mut u64, out_stats: *mut u64) -> c_int;
+    pub fn phnsw_search_collect_device(ix: *const phnsw_index, queries_dev: *const c_float, ldq: u32, qids_dev: *const u32,
+                                       nq: u64, sp: *const phnsw_search_params, upto_layers: u32, exclude_dev: *const u32,
+                                       filter_dev: *const u32, filter_stride_words: u32, flags: u32, k: u64,
+                                       out_ids_dev: *mut u32, out_d_dev: *mut c_float, out_len_dev: *mut u32,
+                                       out_stats_dev: *mut u32, status_dev: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn phnsw_search_collect_labeled(ix: *const phnsw_index, lb: *const phnsw_labels, queries: *const c_float,
+                                        qids: *const u64, nq: u64, sp: *const phnsw_search_params, upto_layers: u32,
+                                        exclude: *const u64, want: *const u32, flags: u32, k: u64, out_ids: *mut u64,
+                                        out_d: *mut c_float, out_len: *mut u64, out_stats: *mut u64) -> c_int;
+    pub fn phnsw_search_collect_labeled_device(ix: *const phnsw_index, lb: *const phnsw_labels, queries_dev: *const c_float,
+                                               ldq: u32, qids_dev: *const u32, nq: u64, sp: *const phnsw_search_params,
+                                               upto_layers: u32, exclude_dev: *const u32, want_dev: *const u32, flags: u32,
+                                               k: u64, out_ids_dev: *mut u32, out_d_dev: *mut c_float, out_len_dev: *mut u32,
+                                               out_stats_dev: *mut u32, status_dev: *mut u32, stream: *mut c_void) -> c_int;
     pub fn phnsw_filter_count_device(ix: *const phnsw_index, filter_dev: *const u32, filter_stride_words: u32,
                                      nbitmaps: u64, out_count_dev: *mut u32, stream: *mut c_void) -> c_int;
     // per query the scan or the graph walk, the scan again for short rows: min(k, candidates) entries, candidates only
