@@ -474,6 +474,19 @@ class Hnsw {
                                           uint64_t nq, const uint32_t *exclude_dev, const uint32_t *want_dev, uint64_t k,
                                           uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev, uint32_t *status_dev,
                                           void *stream) const;
+  // search_many_exact_labeled for a SET of labels per query (phnsw_search_exact_labelset): query i may return the vectors
+  // `labels` lists under any label of want[i]; an empty set, PHNSW_LABEL_NONE and labels nobody carries give nothing, a
+  // label twice counts once.  The same results, bit for bit, as the bitmaps {v : label of v in want[i]} give.  Exact scan
+  // only: there is no graph walk by set.  Throws on a bad k and on want.size() != queries before the library is called
+  inline std::vector<SearchResult> search_many_exact_labelset(const std::vector<const float *> &queries, uint64_t k,
+                                                              const Labels &labels,
+                                                              const std::vector<std::vector<uint32_t>> &want) const;
+  // zero-copy form (phnsw_search_exact_labelset_device): the sets in CSR form, want_first_dev [nq + 1] and want_values_dev
+  // [nwant]; status 8 = a range of want_first_dev that is not sound; enqueued on `stream`, never synchronises it
+  inline void search_exact_labelset_device(const Labels &labels, const float *queries_dev, uint32_t ldq, const uint32_t *qids_dev,
+                                           uint64_t nq, const uint32_t *exclude_dev, const uint32_t *want_first_dev,
+                                           const uint32_t *want_values_dev, uint64_t nwant, uint64_t k, uint32_t *out_ids_dev,
+                                           float *out_d_dev, uint32_t *out_len_dev, uint32_t *status_dev, void *stream) const;
   // search_many_filtered by row label (phnsw_search_batch_labeled): the graph walk of query i restricted to the vectors
   // `labels` lists under want[i], read from the handle's label column instead of a bitmap per query -- the results
   // search_many_filtered gives with the equivalent bitmaps, bit for bit.  A post-filter: about number_of_candidates *
@@ -679,6 +692,11 @@ class Labels {
   void count_device(const uint32_t *want_dev, uint64_t nq, uint32_t *out_count_dev, void *stream) const {
     check(phnsw_labels_count_device(lb_, want_dev, nq, out_count_dev, stream));
   }
+  // per query the summed list lengths of the distinct labels of its set (CSR, as search_exact_labelset_device)
+  void count_set_device(const uint32_t *want_first_dev, const uint32_t *want_values_dev, uint64_t nq, uint64_t nwant,
+                        uint32_t *out_count_dev, void *stream) const {
+    check(phnsw_labels_count_set_device(lb_, want_first_dev, want_values_dev, nq, nwant, out_count_dev, stream));
+  }
   phnsw_labels *handle() const { return lb_; }
 
  private:
@@ -712,6 +730,38 @@ inline void Hnsw::search_exact_labeled_device(const Labels &labels, const float 
                                               uint32_t *out_len_dev, uint32_t *status_dev, void *stream) const {
   check(phnsw_search_exact_labeled_device(ix_, labels.handle(), queries_dev, ldq, qids_dev, nq, exclude_dev, want_dev, k,
                                           out_ids_dev, out_d_dev, out_len_dev, status_dev, stream));
+}
+
+inline std::vector<SearchResult> Hnsw::search_many_exact_labelset(const std::vector<const float *> &queries, uint64_t k,
+                                                                  const Labels &labels,
+                                                                  const std::vector<std::vector<uint32_t>> &want) const {
+  const uint64_t nq = queries.size(), dim = c_->dim();
+  if (k == 0 || k > 1024) throw Error(PHNSW_E_INVALID, "search_many_exact_labelset: k must be 1..1024");
+  if (want.size() != nq) throw Error(PHNSW_E_INVALID, "search_many_exact_labelset: one set of wanted labels per query");
+  std::vector<float> q(nq * dim);
+  for (uint64_t i = 0; i < nq; i++) std::copy(queries[i], queries[i] + dim, q.begin() + i * dim);
+  std::vector<uint32_t> first(nq + 1, 0), values;
+  for (uint64_t i = 0; i < nq; i++) {
+    values.insert(values.end(), want[i].begin(), want[i].end());
+    if (values.size() > 0x7FFFFFFEull) throw Error(PHNSW_E_INVALID, "search_many_exact_labelset: too many wanted labels");
+    first[i + 1] = (uint32_t)values.size();
+  }
+  std::vector<uint64_t> ids(nq * k), len(nq);
+  std::vector<float> d(nq * k);
+  check(phnsw_search_exact_labelset(ix_, labels.handle(), q.data(), nullptr, nq, nullptr, first.data(), values.data(), k,
+                                    ids.data(), d.data(), len.data()));
+  std::vector<SearchResult> out(nq);
+  for (uint64_t i = 0; i < nq; i++)
+    for (uint64_t j = 0; j < len[i]; j++) out[i].push_back({ids[i * k + j], d[i * k + j]});
+  return out;
+}
+inline void Hnsw::search_exact_labelset_device(const Labels &labels, const float *queries_dev, uint32_t ldq,
+                                               const uint32_t *qids_dev, uint64_t nq, const uint32_t *exclude_dev,
+                                               const uint32_t *want_first_dev, const uint32_t *want_values_dev, uint64_t nwant,
+                                               uint64_t k, uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                               uint32_t *status_dev, void *stream) const {
+  check(phnsw_search_exact_labelset_device(ix_, labels.handle(), queries_dev, ldq, qids_dev, nq, exclude_dev, want_first_dev,
+                                           want_values_dev, nwant, k, out_ids_dev, out_d_dev, out_len_dev, status_dev, stream));
 }
 
 inline std::vector<SearchResult> Hnsw::search_many_labeled(const std::vector<const float *> &queries, const SearchParameters &sp,

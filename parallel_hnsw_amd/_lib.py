@@ -148,6 +148,10 @@ SYMBOLS = {
     "phnsw_labels_destroy": (None, [_vp]),
     "phnsw_search_exact_labeled": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp]),
     "phnsw_search_exact_labeled_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "phnsw_labels_count_set_device": (_i32, [_vp, _vp, _vp, _u64, _u64, _vp, _vp]),
+    "phnsw_search_exact_labelset": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "phnsw_search_exact_labelset_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp,
+                                                  _vp]),
     "phnsw_search_batch_labeled": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _u32, _u64, _vp, _vp, _vp, _vp]),
     "phnsw_search_batch_labeled_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp,
                                                  _vp, _vp, _vp]),

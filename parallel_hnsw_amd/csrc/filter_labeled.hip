@@ -26,6 +26,14 @@
 // batch_distances takes them.  What filter_exact.hip has beyond the shared headers is restated here; no existing
 // kernel is touched (profiles/filter_labeled/).
 //
+// A SET of labels per query (phnsw_search_exact_labelset[_device], phnsw_labels_count_set_device; labelset_plan.h): the
+// lists of distinct labels are disjoint, so a set is more slices of the same scan.  A position of the sorted batch is a
+// (query, wanted label) PAIR: ph_labelset_claim_kernel (which query owns a pair; the offsets are not trusted),
+// ph_labelset_lookup_kernel, the same sort, ph_labelset_positions_kernel (the query of a position, the inverse
+// permutation, duplicate flags), the tile table as above, the PAIRS instances of the scan and tile kernels -- every
+// position writes its per-slice lists to scratch, none a row --, ph_labelset_merge_kernel: a wave per query merges the
+// lists of its positions through the same running top-k.  No graph walk by set.
+//
 // The graph walk by label (phnsw_search_batch_labeled[_device], at the end of this file) is the search kernels' own
 // label mode (search_labeled.hip) over label_of; the routed call (phnsw_search_labeled_auto) is filter_auto.hip's and
 // takes its scan from here through the subset form of a call (PhLabeledCall::list).
@@ -40,6 +48,7 @@
 #include "exact_topk.h"
 #include "filter_candidate.h"
 #include "label_plan.h"
+#include "labelset_plan.h"
 #include "phnsw_device.h"
 
 #define PH_TRY(x)          \
@@ -166,7 +175,9 @@ __global__ __launch_bounds__(256) void ph_labeled_count_kernel(const uint32_t *v
 
 // One wave64 per (position, slice of its list); work item = slice * nq + position (slice-major, position-minor, the
 // positions label-major): the waves resident together read the same rows.
-template <class Dist>
+// PAIRS: the form of phnsw_search_exact_labelset -- a position is a (query, wanted label) pair, order[pos] the pair's
+// query; a position never writes a row, its lists go to the scratch at every slice count.
+template <class Dist, bool PAIRS = false>
 __global__ __launch_bounds__(64) void ph_labeled_scan_kernel(PhLabeledArgs a) {
   extern __shared__ float labeled_lds[];
   const uint32_t lane = threadIdx.x;
@@ -197,7 +208,7 @@ __global__ __launch_bounds__(64) void ph_labeled_scan_kernel(PhLabeledArgs a) {
       const float d = dist.batch(a.dist, __ballot(ok), id, lane);
       top.insert(ok && id != ex ? mkkey(d, id) : KEY_NONE, lane);
     }
-    if (a.slices == 1u) {
+    if (!PAIRS && a.slices == 1u) {
       ph_exact_write_row(a, q, top.cur, top.len, bad_query, lane);
     } else {
       uint64_t *const out = a.scratch + ((uint64_t)pos * a.slices + slice) * a.k;
@@ -222,6 +233,113 @@ __global__ __launch_bounds__(64) void ph_labeled_merge_kernel(PhLabeledArgs a) {
         if (!top.insert(b + lane < a.k ? list[b + lane] : KEY_NONE, lane)) break;
     }
     ph_exact_write_row(a, q, top.cur, top.len, !a.queries && a.qids[q] >= a.n, lane);
+  }
+}
+
+// ------------------------------------------------------------------ a SET of labels per query: pairs (labelset_plan.h)
+
+// a = the block of the scan and tile kernels with nq = nwant POSITIONS; order[pos] is the query of the position's pair
+struct PhLabelsetArgs {
+  PhLabeledArgs a;
+  const uint32_t *want_first, *want_values;  // [nq + 1], [nwant]: the caller's, untrusted
+  uint32_t nq, nwant;
+  uint32_t *owner;  // [nwant] by pair: the query that claimed it, PH_LABELSET_OWNER_NONE
+  uint32_t *spair;  // [nwant] by position: its pair
+  uint32_t *inv;    // [nwant] by pair: its position
+  uint32_t *dup;    // [nwant] by position: 1 = the (slot, query) of the position before it
+};
+
+// owner[] is preset to NONE.  One thread per query claims the pairs of a sound range; the lowest query keeps a pair.
+__global__ __launch_bounds__(256) void ph_labelset_claim_kernel(PhLabelsetArgs s) {
+  for (uint64_t q = (uint64_t)blockIdx.x * 256u + threadIdx.x; q < s.nq; q += (uint64_t)gridDim.x * 256u) {
+    const uint32_t b = s.want_first[q], e = s.want_first[q + 1u];
+    if (!ph_labelset_range_ok(b, e, s.nwant)) continue;
+    for (uint32_t i = b; i < e; i++)  // i < e <= nwant
+      if (!ph_labelset_claim_goes_on(atomicMin(&s.owner[i], (uint32_t)q), (uint32_t)q)) break;
+  }
+}
+
+// per pair: its slot (none for an unclaimed pair and for a bad Stored query id) and itself, the sort's value
+__global__ __launch_bounds__(256) void ph_labelset_lookup_kernel(PhLabelsetArgs s) {
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < s.nwant; i += (uint64_t)gridDim.x * 256u) {
+    const uint32_t q = s.owner[i];  // NONE or < nq
+    const bool dead = q == PH_LABELSET_OWNER_NONE || (!s.a.queries && s.a.qids[q] >= s.a.n);
+    s.a.slot[i] = dead ? PH_LABEL_SLOT_NONE : ph_label_slot(s.a.values, s.a.nlabels, s.want_values[i], PHNSW_LABEL_NONE);
+    s.a.iota[i] = (uint32_t)i;
+  }
+}
+
+// per position after the sort: its query (0 for an unclaimed pair, whose slot is none: it reads a row and scans
+// nothing), the inverse permutation, the duplicate flag
+__global__ __launch_bounds__(256) void ph_labelset_positions_kernel(PhLabelsetArgs s, uint32_t *order) {
+  for (uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x; p < s.nwant; p += (uint64_t)gridDim.x * 256u) {
+    const uint32_t i = s.spair[p], q = s.owner[i];
+    order[p] = q == PH_LABELSET_OWNER_NONE ? 0u : q;
+    s.inv[i] = (uint32_t)p;
+    s.dup[p] = p > 0 && ph_labelset_dup(s.a.sslot[p], q, s.a.sslot[p - 1u], s.owner[s.spair[p - 1u]]) ? 1u : 0u;
+  }
+}
+
+// whether query q owns every pair of a sound range: what makes its row; wave-uniform
+__device__ __forceinline__ bool ph_labelset_query_ok(const PhLabelsetArgs &s, uint32_t q, uint32_t b, uint32_t e, uint32_t lane) {
+  if (!ph_labelset_range_ok(b, e, s.nwant)) return false;
+  for (uint32_t i0 = b; i0 < e; i0 += 64u) {  // i0 + lane cannot wrap: e <= nwant < 2^31
+    const uint32_t i = i0 + lane;
+    if (__ballot(i < e && s.owner[i] != q)) return false;
+  }
+  return true;
+}
+
+// One wave per query: the lists of every position of its pairs -- duplicates and slot-less pairs left out -- through the
+// same running top-k as ph_labeled_merge_kernel, so ties across lists fall in id order.  A refused query (labelset_plan.h)
+// gets the empty row and status ST_LABELSET_RANGE.
+#define ST_LABELSET_RANGE 8u
+__global__ __launch_bounds__(64) void ph_labelset_merge_kernel(PhLabelsetArgs s) {
+  extern __shared__ float labeled_lds[];
+  const uint32_t lane = threadIdx.x;
+  const PhLabeledArgs &a = s.a;
+  uint64_t *const keys = (uint64_t *)labeled_lds;
+  for (uint32_t q = blockIdx.x; q < s.nq; q += gridDim.x) {
+    const uint32_t b = s.want_first[q], e = s.want_first[q + 1u];
+    const bool ok = ph_labelset_query_ok(s, q, b, e, lane);
+    __syncthreads();
+    PhExactTopK top;
+    top.cur = keys, top.nxt = keys + a.k, top.sv = keys + 2u * a.k, top.len = 0, top.k = a.k;
+    for (uint32_t i = b; ok && i < e; i++) {
+      const uint32_t pos = s.inv[i];  // < nwant: pair i is q's, so the sort placed it
+      if (s.dup[pos] || a.sslot[pos] == PH_LABEL_SLOT_NONE) continue;
+      for (uint32_t sl = 0; sl < a.slices; sl++) {
+        const uint64_t *const list = a.scratch + ((uint64_t)pos * a.slices + sl) * a.k;
+        for (uint32_t t = 0; t < a.k; t += 64u)
+          if (!top.insert(t + lane < a.k ? list[t + lane] : KEY_NONE, lane)) break;
+      }
+    }
+    ph_exact_write_row(a, q, top.cur, top.len, !a.queries && a.qids[q] >= a.n, lane);
+    if (!ok && lane == 0) a.status[q] = ST_LABELSET_RANGE;  // after the row's own status word, same lane
+  }
+}
+
+// per query the list lengths of the distinct slots of its range; a refused range counts 0.  Distinct: no earlier pair
+// of the range has the label -- sets are short, and the count needs no sort and no scratch.  One wave per query, a pair
+// per lane.
+__global__ __launch_bounds__(64) void ph_labelset_count_kernel(const uint32_t *values, const uint32_t *first, uint32_t nlabels,
+                                                               const uint32_t *want_first, const uint32_t *want_values,
+                                                               uint64_t nq, uint32_t nwant, uint32_t *out_count) {
+  const uint32_t lane = threadIdx.x;
+  for (uint64_t q = blockIdx.x; q < nq; q += gridDim.x) {
+    const uint32_t b = want_first[q], e = want_first[q + 1u];
+    uint32_t c = 0;
+    if (ph_labelset_range_ok(b, e, nwant))
+      for (uint64_t i = (uint64_t)b + lane; i < e; i += 64u) {
+        const uint32_t w = want_values[i];
+        bool seen = false;
+        for (uint32_t j = b; j < i && !seen; j++) seen = want_values[j] == w;
+        if (seen) continue;
+        const uint32_t sl = ph_label_slot(values, nlabels, w, PHNSW_LABEL_NONE);
+        if (sl != PH_LABEL_SLOT_NONE) c += first[sl + 1u] - first[sl];
+      }
+    for (int o = 32; o; o >>= 1) c += __shfl_xor(c, o);
+    if (lane == 0) out_count[q] = c;
   }
 }
 
@@ -313,7 +431,7 @@ __device__ __forceinline__ void ph_labeled_tile_batches(const PhLabeledArgs &a, 
 
 // One wave64 per (tile, slice of the tile's list); work item = slice * nq + tile (nq bounds the tiles; the count is a
 // device word), tiles label-major.
-template <int NV, class R>
+template <int NV, class R, bool PAIRS = false>
 __global__ __launch_bounds__(64) void ph_labeled_tile_kernel(PhLabeledArgs a) {
   extern __shared__ float labeled_lds[];
   const uint32_t lane = threadIdx.x;
@@ -372,7 +490,7 @@ __global__ __launch_bounds__(64) void ph_labeled_tile_kernel(PhLabeledArgs a) {
       const uint32_t *const st = l.state + 4u * t;
       const uint32_t tlen = rfl32(st[0]), q = rfl32(st[2]);
       const uint64_t *const cur = l.keys + (uint64_t)t * keys_per + (rfl32(st[1]) ? a.k : 0u);
-      if (a.slices == 1u) {
+      if (!PAIRS && a.slices == 1u) {
         ph_exact_write_row(a, q, cur, tlen, !a.queries && a.qids[q] >= a.n, lane);
       } else {
         uint64_t *const out = a.scratch + ((uint64_t)(p0 + t) * a.slices + slice) * a.k;
@@ -385,39 +503,40 @@ __global__ __launch_bounds__(64) void ph_labeled_tile_kernel(PhLabeledArgs a) {
 // ------------------------------------------------------------------ launchers
 
 typedef void (*PhLabeledFn)(PhLabeledArgs);
+// pairs: the PAIRS instance, phnsw_search_exact_labelset's
 template <template <int, int> class D>
-static PhLabeledFn labeled_rows_fn(uint32_t nv4) {
+static PhLabeledFn labeled_rows_fn(uint32_t nv4, bool pairs) {
   switch (ph_chunk_count(nv4)) {
-    case 1: return ph_labeled_scan_kernel<D<1, 4>>;
-    case 3: return ph_labeled_scan_kernel<D<3, 4>>;
-    case 6: return ph_labeled_scan_kernel<D<6, 4>>;
+    case 1: return pairs ? ph_labeled_scan_kernel<D<1, 4>, true> : ph_labeled_scan_kernel<D<1, 4>>;
+    case 3: return pairs ? ph_labeled_scan_kernel<D<3, 4>, true> : ph_labeled_scan_kernel<D<3, 4>>;
+    case 6: return pairs ? ph_labeled_scan_kernel<D<6, 4>, true> : ph_labeled_scan_kernel<D<6, 4>>;
     default: return nullptr;
   }
 }
-static PhLabeledFn labeled_scan_fn(const phnsw_store *s) {
+static PhLabeledFn labeled_scan_fn(const phnsw_store *s, bool pairs) {
   switch (s->kind) {
-    case PH_ROWS_PQ: return ph_labeled_scan_kernel<DistPQ>;
-    case PH_ROWS_F16: return labeled_rows_fn<DistF16>(s->ld / 4);
-    case PH_ROWS_I8: return labeled_rows_fn<DistI8>(s->ld / 4);
-    case PH_ROWS_I8Q: return labeled_rows_fn<DistI8Q>(s->ld / 4);
-    default: return labeled_rows_fn<DistF32>(s->ld / 4);
+    case PH_ROWS_PQ: return pairs ? ph_labeled_scan_kernel<DistPQ, true> : ph_labeled_scan_kernel<DistPQ>;
+    case PH_ROWS_F16: return labeled_rows_fn<DistF16>(s->ld / 4, pairs);
+    case PH_ROWS_I8: return labeled_rows_fn<DistI8>(s->ld / 4, pairs);
+    case PH_ROWS_I8Q: return labeled_rows_fn<DistI8Q>(s->ld / 4, pairs);
+    default: return labeled_rows_fn<DistF32>(s->ld / 4, pairs);
   }
 }
 template <class R>
-static PhLabeledFn labeled_tile_rows_fn(uint32_t nv4) {
+static PhLabeledFn labeled_tile_rows_fn(uint32_t nv4, bool pairs) {
   switch (ph_chunk_count(nv4)) {
-    case 1: return ph_labeled_tile_kernel<1, R>;
-    case 3: return ph_labeled_tile_kernel<3, R>;
-    case 6: return ph_labeled_tile_kernel<6, R>;
+    case 1: return pairs ? ph_labeled_tile_kernel<1, R, true> : ph_labeled_tile_kernel<1, R>;
+    case 3: return pairs ? ph_labeled_tile_kernel<3, R, true> : ph_labeled_tile_kernel<3, R>;
+    case 6: return pairs ? ph_labeled_tile_kernel<6, R, true> : ph_labeled_tile_kernel<6, R>;
     default: return nullptr;
   }
 }
 // the tile kernel of a store, nullptr where only the per-query scan serves it (i8q, PQ)
-static PhLabeledFn labeled_tile_fn(const phnsw_store *s) {
+static PhLabeledFn labeled_tile_fn(const phnsw_store *s, bool pairs) {
   switch (s->kind) {
-    case PH_ROWS_F32: return labeled_tile_rows_fn<RowF32>(s->ld / 4);
-    case PH_ROWS_F16: return labeled_tile_rows_fn<RowF16>(s->ld / 4);
-    case PH_ROWS_I8: return labeled_tile_rows_fn<RowI8>(s->ld / 4);
+    case PH_ROWS_F32: return labeled_tile_rows_fn<RowF32>(s->ld / 4, pairs);
+    case PH_ROWS_F16: return labeled_tile_rows_fn<RowF16>(s->ld / 4, pairs);
+    case PH_ROWS_I8: return labeled_tile_rows_fn<RowI8>(s->ld / 4, pairs);
     default: return nullptr;
   }
 }
@@ -548,33 +667,18 @@ const uint32_t *ph_labels_column(const phnsw_labels *lb) { return lb->label_of; 
 
 namespace {
 
-// the orchestration on a set the caller holds; c is checked, 0 < nq <= PH_LABEL_NQ_MAX (with a list: its length).
-// Enqueues and returns.
-int labeled_run(const phnsw_index *ix, const phnsw_labels *lb, const PhLabeledCall &c, PhLabeledSet &set) {
-  const phnsw_store *s = ix->store;
-  const uint64_t nq = c.nq;
-  const PhLabelPre lay = ph_label_pre(nq);
-  if (!set.done) PH_HIP(hipEventCreateWithFlags(&set.done, hipEventDisableTiming));
-  PH_TRY(block_ensure(set, &set.pre, &set.pre_bytes, (size_t)lay.words * 4u, c.stream));
-  uint32_t *const pre = (uint32_t *)set.pre;
-  PhLabeledArgs a = {};
-  a.dist = ph_dist_args(s);
-  a.queries = c.queries, a.ldq = c.ldq, a.qids = c.qids, a.exclude = c.exclude, a.want = c.want, a.list = c.list;
-  a.nq = (uint32_t)nq, a.n = (uint32_t)s->n, a.k = c.k;
-  a.values = lb->values, a.first = lb->first, a.ids = lb->ids, a.nlabels = (uint32_t)lb->nlabels;
-  a.slot = pre + lay.slot, a.iota = pre + lay.iota, a.sslot = pre + lay.sslot, a.order = pre + lay.order;
-  a.flags = pre + lay.flags, a.tidx = pre + lay.tidx, a.tile_first = pre + lay.tile_first, a.head = pre + lay.head;
-  a.out_ids = c.out_ids, a.out_d = c.out_d, a.out_len = c.out_len, a.status = c.status;
-
-  // T and the kernel: the tile kernel for T > 1 on a row store, else the per-query scan
+// T and the kernel of a call -- the tile kernel for T > 1 on a row store, else the per-query scan --, its dynamic LDS and
+// the waves of it a device holds; fills a.T and a.pq_lds.  pairs: the PAIRS instances of phnsw_search_exact_labelset.
+int labeled_kernel(const phnsw_labels *lb, const phnsw_store *s, uint32_t k, bool pairs, PhLabeledArgs &a, PhLabeledFn *fn_out,
+                   size_t *lds_out, uint64_t *resident_out) {
   const size_t pq_lds = (ph_pq_lds_bytes(s) + 15u) & ~(size_t)15u;
-  PhLabeledFn fn = labeled_scan_fn(s);
-  size_t lds = pq_lds + (size_t)ph_label_scan_lds(c.k);
+  PhLabeledFn fn = labeled_scan_fn(s, pairs);
+  size_t lds = pq_lds + (size_t)ph_label_scan_lds(k);
   a.T = 1u, a.pq_lds = (uint32_t)pq_lds;
-  if (PhLabeledFn tile = labeled_tile_fn(s)) {
-    const uint32_t T = ph_label_tile(c.k, s->ld, PH_LABEL_LDS_BYTES, env_ll("PHNSW_LABEL_TILE"));
-    if (T > 1u && ph_label_tile_lds(T, c.k, s->ld) <= PH_LABEL_LDS_BYTES) {
-      fn = tile, a.T = T, lds = (size_t)ph_label_tile_lds(T, c.k, s->ld);
+  if (PhLabeledFn tile = labeled_tile_fn(s, pairs)) {
+    const uint32_t T = ph_label_tile(k, s->ld, PH_LABEL_LDS_BYTES, env_ll("PHNSW_LABEL_TILE"));
+    if (T > 1u && ph_label_tile_lds(T, k, s->ld) <= PH_LABEL_LDS_BYTES) {
+      fn = tile, a.T = T, lds = (size_t)ph_label_tile_lds(T, k, s->ld);
     }
   }
   if (lds > 48 * 1024) PH_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -593,17 +697,48 @@ int labeled_run(const phnsw_index *ix, const phnsw_labels *lb, const PhLabeledCa
       mlb->resident.push_back(PhLabelResident{(const void *)fn, lds, resident});
     }
   }
+  *fn_out = fn, *lds_out = lds, *resident_out = resident;
+  return 0;
+}
+
+// hipCUB's temporaries for a batch of `count` positions: they depend on the count alone
+int labeled_tmp(PhLabeledSet &set, const PhLabeledArgs &a, uint32_t *sslot, uint32_t *order, uint32_t *tidx, uint64_t count,
+                hipStream_t stream) {
+  if (set.tmp_nq != count) {
+    size_t sort_bytes = 0, scan_bytes = 0;
+    PH_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, a.slot, sslot, a.iota, order, (int)count, 0, 32, stream));
+    PH_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, a.flags, tidx, (int)(count + 1u), stream));
+    set.tmp_need = std::max<size_t>(std::max(sort_bytes, scan_bytes), 16), set.tmp_nq = count;
+  }
+  return block_ensure(set, &set.tmp, &set.tmp_bytes, set.tmp_need, stream);
+}
+
+// the orchestration on a set the caller holds; c is checked, 0 < nq <= PH_LABEL_NQ_MAX (with a list: its length).
+// Enqueues and returns.
+int labeled_run(const phnsw_index *ix, const phnsw_labels *lb, const PhLabeledCall &c, PhLabeledSet &set) {
+  const phnsw_store *s = ix->store;
+  const uint64_t nq = c.nq;
+  const PhLabelPre lay = ph_label_pre(nq);
+  if (!set.done) PH_HIP(hipEventCreateWithFlags(&set.done, hipEventDisableTiming));
+  PH_TRY(block_ensure(set, &set.pre, &set.pre_bytes, (size_t)lay.words * 4u, c.stream));
+  uint32_t *const pre = (uint32_t *)set.pre;
+  PhLabeledArgs a = {};
+  a.dist = ph_dist_args(s);
+  a.queries = c.queries, a.ldq = c.ldq, a.qids = c.qids, a.exclude = c.exclude, a.want = c.want, a.list = c.list;
+  a.nq = (uint32_t)nq, a.n = (uint32_t)s->n, a.k = c.k;
+  a.values = lb->values, a.first = lb->first, a.ids = lb->ids, a.nlabels = (uint32_t)lb->nlabels;
+  a.slot = pre + lay.slot, a.iota = pre + lay.iota, a.sslot = pre + lay.sslot, a.order = pre + lay.order;
+  a.flags = pre + lay.flags, a.tidx = pre + lay.tidx, a.tile_first = pre + lay.tile_first, a.head = pre + lay.head;
+  a.out_ids = c.out_ids, a.out_d = c.out_d, a.out_len = c.out_len, a.status = c.status;
+
+  PhLabeledFn fn = nullptr;
+  size_t lds = 0;
+  uint64_t resident = 0;
+  PH_TRY(labeled_kernel(lb, s, c.k, false, a, &fn, &lds, &resident));
   // work items the host can count on: the queries, or at least ceil(nq / T) tiles
   a.slices = ph_label_slice_count((nq + a.T - 1u) / a.T, resident, lb->longest, env_ll("PHNSW_LABEL_SLICES"));
 
-  if (set.tmp_nq != nq) {  // hipCUB's temporaries depend on the batch size alone
-    size_t sort_bytes = 0, scan_bytes = 0;
-    PH_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, a.slot, pre + lay.sslot, a.iota, pre + lay.order, (int)nq, 0,
-                                              32, c.stream));
-    PH_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, a.flags, pre + lay.tidx, (int)(nq + 1u), c.stream));
-    set.tmp_need = std::max<size_t>(std::max(sort_bytes, scan_bytes), 16), set.tmp_nq = nq;
-  }
-  PH_TRY(block_ensure(set, &set.tmp, &set.tmp_bytes, set.tmp_need, c.stream));
+  PH_TRY(labeled_tmp(set, a, pre + lay.sslot, pre + lay.order, pre + lay.tidx, nq, c.stream));
   if (a.slices > 1u) {
     uint64_t bytes = 0;
     if (!ph_label_key_bytes(nq, a.slices, c.k, &bytes)) {
@@ -637,6 +772,79 @@ int labeled_run(const phnsw_index *ix, const phnsw_labels *lb, const PhLabeledCa
                        (size_t)ph_label_scan_lds(c.k), c.stream, a);
     PH_HIP(hipGetLastError());
   }
+  return 0;
+}
+
+// The request of one scan by label sets: c without `want` and `list`, the sets in CSR form (device words), nwant pairs.
+struct PhLabelsetCall {
+  PhLabeledCall c;
+  const uint32_t *want_first, *want_values;
+  uint64_t nwant;
+};
+
+// labeled_run over pairs (labelset_plan.h); c is checked, 0 < nq, nq and nwant <= PH_LABEL_NQ_MAX.  Enqueues and returns.
+int labelset_run(const phnsw_index *ix, const phnsw_labels *lb, const PhLabelsetCall &sc, PhLabeledSet &set) {
+  const phnsw_store *s = ix->store;
+  const PhLabeledCall &c = sc.c;
+  const uint64_t nq = c.nq, np = sc.nwant;  // np positions
+  const PhLabelsetPre lay = ph_labelset_pre(np);
+  if (!set.done) PH_HIP(hipEventCreateWithFlags(&set.done, hipEventDisableTiming));
+  PH_TRY(block_ensure(set, &set.pre, &set.pre_bytes, (size_t)lay.words * 4u, c.stream));
+  uint32_t *const pre = (uint32_t *)set.pre;
+  PhLabelsetArgs sa = {};
+  PhLabeledArgs &a = sa.a;
+  a.dist = ph_dist_args(s);
+  a.queries = c.queries, a.ldq = c.ldq, a.qids = c.qids, a.exclude = c.exclude;
+  a.nq = (uint32_t)np, a.n = (uint32_t)s->n, a.k = c.k, a.slices = 1u, a.T = 1u;
+  a.values = lb->values, a.first = lb->first, a.ids = lb->ids, a.nlabels = (uint32_t)lb->nlabels;
+  a.slot = pre + lay.pos.slot, a.iota = pre + lay.pos.iota, a.sslot = pre + lay.pos.sslot, a.order = pre + lay.pos.order;
+  a.flags = pre + lay.pos.flags, a.tidx = pre + lay.pos.tidx, a.tile_first = pre + lay.pos.tile_first, a.head = pre + lay.pos.head;
+  a.out_ids = c.out_ids, a.out_d = c.out_d, a.out_len = c.out_len, a.status = c.status;
+  sa.want_first = sc.want_first, sa.want_values = sc.want_values, sa.nq = (uint32_t)nq, sa.nwant = (uint32_t)np;
+  sa.owner = pre + lay.owner, sa.spair = pre + lay.spair, sa.inv = pre + lay.inv, sa.dup = pre + lay.dup;
+
+  if (np) {
+    PhLabeledFn fn = nullptr;
+    size_t lds = 0;
+    uint64_t resident = 0;
+    PH_TRY(labeled_kernel(lb, s, c.k, true, a, &fn, &lds, &resident));
+    a.slices = ph_label_slice_count((np + a.T - 1u) / a.T, resident, lb->longest, env_ll("PHNSW_LABEL_SLICES"));
+    PH_TRY(labeled_tmp(set, a, pre + lay.pos.sslot, sa.spair, pre + lay.pos.tidx, np, c.stream));
+    uint64_t bytes = 0;
+    if (!ph_labelset_key_bytes(np, a.slices, c.k, &bytes)) {
+      ph_set_error("exact labelset search: %llu wanted labels in %u slices at k = %u need more scratch than can be addressed",
+                   (unsigned long long)np, a.slices, c.k);
+      return PHNSW_E_INVALID;
+    }
+    PH_TRY(block_ensure(set, &set.keys, &set.keys_bytes, (size_t)bytes, c.stream));
+    a.scratch = (uint64_t *)set.keys;
+
+    PH_HIP(hipMemsetAsync(sa.owner, 0xFF, (size_t)np * 4u, c.stream));  // PH_LABELSET_OWNER_NONE
+    hipLaunchKernelGGL(ph_labelset_claim_kernel, dim3(grid1(nq)), dim3(256), 0, c.stream, sa);
+    PH_HIP(hipGetLastError());
+    hipLaunchKernelGGL(ph_labelset_lookup_kernel, dim3(grid1(np)), dim3(256), 0, c.stream, sa);
+    PH_HIP(hipGetLastError());
+    size_t tmp = set.tmp_bytes;
+    PH_HIP(hipcub::DeviceRadixSort::SortPairs(set.tmp, tmp, a.slot, pre + lay.pos.sslot, a.iota, sa.spair, (int)np, 0, 32,
+                                              c.stream));
+    hipLaunchKernelGGL(ph_labelset_positions_kernel, dim3(grid1(np)), dim3(256), 0, c.stream, sa, pre + lay.pos.order);
+    PH_HIP(hipGetLastError());
+    if (a.T > 1u) {
+      hipLaunchKernelGGL(ph_labeled_tileflag_kernel, dim3(grid1(np + 1u)), dim3(256), 0, c.stream, a);
+      PH_HIP(hipGetLastError());
+      tmp = set.tmp_bytes;
+      PH_HIP(hipcub::DeviceScan::ExclusiveSum(set.tmp, tmp, a.flags, pre + lay.pos.tidx, (int)(np + 1u), c.stream));
+      hipLaunchKernelGGL(ph_labeled_tiles_kernel, dim3(grid1(np + 1u)), dim3(256), 0, c.stream, a);
+      PH_HIP(hipGetLastError());
+    }
+    const uint64_t items = np * (uint64_t)a.slices;
+    hipLaunchKernelGGL(fn, dim3((uint32_t)std::min<uint64_t>(items, 1u << 20)), dim3(64), lds, c.stream, a);
+    PH_HIP(hipGetLastError());
+  }
+  // no pair at all: every sound range is empty, and the merge alone writes the rows
+  hipLaunchKernelGGL(ph_labelset_merge_kernel, dim3((uint32_t)std::min<uint64_t>(nq, 1u << 20)), dim3(64),
+                     (size_t)ph_label_scan_lds(c.k), c.stream, sa);
+  PH_HIP(hipGetLastError());
   return 0;
 }
 
@@ -943,6 +1151,164 @@ extern "C" int phnsw_search_exact_labeled(const phnsw_index *ix, const phnsw_lab
   c.out_ids = ids, c.out_d = d, c.out_len = small + 2u * nq, c.status = small + 3u * nq;
   c.stream = st;
   PH_TRY(labeled_run(ix, lb, c, *set));
+  PH_TRY(ph_take_launch(ids, d, kk, kk, nq, ids64, dk, st));  // u32 -> u64 ids, 0xFFFFFFFF -> PHNSW_EMPTY
+  PH_HIP(hipMemcpyAsync(h_len.data(), small + 2u * nq, (size_t)nq * 4u, hipMemcpyDeviceToHost, st));
+  PH_HIP(hipMemcpyAsync(out_ids, ids64, (size_t)nq * kk * 8u, hipMemcpyDeviceToHost, st));
+  PH_HIP(hipMemcpyAsync(out_d, dk, (size_t)nq * kk * 4u, hipMemcpyDeviceToHost, st));
+  PH_HIP(hipStreamSynchronize(st));
+  for (uint64_t i = 0; i < nq; i++) out_len[i] = h_len[i];
+  return 0;
+} catch (...) { return ph_caught(); }
+
+// ------------------------------------------------------------------ C ABI: a set of labels per query
+
+extern "C" int phnsw_labels_count_set_device(const phnsw_labels *lb, const uint32_t *want_first_dev,
+                                             const uint32_t *want_values_dev, uint64_t nq, uint64_t nwant,
+                                             uint32_t *out_count_dev, void *stream) try {
+  const char *const call = "phnsw_labels_count_set_device";
+  if (!lb) {
+    ph_set_error("%s: null labels", call);
+    return PHNSW_E_INVALID;
+  }
+  if (nq == 0) return 0;
+  if (!want_first_dev || !out_count_dev || (!want_values_dev && nwant)) {
+    ph_set_error("%s: null want_first, null want_values with nwant > 0, or null output", call);
+    return PHNSW_E_INVALID;
+  }
+  if (nq > PH_LABEL_NQ_MAX || nwant > PH_LABELSET_NWANT_MAX) {
+    ph_set_error("%s: nq and nwant must be below 2^31 - 1", call);
+    return PHNSW_E_INVALID;
+  }
+  PH_HIP(hipSetDevice(lb->device));
+  hipLaunchKernelGGL(ph_labelset_count_kernel, dim3((uint32_t)std::min<uint64_t>(nq, 1u << 20)), dim3(64), 0,
+                     (hipStream_t)stream, lb->values, lb->first, (uint32_t)lb->nlabels, want_first_dev, want_values_dev, nq,
+                     (uint32_t)nwant, out_count_dev);
+  PH_HIP(hipGetLastError());
+  return 0;
+} catch (...) { return ph_caught(); }
+
+extern "C" int phnsw_search_exact_labelset_device(const phnsw_index *ix, const phnsw_labels *lb, const float *queries_dev,
+                                                  uint32_t ldq, const uint32_t *qids_dev, uint64_t nq,
+                                                  const uint32_t *exclude_dev, const uint32_t *want_first_dev,
+                                                  const uint32_t *want_values_dev, uint64_t nwant, uint64_t k,
+                                                  uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                                  uint32_t *status_dev, void *stream) try {
+  const char *const call = "phnsw_search_exact_labelset_device";
+  PH_TRY(ph_labeled_check(ix, lb, k, call));
+  if (nq == 0) return 0;
+  if (((!queries_dev) == (!qids_dev)) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev || !want_first_dev ||
+      (!want_values_dev && nwant) || (queries_dev && (ldq < ix->store->ld || (ldq % 4) || ((uintptr_t)queries_dev % 16)))) {
+    ph_set_error("%s: invalid argument (queries or qids, exactly one; outputs; want_first; want_values unless nwant is 0; "
+                 "queries need ldq >= store ld, multiple of 4, 16-byte base)", call);
+    return PHNSW_E_INVALID;
+  }
+  if (nq > PH_LABEL_NQ_MAX || nwant > PH_LABELSET_NWANT_MAX) {
+    ph_set_error("%s: nq and nwant must be below 2^31 - 1", call);
+    return PHNSW_E_INVALID;
+  }
+  PhLabelsetCall sc = {};
+  PhLabeledCall &c = sc.c;
+  c.queries = queries_dev, c.ldq = ldq, c.qids = qids_dev, c.exclude = exclude_dev, c.nq = nq, c.k = (uint32_t)k;
+  c.out_ids = out_ids_dev, c.out_d = out_d_dev, c.out_len = out_len_dev, c.status = status_dev;
+  c.stream = (hipStream_t)stream;
+  sc.want_first = want_first_dev, sc.want_values = want_values_dev, sc.nwant = nwant;
+  PH_HIP(hipSetDevice(ix->store->device));
+  phnsw_labels *mlb = const_cast<phnsw_labels *>(lb);
+  PhLabeledSet *set = set_acquire(mlb, c.stream, false);
+  SetGuard guard{mlb, set, c.stream};
+  return labelset_run(ix, lb, sc, *set);
+} catch (...) { return ph_caught(); }
+
+extern "C" int phnsw_search_exact_labelset(const phnsw_index *ix, const phnsw_labels *lb, const float *queries,
+                                           const uint64_t *qids, uint64_t nq, const uint64_t *exclude,
+                                           const uint32_t *want_first, const uint32_t *want_values, uint64_t k,
+                                           uint64_t *out_ids, float *out_d, uint64_t *out_len) try {
+  const char *const call = "phnsw_search_exact_labelset";
+  PH_TRY(ph_labeled_check(ix, lb, k, call));
+  if (nq == 0) return 0;
+  if ((!queries) == (!qids)) {
+    ph_set_error("%s: pass queries or qids (exactly one)", call);
+    return PHNSW_E_INVALID;
+  }
+  if (!out_ids || !out_d || !out_len || !want_first || nq > PH_LABEL_NQ_MAX) {
+    ph_set_error("%s: invalid argument (outputs; want_first; nq < 2^31 - 1)", call);
+    return PHNSW_E_INVALID;
+  }
+  const uint64_t nwant = want_first[nq];
+  if ((!want_values && nwant) || nwant > PH_LABELSET_NWANT_MAX) {
+    ph_set_error("%s: invalid argument (want_values unless want_first[nq] is 0; want_first[nq] < 2^31 - 1)", call);
+    return PHNSW_E_INVALID;
+  }
+  const phnsw_store *s = ix->store;
+  PH_HIP(hipSetDevice(s->device));
+  if (qids)
+    for (uint64_t i = 0; i < nq; i++)
+      if (qids[i] >= s->n) {
+        ph_set_error("%s: query %llu: stored query id %llu out of range", call, (unsigned long long)i,
+                     (unsigned long long)qids[i]);
+        return PHNSW_E_INVALID;
+      }
+  if (const uint64_t bad = ph_labelset_first_bad(want_first, nq); bad < nq) {
+    ph_set_error("%s: query %llu: want_first must start at 0 and never run backwards (want_first[%llu] = %u, want_first[%llu] "
+                 "= %u)", call, (unsigned long long)bad, (unsigned long long)bad, want_first[bad], (unsigned long long)bad + 1u,
+                 want_first[bad + 1u]);
+    return PHNSW_E_INVALID;
+  }
+  // host words of the per-query ids, alive until the stream has drained (HostBlocks is declared after them)
+  std::vector<uint32_t> h_in, h_len(nq);
+  phnsw_labels *mlb = const_cast<phnsw_labels *>(lb);
+  PhLabeledSet *set = set_acquire(mlb, nullptr, true);
+  if (!set->stream) {
+    hipError_t e = hipStreamCreateWithFlags(&set->stream, hipStreamNonBlocking);
+    if (e != hipSuccess) {
+      SetGuard g{mlb, set, nullptr};
+      return ph_hip_fail(e, "host path: stream", __FILE__, __LINE__);
+    }
+  }
+  const hipStream_t st = set->stream;
+  SetGuard guard{mlb, set, st};
+  HostBlocks hb{st, {}};
+
+  PhLabelsetCall sc = {};
+  PhLabeledCall &c = sc.c;
+  const uint32_t ld = s->ld, kk = (uint32_t)k;
+  if (queries) {  // rows padded to the store's row length
+    float *q = nullptr;
+    PH_TRY(hb.alloc(&q, (size_t)nq * ld * 4u));
+    if (ld != s->dim) {
+      PH_HIP(hipMemsetAsync(q, 0, (size_t)nq * ld * 4u, st));
+      PH_HIP(hipMemcpy2DAsync(q, (size_t)ld * 4u, queries, (size_t)s->dim * 4u, (size_t)s->dim * 4u, nq, hipMemcpyHostToDevice, st));
+    } else {
+      PH_HIP(hipMemcpyAsync(q, queries, (size_t)nq * ld * 4u, hipMemcpyHostToDevice, st));
+    }
+    c.queries = q, c.ldq = ld;
+  }
+  uint32_t *small = nullptr;  // qid | exclude | len | status | want_first [nq + 1] | want_values [nwant]
+  PH_TRY(hb.alloc(&small, ((size_t)nq * 5u + 1u + (size_t)nwant) * 4u));
+  if (qids || exclude) {
+    h_in.resize(2u * nq);
+    if (qids)
+      for (uint64_t i = 0; i < nq; i++) h_in[i] = (uint32_t)qids[i];
+    if (exclude)
+      for (uint64_t i = 0; i < nq; i++) h_in[nq + i] = exclude[i] >= s->n ? PH_EMPTY32 : (uint32_t)exclude[i];
+    PH_HIP(hipMemcpyAsync(small, h_in.data(), (size_t)nq * 2u * 4u, hipMemcpyHostToDevice, st));
+    if (qids) c.qids = small;
+    if (exclude) c.exclude = small + nq;
+  }
+  PH_HIP(hipMemcpyAsync(small + 4u * nq, want_first, (size_t)(nq + 1u) * 4u, hipMemcpyHostToDevice, st));
+  if (nwant) PH_HIP(hipMemcpyAsync(small + 5u * nq + 1u, want_values, (size_t)nwant * 4u, hipMemcpyHostToDevice, st));
+  sc.want_first = small + 4u * nq, sc.want_values = small + 5u * nq + 1u, sc.nwant = nwant;
+  uint32_t *ids = nullptr;
+  float *d = nullptr, *dk = nullptr;
+  uint64_t *ids64 = nullptr;
+  PH_TRY(hb.alloc(&ids, (size_t)nq * kk * 4u));
+  PH_TRY(hb.alloc(&d, (size_t)nq * kk * 4u));
+  PH_TRY(hb.alloc(&ids64, (size_t)nq * kk * 8u));
+  PH_TRY(hb.alloc(&dk, (size_t)nq * kk * 4u));
+  c.nq = nq, c.k = kk;
+  c.out_ids = ids, c.out_d = d, c.out_len = small + 2u * nq, c.status = small + 3u * nq;
+  c.stream = st;
+  PH_TRY(labelset_run(ix, lb, sc, *set));
   PH_TRY(ph_take_launch(ids, d, kk, kk, nq, ids64, dk, st));  // u32 -> u64 ids, 0xFFFFFFFF -> PHNSW_EMPTY
   PH_HIP(hipMemcpyAsync(h_len.data(), small + 2u * nq, (size_t)nq * 4u, hipMemcpyDeviceToHost, st));
   PH_HIP(hipMemcpyAsync(out_ids, ids64, (size_t)nq * kk * 8u, hipMemcpyDeviceToHost, st));

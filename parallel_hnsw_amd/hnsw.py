@@ -127,6 +127,49 @@ def pack_labels(values, count, what):
     return np.ascontiguousarray(a, dtype=np.uint32)
 
 
+LABELSET_NWANT_MAX = 0x7FFFFFFE  # wanted labels of one call by label sets
+
+
+def pack_label_sets(want, nq):
+    """the sets of wanted labels of search_exact_labelset -> CSR (first u32 [nq + 1], values u32 [nwant]): query i wants
+    values[first[i]:first[i + 1]].  want: a sequence of nq integer sequences (empty ones included), or a ready (first,
+    values) pair of arrays.  Values as pack_labels takes them: within u32, -1 or LABEL_NONE = none"""
+    if want is None:
+        raise ValueError("want: %d sets of labels are required" % nq)
+    ready = (isinstance(want, tuple) and len(want) == 2 and all(isinstance(x, np.ndarray) for x in want))
+    if ready:
+        first, values = want
+        if first.dtype.kind not in "iu":
+            raise TypeError("want: integer offsets, got %s" % first.dtype)
+        if first.ndim != 1 or first.shape[0] != nq + 1:
+            raise ValueError("want: offsets of shape [%d] (nq + 1), got %r" % (nq + 1, first.shape))
+        first = first.astype(np.int64)
+    else:
+        sets = list(want)
+        if len(sets) != nq:
+            raise ValueError("want: %d sets of labels (one per query), got %d" % (nq, len(sets)))
+        rows = []
+        for i, s in enumerate(sets):
+            if np.ndim(s) != 1:
+                raise ValueError("want: set %d is not a sequence of labels" % i)
+            rows.append(np.asarray(s) if len(s) else np.zeros(0, dtype=np.int64))
+        first = np.zeros(nq + 1, dtype=np.int64)
+        np.cumsum([len(r) for r in rows], out=first[1:])
+        for i, r in enumerate(rows):
+            if r.dtype.kind not in "iu":
+                raise TypeError("want: set %d: integer labels, got %s" % (i, r.dtype))
+        if any(r.dtype == np.uint64 and (r > LABEL_NONE).any() for r in rows):
+            raise ValueError("want: labels are 32-bit values, -1 or LABEL_NONE")
+        values = np.concatenate([r.astype(np.int64) for r in rows]) if rows else np.zeros(0, dtype=np.int64)
+    if first[0] != 0 or (np.diff(first) < 0).any():
+        bad = 0 if first[0] != 0 else int(np.flatnonzero(np.diff(first) < 0)[0])
+        raise ValueError("want: offsets start at 0 and never run backwards (query %d)" % bad)
+    if first[-1] > LABELSET_NWANT_MAX:
+        raise ValueError("want: at most 2^31 - 2 wanted labels in one call")
+    values = pack_labels(values, int(first[-1]), "want values")
+    return np.ascontiguousarray(first, dtype=np.uint32), values
+
+
 class Labels:
     """phnsw_labels: one label per vector of `hnsw`'s store, turned once into posting lists on the device (the ascending
     VectorIds of every label).  labels: an integer array [n] within u32; -1 or LABEL_NONE = the vector is not listed.  A
@@ -186,6 +229,28 @@ class Labels:
         self.count_device(len(w), wd.data_ptr(), out.data_ptr())
         torch.cuda.synchronize(dev)
         return out.cpu().numpy().view(np.uint32)[:len(w)]
+
+    def count_set_device(self, nq, nwant, want_first, want_values, out_count, stream=0):
+        """phnsw_labels_count_set_device: device pointers as integers; want_first u32 [nq + 1], want_values u32 [nwant],
+        out_count u32 [nq]"""
+        check(lib().phnsw_labels_count_set_device(self._h, C.c_void_p(want_first or None), C.c_void_p(want_values or None),
+                                                  int(nq), int(nwant), C.c_void_p(out_count or None),
+                                                  C.c_void_p(stream or None)))
+
+    def count_sets(self, want):
+        """per set of wanted labels (pack_label_sets) the summed list lengths of its DISTINCT labels, u32 [nq]:
+        filter_count's figure for the equivalent bitmaps.  Host convenience over count_set_device (needs torch)"""
+        import torch
+        nq = len(want[0]) - 1 if isinstance(want, tuple) else len(want)
+        first, values = pack_label_sets(want, nq)
+        dev = torch.device("cuda", getattr(self.hnsw.store, "device", 0))
+        fd = torch.from_numpy(first.view(np.int32)).to(dev)
+        vd = torch.from_numpy(values.view(np.int32)).to(dev) if len(values) else None
+        out = torch.zeros(max(nq, 1), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.count_set_device(nq, len(values), fd.data_ptr(), 0 if vd is None else vd.data_ptr(), out.data_ptr())
+        torch.cuda.synchronize(dev)
+        return out.cpu().numpy().view(np.uint32)[:nq]
 
     def close(self):
         if getattr(self, "_h", None):
@@ -988,6 +1053,48 @@ class Hnsw:
             self._h, labels._h, C.c_void_p(queries or None), ldq, C.c_void_p(qids or None), nq, C.c_void_p(exclude or None),
             C.c_void_p(want or None), int(k), C.c_void_p(out_ids), C.c_void_p(out_d), C.c_void_p(out_len), C.c_void_p(status),
             C.c_void_p(stream or None)))
+
+    def search_exact_labelset(self, queries=None, qids=None, labels=None, want=None, exclude=None, k=10):
+        """search_exact_labeled for a SET of labels per query, `label IN (a, b, c)` (phnsw_search_exact_labelset): query i
+        may return the vectors `labels` lists under any label of want[i] -- the same rows as
+        search_exact_filtered(allow=(label column in want[i])), bit for bit.  want: as pack_label_sets takes it; an empty
+        set, LABEL_NONE and labels nobody carries give nothing, a label twice counts once.  Exactly one of queries / qids.
+        Exact scan only: there is no graph walk and no routed call by set.
+        Returns (ids[nq, k] u64, d[nq, k] f32, len[nq])"""
+        if (queries is None) == (qids is None):
+            raise ValueError("search_exact_labelset: pass queries or qids (exactly one)")
+        if not isinstance(labels, Labels):
+            raise TypeError("search_exact_labelset: labels must be a Labels made for this index")
+        q = qi = None
+        if queries is not None:
+            q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+            assert q.shape[1] == self.store.dim
+            nq = q.shape[0]
+        else:
+            qi = np.ascontiguousarray(qids, dtype=np.uint64)
+            nq = len(qi)
+        first, values = pack_label_sets(want, nq)
+        w = max(int(k), 0)
+        ids = np.empty((nq, w), dtype=np.uint64)
+        d = np.empty((nq, w), dtype=np.float32)
+        ln = np.zeros(nq, dtype=np.uint64)
+        ex = None if exclude is None else np.ascontiguousarray(exclude, dtype=np.uint64)
+        check(lib().phnsw_search_exact_labelset(self._h, labels._h, _p(q), _p(qi), nq, _p(ex), _p(first),
+                                                _p(values) if len(values) else None, int(k), _p(ids), _p(d), _p(ln)))
+        return ids, d, ln
+
+    def search_exact_labelset_device(self, labels, nq, nwant, k, out_ids, out_d, out_len, status, queries=0, ldq=0, qids=0,
+                                     exclude=0, want_first=0, want_values=0, stream=0):
+        """zero-copy form (phnsw_search_exact_labelset_device): device pointers as integers, u32 ids [nq, k] padded with
+        0xFFFFFFFF; want_first = u32 offsets [nq + 1], want_values = u32 labels [nwant].  status 4 = a stored query id at
+        or past n, 8 = a range of want_first that is not sound (empty rows).  Enqueued on `stream`; never synchronises
+        it"""
+        if not isinstance(labels, Labels):
+            raise TypeError("search_exact_labelset_device: labels must be a Labels made for this index")
+        check(lib().phnsw_search_exact_labelset_device(
+            self._h, labels._h, C.c_void_p(queries or None), ldq, C.c_void_p(qids or None), nq, C.c_void_p(exclude or None),
+            C.c_void_p(want_first or None), C.c_void_p(want_values or None), int(nwant), int(k), C.c_void_p(out_ids),
+            C.c_void_p(out_d), C.c_void_p(out_len), C.c_void_p(status), C.c_void_p(stream or None)))
 
     def _labeled_args(self, call, queries, qids, labels, want):
         """the checks the calls by label make before they reach the library: a Labels, exactly one of queries / qids,

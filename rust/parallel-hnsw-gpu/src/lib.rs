@@ -251,6 +251,17 @@ impl GpuLabels {
     pub unsafe fn count_device(&self, want_dev: *const u32, nq: u64, out_count_dev: *mut u32, stream: *mut c_void) {
         check(sys::phnsw_labels_count_device(self.lb, want_dev, nq, out_count_dev, stream));
     }
+
+    /// per query the summed list lengths of the distinct labels of its set (`phnsw_labels_count_set_device`); the sets
+    /// in CSR form
+    ///
+    /// # Safety
+    /// `want_first_dev` (`nq + 1` u32), `want_values_dev` (`nwant` u32) and `out_count_dev` (`nq` u32) must be valid
+    /// device allocations
+    pub unsafe fn count_set_device(&self, want_first_dev: *const u32, want_values_dev: *const u32, nq: u64, nwant: u64,
+                                   out_count_dev: *mut u32, stream: *mut c_void) {
+        check(sys::phnsw_labels_count_set_device(self.lb, want_first_dev, want_values_dev, nq, nwant, out_count_dev, stream));
+    }
 }
 
 impl GpuHnsw {
@@ -647,6 +658,52 @@ impl GpuHnsw {
                                               status_dev: *mut u32, stream: *mut c_void) {
         check(sys::phnsw_search_exact_labeled_device(self.ix, labels.lb, queries_dev, ldq, qids_dev, nq, exclude_dev, want_dev, k,
                                                      out_ids_dev, out_d_dev, out_len_dev, status_dev, stream));
+    }
+
+    /// `search_many_exact_labeled` for a set of labels per query (`phnsw_search_exact_labelset`): query i may return the
+    /// vectors `labels` lists under any label of `want[i]`; an empty set and labels nobody carries give nothing, a label
+    /// twice counts once.  The same results, bit for bit, as the predicates `label of v in want[i]` give.  Exact scan
+    /// only: there is no graph walk by set.  Panics unless 1 <= k <= 1024 and `want` has one set per query
+    pub fn search_many_exact_labelset(&self, queries: &[Vec<f32>], k: usize, labels: &GpuLabels, want: &[Vec<u32>])
+                                      -> Vec<Vec<(VectorId, f32)>> {
+        assert!((1..=1024).contains(&k), "search_many_exact_labelset: k must be 1..1024");
+        let nq = queries.len();
+        assert!(want.len() == nq, "search_many_exact_labelset: one set of wanted labels per query");
+        let mut first: Vec<u32> = Vec::with_capacity(nq + 1);
+        let mut values: Vec<u32> = Vec::new();
+        first.push(0);
+        for s in want {
+            values.extend_from_slice(s);
+            assert!(values.len() <= 0x7FFF_FFFE, "search_many_exact_labelset: too many wanted labels");
+            first.push(values.len() as u32);
+        }
+        let mut q: Vec<f32> = Vec::with_capacity(nq * queries.first().map_or(0, |x| x.len()));
+        for x in queries {
+            q.extend_from_slice(x);
+        }
+        let (mut ids, mut d, mut len) = (vec![0u64; nq * k], vec![0f32; nq * k], vec![0u64; nq]);
+        check(unsafe {
+            sys::phnsw_search_exact_labelset(self.ix, labels.lb, q.as_ptr(), std::ptr::null(), nq as u64, std::ptr::null(),
+                                             first.as_ptr(), values.as_ptr(), k as u64, ids.as_mut_ptr(), d.as_mut_ptr(),
+                                             len.as_mut_ptr())
+        });
+        (0..nq).map(|i| (0..len[i] as usize).map(|j| (VectorId(ids[i * k + j] as usize), d[i * k + j])).collect()).collect()
+    }
+
+    /// zero-copy form (`phnsw_search_exact_labelset_device`): the sets in CSR form; status 8 = a range of
+    /// `want_first_dev` that is not sound; enqueued on `stream`, never synchronises it
+    ///
+    /// # Safety
+    /// the pointers must be valid device allocations of the sizes `phnsw.h` documents for the call
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn search_exact_labelset_device(&self, labels: &GpuLabels, queries_dev: *const f32, ldq: u32,
+                                               qids_dev: *const u32, nq: u64, exclude_dev: *const u32,
+                                               want_first_dev: *const u32, want_values_dev: *const u32, nwant: u64, k: u64,
+                                               out_ids_dev: *mut u32, out_d_dev: *mut f32, out_len_dev: *mut u32,
+                                               status_dev: *mut u32, stream: *mut c_void) {
+        check(sys::phnsw_search_exact_labelset_device(self.ix, labels.lb, queries_dev, ldq, qids_dev, nq, exclude_dev,
+                                                      want_first_dev, want_values_dev, nwant, k, out_ids_dev, out_d_dev,
+                                                      out_len_dev, status_dev, stream));
     }
 
     /// `search_many_filtered` by row label (`phnsw_search_batch_labeled`): the graph walk of query i restricted to the
