@@ -27,17 +27,12 @@
 
 #include "filter_candidate.h"
 #include "filter_route.h"
+#include "host_call.h"
 #include "phnsw_device.h"
 
 static_assert(PH_ROUTE_GRAPH == PHNSW_ROUTE_GRAPH && PH_ROUTE_SCAN == PHNSW_ROUTE_SCAN &&
                   PH_ROUTE_GRAPH_THEN_SCAN == PHNSW_ROUTE_GRAPH_THEN_SCAN,
               "filter_route.h and phnsw.h name the same routes");
-
-#define PH_TRY(x)          \
-  do {                     \
-    int rc__ = (x);        \
-    if (rc__) return rc__; \
-  } while (0)
 
 struct PhAutoArgs {
   uint32_t nq, n, k, ef;
@@ -150,58 +145,14 @@ __global__ __launch_bounds__(64) void ph_auto_finish_kernel(PhAutoArgs a) {
 
 // ------------------------------------------------------------------ a call's scratch
 
-// Kept with the index, one set per call in flight: nothing goes back to the pool while work that uses it may still be
-// enqueued, whichever way a call ends.  `done` closes the last call that used the set; the next one's stream waits.
-struct PhAutoSet {
-  uint32_t *block = nullptr;
-  size_t words = 0;
-  hipEvent_t done = nullptr;
-  uint32_t *h_head = nullptr;    // pinned: the list lengths as the host reads them
-  hipStream_t stream = nullptr;  // the host form's
-  bool in_use = false;
+// A PhCallSet (call_set.h) of the index's `autos` pool.
+struct PhAutoSet : PhCallSet {
+  void *block = nullptr;
+  size_t bytes = 0;
+  uint32_t *h_head = nullptr;  // pinned: the list lengths as the host reads them
 };
 
 namespace {
-
-PhAutoSet *set_acquire(phnsw_index *ix) {
-  std::lock_guard<std::mutex> g(ix->auto_mutex);
-  for (PhAutoSet *s : ix->autos)
-    if (!s->in_use) {
-      s->in_use = true;
-      return s;
-    }
-  PhAutoSet *s = new PhAutoSet();
-  s->in_use = true;
-  ix->autos.push_back(s);
-  return s;
-}
-struct SetGuard {
-  phnsw_index *ix;
-  PhAutoSet *set;
-  hipStream_t stream;
-  ~SetGuard() {
-    if (set->done) hipEventRecord(set->done, stream);
-    std::lock_guard<std::mutex> g(ix->auto_mutex);
-    set->in_use = false;
-  }
-};
-
-int set_ensure(PhAutoSet &s, size_t words, hipStream_t stream) {
-  if (!s.done) PH_HIP(hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
-  if (!s.h_head) PH_HIP(hipHostMalloc((void **)&s.h_head, PH_AUTO_HEAD_WORDS * 4u, hipHostMallocDefault));
-  if (s.words < words) {
-    if (s.block) {
-      PH_HIP(hipEventSynchronize(s.done));  // the block goes back to the pool: nothing may still use it
-      ph_pool_free(s.block);
-      s.block = nullptr, s.words = 0;
-    }
-    PH_HIP(ph_pool_alloc((void **)&s.block, words * 4u));
-    s.words = words;
-  } else {
-    PH_HIP(hipStreamWaitEvent(stream, s.done, 0));
-  }
-  return 0;
-}
 
 // the orchestration on a set the caller holds; c is checked
 int auto_run(const phnsw_index *ix, const PhAutoCall &c, PhAutoSet &set) {
@@ -210,9 +161,11 @@ int auto_run(const phnsw_index *ix, const PhAutoCall &c, PhAutoSet &set) {
   const uint32_t ef = (uint32_t)c.sp->number_of_candidates;
   const bool by_label = c.labels != nullptr;
   const bool per_query = by_label || (c.filter.words && c.filter.stride != 0u);
-  PH_TRY(set_ensure(set, (size_t)ph_auto_scratch_words(nq, per_query, ef), c.stream));
+  PH_TRY(set.ready());
+  if (!set.h_head) PH_HIP(hipHostMalloc((void **)&set.h_head, PH_AUTO_HEAD_WORDS * 4u, hipHostMallocDefault));
+  PH_TRY(set.block_ensure(&set.block, &set.bytes, (size_t)ph_auto_scratch_words(nq, per_query, ef) * 4u, c.stream));
   const uint64_t nb = ph_auto_bitmaps(nq, per_query);
-  uint32_t *const head = set.block, *const counts = head + PH_AUTO_HEAD_WORDS, *const glist = counts + nb;
+  uint32_t *const head = (uint32_t *)set.block, *const counts = head + PH_AUTO_HEAD_WORDS, *const glist = counts + nb;
   uint32_t *const slist = glist + ph_auto_list_words(nq), *const route_own = slist + ph_auto_list_words(nq);
   uint32_t *const walk_len = route_own + nq, *const walk_ids = walk_len + nq;
   float *const walk_d = (float *)(walk_ids + nq * ef);
@@ -290,46 +243,20 @@ int auto_check(const phnsw_index *ix, const phnsw_search_params *sp, uint64_t k,
   return ph_exact_supported(ix, (uint32_t)k);
 }
 
-// device blocks of one host call: handed back only after the stream they were used on has drained, whichever way the
-// call ends
-struct HostBlocks {
-  hipStream_t stream;
-  std::vector<void *> blocks;
-  template <class T>
-  int alloc(T **p, size_t bytes) {
-    void *v = nullptr;
-    PH_HIP(ph_pool_alloc(&v, std::max<size_t>(bytes, 4)));
-    blocks.push_back(v);
-    *p = (T *)v;
-    return 0;
-  }
-  ~HostBlocks() {
-    hipStreamSynchronize(stream);
-    for (void *b : blocks) ph_pool_free(b);
-  }
-};
-
 }  // namespace
 
 void ph_auto_free(phnsw_index *ix) {
-  for (PhAutoSet *s : ix->autos) {
-    if (s->done) {
-      hipEventSynchronize(s->done);
-      hipEventDestroy(s->done);
-    }
-    if (s->block) ph_pool_free(s->block);
-    if (s->h_head) hipHostFree(s->h_head);
-    if (s->stream) hipStreamDestroy(s->stream);
-    delete s;
-  }
-  ix->autos.clear();
+  ph_sets_free<PhAutoSet>(ix->autos, [](PhAutoSet &s) {
+    if (s.block) ph_pool_free(s.block);
+    if (s.h_head) hipHostFree(s.h_head);
+  });
 }
 
 int ph_auto_device(const phnsw_index *ix, const PhAutoCall &c) {
   if (c.nq == 0) return 0;
   phnsw_index *mix = const_cast<phnsw_index *>(ix);
-  PhAutoSet *set = set_acquire(mix);
-  SetGuard guard{mix, set, c.stream};
+  PhAutoSet *set = ph_set_acquire<PhAutoSet>(mix->autos);
+  PhSetGuard guard{mix->autos, set, c.stream};
   return auto_run(ix, c, *set);
 }
 
@@ -375,89 +302,38 @@ static int auto_host(const char *call, const phnsw_index *ix, const phnsw_labels
   PhFilter hf = {};
   if (!lb) PH_TRY(ph_filter_check(ix, filter, filter_stride_words, 0u, call, &hf));
   const phnsw_store *s = ix->store;
-  if (qids)
-    for (uint64_t i = 0; i < nq; i++)
-      if (qids[i] >= s->n) {
-        ph_set_error("search: stored query id %llu out of range", (unsigned long long)qids[i]);
-        return PHNSW_E_INVALID;
-      }
+  PH_TRY(ph_stored_ids_check(qids, nq, s->n, "search"));
   PH_HIP(hipSetDevice(s->device));
-  // host words of the per-query ids, alive until the stream has drained (HostBlocks is declared after them)
-  std::vector<uint32_t> h_in, h_out(3u * nq);
   phnsw_index *mix = const_cast<phnsw_index *>(ix);
-  PhAutoSet *set = set_acquire(mix);
-  if (!set->stream) {
-    hipError_t e = hipStreamCreateWithFlags(&set->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-      SetGuard g{mix, set, nullptr};
-      return ph_hip_fail(e, "host path: stream", __FILE__, __LINE__);
-    }
-  }
-  const hipStream_t st = set->stream;
-  SetGuard guard{mix, set, st};
-  HostBlocks hb{st, {}};
-
+  PhAutoSet *set = ph_set_acquire<PhAutoSet>(mix->autos);
+  PhHostCall h(mix->autos, set);
+  PH_TRY(h.stage_in(s, queries, qids, exclude, nq, (size_t)nq * 2u, 1, (uint32_t)k, (uint32_t)k));  // extras: route | want
   PhAutoCall c = {};
-  const uint32_t ld = s->ld, kk = (uint32_t)k;
-  if (queries) {  // rows padded to the store's row length
-    float *q = nullptr;
-    PH_TRY(hb.alloc(&q, (size_t)nq * ld * 4u));
-    if (ld != s->dim) {
-      PH_HIP(hipMemsetAsync(q, 0, (size_t)nq * ld * 4u, st));
-      PH_HIP(hipMemcpy2DAsync(q, (size_t)ld * 4u, queries, (size_t)s->dim * 4u, (size_t)s->dim * 4u, nq, hipMemcpyHostToDevice, st));
-    } else {
-      PH_HIP(hipMemcpyAsync(q, queries, (size_t)nq * ld * 4u, hipMemcpyHostToDevice, st));
-    }
-    c.queries = q, c.ldq = ld;
-  }
-  uint32_t *small = nullptr;  // qid | exclude | len | status | route | want   [6][nq]
-  PH_TRY(hb.alloc(&small, (size_t)nq * 6u * 4u));
-  if (qids || exclude) {
-    h_in.resize(2u * nq);
-    if (qids)
-      for (uint64_t i = 0; i < nq; i++) h_in[i] = (uint32_t)qids[i];
-    if (exclude)
-      for (uint64_t i = 0; i < nq; i++) h_in[nq + i] = exclude[i] >= s->n ? PH_EMPTY32 : (uint32_t)exclude[i];
-    PH_HIP(hipMemcpyAsync(small, h_in.data(), (size_t)nq * 2u * 4u, hipMemcpyHostToDevice, st));
-    if (qids) c.qids = small;
-    if (exclude) c.exclude = small + nq;
-  }
+  h.fill(c);
   c.filter = hf;
   if (lb) {  // the description of a call by label: 4 bytes per query
-    PH_HIP(hipMemcpyAsync(small + 5u * nq, want, (size_t)nq * 4u, hipMemcpyHostToDevice, st));
-    c.labels = lb, c.want = small + 5u * nq;
+    uint32_t *const want_dev = h.extra() + nq;
+    PH_HIP(hipMemcpyAsync(want_dev, want, (size_t)nq * 4u, hipMemcpyHostToDevice, h.st));
+    c.labels = lb, c.want = want_dev;
   } else if (hf.words) {  // whole strides, as phnsw_search_batch_filtered copies them
     const size_t words = hf.stride ? (size_t)nq * hf.stride : (size_t)((s->n + 31u) / 32u);
     uint32_t *f = nullptr;
-    PH_TRY(hb.alloc(&f, words * 4u));
-    PH_HIP(hipMemcpyAsync(f, hf.words, words * 4u, hipMemcpyHostToDevice, st));
+    PH_TRY(h.blocks.alloc(&f, words * 4u));
+    PH_HIP(hipMemcpyAsync(f, hf.words, words * 4u, hipMemcpyHostToDevice, h.st));
     c.filter.words = f;
   } else {
     c.filter.words = ix->default_filter;  // phnsw_index_set_filter_device: device words
   }
-  uint32_t *ids = nullptr;
-  float *d = nullptr, *dk = nullptr;
-  uint64_t *ids64 = nullptr;
-  PH_TRY(hb.alloc(&ids, (size_t)nq * kk * 4u));
-  PH_TRY(hb.alloc(&d, (size_t)nq * kk * 4u));
-  PH_TRY(hb.alloc(&ids64, (size_t)nq * kk * 8u));
-  PH_TRY(hb.alloc(&dk, (size_t)nq * kk * 4u));
-  c.nq = nq, c.sp = sp, c.k = kk, c.scan_below = scan_below;
-  c.out_ids = ids, c.out_d = d, c.out_len = small + 2u * nq, c.status = small + 3u * nq, c.out_route = small + 4u * nq;
-  c.stream = st;
+  c.sp = sp, c.k = (uint32_t)k, c.scan_below = scan_below, c.out_route = h.extra();
   PH_TRY(auto_run(ix, c, *set));
-  PH_TRY(ph_take_launch(ids, d, kk, kk, nq, ids64, dk, st));  // u32 -> u64 ids, 0xFFFFFFFF -> PHNSW_EMPTY
-  PH_HIP(hipMemcpyAsync(h_out.data(), small + 2u * nq, (size_t)nq * 3u * 4u, hipMemcpyDeviceToHost, st));
-  PH_HIP(hipMemcpyAsync(out_ids, ids64, (size_t)nq * kk * 8u, hipMemcpyDeviceToHost, st));
-  PH_HIP(hipMemcpyAsync(out_d, dk, (size_t)nq * kk * 4u, hipMemcpyDeviceToHost, st));
-  PH_HIP(hipStreamSynchronize(st));
+  PH_TRY(h.finish(out_ids, out_d, nullptr));
   for (uint64_t i = 0; i < nq; i++) {
-    if (h_out[nq + i] != 0u) {  // the ids were checked: what is left is the walk's own failure
+    if (h.status(i) != 0u) {  // the ids were checked: what is left is the walk's own failure
       ph_set_error("search: a candidate vector is missing from a lower layer (layers not nested, lib.rs:261)");
       return PHNSW_E_MISSING_NODE;
     }
-    out_len[i] = h_out[i];
-    if (out_route) out_route[i] = h_out[2u * nq + i];
+    out_len[i] = h.len(i);
+    if (out_route) out_route[i] = h.read_extra(0, i);
   }
   return 0;
 }

@@ -29,13 +29,8 @@
 #include "exact_slices.h"
 #include "exact_topk.h"
 #include "filter_candidate.h"
+#include "host_call.h"
 #include "phnsw_device.h"
-
-#define PH_TRY(x)          \
-  do {                     \
-    int rc__ = (x);        \
-    if (rc__) return rc__; \
-  } while (0)
 
 // ------------------------------------------------------------------ the candidate list
 
@@ -169,20 +164,15 @@ __global__ __launch_bounds__(64) void ph_dense_select_kernel(PhDenseSelectArgs a
 
 // ------------------------------------------------------------------ a call's scratch
 
-// Kept with the index, one set per call in flight, after the pattern of the routed call's (filter_auto.hip): nothing goes
-// back to the pool while work that uses it may still be enqueued, whichever way a call ends.  `done` closes the last call
-// that used the set; the next one's stream waits.  Of `ws` only the tiny_* operand fields are used (tiny_table's packed
-// operands and their key): the search launches' workspaces, with their mutex and alternation, are not touched.
-struct PhDenseSet {
-  uint32_t *pre = nullptr;  // sized before the count is known (dense_plan.h)
-  size_t pre_words = 0;
+// A PhCallSet (call_set.h) of the index's `denses` pool.  Of `ws` only the tiny_* operand fields are used (tiny_table's
+// packed operands and their key): the search launches' workspaces, with their mutex and alternation, are not touched.
+struct PhDenseSet : PhCallSet {
+  void *pre = nullptr;  // sized before the count is known (dense_plan.h)
+  size_t pre_bytes = 0;
   void *post = nullptr;  // key scratch + table
   size_t post_bytes = 0;
-  hipEvent_t done = nullptr;
-  uint32_t *h_head = nullptr;    // pinned: the count and the list's length as the host reads them
-  hipStream_t stream = nullptr;  // the host form's
+  uint32_t *h_head = nullptr;  // pinned: the count and the list's length as the host reads them
   PhWorkspace ws;
-  bool in_use = false;
 };
 
 // the request, checked; device pointers of the caller
@@ -201,94 +191,6 @@ struct PhDenseCall {
 
 namespace {
 
-PhDenseSet *set_acquire(phnsw_index *ix) {
-  std::lock_guard<std::mutex> g(ix->dense_mutex);
-  for (PhDenseSet *s : ix->denses)
-    if (!s->in_use) {
-      s->in_use = true;
-      return s;
-    }
-  PhDenseSet *s = new PhDenseSet();
-  s->in_use = true;
-  ix->denses.push_back(s);
-  return s;
-}
-// the one drain of every return path: the set's event closes what the call enqueued, then the set is handed back
-struct SetGuard {
-  phnsw_index *ix;
-  PhDenseSet *set;
-  hipStream_t stream;
-  ~SetGuard() {
-    set->ws.tiny_pack_key.valid = false;  // the list it described is scratch: the next call writes other ids there
-    if (set->done) hipEventRecord(set->done, stream);
-    std::lock_guard<std::mutex> g(ix->dense_mutex);
-    set->in_use = false;
-  }
-};
-
-// a block of the set at least `need` bytes large, behind the set's last user
-int block_ensure(PhDenseSet &s, void **block, size_t *have, size_t need, hipStream_t stream) {
-  if (*have < need) {
-    if (*block) {
-      PH_HIP(hipEventSynchronize(s.done));  // the block goes back to the pool: nothing may still use it
-      ph_pool_free(*block);
-      *block = nullptr, *have = 0;
-    }
-    PH_HIP(ph_pool_alloc(block, need));
-    *have = need;
-  } else {
-    PH_HIP(hipStreamWaitEvent(stream, s.done, 0));
-  }
-  return 0;
-}
-
-// PHNSW_DENSE_TIMES=1 (scripts/bench_filter_dense.py): the steps' times from events, one line on stderr per call; the
-// call then waits for its own work.  Pack and table are one figure: both are enqueued inside tiny_table.
-struct StepTimes {
-  bool on = false;
-  hipStream_t stream = nullptr;
-  struct Span { int step; hipEvent_t e0, e1; };
-  std::vector<Span> spans;
-  void begin(int step) {
-    if (!on) return;
-    Span s{step, nullptr, nullptr};
-    if (hipEventCreate(&s.e0) != hipSuccess || hipEventCreate(&s.e1) != hipSuccess) {
-      on = false;
-      return;
-    }
-    hipEventRecord(s.e0, stream);
-    spans.push_back(s);
-  }
-  void end() {
-    if (on && !spans.empty()) hipEventRecord(spans.back().e1, stream);
-  }
-  void report(uint64_t c, uint64_t nq) {
-    if (spans.empty()) return;
-    float ms[4] = {0.f, 0.f, 0.f, 0.f};
-    hipStreamSynchronize(stream);
-    for (Span &s : spans) {
-      float t = 0.f;
-      if (hipEventElapsedTime(&t, s.e0, s.e1) == hipSuccess) ms[s.step] += t;
-      hipEventDestroy(s.e0);
-      hipEventDestroy(s.e1);
-    }
-    spans.clear();
-    fprintf(stderr, "[phnsw] exact_shared: %llu queries x %llu candidates: count %.3f ms, list %.3f ms, pack+table %.3f ms, select %.3f ms\n",
-            (unsigned long long)nq, (unsigned long long)c, ms[0], ms[1], ms[2], ms[3]);
-  }
-  ~StepTimes() {
-    for (Span &s : spans) {
-      if (s.e0) hipEventDestroy(s.e0);
-      if (s.e1) hipEventDestroy(s.e1);
-    }
-  }
-};
-
-long long env_ll(const char *name) {
-  const char *e = getenv(name);  // read per call: the tests switch them
-  return e ? atoll(e) : 0;
-}
-
 int select_launch(const PhDenseCall &c, PhDenseSelectArgs &a) {
   hipLaunchKernelGGL(ph_dense_select_kernel, dim3(std::min<uint32_t>(a.npos, 1u << 20)), dim3(64),
                      (size_t)ph_dense_select_lds(c.k), c.stream, a);
@@ -300,22 +202,21 @@ int select_launch(const PhDenseCall &c, PhDenseSelectArgs &a) {
 int dense_run(const phnsw_index *ix, const PhDenseCall &c, PhDenseSet &set) {
   const phnsw_store *s = ix->store;
   const uint64_t nq = c.nq, nwords = ph_exact_words(s->n);
-  if (!set.done) PH_HIP(hipEventCreateWithFlags(&set.done, hipEventDisableTiming));
+  // the packed operand's key describes a list that is scratch: whichever way the last call on this set ended, this one
+  // writes other ids there
+  set.ws.tiny_pack_key.valid = false;
+  PH_TRY(set.ready());
   if (!set.h_head) PH_HIP(hipHostMalloc((void **)&set.h_head, PH_DENSE_HEAD_WORDS * 4u, hipHostMallocDefault));
   PhDenseListArgs l = {};
   l.filter = c.filter, l.n = (uint32_t)s->n, l.nwords = (uint32_t)nwords;
   ph_exact_bottom_layer(ix, &l.n_nodes, &l.nodes, &l.vec2node);
   l.cap = (uint32_t)std::min<uint64_t>(s->n, l.n_nodes);  // a candidate is a vector of the bottom layer
-  void *pre = set.pre;
-  size_t pre_bytes = set.pre_words * 4u;
-  const int rc = block_ensure(set, &pre, &pre_bytes, (size_t)ph_dense_pre_words(nwords, l.cap, nq) * 4u, c.stream);
-  set.pre = (uint32_t *)pre, set.pre_words = pre_bytes / 4u;
-  if (rc) return rc;
-  uint32_t *const head = set.pre, *const off = head + PH_DENSE_HEAD_WORDS, *const list = off + ph_dense_off_words(nwords);
+  PH_TRY(set.block_ensure(&set.pre, &set.pre_bytes, (size_t)ph_dense_pre_words(nwords, l.cap, nq) * 4u, c.stream));
+  uint32_t *const head = (uint32_t *)set.pre, *const off = head + PH_DENSE_HEAD_WORDS, *const list = off + ph_dense_off_words(nwords);
   uint32_t *const safe = list + l.cap, *const flags = safe + nq;
   l.head = head, l.off = off, l.list = list;
 
-  StepTimes times;
+  StepTimes times;  // pack and table are one figure: both are enqueued inside tiny_table
   times.on = env_ll("PHNSW_DENSE_TIMES") > 0, times.stream = c.stream;
   times.begin(0);
   PhFilter one = {c.filter, 0u, 0u};
@@ -353,7 +254,7 @@ int dense_run(const phnsw_index *ix, const PhDenseCall &c, PhDenseSet &set) {
   }
   const PhDensePlan plan = ph_dense_plan(cand, nq, ph_dense_nodes_knob(env_ll("PHNSW_DENSE_NODES")),
                                          ph_dense_bytes_knob(env_ll("PHNSW_DENSE_TABLE_BYTES")));
-  PH_TRY(block_ensure(set, &set.post, &set.post_bytes, (size_t)ph_dense_post_bytes(plan, c.k), c.stream));
+  PH_TRY(set.block_ensure(&set.post, &set.post_bytes, (size_t)ph_dense_post_bytes(plan, c.k), c.stream));
   a.keys = (uint64_t *)set.post;
   float *const D = (float *)((char *)set.post + ph_dense_key_bytes(nq, c.k));
   a.D = D;
@@ -389,28 +290,12 @@ int dense_run(const phnsw_index *ix, const PhDenseCall &c, PhDenseSet &set) {
       times.end();
     }
   }
-  times.report(cand, nq);
+  float ms[4];
+  if (times.collect(ms, 4))
+    fprintf(stderr, "[phnsw] exact_shared: %llu queries x %llu candidates: count %.3f ms, list %.3f ms, pack+table %.3f ms, select %.3f ms\n",
+            (unsigned long long)nq, (unsigned long long)cand, ms[0], ms[1], ms[2], ms[3]);
   return 0;
 }
-
-// device blocks of one host call: handed back only after the stream they were used on has drained, whichever way the
-// call ends
-struct HostBlocks {
-  hipStream_t stream;
-  std::vector<void *> blocks;
-  template <class T>
-  int alloc(T **p, size_t bytes) {
-    void *v = nullptr;
-    PH_HIP(ph_pool_alloc(&v, std::max<size_t>(bytes, 4)));
-    blocks.push_back(v);
-    *p = (T *)v;
-    return 0;
-  }
-  ~HostBlocks() {
-    hipStreamSynchronize(stream);
-    for (void *b : blocks) ph_pool_free(b);
-  }
-};
 
 }  // namespace
 
@@ -439,19 +324,12 @@ int ph_dense_check(const phnsw_index *ix, uint64_t k, const char *call) {
 }
 
 void ph_dense_free(phnsw_index *ix) {
-  for (PhDenseSet *s : ix->denses) {
-    if (s->done) {
-      hipEventSynchronize(s->done);
-      hipEventDestroy(s->done);
-    }
-    if (s->pre) ph_pool_free(s->pre);
-    if (s->post) ph_pool_free(s->post);
-    if (s->h_head) hipHostFree(s->h_head);
-    if (s->stream) hipStreamDestroy(s->stream);
-    ph_tiny_free(s->ws);
-    delete s;
-  }
-  ix->denses.clear();
+  ph_sets_free<PhDenseSet>(ix->denses, [](PhDenseSet &s) {
+    if (s.pre) ph_pool_free(s.pre);
+    if (s.post) ph_pool_free(s.post);
+    if (s.h_head) hipHostFree(s.h_head);
+    ph_tiny_free(s.ws);
+  });
 }
 
 // ------------------------------------------------------------------ C ABI
@@ -482,8 +360,8 @@ extern "C" int phnsw_search_exact_shared_device(const phnsw_index *ix, const flo
   c.stream = (hipStream_t)stream;
   PH_HIP(hipSetDevice(ix->store->device));
   phnsw_index *mix = const_cast<phnsw_index *>(ix);
-  PhDenseSet *set = set_acquire(mix);
-  SetGuard guard{mix, set, c.stream};
+  PhDenseSet *set = ph_set_acquire<PhDenseSet>(mix->denses);
+  PhSetGuard guard{mix->denses, set, c.stream};
   return dense_run(ix, c, *set);
 } catch (...) { return ph_caught(); }
 
@@ -503,77 +381,23 @@ extern "C" int phnsw_search_exact_shared(const phnsw_index *ix, const float *que
   }
   const phnsw_store *s = ix->store;
   PH_HIP(hipSetDevice(s->device));
-  if (qids)
-    for (uint64_t i = 0; i < nq; i++)
-      if (qids[i] >= s->n) {
-        ph_set_error("search: stored query id %llu out of range", (unsigned long long)qids[i]);
-        return PHNSW_E_INVALID;
-      }
-  // host words of the per-query ids, alive until the stream has drained (HostBlocks is declared after them)
-  std::vector<uint32_t> h_in, h_out(2u * nq);
+  PH_TRY(ph_stored_ids_check(qids, nq, s->n, "search"));
   phnsw_index *mix = const_cast<phnsw_index *>(ix);
-  PhDenseSet *set = set_acquire(mix);
-  if (!set->stream) {
-    hipError_t e = hipStreamCreateWithFlags(&set->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-      SetGuard g{mix, set, nullptr};
-      return ph_hip_fail(e, "host path: stream", __FILE__, __LINE__);
-    }
-  }
-  const hipStream_t st = set->stream;
-  SetGuard guard{mix, set, st};
-  HostBlocks hb{st, {}};
-
+  PhDenseSet *set = ph_set_acquire<PhDenseSet>(mix->denses);
+  PhHostCall h(mix->denses, set);
+  PH_TRY(h.stage_in(s, queries, qids, exclude, nq, 0, 0, (uint32_t)k, (uint32_t)k));
   PhDenseCall c = {};
-  const uint32_t ld = s->ld, kk = (uint32_t)k;
-  if (queries) {  // rows padded to the store's row length
-    float *q = nullptr;
-    PH_TRY(hb.alloc(&q, (size_t)nq * ld * 4u));
-    if (ld != s->dim) {
-      PH_HIP(hipMemsetAsync(q, 0, (size_t)nq * ld * 4u, st));
-      PH_HIP(hipMemcpy2DAsync(q, (size_t)ld * 4u, queries, (size_t)s->dim * 4u, (size_t)s->dim * 4u, nq, hipMemcpyHostToDevice, st));
-    } else {
-      PH_HIP(hipMemcpyAsync(q, queries, (size_t)nq * ld * 4u, hipMemcpyHostToDevice, st));
-    }
-    c.queries = q, c.ldq = ld;
-  }
-  uint32_t *small = nullptr;  // qid | exclude | len | status   [4][nq]
-  PH_TRY(hb.alloc(&small, (size_t)nq * 4u * 4u));
-  if (qids || exclude) {
-    h_in.resize(2u * nq);
-    if (qids)
-      for (uint64_t i = 0; i < nq; i++) h_in[i] = (uint32_t)qids[i];
-    if (exclude)
-      for (uint64_t i = 0; i < nq; i++) h_in[nq + i] = exclude[i] >= s->n ? PH_EMPTY32 : (uint32_t)exclude[i];
-    PH_HIP(hipMemcpyAsync(small, h_in.data(), (size_t)nq * 2u * 4u, hipMemcpyHostToDevice, st));
-    if (qids) c.qids = small;
-    if (exclude) c.exclude = small + nq;
-  }
+  h.fill(c);
   if (filter) {
     const size_t words = (size_t)ph_exact_words(s->n);
     uint32_t *f = nullptr;
-    PH_TRY(hb.alloc(&f, words * 4u));
-    PH_HIP(hipMemcpyAsync(f, filter, words * 4u, hipMemcpyHostToDevice, st));
+    PH_TRY(h.blocks.alloc(&f, words * 4u));
+    PH_HIP(hipMemcpyAsync(f, filter, words * 4u, hipMemcpyHostToDevice, h.st));
     c.filter = f;
   } else {
     c.filter = ix->default_filter;  // phnsw_index_set_filter_device: device words
   }
-  uint32_t *ids = nullptr;
-  float *d = nullptr, *dk = nullptr;
-  uint64_t *ids64 = nullptr;
-  PH_TRY(hb.alloc(&ids, (size_t)nq * kk * 4u));
-  PH_TRY(hb.alloc(&d, (size_t)nq * kk * 4u));
-  PH_TRY(hb.alloc(&ids64, (size_t)nq * kk * 8u));
-  PH_TRY(hb.alloc(&dk, (size_t)nq * kk * 4u));
-  c.nq = nq, c.k = kk;
-  c.out_ids = ids, c.out_d = d, c.out_len = small + 2u * nq, c.status = small + 3u * nq;
-  c.stream = st;
+  c.k = (uint32_t)k;
   PH_TRY(dense_run(ix, c, *set));
-  PH_TRY(ph_take_launch(ids, d, kk, kk, nq, ids64, dk, st));  // u32 -> u64 ids, 0xFFFFFFFF -> PHNSW_EMPTY
-  PH_HIP(hipMemcpyAsync(h_out.data(), small + 2u * nq, (size_t)nq * 2u * 4u, hipMemcpyDeviceToHost, st));
-  PH_HIP(hipMemcpyAsync(out_ids, ids64, (size_t)nq * kk * 8u, hipMemcpyDeviceToHost, st));
-  PH_HIP(hipMemcpyAsync(out_d, dk, (size_t)nq * kk * 4u, hipMemcpyDeviceToHost, st));
-  PH_HIP(hipStreamSynchronize(st));
-  for (uint64_t i = 0; i < nq; i++) out_len[i] = h_out[i];  // the ids were checked: every status is 0
-  return 0;
+  return h.finish(out_ids, out_d, out_len);  // the ids were checked: every status is 0
 } catch (...) { return ph_caught(); }

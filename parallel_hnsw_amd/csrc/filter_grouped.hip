@@ -37,13 +37,8 @@
 #include "exact_topk.h"
 #include "filter_candidate.h"
 #include "group_plan.h"
+#include "host_call.h"
 #include "phnsw_device.h"
-
-#define PH_TRY(x)          \
-  do {                     \
-    int rc__ = (x);        \
-    if (rc__) return rc__; \
-  } while (0)
 
 // ------------------------------------------------------------------ grouping
 
@@ -290,18 +285,13 @@ __global__ __launch_bounds__(64) void ph_grouped_select_kernel(PhGroupedSelectAr
 
 // ------------------------------------------------------------------ a call's scratch
 
-// Kept with the index, one set per call in flight, after the pattern of PhDenseSet (filter_dense.hip): nothing goes back
-// to the pool while work that uses it may still be enqueued, whichever way a call ends.  `done` closes the last call
-// that used the set; the next one's stream waits.  Of `ws` only the tiny_* operand fields are used.
-struct PhGroupedSet {
+// A PhCallSet (call_set.h) of the index's `groupeds` pool.  Of `ws` only the tiny_* operand fields are used.
+struct PhGroupedSet : PhCallSet {
   void *pre = nullptr, *tmp = nullptr, *lists = nullptr, *post = nullptr;  // group_plan.h; tmp: the sort's and the scan's
   size_t pre_bytes = 0, tmp_bytes = 0, lists_bytes = 0, post_bytes = 0;
-  hipEvent_t done = nullptr;
   uint32_t *h_read = nullptr;  // pinned: head, groups and counts as the host reads them
   size_t h_read_words = 0;
-  hipStream_t stream = nullptr;  // the host form's
   PhWorkspace ws;
-  bool in_use = false;
 };
 
 // the request, checked; device pointers of the caller
@@ -323,99 +313,6 @@ struct PhGroupedCall {
 
 namespace {
 
-PhGroupedSet *set_acquire(phnsw_index *ix) {
-  std::lock_guard<std::mutex> g(ix->grouped_mutex);
-  for (PhGroupedSet *s : ix->groupeds)
-    if (!s->in_use) {
-      s->in_use = true;
-      return s;
-    }
-  PhGroupedSet *s = new PhGroupedSet();
-  s->in_use = true;
-  ix->groupeds.push_back(s);
-  return s;
-}
-// the one drain of every return path: the set's event closes what the call enqueued, then the set is handed back
-struct SetGuard {
-  phnsw_index *ix;
-  PhGroupedSet *set;
-  hipStream_t stream;
-  ~SetGuard() {
-    set->ws.tiny_pack_key.valid = false;  // the lists it described are scratch: the next call writes other ids there
-    if (set->done) hipEventRecord(set->done, stream);
-    std::lock_guard<std::mutex> g(ix->grouped_mutex);
-    set->in_use = false;
-  }
-};
-
-// a block of the set at least `need` bytes large, behind the set's last user
-int block_ensure(PhGroupedSet &s, void **block, size_t *have, size_t need, hipStream_t stream) {
-  if (*have < need) {
-    if (*block) {
-      PH_HIP(hipEventSynchronize(s.done));  // the block goes back to the pool: nothing may still use it
-      ph_pool_free(*block);
-      *block = nullptr, *have = 0;
-    }
-    PH_HIP(ph_pool_alloc(block, need));
-    *have = need;
-  } else {
-    PH_HIP(hipStreamWaitEvent(stream, s.done, 0));
-  }
-  return 0;
-}
-
-// PHNSW_GROUP_TIMES=1 (scripts/bench_filter_grouped.py): the steps' times from events, one line on stderr per call; the
-// call then waits for its own work.  Pack and table are one figure: both are enqueued inside tiny_table.
-struct StepTimes {
-  enum { GROUP, COUNT, LIST, TABLE, SELECT, STEPS };
-  bool on = false;
-  hipStream_t stream = nullptr;
-  struct Span { int step; hipEvent_t e0, e1; };
-  std::vector<Span> spans;
-  void begin(int step) {
-    if (!on) return;
-    Span s{step, nullptr, nullptr};
-    if (hipEventCreate(&s.e0) != hipSuccess || hipEventCreate(&s.e1) != hipSuccess) {
-      on = false;
-      return;
-    }
-    hipEventRecord(s.e0, stream);
-    spans.push_back(s);
-  }
-  void end() {
-    if (on && !spans.empty()) hipEventRecord(spans.back().e1, stream);
-  }
-  void report(uint64_t nq, uint64_t groups, uint64_t rounds, uint64_t cands) {
-    if (spans.empty()) return;
-    float ms[STEPS] = {};
-    hipStreamSynchronize(stream);
-    for (Span &s : spans) {
-      float t = 0.f;
-      if (hipEventElapsedTime(&t, s.e0, s.e1) == hipSuccess) ms[s.step] += t;
-      hipEventDestroy(s.e0);
-      hipEventDestroy(s.e1);
-    }
-    spans.clear();
-    fprintf(stderr, "[phnsw] exact_grouped: %llu queries, %llu groups in %llu rounds, %llu listed candidates: group %.3f ms, "
-            "count %.3f ms, list %.3f ms, pack+table %.3f ms, select %.3f ms\n",
-            (unsigned long long)nq, (unsigned long long)groups, (unsigned long long)rounds, (unsigned long long)cands, ms[GROUP],
-            ms[COUNT], ms[LIST], ms[TABLE], ms[SELECT]);
-  }
-  ~StepTimes() {
-    for (Span &s : spans) {
-      if (s.e0) hipEventDestroy(s.e0);
-      if (s.e1) hipEventDestroy(s.e1);
-    }
-  }
-};
-
-long long env_ll(const char *name) {
-  const char *e = getenv(name);  // read per call: the tests switch them
-  return e ? atoll(e) : 0;
-}
-
-uint32_t grid1(uint64_t items) { return (uint32_t)std::min<uint64_t>((items + 255u) / 256u, 1u << 16); }
-
 int select_launch(const PhGroupedCall &c, const PhGroupedSelectArgs &a) {
   hipLaunchKernelGGL(ph_grouped_select_kernel, dim3(std::min<uint32_t>(a.npos, 1u << 20)), dim3(64),
                      (size_t)ph_dense_select_lds(c.k), c.stream, a);
@@ -429,7 +326,10 @@ int grouped_run(const phnsw_index *ix, const PhGroupedCall &c, PhGroupedSet &set
   const uint64_t nq = c.nq, nwords = ph_exact_words(s->n);
   const uint64_t gmax = ph_group_max(nq, c.nfilters);
   const PhGroupPre lay = ph_group_pre(nq, gmax);
-  if (!set.done) PH_HIP(hipEventCreateWithFlags(&set.done, hipEventDisableTiming));
+  // the packed operand's key describes lists that are scratch: whichever way the last call on this set ended, this one
+  // writes other ids there
+  set.ws.tiny_pack_key.valid = false;
+  PH_TRY(set.ready());
   if (set.h_read_words < lay.read_words) {
     if (set.h_read) {
       PH_HIP(hipEventSynchronize(set.done));
@@ -439,7 +339,7 @@ int grouped_run(const phnsw_index *ix, const PhGroupedCall &c, PhGroupedSet &set
     PH_HIP(hipHostMalloc((void **)&set.h_read, (size_t)lay.read_words * 4u, hipHostMallocDefault));
     set.h_read_words = (size_t)lay.read_words;
   }
-  PH_TRY(block_ensure(set, &set.pre, &set.pre_bytes, (size_t)lay.words * 4u, c.stream));
+  PH_TRY(set.block_ensure(&set.pre, &set.pre_bytes, (size_t)lay.words * 4u, c.stream));
   uint32_t *const pre = (uint32_t *)set.pre;
   uint32_t *const head = pre + lay.head, *const gfirst = pre + lay.gfirst, *const gkey = pre + lay.gkey;
   uint32_t *const gcount = pre + lay.gcount, *const gerr = pre + lay.gerr;
@@ -450,11 +350,12 @@ int grouped_run(const phnsw_index *ix, const PhGroupedCall &c, PhGroupedSet &set
   size_t sort_bytes = 0, scan_bytes = 0;
   PH_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, keys, skeys, iota, order, (int)nq, 0, 32, c.stream));
   PH_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, flags, slots, (int)(nq + 1u), c.stream));
-  PH_TRY(block_ensure(set, &set.tmp, &set.tmp_bytes, std::max<size_t>(std::max(sort_bytes, scan_bytes), 16), c.stream));
+  PH_TRY(set.block_ensure(&set.tmp, &set.tmp_bytes, std::max<size_t>(std::max(sort_bytes, scan_bytes), 16), c.stream));
 
-  StepTimes times;
+  enum { GROUP, COUNT, LIST, TABLE, SELECT, STEPS };
+  StepTimes times;  // pack and table are one figure: both are enqueued inside tiny_table
   times.on = env_ll("PHNSW_GROUP_TIMES") > 0, times.stream = c.stream;
-  times.begin(StepTimes::GROUP);
+  times.begin(GROUP);
   hipLaunchKernelGGL(ph_grouped_keys_kernel, dim3(grid1(nq)), dim3(256), 0, c.stream, c.filter_of, c.qids, (uint32_t)nq,
                      (uint32_t)s->n, c.nfilters, keys, iota, safe, why);
   PH_HIP(hipGetLastError());
@@ -477,7 +378,7 @@ int grouped_run(const phnsw_index *ix, const PhGroupedCall &c, PhGroupedSet &set
   ph_exact_bottom_layer(ix, &l.n_nodes, &l.nodes, &l.vec2node);
   l.ngroups = slots + nq, l.gmax = (uint32_t)gmax, l.gkey = gkey, l.gcount = gcount, l.gcum = gcum, l.gerr = gerr;
   const uint64_t cap = std::min<uint64_t>(s->n, l.n_nodes);  // a candidate is a vector of the bottom layer
-  times.begin(StepTimes::COUNT);
+  times.begin(COUNT);
   hipLaunchKernelGGL(ph_grouped_count_kernel, dim3((uint32_t)std::min<uint64_t>(gmax, 4096u)), dim3(256), 0, c.stream, l);
   hipLaunchKernelGGL(ph_grouped_cum_kernel, dim3(1), dim3(1024), 0, c.stream, l);
   PH_HIP(hipGetLastError());
@@ -508,8 +409,8 @@ int grouped_run(const phnsw_index *ix, const PhGroupedCall &c, PhGroupedSet &set
     table_floats = std::max(table_floats, plan.table_floats);
     listed += hcount[g];
   }
-  PH_TRY(block_ensure(set, &set.lists, &set.lists_bytes, (size_t)list_bytes, c.stream));
-  PH_TRY(block_ensure(set, &set.post, &set.post_bytes, (size_t)std::max<uint64_t>(ph_group_post_bytes(nq, c.k, table_floats), 16u),
+  PH_TRY(set.block_ensure(&set.lists, &set.lists_bytes, (size_t)list_bytes, c.stream));
+  PH_TRY(set.block_ensure(&set.post, &set.post_bytes, (size_t)std::max<uint64_t>(ph_group_post_bytes(nq, c.k, table_floats), 16u),
                       c.stream));
   PhGroupedSelectArgs a = {};
   a.exclude = c.exclude, a.why = why, a.k = c.k;
@@ -524,7 +425,7 @@ int grouped_run(const phnsw_index *ix, const PhGroupedCall &c, PhGroupedSet &set
     l.g0 = (uint32_t)g0, l.ng = (uint32_t)(g1 - g0);
     l.off = (uint32_t *)set.lists;
     l.list = l.off + ph_group_round_off_words(g0, g1, nwords);
-    times.begin(StepTimes::LIST);
+    times.begin(LIST);
     if (nwords) hipLaunchKernelGGL(ph_grouped_popc_kernel, dim3(wgrid, l.ng), dim3(256), 0, c.stream, l);
     hipLaunchKernelGGL(ph_grouped_prefix_kernel, dim3(l.ng), dim3(1024), 0, c.stream, l);
     if (nwords) hipLaunchKernelGGL(ph_grouped_list_kernel, dim3(wgrid, l.ng), dim3(256), 0, c.stream, l);
@@ -544,7 +445,7 @@ int grouped_run(const phnsw_index *ix, const PhGroupedCall &c, PhGroupedSet &set
       if (cand == 0) {  // empty rows, and the status of the reject group's queries, from the select itself
         a.D = nullptr, a.stride = 0, a.tn = 0, a.list = nullptr;
         a.order = order + first, a.npos = (uint32_t)size, a.first = 1u, a.last = 1u;
-        times.begin(StepTimes::SELECT);
+        times.begin(SELECT);
         PH_TRY(select_launch(c, a));
         times.end();
         continue;
@@ -562,7 +463,7 @@ int grouped_run(const phnsw_index *ix, const PhGroupedCall &c, PhGroupedSet &set
           ph_dense_pos_chunk(plan, j, &pfirst, &a.npos);
           a.order = order + first + pfirst;
           bool kept = false;
-          times.begin(StepTimes::TABLE);
+          times.begin(TABLE);
           const int trc = ph_tiny_table_chunk_ordered(ix, set.ws, c.queries, c.ldq, c.qids ? safe : nullptr, a.order, a.npos, a.list,
                                                       a.tn, D, c.stream, &kept);
           times.end();
@@ -577,7 +478,7 @@ int grouped_run(const phnsw_index *ix, const PhGroupedCall &c, PhGroupedSet &set
                     "node operand %s\n", (unsigned long long)g, hkey[g], i + 1u, plan.node_chunks, a.tn,
                     (unsigned long long)pfirst, a.npos, set.ws.tiny_table_g ? "matrix cores" : "vector units",
                     kept ? "kept" : "packed");
-          times.begin(StepTimes::SELECT);
+          times.begin(SELECT);
           PH_TRY(select_launch(c, a));
           times.end();
         }
@@ -585,28 +486,14 @@ int grouped_run(const phnsw_index *ix, const PhGroupedCall &c, PhGroupedSet &set
     }
     g0 = g1;
   }
-  times.report(nq, ngroups, rounds, listed);
+  float ms[STEPS];
+  if (times.collect(ms, STEPS))
+    fprintf(stderr, "[phnsw] exact_grouped: %llu queries, %llu groups in %llu rounds, %llu listed candidates: group %.3f ms, "
+            "count %.3f ms, list %.3f ms, pack+table %.3f ms, select %.3f ms\n",
+            (unsigned long long)nq, (unsigned long long)ngroups, (unsigned long long)rounds, (unsigned long long)listed, ms[GROUP],
+            ms[COUNT], ms[LIST], ms[TABLE], ms[SELECT]);
   return 0;
 }
-
-// device blocks of one host call: handed back only after the stream they were used on has drained, whichever way the
-// call ends
-struct HostBlocks {
-  hipStream_t stream;
-  std::vector<void *> blocks;
-  template <class T>
-  int alloc(T **p, size_t bytes) {
-    void *v = nullptr;
-    PH_HIP(ph_pool_alloc(&v, std::max<size_t>(bytes, 4)));
-    blocks.push_back(v);
-    *p = (T *)v;
-    return 0;
-  }
-  ~HostBlocks() {
-    hipStreamSynchronize(stream);
-    for (void *b : blocks) ph_pool_free(b);
-  }
-};
 
 // the table arguments both forms take
 bool table_args_ok(const phnsw_index *ix, const uint32_t *filters, uint32_t stride_words, uint64_t nfilters,
@@ -618,21 +505,14 @@ bool table_args_ok(const phnsw_index *ix, const uint32_t *filters, uint32_t stri
 }  // namespace
 
 void ph_grouped_free(phnsw_index *ix) {
-  for (PhGroupedSet *s : ix->groupeds) {
-    if (s->done) {
-      hipEventSynchronize(s->done);
-      hipEventDestroy(s->done);
-    }
-    if (s->pre) ph_pool_free(s->pre);
-    if (s->tmp) ph_pool_free(s->tmp);
-    if (s->lists) ph_pool_free(s->lists);
-    if (s->post) ph_pool_free(s->post);
-    if (s->h_read) hipHostFree(s->h_read);
-    if (s->stream) hipStreamDestroy(s->stream);
-    ph_tiny_free(s->ws);
-    delete s;
-  }
-  ix->groupeds.clear();
+  ph_sets_free<PhGroupedSet>(ix->groupeds, [](PhGroupedSet &s) {
+    if (s.pre) ph_pool_free(s.pre);
+    if (s.tmp) ph_pool_free(s.tmp);
+    if (s.lists) ph_pool_free(s.lists);
+    if (s.post) ph_pool_free(s.post);
+    if (s.h_read) hipHostFree(s.h_read);
+    ph_tiny_free(s.ws);
+  });
 }
 
 // ------------------------------------------------------------------ C ABI
@@ -662,8 +542,8 @@ extern "C" int phnsw_search_exact_grouped_device(const phnsw_index *ix, const fl
   c.stream = (hipStream_t)stream;
   PH_HIP(hipSetDevice(ix->store->device));
   phnsw_index *mix = const_cast<phnsw_index *>(ix);
-  PhGroupedSet *set = set_acquire(mix);
-  SetGuard guard{mix, set, c.stream};
+  PhGroupedSet *set = ph_set_acquire<PhGroupedSet>(mix->groupeds);
+  PhSetGuard guard{mix->groupeds, set, c.stream};
   return grouped_run(ix, c, *set);
 } catch (...) { return ph_caught(); }
 
@@ -685,91 +565,40 @@ extern "C" int phnsw_search_exact_grouped(const phnsw_index *ix, const float *qu
   }
   const phnsw_store *s = ix->store;
   PH_HIP(hipSetDevice(s->device));
-  if (qids)
-    for (uint64_t i = 0; i < nq; i++)
-      if (qids[i] >= s->n) {
-        ph_set_error("search: stored query id %llu out of range", (unsigned long long)qids[i]);
-        return PHNSW_E_INVALID;
-      }
+  PH_TRY(ph_stored_ids_check(qids, nq, s->n, "search"));
   for (uint64_t i = 0; i < nq; i++)
     if (ph_group_key(filter_of[i], nfilters) == PH_GROUP_KEY_REJECT) {
       ph_set_error("%s: query %llu selects bitmap %u of a table of %llu (PHNSW_FILTER_ALL = no bitmap)", call,
                    (unsigned long long)i, filter_of[i], (unsigned long long)nfilters);
       return PHNSW_E_INVALID;
     }
-  // host words of the per-query ids, alive until the stream has drained (HostBlocks is declared after them)
-  std::vector<uint32_t> h_in, h_out(2u * nq);
   phnsw_index *mix = const_cast<phnsw_index *>(ix);
-  PhGroupedSet *set = set_acquire(mix);
-  if (!set->stream) {
-    hipError_t e = hipStreamCreateWithFlags(&set->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-      SetGuard g{mix, set, nullptr};
-      return ph_hip_fail(e, "host path: stream", __FILE__, __LINE__);
-    }
-  }
-  const hipStream_t st = set->stream;
-  SetGuard guard{mix, set, st};
-  HostBlocks hb{st, {}};
-
+  PhGroupedSet *set = ph_set_acquire<PhGroupedSet>(mix->groupeds);
+  PhHostCall h(mix->groupeds, set);
+  PH_TRY(h.stage_in(s, queries, qids, exclude, nq, (size_t)nq, 0, (uint32_t)k, (uint32_t)k));  // extras: the selectors
   PhGroupedCall c = {};
-  const uint32_t ld = s->ld, kk = (uint32_t)k;
-  if (queries) {  // rows padded to the store's row length
-    float *q = nullptr;
-    PH_TRY(hb.alloc(&q, (size_t)nq * ld * 4u));
-    if (ld != s->dim) {
-      PH_HIP(hipMemsetAsync(q, 0, (size_t)nq * ld * 4u, st));
-      PH_HIP(hipMemcpy2DAsync(q, (size_t)ld * 4u, queries, (size_t)s->dim * 4u, (size_t)s->dim * 4u, nq, hipMemcpyHostToDevice, st));
-    } else {
-      PH_HIP(hipMemcpyAsync(q, queries, (size_t)nq * ld * 4u, hipMemcpyHostToDevice, st));
-    }
-    c.queries = q, c.ldq = ld;
-  }
-  uint32_t *small = nullptr;  // qid | exclude | len | status | selector   [5][nq]
-  PH_TRY(hb.alloc(&small, (size_t)nq * 5u * 4u));
-  if (qids || exclude) {
-    h_in.resize(2u * nq);
-    if (qids)
-      for (uint64_t i = 0; i < nq; i++) h_in[i] = (uint32_t)qids[i];
-    if (exclude)
-      for (uint64_t i = 0; i < nq; i++) h_in[nq + i] = exclude[i] >= s->n ? PH_EMPTY32 : (uint32_t)exclude[i];
-    PH_HIP(hipMemcpyAsync(small, h_in.data(), (size_t)nq * 2u * 4u, hipMemcpyHostToDevice, st));
-    if (qids) c.qids = small;
-    if (exclude) c.exclude = small + nq;
-  }
-  PH_HIP(hipMemcpyAsync(small + 4u * nq, filter_of, (size_t)nq * 4u, hipMemcpyHostToDevice, st));
-  c.filter_of = small + 4u * nq;
+  h.fill(c);
+  PH_HIP(hipMemcpyAsync(h.extra(), filter_of, (size_t)nq * 4u, hipMemcpyHostToDevice, h.st));
+  c.filter_of = h.extra();
   {  // the whole table, strides and all: what lies between the bitmaps is never read
     const size_t words = (size_t)((nfilters - 1u) * filter_stride_words + ph_exact_words(s->n));
     uint32_t *f = nullptr;
-    PH_TRY(hb.alloc(&f, words * 4u));
-    PH_HIP(hipMemcpyAsync(f, filters, words * 4u, hipMemcpyHostToDevice, st));
+    PH_TRY(h.blocks.alloc(&f, words * 4u));
+    PH_HIP(hipMemcpyAsync(f, filters, words * 4u, hipMemcpyHostToDevice, h.st));
     c.filters = f, c.stride_words = filter_stride_words, c.nfilters = nfilters;
   }
-  uint32_t *ids = nullptr;
-  float *d = nullptr, *dk = nullptr;
-  uint64_t *ids64 = nullptr;
-  PH_TRY(hb.alloc(&ids, (size_t)nq * kk * 4u));
-  PH_TRY(hb.alloc(&d, (size_t)nq * kk * 4u));
-  PH_TRY(hb.alloc(&ids64, (size_t)nq * kk * 8u));
-  PH_TRY(hb.alloc(&dk, (size_t)nq * kk * 4u));
-  c.nq = nq, c.k = kk;
-  c.out_ids = ids, c.out_d = d, c.out_len = small + 2u * nq, c.status = small + 3u * nq;
-  c.stream = st;
+  c.k = (uint32_t)k;
   PH_TRY(grouped_run(ix, c, *set));
-  PH_TRY(ph_take_launch(ids, d, kk, kk, nq, ids64, dk, st));  // u32 -> u64 ids, 0xFFFFFFFF -> PHNSW_EMPTY
-  PH_HIP(hipMemcpyAsync(h_out.data(), small + 2u * nq, (size_t)nq * 2u * 4u, hipMemcpyDeviceToHost, st));
-  PH_HIP(hipStreamSynchronize(st));
-  // ids and selectors were checked: a status here is 7, a bitmap of the (device-resident copy of the) table changed
+  PH_TRY(h.take());
+  PH_TRY(h.download_words());
+  PH_TRY(h.sync());
+  // ids and selectors were checked: a status here is 7, a bitmap of the (device-resident copy of the) table changed;
+  // the caller's rows are then left as they were
   for (uint64_t i = 0; i < nq; i++)
-    if (h_out[nq + i]) {
+    if (h.status(i)) {
       ph_set_error("%s: a bitmap changed while the call read it (query %llu, status %u)", call, (unsigned long long)i,
-                   h_out[nq + i]);
+                   h.status(i));
       return PHNSW_E_INVALID;
     }
-  PH_HIP(hipMemcpyAsync(out_ids, ids64, (size_t)nq * kk * 8u, hipMemcpyDeviceToHost, st));
-  PH_HIP(hipMemcpyAsync(out_d, dk, (size_t)nq * kk * 4u, hipMemcpyDeviceToHost, st));
-  PH_HIP(hipStreamSynchronize(st));
-  for (uint64_t i = 0; i < nq; i++) out_len[i] = h_out[i];
-  return 0;
+  return h.finish(out_ids, out_d, out_len);
 } catch (...) { return ph_caught(); }

@@ -47,17 +47,11 @@
 #include "exact_slices.h"
 #include "exact_topk.h"
 #include "filter_candidate.h"
+#include "host_call.h"
 #include "label_plan.h"
 #include "labelset_plan.h"
 #include "phnsw_device.h"
 
-#define PH_TRY(x)          \
-  do {                     \
-    int rc__ = (x);        \
-    if (rc__) return rc__; \
-  } while (0)
-
-struct PhLabeledSet;
 struct PhLabelResident {  // resident waves of one kernel at one dynamic LDS size
   const void *fn;
   size_t lds;
@@ -73,9 +67,8 @@ struct phnsw_labels {
   uint32_t *first = nullptr;   // [nlabels + 1]
   uint32_t *ids = nullptr;     // [listed] (allocated [n]): ascending within a label
   uint32_t *label_of = nullptr;  // [n]: the label of a listed vector, PHNSW_LABEL_NONE elsewhere (the label walk's column)
-  std::mutex mutex;
-  std::vector<PhLabeledSet *> sets;  // handed out under mutex, one per call in flight
-  std::vector<PhLabelResident> resident;  // under mutex
+  PhCallPool pool;  // PhLabeledSet, handed out by set_acquire's policy
+  std::vector<PhLabelResident> resident;  // under pool.mutex
   int cus = 0;                            // compute units of the device, 0 = not asked yet
 };
 
@@ -541,19 +534,12 @@ static PhLabeledFn labeled_tile_fn(const phnsw_store *s, bool pairs) {
   }
 }
 
-// A call's scratch, kept with the HANDLE, one set per call in flight, after the pattern of PhGroupedSet: nothing goes
-// back to the pool while work that uses it may still be enqueued.  `done` closes the last call that used the set; the
-// next one's stream waits.
-struct PhLabeledSet {
+// A PhCallSet (call_set.h) kept with the HANDLE, not the index.
+struct PhLabeledSet : PhCallSet {
   void *pre = nullptr, *tmp = nullptr, *keys = nullptr;
   size_t pre_bytes = 0, tmp_bytes = 0, keys_bytes = 0;
-  hipEvent_t done = nullptr;
-  hipStream_t stream = nullptr;  // the host form's
-  hipStream_t last = nullptr;    // the stream of the last call that used the set; has_last: there was one
-  bool has_last = false;
-  uint64_t tmp_nq = 0;           // the batch size tmp_need was asked of hipCUB for (0: none yet)
+  uint64_t tmp_nq = 0;  // the batch size tmp_need was asked of hipCUB for (0: none yet)
   size_t tmp_need = 0;
-  bool in_use = false;
 };
 
 namespace {
@@ -567,66 +553,32 @@ PhLabeledSet *set_acquire(phnsw_labels *lb, hipStream_t stream, bool own_stream)
   // than PH_LABEL_SETS exist, a new one, so that calls on different streams overlap; past that a free set whose event
   // the call's stream waits for.  A handle so holds at most max(PH_LABEL_SETS, calls inside the library at once) sets,
   // each as large as the largest call it served, until phnsw_labels_destroy.
-  std::lock_guard<std::mutex> g(lb->mutex);
+  std::lock_guard<std::mutex> g(lb->pool.mutex);
   if (!own_stream)
-    for (PhLabeledSet *s : lb->sets)
+    for (PhCallSet *s : lb->pool.sets)
       if (!s->in_use && !s->stream && s->has_last && s->last == stream) {
         s->in_use = true;
-        return s;
+        return static_cast<PhLabeledSet *>(s);
       }
-  PhLabeledSet *busy = nullptr;
-  for (PhLabeledSet *s : lb->sets) {
+  PhCallSet *busy = nullptr;
+  for (PhCallSet *s : lb->pool.sets) {
     if (s->in_use) continue;
     if (!s->done || hipEventQuery(s->done) == hipSuccess) {
       s->in_use = true;
-      return s;
+      return static_cast<PhLabeledSet *>(s);
     }
     busy = s;
   }
   (void)hipGetLastError();  // hipErrorNotReady of the query is no error of the call
-  if (busy && lb->sets.size() >= PH_LABEL_SETS) {
+  if (busy && lb->pool.sets.size() >= PH_LABEL_SETS) {
     busy->in_use = true;
-    return busy;
+    return static_cast<PhLabeledSet *>(busy);
   }
   PhLabeledSet *s = new PhLabeledSet();
   s->in_use = true;
-  lb->sets.push_back(s);
+  lb->pool.sets.push_back(s);
   return s;
 }
-// the one drain of every return path: the set's event closes what the call enqueued, then the set is handed back
-struct SetGuard {
-  phnsw_labels *lb;
-  PhLabeledSet *set;
-  hipStream_t stream;
-  ~SetGuard() {
-    if (set->done) hipEventRecord(set->done, stream);
-    std::lock_guard<std::mutex> g(lb->mutex);
-    set->last = stream, set->has_last = true;
-    set->in_use = false;
-  }
-};
-
-int block_ensure(PhLabeledSet &s, void **block, size_t *have, size_t need, hipStream_t stream) {
-  if (*have < need) {
-    if (*block) {
-      PH_HIP(hipEventSynchronize(s.done));  // the block goes back to the pool: nothing may still use it
-      ph_pool_free(*block);
-      *block = nullptr, *have = 0;
-    }
-    PH_HIP(ph_pool_alloc(block, need));
-    *have = need;
-  } else {
-    PH_HIP(hipStreamWaitEvent(stream, s.done, 0));
-  }
-  return 0;
-}
-
-long long env_ll(const char *name) {
-  const char *e = getenv(name);  // read per call: the tests switch them
-  return e ? atoll(e) : 0;
-}
-
-uint32_t grid1(uint64_t items) { return (uint32_t)std::min<uint64_t>((items + 255u) / 256u, 1u << 16); }
 
 }  // namespace
 
@@ -686,7 +638,7 @@ int labeled_kernel(const phnsw_labels *lb, const phnsw_store *s, uint32_t k, boo
   uint64_t resident = 0;
   {
     phnsw_labels *mlb = const_cast<phnsw_labels *>(lb);
-    std::lock_guard<std::mutex> g(mlb->mutex);
+    std::lock_guard<std::mutex> g(mlb->pool.mutex);
     for (const PhLabelResident &r : mlb->resident)
       if (r.fn == (const void *)fn && r.lds == lds) resident = r.waves;
     if (!resident) {
@@ -710,7 +662,7 @@ int labeled_tmp(PhLabeledSet &set, const PhLabeledArgs &a, uint32_t *sslot, uint
     PH_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, a.flags, tidx, (int)(count + 1u), stream));
     set.tmp_need = std::max<size_t>(std::max(sort_bytes, scan_bytes), 16), set.tmp_nq = count;
   }
-  return block_ensure(set, &set.tmp, &set.tmp_bytes, set.tmp_need, stream);
+  return set.block_ensure(&set.tmp, &set.tmp_bytes, set.tmp_need, stream);
 }
 
 // the orchestration on a set the caller holds; c is checked, 0 < nq <= PH_LABEL_NQ_MAX (with a list: its length).
@@ -719,8 +671,8 @@ int labeled_run(const phnsw_index *ix, const phnsw_labels *lb, const PhLabeledCa
   const phnsw_store *s = ix->store;
   const uint64_t nq = c.nq;
   const PhLabelPre lay = ph_label_pre(nq);
-  if (!set.done) PH_HIP(hipEventCreateWithFlags(&set.done, hipEventDisableTiming));
-  PH_TRY(block_ensure(set, &set.pre, &set.pre_bytes, (size_t)lay.words * 4u, c.stream));
+  PH_TRY(set.ready());
+  PH_TRY(set.block_ensure(&set.pre, &set.pre_bytes, (size_t)lay.words * 4u, c.stream));
   uint32_t *const pre = (uint32_t *)set.pre;
   PhLabeledArgs a = {};
   a.dist = ph_dist_args(s);
@@ -746,7 +698,7 @@ int labeled_run(const phnsw_index *ix, const phnsw_labels *lb, const PhLabeledCa
                    (unsigned long long)nq, a.slices, c.k);
       return PHNSW_E_INVALID;
     }
-    PH_TRY(block_ensure(set, &set.keys, &set.keys_bytes, (size_t)bytes, c.stream));
+    PH_TRY(set.block_ensure(&set.keys, &set.keys_bytes, (size_t)bytes, c.stream));
     a.scratch = (uint64_t *)set.keys;
   }
 
@@ -788,8 +740,8 @@ int labelset_run(const phnsw_index *ix, const phnsw_labels *lb, const PhLabelset
   const PhLabeledCall &c = sc.c;
   const uint64_t nq = c.nq, np = sc.nwant;  // np positions
   const PhLabelsetPre lay = ph_labelset_pre(np);
-  if (!set.done) PH_HIP(hipEventCreateWithFlags(&set.done, hipEventDisableTiming));
-  PH_TRY(block_ensure(set, &set.pre, &set.pre_bytes, (size_t)lay.words * 4u, c.stream));
+  PH_TRY(set.ready());
+  PH_TRY(set.block_ensure(&set.pre, &set.pre_bytes, (size_t)lay.words * 4u, c.stream));
   uint32_t *const pre = (uint32_t *)set.pre;
   PhLabelsetArgs sa = {};
   PhLabeledArgs &a = sa.a;
@@ -816,7 +768,7 @@ int labelset_run(const phnsw_index *ix, const phnsw_labels *lb, const PhLabelset
                    (unsigned long long)np, a.slices, c.k);
       return PHNSW_E_INVALID;
     }
-    PH_TRY(block_ensure(set, &set.keys, &set.keys_bytes, (size_t)bytes, c.stream));
+    PH_TRY(set.block_ensure(&set.keys, &set.keys_bytes, (size_t)bytes, c.stream));
     a.scratch = (uint64_t *)set.keys;
 
     PH_HIP(hipMemsetAsync(sa.owner, 0xFF, (size_t)np * 4u, c.stream));  // PH_LABELSET_OWNER_NONE
@@ -848,36 +800,12 @@ int labelset_run(const phnsw_index *ix, const phnsw_labels *lb, const PhLabelset
   return 0;
 }
 
-// device blocks of one host call: handed back only after the stream they were used on has drained
-struct HostBlocks {
-  hipStream_t stream;
-  std::vector<void *> blocks;
-  template <class T>
-  int alloc(T **p, size_t bytes) {
-    void *v = nullptr;
-    PH_HIP(ph_pool_alloc(&v, std::max<size_t>(bytes, 4)));
-    blocks.push_back(v);
-    *p = (T *)v;
-    return 0;
-  }
-  ~HostBlocks() {
-    hipStreamSynchronize(stream);
-    for (void *b : blocks) ph_pool_free(b);
-  }
-};
-
 void labels_free(phnsw_labels *lb) {
-  for (PhLabeledSet *s : lb->sets) {
-    if (s->done) {
-      hipEventSynchronize(s->done);
-      hipEventDestroy(s->done);
-    }
-    if (s->pre) ph_pool_free(s->pre);
-    if (s->tmp) ph_pool_free(s->tmp);
-    if (s->keys) ph_pool_free(s->keys);
-    if (s->stream) hipStreamDestroy(s->stream);
-    delete s;
-  }
+  ph_sets_free<PhLabeledSet>(lb->pool, [](PhLabeledSet &s) {
+    if (s.pre) ph_pool_free(s.pre);
+    if (s.tmp) ph_pool_free(s.tmp);
+    if (s.keys) ph_pool_free(s.keys);
+  });
   if (lb->values) hipFree(lb->values);
   if (lb->first) hipFree(lb->first);
   if (lb->ids) hipFree(lb->ids);
@@ -992,7 +920,7 @@ int ph_labeled_device(const phnsw_index *ix, const phnsw_labels *lb, const PhLab
   if (c.nq == 0) return 0;
   phnsw_labels *mlb = const_cast<phnsw_labels *>(lb);
   PhLabeledSet *set = set_acquire(mlb, c.stream, false);
-  SetGuard guard{mlb, set, c.stream};
+  PhSetGuard guard{mlb->pool, set, c.stream};
   return labeled_run(ix, lb, c, *set);
 }
 
@@ -1092,72 +1020,17 @@ extern "C" int phnsw_search_exact_labeled(const phnsw_index *ix, const phnsw_lab
   }
   const phnsw_store *s = ix->store;
   PH_HIP(hipSetDevice(s->device));
-  if (qids)
-    for (uint64_t i = 0; i < nq; i++)
-      if (qids[i] >= s->n) {
-        ph_set_error("%s: stored query id %llu out of range", call, (unsigned long long)qids[i]);
-        return PHNSW_E_INVALID;
-      }
-  // host words of the per-query ids, alive until the stream has drained (HostBlocks is declared after them)
-  std::vector<uint32_t> h_in, h_len(nq);
+  PH_TRY(ph_stored_ids_check(qids, nq, s->n, call));
   phnsw_labels *mlb = const_cast<phnsw_labels *>(lb);
   PhLabeledSet *set = set_acquire(mlb, nullptr, true);
-  if (!set->stream) {
-    hipError_t e = hipStreamCreateWithFlags(&set->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-      SetGuard g{mlb, set, nullptr};
-      return ph_hip_fail(e, "host path: stream", __FILE__, __LINE__);
-    }
-  }
-  const hipStream_t st = set->stream;
-  SetGuard guard{mlb, set, st};
-  HostBlocks hb{st, {}};
-
+  PhHostCall h(mlb->pool, set);
+  PH_TRY(h.stage_in(s, queries, qids, exclude, nq, (size_t)nq, 0, (uint32_t)k, (uint32_t)k));  // extras: want
   PhLabeledCall c = {};
-  const uint32_t ld = s->ld, kk = (uint32_t)k;
-  if (queries) {  // rows padded to the store's row length
-    float *q = nullptr;
-    PH_TRY(hb.alloc(&q, (size_t)nq * ld * 4u));
-    if (ld != s->dim) {
-      PH_HIP(hipMemsetAsync(q, 0, (size_t)nq * ld * 4u, st));
-      PH_HIP(hipMemcpy2DAsync(q, (size_t)ld * 4u, queries, (size_t)s->dim * 4u, (size_t)s->dim * 4u, nq, hipMemcpyHostToDevice, st));
-    } else {
-      PH_HIP(hipMemcpyAsync(q, queries, (size_t)nq * ld * 4u, hipMemcpyHostToDevice, st));
-    }
-    c.queries = q, c.ldq = ld;
-  }
-  uint32_t *small = nullptr;  // qid | exclude | len | status | want   [5][nq]
-  PH_TRY(hb.alloc(&small, (size_t)nq * 5u * 4u));
-  if (qids || exclude) {
-    h_in.resize(2u * nq);
-    if (qids)
-      for (uint64_t i = 0; i < nq; i++) h_in[i] = (uint32_t)qids[i];
-    if (exclude)
-      for (uint64_t i = 0; i < nq; i++) h_in[nq + i] = exclude[i] >= s->n ? PH_EMPTY32 : (uint32_t)exclude[i];
-    PH_HIP(hipMemcpyAsync(small, h_in.data(), (size_t)nq * 2u * 4u, hipMemcpyHostToDevice, st));
-    if (qids) c.qids = small;
-    if (exclude) c.exclude = small + nq;
-  }
-  PH_HIP(hipMemcpyAsync(small + 4u * nq, want, (size_t)nq * 4u, hipMemcpyHostToDevice, st));
-  c.want = small + 4u * nq;
-  uint32_t *ids = nullptr;
-  float *d = nullptr, *dk = nullptr;
-  uint64_t *ids64 = nullptr;
-  PH_TRY(hb.alloc(&ids, (size_t)nq * kk * 4u));
-  PH_TRY(hb.alloc(&d, (size_t)nq * kk * 4u));
-  PH_TRY(hb.alloc(&ids64, (size_t)nq * kk * 8u));
-  PH_TRY(hb.alloc(&dk, (size_t)nq * kk * 4u));
-  c.nq = nq, c.k = kk;
-  c.out_ids = ids, c.out_d = d, c.out_len = small + 2u * nq, c.status = small + 3u * nq;
-  c.stream = st;
+  h.fill(c);
+  PH_HIP(hipMemcpyAsync(h.extra(), want, (size_t)nq * 4u, hipMemcpyHostToDevice, h.st));
+  c.want = h.extra(), c.k = (uint32_t)k;
   PH_TRY(labeled_run(ix, lb, c, *set));
-  PH_TRY(ph_take_launch(ids, d, kk, kk, nq, ids64, dk, st));  // u32 -> u64 ids, 0xFFFFFFFF -> PHNSW_EMPTY
-  PH_HIP(hipMemcpyAsync(h_len.data(), small + 2u * nq, (size_t)nq * 4u, hipMemcpyDeviceToHost, st));
-  PH_HIP(hipMemcpyAsync(out_ids, ids64, (size_t)nq * kk * 8u, hipMemcpyDeviceToHost, st));
-  PH_HIP(hipMemcpyAsync(out_d, dk, (size_t)nq * kk * 4u, hipMemcpyDeviceToHost, st));
-  PH_HIP(hipStreamSynchronize(st));
-  for (uint64_t i = 0; i < nq; i++) out_len[i] = h_len[i];
-  return 0;
+  return h.finish(out_ids, out_d, out_len);
 } catch (...) { return ph_caught(); }
 
 // ------------------------------------------------------------------ C ABI: a set of labels per query
@@ -1215,7 +1088,7 @@ extern "C" int phnsw_search_exact_labelset_device(const phnsw_index *ix, const p
   PH_HIP(hipSetDevice(ix->store->device));
   phnsw_labels *mlb = const_cast<phnsw_labels *>(lb);
   PhLabeledSet *set = set_acquire(mlb, c.stream, false);
-  SetGuard guard{mlb, set, c.stream};
+  PhSetGuard guard{mlb->pool, set, c.stream};
   return labelset_run(ix, lb, sc, *set);
 } catch (...) { return ph_caught(); }
 
@@ -1241,81 +1114,27 @@ extern "C" int phnsw_search_exact_labelset(const phnsw_index *ix, const phnsw_la
   }
   const phnsw_store *s = ix->store;
   PH_HIP(hipSetDevice(s->device));
-  if (qids)
-    for (uint64_t i = 0; i < nq; i++)
-      if (qids[i] >= s->n) {
-        ph_set_error("%s: query %llu: stored query id %llu out of range", call, (unsigned long long)i,
-                     (unsigned long long)qids[i]);
-        return PHNSW_E_INVALID;
-      }
+  PH_TRY(ph_stored_ids_check(qids, nq, s->n, call, true));
   if (const uint64_t bad = ph_labelset_first_bad(want_first, nq); bad < nq) {
     ph_set_error("%s: query %llu: want_first must start at 0 and never run backwards (want_first[%llu] = %u, want_first[%llu] "
                  "= %u)", call, (unsigned long long)bad, (unsigned long long)bad, want_first[bad], (unsigned long long)bad + 1u,
                  want_first[bad + 1u]);
     return PHNSW_E_INVALID;
   }
-  // host words of the per-query ids, alive until the stream has drained (HostBlocks is declared after them)
-  std::vector<uint32_t> h_in, h_len(nq);
   phnsw_labels *mlb = const_cast<phnsw_labels *>(lb);
   PhLabeledSet *set = set_acquire(mlb, nullptr, true);
-  if (!set->stream) {
-    hipError_t e = hipStreamCreateWithFlags(&set->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-      SetGuard g{mlb, set, nullptr};
-      return ph_hip_fail(e, "host path: stream", __FILE__, __LINE__);
-    }
-  }
-  const hipStream_t st = set->stream;
-  SetGuard guard{mlb, set, st};
-  HostBlocks hb{st, {}};
-
+  PhHostCall h(mlb->pool, set);
+  // extras: want_first [nq + 1] | want_values [nwant]
+  PH_TRY(h.stage_in(s, queries, qids, exclude, nq, (size_t)nq + 1u + (size_t)nwant, 0, (uint32_t)k, (uint32_t)k));
   PhLabelsetCall sc = {};
-  PhLabeledCall &c = sc.c;
-  const uint32_t ld = s->ld, kk = (uint32_t)k;
-  if (queries) {  // rows padded to the store's row length
-    float *q = nullptr;
-    PH_TRY(hb.alloc(&q, (size_t)nq * ld * 4u));
-    if (ld != s->dim) {
-      PH_HIP(hipMemsetAsync(q, 0, (size_t)nq * ld * 4u, st));
-      PH_HIP(hipMemcpy2DAsync(q, (size_t)ld * 4u, queries, (size_t)s->dim * 4u, (size_t)s->dim * 4u, nq, hipMemcpyHostToDevice, st));
-    } else {
-      PH_HIP(hipMemcpyAsync(q, queries, (size_t)nq * ld * 4u, hipMemcpyHostToDevice, st));
-    }
-    c.queries = q, c.ldq = ld;
-  }
-  uint32_t *small = nullptr;  // qid | exclude | len | status | want_first [nq + 1] | want_values [nwant]
-  PH_TRY(hb.alloc(&small, ((size_t)nq * 5u + 1u + (size_t)nwant) * 4u));
-  if (qids || exclude) {
-    h_in.resize(2u * nq);
-    if (qids)
-      for (uint64_t i = 0; i < nq; i++) h_in[i] = (uint32_t)qids[i];
-    if (exclude)
-      for (uint64_t i = 0; i < nq; i++) h_in[nq + i] = exclude[i] >= s->n ? PH_EMPTY32 : (uint32_t)exclude[i];
-    PH_HIP(hipMemcpyAsync(small, h_in.data(), (size_t)nq * 2u * 4u, hipMemcpyHostToDevice, st));
-    if (qids) c.qids = small;
-    if (exclude) c.exclude = small + nq;
-  }
-  PH_HIP(hipMemcpyAsync(small + 4u * nq, want_first, (size_t)(nq + 1u) * 4u, hipMemcpyHostToDevice, st));
-  if (nwant) PH_HIP(hipMemcpyAsync(small + 5u * nq + 1u, want_values, (size_t)nwant * 4u, hipMemcpyHostToDevice, st));
-  sc.want_first = small + 4u * nq, sc.want_values = small + 5u * nq + 1u, sc.nwant = nwant;
-  uint32_t *ids = nullptr;
-  float *d = nullptr, *dk = nullptr;
-  uint64_t *ids64 = nullptr;
-  PH_TRY(hb.alloc(&ids, (size_t)nq * kk * 4u));
-  PH_TRY(hb.alloc(&d, (size_t)nq * kk * 4u));
-  PH_TRY(hb.alloc(&ids64, (size_t)nq * kk * 8u));
-  PH_TRY(hb.alloc(&dk, (size_t)nq * kk * 4u));
-  c.nq = nq, c.k = kk;
-  c.out_ids = ids, c.out_d = d, c.out_len = small + 2u * nq, c.status = small + 3u * nq;
-  c.stream = st;
+  h.fill(sc.c);
+  uint32_t *const first_dev = h.extra(), *const values_dev = first_dev + nq + 1u;
+  PH_HIP(hipMemcpyAsync(first_dev, want_first, (size_t)(nq + 1u) * 4u, hipMemcpyHostToDevice, h.st));
+  if (nwant) PH_HIP(hipMemcpyAsync(values_dev, want_values, (size_t)nwant * 4u, hipMemcpyHostToDevice, h.st));
+  sc.want_first = first_dev, sc.want_values = values_dev, sc.nwant = nwant;
+  sc.c.k = (uint32_t)k;
   PH_TRY(labelset_run(ix, lb, sc, *set));
-  PH_TRY(ph_take_launch(ids, d, kk, kk, nq, ids64, dk, st));  // u32 -> u64 ids, 0xFFFFFFFF -> PHNSW_EMPTY
-  PH_HIP(hipMemcpyAsync(h_len.data(), small + 2u * nq, (size_t)nq * 4u, hipMemcpyDeviceToHost, st));
-  PH_HIP(hipMemcpyAsync(out_ids, ids64, (size_t)nq * kk * 8u, hipMemcpyDeviceToHost, st));
-  PH_HIP(hipMemcpyAsync(out_d, dk, (size_t)nq * kk * 4u, hipMemcpyDeviceToHost, st));
-  PH_HIP(hipStreamSynchronize(st));
-  for (uint64_t i = 0; i < nq; i++) out_len[i] = h_len[i];
-  return 0;
+  return h.finish(out_ids, out_d, out_len);
 } catch (...) { return ph_caught(); }
 
 // ------------------------------------------------------------------ the graph walk by label
@@ -1386,74 +1205,31 @@ extern "C" int phnsw_search_batch_labeled(const phnsw_index *ix, const phnsw_lab
   }
   const phnsw_store *s = ix->store;
   PH_HIP(hipSetDevice(s->device));
-  if (qids)
-    for (uint64_t i = 0; i < nq; i++)
-      if (qids[i] >= s->n) {
-        ph_set_error("%s: stored query id %llu out of range", call, (unsigned long long)qids[i]);
-        return PHNSW_E_INVALID;
-      }
-  // host words of the per-query ids, alive until the stream has drained (HostBlocks is declared after them)
-  std::vector<uint32_t> h_in, h_out(4u * nq), redo;
+  PH_TRY(ph_stored_ids_check(qids, nq, s->n, call));
   phnsw_labels *mlb = const_cast<phnsw_labels *>(lb);
   PhLabeledSet *set = set_acquire(mlb, nullptr, true);
-  if (!set->stream) {
-    hipError_t e = hipStreamCreateWithFlags(&set->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-      SetGuard g{mlb, set, nullptr};
-      return ph_hip_fail(e, "host path: stream", __FILE__, __LINE__);
-    }
-  }
-  const hipStream_t st = set->stream;
-  SetGuard guard{mlb, set, st};
-  HostBlocks hb{st, {}};
-
+  PhHostCall h(mlb->pool, set);
+  // extras: stats(2), which the host reads back with len and status | want | the redo list
+  PH_TRY(h.stage_in(s, queries, qids, exclude, nq, (size_t)nq * 4u, 2, ef, k ? (uint32_t)k : ef));
+  uint32_t *const want_dev = h.extra() + 2u * nq, *const redo_dev = want_dev + nq;
   PhSearchCall c = {};
-  const uint32_t ld = s->ld, kk = k ? (uint32_t)k : ef;
-  if (queries) {  // rows padded to the store's row length
-    float *q = nullptr;
-    PH_TRY(hb.alloc(&q, (size_t)nq * ld * 4u));
-    if (ld != s->dim) {
-      PH_HIP(hipMemsetAsync(q, 0, (size_t)nq * ld * 4u, st));
-      PH_HIP(hipMemcpy2DAsync(q, (size_t)ld * 4u, queries, (size_t)s->dim * 4u, (size_t)s->dim * 4u, nq, hipMemcpyHostToDevice, st));
-    } else {
-      PH_HIP(hipMemcpyAsync(q, queries, (size_t)nq * ld * 4u, hipMemcpyHostToDevice, st));
-    }
-    c.queries = q, c.ldq = ld;
-  }
-  uint32_t *small = nullptr;  // qid | exclude | want | redo list | len | status | stats(2)   [8][nq]
-  PH_TRY(hb.alloc(&small, (size_t)nq * 8u * 4u));
-  h_in.resize(3u * nq);
-  if (qids)
-    for (uint64_t i = 0; i < nq; i++) h_in[i] = (uint32_t)qids[i];
-  if (exclude)
-    for (uint64_t i = 0; i < nq; i++) h_in[nq + i] = exclude[i] >= s->n ? PH_EMPTY32 : (uint32_t)exclude[i];
-  for (uint64_t i = 0; i < nq; i++) h_in[2u * nq + i] = want[i];
-  PH_HIP(hipMemcpyAsync(small, h_in.data(), (size_t)nq * 3u * 4u, hipMemcpyHostToDevice, st));
-  if (qids) c.qids = small;
-  if (exclude) c.exclude = small + nq;
-  c.filter.label_of = lb->label_of, c.filter.want = small + 2u * nq, c.filter.flags = flags;
-  uint32_t *ids = nullptr;
-  float *d = nullptr, *dk = nullptr;
-  uint64_t *ids64 = nullptr;
-  PH_TRY(hb.alloc(&ids, (size_t)nq * ef * 4u));
-  PH_TRY(hb.alloc(&d, (size_t)nq * ef * 4u));
-  PH_TRY(hb.alloc(&ids64, (size_t)nq * kk * 8u));
-  PH_TRY(hb.alloc(&dk, (size_t)nq * kk * 4u));
-  c.nq = nq, c.sp = sp, c.upto = upto_layers;
-  c.out_ids = ids, c.out_d = d, c.out_len = small + 4u * nq, c.status = small + 5u * nq, c.out_stats = small + 6u * nq;
-  c.stream = st;
+  h.fill(c);
+  PH_HIP(hipMemcpyAsync(want_dev, want, (size_t)nq * 4u, hipMemcpyHostToDevice, h.st));
+  c.filter.label_of = lb->label_of, c.filter.want = want_dev, c.filter.flags = flags;
+  c.sp = sp, c.upto = upto_layers, c.out_stats = h.extra();
+  std::vector<uint32_t> &redo = h.h_list;  // read by a copy: kept by h, changed only behind the next sync
   uint32_t ovf_cap = ph_default_ovf_cap(ef);
   for (int attempt = 0;; attempt++) {
     PH_TRY(ph_search_device(ix, c));
-    PH_HIP(hipMemcpyAsync(h_out.data(), small + 4u * nq, (size_t)nq * 4u * 4u, hipMemcpyDeviceToHost, st));
-    PH_HIP(hipStreamSynchronize(st));
+    PH_TRY(h.download_words());
+    PH_TRY(h.sync());
     redo.clear();
     for (uint64_t i = 0; i < nq; i++) {
-      if (h_out[nq + i] == 4u) {
+      if (h.status(i) == 4u) {
         ph_set_error("search: a candidate vector is missing from a lower layer (layers not nested, lib.rs:261)");
         return PHNSW_E_MISSING_NODE;
       }
-      if (h_out[nq + i] == 5u) redo.push_back((uint32_t)i);
+      if (h.status(i) == 5u) redo.push_back((uint32_t)i);
     }
     if (redo.empty()) break;
     if (attempt == 3) {
@@ -1462,15 +1238,11 @@ extern "C" int phnsw_search_batch_labeled(const phnsw_index *ix, const phnsw_lab
     }
     // the overflowed queries alone, from a device list, with 8x the room: everything stays addressed by the query index
     ovf_cap *= 8;
-    PH_HIP(hipMemcpyAsync(small + 3u * nq, redo.data(), redo.size() * 4u, hipMemcpyHostToDevice, st));
-    c.order = small + 3u * nq, c.nq = redo.size(), c.ovf_cap = ovf_cap;
+    PH_TRY(h.upload_list(redo_dev));
+    c.order = redo_dev, c.nq = redo.size(), c.ovf_cap = ovf_cap;
   }
-  PH_TRY(ph_take_launch(ids, d, ef, kk, nq, ids64, dk, st));  // u32 -> u64 ids, 0xFFFFFFFF -> PHNSW_EMPTY
-  PH_HIP(hipMemcpyAsync(out_ids, ids64, (size_t)nq * kk * 8u, hipMemcpyDeviceToHost, st));
-  PH_HIP(hipMemcpyAsync(out_d, dk, (size_t)nq * kk * 4u, hipMemcpyDeviceToHost, st));
-  PH_HIP(hipStreamSynchronize(st));
-  for (uint64_t i = 0; i < nq; i++) out_len[i] = std::min<uint32_t>(h_out[i], kk);
+  PH_TRY(h.finish(out_ids, out_d, out_len));
   if (out_stats)
-    for (uint64_t i = 0; i < 2u * nq; i++) out_stats[i] = h_out[2u * nq + i];
+    for (uint64_t i = 0; i < 2u * nq; i++) out_stats[i] = h.read_extra(0, i);
   return 0;
 } catch (...) { return ph_caught(); }

@@ -241,9 +241,12 @@ struct PhExactScratch {
   hipEvent_t done = nullptr;
 };
 
-struct PhAutoSet;  // filter_auto.hip: the scratch of one routed filtered search, one per concurrent call
-struct PhDenseSet;  // filter_dense.hip: the scratch of one exact search for a shared allow-list, one per concurrent call
-struct PhGroupedSet;  // filter_grouped.hip: the scratch of one exact search over a table of allow-lists, one per concurrent call
+// call_set.h: the scratch sets of one kind of filtered or exact call, one set per call in flight, handed out under mutex
+struct PhCallSet;
+struct PhCallPool {
+  std::mutex mutex;
+  std::vector<PhCallSet *> sets;
+};
 struct PhPendingLayer;
 struct PhHostStage;  // hostpath.hip: persistent staging of the host-pointer search entry points
 struct phnsw_index {
@@ -274,12 +277,9 @@ struct phnsw_index {
   std::mutex exact_mutex;  // filter_exact.hip
   PhExactScratch exact[2];
   uint32_t exact_next = 0;
-  std::vector<PhAutoSet *> autos;  // filter_auto.hip: handed out under auto_mutex
-  std::mutex auto_mutex;
-  std::vector<PhDenseSet *> denses;  // filter_dense.hip: handed out under dense_mutex
-  std::mutex dense_mutex;
-  std::vector<PhGroupedSet *> groupeds;  // filter_grouped.hip: handed out under grouped_mutex
-  std::mutex grouped_mutex;
+  PhCallPool autos;     // filter_auto.hip: PhAutoSet, the scratch of one routed filtered search
+  PhCallPool denses;    // filter_dense.hip: PhDenseSet, of one exact search for a shared allow-list
+  PhCallPool groupeds;  // filter_grouped.hip: PhGroupedSet, of one exact search over a table of allow-lists
 };
 
 // ---- kernel argument block for the batched greedy search ----
@@ -394,6 +394,16 @@ hipError_t ph_timed_free(void *p);
 #define hipMalloc(p, n) ph_timed_malloc((void **)(p), (n))
 #define hipFree(p) ph_timed_free((void *)(p))
 #endif
+// a knob of the environment as a number, 0 when unset; read per call: the tests switch them
+static inline long long env_ll(const char *name) {
+  const char *e = getenv(name);
+  return e ? atoll(e) : 0;
+}
+// the grid of a kernel whose 256-thread blocks stride over `items`
+static inline uint32_t grid1(uint64_t items) {
+  const uint64_t blocks = (items + 255u) / 256u;
+  return (uint32_t)(blocks < (1u << 16) ? blocks : (1u << 16));
+}
 int ph_stream_beside(hipStream_t other, hipStream_t *io);  // a non-blocking stream on another hardware queue than `other` (misc.hip)
 hipError_t ph_pool_alloc(void **p, size_t bytes);
 void ph_pool_free(void *p);
