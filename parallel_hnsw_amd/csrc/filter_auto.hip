@@ -271,9 +271,8 @@ extern "C" int phnsw_search_filtered_auto_device(const phnsw_index *ix, const fl
   const char *const call = "phnsw_search_filtered_auto_device";
   PH_TRY(auto_check(ix, sp, k, call));
   if (nq == 0) return 0;
-  if (!ph_auto_queries_valid(queries_dev != nullptr, qids_dev != nullptr) || !out_ids_dev || !out_d_dev || !out_len_dev ||
-      !status_dev || !ph_auto_nq_valid(nq) ||
-      (queries_dev && (ldq < ix->store->ld || (ldq % 4) || ((uintptr_t)queries_dev % 16)))) {
+  if (!ph_device_queries_ok(ix, queries_dev, qids_dev, ldq) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev ||
+      !ph_auto_nq_valid(nq)) {
     ph_set_error("%s: invalid argument (queries or qids, exactly one; outputs; queries need ldq >= store ld, multiple of 4, "
                  "16-byte base)", call);
     return PHNSW_E_INVALID;
@@ -373,9 +372,8 @@ extern "C" int phnsw_search_labeled_auto_device(const phnsw_index *ix, const phn
   PH_TRY(auto_check(ix, sp, k, call));
   PH_TRY(ph_labeled_check(ix, lb, k, call));
   if (nq == 0) return 0;
-  if (!ph_auto_queries_valid(queries_dev != nullptr, qids_dev != nullptr) || !out_ids_dev || !out_d_dev || !out_len_dev ||
-      !status_dev || !want_dev || !ph_auto_nq_valid(nq) || nq > 0x7FFFFFFEull ||
-      (queries_dev && (ldq < ix->store->ld || (ldq % 4) || ((uintptr_t)queries_dev % 16)))) {
+  if (!ph_device_queries_ok(ix, queries_dev, qids_dev, ldq) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev ||
+      !want_dev || !ph_auto_nq_valid(nq) || nq > 0x7FFFFFFEull) {
     ph_set_error("%s: invalid argument (queries or qids, exactly one; outputs; want; queries need ldq >= store ld, multiple "
                  "of 4, 16-byte base)", call);
     return PHNSW_E_INVALID;

@@ -7,17 +7,19 @@
 //      ph_dense_prefix_kernel   their exclusive prefix over the ceil(n / 32) words; the total is the list's length
 //      ph_dense_list_kernel     every word writes its ids at its offset: the ascending VectorId list of the candidates
 //      -- the host reads the length c (the one synchronisation); c == 0 writes empty rows and returns
-//   3. ph_dense_qids_kernel     Stored queries: ids at or past n replaced by 0 and flagged (the pack kernel reads rows
-//                               unchecked); the select reports them, status 4 and an empty row, as the scan does
-//   4. per node chunk, per position chunk (dense_plan.h): ph_tiny_table_chunk (tiny.hip) -- the existing table
-//      kernels, the per-hop bits -- into D[positions][stride]
-//   5. ph_dense_select_kernel   one wave64 per position: the running top-k of (distance, id) keys over the chunk's row
+//   3. ph_dense_qids_kernel     Stored queries: ids at or past n replaced by 0 (the pack kernel reads rows unchecked)
+//                               and given the status word the select reports them with: 4 and an empty row, as the scan
+//   4. ph_table_run: per node chunk, per position chunk (dense_plan.h): ph_tiny_table_chunk (tiny.hip) -- the search's
+//      table kernels, the per-hop bits -- into D[positions][stride]
+//   5. ph_table_select_kernel   one wave64 per position: the running top-k of (distance, id) keys over the chunk's row
 //                               of D, carried between node chunks in a [nq][k] key scratch; after the last node chunk
 //                               the row is written
 //
 // The keys are distinct, so the k smallest are one set in one order whatever the chunk sizes; the distances are the
 // table's, i.e. phnsw_distance_batch's bits, so a row equals phnsw_search_exact_filtered's row bit for bit.
-// The table kernels, their pack / quant kernels and the scan are untouched (profiles/filter_dense/).
+// Steps 4 and 5 also serve every group of filter_grouped.hip: position p is then query order[p], and a query may be
+// refused for its selector or its group's bitmap.  The running top-k, the block scan and the row writer are
+// exact_topk.h's (profiles/exact_once/).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -29,6 +31,7 @@
 #include "exact_slices.h"
 #include "exact_topk.h"
 #include "filter_candidate.h"
+#include "group_plan.h"
 #include "host_call.h"
 #include "phnsw_device.h"
 
@@ -52,30 +55,14 @@ __global__ __launch_bounds__(256) void ph_dense_popc_kernel(PhDenseListArgs a) {
     a.off[w] = (uint32_t)__popc(ph_exact_word(a.filter, (uint32_t)w, a.nwords, nlim, a.vec2node));
 }
 
-// One workgroup walks the counts 1024 at a time and leaves their exclusive prefix in place: a shuffle scan per wave,
-// the 16 waves' totals through LDS, the running base in every thread.  The total is at most n <= 2^31 - 1.
+// One workgroup walks the counts 1024 at a time and leaves their exclusive prefix in place (ph_block_exclusive_scan).
+// The total is at most n <= 2^31 - 1.
 __global__ __launch_bounds__(1024) void ph_dense_prefix_kernel(PhDenseListArgs a) {
-  __shared__ uint32_t wave_total[16];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   uint32_t base = 0;
   for (uint64_t at = 0; at < a.nwords; at += 1024u) {
     const uint64_t w = at + threadIdx.x;
-    const uint32_t v = w < a.nwords ? a.off[w] : 0u;
-    uint32_t incl = v;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-      const uint32_t t = __shfl_up(incl, d);
-      if (lane >= d) incl += t;
-    }
-    if (lane == 63u) wave_total[wave] = incl;
-    __syncthreads();
-    uint32_t before = base, all = 0;
-    for (uint32_t i = 0; i < 16u; i++) {
-      if (i < wave) before += wave_total[i];
-      all += wave_total[i];
-    }
-    if (w < a.nwords) a.off[w] = before + incl - v;
-    base += all;
+    const uint32_t before = ph_block_exclusive_scan(w < a.nwords ? a.off[w] : 0u, base);
+    if (w < a.nwords) a.off[w] = before;
     __syncthreads();  // the totals are rewritten by the next 1024
   }
   if (threadIdx.x == 0) a.off[a.nwords] = base, a.head[1] = base;
@@ -93,25 +80,27 @@ __global__ __launch_bounds__(256) void ph_dense_list_kernel(PhDenseListArgs a) {
 }
 
 // Stored queries as the table kernels may read them: an id at or past n becomes 0 (n >= 1: the index has a bottom layer
-// with candidates when this runs into a table) and its flag is set
+// with candidates when this runs into a table) and its word of `refuse` is the status the select reports for it
 __global__ __launch_bounds__(256) void ph_dense_qids_kernel(const uint32_t *qids, uint64_t nq, uint32_t n, uint32_t *safe,
-                                                            uint32_t *flags) {
+                                                            uint32_t *refuse) {
   for (uint64_t q = (uint64_t)blockIdx.x * 256u + threadIdx.x; q < nq; q += (uint64_t)gridDim.x * 256u) {
     const uint32_t v = qids[q];
     safe[q] = v < n ? v : 0u;
-    flags[q] = v < n ? 0u : 1u;
+    refuse[q] = v < n ? ST_OK : ST_MISSING;
   }
 }
 
 // ------------------------------------------------------------------ the select
 
-struct PhDenseSelectArgs {
+struct PhTableSelectArgs {
   const float *D;          // [npos][stride]: the table of this (node chunk, position chunk); unread when tn == 0
   uint32_t stride, tn;     // tn <= stride
-  uint32_t npos, pos_first;  // positions of this chunk; position p is query pos_first + p
+  uint32_t npos, pos_first;  // positions of this chunk
+  const uint32_t *order;   // [npos]: position p is query order[p]; nullptr: query pos_first + p
   const uint32_t *list;    // [tn]: the node chunk's VectorIds, ascending
   const uint32_t *exclude;  // [nq] or nullptr
-  const uint32_t *flags;    // [nq] or nullptr: a Stored query id at or past n
+  const uint32_t *refuse;   // [nq] or nullptr: 0, or the status of a refused query
+  const uint32_t *changed;  // nullptr, or the group's word: nonzero = its bitmap changed while the call read it
   uint64_t *keys;           // [nq][k]: the running top-k between node chunks, ascending, KEY_NONE padded
   uint32_t k;
   uint32_t first, last;  // the first node chunk starts empty; the last one writes the row
@@ -120,44 +109,29 @@ struct PhDenseSelectArgs {
   uint32_t *out_len, *status;  // [nq]
 };
 
-// One wave64 per position.  The row of D is read 64 entries at a time, coalesced; a batch is one ballot against the
-// current k-th key (PhExactTopK::insert) and most batches end there once the list is full.
-__global__ __launch_bounds__(64) void ph_dense_select_kernel(PhDenseSelectArgs a) {
-  extern __shared__ uint64_t dense_keys[];  // ph_dense_select_lds(k)
+// One wave64 per position; the row of the table goes by the position, the exclude, the refusal and the key scratch by
+// the query.  A batch of the row is one ballot against the current k-th key (PhExactTopK::insert) and most batches end
+// there once the list is full.  A refused query gets the empty row and its status.
+__global__ __launch_bounds__(64) void ph_table_select_kernel(PhTableSelectArgs a) {
+  extern __shared__ uint64_t select_keys[];  // ph_dense_select_lds(k)
   const uint32_t lane = threadIdx.x;
+  const uint32_t changed = a.changed && a.changed[0] ? PH_GROUP_ST_CHANGED : ST_OK;
   for (uint32_t p = blockIdx.x; p < a.npos; p += gridDim.x) {
-    const uint32_t q = a.pos_first + p;  // < nq <= 2^32 - 1
+    const uint32_t q = a.order ? a.order[p] : a.pos_first + p;  // < nq <= 2^32 - 1
     __syncthreads();  // the previous position's lists are done with
     PhExactTopK top;
-    top.cur = dense_keys, top.nxt = dense_keys + a.k, top.sv = dense_keys + 2u * a.k, top.len = 0, top.k = a.k;
+    top.init(select_keys, a.k);
     uint64_t *const mine = a.keys + (uint64_t)q * a.k;
-    const bool bad_query = a.flags && a.flags[q] != 0u;
-    if (!a.first) {
-      uint32_t have = 0;
-      for (uint32_t i = lane; i < a.k; i += 64u) {
-        const uint64_t key = mine[i];
-        top.cur[i] = key;
-        have += key != KEY_NONE ? 1u : 0u;
-      }
-#pragma unroll
-      for (int sft = 32; sft >= 1; sft >>= 1) have += __shfl_xor(have, sft);
-      top.len = have;  // the padding is KEY_NONE and no key is (mkkey keeps bit 31 of the id word clear)
-      __syncthreads();
-    }
-    if (!bad_query) {
-      const uint32_t ex = a.exclude ? a.exclude[q] : PH_EMPTY32;
-      const float *const row = a.D + (uint64_t)p * a.stride;
-      for (uint32_t b = 0; b < a.tn; b += 64u) {
-        const uint32_t j = b + lane;
-        const bool ok = j < a.tn;  // tn <= stride: inside the row
-        const uint32_t id = ok ? a.list[j] : PH_EMPTY32;
-        top.insert(ok && id != ex ? mkkey(row[j], id) : KEY_NONE, lane);
-      }
-    }
+    const uint32_t why = a.refuse ? a.refuse[q] : ST_OK;
+    const uint32_t refused = why ? why : changed;
+    if (!a.first) top.load(mine, lane);
+    if (!refused)
+      top.insert_row(a.D + (uint64_t)p * a.stride, a.list, a.tn, a.exclude ? a.exclude[q] : PH_EMPTY32, lane);
     if (a.last) {
-      ph_exact_write_row(a, q, top.cur, top.len, bad_query, lane);
+      ph_exact_write_row(a, q, top.cur, refused ? 0u : top.len, false, lane);
+      if (lane == 0 && refused) a.status[q] = refused;  // 4, 6 or 7 after the row writer's 0, same lane
     } else {
-      for (uint32_t i = lane; i < a.k; i += 64u) mine[i] = i < top.len ? top.cur[i] : KEY_NONE;
+      ph_exact_store_list(mine, top.cur, top.len, a.k, lane);
     }
   }
 }
@@ -191,9 +165,9 @@ struct PhDenseCall {
 
 namespace {
 
-int select_launch(const PhDenseCall &c, PhDenseSelectArgs &a) {
-  hipLaunchKernelGGL(ph_dense_select_kernel, dim3(std::min<uint32_t>(a.npos, 1u << 20)), dim3(64),
-                     (size_t)ph_dense_select_lds(c.k), c.stream, a);
+int select_launch(const PhTableRun &r, const PhTableSelectArgs &a) {
+  hipLaunchKernelGGL(ph_table_select_kernel, dim3(std::min<uint32_t>(a.npos, 1u << 20)), dim3(64),
+                     (size_t)ph_dense_select_lds(r.k), r.stream, a);
   PH_HIP(hipGetLastError());
   return 0;
 }
@@ -202,9 +176,6 @@ int select_launch(const PhDenseCall &c, PhDenseSelectArgs &a) {
 int dense_run(const phnsw_index *ix, const PhDenseCall &c, PhDenseSet &set) {
   const phnsw_store *s = ix->store;
   const uint64_t nq = c.nq, nwords = ph_exact_words(s->n);
-  // the packed operand's key describes a list that is scratch: whichever way the last call on this set ended, this one
-  // writes other ids there
-  set.ws.tiny_pack_key.valid = false;
   PH_TRY(set.ready());
   if (!set.h_head) PH_HIP(hipHostMalloc((void **)&set.h_head, PH_DENSE_HEAD_WORDS * 4u, hipHostMallocDefault));
   PhDenseListArgs l = {};
@@ -213,7 +184,7 @@ int dense_run(const phnsw_index *ix, const PhDenseCall &c, PhDenseSet &set) {
   l.cap = (uint32_t)std::min<uint64_t>(s->n, l.n_nodes);  // a candidate is a vector of the bottom layer
   PH_TRY(set.block_ensure(&set.pre, &set.pre_bytes, (size_t)ph_dense_pre_words(nwords, l.cap, nq) * 4u, c.stream));
   uint32_t *const head = (uint32_t *)set.pre, *const off = head + PH_DENSE_HEAD_WORDS, *const list = off + ph_dense_off_words(nwords);
-  uint32_t *const safe = list + l.cap, *const flags = safe + nq;
+  uint32_t *const safe = list + l.cap, *const refuse = safe + nq;
   l.head = head, l.off = off, l.list = list;
 
   StepTimes times;  // pack and table are one figure: both are enqueued inside tiny_table
@@ -233,7 +204,7 @@ int dense_run(const phnsw_index *ix, const PhDenseCall &c, PhDenseSet &set) {
   }
   if (c.qids)
     hipLaunchKernelGGL(ph_dense_qids_kernel, dim3((uint32_t)std::min<uint64_t>((nq + 255u) / 256u, 1u << 16)), dim3(256), 0,
-                       c.stream, c.qids, nq, (uint32_t)s->n, safe, flags);
+                       c.stream, c.qids, nq, (uint32_t)s->n, safe, refuse);
   PH_HIP(hipGetLastError());
   times.end();
   PH_HIP(hipMemcpyAsync(set.h_head, head, 8, hipMemcpyDeviceToHost, c.stream));
@@ -245,51 +216,22 @@ int dense_run(const phnsw_index *ix, const PhDenseCall &c, PhDenseSet &set) {
     return PHNSW_E_INVALID;
   }
 
-  PhDenseSelectArgs a = {};
-  a.exclude = c.exclude, a.flags = c.qids ? flags : nullptr, a.k = c.k;
-  a.out_ids = c.out_ids, a.out_d = c.out_d, a.out_len = c.out_len, a.status = c.status;
-  if (cand == 0) {  // empty rows (and the status of a Stored query id at or past n) from the select itself
-    a.npos = (uint32_t)nq, a.first = 1u, a.last = 1u;
-    return select_launch(c, a);
+  PhTableRun r = {};
+  r.queries = c.queries, r.ldq = c.ldq, r.qids = c.qids ? safe : nullptr, r.npos = nq, r.list = list, r.cand = cand;
+  r.exclude = c.exclude, r.refuse = c.qids ? refuse : nullptr, r.k = c.k;
+  r.out_ids = c.out_ids, r.out_d = c.out_d, r.out_len = c.out_len, r.status = c.status;
+  r.stream = c.stream, r.times = &times, r.step_table = 2, r.step_select = 3;
+  r.verbose_prefix = "exact shared table: ", r.call = "exact shared search";
+  if (cand) {
+    r.nodes_knob = ph_dense_nodes_knob(env_ll("PHNSW_DENSE_NODES"));
+    r.bytes_knob = ph_dense_bytes_knob(env_ll("PHNSW_DENSE_TABLE_BYTES"));
+    const PhDensePlan plan = ph_dense_plan(cand, nq, r.nodes_knob, r.bytes_knob);
+    PH_TRY(set.block_ensure(&set.post, &set.post_bytes, (size_t)ph_dense_post_bytes(plan, c.k), c.stream));
+    r.keys = (uint64_t *)set.post, r.D = (float *)((char *)set.post + ph_dense_key_bytes(nq, c.k));
   }
-  const PhDensePlan plan = ph_dense_plan(cand, nq, ph_dense_nodes_knob(env_ll("PHNSW_DENSE_NODES")),
-                                         ph_dense_bytes_knob(env_ll("PHNSW_DENSE_TABLE_BYTES")));
-  PH_TRY(set.block_ensure(&set.post, &set.post_bytes, (size_t)ph_dense_post_bytes(plan, c.k), c.stream));
-  a.keys = (uint64_t *)set.post;
-  float *const D = (float *)((char *)set.post + ph_dense_key_bytes(nq, c.k));
-  a.D = D;
-  const bool verbose = getenv("PHNSW_VERBOSE") != nullptr;
-  for (uint32_t i = 0; i < plan.node_chunks; i++) {
-    uint64_t nfirst;
-    ph_dense_node_chunk(plan, i, &nfirst, &a.tn, &a.stride);
-    a.list = list + nfirst;  // nfirst + tn <= cand <= cap
-    a.first = i == 0 ? 1u : 0u, a.last = i + 1u == plan.node_chunks ? 1u : 0u;
-    // the packed node operand is kept under the list's ADDRESS and length, not its contents: it may serve the position
-    // chunks of this node chunk and nothing else
-    set.ws.tiny_pack_key.valid = false;
-    for (uint64_t j = 0; j < plan.pos_chunks; j++) {
-      uint64_t pfirst;
-      ph_dense_pos_chunk(plan, j, &pfirst, &a.npos);
-      a.pos_first = (uint32_t)pfirst;
-      bool kept = false;
-      times.begin(2);
-      const int trc = ph_tiny_table_chunk(ix, set.ws, c.queries ? c.queries + pfirst * c.ldq : nullptr, c.ldq,
-                                          c.qids ? safe + pfirst : nullptr, a.npos, a.list, a.tn, D, c.stream, &kept);
-      times.end();
-      if (trc > 0) {
-        ph_set_error("exact shared search: no device memory for the table's operands (%u positions x %u candidates)", a.npos, a.tn);
-        return PHNSW_E_HIP;
-      }
-      if (trc) return trc;
-      if (verbose)
-        fprintf(stderr, "[phnsw] exact shared table: node chunk %u/%u (%u ids), positions %llu..+%u, %s, node operand %s\n", i + 1u,
-                plan.node_chunks, a.tn, (unsigned long long)pfirst, a.npos,
-                set.ws.tiny_table_g ? "matrix cores" : "vector units", kept ? "kept" : "packed");
-      times.begin(3);
-      PH_TRY(select_launch(c, a));
-      times.end();
-    }
-  }
+  if (!cand) times.on = false;  // empty rows (and the status of a Stored query id at or past n): nothing timed or printed
+  PH_TRY(ph_table_run(ix, set.ws, r));
+  if (!cand) return 0;
   float ms[4];
   if (times.collect(ms, 4))
     fprintf(stderr, "[phnsw] exact_shared: %llu queries x %llu candidates: count %.3f ms, list %.3f ms, pack+table %.3f ms, select %.3f ms\n",
@@ -298,6 +240,61 @@ int dense_run(const phnsw_index *ix, const PhDenseCall &c, PhDenseSet &set) {
 }
 
 }  // namespace
+
+// Node chunks x position chunks of one run (phnsw_internal.h): the table of a chunk (ph_tiny_table_chunk), then its
+// select; without candidates the select alone, over no table.  The packed node operand is kept under the list's ADDRESS
+// and length, not its contents, and the list is scratch that runs and rounds reuse: the key is dropped per run and per
+// node chunk, so the operand serves the position chunks of one node chunk and nothing else.
+int ph_table_run(const phnsw_index *ix, PhWorkspace &ws, const PhTableRun &r) {
+  PhTableSelectArgs a = {};
+  a.exclude = r.exclude, a.refuse = r.refuse, a.changed = r.changed, a.keys = r.keys, a.k = r.k;
+  a.out_ids = r.out_ids, a.out_d = r.out_d, a.out_len = r.out_len, a.status = r.status;
+  ws.tiny_pack_key.valid = false;
+  if (r.cand == 0) {
+    a.order = r.order ? r.order + r.first : nullptr, a.pos_first = (uint32_t)r.first, a.npos = (uint32_t)r.npos;
+    a.first = 1u, a.last = 1u;
+    r.times->begin(r.step_select);
+    PH_TRY(select_launch(r, a));
+    r.times->end();
+    return 0;
+  }
+  const PhDensePlan plan = ph_dense_plan(r.cand, r.npos, r.nodes_knob, r.bytes_knob);
+  a.D = r.D;
+  const bool verbose = getenv("PHNSW_VERBOSE") != nullptr;
+  for (uint32_t i = 0; i < plan.node_chunks; i++) {
+    uint64_t nfirst;
+    ph_dense_node_chunk(plan, i, &nfirst, &a.tn, &a.stride);
+    a.list = r.list + nfirst;  // nfirst + tn <= cand
+    a.first = i == 0 ? 1u : 0u, a.last = i + 1u == plan.node_chunks ? 1u : 0u;
+    ws.tiny_pack_key.valid = false;
+    for (uint64_t j = 0; j < plan.pos_chunks; j++) {
+      uint64_t pfirst;
+      ph_dense_pos_chunk(plan, j, &pfirst, &a.npos);
+      const uint64_t at = r.first + pfirst;
+      a.order = r.order ? r.order + at : nullptr, a.pos_first = (uint32_t)at;
+      // with an order the table kernels address the whole batch's queries by it, without one the chunk's own
+      const float *const queries = r.queries && !r.order ? r.queries + at * r.ldq : r.queries;
+      const uint32_t *const qids = r.qids && !r.order ? r.qids + at : r.qids;
+      bool kept = false;
+      r.times->begin(r.step_table);
+      const int trc = ph_tiny_table_chunk(ix, ws, queries, r.ldq, qids, a.order, a.npos, a.list, a.tn, r.D, r.stream, &kept);
+      r.times->end();
+      if (trc > 0) {
+        ph_set_error("%s: no device memory for the table's operands (%u positions x %u candidates)", r.call, a.npos, a.tn);
+        return PHNSW_E_HIP;
+      }
+      if (trc) return trc;
+      if (verbose)
+        fprintf(stderr, "[phnsw] %snode chunk %u/%u (%u ids), positions %llu..+%u, %s, node operand %s\n", r.verbose_prefix, i + 1u,
+                plan.node_chunks, a.tn, (unsigned long long)pfirst, a.npos, ws.tiny_table_g ? "matrix cores" : "vector units",
+                kept ? "kept" : "packed");
+      r.times->begin(r.step_select);
+      PH_TRY(select_launch(r, a));
+      r.times->end();
+    }
+  }
+  return 0;
+}
 
 // the checks every entry point makes (filter_grouped.hip's too) before it looks at another argument: index, k, store kind and row length
 int ph_dense_check(const phnsw_index *ix, uint64_t k, const char *call) {
@@ -346,8 +343,8 @@ extern "C" int phnsw_search_exact_shared_device(const phnsw_index *ix, const flo
   const char *const call = "phnsw_search_exact_shared_device";
   PH_TRY(ph_dense_check(ix, k, call));
   if (nq == 0) return 0;
-  if (((!queries_dev) == (!qids_dev)) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev || nq > 0xFFFFFFFFull ||
-      (queries_dev && (ldq < ix->store->ld || (ldq % 4) || ((uintptr_t)queries_dev % 16)))) {
+  if (!ph_device_queries_ok(ix, queries_dev, qids_dev, ldq) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev ||
+      nq > 0xFFFFFFFFull) {
     ph_set_error("%s: invalid argument (queries or qids, exactly one; outputs; queries need ldq >= store ld, multiple of 4, "
                  "16-byte base)", call);
     return PHNSW_E_INVALID;

@@ -11,10 +11,11 @@
 // The keys are distinct (the id is part of the key), so the k smallest are one set in one order: the result does not
 // depend on how the bitmap is cut into slices (exact_slices.h), nor on the order in which candidates arrive.
 //
-// Kernels of this file only: no existing kernel, and no translation unit that holds one, is touched
-// (profiles/filter_exact/).  The candidate test lives in filter_candidate.h, shared with filter_auto.hip, whose routed
-// call also scans a LIST of queries (PhExactCall::list): work goes by list position, everything else by the query index.
-// The running top-k and the row writer live in exact_topk.h, shared with filter_dense.hip (a shared bitmap as a table).
+// The candidate test lives in filter_candidate.h, shared with filter_auto.hip, whose routed call also scans a LIST of
+// queries (PhExactCall::list): work goes by list position, everything else by the query index.  The running top-k, the
+// list feed, the row writer and the block sum live in exact_topk.h, shared with filter_dense.hip, filter_grouped.hip and
+// filter_labeled.hip (profiles/exact_once/).  ph_resident_waves, the launch preparation of every one-wave kernel of the
+// family, is here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -45,15 +46,6 @@ struct PhExactArgs {
   uint32_t *out_len, *status;  // [nq]
 };
 
-__device__ __forceinline__ uint32_t ph_wave_inclusive_sum(uint32_t v, uint32_t lane) {
-#pragma unroll
-  for (uint32_t d = 1; d < 64u; d <<= 1) {
-    const uint32_t t = __shfl_up(v, d);
-    if (lane >= d) v += t;
-  }
-  return v;
-}
-
 // One wave64 per (query, slice of the bitmap); work item = slice * nq + q (slice-major, query-minor): the waves resident
 // together walk the same part of the id range, so with a shared bitmap they read the same rows and L2 can serve them.
 template <class Dist>
@@ -75,7 +67,7 @@ __global__ __launch_bounds__(64) void ph_exact_scan_kernel(PhExactArgs a) {
     else if (!bad_query)
       dist.prepare_stored(a.dist, a.qids[q], exact_lds, lane);
     PhExactTopK top;
-    top.cur = keys, top.nxt = keys + a.k, top.sv = keys + 2u * a.k, top.len = 0, top.k = a.k;
+    top.init(keys, a.k);
     const uint32_t *const bitmap = a.filter ? a.filter + (uint64_t)q * a.filter_stride : nullptr;
     const uint32_t ex = a.exclude ? a.exclude[q] : PH_EMPTY32;
     uint64_t p0, p1;
@@ -101,17 +93,11 @@ __global__ __launch_bounds__(64) void ph_exact_scan_kernel(PhExactArgs a) {
       }
       __syncthreads();  // the next pass overwrites the staged ids
     }
-    if (a.slices == 1u) {
-      ph_exact_write_row(a, q, top.cur, top.len, bad_query, lane);
-    } else {
-      uint64_t *const out = a.scratch + ((uint64_t)pos * a.slices + slice) * a.k;
-      for (uint32_t i = lane; i < a.k; i += 64u) out[i] = i < top.len ? top.cur[i] : KEY_NONE;
-    }
+    ph_exact_write_slice<false>(a, q, pos, slice, top.cur, top.len, bad_query, lane);
   }
 }
 
-// One wave per query: the slices' ascending lists merged through the same running top-k.  A list is fed 64 keys at a
-// time and left at the first batch without a survivor -- whatever follows in it is larger still.
+// One wave per query: the slices' ascending lists merged through the same running top-k (PH_EXACT_FEED).
 __global__ __launch_bounds__(64) void ph_exact_merge_kernel(PhExactArgs a) {
   extern __shared__ float exact_lds[];
   const uint32_t lane = threadIdx.x;
@@ -120,12 +106,9 @@ __global__ __launch_bounds__(64) void ph_exact_merge_kernel(PhExactArgs a) {
     const uint32_t q = a.list ? a.list[pos] : pos;
     __syncthreads();
     PhExactTopK top;
-    top.cur = keys, top.nxt = keys + a.k, top.sv = keys + 2u * a.k, top.len = 0, top.k = a.k;
-    for (uint32_t s = 0; s < a.slices; s++) {
-      const uint64_t *const list = a.scratch + ((uint64_t)pos * a.slices + s) * a.k;
-      for (uint32_t b = 0; b < a.k; b += 64u)
-        if (!top.insert(b + lane < a.k ? list[b + lane] : KEY_NONE, lane)) break;
-    }
+    top.init(keys, a.k);
+    for (uint32_t s = 0; s < a.slices; s++)
+      PH_EXACT_FEED(top, a.scratch + ((uint64_t)pos * a.slices + s) * a.k, a.k, lane);
     ph_exact_write_row(a, q, top.cur, top.len, !a.queries && a.qids[q] >= a.n, lane);
   }
 }
@@ -135,19 +118,14 @@ __global__ __launch_bounds__(256) void ph_filter_count_kernel(const uint32_t *fi
                                                               uint32_t n, uint32_t nwords, uint32_t n_nodes,
                                                               const uint32_t *nodes, const uint32_t *vec2node,
                                                               uint32_t *out_count) {
-  __shared__ uint32_t part[4];
   const uint32_t nlim = ph_exact_id_limit(n, n_nodes, nodes, vec2node);
   for (uint64_t b = blockIdx.x; b < nbitmaps; b += gridDim.x) {
     const uint32_t *const bitmap = filter ? filter + b * stride : nullptr;
     uint32_t c = 0;
     for (uint32_t widx = threadIdx.x; widx < nwords; widx += 256u)
       c += (uint32_t)__popc(ph_exact_word(bitmap, widx, nwords, nlim, vec2node));
-#pragma unroll
-    for (int sft = 32; sft >= 1; sft >>= 1) c += __shfl_xor(c, sft);
-    __syncthreads();  // part[] of the previous bitmap has been read
-    if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) out_count[b] = part[0] + part[1] + part[2] + part[3];
+    c = ph_block_sum256(c);
+    if (threadIdx.x == 0) out_count[b] = c;
   }
 }
 
@@ -207,6 +185,25 @@ int ph_exact_supported(const phnsw_index *ix, uint32_t k) {
   return 0;
 }
 
+// The launch preparation of a one-wave kernel with `lds` bytes of dynamic LDS: the attribute a size above 48 KiB needs
+// (per call: it belongs to the kernel, not to the memo's owner) and the waves of it the device holds at once, asked of
+// the runtime once per (kernel, LDS) and kept in `memo` under `mutex`.
+int ph_resident_waves(PhResidentMemo &memo, std::mutex &mutex, int device, const void *fn, size_t lds, uint64_t *waves) {
+  if (lds > 48 * 1024) PH_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  std::lock_guard<std::mutex> g(mutex);
+  for (const PhResidentMemo::Entry &r : memo.known)
+    if (r.fn == fn && r.lds == lds) {
+      *waves = r.waves;
+      return 0;
+    }
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, lds) != hipSuccess || per_cu <= 0) per_cu = 1;
+  if (!memo.cus) PH_HIP(hipDeviceGetAttribute(&memo.cus, hipDeviceAttributeMultiprocessorCount, device));
+  *waves = (uint64_t)per_cu * (uint64_t)std::max(memo.cus, 1);
+  memo.known.push_back(PhResidentMemo::Entry{fn, lds, *waves});
+  return 0;
+}
+
 int ph_exact_device(const phnsw_index *ix, const PhExactCall &c) {
   phnsw_index *mix = const_cast<phnsw_index *>(ix);
   const phnsw_store *s = ix->store;
@@ -215,13 +212,8 @@ int ph_exact_device(const phnsw_index *ix, const PhExactCall &c) {
   const PhExactFn fn = exact_fn(s);
   const size_t pq_lds = (ph_pq_lds_bytes(s) + 15u) & ~(size_t)15u, own_lds = (size_t)ph_exact_own_lds(c.k);
   const size_t lds = pq_lds + own_lds;
-  if (lds > 48 * 1024)
-    PH_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  // waves of the scan the device holds at once
-  int per_cu = 0, cus = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)fn, 64, lds) != hipSuccess || per_cu <= 0) per_cu = 1;
-  PH_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device));
-  const uint64_t resident = (uint64_t)per_cu * (uint64_t)std::max(cus, 1);
+  uint64_t resident = 0;  // waves of the scan the device holds at once
+  if (int rc = ph_resident_waves(mix->exact_resident, mix->exact_mutex, s->device, (const void *)fn, lds, &resident)) return rc;
   const char *e = getenv("PHNSW_EXACT_SLICES");  // tests and tuning: forces the slice count, changes no result
   PhExactArgs a = {};
   a.dist = ph_dist_args(s);

@@ -15,15 +15,15 @@
 //      ph_grouped_popc_kernel / ph_grouped_prefix_kernel / ph_grouped_list_kernel: the ascending VectorId list of
 //      every group, CSR; the prefix checks the list's length against the count, the list kernel every word against
 //      its popcount: a bitmap that changed under the call marks its group, whose rows come back empty with status 7
-//   4. per group, per node chunk, per position chunk (dense_plan.h): ph_tiny_table_chunk_ordered (tiny.hip) -- the
-//      existing table kernels, position p of the group being query order[first + p]
-//   5. ph_grouped_select_kernel  one wave64 per position, the running top-k carried between node chunks in a [nq][k]
-//                                key scratch indexed by the QUERY; rows of refused queries and of groups without
-//                                candidates are written by the same kernel over no table
+//   4. per group ph_table_run (filter_dense.hip): per node chunk, per position chunk (dense_plan.h) the table
+//      (ph_tiny_table_chunk, tiny.hip: the search's table kernels), position p of the group being query order[first + p],
+//   5. then ph_table_select_kernel: one wave64 per position, the running top-k carried between node chunks in a
+//      [nq][k] key scratch indexed by the QUERY; rows of refused queries and of groups without candidates are written
+//      by the same kernel over no table
 //
 // The keys are distinct, so the k smallest are one set in one order whatever the grouping and the chunk sizes; the
 // distances are the table's, i.e. phnsw_distance_batch's bits, so a row equals phnsw_search_exact_filtered's bit for bit.
-// No table, pack or quant kernel and no kernel of the scan or of filter_dense.hip is touched (profiles/filter_grouped/).
+// The block scan and the block sum of the list builder are exact_topk.h's (profiles/exact_once/).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -110,46 +110,25 @@ __device__ __forceinline__ uint32_t ph_grouped_word(const PhGroupedListArgs &a, 
 
 // one block per group, striding: a popcount over the scan's candidate test
 __global__ __launch_bounds__(256) void ph_grouped_count_kernel(PhGroupedListArgs a) {
-  __shared__ uint32_t part[4];
   const uint32_t nlim = ph_exact_id_limit(a.n, a.n_nodes, a.nodes, a.vec2node);
   const uint32_t ng = min(a.ngroups[0], a.gmax);
   for (uint32_t g = blockIdx.x; g < ng; g += gridDim.x) {
     const uint32_t key = a.gkey[g];
     uint32_t c = 0;
     for (uint32_t w = threadIdx.x; w < a.nwords; w += 256u) c += (uint32_t)__popc(ph_grouped_word(a, key, w, nlim));
-#pragma unroll
-    for (int sft = 32; sft >= 1; sft >>= 1) c += __shfl_xor(c, sft);
-    __syncthreads();  // part[] of the previous group has been read
-    if ((threadIdx.x & 63u) == 0) part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) a.gcount[g] = part[0] + part[1] + part[2] + part[3];
+    c = ph_block_sum256(c);
+    if (threadIdx.x == 0) a.gcount[g] = c;
   }
 }
 
 // one workgroup: gcum[0 .. ng] = exclusive 64-bit prefix of gcount[0 .. ng), 1024 groups at a time
 __global__ __launch_bounds__(1024) void ph_grouped_cum_kernel(PhGroupedListArgs a) {
-  __shared__ unsigned long long wave_total[16];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const uint32_t ng = min(a.ngroups[0], a.gmax);
   unsigned long long base = 0;
   for (uint32_t at = 0; at < ng; at += 1024u) {
     const uint32_t g = at + threadIdx.x;
-    const unsigned long long v = g < ng ? a.gcount[g] : 0ull;
-    unsigned long long incl = v;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-      const unsigned long long t = __shfl_up(incl, d);
-      if (lane >= d) incl += t;
-    }
-    if (lane == 63u) wave_total[wave] = incl;
-    __syncthreads();
-    unsigned long long before = base, all = 0;
-    for (uint32_t i = 0; i < 16u; i++) {
-      if (i < wave) before += wave_total[i];
-      all += wave_total[i];
-    }
-    if (g < ng) a.gcum[g] = before + incl - v;
-    base += all;
+    const unsigned long long before = ph_block_exclusive_scan<unsigned long long>(g < ng ? a.gcount[g] : 0ull, base);
+    if (g < ng) a.gcum[g] = before;
     __syncthreads();  // the totals are rewritten by the next 1024
   }
   if (threadIdx.x == 0) a.gcum[ng] = base;
@@ -164,32 +143,16 @@ __global__ __launch_bounds__(256) void ph_grouped_popc_kernel(PhGroupedListArgs 
     off[w] = (uint32_t)__popc(ph_grouped_word(a, key, (uint32_t)w, nlim));
 }
 
-// one workgroup per group of the round: the exclusive prefix of its counts in place (as ph_dense_prefix_kernel), the
-// total checked against the count the round was laid out from
+// one workgroup per group of the round: the exclusive prefix of its counts in place, the total checked against the count
+// the round was laid out from
 __global__ __launch_bounds__(1024) void ph_grouped_prefix_kernel(PhGroupedListArgs a) {
-  __shared__ uint32_t wave_total[16];
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
   const uint32_t g = a.g0 + blockIdx.x;
   uint32_t *const off = a.off + (uint64_t)blockIdx.x * ph_group_off_words(a.nwords);
   uint32_t base = 0;
   for (uint64_t at = 0; at < a.nwords; at += 1024u) {
     const uint64_t w = at + threadIdx.x;
-    const uint32_t v = w < a.nwords ? off[w] : 0u;
-    uint32_t incl = v;
-#pragma unroll
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-      const uint32_t t = __shfl_up(incl, d);
-      if (lane >= d) incl += t;
-    }
-    if (lane == 63u) wave_total[wave] = incl;
-    __syncthreads();
-    uint32_t before = base, all = 0;
-    for (uint32_t i = 0; i < 16u; i++) {
-      if (i < wave) before += wave_total[i];
-      all += wave_total[i];
-    }
-    if (w < a.nwords) off[w] = before + incl - v;
-    base += all;
+    const uint32_t before = ph_block_exclusive_scan(w < a.nwords ? off[w] : 0u, base);
+    if (w < a.nwords) off[w] = before;
     __syncthreads();  // the totals are rewritten by the next 1024
   }
   if (threadIdx.x == 0) off[a.nwords] = base, a.gerr[g] = base != a.gcount[g] ? 1u : 0u;
@@ -217,68 +180,6 @@ __global__ __launch_bounds__(256) void ph_grouped_list_kernel(PhGroupedListArgs 
     for (uint32_t i = 0; i < cnt; i++) {
       list[o + i] = t ? (uint32_t)w * 32u + (uint32_t)__ffs((int)t) - 1u : 0u;  // ascending within the word and across words
       t &= t - 1u;
-    }
-  }
-}
-
-// ------------------------------------------------------------------ the select
-
-struct PhGroupedSelectArgs {
-  const float *D;          // [npos][stride]: the table of this (node chunk, position chunk); unread when tn == 0
-  uint32_t stride, tn;     // tn <= stride
-  uint32_t npos;           // positions of this chunk
-  const uint32_t *order;   // [npos]: position p is query order[p]
-  const uint32_t *list;    // [tn]: the node chunk's VectorIds, ascending
-  const uint32_t *exclude;  // [nq] or nullptr
-  const uint32_t *why;      // [nq]: 0, or the status of a refused query
-  const uint32_t *gerr;     // the group's word: nonzero = its bitmap changed while the call read it
-  uint64_t *keys;           // [nq][k]: the running top-k between node chunks, ascending, KEY_NONE padded
-  uint32_t k;
-  uint32_t first, last;  // the first node chunk starts empty; the last one writes the row
-  uint32_t *out_ids;     // [nq][k]
-  float *out_d;
-  uint32_t *out_len, *status;  // [nq]
-};
-
-// One wave64 per position, as ph_dense_select_kernel; the row, the exclude and the key scratch go by the query.
-__global__ __launch_bounds__(64) void ph_grouped_select_kernel(PhGroupedSelectArgs a) {
-  extern __shared__ uint64_t grouped_keys[];  // ph_dense_select_lds(k)
-  const uint32_t lane = threadIdx.x;
-  const uint32_t changed = a.gerr[0] ? PH_GROUP_ST_CHANGED : PH_GROUP_ST_OK;
-  for (uint32_t p = blockIdx.x; p < a.npos; p += gridDim.x) {
-    const uint32_t q = a.order[p];  // < nq
-    __syncthreads();  // the previous position's lists are done with
-    PhExactTopK top;
-    top.cur = grouped_keys, top.nxt = grouped_keys + a.k, top.sv = grouped_keys + 2u * a.k, top.len = 0, top.k = a.k;
-    uint64_t *const mine = a.keys + (uint64_t)q * a.k;
-    const uint32_t refused = a.why[q] ? a.why[q] : changed;
-    if (!a.first) {
-      uint32_t have = 0;
-      for (uint32_t i = lane; i < a.k; i += 64u) {
-        const uint64_t key = mine[i];
-        top.cur[i] = key;
-        have += key != KEY_NONE ? 1u : 0u;
-      }
-#pragma unroll
-      for (int sft = 32; sft >= 1; sft >>= 1) have += __shfl_xor(have, sft);
-      top.len = have;  // the padding is KEY_NONE and no key is (mkkey keeps bit 31 of the id word clear)
-      __syncthreads();
-    }
-    if (!refused) {
-      const uint32_t ex = a.exclude ? a.exclude[q] : PH_EMPTY32;
-      const float *const row = a.D + (uint64_t)p * a.stride;
-      for (uint32_t b = 0; b < a.tn; b += 64u) {
-        const uint32_t j = b + lane;
-        const bool ok = j < a.tn;  // tn <= stride: inside the row
-        const uint32_t id = ok ? a.list[j] : PH_EMPTY32;
-        top.insert(ok && id != ex ? mkkey(row[j], id) : KEY_NONE, lane);
-      }
-    }
-    if (a.last) {
-      ph_exact_write_row(a, q, top.cur, refused ? 0u : top.len, refused != 0u, lane);
-      if (lane == 0 && refused) a.status[q] = refused;  // 4, 6 or 7 in place of the row writer's 4
-    } else {
-      for (uint32_t i = lane; i < a.k; i += 64u) mine[i] = i < top.len ? top.cur[i] : KEY_NONE;
     }
   }
 }
@@ -313,22 +214,12 @@ struct PhGroupedCall {
 
 namespace {
 
-int select_launch(const PhGroupedCall &c, const PhGroupedSelectArgs &a) {
-  hipLaunchKernelGGL(ph_grouped_select_kernel, dim3(std::min<uint32_t>(a.npos, 1u << 20)), dim3(64),
-                     (size_t)ph_dense_select_lds(c.k), c.stream, a);
-  PH_HIP(hipGetLastError());
-  return 0;
-}
-
 // the orchestration on a set the caller holds; c is checked, 0 < nq <= PH_GROUP_NQ_MAX
 int grouped_run(const phnsw_index *ix, const PhGroupedCall &c, PhGroupedSet &set) {
   const phnsw_store *s = ix->store;
   const uint64_t nq = c.nq, nwords = ph_exact_words(s->n);
   const uint64_t gmax = ph_group_max(nq, c.nfilters);
   const PhGroupPre lay = ph_group_pre(nq, gmax);
-  // the packed operand's key describes lists that are scratch: whichever way the last call on this set ended, this one
-  // writes other ids there
-  set.ws.tiny_pack_key.valid = false;
   PH_TRY(set.ready());
   if (set.h_read_words < lay.read_words) {
     if (set.h_read) {
@@ -412,11 +303,14 @@ int grouped_run(const phnsw_index *ix, const PhGroupedCall &c, PhGroupedSet &set
   PH_TRY(set.block_ensure(&set.lists, &set.lists_bytes, (size_t)list_bytes, c.stream));
   PH_TRY(set.block_ensure(&set.post, &set.post_bytes, (size_t)std::max<uint64_t>(ph_group_post_bytes(nq, c.k, table_floats), 16u),
                       c.stream));
-  PhGroupedSelectArgs a = {};
-  a.exclude = c.exclude, a.why = why, a.k = c.k;
-  a.out_ids = c.out_ids, a.out_d = c.out_d, a.out_len = c.out_len, a.status = c.status;
-  a.keys = (uint64_t *)set.post;
-  float *const D = (float *)((char *)set.post + ph_group_key_bytes(nq, c.k));
+  PhTableRun r = {};
+  r.queries = c.queries, r.ldq = c.ldq, r.qids = c.qids ? safe : nullptr;
+  r.nodes_knob = nodes_knob, r.bytes_knob = bytes_knob;
+  r.exclude = c.exclude, r.refuse = why, r.k = c.k;
+  r.keys = (uint64_t *)set.post, r.D = (float *)((char *)set.post + ph_group_key_bytes(nq, c.k));
+  r.out_ids = c.out_ids, r.out_d = c.out_d, r.out_len = c.out_len, r.status = c.status;
+  r.stream = c.stream, r.times = &times, r.step_table = TABLE, r.step_select = SELECT;
+  r.call = "exact grouped search";
   const bool verbose = getenv("PHNSW_VERBOSE") != nullptr;
   const uint32_t wgrid = grid1(nwords);
 
@@ -436,53 +330,13 @@ int grouped_run(const phnsw_index *ix, const PhGroupedCall &c, PhGroupedSet &set
               (unsigned long long)rounds, (unsigned long long)g0, (unsigned long long)g1, (unsigned long long)ngroups);
     uint64_t list_at = 0;
     for (uint64_t g = g0; g < g1; list_at += hcount[g], g++) {
-      const uint64_t first = hfirst[g], size = hfirst[g + 1u] - first, cand = hcount[g];
-      const uint32_t *const glist = l.list + list_at;
-      a.gerr = gerr + g;
-      // the packed node operand is kept under the list's ADDRESS and length, not its contents: rounds reuse the
-      // addresses and two groups may have equal counts
-      set.ws.tiny_pack_key.valid = false;
-      if (cand == 0) {  // empty rows, and the status of the reject group's queries, from the select itself
-        a.D = nullptr, a.stride = 0, a.tn = 0, a.list = nullptr;
-        a.order = order + first, a.npos = (uint32_t)size, a.first = 1u, a.last = 1u;
-        times.begin(SELECT);
-        PH_TRY(select_launch(c, a));
-        times.end();
-        continue;
-      }
-      const PhDensePlan plan = ph_dense_plan(cand, size, nodes_knob, bytes_knob);
-      a.D = D;
-      for (uint32_t i = 0; i < plan.node_chunks; i++) {
-        uint64_t nfirst;
-        ph_dense_node_chunk(plan, i, &nfirst, &a.tn, &a.stride);
-        a.list = glist + nfirst;  // nfirst + tn <= cand
-        a.first = i == 0 ? 1u : 0u, a.last = i + 1u == plan.node_chunks ? 1u : 0u;
-        set.ws.tiny_pack_key.valid = false;  // it may serve the position chunks of this node chunk and nothing else
-        for (uint64_t j = 0; j < plan.pos_chunks; j++) {
-          uint64_t pfirst;
-          ph_dense_pos_chunk(plan, j, &pfirst, &a.npos);
-          a.order = order + first + pfirst;
-          bool kept = false;
-          times.begin(TABLE);
-          const int trc = ph_tiny_table_chunk_ordered(ix, set.ws, c.queries, c.ldq, c.qids ? safe : nullptr, a.order, a.npos, a.list,
-                                                      a.tn, D, c.stream, &kept);
-          times.end();
-          if (trc > 0) {
-            ph_set_error("exact grouped search: no device memory for the table's operands (%u positions x %u candidates)", a.npos,
-                         a.tn);
-            return PHNSW_E_HIP;
-          }
-          if (trc) return trc;
-          if (verbose)
-            fprintf(stderr, "[phnsw] exact grouped table: group %llu (key %u), node chunk %u/%u (%u ids), positions %llu..+%u, %s, "
-                    "node operand %s\n", (unsigned long long)g, hkey[g], i + 1u, plan.node_chunks, a.tn,
-                    (unsigned long long)pfirst, a.npos, set.ws.tiny_table_g ? "matrix cores" : "vector units",
-                    kept ? "kept" : "packed");
-          times.begin(SELECT);
-          PH_TRY(select_launch(c, a));
-          times.end();
-        }
-      }
+      char prefix[96] = "";
+      if (verbose) snprintf(prefix, sizeof prefix, "exact grouped table: group %llu (key %u), ", (unsigned long long)g, hkey[g]);
+      // positions [first, first + npos) of the order are the group's queries; without candidates: empty rows, and the
+      // status of the reject group's queries, from the select itself
+      r.order = order, r.first = hfirst[g], r.npos = hfirst[g + 1u] - hfirst[g];
+      r.list = l.list + list_at, r.cand = hcount[g], r.changed = gerr + g, r.verbose_prefix = prefix;
+      PH_TRY(ph_table_run(ix, set.ws, r));
     }
     g0 = g1;
   }
@@ -526,9 +380,8 @@ extern "C" int phnsw_search_exact_grouped_device(const phnsw_index *ix, const fl
   const char *const call = "phnsw_search_exact_grouped_device";
   PH_TRY(ph_dense_check(ix, k, call));
   if (nq == 0) return 0;
-  if (((!queries_dev) == (!qids_dev)) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev ||
-      !table_args_ok(ix, filters_dev, filter_stride_words, nfilters, filter_of_dev, nq) ||
-      (queries_dev && (ldq < ix->store->ld || (ldq % 4) || ((uintptr_t)queries_dev % 16)))) {
+  if (!ph_device_queries_ok(ix, queries_dev, qids_dev, ldq) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev ||
+      !table_args_ok(ix, filters_dev, filter_stride_words, nfilters, filter_of_dev, nq)) {
     ph_set_error("%s: invalid argument (queries or qids, exactly one; outputs; filters and filter_of, a stride of at least "
                  "ceil(n/32) words, 1 <= nfilters <= 0xFFFFFFFE, nq < 2^31 - 1; queries need ldq >= store ld, multiple of 4, "
                  "16-byte base)", call);

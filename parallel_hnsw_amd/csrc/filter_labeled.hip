@@ -23,8 +23,8 @@
 // the definition above, the keys are distinct, so the k smallest are one set in one order however the list is cut; the
 // distances of path 2 are dist.batch's, and those of path 3 go through the same functions with the same operands in the
 // same order (chain_partial with the row as x and the query as q, wave_sum4, finalize_metric), four rows at a time as
-// batch_distances takes them.  What filter_exact.hip has beyond the shared headers is restated here; no existing
-// kernel is touched (profiles/filter_labeled/).
+// batch_distances takes them.  The running top-k, what feeds it and what is written from it are exact_topk.h's, shared
+// with filter_exact.hip and filter_dense.hip (profiles/exact_once/).
 //
 // A SET of labels per query (phnsw_search_exact_labelset[_device], phnsw_labels_count_set_device; labelset_plan.h): the
 // lists of distinct labels are disjoint, so a set is more slices of the same scan.  A position of the sorted batch is a
@@ -52,11 +52,6 @@
 #include "labelset_plan.h"
 #include "phnsw_device.h"
 
-struct PhLabelResident {  // resident waves of one kernel at one dynamic LDS size
-  const void *fn;
-  size_t lds;
-  uint64_t waves;
-};
 struct phnsw_labels {
   const phnsw_index *ix = nullptr;  // the index the lists were made for, and what it looked like then
   uint64_t n = 0;
@@ -68,8 +63,7 @@ struct phnsw_labels {
   uint32_t *ids = nullptr;     // [listed] (allocated [n]): ascending within a label
   uint32_t *label_of = nullptr;  // [n]: the label of a listed vector, PHNSW_LABEL_NONE elsewhere (the label walk's column)
   PhCallPool pool;  // PhLabeledSet, handed out by set_acquire's policy
-  std::vector<PhLabelResident> resident;  // under pool.mutex
-  int cus = 0;                            // compute units of the device, 0 = not asked yet
+  PhResidentMemo resident;  // under pool.mutex
 };
 
 // ------------------------------------------------------------------ construction
@@ -187,7 +181,7 @@ __global__ __launch_bounds__(64) void ph_labeled_scan_kernel(PhLabeledArgs a) {
     else if (!bad_query)
       dist.prepare_stored(a.dist, a.qids[q], labeled_lds, lane);
     PhExactTopK top;
-    top.cur = keys, top.nxt = keys + a.k, top.sv = keys + 2u * a.k, top.len = 0, top.k = a.k;
+    top.init(keys, a.k);
     const uint32_t ex = a.exclude ? a.exclude[q] : PH_EMPTY32;
     const uint32_t at = s == PH_LABEL_SLOT_NONE ? 0u : a.first[s];
     const uint32_t len = s == PH_LABEL_SLOT_NONE ? 0u : a.first[s + 1u] - at;  // a bad query's slot is NONE
@@ -201,16 +195,11 @@ __global__ __launch_bounds__(64) void ph_labeled_scan_kernel(PhLabeledArgs a) {
       const float d = dist.batch(a.dist, __ballot(ok), id, lane);
       top.insert(ok && id != ex ? mkkey(d, id) : KEY_NONE, lane);
     }
-    if (!PAIRS && a.slices == 1u) {
-      ph_exact_write_row(a, q, top.cur, top.len, bad_query, lane);
-    } else {
-      uint64_t *const out = a.scratch + ((uint64_t)pos * a.slices + slice) * a.k;
-      for (uint32_t i = lane; i < a.k; i += 64u) out[i] = i < top.len ? top.cur[i] : KEY_NONE;
-    }
+    ph_exact_write_slice<PAIRS>(a, q, pos, slice, top.cur, top.len, bad_query, lane);
   }
 }
 
-// One wave per position: the slices' ascending lists merged through the same running top-k (as ph_exact_merge_kernel).
+// One wave per position: the slices' ascending lists merged through the same running top-k (PH_EXACT_FEED).
 __global__ __launch_bounds__(64) void ph_labeled_merge_kernel(PhLabeledArgs a) {
   extern __shared__ float labeled_lds[];
   const uint32_t lane = threadIdx.x;
@@ -219,12 +208,9 @@ __global__ __launch_bounds__(64) void ph_labeled_merge_kernel(PhLabeledArgs a) {
     const uint32_t q = a.order[pos];
     __syncthreads();
     PhExactTopK top;
-    top.cur = keys, top.nxt = keys + a.k, top.sv = keys + 2u * a.k, top.len = 0, top.k = a.k;
-    for (uint32_t s = 0; s < a.slices; s++) {
-      const uint64_t *const list = a.scratch + ((uint64_t)pos * a.slices + s) * a.k;
-      for (uint32_t b = 0; b < a.k; b += 64u)
-        if (!top.insert(b + lane < a.k ? list[b + lane] : KEY_NONE, lane)) break;
-    }
+    top.init(keys, a.k);
+    for (uint32_t s = 0; s < a.slices; s++)
+      PH_EXACT_FEED(top, a.scratch + ((uint64_t)pos * a.slices + s) * a.k, a.k, lane);
     ph_exact_write_row(a, q, top.cur, top.len, !a.queries && a.qids[q] >= a.n, lane);
   }
 }
@@ -297,15 +283,12 @@ __global__ __launch_bounds__(64) void ph_labelset_merge_kernel(PhLabelsetArgs s)
     const bool ok = ph_labelset_query_ok(s, q, b, e, lane);
     __syncthreads();
     PhExactTopK top;
-    top.cur = keys, top.nxt = keys + a.k, top.sv = keys + 2u * a.k, top.len = 0, top.k = a.k;
+    top.init(keys, a.k);
     for (uint32_t i = b; ok && i < e; i++) {
       const uint32_t pos = s.inv[i];  // < nwant: pair i is q's, so the sort placed it
       if (s.dup[pos] || a.sslot[pos] == PH_LABEL_SLOT_NONE) continue;
-      for (uint32_t sl = 0; sl < a.slices; sl++) {
-        const uint64_t *const list = a.scratch + ((uint64_t)pos * a.slices + sl) * a.k;
-        for (uint32_t t = 0; t < a.k; t += 64u)
-          if (!top.insert(t + lane < a.k ? list[t + lane] : KEY_NONE, lane)) break;
-      }
+      for (uint32_t sl = 0; sl < a.slices; sl++)
+        PH_EXACT_FEED(top, a.scratch + ((uint64_t)pos * a.slices + sl) * a.k, a.k, lane);
     }
     ph_exact_write_row(a, q, top.cur, top.len, !a.queries && a.qids[q] >= a.n, lane);
     if (!ok && lane == 0) a.status[q] = ST_LABELSET_RANGE;  // after the row's own status word, same lane
@@ -413,7 +396,9 @@ __device__ __forceinline__ void ph_labeled_tile_batches(const PhLabeledArgs &a, 
       uint64_t *const kb = l.keys + (uint64_t)t * keys_per;
       const uint32_t flip = rfl32(st[1]), ex = rfl32(st[3]);
       PhExactTopK top;
-      top.cur = flip ? kb + a.k : kb, top.nxt = flip ? kb : kb + a.k, top.sv = kb + 2u * a.k, top.len = rfl32(st[0]), top.k = a.k;
+      top.init(kb, a.k);  // then as the state words left it: which list is in use, and its length
+      if (flip) top.cur = kb + a.k, top.nxt = kb;
+      top.len = rfl32(st[0]);
       const float d = l.dbuf[t * 64u + lane];
       top.insert(ok && id != ex ? mkkey(d, id) : KEY_NONE, lane);
       __syncthreads();
@@ -483,12 +468,7 @@ __global__ __launch_bounds__(64) void ph_labeled_tile_kernel(PhLabeledArgs a) {
       const uint32_t *const st = l.state + 4u * t;
       const uint32_t tlen = rfl32(st[0]), q = rfl32(st[2]);
       const uint64_t *const cur = l.keys + (uint64_t)t * keys_per + (rfl32(st[1]) ? a.k : 0u);
-      if (!PAIRS && a.slices == 1u) {
-        ph_exact_write_row(a, q, cur, tlen, !a.queries && a.qids[q] >= a.n, lane);
-      } else {
-        uint64_t *const out = a.scratch + ((uint64_t)(p0 + t) * a.slices + slice) * a.k;
-        for (uint32_t i = lane; i < a.k; i += 64u) out[i] = i < tlen ? cur[i] : KEY_NONE;
-      }
+      ph_exact_write_slice<PAIRS>(a, q, p0 + t, slice, cur, tlen, !a.queries && a.qids[q] >= a.n, lane);
     }
   }
 }
@@ -619,50 +599,80 @@ const uint32_t *ph_labels_column(const phnsw_labels *lb) { return lb->label_of; 
 
 namespace {
 
-// T and the kernel of a call -- the tile kernel for T > 1 on a row store, else the per-query scan --, its dynamic LDS and
-// the waves of it a device holds; fills a.T and a.pq_lds.  pairs: the PAIRS instances of phnsw_search_exact_labelset.
-int labeled_kernel(const phnsw_labels *lb, const phnsw_store *s, uint32_t k, bool pairs, PhLabeledArgs &a, PhLabeledFn *fn_out,
-                   size_t *lds_out, uint64_t *resident_out) {
-  const size_t pq_lds = (ph_pq_lds_bytes(s) + 15u) & ~(size_t)15u;
-  PhLabeledFn fn = labeled_scan_fn(s, pairs);
-  size_t lds = pq_lds + (size_t)ph_label_scan_lds(k);
-  a.T = 1u, a.pq_lds = (uint32_t)pq_lds;
-  if (PhLabeledFn tile = labeled_tile_fn(s, pairs)) {
-    const uint32_t T = ph_label_tile(k, s->ld, PH_LABEL_LDS_BYTES, env_ll("PHNSW_LABEL_TILE"));
-    if (T > 1u && ph_label_tile_lds(T, k, s->ld) <= PH_LABEL_LDS_BYTES) {
-      fn = tile, a.T = T, lds = (size_t)ph_label_tile_lds(T, k, s->ld);
-    }
-  }
-  if (lds > 48 * 1024) PH_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  // resident waves of this kernel at this LDS size: asked of the runtime once per (kernel, LDS) and kept with the handle
-  uint64_t resident = 0;
-  {
-    phnsw_labels *mlb = const_cast<phnsw_labels *>(lb);
-    std::lock_guard<std::mutex> g(mlb->pool.mutex);
-    for (const PhLabelResident &r : mlb->resident)
-      if (r.fn == (const void *)fn && r.lds == lds) resident = r.waves;
-    if (!resident) {
-      int per_cu = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)fn, 64, lds) != hipSuccess || per_cu <= 0) per_cu = 1;
-      if (!mlb->cus) PH_HIP(hipDeviceGetAttribute(&mlb->cus, hipDeviceAttributeMultiprocessorCount, s->device));
-      resident = (uint64_t)per_cu * (uint64_t)std::max(mlb->cus, 1);
-      mlb->resident.push_back(PhLabelResident{(const void *)fn, lds, resident});
-    }
-  }
-  *fn_out = fn, *lds_out = lds, *resident_out = resident;
-  return 0;
+// What both runs fill alike of the argument block: the store, the request, the posting lists and the grouping arrays of
+// a layout over `count` positions in `pre`.
+void labeled_args(const phnsw_store *s, const phnsw_labels *lb, const PhLabeledCall &c, uint32_t *pre, const PhLabelPre &lay,
+                  uint64_t count, PhLabeledArgs &a) {
+  a.dist = ph_dist_args(s);
+  a.queries = c.queries, a.ldq = c.ldq, a.qids = c.qids, a.exclude = c.exclude;
+  a.nq = (uint32_t)count, a.n = (uint32_t)s->n, a.k = c.k;
+  a.values = lb->values, a.first = lb->first, a.ids = lb->ids, a.nlabels = (uint32_t)lb->nlabels;
+  a.slot = pre + lay.slot, a.iota = pre + lay.iota, a.sslot = pre + lay.sslot, a.order = pre + lay.order;
+  a.flags = pre + lay.flags, a.tidx = pre + lay.tidx, a.tile_first = pre + lay.tile_first, a.head = pre + lay.head;
+  a.out_ids = c.out_ids, a.out_d = c.out_d, a.out_len = c.out_len, a.status = c.status;
 }
 
-// hipCUB's temporaries for a batch of `count` positions: they depend on the count alone
-int labeled_tmp(PhLabeledSet &set, const PhLabeledArgs &a, uint32_t *sslot, uint32_t *order, uint32_t *tidx, uint64_t count,
-                hipStream_t stream) {
+// the kernel of a call with its dynamic LDS, and what the sort and the tile scan write: the layout's arrays as outputs
+// (the argument block holds them as the kernels' inputs)
+struct PhLabeledLaunch {
+  PhLabeledFn fn;
+  size_t lds;
+  uint32_t *sslot, *sorted_values, *tidx;  // sorted_values: the queries of labeled_run, the pairs of labelset_run
+};
+
+// Before anything is enqueued: T and the kernel of a call -- the tile kernel for T > 1 on a row store, else the per-query
+// scan; pairs: the PAIRS instances of phnsw_search_exact_labelset --, its dynamic LDS, the slice count from the waves of
+// it the device holds, and hipCUB's temporaries, which depend on the position count alone.  Fills a.T, a.pq_lds, a.slices.
+int labeled_plan(const phnsw_labels *lb, const phnsw_store *s, PhLabeledSet &set, bool pairs, hipStream_t stream,
+                 PhLabeledArgs &a, PhLabeledLaunch *ln) {
+  const size_t pq_lds = (ph_pq_lds_bytes(s) + 15u) & ~(size_t)15u;
+  ln->fn = labeled_scan_fn(s, pairs), ln->lds = pq_lds + (size_t)ph_label_scan_lds(a.k);
+  a.T = 1u, a.pq_lds = (uint32_t)pq_lds;
+  if (PhLabeledFn tile = labeled_tile_fn(s, pairs)) {
+    const uint32_t T = ph_label_tile(a.k, s->ld, PH_LABEL_LDS_BYTES, env_ll("PHNSW_LABEL_TILE"));
+    if (T > 1u && ph_label_tile_lds(T, a.k, s->ld) <= PH_LABEL_LDS_BYTES) {
+      ln->fn = tile, a.T = T, ln->lds = (size_t)ph_label_tile_lds(T, a.k, s->ld);
+    }
+  }
+  phnsw_labels *mlb = const_cast<phnsw_labels *>(lb);
+  uint64_t resident = 0;
+  PH_TRY(ph_resident_waves(mlb->resident, mlb->pool.mutex, s->device, (const void *)ln->fn, ln->lds, &resident));
+  // work items the host can count on: the positions, or at least ceil(positions / T) tiles
+  const uint64_t count = a.nq;
+  a.slices = ph_label_slice_count((count + a.T - 1u) / a.T, resident, lb->longest, env_ll("PHNSW_LABEL_SLICES"));
   if (set.tmp_nq != count) {
     size_t sort_bytes = 0, scan_bytes = 0;
-    PH_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, a.slot, sslot, a.iota, order, (int)count, 0, 32, stream));
-    PH_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, a.flags, tidx, (int)(count + 1u), stream));
+    PH_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, a.slot, ln->sslot, a.iota, ln->sorted_values, (int)count, 0, 32,
+                                              stream));
+    PH_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, a.flags, ln->tidx, (int)(count + 1u), stream));
     set.tmp_need = std::max<size_t>(std::max(sort_bytes, scan_bytes), 16), set.tmp_nq = count;
   }
   return set.block_ensure(&set.tmp, &set.tmp_bytes, set.tmp_need, stream);
+}
+
+// (slot, value) of the lookup positions sorted by slot: sslot and sorted_values
+int labeled_sort(PhLabeledSet &set, const PhLabeledArgs &a, const PhLabeledLaunch &ln, hipStream_t stream) {
+  size_t bytes = set.tmp_bytes;
+  PH_HIP(hipcub::DeviceRadixSort::SortPairs(set.tmp, bytes, a.slot, ln.sslot, a.iota, ln.sorted_values, (int)a.nq, 0, 32, stream));
+  return 0;
+}
+
+// After the lookup and the sort: the tile table for T > 1, then the scan or tile kernel over (positions, slices).
+int labeled_scan(PhLabeledSet &set, const PhLabeledArgs &a, const PhLabeledLaunch &ln, hipStream_t stream) {
+  const uint64_t count = a.nq;
+  if (a.T > 1u) {
+    hipLaunchKernelGGL(ph_labeled_tileflag_kernel, dim3(grid1(count + 1u)), dim3(256), 0, stream, a);
+    PH_HIP(hipGetLastError());
+    size_t bytes = set.tmp_bytes;
+    PH_HIP(hipcub::DeviceScan::ExclusiveSum(set.tmp, bytes, a.flags, ln.tidx, (int)(count + 1u), stream));
+    hipLaunchKernelGGL(ph_labeled_tiles_kernel, dim3(grid1(count + 1u)), dim3(256), 0, stream, a);
+    PH_HIP(hipGetLastError());
+  }
+  const uint64_t items = count * (uint64_t)a.slices;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>(items, 1u << 20);  // the kernels stride over what is left
+  hipLaunchKernelGGL(ln.fn, dim3(grid), dim3(64), ln.lds, stream, a);
+  PH_HIP(hipGetLastError());
+  return 0;
 }
 
 // the orchestration on a set the caller holds; c is checked, 0 < nq <= PH_LABEL_NQ_MAX (with a list: its length).
@@ -675,22 +685,10 @@ int labeled_run(const phnsw_index *ix, const phnsw_labels *lb, const PhLabeledCa
   PH_TRY(set.block_ensure(&set.pre, &set.pre_bytes, (size_t)lay.words * 4u, c.stream));
   uint32_t *const pre = (uint32_t *)set.pre;
   PhLabeledArgs a = {};
-  a.dist = ph_dist_args(s);
-  a.queries = c.queries, a.ldq = c.ldq, a.qids = c.qids, a.exclude = c.exclude, a.want = c.want, a.list = c.list;
-  a.nq = (uint32_t)nq, a.n = (uint32_t)s->n, a.k = c.k;
-  a.values = lb->values, a.first = lb->first, a.ids = lb->ids, a.nlabels = (uint32_t)lb->nlabels;
-  a.slot = pre + lay.slot, a.iota = pre + lay.iota, a.sslot = pre + lay.sslot, a.order = pre + lay.order;
-  a.flags = pre + lay.flags, a.tidx = pre + lay.tidx, a.tile_first = pre + lay.tile_first, a.head = pre + lay.head;
-  a.out_ids = c.out_ids, a.out_d = c.out_d, a.out_len = c.out_len, a.status = c.status;
-
-  PhLabeledFn fn = nullptr;
-  size_t lds = 0;
-  uint64_t resident = 0;
-  PH_TRY(labeled_kernel(lb, s, c.k, false, a, &fn, &lds, &resident));
-  // work items the host can count on: the queries, or at least ceil(nq / T) tiles
-  a.slices = ph_label_slice_count((nq + a.T - 1u) / a.T, resident, lb->longest, env_ll("PHNSW_LABEL_SLICES"));
-
-  PH_TRY(labeled_tmp(set, a, pre + lay.sslot, pre + lay.order, pre + lay.tidx, nq, c.stream));
+  labeled_args(s, lb, c, pre, lay, nq, a);
+  a.want = c.want, a.list = c.list;
+  PhLabeledLaunch ln = {nullptr, 0, pre + lay.sslot, pre + lay.order, pre + lay.tidx};
+  PH_TRY(labeled_plan(lb, s, set, false, c.stream, a, &ln));
   if (a.slices > 1u) {
     uint64_t bytes = 0;
     if (!ph_label_key_bytes(nq, a.slices, c.k, &bytes)) {
@@ -704,21 +702,8 @@ int labeled_run(const phnsw_index *ix, const phnsw_labels *lb, const PhLabeledCa
 
   hipLaunchKernelGGL(ph_labeled_lookup_kernel, dim3(grid1(nq)), dim3(256), 0, c.stream, a);
   PH_HIP(hipGetLastError());
-  size_t bytes = set.tmp_bytes;
-  PH_HIP(hipcub::DeviceRadixSort::SortPairs(set.tmp, bytes, a.slot, pre + lay.sslot, a.iota, pre + lay.order, (int)nq, 0, 32,
-                                            c.stream));
-  if (a.T > 1u) {
-    hipLaunchKernelGGL(ph_labeled_tileflag_kernel, dim3(grid1(nq + 1u)), dim3(256), 0, c.stream, a);
-    PH_HIP(hipGetLastError());
-    bytes = set.tmp_bytes;
-    PH_HIP(hipcub::DeviceScan::ExclusiveSum(set.tmp, bytes, a.flags, pre + lay.tidx, (int)(nq + 1u), c.stream));
-    hipLaunchKernelGGL(ph_labeled_tiles_kernel, dim3(grid1(nq + 1u)), dim3(256), 0, c.stream, a);
-    PH_HIP(hipGetLastError());
-  }
-  const uint64_t items = nq * (uint64_t)a.slices;
-  const uint32_t grid = (uint32_t)std::min<uint64_t>(items, 1u << 20);  // the kernels stride over what is left
-  hipLaunchKernelGGL(fn, dim3(grid), dim3(64), lds, c.stream, a);
-  PH_HIP(hipGetLastError());
+  PH_TRY(labeled_sort(set, a, ln, c.stream));
+  PH_TRY(labeled_scan(set, a, ln, c.stream));
   if (a.slices > 1u) {
     hipLaunchKernelGGL(ph_labeled_merge_kernel, dim3((uint32_t)std::min<uint64_t>(nq, 1u << 20)), dim3(64),
                        (size_t)ph_label_scan_lds(c.k), c.stream, a);
@@ -745,23 +730,14 @@ int labelset_run(const phnsw_index *ix, const phnsw_labels *lb, const PhLabelset
   uint32_t *const pre = (uint32_t *)set.pre;
   PhLabelsetArgs sa = {};
   PhLabeledArgs &a = sa.a;
-  a.dist = ph_dist_args(s);
-  a.queries = c.queries, a.ldq = c.ldq, a.qids = c.qids, a.exclude = c.exclude;
-  a.nq = (uint32_t)np, a.n = (uint32_t)s->n, a.k = c.k, a.slices = 1u, a.T = 1u;
-  a.values = lb->values, a.first = lb->first, a.ids = lb->ids, a.nlabels = (uint32_t)lb->nlabels;
-  a.slot = pre + lay.pos.slot, a.iota = pre + lay.pos.iota, a.sslot = pre + lay.pos.sslot, a.order = pre + lay.pos.order;
-  a.flags = pre + lay.pos.flags, a.tidx = pre + lay.pos.tidx, a.tile_first = pre + lay.pos.tile_first, a.head = pre + lay.pos.head;
-  a.out_ids = c.out_ids, a.out_d = c.out_d, a.out_len = c.out_len, a.status = c.status;
+  labeled_args(s, lb, c, pre, lay.pos, np, a);
+  a.slices = 1u, a.T = 1u;
   sa.want_first = sc.want_first, sa.want_values = sc.want_values, sa.nq = (uint32_t)nq, sa.nwant = (uint32_t)np;
   sa.owner = pre + lay.owner, sa.spair = pre + lay.spair, sa.inv = pre + lay.inv, sa.dup = pre + lay.dup;
 
   if (np) {
-    PhLabeledFn fn = nullptr;
-    size_t lds = 0;
-    uint64_t resident = 0;
-    PH_TRY(labeled_kernel(lb, s, c.k, true, a, &fn, &lds, &resident));
-    a.slices = ph_label_slice_count((np + a.T - 1u) / a.T, resident, lb->longest, env_ll("PHNSW_LABEL_SLICES"));
-    PH_TRY(labeled_tmp(set, a, pre + lay.pos.sslot, sa.spair, pre + lay.pos.tidx, np, c.stream));
+    PhLabeledLaunch ln = {nullptr, 0, pre + lay.pos.sslot, sa.spair, pre + lay.pos.tidx};
+    PH_TRY(labeled_plan(lb, s, set, true, c.stream, a, &ln));
     uint64_t bytes = 0;
     if (!ph_labelset_key_bytes(np, a.slices, c.k, &bytes)) {
       ph_set_error("exact labelset search: %llu wanted labels in %u slices at k = %u need more scratch than can be addressed",
@@ -776,22 +752,10 @@ int labelset_run(const phnsw_index *ix, const phnsw_labels *lb, const PhLabelset
     PH_HIP(hipGetLastError());
     hipLaunchKernelGGL(ph_labelset_lookup_kernel, dim3(grid1(np)), dim3(256), 0, c.stream, sa);
     PH_HIP(hipGetLastError());
-    size_t tmp = set.tmp_bytes;
-    PH_HIP(hipcub::DeviceRadixSort::SortPairs(set.tmp, tmp, a.slot, pre + lay.pos.sslot, a.iota, sa.spair, (int)np, 0, 32,
-                                              c.stream));
+    PH_TRY(labeled_sort(set, a, ln, c.stream));
     hipLaunchKernelGGL(ph_labelset_positions_kernel, dim3(grid1(np)), dim3(256), 0, c.stream, sa, pre + lay.pos.order);
     PH_HIP(hipGetLastError());
-    if (a.T > 1u) {
-      hipLaunchKernelGGL(ph_labeled_tileflag_kernel, dim3(grid1(np + 1u)), dim3(256), 0, c.stream, a);
-      PH_HIP(hipGetLastError());
-      tmp = set.tmp_bytes;
-      PH_HIP(hipcub::DeviceScan::ExclusiveSum(set.tmp, tmp, a.flags, pre + lay.pos.tidx, (int)(np + 1u), c.stream));
-      hipLaunchKernelGGL(ph_labeled_tiles_kernel, dim3(grid1(np + 1u)), dim3(256), 0, c.stream, a);
-      PH_HIP(hipGetLastError());
-    }
-    const uint64_t items = np * (uint64_t)a.slices;
-    hipLaunchKernelGGL(fn, dim3((uint32_t)std::min<uint64_t>(items, 1u << 20)), dim3(64), lds, c.stream, a);
-    PH_HIP(hipGetLastError());
+    PH_TRY(labeled_scan(set, a, ln, c.stream));
   }
   // no pair at all: every sound range is empty, and the merge alone writes the rows
   hipLaunchKernelGGL(ph_labelset_merge_kernel, dim3((uint32_t)std::min<uint64_t>(nq, 1u << 20)), dim3(64),
@@ -989,8 +953,8 @@ extern "C" int phnsw_search_exact_labeled_device(const phnsw_index *ix, const ph
   const char *const call = "phnsw_search_exact_labeled_device";
   PH_TRY(ph_labeled_check(ix, lb, k, call));
   if (nq == 0) return 0;
-  if (((!queries_dev) == (!qids_dev)) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev || !want_dev ||
-      nq > PH_LABEL_NQ_MAX || (queries_dev && (ldq < ix->store->ld || (ldq % 4) || ((uintptr_t)queries_dev % 16)))) {
+  if (!ph_device_queries_ok(ix, queries_dev, qids_dev, ldq) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev ||
+      !want_dev || nq > PH_LABEL_NQ_MAX) {
     ph_set_error("%s: invalid argument (queries or qids, exactly one; outputs; want; nq < 2^31 - 1; queries need ldq >= store "
                  "ld, multiple of 4, 16-byte base)", call);
     return PHNSW_E_INVALID;
@@ -1069,8 +1033,8 @@ extern "C" int phnsw_search_exact_labelset_device(const phnsw_index *ix, const p
   const char *const call = "phnsw_search_exact_labelset_device";
   PH_TRY(ph_labeled_check(ix, lb, k, call));
   if (nq == 0) return 0;
-  if (((!queries_dev) == (!qids_dev)) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev || !want_first_dev ||
-      (!want_values_dev && nwant) || (queries_dev && (ldq < ix->store->ld || (ldq % 4) || ((uintptr_t)queries_dev % 16)))) {
+  if (!ph_device_queries_ok(ix, queries_dev, qids_dev, ldq) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev ||
+      !want_first_dev || (!want_values_dev && nwant)) {
     ph_set_error("%s: invalid argument (queries or qids, exactly one; outputs; want_first; want_values unless nwant is 0; "
                  "queries need ldq >= store ld, multiple of 4, 16-byte base)", call);
     return PHNSW_E_INVALID;
@@ -1163,8 +1127,8 @@ extern "C" int phnsw_search_batch_labeled_device(const phnsw_index *ix, const ph
   const char *const call = "phnsw_search_batch_labeled_device";
   PH_TRY(walk_check(ix, lb, sp, flags, call));
   if (nq == 0) return 0;
-  if (((!queries_dev) == (!qids_dev)) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev || !want_dev ||
-      nq > 0xFFFFFFFFull || (queries_dev && (ldq < ix->store->ld || (ldq % 4) || ((uintptr_t)queries_dev % 16)))) {
+  if (!ph_device_queries_ok(ix, queries_dev, qids_dev, ldq) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev ||
+      !want_dev || nq > 0xFFFFFFFFull) {
     ph_set_error("%s: invalid argument (queries or qids, exactly one; outputs; want; queries need ldq >= store ld, multiple of "
                  "4, 16-byte base)", call);
     return PHNSW_E_INVALID;

@@ -241,6 +241,18 @@ struct PhExactScratch {
   hipEvent_t done = nullptr;
 };
 
+// resident waves of the one-wave kernels an index or a labels handle has launched, per (kernel, dynamic LDS size):
+// ph_resident_waves (filter_exact.hip), under a mutex of the owner
+struct PhResidentMemo {
+  struct Entry {
+    const void *fn;
+    size_t lds;
+    uint64_t waves;
+  };
+  std::vector<Entry> known;
+  int cus = 0;  // compute units of the device, 0 = not asked yet
+};
+
 // call_set.h: the scratch sets of one kind of filtered or exact call, one set per call in flight, handed out under mutex
 struct PhCallSet;
 struct PhCallPool {
@@ -277,6 +289,7 @@ struct phnsw_index {
   std::mutex exact_mutex;  // filter_exact.hip
   PhExactScratch exact[2];
   uint32_t exact_next = 0;
+  PhResidentMemo exact_resident;  // under exact_mutex
   PhCallPool autos;     // filter_auto.hip: PhAutoSet, the scratch of one routed filtered search
   PhCallPool denses;    // filter_dense.hip: PhDenseSet, of one exact search for a shared allow-list
   PhCallPool groupeds;  // filter_grouped.hip: PhGroupedSet, of one exact search over a table of allow-lists
@@ -498,6 +511,44 @@ int ph_exact_supported(const phnsw_index *ix, uint32_t k);
 void ph_exact_bottom_layer(const phnsw_index *ix, uint32_t *n_nodes, const uint32_t **nodes, const uint32_t **vec2node);
 int ph_filter_count(const phnsw_index *ix, const PhFilter &f, uint64_t nbitmaps, uint32_t *out_count_dev, hipStream_t stream);
 void ph_exact_free(phnsw_index *ix);
+// launch preparation of a one-wave kernel: the dynamic-LDS attribute above 48 KiB, and the waves of it the device holds
+// at once, asked once per (kernel, LDS) and kept in `memo` under `mutex` (filter_exact.hip)
+int ph_resident_waves(PhResidentMemo &memo, std::mutex &mutex, int device, const void *fn, size_t lds, uint64_t *waves);
+// what the device forms of the filtered calls ask of their queries: raw rows or Stored ids, exactly one; raw rows at
+// least a store row long, a multiple of 4 floats, on a 16-byte base
+static inline bool ph_device_queries_ok(const phnsw_index *ix, const float *queries_dev, const uint32_t *qids_dev, uint32_t ldq) {
+  return ((!queries_dev) != (!qids_dev)) &&
+         !(queries_dev && (ldq < ix->store->ld || (ldq % 4) || ((uintptr_t)queries_dev % 16)));
+}
+// The table of the exact calls over shared allow-lists, then its select (filter_dense.hip): one run of positions against
+// one ascending candidate list, node chunks x position chunks (dense_plan.h).
+struct StepTimes;  // call_set.h
+struct PhTableRun {
+  const float *queries;  // [..][ldq] or nullptr: Stored queries
+  uint32_t ldq;
+  const uint32_t *qids;     // Stored ids the caller has checked (below n), or nullptr
+  const uint32_t *order;    // position p is query order[p]; nullptr: query first + p
+  uint64_t first, npos;     // the run
+  const uint32_t *list;     // [cand] ascending VectorIds; cand == 0: the select alone, over no table
+  uint64_t cand;
+  uint32_t nodes_knob;      // ph_dense_nodes_knob / ph_dense_bytes_knob
+  uint64_t bytes_knob;
+  const uint32_t *exclude;  // [nq] or nullptr
+  const uint32_t *refuse;   // [nq] or nullptr: 0, or the status of a query that gets the empty row
+  const uint32_t *changed;  // nullptr, or the word of the run's group: nonzero = every row empty, PH_GROUP_ST_CHANGED
+  uint64_t *keys;           // [nq][k] key scratch
+  float *D;                 // the table block, plan.table_floats
+  uint32_t k;
+  uint32_t *out_ids;  // [nq][k]
+  float *out_d;
+  uint32_t *out_len, *status;  // [nq]
+  hipStream_t stream;
+  StepTimes *times;
+  int step_table, step_select;
+  const char *verbose_prefix;  // what PHNSW_VERBOSE's line says after "[phnsw] " and before "node chunk"
+  const char *call;            // the call's name in the error text
+};
+int ph_table_run(const phnsw_index *ix, PhWorkspace &ws, const PhTableRun &r);
 // The request of one routed filtered search (ph_auto_device, filter_auto.hip): per query the exact scan or the graph
 // walk, and the scan again for whatever the walk left short.  Device pointers of the caller; rows of k entries.
 struct PhAutoCall {
@@ -596,14 +647,12 @@ bool ph_tiny_matrix_cores(const phnsw_index *ix);  // the table of this index's 
 uint32_t ph_tiny_layer_count(const phnsw_index *ix, uint32_t n_layers, uint32_t ef);  // leading layers a launch may run densely
 uint64_t ph_tiny_max_positions(const phnsw_index *ix, uint32_t n_layers, uint32_t ef);  // 0 = no dense layers for this launch shape
 void ph_tiny_free(PhWorkspace &ws);
-// one table call of the exact search for a shared allow-list (filter_dense.hip) on a workspace of its own: D[p][t] for
-// positions [0, npos) and the VectorIds tnodes[0 .. tn), stride = tn rounded up to 64
+// one table call of the exact searches over shared allow-lists (ph_table_run) on a workspace of its own: D[p][t] for
+// positions [0, npos) -- position p is query order[p], or p itself without an order -- and the VectorIds tnodes[0 .. tn),
+// stride = tn rounded up to 64
 int ph_tiny_table_chunk(const phnsw_index *ix, PhWorkspace &ws, const float *queries, uint32_t ldq, const uint32_t *qids,
-                        uint32_t npos, const uint32_t *tnodes, uint32_t tn, float *D, hipStream_t stream, bool *kept);
-// ... and of the exact search over a table of allow-lists (filter_grouped.hip): position p is query order[p]
-int ph_tiny_table_chunk_ordered(const phnsw_index *ix, PhWorkspace &ws, const float *queries, uint32_t ldq,
-                                const uint32_t *qids, const uint32_t *order, uint32_t npos, const uint32_t *tnodes,
-                                uint32_t tn, float *D, hipStream_t stream, bool *kept);
+                        const uint32_t *order, uint32_t npos, const uint32_t *tnodes, uint32_t tn, float *D, hipStream_t stream,
+                        bool *kept);
 
 // launchers (search.hip)
 int ph_search_begin(PhWorkspace &ws, hipStream_t stream);

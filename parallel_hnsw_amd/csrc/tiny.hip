@@ -887,21 +887,14 @@ static int tiny_table(const phnsw_index *ix, PhWorkspace &ws, const PhDistArgs &
   return 0;
 }
 
-// the table of one (node chunk, position chunk) of the exact call for a shared allow-list (filter_dense.hip): positions
-// [0, npos) of the given queries (raw rows, or Stored ids the caller has checked) against the VectorIds tnodes[0 .. tn),
-// rows of D tn rounded up to 64 floats apart, the G = 2 form.  `ws` is the caller's own: only its operand buffers and
-// their key are used.  Returns what tiny_table returns.
+// the table of one (node chunk, position chunk) of the exact calls over shared allow-lists (ph_table_run,
+// filter_dense.hip): positions [0, npos) of the given queries (raw rows, or Stored ids the caller has checked) -- position
+// p is query order[p], or p itself without an order -- against the VectorIds tnodes[0 .. tn), rows of D tn rounded up to
+// 64 floats apart, the G = 2 form.  `ws` is the caller's own: only its operand buffers and their key are used.  Returns
+// what tiny_table returns.
 int ph_tiny_table_chunk(const phnsw_index *ix, PhWorkspace &ws, const float *queries, uint32_t ldq, const uint32_t *qids,
-                        uint32_t npos, const uint32_t *tnodes, uint32_t tn, float *D, hipStream_t stream, bool *kept) {
-  return tiny_table(ix, ws, ph_dist_args(ix->store), queries, ldq, qids, nullptr, npos, tnodes, tn, tiny_stride_of(tn), D, stream,
-                    2, kept);
-}
-
-// the same for a group of the exact call over a table of allow-lists (filter_grouped.hip): position p is query order[p]
-// of the whole batch's queries / checked Stored ids
-int ph_tiny_table_chunk_ordered(const phnsw_index *ix, PhWorkspace &ws, const float *queries, uint32_t ldq,
-                                const uint32_t *qids, const uint32_t *order, uint32_t npos, const uint32_t *tnodes,
-                                uint32_t tn, float *D, hipStream_t stream, bool *kept) {
+                        const uint32_t *order, uint32_t npos, const uint32_t *tnodes, uint32_t tn, float *D, hipStream_t stream,
+                        bool *kept) {
   return tiny_table(ix, ws, ph_dist_args(ix->store), queries, ldq, qids, order, npos, tnodes, tn, tiny_stride_of(tn), D, stream,
                     2, kept);
 }

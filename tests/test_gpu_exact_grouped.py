@@ -336,6 +336,23 @@ def test_bad_ids_and_selectors_are_reported_and_harm_nobody(kind, dim):
         assert (ids == 7).all() and (d == -1.0).all() and (ln == 7).all()
 
 
+def test_a_refused_selector_beside_a_group_of_three_node_chunks(monkeypatch):
+    """A selector outside the table puts its query into the reject group, which has no candidates: its row is written by
+    the select over no table, whatever the other groups need -- here 130 candidates in three node chunks of 64."""
+    w = sworld("f32", 256)
+    masks = np.stack([exactly(130, 77)])
+    sel = np.array([0, 0, 1, 0, 0])  # 1 == nfilters
+    qids = w["qids"][:5]
+    with env(monkeypatch, PHNSW_DENSE_NODES="64"):
+        dv = device_grouped(w["hix"], 10, masks, sel, qids=qids)
+    ref = xr.exact_topk(w["Ds"][:5], per_query(masks, np.zeros(5, dtype=np.int64)), None, None, 10)
+    good = [0, 1, 3, 4]
+    same(tuple(x[good] for x in dv[:3]), tuple(x[good] for x in ref))
+    assert not dv[3][good].any() and (ref[2][good] == 10).all()
+    assert dv[3][2] == 6 and dv[2][2] == 0
+    assert (dv[0][2] == EMPTY).all() and (bits(dv[1][2]) == bits(xr.FMAX)).all()
+
+
 # ---------------------------------------------------------------- 8: two streams, one stream twice
 def test_calls_in_flight_on_two_streams_and_twice_on_one():
     import torch

@@ -300,6 +300,23 @@ def test_a_stored_query_id_past_n_is_reported_and_harms_nobody(kind, dim):
     assert (none[3][bad] == 4).all() and not none[3][good].any() and not none[2].any()
 
 
+def test_a_refused_query_carried_through_three_node_chunks(monkeypatch):
+    """The refusal word of the select is the status itself.  130 candidates in node chunks of 64 are three chunks, so
+    the refused query's key list is stored empty, reloaded twice and written by a chunk that is not the first."""
+    w = sworld("f32", 256)
+    allow = exactly(130, 77)
+    qids = w["qids"][:5].copy()
+    qids[2] = N + 7
+    with env(monkeypatch, PHNSW_DENSE_NODES="64"):
+        dv = device_shared(w["hix"], 10, qids=qids, allow=allow)
+    ref = xr.exact_topk(w["Ds"][:5], allow, None, None, 10)
+    good = [0, 1, 3, 4]
+    same(tuple(x[good] for x in dv[:3]), tuple(x[good] for x in ref))
+    assert not dv[3][good].any() and (ref[2][good] == 10).all()
+    assert dv[3][2] == 4 and dv[2][2] == 0
+    assert (dv[0][2] == EMPTY).all() and (bits(dv[1][2]) == bits(xr.FMAX)).all()
+
+
 def test_two_calls_in_flight_on_two_streams():
     import torch
     w = sworld("f32", 256)
