@@ -685,6 +685,8 @@ static uint64_t two_launch_min() {
 }
 static std::atomic<uint64_t> g_two_launch_count{0};  // tests check that the split path really ran
 extern "C" uint64_t phnsw_debug_two_launch_count(void) { return g_two_launch_count.load(); }
+static std::atomic<uint64_t> g_table_order_count{0};  // ... and that a launch really took the table order
+extern "C" uint64_t phnsw_debug_table_order_count(void) { return g_table_order_count.load(); }
 // chunks of the last descent on this index (phnsw_last_search_dispatches then describes the last one)
 extern "C" uint32_t phnsw_debug_last_search_chunks(const phnsw_index *ix) { return ix ? ix->ws[ix->ws_last].n_chunks : 0; }
 
@@ -837,6 +839,21 @@ int ph_search_device(const phnsw_index *ix, const PhSearchCall &c) {
       a.out_d = ws.park_d;
     }
   }
+  // A plain launch that is not split and has a dense table walks in the order of the cells its queries land in: the
+  // table is made in natural order, a query's key is the cell of its nearest table nodes (tiny.hip), and a counting
+  // sort of the keys is the launch's `order` -- all on the launch's stream.  Order only: same arithmetic per query.
+  // (PHNSW_TABLE_ORDER=0 switches it off; lists under PH_TABLE_ORDER_MIN, the filtered, labeled and collecting calls
+  // and the build's searches keep the natural order.)
+  const uint32_t *table_pos = nullptr;
+  const char *const table_order_env = getenv("PHNSW_TABLE_ORDER");  // read per call: the tests switch it
+  if (T && !split && !a.order && !knn_mode && !out_stride && !out_index && !c.hint && !c.out_hit && !a.filter && !a.label_of &&
+      !a.collect_k && nq >= PH_TABLE_ORDER_MIN && !getenv("PHNSW_NO_LOCALITY") && !(table_order_env && table_order_env[0] == '0')) {
+    PhLayerHost &TL = mix->layers[T - 1];
+    rc = ph_layer_anchor_pos(ix->store, TL);  // first use on a loaded index; no-op afterwards, and for a layer without cells
+    if (!rc && TL.pos) rc = ph_workspace_order_ensure(ws, a.nq);
+    if (rc) return rc;
+    table_pos = TL.pos;
+  }
   rc = attach_probes(mix, c, a);
   if (rc) return rc;
   rc = ph_search_begin(ws, stream);
@@ -878,6 +895,10 @@ int ph_search_device(const phnsw_index *ix, const PhSearchCall &c) {
     if (c0) PH_HIP(hipMemsetAsync(ws.dtotals, 0, sizeof(unsigned long long) * 3 * PH_MAX_DISPATCH, stream));  // ... and counters
     if (!kept_table) {
       rc = ph_tiny_prepare(ix, ws, b, T, stream);
+      if (!rc && table_pos && b.tiny_layers == T) {
+        rc = ph_tiny_table_order(ws, b, table_pos, ix->store->n_anchors, stream);
+        if (!rc && b.table_by_query) g_table_order_count++;
+      }
       if (rc) return rc;
     }
     ws.d_tiny = b.tiny_layers != 0;

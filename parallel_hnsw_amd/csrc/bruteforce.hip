@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstring>
 #include <vector>
 
 #include "phnsw_device.h"
@@ -328,13 +329,104 @@ __global__ void ph_rank_of_cell_kernel(uint32_t *pos, uint32_t n, const uint32_t
   if (i < n) pos[i] = rank[pos[i]];
 }
 
-// The store's coarse cells: A anchors (every (n/A)-th row) and their chain ranks, made once.
+// One anchor per block: the normalised sum of the sample rows of its cell, added in sample order (members[] is the
+// stable counting sort of the sample by cell), component by component -- no float atomics, one order of additions,
+// so every run and every rank of a sharded build gets the same bits.  A cell without sample rows, or whose rows sum
+// to nothing, keeps its row.
+__global__ __launch_bounds__(256) void ph_anchor_mean_kernel(const float *__restrict__ rows, uint64_t row_stride, uint32_t ld,
+                                                             const uint32_t *__restrict__ start,
+                                                             const uint32_t *__restrict__ members, uint32_t A,
+                                                             const float *__restrict__ old, float *__restrict__ out) {
+  __shared__ float wsum[4];
+  const uint32_t a = blockIdx.x, t = threadIdx.x;
+  if (a >= A) return;
+  const uint32_t first = start[a], cnt = start[a + 1u] - first;
+  float ss = 0.f;
+  for (uint32_t j = t; j < ld; j += 256u) {
+    float acc = 0.f;
+    for (uint32_t i = 0; i < cnt; i++) acc += rows[(uint64_t)members[first + i] * row_stride + j];
+    out[(uint64_t)a * ld + j] = acc;
+    ss += acc * acc;
+  }
+#pragma unroll
+  for (int sft = 32; sft >= 1; sft >>= 1) ss += __shfl_xor(ss, sft);
+  if ((t & 63u) == 0) wsum[t >> 6] = ss;
+  __syncthreads();
+  const float norm = sqrtf(((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]);
+  const bool keep = !(norm > 0.f) || !(norm < PH_FMAX);  // empty cell, zero sum, or not a number: the row stays
+  for (uint32_t j = t; j < ld; j += 256u)  // a thread reads back only what it wrote itself
+    out[(uint64_t)a * ld + j] = keep ? old[(uint64_t)a * ld + j] : out[(uint64_t)a * ld + j] / norm;
+}
+
+#define PH_CELL_SAMPLE 262144u  // store rows the anchors are refined on, at most: a 1M build pays milliseconds
+
+// Cells that follow the data: every anchor is replaced ONCE by the normalised mean of the sample rows nearest to it
+// over all dimensions (a second pass adds nothing on clustered data).  raw [A][ld] in, refined [A][ld] out.
+static int ph_refine_anchors(const phnsw_store *s, uint32_t A, const float *raw, float *refined) {
+  const uint32_t ld = s->ld, m = (uint32_t)std::min<uint64_t>(s->n, PH_CELL_SAMPLE);
+  const uint64_t step = s->n / m;  // sample row i is store row i * step
+  const uint32_t QC = 65536;
+  float *samp = nullptr, *scores = nullptr;
+  uint32_t *cell = nullptr, *start = nullptr, *members = nullptr, *ids = nullptr;
+  const float *base = s->rows;
+  uint64_t row_stride = step * ld;
+  int rc = 0;
+  hipError_t e = hipMalloc(&scores, (size_t)std::min(QC, m) * A * 4);
+  if (e == hipSuccess) e = hipMalloc(&cell, (size_t)m * 4);
+  if (e == hipSuccess) e = hipMalloc(&start, ((size_t)A + 1u) * 4);
+  if (e == hipSuccess) e = hipMalloc(&members, (size_t)m * 4);
+  if (e == hipSuccess && (ph_store_converted(s) || row_stride > 0xFFFFFFFCull)) {
+    // f16 / i8 store (or a stride the GEMM cannot take): the sample as dense f32 rows
+    std::vector<uint32_t> h(m);
+    for (uint32_t i = 0; i < m; i++) h[i] = (uint32_t)(i * step);
+    e = hipMalloc(&samp, (size_t)m * ld * 4);
+    if (e == hipSuccess) e = hipMalloc(&ids, (size_t)m * 4);
+    if (e == hipSuccess) e = hipMemcpy(ids, h.data(), (size_t)m * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+      if (ph_store_converted(s))
+        rc = ph_converted_gather_rows(s, ids, 0, m, samp);
+      else
+        hipLaunchKernelGGL(ph_gather_rows_f32_kernel, dim3((m + 3) / 4), dim3(256), 0, 0, s->rows, ld, ids, 1u, m, samp);
+    }
+    base = samp;
+    row_stride = ld;
+  }
+  if (e == hipSuccess && !rc) {
+    for (uint32_t at = 0; at < m; at += QC) {
+      const uint32_t cnt = std::min(QC, m - at);
+      dim3 grid((A + BF_TN - 1) / BF_TN, (cnt + BF_TM - 1) / BF_TM);
+      hipLaunchKernelGGL(ph_gemm_nt_mfma_kernel, grid, dim3(256), 0, 0, base + (uint64_t)at * row_stride, (uint32_t)row_stride,
+                         cnt, raw, ld, A, ld, scores, (uint64_t)A);
+      hipLaunchKernelGGL(ph_argmax_rows_kernel, dim3(std::min<uint32_t>(cnt, 256u * 16u)), dim3(64), 0, 0, scores, (uint64_t)A,
+                         A, cnt, cell + at);
+    }
+    rc = ph_cell_order_device(cell, m, A, start, members, 0);
+    if (!rc) {
+      hipLaunchKernelGGL(ph_anchor_mean_kernel, dim3(A), dim3(256), 0, 0, base, row_stride, ld, start, members, A, raw, refined);
+      e = hipGetLastError();
+      if (e == hipSuccess) e = hipDeviceSynchronize();
+    }
+  }
+  if (e != hipSuccess) rc = ph_hip_fail(e, "store cells (anchor means)", __FILE__, __LINE__);
+  if (samp) hipFree(samp);
+  if (ids) hipFree(ids);
+  if (scores) hipFree(scores);
+  if (cell) hipFree(cell);
+  if (start) hipFree(start);
+  if (members) hipFree(members);
+  return rc;
+}
+
+// The store's coarse cells: A anchors and their chain ranks, made once.  The anchors start as every (n/A)-th row and
+// are then refined (above); PHNSW_CELLS=raw keeps the rows themselves and the 256-dimension assignment of before.
 static int ph_store_anchors(phnsw_store *s) {
   if (s->anchors) return 0;
   uint32_t amax = 4096u;
   if (const char *e = getenv("PHNSW_ANCHORS")) amax = atoi(e) >= 64 ? (uint32_t)atoi(e) : amax;  // tuning knob
   const uint32_t A = (uint32_t)std::min<uint64_t>(amax, std::max<uint64_t>(s->n / 16u, 1u)), ld = s->ld;
   const uint64_t stride = s->n / A;
+  const char *const cells_env = getenv("PHNSW_CELLS");
+  const bool cells_raw = cells_env && !strcmp(cells_env, "raw");
   float *anchors = nullptr, *gram = nullptr;
   uint32_t *rank = nullptr, *ids = nullptr;
   std::vector<uint32_t> h(A);
@@ -349,6 +441,15 @@ static int ph_store_anchors(phnsw_store *s) {
       (void)ph_converted_gather_rows(s, ids, 0, A, anchors);
     else
       hipLaunchKernelGGL(ph_gather_rows_f32_kernel, dim3((A + 3) / 4), dim3(256), 0, 0, s->rows, ld, ids, 1u, A, anchors);
+    if (!cells_raw) {
+      float *refined = nullptr;
+      e = hipMalloc(&refined, (size_t)A * ld * 4);
+      if (e == hipSuccess && ph_refine_anchors(s, A, anchors, refined)) e = hipErrorUnknown;  // (its message stands)
+      if (e == hipSuccess) std::swap(anchors, refined);
+      if (refined) hipFree(refined);
+    }
+  }
+  if (e == hipSuccess) {
     dim3 grid((A + BF_TN - 1) / BF_TN, (A + BF_TM - 1) / BF_TM);
     hipLaunchKernelGGL(ph_gemm_nt_mfma_kernel, grid, dim3(256), 0, 0, anchors, ld, A, anchors, ld, A, ld, gram, (uint64_t)A);
     hipLaunchKernelGGL(ph_anchor_chain_kernel, dim3(1), dim3(1024), (A + 32) * 4, 0, gram, A, rank);
@@ -365,6 +466,7 @@ static int ph_store_anchors(phnsw_store *s) {
   s->anchors = anchors;
   s->anchor_rank = rank;
   s->n_anchors = A;
+  s->cells_raw = cells_raw;
   return 0;
 }
 
@@ -406,9 +508,10 @@ int ph_layer_cells_range(const phnsw_store *cs, const PhLayerHost &L, uint32_t f
         Q = qrows;
       }
       dim3 grid((A + BF_TN - 1) / BF_TN, (cnt + BF_TM - 1) / BF_TM);
-      // the leading 256 dimensions are enough for a coarse cell (a hint, not a result)
+      // all dimensions: over the leading 256 the noise of a clustered row outweighs what it shares with its cluster,
+      // and the best of the foreign anchors wins; the raw cells keep their 256
       hipLaunchKernelGGL(ph_gemm_nt_mfma_kernel, grid, dim3(256), 0, 0, Q, ld, cnt, s->anchors, ld, A,
-                         std::min<uint32_t>(ld, 256u), scores, (uint64_t)A);
+                         s->cells_raw ? std::min<uint32_t>(ld, 256u) : ld, scores, (uint64_t)A);
       hipLaunchKernelGGL(ph_argmax_rows_kernel, dim3(std::min<uint32_t>(cnt, 256u * 16u)), dim3(64), 0, 0, scores,
                          (uint64_t)A, A, cnt, out_pos + at);
     }
@@ -436,6 +539,37 @@ int ph_layer_anchor_pos(const phnsw_store *cs, PhLayerHost &L) {
   }
   return rc;
 }
+
+// the cells as the tests and the measuring scripts read them (made on first use, like everywhere): the store's anchors
+// [n_anchors][ld] and chain ranks [n_anchors] (either pointer may be NULL: the count alone), a layer's pos [n_nodes]
+extern "C" int phnsw_debug_store_cells(phnsw_store *s, float *anchors_out, uint32_t *rank_out, uint32_t *n_anchors_out) try {
+  if (!s || !n_anchors_out || !(ph_store_f32(s) || ph_store_converted(s)) || s->n < 16 || s->metric == PHNSW_METRIC_L2) {
+    ph_set_error("phnsw_debug_store_cells: need an f32, f16 or i8 store with a dot-product metric");
+    return PHNSW_E_INVALID;
+  }
+  PH_HIP(hipSetDevice(s->device));
+  if (int rc = ph_store_anchors(s)) return rc;
+  *n_anchors_out = s->n_anchors;
+  if (anchors_out) PH_HIP(hipMemcpy(anchors_out, s->anchors, (size_t)s->n_anchors * s->ld * 4, hipMemcpyDeviceToHost));
+  if (rank_out) PH_HIP(hipMemcpy(rank_out, s->anchor_rank, (size_t)s->n_anchors * 4, hipMemcpyDeviceToHost));
+  return 0;
+} catch (...) { return ph_caught(); }
+
+extern "C" int phnsw_debug_layer_cells(phnsw_index *ix, uint32_t lft, uint32_t *pos_out) try {
+  if (!ix || !pos_out || lft >= ix->layers.size()) {
+    ph_set_error("phnsw_debug_layer_cells: invalid argument");
+    return PHNSW_E_INVALID;
+  }
+  PH_HIP(hipSetDevice(ix->store->device));
+  PhLayerHost &L = ix->layers[lft];
+  if (int rc = ph_layer_anchor_pos(ix->store, L)) return rc;
+  if (!L.pos) {
+    ph_set_error("phnsw_debug_layer_cells: layer %u carries no cells", lft);
+    return PHNSW_E_UNSUPPORTED;
+  }
+  PH_HIP(hipMemcpy(pos_out, L.pos, (size_t)L.n_nodes * 4, hipMemcpyDeviceToHost));
+  return 0;
+} catch (...) { return ph_caught(); }
 
 // milliseconds the MFMA GEMM launches of the calling thread's last brute-force pass took
 extern "C" float phnsw_bruteforce_last_gemm_ms(void) { return g_bf_gemm_ms; }

@@ -1278,13 +1278,28 @@ static int extend_layer_impl(phnsw_index *ix, uint32_t lft, std::vector<uint32_t
       return ph_hip_fail(e, "extend_layer upload", __FILE__, __LINE__);
     }
   }
-  if (L.pos) {  // keep the locality order: old nodes keep their rank, new nodes go last
-    std::vector<uint32_t> op(n_old), np(n_new, PH_EMPTY32);
+  if (L.pos) {  // keep the cells: old nodes keep theirs, new nodes get their own (a pos is always below the anchor count)
+    std::vector<uint32_t> op(n_old), np(n_new, PH_EMPTY32), fresh_at, fresh;
     PH_HIP(hipMemcpy(op.data(), L.pos, (size_t)n_old * 4, hipMemcpyDeviceToHost));
     for (uint32_t i = 0; i < n_old; i++) np[old_map[i]] = op[i];
-    uint32_t next = n_old;
     for (uint32_t i = 0; i < n_new; i++)
-      if (np[i] == PH_EMPTY32) np[i] = next++;
+      if (np[i] == PH_EMPTY32) fresh_at.push_back(i), fresh.push_back(nodes[i]);
+    int crc = 0;
+    if (!fresh.empty()) {
+      DevBuf<uint32_t> fnodes, fpos;
+      crc = fnodes.alloc(fresh.size());
+      if (!crc) crc = fpos.alloc(fresh.size());
+      if (!crc && hipMemcpy(fnodes.p, fresh.data(), fresh.size() * 4, hipMemcpyHostToDevice) != hipSuccess) crc = PHNSW_E_HIP;
+      PhLayerHost F;  // the new nodes as a node list of their own: borrowed pointers, never freed as a layer
+      F.nodes = fnodes.p, F.n_nodes = (uint32_t)fresh.size(), F.identity = false;
+      if (!crc) crc = ph_layer_cells_range(ix->store, F, 0, F.n_nodes, fpos.p);
+      if (!crc && hipMemcpy(fresh.data(), fpos.p, fresh.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) crc = PHNSW_E_HIP;
+      for (size_t k = 0; k < fresh.size() && !crc; k++) np[fresh_at[k]] = fresh[k];
+    }
+    if (crc) {
+      ph_layer_free(NL);
+      return crc;
+    }
     hipError_t e = hipMalloc(&NL.pos, (size_t)n_new * 4);
     if (e == hipSuccess) e = hipMemcpy(NL.pos, np.data(), (size_t)n_new * 4, hipMemcpyHostToDevice);
     if (e != hipSuccess) {

@@ -70,7 +70,7 @@ int ph_build_groups_device(const uint32_t *init_ids, const float *init_d, const 
 
 // ---- locality schedule (a scheduling hint, never part of a result) ----
 // Every large layer carries pos[node] = the node's coarse cell: its exact nearest anchor, the
-// anchors being a strided sample of the layer (bruteforce.hip, one MFMA GEMM pass).  The search
+// anchors being the means of the cells of a strided sample (bruteforce.hip, one MFMA GEMM pass).  The search
 // kernel walks a query list sorted by cell, one contiguous eighth per XCD, so that the rows
 // one L2 / the Infinity Cache serve together belong to neighbouring queries (search.hip).
 
@@ -102,6 +102,101 @@ int ph_order_by_keys_device(const uint32_t *keys, uint32_t n, uint32_t *order_ou
   if (tmp) ph_pool_free(tmp);
   return rc;
 }
+
+// ---- stable counting sort by cell (the table order of a launch, api.hip; the anchors' means, bruteforce.hip) ----
+// Three kernels, nothing else on the stream: how many indices a cell has (integer atomics: a count has one value
+// whatever their order), where a cell starts, and one wave per cell that passes over the keys in index order and
+// writes its own indices as it meets them -- so equal keys keep index order by construction, run after run.
+static __device__ __forceinline__ uint32_t cell_of_key(uint32_t key, uint32_t bins) { return key < bins ? key : bins - 1u; }
+
+__global__ void ph_cell_hist_kernel(const uint32_t *keys, uint32_t n, uint32_t bins, uint32_t *cnt) {
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    atomicAdd(&cnt[cell_of_key(keys[i], bins)], 1u);
+}
+
+// in place, one block: cnt[0 .. bins] (cnt[bins] = 0) -> exclusive prefix sums, cnt[bins] = n
+__global__ __launch_bounds__(1024) void ph_cell_prefix_kernel(uint32_t *cnt, uint32_t bins) {
+  __shared__ uint32_t part[1024];
+  const uint32_t t = threadIdx.x, per = (bins + 1u + 1023u) / 1024u;
+  const uint32_t lo = min(t * per, bins + 1u), hi = min(lo + per, bins + 1u);
+  uint32_t sum = 0;
+  for (uint32_t i = lo; i < hi; i++) sum += cnt[i];
+  part[t] = sum;
+  __syncthreads();
+  for (uint32_t d = 1; d < 1024u; d <<= 1) {  // inclusive scan of the threads' sums
+    const uint32_t v = t >= d ? part[t - d] : 0u;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  uint32_t run = part[t] - sum;
+  for (uint32_t i = lo; i < hi; i++) {
+    const uint32_t c = cnt[i];
+    cnt[i] = run;
+    run += c;
+  }
+}
+
+__global__ __launch_bounds__(64) void ph_cell_scatter_kernel(const uint32_t *__restrict__ keys, uint32_t n, uint32_t bins,
+                                                             const uint32_t *__restrict__ start, uint32_t *__restrict__ order) {
+  const uint32_t lane = threadIdx.x;
+  const uint64_t lt = lanemask_lt(lane);
+  for (uint32_t b = blockIdx.x; b < bins; b += gridDim.x) {
+    const uint32_t first = start[b], want = start[b + 1u] - first;  // start[] is non-decreasing and ends at n
+    uint32_t have = 0;
+    for (uint32_t base = 0; base < n && have < want; base += 256u) {
+      uint32_t k[4];
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const uint32_t i = base + 64u * j + lane;
+        k[j] = i < n ? cell_of_key(keys[i], bins) : PH_EMPTY32;  // bins <= 2^31: never a cell
+      }
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        const bool mine = k[j] == b;
+        const uint64_t m = __ballot(mine);
+        // have + rank < want <= n - first: the cell holds exactly `want` indices, counted from these same keys
+        const uint32_t at = first + have + (uint32_t)__popcll(m & lt);
+        if (mine && at < n) order[at] = base + 64u * j + lane;
+        have += (uint32_t)__popcll(m);
+      }
+    }
+  }
+}
+
+int ph_cell_order_device(const uint32_t *keys, uint32_t n, uint32_t bins, uint32_t *start, uint32_t *order_out, hipStream_t st) {
+  if (n == 0 || bins == 0) return 0;
+  PH_HIP(hipMemsetAsync(start, 0, ((size_t)bins + 1u) * 4u, st));
+  hipLaunchKernelGGL(ph_cell_hist_kernel, dim3(grid1(n)), dim3(256), 0, st, keys, n, bins, start);
+  hipLaunchKernelGGL(ph_cell_prefix_kernel, dim3(1), dim3(1024), 0, st, start, bins);
+  hipLaunchKernelGGL(ph_cell_scatter_kernel, dim3(std::min<uint32_t>(bins, 1u << 16)), dim3(64), 0, st, keys, n, bins, start,
+                     order_out);
+  PH_HIP(hipGetLastError());
+  return 0;
+}
+
+// the sort alone, host arrays in and out (tests)
+extern "C" int phnsw_debug_cell_order(const uint32_t *keys, uint32_t n, uint32_t bins, uint32_t *order_out) try {
+  if (!keys || !order_out || n == 0 || bins == 0 || bins > (1u << 24)) {
+    ph_set_error("phnsw_debug_cell_order: invalid argument");
+    return PHNSW_E_INVALID;
+  }
+  uint32_t *k = nullptr, *start = nullptr, *order = nullptr;
+  hipError_t e = ph_pool_alloc((void **)&k, (size_t)n * 4);
+  if (e == hipSuccess) e = ph_pool_alloc((void **)&start, ((size_t)bins + 1u) * 4);
+  if (e == hipSuccess) e = ph_pool_alloc((void **)&order, (size_t)n * 4);
+  if (e == hipSuccess) e = hipMemcpy(k, keys, (size_t)n * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemset(order, 0xFF, (size_t)n * 4);
+  int rc = e == hipSuccess ? ph_cell_order_device(k, n, bins, start, order, 0) : ph_hip_fail(e, "cell order staging", __FILE__, __LINE__);
+  if (!rc) {
+    e = hipMemcpy(order_out, order, (size_t)n * 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = ph_hip_fail(e, "cell order readback", __FILE__, __LINE__);
+  }
+  if (k) ph_pool_free(k);
+  if (start) ph_pool_free(start);
+  if (order) ph_pool_free(order);
+  return rc;
+} catch (...) { return ph_caught(); }
 
 // start[0..n] = exclusive prefix sums of cnt[0..n] (cnt[n] must be 0, so start[n] = total); async on `st`
 int ph_exclusive_scan_u32(const uint32_t *cnt, uint32_t n_plus_1, uint32_t *start, hipStream_t st) {
@@ -144,6 +239,9 @@ void ph_workspace_order_free(PhWorkspace &ws) {
   if (ws.oiota) hipFree(ws.oiota);
   if (ws.oorder) hipFree(ws.oorder);
   if (ws.sort_tmp) hipFree(ws.sort_tmp);
+  if (ws.ocell) hipFree(ws.ocell);
+  ws.ocell = nullptr;
+  ws.ocell_cap = 0;
   ws.okey = ws.okey_sorted = ws.oiota = ws.oorder = nullptr;
   ws.sort_tmp = nullptr;
   ws.sort_tmp_bytes = 0;

@@ -122,6 +122,7 @@ struct phnsw_store {
   float *anchors = nullptr;
   uint32_t *anchor_rank = nullptr;
   uint32_t n_anchors = 0;
+  bool cells_raw = false;  // PHNSW_CELLS=raw when the anchors were made: the cells of before (A/B comparison)
   bool owns_rows = true;
   uint64_t n = 0;
   uint32_t dim = 0, ld = 0;
@@ -165,6 +166,8 @@ struct PhWorkspace {
   void *sort_tmp = nullptr;
   size_t sort_tmp_bytes = 0;
   uint32_t order_cap = 0;
+  uint32_t *ocell = nullptr;  // table order (api.hip): queries per cell, then where a cell's queries start, [ocell_cap + 1]
+  uint32_t ocell_cap = 0;
   // dense top layers (tiny.hip): distance table [positions][stride], neighbour rows in table ids,
   // per-node layer membership (+ one flag word)
   float *tiny_d = nullptr;
@@ -395,6 +398,9 @@ struct PhSearchArgs {
   uint32_t collect_k, collect_flags;
   uint32_t *collect_ids;
   float *collect_d;
+  // table_by_query != 0: the per-launch table was made in natural order and `order` only afterwards (api.hip: the
+  // table order), so a query's row is q, not its position.  (At the end, like the pairs above.)
+  uint32_t table_by_query;
 };
 
 uint32_t ph_default_ovf_cap(uint32_t ef);
@@ -606,6 +612,7 @@ int ph_exact_check(const phnsw_index *ix, uint64_t k, const char *call);
 // locality schedule helpers (group.hip / api.hip)
 #define PH_ORDER_MIN 16384u  // shorter query lists run in natural order
 #define PH_POS_MIN 256u     // smaller layers carry no cells (their node id is the key)
+#define PH_TABLE_ORDER_MIN 2048u  // a plain launch with a dense table and at least this many queries walks in cell order
 // a layer whose vector rows do not fit one XCD's L2 (4 MiB) gets a launch of its own in a split
 // descent, its queries sorted by the cell they arrive in (PHNSW_SPLIT_BYTES overrides: tuning knob)
 #define PH_SPLIT_BYTES (4ull << 20)
@@ -620,6 +627,12 @@ int ph_layer_cells_range(const phnsw_store *s, const PhLayerHost &L, uint32_t fi
 void ph_store_anchors_free(phnsw_store *s);
 int ph_order_by_keys_device(const uint32_t *keys, uint32_t n, uint32_t *order_out, hipStream_t st);
 int ph_layer_range_order(PhLayerHost &L, uint32_t first, uint32_t count, const uint32_t **out);
+// stable counting sort (group.hip): order_out [n] = the indices 0 .. n-1 by ascending key, equal keys in index order.
+// Keys are taken as min(key, bins - 1); start [bins + 1] is scratch.  Async on `st`, no host synchronisation.
+int ph_cell_order_device(const uint32_t *keys, uint32_t n, uint32_t bins, uint32_t *start, uint32_t *order_out, hipStream_t st);
+// the table order of a launch (tiny.hip): key of query q = pos[arg-min of row q of the natural-order table], the
+// counting sort of the queries by it into ws.oorder; points b.order at it and sets b.table_by_query
+int ph_tiny_table_order(PhWorkspace &ws, PhSearchArgs &b, const uint32_t *pos, uint32_t bins, hipStream_t stream);
 
 // a search-only row store (f16, i8 or i8q): searched like the f32 store, its rows converted to f32 where a GEMM or a host reads them
 static inline bool ph_store_converted(const phnsw_store *s) { return ph_rows_converted(s->kind); }

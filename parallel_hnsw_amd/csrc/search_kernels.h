@@ -193,8 +193,9 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
     // knn modes: the query is a node of the bottom layer
     const uint32_t qnode = (BIG && a.knn_nodes) ? a.knn_nodes[q] : a.first_node + q;
     uint32_t qvec = a.knn_mode ? a.layers[last_layer].nodes[qnode] : (a.qids ? a.qids[q] : 0u);
-    // row of this query in the dense table: its launch position, or (the build's kept table) its NodeId in layer X
-    uint64_t trow = qpos;
+    // row of this query in the dense table: its launch position (the query itself when the table was made before the
+    // order, api.hip), or (the build's kept table) its NodeId in layer X
+    uint64_t trow = a.table_by_query ? q : qpos;
     if (a.tiny_rows) trow = (uint64_t)((a.tiny_row_map ? a.tiny_row_map[qvec] : qvec) - a.tiny_row_first);
     Dist dist;
     if (a.queries && !a.knn_mode)

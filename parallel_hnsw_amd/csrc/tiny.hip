@@ -954,6 +954,74 @@ int ph_tiny_prepare(const phnsw_index *ix, PhWorkspace &ws, PhSearchArgs &a, uin
   return 0;
 }
 
+// ------------------------------------------------------------------ the table order of a launch
+
+// The table of a launch already holds every query's distance to every node of the table layer, so where a query
+// will land there costs one pass over its row.  key[q] = the cell (pos, bruteforce.hip) most of its four nearest
+// table nodes lie in, the nearest of them deciding a tie: on the headline data the nearest node alone names the cell
+// a GEMM of the query against the anchors would in 0.43 of the queries, the four in 0.47 (profiles/cells/).  One wave
+// per query; the nodes are ranked by (distance, table id) like everywhere, so the key is one value run after run.
+__global__ __launch_bounds__(64) void ph_tiny_row_cell_kernel(const float *__restrict__ D, uint32_t stride, uint32_t tn,
+                                                              uint32_t nq, const uint32_t *__restrict__ pos,
+                                                              uint32_t *__restrict__ key) {
+  const uint32_t lane = threadIdx.x;
+  for (uint32_t q = blockIdx.x; q < nq; q += gridDim.x) {
+    const float *row = D + (uint64_t)q * stride;
+    uint64_t top[4] = {KEY_NONE, KEY_NONE, KEY_NONE, KEY_NONE};  // the lane's own four nearest, ascending
+    for (uint32_t t = lane; t < tn; t += 64) {
+      uint64_t k = mkkey(row[t], t);
+      if (k < top[3]) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          const uint64_t lo = k < top[j] ? k : top[j], hi = k < top[j] ? top[j] : k;
+          top[j] = lo;
+          k = hi;
+        }
+      }
+    }
+    uint32_t cell[4], n = 0;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {  // the wave's four nearest: the least head, four times (keys are distinct)
+      uint64_t m = top[0];
+#pragma unroll
+      for (int s = 32; s >= 1; s >>= 1) {
+        const uint64_t o = __shfl_xor(m, s);
+        m = o < m ? o : m;
+      }
+      if (top[0] == m) top[0] = top[1], top[1] = top[2], top[2] = top[3], top[3] = KEY_NONE;
+      const uint32_t t = (uint32_t)m & IDM;
+      cell[r] = 0u;
+      if (m != KEY_NONE && t < tn) cell[r] = pos[t], n = r + 1;  // (wave-uniform)
+    }
+    uint32_t best = 0, best_cnt = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      uint32_t cnt = 0;
+#pragma unroll
+      for (int j = 0; j < 4; j++) cnt += ((uint32_t)j < n && cell[j] == cell[i]) ? 1u : 0u;
+      if ((uint32_t)i < n && cnt > best_cnt) best = cell[i], best_cnt = cnt;
+    }
+    if (lane == 0) key[q] = best;
+  }
+}
+
+int ph_tiny_table_order(PhWorkspace &ws, PhSearchArgs &b, const uint32_t *pos, uint32_t bins, hipStream_t stream) {
+  if (!b.tiny_layers || b.tiny_rows || !pos || !bins || ws.order_cap < b.nq) return 0;
+  if (ws.ocell_cap < bins) {
+    if (ws.ocell) PH_HIP(hipFree(ws.ocell));
+    ws.ocell = nullptr, ws.ocell_cap = 0;
+    PH_HIP(hipMalloc(&ws.ocell, ((size_t)bins + 1u) * 4u));
+    ws.ocell_cap = bins;
+  }
+  hipLaunchKernelGGL(ph_tiny_row_cell_kernel, dim3(std::min<uint32_t>(b.nq, 1u << 16)), dim3(64), 0, stream, b.tiny_d,
+                     b.tiny_stride, b.tiny_n, b.nq, pos, ws.okey);
+  int rc = ph_cell_order_device(ws.okey, b.nq, bins, ws.ocell, ws.oorder, stream);
+  if (rc) return rc;
+  b.order = ws.oorder;
+  b.table_by_query = 1u;
+  return 0;
+}
+
 // ------------------------------------------------------------------ the build's kept table
 
 void ph_build_table_free(phnsw_index *ix) {
