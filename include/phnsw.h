@@ -457,8 +457,8 @@ int phnsw_search_exact_labeled_device(const phnsw_index *ix, const phnsw_labels 
  * shared collection, a time range as a few bucket labels.  One label per row makes the lists of distinct labels
  * disjoint, so a set is more slices of the same scan: a (query, wanted label) PAIR takes the place of a query in the
  * machinery of phnsw_search_exact_labeled, and a query that wants {a, b} shares the tile of label a with every other
- * query that wants a.  EXACT scan only: there is NO graph walk by set and NO routed call by set (phnsw_search_batch_labeled
- * and phnsw_search_labeled_auto take one label per query).
+ * query that wants a.  This is the EXACT scan; the graph walk by set is phnsw_search_batch_labelset and the routed call by
+ * set phnsw_search_labelset_auto (both below, after their one-label forms).
  * The sets of a batch in CSR form: want_first[nq + 1] (u32, want_first[0] == 0, non-decreasing) and
  * want_values[nwant] (u32 labels), nwant == want_first[nq]; S_q = { want_values[i] : want_first[q] <= i < want_first[q+1] }.
  * Candidates of q: the vectors listed (as phnsw_labels_create lists) under any label of S_q, except exclude[q].  A label
@@ -620,6 +620,93 @@ int phnsw_search_labeled_auto_device(const phnsw_index *ix, const phnsw_labels *
                                      const uint32_t *exclude_dev, const uint32_t *want_dev, uint64_t k, uint64_t scan_below,
                                      uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
                                      uint32_t *out_route_dev, uint32_t *status_dev, void *stream);
+/* ---- the graph walk restricted by a SET of row labels, `label IN (a, b, c)`: phnsw_search_batch_labeled with a set per
+ * query.  The sets of a batch in CSR form as phnsw_search_exact_labelset takes them: want_first[nq + 1], want_values[nwant],
+ * S_q = { want_values[i] : want_first[q] <= i < want_first[q+1] }.  A batch sends 4 * (nq + 1) + 4 * nwant bytes, not nq
+ * bitmaps of ceil(n / 32) words.
+ * Candidates: vector v passes iff label_of[v] != PHNSW_LABEL_NONE (v is listed) and label_of[v] is a label of S_q.  A
+ * label that occurs twice in S_q, PHNSW_LABEL_NONE in S_q and labels nobody carries need no handling under this test.
+ * Arguments as phnsw_search_batch_labeled[_device] with (want_first, want_values) in place of want; the device form takes
+ * nwant as well, as phnsw_search_exact_labelset_device does.
+ * ROW EQUALITY: the rows, lengths, stats and statuses are those of phnsw_search_batch_filtered[_device] called with the
+ * per-query bitmaps {v : v listed and labels[v] in S_q}, bit for bit: the same post-filter walk, the same entry-vector
+ * quirk unless flags has PHNSW_FILTER_STRICT, k cuts the same way (host form; 0 = the whole queue).  An empty set, a set
+ * of PHNSW_LABEL_NONE only, or a set of labels nobody carries gives the row an all-zero bitmap gives.  The default filter
+ * of phnsw_index_set_filter_device is NOT consulted.  The result depends on none of: the order of labels inside a set,
+ * duplicates, the order of the batch, how the sets overlap, any knob.  Hence a batch of one-label sets equals
+ * phnsw_search_batch_labeled's rows, stats included.
+ * Checks, in this order: index and sp as phnsw_search_batch; a null or stale `lb`, refused as phnsw_search_batch_labeled
+ * refuses it; unknown flag bits; (host form) k past number_of_candidates; nq == 0, a no-op; exactly one of queries /
+ * qids, the outputs, want_first, and want_values (NULL only when nwant == 0); nq and nwant <= 2^31 - 2 (PHNSW_E_INVALID).
+ * The host form reads nwant from want_first[nq] and then refuses, before any device work and naming the query, a Stored
+ * query id at or past n, want_first[0] != 0 and a want_first that runs backwards.  Every message names the call.
+ * Cost of the membership test: per 64 tested ids one 4-byte load per lane and, per label of the set, one scalar load, one
+ * compare and one OR -- LINEAR in the length of the set, no LDS, no sort and no preparation kernel; first and last are
+ * read once per query.  The test runs over a layer's queue once per layer, not per evaluated row.  Sets of hundreds of
+ * labels are legal and slow in proportion.
+ * The host form stages its arrays once per call (queries, ids, the 4 * (nq + 1) + 4 * nwant bytes of the sets) and runs
+ * on a stream of its own; a query whose frontier spill overflowed is re-run with more room, as in
+ * phnsw_search_batch_labeled.
+ * Guidance (measured on 1M x 768 f32 rows, cosine, ef 256 / probe_depth 8, strict, 10 000-query batches of distinct
+ * labels drawn at random out of 1000 labels of 1000 rows, the variants alternating in one run;
+ * profiles/labelset_walk/README.md): against phnsw_search_batch_filtered_device with the union as per-query bitmaps
+ * already on the device the device form took 0.992, 0.993 and 0.998 of its time at sets of 1, 4 and 32 labels (26.4,
+ * 25.5 and 20.9 ms; run-to-run spread of either up to 0.25 ms), and 0.54, 0.54 and 0.49 of it with the upload of what
+ * describes the filter counted on both sides (1.25 GB of bitmaps against 80 KB to 1.3 MB of sets).  At one label per set
+ * it took 26.36 ms where phnsw_search_batch_labeled_device took 26.39 ms: the difference is below the spread of the same
+ * run (0.16 to 0.25 ms).  Against phnsw_search_exact_labelset_device at sets of 4: slower up to a union of 20 000 rows
+ * (22.0 ms against 17.6), faster from 40 000 (20.3 against 34.2).  Not measured: the host form, sets longer than 32, other
+ * store kinds, L2, the latency kernels (small batches), and whether the registers or the LDS decide the resident waves of
+ * the 15 instances that report one wave per SIMD fewer than their label twins. */
+int phnsw_search_batch_labelset(const phnsw_index *ix, const phnsw_labels *lb, const float *queries, const uint64_t *qids,
+                                uint64_t nq, const phnsw_search_params *sp, uint32_t upto_layers, const uint64_t *exclude,
+                                const uint32_t *want_first, const uint32_t *want_values, uint32_t flags, uint64_t k,
+                                uint64_t *out_ids, float *out_d, uint64_t *out_len, uint64_t *out_stats);
+/* device form: device pointers, rows of number_of_candidates entries as phnsw_search_batch_filtered_device writes them.
+ * ENQUEUED on `stream`; never synchronises.  want_first_dev [nq + 1] and want_values_dev [nwant] are read by the kernels:
+ * keep them alive and unchanged until the work on `stream` is done.  The offsets are not trusted: a query whose range is
+ * not inside [0, nwant] or runs backwards does not walk -- status_dev[q] = 8 (phnsw_search_exact_labelset_device's
+ * value), an empty row, length 0, stats 0 --, nothing outside want_values[0 .. nwant) is ever read, and every other
+ * query is unaffected.  Status 8 is raised for these range faults ONLY: ranges that OVERLAP are harmless to a walk (every
+ * query reads its own range) and are NOT detected here, unlike in phnsw_search_exact_labelset_device and
+ * phnsw_search_labelset_auto_device.  Other statuses as phnsw_search_batch_labeled_device. */
+int phnsw_search_batch_labelset_device(const phnsw_index *ix, const phnsw_labels *lb, const float *queries_dev, uint32_t ldq,
+                                       const uint32_t *qids_dev, uint64_t nq, const phnsw_search_params *sp,
+                                       uint32_t upto_layers, const uint32_t *exclude_dev, const uint32_t *want_first_dev,
+                                       const uint32_t *want_values_dev, uint64_t nwant, uint32_t flags,
+                                       uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                       uint32_t *out_stats_dev, uint32_t *status_dev, void *stream);
+/* ---- one call by a set of labels that routes: phnsw_search_labeled_auto with (want_first, want_values[, nwant]) in
+ * place of want.  Same three routes, same out_route values, same promise: every row holds exactly min(k, c_q - e_q)
+ * entries and only candidates, where c_q is what phnsw_labels_count_set_device writes (distinct labels, listed vectors)
+ * and e_q is 1 iff exclude[q] is listed under a label of S_q.  The rule is the one above (filter_route.h), the walk is
+ * the PHNSW_FILTER_STRICT walk of phnsw_search_batch_labelset over the graph list, and a scanned row is
+ * phnsw_search_exact_labelset's row bit for bit, routed and short queries in ONE scan launch (the scan's subset form:
+ * which query owns a pair is still decided over the whole batch).  Hence every row equals the row of
+ * phnsw_search_filtered_auto with the per-query bitmaps {v : v listed and labels[v] in S_q} and the same scan_below.
+ * scan_below 0 = the library default for sets (filter_route.h, PH_AUTO_SCAN_BELOW_LABELSET): 20 000 candidates of the
+ * UNION, from the crossover of phnsw_search_exact_labelset and the walk by set at sets of 4 labels (at a union of 20 000
+ * rows the scan took 17.6 ms against the walk's 22.0, at 40 000 rows 34.2 against 20.3; the lines cross near 25 000) --
+ * measured on 1M x 768 f32 rows, ef 256 / probe_depth 8, k = 10, batches of 10 000 queries; other set sizes, store kinds,
+ * dimensions and parameters are unmeasured, pass your own.  UINT64_MAX = always scan.
+ * Checks: those of phnsw_search_labeled_auto (sp, then 1 <= k <= number_of_candidates, then the store, then the handle),
+ * then the pointer and size checks of phnsw_search_batch_labelset; the host form refuses the same offsets and Stored
+ * ids, naming the query.  The default filter is not consulted.
+ * The device form reports status 8 exactly where phnsw_search_exact_labelset_device reports it for the same arrays,
+ * whichever route the count would have chosen -- a range fault, or an overlap with a LOWER query: such a query is routed
+ * to the scan, its row is empty and its route reads PHNSW_ROUTE_SCAN.  A Stored query id at or past n: status 4, scanned,
+ * an empty row (8 wins where both hold).  It synchronises `stream` at most twice, like its siblings.  The routed call
+ * itself has not been timed against the two calls it chooses between. */
+int phnsw_search_labelset_auto(const phnsw_index *ix, const phnsw_labels *lb, const float *queries, const uint64_t *qids,
+                               uint64_t nq, const phnsw_search_params *sp, const uint64_t *exclude,
+                               const uint32_t *want_first, const uint32_t *want_values, uint64_t k, uint64_t scan_below,
+                               uint64_t *out_ids, float *out_d, uint64_t *out_len, uint32_t *out_route);
+int phnsw_search_labelset_auto_device(const phnsw_index *ix, const phnsw_labels *lb, const float *queries_dev, uint32_t ldq,
+                                      const uint32_t *qids_dev, uint64_t nq, const phnsw_search_params *sp,
+                                      const uint32_t *exclude_dev, const uint32_t *want_first_dev,
+                                      const uint32_t *want_values_dev, uint64_t nwant, uint64_t k, uint64_t scan_below,
+                                      uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                      uint32_t *out_route_dev, uint32_t *status_dev, void *stream);
 /* ---- the COLLECTING search: the graph walk that remembers the best ALLOWED rows it evaluates.  The filtered walks above
  * are post-filters: they keep the best number_of_candidates rows, allowed or not, and filter that queue when the layer
  * ends, so a filter of density p leaves about p * number_of_candidates results although the walk evaluated several

@@ -476,8 +476,8 @@ class Hnsw {
                                           void *stream) const;
   // search_many_exact_labeled for a SET of labels per query (phnsw_search_exact_labelset): query i may return the vectors
   // `labels` lists under any label of want[i]; an empty set, PHNSW_LABEL_NONE and labels nobody carries give nothing, a
-  // label twice counts once.  The same results, bit for bit, as the bitmaps {v : label of v in want[i]} give.  Exact scan
-  // only: there is no graph walk by set.  Throws on a bad k and on want.size() != queries before the library is called
+  // label twice counts once.  The same results, bit for bit, as the bitmaps {v : label of v in want[i]} give.  The exact
+  // scan; search_many_labelset walks the graph by set, search_many_labelset_auto routes.  Throws on a bad k and on want.size() != queries before the library is called
   inline std::vector<SearchResult> search_many_exact_labelset(const std::vector<const float *> &queries, uint64_t k,
                                                               const Labels &labels,
                                                               const std::vector<std::vector<uint32_t>> &want) const;
@@ -487,6 +487,36 @@ class Hnsw {
                                            uint64_t nq, const uint32_t *exclude_dev, const uint32_t *want_first_dev,
                                            const uint32_t *want_values_dev, uint64_t nwant, uint64_t k, uint32_t *out_ids_dev,
                                            float *out_d_dev, uint32_t *out_len_dev, uint32_t *status_dev, void *stream) const;
+  // search_many_labeled for a SET of labels per query (phnsw_search_batch_labelset): the graph walk of query i restricted to
+  // the vectors `labels` lists under any label of want[i] -- the results search_many_filtered gives with the equivalent
+  // bitmaps, bit for bit.  A post-filter; strict also removes an entry vector whose label is not wanted.  k = 0: the whole
+  // queue.  The membership test is linear in the length of a set.  Throws on want.size() != queries and k >
+  // number_of_candidates before the library is called
+  inline std::vector<SearchResult> search_many_labelset(const std::vector<const float *> &queries, const SearchParameters &sp,
+                                                        const Labels &labels, const std::vector<std::vector<uint32_t>> &want,
+                                                        bool strict = false, uint64_t k = 0) const;
+  // zero-copy form (phnsw_search_batch_labelset_device): the sets in CSR form; status 8 = a range of want_first_dev that is
+  // not sound (that query does not walk); enqueued on `stream`, never synchronises it
+  inline void search_batch_labelset_device(const Labels &labels, const float *queries_dev, uint32_t ldq, const uint32_t *qids_dev,
+                                           uint64_t nq, const SearchParameters &sp, uint32_t upto_layers,
+                                           const uint32_t *exclude_dev, const uint32_t *want_first_dev,
+                                           const uint32_t *want_values_dev, uint64_t nwant, uint32_t flags,
+                                           uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                           uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) const;
+  // search_many_labeled_auto for a SET of labels per query (phnsw_search_labelset_auto): per query the scan by set or the
+  // strict walk by set, the scan again for short rows; every result holds min(k, candidates) entries, listed vectors of the
+  // labels of want[i] only.  scan_below 0 = the library's threshold for sets (20 000 rows of the union, phnsw.h),
+  // UINT64_MAX = always scan.  Throws unless 1 <= k <= number_of_candidates and want.size() == queries
+  inline std::vector<SearchResult> search_many_labelset_auto(const std::vector<const float *> &queries, const SearchParameters &sp,
+                                                             uint64_t k, const Labels &labels,
+                                                             const std::vector<std::vector<uint32_t>> &want,
+                                                             uint64_t scan_below = 0, std::vector<uint32_t> *routes = nullptr) const;
+  // device form (phnsw_search_labelset_auto_device): u32 ids [nq][k]; synchronises `stream` up to twice (phnsw.h)
+  inline void search_labelset_auto_device(const Labels &labels, const float *queries_dev, uint32_t ldq, const uint32_t *qids_dev,
+                                          uint64_t nq, const SearchParameters &sp, const uint32_t *exclude_dev,
+                                          const uint32_t *want_first_dev, const uint32_t *want_values_dev, uint64_t nwant,
+                                          uint64_t k, uint64_t scan_below, uint32_t *out_ids_dev, float *out_d_dev,
+                                          uint32_t *out_len_dev, uint32_t *out_route_dev, uint32_t *status_dev, void *stream) const;
   // search_many_filtered by row label (phnsw_search_batch_labeled): the graph walk of query i restricted to the vectors
   // `labels` lists under want[i], read from the handle's label column instead of a bitmap per query -- the results
   // search_many_filtered gives with the equivalent bitmaps, bit for bit.  A post-filter: about number_of_candidates *
@@ -732,20 +762,28 @@ inline void Hnsw::search_exact_labeled_device(const Labels &labels, const float 
                                           out_ids_dev, out_d_dev, out_len_dev, status_dev, stream));
 }
 
+// the sets of a batch in CSR form, as the calls by set take them; `call` opens the message of what it throws
+inline void pack_label_sets(const std::vector<std::vector<uint32_t>> &want, uint64_t nq, const char *call,
+                            std::vector<uint32_t> *first, std::vector<uint32_t> *values) {
+  if (want.size() != nq) throw Error(PHNSW_E_INVALID, std::string(call) + ": one set of wanted labels per query");
+  first->assign(nq + 1, 0);
+  values->clear();
+  for (uint64_t i = 0; i < nq; i++) {
+    values->insert(values->end(), want[i].begin(), want[i].end());
+    if (values->size() > 0x7FFFFFFEull) throw Error(PHNSW_E_INVALID, std::string(call) + ": too many wanted labels");
+    (*first)[i + 1] = (uint32_t)values->size();
+  }
+}
+
 inline std::vector<SearchResult> Hnsw::search_many_exact_labelset(const std::vector<const float *> &queries, uint64_t k,
                                                                   const Labels &labels,
                                                                   const std::vector<std::vector<uint32_t>> &want) const {
   const uint64_t nq = queries.size(), dim = c_->dim();
   if (k == 0 || k > 1024) throw Error(PHNSW_E_INVALID, "search_many_exact_labelset: k must be 1..1024");
-  if (want.size() != nq) throw Error(PHNSW_E_INVALID, "search_many_exact_labelset: one set of wanted labels per query");
+  std::vector<uint32_t> first, values;
+  pack_label_sets(want, nq, "search_many_exact_labelset", &first, &values);
   std::vector<float> q(nq * dim);
   for (uint64_t i = 0; i < nq; i++) std::copy(queries[i], queries[i] + dim, q.begin() + i * dim);
-  std::vector<uint32_t> first(nq + 1, 0), values;
-  for (uint64_t i = 0; i < nq; i++) {
-    values.insert(values.end(), want[i].begin(), want[i].end());
-    if (values.size() > 0x7FFFFFFEull) throw Error(PHNSW_E_INVALID, "search_many_exact_labelset: too many wanted labels");
-    first[i + 1] = (uint32_t)values.size();
-  }
   std::vector<uint64_t> ids(nq * k), len(nq);
   std::vector<float> d(nq * k);
   check(phnsw_search_exact_labelset(ix_, labels.handle(), q.data(), nullptr, nq, nullptr, first.data(), values.data(), k,
@@ -762,6 +800,67 @@ inline void Hnsw::search_exact_labelset_device(const Labels &labels, const float
                                                uint32_t *status_dev, void *stream) const {
   check(phnsw_search_exact_labelset_device(ix_, labels.handle(), queries_dev, ldq, qids_dev, nq, exclude_dev, want_first_dev,
                                            want_values_dev, nwant, k, out_ids_dev, out_d_dev, out_len_dev, status_dev, stream));
+}
+
+inline std::vector<SearchResult> Hnsw::search_many_labelset(const std::vector<const float *> &queries, const SearchParameters &sp,
+                                                            const Labels &labels, const std::vector<std::vector<uint32_t>> &want,
+                                                            bool strict, uint64_t k) const {
+  const uint64_t nq = queries.size(), dim = c_->dim(), ef = sp.number_of_candidates;
+  if (k > ef) throw Error(PHNSW_E_INVALID, "search_many_labelset: k must be 0 or 1..number_of_candidates");
+  std::vector<uint32_t> first, values;
+  pack_label_sets(want, nq, "search_many_labelset", &first, &values);
+  const uint64_t w = k ? k : ef;
+  std::vector<float> q(nq * dim);
+  for (uint64_t i = 0; i < nq; i++) std::copy(queries[i], queries[i] + dim, q.begin() + i * dim);
+  std::vector<uint64_t> ids(nq * w), len(nq);
+  std::vector<float> d(nq * w);
+  check(phnsw_search_batch_labelset(ix_, labels.handle(), q.data(), nullptr, nq, &sp, 0, nullptr, first.data(), values.data(),
+                                    strict ? PHNSW_FILTER_STRICT : 0u, k, ids.data(), d.data(), len.data(), nullptr));
+  std::vector<SearchResult> out(nq);
+  for (uint64_t i = 0; i < nq; i++)
+    for (uint64_t j = 0; j < len[i]; j++) out[i].push_back({ids[i * w + j], d[i * w + j]});
+  return out;
+}
+inline void Hnsw::search_batch_labelset_device(const Labels &labels, const float *queries_dev, uint32_t ldq,
+                                               const uint32_t *qids_dev, uint64_t nq, const SearchParameters &sp,
+                                               uint32_t upto_layers, const uint32_t *exclude_dev, const uint32_t *want_first_dev,
+                                               const uint32_t *want_values_dev, uint64_t nwant, uint32_t flags,
+                                               uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                               uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) const {
+  check(phnsw_search_batch_labelset_device(ix_, labels.handle(), queries_dev, ldq, qids_dev, nq, &sp, upto_layers, exclude_dev,
+                                           want_first_dev, want_values_dev, nwant, flags, out_ids_dev, out_d_dev, out_len_dev,
+                                           out_stats_dev, status_dev, stream));
+}
+inline std::vector<SearchResult> Hnsw::search_many_labelset_auto(const std::vector<const float *> &queries,
+                                                                 const SearchParameters &sp, uint64_t k, const Labels &labels,
+                                                                 const std::vector<std::vector<uint32_t>> &want,
+                                                                 uint64_t scan_below, std::vector<uint32_t> *routes) const {
+  const uint64_t nq = queries.size(), dim = c_->dim();
+  if (k == 0 || k > sp.number_of_candidates)
+    throw Error(PHNSW_E_INVALID, "search_many_labelset_auto: k must be 1..number_of_candidates");
+  std::vector<uint32_t> first, values;
+  pack_label_sets(want, nq, "search_many_labelset_auto", &first, &values);
+  std::vector<float> q(nq * dim);
+  for (uint64_t i = 0; i < nq; i++) std::copy(queries[i], queries[i] + dim, q.begin() + i * dim);
+  std::vector<uint64_t> ids(nq * k), len(nq);
+  std::vector<float> d(nq * k);
+  if (routes) routes->assign(nq, 0u);
+  check(phnsw_search_labelset_auto(ix_, labels.handle(), q.data(), nullptr, nq, &sp, nullptr, first.data(), values.data(), k,
+                                   scan_below, ids.data(), d.data(), len.data(), routes ? routes->data() : nullptr));
+  std::vector<SearchResult> out(nq);
+  for (uint64_t i = 0; i < nq; i++)
+    for (uint64_t j = 0; j < len[i]; j++) out[i].push_back({ids[i * k + j], d[i * k + j]});
+  return out;
+}
+inline void Hnsw::search_labelset_auto_device(const Labels &labels, const float *queries_dev, uint32_t ldq,
+                                              const uint32_t *qids_dev, uint64_t nq, const SearchParameters &sp,
+                                              const uint32_t *exclude_dev, const uint32_t *want_first_dev,
+                                              const uint32_t *want_values_dev, uint64_t nwant, uint64_t k, uint64_t scan_below,
+                                              uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                              uint32_t *out_route_dev, uint32_t *status_dev, void *stream) const {
+  check(phnsw_search_labelset_auto_device(ix_, labels.handle(), queries_dev, ldq, qids_dev, nq, &sp, exclude_dev, want_first_dev,
+                                          want_values_dev, nwant, k, scan_below, out_ids_dev, out_d_dev, out_len_dev,
+                                          out_route_dev, status_dev, stream));
 }
 
 inline std::vector<SearchResult> Hnsw::search_many_labeled(const std::vector<const float *> &queries, const SearchParameters &sp,

@@ -158,6 +158,12 @@ SYMBOLS = {
     "phnsw_search_labeled_auto": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
     "phnsw_search_labeled_auto_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp,
                                                 _vp, _vp, _vp]),
+    "phnsw_search_batch_labelset": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _u32, _u64, _vp, _vp, _vp, _vp]),
+    "phnsw_search_batch_labelset_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _u64, _u32, _vp,
+                                                  _vp, _vp, _vp, _vp, _vp]),
+    "phnsw_search_labelset_auto": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
+    "phnsw_search_labelset_auto_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _u64, _u64, _vp,
+                                                 _vp, _vp, _vp, _vp, _vp]),
     "phnsw_search_collect": (_i32, [_vp, _vp, _vp, _u64, C.POINTER(SearchParams), _u32, _vp, _vp, _u32, _u32, _u64, _vp, _vp,
                                     _vp, _vp]),
     "phnsw_search_collect_device": (_i32, [_vp, _vp, _u32, _vp, _u64, C.POINTER(SearchParams), _u32, _vp, _vp, _u32, _u32,

@@ -642,6 +642,10 @@ static void fill_args(const phnsw_index *ix, const PhSearchCall &c, PhSearchArgs
     a.label_of = c.filter.label_of;
     a.label_want = c.filter.want;
     a.filter_flags = c.filter.flags;
+    if (c.filter.set_first) {  // ... or its set form: the table of wanted labels instead of one label per query
+      a.label_want = nullptr;
+      a.set_first = c.filter.set_first, a.set_values = c.filter.set_values, a.set_nwant = c.filter.set_nwant;
+    }
   }
   a.nq = (uint32_t)c.nq;
   a.out_ids = c.out_ids;
@@ -882,6 +886,7 @@ int ph_search_device(const phnsw_index *ix, const PhSearchCall &c) {
       if (b.exclude) b.exclude += c0;
       if (b.filter) b.filter += c0 * b.filter_stride;  // per-query bitmaps follow the chunk; a shared one (stride 0) stays
       if (b.label_want) b.label_want += c0;  // ... and so do the wanted labels; the column is indexed by VectorId
+      if (b.set_first) b.set_first += c0;    // ... and the offsets of the sets, which stay absolute: set_values does not move
       if (b.out_ids) b.out_ids += c0 * ostride, b.out_d += c0 * ostride;
       if (b.collect_k) b.collect_ids += c0 * b.collect_k, b.collect_d += c0 * b.collect_k;
       b.out_len += c0;

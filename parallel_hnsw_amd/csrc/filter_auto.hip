@@ -20,6 +20,12 @@
 //   3. the walk is the search kernels' label mode over the handle's column
 //   4. "exclude[q] is a candidate" is label_of[exclude[q]] == want[q]
 //   5. the scan is filter_labeled.hip's, over the scan list (PhLabeledCall::list)
+// ... or BY A SET OF LABELS (phnsw_search_labelset_auto[_device]: the handle, want_first and want_values):
+//   1. the counts are ph_labels_count_set's: the lists of the distinct labels of the range, and 0 for a query the scan by
+//      set refuses (a range that is not sound, a pair a lower query holds) -- so it is routed to the scan, which reports it
+//   3. the walk is the search kernels' set mode
+//   4. "exclude[q] is a candidate" is ph_auto_set_candidate, the membership predicate of the walk
+//   5. the scan is the subset form of the scan by set (PhLabelsetCall with a list): its claim runs over the whole batch
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -42,6 +48,8 @@ struct PhAutoArgs {
   uint32_t filter_stride;          // 0 = one bitmap for all
   uint32_t per_query;              // counts holds nq entries, else one
   const uint32_t *label_of, *want;  // a call by label: the handle's column [n] and want [nq]; else nullptr
+  // a call by set: the column, want == nullptr and the table (graph-list queries have sound ranges: their counts are not 0)
+  const uint32_t *set_first, *set_values;
   // the index's bottom layer, as the candidate test takes it
   uint32_t n_nodes;
   const uint32_t *nodes, *vec2node;
@@ -128,8 +136,13 @@ __global__ __launch_bounds__(64) void ph_auto_finish_kernel(PhAutoArgs a) {
     }
     if (lane == 0) {
       const uint32_t *const bitmap = a.filter ? a.filter + (uint64_t)q * a.filter_stride : nullptr;
-      const bool ex_cand = a.label_of ? ph_auto_label_candidate(a.label_of, a.n, a.want[q], ex, PHNSW_LABEL_NONE)
-                                      : ph_exact_is_candidate(bitmap, ex, nlim, a.vec2node);
+      bool ex_cand;
+      if (a.set_first)
+        ex_cand = ph_auto_set_candidate(a.label_of, a.n, a.set_first[q], a.set_first[q + 1u], a.set_values, ex, PHNSW_LABEL_NONE);
+      else if (a.label_of)
+        ex_cand = ph_auto_label_candidate(a.label_of, a.n, a.want[q], ex, PHNSW_LABEL_NONE);
+      else
+        ex_cand = ph_exact_is_candidate(bitmap, ex, nlim, a.vec2node);
       const uint32_t e = (ex != PH_EMPTY32 && ex_cand) ? 1u : 0u;
       const uint32_t full = ph_auto_full_len(a.counts[a.per_query ? q : 0u], e, a.k);
       if (st == ST_OVERFLOW || (st == ST_OK && kept < full)) {
@@ -159,29 +172,39 @@ int auto_run(const phnsw_index *ix, const PhAutoCall &c, PhAutoSet &set) {
   const phnsw_store *s = ix->store;
   const uint64_t nq = c.nq;
   const uint32_t ef = (uint32_t)c.sp->number_of_candidates;
-  const bool by_label = c.labels != nullptr;
+  const bool by_label = c.labels != nullptr, by_set = by_label && c.want_first != nullptr;
   const bool per_query = by_label || (c.filter.words && c.filter.stride != 0u);
   PH_TRY(set.ready());
   if (!set.h_head) PH_HIP(hipHostMalloc((void **)&set.h_head, PH_AUTO_HEAD_WORDS * 4u, hipHostMallocDefault));
-  PH_TRY(set.block_ensure(&set.block, &set.bytes, (size_t)ph_auto_scratch_words(nq, per_query, ef) * 4u, c.stream));
+  // (a call by set: the claim's owner words [nwant] behind everything else)
+  const uint64_t words = ph_auto_scratch_words(nq, per_query, ef);
+  PH_TRY(set.block_ensure(&set.block, &set.bytes, (size_t)(words + (by_set ? c.nwant : 0u)) * 4u, c.stream));
   const uint64_t nb = ph_auto_bitmaps(nq, per_query);
   uint32_t *const head = (uint32_t *)set.block, *const counts = head + PH_AUTO_HEAD_WORDS, *const glist = counts + nb;
   uint32_t *const slist = glist + ph_auto_list_words(nq), *const route_own = slist + ph_auto_list_words(nq);
   uint32_t *const walk_len = route_own + nq, *const walk_ids = walk_len + nq;
   float *const walk_d = (float *)(walk_ids + nq * ef);
 
-  if (by_label)
+  if (by_set)
+    PH_TRY(ph_labels_count_set(c.labels, c.want_first, c.want_values, nq, c.nwant, counts, head + words, c.stream));
+  else if (by_label)
     PH_TRY(ph_labels_count(c.labels, c.want, nq, counts, c.stream));
   else
     PH_TRY(ph_filter_count(ix, c.filter, nb, counts, c.stream));
   PhAutoArgs a = {};
   a.nq = (uint32_t)nq, a.n = (uint32_t)s->n, a.k = c.k, a.ef = ef;
-  a.scan_below = by_label ? ph_auto_scan_below_labeled(c.scan_below) : ph_auto_scan_below(c.scan_below, per_query);
+  a.scan_below = by_set ? ph_auto_scan_below_labelset(c.scan_below)
+                        : (by_label ? ph_auto_scan_below_labeled(c.scan_below) : ph_auto_scan_below(c.scan_below, per_query));
   a.qids = c.qids, a.exclude = c.exclude;
   PhFilter filter = c.filter;  // what the walk gets
   if (by_label) {
     filter = PhFilter{};
     filter.label_of = a.label_of = ph_labels_column(c.labels), filter.want = a.want = c.want;
+    if (by_set) {
+      filter.want = a.want = nullptr;
+      filter.set_first = a.set_first = c.want_first, filter.set_values = a.set_values = c.want_values;
+      filter.set_nwant = (uint32_t)c.nwant;
+    }
   }
   a.filter = filter.words, a.filter_stride = filter.words ? filter.stride : 0u, a.per_query = per_query ? 1u : 0u;
   ph_exact_bottom_layer(ix, &a.n_nodes, &a.nodes, &a.vec2node);
@@ -210,7 +233,17 @@ int auto_run(const phnsw_index *ix, const PhAutoCall &c, PhAutoSet &set) {
     PH_HIP(hipStreamSynchronize(c.stream));
     slen = std::min<uint64_t>(set.h_head[1], nq);
   }
-  if (slen && by_label) {
+  if (slen && by_set) {
+    PhLabelsetCall sx = {};
+    PhLabeledCall &x = sx.c;
+    x.queries = c.queries, x.ldq = c.ldq, x.qids = c.qids, x.exclude = c.exclude;
+    x.nq = slen, x.list = slist;
+    x.k = c.k;
+    x.out_ids = c.out_ids, x.out_d = c.out_d, x.out_len = c.out_len, x.status = c.status;
+    x.stream = c.stream;
+    sx.want_first = c.want_first, sx.want_values = c.want_values, sx.nwant = c.nwant, sx.batch_nq = nq;
+    PH_TRY(ph_labelset_device(ix, c.labels, sx));
+  } else if (slen && by_label) {
     PhLabeledCall x = {};
     x.queries = c.queries, x.ldq = c.ldq, x.qids = c.qids, x.exclude = c.exclude, x.want = c.want;
     x.nq = slen, x.list = slist;
@@ -288,29 +321,53 @@ extern "C" int phnsw_search_filtered_auto_device(const phnsw_index *ix, const fl
   return ph_auto_device(ix, c);
 } catch (...) { return ph_caught(); }
 
-// the host form of both descriptions; lb != nullptr: by label (want: host words [nq]; filter unused), else by bitmap
+// the host form of the three descriptions; lb != nullptr: by label (want: host words [nq]; filter unused) or, with
+// want_first, by set (want_first [nq + 1], want_values: host words; want unused), else by bitmap
 static int auto_host(const char *call, const phnsw_index *ix, const phnsw_labels *lb, const float *queries, const uint64_t *qids,
                      uint64_t nq, const phnsw_search_params *sp, const uint64_t *exclude, const uint32_t *filter,
-                     uint32_t filter_stride_words, const uint32_t *want, uint64_t k, uint64_t scan_below, uint64_t *out_ids,
-                     float *out_d, uint64_t *out_len, uint32_t *out_route) {
+                     uint32_t filter_stride_words, const uint32_t *want, const uint32_t *want_first, const uint32_t *want_values,
+                     uint64_t k, uint64_t scan_below, uint64_t *out_ids, float *out_d, uint64_t *out_len, uint32_t *out_route) {
+  const bool by_set = lb && want_first;
   if (!ph_auto_queries_valid(queries != nullptr, qids != nullptr) || !out_ids || !out_d || !out_len || !ph_auto_nq_valid(nq) ||
-      (lb && (!want || nq > 0x7FFFFFFEull))) {
+      (lb && ((!want && !want_first) || nq > 0x7FFFFFFEull))) {
     ph_set_error("%s: invalid argument (queries or qids, exactly one; outputs%s)", call, lb ? "; want; nq < 2^31 - 1" : "");
+    return PHNSW_E_INVALID;
+  }
+  const uint64_t nwant = by_set ? want_first[nq] : 0u;
+  if (by_set && ((!want_values && nwant) || nwant > 0x7FFFFFFEull)) {
+    ph_set_error("%s: invalid argument (want_values unless want_first[nq] is 0; want_first[nq] < 2^31 - 1)", call);
     return PHNSW_E_INVALID;
   }
   PhFilter hf = {};
   if (!lb) PH_TRY(ph_filter_check(ix, filter, filter_stride_words, 0u, call, &hf));
   const phnsw_store *s = ix->store;
-  PH_TRY(ph_stored_ids_check(qids, nq, s->n, "search"));
+  if (by_set) {  // as the walk and the scan by set refuse them: naming the call and the query
+    PH_TRY(ph_stored_ids_check(qids, nq, s->n, call, true));
+    for (uint64_t q = 0; q < nq; q++)
+      if ((q == 0 && want_first[0] != 0u) || want_first[q] > want_first[q + 1u]) {
+        ph_set_error("%s: query %llu: want_first must start at 0 and never run backwards (want_first[%llu] = %u, "
+                     "want_first[%llu] = %u)", call, (unsigned long long)q, (unsigned long long)q, want_first[q],
+                     (unsigned long long)q + 1u, want_first[q + 1u]);
+        return PHNSW_E_INVALID;
+      }
+  } else {
+    PH_TRY(ph_stored_ids_check(qids, nq, s->n, "search"));
+  }
   PH_HIP(hipSetDevice(s->device));
   phnsw_index *mix = const_cast<phnsw_index *>(ix);
   PhAutoSet *set = ph_set_acquire<PhAutoSet>(mix->autos);
   PhHostCall h(mix->autos, set);
-  PH_TRY(h.stage_in(s, queries, qids, exclude, nq, (size_t)nq * 2u, 1, (uint32_t)k, (uint32_t)k));  // extras: route | want
+  // extras: route | want, or for a call by set want_first [nq + 1] | want_values [nwant]
+  PH_TRY(h.stage_in(s, queries, qids, exclude, nq, (size_t)nq * 2u + (by_set ? 1u + (size_t)nwant : 0u), 1, (uint32_t)k, (uint32_t)k));
   PhAutoCall c = {};
   h.fill(c);
   c.filter = hf;
-  if (lb) {  // the description of a call by label: 4 bytes per query
+  if (by_set) {  // the description of a call by set: 4 * (nq + 1) + 4 * nwant bytes
+    uint32_t *const first_dev = h.extra() + nq, *const values_dev = first_dev + nq + 1u;
+    PH_HIP(hipMemcpyAsync(first_dev, want_first, (size_t)(nq + 1u) * 4u, hipMemcpyHostToDevice, h.st));
+    if (nwant) PH_HIP(hipMemcpyAsync(values_dev, want_values, (size_t)nwant * 4u, hipMemcpyHostToDevice, h.st));
+    c.labels = lb, c.want_first = first_dev, c.want_values = values_dev, c.nwant = nwant;
+  } else if (lb) {  // the description of a call by label: 4 bytes per query
     uint32_t *const want_dev = h.extra() + nq;
     PH_HIP(hipMemcpyAsync(want_dev, want, (size_t)nq * 4u, hipMemcpyHostToDevice, h.st));
     c.labels = lb, c.want = want_dev;
@@ -344,8 +401,8 @@ extern "C" int phnsw_search_filtered_auto(const phnsw_index *ix, const float *qu
   const char *const call = "phnsw_search_filtered_auto";
   PH_TRY(auto_check(ix, sp, k, call));
   if (nq == 0) return 0;
-  return auto_host(call, ix, nullptr, queries, qids, nq, sp, exclude, filter, filter_stride_words, nullptr, k, scan_below,
-                   out_ids, out_d, out_len, out_route);
+  return auto_host(call, ix, nullptr, queries, qids, nq, sp, exclude, filter, filter_stride_words, nullptr, nullptr, nullptr, k,
+                   scan_below, out_ids, out_d, out_len, out_route);
 } catch (...) { return ph_caught(); }
 
 // ---- by label
@@ -358,8 +415,8 @@ extern "C" int phnsw_search_labeled_auto(const phnsw_index *ix, const phnsw_labe
   PH_TRY(auto_check(ix, sp, k, call));
   PH_TRY(ph_labeled_check(ix, lb, k, call));
   if (nq == 0) return 0;
-  return auto_host(call, ix, lb, queries, qids, nq, sp, exclude, nullptr, 0u, want, k, scan_below, out_ids, out_d, out_len,
-                   out_route);
+  return auto_host(call, ix, lb, queries, qids, nq, sp, exclude, nullptr, 0u, want, nullptr, nullptr, k, scan_below, out_ids,
+                   out_d, out_len, out_route);
 } catch (...) { return ph_caught(); }
 
 extern "C" int phnsw_search_labeled_auto_device(const phnsw_index *ix, const phnsw_labels *lb, const float *queries_dev,
@@ -380,6 +437,55 @@ extern "C" int phnsw_search_labeled_auto_device(const phnsw_index *ix, const phn
   }
   PhAutoCall c = {};
   c.labels = lb, c.want = want_dev;
+  c.queries = queries_dev, c.ldq = ldq, c.qids = qids_dev, c.exclude = exclude_dev, c.nq = nq, c.sp = sp;
+  c.k = (uint32_t)k, c.scan_below = scan_below;
+  c.out_ids = out_ids_dev, c.out_d = out_d_dev, c.out_len = out_len_dev, c.out_route = out_route_dev, c.status = status_dev;
+  c.stream = (hipStream_t)stream;
+  PH_HIP(hipSetDevice(ix->store->device));
+  return ph_auto_device(ix, c);
+} catch (...) { return ph_caught(); }
+
+// ---- by a set of labels
+
+extern "C" int phnsw_search_labelset_auto(const phnsw_index *ix, const phnsw_labels *lb, const float *queries, const uint64_t *qids,
+                                          uint64_t nq, const phnsw_search_params *sp, const uint64_t *exclude,
+                                          const uint32_t *want_first, const uint32_t *want_values, uint64_t k, uint64_t scan_below,
+                                          uint64_t *out_ids, float *out_d, uint64_t *out_len, uint32_t *out_route) try {
+  const char *const call = "phnsw_search_labelset_auto";
+  PH_TRY(auto_check(ix, sp, k, call));
+  PH_TRY(ph_labeled_check(ix, lb, k, call));
+  if (nq == 0) return 0;
+  if (!want_first) {
+    ph_set_error("%s: invalid argument (want_first)", call);
+    return PHNSW_E_INVALID;
+  }
+  return auto_host(call, ix, lb, queries, qids, nq, sp, exclude, nullptr, 0u, nullptr, want_first, want_values, k, scan_below,
+                   out_ids, out_d, out_len, out_route);
+} catch (...) { return ph_caught(); }
+
+extern "C" int phnsw_search_labelset_auto_device(const phnsw_index *ix, const phnsw_labels *lb, const float *queries_dev,
+                                                 uint32_t ldq, const uint32_t *qids_dev, uint64_t nq,
+                                                 const phnsw_search_params *sp, const uint32_t *exclude_dev,
+                                                 const uint32_t *want_first_dev, const uint32_t *want_values_dev, uint64_t nwant,
+                                                 uint64_t k, uint64_t scan_below, uint32_t *out_ids_dev, float *out_d_dev,
+                                                 uint32_t *out_len_dev, uint32_t *out_route_dev, uint32_t *status_dev,
+                                                 void *stream) try {
+  const char *const call = "phnsw_search_labelset_auto_device";
+  PH_TRY(auto_check(ix, sp, k, call));
+  PH_TRY(ph_labeled_check(ix, lb, k, call));
+  if (nq == 0) return 0;
+  if (!ph_device_queries_ok(ix, queries_dev, qids_dev, ldq) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev ||
+      !want_first_dev || (!want_values_dev && nwant)) {
+    ph_set_error("%s: invalid argument (queries or qids, exactly one; outputs; want_first; want_values unless nwant is 0; "
+                 "queries need ldq >= store ld, multiple of 4, 16-byte base)", call);
+    return PHNSW_E_INVALID;
+  }
+  if (nq > 0x7FFFFFFEull || nwant > 0x7FFFFFFEull) {
+    ph_set_error("%s: nq and nwant must be below 2^31 - 1", call);
+    return PHNSW_E_INVALID;
+  }
+  PhAutoCall c = {};
+  c.labels = lb, c.want_first = want_first_dev, c.want_values = want_values_dev, c.nwant = nwant;
   c.queries = queries_dev, c.ldq = ldq, c.qids = qids_dev, c.exclude = exclude_dev, c.nq = nq, c.sp = sp;
   c.k = (uint32_t)k, c.scan_below = scan_below;
   c.out_ids = out_ids_dev, c.out_d = out_d_dev, c.out_len = out_len_dev, c.out_route = out_route_dev, c.status = status_dev;

@@ -32,11 +32,14 @@
 // ph_labelset_lookup_kernel, the same sort, ph_labelset_positions_kernel (the query of a position, the inverse
 // permutation, duplicate flags), the tile table as above, the PAIRS instances of the scan and tile kernels -- every
 // position writes its per-slice lists to scratch, none a row --, ph_labelset_merge_kernel: a wave per query merges the
-// lists of its positions through the same running top-k.  No graph walk by set.
+// lists of its positions through the same running top-k.  Its subset form (PhLabelsetCall with c.list): the claim still
+// runs over the whole batch -- which query owns a pair is a property of the batch --, ph_labelset_select_kernel marks the
+// listed queries, the pairs of every other query get no slot and scan nothing, and the merge writes the listed rows alone.
 //
 // The graph walk by label (phnsw_search_batch_labeled[_device], at the end of this file) is the search kernels' own
-// label mode (search_labeled.hip) over label_of; the routed call (phnsw_search_labeled_auto) is filter_auto.hip's and
-// takes its scan from here through the subset form of a call (PhLabeledCall::list).
+// label mode (search_labeled.hip) over label_of, the walk by set (phnsw_search_batch_labelset[_device]) their set mode
+// (search_labelset.hip); the routed calls (phnsw_search_labeled_auto, phnsw_search_labelset_auto) are filter_auto.hip's
+// and take their scans from here through the subset forms (PhLabeledCall::list).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -47,6 +50,7 @@
 #include "exact_slices.h"
 #include "exact_topk.h"
 #include "filter_candidate.h"
+#include "filter_route.h"
 #include "host_call.h"
 #include "label_plan.h"
 #include "labelset_plan.h"
@@ -226,6 +230,9 @@ struct PhLabelsetArgs {
   uint32_t *spair;  // [nwant] by position: its pair
   uint32_t *inv;    // [nwant] by pair: its position
   uint32_t *dup;    // [nwant] by position: 1 = the (slot, query) of the position before it
+  // the subset form (a.list != nullptr): the rows of queries a.list[0 .. nlist) are made; sel [nq] = 1 for those
+  const uint32_t *sel;
+  uint32_t nlist;  // rows the merge writes: the list's length, nq without a list
 };
 
 // owner[] is preset to NONE.  One thread per query claims the pairs of a sound range; the lowest query keeps a pair.
@@ -238,11 +245,18 @@ __global__ __launch_bounds__(256) void ph_labelset_claim_kernel(PhLabelsetArgs s
   }
 }
 
-// per pair: its slot (none for an unclaimed pair and for a bad Stored query id) and itself, the sort's value
+// the subset form: sel [nq] is preset to 0; one thread per entry of the list marks its query
+__global__ __launch_bounds__(256) void ph_labelset_select_kernel(const uint32_t *list, uint32_t nlist, uint32_t nq, uint32_t *sel) {
+  for (uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x; p < nlist; p += (uint64_t)gridDim.x * 256u)
+    if (list[p] < nq) sel[list[p]] = 1u;
+}
+
+// per pair: its slot (none for an unclaimed pair, for a bad Stored query id and for a query the list leaves out) and
+// itself, the sort's value
 __global__ __launch_bounds__(256) void ph_labelset_lookup_kernel(PhLabelsetArgs s) {
   for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < s.nwant; i += (uint64_t)gridDim.x * 256u) {
     const uint32_t q = s.owner[i];  // NONE or < nq
-    const bool dead = q == PH_LABELSET_OWNER_NONE || (!s.a.queries && s.a.qids[q] >= s.a.n);
+    const bool dead = q == PH_LABELSET_OWNER_NONE || (!s.a.queries && s.a.qids[q] >= s.a.n) || (s.sel && !s.sel[q]);
     s.a.slot[i] = dead ? PH_LABEL_SLOT_NONE : ph_label_slot(s.a.values, s.a.nlabels, s.want_values[i], PHNSW_LABEL_NONE);
     s.a.iota[i] = (uint32_t)i;
   }
@@ -278,7 +292,9 @@ __global__ __launch_bounds__(64) void ph_labelset_merge_kernel(PhLabelsetArgs s)
   const uint32_t lane = threadIdx.x;
   const PhLabeledArgs &a = s.a;
   uint64_t *const keys = (uint64_t *)labeled_lds;
-  for (uint32_t q = blockIdx.x; q < s.nq; q += gridDim.x) {
+  for (uint32_t at = blockIdx.x; at < s.nlist; at += gridDim.x) {
+    const uint32_t q = a.list ? a.list[at] : at;
+    if (q >= s.nq) continue;  // (a list holds query indices of the batch)
     const uint32_t b = s.want_first[q], e = s.want_first[q + 1u];
     const bool ok = ph_labelset_query_ok(s, q, b, e, lane);
     __syncthreads();
@@ -316,6 +332,16 @@ __global__ __launch_bounds__(64) void ph_labelset_count_kernel(const uint32_t *v
       }
     for (int o = 32; o; o >>= 1) c += __shfl_xor(c, o);
     if (lane == 0) out_count[q] = c;
+  }
+}
+
+// the routed call by set: the count of a query that the scan would refuse (a range that is not sound, a pair a lower
+// query holds) becomes 0, so that it is routed to the scan, which reports it.  owner[] as the claim kernel left it.
+__global__ __launch_bounds__(64) void ph_labelset_refused_kernel(PhLabelsetArgs s, uint32_t *count) {
+  const uint32_t lane = threadIdx.x;
+  for (uint32_t q = blockIdx.x; q < s.nq; q += gridDim.x) {
+    const bool ok = ph_labelset_query_ok(s, q, s.want_first[q], s.want_first[q + 1u], lane);
+    if (!ok && lane == 0) count[q] = 0u;
   }
 }
 
@@ -712,21 +738,16 @@ int labeled_run(const phnsw_index *ix, const phnsw_labels *lb, const PhLabeledCa
   return 0;
 }
 
-// The request of one scan by label sets: c without `want` and `list`, the sets in CSR form (device words), nwant pairs.
-struct PhLabelsetCall {
-  PhLabeledCall c;
-  const uint32_t *want_first, *want_values;
-  uint64_t nwant;
-};
-
-// labeled_run over pairs (labelset_plan.h); c is checked, 0 < nq, nq and nwant <= PH_LABEL_NQ_MAX.  Enqueues and returns.
+// labeled_run over pairs (labelset_plan.h; the request: PhLabelsetCall, phnsw_internal.h); c is checked, 0 < batch_nq,
+// batch_nq and nwant <= PH_LABEL_NQ_MAX; with c.list, c.nq > 0 is its length.  Enqueues and returns.
 int labelset_run(const phnsw_index *ix, const phnsw_labels *lb, const PhLabelsetCall &sc, PhLabeledSet &set) {
   const phnsw_store *s = ix->store;
   const PhLabeledCall &c = sc.c;
-  const uint64_t nq = c.nq, np = sc.nwant;  // np positions
+  const uint64_t nq = sc.batch_nq, np = sc.nwant;  // np positions
   const PhLabelsetPre lay = ph_labelset_pre(np);
   PH_TRY(set.ready());
-  PH_TRY(set.block_ensure(&set.pre, &set.pre_bytes, (size_t)lay.words * 4u, c.stream));
+  // (the subset form's marks [nq] behind the layout's words)
+  PH_TRY(set.block_ensure(&set.pre, &set.pre_bytes, (size_t)(lay.words + (c.list ? nq : 0u)) * 4u, c.stream));
   uint32_t *const pre = (uint32_t *)set.pre;
   PhLabelsetArgs sa = {};
   PhLabeledArgs &a = sa.a;
@@ -734,6 +755,7 @@ int labelset_run(const phnsw_index *ix, const phnsw_labels *lb, const PhLabelset
   a.slices = 1u, a.T = 1u;
   sa.want_first = sc.want_first, sa.want_values = sc.want_values, sa.nq = (uint32_t)nq, sa.nwant = (uint32_t)np;
   sa.owner = pre + lay.owner, sa.spair = pre + lay.spair, sa.inv = pre + lay.inv, sa.dup = pre + lay.dup;
+  a.list = c.list, sa.nlist = (uint32_t)(c.list ? c.nq : nq);
 
   if (np) {
     PhLabeledLaunch ln = {nullptr, 0, pre + lay.pos.sslot, sa.spair, pre + lay.pos.tidx};
@@ -750,6 +772,13 @@ int labelset_run(const phnsw_index *ix, const phnsw_labels *lb, const PhLabelset
     PH_HIP(hipMemsetAsync(sa.owner, 0xFF, (size_t)np * 4u, c.stream));  // PH_LABELSET_OWNER_NONE
     hipLaunchKernelGGL(ph_labelset_claim_kernel, dim3(grid1(nq)), dim3(256), 0, c.stream, sa);
     PH_HIP(hipGetLastError());
+    if (c.list) {
+      uint32_t *const sel = pre + lay.words;
+      PH_HIP(hipMemsetAsync(sel, 0, (size_t)nq * 4u, c.stream));
+      hipLaunchKernelGGL(ph_labelset_select_kernel, dim3(grid1(sa.nlist)), dim3(256), 0, c.stream, c.list, sa.nlist, (uint32_t)nq, sel);
+      PH_HIP(hipGetLastError());
+      sa.sel = sel;
+    }
     hipLaunchKernelGGL(ph_labelset_lookup_kernel, dim3(grid1(np)), dim3(256), 0, c.stream, sa);
     PH_HIP(hipGetLastError());
     PH_TRY(labeled_sort(set, a, ln, c.stream));
@@ -758,7 +787,7 @@ int labelset_run(const phnsw_index *ix, const phnsw_labels *lb, const PhLabelset
     PH_TRY(labeled_scan(set, a, ln, c.stream));
   }
   // no pair at all: every sound range is empty, and the merge alone writes the rows
-  hipLaunchKernelGGL(ph_labelset_merge_kernel, dim3((uint32_t)std::min<uint64_t>(nq, 1u << 20)), dim3(64),
+  hipLaunchKernelGGL(ph_labelset_merge_kernel, dim3((uint32_t)std::min<uint64_t>(sa.nlist, 1u << 20)), dim3(64),
                      (size_t)ph_label_scan_lds(c.k), c.stream, sa);
   PH_HIP(hipGetLastError());
   return 0;
@@ -886,6 +915,32 @@ int ph_labeled_device(const phnsw_index *ix, const phnsw_labels *lb, const PhLab
   PhLabeledSet *set = set_acquire(mlb, c.stream, false);
   PhSetGuard guard{mlb->pool, set, c.stream};
   return labeled_run(ix, lb, c, *set);
+}
+
+int ph_labelset_device(const phnsw_index *ix, const phnsw_labels *lb, const PhLabelsetCall &sc) {
+  if (sc.c.nq == 0 || sc.batch_nq == 0) return 0;
+  phnsw_labels *mlb = const_cast<phnsw_labels *>(lb);
+  PhLabeledSet *set = set_acquire(mlb, sc.c.stream, false);
+  PhSetGuard guard{mlb->pool, set, sc.c.stream};
+  return labelset_run(ix, lb, sc, *set);
+}
+
+int ph_labels_count_set(const phnsw_labels *lb, const uint32_t *want_first_dev, const uint32_t *want_values_dev, uint64_t nq,
+                        uint64_t nwant, uint32_t *out_count_dev, uint32_t *owner_scratch, hipStream_t stream) {
+  hipLaunchKernelGGL(ph_labelset_count_kernel, dim3((uint32_t)std::min<uint64_t>(nq, 1u << 20)), dim3(64), 0, stream, lb->values,
+                     lb->first, (uint32_t)lb->nlabels, want_first_dev, want_values_dev, nq, (uint32_t)nwant, out_count_dev);
+  PH_HIP(hipGetLastError());
+  if (!owner_scratch || !nwant) return 0;  // without a pair no range overlaps another, and a bad range counts 0 already
+  PhLabelsetArgs sa = {};
+  sa.want_first = want_first_dev, sa.want_values = want_values_dev, sa.nq = (uint32_t)nq, sa.nwant = (uint32_t)nwant;
+  sa.owner = owner_scratch;
+  PH_HIP(hipMemsetAsync(sa.owner, 0xFF, (size_t)nwant * 4u, stream));  // PH_LABELSET_OWNER_NONE
+  hipLaunchKernelGGL(ph_labelset_claim_kernel, dim3(grid1(nq)), dim3(256), 0, stream, sa);
+  PH_HIP(hipGetLastError());
+  hipLaunchKernelGGL(ph_labelset_refused_kernel, dim3((uint32_t)std::min<uint64_t>(nq, 1u << 20)), dim3(64), 0, stream, sa,
+                     out_count_dev);
+  PH_HIP(hipGetLastError());
+  return 0;
 }
 
 // ------------------------------------------------------------------ C ABI
@@ -1017,11 +1072,7 @@ extern "C" int phnsw_labels_count_set_device(const phnsw_labels *lb, const uint3
     return PHNSW_E_INVALID;
   }
   PH_HIP(hipSetDevice(lb->device));
-  hipLaunchKernelGGL(ph_labelset_count_kernel, dim3((uint32_t)std::min<uint64_t>(nq, 1u << 20)), dim3(64), 0,
-                     (hipStream_t)stream, lb->values, lb->first, (uint32_t)lb->nlabels, want_first_dev, want_values_dev, nq,
-                     (uint32_t)nwant, out_count_dev);
-  PH_HIP(hipGetLastError());
-  return 0;
+  return ph_labels_count_set(lb, want_first_dev, want_values_dev, nq, nwant, out_count_dev, nullptr, (hipStream_t)stream);
 } catch (...) { return ph_caught(); }
 
 extern "C" int phnsw_search_exact_labelset_device(const phnsw_index *ix, const phnsw_labels *lb, const float *queries_dev,
@@ -1048,7 +1099,7 @@ extern "C" int phnsw_search_exact_labelset_device(const phnsw_index *ix, const p
   c.queries = queries_dev, c.ldq = ldq, c.qids = qids_dev, c.exclude = exclude_dev, c.nq = nq, c.k = (uint32_t)k;
   c.out_ids = out_ids_dev, c.out_d = out_d_dev, c.out_len = out_len_dev, c.status = status_dev;
   c.stream = (hipStream_t)stream;
-  sc.want_first = want_first_dev, sc.want_values = want_values_dev, sc.nwant = nwant;
+  sc.want_first = want_first_dev, sc.want_values = want_values_dev, sc.nwant = nwant, sc.batch_nq = nq;
   PH_HIP(hipSetDevice(ix->store->device));
   phnsw_labels *mlb = const_cast<phnsw_labels *>(lb);
   PhLabeledSet *set = set_acquire(mlb, c.stream, false);
@@ -1095,7 +1146,7 @@ extern "C" int phnsw_search_exact_labelset(const phnsw_index *ix, const phnsw_la
   uint32_t *const first_dev = h.extra(), *const values_dev = first_dev + nq + 1u;
   PH_HIP(hipMemcpyAsync(first_dev, want_first, (size_t)(nq + 1u) * 4u, hipMemcpyHostToDevice, h.st));
   if (nwant) PH_HIP(hipMemcpyAsync(values_dev, want_values, (size_t)nwant * 4u, hipMemcpyHostToDevice, h.st));
-  sc.want_first = first_dev, sc.want_values = values_dev, sc.nwant = nwant;
+  sc.want_first = first_dev, sc.want_values = values_dev, sc.nwant = nwant, sc.batch_nq = nq;
   sc.c.k = (uint32_t)k;
   PH_TRY(labelset_run(ix, lb, sc, *set));
   return h.finish(out_ids, out_d, out_len);
@@ -1113,6 +1164,42 @@ int walk_check(const phnsw_index *ix, const phnsw_labels *lb, const phnsw_search
     ph_set_error("%s: unknown flag bits 0x%x", call, flags);
     return PHNSW_E_INVALID;
   }
+  return 0;
+}
+
+// The run of both host walks (by label, by set) once everything is staged: the launch, the words back, and the queries
+// whose frontier spill overflowed (status 5) again from a device list with 8x the room, as ph_search_host re-runs them;
+// then the rows and the stats (the first two extra words of `small`).  redo_dev: nq words of the staging.
+int walk_host_run(const phnsw_index *ix, PhHostCall &h, PhSearchCall &c, uint32_t *redo_dev, uint32_t ef, uint64_t *out_ids,
+                  float *out_d, uint64_t *out_len, uint64_t *out_stats) {
+  const uint64_t nq = h.nq;
+  std::vector<uint32_t> &redo = h.h_list;  // read by a copy: kept by h, changed only behind the next sync
+  uint32_t ovf_cap = ph_default_ovf_cap(ef);
+  for (int attempt = 0;; attempt++) {
+    PH_TRY(ph_search_device(ix, c));
+    PH_TRY(h.download_words());
+    PH_TRY(h.sync());
+    redo.clear();
+    for (uint64_t i = 0; i < nq; i++) {
+      if (h.status(i) == 4u) {
+        ph_set_error("search: a candidate vector is missing from a lower layer (layers not nested, lib.rs:261)");
+        return PHNSW_E_MISSING_NODE;
+      }
+      if (h.status(i) == 5u) redo.push_back((uint32_t)i);
+    }
+    if (redo.empty()) break;
+    if (attempt == 3) {
+      ph_set_error("search: frontier spill exceeded %u entries for %zu queries", ovf_cap, redo.size());
+      return PHNSW_E_OVERFLOW;
+    }
+    // the overflowed queries alone, from a device list, with 8x the room: everything stays addressed by the query index
+    ovf_cap *= 8;
+    PH_TRY(h.upload_list(redo_dev));
+    c.order = redo_dev, c.nq = redo.size(), c.ovf_cap = ovf_cap;
+  }
+  PH_TRY(h.finish(out_ids, out_d, out_len));
+  if (out_stats)
+    for (uint64_t i = 0; i < 2u * nq; i++) out_stats[i] = h.read_extra(0, i);
   return 0;
 }
 
@@ -1181,32 +1268,96 @@ extern "C" int phnsw_search_batch_labeled(const phnsw_index *ix, const phnsw_lab
   PH_HIP(hipMemcpyAsync(want_dev, want, (size_t)nq * 4u, hipMemcpyHostToDevice, h.st));
   c.filter.label_of = lb->label_of, c.filter.want = want_dev, c.filter.flags = flags;
   c.sp = sp, c.upto = upto_layers, c.out_stats = h.extra();
-  std::vector<uint32_t> &redo = h.h_list;  // read by a copy: kept by h, changed only behind the next sync
-  uint32_t ovf_cap = ph_default_ovf_cap(ef);
-  for (int attempt = 0;; attempt++) {
-    PH_TRY(ph_search_device(ix, c));
-    PH_TRY(h.download_words());
-    PH_TRY(h.sync());
-    redo.clear();
-    for (uint64_t i = 0; i < nq; i++) {
-      if (h.status(i) == 4u) {
-        ph_set_error("search: a candidate vector is missing from a lower layer (layers not nested, lib.rs:261)");
-        return PHNSW_E_MISSING_NODE;
-      }
-      if (h.status(i) == 5u) redo.push_back((uint32_t)i);
-    }
-    if (redo.empty()) break;
-    if (attempt == 3) {
-      ph_set_error("search: frontier spill exceeded %u entries for %zu queries", ovf_cap, redo.size());
-      return PHNSW_E_OVERFLOW;
-    }
-    // the overflowed queries alone, from a device list, with 8x the room: everything stays addressed by the query index
-    ovf_cap *= 8;
-    PH_TRY(h.upload_list(redo_dev));
-    c.order = redo_dev, c.nq = redo.size(), c.ovf_cap = ovf_cap;
+  return walk_host_run(ix, h, c, redo_dev, ef, out_ids, out_d, out_len, out_stats);
+} catch (...) { return ph_caught(); }
+
+// ------------------------------------------------------------------ the graph walk by a set of labels
+
+// The search kernels' set mode (search_labelset.hip) over label_of and the caller's table.  The device form hands the
+// table to the kernels as it is: they refuse a range that is not sound per query (status 8) and read nothing outside
+// want_values[0 .. nwant); ranges that OVERLAP are harmless to a walk -- every query reads its own range -- and are not
+// detected here (the exact scan and the routed call do detect them).
+extern "C" int phnsw_search_batch_labelset_device(const phnsw_index *ix, const phnsw_labels *lb, const float *queries_dev,
+                                                  uint32_t ldq, const uint32_t *qids_dev, uint64_t nq,
+                                                  const phnsw_search_params *sp, uint32_t upto_layers,
+                                                  const uint32_t *exclude_dev, const uint32_t *want_first_dev,
+                                                  const uint32_t *want_values_dev, uint64_t nwant, uint32_t flags,
+                                                  uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                                  uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) try {
+  const char *const call = "phnsw_search_batch_labelset_device";
+  PH_TRY(walk_check(ix, lb, sp, flags, call));
+  if (nq == 0) return 0;
+  if (!ph_device_queries_ok(ix, queries_dev, qids_dev, ldq) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev ||
+      !want_first_dev || (!want_values_dev && nwant)) {
+    ph_set_error("%s: invalid argument (queries or qids, exactly one; outputs; want_first; want_values unless nwant is 0; "
+                 "queries need ldq >= store ld, multiple of 4, 16-byte base)", call);
+    return PHNSW_E_INVALID;
   }
-  PH_TRY(h.finish(out_ids, out_d, out_len));
-  if (out_stats)
-    for (uint64_t i = 0; i < 2u * nq; i++) out_stats[i] = h.read_extra(0, i);
-  return 0;
+  if (nq > PH_LABEL_NQ_MAX || nwant > PH_LABELSET_NWANT_MAX) {
+    ph_set_error("%s: nq and nwant must be below 2^31 - 1", call);
+    return PHNSW_E_INVALID;
+  }
+  PhSearchCall c = {};
+  c.queries = queries_dev, c.ldq = ldq, c.qids = qids_dev, c.exclude = exclude_dev, c.nq = nq;
+  c.sp = sp, c.upto = upto_layers;
+  c.filter.label_of = lb->label_of, c.filter.flags = flags;
+  c.filter.set_first = want_first_dev, c.filter.set_values = want_values_dev, c.filter.set_nwant = (uint32_t)nwant;
+  c.out_ids = out_ids_dev, c.out_d = out_d_dev, c.out_len = out_len_dev, c.status = status_dev, c.out_stats = out_stats_dev;
+  c.stream = (hipStream_t)stream;
+  PH_HIP(hipSetDevice(ix->store->device));
+  return ph_search_device(ix, c);
+} catch (...) { return ph_caught(); }
+
+// The host form stages everything once, as phnsw_search_batch_labeled does: query rows, the id words, and the filter's
+// 4 * (nq + 1) + 4 * nwant bytes.  The offsets are checked here, so no query can come back with status 8.
+extern "C" int phnsw_search_batch_labelset(const phnsw_index *ix, const phnsw_labels *lb, const float *queries,
+                                           const uint64_t *qids, uint64_t nq, const phnsw_search_params *sp, uint32_t upto_layers,
+                                           const uint64_t *exclude, const uint32_t *want_first, const uint32_t *want_values,
+                                           uint32_t flags, uint64_t k, uint64_t *out_ids, float *out_d, uint64_t *out_len,
+                                           uint64_t *out_stats) try {
+  const char *const call = "phnsw_search_batch_labelset";
+  PH_TRY(walk_check(ix, lb, sp, flags, call));
+  const uint32_t ef = (uint32_t)sp->number_of_candidates;
+  if (k > ef) {
+    ph_set_error("%s: k must be 0 (the whole queue) or 1..number_of_candidates (got %llu, number_of_candidates %u)", call,
+                 (unsigned long long)k, ef);
+    return PHNSW_E_INVALID;
+  }
+  if (nq == 0) return 0;
+  if ((!queries) == (!qids)) {
+    ph_set_error("%s: pass queries or qids (exactly one)", call);
+    return PHNSW_E_INVALID;
+  }
+  if (!out_ids || !out_d || !out_len || !want_first || nq > PH_LABEL_NQ_MAX) {
+    ph_set_error("%s: invalid argument (outputs; want_first; nq < 2^31 - 1)", call);
+    return PHNSW_E_INVALID;
+  }
+  const uint64_t nwant = want_first[nq];
+  if ((!want_values && nwant) || nwant > PH_LABELSET_NWANT_MAX) {
+    ph_set_error("%s: invalid argument (want_values unless want_first[nq] is 0; want_first[nq] < 2^31 - 1)", call);
+    return PHNSW_E_INVALID;
+  }
+  const phnsw_store *s = ix->store;
+  PH_HIP(hipSetDevice(s->device));
+  PH_TRY(ph_stored_ids_check(qids, nq, s->n, call, true));
+  if (const uint64_t bad = ph_labelset_first_bad(want_first, nq); bad < nq) {
+    ph_set_error("%s: query %llu: want_first must start at 0 and never run backwards (want_first[%llu] = %u, want_first[%llu] "
+                 "= %u)", call, (unsigned long long)bad, (unsigned long long)bad, want_first[bad], (unsigned long long)bad + 1u,
+                 want_first[bad + 1u]);
+    return PHNSW_E_INVALID;
+  }
+  phnsw_labels *mlb = const_cast<phnsw_labels *>(lb);
+  PhLabeledSet *set = set_acquire(mlb, nullptr, true);
+  PhHostCall h(mlb->pool, set);
+  // extras: stats(2), which the host reads back with len and status | want_first [nq + 1] | want_values [nwant] | the redo list
+  PH_TRY(h.stage_in(s, queries, qids, exclude, nq, (size_t)nq * 4u + 1u + (size_t)nwant, 2, ef, k ? (uint32_t)k : ef));
+  uint32_t *const first_dev = h.extra() + 2u * nq, *const values_dev = first_dev + nq + 1u, *const redo_dev = values_dev + nwant;
+  PhSearchCall c = {};
+  h.fill(c);
+  PH_HIP(hipMemcpyAsync(first_dev, want_first, (size_t)(nq + 1u) * 4u, hipMemcpyHostToDevice, h.st));
+  if (nwant) PH_HIP(hipMemcpyAsync(values_dev, want_values, (size_t)nwant * 4u, hipMemcpyHostToDevice, h.st));
+  c.filter.label_of = lb->label_of, c.filter.flags = flags;
+  c.filter.set_first = first_dev, c.filter.set_values = values_dev, c.filter.set_nwant = (uint32_t)nwant;
+  c.sp = sp, c.upto = upto_layers, c.out_stats = h.extra();
+  return walk_host_run(ix, h, c, redo_dev, ef, out_ids, out_d, out_len, out_stats);
 } catch (...) { return ph_caught(); }

@@ -49,6 +49,38 @@ PH_ROUTE_HD static inline bool ph_auto_label_candidate(const uint32_t *label_of,
   return v < n && want != none_label && label_of[v] == want;
 }
 
+// ---- a SET of labels per query (phnsw_search_batch_labelset, phnsw_search_labelset_auto): want_first [nq + 1] offsets
+// into want_values [nwant].  Used by the search kernels' set mode (search_kernels.h), by filter_auto.hip and by
+// tests/cpp/test_labelset_route.cpp.
+// scan_below == 0 of the routed call by set: the measured crossover of phnsw_search_exact_labelset and the walk by set in
+// candidates of the UNION (profiles/labelset_walk/README.md, "Crossover": sets of 4 labels; at a union of 20 000 rows the
+// scan took 17.6 ms against the walk's 22.0, at 40 000 rows 34.2 against 20.3, the lines cross near 25 000 -- 1M x 768 f32
+// rows, ef 256 / probe_depth 8, k = 10, 10 000 queries; other set sizes and shapes are unmeasured).  The last measured
+// count at which the scan still won, which happens to be the one-label figure
+#define PH_AUTO_SCAN_BELOW_LABELSET 20000u
+PH_ROUTE_HD static inline uint64_t ph_auto_scan_below_labelset(uint64_t scan_below) {
+  return scan_below != 0u ? scan_below : PH_AUTO_SCAN_BELOW_LABELSET;
+}
+// the range [first, last) of a query is sound: inside [0, nwant] and not backwards.  The offsets of a device call are
+// not trusted: a query whose range is not sound reads nothing of want_values (status 8, an empty row)
+PH_ROUTE_HD static inline bool ph_set_range_sound(uint64_t first, uint64_t last, uint64_t nwant) {
+  return first <= last && last <= nwant;
+}
+// the membership test of the set mode, written for one id: v passes iff its label is a label (not none_label) and one of
+// values[first .. last).  Duplicates and none_label in the set need no handling: a duplicate matches what its first copy
+// matches, and none_label is never the label of a passing vector.  The caller has found the range sound.
+PH_ROUTE_HD static inline bool ph_set_holds(uint32_t lbl, uint32_t first, uint32_t last, const uint32_t *values,
+                                            uint32_t none_label) {
+  bool hit = false;
+  for (uint32_t i = first; i < last; i++) hit |= values[i] == lbl;
+  return hit && lbl != none_label;
+}
+// e of ph_auto_full_len for a call by set: exclude[q] is a candidate iff it is listed under a label of the set
+PH_ROUTE_HD static inline bool ph_auto_set_candidate(const uint32_t *label_of, uint32_t n, uint32_t first, uint32_t last,
+                                                     const uint32_t *values, uint32_t v, uint32_t none_label) {
+  return v < n && ph_set_holds(label_of[v], first, last, values, none_label);
+}
+
 // the route of a query with c candidates.  c and n_nodes are 32-bit counts, ef and k at most 1024: the two products
 // stay below 2^42 and cannot wrap
 PH_ROUTE_HD static inline uint32_t ph_auto_route(uint32_t c, uint64_t scan_below, uint32_t ef, uint32_t k, uint32_t n_nodes) {

@@ -1,7 +1,7 @@
 // The unpipelined host form of the filtered and exact calls, written once (phnsw_search_exact_shared, _exact_grouped,
-// _exact_labeled, _exact_labelset, _batch_labeled, _filtered_auto and _labeled_auto): host arrays in, one stream of the
-// call's scratch set (call_set.h), host arrays out.  ph_search_host (hostpath.hip) is another thing: pinned, chunked,
-// two streams.
+// _exact_labeled, _exact_labelset, _batch_labeled, _batch_labelset, _filtered_auto, _labeled_auto and _labelset_auto): host
+// arrays in, one stream of the call's scratch set (call_set.h), host arrays out.  ph_search_host (hostpath.hip) is another
+// thing: pinned, chunked, two streams.
 //
 // A caller checks its arguments (ph_stored_ids_check among them, where its order of checks has it), acquires a set by
 // its owner's policy and then

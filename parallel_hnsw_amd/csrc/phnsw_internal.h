@@ -229,10 +229,14 @@ struct PhRowHint {
 // the allow-list of a filtered search as ph_search_device takes it (device words; PhSearchArgs::filter*)
 // ... or its label form: label_of != nullptr, the column [n] of a phnsw_labels handle (PHNSW_LABEL_NONE where a vector
 // is not listed) and want [nq], the label each query wants; words is then unused, flags mean the same
+// ... or its set form: label_of and set_first != nullptr, set_first [nq + 1] offsets into set_values [set_nwant] (the
+// labels each query wants, untrusted: PhSearchArgs::set_first); want is then unused
 struct PhFilter {
   const uint32_t *words;
   uint32_t stride, flags;
   const uint32_t *label_of, *want;
+  const uint32_t *set_first, *set_values;
+  uint32_t set_nwant;
 };
 
 // per-slice results of an exact scan that was cut into slices (filter_exact.hip): [nq][slices][k] keys from
@@ -401,6 +405,12 @@ struct PhSearchArgs {
   // table_by_query != 0: the per-launch table was made in natural order and `order` only afterwards (api.hip: the
   // table order), so a query's row is q, not its position.  (At the end, like the pairs above.)
   uint32_t table_by_query;
+  // the filter by a SET of row labels (search_labelset.hip): set_first [nq + 1] offsets into set_values [set_nwant], the
+  // labels query q wants = set_values[set_first[q] .. set_first[q + 1]); label_of is the column as above.  nullptr = not
+  // a set launch; never with a bitmap or with label_want.  The offsets are absolute and NOT trusted: a query whose range
+  // is not inside [0, set_nwant] or runs backwards does not walk (status 8).  (At the end, like the pairs above.)
+  const uint32_t *set_first, *set_values;
+  uint32_t set_nwant;
 };
 
 uint32_t ph_default_ovf_cap(uint32_t ef);
@@ -567,6 +577,10 @@ struct PhAutoCall {
   // the label form (phnsw_search_labeled_auto): candidates = the listed vectors of want[q]; filter is then unused
   const phnsw_labels *labels;
   const uint32_t *want;  // [nq]
+  // the set form (phnsw_search_labelset_auto): labels with want_first [nq + 1] and want_values [nwant] instead of want;
+  // candidates = the listed vectors of the labels of the query's range.  The offsets are not trusted
+  const uint32_t *want_first, *want_values;
+  uint64_t nwant;
   uint32_t k;
   uint64_t scan_below;  // 0 = the library default, UINT64_MAX = always scan (filter_route.h)
   uint32_t *out_ids;    // [nq][k]
@@ -593,6 +607,20 @@ struct PhLabeledCall {
   const uint32_t *list;
 };
 int ph_labeled_device(const phnsw_index *ix, const phnsw_labels *lb, const PhLabeledCall &c);
+// The request of one scan by label sets (ph_labelset_device, filter_labeled.hip): c without `want`, the sets in CSR form
+// (device words, untrusted), nwant pairs.  c.list as above: the scan covers the queries of the list, but which query
+// owns a pair -- and so which queries get status 8 -- is decided over the whole batch of batch_nq queries (c.nq is the
+// list's length with a list, else batch_nq)
+struct PhLabelsetCall {
+  PhLabeledCall c;
+  const uint32_t *want_first, *want_values;
+  uint64_t nwant, batch_nq;
+};
+int ph_labelset_device(const phnsw_index *ix, const phnsw_labels *lb, const PhLabelsetCall &sc);
+// out_count_dev[q] = the candidates of query q's set as phnsw_labels_count_set_device counts them, and 0 for a query the
+// scan by set refuses (a range that is not sound, or a pair that a lower query holds); owner_scratch [nwant] words
+int ph_labels_count_set(const phnsw_labels *lb, const uint32_t *want_first_dev, const uint32_t *want_values_dev, uint64_t nq,
+                        uint64_t nwant, uint32_t *out_count_dev, uint32_t *owner_scratch, hipStream_t stream);
 // a null handle, one made for another index or before the index changed: PHNSW_E_INVALID ("the labels are stale")
 int ph_labels_fresh(const phnsw_index *ix, const phnsw_labels *lb, const char *call);
 // the index, k, handle and store checks of phnsw_search_exact_labeled, in its order

@@ -178,13 +178,14 @@ static PhKernelChoice pick_unfiltered_kernel(const phnsw_store *s, uint32_t ef_m
 }
 
 // mode: the launch carries an allow-list or a label column and runs that twin of the kernel it would run without one
-// (same family, same queues, same LDS; search_filtered.hip, search_labeled.hip).  Never with instr, which
+// (same family, same queues, same LDS; search_filtered.hip, search_labeled.hip, search_labelset.hip).  Never with instr, which
 // ph_search_launch refuses.
 static PhKernelChoice pick_search_kernel(const phnsw_store *s, uint32_t ef_max, uint32_t nv4, bool grows, uint64_t nq,
                                          bool instr, int mode = PH_FM_NONE) {
   PhKernelChoice k = pick_unfiltered_kernel(s, ef_max, nv4, grows, nq, instr);
   if (mode == PH_FM_BITMAP && k.fn) k.fn = ph_pick_filtered_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
   if (mode == PH_FM_LABEL && k.fn) k.fn = ph_pick_labeled_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
+  if (mode == PH_FM_LABELSET && k.fn) k.fn = ph_pick_labelset_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
   // the collecting twins: the new calls only (PhSearchArgs::collect_k), and only the last launch of their descent
   if (mode == (PH_FM_BITMAP | PH_FM_COLLECT) && k.fn)
     k.fn = ph_pick_collect_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
@@ -334,8 +335,10 @@ static int search_launch_dense(PhWorkspace &ws, PhSearchArgs &a, hipStream_t str
     ph_set_error("a collecting search has no dense-only launch");
     return PHNSW_E_UNSUPPORTED;
   }
-  ph_search_fn fn = mode == PH_FM_LABEL ? ph_pick_labeled_dense(capc)
-                                        : (mode == PH_FM_BITMAP ? ph_pick_filtered_dense(capc) : pick_kernel_dense<PH_FM_NONE>(capc));
+  ph_search_fn fn = mode == PH_FM_LABELSET
+                        ? ph_pick_labelset_dense(capc)
+                        : (mode == PH_FM_LABEL ? ph_pick_labeled_dense(capc)
+                                               : (mode == PH_FM_BITMAP ? ph_pick_filtered_dense(capc) : pick_kernel_dense<PH_FM_NONE>(capc)));
   if (!fn) {
     ph_set_error("unsupported search shape: ef=%u", a.ef);
     return PHNSW_E_UNSUPPORTED;
@@ -418,6 +421,12 @@ int ph_search_launch(const phnsw_index *ix, PhWorkspace &ws, PhSearchArgs &a, hi
   if (mode != PH_FM_NONE && (a.knn_mode || a.out_index)) {  // only the plain searches have filtered kernels
     ph_set_error("knn / threshold_nn / search_instrumented take no filter");
     return PHNSW_E_UNSUPPORTED;
+  }
+  if (mode & PH_FM_LABELSET) {  // a set launch carries the column and the whole table, and nothing of the other modes
+    if ((mode & PH_FM_COLLECT) || a.filter || a.label_want || !a.label_of || (!a.set_values && a.set_nwant)) {
+      ph_set_error("a search by label sets takes the label column and the set table alone: no bitmap, no single label, not collecting");
+      return PHNSW_E_UNSUPPORTED;
+    }
   }
   if ((mode & PH_FM_COLLECT) &&
       (mode == PH_FM_COLLECT || (a.layer_hi && a.layer_hi != a.n_layers) || !a.collect_ids || !a.collect_d ||

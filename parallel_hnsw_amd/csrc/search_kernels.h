@@ -2,7 +2,8 @@
 // translation units that instantiate them: search.hip the kernels as they always were, search_filtered.hip their bitmap
 // twins, the kernels of a search restricted to an allow-list of VectorIds, search_labeled.hip their label twins, the same
 // restriction read from a label column; search_collect.hip and search_collect_labeled.hip the collecting twins of those
-// two (PH_FM_COLLECT).  Five units so that they compile side by side.
+// two (PH_FM_COLLECT); search_labelset.hip the twins over a SET of labels per query (PH_FM_LABELSET).  Six units so that
+// they compile side by side.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,6 +14,7 @@
 
 #include "phnsw_internal.h"
 
+#include "filter_route.h"
 #include "phnsw_device.h"
 
 // -DPH_HOP_PROFILE: a debugging build that prints, per layer of every query, where the hops' time went
@@ -91,23 +93,35 @@ __device__ __forceinline__ bool vis_insert(uint32_t *H, uint32_t slots, uint32_t
 //                 want != PHNSW_LABEL_NONE && label_of[v] == want -- one 4-byte load where the bitmap mode loads a word.
 //                 Written per lane as label_of[v] == want && label_of[v] != NONE: the same predicate, and the scalar
 //                 test of `want` cost seven twins a wave per SIMD (profiles/labeled_walk)
+//   PH_FM_LABELSET  the label column and a SET of wanted labels per query (a.set_first, a.set_values): VectorId v passes
+//                 iff label_of[v] != PHNSW_LABEL_NONE && label_of[v] is one of set_values[first .. last), first and last
+//                 the query's offsets, wave-uniform, read once per query.  The test is a loop over the set: every
+//                 wave-uniform set value (a scalar load) against every lane's label -- per 64 tested ids one 4-byte load
+//                 per lane and, per label of the set, one scalar load, one compare and one OR: LINEAR in the set's
+//                 length, no LDS (the LDS budget decides occupancy and the visited table's size), no sort, no
+//                 preparation.  In these (non-collecting) walks it runs over a layer's queue once per layer, not per
+//                 evaluated row.  The offsets are not trusted: a query whose range is not sound (filter_route.h) does
+//                 not walk -- ST_SET_RANGE, an empty row, stats 0 -- and nothing outside set_values[0 .. set_nwant) is
+//                 read.  Never with a bitmap or label_want, and there is no collecting twin.
 // A mode of the body and not a run-time test of the pointers: the test alone cost 19 of the 88 kernels scratch
 // (profiles/filter), so the filtered instances exist beside the others and are picked only when a filter is given.
 //   PH_FM_COLLECT  a bit on top of PH_FM_BITMAP / PH_FM_LABEL: the collecting walk (phnsw_search_collect*, search_collect.hip,
 //                  search_collect_labeled.hip).  The descent is the PLAIN search's -- the layer tails apply `exclude` only --
 //                  and the walk of the last layer keeps, beside the layer's queue, the a.collect_k best evaluated rows
 //                  that pass the filter (`kq`, below); those are the result row.  Only ever the last launch of a descent.
-enum : int { PH_FM_NONE = 0, PH_FM_BITMAP = 1, PH_FM_LABEL = 2, PH_FM_COLLECT = 4 };
+enum : int { PH_FM_NONE = 0, PH_FM_BITMAP = 1, PH_FM_LABEL = 2, PH_FM_COLLECT = 4, PH_FM_LABELSET = 8 };
+#define ST_SET_RANGE 8u  // the status of a query whose set range is not sound: phnsw_search_exact_labelset_device's value
 // the mode a launch's arguments ask for
 static inline int ph_filter_mode(const PhSearchArgs &a) {
-  return (a.label_of ? PH_FM_LABEL : (a.filter ? PH_FM_BITMAP : PH_FM_NONE)) | (a.collect_k ? PH_FM_COLLECT : PH_FM_NONE);
+  const int where = a.set_first ? PH_FM_LABELSET : (a.label_of ? PH_FM_LABEL : (a.filter ? PH_FM_BITMAP : PH_FM_NONE));
+  return where | (a.collect_k ? PH_FM_COLLECT : PH_FM_NONE);
 }
 
 template <int CAPC, class Dist, bool INSTR = false, bool BIG = false, int FILT = PH_FM_NONE>
 __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
   extern __shared__ uint32_t smem[];
   constexpr int CAP = CAPC * 64;
-  constexpr int FM = FILT & (PH_FM_BITMAP | PH_FM_LABEL);  // where the filter is read from
+  constexpr int FM = FILT & (PH_FM_BITMAP | PH_FM_LABEL | PH_FM_LABELSET);  // where the filter is read from
   constexpr bool COLLECT = (FILT & PH_FM_COLLECT) != 0;
   constexpr int TAILF = COLLECT ? PH_FM_NONE : FM;  // closest_vectors' `include` beyond `exclude`: none in a collecting walk
   uint32_t *Cid = smem;                    // running candidates: VectorIds (search.rs:110)
@@ -207,6 +221,28 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
     const uint32_t *const allow = FM == PH_FM_BITMAP ? a.filter + (uint64_t)q * a.filter_stride : nullptr;
     // ... or the label it wants (wave-uniform); NONE matches nothing, not even the unlisted vectors that carry it
     const uint32_t want = FM == PH_FM_LABEL ? rfl32(a.label_want[q]) : PHNSW_LABEL_NONE;
+    // ... or the range of its set in set_values (wave-uniform, absolute offsets).  A range that is not sound ends the
+    // query here, before anything of set_values is read: the row a failed query gets, ST_SET_RANGE, stats 0.  (A later
+    // launch of a split descent never comes here: the status check above.)
+    uint32_t set_b = 0, set_e = 0;
+    if constexpr (FM == PH_FM_LABELSET) {
+      set_b = rfl32(a.set_first[q]);
+      set_e = rfl32(a.set_first[q + 1u]);
+      if (!ph_set_range_sound(set_b, set_e, a.set_nwant)) {
+        const uint32_t ostride = a.out_stride ? a.out_stride : a.ef;
+        for (uint32_t i = lane; i < ostride; i += 64) {
+          a.out_ids[(uint64_t)q * ostride + i] = PH_EMPTY32;
+          a.out_d[(uint64_t)q * ostride + i] = PH_FMAX;
+        }
+        if (lane == 0) {
+          a.out_len[q] = 0u;
+          a.status[q] = ST_SET_RANGE;
+          if (a.out_stats) a.out_stats[2 * (uint64_t)q] = 0u, a.out_stats[2 * (uint64_t)q + 1] = 0u;
+          if (a.out_key) a.out_key[q] = PH_EMPTY32;
+        }
+        continue;
+      }
+    }
     // the filter test of VectorId v, written once for the layer tail, the strict pass and the collecting walk (callers
     // guard it: only lanes holding an id read a word or a label)
     auto passes = [&](uint32_t v) -> bool {
@@ -215,6 +251,8 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
       } else if constexpr (FM == PH_FM_LABEL) {
         const uint32_t lbl = a.label_of[v];
         return lbl == want && lbl != PHNSW_LABEL_NONE;
+      } else if constexpr (FM == PH_FM_LABELSET) {
+        return ph_set_holds(a.label_of[v], set_b, set_e, a.set_values, PHNSW_LABEL_NONE);
       } else {
         return true;
       }
@@ -1178,6 +1216,9 @@ ph_search_fn ph_pick_filtered_kernel(int family, int capc, int nv, int pqr_m, bo
 ph_search_fn ph_pick_filtered_dense(int capc);
 ph_search_fn ph_pick_labeled_kernel(int family, int capc, int nv, int pqr_m, bool pq_global);
 ph_search_fn ph_pick_labeled_dense(int capc);
+// the set twins: search_labelset.hip
+ph_search_fn ph_pick_labelset_kernel(int family, int capc, int nv, int pqr_m, bool pq_global);
+ph_search_fn ph_pick_labelset_dense(int capc);
 // the collecting twins (PH_FM_COLLECT over the bitmap and over the label column): search_collect.hip and
 // search_collect_labeled.hip.  No dense-only twin: a collecting kernel runs the last layer of a descent, and the
 // dense-only launch of a split descent never holds it (api.hip)

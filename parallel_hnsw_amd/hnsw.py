@@ -176,7 +176,8 @@ class Labels:
     vector is listed iff the index's bottom layer holds it.  The handle is a snapshot: after store.append, or with
     another index, search_exact_labeled refuses it as stale -- make a new one.  Keep `hnsw` alive while it is used.
     The handle also keeps the label column itself on the device (4 bytes per vector beside the lists): the graph walk by
-    label, search_batch_labeled, and the routed search_labeled read it."""
+    label, search_batch_labeled, the routed search_labeled and their forms by a set of labels (search_batch_labelset,
+    search_labelset) read it."""
 
     def __init__(self, hnsw, labels):
         self._h = None
@@ -1059,7 +1060,7 @@ class Hnsw:
         may return the vectors `labels` lists under any label of want[i] -- the same rows as
         search_exact_filtered(allow=(label column in want[i])), bit for bit.  want: as pack_label_sets takes it; an empty
         set, LABEL_NONE and labels nobody carries give nothing, a label twice counts once.  Exactly one of queries / qids.
-        Exact scan only: there is no graph walk and no routed call by set.
+        This is the exact scan; search_batch_labelset is the graph walk by set, search_labelset the routed call.
         Returns (ids[nq, k] u64, d[nq, k] f32, len[nq])"""
         if (queries is None) == (qids is None):
             raise ValueError("search_exact_labelset: pass queries or qids (exactly one)")
@@ -1099,6 +1100,17 @@ class Hnsw:
     def _labeled_args(self, call, queries, qids, labels, want):
         """the checks the calls by label make before they reach the library: a Labels, exactly one of queries / qids,
         want as pack_labels takes it.  Returns (q, qi, nq, want u32 [nq])"""
+        q, qi, nq = self._label_queries(call, queries, qids, labels)
+        return q, qi, nq, pack_labels(want, nq, "want")
+
+    def _labelset_args(self, call, queries, qids, labels, want):
+        """... of the calls by a set of labels: want as pack_label_sets takes it.  Returns (q, qi, nq, first u32 [nq + 1],
+        values u32 [nwant])"""
+        q, qi, nq = self._label_queries(call, queries, qids, labels)
+        first, values = pack_label_sets(want, nq)
+        return q, qi, nq, first, values
+
+    def _label_queries(self, call, queries, qids, labels):
         if not isinstance(labels, Labels):
             raise TypeError("%s: labels must be a Labels made for this index" % call)
         if (queries is None) == (qids is None):
@@ -1112,7 +1124,7 @@ class Hnsw:
         else:
             qi = np.ascontiguousarray(qids, dtype=np.uint64)
             nq = len(qi)
-        return q, qi, nq, pack_labels(want, nq, "want")
+        return q, qi, nq
 
     def search_batch_labeled(self, queries=None, qids=None, sp=None, labels=None, want=None, strict=False, exclude=None,
                              upto=0, stats=False, k=None):
@@ -1193,6 +1205,91 @@ class Hnsw:
             C.c_void_p(exclude or None), C.c_void_p(want or None), int(k), int(scan_below), C.c_void_p(out_ids),
             C.c_void_p(out_d), C.c_void_p(out_len), C.c_void_p(out_route or None), C.c_void_p(status),
             C.c_void_p(stream or None)))
+
+    def search_batch_labelset(self, queries=None, qids=None, sp=None, labels=None, want=None, strict=False, exclude=None,
+                              upto=0, stats=False, k=None):
+        """search_batch_labeled for a SET of labels per query, `label IN (a, b, c)` (phnsw_search_batch_labelset): the
+        graph walk of query i restricted to the vectors `labels` lists under any label of want[i] -- the rows, lengths and
+        stats of search_batch_filtered(allow=(label column in want[i])), bit for bit, without a bitmap per query.  want: as
+        pack_label_sets takes it; an empty set, LABEL_NONE and labels nobody carries give what an all-zero bitmap gives, a
+        label twice counts once, the order inside a set does not matter.  A post-filter like search_batch_labeled
+        (search_labelset completes rows); the entry vector may be returned although its label is not wanted, strict=True
+        removes it.  The membership test costs time linear in the length of a set.  Measured on 1M x 768 f32 rows, ef 256 /
+        probe_depth 8, 10 000 queries, sets of 1, 4 and 32 out of 1000 labels: the device form took 0.99 to 1.00 of the
+        bitmap call's kernel time and 0.49 to 0.54 of it with the upload counted (profiles/labelset_walk/README.md); the
+        host forms were not timed.
+        Returns (ids[nq, k or ef] u64, d f32, len[nq]) and the stats with stats=True"""
+        q, qi, nq, first, values = self._labelset_args("search_batch_labelset", queries, qids, labels, want)
+        sp = sp or SearchParameters()
+        ef = sp.number_of_candidates
+        w = ef if k is None else int(k)
+        if w < 0:
+            raise ValueError("search_batch_labelset: k must not be negative")
+        ids = np.empty((nq, w), dtype=np.uint64)
+        d = np.empty((nq, w), dtype=np.float32)
+        ln = np.zeros(nq, dtype=np.uint64)
+        st = np.zeros((nq, 2), dtype=np.uint64) if stats else None
+        ex = None if exclude is None else np.ascontiguousarray(exclude, dtype=np.uint64)
+        check(lib().phnsw_search_batch_labelset(self._h, labels._h, _p(q), _p(qi), nq, C.byref(sp), upto, _p(ex), _p(first),
+                                                _p(values) if len(values) else None, FILTER_STRICT if strict else 0,
+                                                0 if k is None else w, _p(ids), _p(d), _p(ln), _p(st)))
+        return (ids, d, ln, st) if stats else (ids, d, ln)
+
+    def search_batch_labelset_device(self, labels, nq, nwant, sp, out_ids, out_d, out_len, status, queries=0, ldq=0, qids=0,
+                                     exclude=0, want_first=0, want_values=0, strict=False, out_stats=0, upto=0, stream=0):
+        """zero-copy form (phnsw_search_batch_labelset_device): search_batch_labeled_device with want_first = u32 offsets
+        [nq + 1] and want_values = u32 labels [nwant] (device pointers, alive until the work on `stream` is done) in place
+        of want.  status 8 = a range of want_first that is not inside [0, nwant] or runs backwards: that query does not
+        walk (empty row, stats 0); overlapping ranges are not detected here.  Enqueued on `stream`; never synchronises
+        it"""
+        if not isinstance(labels, Labels):
+            raise TypeError("search_batch_labelset_device: labels must be a Labels made for this index")
+        check(lib().phnsw_search_batch_labelset_device(
+            self._h, labels._h, C.c_void_p(queries or None), ldq, C.c_void_p(qids or None), nq, C.byref(sp), upto,
+            C.c_void_p(exclude or None), C.c_void_p(want_first or None), C.c_void_p(want_values or None), int(nwant),
+            FILTER_STRICT if strict else 0, C.c_void_p(out_ids), C.c_void_p(out_d), C.c_void_p(out_len),
+            C.c_void_p(out_stats or None), C.c_void_p(status), C.c_void_p(stream or None)))
+
+    def search_labelset(self, queries=None, qids=None, sp=None, labels=None, want=None, exclude=None, k=10, scan_below=0,
+                        route=False):
+        """search_labeled for a SET of labels per query (phnsw_search_labelset_auto): per query the scan by set
+        (search_exact_labelset) where the union of the lists is short (count <= scan_below, or count *
+        number_of_candidates < k * vector_count, count as Labels.count_sets gives it), the strict graph walk by set
+        otherwise, and the scan again for every query whose walk came back short.  Every row holds exactly min(k, count - e)
+        entries and only listed vectors of the labels of want[i] (e = 1 iff exclude[i] is one of them): the rows of
+        search_filtered with the equivalent per-query bitmaps, bit for bit.  scan_below 0 = the library's threshold for
+        sets, 20 000 rows of the union: measured at sets of 4 labels on 1M x 768 f32 rows, ef 256, k = 10 (scan 17.6 ms
+        against the walk's 22.0 at 20 000, 34.2 against 20.3 at 40 000; profiles/labelset_walk/README.md), other shapes
+        unmeasured; 2**64 - 1 = always scan.
+        1 <= k <= sp.number_of_candidates.
+        Returns (ids[nq, k] u64, d[nq, k] f32, len[nq]) and, with route=True, route[nq] u32: ROUTE_GRAPH, ROUTE_SCAN or
+        ROUTE_GRAPH_THEN_SCAN"""
+        q, qi, nq, first, values = self._labelset_args("search_labelset", queries, qids, labels, want)
+        sp = sp or SearchParameters()
+        w = max(int(k), 0)
+        ids = np.empty((nq, w), dtype=np.uint64)
+        d = np.empty((nq, w), dtype=np.float32)
+        ln = np.zeros(nq, dtype=np.uint64)
+        rt = np.zeros(nq, dtype=np.uint32) if route else None
+        ex = None if exclude is None else np.ascontiguousarray(exclude, dtype=np.uint64)
+        check(lib().phnsw_search_labelset_auto(self._h, labels._h, _p(q), _p(qi), nq, C.byref(sp), _p(ex), _p(first),
+                                               _p(values) if len(values) else None, int(k), int(scan_below), _p(ids), _p(d),
+                                               _p(ln), _p(rt)))
+        return (ids, d, ln, rt) if route else (ids, d, ln)
+
+    def search_labelset_device(self, labels, nq, nwant, sp, k, out_ids, out_d, out_len, status, queries=0, ldq=0, qids=0,
+                               exclude=0, want_first=0, want_values=0, scan_below=0, out_route=0, stream=0):
+        """device form (phnsw_search_labelset_auto_device): device pointers as integers, u32 ids [nq, k] padded with
+        0xFFFFFFFF; want_first = u32 offsets [nq + 1], want_values = u32 labels [nwant]; out_route u32 [nq] or 0.  status
+        8 where search_exact_labelset_device reports it (a range fault, an overlap with a lower query): scanned, empty.
+        Like search_labeled_device it synchronises `stream`, up to twice"""
+        if not isinstance(labels, Labels):
+            raise TypeError("search_labelset_device: labels must be a Labels made for this index")
+        check(lib().phnsw_search_labelset_auto_device(
+            self._h, labels._h, C.c_void_p(queries or None), ldq, C.c_void_p(qids or None), nq, C.byref(sp),
+            C.c_void_p(exclude or None), C.c_void_p(want_first or None), C.c_void_p(want_values or None), int(nwant), int(k),
+            int(scan_below), C.c_void_p(out_ids), C.c_void_p(out_d), C.c_void_p(out_len), C.c_void_p(out_route or None),
+            C.c_void_p(status), C.c_void_p(stream or None)))
 
     def search_collect(self, queries=None, qids=None, sp=None, allow=None, exclude=None, upto=0, stats=False, k=10,
                        extend=False):

@@ -32,6 +32,20 @@ fn sp_c(s: SearchParameters) -> sys::phnsw_search_params {
         probe_depth: s.probe_depth as u64,
     }
 }
+/// the sets of a batch in CSR form, as the calls by set take them; panics, naming `call`, unless `want` has one set per
+/// query and at most 2^31 - 2 labels in all
+fn pack_label_sets(want: &[Vec<u32>], nq: usize, call: &str) -> (Vec<u32>, Vec<u32>) {
+    assert!(want.len() == nq, "{call}: one set of wanted labels per query");
+    let mut first: Vec<u32> = Vec::with_capacity(nq + 1);
+    let mut values: Vec<u32> = Vec::new();
+    first.push(0);
+    for s in want {
+        values.extend_from_slice(s);
+        assert!(values.len() <= 0x7FFF_FFFE, "{call}: too many wanted labels");
+        first.push(values.len() as u32);
+    }
+    (first, values)
+}
 fn op_c(o: OptimizationParameters) -> sys::phnsw_optimization_params {
     sys::phnsw_optimization_params {
         promotion_threshold: o.promotion_threshold,
@@ -662,21 +676,13 @@ impl GpuHnsw {
 
     /// `search_many_exact_labeled` for a set of labels per query (`phnsw_search_exact_labelset`): query i may return the
     /// vectors `labels` lists under any label of `want[i]`; an empty set and labels nobody carries give nothing, a label
-    /// twice counts once.  The same results, bit for bit, as the predicates `label of v in want[i]` give.  Exact scan
-    /// only: there is no graph walk by set.  Panics unless 1 <= k <= 1024 and `want` has one set per query
+    /// twice counts once.  The same results, bit for bit, as the predicates `label of v in want[i]` give.  The exact
+    /// scan; `search_many_labelset` walks the graph by set, `search_many_labelset_auto` routes.  Panics unless 1 <= k <= 1024 and `want` has one set per query
     pub fn search_many_exact_labelset(&self, queries: &[Vec<f32>], k: usize, labels: &GpuLabels, want: &[Vec<u32>])
                                       -> Vec<Vec<(VectorId, f32)>> {
         assert!((1..=1024).contains(&k), "search_many_exact_labelset: k must be 1..1024");
         let nq = queries.len();
-        assert!(want.len() == nq, "search_many_exact_labelset: one set of wanted labels per query");
-        let mut first: Vec<u32> = Vec::with_capacity(nq + 1);
-        let mut values: Vec<u32> = Vec::new();
-        first.push(0);
-        for s in want {
-            values.extend_from_slice(s);
-            assert!(values.len() <= 0x7FFF_FFFE, "search_many_exact_labelset: too many wanted labels");
-            first.push(values.len() as u32);
-        }
+        let (first, values) = pack_label_sets(want, nq, "search_many_exact_labelset");
         let mut q: Vec<f32> = Vec::with_capacity(nq * queries.first().map_or(0, |x| x.len()));
         for x in queries {
             q.extend_from_slice(x);
@@ -704,6 +710,90 @@ impl GpuHnsw {
         check(sys::phnsw_search_exact_labelset_device(self.ix, labels.lb, queries_dev, ldq, qids_dev, nq, exclude_dev,
                                                       want_first_dev, want_values_dev, nwant, k, out_ids_dev, out_d_dev,
                                                       out_len_dev, status_dev, stream));
+    }
+
+    /// `search_many_labeled` for a set of labels per query (`phnsw_search_batch_labelset`): the graph walk of query i
+    /// restricted to the vectors `labels` lists under any label of `want[i]` -- the results `search_many_filtered` gives
+    /// with the equivalent predicates, bit for bit.  A post-filter; `strict` also removes an entry vector whose label is
+    /// not wanted.  The membership test is linear in the length of a set.  Panics unless `want` has one set per query
+    pub fn search_many_labelset(&self, queries: &[Vec<f32>], sp: SearchParameters, labels: &GpuLabels, want: &[Vec<u32>],
+                                strict: bool) -> Vec<Vec<(VectorId, f32)>> {
+        let nq = queries.len();
+        let (first, values) = pack_label_sets(want, nq, "search_many_labelset");
+        let ef = sp.number_of_candidates;
+        let psp = sp_c(sp);
+        let mut q: Vec<f32> = Vec::with_capacity(nq * queries.first().map_or(0, |x| x.len()));
+        for x in queries {
+            q.extend_from_slice(x);
+        }
+        let (mut ids, mut d, mut len) = (vec![0u64; nq * ef], vec![0f32; nq * ef], vec![0u64; nq]);
+        check(unsafe {
+            sys::phnsw_search_batch_labelset(self.ix, labels.lb, q.as_ptr(), std::ptr::null(), nq as u64, &psp, 0, std::ptr::null(),
+                                             first.as_ptr(), values.as_ptr(), if strict { 1 } else { 0 }, 0, ids.as_mut_ptr(),
+                                             d.as_mut_ptr(), len.as_mut_ptr(), std::ptr::null_mut())
+        });
+        (0..nq).map(|i| (0..len[i] as usize).map(|j| (VectorId(ids[i * ef + j] as usize), d[i * ef + j])).collect()).collect()
+    }
+
+    /// zero-copy form (`phnsw_search_batch_labelset_device`): the sets in CSR form; status 8 = a range of
+    /// `want_first_dev` that is not sound (that query does not walk); enqueued on `stream`, never synchronises it
+    ///
+    /// # Safety
+    /// the pointers must be valid device allocations of the sizes `phnsw.h` documents for the call
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn search_batch_labelset_device(&self, labels: &GpuLabels, queries_dev: *const f32, ldq: u32,
+                                               qids_dev: *const u32, nq: u64, sp: SearchParameters, upto_layers: u32,
+                                               exclude_dev: *const u32, want_first_dev: *const u32,
+                                               want_values_dev: *const u32, nwant: u64, flags: u32, out_ids_dev: *mut u32,
+                                               out_d_dev: *mut f32, out_len_dev: *mut u32, out_stats_dev: *mut u32,
+                                               status_dev: *mut u32, stream: *mut c_void) {
+        let psp = sp_c(sp);
+        check(sys::phnsw_search_batch_labelset_device(self.ix, labels.lb, queries_dev, ldq, qids_dev, nq, &psp, upto_layers,
+                                                      exclude_dev, want_first_dev, want_values_dev, nwant, flags, out_ids_dev,
+                                                      out_d_dev, out_len_dev, out_stats_dev, status_dev, stream));
+    }
+
+    /// `search_many_labeled_auto` for a set of labels per query (`phnsw_search_labelset_auto`): per query the scan by set
+    /// or the strict walk by set, the scan again for short rows; every result holds min(k, candidates) entries, listed
+    /// vectors of the labels of `want[i]` only.  `scan_below` 0 = the library's threshold for sets (20 000 rows of
+    /// the union, `phnsw.h`), `u64::MAX` = always scan.  Returns the results and one route per query.  Panics
+    /// unless 1 <= k <= number_of_candidates and `want` has one set per query
+    pub fn search_many_labelset_auto(&self, queries: &[Vec<f32>], sp: SearchParameters, k: usize, scan_below: u64,
+                                     labels: &GpuLabels, want: &[Vec<u32>]) -> (Vec<Vec<(VectorId, f32)>>, Vec<u32>) {
+        assert!(k >= 1 && k <= sp.number_of_candidates, "search_many_labelset_auto: k must be 1..number_of_candidates");
+        let nq = queries.len();
+        let (first, values) = pack_label_sets(want, nq, "search_many_labelset_auto");
+        let psp = sp_c(sp);
+        let mut q: Vec<f32> = Vec::with_capacity(nq * queries.first().map_or(0, |x| x.len()));
+        for x in queries {
+            q.extend_from_slice(x);
+        }
+        let (mut ids, mut d, mut len) = (vec![0u64; nq * k], vec![0f32; nq * k], vec![0u64; nq]);
+        let mut route = vec![0u32; nq];
+        check(unsafe {
+            sys::phnsw_search_labelset_auto(self.ix, labels.lb, q.as_ptr(), std::ptr::null(), nq as u64, &psp, std::ptr::null(),
+                                            first.as_ptr(), values.as_ptr(), k as u64, scan_below, ids.as_mut_ptr(),
+                                            d.as_mut_ptr(), len.as_mut_ptr(), route.as_mut_ptr())
+        });
+        let rows = (0..nq).map(|i| (0..len[i] as usize).map(|j| (VectorId(ids[i * k + j] as usize), d[i * k + j])).collect()).collect();
+        (rows, route)
+    }
+
+    /// device form (`phnsw_search_labelset_auto_device`): u32 ids `[nq][k]`; synchronises `stream` up to twice
+    ///
+    /// # Safety
+    /// the pointers must be valid device allocations of the sizes `phnsw.h` documents for the call
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn search_labelset_auto_device(&self, labels: &GpuLabels, queries_dev: *const f32, ldq: u32,
+                                              qids_dev: *const u32, nq: u64, sp: SearchParameters, exclude_dev: *const u32,
+                                              want_first_dev: *const u32, want_values_dev: *const u32, nwant: u64, k: u64,
+                                              scan_below: u64, out_ids_dev: *mut u32, out_d_dev: *mut f32,
+                                              out_len_dev: *mut u32, out_route_dev: *mut u32, status_dev: *mut u32,
+                                              stream: *mut c_void) {
+        let psp = sp_c(sp);
+        check(sys::phnsw_search_labelset_auto_device(self.ix, labels.lb, queries_dev, ldq, qids_dev, nq, &psp, exclude_dev,
+                                                     want_first_dev, want_values_dev, nwant, k, scan_below, out_ids_dev,
+                                                     out_d_dev, out_len_dev, out_route_dev, status_dev, stream));
     }
 
     /// `search_many_filtered` by row label (`phnsw_search_batch_labeled`): the graph walk of query i restricted to the
