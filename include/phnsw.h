@@ -707,6 +707,100 @@ int phnsw_search_labelset_auto_device(const phnsw_index *ix, const phnsw_labels 
                                       const uint32_t *want_values_dev, uint64_t nwant, uint64_t k, uint64_t scan_below,
                                       uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
                                       uint32_t *out_route_dev, uint32_t *status_dev, void *stream);
+/* ---- search by a NUMERIC RANGE of a row attribute, `lo <= attribute <= hi`: a timestamp, a price, a version, a size.
+ * Every vector carries one u32 key, compared as an unsigned integer; PHNSW_ATTR_NONE means the row carries no value.
+ * A phnsw_attr handle sorts the listed rows ONCE by (key, id) on the device; every range is then one contiguous span of
+ * that order, found with two binary searches, and its candidate count is upper - lower: no bitmap per query, no bucket
+ * labels, no merge of lists.  The handle keeps skeys[listed] (ascending), ids[listed] (ascending within equal keys) and,
+ * for the graph walk, attr_of[n] (the key of a listed row, PHNSW_ATTR_NONE elsewhere): TWELVE BYTES PER VECTOR.
+ * Listed: v is listed iff v < n, keys[v] != PHNSW_ATTR_NONE and v is a vector of the index's bottom layer (the test of
+ * phnsw_labels_create).  n must equal the store's vector count, else PHNSW_E_INVALID.
+ * Ranges are INCLUSIVE on both ends.  hi == 0xFFFFFFFF is legal and means "no upper bound": rows without a value are in
+ * no span.  lo > hi is the empty range, not an error: the row is empty, the length 0, the status 0.
+ * VALUE TYPES: the ABI is u32 keys.  Other 32-bit types go through an order-preserving map, applied to the column and to
+ * both bounds alike (phnsw.hpp: phnsw::attr_key; Python: attr_keys):
+ *   u32   the value itself
+ *   i32   x ^ 0x80000000
+ *   f32   -0.0 is first made +0.0; then bits | 0x80000000 for a value that is not negative, ~bits for a negative one
+ * NaN has no place in an order and must not be mapped; a u32 value of 0xFFFFFFFF -- and so an i32 value of INT32_MAX,
+ * which maps onto it -- cannot be told from "no value" in a column (as a bound it is "no upper end", which is what it
+ * means).  64-bit columns are out of scope.
+ * The handle is a SNAPSHOT like phnsw_labels, with its rule and its wording: a null handle, one made for another index
+ * or before the store's n or the bottom layer's node count changed is PHNSW_E_INVALID ("... are stale").  Creation
+ * synchronises (the null stream, or `stream` of the device form, whose keys_dev is read before the call returns).
+ * phnsw_attr_info: the n it was made for, the listed vectors, the smallest and the largest key (0xFFFFFFFF and 0 when
+ * nothing is listed); any output may be NULL.  phnsw_attr_count_device writes, per query, the length of the span of
+ * [lo_dev[q], hi_dev[q]], 0 when lo > hi: phnsw_filter_count_device's figure for the equivalent bitmap; it is enqueued
+ * on `stream` and never synchronises.  phnsw_attr_destroy waits for the calls in flight that use the handle; NULL is a
+ * no-op.  The handle does not own the index and must not outlive it in use. */
+typedef struct phnsw_attr phnsw_attr;
+#define PHNSW_ATTR_NONE 0xFFFFFFFFu /* keys[v]: v carries no value */
+int phnsw_attr_create(const phnsw_index *ix, const uint32_t *keys, uint64_t n, phnsw_attr **out); /* host keys [n] */
+int phnsw_attr_create_device(const phnsw_index *ix, const uint32_t *keys_dev, uint64_t n, void *stream, phnsw_attr **out);
+int phnsw_attr_info(const phnsw_attr *at, uint64_t *n, uint64_t *listed, uint32_t *key_min, uint32_t *key_max);
+int phnsw_attr_count_device(const phnsw_attr *at, const uint32_t *lo_dev, const uint32_t *hi_dev, uint64_t nq,
+                            uint32_t *out_count_dev, void *stream);
+void phnsw_attr_destroy(phnsw_attr *at); /* waits for the calls in flight that use it */
+/* exact top-k over a range: phnsw_search_exact_labeled with (at, lo, hi) in place of (lb, want); lo and hi are u32 [nq].
+ * Candidates of q: the listed vectors with lo[q] <= key <= hi[q], except exclude[q].
+ * EQUALITY: the row of every query equals, in ids, distance bits, length and status, the row
+ * phnsw_search_exact_filtered returns for that query with the bitmap {v : v listed, lo[q] <= keys[v] <= hi[q]}: ascending
+ * (distance, id) with phnsw_distance_batch's bits, +inf and tie order as there, rows of k entries padded with
+ * PHNSW_EMPTY / f32::MAX, 1 <= k <= 1024.  The ids of a span are NOT ascending; the keys of the running top-k are
+ * (distance, id), distinct, so the k smallest are one set in one order however the span is ordered or cut.  The result
+ * does not depend on the batch's order or on the knob below.
+ * Checks: those of phnsw_search_exact_labeled in its order, with `at` for `lb` and lo / hi for want.
+ * How: per query the span; the batch sorted by span start, so that waves resident together read neighbouring rows; one
+ * wave64 per (query, slice of its span), the scan loop of phnsw_search_exact_labeled's per-query path, over every store
+ * kind that call scans.  There is NO tile path: overlapping spans are not the lists of one label.  Knob (environment,
+ * read per call, changes no result): PHNSW_RANGE_SLICES forces the number of slices a span is cut into.
+ * Guidance: NOT MEASURED (scripts/bench_ranged.py, profiles/ranged/README.md).  The per-query path of the label scan
+ * measured 2.2 x to 3.6 x slower than its tile path; expect this call near phnsw_search_exact_labeled under
+ * PHNSW_LABEL_TILE=1 for spans as long as the lists. */
+int phnsw_search_exact_ranged(const phnsw_index *ix, const phnsw_attr *at, const float *queries, const uint64_t *qids,
+                              uint64_t nq, const uint64_t *exclude, const uint32_t *lo, const uint32_t *hi, uint64_t k,
+                              uint64_t *out_ids, float *out_d, uint64_t *out_len);
+/* device form, as phnsw_search_exact_labeled_device: ENQUEUES AND RETURNS, never synchronises; status_dev[q] = 4 for a
+ * Stored query id at or past n (an empty row, the others unaffected).  Scratch sets -- 28 bytes per query, the sort's
+ * temporaries, nq x slices x k keys -- live with the handle under that call's policy until phnsw_attr_destroy. */
+int phnsw_search_exact_ranged_device(const phnsw_index *ix, const phnsw_attr *at, const float *queries_dev, uint32_t ldq,
+                                     const uint32_t *qids_dev, uint64_t nq, const uint32_t *exclude_dev,
+                                     const uint32_t *lo_dev, const uint32_t *hi_dev, uint64_t k, uint32_t *out_ids_dev,
+                                     float *out_d_dev, uint32_t *out_len_dev, uint32_t *status_dev, void *stream);
+/* the graph walk by range: phnsw_search_batch_labeled with (at, lo, hi) in place of (lb, want) -- the search kernels'
+ * range mode over attr_of, one 4-byte load and two compares per tested id.
+ * ROW EQUALITY: rows, lengths, stats and statuses are those of phnsw_search_batch_filtered[_device] called with the
+ * per-query bitmaps {v : v listed, lo[q] <= keys[v] <= hi[q]}, bit for bit, the entry-vector quirk and
+ * PHNSW_FILTER_STRICT included.  The index's default filter is not consulted.  Every store kind
+ * phnsw_search_batch_filtered walks is accepted.  Not measured against it (profiles/ranged/README.md). */
+int phnsw_search_batch_ranged(const phnsw_index *ix, const phnsw_attr *at, const float *queries, const uint64_t *qids,
+                              uint64_t nq, const phnsw_search_params *sp, uint32_t upto_layers, const uint64_t *exclude,
+                              const uint32_t *lo, const uint32_t *hi, uint32_t flags, uint64_t k, uint64_t *out_ids,
+                              float *out_d, uint64_t *out_len, uint64_t *out_stats);
+/* device form: ENQUEUED on `stream`, never synchronises.  lo_dev and hi_dev [nq] are read by the kernels: keep them alive
+ * and unchanged until the work on `stream` is done. */
+int phnsw_search_batch_ranged_device(const phnsw_index *ix, const phnsw_attr *at, const float *queries_dev, uint32_t ldq,
+                                     const uint32_t *qids_dev, uint64_t nq, const phnsw_search_params *sp,
+                                     uint32_t upto_layers, const uint32_t *exclude_dev, const uint32_t *lo_dev,
+                                     const uint32_t *hi_dev, uint32_t flags, uint32_t *out_ids_dev, float *out_d_dev,
+                                     uint32_t *out_len_dev, uint32_t *out_stats_dev, uint32_t *status_dev, void *stream);
+/* one call by range that routes: phnsw_search_labeled_auto with (at, lo, hi).  Same three routes, rule and promise: every
+ * row holds exactly min(k, c_q - e_q) entries and only candidates; c_q is the span's length (no bitmap is made or
+ * counted), e_q is 1 iff exclude[q] < n and its key is inside the range.  The walk is the STRICT range walk; scanned rows
+ * and graph rows left short go through ONE launch of the exact scan above.  Hence every row equals the row of
+ * phnsw_search_filtered_auto with the per-query bitmaps and the same scan_below.  The device form synchronises `stream`
+ * at most twice.  scan_below 0 = the library default for ranges (filter_route.h, PH_AUTO_SCAN_BELOW_RANGED): 20 000,
+ * UNMEASURED -- it is the one-label figure, and the range scan has no tile path, so the true crossover is expected
+ * below it; pass your own.  UINT64_MAX = always scan. */
+int phnsw_search_ranged_auto(const phnsw_index *ix, const phnsw_attr *at, const float *queries, const uint64_t *qids,
+                             uint64_t nq, const phnsw_search_params *sp, const uint64_t *exclude, const uint32_t *lo,
+                             const uint32_t *hi, uint64_t k, uint64_t scan_below, uint64_t *out_ids, float *out_d,
+                             uint64_t *out_len, uint32_t *out_route);
+int phnsw_search_ranged_auto_device(const phnsw_index *ix, const phnsw_attr *at, const float *queries_dev, uint32_t ldq,
+                                    const uint32_t *qids_dev, uint64_t nq, const phnsw_search_params *sp,
+                                    const uint32_t *exclude_dev, const uint32_t *lo_dev, const uint32_t *hi_dev, uint64_t k,
+                                    uint64_t scan_below, uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                    uint32_t *out_route_dev, uint32_t *status_dev, void *stream);
 /* ---- the COLLECTING search: the graph walk that remembers the best ALLOWED rows it evaluates.  The filtered walks above
  * are post-filters: they keep the best number_of_candidates rows, allowed or not, and filter that queue when the layer
  * ends, so a filter of density p leaves about p * number_of_candidates results although the walk evaluated several

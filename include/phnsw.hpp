@@ -17,6 +17,7 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -159,6 +160,7 @@ struct Layer {
 using SearchResult = std::vector<std::pair<VectorId, float>>;
 
 class Labels;
+class Attribute;
 
 class Hnsw {
  public:
@@ -557,6 +559,39 @@ class Hnsw {
                                          const uint32_t *want_dev, uint64_t k, uint64_t scan_below, uint32_t *out_ids_dev,
                                          float *out_d_dev, uint32_t *out_len_dev, uint32_t *out_route_dev, uint32_t *status_dev,
                                          void *stream) const;
+  // search_many_exact_filtered by a numeric range (phnsw_search_exact_ranged): query i may return the vectors `attr` lists
+  // with lo[i] <= key <= hi[i], both ends inclusive, u32 KEYS (attr_key maps i32 and f32 bounds); lo > hi = nothing
+  inline std::vector<SearchResult> search_many_exact_ranged(const std::vector<const float *> &queries, uint64_t k,
+                                                            const Attribute &attr, const std::vector<uint32_t> &lo,
+                                                            const std::vector<uint32_t> &hi) const;
+  // zero-copy form (phnsw_search_exact_ranged_device): u32 ids [nq][k]; enqueued on `stream`, never synchronises it
+  inline void search_exact_ranged_device(const Attribute &attr, const float *queries_dev, uint32_t ldq, const uint32_t *qids_dev,
+                                         uint64_t nq, const uint32_t *exclude_dev, const uint32_t *lo_dev, const uint32_t *hi_dev,
+                                         uint64_t k, uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                         uint32_t *status_dev, void *stream) const;
+  // search_many_filtered by a numeric range (phnsw_search_batch_ranged): the graph walk restricted to the range; k 0 =
+  // all number_of_candidates entries of a row
+  inline std::vector<SearchResult> search_many_ranged(const std::vector<const float *> &queries, const SearchParameters &sp,
+                                                      uint64_t k, const Attribute &attr, const std::vector<uint32_t> &lo,
+                                                      const std::vector<uint32_t> &hi, bool strict = false) const;
+  // zero-copy form (phnsw_search_batch_ranged_device): lo_dev / hi_dev stay alive until the work on `stream` is done
+  inline void search_batch_ranged_device(const Attribute &attr, const float *queries_dev, uint32_t ldq, const uint32_t *qids_dev,
+                                         uint64_t nq, const SearchParameters &sp, uint32_t upto_layers,
+                                         const uint32_t *exclude_dev, const uint32_t *lo_dev, const uint32_t *hi_dev, bool strict,
+                                         uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev, uint32_t *out_stats_dev,
+                                         uint32_t *status_dev, void *stream) const;
+  // search_many_filtered_auto by a numeric range (phnsw_search_ranged_auto): per query the span scan or the strict range
+  // walk, the scan again for short rows.  scan_below 0 = the library's threshold for ranges (20 000, UNMEASURED: phnsw.h)
+  inline std::vector<SearchResult> search_many_ranged_auto(const std::vector<const float *> &queries, const SearchParameters &sp,
+                                                           uint64_t k, const Attribute &attr, const std::vector<uint32_t> &lo,
+                                                           const std::vector<uint32_t> &hi, uint64_t scan_below = 0,
+                                                           std::vector<uint32_t> *routes = nullptr) const;
+  // device form (phnsw_search_ranged_auto_device): u32 ids [nq][k]; synchronises `stream` up to twice (phnsw.h)
+  inline void search_ranged_auto_device(const Attribute &attr, const float *queries_dev, uint32_t ldq, const uint32_t *qids_dev,
+                                        uint64_t nq, const SearchParameters &sp, const uint32_t *exclude_dev,
+                                        const uint32_t *lo_dev, const uint32_t *hi_dev, uint64_t k, uint64_t scan_below,
+                                        uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev, uint32_t *out_route_dev,
+                                        uint32_t *status_dev, void *stream) const;
   // 0, or the code search_many_exact_shared would refuse this index and k with (phnsw_exact_shared_supported)
   int exact_shared_supported(uint64_t k) const { return phnsw_exact_shared_supported(ix_, k); }
   // candidates of each of nbitmaps device bitmaps (phnsw_filter_count_device): what to choose the search call by
@@ -944,6 +979,135 @@ inline void Hnsw::search_labeled_auto_device(const Labels &labels, const float *
                                              uint32_t *out_route_dev, uint32_t *status_dev, void *stream) const {
   check(phnsw_search_labeled_auto_device(ix_, labels.handle(), queries_dev, ldq, qids_dev, nq, &sp, exclude_dev, want_dev, k,
                                          scan_below, out_ids_dev, out_d_dev, out_len_dev, out_route_dev, status_dev, stream));
+}
+
+// The order-preserving maps onto the u32 keys of an Attribute (phnsw.h, "VALUE TYPES"): the unsigned order of the keys is
+// the order of the values.  Apply the same map to the column and to both bounds.  NaN has no place in an order: do not
+// map it.  A u32 0xFFFFFFFF and an i32 INT32_MAX are Attribute::NONE in a column, "no upper end" as a bound.
+inline uint32_t attr_key(uint32_t x) { return x; }
+inline uint32_t attr_key(int32_t x) { return (uint32_t)x ^ 0x80000000u; }
+inline uint32_t attr_key(float x) {
+  if (x == 0.0f) x = 0.0f;  // -0.0 -> +0.0
+  uint32_t bits;
+  std::memcpy(&bits, &x, 4);
+  return (bits >> 31) ? ~bits : (bits | 0x80000000u);
+}
+
+// phnsw_attr: one u32 key per vector of the index's store, sorted once by (key, id) on the device (12 bytes per vector).
+// A snapshot like Labels.  The Hnsw must outlive its use
+class Attribute {
+ public:
+  static constexpr uint32_t NONE = PHNSW_ATTR_NONE;  // a row without a value
+  Attribute(const Hnsw &hnsw, const std::vector<uint32_t> &keys) {
+    check(phnsw_attr_create(hnsw.handle(), keys.data(), keys.size(), &at_));
+  }
+  // keys_dev: u32 [store n] in device memory, read on `stream`, which is synchronised
+  Attribute(const Hnsw &hnsw, const uint32_t *keys_dev, uint64_t n, void *stream) {
+    check(phnsw_attr_create_device(hnsw.handle(), keys_dev, n, stream, &at_));
+  }
+  Attribute(const Attribute &) = delete;
+  Attribute &operator=(const Attribute &) = delete;
+  Attribute(Attribute &&o) noexcept : at_(o.at_) { o.at_ = nullptr; }
+  ~Attribute() { phnsw_attr_destroy(at_); }
+  uint64_t listed() const {
+    uint64_t v = 0;
+    check(phnsw_attr_info(at_, nullptr, &v, nullptr, nullptr));
+    return v;
+  }
+  // the smallest and the largest key (0xFFFFFFFF and 0 when nothing is listed)
+  std::pair<uint32_t, uint32_t> key_range() const {
+    uint32_t a = 0, b = 0;
+    check(phnsw_attr_info(at_, nullptr, nullptr, &a, &b));
+    return {a, b};
+  }
+  void count_device(const uint32_t *lo_dev, const uint32_t *hi_dev, uint64_t nq, uint32_t *out_count_dev, void *stream) const {
+    check(phnsw_attr_count_device(at_, lo_dev, hi_dev, nq, out_count_dev, stream));
+  }
+  phnsw_attr *handle() const { return at_; }
+
+ private:
+  phnsw_attr *at_ = nullptr;
+};
+
+namespace detail {
+// the host forms by range: queries copied to one block, rows of `row` entries cut to their lengths
+template <class F>
+inline std::vector<SearchResult> ranged_rows(const std::vector<const float *> &queries, uint64_t dim, uint64_t row,
+                                             const std::vector<uint32_t> &lo, const std::vector<uint32_t> &hi, const char *call,
+                                             F run) {
+  const uint64_t nq = queries.size();
+  if (lo.size() != nq || hi.size() != nq) throw Error(PHNSW_E_INVALID, std::string(call) + ": one lo and one hi per query");
+  std::vector<float> q(nq * dim);
+  for (uint64_t i = 0; i < nq; i++) std::copy(queries[i], queries[i] + dim, q.begin() + i * dim);
+  std::vector<uint64_t> ids(nq * row), len(nq);
+  std::vector<float> d(nq * row);
+  run(q.data(), nq, ids.data(), d.data(), len.data());
+  std::vector<SearchResult> out(nq);
+  for (uint64_t i = 0; i < nq; i++)
+    for (uint64_t j = 0; j < len[i]; j++) out[i].push_back({ids[i * row + j], d[i * row + j]});
+  return out;
+}
+}  // namespace detail
+
+inline std::vector<SearchResult> Hnsw::search_many_exact_ranged(const std::vector<const float *> &queries, uint64_t k,
+                                                                const Attribute &attr, const std::vector<uint32_t> &lo,
+                                                                const std::vector<uint32_t> &hi) const {
+  if (k == 0 || k > 1024) throw Error(PHNSW_E_INVALID, "search_many_exact_ranged: k must be 1..1024");
+  return detail::ranged_rows(queries, c_->dim(), k, lo, hi, "search_many_exact_ranged",
+                             [&](const float *q, uint64_t nq, uint64_t *ids, float *d, uint64_t *len) {
+                               check(phnsw_search_exact_ranged(ix_, attr.handle(), q, nullptr, nq, nullptr, lo.data(), hi.data(), k,
+                                                               ids, d, len));
+                             });
+}
+inline void Hnsw::search_exact_ranged_device(const Attribute &attr, const float *queries_dev, uint32_t ldq,
+                                             const uint32_t *qids_dev, uint64_t nq, const uint32_t *exclude_dev,
+                                             const uint32_t *lo_dev, const uint32_t *hi_dev, uint64_t k, uint32_t *out_ids_dev,
+                                             float *out_d_dev, uint32_t *out_len_dev, uint32_t *status_dev, void *stream) const {
+  check(phnsw_search_exact_ranged_device(ix_, attr.handle(), queries_dev, ldq, qids_dev, nq, exclude_dev, lo_dev, hi_dev, k,
+                                         out_ids_dev, out_d_dev, out_len_dev, status_dev, stream));
+}
+inline std::vector<SearchResult> Hnsw::search_many_ranged(const std::vector<const float *> &queries, const SearchParameters &sp,
+                                                          uint64_t k, const Attribute &attr, const std::vector<uint32_t> &lo,
+                                                          const std::vector<uint32_t> &hi, bool strict) const {
+  if (k == 0) k = sp.number_of_candidates;  // the C call's "whole row"; the buffers are sized by it
+  if (k > sp.number_of_candidates) throw Error(PHNSW_E_INVALID, "search_many_ranged: k exceeds number_of_candidates");
+  return detail::ranged_rows(queries, c_->dim(), k, lo, hi, "search_many_ranged",
+                             [&](const float *q, uint64_t nq, uint64_t *ids, float *d, uint64_t *len) {
+                               check(phnsw_search_batch_ranged(ix_, attr.handle(), q, nullptr, nq, &sp, 0, nullptr, lo.data(),
+                                                               hi.data(), strict ? PHNSW_FILTER_STRICT : 0u, k, ids, d, len,
+                                                               nullptr));
+                             });
+}
+inline void Hnsw::search_batch_ranged_device(const Attribute &attr, const float *queries_dev, uint32_t ldq,
+                                             const uint32_t *qids_dev, uint64_t nq, const SearchParameters &sp,
+                                             uint32_t upto_layers, const uint32_t *exclude_dev, const uint32_t *lo_dev,
+                                             const uint32_t *hi_dev, bool strict, uint32_t *out_ids_dev, float *out_d_dev,
+                                             uint32_t *out_len_dev, uint32_t *out_stats_dev, uint32_t *status_dev,
+                                             void *stream) const {
+  check(phnsw_search_batch_ranged_device(ix_, attr.handle(), queries_dev, ldq, qids_dev, nq, &sp, upto_layers, exclude_dev, lo_dev,
+                                         hi_dev, strict ? PHNSW_FILTER_STRICT : 0u, out_ids_dev, out_d_dev, out_len_dev,
+                                         out_stats_dev, status_dev, stream));
+}
+inline std::vector<SearchResult> Hnsw::search_many_ranged_auto(const std::vector<const float *> &queries,
+                                                               const SearchParameters &sp, uint64_t k, const Attribute &attr,
+                                                               const std::vector<uint32_t> &lo, const std::vector<uint32_t> &hi,
+                                                               uint64_t scan_below, std::vector<uint32_t> *routes) const {
+  if (k == 0 || k > sp.number_of_candidates)
+    throw Error(PHNSW_E_INVALID, "search_many_ranged_auto: k must be 1..number_of_candidates");
+  if (routes) routes->assign(queries.size(), 0u);
+  return detail::ranged_rows(queries, c_->dim(), k, lo, hi, "search_many_ranged_auto",
+                             [&](const float *q, uint64_t nq, uint64_t *ids, float *d, uint64_t *len) {
+                               check(phnsw_search_ranged_auto(ix_, attr.handle(), q, nullptr, nq, &sp, nullptr, lo.data(), hi.data(),
+                                                              k, scan_below, ids, d, len, routes ? routes->data() : nullptr));
+                             });
+}
+inline void Hnsw::search_ranged_auto_device(const Attribute &attr, const float *queries_dev, uint32_t ldq,
+                                            const uint32_t *qids_dev, uint64_t nq, const SearchParameters &sp,
+                                            const uint32_t *exclude_dev, const uint32_t *lo_dev, const uint32_t *hi_dev, uint64_t k,
+                                            uint64_t scan_below, uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                            uint32_t *out_route_dev, uint32_t *status_dev, void *stream) const {
+  check(phnsw_search_ranged_auto_device(ix_, attr.handle(), queries_dev, ldq, qids_dev, nq, &sp, exclude_dev, lo_dev, hi_dev, k,
+                                        scan_below, out_ids_dev, out_d_dev, out_len_dev, out_route_dev, status_dev, stream));
 }
 
 // QuantizedHnsw  pq.rs:120-131, 287-364 (per-sub-space codebooks, u8 codes)

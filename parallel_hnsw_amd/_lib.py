@@ -158,6 +158,19 @@ SYMBOLS = {
     "phnsw_search_labeled_auto": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
     "phnsw_search_labeled_auto_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp,
                                                 _vp, _vp, _vp]),
+    "phnsw_attr_create": (_i32, [_vp, _vp, _u64, _pp]),
+    "phnsw_attr_create_device": (_i32, [_vp, _vp, _u64, _vp, _pp]),
+    "phnsw_attr_info": (_i32, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u32), C.POINTER(_u32)]),
+    "phnsw_attr_count_device": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp]),
+    "phnsw_attr_destroy": (None, [_vp]),
+    "phnsw_search_exact_ranged": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "phnsw_search_exact_ranged_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "phnsw_search_batch_ranged": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _u32, _u64, _vp, _vp, _vp, _vp]),
+    "phnsw_search_batch_ranged_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _vp,
+                                                _vp, _vp, _vp]),
+    "phnsw_search_ranged_auto": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
+    "phnsw_search_ranged_auto_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp,
+                                               _vp, _vp, _vp]),
     "phnsw_search_batch_labelset": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _u32, _u64, _vp, _vp, _vp, _vp]),
     "phnsw_search_batch_labelset_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _u64, _u32, _vp,
                                                   _vp, _vp, _vp, _vp, _vp]),

@@ -1,5 +1,6 @@
 // The scratch set of the filtered and exact calls, written once: filter_auto.hip, filter_dense.hip, filter_grouped.hip
-// and filter_labeled.hip each derive their set from PhCallSet and keep only their own blocks on top of it.
+// and filter_labeled.hip each derive their set from PhCallSet and keep only their own blocks on top of it
+// (filter_ranged.hip uses the labels' set, list_scan.h).
 //
 // A set is kept with its owner (an index's PhCallPool per kind of call, or a labels handle's), one per call in flight.
 // The rule all of this serves: nothing goes back to the pool while work that uses it may still be enqueued, whichever
@@ -55,8 +56,8 @@ struct PhSetGuard {
   }
 };
 
-// The acquire of the index's pools: any set not in use, else a new one.  (The labels handle has a policy of its own,
-// filter_labeled.hip.)
+// The acquire of the index's pools: any set not in use, else a new one.  (The handles -- labels, attribute -- have a
+// policy of their own, ph_handle_set_acquire in list_scan.h.)
 template <class Set>
 Set *ph_set_acquire(PhCallPool &pool) {
   std::lock_guard<std::mutex> g(pool.mutex);

@@ -1,6 +1,7 @@
 // The running top-k of (distance, id) keys that the exact calls over an allow-list keep per wave, what feeds it and what
 // is written from it, and the block-level scan and sum of their list builders: everything the kernels of
-// filter_exact.hip, filter_dense.hip, filter_grouped.hip and filter_labeled.hip have in common, written once.
+// filter_exact.hip, filter_dense.hip, filter_grouped.hip, filter_labeled.hip and filter_ranged.hip have in common, written
+// once.
 // Device code; the keys are mkkey's (phnsw_device.h), distinct because the id is part of the key.
 #pragma once
 #include "phnsw_device.h"

@@ -26,6 +26,11 @@
 //   3. the walk is the search kernels' set mode
 //   4. "exclude[q] is a candidate" is ph_auto_set_candidate, the membership predicate of the walk
 //   5. the scan is the subset form of the scan by set (PhLabelsetCall with a list): its claim runs over the whole batch
+// ... or BY A NUMERIC RANGE (phnsw_search_ranged_auto[_device]: a phnsw_attr handle, lo[q] and hi[q]):
+//   1. the counts are the lengths of the spans (ph_attr_count): no bitmap is made or counted
+//   3. the walk is the search kernels' range mode over the handle's column
+//   4. "exclude[q] is a candidate" is ph_auto_range_candidate, the predicate of the walk
+//   5. the scan is filter_ranged.hip's, over the scan list (PhRangedCall::list)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -50,6 +55,8 @@ struct PhAutoArgs {
   const uint32_t *label_of, *want;  // a call by label: the handle's column [n] and want [nq]; else nullptr
   // a call by set: the column, want == nullptr and the table (graph-list queries have sound ranges: their counts are not 0)
   const uint32_t *set_first, *set_values;
+  // a call by range: the handle's column [n] and the bounds [nq]; else nullptr
+  const uint32_t *attr_of, *range_lo, *range_hi;
   // the index's bottom layer, as the candidate test takes it
   uint32_t n_nodes;
   const uint32_t *nodes, *vec2node;
@@ -137,7 +144,9 @@ __global__ __launch_bounds__(64) void ph_auto_finish_kernel(PhAutoArgs a) {
     if (lane == 0) {
       const uint32_t *const bitmap = a.filter ? a.filter + (uint64_t)q * a.filter_stride : nullptr;
       bool ex_cand;
-      if (a.set_first)
+      if (a.attr_of)
+        ex_cand = ph_auto_range_candidate(a.attr_of, a.n, a.range_lo[q], a.range_hi[q], ex, PHNSW_ATTR_NONE);
+      else if (a.set_first)
         ex_cand = ph_auto_set_candidate(a.label_of, a.n, a.set_first[q], a.set_first[q + 1u], a.set_values, ex, PHNSW_LABEL_NONE);
       else if (a.label_of)
         ex_cand = ph_auto_label_candidate(a.label_of, a.n, a.want[q], ex, PHNSW_LABEL_NONE);
@@ -173,7 +182,8 @@ int auto_run(const phnsw_index *ix, const PhAutoCall &c, PhAutoSet &set) {
   const uint64_t nq = c.nq;
   const uint32_t ef = (uint32_t)c.sp->number_of_candidates;
   const bool by_label = c.labels != nullptr, by_set = by_label && c.want_first != nullptr;
-  const bool per_query = by_label || (c.filter.words && c.filter.stride != 0u);
+  const bool by_range = c.attr != nullptr;
+  const bool per_query = by_label || by_range || (c.filter.words && c.filter.stride != 0u);
   PH_TRY(set.ready());
   if (!set.h_head) PH_HIP(hipHostMalloc((void **)&set.h_head, PH_AUTO_HEAD_WORDS * 4u, hipHostMallocDefault));
   // (a call by set: the claim's owner words [nwant] behind everything else)
@@ -185,7 +195,9 @@ int auto_run(const phnsw_index *ix, const PhAutoCall &c, PhAutoSet &set) {
   uint32_t *const walk_len = route_own + nq, *const walk_ids = walk_len + nq;
   float *const walk_d = (float *)(walk_ids + nq * ef);
 
-  if (by_set)
+  if (by_range)
+    PH_TRY(ph_attr_count(c.attr, c.range_lo, c.range_hi, nq, counts, c.stream));
+  else if (by_set)
     PH_TRY(ph_labels_count_set(c.labels, c.want_first, c.want_values, nq, c.nwant, counts, head + words, c.stream));
   else if (by_label)
     PH_TRY(ph_labels_count(c.labels, c.want, nq, counts, c.stream));
@@ -193,7 +205,8 @@ int auto_run(const phnsw_index *ix, const PhAutoCall &c, PhAutoSet &set) {
     PH_TRY(ph_filter_count(ix, c.filter, nb, counts, c.stream));
   PhAutoArgs a = {};
   a.nq = (uint32_t)nq, a.n = (uint32_t)s->n, a.k = c.k, a.ef = ef;
-  a.scan_below = by_set ? ph_auto_scan_below_labelset(c.scan_below)
+  a.scan_below = by_range ? ph_auto_scan_below_ranged(c.scan_below)
+                 : by_set ? ph_auto_scan_below_labelset(c.scan_below)
                         : (by_label ? ph_auto_scan_below_labeled(c.scan_below) : ph_auto_scan_below(c.scan_below, per_query));
   a.qids = c.qids, a.exclude = c.exclude;
   PhFilter filter = c.filter;  // what the walk gets
@@ -205,6 +218,11 @@ int auto_run(const phnsw_index *ix, const PhAutoCall &c, PhAutoSet &set) {
       filter.set_first = a.set_first = c.want_first, filter.set_values = a.set_values = c.want_values;
       filter.set_nwant = (uint32_t)c.nwant;
     }
+  }
+  if (by_range) {
+    filter = PhFilter{};
+    filter.attr_of = a.attr_of = ph_attr_column(c.attr);
+    filter.range_lo = a.range_lo = c.range_lo, filter.range_hi = a.range_hi = c.range_hi;
   }
   a.filter = filter.words, a.filter_stride = filter.words ? filter.stride : 0u, a.per_query = per_query ? 1u : 0u;
   ph_exact_bottom_layer(ix, &a.n_nodes, &a.nodes, &a.vec2node);
@@ -233,7 +251,15 @@ int auto_run(const phnsw_index *ix, const PhAutoCall &c, PhAutoSet &set) {
     PH_HIP(hipStreamSynchronize(c.stream));
     slen = std::min<uint64_t>(set.h_head[1], nq);
   }
-  if (slen && by_set) {
+  if (slen && by_range) {
+    PhRangedCall x = {};
+    x.queries = c.queries, x.ldq = c.ldq, x.qids = c.qids, x.exclude = c.exclude, x.lo = c.range_lo, x.hi = c.range_hi;
+    x.nq = slen, x.list = slist;
+    x.k = c.k;
+    x.out_ids = c.out_ids, x.out_d = c.out_d, x.out_len = c.out_len, x.status = c.status;
+    x.stream = c.stream;
+    PH_TRY(ph_ranged_device(ix, c.attr, x));
+  } else if (slen && by_set) {
     PhLabelsetCall sx = {};
     PhLabeledCall &x = sx.c;
     x.queries = c.queries, x.ldq = c.ldq, x.qids = c.qids, x.exclude = c.exclude;
@@ -322,12 +348,18 @@ extern "C" int phnsw_search_filtered_auto_device(const phnsw_index *ix, const fl
 } catch (...) { return ph_caught(); }
 
 // the host form of the three descriptions; lb != nullptr: by label (want: host words [nq]; filter unused) or, with
-// want_first, by set (want_first [nq + 1], want_values: host words; want unused), else by bitmap
+// want_first, by set (want_first [nq + 1], want_values: host words; want unused), else by bitmap; at != nullptr: by range
+// (range_lo, range_hi: host words [nq]; lb and filter unused)
 static int auto_host(const char *call, const phnsw_index *ix, const phnsw_labels *lb, const float *queries, const uint64_t *qids,
                      uint64_t nq, const phnsw_search_params *sp, const uint64_t *exclude, const uint32_t *filter,
                      uint32_t filter_stride_words, const uint32_t *want, const uint32_t *want_first, const uint32_t *want_values,
-                     uint64_t k, uint64_t scan_below, uint64_t *out_ids, float *out_d, uint64_t *out_len, uint32_t *out_route) {
+                     uint64_t k, uint64_t scan_below, uint64_t *out_ids, float *out_d, uint64_t *out_len, uint32_t *out_route,
+                     const phnsw_attr *at = nullptr, const uint32_t *range_lo = nullptr, const uint32_t *range_hi = nullptr) {
   const bool by_set = lb && want_first;
+  if (at && (!range_lo || !range_hi || nq > 0x7FFFFFFEull)) {
+    ph_set_error("%s: invalid argument (lo and hi; nq < 2^31 - 1)", call);
+    return PHNSW_E_INVALID;
+  }
   if (!ph_auto_queries_valid(queries != nullptr, qids != nullptr) || !out_ids || !out_d || !out_len || !ph_auto_nq_valid(nq) ||
       (lb && ((!want && !want_first) || nq > 0x7FFFFFFEull))) {
     ph_set_error("%s: invalid argument (queries or qids, exactly one; outputs%s)", call, lb ? "; want; nq < 2^31 - 1" : "");
@@ -339,7 +371,7 @@ static int auto_host(const char *call, const phnsw_index *ix, const phnsw_labels
     return PHNSW_E_INVALID;
   }
   PhFilter hf = {};
-  if (!lb) PH_TRY(ph_filter_check(ix, filter, filter_stride_words, 0u, call, &hf));
+  if (!lb && !at) PH_TRY(ph_filter_check(ix, filter, filter_stride_words, 0u, call, &hf));
   const phnsw_store *s = ix->store;
   if (by_set) {  // as the walk and the scan by set refuse them: naming the call and the query
     PH_TRY(ph_stored_ids_check(qids, nq, s->n, call, true));
@@ -357,12 +389,17 @@ static int auto_host(const char *call, const phnsw_index *ix, const phnsw_labels
   phnsw_index *mix = const_cast<phnsw_index *>(ix);
   PhAutoSet *set = ph_set_acquire<PhAutoSet>(mix->autos);
   PhHostCall h(mix->autos, set);
-  // extras: route | want, or for a call by set want_first [nq + 1] | want_values [nwant]
-  PH_TRY(h.stage_in(s, queries, qids, exclude, nq, (size_t)nq * 2u + (by_set ? 1u + (size_t)nwant : 0u), 1, (uint32_t)k, (uint32_t)k));
+  // extras: route | want, or for a call by set want_first [nq + 1] | want_values [nwant], or for a call by range lo | hi
+  PH_TRY(h.stage_in(s, queries, qids, exclude, nq, (size_t)nq * 3u + (by_set ? 1u + (size_t)nwant : 0u), 1, (uint32_t)k, (uint32_t)k));
   PhAutoCall c = {};
   h.fill(c);
   c.filter = hf;
-  if (by_set) {  // the description of a call by set: 4 * (nq + 1) + 4 * nwant bytes
+  if (at) {  // the description of a call by range: 8 bytes per query
+    uint32_t *const lo_dev = h.extra() + nq, *const hi_dev = lo_dev + nq;
+    PH_HIP(hipMemcpyAsync(lo_dev, range_lo, (size_t)nq * 4u, hipMemcpyHostToDevice, h.st));
+    PH_HIP(hipMemcpyAsync(hi_dev, range_hi, (size_t)nq * 4u, hipMemcpyHostToDevice, h.st));
+    c.attr = at, c.range_lo = lo_dev, c.range_hi = hi_dev;
+  } else if (by_set) {  // the description of a call by set: 4 * (nq + 1) + 4 * nwant bytes
     uint32_t *const first_dev = h.extra() + nq, *const values_dev = first_dev + nq + 1u;
     PH_HIP(hipMemcpyAsync(first_dev, want_first, (size_t)(nq + 1u) * 4u, hipMemcpyHostToDevice, h.st));
     if (nwant) PH_HIP(hipMemcpyAsync(values_dev, want_values, (size_t)nwant * 4u, hipMemcpyHostToDevice, h.st));
@@ -486,6 +523,46 @@ extern "C" int phnsw_search_labelset_auto_device(const phnsw_index *ix, const ph
   }
   PhAutoCall c = {};
   c.labels = lb, c.want_first = want_first_dev, c.want_values = want_values_dev, c.nwant = nwant;
+  c.queries = queries_dev, c.ldq = ldq, c.qids = qids_dev, c.exclude = exclude_dev, c.nq = nq, c.sp = sp;
+  c.k = (uint32_t)k, c.scan_below = scan_below;
+  c.out_ids = out_ids_dev, c.out_d = out_d_dev, c.out_len = out_len_dev, c.out_route = out_route_dev, c.status = status_dev;
+  c.stream = (hipStream_t)stream;
+  PH_HIP(hipSetDevice(ix->store->device));
+  return ph_auto_device(ix, c);
+} catch (...) { return ph_caught(); }
+
+// ---- by a numeric range
+
+extern "C" int phnsw_search_ranged_auto(const phnsw_index *ix, const phnsw_attr *at, const float *queries, const uint64_t *qids,
+                                        uint64_t nq, const phnsw_search_params *sp, const uint64_t *exclude, const uint32_t *lo,
+                                        const uint32_t *hi, uint64_t k, uint64_t scan_below, uint64_t *out_ids, float *out_d,
+                                        uint64_t *out_len, uint32_t *out_route) try {
+  const char *const call = "phnsw_search_ranged_auto";
+  PH_TRY(auto_check(ix, sp, k, call));
+  PH_TRY(ph_ranged_check(ix, at, k, call));
+  if (nq == 0) return 0;
+  return auto_host(call, ix, nullptr, queries, qids, nq, sp, exclude, nullptr, 0u, nullptr, nullptr, nullptr, k, scan_below, out_ids,
+                   out_d, out_len, out_route, at, lo, hi);
+} catch (...) { return ph_caught(); }
+
+extern "C" int phnsw_search_ranged_auto_device(const phnsw_index *ix, const phnsw_attr *at, const float *queries_dev, uint32_t ldq,
+                                               const uint32_t *qids_dev, uint64_t nq, const phnsw_search_params *sp,
+                                               const uint32_t *exclude_dev, const uint32_t *lo_dev, const uint32_t *hi_dev,
+                                               uint64_t k, uint64_t scan_below, uint32_t *out_ids_dev, float *out_d_dev,
+                                               uint32_t *out_len_dev, uint32_t *out_route_dev, uint32_t *status_dev,
+                                               void *stream) try {
+  const char *const call = "phnsw_search_ranged_auto_device";
+  PH_TRY(auto_check(ix, sp, k, call));
+  PH_TRY(ph_ranged_check(ix, at, k, call));
+  if (nq == 0) return 0;
+  if (!ph_device_queries_ok(ix, queries_dev, qids_dev, ldq) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev ||
+      !lo_dev || !hi_dev || !ph_auto_nq_valid(nq) || nq > 0x7FFFFFFEull) {
+    ph_set_error("%s: invalid argument (queries or qids, exactly one; outputs; lo and hi; queries need ldq >= store ld, "
+                 "multiple of 4, 16-byte base)", call);
+    return PHNSW_E_INVALID;
+  }
+  PhAutoCall c = {};
+  c.attr = at, c.range_lo = lo_dev, c.range_hi = hi_dev;
   c.queries = queries_dev, c.ldq = ldq, c.qids = qids_dev, c.exclude = exclude_dev, c.nq = nq, c.sp = sp;
   c.k = (uint32_t)k, c.scan_below = scan_below;
   c.out_ids = out_ids_dev, c.out_d = out_d_dev, c.out_len = out_len_dev, c.out_route = out_route_dev, c.status = status_dev;

@@ -14,10 +14,11 @@
 //                 the queries of one label are adjacent positions; ph_labeled_tileflag_kernel, exclusive sum,
 //                 ph_labeled_tiles_kernel: the tile table and its count, on the device
 //              2. ph_labeled_scan_kernel: one wave64 per (position, slice of its list); ids 64 at a time from the
-//                 posting list into dist.batch of the store's policy -- every store kind, and T = 1
+//                 posting list into dist.batch of the store's policy (ph_list_scan, list_scan.h: the loop the scan by
+//                 range, filter_ranged.hip, runs over its spans) -- every store kind, and T = 1
 //              3. ph_labeled_tile_kernel (f32 / f16 / i8 row stores, T > 1): one wave64 per (tile of up to T queries of
 //                 ONE label, slice of that label's list); every candidate row is read once for the whole tile
-//                 ph_labeled_merge_kernel: the slices' lists of a position through the same running top-k
+//                 ph_list_merge_kernel (list_scan.h): the slices' lists of a position through the same running top-k
 //
 // Equality with phnsw_search_exact_filtered over the bitmap {v : labels[v] == want[q]}: the candidate sets are equal by
 // the definition above, the keys are distinct, so the k smallest are one set in one order however the list is cut; the
@@ -54,6 +55,7 @@
 #include "host_call.h"
 #include "label_plan.h"
 #include "labelset_plan.h"
+#include "list_scan.h"
 #include "phnsw_device.h"
 
 struct phnsw_labels {
@@ -72,16 +74,7 @@ struct phnsw_labels {
 
 // ------------------------------------------------------------------ construction
 
-__global__ __launch_bounds__(256) void ph_label_key_kernel(const uint32_t *labels, uint32_t n, uint32_t n_nodes,
-                                                           const uint32_t *nodes, const uint32_t *vec2node, uint32_t *keys,
-                                                           uint32_t *iota) {
-  const uint32_t nlim = ph_exact_id_limit(n, n_nodes, nodes, vec2node);
-  for (uint64_t v = (uint64_t)blockIdx.x * 256u + threadIdx.x; v < n; v += (uint64_t)gridDim.x * 256u) {
-    const bool listed = v < nlim && (!vec2node || vec2node[v] != PH_EMPTY32);
-    keys[v] = listed ? labels[v] : PHNSW_LABEL_NONE;
-    iota[v] = (uint32_t)v;
-  }
-}
+// (ph_label_key_kernel: list_scan.h, shared with the attribute handle)
 
 // flags [n + 1]: 1 where a label starts (NONE sorts last and starts nothing); head[1] = listed, the first NONE position
 __global__ __launch_bounds__(256) void ph_label_flags_kernel(const uint32_t *skeys, uint32_t n, uint32_t *flags, uint32_t *head) {
@@ -184,40 +177,13 @@ __global__ __launch_bounds__(64) void ph_labeled_scan_kernel(PhLabeledArgs a) {
       dist.prepare_raw(a.dist, a.queries + (uint64_t)q * a.ldq, labeled_lds, lane);
     else if (!bad_query)
       dist.prepare_stored(a.dist, a.qids[q], labeled_lds, lane);
-    PhExactTopK top;
-    top.init(keys, a.k);
-    const uint32_t ex = a.exclude ? a.exclude[q] : PH_EMPTY32;
     const uint32_t at = s == PH_LABEL_SLOT_NONE ? 0u : a.first[s];
     const uint32_t len = s == PH_LABEL_SLOT_NONE ? 0u : a.first[s + 1u] - at;  // a bad query's slot is NONE
-    const uint32_t *const list = a.ids + at;
-    uint64_t b0, b1;
-    ph_label_slice_range(slice, a.slices, len, &b0, &b1);
-    for (uint64_t b = b0; b < b1; b++) {
-      const uint32_t j = (uint32_t)b * PH_LABEL_BATCH + lane;
-      const bool ok = j < len;
-      const uint32_t id = ok ? list[j] : 0u;  // a listed id: a row of the store
-      const float d = dist.batch(a.dist, __ballot(ok), id, lane);
-      top.insert(ok && id != ex ? mkkey(d, id) : KEY_NONE, lane);
-    }
-    ph_exact_write_slice<PAIRS>(a, q, pos, slice, top.cur, top.len, bad_query, lane);
+    ph_list_scan<PAIRS>(a, dist, keys, a.ids + at, len, q, pos, slice, bad_query, lane);  // list_scan.h
   }
 }
 
-// One wave per position: the slices' ascending lists merged through the same running top-k (PH_EXACT_FEED).
-__global__ __launch_bounds__(64) void ph_labeled_merge_kernel(PhLabeledArgs a) {
-  extern __shared__ float labeled_lds[];
-  const uint32_t lane = threadIdx.x;
-  uint64_t *const keys = (uint64_t *)labeled_lds;
-  for (uint32_t pos = blockIdx.x; pos < a.nq; pos += gridDim.x) {
-    const uint32_t q = a.order[pos];
-    __syncthreads();
-    PhExactTopK top;
-    top.init(keys, a.k);
-    for (uint32_t s = 0; s < a.slices; s++)
-      PH_EXACT_FEED(top, a.scratch + ((uint64_t)pos * a.slices + s) * a.k, a.k, lane);
-    ph_exact_write_row(a, q, top.cur, top.len, !a.queries && a.qids[q] >= a.n, lane);
-  }
-}
+// (the merge of the slices' lists: ph_list_merge_kernel, list_scan.h)
 
 // ------------------------------------------------------------------ a SET of labels per query: pairs (labelset_plan.h)
 
@@ -284,7 +250,7 @@ __device__ __forceinline__ bool ph_labelset_query_ok(const PhLabelsetArgs &s, ui
 }
 
 // One wave per query: the lists of every position of its pairs -- duplicates and slot-less pairs left out -- through the
-// same running top-k as ph_labeled_merge_kernel, so ties across lists fall in id order.  A refused query (labelset_plan.h)
+// same running top-k as ph_list_merge_kernel, so ties across lists fall in id order.  A refused query (labelset_plan.h)
 // gets the empty row and status ST_LABELSET_RANGE.
 #define ST_LABELSET_RANGE 8u
 __global__ __launch_bounds__(64) void ph_labelset_merge_kernel(PhLabelsetArgs s) {
@@ -540,67 +506,30 @@ static PhLabeledFn labeled_tile_fn(const phnsw_store *s, bool pairs) {
   }
 }
 
-// A PhCallSet (call_set.h) kept with the HANDLE, not the index.
-struct PhLabeledSet : PhCallSet {
-  void *pre = nullptr, *tmp = nullptr, *keys = nullptr;
-  size_t pre_bytes = 0, tmp_bytes = 0, keys_bytes = 0;
-  uint64_t tmp_nq = 0;  // the batch size tmp_need was asked of hipCUB for (0: none yet)
-  size_t tmp_need = 0;
-};
-
-namespace {
-
-const size_t PH_LABEL_SETS = 4;  // scratch sets a handle makes before calls share one behind its event
-
-// own_stream: the host form, which runs on the set's own stream (`stream` is then ignored)
-PhLabeledSet *set_acquire(phnsw_labels *lb, hipStream_t stream, bool own_stream) {
-  // First a set whose last call ran on this very stream: stream order already protects it, so back-to-back calls on one
-  // stream share one set however far the device is behind.  Then a set whose last call has finished.  Then, while fewer
-  // than PH_LABEL_SETS exist, a new one, so that calls on different streams overlap; past that a free set whose event
-  // the call's stream waits for.  A handle so holds at most max(PH_LABEL_SETS, calls inside the library at once) sets,
-  // each as large as the largest call it served, until phnsw_labels_destroy.
-  std::lock_guard<std::mutex> g(lb->pool.mutex);
-  if (!own_stream)
-    for (PhCallSet *s : lb->pool.sets)
-      if (!s->in_use && !s->stream && s->has_last && s->last == stream) {
-        s->in_use = true;
-        return static_cast<PhLabeledSet *>(s);
-      }
-  PhCallSet *busy = nullptr;
-  for (PhCallSet *s : lb->pool.sets) {
-    if (s->in_use) continue;
-    if (!s->done || hipEventQuery(s->done) == hipSuccess) {
-      s->in_use = true;
-      return static_cast<PhLabeledSet *>(s);
-    }
-    busy = s;
-  }
-  (void)hipGetLastError();  // hipErrorNotReady of the query is no error of the call
-  if (busy && lb->pool.sets.size() >= PH_LABEL_SETS) {
-    busy->in_use = true;
-    return static_cast<PhLabeledSet *>(busy);
-  }
-  PhLabeledSet *s = new PhLabeledSet();
-  s->in_use = true;
-  lb->pool.sets.push_back(s);
-  return s;
+// (PhLabeledSet, the scratch set kept with the handle, and its acquire: list_scan.h)
+static PhLabeledSet *set_acquire(phnsw_labels *lb, hipStream_t stream, bool own_stream) {
+  return ph_handle_set_acquire(lb->pool, stream, own_stream);
 }
 
-}  // namespace
-
-// the handle test every call by label makes (ix has layers)
-int ph_labels_fresh(const phnsw_index *ix, const phnsw_labels *lb, const char *call) {
-  if (!lb) {
-    ph_set_error("%s: null labels", call);
+// the snapshot test of a handle, written once for phnsw_labels and phnsw_attr
+int ph_snapshot_fresh(const phnsw_index *ix, bool present, const phnsw_index *h_ix, uint64_t h_n, uint32_t h_nodes, const char *what,
+                      const char *call) {
+  if (!present) {
+    ph_set_error("%s: null %s", call, what);
     return PHNSW_E_INVALID;
   }
-  if (lb->ix != ix || lb->n != ix->store->n || lb->n_nodes != ix->layers.back().n_nodes) {
-    ph_set_error("%s: the labels are stale: made for %s (%llu vectors, %u bottom-layer nodes then; %llu and %u now); make a "
-                 "new handle", call, lb->ix != ix ? "another index" : "this index before it changed", (unsigned long long)lb->n,
-                 lb->n_nodes, (unsigned long long)ix->store->n, ix->layers.back().n_nodes);
+  if (h_ix != ix || h_n != ix->store->n || h_nodes != ix->layers.back().n_nodes) {
+    ph_set_error("%s: the %s are stale: made for %s (%llu vectors, %u bottom-layer nodes then; %llu and %u now); make a "
+                 "new handle", call, what, h_ix != ix ? "another index" : "this index before it changed", (unsigned long long)h_n,
+                 h_nodes, (unsigned long long)ix->store->n, ix->layers.back().n_nodes);
     return PHNSW_E_INVALID;
   }
   return 0;
+}
+
+// the handle test every call by label makes (ix has layers)
+int ph_labels_fresh(const phnsw_index *ix, const phnsw_labels *lb, const char *call) {
+  return ph_snapshot_fresh(ix, lb != nullptr, lb ? lb->ix : nullptr, lb ? lb->n : 0u, lb ? lb->n_nodes : 0u, "labels", call);
 }
 
 // index, k, handle, store: the checks every exact form makes before it looks at another argument, in this order
@@ -731,7 +660,7 @@ int labeled_run(const phnsw_index *ix, const phnsw_labels *lb, const PhLabeledCa
   PH_TRY(labeled_sort(set, a, ln, c.stream));
   PH_TRY(labeled_scan(set, a, ln, c.stream));
   if (a.slices > 1u) {
-    hipLaunchKernelGGL(ph_labeled_merge_kernel, dim3((uint32_t)std::min<uint64_t>(nq, 1u << 20)), dim3(64),
+    hipLaunchKernelGGL(ph_list_merge_kernel<PhLabeledArgs>, dim3((uint32_t)std::min<uint64_t>(nq, 1u << 20)), dim3(64),
                        (size_t)ph_label_scan_lds(c.k), c.stream, a);
     PH_HIP(hipGetLastError());
   }
@@ -794,11 +723,7 @@ int labelset_run(const phnsw_index *ix, const phnsw_labels *lb, const PhLabelset
 }
 
 void labels_free(phnsw_labels *lb) {
-  ph_sets_free<PhLabeledSet>(lb->pool, [](PhLabeledSet &s) {
-    if (s.pre) ph_pool_free(s.pre);
-    if (s.tmp) ph_pool_free(s.tmp);
-    if (s.keys) ph_pool_free(s.keys);
-  });
+  ph_handle_sets_free(lb->pool);
   if (lb->values) hipFree(lb->values);
   if (lb->first) hipFree(lb->first);
   if (lb->ids) hipFree(lb->ids);
@@ -1167,10 +1092,12 @@ int walk_check(const phnsw_index *ix, const phnsw_labels *lb, const phnsw_search
   return 0;
 }
 
-// The run of both host walks (by label, by set) once everything is staged: the launch, the words back, and the queries
+}  // namespace
+
+// The run of the host walks (by label, by set, by range: list_scan.h) once everything is staged: the launch, the words back, and the queries
 // whose frontier spill overflowed (status 5) again from a device list with 8x the room, as ph_search_host re-runs them;
 // then the rows and the stats (the first two extra words of `small`).  redo_dev: nq words of the staging.
-int walk_host_run(const phnsw_index *ix, PhHostCall &h, PhSearchCall &c, uint32_t *redo_dev, uint32_t ef, uint64_t *out_ids,
+int ph_walk_host_run(const phnsw_index *ix, PhHostCall &h, PhSearchCall &c, uint32_t *redo_dev, uint32_t ef, uint64_t *out_ids,
                   float *out_d, uint64_t *out_len, uint64_t *out_stats) {
   const uint64_t nq = h.nq;
   std::vector<uint32_t> &redo = h.h_list;  // read by a copy: kept by h, changed only behind the next sync
@@ -1202,8 +1129,6 @@ int walk_host_run(const phnsw_index *ix, PhHostCall &h, PhSearchCall &c, uint32_
     for (uint64_t i = 0; i < 2u * nq; i++) out_stats[i] = h.read_extra(0, i);
   return 0;
 }
-
-}  // namespace
 
 extern "C" int phnsw_search_batch_labeled_device(const phnsw_index *ix, const phnsw_labels *lb, const float *queries_dev,
                                                  uint32_t ldq, const uint32_t *qids_dev, uint64_t nq,
@@ -1268,7 +1193,7 @@ extern "C" int phnsw_search_batch_labeled(const phnsw_index *ix, const phnsw_lab
   PH_HIP(hipMemcpyAsync(want_dev, want, (size_t)nq * 4u, hipMemcpyHostToDevice, h.st));
   c.filter.label_of = lb->label_of, c.filter.want = want_dev, c.filter.flags = flags;
   c.sp = sp, c.upto = upto_layers, c.out_stats = h.extra();
-  return walk_host_run(ix, h, c, redo_dev, ef, out_ids, out_d, out_len, out_stats);
+  return ph_walk_host_run(ix, h, c, redo_dev, ef, out_ids, out_d, out_len, out_stats);
 } catch (...) { return ph_caught(); }
 
 // ------------------------------------------------------------------ the graph walk by a set of labels
@@ -1359,5 +1284,5 @@ extern "C" int phnsw_search_batch_labelset(const phnsw_index *ix, const phnsw_la
   c.filter.label_of = lb->label_of, c.filter.flags = flags;
   c.filter.set_first = first_dev, c.filter.set_values = values_dev, c.filter.set_nwant = (uint32_t)nwant;
   c.sp = sp, c.upto = upto_layers, c.out_stats = h.extra();
-  return walk_host_run(ix, h, c, redo_dev, ef, out_ids, out_d, out_len, out_stats);
+  return ph_walk_host_run(ix, h, c, redo_dev, ef, out_ids, out_d, out_len, out_stats);
 } catch (...) { return ph_caught(); }

@@ -49,6 +49,26 @@ PH_ROUTE_HD static inline bool ph_auto_label_candidate(const uint32_t *label_of,
   return v < n && want != none_label && label_of[v] == want;
 }
 
+// ---- a numeric range per query (phnsw_search_batch_ranged, phnsw_search_ranged_auto): attr_of [n] holds the key of a
+// listed vector and none_key elsewhere; a vector passes iff lo <= key <= hi and the key is a value.  Used by the search
+// kernels' range mode (search_kernels.h), by filter_auto.hip and by tests/cpp/test_range_plan.cpp.
+// scan_below == 0 of the routed call by range: UNMEASURED.  This is the one-label figure above; the range scan has no
+// tile path (the label tile path measured 2.2-3.6x faster than the per-query scan), so its crossover with the range walk
+// is expected BELOW this number.  scripts/bench_ranged.py --crossover measures it (profiles/ranged/README.md)
+#define PH_AUTO_SCAN_BELOW_RANGED 20000u
+PH_ROUTE_HD static inline uint64_t ph_auto_scan_below_ranged(uint64_t scan_below) {
+  return scan_below != 0u ? scan_below : PH_AUTO_SCAN_BELOW_RANGED;
+}
+// the range test of one key, the form the walk's lanes run
+PH_ROUTE_HD static inline bool ph_range_holds(uint32_t key, uint32_t lo, uint32_t hi, uint32_t none_key) {
+  return key >= lo && key <= hi && key != none_key;
+}
+// e of ph_auto_full_len for a call by range: exclude[q] is a candidate iff it is listed with a key inside [lo, hi]
+PH_ROUTE_HD static inline bool ph_auto_range_candidate(const uint32_t *attr_of, uint32_t n, uint32_t lo, uint32_t hi, uint32_t v,
+                                                       uint32_t none_key) {
+  return v < n && ph_range_holds(attr_of[v], lo, hi, none_key);
+}
+
 // ---- a SET of labels per query (phnsw_search_batch_labelset, phnsw_search_labelset_auto): want_first [nq + 1] offsets
 // into want_values [nwant].  Used by the search kernels' set mode (search_kernels.h), by filter_auto.hip and by
 // tests/cpp/test_labelset_route.cpp.

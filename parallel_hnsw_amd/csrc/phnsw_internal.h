@@ -237,6 +237,9 @@ struct PhFilter {
   const uint32_t *label_of, *want;
   const uint32_t *set_first, *set_values;
   uint32_t set_nwant;
+  // ... or its range form: attr_of != nullptr, the column [n] of a phnsw_attr handle (PHNSW_ATTR_NONE where a vector is
+  // not listed), range_lo and range_hi [nq], the inclusive bounds of each query; nothing of the forms above goes with it
+  const uint32_t *attr_of, *range_lo, *range_hi;
 };
 
 // per-slice results of an exact scan that was cut into slices (filter_exact.hip): [nq][slices][k] keys from
@@ -411,6 +414,10 @@ struct PhSearchArgs {
   // is not inside [0, set_nwant] or runs backwards does not walk (status 8).  (At the end, like the pairs above.)
   const uint32_t *set_first, *set_values;
   uint32_t set_nwant;
+  // the filter by a numeric range of a row attribute (search_ranged.hip): attr_of [n], the key of every listed vector and
+  // PHNSW_ATTR_NONE elsewhere; range_lo / range_hi [nq], the inclusive bounds of query q.  nullptr = not a range launch;
+  // never with a bitmap, a label or a set, and never collecting.  (At the end, like the pairs above.)
+  const uint32_t *attr_of, *range_lo, *range_hi;
 };
 
 uint32_t ph_default_ovf_cap(uint32_t ef);
@@ -581,6 +588,10 @@ struct PhAutoCall {
   // candidates = the listed vectors of the labels of the query's range.  The offsets are not trusted
   const uint32_t *want_first, *want_values;
   uint64_t nwant;
+  // the range form (phnsw_search_ranged_auto): candidates = the listed vectors with range_lo[q] <= key <= range_hi[q];
+  // filter and labels are then unused
+  const phnsw_attr *attr;
+  const uint32_t *range_lo, *range_hi;  // [nq]
   uint32_t k;
   uint64_t scan_below;  // 0 = the library default, UINT64_MAX = always scan (filter_route.h)
   uint32_t *out_ids;    // [nq][k]
@@ -629,6 +640,30 @@ int ph_labeled_check(const phnsw_index *ix, const phnsw_labels *lb, uint64_t k, 
 const uint32_t *ph_labels_column(const phnsw_labels *lb);
 // out_count_dev[q] = the length of the list of want_dev[q] (phnsw_labels_count_device without its checks)
 int ph_labels_count(const phnsw_labels *lb, const uint32_t *want_dev, uint64_t nq, uint32_t *out_count_dev, hipStream_t stream);
+// The request of one exact top-k scan over the spans of a sorted attribute column (ph_ranged_device, filter_ranged.hip):
+// PhLabeledCall with the bounds lo, hi [nq] in place of want; list as there
+struct PhRangedCall {
+  const float *queries;
+  uint32_t ldq;
+  const uint32_t *qids, *exclude, *lo, *hi;
+  uint64_t nq;
+  uint32_t k;
+  uint32_t *out_ids;
+  float *out_d;
+  uint32_t *out_len, *status;
+  hipStream_t stream;
+  const uint32_t *list;
+};
+int ph_ranged_device(const phnsw_index *ix, const phnsw_attr *at, const PhRangedCall &c);
+// a null handle, one made for another index or before the index changed: PHNSW_E_INVALID, ph_labels_fresh's wording
+int ph_attr_fresh(const phnsw_index *ix, const phnsw_attr *at, const char *call);
+// ph_labeled_check for an attribute handle: the same checks in the same order
+int ph_ranged_check(const phnsw_index *ix, const phnsw_attr *at, uint64_t k, const char *call);
+// attr_of [n] of a handle: the key of every listed vector, PHNSW_ATTR_NONE elsewhere (device words)
+const uint32_t *ph_attr_column(const phnsw_attr *at);
+// out_count_dev[q] = the length of the span of [lo_dev[q], hi_dev[q]] (phnsw_attr_count_device without its checks)
+int ph_attr_count(const phnsw_attr *at, const uint32_t *lo_dev, const uint32_t *hi_dev, uint64_t nq, uint32_t *out_count_dev,
+                  hipStream_t stream);
 void ph_auto_free(phnsw_index *ix);
 void ph_dense_free(phnsw_index *ix);  // filter_dense.hip
 // the checks the table calls make before they look at another argument: index, k, store kind and row length

@@ -186,6 +186,7 @@ static PhKernelChoice pick_search_kernel(const phnsw_store *s, uint32_t ef_max, 
   if (mode == PH_FM_BITMAP && k.fn) k.fn = ph_pick_filtered_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
   if (mode == PH_FM_LABEL && k.fn) k.fn = ph_pick_labeled_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
   if (mode == PH_FM_LABELSET && k.fn) k.fn = ph_pick_labelset_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
+  if (mode == PH_FM_RANGE && k.fn) k.fn = ph_pick_ranged_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
   // the collecting twins: the new calls only (PhSearchArgs::collect_k), and only the last launch of their descent
   if (mode == (PH_FM_BITMAP | PH_FM_COLLECT) && k.fn)
     k.fn = ph_pick_collect_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
@@ -335,7 +336,9 @@ static int search_launch_dense(PhWorkspace &ws, PhSearchArgs &a, hipStream_t str
     ph_set_error("a collecting search has no dense-only launch");
     return PHNSW_E_UNSUPPORTED;
   }
-  ph_search_fn fn = mode == PH_FM_LABELSET
+  ph_search_fn fn = mode == PH_FM_RANGE
+                        ? ph_pick_ranged_dense(capc)
+                    : mode == PH_FM_LABELSET
                         ? ph_pick_labelset_dense(capc)
                         : (mode == PH_FM_LABEL ? ph_pick_labeled_dense(capc)
                                                : (mode == PH_FM_BITMAP ? ph_pick_filtered_dense(capc) : pick_kernel_dense<PH_FM_NONE>(capc)));
@@ -425,6 +428,12 @@ int ph_search_launch(const phnsw_index *ix, PhWorkspace &ws, PhSearchArgs &a, hi
   if (mode & PH_FM_LABELSET) {  // a set launch carries the column and the whole table, and nothing of the other modes
     if ((mode & PH_FM_COLLECT) || a.filter || a.label_want || !a.label_of || (!a.set_values && a.set_nwant)) {
       ph_set_error("a search by label sets takes the label column and the set table alone: no bitmap, no single label, not collecting");
+      return PHNSW_E_UNSUPPORTED;
+    }
+  }
+  if (mode & PH_FM_RANGE) {  // a range launch carries the attribute column and both bounds, and nothing of the other modes
+    if ((mode & PH_FM_COLLECT) || a.filter || a.label_of || a.label_want || a.set_first || !a.range_lo || !a.range_hi) {
+      ph_set_error("a search by range takes the attribute column and its two bounds alone: no bitmap, no label, no set, not collecting");
       return PHNSW_E_UNSUPPORTED;
     }
   }

@@ -2,8 +2,9 @@
 // translation units that instantiate them: search.hip the kernels as they always were, search_filtered.hip their bitmap
 // twins, the kernels of a search restricted to an allow-list of VectorIds, search_labeled.hip their label twins, the same
 // restriction read from a label column; search_collect.hip and search_collect_labeled.hip the collecting twins of those
-// two (PH_FM_COLLECT); search_labelset.hip the twins over a SET of labels per query (PH_FM_LABELSET).  Six units so that
-// they compile side by side.
+// two (PH_FM_COLLECT); search_labelset.hip the twins over a SET of labels per query (PH_FM_LABELSET); search_ranged.hip
+// the twins over a numeric range of an attribute column per query (PH_FM_RANGE).  Seven units so that they compile side
+// by side.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -103,17 +104,24 @@ __device__ __forceinline__ bool vis_insert(uint32_t *H, uint32_t slots, uint32_t
 //                 evaluated row.  The offsets are not trusted: a query whose range is not sound (filter_route.h) does
 //                 not walk -- ST_SET_RANGE, an empty row, stats 0 -- and nothing outside set_values[0 .. set_nwant) is
 //                 read.  Never with a bitmap or label_want, and there is no collecting twin.
+//   PH_FM_RANGE   an attribute column (a.attr_of) and two inclusive bounds per query (a.range_lo, a.range_hi, read once
+//                 per query, wave-uniform): VectorId v passes iff lo <= attr_of[v] <= hi and attr_of[v] is a value, not
+//                 PHNSW_ATTR_NONE -- one 4-byte load per lane as in the label mode, two compares.  Written per lane,
+//                 ph_range_holds (filter_route.h): an empty range (lo > hi) passes nothing without a scalar test of the
+//                 bounds, which is what cost the label twins a wave per SIMD.  Never with a bitmap, a label or a set,
+//                 and there is no collecting twin (profiles/ranged).
 // A mode of the body and not a run-time test of the pointers: the test alone cost 19 of the 88 kernels scratch
 // (profiles/filter), so the filtered instances exist beside the others and are picked only when a filter is given.
 //   PH_FM_COLLECT  a bit on top of PH_FM_BITMAP / PH_FM_LABEL: the collecting walk (phnsw_search_collect*, search_collect.hip,
 //                  search_collect_labeled.hip).  The descent is the PLAIN search's -- the layer tails apply `exclude` only --
 //                  and the walk of the last layer keeps, beside the layer's queue, the a.collect_k best evaluated rows
 //                  that pass the filter (`kq`, below); those are the result row.  Only ever the last launch of a descent.
-enum : int { PH_FM_NONE = 0, PH_FM_BITMAP = 1, PH_FM_LABEL = 2, PH_FM_COLLECT = 4, PH_FM_LABELSET = 8 };
+enum : int { PH_FM_NONE = 0, PH_FM_BITMAP = 1, PH_FM_LABEL = 2, PH_FM_COLLECT = 4, PH_FM_LABELSET = 8, PH_FM_RANGE = 16 };
 #define ST_SET_RANGE 8u  // the status of a query whose set range is not sound: phnsw_search_exact_labelset_device's value
 // the mode a launch's arguments ask for
 static inline int ph_filter_mode(const PhSearchArgs &a) {
-  const int where = a.set_first ? PH_FM_LABELSET : (a.label_of ? PH_FM_LABEL : (a.filter ? PH_FM_BITMAP : PH_FM_NONE));
+  const int where = a.attr_of ? PH_FM_RANGE
+                              : (a.set_first ? PH_FM_LABELSET : (a.label_of ? PH_FM_LABEL : (a.filter ? PH_FM_BITMAP : PH_FM_NONE)));
   return where | (a.collect_k ? PH_FM_COLLECT : PH_FM_NONE);
 }
 
@@ -121,7 +129,7 @@ template <int CAPC, class Dist, bool INSTR = false, bool BIG = false, int FILT =
 __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
   extern __shared__ uint32_t smem[];
   constexpr int CAP = CAPC * 64;
-  constexpr int FM = FILT & (PH_FM_BITMAP | PH_FM_LABEL | PH_FM_LABELSET);  // where the filter is read from
+  constexpr int FM = FILT & (PH_FM_BITMAP | PH_FM_LABEL | PH_FM_LABELSET | PH_FM_RANGE);  // where the filter is read from
   constexpr bool COLLECT = (FILT & PH_FM_COLLECT) != 0;
   constexpr int TAILF = COLLECT ? PH_FM_NONE : FM;  // closest_vectors' `include` beyond `exclude`: none in a collecting walk
   uint32_t *Cid = smem;                    // running candidates: VectorIds (search.rs:110)
@@ -243,6 +251,9 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
         continue;
       }
     }
+    // ... or the bounds of its range (wave-uniform, inclusive)
+    const uint32_t range_lo = FM == PH_FM_RANGE ? rfl32(a.range_lo[q]) : 0u;
+    const uint32_t range_hi = FM == PH_FM_RANGE ? rfl32(a.range_hi[q]) : 0u;
     // the filter test of VectorId v, written once for the layer tail, the strict pass and the collecting walk (callers
     // guard it: only lanes holding an id read a word or a label)
     auto passes = [&](uint32_t v) -> bool {
@@ -253,6 +264,8 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
         return lbl == want && lbl != PHNSW_LABEL_NONE;
       } else if constexpr (FM == PH_FM_LABELSET) {
         return ph_set_holds(a.label_of[v], set_b, set_e, a.set_values, PHNSW_LABEL_NONE);
+      } else if constexpr (FM == PH_FM_RANGE) {
+        return ph_range_holds(a.attr_of[v], range_lo, range_hi, PHNSW_ATTR_NONE);
       } else {
         return true;
       }
@@ -1219,6 +1232,9 @@ ph_search_fn ph_pick_labeled_dense(int capc);
 // the set twins: search_labelset.hip
 ph_search_fn ph_pick_labelset_kernel(int family, int capc, int nv, int pqr_m, bool pq_global);
 ph_search_fn ph_pick_labelset_dense(int capc);
+// the range twins: search_ranged.hip
+ph_search_fn ph_pick_ranged_kernel(int family, int capc, int nv, int pqr_m, bool pq_global);
+ph_search_fn ph_pick_ranged_dense(int capc);
 // the collecting twins (PH_FM_COLLECT over the bitmap and over the label column): search_collect.hip and
 // search_collect_labeled.hip.  No dense-only twin: a collecting kernel runs the last layer of a descent, and the
 // dense-only launch of a split descent never holds it (api.hip)

@@ -170,6 +170,158 @@ def pack_label_sets(want, nq):
     return np.ascontiguousarray(first, dtype=np.uint32), values
 
 
+ATTR_NONE = 0xFFFFFFFF  # PHNSW_ATTR_NONE: a row that carries no value
+
+
+def attr_keys(values, what="values"):
+    """a numeric column (or bounds) -> the u32 keys of Attribute, whose unsigned order is the values' order (phnsw.h,
+    "VALUE TYPES"): uint32 as it is, int32 x ^ 0x80000000, float32 with -0.0 made +0.0, then bits | 0x80000000 for a
+    value that is not negative and ~bits for a negative one.  NaN has no place in an order and a uint32 0xFFFFFFFF cannot
+    be told from ATTR_NONE: both are a ValueError naming the first index.  Other dtypes are a TypeError (64-bit columns
+    are out of scope)"""
+    a = np.asarray(values)
+    if a.dtype == np.uint32:
+        bad = np.flatnonzero(a.reshape(-1) == ATTR_NONE)
+        if len(bad):
+            raise ValueError("%s: index %d: 0xFFFFFFFF is ATTR_NONE, not a uint32 value" % (what, int(bad[0])))
+        return np.ascontiguousarray(a)
+    if a.dtype == np.int32:
+        return np.ascontiguousarray(a).view(np.uint32) ^ np.uint32(0x80000000)
+    if a.dtype == np.float32:
+        bad = np.flatnonzero(np.isnan(a.reshape(-1)))
+        if len(bad):
+            raise ValueError("%s: index %d: NaN has no place in an order" % (what, int(bad[0])))
+        bits = np.ascontiguousarray(a + np.float32(0.0)).view(np.uint32)  # -0.0 + 0.0 = +0.0
+        neg = (bits >> np.uint32(31)).astype(bool)
+        return np.where(neg, ~bits, bits | np.uint32(0x80000000)).astype(np.uint32)
+    raise TypeError("%s: a uint32, int32 or float32 array, got %s" % (what, a.dtype))
+
+
+class Attribute:
+    """phnsw_attr: one numeric value per vector of `hnsw`'s store, sorted once on the device by (key, id), so that every
+    range lo <= value <= hi is one contiguous span (twelve bytes per vector).  values: a uint32, int32 or float32 array
+    [n] (attr_keys maps it; the dtype is remembered and bounds are given in it); missing: a bool mask [n], True = the row
+    carries no value.  A vector is listed iff it has a value and the index's bottom layer holds it.  The handle is a
+    snapshot like Labels: after store.append, or with another index, the calls refuse it as stale.  Keep `hnsw` alive
+    while it is used.  search_exact_ranged, search_batch_ranged and search_ranged take it."""
+
+    def __init__(self, hnsw, values, missing=None):
+        self._h = None
+        if not isinstance(hnsw, Hnsw):
+            raise TypeError("Attribute: hnsw must be an Hnsw")
+        n = int(hnsw.store.n)
+        if values is None:
+            raise ValueError("Attribute: values: an array of shape [%d] is required" % n)
+        a = np.asarray(values)
+        if a.ndim != 1 or a.shape[0] != n:
+            raise ValueError("Attribute: values: an array of shape [%d], got %r" % (n, a.shape))
+        if missing is not None:
+            m = np.asarray(missing)
+            if m.dtype != np.bool_ or m.shape != a.shape:
+                raise ValueError("Attribute: missing: a bool mask of shape [%d], got %s %r" % (n, m.dtype, m.shape))
+            a = a.copy()
+            a[m] = 0  # whatever stood there (a NaN, 0xFFFFFFFF) is no value
+        keys = attr_keys(a, "Attribute: values").copy()
+        bad = np.flatnonzero(keys == ATTR_NONE)  # int32: 2**31 - 1 maps onto it (as a bound: "no upper end")
+        if len(bad):
+            raise ValueError("Attribute: values: index %d: %r maps onto ATTR_NONE; mark the row missing" % (int(bad[0]), a[bad[0]]))
+        if missing is not None:
+            keys[m] = ATTR_NONE
+        h = C.c_void_p()
+        check(lib().phnsw_attr_create(hnsw._h, _p(keys), len(keys), C.byref(h)))
+        self._h, self.hnsw, self.dtype = h, hnsw, a.dtype
+
+    @classmethod
+    def from_device(cls, hnsw, ptr, dtype=np.uint32, stream=0):
+        """phnsw_attr_create_device: ptr = u32 KEYS [store n] in device memory (an integer; mapped already, ATTR_NONE =
+        no value), read on `stream`, which is synchronised.  dtype: what key() maps bounds from"""
+        if not isinstance(hnsw, Hnsw):
+            raise TypeError("Attribute.from_device: hnsw must be an Hnsw")
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.uint32), np.dtype(np.int32), np.dtype(np.float32)):
+            raise TypeError("Attribute.from_device: dtype uint32, int32 or float32, got %s" % dtype)
+        self = cls.__new__(cls)
+        self._h = None
+        h = C.c_void_p()
+        check(lib().phnsw_attr_create_device(hnsw._h, C.c_void_p(ptr or None), int(hnsw.store.n), C.c_void_p(stream or None),
+                                             C.byref(h)))
+        self._h, self.hnsw, self.dtype = h, hnsw, dtype
+        return self
+
+    def key(self, x):
+        """the u32 key of a bound given in the column's dtype (a scalar or an array)"""
+        return attr_keys(np.asarray(x).astype(self.dtype, copy=False), "bound")
+
+    def bounds(self, call, lo, hi, nq):
+        """lo / hi of a call -> u32 keys [nq] each: a scalar is broadcast, an array is [nq] in the column's dtype, None
+        is an open end.  Errors name the call and the first offending query"""
+        out = []
+        for name, b, open_end in (("lo", lo, 0), ("hi", hi, ATTR_NONE)):
+            if b is None:
+                out.append(np.full(nq, open_end, dtype=np.uint32))
+                continue
+            a = np.asarray(b)
+            if a.ndim == 0:
+                a = np.full(nq, a[()])
+            if a.ndim != 1 or a.shape[0] != nq:
+                raise ValueError("%s: %s: a scalar or an array of shape [%d], got %r" % (call, name, nq, a.shape))
+            if a.dtype.kind not in "iuf" or (a.dtype.kind == "f") != (self.dtype.kind == "f"):
+                raise TypeError("%s: %s: bounds in the column's dtype %s, got %s" % (call, name, self.dtype, a.dtype))
+            if a.dtype != self.dtype:
+                c = a.astype(self.dtype)
+                bad = np.flatnonzero(~((c == a) | ((a != a) & (c != c))))
+                if len(bad):
+                    raise ValueError("%s: %s: query %d: %r is not a value of dtype %s" % (call, name, int(bad[0]), a[bad[0]],
+                                                                                         self.dtype))
+                a = c
+            try:
+                out.append(np.ascontiguousarray(attr_keys(a, name), dtype=np.uint32))
+            except ValueError as e:
+                raise ValueError("%s: %s" % (call, str(e).replace("index", "query"))) from None
+        return out[0], out[1]
+
+    def info(self):
+        """(n, listed, key_min, key_max): the vector count the handle was made for, the listed vectors, the smallest and
+        the largest KEY (0xFFFFFFFF and 0 when nothing is listed)"""
+        a, b = C.c_uint64(), C.c_uint64()
+        c, d = C.c_uint32(), C.c_uint32()
+        check(lib().phnsw_attr_info(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return int(a.value), int(b.value), int(c.value), int(d.value)
+
+    listed = property(lambda self: self.info()[1])
+
+    def count_device(self, nq, lo, hi, out_count, stream=0):
+        """phnsw_attr_count_device: device pointers as integers, u32 [nq] each (lo and hi are KEYS); enqueued"""
+        check(lib().phnsw_attr_count_device(self._h, C.c_void_p(lo or None), C.c_void_p(hi or None), int(nq),
+                                            C.c_void_p(out_count or None), C.c_void_p(stream or None)))
+
+    def count(self, lo, hi):
+        """the candidates of every range, u32 [nq] (0 where lo > hi): filter_count's figure for the equivalent bitmaps.
+        lo / hi as the searches take them, at least one an array.  Host convenience over count_device (needs torch)"""
+        import torch
+        nq = max([len(np.atleast_1d(x)) for x in (lo, hi) if x is not None] or [1])
+        l32, h32 = self.bounds("Attribute.count", lo, hi, nq)
+        dev = torch.device("cuda", getattr(self.hnsw.store, "device", 0))
+        ld = torch.from_numpy(l32.view(np.int32)).to(dev)
+        hd = torch.from_numpy(h32.view(np.int32)).to(dev)
+        out = torch.zeros(max(nq, 1), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.count_device(nq, ld.data_ptr(), hd.data_ptr(), out.data_ptr())
+        torch.cuda.synchronize(dev)
+        return out.cpu().numpy().view(np.uint32)[:nq]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().phnsw_attr_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Labels:
     """phnsw_labels: one label per vector of `hnsw`'s store, turned once into posting lists on the device (the ascending
     VectorIds of every label).  labels: an integer array [n] within u32; -1 or LABEL_NONE = the vector is not listed.  A
@@ -1204,6 +1356,128 @@ class Hnsw:
             self._h, labels._h, C.c_void_p(queries or None), ldq, C.c_void_p(qids or None), nq, C.byref(sp),
             C.c_void_p(exclude or None), C.c_void_p(want or None), int(k), int(scan_below), C.c_void_p(out_ids),
             C.c_void_p(out_d), C.c_void_p(out_len), C.c_void_p(out_route or None), C.c_void_p(status),
+            C.c_void_p(stream or None)))
+
+    def _ranged_args(self, call, queries, qids, attr, lo, hi):
+        """the checks the calls by range make before they reach the library: an Attribute, exactly one of queries / qids,
+        lo / hi as Attribute.bounds takes them.  Returns (q, qi, nq, lo u32 [nq], hi u32 [nq])"""
+        if not isinstance(attr, Attribute):
+            raise TypeError("%s: attr must be an Attribute made for this index" % call)
+        if (queries is None) == (qids is None):
+            raise ValueError("%s: pass queries or qids (exactly one)" % call)
+        q = qi = None
+        if queries is not None:
+            q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+            if q.shape[1] != self.store.dim:
+                raise ValueError("%s: queries of shape [nq, %d], got %r" % (call, self.store.dim, q.shape))
+            nq = q.shape[0]
+        else:
+            qi = np.ascontiguousarray(qids, dtype=np.uint64)
+            nq = len(qi)
+        l32, h32 = attr.bounds(call, lo, hi, nq)
+        return q, qi, nq, l32, h32
+
+    def search_exact_ranged(self, queries=None, qids=None, attr=None, lo=None, hi=None, exclude=None, k=10):
+        """search_exact_filtered by a numeric range (phnsw_search_exact_ranged): query i may return the vectors `attr`
+        lists with lo[i] <= value <= hi[i], both ends inclusive -- the same rows as search_exact_filtered(allow=(the
+        listed vectors inside the range)), bit for bit, from one span of the sorted column instead of a bitmap.  attr: an
+        Attribute made for this index; lo / hi: scalars (broadcast), arrays [nq] in the column's dtype, or None for an
+        open end; lo > hi is an empty row.  Exactly one of queries / qids.  Not measured yet (profiles/ranged/README.md).
+        Returns (ids[nq, k] u64, d[nq, k] f32, len[nq])"""
+        q, qi, nq, l32, h32 = self._ranged_args("search_exact_ranged", queries, qids, attr, lo, hi)
+        w = max(int(k), 0)
+        ids = np.empty((nq, w), dtype=np.uint64)
+        d = np.empty((nq, w), dtype=np.float32)
+        ln = np.zeros(nq, dtype=np.uint64)
+        ex = None if exclude is None else np.ascontiguousarray(exclude, dtype=np.uint64)
+        check(lib().phnsw_search_exact_ranged(self._h, attr._h, _p(q), _p(qi), nq, _p(ex), _p(l32), _p(h32), int(k), _p(ids),
+                                              _p(d), _p(ln)))
+        return ids, d, ln
+
+    def search_exact_ranged_device(self, attr, nq, k, out_ids, out_d, out_len, status, queries=0, ldq=0, qids=0, exclude=0,
+                                   lo=0, hi=0, stream=0):
+        """zero-copy form (phnsw_search_exact_ranged_device): device pointers as integers, u32 ids [nq, k] padded with
+        0xFFFFFFFF; lo, hi = u32 KEYS [nq] (Attribute.key).  status 4 = a stored query id at or past n (an empty row).
+        Enqueued on `stream`; never synchronises it"""
+        if not isinstance(attr, Attribute):
+            raise TypeError("search_exact_ranged_device: attr must be an Attribute made for this index")
+        check(lib().phnsw_search_exact_ranged_device(
+            self._h, attr._h, C.c_void_p(queries or None), ldq, C.c_void_p(qids or None), nq, C.c_void_p(exclude or None),
+            C.c_void_p(lo or None), C.c_void_p(hi or None), int(k), C.c_void_p(out_ids), C.c_void_p(out_d), C.c_void_p(out_len),
+            C.c_void_p(status), C.c_void_p(stream or None)))
+
+    def search_batch_ranged(self, queries=None, qids=None, sp=None, attr=None, lo=None, hi=None, strict=False, exclude=None,
+                            upto=0, stats=False, k=None):
+        """search_batch_filtered by a numeric range (phnsw_search_batch_ranged): the graph walk of query i restricted to
+        the vectors `attr` lists with lo[i] <= value <= hi[i] -- the rows, lengths and stats of
+        search_batch_filtered(allow=(those vectors)), bit for bit, without a bitmap per query: the kernels test the
+        handle's column.  A post-filter like search_batch_filtered (search_ranged completes rows); the entry vector may
+        be returned although it is outside the range, strict=True removes it.  set_filter's default is not consulted.
+        Not measured yet (profiles/ranged/README.md).
+        Returns (ids[nq, k or ef] u64, d f32, len[nq]) and the stats with stats=True"""
+        q, qi, nq, l32, h32 = self._ranged_args("search_batch_ranged", queries, qids, attr, lo, hi)
+        sp = sp or SearchParameters()
+        ef = sp.number_of_candidates
+        w = ef if k is None else int(k)
+        if w < 0:
+            raise ValueError("search_batch_ranged: k must not be negative")
+        ids = np.empty((nq, w), dtype=np.uint64)
+        d = np.empty((nq, w), dtype=np.float32)
+        ln = np.zeros(nq, dtype=np.uint64)
+        st = np.zeros((nq, 2), dtype=np.uint64) if stats else None
+        ex = None if exclude is None else np.ascontiguousarray(exclude, dtype=np.uint64)
+        check(lib().phnsw_search_batch_ranged(self._h, attr._h, _p(q), _p(qi), nq, C.byref(sp), upto, _p(ex), _p(l32), _p(h32),
+                                              FILTER_STRICT if strict else 0, 0 if k is None else w, _p(ids), _p(d), _p(ln),
+                                              _p(st)))
+        return (ids, d, ln, st) if stats else (ids, d, ln)
+
+    def search_batch_ranged_device(self, attr, nq, sp, out_ids, out_d, out_len, status, queries=0, ldq=0, qids=0, exclude=0,
+                                   lo=0, hi=0, strict=False, out_stats=0, upto=0, stream=0):
+        """zero-copy form (phnsw_search_batch_ranged_device): search_batch_filtered_device with lo, hi = u32 KEYS [nq]
+        (device pointers, alive until the work on `stream` is done) in place of the bitmaps.  Enqueued on `stream`; never
+        synchronises it"""
+        if not isinstance(attr, Attribute):
+            raise TypeError("search_batch_ranged_device: attr must be an Attribute made for this index")
+        check(lib().phnsw_search_batch_ranged_device(
+            self._h, attr._h, C.c_void_p(queries or None), ldq, C.c_void_p(qids or None), nq, C.byref(sp), upto,
+            C.c_void_p(exclude or None), C.c_void_p(lo or None), C.c_void_p(hi or None), FILTER_STRICT if strict else 0,
+            C.c_void_p(out_ids), C.c_void_p(out_d), C.c_void_p(out_len), C.c_void_p(out_stats or None), C.c_void_p(status),
+            C.c_void_p(stream or None)))
+
+    def search_ranged(self, queries=None, qids=None, sp=None, attr=None, lo=None, hi=None, exclude=None, k=10, scan_below=0,
+                      route=False):
+        """search_filtered by a numeric range (phnsw_search_ranged_auto): per query the span scan (search_exact_ranged)
+        where the range holds few rows (count <= scan_below, or count * number_of_candidates < k * vector_count), the
+        strict graph walk by range otherwise, and the scan again for every query whose walk came back short.  Every row
+        holds exactly min(k, count - e) entries and only listed vectors inside the range (e = 1 iff exclude[i] is one of
+        them): the rows of search_filtered with the equivalent per-query bitmaps, bit for bit.  scan_below 0 = the
+        library's threshold for ranges, 20 000: UNMEASURED, the one-label figure (the true crossover is expected below
+        it: the range scan has no tile path); 2**64 - 1 = always scan.  1 <= k <= sp.number_of_candidates.
+        Returns (ids[nq, k] u64, d[nq, k] f32, len[nq]) and, with route=True, route[nq] u32: ROUTE_GRAPH, ROUTE_SCAN or
+        ROUTE_GRAPH_THEN_SCAN"""
+        q, qi, nq, l32, h32 = self._ranged_args("search_ranged", queries, qids, attr, lo, hi)
+        sp = sp or SearchParameters()
+        w = max(int(k), 0)
+        ids = np.empty((nq, w), dtype=np.uint64)
+        d = np.empty((nq, w), dtype=np.float32)
+        ln = np.zeros(nq, dtype=np.uint64)
+        rt = np.zeros(nq, dtype=np.uint32) if route else None
+        ex = None if exclude is None else np.ascontiguousarray(exclude, dtype=np.uint64)
+        check(lib().phnsw_search_ranged_auto(self._h, attr._h, _p(q), _p(qi), nq, C.byref(sp), _p(ex), _p(l32), _p(h32), int(k),
+                                             int(scan_below), _p(ids), _p(d), _p(ln), _p(rt)))
+        return (ids, d, ln, rt) if route else (ids, d, ln)
+
+    def search_ranged_device(self, attr, nq, sp, k, out_ids, out_d, out_len, status, queries=0, ldq=0, qids=0, exclude=0, lo=0,
+                             hi=0, scan_below=0, out_route=0, stream=0):
+        """device form (phnsw_search_ranged_auto_device): device pointers as integers, u32 ids [nq, k] padded with
+        0xFFFFFFFF; lo, hi = u32 KEYS [nq]; out_route u32 [nq] or 0.  Like search_filtered_device it synchronises
+        `stream`, up to twice"""
+        if not isinstance(attr, Attribute):
+            raise TypeError("search_ranged_device: attr must be an Attribute made for this index")
+        check(lib().phnsw_search_ranged_auto_device(
+            self._h, attr._h, C.c_void_p(queries or None), ldq, C.c_void_p(qids or None), nq, C.byref(sp),
+            C.c_void_p(exclude or None), C.c_void_p(lo or None), C.c_void_p(hi or None), int(k), int(scan_below),
+            C.c_void_p(out_ids), C.c_void_p(out_d), C.c_void_p(out_len), C.c_void_p(out_route or None), C.c_void_p(status),
             C.c_void_p(stream or None)))
 
     def search_batch_labelset(self, queries=None, qids=None, sp=None, labels=None, want=None, strict=False, exclude=None,

@@ -77,6 +77,10 @@ pub struct phnsw_index {
 pub struct phnsw_labels {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct phnsw_attr {
+    _private: [u8; 0],
+}
 
 /// ProgressMonitor::update / keep_alive  progress.rs:12-16
 pub type phnsw_progress_cb =
@@ -345,6 +349,42 @@ extern "C" {
                                              want_values_dev: *const u32, nwant: u64, k: u64, scan_below: u64,
                                              out_ids_dev: *mut u32, out_d_dev: *mut c_float, out_len_dev: *mut u32,
                                              out_route_dev: *mut u32, status_dev: *mut u32, stream: *mut c_void) -> c_int;
+    // search by a numeric range of a row attribute: a u32 key column sorted once, every range one span of it
+    pub fn phnsw_attr_create(ix: *const phnsw_index, keys: *const u32, n: u64, out: *mut *mut phnsw_attr) -> c_int;
+    pub fn phnsw_attr_create_device(ix: *const phnsw_index, keys_dev: *const u32, n: u64, stream: *mut c_void,
+                                    out: *mut *mut phnsw_attr) -> c_int;
+    pub fn phnsw_attr_info(at: *const phnsw_attr, n: *mut u64, listed: *mut u64, key_min: *mut u32, key_max: *mut u32) -> c_int;
+    pub fn phnsw_attr_count_device(at: *const phnsw_attr, lo_dev: *const u32, hi_dev: *const u32, nq: u64,
+                                   out_count_dev: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn phnsw_attr_destroy(at: *mut phnsw_attr);
+    pub fn phnsw_search_exact_ranged(ix: *const phnsw_index, at: *const phnsw_attr, queries: *const c_float,
+                                     qids: *const u64, nq: u64, exclude: *const u64, lo: *const u32, hi: *const u32, k: u64,
+                                     out_ids: *mut u64, out_d: *mut c_float, out_len: *mut u64) -> c_int;
+    pub fn phnsw_search_exact_ranged_device(ix: *const phnsw_index, at: *const phnsw_attr, queries_dev: *const c_float,
+                                            ldq: u32, qids_dev: *const u32, nq: u64, exclude_dev: *const u32,
+                                            lo_dev: *const u32, hi_dev: *const u32, k: u64, out_ids_dev: *mut u32,
+                                            out_d_dev: *mut c_float, out_len_dev: *mut u32, status_dev: *mut u32,
+                                            stream: *mut c_void) -> c_int;
+    pub fn phnsw_search_batch_ranged(ix: *const phnsw_index, at: *const phnsw_attr, queries: *const c_float,
+                                     qids: *const u64, nq: u64, sp: *const phnsw_search_params, upto_layers: u32,
+                                     exclude: *const u64, lo: *const u32, hi: *const u32, flags: u32, k: u64,
+                                     out_ids: *mut u64, out_d: *mut c_float, out_len: *mut u64, out_stats: *mut u64) -> c_int;
+    pub fn phnsw_search_batch_ranged_device(ix: *const phnsw_index, at: *const phnsw_attr, queries_dev: *const c_float,
+                                            ldq: u32, qids_dev: *const u32, nq: u64, sp: *const phnsw_search_params,
+                                            upto_layers: u32, exclude_dev: *const u32, lo_dev: *const u32,
+                                            hi_dev: *const u32, flags: u32, out_ids_dev: *mut u32, out_d_dev: *mut c_float,
+                                            out_len_dev: *mut u32, out_stats_dev: *mut u32, status_dev: *mut u32,
+                                            stream: *mut c_void) -> c_int;
+    pub fn phnsw_search_ranged_auto(ix: *const phnsw_index, at: *const phnsw_attr, queries: *const c_float,
+                                    qids: *const u64, nq: u64, sp: *const phnsw_search_params, exclude: *const u64,
+                                    lo: *const u32, hi: *const u32, k: u64, scan_below: u64, out_ids: *mut u64,
+                                    out_d: *mut c_float, out_len: *mut u64, out_route: *mut u32) -> c_int;
+    pub fn phnsw_search_ranged_auto_device(ix: *const phnsw_index, at: *const phnsw_attr, queries_dev: *const c_float,
+                                           ldq: u32, qids_dev: *const u32, nq: u64, sp: *const phnsw_search_params,
+                                           exclude_dev: *const u32, lo_dev: *const u32, hi_dev: *const u32, k: u64,
+                                           scan_below: u64, out_ids_dev: *mut u32, out_d_dev: *mut c_float,
+                                           out_len_dev: *mut u32, out_route_dev: *mut u32, status_dev: *mut u32,
+                                           stream: *mut c_void) -> c_int;
     // the collecting search: the plain walk whose last layer keeps the best k allowed rows it evaluates (k <= 64)
     pub fn phnsw_search_collect(ix: *const phnsw_index, queries: *const c_float, qids: *const u64, nq: u64,
                                 sp: *const phnsw_search_params, upto_layers: u32, exclude: *const u64, filter: *const u32,
