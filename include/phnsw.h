@@ -801,6 +801,97 @@ int phnsw_search_ranged_auto_device(const phnsw_index *ix, const phnsw_attr *at,
                                     const uint32_t *exclude_dev, const uint32_t *lo_dev, const uint32_t *hi_dev, uint64_t k,
                                     uint64_t scan_below, uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
                                     uint32_t *out_route_dev, uint32_t *status_dev, void *stream);
+/* ---- search by a ROW LABEL AND A NUMERIC RANGE, `label == want AND lo <= attribute <= hi`: this tenant's rows of the
+ * last week.  Every vector carries one u32 label (PHNSW_LABEL_NONE: none) and one u32 key (PHNSW_ATTR_NONE: no value);
+ * the value types and the key map are those of phnsw_attr above.
+ * A phnsw_label_attr handle sorts the listed rows ONCE on the device by the 64-bit composite (label << 32) | key, then
+ * by id; every (label, range) pair is then one contiguous SPAN of that order,
+ *   [lower_bound(want << 32 | lo), upper_bound(want << 32 | hi)),
+ * found with two binary searches: no bitmap per query, no merge of a posting list with a span, no bucket labels.  The
+ * handle keeps spairs[listed] (u64, ascending), ids[listed] (ascending within equal composites) and, for the graph walk,
+ * pair_of[n] (the composite of a listed row, UINT64_MAX elsewhere): TWENTY BYTES PER VECTOR (8 + 4 + 8).
+ * Listed: v is listed iff v < n, labels[v] != PHNSW_LABEL_NONE, keys[v] != PHNSW_ATTR_NONE and v is a vector of the
+ * index's bottom layer.  A row with a label but no value, or a value but no label, is not listed.  n must equal the
+ * store's vector count, else PHNSW_E_INVALID.
+ * The span is EMPTY -- the row empty, the length 0, the status 0, no error -- when want == PHNSW_LABEL_NONE, when
+ * lo > hi, or when nobody carries the label.  Ranges are inclusive on both ends; hi == 0xFFFFFFFF means "no upper end
+ * within this label": no listed row has that key, so the span ends at the first row of the next label.
+ * The handle is a SNAPSHOT like phnsw_attr, with its rule and its wording; creation synchronises.
+ * phnsw_label_attr_info: the n it was made for, the listed vectors, the number of distinct labels that list a row and
+ * the most rows listed under one label; any output may be NULL.  phnsw_label_attr_count_device writes, per query, the
+ * length of its span: phnsw_filter_count_device's figure for the equivalent bitmap; enqueued on `stream`, never
+ * synchronises.  phnsw_label_attr_destroy waits for the calls in flight that use the handle; NULL is a no-op.
+ * NOT BUILT: a set of labels with a range, 64-bit keys, a tile path for the scan, a collecting twin of the walk. */
+typedef struct phnsw_label_attr phnsw_label_attr;
+int phnsw_label_attr_create(const phnsw_index *ix, const uint32_t *labels, const uint32_t *keys, uint64_t n,
+                            phnsw_label_attr **out); /* host labels [n], keys [n] */
+int phnsw_label_attr_create_device(const phnsw_index *ix, const uint32_t *labels_dev, const uint32_t *keys_dev, uint64_t n,
+                                   void *stream, phnsw_label_attr **out);
+int phnsw_label_attr_info(const phnsw_label_attr *h, uint64_t *n, uint64_t *listed, uint64_t *nlabels, uint64_t *longest);
+int phnsw_label_attr_count_device(const phnsw_label_attr *h, const uint32_t *want_dev, const uint32_t *lo_dev,
+                                  const uint32_t *hi_dev, uint64_t nq, uint32_t *out_count_dev, void *stream);
+void phnsw_label_attr_destroy(phnsw_label_attr *h); /* waits for the calls in flight that use it */
+/* exact top-k over a label and a range: phnsw_search_exact_ranged with (h, want, lo, hi) in place of (at, lo, hi); want,
+ * lo and hi are u32 [nq].  Candidates of q: the listed vectors with labels[v] == want[q] and lo[q] <= keys[v] <= hi[q],
+ * except exclude[q].
+ * EQUALITY: the row of every query equals, in ids, distance bits, length and status, the row
+ * phnsw_search_exact_filtered returns for that query with the bitmap
+ * {v : v listed, labels[v] == want[q], lo[q] <= keys[v] <= hi[q]}; +inf, tie order by id, padding and 1 <= k <= 1024 as
+ * there.  The result does not depend on the batch's order or on the knob below.
+ * Checks: those of phnsw_search_exact_ranged in its order, with `h` for `at` and want / lo / hi for lo / hi.
+ * How: the kernel sequence of phnsw_search_exact_ranged over every store kind that call scans; no tile path.  Knob
+ * (environment, read per call, changes no result): PHNSW_LABEL_RANGE_SLICES forces the number of slices a span is cut
+ * into.
+ * Guidance: NOT MEASURED (scripts/bench_label_ranged.py, profiles/label_ranged/README.md).  The scan runs the loop of
+ * phnsw_search_exact_ranged over spans found in u64 instead of u32 words; expect that call's times. */
+int phnsw_search_exact_label_ranged(const phnsw_index *ix, const phnsw_label_attr *h, const float *queries,
+                                    const uint64_t *qids, uint64_t nq, const uint64_t *exclude, const uint32_t *want,
+                                    const uint32_t *lo, const uint32_t *hi, uint64_t k, uint64_t *out_ids, float *out_d,
+                                    uint64_t *out_len);
+/* device form: ENQUEUES AND RETURNS, never synchronises; status_dev[q] = 4 for a Stored query id at or past n (an empty
+ * row, the others unaffected).  Scratch sets live with the handle until phnsw_label_attr_destroy. */
+int phnsw_search_exact_label_ranged_device(const phnsw_index *ix, const phnsw_label_attr *h, const float *queries_dev,
+                                           uint32_t ldq, const uint32_t *qids_dev, uint64_t nq, const uint32_t *exclude_dev,
+                                           const uint32_t *want_dev, const uint32_t *lo_dev, const uint32_t *hi_dev,
+                                           uint64_t k, uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                           uint32_t *status_dev, void *stream);
+/* the graph walk by label and range: phnsw_search_batch_ranged with (h, want, lo, hi) -- the search kernels' label-range
+ * mode over pair_of, one 8-byte load per tested id, compared word by word with the query's three words.
+ * ROW EQUALITY: rows, lengths, stats and statuses are those of phnsw_search_batch_filtered[_device] called with the
+ * per-query bitmaps above, bit for bit, the entry-vector quirk and PHNSW_FILTER_STRICT included.  The index's default
+ * filter is not consulted.  Every store kind phnsw_search_batch_filtered walks is accepted.  Not measured against it
+ * (profiles/label_ranged/README.md). */
+int phnsw_search_batch_label_ranged(const phnsw_index *ix, const phnsw_label_attr *h, const float *queries,
+                                    const uint64_t *qids, uint64_t nq, const phnsw_search_params *sp, uint32_t upto_layers,
+                                    const uint64_t *exclude, const uint32_t *want, const uint32_t *lo, const uint32_t *hi,
+                                    uint32_t flags, uint64_t k, uint64_t *out_ids, float *out_d, uint64_t *out_len,
+                                    uint64_t *out_stats);
+/* device form: ENQUEUED on `stream`, never synchronises.  want_dev, lo_dev and hi_dev [nq] are read by the kernels: keep
+ * them alive and unchanged until the work on `stream` is done. */
+int phnsw_search_batch_label_ranged_device(const phnsw_index *ix, const phnsw_label_attr *h, const float *queries_dev,
+                                           uint32_t ldq, const uint32_t *qids_dev, uint64_t nq,
+                                           const phnsw_search_params *sp, uint32_t upto_layers, const uint32_t *exclude_dev,
+                                           const uint32_t *want_dev, const uint32_t *lo_dev, const uint32_t *hi_dev,
+                                           uint32_t flags, uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                           uint32_t *out_stats_dev, uint32_t *status_dev, void *stream);
+/* one call by label and range that routes: phnsw_search_ranged_auto with (h, want, lo, hi).  Same three routes, rule and
+ * promise: every row holds exactly min(k, c_q - e_q) entries and only candidates; c_q is the span's length, e_q is 1 iff
+ * exclude[q] < n and it is listed under want[q] with its key inside the range.  The walk is the STRICT walk above;
+ * scanned rows and graph rows left short go through ONE launch of the exact scan above.  Hence every row equals the row
+ * of phnsw_search_filtered_auto with the per-query bitmaps and the same scan_below.  The device form synchronises
+ * `stream` at most twice.  scan_below 0 = the library default (filter_route.h, PH_AUTO_SCAN_BELOW_LABEL_RANGED): the
+ * ranged figure, 20 000, UNMEASURED; pass your own.  UINT64_MAX = always scan. */
+int phnsw_search_label_ranged_auto(const phnsw_index *ix, const phnsw_label_attr *h, const float *queries,
+                                   const uint64_t *qids, uint64_t nq, const phnsw_search_params *sp, const uint64_t *exclude,
+                                   const uint32_t *want, const uint32_t *lo, const uint32_t *hi, uint64_t k,
+                                   uint64_t scan_below, uint64_t *out_ids, float *out_d, uint64_t *out_len,
+                                   uint32_t *out_route);
+int phnsw_search_label_ranged_auto_device(const phnsw_index *ix, const phnsw_label_attr *h, const float *queries_dev,
+                                          uint32_t ldq, const uint32_t *qids_dev, uint64_t nq, const phnsw_search_params *sp,
+                                          const uint32_t *exclude_dev, const uint32_t *want_dev, const uint32_t *lo_dev,
+                                          const uint32_t *hi_dev, uint64_t k, uint64_t scan_below, uint32_t *out_ids_dev,
+                                          float *out_d_dev, uint32_t *out_len_dev, uint32_t *out_route_dev,
+                                          uint32_t *status_dev, void *stream);
 /* ---- the COLLECTING search: the graph walk that remembers the best ALLOWED rows it evaluates.  The filtered walks above
  * are post-filters: they keep the best number_of_candidates rows, allowed or not, and filter that queue when the layer
  * ends, so a filter of density p leaves about p * number_of_candidates results although the walk evaluated several

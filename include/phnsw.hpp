@@ -161,6 +161,7 @@ using SearchResult = std::vector<std::pair<VectorId, float>>;
 
 class Labels;
 class Attribute;
+class LabeledAttribute;
 
 class Hnsw {
  public:
@@ -592,6 +593,48 @@ class Hnsw {
                                         const uint32_t *lo_dev, const uint32_t *hi_dev, uint64_t k, uint64_t scan_below,
                                         uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev, uint32_t *out_route_dev,
                                         uint32_t *status_dev, void *stream) const;
+  // search_many_exact_filtered by a label and a numeric range (phnsw_search_exact_label_ranged): query i may return the
+  // vectors `attr` lists under want[i] with lo[i] <= key <= hi[i], both ends inclusive, u32 KEYS (attr_key); want
+  // LabeledAttribute::NONE, lo > hi or a label nobody carries = nothing
+  inline std::vector<SearchResult> search_many_exact_label_ranged(const std::vector<const float *> &queries, uint64_t k,
+                                                                  const LabeledAttribute &attr, const std::vector<uint32_t> &want,
+                                                                  const std::vector<uint32_t> &lo,
+                                                                  const std::vector<uint32_t> &hi) const;
+  // zero-copy form (phnsw_search_exact_label_ranged_device): u32 ids [nq][k]; enqueued on `stream`, never synchronises it
+  inline void search_exact_label_ranged_device(const LabeledAttribute &attr, const float *queries_dev, uint32_t ldq,
+                                               const uint32_t *qids_dev, uint64_t nq, const uint32_t *exclude_dev,
+                                               const uint32_t *want_dev, const uint32_t *lo_dev, const uint32_t *hi_dev, uint64_t k,
+                                               uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev, uint32_t *status_dev,
+                                               void *stream) const;
+  // search_many_filtered by a label and a numeric range (phnsw_search_batch_label_ranged): the graph walk restricted to
+  // the pair; k 0 = all number_of_candidates entries of a row
+  inline std::vector<SearchResult> search_many_label_ranged(const std::vector<const float *> &queries, const SearchParameters &sp,
+                                                            uint64_t k, const LabeledAttribute &attr,
+                                                            const std::vector<uint32_t> &want, const std::vector<uint32_t> &lo,
+                                                            const std::vector<uint32_t> &hi, bool strict = false) const;
+  // zero-copy form (phnsw_search_batch_label_ranged_device): want_dev / lo_dev / hi_dev stay alive until the work on
+  // `stream` is done
+  inline void search_batch_label_ranged_device(const LabeledAttribute &attr, const float *queries_dev, uint32_t ldq,
+                                               const uint32_t *qids_dev, uint64_t nq, const SearchParameters &sp,
+                                               uint32_t upto_layers, const uint32_t *exclude_dev, const uint32_t *want_dev,
+                                               const uint32_t *lo_dev, const uint32_t *hi_dev, bool strict, uint32_t *out_ids_dev,
+                                               float *out_d_dev, uint32_t *out_len_dev, uint32_t *out_stats_dev,
+                                               uint32_t *status_dev, void *stream) const;
+  // search_many_filtered_auto by a label and a numeric range (phnsw_search_label_ranged_auto): per query the span scan or
+  // the strict walk, the scan again for short rows.  scan_below 0 = the library's threshold (20 000, UNMEASURED: phnsw.h)
+  inline std::vector<SearchResult> search_many_label_ranged_auto(const std::vector<const float *> &queries,
+                                                                 const SearchParameters &sp, uint64_t k,
+                                                                 const LabeledAttribute &attr, const std::vector<uint32_t> &want,
+                                                                 const std::vector<uint32_t> &lo, const std::vector<uint32_t> &hi,
+                                                                 uint64_t scan_below = 0,
+                                                                 std::vector<uint32_t> *routes = nullptr) const;
+  // device form (phnsw_search_label_ranged_auto_device): u32 ids [nq][k]; synchronises `stream` up to twice (phnsw.h)
+  inline void search_label_ranged_auto_device(const LabeledAttribute &attr, const float *queries_dev, uint32_t ldq,
+                                              const uint32_t *qids_dev, uint64_t nq, const SearchParameters &sp,
+                                              const uint32_t *exclude_dev, const uint32_t *want_dev, const uint32_t *lo_dev,
+                                              const uint32_t *hi_dev, uint64_t k, uint64_t scan_below, uint32_t *out_ids_dev,
+                                              float *out_d_dev, uint32_t *out_len_dev, uint32_t *out_route_dev,
+                                              uint32_t *status_dev, void *stream) const;
   // 0, or the code search_many_exact_shared would refuse this index and k with (phnsw_exact_shared_supported)
   int exact_shared_supported(uint64_t k) const { return phnsw_exact_shared_supported(ix_, k); }
   // candidates of each of nbitmaps device bitmaps (phnsw_filter_count_device): what to choose the search call by
@@ -1108,6 +1151,120 @@ inline void Hnsw::search_ranged_auto_device(const Attribute &attr, const float *
                                             uint32_t *out_route_dev, uint32_t *status_dev, void *stream) const {
   check(phnsw_search_ranged_auto_device(ix_, attr.handle(), queries_dev, ldq, qids_dev, nq, &sp, exclude_dev, lo_dev, hi_dev, k,
                                         scan_below, out_ids_dev, out_d_dev, out_len_dev, out_route_dev, status_dev, stream));
+}
+
+// phnsw_label_attr: one u32 label and one u32 key per vector of the index's store, sorted once on the device by
+// (label << 32) | key, then by id (20 bytes per vector).  A vector is listed iff it carries both and the index's bottom
+// layer holds it.  A snapshot like Attribute.  The Hnsw must outlive its use
+class LabeledAttribute {
+ public:
+  static constexpr uint32_t NONE = 0xFFFFFFFFu;  // PHNSW_LABEL_NONE and PHNSW_ATTR_NONE: no label, no value
+  LabeledAttribute(const Hnsw &hnsw, const std::vector<uint32_t> &labels, const std::vector<uint32_t> &keys) {
+    if (labels.size() != keys.size()) throw Error(PHNSW_E_INVALID, "LabeledAttribute: one label and one key per vector");
+    check(phnsw_label_attr_create(hnsw.handle(), labels.data(), keys.data(), keys.size(), &h_));
+  }
+  // labels_dev, keys_dev: u32 [store n] each in device memory, read on `stream`, which is synchronised
+  LabeledAttribute(const Hnsw &hnsw, const uint32_t *labels_dev, const uint32_t *keys_dev, uint64_t n, void *stream) {
+    check(phnsw_label_attr_create_device(hnsw.handle(), labels_dev, keys_dev, n, stream, &h_));
+  }
+  LabeledAttribute(const LabeledAttribute &) = delete;
+  LabeledAttribute &operator=(const LabeledAttribute &) = delete;
+  LabeledAttribute(LabeledAttribute &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+  ~LabeledAttribute() { phnsw_label_attr_destroy(h_); }
+  uint64_t listed() const {
+    uint64_t v = 0;
+    check(phnsw_label_attr_info(h_, nullptr, &v, nullptr, nullptr));
+    return v;
+  }
+  // the distinct labels that list a row, and the most rows listed under one of them
+  std::pair<uint64_t, uint64_t> label_stats() const {
+    uint64_t a = 0, b = 0;
+    check(phnsw_label_attr_info(h_, nullptr, nullptr, &a, &b));
+    return {a, b};
+  }
+  void count_device(const uint32_t *want_dev, const uint32_t *lo_dev, const uint32_t *hi_dev, uint64_t nq, uint32_t *out_count_dev,
+                    void *stream) const {
+    check(phnsw_label_attr_count_device(h_, want_dev, lo_dev, hi_dev, nq, out_count_dev, stream));
+  }
+  phnsw_label_attr *handle() const { return h_; }
+
+ private:
+  phnsw_label_attr *h_ = nullptr;
+};
+
+inline std::vector<SearchResult> Hnsw::search_many_exact_label_ranged(const std::vector<const float *> &queries, uint64_t k,
+                                                                      const LabeledAttribute &attr,
+                                                                      const std::vector<uint32_t> &want,
+                                                                      const std::vector<uint32_t> &lo,
+                                                                      const std::vector<uint32_t> &hi) const {
+  if (k == 0 || k > 1024) throw Error(PHNSW_E_INVALID, "search_many_exact_label_ranged: k must be 1..1024");
+  if (want.size() != queries.size()) throw Error(PHNSW_E_INVALID, "search_many_exact_label_ranged: one wanted label per query");
+  return detail::ranged_rows(queries, c_->dim(), k, lo, hi, "search_many_exact_label_ranged",
+                             [&](const float *q, uint64_t nq, uint64_t *ids, float *d, uint64_t *len) {
+                               check(phnsw_search_exact_label_ranged(ix_, attr.handle(), q, nullptr, nq, nullptr, want.data(),
+                                                                     lo.data(), hi.data(), k, ids, d, len));
+                             });
+}
+inline void Hnsw::search_exact_label_ranged_device(const LabeledAttribute &attr, const float *queries_dev, uint32_t ldq,
+                                                   const uint32_t *qids_dev, uint64_t nq, const uint32_t *exclude_dev,
+                                                   const uint32_t *want_dev, const uint32_t *lo_dev, const uint32_t *hi_dev,
+                                                   uint64_t k, uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                                   uint32_t *status_dev, void *stream) const {
+  check(phnsw_search_exact_label_ranged_device(ix_, attr.handle(), queries_dev, ldq, qids_dev, nq, exclude_dev, want_dev, lo_dev,
+                                               hi_dev, k, out_ids_dev, out_d_dev, out_len_dev, status_dev, stream));
+}
+inline std::vector<SearchResult> Hnsw::search_many_label_ranged(const std::vector<const float *> &queries,
+                                                                const SearchParameters &sp, uint64_t k,
+                                                                const LabeledAttribute &attr, const std::vector<uint32_t> &want,
+                                                                const std::vector<uint32_t> &lo, const std::vector<uint32_t> &hi,
+                                                                bool strict) const {
+  if (k == 0) k = sp.number_of_candidates;  // the C call's "whole row"; the buffers are sized by it
+  if (k > sp.number_of_candidates) throw Error(PHNSW_E_INVALID, "search_many_label_ranged: k exceeds number_of_candidates");
+  if (want.size() != queries.size()) throw Error(PHNSW_E_INVALID, "search_many_label_ranged: one wanted label per query");
+  return detail::ranged_rows(queries, c_->dim(), k, lo, hi, "search_many_label_ranged",
+                             [&](const float *q, uint64_t nq, uint64_t *ids, float *d, uint64_t *len) {
+                               check(phnsw_search_batch_label_ranged(ix_, attr.handle(), q, nullptr, nq, &sp, 0, nullptr,
+                                                                     want.data(), lo.data(), hi.data(),
+                                                                     strict ? PHNSW_FILTER_STRICT : 0u, k, ids, d, len, nullptr));
+                             });
+}
+inline void Hnsw::search_batch_label_ranged_device(const LabeledAttribute &attr, const float *queries_dev, uint32_t ldq,
+                                                   const uint32_t *qids_dev, uint64_t nq, const SearchParameters &sp,
+                                                   uint32_t upto_layers, const uint32_t *exclude_dev, const uint32_t *want_dev,
+                                                   const uint32_t *lo_dev, const uint32_t *hi_dev, bool strict,
+                                                   uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                                   uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) const {
+  check(phnsw_search_batch_label_ranged_device(ix_, attr.handle(), queries_dev, ldq, qids_dev, nq, &sp, upto_layers, exclude_dev,
+                                               want_dev, lo_dev, hi_dev, strict ? PHNSW_FILTER_STRICT : 0u, out_ids_dev, out_d_dev,
+                                               out_len_dev, out_stats_dev, status_dev, stream));
+}
+inline std::vector<SearchResult> Hnsw::search_many_label_ranged_auto(const std::vector<const float *> &queries,
+                                                                     const SearchParameters &sp, uint64_t k,
+                                                                     const LabeledAttribute &attr,
+                                                                     const std::vector<uint32_t> &want,
+                                                                     const std::vector<uint32_t> &lo,
+                                                                     const std::vector<uint32_t> &hi, uint64_t scan_below,
+                                                                     std::vector<uint32_t> *routes) const {
+  if (k == 0 || k > sp.number_of_candidates)
+    throw Error(PHNSW_E_INVALID, "search_many_label_ranged_auto: k must be 1..number_of_candidates");
+  if (want.size() != queries.size()) throw Error(PHNSW_E_INVALID, "search_many_label_ranged_auto: one wanted label per query");
+  if (routes) routes->assign(queries.size(), 0u);
+  return detail::ranged_rows(queries, c_->dim(), k, lo, hi, "search_many_label_ranged_auto",
+                             [&](const float *q, uint64_t nq, uint64_t *ids, float *d, uint64_t *len) {
+                               check(phnsw_search_label_ranged_auto(ix_, attr.handle(), q, nullptr, nq, &sp, nullptr, want.data(),
+                                                                    lo.data(), hi.data(), k, scan_below, ids, d, len,
+                                                                    routes ? routes->data() : nullptr));
+                             });
+}
+inline void Hnsw::search_label_ranged_auto_device(const LabeledAttribute &attr, const float *queries_dev, uint32_t ldq,
+                                                  const uint32_t *qids_dev, uint64_t nq, const SearchParameters &sp,
+                                                  const uint32_t *exclude_dev, const uint32_t *want_dev, const uint32_t *lo_dev,
+                                                  const uint32_t *hi_dev, uint64_t k, uint64_t scan_below, uint32_t *out_ids_dev,
+                                                  float *out_d_dev, uint32_t *out_len_dev, uint32_t *out_route_dev,
+                                                  uint32_t *status_dev, void *stream) const {
+  check(phnsw_search_label_ranged_auto_device(ix_, attr.handle(), queries_dev, ldq, qids_dev, nq, &sp, exclude_dev, want_dev, lo_dev,
+                                              hi_dev, k, scan_below, out_ids_dev, out_d_dev, out_len_dev, out_route_dev, status_dev,
+                                              stream));
 }
 
 // QuantizedHnsw  pq.rs:120-131, 287-364 (per-sub-space codebooks, u8 codes)

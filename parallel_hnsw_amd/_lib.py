@@ -171,6 +171,22 @@ SYMBOLS = {
     "phnsw_search_ranged_auto": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp, _vp]),
     "phnsw_search_ranged_auto_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp,
                                                _vp, _vp, _vp]),
+    "phnsw_label_attr_create": (_i32, [_vp, _vp, _vp, _u64, _pp]),
+    "phnsw_label_attr_create_device": (_i32, [_vp, _vp, _vp, _u64, _vp, _pp]),
+    "phnsw_label_attr_info": (_i32, [_vp, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "phnsw_label_attr_count_device": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp]),
+    "phnsw_label_attr_destroy": (None, [_vp]),
+    "phnsw_search_exact_label_ranged": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "phnsw_search_exact_label_ranged_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp,
+                                                      _vp, _vp]),
+    "phnsw_search_batch_label_ranged": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u64, _vp, _vp,
+                                               _vp, _vp]),
+    "phnsw_search_batch_label_ranged_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp,
+                                                      _vp, _vp, _vp, _vp, _vp]),
+    "phnsw_search_label_ranged_auto": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp, _vp,
+                                              _vp]),
+    "phnsw_search_label_ranged_auto_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _vp,
+                                                     _vp, _vp, _vp, _vp, _vp]),
     "phnsw_search_batch_labelset": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _u32, _u64, _vp, _vp, _vp, _vp]),
     "phnsw_search_batch_labelset_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _u64, _u32, _vp,
                                                   _vp, _vp, _vp, _vp, _vp]),

@@ -652,6 +652,11 @@ static void fill_args(const phnsw_index *ix, const PhSearchCall &c, PhSearchArgs
     a.attr_of = c.filter.attr_of, a.range_lo = c.filter.range_lo, a.range_hi = c.filter.range_hi;
     a.filter_flags = c.filter.flags;
   }
+  if (c.filter.pair_of) {  // ... or the label-range form: the pair column, a label and two bounds per query, nothing else
+    a.filter = nullptr, a.filter_stride = 0u;
+    a.pair_of = c.filter.pair_of, a.pair_want = c.filter.pair_want, a.pair_lo = c.filter.pair_lo, a.pair_hi = c.filter.pair_hi;
+    a.filter_flags = c.filter.flags;
+  }
   a.nq = (uint32_t)c.nq;
   a.out_ids = c.out_ids;
   a.out_d = c.out_d;
@@ -855,7 +860,7 @@ int ph_search_device(const phnsw_index *ix, const PhSearchCall &c) {
   // and the build's searches keep the natural order.)
   const uint32_t *table_pos = nullptr;
   const char *const table_order_env = getenv("PHNSW_TABLE_ORDER");  // read per call: the tests switch it
-  if (T && !split && !a.order && !knn_mode && !out_stride && !out_index && !c.hint && !c.out_hit && !a.filter && !a.label_of && !a.attr_of &&
+  if (T && !split && !a.order && !knn_mode && !out_stride && !out_index && !c.hint && !c.out_hit && !a.filter && !a.label_of && !a.attr_of && !a.pair_of &&
       !a.collect_k && nq >= PH_TABLE_ORDER_MIN && !getenv("PHNSW_NO_LOCALITY") && !(table_order_env && table_order_env[0] == '0')) {
     PhLayerHost &TL = mix->layers[T - 1];
     rc = ph_layer_anchor_pos(ix->store, TL);  // first use on a loaded index; no-op afterwards, and for a layer without cells
@@ -892,6 +897,7 @@ int ph_search_device(const phnsw_index *ix, const PhSearchCall &c) {
       if (b.filter) b.filter += c0 * b.filter_stride;  // per-query bitmaps follow the chunk; a shared one (stride 0) stays
       if (b.label_want) b.label_want += c0;  // ... and so do the wanted labels; the column is indexed by VectorId
       if (b.range_lo) b.range_lo += c0, b.range_hi += c0;  // ... and the bounds of the ranges
+      if (b.pair_want) b.pair_want += c0, b.pair_lo += c0, b.pair_hi += c0;  // ... and the labels and bounds of the pairs
       if (b.set_first) b.set_first += c0;    // ... and the offsets of the sets, which stay absolute: set_values does not move
       if (b.out_ids) b.out_ids += c0 * ostride, b.out_d += c0 * ostride;
       if (b.collect_k) b.collect_ids += c0 * b.collect_k, b.collect_d += c0 * b.collect_k;

@@ -31,6 +31,12 @@
 //   3. the walk is the search kernels' range mode over the handle's column
 //   4. "exclude[q] is a candidate" is ph_auto_range_candidate, the predicate of the walk
 //   5. the scan is filter_ranged.hip's, over the scan list (PhRangedCall::list)
+// ... or BY A LABEL AND A NUMERIC RANGE (phnsw_search_label_ranged_auto[_device]: a phnsw_label_attr handle, want[q], lo[q]
+// and hi[q]):
+//   1. the counts are the lengths of the spans (ph_label_attr_count): no bitmap is made or counted
+//   3. the walk is the search kernels' label-range mode over the handle's column
+//   4. "exclude[q] is a candidate" is ph_auto_pair_candidate, the predicate of the walk (ph_pair_holds)
+//   5. the scan is filter_label_ranged.hip's, over the scan list (PhLabelRangedCall::list)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -57,6 +63,9 @@ struct PhAutoArgs {
   const uint32_t *set_first, *set_values;
   // a call by range: the handle's column [n] and the bounds [nq]; else nullptr
   const uint32_t *attr_of, *range_lo, *range_hi;
+  // a call by label and range: the handle's column [n], the labels and the bounds [nq]; else nullptr
+  const uint64_t *pair_of;
+  const uint32_t *pair_want, *pair_lo, *pair_hi;
   // the index's bottom layer, as the candidate test takes it
   uint32_t n_nodes;
   const uint32_t *nodes, *vec2node;
@@ -144,7 +153,9 @@ __global__ __launch_bounds__(64) void ph_auto_finish_kernel(PhAutoArgs a) {
     if (lane == 0) {
       const uint32_t *const bitmap = a.filter ? a.filter + (uint64_t)q * a.filter_stride : nullptr;
       bool ex_cand;
-      if (a.attr_of)
+      if (a.pair_of)
+        ex_cand = ph_auto_pair_candidate(a.pair_of, a.n, a.pair_want[q], a.pair_lo[q], a.pair_hi[q], ex, 0xFFFFFFFFFFFFFFFFull);
+      else if (a.attr_of)
         ex_cand = ph_auto_range_candidate(a.attr_of, a.n, a.range_lo[q], a.range_hi[q], ex, PHNSW_ATTR_NONE);
       else if (a.set_first)
         ex_cand = ph_auto_set_candidate(a.label_of, a.n, a.set_first[q], a.set_first[q + 1u], a.set_values, ex, PHNSW_LABEL_NONE);
@@ -183,7 +194,8 @@ int auto_run(const phnsw_index *ix, const PhAutoCall &c, PhAutoSet &set) {
   const uint32_t ef = (uint32_t)c.sp->number_of_candidates;
   const bool by_label = c.labels != nullptr, by_set = by_label && c.want_first != nullptr;
   const bool by_range = c.attr != nullptr;
-  const bool per_query = by_label || by_range || (c.filter.words && c.filter.stride != 0u);
+  const bool by_pair = c.label_attr != nullptr;
+  const bool per_query = by_label || by_range || by_pair || (c.filter.words && c.filter.stride != 0u);
   PH_TRY(set.ready());
   if (!set.h_head) PH_HIP(hipHostMalloc((void **)&set.h_head, PH_AUTO_HEAD_WORDS * 4u, hipHostMallocDefault));
   // (a call by set: the claim's owner words [nwant] behind everything else)
@@ -195,7 +207,9 @@ int auto_run(const phnsw_index *ix, const PhAutoCall &c, PhAutoSet &set) {
   uint32_t *const walk_len = route_own + nq, *const walk_ids = walk_len + nq;
   float *const walk_d = (float *)(walk_ids + nq * ef);
 
-  if (by_range)
+  if (by_pair)
+    PH_TRY(ph_label_attr_count(c.label_attr, c.pair_want, c.pair_lo, c.pair_hi, nq, counts, c.stream));
+  else if (by_range)
     PH_TRY(ph_attr_count(c.attr, c.range_lo, c.range_hi, nq, counts, c.stream));
   else if (by_set)
     PH_TRY(ph_labels_count_set(c.labels, c.want_first, c.want_values, nq, c.nwant, counts, head + words, c.stream));
@@ -205,7 +219,8 @@ int auto_run(const phnsw_index *ix, const PhAutoCall &c, PhAutoSet &set) {
     PH_TRY(ph_filter_count(ix, c.filter, nb, counts, c.stream));
   PhAutoArgs a = {};
   a.nq = (uint32_t)nq, a.n = (uint32_t)s->n, a.k = c.k, a.ef = ef;
-  a.scan_below = by_range ? ph_auto_scan_below_ranged(c.scan_below)
+  a.scan_below = by_pair    ? ph_auto_scan_below_label_ranged(c.scan_below)
+                 : by_range ? ph_auto_scan_below_ranged(c.scan_below)
                  : by_set ? ph_auto_scan_below_labelset(c.scan_below)
                         : (by_label ? ph_auto_scan_below_labeled(c.scan_below) : ph_auto_scan_below(c.scan_below, per_query));
   a.qids = c.qids, a.exclude = c.exclude;
@@ -223,6 +238,11 @@ int auto_run(const phnsw_index *ix, const PhAutoCall &c, PhAutoSet &set) {
     filter = PhFilter{};
     filter.attr_of = a.attr_of = ph_attr_column(c.attr);
     filter.range_lo = a.range_lo = c.range_lo, filter.range_hi = a.range_hi = c.range_hi;
+  }
+  if (by_pair) {
+    filter = PhFilter{};
+    filter.pair_of = a.pair_of = ph_label_attr_column(c.label_attr);
+    filter.pair_want = a.pair_want = c.pair_want, filter.pair_lo = a.pair_lo = c.pair_lo, filter.pair_hi = a.pair_hi = c.pair_hi;
   }
   a.filter = filter.words, a.filter_stride = filter.words ? filter.stride : 0u, a.per_query = per_query ? 1u : 0u;
   ph_exact_bottom_layer(ix, &a.n_nodes, &a.nodes, &a.vec2node);
@@ -251,7 +271,16 @@ int auto_run(const phnsw_index *ix, const PhAutoCall &c, PhAutoSet &set) {
     PH_HIP(hipStreamSynchronize(c.stream));
     slen = std::min<uint64_t>(set.h_head[1], nq);
   }
-  if (slen && by_range) {
+  if (slen && by_pair) {
+    PhLabelRangedCall x = {};
+    x.queries = c.queries, x.ldq = c.ldq, x.qids = c.qids, x.exclude = c.exclude;
+    x.want = c.pair_want, x.lo = c.pair_lo, x.hi = c.pair_hi;
+    x.nq = slen, x.list = slist;
+    x.k = c.k;
+    x.out_ids = c.out_ids, x.out_d = c.out_d, x.out_len = c.out_len, x.status = c.status;
+    x.stream = c.stream;
+    PH_TRY(ph_label_ranged_device(ix, c.label_attr, x));
+  } else if (slen && by_range) {
     PhRangedCall x = {};
     x.queries = c.queries, x.ldq = c.ldq, x.qids = c.qids, x.exclude = c.exclude, x.lo = c.range_lo, x.hi = c.range_hi;
     x.nq = slen, x.list = slist;
@@ -349,13 +378,19 @@ extern "C" int phnsw_search_filtered_auto_device(const phnsw_index *ix, const fl
 
 // the host form of the three descriptions; lb != nullptr: by label (want: host words [nq]; filter unused) or, with
 // want_first, by set (want_first [nq + 1], want_values: host words; want unused), else by bitmap; at != nullptr: by range
-// (range_lo, range_hi: host words [nq]; lb and filter unused)
+// (range_lo, range_hi: host words [nq]; lb and filter unused); la != nullptr: by label and range (pair_want, range_lo,
+// range_hi: host words [nq]; lb, at and filter unused)
 static int auto_host(const char *call, const phnsw_index *ix, const phnsw_labels *lb, const float *queries, const uint64_t *qids,
                      uint64_t nq, const phnsw_search_params *sp, const uint64_t *exclude, const uint32_t *filter,
                      uint32_t filter_stride_words, const uint32_t *want, const uint32_t *want_first, const uint32_t *want_values,
                      uint64_t k, uint64_t scan_below, uint64_t *out_ids, float *out_d, uint64_t *out_len, uint32_t *out_route,
-                     const phnsw_attr *at = nullptr, const uint32_t *range_lo = nullptr, const uint32_t *range_hi = nullptr) {
+                     const phnsw_attr *at = nullptr, const uint32_t *range_lo = nullptr, const uint32_t *range_hi = nullptr,
+                     const phnsw_label_attr *la = nullptr, const uint32_t *pair_want = nullptr) {
   const bool by_set = lb && want_first;
+  if (la && (!pair_want || !range_lo || !range_hi || nq > 0x7FFFFFFEull)) {
+    ph_set_error("%s: invalid argument (want, lo and hi; nq < 2^31 - 1)", call);
+    return PHNSW_E_INVALID;
+  }
   if (at && (!range_lo || !range_hi || nq > 0x7FFFFFFEull)) {
     ph_set_error("%s: invalid argument (lo and hi; nq < 2^31 - 1)", call);
     return PHNSW_E_INVALID;
@@ -371,7 +406,7 @@ static int auto_host(const char *call, const phnsw_index *ix, const phnsw_labels
     return PHNSW_E_INVALID;
   }
   PhFilter hf = {};
-  if (!lb && !at) PH_TRY(ph_filter_check(ix, filter, filter_stride_words, 0u, call, &hf));
+  if (!lb && !at && !la) PH_TRY(ph_filter_check(ix, filter, filter_stride_words, 0u, call, &hf));
   const phnsw_store *s = ix->store;
   if (by_set) {  // as the walk and the scan by set refuse them: naming the call and the query
     PH_TRY(ph_stored_ids_check(qids, nq, s->n, call, true));
@@ -389,12 +424,19 @@ static int auto_host(const char *call, const phnsw_index *ix, const phnsw_labels
   phnsw_index *mix = const_cast<phnsw_index *>(ix);
   PhAutoSet *set = ph_set_acquire<PhAutoSet>(mix->autos);
   PhHostCall h(mix->autos, set);
-  // extras: route | want, or for a call by set want_first [nq + 1] | want_values [nwant], or for a call by range lo | hi
-  PH_TRY(h.stage_in(s, queries, qids, exclude, nq, (size_t)nq * 3u + (by_set ? 1u + (size_t)nwant : 0u), 1, (uint32_t)k, (uint32_t)k));
+  // extras: route | want, or for a call by set want_first [nq + 1] | want_values [nwant], or for a call by range lo | hi, or for a call by
+  // label and range want | lo | hi
+  PH_TRY(h.stage_in(s, queries, qids, exclude, nq, (size_t)nq * 4u + (by_set ? 1u + (size_t)nwant : 0u), 1, (uint32_t)k, (uint32_t)k));
   PhAutoCall c = {};
   h.fill(c);
   c.filter = hf;
-  if (at) {  // the description of a call by range: 8 bytes per query
+  if (la) {  // the description of a call by label and range: 12 bytes per query
+    uint32_t *const want_dev = h.extra() + nq, *const lo_dev = want_dev + nq, *const hi_dev = lo_dev + nq;
+    PH_HIP(hipMemcpyAsync(want_dev, pair_want, (size_t)nq * 4u, hipMemcpyHostToDevice, h.st));
+    PH_HIP(hipMemcpyAsync(lo_dev, range_lo, (size_t)nq * 4u, hipMemcpyHostToDevice, h.st));
+    PH_HIP(hipMemcpyAsync(hi_dev, range_hi, (size_t)nq * 4u, hipMemcpyHostToDevice, h.st));
+    c.label_attr = la, c.pair_want = want_dev, c.pair_lo = lo_dev, c.pair_hi = hi_dev;
+  } else if (at) {  // the description of a call by range: 8 bytes per query
     uint32_t *const lo_dev = h.extra() + nq, *const hi_dev = lo_dev + nq;
     PH_HIP(hipMemcpyAsync(lo_dev, range_lo, (size_t)nq * 4u, hipMemcpyHostToDevice, h.st));
     PH_HIP(hipMemcpyAsync(hi_dev, range_hi, (size_t)nq * 4u, hipMemcpyHostToDevice, h.st));
@@ -563,6 +605,48 @@ extern "C" int phnsw_search_ranged_auto_device(const phnsw_index *ix, const phns
   }
   PhAutoCall c = {};
   c.attr = at, c.range_lo = lo_dev, c.range_hi = hi_dev;
+  c.queries = queries_dev, c.ldq = ldq, c.qids = qids_dev, c.exclude = exclude_dev, c.nq = nq, c.sp = sp;
+  c.k = (uint32_t)k, c.scan_below = scan_below;
+  c.out_ids = out_ids_dev, c.out_d = out_d_dev, c.out_len = out_len_dev, c.out_route = out_route_dev, c.status = status_dev;
+  c.stream = (hipStream_t)stream;
+  PH_HIP(hipSetDevice(ix->store->device));
+  return ph_auto_device(ix, c);
+} catch (...) { return ph_caught(); }
+
+// ---- by a label and a numeric range
+
+extern "C" int phnsw_search_label_ranged_auto(const phnsw_index *ix, const phnsw_label_attr *h, const float *queries,
+                                              const uint64_t *qids, uint64_t nq, const phnsw_search_params *sp,
+                                              const uint64_t *exclude, const uint32_t *want, const uint32_t *lo, const uint32_t *hi,
+                                              uint64_t k, uint64_t scan_below, uint64_t *out_ids, float *out_d, uint64_t *out_len,
+                                              uint32_t *out_route) try {
+  const char *const call = "phnsw_search_label_ranged_auto";
+  PH_TRY(auto_check(ix, sp, k, call));
+  PH_TRY(ph_label_ranged_check(ix, h, k, call));
+  if (nq == 0) return 0;
+  return auto_host(call, ix, nullptr, queries, qids, nq, sp, exclude, nullptr, 0u, nullptr, nullptr, nullptr, k, scan_below, out_ids,
+                   out_d, out_len, out_route, nullptr, lo, hi, h, want);
+} catch (...) { return ph_caught(); }
+
+extern "C" int phnsw_search_label_ranged_auto_device(const phnsw_index *ix, const phnsw_label_attr *h, const float *queries_dev,
+                                                     uint32_t ldq, const uint32_t *qids_dev, uint64_t nq,
+                                                     const phnsw_search_params *sp, const uint32_t *exclude_dev,
+                                                     const uint32_t *want_dev, const uint32_t *lo_dev, const uint32_t *hi_dev,
+                                                     uint64_t k, uint64_t scan_below, uint32_t *out_ids_dev, float *out_d_dev,
+                                                     uint32_t *out_len_dev, uint32_t *out_route_dev, uint32_t *status_dev,
+                                                     void *stream) try {
+  const char *const call = "phnsw_search_label_ranged_auto_device";
+  PH_TRY(auto_check(ix, sp, k, call));
+  PH_TRY(ph_label_ranged_check(ix, h, k, call));
+  if (nq == 0) return 0;
+  if (!ph_device_queries_ok(ix, queries_dev, qids_dev, ldq) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev ||
+      !want_dev || !lo_dev || !hi_dev || !ph_auto_nq_valid(nq) || nq > 0x7FFFFFFEull) {
+    ph_set_error("%s: invalid argument (queries or qids, exactly one; outputs; want, lo and hi; queries need ldq >= store ld, "
+                 "multiple of 4, 16-byte base)", call);
+    return PHNSW_E_INVALID;
+  }
+  PhAutoCall c = {};
+  c.label_attr = h, c.pair_want = want_dev, c.pair_lo = lo_dev, c.pair_hi = hi_dev;
   c.queries = queries_dev, c.ldq = ldq, c.qids = qids_dev, c.exclude = exclude_dev, c.nq = nq, c.sp = sp;
   c.k = (uint32_t)k, c.scan_below = scan_below;
   c.out_ids = out_ids_dev, c.out_d = out_d_dev, c.out_len = out_len_dev, c.out_route = out_route_dev, c.status = status_dev;

@@ -69,6 +69,38 @@ PH_ROUTE_HD static inline bool ph_auto_range_candidate(const uint32_t *attr_of, 
   return v < n && ph_range_holds(attr_of[v], lo, hi, none_key);
 }
 
+// ---- a label AND a numeric range per query (phnsw_search_batch_label_ranged, phnsw_search_label_ranged_auto): pair_of
+// [n] holds the composite (label << 32) | key of a listed vector and none_pair (UINT64_MAX) elsewhere; a vector passes
+// iff lo64 <= pair <= hi64 and the pair is a listed one, with lo64 = want << 32 | lo and hi64 = want << 32 | hi.  An
+// empty range (lo > hi) gives lo64 > hi64, and a query that wants the NONE label can only be met by none_pair, which the
+// third term refuses: both pass nothing without a test of want or of the bounds.  Used by the search kernels'
+// label-range mode (search_kernels.h), by filter_auto.hip and by tests/cpp/test_label_range_plan.cpp.
+// scan_below == 0 of the routed call by label and range: UNMEASURED.  This is the ranged figure above, itself
+// unmeasured; scripts/bench_label_ranged.py --crossover measures it (profiles/label_ranged/README.md)
+#define PH_AUTO_SCAN_BELOW_LABEL_RANGED PH_AUTO_SCAN_BELOW_RANGED
+PH_ROUTE_HD static inline uint64_t ph_auto_scan_below_label_ranged(uint64_t scan_below) {
+  return scan_below != 0u ? scan_below : PH_AUTO_SCAN_BELOW_LABEL_RANGED;
+}
+// the test of one composite, the form the walk's lanes run
+PH_ROUTE_HD static inline bool ph_pair_holds(uint64_t pair, uint64_t lo64, uint64_t hi64, uint64_t none_pair) {
+  return pair >= lo64 && pair <= hi64 && pair != none_pair;
+}
+PH_ROUTE_HD static inline uint64_t ph_pair_bound(uint32_t want, uint32_t key) { return ((uint64_t)want << 32) | (uint64_t)key; }
+// ph_pair_holds(pair, ph_pair_bound(want, lo), ph_pair_bound(want, hi), none_pair) word by word, equal to it for every
+// input: the composites order by the label first, so both 64-bit compares hold iff the label word IS want and the key
+// word lies inside [lo, hi].  The form the search kernels run: three wave-uniform words per query, no 64-bit bound to
+// put together per lane (profiles/label_ranged)
+PH_ROUTE_HD static inline bool ph_pair_holds_words(uint64_t pair, uint32_t want, uint32_t lo, uint32_t hi, uint64_t none_pair) {
+  const uint32_t lbl = (uint32_t)(pair >> 32), key = (uint32_t)pair;
+  return lbl == want && key >= lo && key <= hi && pair != none_pair;
+}
+// e of ph_auto_full_len for a call by label and range: exclude[q] is a candidate iff it is listed under want with a key
+// inside [lo, hi]
+PH_ROUTE_HD static inline bool ph_auto_pair_candidate(const uint64_t *pair_of, uint32_t n, uint32_t want, uint32_t lo, uint32_t hi,
+                                                      uint32_t v, uint64_t none_pair) {
+  return v < n && ph_pair_holds(pair_of[v], ph_pair_bound(want, lo), ph_pair_bound(want, hi), none_pair);
+}
+
 // ---- a SET of labels per query (phnsw_search_batch_labelset, phnsw_search_labelset_auto): want_first [nq + 1] offsets
 // into want_values [nwant].  Used by the search kernels' set mode (search_kernels.h), by filter_auto.hip and by
 // tests/cpp/test_labelset_route.cpp.

@@ -103,10 +103,11 @@ static inline void ph_handle_sets_free(PhCallPool &pool) {
 
 // the key of a vector as a handle lists it -- its value, or NONE (PHNSW_LABEL_NONE and PHNSW_ATTR_NONE are one word)
 // where the vector is not listed -- and the values of the construction's sort.  (A kernel of the header: each unit
-// launches its own copy.)
-static __global__ __launch_bounds__(256) void ph_label_key_kernel(const uint32_t *labels, uint32_t n, uint32_t n_nodes,
-                                                                  const uint32_t *nodes, const uint32_t *vec2node, uint32_t *keys,
-                                                                  uint32_t *iota) {
+// launches its own copy; filter_label_ranged.hip writes composites and launches none.)
+[[maybe_unused]] static __global__ __launch_bounds__(256) void ph_label_key_kernel(const uint32_t *labels, uint32_t n,
+                                                                                   uint32_t n_nodes, const uint32_t *nodes,
+                                                                                   const uint32_t *vec2node, uint32_t *keys,
+                                                                                   uint32_t *iota) {
   const uint32_t nlim = ph_exact_id_limit(n, n_nodes, nodes, vec2node);
   for (uint64_t v = (uint64_t)blockIdx.x * 256u + threadIdx.x; v < n; v += (uint64_t)gridDim.x * 256u) {
     const bool listed = v < nlim && (!vec2node || vec2node[v] != PH_EMPTY32);

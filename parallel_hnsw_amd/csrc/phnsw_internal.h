@@ -240,6 +240,11 @@ struct PhFilter {
   // ... or its range form: attr_of != nullptr, the column [n] of a phnsw_attr handle (PHNSW_ATTR_NONE where a vector is
   // not listed), range_lo and range_hi [nq], the inclusive bounds of each query; nothing of the forms above goes with it
   const uint32_t *attr_of, *range_lo, *range_hi;
+  // ... or its label-range form: pair_of != nullptr, the column [n] of a phnsw_label_attr handle (the composite
+  // (label << 32) | key of a listed vector, UINT64_MAX elsewhere), pair_want, pair_lo and pair_hi [nq], the label and
+  // the inclusive bounds of each query; nothing of the forms above goes with it
+  const uint64_t *pair_of;
+  const uint32_t *pair_want, *pair_lo, *pair_hi;
 };
 
 // per-slice results of an exact scan that was cut into slices (filter_exact.hip): [nq][slices][k] keys from
@@ -418,6 +423,12 @@ struct PhSearchArgs {
   // PHNSW_ATTR_NONE elsewhere; range_lo / range_hi [nq], the inclusive bounds of query q.  nullptr = not a range launch;
   // never with a bitmap, a label or a set, and never collecting.  (At the end, like the pairs above.)
   const uint32_t *attr_of, *range_lo, *range_hi;
+  // the filter by a label and a numeric range (search_label_ranged.hip): pair_of [n], the composite (label << 32) | key
+  // of every listed vector and UINT64_MAX elsewhere; pair_want / pair_lo / pair_hi [nq], the label and the inclusive
+  // bounds of query q.  nullptr = not a label-range launch; never with a bitmap, a label, a set or a range, and never
+  // collecting.  (At the end, like the pairs above.)
+  const uint64_t *pair_of;
+  const uint32_t *pair_want, *pair_lo, *pair_hi;
 };
 
 uint32_t ph_default_ovf_cap(uint32_t ef);
@@ -592,6 +603,10 @@ struct PhAutoCall {
   // filter and labels are then unused
   const phnsw_attr *attr;
   const uint32_t *range_lo, *range_hi;  // [nq]
+  // the label-range form (phnsw_search_label_ranged_auto): candidates = the listed vectors with label pair_want[q] and
+  // pair_lo[q] <= key <= pair_hi[q]; filter, labels and attr are then unused
+  const phnsw_label_attr *label_attr;
+  const uint32_t *pair_want, *pair_lo, *pair_hi;  // [nq]
   uint32_t k;
   uint64_t scan_below;  // 0 = the library default, UINT64_MAX = always scan (filter_route.h)
   uint32_t *out_ids;    // [nq][k]
@@ -664,6 +679,31 @@ const uint32_t *ph_attr_column(const phnsw_attr *at);
 // out_count_dev[q] = the length of the span of [lo_dev[q], hi_dev[q]] (phnsw_attr_count_device without its checks)
 int ph_attr_count(const phnsw_attr *at, const uint32_t *lo_dev, const uint32_t *hi_dev, uint64_t nq, uint32_t *out_count_dev,
                   hipStream_t stream);
+// The request of one exact top-k scan over the spans of a column sorted by (label, key) (ph_label_ranged_device,
+// filter_label_ranged.hip): PhRangedCall with the wanted label beside the bounds; list as there
+struct PhLabelRangedCall {
+  const float *queries;
+  uint32_t ldq;
+  const uint32_t *qids, *exclude, *want, *lo, *hi;
+  uint64_t nq;
+  uint32_t k;
+  uint32_t *out_ids;
+  float *out_d;
+  uint32_t *out_len, *status;
+  hipStream_t stream;
+  const uint32_t *list;
+};
+int ph_label_ranged_device(const phnsw_index *ix, const phnsw_label_attr *h, const PhLabelRangedCall &c);
+// a null handle, one made for another index or before the index changed: PHNSW_E_INVALID, ph_labels_fresh's wording
+int ph_label_attr_fresh(const phnsw_index *ix, const phnsw_label_attr *h, const char *call);
+// ph_ranged_check for a label-attribute handle: the same checks in the same order
+int ph_label_ranged_check(const phnsw_index *ix, const phnsw_label_attr *h, uint64_t k, const char *call);
+// pair_of [n] of a handle: the composite of every listed vector, UINT64_MAX elsewhere (device words)
+const uint64_t *ph_label_attr_column(const phnsw_label_attr *h);
+// out_count_dev[q] = the length of the span of (want_dev[q], [lo_dev[q], hi_dev[q]]) (phnsw_label_attr_count_device
+// without its checks)
+int ph_label_attr_count(const phnsw_label_attr *h, const uint32_t *want_dev, const uint32_t *lo_dev, const uint32_t *hi_dev,
+                        uint64_t nq, uint32_t *out_count_dev, hipStream_t stream);
 void ph_auto_free(phnsw_index *ix);
 void ph_dense_free(phnsw_index *ix);  // filter_dense.hip
 // the checks the table calls make before they look at another argument: index, k, store kind and row length

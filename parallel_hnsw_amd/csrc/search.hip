@@ -187,6 +187,7 @@ static PhKernelChoice pick_search_kernel(const phnsw_store *s, uint32_t ef_max, 
   if (mode == PH_FM_LABEL && k.fn) k.fn = ph_pick_labeled_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
   if (mode == PH_FM_LABELSET && k.fn) k.fn = ph_pick_labelset_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
   if (mode == PH_FM_RANGE && k.fn) k.fn = ph_pick_ranged_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
+  if (mode == PH_FM_LABEL_RANGE && k.fn) k.fn = ph_pick_label_ranged_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
   // the collecting twins: the new calls only (PhSearchArgs::collect_k), and only the last launch of their descent
   if (mode == (PH_FM_BITMAP | PH_FM_COLLECT) && k.fn)
     k.fn = ph_pick_collect_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
@@ -336,7 +337,9 @@ static int search_launch_dense(PhWorkspace &ws, PhSearchArgs &a, hipStream_t str
     ph_set_error("a collecting search has no dense-only launch");
     return PHNSW_E_UNSUPPORTED;
   }
-  ph_search_fn fn = mode == PH_FM_RANGE
+  ph_search_fn fn = mode == PH_FM_LABEL_RANGE
+                        ? ph_pick_label_ranged_dense(capc)
+                    : mode == PH_FM_RANGE
                         ? ph_pick_ranged_dense(capc)
                     : mode == PH_FM_LABELSET
                         ? ph_pick_labelset_dense(capc)
@@ -434,6 +437,14 @@ int ph_search_launch(const phnsw_index *ix, PhWorkspace &ws, PhSearchArgs &a, hi
   if (mode & PH_FM_RANGE) {  // a range launch carries the attribute column and both bounds, and nothing of the other modes
     if ((mode & PH_FM_COLLECT) || a.filter || a.label_of || a.label_want || a.set_first || !a.range_lo || !a.range_hi) {
       ph_set_error("a search by range takes the attribute column and its two bounds alone: no bitmap, no label, no set, not collecting");
+      return PHNSW_E_UNSUPPORTED;
+    }
+  }
+  if (mode & PH_FM_LABEL_RANGE) {  // a label-range launch carries the pair column and the three per-query arrays and nothing of the other modes
+    if ((mode & PH_FM_COLLECT) || a.filter || a.label_of || a.label_want || a.set_first || a.attr_of || a.range_lo || a.range_hi ||
+        !a.pair_want || !a.pair_lo || !a.pair_hi) {
+      ph_set_error("a search by label and range takes the pair column, its labels and its two bounds alone: no bitmap, no label, "
+                   "no set, no range, not collecting");
       return PHNSW_E_UNSUPPORTED;
     }
   }

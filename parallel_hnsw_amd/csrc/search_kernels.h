@@ -3,8 +3,8 @@
 // twins, the kernels of a search restricted to an allow-list of VectorIds, search_labeled.hip their label twins, the same
 // restriction read from a label column; search_collect.hip and search_collect_labeled.hip the collecting twins of those
 // two (PH_FM_COLLECT); search_labelset.hip the twins over a SET of labels per query (PH_FM_LABELSET); search_ranged.hip
-// the twins over a numeric range of an attribute column per query (PH_FM_RANGE).  Seven units so that they compile side
-// by side.
+// the twins over a numeric range of an attribute column per query (PH_FM_RANGE); search_label_ranged.hip the twins over a
+// label and a numeric range per query (PH_FM_LABEL_RANGE).  Eight units so that they compile side by side.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -110,17 +110,28 @@ __device__ __forceinline__ bool vis_insert(uint32_t *H, uint32_t slots, uint32_t
 //                 ph_range_holds (filter_route.h): an empty range (lo > hi) passes nothing without a scalar test of the
 //                 bounds, which is what cost the label twins a wave per SIMD.  Never with a bitmap, a label or a set,
 //                 and there is no collecting twin (profiles/ranged).
+//   PH_FM_LABEL_RANGE  a column of composites (a.pair_of: (label << 32) | key of a listed vector, UINT64_MAX elsewhere)
+//                 and a label and two inclusive bounds per query (a.pair_want, a.pair_lo, a.pair_hi): VectorId v passes iff
+//                 want << 32 | lo <= pair_of[v] <= want << 32 | hi and pair_of[v] is not UINT64_MAX -- ONE 8-byte load per
+//                 lane.  Written per lane, ph_pair_holds_words (filter_route.h: ph_pair_holds word by word): lo > hi and a
+//                 wanted NONE label pass nothing without a scalar test of want or the bounds (what cost the label twins a
+//                 wave per SIMD).  The three words of the query are read where the test runs (rfl32: wave-uniform scalar
+//                 loads at the layer tails), NOT once per query in front of the walk: held across the walk they cost
+//                 ph_search_kernel_dense<2> 20 bytes of scratch that its range sibling does not use, as two aligned 64-bit
+//                 bounds and as three words alike (profiles/label_ranged).  Never with a bitmap, a label, a set or a
+//                 range, and there is no collecting twin.
 // A mode of the body and not a run-time test of the pointers: the test alone cost 19 of the 88 kernels scratch
 // (profiles/filter), so the filtered instances exist beside the others and are picked only when a filter is given.
 //   PH_FM_COLLECT  a bit on top of PH_FM_BITMAP / PH_FM_LABEL: the collecting walk (phnsw_search_collect*, search_collect.hip,
 //                  search_collect_labeled.hip).  The descent is the PLAIN search's -- the layer tails apply `exclude` only --
 //                  and the walk of the last layer keeps, beside the layer's queue, the a.collect_k best evaluated rows
 //                  that pass the filter (`kq`, below); those are the result row.  Only ever the last launch of a descent.
-enum : int { PH_FM_NONE = 0, PH_FM_BITMAP = 1, PH_FM_LABEL = 2, PH_FM_COLLECT = 4, PH_FM_LABELSET = 8, PH_FM_RANGE = 16 };
+enum : int { PH_FM_NONE = 0, PH_FM_BITMAP = 1, PH_FM_LABEL = 2, PH_FM_COLLECT = 4, PH_FM_LABELSET = 8, PH_FM_RANGE = 16, PH_FM_LABEL_RANGE = 32 };
 #define ST_SET_RANGE 8u  // the status of a query whose set range is not sound: phnsw_search_exact_labelset_device's value
 // the mode a launch's arguments ask for
 static inline int ph_filter_mode(const PhSearchArgs &a) {
-  const int where = a.attr_of ? PH_FM_RANGE
+  const int where = a.pair_of   ? PH_FM_LABEL_RANGE
+                    : a.attr_of ? PH_FM_RANGE
                               : (a.set_first ? PH_FM_LABELSET : (a.label_of ? PH_FM_LABEL : (a.filter ? PH_FM_BITMAP : PH_FM_NONE)));
   return where | (a.collect_k ? PH_FM_COLLECT : PH_FM_NONE);
 }
@@ -129,7 +140,7 @@ template <int CAPC, class Dist, bool INSTR = false, bool BIG = false, int FILT =
 __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
   extern __shared__ uint32_t smem[];
   constexpr int CAP = CAPC * 64;
-  constexpr int FM = FILT & (PH_FM_BITMAP | PH_FM_LABEL | PH_FM_LABELSET | PH_FM_RANGE);  // where the filter is read from
+  constexpr int FM = FILT & (PH_FM_BITMAP | PH_FM_LABEL | PH_FM_LABELSET | PH_FM_RANGE | PH_FM_LABEL_RANGE);  // where the filter is read from
   constexpr bool COLLECT = (FILT & PH_FM_COLLECT) != 0;
   constexpr int TAILF = COLLECT ? PH_FM_NONE : FM;  // closest_vectors' `include` beyond `exclude`: none in a collecting walk
   uint32_t *Cid = smem;                    // running candidates: VectorIds (search.rs:110)
@@ -266,6 +277,8 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
         return ph_set_holds(a.label_of[v], set_b, set_e, a.set_values, PHNSW_LABEL_NONE);
       } else if constexpr (FM == PH_FM_RANGE) {
         return ph_range_holds(a.attr_of[v], range_lo, range_hi, PHNSW_ATTR_NONE);
+      } else if constexpr (FM == PH_FM_LABEL_RANGE) {
+        return ph_pair_holds_words(a.pair_of[v], rfl32(a.pair_want[q]), rfl32(a.pair_lo[q]), rfl32(a.pair_hi[q]), 0xFFFFFFFFFFFFFFFFull);
       } else {
         return true;
       }
@@ -1235,6 +1248,9 @@ ph_search_fn ph_pick_labelset_dense(int capc);
 // the range twins: search_ranged.hip
 ph_search_fn ph_pick_ranged_kernel(int family, int capc, int nv, int pqr_m, bool pq_global);
 ph_search_fn ph_pick_ranged_dense(int capc);
+// the label-range twins: search_label_ranged.hip
+ph_search_fn ph_pick_label_ranged_kernel(int family, int capc, int nv, int pqr_m, bool pq_global);
+ph_search_fn ph_pick_label_ranged_dense(int capc);
 // the collecting twins (PH_FM_COLLECT over the bitmap and over the label column): search_collect.hip and
 // search_collect_labeled.hip.  No dense-only twin: a collecting kernel runs the last layer of a descent, and the
 // dense-only launch of a split descent never holds it (api.hip)

@@ -322,6 +322,125 @@ class Attribute:
             pass
 
 
+class LabeledAttribute:
+    """phnsw_label_attr: one label AND one numeric value per vector of `hnsw`'s store, sorted once on the device by the
+    composite (label << 32) | key, then by id, so that every pair (label, lo <= value <= hi) is one contiguous span
+    (twenty bytes per vector).  labels: as Labels takes them (integers within u32, -1 or LABEL_NONE = none); values and
+    missing: as Attribute takes them.  A vector is listed iff it has a label AND a value and the index's bottom layer
+    holds it.  The handle is a snapshot like Labels and Attribute.  Keep `hnsw` alive while it is used.
+    search_exact_label_ranged, search_batch_label_ranged and search_label_ranged take it."""
+
+    def __init__(self, hnsw, labels, values, missing=None):
+        self._h = None
+        if not isinstance(hnsw, Hnsw):
+            raise TypeError("LabeledAttribute: hnsw must be an Hnsw")
+        n = int(hnsw.store.n)
+        lab = pack_labels(labels, n, "LabeledAttribute: labels")
+        if values is None:
+            raise ValueError("LabeledAttribute: values: an array of shape [%d] is required" % n)
+        a = np.asarray(values)
+        if a.ndim != 1 or a.shape[0] != n:
+            raise ValueError("LabeledAttribute: values: an array of shape [%d], got %r" % (n, a.shape))
+        if missing is not None:
+            m = np.asarray(missing)
+            if m.dtype != np.bool_ or m.shape != a.shape:
+                raise ValueError("LabeledAttribute: missing: a bool mask of shape [%d], got %s %r" % (n, m.dtype, m.shape))
+            a = a.copy()
+            a[m] = 0  # whatever stood there (a NaN, 0xFFFFFFFF) is no value
+        keys = attr_keys(a, "LabeledAttribute: values").copy()
+        bad = np.flatnonzero(keys == ATTR_NONE)  # int32: 2**31 - 1 maps onto it (as a bound: "no upper end")
+        if len(bad):
+            raise ValueError("LabeledAttribute: values: index %d: %r maps onto ATTR_NONE; mark the row missing"
+                             % (int(bad[0]), a[bad[0]]))
+        if missing is not None:
+            keys[m] = ATTR_NONE
+        h = C.c_void_p()
+        check(lib().phnsw_label_attr_create(hnsw._h, _p(lab), _p(keys), len(keys), C.byref(h)))
+        self._h, self.hnsw, self.dtype = h, hnsw, a.dtype
+
+    @classmethod
+    def from_device(cls, hnsw, labels_ptr, keys_ptr, dtype=np.uint32, stream=0):
+        """phnsw_label_attr_create_device: labels_ptr = u32 labels, keys_ptr = u32 KEYS, [store n] each in device memory
+        (integers; LABEL_NONE = no label, ATTR_NONE = no value), read on `stream`, which is synchronised.  dtype: what
+        key() maps bounds from"""
+        if not isinstance(hnsw, Hnsw):
+            raise TypeError("LabeledAttribute.from_device: hnsw must be an Hnsw")
+        dtype = np.dtype(dtype)
+        if dtype not in (np.dtype(np.uint32), np.dtype(np.int32), np.dtype(np.float32)):
+            raise TypeError("LabeledAttribute.from_device: dtype uint32, int32 or float32, got %s" % dtype)
+        self = cls.__new__(cls)
+        self._h = None
+        h = C.c_void_p()
+        check(lib().phnsw_label_attr_create_device(hnsw._h, C.c_void_p(labels_ptr or None), C.c_void_p(keys_ptr or None),
+                                                   int(hnsw.store.n), C.c_void_p(stream or None), C.byref(h)))
+        self._h, self.hnsw, self.dtype = h, hnsw, dtype
+        return self
+
+    key = Attribute.key        # the u32 key of a bound given in the column's dtype
+    bounds = Attribute.bounds  # lo / hi of a call -> u32 keys [nq] each, Attribute's rules
+
+    @staticmethod
+    def wanted(call, want, nq):
+        """want of a call -> u32 labels [nq]: a scalar is broadcast, an array is [nq]; -1 or LABEL_NONE = none (an empty
+        row).  Errors name the call and the first offending query"""
+        if want is None:
+            raise ValueError("%s: want: a label or an integer array of shape [%d] is required" % (call, nq))
+        a = np.asarray(want)
+        if a.ndim == 0:
+            a = np.full(nq, a[()])
+        if a.dtype.kind not in "iu":
+            raise TypeError("%s: want: an integer array, got %s" % (call, a.dtype))
+        if a.ndim != 1 or a.shape[0] != nq:
+            raise ValueError("%s: want: a scalar or an integer array of shape [%d], got %r" % (call, nq, a.shape))
+        wide = a.astype(np.uint64) if a.dtype == np.uint64 else a.astype(np.int64)
+        bad = np.flatnonzero(wide > LABEL_NONE) if a.dtype == np.uint64 else np.flatnonzero((wide < -1) | (wide > LABEL_NONE))
+        if len(bad):
+            raise ValueError("%s: want: query %d: %r is not a 32-bit label, -1 or LABEL_NONE" % (call, int(bad[0]), a[bad[0]]))
+        return pack_labels(a, nq, "%s: want" % call)
+
+    def info(self):
+        """(n, listed, nlabels, longest): the vector count the handle was made for, the listed vectors, the distinct
+        labels that list a row, the most rows listed under one label"""
+        a, b, c, d = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(lib().phnsw_label_attr_info(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return int(a.value), int(b.value), int(c.value), int(d.value)
+
+    listed = property(lambda self: self.info()[1])
+
+    def count_device(self, nq, want, lo, hi, out_count, stream=0):
+        """phnsw_label_attr_count_device: device pointers as integers, u32 [nq] each (lo and hi are KEYS); enqueued"""
+        check(lib().phnsw_label_attr_count_device(self._h, C.c_void_p(want or None), C.c_void_p(lo or None), C.c_void_p(hi or None),
+                                                  int(nq), C.c_void_p(out_count or None), C.c_void_p(stream or None)))
+
+    def count(self, want, lo, hi):
+        """the candidates of every (label, range) pair, u32 [nq]: filter_count's figure for the equivalent bitmaps.  want
+        / lo / hi as the searches take them, at least one an array.  Host convenience over count_device (needs torch)"""
+        import torch
+        nq = max([len(np.atleast_1d(x)) for x in (want, lo, hi) if x is not None] or [1])
+        w32 = self.wanted("LabeledAttribute.count", want, nq)
+        l32, h32 = self.bounds("LabeledAttribute.count", lo, hi, nq)
+        dev = torch.device("cuda", getattr(self.hnsw.store, "device", 0))
+        wd = torch.from_numpy(w32.view(np.int32)).to(dev)
+        ld = torch.from_numpy(l32.view(np.int32)).to(dev)
+        hd = torch.from_numpy(h32.view(np.int32)).to(dev)
+        out = torch.zeros(max(nq, 1), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize(dev)
+        self.count_device(nq, wd.data_ptr(), ld.data_ptr(), hd.data_ptr(), out.data_ptr())
+        torch.cuda.synchronize(dev)
+        return out.cpu().numpy().view(np.uint32)[:nq]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().phnsw_label_attr_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Labels:
     """phnsw_labels: one label per vector of `hnsw`'s store, turned once into posting lists on the device (the ascending
     VectorIds of every label).  labels: an integer array [n] within u32; -1 or LABEL_NONE = the vector is not listed.  A
@@ -1479,6 +1598,131 @@ class Hnsw:
             C.c_void_p(exclude or None), C.c_void_p(lo or None), C.c_void_p(hi or None), int(k), int(scan_below),
             C.c_void_p(out_ids), C.c_void_p(out_d), C.c_void_p(out_len), C.c_void_p(out_route or None), C.c_void_p(status),
             C.c_void_p(stream or None)))
+
+    def _label_ranged_args(self, call, queries, qids, attr, want, lo, hi):
+        """the checks the calls by label and range make before they reach the library: a LabeledAttribute, exactly one of
+        queries / qids, want as LabeledAttribute.wanted and lo / hi as Attribute.bounds take them.  Returns (q, qi, nq,
+        want u32 [nq], lo u32 [nq], hi u32 [nq])"""
+        if not isinstance(attr, LabeledAttribute):
+            raise TypeError("%s: attr must be a LabeledAttribute made for this index" % call)
+        if (queries is None) == (qids is None):
+            raise ValueError("%s: pass queries or qids (exactly one)" % call)
+        q = qi = None
+        if queries is not None:
+            q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+            if q.shape[1] != self.store.dim:
+                raise ValueError("%s: queries of shape [nq, %d], got %r" % (call, self.store.dim, q.shape))
+            nq = q.shape[0]
+        else:
+            qi = np.ascontiguousarray(qids, dtype=np.uint64)
+            nq = len(qi)
+        w32 = attr.wanted(call, want, nq)
+        l32, h32 = attr.bounds(call, lo, hi, nq)
+        return q, qi, nq, w32, l32, h32
+
+    def search_exact_label_ranged(self, queries=None, qids=None, attr=None, want=None, lo=None, hi=None, exclude=None, k=10):
+        """search_exact_filtered by a label and a numeric range (phnsw_search_exact_label_ranged): query i may return the
+        vectors `attr` lists under label want[i] with lo[i] <= value <= hi[i], both ends inclusive -- the same rows as
+        search_exact_filtered(allow=(those vectors)), bit for bit, from one span of the sorted column instead of a
+        bitmap.  attr: a LabeledAttribute made for this index; want: a label or an array [nq] (-1 or LABEL_NONE: an empty
+        row); lo / hi: scalars (broadcast), arrays [nq] in the column's dtype, or None for an open end; lo > hi is an
+        empty row.  Exactly one of queries / qids.  Not measured yet (profiles/label_ranged/README.md).
+        Returns (ids[nq, k] u64, d[nq, k] f32, len[nq])"""
+        q, qi, nq, w32, l32, h32 = self._label_ranged_args("search_exact_label_ranged", queries, qids, attr, want, lo, hi)
+        w = max(int(k), 0)
+        ids = np.empty((nq, w), dtype=np.uint64)
+        d = np.empty((nq, w), dtype=np.float32)
+        ln = np.zeros(nq, dtype=np.uint64)
+        ex = None if exclude is None else np.ascontiguousarray(exclude, dtype=np.uint64)
+        check(lib().phnsw_search_exact_label_ranged(self._h, attr._h, _p(q), _p(qi), nq, _p(ex), _p(w32), _p(l32), _p(h32),
+                                                    int(k), _p(ids), _p(d), _p(ln)))
+        return ids, d, ln
+
+    def search_exact_label_ranged_device(self, attr, nq, k, out_ids, out_d, out_len, status, queries=0, ldq=0, qids=0,
+                                         exclude=0, want=0, lo=0, hi=0, stream=0):
+        """zero-copy form (phnsw_search_exact_label_ranged_device): device pointers as integers, u32 ids [nq, k] padded
+        with 0xFFFFFFFF; want = u32 labels [nq], lo, hi = u32 KEYS [nq] (LabeledAttribute.key).  status 4 = a stored query
+        id at or past n (an empty row).  Enqueued on `stream`; never synchronises it"""
+        if not isinstance(attr, LabeledAttribute):
+            raise TypeError("search_exact_label_ranged_device: attr must be a LabeledAttribute made for this index")
+        check(lib().phnsw_search_exact_label_ranged_device(
+            self._h, attr._h, C.c_void_p(queries or None), ldq, C.c_void_p(qids or None), nq, C.c_void_p(exclude or None),
+            C.c_void_p(want or None), C.c_void_p(lo or None), C.c_void_p(hi or None), int(k), C.c_void_p(out_ids),
+            C.c_void_p(out_d), C.c_void_p(out_len), C.c_void_p(status), C.c_void_p(stream or None)))
+
+    def search_batch_label_ranged(self, queries=None, qids=None, sp=None, attr=None, want=None, lo=None, hi=None, strict=False,
+                                  exclude=None, upto=0, stats=False, k=None):
+        """search_batch_filtered by a label and a numeric range (phnsw_search_batch_label_ranged): the graph walk of query
+        i restricted to the vectors `attr` lists under want[i] with lo[i] <= value <= hi[i] -- the rows, lengths and stats
+        of search_batch_filtered(allow=(those vectors)), bit for bit, without a bitmap per query: the kernels test the
+        handle's column of composites, one 8-byte load per id.  A post-filter like search_batch_filtered
+        (search_label_ranged completes rows); the entry vector may be returned although it does not pass, strict=True
+        removes it.  set_filter's default is not consulted.  Not measured yet (profiles/label_ranged/README.md).
+        Returns (ids[nq, k or ef] u64, d f32, len[nq]) and the stats with stats=True"""
+        q, qi, nq, w32, l32, h32 = self._label_ranged_args("search_batch_label_ranged", queries, qids, attr, want, lo, hi)
+        sp = sp or SearchParameters()
+        ef = sp.number_of_candidates
+        w = ef if k is None else int(k)
+        if w < 0:
+            raise ValueError("search_batch_label_ranged: k must not be negative")
+        ids = np.empty((nq, w), dtype=np.uint64)
+        d = np.empty((nq, w), dtype=np.float32)
+        ln = np.zeros(nq, dtype=np.uint64)
+        st = np.zeros((nq, 2), dtype=np.uint64) if stats else None
+        ex = None if exclude is None else np.ascontiguousarray(exclude, dtype=np.uint64)
+        check(lib().phnsw_search_batch_label_ranged(self._h, attr._h, _p(q), _p(qi), nq, C.byref(sp), upto, _p(ex), _p(w32),
+                                                    _p(l32), _p(h32), FILTER_STRICT if strict else 0, 0 if k is None else w,
+                                                    _p(ids), _p(d), _p(ln), _p(st)))
+        return (ids, d, ln, st) if stats else (ids, d, ln)
+
+    def search_batch_label_ranged_device(self, attr, nq, sp, out_ids, out_d, out_len, status, queries=0, ldq=0, qids=0,
+                                         exclude=0, want=0, lo=0, hi=0, strict=False, out_stats=0, upto=0, stream=0):
+        """zero-copy form (phnsw_search_batch_label_ranged_device): search_batch_filtered_device with want = u32 labels
+        [nq] and lo, hi = u32 KEYS [nq] (device pointers, alive until the work on `stream` is done) in place of the
+        bitmaps.  Enqueued on `stream`; never synchronises it"""
+        if not isinstance(attr, LabeledAttribute):
+            raise TypeError("search_batch_label_ranged_device: attr must be a LabeledAttribute made for this index")
+        check(lib().phnsw_search_batch_label_ranged_device(
+            self._h, attr._h, C.c_void_p(queries or None), ldq, C.c_void_p(qids or None), nq, C.byref(sp), upto,
+            C.c_void_p(exclude or None), C.c_void_p(want or None), C.c_void_p(lo or None), C.c_void_p(hi or None),
+            FILTER_STRICT if strict else 0, C.c_void_p(out_ids), C.c_void_p(out_d), C.c_void_p(out_len),
+            C.c_void_p(out_stats or None), C.c_void_p(status), C.c_void_p(stream or None)))
+
+    def search_label_ranged(self, queries=None, qids=None, sp=None, attr=None, want=None, lo=None, hi=None, exclude=None, k=10,
+                            scan_below=0, route=False):
+        """search_filtered by a label and a numeric range (phnsw_search_label_ranged_auto): per query the span scan
+        (search_exact_label_ranged) where the pair holds few rows (count <= scan_below, or count * number_of_candidates <
+        k * vector_count), the strict graph walk otherwise, and the scan again for every query whose walk came back
+        short.  Every row holds exactly min(k, count - e) entries and only listed vectors of the label inside the range
+        (e = 1 iff exclude[i] is one of them): the rows of search_filtered with the equivalent per-query bitmaps, bit for
+        bit.  scan_below 0 = the library's threshold, 20 000: UNMEASURED, the ranged figure; 2**64 - 1 = always scan.
+        1 <= k <= sp.number_of_candidates.
+        Returns (ids[nq, k] u64, d[nq, k] f32, len[nq]) and, with route=True, route[nq] u32: ROUTE_GRAPH, ROUTE_SCAN or
+        ROUTE_GRAPH_THEN_SCAN"""
+        q, qi, nq, w32, l32, h32 = self._label_ranged_args("search_label_ranged", queries, qids, attr, want, lo, hi)
+        sp = sp or SearchParameters()
+        w = max(int(k), 0)
+        ids = np.empty((nq, w), dtype=np.uint64)
+        d = np.empty((nq, w), dtype=np.float32)
+        ln = np.zeros(nq, dtype=np.uint64)
+        rt = np.zeros(nq, dtype=np.uint32) if route else None
+        ex = None if exclude is None else np.ascontiguousarray(exclude, dtype=np.uint64)
+        check(lib().phnsw_search_label_ranged_auto(self._h, attr._h, _p(q), _p(qi), nq, C.byref(sp), _p(ex), _p(w32), _p(l32),
+                                                   _p(h32), int(k), int(scan_below), _p(ids), _p(d), _p(ln), _p(rt)))
+        return (ids, d, ln, rt) if route else (ids, d, ln)
+
+    def search_label_ranged_device(self, attr, nq, sp, k, out_ids, out_d, out_len, status, queries=0, ldq=0, qids=0, exclude=0,
+                                   want=0, lo=0, hi=0, scan_below=0, out_route=0, stream=0):
+        """device form (phnsw_search_label_ranged_auto_device): device pointers as integers, u32 ids [nq, k] padded with
+        0xFFFFFFFF; want = u32 labels [nq], lo, hi = u32 KEYS [nq]; out_route u32 [nq] or 0.  Like search_filtered_device
+        it synchronises `stream`, up to twice"""
+        if not isinstance(attr, LabeledAttribute):
+            raise TypeError("search_label_ranged_device: attr must be a LabeledAttribute made for this index")
+        check(lib().phnsw_search_label_ranged_auto_device(
+            self._h, attr._h, C.c_void_p(queries or None), ldq, C.c_void_p(qids or None), nq, C.byref(sp),
+            C.c_void_p(exclude or None), C.c_void_p(want or None), C.c_void_p(lo or None), C.c_void_p(hi or None), int(k),
+            int(scan_below), C.c_void_p(out_ids), C.c_void_p(out_d), C.c_void_p(out_len), C.c_void_p(out_route or None),
+            C.c_void_p(status), C.c_void_p(stream or None)))
 
     def search_batch_labelset(self, queries=None, qids=None, sp=None, labels=None, want=None, strict=False, exclude=None,
                               upto=0, stats=False, k=None):

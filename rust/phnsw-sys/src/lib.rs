@@ -81,6 +81,10 @@ pub struct phnsw_labels {
 pub struct phnsw_attr {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct phnsw_label_attr {
+    _private: [u8; 0],
+}
 
 /// ProgressMonitor::update / keep_alive  progress.rs:12-16
 pub type phnsw_progress_cb =
@@ -385,6 +389,50 @@ extern "C" {
                                            scan_below: u64, out_ids_dev: *mut u32, out_d_dev: *mut c_float,
                                            out_len_dev: *mut u32, out_route_dev: *mut u32, status_dev: *mut u32,
                                            stream: *mut c_void) -> c_int;
+    // search by a row label and a numeric range: the listed rows sorted once by (label << 32) | key, every pair one span
+    pub fn phnsw_label_attr_create(ix: *const phnsw_index, labels: *const u32, keys: *const u32, n: u64,
+                                   out: *mut *mut phnsw_label_attr) -> c_int;
+    pub fn phnsw_label_attr_create_device(ix: *const phnsw_index, labels_dev: *const u32, keys_dev: *const u32, n: u64,
+                                          stream: *mut c_void, out: *mut *mut phnsw_label_attr) -> c_int;
+    pub fn phnsw_label_attr_info(h: *const phnsw_label_attr, n: *mut u64, listed: *mut u64, nlabels: *mut u64,
+                                 longest: *mut u64) -> c_int;
+    pub fn phnsw_label_attr_count_device(h: *const phnsw_label_attr, want_dev: *const u32, lo_dev: *const u32,
+                                         hi_dev: *const u32, nq: u64, out_count_dev: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn phnsw_label_attr_destroy(h: *mut phnsw_label_attr);
+    pub fn phnsw_search_exact_label_ranged(ix: *const phnsw_index, h: *const phnsw_label_attr, queries: *const c_float,
+                                           qids: *const u64, nq: u64, exclude: *const u64, want: *const u32,
+                                           lo: *const u32, hi: *const u32, k: u64, out_ids: *mut u64, out_d: *mut c_float,
+                                           out_len: *mut u64) -> c_int;
+    pub fn phnsw_search_exact_label_ranged_device(ix: *const phnsw_index, h: *const phnsw_label_attr,
+                                                  queries_dev: *const c_float, ldq: u32, qids_dev: *const u32, nq: u64,
+                                                  exclude_dev: *const u32, want_dev: *const u32, lo_dev: *const u32,
+                                                  hi_dev: *const u32, k: u64, out_ids_dev: *mut u32,
+                                                  out_d_dev: *mut c_float, out_len_dev: *mut u32, status_dev: *mut u32,
+                                                  stream: *mut c_void) -> c_int;
+    pub fn phnsw_search_batch_label_ranged(ix: *const phnsw_index, h: *const phnsw_label_attr, queries: *const c_float,
+                                           qids: *const u64, nq: u64, sp: *const phnsw_search_params, upto_layers: u32,
+                                           exclude: *const u64, want: *const u32, lo: *const u32, hi: *const u32,
+                                           flags: u32, k: u64, out_ids: *mut u64, out_d: *mut c_float, out_len: *mut u64,
+                                           out_stats: *mut u64) -> c_int;
+    pub fn phnsw_search_batch_label_ranged_device(ix: *const phnsw_index, h: *const phnsw_label_attr,
+                                                  queries_dev: *const c_float, ldq: u32, qids_dev: *const u32, nq: u64,
+                                                  sp: *const phnsw_search_params, upto_layers: u32,
+                                                  exclude_dev: *const u32, want_dev: *const u32, lo_dev: *const u32,
+                                                  hi_dev: *const u32, flags: u32, out_ids_dev: *mut u32,
+                                                  out_d_dev: *mut c_float, out_len_dev: *mut u32, out_stats_dev: *mut u32,
+                                                  status_dev: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn phnsw_search_label_ranged_auto(ix: *const phnsw_index, h: *const phnsw_label_attr, queries: *const c_float,
+                                          qids: *const u64, nq: u64, sp: *const phnsw_search_params, exclude: *const u64,
+                                          want: *const u32, lo: *const u32, hi: *const u32, k: u64, scan_below: u64,
+                                          out_ids: *mut u64, out_d: *mut c_float, out_len: *mut u64,
+                                          out_route: *mut u32) -> c_int;
+    pub fn phnsw_search_label_ranged_auto_device(ix: *const phnsw_index, h: *const phnsw_label_attr,
+                                                 queries_dev: *const c_float, ldq: u32, qids_dev: *const u32, nq: u64,
+                                                 sp: *const phnsw_search_params, exclude_dev: *const u32,
+                                                 want_dev: *const u32, lo_dev: *const u32, hi_dev: *const u32, k: u64,
+                                                 scan_below: u64, out_ids_dev: *mut u32, out_d_dev: *mut c_float,
+                                                 out_len_dev: *mut u32, out_route_dev: *mut u32, status_dev: *mut u32,
+                                                 stream: *mut c_void) -> c_int;
     // the collecting search: the plain walk whose last layer keeps the best k allowed rows it evaluates (k <= 64)
     pub fn phnsw_search_collect(ix: *const phnsw_index, queries: *const c_float, qids: *const u64, nq: u64,
                                 sp: *const phnsw_search_params, upto_layers: u32, exclude: *const u64, filter: *const u32,
