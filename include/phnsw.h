@@ -821,7 +821,9 @@ int phnsw_search_ranged_auto_device(const phnsw_index *ix, const phnsw_attr *at,
  * the most rows listed under one label; any output may be NULL.  phnsw_label_attr_count_device writes, per query, the
  * length of its span: phnsw_filter_count_device's figure for the equivalent bitmap; enqueued on `stream`, never
  * synchronises.  phnsw_label_attr_destroy waits for the calls in flight that use the handle; NULL is a no-op.
- * NOT BUILT: a set of labels with a range, 64-bit keys, a tile path for the scan, a collecting twin of the walk. */
+ * A SET of labels with one range is built on the same handle (phnsw_search_exact_labelset_ranged and its siblings,
+ * below).  NOT BUILT: a different range per label of a set, 64-bit keys, a tile path for the scan, a collecting twin of
+ * the walk. */
 typedef struct phnsw_label_attr phnsw_label_attr;
 int phnsw_label_attr_create(const phnsw_index *ix, const uint32_t *labels, const uint32_t *keys, uint64_t n,
                             phnsw_label_attr **out); /* host labels [n], keys [n] */
@@ -892,6 +894,120 @@ int phnsw_search_label_ranged_auto_device(const phnsw_index *ix, const phnsw_lab
                                           const uint32_t *hi_dev, uint64_t k, uint64_t scan_below, uint32_t *out_ids_dev,
                                           float *out_d_dev, uint32_t *out_len_dev, uint32_t *out_route_dev,
                                           uint32_t *status_dev, void *stream);
+/* ---- search by a SET OF ROW LABELS AND A NUMERIC RANGE, `label IN (a, b, c) AND lo <= attribute <= hi`: the rows of my
+ * ACL groups from the last week.  Seven calls over the phnsw_label_attr handle above; no new handle, and the handle's
+ * layout does not change.  The sets of a batch are in CSR form exactly as phnsw_search_exact_labelset takes them:
+ * want_first[nq + 1] (u32, want_first[0] == 0, non-decreasing) and want_values[nwant] (u32 labels), nwant ==
+ * want_first[nq]; S_q = { want_values[i] : want_first[q] <= i < want_first[q+1] }; the device forms also take nwant.
+ * lo[nq] and hi[nq] are u32 keys, inclusive, ONE range per query, shared by every label of that query's set.
+ * Candidates of q, the same in all seven: v is a candidate iff v is listed by the handle, labels[v] is in S_q,
+ * lo[q] <= keys[v] <= hi[q] and v != exclude[q].  A label that occurs twice in S_q counts once; PHNSW_LABEL_NONE in a set
+ * and a label nobody carries contribute nothing; an empty set, or lo > hi, is no error: the row is empty, the length 0,
+ * the status 0; hi == 0xFFFFFFFF means "no upper end within each label".
+ * phnsw_label_attr_count_set_device: out_count[q] = the sum of the span lengths of the DISTINCT labels of S_q --
+ * phnsw_filter_count_device's figure for the equivalent bitmap -- and 0 for a query the exact device form below would
+ * refuse (status 8); enqueued on `stream`, never synchronises.  Its cost is quadratic in the length of a set (a wave per
+ * query tests distinctness in place).  Checks, in this order: null `h`; nq == 0 returns 0; null want_first, lo, hi or
+ * output, null want_values with nwant > 0; nq and nwant below 2^31 - 1 (PHNSW_E_INVALID). */
+int phnsw_label_attr_count_set_device(const phnsw_label_attr *h, const uint32_t *want_first_dev,
+                                      const uint32_t *want_values_dev, const uint32_t *lo_dev, const uint32_t *hi_dev,
+                                      uint64_t nq, uint64_t nwant, uint32_t *out_count_dev, void *stream);
+/* exact top-k over a set of labels and a range.
+ * EQUALITY: the row of every query equals, in ids, distance bits, length and status, the row
+ * phnsw_search_exact_filtered returns for that query with the bitmap
+ * {v : v listed, labels[v] in S_q, lo[q] <= keys[v] <= hi[q]}: ascending (distance, id), equal distances by id ALSO where
+ * the tied rows come from different spans; +inf, padding and 1 <= k <= 1024 as there.  Hence a batch of one-label sets
+ * equals phnsw_search_exact_label_ranged's rows.  The result depends on none of: the order of labels inside a set, the
+ * order of queries in the batch, the knob below.
+ * Checks, in this order: those of phnsw_search_exact_label_ranged (index, k, null or stale `h`, store kind and its
+ * limits); nq == 0 returns 0; queries or qids, exactly one; outputs, want_first, lo, hi, nq < 2^31 - 1; then those of
+ * phnsw_search_exact_labelset: want_values unless want_first[nq] is 0 and want_first[nq] < 2^31 - 1; a Stored id at or
+ * past n, naming the query; want_first[0] != 0 or offsets that run backwards, naming the query (all PHNSW_E_INVALID).
+ * How: every query claims the pairs (query, wanted label) of its range, as phnsw_search_exact_labelset does; per pair
+ * the span of (its label, its query's range), two binary searches; the pairs sorted by span start (stable); a position
+ * that has the query and the non-empty span of the position before it is a duplicate and scans nothing
+ * (labelset_range_plan.h has the argument why that finds every repeated label); one wave64 per (pair, slice of its
+ * span) through the scan loop of phnsw_search_exact_label_ranged, every store kind it scans, every pair writing its
+ * per-slice lists of k keys to scratch; then a wave per query merges the lists of its pairs through the same running
+ * top-k.  The slice count comes from the longest label's run; nothing is read back; no tile path.  Knob (environment,
+ * read per call, changes no result): PHNSW_LABELSET_RANGE_SLICES forces the number of slices a span is cut into.
+ * Guidance (the run described at phnsw_search_labelset_ranged_auto below): against phnsw_search_exact_filtered with the
+ * equivalent per-query bitmaps already on the device this call took 6.61 ms against 6.62 at sets of 1, 25.4 against 25.6
+ * at sets of 4 and 149 against 200 at sets of 32 (a tenth of each label: 1 538, 6 152 and 49 216 candidates); with the
+ * upload counted -- 160 KB to 1.4 MB against 1.25 GB -- 0.23, 0.54 and 0.67 of it.  Its time grows with the candidates
+ * (no tile path): 20.8 ms at 5 000 candidates of a set of 4, 77.7 at 20 000, 195 at 60 000. */
+int phnsw_search_exact_labelset_ranged(const phnsw_index *ix, const phnsw_label_attr *h, const float *queries,
+                                       const uint64_t *qids, uint64_t nq, const uint64_t *exclude, const uint32_t *want_first,
+                                       const uint32_t *want_values, const uint32_t *lo, const uint32_t *hi, uint64_t k,
+                                       uint64_t *out_ids, float *out_d, uint64_t *out_len);
+/* device form: ENQUEUES AND RETURNS, never synchronises; scratch sets live with the handle.  The offsets are NOT trusted:
+ * status_dev[q] = 8 for a query whose range [want_first[q], want_first[q+1]) is not inside [0, nwant], runs backwards,
+ * or overlaps the range of a LOWER query; such a query gets an empty row, every other query is unaffected, and nothing
+ * outside want_values[0 .. nwant) is ever read.  status_dev[q] = 4 for a Stored query id at or past n (an empty row);
+ * status 8 wins where both hold. */
+int phnsw_search_exact_labelset_ranged_device(const phnsw_index *ix, const phnsw_label_attr *h, const float *queries_dev,
+                                              uint32_t ldq, const uint32_t *qids_dev, uint64_t nq, const uint32_t *exclude_dev,
+                                              const uint32_t *want_first_dev, const uint32_t *want_values_dev, uint64_t nwant,
+                                              const uint32_t *lo_dev, const uint32_t *hi_dev, uint64_t k, uint32_t *out_ids_dev,
+                                              float *out_d_dev, uint32_t *out_len_dev, uint32_t *status_dev, void *stream);
+/* the graph walk by a set of labels and a range: phnsw_search_batch_labelset with (h, want_first, want_values, lo, hi)
+ * -- the search kernels' set-range mode over pair_of: one 8-byte load per tested id, the loop of the set mode over the
+ * wave-uniform set values against the label word, two compares of the key word (ph_pairset_holds, filter_route.h).
+ * ROW EQUALITY: rows, lengths, stats and statuses are those of phnsw_search_batch_filtered[_device] called with the
+ * per-query bitmaps above, bit for bit, the entry-vector quirk and PHNSW_FILTER_STRICT included.  k cuts as in
+ * phnsw_search_batch_labelset (host form; 0 = the whole queue).  The index's default filter is not consulted.  Every
+ * store kind phnsw_search_batch_filtered walks is accepted.  The host form checks the offsets and the Stored ids as
+ * the exact host form does.  Measured (the run described at phnsw_search_labelset_ranged_auto below): the device form
+ * took 0.997 to 1.008 of the bitmap walk's kernel time at sets of 1, 4 and 32 labels (24.2, 23.1 and 18.4 ms) and 0.46
+ * to 0.52 of it with the upload counted. */
+int phnsw_search_batch_labelset_ranged(const phnsw_index *ix, const phnsw_label_attr *h, const float *queries,
+                                       const uint64_t *qids, uint64_t nq, const phnsw_search_params *sp, uint32_t upto_layers,
+                                       const uint64_t *exclude, const uint32_t *want_first, const uint32_t *want_values,
+                                       const uint32_t *lo, const uint32_t *hi, uint32_t flags, uint64_t k, uint64_t *out_ids,
+                                       float *out_d, uint64_t *out_len, uint64_t *out_stats);
+/* device form: ENQUEUED on `stream`, never synchronises.  want_first_dev, want_values_dev, lo_dev and hi_dev are read by
+ * the kernels: keep them alive and unchanged until the work on `stream` is done.  A query whose range is not inside
+ * [0, nwant] or runs backwards does not walk -- status_dev[q] = 8, an empty row, length 0, stats 0 --, nothing outside
+ * want_values[0 .. nwant) is ever read, and every other query is unaffected.  Status 8 is raised for these range faults
+ * ONLY: ranges that OVERLAP are harmless to a walk and are NOT detected here, as in phnsw_search_batch_labelset_device. */
+int phnsw_search_batch_labelset_ranged_device(const phnsw_index *ix, const phnsw_label_attr *h, const float *queries_dev,
+                                              uint32_t ldq, const uint32_t *qids_dev, uint64_t nq,
+                                              const phnsw_search_params *sp, uint32_t upto_layers, const uint32_t *exclude_dev,
+                                              const uint32_t *want_first_dev, const uint32_t *want_values_dev, uint64_t nwant,
+                                              const uint32_t *lo_dev, const uint32_t *hi_dev, uint32_t flags,
+                                              uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                              uint32_t *out_stats_dev, uint32_t *status_dev, void *stream);
+/* one call by a set of labels and a range that routes: phnsw_search_labelset_auto with the handle and (lo, hi).  Same
+ * three routes, out_route values, rule and promise: every row holds exactly min(k, c_q - e_q) entries and only
+ * candidates; c_q is what phnsw_label_attr_count_set_device writes, e_q is 1 iff exclude[q] passes the walk's predicate.
+ * The walk is the STRICT walk above over the graph list; scanned rows and graph rows left short go through ONE launch
+ * of the exact scan's subset form, whose claim still runs over the whole batch.  Hence every row equals the row of
+ * phnsw_search_filtered_auto with the per-query bitmaps and the same scan_below.  Status 8 is reported where
+ * phnsw_search_exact_labelset_ranged_device reports it, whatever the route; such a query reads PHNSW_ROUTE_SCAN.  The
+ * device form synchronises `stream` at most twice.  scan_below 0 = the library default (filter_route.h,
+ * PH_AUTO_SCAN_BELOW_LABELSET_RANGED): 5 000 candidates of the union, the last measured count at which the scan still
+ * won.  UINT64_MAX = always scan.
+ * Guidance (measured on 1M x 768 f32 rows, cosine, ef 256 / probe_depth 8, 10 000-query batches, k = 10, 64 labels of
+ * about 15 600 rows, the variants alternating in one run, run-to-run spread under 1 % unless said;
+ * profiles/labelset_ranged/README.md): sets of 4 labels, scan against walk by candidates of the union -- 20.8 ms against
+ * 23.6 at 5 000, 40.2 against 22.3 at 10 000, 77.7 against 20.5 at 20 000, 195 against 17.8 at 60 000: the lines cross
+ * between 5 000 and 10 000.  With a range that keeps a tenth of each label the routed call took 6.72 ms at sets of 1
+ * (all scanned), 25.5 ms at sets of 4 (all scanned; the walk alone took 23.1 and returned 6.1 rows per query) and
+ * 18.4 ms at sets of 32 (all walked), 0.96 to 0.99 of phnsw_search_filtered_auto over bitmaps on the device and 0.23 to
+ * 0.53 of it with the upload of the filter's description counted.  Other store kinds, other k, uneven or duplicated
+ * sets and the host forms: not measured. */
+int phnsw_search_labelset_ranged_auto(const phnsw_index *ix, const phnsw_label_attr *h, const float *queries,
+                                      const uint64_t *qids, uint64_t nq, const phnsw_search_params *sp, const uint64_t *exclude,
+                                      const uint32_t *want_first, const uint32_t *want_values, const uint32_t *lo,
+                                      const uint32_t *hi, uint64_t k, uint64_t scan_below, uint64_t *out_ids, float *out_d,
+                                      uint64_t *out_len, uint32_t *out_route);
+int phnsw_search_labelset_ranged_auto_device(const phnsw_index *ix, const phnsw_label_attr *h, const float *queries_dev,
+                                             uint32_t ldq, const uint32_t *qids_dev, uint64_t nq, const phnsw_search_params *sp,
+                                             const uint32_t *exclude_dev, const uint32_t *want_first_dev,
+                                             const uint32_t *want_values_dev, uint64_t nwant, const uint32_t *lo_dev,
+                                             const uint32_t *hi_dev, uint64_t k, uint64_t scan_below, uint32_t *out_ids_dev,
+                                             float *out_d_dev, uint32_t *out_len_dev, uint32_t *out_route_dev,
+                                             uint32_t *status_dev, void *stream);
 /* ---- the COLLECTING search: the graph walk that remembers the best ALLOWED rows it evaluates.  The filtered walks above
  * are post-filters: they keep the best number_of_candidates rows, allowed or not, and filter that queue when the layer
  * ends, so a filter of density p leaves about p * number_of_candidates results although the walk evaluated several

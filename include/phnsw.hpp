@@ -635,6 +635,57 @@ class Hnsw {
                                               const uint32_t *hi_dev, uint64_t k, uint64_t scan_below, uint32_t *out_ids_dev,
                                               float *out_d_dev, uint32_t *out_len_dev, uint32_t *out_route_dev,
                                               uint32_t *status_dev, void *stream) const;
+  // search_many_exact_label_ranged for a SET of labels per query (phnsw_search_exact_labelset_ranged): query i may return
+  // the vectors `attr` lists under any label of want[i] with lo[i] <= key <= hi[i], ONE range per query shared by its
+  // labels.  A label twice counts once; LabeledAttribute::NONE, a label nobody carries, an empty set and lo > hi = nothing
+  inline std::vector<SearchResult> search_many_exact_labelset_ranged(const std::vector<const float *> &queries, uint64_t k,
+                                                                     const LabeledAttribute &attr,
+                                                                     const std::vector<std::vector<uint32_t>> &want,
+                                                                     const std::vector<uint32_t> &lo,
+                                                                     const std::vector<uint32_t> &hi) const;
+  // zero-copy form (phnsw_search_exact_labelset_ranged_device): the sets in CSR form, want_first_dev [nq + 1] and
+  // want_values_dev [nwant]; status 8 = a range of want_first_dev that is not sound or overlaps a lower query's, 4 = a
+  // Stored id at or past n (empty rows).  Enqueued on `stream`, never synchronises it
+  inline void search_exact_labelset_ranged_device(const LabeledAttribute &attr, const float *queries_dev, uint32_t ldq,
+                                                  const uint32_t *qids_dev, uint64_t nq, const uint32_t *exclude_dev,
+                                                  const uint32_t *want_first_dev, const uint32_t *want_values_dev, uint64_t nwant,
+                                                  const uint32_t *lo_dev, const uint32_t *hi_dev, uint64_t k, uint32_t *out_ids_dev,
+                                                  float *out_d_dev, uint32_t *out_len_dev, uint32_t *status_dev,
+                                                  void *stream) const;
+  // search_many_label_ranged for a SET of labels per query (phnsw_search_batch_labelset_ranged): the graph walk restricted
+  // to the sets and the ranges; k 0 = all number_of_candidates entries of a row
+  inline std::vector<SearchResult> search_many_labelset_ranged(const std::vector<const float *> &queries,
+                                                               const SearchParameters &sp, uint64_t k,
+                                                               const LabeledAttribute &attr,
+                                                               const std::vector<std::vector<uint32_t>> &want,
+                                                               const std::vector<uint32_t> &lo, const std::vector<uint32_t> &hi,
+                                                               bool strict = false) const;
+  // zero-copy form (phnsw_search_batch_labelset_ranged_device): the table and the bounds stay alive until the work on
+  // `stream` is done; status 8 = a range of want_first_dev that is not inside [0, nwant] or runs backwards
+  inline void search_batch_labelset_ranged_device(const LabeledAttribute &attr, const float *queries_dev, uint32_t ldq,
+                                                  const uint32_t *qids_dev, uint64_t nq, const SearchParameters &sp,
+                                                  uint32_t upto_layers, const uint32_t *exclude_dev,
+                                                  const uint32_t *want_first_dev, const uint32_t *want_values_dev, uint64_t nwant,
+                                                  const uint32_t *lo_dev, const uint32_t *hi_dev, bool strict,
+                                                  uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                                  uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) const;
+  // search_many_label_ranged_auto for a SET of labels per query (phnsw_search_labelset_ranged_auto): per query the span
+  // scan or the strict walk, the scan again for short rows.  scan_below 0 = the library's threshold (5 000: phnsw.h)
+  inline std::vector<SearchResult> search_many_labelset_ranged_auto(const std::vector<const float *> &queries,
+                                                                    const SearchParameters &sp, uint64_t k,
+                                                                    const LabeledAttribute &attr,
+                                                                    const std::vector<std::vector<uint32_t>> &want,
+                                                                    const std::vector<uint32_t> &lo,
+                                                                    const std::vector<uint32_t> &hi, uint64_t scan_below = 0,
+                                                                    std::vector<uint32_t> *routes = nullptr) const;
+  // device form (phnsw_search_labelset_ranged_auto_device): u32 ids [nq][k]; synchronises `stream` up to twice (phnsw.h)
+  inline void search_labelset_ranged_auto_device(const LabeledAttribute &attr, const float *queries_dev, uint32_t ldq,
+                                                 const uint32_t *qids_dev, uint64_t nq, const SearchParameters &sp,
+                                                 const uint32_t *exclude_dev, const uint32_t *want_first_dev,
+                                                 const uint32_t *want_values_dev, uint64_t nwant, const uint32_t *lo_dev,
+                                                 const uint32_t *hi_dev, uint64_t k, uint64_t scan_below, uint32_t *out_ids_dev,
+                                                 float *out_d_dev, uint32_t *out_len_dev, uint32_t *out_route_dev,
+                                                 uint32_t *status_dev, void *stream) const;
   // 0, or the code search_many_exact_shared would refuse this index and k with (phnsw_exact_shared_supported)
   int exact_shared_supported(uint64_t k) const { return phnsw_exact_shared_supported(ix_, k); }
   // candidates of each of nbitmaps device bitmaps (phnsw_filter_count_device): what to choose the search call by
@@ -1186,6 +1237,12 @@ class LabeledAttribute {
                     void *stream) const {
     check(phnsw_label_attr_count_device(h_, want_dev, lo_dev, hi_dev, nq, out_count_dev, stream));
   }
+  // per query the summed span lengths of the distinct labels of its set inside its range (CSR, as
+  // search_exact_labelset_ranged_device); 0 for a query that call would refuse
+  void count_set_device(const uint32_t *want_first_dev, const uint32_t *want_values_dev, const uint32_t *lo_dev,
+                        const uint32_t *hi_dev, uint64_t nq, uint64_t nwant, uint32_t *out_count_dev, void *stream) const {
+    check(phnsw_label_attr_count_set_device(h_, want_first_dev, want_values_dev, lo_dev, hi_dev, nq, nwant, out_count_dev, stream));
+  }
   phnsw_label_attr *handle() const { return h_; }
 
  private:
@@ -1265,6 +1322,90 @@ inline void Hnsw::search_label_ranged_auto_device(const LabeledAttribute &attr, 
   check(phnsw_search_label_ranged_auto_device(ix_, attr.handle(), queries_dev, ldq, qids_dev, nq, &sp, exclude_dev, want_dev, lo_dev,
                                               hi_dev, k, scan_below, out_ids_dev, out_d_dev, out_len_dev, out_route_dev, status_dev,
                                               stream));
+}
+
+inline std::vector<SearchResult> Hnsw::search_many_exact_labelset_ranged(const std::vector<const float *> &queries, uint64_t k,
+                                                                         const LabeledAttribute &attr,
+                                                                         const std::vector<std::vector<uint32_t>> &want,
+                                                                         const std::vector<uint32_t> &lo,
+                                                                         const std::vector<uint32_t> &hi) const {
+  if (k == 0 || k > 1024) throw Error(PHNSW_E_INVALID, "search_many_exact_labelset_ranged: k must be 1..1024");
+  std::vector<uint32_t> first, values;
+  pack_label_sets(want, queries.size(), "search_many_exact_labelset_ranged", &first, &values);
+  return detail::ranged_rows(queries, c_->dim(), k, lo, hi, "search_many_exact_labelset_ranged",
+                             [&](const float *q, uint64_t nq, uint64_t *ids, float *d, uint64_t *len) {
+                               check(phnsw_search_exact_labelset_ranged(ix_, attr.handle(), q, nullptr, nq, nullptr, first.data(),
+                                                                        values.data(), lo.data(), hi.data(), k, ids, d, len));
+                             });
+}
+inline void Hnsw::search_exact_labelset_ranged_device(const LabeledAttribute &attr, const float *queries_dev, uint32_t ldq,
+                                                      const uint32_t *qids_dev, uint64_t nq, const uint32_t *exclude_dev,
+                                                      const uint32_t *want_first_dev, const uint32_t *want_values_dev,
+                                                      uint64_t nwant, const uint32_t *lo_dev, const uint32_t *hi_dev, uint64_t k,
+                                                      uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                                      uint32_t *status_dev, void *stream) const {
+  check(phnsw_search_exact_labelset_ranged_device(ix_, attr.handle(), queries_dev, ldq, qids_dev, nq, exclude_dev, want_first_dev,
+                                                  want_values_dev, nwant, lo_dev, hi_dev, k, out_ids_dev, out_d_dev, out_len_dev,
+                                                  status_dev, stream));
+}
+inline std::vector<SearchResult> Hnsw::search_many_labelset_ranged(const std::vector<const float *> &queries,
+                                                                   const SearchParameters &sp, uint64_t k,
+                                                                   const LabeledAttribute &attr,
+                                                                   const std::vector<std::vector<uint32_t>> &want,
+                                                                   const std::vector<uint32_t> &lo, const std::vector<uint32_t> &hi,
+                                                                   bool strict) const {
+  if (k == 0) k = sp.number_of_candidates;  // the C call's "whole row"; the buffers are sized by it
+  if (k > sp.number_of_candidates) throw Error(PHNSW_E_INVALID, "search_many_labelset_ranged: k exceeds number_of_candidates");
+  std::vector<uint32_t> first, values;
+  pack_label_sets(want, queries.size(), "search_many_labelset_ranged", &first, &values);
+  return detail::ranged_rows(queries, c_->dim(), k, lo, hi, "search_many_labelset_ranged",
+                             [&](const float *q, uint64_t nq, uint64_t *ids, float *d, uint64_t *len) {
+                               check(phnsw_search_batch_labelset_ranged(ix_, attr.handle(), q, nullptr, nq, &sp, 0, nullptr,
+                                                                        first.data(), values.data(), lo.data(), hi.data(),
+                                                                        strict ? PHNSW_FILTER_STRICT : 0u, k, ids, d, len, nullptr));
+                             });
+}
+inline void Hnsw::search_batch_labelset_ranged_device(const LabeledAttribute &attr, const float *queries_dev, uint32_t ldq,
+                                                      const uint32_t *qids_dev, uint64_t nq, const SearchParameters &sp,
+                                                      uint32_t upto_layers, const uint32_t *exclude_dev,
+                                                      const uint32_t *want_first_dev, const uint32_t *want_values_dev,
+                                                      uint64_t nwant, const uint32_t *lo_dev, const uint32_t *hi_dev, bool strict,
+                                                      uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                                      uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) const {
+  check(phnsw_search_batch_labelset_ranged_device(ix_, attr.handle(), queries_dev, ldq, qids_dev, nq, &sp, upto_layers, exclude_dev,
+                                                  want_first_dev, want_values_dev, nwant, lo_dev, hi_dev,
+                                                  strict ? PHNSW_FILTER_STRICT : 0u, out_ids_dev, out_d_dev, out_len_dev,
+                                                  out_stats_dev, status_dev, stream));
+}
+inline std::vector<SearchResult> Hnsw::search_many_labelset_ranged_auto(const std::vector<const float *> &queries,
+                                                                        const SearchParameters &sp, uint64_t k,
+                                                                        const LabeledAttribute &attr,
+                                                                        const std::vector<std::vector<uint32_t>> &want,
+                                                                        const std::vector<uint32_t> &lo,
+                                                                        const std::vector<uint32_t> &hi, uint64_t scan_below,
+                                                                        std::vector<uint32_t> *routes) const {
+  if (k == 0 || k > sp.number_of_candidates)
+    throw Error(PHNSW_E_INVALID, "search_many_labelset_ranged_auto: k must be 1..number_of_candidates");
+  std::vector<uint32_t> first, values;
+  pack_label_sets(want, queries.size(), "search_many_labelset_ranged_auto", &first, &values);
+  if (routes) routes->assign(queries.size(), 0u);
+  return detail::ranged_rows(queries, c_->dim(), k, lo, hi, "search_many_labelset_ranged_auto",
+                             [&](const float *q, uint64_t nq, uint64_t *ids, float *d, uint64_t *len) {
+                               check(phnsw_search_labelset_ranged_auto(ix_, attr.handle(), q, nullptr, nq, &sp, nullptr,
+                                                                       first.data(), values.data(), lo.data(), hi.data(), k,
+                                                                       scan_below, ids, d, len, routes ? routes->data() : nullptr));
+                             });
+}
+inline void Hnsw::search_labelset_ranged_auto_device(const LabeledAttribute &attr, const float *queries_dev, uint32_t ldq,
+                                                     const uint32_t *qids_dev, uint64_t nq, const SearchParameters &sp,
+                                                     const uint32_t *exclude_dev, const uint32_t *want_first_dev,
+                                                     const uint32_t *want_values_dev, uint64_t nwant, const uint32_t *lo_dev,
+                                                     const uint32_t *hi_dev, uint64_t k, uint64_t scan_below,
+                                                     uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                                     uint32_t *out_route_dev, uint32_t *status_dev, void *stream) const {
+  check(phnsw_search_labelset_ranged_auto_device(ix_, attr.handle(), queries_dev, ldq, qids_dev, nq, &sp, exclude_dev,
+                                                 want_first_dev, want_values_dev, nwant, lo_dev, hi_dev, k, scan_below, out_ids_dev,
+                                                 out_d_dev, out_len_dev, out_route_dev, status_dev, stream));
 }
 
 // QuantizedHnsw  pq.rs:120-131, 287-364 (per-sub-space codebooks, u8 codes)

@@ -187,6 +187,19 @@ SYMBOLS = {
                                               _vp]),
     "phnsw_search_label_ranged_auto_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _vp,
                                                      _vp, _vp, _vp, _vp, _vp]),
+    # (h, want_first, want_values[, nwant], lo, hi): a set of labels and one range per query
+    "phnsw_label_attr_count_set_device": (_i32, [_vp, _vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp]),
+    "phnsw_search_exact_labelset_ranged": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "phnsw_search_exact_labelset_ranged_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _u64,
+                                                         _vp, _vp, _vp, _vp, _vp]),
+    "phnsw_search_batch_labelset_ranged": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _u64,
+                                                  _vp, _vp, _vp, _vp]),
+    "phnsw_search_batch_labelset_ranged_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _u64, _vp,
+                                                         _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "phnsw_search_labelset_ranged_auto": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _u64, _vp, _vp,
+                                                 _vp, _vp]),
+    "phnsw_search_labelset_ranged_auto_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp,
+                                                        _u64, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "phnsw_search_batch_labelset": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _u32, _u64, _vp, _vp, _vp, _vp]),
     "phnsw_search_batch_labelset_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _u64, _u32, _vp,
                                                   _vp, _vp, _vp, _vp, _vp]),

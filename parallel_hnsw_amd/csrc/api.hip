@@ -656,6 +656,10 @@ static void fill_args(const phnsw_index *ix, const PhSearchCall &c, PhSearchArgs
     a.filter = nullptr, a.filter_stride = 0u;
     a.pair_of = c.filter.pair_of, a.pair_want = c.filter.pair_want, a.pair_lo = c.filter.pair_lo, a.pair_hi = c.filter.pair_hi;
     a.filter_flags = c.filter.flags;
+    if (c.filter.set_first) {  // ... or its set form: the table of wanted labels instead of one label per query
+      a.pair_want = nullptr;
+      a.set_first = c.filter.set_first, a.set_values = c.filter.set_values, a.set_nwant = c.filter.set_nwant;
+    }
   }
   a.nq = (uint32_t)c.nq;
   a.out_ids = c.out_ids;
@@ -897,7 +901,8 @@ int ph_search_device(const phnsw_index *ix, const PhSearchCall &c) {
       if (b.filter) b.filter += c0 * b.filter_stride;  // per-query bitmaps follow the chunk; a shared one (stride 0) stays
       if (b.label_want) b.label_want += c0;  // ... and so do the wanted labels; the column is indexed by VectorId
       if (b.range_lo) b.range_lo += c0, b.range_hi += c0;  // ... and the bounds of the ranges
-      if (b.pair_want) b.pair_want += c0, b.pair_lo += c0, b.pair_hi += c0;  // ... and the labels and bounds of the pairs
+      if (b.pair_want) b.pair_want += c0;  // ... and the labels and bounds of the pairs (a call by set and range: bounds alone)
+      if (b.pair_lo) b.pair_lo += c0, b.pair_hi += c0;
       if (b.set_first) b.set_first += c0;    // ... and the offsets of the sets, which stay absolute: set_values does not move
       if (b.out_ids) b.out_ids += c0 * ostride, b.out_d += c0 * ostride;
       if (b.collect_k) b.collect_ids += c0 * b.collect_k, b.collect_d += c0 * b.collect_k;

@@ -37,6 +37,14 @@
 //   3. the walk is the search kernels' label-range mode over the handle's column
 //   4. "exclude[q] is a candidate" is ph_auto_pair_candidate, the predicate of the walk (ph_pair_holds)
 //   5. the scan is filter_label_ranged.hip's, over the scan list (PhLabelRangedCall::list)
+// ... or BY A SET OF LABELS AND A NUMERIC RANGE (phnsw_search_labelset_ranged_auto[_device]: a phnsw_label_attr handle,
+// want_first, want_values, lo[q] and hi[q]):
+//   1. the counts are ph_label_attr_count_set's: the spans of the distinct labels of the range, and 0 for a query the scan
+//      refuses (a range that is not sound, a pair a lower query holds) -- so it is routed to the scan, which reports it
+//   3. the walk is the search kernels' set-range mode over the handle's column
+//   4. "exclude[q] is a candidate" is ph_auto_pairset_candidate, the predicate of the walk (ph_pairset_holds)
+//   5. the scan is the subset form of the scan by set and range (PhLabelsetRangedCall with a list): its claim runs over
+//      the whole batch
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -153,7 +161,10 @@ __global__ __launch_bounds__(64) void ph_auto_finish_kernel(PhAutoArgs a) {
     if (lane == 0) {
       const uint32_t *const bitmap = a.filter ? a.filter + (uint64_t)q * a.filter_stride : nullptr;
       bool ex_cand;
-      if (a.pair_of)
+      if (a.pair_of && a.set_first)
+        ex_cand = ph_auto_pairset_candidate(a.pair_of, a.n, a.set_first[q], a.set_first[q + 1u], a.set_values, a.pair_lo[q], a.pair_hi[q],
+                                            ex, 0xFFFFFFFFFFFFFFFFull);
+      else if (a.pair_of)
         ex_cand = ph_auto_pair_candidate(a.pair_of, a.n, a.pair_want[q], a.pair_lo[q], a.pair_hi[q], ex, 0xFFFFFFFFFFFFFFFFull);
       else if (a.attr_of)
         ex_cand = ph_auto_range_candidate(a.attr_of, a.n, a.range_lo[q], a.range_hi[q], ex, PHNSW_ATTR_NONE);
@@ -194,20 +205,23 @@ int auto_run(const phnsw_index *ix, const PhAutoCall &c, PhAutoSet &set) {
   const uint32_t ef = (uint32_t)c.sp->number_of_candidates;
   const bool by_label = c.labels != nullptr, by_set = by_label && c.want_first != nullptr;
   const bool by_range = c.attr != nullptr;
-  const bool by_pair = c.label_attr != nullptr;
+  const bool by_pair = c.label_attr != nullptr, by_pairset = by_pair && c.want_first != nullptr;
   const bool per_query = by_label || by_range || by_pair || (c.filter.words && c.filter.stride != 0u);
   PH_TRY(set.ready());
   if (!set.h_head) PH_HIP(hipHostMalloc((void **)&set.h_head, PH_AUTO_HEAD_WORDS * 4u, hipHostMallocDefault));
   // (a call by set: the claim's owner words [nwant] behind everything else)
   const uint64_t words = ph_auto_scratch_words(nq, per_query, ef);
-  PH_TRY(set.block_ensure(&set.block, &set.bytes, (size_t)(words + (by_set ? c.nwant : 0u)) * 4u, c.stream));
+  PH_TRY(set.block_ensure(&set.block, &set.bytes, (size_t)(words + (by_set || by_pairset ? c.nwant : 0u)) * 4u, c.stream));
   const uint64_t nb = ph_auto_bitmaps(nq, per_query);
   uint32_t *const head = (uint32_t *)set.block, *const counts = head + PH_AUTO_HEAD_WORDS, *const glist = counts + nb;
   uint32_t *const slist = glist + ph_auto_list_words(nq), *const route_own = slist + ph_auto_list_words(nq);
   uint32_t *const walk_len = route_own + nq, *const walk_ids = walk_len + nq;
   float *const walk_d = (float *)(walk_ids + nq * ef);
 
-  if (by_pair)
+  if (by_pairset)
+    PH_TRY(ph_label_attr_count_set(c.label_attr, c.want_first, c.want_values, c.pair_lo, c.pair_hi, nq, c.nwant, counts, head + words,
+                                   c.stream));
+  else if (by_pair)
     PH_TRY(ph_label_attr_count(c.label_attr, c.pair_want, c.pair_lo, c.pair_hi, nq, counts, c.stream));
   else if (by_range)
     PH_TRY(ph_attr_count(c.attr, c.range_lo, c.range_hi, nq, counts, c.stream));
@@ -219,7 +233,8 @@ int auto_run(const phnsw_index *ix, const PhAutoCall &c, PhAutoSet &set) {
     PH_TRY(ph_filter_count(ix, c.filter, nb, counts, c.stream));
   PhAutoArgs a = {};
   a.nq = (uint32_t)nq, a.n = (uint32_t)s->n, a.k = c.k, a.ef = ef;
-  a.scan_below = by_pair    ? ph_auto_scan_below_label_ranged(c.scan_below)
+  a.scan_below = by_pairset ? ph_auto_scan_below_labelset_ranged(c.scan_below)
+                 : by_pair  ? ph_auto_scan_below_label_ranged(c.scan_below)
                  : by_range ? ph_auto_scan_below_ranged(c.scan_below)
                  : by_set ? ph_auto_scan_below_labelset(c.scan_below)
                         : (by_label ? ph_auto_scan_below_labeled(c.scan_below) : ph_auto_scan_below(c.scan_below, per_query));
@@ -243,6 +258,11 @@ int auto_run(const phnsw_index *ix, const PhAutoCall &c, PhAutoSet &set) {
     filter = PhFilter{};
     filter.pair_of = a.pair_of = ph_label_attr_column(c.label_attr);
     filter.pair_want = a.pair_want = c.pair_want, filter.pair_lo = a.pair_lo = c.pair_lo, filter.pair_hi = a.pair_hi = c.pair_hi;
+    if (by_pairset) {  // (graph-list queries have sound ranges: their counts are not 0)
+      filter.pair_want = a.pair_want = nullptr;
+      filter.set_first = a.set_first = c.want_first, filter.set_values = a.set_values = c.want_values;
+      filter.set_nwant = (uint32_t)c.nwant;
+    }
   }
   a.filter = filter.words, a.filter_stride = filter.words ? filter.stride : 0u, a.per_query = per_query ? 1u : 0u;
   ph_exact_bottom_layer(ix, &a.n_nodes, &a.nodes, &a.vec2node);
@@ -271,7 +291,17 @@ int auto_run(const phnsw_index *ix, const PhAutoCall &c, PhAutoSet &set) {
     PH_HIP(hipStreamSynchronize(c.stream));
     slen = std::min<uint64_t>(set.h_head[1], nq);
   }
-  if (slen && by_pair) {
+  if (slen && by_pairset) {
+    PhLabelsetRangedCall sx = {};
+    PhLabelRangedCall &x = sx.c;
+    x.queries = c.queries, x.ldq = c.ldq, x.qids = c.qids, x.exclude = c.exclude, x.lo = c.pair_lo, x.hi = c.pair_hi;
+    x.nq = slen, x.list = slist;
+    x.k = c.k;
+    x.out_ids = c.out_ids, x.out_d = c.out_d, x.out_len = c.out_len, x.status = c.status;
+    x.stream = c.stream;
+    sx.want_first = c.want_first, sx.want_values = c.want_values, sx.nwant = c.nwant, sx.batch_nq = nq;
+    PH_TRY(ph_labelset_ranged_device(ix, c.label_attr, sx));
+  } else if (slen && by_pair) {
     PhLabelRangedCall x = {};
     x.queries = c.queries, x.ldq = c.ldq, x.qids = c.qids, x.exclude = c.exclude;
     x.want = c.pair_want, x.lo = c.pair_lo, x.hi = c.pair_hi;
@@ -386,9 +416,9 @@ static int auto_host(const char *call, const phnsw_index *ix, const phnsw_labels
                      uint64_t k, uint64_t scan_below, uint64_t *out_ids, float *out_d, uint64_t *out_len, uint32_t *out_route,
                      const phnsw_attr *at = nullptr, const uint32_t *range_lo = nullptr, const uint32_t *range_hi = nullptr,
                      const phnsw_label_attr *la = nullptr, const uint32_t *pair_want = nullptr) {
-  const bool by_set = lb && want_first;
-  if (la && (!pair_want || !range_lo || !range_hi || nq > 0x7FFFFFFEull)) {
-    ph_set_error("%s: invalid argument (want, lo and hi; nq < 2^31 - 1)", call);
+  const bool by_set = (lb || la) && want_first;  // with la: by set and range (pair_want unused)
+  if (la && ((!pair_want && !want_first) || !range_lo || !range_hi || nq > 0x7FFFFFFEull)) {
+    ph_set_error("%s: invalid argument (want%s, lo and hi; nq < 2^31 - 1)", call, want_first ? "_first" : "");
     return PHNSW_E_INVALID;
   }
   if (at && (!range_lo || !range_hi || nq > 0x7FFFFFFEull)) {
@@ -425,12 +455,21 @@ static int auto_host(const char *call, const phnsw_index *ix, const phnsw_labels
   PhAutoSet *set = ph_set_acquire<PhAutoSet>(mix->autos);
   PhHostCall h(mix->autos, set);
   // extras: route | want, or for a call by set want_first [nq + 1] | want_values [nwant], or for a call by range lo | hi, or for a call by
-  // label and range want | lo | hi
+  // label and range want | lo | hi, or for a call by set and range want_first [nq + 1] | want_values [nwant] | lo | hi
   PH_TRY(h.stage_in(s, queries, qids, exclude, nq, (size_t)nq * 4u + (by_set ? 1u + (size_t)nwant : 0u), 1, (uint32_t)k, (uint32_t)k));
   PhAutoCall c = {};
   h.fill(c);
   c.filter = hf;
-  if (la) {  // the description of a call by label and range: 12 bytes per query
+  if (la && by_set) {  // the description of a call by set and range: 4 * (nq + 1) + 4 * nwant + 8 * nq bytes
+    uint32_t *const first_dev = h.extra() + nq, *const values_dev = first_dev + nq + 1u, *const lo_dev = values_dev + nwant;
+    uint32_t *const hi_dev = lo_dev + nq;
+    PH_HIP(hipMemcpyAsync(first_dev, want_first, (size_t)(nq + 1u) * 4u, hipMemcpyHostToDevice, h.st));
+    if (nwant) PH_HIP(hipMemcpyAsync(values_dev, want_values, (size_t)nwant * 4u, hipMemcpyHostToDevice, h.st));
+    PH_HIP(hipMemcpyAsync(lo_dev, range_lo, (size_t)nq * 4u, hipMemcpyHostToDevice, h.st));
+    PH_HIP(hipMemcpyAsync(hi_dev, range_hi, (size_t)nq * 4u, hipMemcpyHostToDevice, h.st));
+    c.label_attr = la, c.pair_lo = lo_dev, c.pair_hi = hi_dev;
+    c.want_first = first_dev, c.want_values = values_dev, c.nwant = nwant;
+  } else if (la) {  // the description of a call by label and range: 12 bytes per query
     uint32_t *const want_dev = h.extra() + nq, *const lo_dev = want_dev + nq, *const hi_dev = lo_dev + nq;
     PH_HIP(hipMemcpyAsync(want_dev, pair_want, (size_t)nq * 4u, hipMemcpyHostToDevice, h.st));
     PH_HIP(hipMemcpyAsync(lo_dev, range_lo, (size_t)nq * 4u, hipMemcpyHostToDevice, h.st));
@@ -647,6 +686,58 @@ extern "C" int phnsw_search_label_ranged_auto_device(const phnsw_index *ix, cons
   }
   PhAutoCall c = {};
   c.label_attr = h, c.pair_want = want_dev, c.pair_lo = lo_dev, c.pair_hi = hi_dev;
+  c.queries = queries_dev, c.ldq = ldq, c.qids = qids_dev, c.exclude = exclude_dev, c.nq = nq, c.sp = sp;
+  c.k = (uint32_t)k, c.scan_below = scan_below;
+  c.out_ids = out_ids_dev, c.out_d = out_d_dev, c.out_len = out_len_dev, c.out_route = out_route_dev, c.status = status_dev;
+  c.stream = (hipStream_t)stream;
+  PH_HIP(hipSetDevice(ix->store->device));
+  return ph_auto_device(ix, c);
+} catch (...) { return ph_caught(); }
+
+// ---- by a set of labels and a numeric range
+
+extern "C" int phnsw_search_labelset_ranged_auto(const phnsw_index *ix, const phnsw_label_attr *h, const float *queries,
+                                                 const uint64_t *qids, uint64_t nq, const phnsw_search_params *sp,
+                                                 const uint64_t *exclude, const uint32_t *want_first, const uint32_t *want_values,
+                                                 const uint32_t *lo, const uint32_t *hi, uint64_t k, uint64_t scan_below,
+                                                 uint64_t *out_ids, float *out_d, uint64_t *out_len, uint32_t *out_route) try {
+  const char *const call = "phnsw_search_labelset_ranged_auto";
+  PH_TRY(auto_check(ix, sp, k, call));
+  PH_TRY(ph_label_ranged_check(ix, h, k, call));
+  if (nq == 0) return 0;
+  if (!want_first) {
+    ph_set_error("%s: invalid argument (want_first)", call);
+    return PHNSW_E_INVALID;
+  }
+  return auto_host(call, ix, nullptr, queries, qids, nq, sp, exclude, nullptr, 0u, nullptr, want_first, want_values, k, scan_below,
+                   out_ids, out_d, out_len, out_route, nullptr, lo, hi, h, nullptr);
+} catch (...) { return ph_caught(); }
+
+extern "C" int phnsw_search_labelset_ranged_auto_device(const phnsw_index *ix, const phnsw_label_attr *h, const float *queries_dev,
+                                                        uint32_t ldq, const uint32_t *qids_dev, uint64_t nq,
+                                                        const phnsw_search_params *sp, const uint32_t *exclude_dev,
+                                                        const uint32_t *want_first_dev, const uint32_t *want_values_dev,
+                                                        uint64_t nwant, const uint32_t *lo_dev, const uint32_t *hi_dev, uint64_t k,
+                                                        uint64_t scan_below, uint32_t *out_ids_dev, float *out_d_dev,
+                                                        uint32_t *out_len_dev, uint32_t *out_route_dev, uint32_t *status_dev,
+                                                        void *stream) try {
+  const char *const call = "phnsw_search_labelset_ranged_auto_device";
+  PH_TRY(auto_check(ix, sp, k, call));
+  PH_TRY(ph_label_ranged_check(ix, h, k, call));
+  if (nq == 0) return 0;
+  if (!ph_device_queries_ok(ix, queries_dev, qids_dev, ldq) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev ||
+      !want_first_dev || (!want_values_dev && nwant) || !lo_dev || !hi_dev) {
+    ph_set_error("%s: invalid argument (queries or qids, exactly one; outputs; want_first; want_values unless nwant is 0; lo and "
+                 "hi; queries need ldq >= store ld, multiple of 4, 16-byte base)", call);
+    return PHNSW_E_INVALID;
+  }
+  if (nq > 0x7FFFFFFEull || nwant > 0x7FFFFFFEull) {
+    ph_set_error("%s: nq and nwant must be below 2^31 - 1", call);
+    return PHNSW_E_INVALID;
+  }
+  PhAutoCall c = {};
+  c.label_attr = h, c.pair_lo = lo_dev, c.pair_hi = hi_dev;
+  c.want_first = want_first_dev, c.want_values = want_values_dev, c.nwant = nwant;
   c.queries = queries_dev, c.ldq = ldq, c.qids = qids_dev, c.exclude = exclude_dev, c.nq = nq, c.sp = sp;
   c.k = (uint32_t)k, c.scan_below = scan_below;
   c.out_ids = out_ids_dev, c.out_d = out_d_dev, c.out_len = out_len_dev, c.out_route = out_route_dev, c.status = status_dev;

@@ -23,6 +23,18 @@
 // the keys of the running top-k are (distance, id), distinct, so the k smallest are one set in one order however the span
 // is ordered or cut (exact_topk.h); the distances are dist.batch's.  There is no tile path.
 //
+// A SET of labels and one range per query (phnsw_label_attr_count_set_device,
+// phnsw_search_exact_labelset_ranged[_device]; labelset_range_plan.h): `label IN S_q AND lo <= attribute <= hi`.  The
+// kernel sequence of the scan by set (filter_labeled.hip) with spans in place of posting lists: a lookup position is a
+// (query, wanted label) PAIR --
+//   a call     1. ph_labelset_claim_kernel (labelset_claim.h: which query owns a pair; the offsets are not trusted)
+//              2. ph_labelset_ranged_lookup_kernel: per pair the span of (its label, its owner's range); the same sort
+//              3. ph_labelset_ranged_dup_kernel: a position that repeats the (query, span) of the position before it
+//              4. ph_label_ranged_scan_kernel<Dist, PAIRS>: every pair writes its per-slice lists to scratch, none a row
+//              5. ph_labelset_ranged_merge_kernel: a wave per query merges the lists of its pairs, duplicates left out
+// The subset form (PhLabelsetRangedCall with a list) makes the rows of the listed queries only; its claim runs over the
+// whole batch.  No tile path.
+//
 // The graph walk (at the end of this file) is the search kernels' label-range mode (search_label_ranged.hip) over
 // pair_of; the routed call (phnsw_search_label_ranged_auto) is filter_auto.hip's and takes its scan from here through the
 // subset form (PhLabelRangedCall::list).
@@ -39,6 +51,8 @@
 #include "filter_route.h"
 #include "host_call.h"
 #include "label_range_plan.h"
+#include "labelset_claim.h"
+#include "labelset_range_plan.h"
 #include "list_scan.h"
 #include "phnsw_device.h"
 
@@ -105,6 +119,7 @@ struct PhLabelRangedArgs {
   // the grouping (range_plan.h), by lookup position: key and iota feed the sort; order = the query of a position
   uint32_t *key, *iota, *order, *at, *len;
   const uint32_t *sorted;  // [nq] by position of the sorted batch: its lookup position
+  const uint32_t *dup;     // the PAIRS form: [nq] by lookup position, 1 = scans nothing (labelset_range_plan.h); else nullptr
   uint32_t pq_lds;         // bytes of dynamic LDS in front of the scan's own: a PQ store's table
   uint64_t *scratch;       // slices > 1: [nq lookup positions][slices][k] keys, each list ascending, KEY_NONE padded
   uint32_t *out_ids;       // [nq][k]
@@ -133,7 +148,10 @@ __global__ __launch_bounds__(256) void ph_label_ranged_count_kernel(const uint64
 // One wave64 per (position of the sorted batch, slice of its span); work item = slice * nq + position (slice-major,
 // the positions by span start): the waves resident together read neighbouring rows.  What a wave leaves is addressed by
 // the LOOKUP position, which the merge walks.
-template <class Dist>
+// PAIRS: the form of phnsw_search_exact_labelset_ranged -- a lookup position is a (query, wanted label) pair, order[p]
+// the pair's query; a position never writes a row, its lists go to the scratch at every slice count, and a duplicate
+// scans nothing.
+template <class Dist, bool PAIRS = false>
 __global__ __launch_bounds__(64) void ph_label_ranged_scan_kernel(PhLabelRangedArgs a) {
   extern __shared__ float label_ranged_lds[];
   const uint32_t lane = threadIdx.x;
@@ -150,28 +168,122 @@ __global__ __launch_bounds__(64) void ph_label_ranged_scan_kernel(PhLabelRangedA
       dist.prepare_raw(a.dist, a.queries + (uint64_t)q * a.ldq, label_ranged_lds, lane);
     else if (!bad_query)
       dist.prepare_stored(a.dist, a.qids[q], label_ranged_lds, lane);
-    const uint32_t at = a.at[p], len = a.len[p];  // a bad query's span is empty
-    ph_list_scan<false>(a, dist, keys, a.ids + at, len, q, p, slice, bad_query, lane);  // list_scan.h
+    const uint32_t at = a.at[p], len = PAIRS && a.dup[p] ? 0u : a.len[p];  // a bad query's span is empty
+    ph_list_scan<PAIRS>(a, dist, keys, a.ids + at, len, q, p, slice, bad_query, lane);  // list_scan.h
   }
 }
 
 typedef void (*PhLabelRangedFn)(PhLabelRangedArgs);
+// pairs: the PAIRS instance, phnsw_search_exact_labelset_ranged's
 template <template <int, int> class D>
-static PhLabelRangedFn label_ranged_rows_fn(uint32_t nv4) {
+static PhLabelRangedFn label_ranged_rows_fn(uint32_t nv4, bool pairs) {
   switch (ph_chunk_count(nv4)) {
-    case 1: return ph_label_ranged_scan_kernel<D<1, 4>>;
-    case 3: return ph_label_ranged_scan_kernel<D<3, 4>>;
-    case 6: return ph_label_ranged_scan_kernel<D<6, 4>>;
+    case 1: return pairs ? ph_label_ranged_scan_kernel<D<1, 4>, true> : ph_label_ranged_scan_kernel<D<1, 4>>;
+    case 3: return pairs ? ph_label_ranged_scan_kernel<D<3, 4>, true> : ph_label_ranged_scan_kernel<D<3, 4>>;
+    case 6: return pairs ? ph_label_ranged_scan_kernel<D<6, 4>, true> : ph_label_ranged_scan_kernel<D<6, 4>>;
     default: return nullptr;
   }
 }
-static PhLabelRangedFn label_ranged_scan_fn(const phnsw_store *s) {
+static PhLabelRangedFn label_ranged_scan_fn(const phnsw_store *s, bool pairs = false) {
   switch (s->kind) {
-    case PH_ROWS_PQ: return ph_label_ranged_scan_kernel<DistPQ>;
-    case PH_ROWS_F16: return label_ranged_rows_fn<DistF16>(s->ld / 4);
-    case PH_ROWS_I8: return label_ranged_rows_fn<DistI8>(s->ld / 4);
-    case PH_ROWS_I8Q: return label_ranged_rows_fn<DistI8Q>(s->ld / 4);
-    default: return label_ranged_rows_fn<DistF32>(s->ld / 4);
+    case PH_ROWS_PQ: return pairs ? ph_label_ranged_scan_kernel<DistPQ, true> : ph_label_ranged_scan_kernel<DistPQ>;
+    case PH_ROWS_F16: return label_ranged_rows_fn<DistF16>(s->ld / 4, pairs);
+    case PH_ROWS_I8: return label_ranged_rows_fn<DistI8>(s->ld / 4, pairs);
+    case PH_ROWS_I8Q: return label_ranged_rows_fn<DistI8Q>(s->ld / 4, pairs);
+    default: return label_ranged_rows_fn<DistF32>(s->ld / 4, pairs);
+  }
+}
+
+// ------------------------------------------------------------------ a SET of labels and a range per query: pairs
+
+// a = the block of the scan kernel with nq = nwant lookup positions, the PAIRS: order[i] is the query of pair i (0 for a
+// pair that scans nothing), at[i] and len[i] its span, dup[i] the duplicate mark; lo and hi are indexed by QUERY
+struct PhLabelsetRangedArgs {
+  PhLabelRangedArgs a;
+  const uint32_t *want_first, *want_values;  // [nq + 1], [nwant]: the caller's, untrusted
+  uint32_t nq, nwant;
+  uint32_t *owner;  // [nwant] by pair: the query that claimed it, PH_LABELSET_OWNER_NONE
+  uint32_t *dup;    // [nwant] by pair (a.dup, writable)
+  // the subset form (a.list != nullptr): the rows of queries a.list[0 .. nlist) are made; sel [nq] = 1 for those
+  const uint32_t *sel;
+  uint32_t nlist;  // rows the merge writes: the list's length, nq without a list
+};
+
+// per pair: its span (empty for an unclaimed pair, for a bad Stored query id and for a query the list leaves out), the
+// sort key of the span and the pair itself, the sort's value
+__global__ __launch_bounds__(256) void ph_labelset_ranged_lookup_kernel(PhLabelsetRangedArgs s) {
+  const PhLabelRangedArgs &a = s.a;
+  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < s.nwant; i += (uint64_t)gridDim.x * 256u) {
+    const uint32_t q = s.owner[i];  // NONE or < nq
+    const bool dead = q == PH_LABELSET_OWNER_NONE || (!a.queries && a.qids[q] >= a.n) || (s.sel && !s.sel[q]);
+    uint32_t at = 0u, len = 0u;
+    if (!dead) ph_label_range_span(a.spairs, a.listed, s.want_values[i], a.lo[q], a.hi[q], &at, &len);  // at + len <= listed
+    a.order[i] = dead ? 0u : q, a.at[i] = at, a.len[i] = len;
+    a.key[i] = ph_label_range_sort_key(at, len), a.iota[i] = (uint32_t)i;
+  }
+}
+
+// per position after the sort: whether its pair repeats the (query, span) of the pair before it (labelset_range_plan.h)
+__global__ __launch_bounds__(256) void ph_labelset_ranged_dup_kernel(PhLabelsetRangedArgs s) {
+  const PhLabelRangedArgs &a = s.a;
+  for (uint64_t pos = (uint64_t)blockIdx.x * 256u + threadIdx.x; pos < s.nwant; pos += (uint64_t)gridDim.x * 256u) {
+    const uint32_t i = min(a.sorted[pos], s.nwant - 1u);
+    bool dup = false;
+    if (pos > 0) {
+      const uint32_t j = min(a.sorted[pos - 1u], s.nwant - 1u);
+      dup = ph_labelset_range_dup(a.at[i], a.len[i], s.owner[i], a.at[j], a.len[j], s.owner[j]);
+    }
+    s.dup[i] = dup ? 1u : 0u;
+  }
+}
+
+// One wave per query: the lists of every pair of its range -- duplicates and empty spans left out -- through the same
+// running top-k as ph_list_merge_kernel, so ties across spans fall in id order.  A refused query (labelset_plan.h)
+// gets the empty row and status ST_LABELSET_RANGE.
+#define ST_LABELSET_RANGE 8u
+__global__ __launch_bounds__(64) void ph_labelset_ranged_merge_kernel(PhLabelsetRangedArgs s) {
+  extern __shared__ float label_ranged_lds[];
+  const uint32_t lane = threadIdx.x;
+  const PhLabelRangedArgs &a = s.a;
+  uint64_t *const keys = (uint64_t *)label_ranged_lds;
+  for (uint32_t at = blockIdx.x; at < s.nlist; at += gridDim.x) {
+    const uint32_t q = a.list ? a.list[at] : at;
+    if (q >= s.nq) continue;  // (a list holds query indices of the batch)
+    const uint32_t b = s.want_first[q], e = s.want_first[q + 1u];
+    const bool ok = ph_labelset_owns_range(s.owner, s.nwant, q, b, e, lane);  // labelset_claim.h
+    __syncthreads();
+    PhExactTopK top;
+    top.init(keys, a.k);
+    for (uint32_t i = b; ok && i < e; i++) {  // i < nwant: the range is sound, and every pair of it is q's
+      if (s.dup[i] || a.len[i] == 0u) continue;
+      for (uint32_t sl = 0; sl < a.slices; sl++)
+        PH_EXACT_FEED(top, a.scratch + ((uint64_t)i * a.slices + sl) * a.k, a.k, lane);
+    }
+    ph_exact_write_row(a, q, top.cur, top.len, !a.queries && a.qids[q] >= a.n, lane);
+    if (!ok && lane == 0) a.status[q] = ST_LABELSET_RANGE;  // after the row's own status word, same lane
+  }
+}
+
+// per query the span lengths of the distinct labels of its range (labelset_range_plan.h); a refused query counts 0: a
+// range that is not sound and, with owner[] as the claim kernel left it (nullable), a pair a lower query holds.  One
+// wave per query, a pair per lane.
+__global__ __launch_bounds__(64) void ph_labelset_ranged_count_kernel(const uint64_t *spairs, uint32_t listed,
+                                                                      const uint32_t *want_first, const uint32_t *want_values,
+                                                                      const uint32_t *lo, const uint32_t *hi, uint64_t nq,
+                                                                      uint32_t nwant, const uint32_t *owner, uint32_t *out_count) {
+  const uint32_t lane = threadIdx.x;
+  for (uint64_t q = blockIdx.x; q < nq; q += gridDim.x) {
+    const uint32_t b = want_first[q], e = want_first[q + 1u];
+    uint32_t c = 0;
+    bool ok = ph_labelset_range_ok(b, e, nwant);
+    if (ok && owner) ok = ph_labelset_owns_range(owner, nwant, (uint32_t)q, b, e, lane);
+    if (ok) {
+      const uint32_t l = lo[q], h = hi[q];
+      for (uint64_t i = (uint64_t)b + lane; i < e; i += 64u)
+        c += ph_labelset_range_count_pair(spairs, listed, want_values, b, (uint32_t)i, l, h);
+    }
+    for (int o = 32; o; o >>= 1) c += __shfl_xor(c, o);
+    if (lane == 0) out_count[q] = c;
   }
 }
 
@@ -260,6 +372,86 @@ int label_ranged_run(const phnsw_index *ix, const phnsw_label_attr *h, const PhL
                        (size_t)ph_label_scan_lds(c.k), c.stream, a);
     PH_HIP(hipGetLastError());
   }
+  return 0;
+}
+
+// label_ranged_run over pairs (labelset_range_plan.h; the request: PhLabelsetRangedCall, phnsw_internal.h); sc is checked,
+// 0 < batch_nq, batch_nq and nwant <= PH_LABEL_NQ_MAX; with c.list, c.nq > 0 is its length.  Enqueues and returns.
+int labelset_ranged_run(const phnsw_index *ix, const phnsw_label_attr *h, const PhLabelsetRangedCall &sc, PhLabeledSet &set) {
+  const phnsw_store *s = ix->store;
+  const PhLabelRangedCall &c = sc.c;
+  const uint64_t nq = sc.batch_nq, np = sc.nwant;  // np lookup positions
+  const PhLabelsetPre lay = ph_labelset_pre(np);
+  PH_TRY(set.ready());
+  // (the subset form's marks [nq] behind the layout's words)
+  PH_TRY(set.block_ensure(&set.pre, &set.pre_bytes, (size_t)(lay.words + (c.list ? nq : 0u)) * 4u, c.stream));
+  uint32_t *const pre = (uint32_t *)set.pre;
+  PhLabelsetRangedArgs sa = {};
+  PhLabelRangedArgs &a = sa.a;
+  a.dist = ph_dist_args(s);
+  a.queries = c.queries, a.ldq = c.ldq, a.qids = c.qids, a.exclude = c.exclude, a.lo = c.lo, a.hi = c.hi;
+  a.list = c.list;
+  a.nq = (uint32_t)np, a.n = (uint32_t)s->n, a.k = c.k, a.slices = 1u;
+  a.spairs = h->spairs, a.ids = h->ids, a.listed = (uint32_t)h->listed;
+  // the arrays of ph_labelset_pre as labelset_range_plan.h reads them
+  a.key = pre + lay.pos.slot, a.iota = pre + lay.pos.iota, a.order = pre + lay.pos.order;
+  a.at = pre + lay.pos.tile_first, a.len = pre + lay.pos.flags;
+  uint32_t *const skey = pre + lay.pos.sslot, *const sorted = pre + lay.spair;
+  a.sorted = sorted;
+  sa.owner = pre + lay.owner, sa.dup = pre + lay.dup, a.dup = sa.dup;
+  a.out_ids = c.out_ids, a.out_d = c.out_d, a.out_len = c.out_len, a.status = c.status;
+  sa.want_first = sc.want_first, sa.want_values = sc.want_values, sa.nq = (uint32_t)nq, sa.nwant = (uint32_t)np;
+  sa.nlist = (uint32_t)(c.list ? c.nq : nq);
+
+  if (np) {
+    // before anything is enqueued: the kernel with its dynamic LDS, the slice count, hipCUB's temporaries
+    const size_t pq_lds = (ph_pq_lds_bytes(s) + 15u) & ~(size_t)15u;
+    const PhLabelRangedFn fn = label_ranged_scan_fn(s, true);
+    const size_t lds = pq_lds + (size_t)ph_label_scan_lds(a.k);
+    a.pq_lds = (uint32_t)pq_lds;
+    phnsw_label_attr *mh = const_cast<phnsw_label_attr *>(h);
+    uint64_t resident = 0;
+    PH_TRY(ph_resident_waves(mh->resident, mh->pool.mutex, s->device, (const void *)fn, lds, &resident));
+    a.slices = ph_label_slice_count(np, resident, h->longest, env_ll("PHNSW_LABELSET_RANGE_SLICES"));
+    if (set.tmp_nq != np) {
+      size_t sort_bytes = 0;
+      PH_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, a.key, skey, a.iota, sorted, (int)np, 0, 32, c.stream));
+      set.tmp_need = std::max<size_t>(sort_bytes, 16), set.tmp_nq = np;
+    }
+    PH_TRY(set.block_ensure(&set.tmp, &set.tmp_bytes, set.tmp_need, c.stream));
+    uint64_t bytes = 0;
+    if (!ph_labelset_key_bytes(np, a.slices, c.k, &bytes)) {
+      ph_set_error("exact labelset-ranged search: %llu wanted labels in %u slices at k = %u need more scratch than can be addressed",
+                   (unsigned long long)np, a.slices, c.k);
+      return PHNSW_E_INVALID;
+    }
+    PH_TRY(set.block_ensure(&set.keys, &set.keys_bytes, (size_t)bytes, c.stream));
+    a.scratch = (uint64_t *)set.keys;
+
+    PH_HIP(hipMemsetAsync(sa.owner, 0xFF, (size_t)np * 4u, c.stream));  // PH_LABELSET_OWNER_NONE
+    hipLaunchKernelGGL(ph_labelset_claim_kernel, dim3(grid1(nq)), dim3(256), 0, c.stream, sa.want_first, sa.nq, sa.nwant, sa.owner);
+    PH_HIP(hipGetLastError());
+    if (c.list) {
+      uint32_t *const sel = pre + lay.words;
+      PH_HIP(hipMemsetAsync(sel, 0, (size_t)nq * 4u, c.stream));
+      hipLaunchKernelGGL(ph_labelset_select_kernel, dim3(grid1(sa.nlist)), dim3(256), 0, c.stream, c.list, sa.nlist, (uint32_t)nq, sel);
+      PH_HIP(hipGetLastError());
+      sa.sel = sel;
+    }
+    hipLaunchKernelGGL(ph_labelset_ranged_lookup_kernel, dim3(grid1(np)), dim3(256), 0, c.stream, sa);
+    PH_HIP(hipGetLastError());
+    size_t tmp_bytes = set.tmp_bytes;
+    PH_HIP(hipcub::DeviceRadixSort::SortPairs(set.tmp, tmp_bytes, a.key, skey, a.iota, sorted, (int)np, 0, 32, c.stream));
+    hipLaunchKernelGGL(ph_labelset_ranged_dup_kernel, dim3(grid1(np)), dim3(256), 0, c.stream, sa);
+    PH_HIP(hipGetLastError());
+    const uint64_t items = np * (uint64_t)a.slices;
+    hipLaunchKernelGGL(fn, dim3((uint32_t)std::min<uint64_t>(items, 1u << 20)), dim3(64), lds, c.stream, a);
+    PH_HIP(hipGetLastError());
+  }
+  // no pair at all: every sound range is empty, and the merge alone writes the rows
+  hipLaunchKernelGGL(ph_labelset_ranged_merge_kernel, dim3((uint32_t)std::min<uint64_t>(sa.nlist, 1u << 20)), dim3(64),
+                     (size_t)ph_label_scan_lds(c.k), c.stream, sa);
+  PH_HIP(hipGetLastError());
   return 0;
 }
 
@@ -364,6 +556,29 @@ int ph_label_attr_count(const phnsw_label_attr *h, const uint32_t *want_dev, con
                      lo_dev, hi_dev, nq, out_count_dev);
   PH_HIP(hipGetLastError());
   return 0;
+}
+
+int ph_label_attr_count_set(const phnsw_label_attr *h, const uint32_t *want_first_dev, const uint32_t *want_values_dev,
+                            const uint32_t *lo_dev, const uint32_t *hi_dev, uint64_t nq, uint64_t nwant, uint32_t *out_count_dev,
+                            uint32_t *owner_scratch, hipStream_t stream) {
+  uint32_t *const owner = nwant ? owner_scratch : nullptr;  // without a pair no range overlaps another
+  if (owner) {
+    PH_HIP(hipMemsetAsync(owner, 0xFF, (size_t)nwant * 4u, stream));  // PH_LABELSET_OWNER_NONE
+    hipLaunchKernelGGL(ph_labelset_claim_kernel, dim3(grid1(nq)), dim3(256), 0, stream, want_first_dev, (uint32_t)nq, (uint32_t)nwant, owner);
+    PH_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(ph_labelset_ranged_count_kernel, dim3((uint32_t)std::min<uint64_t>(nq, 1u << 20)), dim3(64), 0, stream, h->spairs,
+                     (uint32_t)h->listed, want_first_dev, want_values_dev, lo_dev, hi_dev, nq, (uint32_t)nwant, owner, out_count_dev);
+  PH_HIP(hipGetLastError());
+  return 0;
+}
+
+int ph_labelset_ranged_device(const phnsw_index *ix, const phnsw_label_attr *h, const PhLabelsetRangedCall &sc) {
+  if (sc.c.nq == 0 || sc.batch_nq == 0) return 0;
+  phnsw_label_attr *mh = const_cast<phnsw_label_attr *>(h);
+  PhLabeledSet *set = ph_handle_set_acquire(mh->pool, sc.c.stream, false);
+  PhSetGuard guard{mh->pool, set, sc.c.stream};
+  return labelset_ranged_run(ix, h, sc, *set);
 }
 
 int ph_label_ranged_device(const phnsw_index *ix, const phnsw_label_attr *h, const PhLabelRangedCall &c) {
@@ -496,6 +711,125 @@ extern "C" int phnsw_search_exact_label_ranged(const phnsw_index *ix, const phns
   return hc.finish(out_ids, out_d, out_len);
 } catch (...) { return ph_caught(); }
 
+// ------------------------------------------------------------------ C ABI: a set of labels and a range per query
+
+extern "C" int phnsw_label_attr_count_set_device(const phnsw_label_attr *h, const uint32_t *want_first_dev,
+                                                 const uint32_t *want_values_dev, const uint32_t *lo_dev, const uint32_t *hi_dev,
+                                                 uint64_t nq, uint64_t nwant, uint32_t *out_count_dev, void *stream) try {
+  const char *const call = "phnsw_label_attr_count_set_device";
+  if (!h) {
+    ph_set_error("%s: null label and attribute keys", call);
+    return PHNSW_E_INVALID;
+  }
+  if (nq == 0) return 0;
+  if (!want_first_dev || !lo_dev || !hi_dev || !out_count_dev || (!want_values_dev && nwant)) {
+    ph_set_error("%s: null want_first, null want_values with nwant > 0, null lo, null hi or null output", call);
+    return PHNSW_E_INVALID;
+  }
+  if (nq > PH_LABEL_NQ_MAX || nwant > PH_LABELSET_NWANT_MAX) {
+    ph_set_error("%s: nq and nwant must be below 2^31 - 1", call);
+    return PHNSW_E_INVALID;
+  }
+  PH_HIP(hipSetDevice(h->device));
+  hipStream_t st = (hipStream_t)stream;
+  if (!nwant) return ph_label_attr_count_set(h, want_first_dev, want_values_dev, lo_dev, hi_dev, nq, 0u, out_count_dev, nullptr, st);
+  // the claim's owner words [nwant]: a scratch set of the handle, as the scan takes one
+  phnsw_label_attr *mh = const_cast<phnsw_label_attr *>(h);
+  PhLabeledSet *set = ph_handle_set_acquire(mh->pool, st, false);
+  PhSetGuard guard{mh->pool, set, st};
+  PH_TRY(set->ready());
+  PH_TRY(set->block_ensure(&set->pre, &set->pre_bytes, (size_t)nwant * 4u, st));
+  return ph_label_attr_count_set(h, want_first_dev, want_values_dev, lo_dev, hi_dev, nq, nwant, out_count_dev, (uint32_t *)set->pre, st);
+} catch (...) { return ph_caught(); }
+
+extern "C" int phnsw_search_exact_labelset_ranged_device(const phnsw_index *ix, const phnsw_label_attr *h, const float *queries_dev,
+                                                         uint32_t ldq, const uint32_t *qids_dev, uint64_t nq,
+                                                         const uint32_t *exclude_dev, const uint32_t *want_first_dev,
+                                                         const uint32_t *want_values_dev, uint64_t nwant, const uint32_t *lo_dev,
+                                                         const uint32_t *hi_dev, uint64_t k, uint32_t *out_ids_dev, float *out_d_dev,
+                                                         uint32_t *out_len_dev, uint32_t *status_dev, void *stream) try {
+  const char *const call = "phnsw_search_exact_labelset_ranged_device";
+  PH_TRY(ph_label_ranged_check(ix, h, k, call));
+  if (nq == 0) return 0;
+  if (!ph_device_queries_ok(ix, queries_dev, qids_dev, ldq) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev ||
+      !want_first_dev || (!want_values_dev && nwant) || !lo_dev || !hi_dev) {
+    ph_set_error("%s: invalid argument (queries or qids, exactly one; outputs; want_first; want_values unless nwant is 0; lo and "
+                 "hi; queries need ldq >= store ld, multiple of 4, 16-byte base)", call);
+    return PHNSW_E_INVALID;
+  }
+  if (nq > PH_LABEL_NQ_MAX || nwant > PH_LABELSET_NWANT_MAX) {
+    ph_set_error("%s: nq and nwant must be below 2^31 - 1", call);
+    return PHNSW_E_INVALID;
+  }
+  PhLabelsetRangedCall sc = {};
+  PhLabelRangedCall &c = sc.c;
+  c.queries = queries_dev, c.ldq = ldq, c.qids = qids_dev, c.exclude = exclude_dev, c.nq = nq, c.k = (uint32_t)k;
+  c.lo = lo_dev, c.hi = hi_dev;
+  c.out_ids = out_ids_dev, c.out_d = out_d_dev, c.out_len = out_len_dev, c.status = status_dev;
+  c.stream = (hipStream_t)stream;
+  sc.want_first = want_first_dev, sc.want_values = want_values_dev, sc.nwant = nwant, sc.batch_nq = nq;
+  PH_HIP(hipSetDevice(ix->store->device));
+  return ph_labelset_ranged_device(ix, h, sc);
+} catch (...) { return ph_caught(); }
+
+// the offset and size checks the host forms by set and range make once outputs and pointers are known to be there:
+// want_values against want_first[nq], the Stored ids, the offsets, each naming the call and the query
+static int labelset_ranged_host_check(const char *call, const phnsw_store *s, const uint64_t *qids, uint64_t nq,
+                                      const uint32_t *want_first, const uint32_t *want_values, uint64_t *nwant) {
+  *nwant = want_first[nq];
+  if ((!want_values && *nwant) || *nwant > PH_LABELSET_NWANT_MAX) {
+    ph_set_error("%s: invalid argument (want_values unless want_first[nq] is 0; want_first[nq] < 2^31 - 1)", call);
+    return PHNSW_E_INVALID;
+  }
+  PH_TRY(ph_stored_ids_check(qids, nq, s->n, call, true));
+  if (const uint64_t bad = ph_labelset_first_bad(want_first, nq); bad < nq) {
+    ph_set_error("%s: query %llu: want_first must start at 0 and never run backwards (want_first[%llu] = %u, want_first[%llu] "
+                 "= %u)", call, (unsigned long long)bad, (unsigned long long)bad, want_first[bad], (unsigned long long)bad + 1u,
+                 want_first[bad + 1u]);
+    return PHNSW_E_INVALID;
+  }
+  return 0;
+}
+
+extern "C" int phnsw_search_exact_labelset_ranged(const phnsw_index *ix, const phnsw_label_attr *h, const float *queries,
+                                                  const uint64_t *qids, uint64_t nq, const uint64_t *exclude,
+                                                  const uint32_t *want_first, const uint32_t *want_values, const uint32_t *lo,
+                                                  const uint32_t *hi, uint64_t k, uint64_t *out_ids, float *out_d,
+                                                  uint64_t *out_len) try {
+  const char *const call = "phnsw_search_exact_labelset_ranged";
+  PH_TRY(ph_label_ranged_check(ix, h, k, call));
+  if (nq == 0) return 0;
+  if ((!queries) == (!qids)) {
+    ph_set_error("%s: pass queries or qids (exactly one)", call);
+    return PHNSW_E_INVALID;
+  }
+  if (!out_ids || !out_d || !out_len || !want_first || !lo || !hi || nq > PH_LABEL_NQ_MAX) {
+    ph_set_error("%s: invalid argument (outputs; want_first, lo and hi; nq < 2^31 - 1)", call);
+    return PHNSW_E_INVALID;
+  }
+  const phnsw_store *s = ix->store;
+  PH_HIP(hipSetDevice(s->device));
+  uint64_t nwant = 0;
+  PH_TRY(labelset_ranged_host_check(call, s, qids, nq, want_first, want_values, &nwant));
+  phnsw_label_attr *mh = const_cast<phnsw_label_attr *>(h);
+  PhLabeledSet *set = ph_handle_set_acquire(mh->pool, nullptr, true);
+  PhHostCall hc(mh->pool, set);
+  // extras: want_first [nq + 1] | want_values [nwant] | lo | hi
+  PH_TRY(hc.stage_in(s, queries, qids, exclude, nq, (size_t)nq * 3u + 1u + (size_t)nwant, 0, (uint32_t)k, (uint32_t)k));
+  PhLabelsetRangedCall sc = {};
+  hc.fill(sc.c);
+  uint32_t *const first_dev = hc.extra(), *const values_dev = first_dev + nq + 1u, *const lo_dev = values_dev + nwant;
+  uint32_t *const hi_dev = lo_dev + nq;
+  PH_HIP(hipMemcpyAsync(first_dev, want_first, (size_t)(nq + 1u) * 4u, hipMemcpyHostToDevice, hc.st));
+  if (nwant) PH_HIP(hipMemcpyAsync(values_dev, want_values, (size_t)nwant * 4u, hipMemcpyHostToDevice, hc.st));
+  PH_HIP(hipMemcpyAsync(lo_dev, lo, (size_t)nq * 4u, hipMemcpyHostToDevice, hc.st));
+  PH_HIP(hipMemcpyAsync(hi_dev, hi, (size_t)nq * 4u, hipMemcpyHostToDevice, hc.st));
+  sc.want_first = first_dev, sc.want_values = values_dev, sc.nwant = nwant, sc.batch_nq = nq;
+  sc.c.lo = lo_dev, sc.c.hi = hi_dev, sc.c.k = (uint32_t)k;
+  PH_TRY(labelset_ranged_run(ix, h, sc, *set));
+  return hc.finish(out_ids, out_d, out_len);
+} catch (...) { return ph_caught(); }
+
 // ------------------------------------------------------------------ the graph walk by label and range
 
 extern "C" int phnsw_search_batch_label_ranged_device(const phnsw_index *ix, const phnsw_label_attr *h, const float *queries_dev,
@@ -565,6 +899,92 @@ extern "C" int phnsw_search_batch_label_ranged(const phnsw_index *ix, const phns
   PH_HIP(hipMemcpyAsync(hi_dev, hi, (size_t)nq * 4u, hipMemcpyHostToDevice, hc.st));
   c.filter.pair_of = h->pair_of, c.filter.pair_want = want_dev, c.filter.pair_lo = lo_dev, c.filter.pair_hi = hi_dev;
   c.filter.flags = flags;
+  c.sp = sp, c.upto = upto_layers, c.out_stats = hc.extra();
+  return ph_walk_host_run(ix, hc, c, redo_dev, ef, out_ids, out_d, out_len, out_stats);
+} catch (...) { return ph_caught(); }
+
+// ------------------------------------------------------------------ the graph walk by a set of labels and a range
+
+// The search kernels' set-range mode (search_labelset_ranged.hip) over pair_of, the caller's table and the bounds.  The
+// device form hands the table to the kernels as it is: they refuse a range that is not sound per query (status 8) and
+// read nothing outside want_values[0 .. nwant); ranges that OVERLAP are harmless to a walk and are not detected here.
+extern "C" int phnsw_search_batch_labelset_ranged_device(const phnsw_index *ix, const phnsw_label_attr *h, const float *queries_dev,
+                                                         uint32_t ldq, const uint32_t *qids_dev, uint64_t nq,
+                                                         const phnsw_search_params *sp, uint32_t upto_layers,
+                                                         const uint32_t *exclude_dev, const uint32_t *want_first_dev,
+                                                         const uint32_t *want_values_dev, uint64_t nwant, const uint32_t *lo_dev,
+                                                         const uint32_t *hi_dev, uint32_t flags, uint32_t *out_ids_dev,
+                                                         float *out_d_dev, uint32_t *out_len_dev, uint32_t *out_stats_dev,
+                                                         uint32_t *status_dev, void *stream) try {
+  const char *const call = "phnsw_search_batch_labelset_ranged_device";
+  PH_TRY(walk_check(ix, h, sp, flags, call));
+  if (nq == 0) return 0;
+  if (!ph_device_queries_ok(ix, queries_dev, qids_dev, ldq) || !out_ids_dev || !out_d_dev || !out_len_dev || !status_dev ||
+      !want_first_dev || (!want_values_dev && nwant) || !lo_dev || !hi_dev) {
+    ph_set_error("%s: invalid argument (queries or qids, exactly one; outputs; want_first; want_values unless nwant is 0; lo and "
+                 "hi; queries need ldq >= store ld, multiple of 4, 16-byte base)", call);
+    return PHNSW_E_INVALID;
+  }
+  if (nq > PH_LABEL_NQ_MAX || nwant > PH_LABELSET_NWANT_MAX) {
+    ph_set_error("%s: nq and nwant must be below 2^31 - 1", call);
+    return PHNSW_E_INVALID;
+  }
+  PhSearchCall c = {};
+  c.queries = queries_dev, c.ldq = ldq, c.qids = qids_dev, c.exclude = exclude_dev, c.nq = nq;
+  c.sp = sp, c.upto = upto_layers;
+  c.filter.pair_of = h->pair_of, c.filter.pair_lo = lo_dev, c.filter.pair_hi = hi_dev, c.filter.flags = flags;
+  c.filter.set_first = want_first_dev, c.filter.set_values = want_values_dev, c.filter.set_nwant = (uint32_t)nwant;
+  c.out_ids = out_ids_dev, c.out_d = out_d_dev, c.out_len = out_len_dev, c.status = status_dev, c.out_stats = out_stats_dev;
+  c.stream = (hipStream_t)stream;
+  PH_HIP(hipSetDevice(ix->store->device));
+  return ph_search_device(ix, c);
+} catch (...) { return ph_caught(); }
+
+// The host form stages everything once, as phnsw_search_batch_labelset does, with the bounds behind the table.  The
+// offsets are checked here, so no query can come back with status 8.
+extern "C" int phnsw_search_batch_labelset_ranged(const phnsw_index *ix, const phnsw_label_attr *h, const float *queries,
+                                                  const uint64_t *qids, uint64_t nq, const phnsw_search_params *sp,
+                                                  uint32_t upto_layers, const uint64_t *exclude, const uint32_t *want_first,
+                                                  const uint32_t *want_values, const uint32_t *lo, const uint32_t *hi,
+                                                  uint32_t flags, uint64_t k, uint64_t *out_ids, float *out_d, uint64_t *out_len,
+                                                  uint64_t *out_stats) try {
+  const char *const call = "phnsw_search_batch_labelset_ranged";
+  PH_TRY(walk_check(ix, h, sp, flags, call));
+  const uint32_t ef = (uint32_t)sp->number_of_candidates;
+  if (k > ef) {
+    ph_set_error("%s: k must be 0 (the whole queue) or 1..number_of_candidates (got %llu, number_of_candidates %u)", call,
+                 (unsigned long long)k, ef);
+    return PHNSW_E_INVALID;
+  }
+  if (nq == 0) return 0;
+  if ((!queries) == (!qids)) {
+    ph_set_error("%s: pass queries or qids (exactly one)", call);
+    return PHNSW_E_INVALID;
+  }
+  if (!out_ids || !out_d || !out_len || !want_first || !lo || !hi || nq > PH_LABEL_NQ_MAX) {
+    ph_set_error("%s: invalid argument (outputs; want_first, lo and hi; nq < 2^31 - 1)", call);
+    return PHNSW_E_INVALID;
+  }
+  const phnsw_store *s = ix->store;
+  PH_HIP(hipSetDevice(s->device));
+  uint64_t nwant = 0;
+  PH_TRY(labelset_ranged_host_check(call, s, qids, nq, want_first, want_values, &nwant));
+  phnsw_label_attr *mh = const_cast<phnsw_label_attr *>(h);
+  PhLabeledSet *set = ph_handle_set_acquire(mh->pool, nullptr, true);
+  PhHostCall hc(mh->pool, set);
+  // extras: stats(2), which the host reads back with len and status | want_first [nq + 1] | want_values [nwant] | lo | hi |
+  // the redo list
+  PH_TRY(hc.stage_in(s, queries, qids, exclude, nq, (size_t)nq * 6u + 1u + (size_t)nwant, 2, ef, k ? (uint32_t)k : ef));
+  uint32_t *const first_dev = hc.extra() + 2u * nq, *const values_dev = first_dev + nq + 1u, *const lo_dev = values_dev + nwant;
+  uint32_t *const hi_dev = lo_dev + nq, *const redo_dev = hi_dev + nq;
+  PhSearchCall c = {};
+  hc.fill(c);
+  PH_HIP(hipMemcpyAsync(first_dev, want_first, (size_t)(nq + 1u) * 4u, hipMemcpyHostToDevice, hc.st));
+  if (nwant) PH_HIP(hipMemcpyAsync(values_dev, want_values, (size_t)nwant * 4u, hipMemcpyHostToDevice, hc.st));
+  PH_HIP(hipMemcpyAsync(lo_dev, lo, (size_t)nq * 4u, hipMemcpyHostToDevice, hc.st));
+  PH_HIP(hipMemcpyAsync(hi_dev, hi, (size_t)nq * 4u, hipMemcpyHostToDevice, hc.st));
+  c.filter.pair_of = h->pair_of, c.filter.pair_lo = lo_dev, c.filter.pair_hi = hi_dev, c.filter.flags = flags;
+  c.filter.set_first = first_dev, c.filter.set_values = values_dev, c.filter.set_nwant = (uint32_t)nwant;
   c.sp = sp, c.upto = upto_layers, c.out_stats = hc.extra();
   return ph_walk_host_run(ix, hc, c, redo_dev, ef, out_ids, out_d, out_len, out_stats);
 } catch (...) { return ph_caught(); }

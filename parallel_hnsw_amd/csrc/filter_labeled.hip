@@ -54,6 +54,7 @@
 #include "filter_route.h"
 #include "host_call.h"
 #include "label_plan.h"
+#include "labelset_claim.h"
 #include "labelset_plan.h"
 #include "list_scan.h"
 #include "phnsw_device.h"
@@ -201,21 +202,7 @@ struct PhLabelsetArgs {
   uint32_t nlist;  // rows the merge writes: the list's length, nq without a list
 };
 
-// owner[] is preset to NONE.  One thread per query claims the pairs of a sound range; the lowest query keeps a pair.
-__global__ __launch_bounds__(256) void ph_labelset_claim_kernel(PhLabelsetArgs s) {
-  for (uint64_t q = (uint64_t)blockIdx.x * 256u + threadIdx.x; q < s.nq; q += (uint64_t)gridDim.x * 256u) {
-    const uint32_t b = s.want_first[q], e = s.want_first[q + 1u];
-    if (!ph_labelset_range_ok(b, e, s.nwant)) continue;
-    for (uint32_t i = b; i < e; i++)  // i < e <= nwant
-      if (!ph_labelset_claim_goes_on(atomicMin(&s.owner[i], (uint32_t)q), (uint32_t)q)) break;
-  }
-}
-
-// the subset form: sel [nq] is preset to 0; one thread per entry of the list marks its query
-__global__ __launch_bounds__(256) void ph_labelset_select_kernel(const uint32_t *list, uint32_t nlist, uint32_t nq, uint32_t *sel) {
-  for (uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x; p < nlist; p += (uint64_t)gridDim.x * 256u)
-    if (list[p] < nq) sel[list[p]] = 1u;
-}
+// (which query owns a pair, the marks of the subset form: ph_labelset_claim_kernel, ph_labelset_select_kernel, labelset_claim.h)
 
 // per pair: its slot (none for an unclaimed pair, for a bad Stored query id and for a query the list leaves out) and
 // itself, the sort's value
@@ -241,12 +228,7 @@ __global__ __launch_bounds__(256) void ph_labelset_positions_kernel(PhLabelsetAr
 
 // whether query q owns every pair of a sound range: what makes its row; wave-uniform
 __device__ __forceinline__ bool ph_labelset_query_ok(const PhLabelsetArgs &s, uint32_t q, uint32_t b, uint32_t e, uint32_t lane) {
-  if (!ph_labelset_range_ok(b, e, s.nwant)) return false;
-  for (uint32_t i0 = b; i0 < e; i0 += 64u) {  // i0 + lane cannot wrap: e <= nwant < 2^31
-    const uint32_t i = i0 + lane;
-    if (__ballot(i < e && s.owner[i] != q)) return false;
-  }
-  return true;
+  return ph_labelset_owns_range(s.owner, s.nwant, q, b, e, lane);  // labelset_claim.h
 }
 
 // One wave per query: the lists of every position of its pairs -- duplicates and slot-less pairs left out -- through the
@@ -699,7 +681,7 @@ int labelset_run(const phnsw_index *ix, const phnsw_labels *lb, const PhLabelset
     a.scratch = (uint64_t *)set.keys;
 
     PH_HIP(hipMemsetAsync(sa.owner, 0xFF, (size_t)np * 4u, c.stream));  // PH_LABELSET_OWNER_NONE
-    hipLaunchKernelGGL(ph_labelset_claim_kernel, dim3(grid1(nq)), dim3(256), 0, c.stream, sa);
+    hipLaunchKernelGGL(ph_labelset_claim_kernel, dim3(grid1(nq)), dim3(256), 0, c.stream, sa.want_first, sa.nq, sa.nwant, sa.owner);
     PH_HIP(hipGetLastError());
     if (c.list) {
       uint32_t *const sel = pre + lay.words;
@@ -860,7 +842,7 @@ int ph_labels_count_set(const phnsw_labels *lb, const uint32_t *want_first_dev, 
   sa.want_first = want_first_dev, sa.want_values = want_values_dev, sa.nq = (uint32_t)nq, sa.nwant = (uint32_t)nwant;
   sa.owner = owner_scratch;
   PH_HIP(hipMemsetAsync(sa.owner, 0xFF, (size_t)nwant * 4u, stream));  // PH_LABELSET_OWNER_NONE
-  hipLaunchKernelGGL(ph_labelset_claim_kernel, dim3(grid1(nq)), dim3(256), 0, stream, sa);
+  hipLaunchKernelGGL(ph_labelset_claim_kernel, dim3(grid1(nq)), dim3(256), 0, stream, sa.want_first, sa.nq, sa.nwant, sa.owner);
   PH_HIP(hipGetLastError());
   hipLaunchKernelGGL(ph_labelset_refused_kernel, dim3((uint32_t)std::min<uint64_t>(nq, 1u << 20)), dim3(64), 0, stream, sa,
                      out_count_dev);

@@ -133,6 +133,37 @@ PH_ROUTE_HD static inline bool ph_auto_set_candidate(const uint32_t *label_of, u
   return v < n && ph_set_holds(label_of[v], first, last, values, none_label);
 }
 
+// ---- a SET of labels AND a numeric range per query (phnsw_search_batch_labelset_ranged,
+// phnsw_search_labelset_ranged_auto): pair_of as in the label-range calls, the set as in the calls by set, and ONE range
+// lo .. hi per query, shared by every label of its set.  Used by the search kernels' set-range mode (search_kernels.h),
+// by filter_auto.hip and by tests/cpp/test_labelset_range_plan.cpp.
+// scan_below == 0 of the routed call by set and range: the measured crossover of phnsw_search_exact_labelset_ranged and
+// the walk by set and range in candidates of the UNION (profiles/labelset_ranged/README.md, "Crossover": sets of 4 labels;
+// at a union of 5 000 rows the scan took 20.8 ms against the walk's 23.6, at 10 000 rows 40.2 against 22.3 -- 1M x 768 f32
+// rows, ef 256 / probe_depth 8, k = 10, 10 000 queries; other set sizes and shapes are unmeasured).  The last measured
+// count at which the scan still won: this scan has no tile path, so it lies below the figure of the scan by set
+#define PH_AUTO_SCAN_BELOW_LABELSET_RANGED 5000u
+PH_ROUTE_HD static inline uint64_t ph_auto_scan_below_labelset_ranged(uint64_t scan_below) {
+  return scan_below != 0u ? scan_below : PH_AUTO_SCAN_BELOW_LABELSET_RANGED;
+}
+// the test of one composite: its label word is one of values[first .. last) and its key word lies inside [lo, hi].  A
+// NONE label in the set can only match none_pair's top word, which the last term refuses (a listed composite's label is
+// at most 0xFFFFFFFE); lo > hi passes nothing without a scalar test; a duplicate matches what its first copy matches.
+// The caller has found the range [first, last) sound.
+PH_ROUTE_HD static inline bool ph_pairset_holds(uint64_t pair, uint32_t first, uint32_t last, const uint32_t *values, uint32_t lo,
+                                                uint32_t hi, uint64_t none_pair) {
+  const uint32_t lbl = (uint32_t)(pair >> 32), key = (uint32_t)pair;
+  bool hit = false;
+  for (uint32_t i = first; i < last; i++) hit |= values[i] == lbl;
+  return hit && key >= lo && key <= hi && pair != none_pair;
+}
+// e of ph_auto_full_len for a call by set and range: exclude[q] is a candidate iff it passes the walk's predicate
+PH_ROUTE_HD static inline bool ph_auto_pairset_candidate(const uint64_t *pair_of, uint32_t n, uint32_t first, uint32_t last,
+                                                         const uint32_t *values, uint32_t lo, uint32_t hi, uint32_t v,
+                                                         uint64_t none_pair) {
+  return v < n && ph_pairset_holds(pair_of[v], first, last, values, lo, hi, none_pair);
+}
+
 // the route of a query with c candidates.  c and n_nodes are 32-bit counts, ef and k at most 1024: the two products
 // stay below 2^42 and cannot wrap
 PH_ROUTE_HD static inline uint32_t ph_auto_route(uint32_t c, uint64_t scan_below, uint32_t ef, uint32_t k, uint32_t n_nodes) {

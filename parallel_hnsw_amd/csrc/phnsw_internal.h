@@ -243,6 +243,8 @@ struct PhFilter {
   // ... or its label-range form: pair_of != nullptr, the column [n] of a phnsw_label_attr handle (the composite
   // (label << 32) | key of a listed vector, UINT64_MAX elsewhere), pair_want, pair_lo and pair_hi [nq], the label and
   // the inclusive bounds of each query; nothing of the forms above goes with it
+  // ... or the set form of that: pair_of and set_first != nullptr -- the set table above in place of pair_want, which is
+  // then unused, and pair_lo, pair_hi [nq], ONE range per query shared by the labels of its set; label_of stays nullptr
   const uint64_t *pair_of;
   const uint32_t *pair_want, *pair_lo, *pair_hi;
 };
@@ -426,7 +428,8 @@ struct PhSearchArgs {
   // the filter by a label and a numeric range (search_label_ranged.hip): pair_of [n], the composite (label << 32) | key
   // of every listed vector and UINT64_MAX elsewhere; pair_want / pair_lo / pair_hi [nq], the label and the inclusive
   // bounds of query q.  nullptr = not a label-range launch; never with a bitmap, a label, a set or a range, and never
-  // collecting.  (At the end, like the pairs above.)
+  // collecting.  (At the end, like the pairs above.)  With set_first beside pair_of the launch is one by a SET of labels
+  // and a range (search_labelset_ranged.hip): the set table above instead of pair_want (nullptr), label_of nullptr.
   const uint64_t *pair_of;
   const uint32_t *pair_want, *pair_lo, *pair_hi;
 };
@@ -605,6 +608,8 @@ struct PhAutoCall {
   const uint32_t *range_lo, *range_hi;  // [nq]
   // the label-range form (phnsw_search_label_ranged_auto): candidates = the listed vectors with label pair_want[q] and
   // pair_lo[q] <= key <= pair_hi[q]; filter, labels and attr are then unused
+  // ... and its set form (phnsw_search_labelset_ranged_auto): label_attr with want_first, want_values and nwant (above)
+  // in place of pair_want (nullptr); labels stays nullptr
   const phnsw_label_attr *label_attr;
   const uint32_t *pair_want, *pair_lo, *pair_hi;  // [nq]
   uint32_t k;
@@ -704,6 +709,20 @@ const uint64_t *ph_label_attr_column(const phnsw_label_attr *h);
 // without its checks)
 int ph_label_attr_count(const phnsw_label_attr *h, const uint32_t *want_dev, const uint32_t *lo_dev, const uint32_t *hi_dev,
                         uint64_t nq, uint32_t *out_count_dev, hipStream_t stream);
+// The request of one scan by label sets and a range (ph_labelset_ranged_device, filter_label_ranged.hip): c without
+// `want` -- c.lo and c.hi [batch_nq] are the one range of each query --, the sets in CSR form (device words, untrusted),
+// nwant pairs.  c.list, c.nq and batch_nq as in PhLabelsetCall: the claim runs over the whole batch
+struct PhLabelsetRangedCall {
+  PhLabelRangedCall c;
+  const uint32_t *want_first, *want_values;
+  uint64_t nwant, batch_nq;
+};
+int ph_labelset_ranged_device(const phnsw_index *ix, const phnsw_label_attr *h, const PhLabelsetRangedCall &sc);
+// out_count_dev[q] = the candidates of query q as phnsw_label_attr_count_set_device counts them, and 0 for a query the
+// scan refuses (a range that is not sound, or a pair that a lower query holds); owner_scratch [nwant] words
+int ph_label_attr_count_set(const phnsw_label_attr *h, const uint32_t *want_first_dev, const uint32_t *want_values_dev,
+                            const uint32_t *lo_dev, const uint32_t *hi_dev, uint64_t nq, uint64_t nwant, uint32_t *out_count_dev,
+                            uint32_t *owner_scratch, hipStream_t stream);
 void ph_auto_free(phnsw_index *ix);
 void ph_dense_free(phnsw_index *ix);  // filter_dense.hip
 // the checks the table calls make before they look at another argument: index, k, store kind and row length

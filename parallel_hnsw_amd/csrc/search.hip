@@ -188,6 +188,7 @@ static PhKernelChoice pick_search_kernel(const phnsw_store *s, uint32_t ef_max, 
   if (mode == PH_FM_LABELSET && k.fn) k.fn = ph_pick_labelset_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
   if (mode == PH_FM_RANGE && k.fn) k.fn = ph_pick_ranged_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
   if (mode == PH_FM_LABEL_RANGE && k.fn) k.fn = ph_pick_label_ranged_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
+  if (mode == PH_FM_LABELSET_RANGE && k.fn) k.fn = ph_pick_labelset_ranged_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
   // the collecting twins: the new calls only (PhSearchArgs::collect_k), and only the last launch of their descent
   if (mode == (PH_FM_BITMAP | PH_FM_COLLECT) && k.fn)
     k.fn = ph_pick_collect_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
@@ -337,7 +338,9 @@ static int search_launch_dense(PhWorkspace &ws, PhSearchArgs &a, hipStream_t str
     ph_set_error("a collecting search has no dense-only launch");
     return PHNSW_E_UNSUPPORTED;
   }
-  ph_search_fn fn = mode == PH_FM_LABEL_RANGE
+  ph_search_fn fn = mode == PH_FM_LABELSET_RANGE
+                        ? ph_pick_labelset_ranged_dense(capc)
+                    : mode == PH_FM_LABEL_RANGE
                         ? ph_pick_label_ranged_dense(capc)
                     : mode == PH_FM_RANGE
                         ? ph_pick_ranged_dense(capc)
@@ -445,6 +448,14 @@ int ph_search_launch(const phnsw_index *ix, PhWorkspace &ws, PhSearchArgs &a, hi
         !a.pair_want || !a.pair_lo || !a.pair_hi) {
       ph_set_error("a search by label and range takes the pair column, its labels and its two bounds alone: no bitmap, no label, "
                    "no set, no range, not collecting");
+      return PHNSW_E_UNSUPPORTED;
+    }
+  }
+  if (mode & PH_FM_LABELSET_RANGE) {  // a set-range launch carries the pair column, the set table and the two bounds, nothing else
+    if ((mode & PH_FM_COLLECT) || a.filter || a.label_of || a.label_want || a.attr_of || a.range_lo || a.range_hi || a.pair_want ||
+        !a.pair_lo || !a.pair_hi || (!a.set_values && a.set_nwant)) {
+      ph_set_error("a search by label sets and range takes the pair column, the set table and its two bounds alone: no bitmap, no "
+                   "label column, no single label, no attribute column, not collecting");
       return PHNSW_E_UNSUPPORTED;
     }
   }

@@ -4,7 +4,8 @@
 // restriction read from a label column; search_collect.hip and search_collect_labeled.hip the collecting twins of those
 // two (PH_FM_COLLECT); search_labelset.hip the twins over a SET of labels per query (PH_FM_LABELSET); search_ranged.hip
 // the twins over a numeric range of an attribute column per query (PH_FM_RANGE); search_label_ranged.hip the twins over a
-// label and a numeric range per query (PH_FM_LABEL_RANGE).  Eight units so that they compile side by side.
+// label and a numeric range per query (PH_FM_LABEL_RANGE); search_labelset_ranged.hip the twins over a set of labels and a
+// numeric range per query (PH_FM_LABELSET_RANGE).  Nine units so that they compile side by side.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -120,27 +121,56 @@ __device__ __forceinline__ bool vis_insert(uint32_t *H, uint32_t slots, uint32_t
 //                 ph_search_kernel_dense<2> 20 bytes of scratch that its range sibling does not use, as two aligned 64-bit
 //                 bounds and as three words alike (profiles/label_ranged).  Never with a bitmap, a label, a set or a
 //                 range, and there is no collecting twin.
+//   PH_FM_LABELSET_RANGE  the column of composites (a.pair_of) and, per query, a SET of wanted labels (a.set_first,
+//                 a.set_values, as in PH_FM_LABELSET: offsets read once per query, not trusted, ST_SET_RANGE for a range
+//                 that is not sound) and ONE inclusive range shared by the set's labels (a.pair_lo, a.pair_hi): VectorId v
+//                 passes iff the label word of pair_of[v] is one of set_values[first .. last), its key word lies inside
+//                 [lo, hi] and pair_of[v] is not UINT64_MAX -- ONE 8-byte load per lane, then PH_FM_LABELSET's loop over
+//                 the wave-uniform set values against the label word, and two compares of the key word
+//                 (ph_pairset_holds, filter_route.h).  A NONE label in the set, lo > hi and duplicates need no scalar
+//                 test.  The two bounds are read ONCE PER QUERY in front of the walk, beside the two offsets, and held
+//                 across it -- NOT where the test runs, as PH_FM_LABEL_RANGE reads its three words: here that form left
+//                 five instances with scratch where the set twin has none, this one leaves one
+//                 (profiles/labelset_ranged, which compiles the other form with -DPH_LABELSET_RANGE_BOUNDS_AT_TEST).
+//                 a.pair_want is unused.  Never with a bitmap, a single
+//                 label or an attribute column, and there is no collecting twin.
 // A mode of the body and not a run-time test of the pointers: the test alone cost 19 of the 88 kernels scratch
 // (profiles/filter), so the filtered instances exist beside the others and are picked only when a filter is given.
 //   PH_FM_COLLECT  a bit on top of PH_FM_BITMAP / PH_FM_LABEL: the collecting walk (phnsw_search_collect*, search_collect.hip,
 //                  search_collect_labeled.hip).  The descent is the PLAIN search's -- the layer tails apply `exclude` only --
 //                  and the walk of the last layer keeps, beside the layer's queue, the a.collect_k best evaluated rows
 //                  that pass the filter (`kq`, below); those are the result row.  Only ever the last launch of a descent.
-enum : int { PH_FM_NONE = 0, PH_FM_BITMAP = 1, PH_FM_LABEL = 2, PH_FM_COLLECT = 4, PH_FM_LABELSET = 8, PH_FM_RANGE = 16, PH_FM_LABEL_RANGE = 32 };
+enum : int { PH_FM_NONE = 0, PH_FM_BITMAP = 1, PH_FM_LABEL = 2, PH_FM_COLLECT = 4, PH_FM_LABELSET = 8, PH_FM_RANGE = 16, PH_FM_LABEL_RANGE = 32, PH_FM_LABELSET_RANGE = 64 };
 #define ST_SET_RANGE 8u  // the status of a query whose set range is not sound: phnsw_search_exact_labelset_device's value
 // the mode a launch's arguments ask for
 static inline int ph_filter_mode(const PhSearchArgs &a) {
-  const int where = a.pair_of   ? PH_FM_LABEL_RANGE
+  const int where = a.pair_of   ? (a.set_first ? PH_FM_LABELSET_RANGE : PH_FM_LABEL_RANGE)
                     : a.attr_of ? PH_FM_RANGE
                               : (a.set_first ? PH_FM_LABELSET : (a.label_of ? PH_FM_LABEL : (a.filter ? PH_FM_BITMAP : PH_FM_NONE)));
   return where | (a.collect_k ? PH_FM_COLLECT : PH_FM_NONE);
+}
+
+// What a query of the set modes gets whose range in set_values is not sound: the row of a failed query, ST_SET_RANGE,
+// stats 0; nothing of set_values has been read
+__device__ __forceinline__ void ph_search_refuse_set(const PhSearchArgs &a, uint32_t q, uint32_t lane) {
+  const uint32_t ostride = a.out_stride ? a.out_stride : a.ef;
+  for (uint32_t i = lane; i < ostride; i += 64) {
+    a.out_ids[(uint64_t)q * ostride + i] = PH_EMPTY32;
+    a.out_d[(uint64_t)q * ostride + i] = PH_FMAX;
+  }
+  if (lane == 0) {
+    a.out_len[q] = 0u;
+    a.status[q] = ST_SET_RANGE;
+    if (a.out_stats) a.out_stats[2 * (uint64_t)q] = 0u, a.out_stats[2 * (uint64_t)q + 1] = 0u;
+    if (a.out_key) a.out_key[q] = PH_EMPTY32;
+  }
 }
 
 template <int CAPC, class Dist, bool INSTR = false, bool BIG = false, int FILT = PH_FM_NONE>
 __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
   extern __shared__ uint32_t smem[];
   constexpr int CAP = CAPC * 64;
-  constexpr int FM = FILT & (PH_FM_BITMAP | PH_FM_LABEL | PH_FM_LABELSET | PH_FM_RANGE | PH_FM_LABEL_RANGE);  // where the filter is read from
+  constexpr int FM = FILT & (PH_FM_BITMAP | PH_FM_LABEL | PH_FM_LABELSET | PH_FM_RANGE | PH_FM_LABEL_RANGE | PH_FM_LABELSET_RANGE);  // where the filter is read from
   constexpr bool COLLECT = (FILT & PH_FM_COLLECT) != 0;
   constexpr int TAILF = COLLECT ? PH_FM_NONE : FM;  // closest_vectors' `include` beyond `exclude`: none in a collecting walk
   uint32_t *Cid = smem;                    // running candidates: VectorIds (search.rs:110)
@@ -244,27 +274,22 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
     // query here, before anything of set_values is read: the row a failed query gets, ST_SET_RANGE, stats 0.  (A later
     // launch of a split descent never comes here: the status check above.)
     uint32_t set_b = 0, set_e = 0;
-    if constexpr (FM == PH_FM_LABELSET) {
+    if constexpr (FM == PH_FM_LABELSET || FM == PH_FM_LABELSET_RANGE) {
       set_b = rfl32(a.set_first[q]);
       set_e = rfl32(a.set_first[q + 1u]);
       if (!ph_set_range_sound(set_b, set_e, a.set_nwant)) {
-        const uint32_t ostride = a.out_stride ? a.out_stride : a.ef;
-        for (uint32_t i = lane; i < ostride; i += 64) {
-          a.out_ids[(uint64_t)q * ostride + i] = PH_EMPTY32;
-          a.out_d[(uint64_t)q * ostride + i] = PH_FMAX;
-        }
-        if (lane == 0) {
-          a.out_len[q] = 0u;
-          a.status[q] = ST_SET_RANGE;
-          if (a.out_stats) a.out_stats[2 * (uint64_t)q] = 0u, a.out_stats[2 * (uint64_t)q + 1] = 0u;
-          if (a.out_key) a.out_key[q] = PH_EMPTY32;
-        }
+        ph_search_refuse_set(a, q, lane);
         continue;
       }
     }
     // ... or the bounds of its range (wave-uniform, inclusive)
     const uint32_t range_lo = FM == PH_FM_RANGE ? rfl32(a.range_lo[q]) : 0u;
     const uint32_t range_hi = FM == PH_FM_RANGE ? rfl32(a.range_hi[q]) : 0u;
+#ifndef PH_LABELSET_RANGE_BOUNDS_AT_TEST
+    // ... or, beside the offsets of its set, the bounds of the set-range mode (wave-uniform, inclusive)
+    const uint32_t pairset_lo = FM == PH_FM_LABELSET_RANGE ? rfl32(a.pair_lo[q]) : 0u;
+    const uint32_t pairset_hi = FM == PH_FM_LABELSET_RANGE ? rfl32(a.pair_hi[q]) : 0u;
+#endif
     // the filter test of VectorId v, written once for the layer tail, the strict pass and the collecting walk (callers
     // guard it: only lanes holding an id read a word or a label)
     auto passes = [&](uint32_t v) -> bool {
@@ -279,6 +304,12 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
         return ph_range_holds(a.attr_of[v], range_lo, range_hi, PHNSW_ATTR_NONE);
       } else if constexpr (FM == PH_FM_LABEL_RANGE) {
         return ph_pair_holds_words(a.pair_of[v], rfl32(a.pair_want[q]), rfl32(a.pair_lo[q]), rfl32(a.pair_hi[q]), 0xFFFFFFFFFFFFFFFFull);
+      } else if constexpr (FM == PH_FM_LABELSET_RANGE) {
+#ifndef PH_LABELSET_RANGE_BOUNDS_AT_TEST
+        return ph_pairset_holds(a.pair_of[v], set_b, set_e, a.set_values, pairset_lo, pairset_hi, 0xFFFFFFFFFFFFFFFFull);
+#else  // the form profiles/labelset_ranged compiles for comparison
+        return ph_pairset_holds(a.pair_of[v], set_b, set_e, a.set_values, rfl32(a.pair_lo[q]), rfl32(a.pair_hi[q]), 0xFFFFFFFFFFFFFFFFull);
+#endif
       } else {
         return true;
       }
@@ -1245,6 +1276,9 @@ ph_search_fn ph_pick_labeled_dense(int capc);
 // the set twins: search_labelset.hip
 ph_search_fn ph_pick_labelset_kernel(int family, int capc, int nv, int pqr_m, bool pq_global);
 ph_search_fn ph_pick_labelset_dense(int capc);
+// the set-range twins: search_labelset_ranged.hip
+ph_search_fn ph_pick_labelset_ranged_kernel(int family, int capc, int nv, int pqr_m, bool pq_global);
+ph_search_fn ph_pick_labelset_ranged_dense(int capc);
 // the range twins: search_ranged.hip
 ph_search_fn ph_pick_ranged_kernel(int family, int capc, int nv, int pqr_m, bool pq_global);
 ph_search_fn ph_pick_ranged_dense(int capc);

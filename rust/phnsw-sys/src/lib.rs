@@ -433,6 +433,48 @@ extern "C" {
                                                  scan_below: u64, out_ids_dev: *mut u32, out_d_dev: *mut c_float,
                                                  out_len_dev: *mut u32, out_route_dev: *mut u32, status_dev: *mut u32,
                                                  stream: *mut c_void) -> c_int;
+    // a set of labels and one numeric range per query, over the same handle: (want_first, want_values[, nwant], lo, hi)
+    pub fn phnsw_label_attr_count_set_device(h: *const phnsw_label_attr, want_first_dev: *const u32,
+                                             want_values_dev: *const u32, lo_dev: *const u32, hi_dev: *const u32, nq: u64,
+                                             nwant: u64, out_count_dev: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn phnsw_search_exact_labelset_ranged(ix: *const phnsw_index, h: *const phnsw_label_attr, queries: *const c_float,
+                                              qids: *const u64, nq: u64, exclude: *const u64, want_first: *const u32,
+                                              want_values: *const u32, lo: *const u32, hi: *const u32, k: u64,
+                                              out_ids: *mut u64, out_d: *mut c_float, out_len: *mut u64) -> c_int;
+    pub fn phnsw_search_exact_labelset_ranged_device(ix: *const phnsw_index, h: *const phnsw_label_attr,
+                                                     queries_dev: *const c_float, ldq: u32, qids_dev: *const u32, nq: u64,
+                                                     exclude_dev: *const u32, want_first_dev: *const u32,
+                                                     want_values_dev: *const u32, nwant: u64, lo_dev: *const u32,
+                                                     hi_dev: *const u32, k: u64, out_ids_dev: *mut u32,
+                                                     out_d_dev: *mut c_float, out_len_dev: *mut u32, status_dev: *mut u32,
+                                                     stream: *mut c_void) -> c_int;
+    pub fn phnsw_search_batch_labelset_ranged(ix: *const phnsw_index, h: *const phnsw_label_attr, queries: *const c_float,
+                                              qids: *const u64, nq: u64, sp: *const phnsw_search_params, upto_layers: u32,
+                                              exclude: *const u64, want_first: *const u32, want_values: *const u32,
+                                              lo: *const u32, hi: *const u32, flags: u32, k: u64, out_ids: *mut u64,
+                                              out_d: *mut c_float, out_len: *mut u64, out_stats: *mut u64) -> c_int;
+    pub fn phnsw_search_batch_labelset_ranged_device(ix: *const phnsw_index, h: *const phnsw_label_attr,
+                                                     queries_dev: *const c_float, ldq: u32, qids_dev: *const u32, nq: u64,
+                                                     sp: *const phnsw_search_params, upto_layers: u32,
+                                                     exclude_dev: *const u32, want_first_dev: *const u32,
+                                                     want_values_dev: *const u32, nwant: u64, lo_dev: *const u32,
+                                                     hi_dev: *const u32, flags: u32, out_ids_dev: *mut u32,
+                                                     out_d_dev: *mut c_float, out_len_dev: *mut u32,
+                                                     out_stats_dev: *mut u32, status_dev: *mut u32,
+                                                     stream: *mut c_void) -> c_int;
+    pub fn phnsw_search_labelset_ranged_auto(ix: *const phnsw_index, h: *const phnsw_label_attr, queries: *const c_float,
+                                             qids: *const u64, nq: u64, sp: *const phnsw_search_params, exclude: *const u64,
+                                             want_first: *const u32, want_values: *const u32, lo: *const u32,
+                                             hi: *const u32, k: u64, scan_below: u64, out_ids: *mut u64,
+                                             out_d: *mut c_float, out_len: *mut u64, out_route: *mut u32) -> c_int;
+    pub fn phnsw_search_labelset_ranged_auto_device(ix: *const phnsw_index, h: *const phnsw_label_attr,
+                                                    queries_dev: *const c_float, ldq: u32, qids_dev: *const u32, nq: u64,
+                                                    sp: *const phnsw_search_params, exclude_dev: *const u32,
+                                                    want_first_dev: *const u32, want_values_dev: *const u32, nwant: u64,
+                                                    lo_dev: *const u32, hi_dev: *const u32, k: u64, scan_below: u64,
+                                                    out_ids_dev: *mut u32, out_d_dev: *mut c_float,
+                                                    out_len_dev: *mut u32, out_route_dev: *mut u32, status_dev: *mut u32,
+                                                    stream: *mut c_void) -> c_int;
     // the collecting search: the plain walk whose last layer keeps the best k allowed rows it evaluates (k <= 64)
     pub fn phnsw_search_collect(ix: *const phnsw_index, queries: *const c_float, qids: *const u64, nq: u64,
                                 sp: *const phnsw_search_params, upto_layers: u32, exclude: *const u64, filter: *const u32,
