@@ -326,6 +326,103 @@ int phnsw_search_exact_shared_device(const phnsw_index *ix, const float *queries
                                      const uint32_t *qids_dev, uint64_t nq, const uint32_t *exclude_dev,
                                      const uint32_t *filter_dev, uint64_t k, uint32_t *out_ids_dev, float *out_d_dev,
                                      uint32_t *out_len_dev, uint32_t *status_dev, void *stream);
+/* ---- exact RADIUS search: every candidate closer to a query than the query's radius, for a batch of queries and ONE
+ * allow-list shared by the batch (near-duplicate detection, clustering joins, retrieval by threshold).  The candidates
+ * and the distance tables are those of phnsw_search_exact_shared; in place of the top-k select a table is compacted by
+ * threshold into a pool of (query, distance, id) records, which is sorted and unpacked after the last table.
+ * Arguments: those of phnsw_search_exact_shared[_device] with `radius` [nq] f32 (one per query) and `cap`, the entries
+ * out_ids / out_d hold, in place of k.
+ * Candidates of q: exactly those of phnsw_search_exact_shared -- v < n, bit set (filter NULL = the index's default
+ * filter, else every vector of the index), v != exclude[q], v a vector of the bottom layer.
+ * A candidate is returned iff d(q, v) < radius[q] as an f32 comparison: strict, as the reference's threshold_nn takes
+ * while distance < threshold (src/lib.rs:955-958).  A NaN, zero or negative radius matches nothing; a candidate at +inf
+ * or NaN is never inside a radius, not even +inf.
+ * Result (CSR): the rows of q are out_ids / out_d[out_first[q] .. out_first[q + 1]), ascending by (distance, id);
+ * out_first has nq + 1 entries, out_first[0] == 0 and out_first[nq] == *out_total.  The distances carry the bits of
+ * phnsw_distance_batch on the same store (a -0.0 comes back as +0.0, as from the exact top-k calls).
+ * Size negotiation, as snprintf: out_first and *out_total are always complete and exact; out_ids / out_d are written
+ * only if *out_total <= cap, and left untouched otherwise -- call again with cap >= *out_total.  cap == 0 with NULL
+ * out_ids / out_d is the count-only form: no record is kept, sorted or written.  The return is PHNSW_OK in all three
+ * cases.  cap <= 2^31 - 1 and nq <= 2^31 - 2, else PHNSW_E_INVALID.  The scratch of a call holds min(cap, nq x
+ * candidates) records of 12 bytes twice over, so a cap far above the total costs device memory, not time.
+ * The result does not depend on PHNSW_DENSE_NODES / PHNSW_DENSE_TABLE_BYTES (the knobs of phnsw_search_exact_shared,
+ * which cut the tables here too), on the chunk plan or on how the waves are scheduled: the pool's order does, the
+ * sorted order does not, because the keys of one query are distinct.
+ * Checks, in this order (as phnsw_search_exact_shared, cap in k's place): a null index or one without layers, then cap
+ * above 2^31 - 1 (PHNSW_E_INVALID); then the store: f32, f16, i8 and i8q stores with rows of at most 1536 floats, every
+ * metric the store kind has -- a PQ store of either form and longer rows are PHNSW_E_UNSUPPORTED
+ * (phnsw_exact_shared_supported(ix, 1) answers for this call too); then nq == 0: the empty result (the host form writes
+ * out_first[0] = 0 and *out_total = 0 where the pointers are given; the device form enqueues nothing); then exactly one
+ * of queries / qids, radius, out_first, out_total, the device form's status, out_ids / out_d unless cap == 0, nq
+ * (PHNSW_E_INVALID); the host form then refuses a Stored query id at or past n as its siblings do (PHNSW_E_INVALID).
+ * PHNSW_DENSE_TIMES=1 prints the steps' times of a call on stderr.
+ * OUT OF SCOPE, so that nobody assumes otherwise: per-query bitmaps, labels or ranges as the filter of a radius call; a
+ * radius search by graph walk; routing between a walk and this call; re-ranked (f16 / i8 / PQ first, f32 after) radius
+ * calls -- a converted store is searched with its own distances, as by phnsw_search_exact_shared.
+ * Guidance (measured on 1M x 768 f32 rows, cosine, 10 000-query batches, no filter, one radius for the batch, the calls
+ * alternating in one run; profiles/radius/README.md): with 9.6 / 97.6 / 991.7 rows inside the radius per query on
+ * average the call took 179.7 / 185.0 / 202.5 ms, against 177.3 ms of phnsw_search_exact_shared at k = 10 over the same
+ * tables: 2.3, 8.0 and 25.2 ms for compaction, sort and unpack in place of that call's select.  The count-only form took
+ * 176.0 / 179.8 / 185.9 ms.  Of a call's 150 ms of tables and 33 to 54 ms of compaction the sort is 0.2 to 1.1 ms.
+ * f16, i8 and i8q stores, L2 and ragged dimensions (the vector-unit pass), a filter, per-query radii, other batch sizes,
+ * the host form and a cap below the total (two calls): not measured. */
+int phnsw_search_exact_radius(const phnsw_index *ix, const float *queries, const uint64_t *qids, uint64_t nq,
+                              const uint64_t *exclude, const uint32_t *filter, const float *radius, uint64_t cap,
+                              uint64_t *out_first, uint64_t *out_ids, float *out_d, uint64_t *out_total);
+/* device form: device pointers; u32 ids [cap], u64 out_first [nq + 1] and one u64 at out_total_dev; queries [nq][ldq]
+ * as for phnsw_search_batch_device.  status_dev[q]: 0 = ok, 4 = a Stored query id at or past n (its segment is then
+ * empty, the other segments unaffected).  The call SYNCHRONISES `stream` twice: once to read the candidate count back
+ * (the tables' shape depends on it) and once, after the last table, to read the total (whether and how much to sort
+ * depends on it); with cap == 0 only the first.  The sort and the unpack are enqueued after that and the call returns
+ * without waiting for them.  Thread safe like the other exact calls: every call in flight has a scratch set of its
+ * own. */
+int phnsw_search_exact_radius_device(const phnsw_index *ix, const float *queries_dev, uint32_t ldq,
+                                     const uint32_t *qids_dev, uint64_t nq, const uint32_t *exclude_dev,
+                                     const uint32_t *filter_dev, const float *radius_dev, uint64_t cap,
+                                     uint64_t *out_first_dev, uint32_t *out_ids_dev, float *out_d_dev,
+                                     uint32_t *status_dev, uint64_t *out_total_dev, void *stream);
+/* ---- RADIUS search by graph walk: the approximate sibling of phnsw_search_exact_radius, for external queries with a
+ * radius each.  The reference's own functions, composed: layers[0 .. L-1) are descended exactly as search_layers does
+ * (search.rs:93-140: queue capacity number_of_candidates, upper_layer_candidate_count, probe_depth, include = v !=
+ * exclude[q]); on the bottom layer the running candidates are mapped to NodeIds as closest_vectors maps them
+ * (lib.rs:258-266) into a queue of capacity number_of_candidates, and that queue goes through threshold_nn's loop
+ * (lib.rs:944-953) with threshold = radius[q]: last = 0, last_size = 0; while last < r and len > last_size: closest_nodes,
+ * last = the queue's last distance, and the capacity doubles when last < r and the queue is full.
+ * Result: the queue's entries with v != exclude[q], taken while d < radius[q], as VectorIds, ascending by (distance, id).
+ * An excluded id is never returned (there is no entry-vector quirk: the row is read from the queue, not merged into the
+ * running candidates).  out_len[q] is the number of such entries and MAY EXCEED max_out; the row holds the nearest
+ * max_out of them, padded with PHNSW_EMPTY / f32::MAX; 1 <= max_out <= 1024.  A zero, negative or NaN radius makes no
+ * bottom-layer call: the empty row, and the counters of the upper layers alone.
+ * out_status[q]: 0 = ok; 4 = a candidate is not a node of the layer below, or (device form) a Stored query id at or past
+ * n; 5 = the spill list overflowed; 6 = the queue would pass 1024 entries (the queues live in LDS): the row is empty
+ * and out_len[q] is 0 -- phnsw_search_exact_radius answers such a query.  out_stats (nullable): [nq][2] = {distance
+ * evaluations, hops}.  number_of_candidates <= 1024 as everywhere.
+ * Every call runs as ONE launch: it takes no part in the split descent of large batches, the locality order or the
+ * dense top-layer tables, none of which changes a result.  Stores: f32, f16, i8 and i8q rows of at most 1536 floats (a
+ * converted store is searched with its own distances); a PQ store of either form is PHNSW_E_UNSUPPORTED.
+ * Checks, in this order: the index and the search parameters as phnsw_search_batch; max_out outside 1..1024
+ * (PHNSW_E_INVALID); the store; nq == 0, a no-op; exactly one of queries / qids, radius and the outputs
+ * (PHNSW_E_INVALID); the host form then refuses a Stored query id at or past n.
+ * OUT OF SCOPE: a filter on this call; the global-memory queue of phnsw_threshold_nn for external queries (status 6
+ * instead); routing between this walk and the exact call on the device.
+ * Guidance (1M x 768 f32 rows, 10 000 queries, max_out 1024, upper_layer_candidate_count = number_of_candidates / 4,
+ * probe_depth 2; profiles/radius/README.md): at number_of_candidates 128 / 256 / 512 the walk took 10.3 / 13.5 / 19.7 ms
+ * with about 10 rows inside the radius per query, 10.8 / 13.6 / 19.7 ms with about 98, and 20.9 / 20.0 / 21.1 ms with about
+ * 992 -- 1.5 to 3.0 times the plain walk (phnsw_search_batch_device) at the same parameters -- and returned 0.81 / 0.91 /
+ * 0.96, 0.74 / 0.84 / 0.91 and 0.40 / 0.42 / 0.44 of the exact in-radius rows; no query had status 6.  With
+ * upper_layer_candidate_count equal to number_of_candidates the bottom-layer queue starts full and the loop ends after
+ * one call (len cannot pass last_size): choose it smaller.  Other stores, metrics and batch sizes: not measured. */
+int phnsw_search_batch_radius(const phnsw_index *ix, const float *queries, const uint64_t *qids, uint64_t nq,
+                              const phnsw_search_params *sp, const uint64_t *exclude, const float *radius,
+                              uint64_t max_out, uint64_t *out_ids, float *out_d, uint64_t *out_len, uint64_t *out_stats,
+                              uint32_t *out_status);
+/* device form: device pointers, u32 ids [nq][max_out] padded with 0xFFFFFFFF / f32::MAX, u32 out_len and out_stats;
+ * queries [nq][ldq] as for phnsw_search_batch_device; enqueued on `stream` without synchronising. */
+int phnsw_search_batch_radius_device(const phnsw_index *ix, const float *queries_dev, uint32_t ldq,
+                                     const uint32_t *qids_dev, uint64_t nq, const phnsw_search_params *sp,
+                                     const uint32_t *exclude_dev, const float *radius_dev, uint64_t max_out,
+                                     uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                     uint32_t *out_stats_dev, uint32_t *status_dev, void *stream);
 /* ---- exact top-k for a TABLE of allow-lists with a selector per query, grouped by bitmap: a handful of distinct
  * bitmaps (tenants, ACL classes), each shared by many queries of the batch.  The call groups the batch by bitmap on the
  * device and runs every group as phnsw_search_exact_shared runs its batch -- the candidate list of the group's bitmap,

@@ -429,6 +429,73 @@ class Hnsw {
     check(phnsw_search_exact_shared_device(ix_, queries_dev, ldq, qids_dev, nq, exclude_dev, filter_dev, k, out_ids_dev,
                                            out_d_dev, out_len_dev, status_dev, stream));
   }
+  // Exact radius search (phnsw_search_exact_radius): for every query the candidates with d < radius[i] (an f32
+  // comparison, strict; a NaN, zero or negative radius matches nothing), ascending by (distance, id).  Candidates, `allow`
+  // and stores as for search_many_exact_shared, whose distance tables this computes.  Calls the library once with room
+  // for 64 results per query and, when more are inside the radii, once more with exactly that room
+  std::vector<SearchResult> search_many_exact_radius(const std::vector<const float *> &queries, const std::vector<float> &radius,
+                                                     const std::vector<uint32_t> &allow) const {
+    const uint64_t nq = queries.size(), dim = c_->dim(), words = (c_->len() + 31) / 32;
+    if (radius.size() != nq) throw Error(PHNSW_E_INVALID, "search_many_exact_radius: one radius per query");
+    if (!allow.empty() && allow.size() < words)
+      throw Error(PHNSW_E_INVALID, "search_many_exact_radius: allow is shorter than one bitmap (ceil(n / 32) words)");
+    std::vector<float> q(nq * dim);
+    for (uint64_t i = 0; i < nq; i++) std::copy(queries[i], queries[i] + dim, q.begin() + i * dim);
+    std::vector<uint64_t> first(nq + 1), ids(std::max<uint64_t>(nq * 64, 1));
+    std::vector<float> d(ids.size());
+    uint64_t total = 0;
+    for (int round = 0; round < 2; round++) {
+      check(phnsw_search_exact_radius(ix_, q.data(), nullptr, nq, nullptr, allow.empty() ? nullptr : allow.data(), radius.data(),
+                                      ids.size(), first.data(), ids.data(), d.data(), &total));
+      if (total <= ids.size()) break;
+      ids.resize(total), d.resize(total);
+    }
+    std::vector<SearchResult> out(nq);
+    for (uint64_t i = 0; i < nq; i++)
+      for (uint64_t j = first[i]; j < first[i + 1]; j++) out[i].push_back({ids[j], d[j]});
+    return out;
+  }
+  // zero-copy form (phnsw_search_exact_radius_device): u32 ids [cap], u64 first [nq + 1], one u64 total; synchronises
+  // `stream` twice (once with cap == 0)
+  void search_exact_radius_device(const float *queries_dev, uint32_t ldq, const uint32_t *qids_dev, uint64_t nq,
+                                  const uint32_t *exclude_dev, const uint32_t *filter_dev, const float *radius_dev, uint64_t cap,
+                                  uint64_t *out_first_dev, uint32_t *out_ids_dev, float *out_d_dev, uint32_t *status_dev,
+                                  uint64_t *out_total_dev, void *stream) const {
+    check(phnsw_search_exact_radius_device(ix_, queries_dev, ldq, qids_dev, nq, exclude_dev, filter_dev, radius_dev, cap,
+                                           out_first_dev, out_ids_dev, out_d_dev, status_dev, out_total_dev, stream));
+  }
+  // Radius search by graph walk (phnsw_search_batch_radius): the plain descent, then threshold_nn's doubling-queue loop
+  // on the bottom layer against radius[i]; approximate.  Per query the nearest max_out (1..1024) of the entries inside
+  // the radius; `found` (nullable) gets how many were inside it, which may exceed max_out, and `status` (nullable) the
+  // status words -- 6: the queue would pass 1024 entries, an empty row; search_many_exact_radius answers such a query
+  std::vector<SearchResult> search_many_radius(const std::vector<const float *> &queries, const std::vector<float> &radius,
+                                               const SearchParameters &sp, uint64_t max_out, std::vector<uint64_t> *found = nullptr,
+                                               std::vector<uint32_t> *status = nullptr) const {
+    const uint64_t nq = queries.size(), dim = c_->dim();
+    if (radius.size() != nq) throw Error(PHNSW_E_INVALID, "search_many_radius: one radius per query");
+    if (max_out == 0 || max_out > 1024) throw Error(PHNSW_E_INVALID, "search_many_radius: max_out must be 1..1024");
+    std::vector<float> q(nq * dim);
+    for (uint64_t i = 0; i < nq; i++) std::copy(queries[i], queries[i] + dim, q.begin() + i * dim);
+    std::vector<uint64_t> ids(nq * max_out), len(nq);
+    std::vector<float> d(nq * max_out);
+    std::vector<uint32_t> st(nq);
+    check(phnsw_search_batch_radius(ix_, q.data(), nullptr, nq, &sp, nullptr, radius.data(), max_out, ids.data(), d.data(),
+                                    len.data(), nullptr, st.data()));
+    std::vector<SearchResult> out(nq);
+    for (uint64_t i = 0; i < nq; i++)
+      for (uint64_t j = 0; j < std::min(len[i], max_out); j++) out[i].push_back({ids[i * max_out + j], d[i * max_out + j]});
+    if (found) *found = len;
+    if (status) *status = st;
+    return out;
+  }
+  // zero-copy form (phnsw_search_batch_radius_device): u32 ids [nq][max_out]; enqueued on `stream`
+  void search_radius_device(const float *queries_dev, uint32_t ldq, const uint32_t *qids_dev, uint64_t nq,
+                            const SearchParameters &sp, const uint32_t *exclude_dev, const float *radius_dev, uint64_t max_out,
+                            uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev, uint32_t *out_stats_dev,
+                            uint32_t *status_dev, void *stream) const {
+    check(phnsw_search_batch_radius_device(ix_, queries_dev, ldq, qids_dev, nq, &sp, exclude_dev, radius_dev, max_out,
+                                           out_ids_dev, out_d_dev, out_len_dev, out_stats_dev, status_dev, stream));
+  }
   // search_many_exact_filtered for a TABLE of bitmaps and a selector per query (phnsw_search_exact_grouped): query i may
   // return the vectors of bitmap allow_of[i] (PHNSW_FILTER_ALL: every vector of the index).  The batch is grouped by
   // bitmap on the device and every group runs as search_many_exact_shared runs its batch: the same results, bit for

@@ -138,6 +138,11 @@ SYMBOLS = {
     "phnsw_exact_shared_supported": (_i32, [_vp, _u64]),
     "phnsw_search_exact_shared": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp]),
     "phnsw_search_exact_shared_device": (_i32, [_vp, _vp, _u32, _vp, _u64, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "phnsw_search_exact_radius": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "phnsw_search_exact_radius_device": (_i32, [_vp, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "phnsw_search_batch_radius": (_i32, [_vp, _vp, _vp, _u64, C.POINTER(SearchParams), _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "phnsw_search_batch_radius_device": (_i32, [_vp, _vp, _u32, _vp, _u64, C.POINTER(SearchParams), _vp, _vp, _u64, _vp, _vp, _vp,
+                                                _vp, _vp, _vp]),
     "phnsw_search_exact_grouped": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _u32, _u64, _vp, _u64, _vp, _vp, _vp]),
     "phnsw_search_exact_grouped_device": (_i32, [_vp, _vp, _u32, _vp, _u64, _vp, _vp, _u32, _u64, _vp, _u64, _vp, _vp, _vp,
                                                  _vp, _vp]),

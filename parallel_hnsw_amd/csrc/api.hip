@@ -554,6 +554,7 @@ extern "C" void phnsw_index_destroy(phnsw_index *ix) {
   ph_auto_free(ix);
   ph_dense_free(ix);
   ph_grouped_free(ix);
+  ph_radius_free(ix);
   ph_build_table_free(ix);
   if (ix->totals) hipFree(ix->totals);
   if (ix->all_ones) hipFree(ix->all_ones);
@@ -674,6 +675,7 @@ static void fill_args(const phnsw_index *ix, const PhSearchCall &c, PhSearchArgs
   a.first_node = c.first_node;
   a.hit_eps = c.hit_eps;
   a.cap_max = c.knn_mode == 2 ? c.out_stride : 0;
+  if (c.radius) a.radius = c.radius, a.cap_max = 1024u;  // the radius walk: its last layer's queue may double up to the 1024 slots
   a.out_index = c.out_index;  // Hnsw::search_instrumented: the INSTR kernels, every layer on the per-hop path, one launch
   a.order = c.order;
   if (c.collect_k) {  // the caller's rows hold collect_k entries; out_ids / out_d: only a split descent's parking (below)
@@ -814,7 +816,9 @@ int ph_search_device(const phnsw_index *ix, const PhSearchCall &c) {
   // the running candidates are parked in the output rows.
   // (layers evaluated densely, tiny.hip, never read a vector row during the traversal: they stay in
   // the first launch whatever their size)
-  const uint32_t T = (knn_mode || out_index) ? 0u : ph_tiny_layer_count(ix, a.n_layers, a.ef);
+  // (a radius walk re-seeds the last layer's visited set between closest_nodes calls, which the table layers' own
+  // visited bits do not take part in: it walks every layer per hop -- the same distance bits)
+  const uint32_t T = (knn_mode || out_index || c.radius) ? 0u : ph_tiny_layer_count(ix, a.n_layers, a.ef);
   uint32_t first_big = a.n_layers;
   for (uint32_t l = std::max(1u, T); l < a.n_layers; l++)
     if (ph_layer_own_launch(ix->layers[l].n_nodes, ph_row_bytes(ix->store))) {

@@ -90,6 +90,49 @@ __global__ __launch_bounds__(256) void ph_dense_qids_kernel(const uint32_t *qids
   }
 }
 
+// Steps 1 to 3 on scratch the caller holds (`pre`: ph_dense_pre_words(words of the store, ph_dense_list_cap, nq) words),
+// enqueued on `stream`: the count, the list and -- with Stored queries -- their sanitised ids and refusal words.  The
+// exact radius search (filter_radius.hip) builds its candidates with it too.
+uint32_t ph_dense_list_cap(const phnsw_index *ix) {
+  uint32_t n_nodes;
+  const uint32_t *nodes, *vec2node;
+  ph_exact_bottom_layer(ix, &n_nodes, &nodes, &vec2node);
+  return (uint32_t)std::min<uint64_t>(ix->store->n, n_nodes);  // a candidate is a vector of the bottom layer
+}
+
+int ph_dense_list_enqueue(const phnsw_index *ix, const uint32_t *filter, const uint32_t *qids, uint64_t nq, uint32_t *pre,
+                          StepTimes *times, int step_count, int step_list, hipStream_t stream, PhDenseList *out) {
+  const phnsw_store *s = ix->store;
+  const uint64_t nwords = ph_exact_words(s->n);
+  PhDenseListArgs l = {};
+  l.filter = filter, l.n = (uint32_t)s->n, l.nwords = (uint32_t)nwords;
+  ph_exact_bottom_layer(ix, &l.n_nodes, &l.nodes, &l.vec2node);
+  l.cap = ph_dense_list_cap(ix);
+  uint32_t *const head = pre, *const off = head + PH_DENSE_HEAD_WORDS, *const list = off + ph_dense_off_words(nwords);
+  uint32_t *const safe = list + l.cap, *const refuse = safe + nq;
+  l.head = head, l.off = off, l.list = list;
+  times->begin(step_count);
+  PhFilter one = {filter, 0u, 0u};
+  PH_TRY(ph_filter_count(ix, one, 1, head, stream));
+  times->end();
+  times->begin(step_list);
+  const uint32_t wgrid = (uint32_t)std::min<uint64_t>((nwords + 255u) / 256u, 1u << 16);
+  if (nwords) {
+    hipLaunchKernelGGL(ph_dense_popc_kernel, dim3(wgrid), dim3(256), 0, stream, l);
+    hipLaunchKernelGGL(ph_dense_prefix_kernel, dim3(1), dim3(1024), 0, stream, l);
+    hipLaunchKernelGGL(ph_dense_list_kernel, dim3(wgrid), dim3(256), 0, stream, l);
+  } else {
+    PH_HIP(hipMemsetAsync(head, 0, PH_DENSE_HEAD_WORDS * 4u, stream));
+  }
+  if (qids)
+    hipLaunchKernelGGL(ph_dense_qids_kernel, dim3((uint32_t)std::min<uint64_t>((nq + 255u) / 256u, 1u << 16)), dim3(256), 0,
+                       stream, qids, nq, (uint32_t)s->n, safe, refuse);
+  PH_HIP(hipGetLastError());
+  times->end();
+  out->head = head, out->list = list, out->safe = safe, out->refuse = refuse;
+  return 0;
+}
+
 // ------------------------------------------------------------------ the select
 
 struct PhTableSelectArgs {
@@ -178,39 +221,18 @@ int dense_run(const phnsw_index *ix, const PhDenseCall &c, PhDenseSet &set) {
   const uint64_t nq = c.nq, nwords = ph_exact_words(s->n);
   PH_TRY(set.ready());
   if (!set.h_head) PH_HIP(hipHostMalloc((void **)&set.h_head, PH_DENSE_HEAD_WORDS * 4u, hipHostMallocDefault));
-  PhDenseListArgs l = {};
-  l.filter = c.filter, l.n = (uint32_t)s->n, l.nwords = (uint32_t)nwords;
-  ph_exact_bottom_layer(ix, &l.n_nodes, &l.nodes, &l.vec2node);
-  l.cap = (uint32_t)std::min<uint64_t>(s->n, l.n_nodes);  // a candidate is a vector of the bottom layer
-  PH_TRY(set.block_ensure(&set.pre, &set.pre_bytes, (size_t)ph_dense_pre_words(nwords, l.cap, nq) * 4u, c.stream));
-  uint32_t *const head = (uint32_t *)set.pre, *const off = head + PH_DENSE_HEAD_WORDS, *const list = off + ph_dense_off_words(nwords);
-  uint32_t *const safe = list + l.cap, *const refuse = safe + nq;
-  l.head = head, l.off = off, l.list = list;
+  const uint32_t lcap = ph_dense_list_cap(ix);
+  PH_TRY(set.block_ensure(&set.pre, &set.pre_bytes, (size_t)ph_dense_pre_words(nwords, lcap, nq) * 4u, c.stream));
 
   StepTimes times;  // pack and table are one figure: both are enqueued inside tiny_table
   times.on = env_ll("PHNSW_DENSE_TIMES") > 0, times.stream = c.stream;
-  times.begin(0);
-  PhFilter one = {c.filter, 0u, 0u};
-  PH_TRY(ph_filter_count(ix, one, 1, head, c.stream));
-  times.end();
-  times.begin(1);
-  const uint32_t wgrid = (uint32_t)std::min<uint64_t>((nwords + 255u) / 256u, 1u << 16);
-  if (nwords) {
-    hipLaunchKernelGGL(ph_dense_popc_kernel, dim3(wgrid), dim3(256), 0, c.stream, l);
-    hipLaunchKernelGGL(ph_dense_prefix_kernel, dim3(1), dim3(1024), 0, c.stream, l);
-    hipLaunchKernelGGL(ph_dense_list_kernel, dim3(wgrid), dim3(256), 0, c.stream, l);
-  } else {
-    PH_HIP(hipMemsetAsync(head, 0, PH_DENSE_HEAD_WORDS * 4u, c.stream));
-  }
-  if (c.qids)
-    hipLaunchKernelGGL(ph_dense_qids_kernel, dim3((uint32_t)std::min<uint64_t>((nq + 255u) / 256u, 1u << 16)), dim3(256), 0,
-                       c.stream, c.qids, nq, (uint32_t)s->n, safe, refuse);
-  PH_HIP(hipGetLastError());
-  times.end();
+  PhDenseList l;
+  PH_TRY(ph_dense_list_enqueue(ix, c.filter, c.qids, nq, (uint32_t *)set.pre, &times, 0, 1, c.stream, &l));
+  uint32_t *const head = l.head, *const list = l.list, *const safe = l.safe, *const refuse = l.refuse;
   PH_HIP(hipMemcpyAsync(set.h_head, head, 8, hipMemcpyDeviceToHost, c.stream));
   PH_HIP(hipStreamSynchronize(c.stream));  // the one synchronisation: the table's shape depends on the count
   const uint64_t cand = set.h_head[1];
-  if (cand != set.h_head[0] || cand > l.cap) {
+  if (cand != set.h_head[0] || cand > lcap) {
     ph_set_error("exact shared search: the bitmap changed while the call read it (%u candidates counted, %u listed)",
                  set.h_head[0], set.h_head[1]);
     return PHNSW_E_INVALID;

@@ -310,6 +310,7 @@ struct phnsw_index {
   PhCallPool autos;     // filter_auto.hip: PhAutoSet, the scratch of one routed filtered search
   PhCallPool denses;    // filter_dense.hip: PhDenseSet, of one exact search for a shared allow-list
   PhCallPool groupeds;  // filter_grouped.hip: PhGroupedSet, of one exact search over a table of allow-lists
+  PhCallPool radii;     // filter_radius.hip: PhRadiusSet, of one exact radius search
 };
 
 // ---- kernel argument block for the batched greedy search ----
@@ -432,6 +433,11 @@ struct PhSearchArgs {
   // and a range (search_labelset_ranged.hip): the set table above instead of pair_want (nullptr), label_of nullptr.
   const uint64_t *pair_of;
   const uint32_t *pair_want, *pair_lo, *pair_hi;
+  // the radius search by graph walk (search_radius.hip): radius [nq], the threshold of each query's loop on the last
+  // layer; nullptr = not a radius launch.  Selects the PH_FM_RADIUS twins: one launch over every layer, rows of
+  // out_stride entries read from the last layer's queue, cap_max 1024.  Never with a filter, a knn mode or collecting.
+  // (At the end, like the pairs above.)
+  const float *radius;
 };
 
 uint32_t ph_default_ovf_cap(uint32_t ef);
@@ -489,6 +495,9 @@ struct PhSearchCall {
   // rows of collect_k entries; `filter` is what the last layer's walk collects by (never STRICT: the descent itself is
   // the plain search's).  collect_flags: PHNSW_COLLECT_EXTEND
   uint32_t collect_k, collect_flags;
+  // the radius search by graph walk: radius [nq] (device), rows of out_stride = max_out entries read from the last
+  // layer's queue; out_len counts every entry inside the radius.  One launch, no dense tables, no filter
+  const float *radius;
 };
 int ph_search_device(const phnsw_index *ix, const PhSearchCall &c);
 // argument checks the search entry points share (api.hip): index and parameters; the device forms' pointers (`call`
@@ -727,7 +736,20 @@ void ph_auto_free(phnsw_index *ix);
 void ph_dense_free(phnsw_index *ix);  // filter_dense.hip
 // the checks the table calls make before they look at another argument: index, k, store kind and row length
 int ph_dense_check(const phnsw_index *ix, uint64_t k, const char *call);  // filter_dense.hip
+// The candidate list of ONE bitmap as the table calls take it (filter_dense.hip): ph_filter_count's count in head[0],
+// the ascending VectorId list and its length in head[1], and -- with Stored queries -- safe [nq] (ids at or past n
+// replaced by 0) and refuse [nq] (0, or status 4 for such an id).  Enqueued on `stream` into `pre`, which the caller
+// holds: ph_dense_pre_words(words of the store, ph_dense_list_cap(ix), nq) words (dense_plan.h).
+struct PhDenseList {
+  uint32_t *head, *list, *safe, *refuse;
+};
+uint32_t ph_dense_list_cap(const phnsw_index *ix);  // the ids a list can hold at most
+int ph_dense_list_enqueue(const phnsw_index *ix, const uint32_t *filter, const uint32_t *qids, uint64_t nq, uint32_t *pre,
+                          StepTimes *times, int step_count, int step_list, hipStream_t stream, PhDenseList *out);
 void ph_grouped_free(phnsw_index *ix);  // filter_grouped.hip
+void ph_radius_free(phnsw_index *ix);   // filter_radius.hip
+// a scratch set of the index's `radii` pool for a host call that needs only its stream and event (search_radius.hip)
+PhCallSet *ph_radius_host_set(phnsw_index *ix);
 // the argument checks the exact entry points share (api.hip): index with layers, 1 <= k <= 1024, a store kind the
 // distance batch accepts
 int ph_exact_check(const phnsw_index *ix, uint64_t k, const char *call);

@@ -194,6 +194,8 @@ static PhKernelChoice pick_search_kernel(const phnsw_store *s, uint32_t ef_max, 
     k.fn = ph_pick_collect_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
   if (mode == (PH_FM_LABEL | PH_FM_COLLECT) && k.fn)
     k.fn = ph_pick_collect_labeled_kernel(k.family, k.capc, k.nv, k.pqr_m, ph_pq_global_tables());
+  // the radius twins: row stores, the 1024-slot queues (ph_search_device sets cap_max 1024 for them)
+  if (mode == PH_FM_RADIUS && k.fn) k.fn = (kf_rows(k.family) && k.capc == 16) ? ph_pick_radius_kernel(k.family, k.nv) : nullptr;
   return k;
 }
 
@@ -458,6 +460,10 @@ int ph_search_launch(const phnsw_index *ix, PhWorkspace &ws, PhSearchArgs &a, hi
                    "label column, no single label, no attribute column, not collecting");
       return PHNSW_E_UNSUPPORTED;
     }
+  }
+  if ((mode & PH_FM_RADIUS) && (mode != PH_FM_RADIUS || a.layer_lo || a.layer_hi || a.tiny_layers || !a.out_stride || a.out_stride > 1024u)) {
+    ph_set_error("a radius launch is the one launch of its descent, without a filter or dense tables, with rows of 1..1024 entries");
+    return PHNSW_E_UNSUPPORTED;
   }
   if ((mode & PH_FM_COLLECT) &&
       (mode == PH_FM_COLLECT || (a.layer_hi && a.layer_hi != a.n_layers) || !a.collect_ids || !a.collect_d ||

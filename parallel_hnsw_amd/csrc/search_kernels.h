@@ -140,14 +140,22 @@ __device__ __forceinline__ bool vis_insert(uint32_t *H, uint32_t slots, uint32_t
 //                  search_collect_labeled.hip).  The descent is the PLAIN search's -- the layer tails apply `exclude` only --
 //                  and the walk of the last layer keeps, beside the layer's queue, the a.collect_k best evaluated rows
 //                  that pass the filter (`kq`, below); those are the result row.  Only ever the last launch of a descent.
-enum : int { PH_FM_NONE = 0, PH_FM_BITMAP = 1, PH_FM_LABEL = 2, PH_FM_COLLECT = 4, PH_FM_LABELSET = 8, PH_FM_RANGE = 16, PH_FM_LABEL_RANGE = 32, PH_FM_LABELSET_RANGE = 64 };
+//   PH_FM_RADIUS   a mode of its own, with no filter: the radius search by graph walk (phnsw_search_batch_radius*,
+//                  search_radius.hip).  The descent is the PLAIN search's; on the LAST layer the queue the running
+//                  candidates were mapped into goes through threshold_nn's loop (lib.rs:944-953) against the query's own
+//                  a.radius[q] -- closest_nodes again and again, every entry a seed again, the capacity doubled while the
+//                  queue is full and its last entry inside the radius -- and the row is read from that QUEUE: the entries
+//                  other than `exclude`, taken while d < radius, the nearest a.out_stride of them written and ALL of them
+//                  counted in out_len.  Instantiated over the 1024-slot queues only, and only in search_radius.hip; a
+//                  queue that would pass 1024 entries ends the query with ST_CAPACITY.  One launch, no dense tables.
+enum : int { PH_FM_NONE = 0, PH_FM_BITMAP = 1, PH_FM_LABEL = 2, PH_FM_COLLECT = 4, PH_FM_LABELSET = 8, PH_FM_RANGE = 16, PH_FM_LABEL_RANGE = 32, PH_FM_LABELSET_RANGE = 64, PH_FM_RADIUS = 128 };
 #define ST_SET_RANGE 8u  // the status of a query whose set range is not sound: phnsw_search_exact_labelset_device's value
 // the mode a launch's arguments ask for
 static inline int ph_filter_mode(const PhSearchArgs &a) {
   const int where = a.pair_of   ? (a.set_first ? PH_FM_LABELSET_RANGE : PH_FM_LABEL_RANGE)
                     : a.attr_of ? PH_FM_RANGE
                               : (a.set_first ? PH_FM_LABELSET : (a.label_of ? PH_FM_LABEL : (a.filter ? PH_FM_BITMAP : PH_FM_NONE)));
-  return where | (a.collect_k ? PH_FM_COLLECT : PH_FM_NONE);
+  return where | (a.collect_k ? PH_FM_COLLECT : PH_FM_NONE) | (a.radius ? PH_FM_RADIUS : PH_FM_NONE);
 }
 
 // What a query of the set modes gets whose range in set_values is not sound: the row of a failed query, ST_SET_RANGE,
@@ -172,6 +180,7 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
   constexpr int CAP = CAPC * 64;
   constexpr int FM = FILT & (PH_FM_BITMAP | PH_FM_LABEL | PH_FM_LABELSET | PH_FM_RANGE | PH_FM_LABEL_RANGE | PH_FM_LABELSET_RANGE);  // where the filter is read from
   constexpr bool COLLECT = (FILT & PH_FM_COLLECT) != 0;
+  constexpr bool RADIUS = (FILT & PH_FM_RADIUS) != 0;
   constexpr int TAILF = COLLECT ? PH_FM_NONE : FM;  // closest_vectors' `include` beyond `exclude`: none in a collecting walk
   uint32_t *Cid = smem;                    // running candidates: VectorIds (search.rs:110)
   float *Cd = (float *)(smem + CAP);       //
@@ -266,6 +275,8 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
     else
       dist.prepare_stored(a.dist, qvec, dist_lds, lane);
     const uint32_t excl = a.exclude ? a.exclude[q] : PH_EMPTY32;
+    float rad = 0.0f;  // RADIUS: the threshold of this query's loop on the last layer
+    if constexpr (RADIUS) rad = a.radius[q];
     // the allow-list of this query (wave-uniform): `include` of lib.rs:250-277
     const uint32_t *const allow = FM == PH_FM_BITMAP ? a.filter + (uint64_t)q * a.filter_stride : nullptr;
     // ... or the label it wants (wave-uniform); NONE matches nothing, not even the unlisted vectors that carry it
@@ -412,6 +423,20 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
         L.neighbors = a.tiny_nbr + a.tiny_off[li];
       }
       const bool identity = L.vec2node == nullptr;
+      if constexpr (RADIUS) {
+        // `while last < threshold` with last = 0.0 (lib.rs:944-946): a zero, negative or NaN radius never calls
+        // closest_nodes on the last layer, and nothing of the queue lies inside it -- the empty row, the counters of the
+        // layers above
+        if (li == last_layer && !(rad > 0.0f)) {
+          for (uint32_t i = lane; i < a.out_stride; i += 64) {
+            a.out_ids[(uint64_t)q * a.out_stride + i] = PH_EMPTY32;
+            a.out_d[(uint64_t)q * a.out_stride + i] = PH_FMAX;
+          }
+          clen = 0;
+          big_written = true;
+          continue;
+        }
+      }
       bool hv = hslots && !tl;  // this layer's visited set is the LDS table (until it would pass its load limit)
       uint32_t hn = 0;          // ids in the table
       // test-and-set of one id per valid lane in the layer's visited set: true when it was not in it.  A batch that
@@ -503,6 +528,27 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
       float thr_last = 0.0f;
       uint32_t thr_last_size = 0;
       for (;;) {
+      if constexpr (RADIUS) {
+        if (li == last_layer) {
+          if (!(thr_last < rad && qlen > thr_last_size)) break;  // lib.rs:946, threshold = the query's radius
+          const bool again = thr_last_size != 0;  // the first call's seeds were marked when the candidates were mapped
+          thr_last_size = qlen;
+          if (again) {
+            // a fresh closest_nodes call: every queue entry is a seed again (lib.rs:182-187)
+#pragma unroll
+            for (int c = 0; c < CAPC; c++) {
+              uint32_t i = lane + 64u * c;
+              uint32_t nid = 0;
+              if (i < qlen) {
+                nid = Qid[i] & IDM;
+                Qid[i] = nid;
+              }
+              if (64u * c < qlen) visit(nid, i < qlen);
+            }
+            queue_sync<BIG>();
+          }
+        }
+      } else
       if (a.knn_mode == 2) {
         if (!(thr_last < a.threshold && qlen > thr_last_size)) break;  // lib.rs:945
         thr_last_size = qlen;
@@ -885,9 +931,12 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
       wait_vm0();
       hv = hslots && !tl;
       hn = 0;
+      if constexpr (RADIUS) {
+        if (li != last_layer) break;
+      } else
       if (a.knn_mode != 2) break;
       thr_last = Qd[qlen - 1];  // pq.last().1  lib.rs:948
-      if (thr_last < a.threshold && qlen == ef) {  // pq.resize_capacity(capacity * 2)  lib.rs:949-951
+      if (thr_last < (RADIUS ? rad : a.threshold) && qlen == ef) {  // pq.resize_capacity(capacity * 2)  lib.rs:949-951
         if (ef * 2 > (BIG ? a.cap_max : (uint32_t)CAP)) {
           err = ST_CAPACITY;
           break;
@@ -924,6 +973,37 @@ __device__ __forceinline__ void ph_search_body(const PhSearchArgs &a) {
         }
         big_written = true;
         continue;
+      }
+      if constexpr (RADIUS) {
+        // the row of a radius search is read from the queue (lib.rs:954-959): the entries other than `exclude`, taken
+        // while d < radius -- the queue ascends, so that is every such entry --, all of them counted, the nearest
+        // out_stride written
+        if (li == last_layer) {
+          const uint32_t os = a.out_stride;
+          uint32_t kept = 0;
+          for (uint32_t base = 0; base < qlen; base += 64) {
+            const uint32_t i = base + lane;
+            const bool has = i < qlen;
+            const uint32_t nid = has ? (Qid[i] & IDM) : 0u;
+            const uint32_t v = has ? (identity ? nid : L.nodes[nid]) : PH_EMPTY32;
+            const float d = has ? Qd[i] : PH_FMAX;
+            const bool keep = has && v != excl && d < rad;
+            const uint64_t km = __ballot(keep);
+            const uint32_t at = kept + __popcll(km & lt);
+            if (keep && at < os) {
+              a.out_ids[(uint64_t)q * os + at] = v;
+              a.out_d[(uint64_t)q * os + at] = d;
+            }
+            kept += __popcll(km);
+          }
+          for (uint32_t i = min(kept, os) + lane; i < os; i += 64) {
+            a.out_ids[(uint64_t)q * os + i] = PH_EMPTY32;
+            a.out_d[(uint64_t)q * os + i] = PH_FMAX;
+          }
+          clen = kept;  // out_len: every entry inside the radius, written or not
+          big_written = true;
+          continue;
+        }
       }
       // ---- closest_vectors tail: NodeId -> VectorId, filter(include), take(count)  lib.rs:268-276
       const uint32_t candidate_count = (a.n_layers == 1 || li == last_layer) ? ef : a.upper;  // search.rs:122-126
@@ -1285,6 +1365,9 @@ ph_search_fn ph_pick_ranged_dense(int capc);
 // the label-range twins: search_label_ranged.hip
 ph_search_fn ph_pick_label_ranged_kernel(int family, int capc, int nv, int pqr_m, bool pq_global);
 ph_search_fn ph_pick_label_ranged_dense(int capc);
+// the radius twins (PH_FM_RADIUS, no filter): search_radius.hip.  Row stores and the 1024-slot queues only; nullptr for
+// every other family or shape
+ph_search_fn ph_pick_radius_kernel(int family, int nv);
 // the collecting twins (PH_FM_COLLECT over the bitmap and over the label column): search_collect.hip and
 // search_collect_labeled.hip.  No dense-only twin: a collecting kernel runs the last layer of a descent, and the
 // dense-only launch of a split descent never holds it (api.hip)

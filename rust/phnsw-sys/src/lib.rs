@@ -272,6 +272,28 @@ extern "C" {
                                             filter_dev: *const u32, k: u64, out_ids_dev: *mut u32,
                                             out_d_dev: *mut c_float, out_len_dev: *mut u32, status_dev: *mut u32,
                                             stream: *mut c_void) -> c_int;
+    // exact radius search over the same tables: every candidate with d < radius[q], CSR, sizes negotiated as snprintf
+    pub fn phnsw_search_exact_radius(ix: *const phnsw_index, queries: *const c_float, qids: *const u64, nq: u64,
+                                     exclude: *const u64, filter: *const u32, radius: *const c_float, cap: u64,
+                                     out_first: *mut u64, out_ids: *mut u64, out_d: *mut c_float,
+                                     out_total: *mut u64) -> c_int;
+    pub fn phnsw_search_exact_radius_device(ix: *const phnsw_index, queries_dev: *const c_float, ldq: u32,
+                                            qids_dev: *const u32, nq: u64, exclude_dev: *const u32,
+                                            filter_dev: *const u32, radius_dev: *const c_float, cap: u64,
+                                            out_first_dev: *mut u64, out_ids_dev: *mut u32, out_d_dev: *mut c_float,
+                                            status_dev: *mut u32, out_total_dev: *mut u64,
+                                            stream: *mut c_void) -> c_int;
+    // radius search by graph walk: threshold_nn's doubling-queue loop after a plain descent, a radius per query
+    pub fn phnsw_search_batch_radius(ix: *const phnsw_index, queries: *const c_float, qids: *const u64, nq: u64,
+                                     sp: *const phnsw_search_params, exclude: *const u64, radius: *const c_float,
+                                     max_out: u64, out_ids: *mut u64, out_d: *mut c_float, out_len: *mut u64,
+                                     out_stats: *mut u64, out_status: *mut u32) -> c_int;
+    pub fn phnsw_search_batch_radius_device(ix: *const phnsw_index, queries_dev: *const c_float, ldq: u32,
+                                            qids_dev: *const u32, nq: u64, sp: *const phnsw_search_params,
+                                            exclude_dev: *const u32, radius_dev: *const c_float, max_out: u64,
+                                            out_ids_dev: *mut u32, out_d_dev: *mut c_float, out_len_dev: *mut u32,
+                                            out_stats_dev: *mut u32, status_dev: *mut u32,
+                                            stream: *mut c_void) -> c_int;
     // ... and for a table of bitmaps with a selector per query (PHNSW_FILTER_ALL: no bitmap), grouped on the device
     pub fn phnsw_search_exact_grouped(ix: *const phnsw_index, queries: *const c_float, qids: *const u64, nq: u64,
                                       exclude: *const u64, filters: *const u32, filter_stride_words: u32, nfilters: u64,
