@@ -356,8 +356,8 @@ int phnsw_search_exact_shared_device(const phnsw_index *ix, const float *queries
  * of queries / qids, radius, out_first, out_total, the device form's status, out_ids / out_d unless cap == 0, nq
  * (PHNSW_E_INVALID); the host form then refuses a Stored query id at or past n as its siblings do (PHNSW_E_INVALID).
  * PHNSW_DENSE_TIMES=1 prints the steps' times of a call on stderr.
- * OUT OF SCOPE, so that nobody assumes otherwise: per-query bitmaps, labels or ranges as the filter of a radius call; a
- * radius search by graph walk; routing between a walk and this call; re-ranked (f16 / i8 / PQ first, f32 after) radius
+ * OUT OF SCOPE, so that nobody assumes otherwise: per-query bitmaps as the filter of a radius call (a row label or a
+ * numeric range per query: phnsw_search_exact_radius_labeled / _ranged below); routing between a walk and this call; re-ranked (f16 / i8 / PQ first, f32 after) radius
  * calls -- a converted store is searched with its own distances, as by phnsw_search_exact_shared.
  * Guidance (measured on 1M x 768 f32 rows, cosine, 10 000-query batches, no filter, one radius for the batch, the calls
  * alternating in one run; profiles/radius/README.md): with 9.6 / 97.6 / 991.7 rows inside the radius per query on
@@ -864,6 +864,77 @@ int phnsw_search_exact_ranged_device(const phnsw_index *ix, const phnsw_attr *at
                                      const uint32_t *qids_dev, uint64_t nq, const uint32_t *exclude_dev,
                                      const uint32_t *lo_dev, const uint32_t *hi_dev, uint64_t k, uint32_t *out_ids_dev,
                                      float *out_d_dev, uint32_t *out_len_dev, uint32_t *status_dev, void *stream);
+/* ---- exact RADIUS search by ROW LABEL and by NUMERIC RANGE: phnsw_search_exact_radius with a filter PER QUERY -- every
+ * row of this query's tenant, or newer than this query's cut-off, closer than this query's radius.  Arguments: those of
+ * phnsw_search_exact_radius[_device] with the handle and want [nq] (or lo / hi [nq]) in the bitmap's place, as in
+ * phnsw_search_exact_labeled / phnsw_search_exact_ranged.
+ * Candidates of q: the listed vectors of label want[q], or the listed vectors with lo[q] <= key <= hi[q], except
+ * exclude[q].  want[q] == PHNSW_LABEL_NONE, a label nobody carries and lo > hi give an empty segment with status 0, not
+ * an error.
+ * Inside the radius: d(q, v) < radius[q] as an f32 comparison, strict.  A NaN, zero or negative radius matches nothing,
+ * and the rows of such a query are not read at all; a candidate at +inf or NaN is never inside a radius.
+ * Result and size negotiation: exactly those of phnsw_search_exact_radius -- out_first [nq + 1] and *out_total always
+ * complete and exact, segments ascending by (distance, id), phnsw_distance_batch's bits (a -0.0 comes back as +0.0),
+ * out_ids / out_d written only if the total is at most cap, cap == 0 with NULL arrays the count-only form,
+ * cap <= 2^31 - 1 and nq <= 2^31 - 2.
+ * EQUALITY: for every query the segment equals, in ids, distance bits and count, the segment phnsw_search_exact_radius
+ * returns for that query with the bitmap {v : labels[v] == want[q]} (or {v : v listed, lo[q] <= keys[v] <= hi[q]}), on
+ * the stores that call accepts; its leading min(1024, count) entries equal the row of phnsw_search_exact_labeled /
+ * phnsw_search_exact_ranged at k = 1024, cut at d < radius[q].  The result depends neither on the batch's order nor on
+ * the slice count: the pool's order depends on scheduling, the sorted order does not (the keys of one query are distinct).
+ * Stores: every kind the list scans accept -- f32, f16, i8, i8q and per-sub-space PQ, rows of at most 1536 floats --, one
+ * kind more than phnsw_search_exact_radius: the distances are dist.batch's, not a table's.
+ * Checks, in this order: a null index or one without layers; cap above 2^31 - 1 (PHNSW_E_INVALID); a null or stale
+ * handle, refused as by phnsw_search_exact_labeled / _ranged (PHNSW_E_INVALID); the store as those calls check it at
+ * k = 1 (a shared-codebook PQ store and longer rows: PHNSW_E_UNSUPPORTED); nq == 0: the host form writes the empty result,
+ * the device form enqueues nothing; the pointers and nq (PHNSW_E_INVALID); the host form's Stored ids at or past n.
+ * How: a lookup kernel writes the list (start, length) of every query; the batch is sorted by list start; ONE scan
+ * kernel, one wave64 per (query, slice of its list) in slice-major order, takes 64 ids at a time into dist.batch, tests
+ * ok && id != exclude && d < radius, stages the hits as (key, query) records in a per-wave LDS buffer and flushes it with
+ * one 64-bit atomic add on the pool's cursor per flush -- every row is read once; records at or past the pool's capacity
+ * are dropped but counted.  The tail (exclusive sum, the total's read-back, two stable radix passes, the unpack) is
+ * phnsw_search_exact_radius's own code.  The pool holds min(cap, nq x the longest list of the handle) records and lives,
+ * with the rest of a call's scratch, in the handle's scratch sets until phnsw_labels_destroy / phnsw_attr_destroy.
+ * Knobs (environment, read per call, change no result): PHNSW_LABEL_SLICES / PHNSW_RANGE_SLICES force the slice count;
+ * PHNSW_DENSE_TIMES=1 prints the times of scan and scan + sort on stderr.
+ * NOT BUILT: a form for phnsw_label_attr, sets of labels, a tile path (queries of one label sharing a row read), a walk,
+ * routing.
+ * Guidance (measured on 1M x 768 f32 rows, cosine, 10 000-query batches, one radius for the batch, the calls alternating
+ * in one run; scripts/list_radius_profile.py, profiles/radius_list/README.md): the call costs what the per-query top-k
+ * scan over the same lists costs at k = 10 (phnsw_search_exact_labeled under PHNSW_LABEL_TILE=1,
+ * phnsw_search_exact_ranged), which reads the same rows, plus the sort and unpack.  By label, lists of 100 000 / 10 000 /
+ * 1000 rows: 320.1 / 31.4 / 4.07 ms with about 10 rows inside the radius per query, 319.5 / 31.6 / 4.36 ms with about 100
+ * and 318.4 / 32.5 / 5.09 ms with about 1000, against 318.4 / 31.4 / 3.90, 319.9 / 31.8 / 3.95 and 317.2 / 31.6 / 3.93 ms of
+ * the top-k scan; the scan kernel alone takes the top-k scan's time, the sort and unpack 0.2 / 0.4 / 1.2 ms at totals of
+ * 10^5 / 10^6 / 10^7 records.  By range, windows of the same lengths: 390.8 / 42.0 / 4.41, 390.5 / 42.3 / 4.67 and 391.2 /
+ * 43.1 / 5.44 ms (the top-k scan by range: 389.3 / 41.8 / 4.28 at 10 rows inside).  Counting only saves the sort and the
+ * unpack: 3.90 against 5.09 ms at lists of 1000 rows all inside the radius.  Against phnsw_search_exact_radius called once
+ * per distinct label with its bitmap (warmed, the same rounds) this call LOSES at few long lists -- 8 labels of 100 000
+ * rows: 318 to 320 against 29 to 34 ms, eight matrix-core tables against 10 000 waves reading 100 000 rows each --, is level
+ * at 64 labels of 10 000 rows (31.4 to 32.5 against 24.9 to 31.0 ms) and wins at 1000 labels of 1000 rows (4.1 to 5.1
+ * against 180 to 217 ms, about 40 to 1): with a handful of tenants keep calling the table call per tenant.  f16, i8, i8q
+ * and PQ stores, L2 and ragged dimensions, per-query radii, batches
+ * small enough for slices, exclude, the host forms and a cap below the total: not measured. */
+int phnsw_search_exact_radius_labeled(const phnsw_index *ix, const phnsw_labels *lb, const float *queries, const uint64_t *qids,
+                                      uint64_t nq, const uint64_t *exclude, const uint32_t *want, const float *radius,
+                                      uint64_t cap, uint64_t *out_first, uint64_t *out_ids, float *out_d, uint64_t *out_total);
+/* device forms: device pointers as for phnsw_search_exact_radius_device; status_dev[q] = 4 for a Stored query id at or
+ * past n (an empty segment, the others unaffected).  The call synchronises `stream` ONCE, to read the total, when
+ * cap > 0; with cap == 0 it never synchronises.  No candidate count is read back. */
+int phnsw_search_exact_radius_labeled_device(const phnsw_index *ix, const phnsw_labels *lb, const float *queries_dev, uint32_t ldq,
+                                             const uint32_t *qids_dev, uint64_t nq, const uint32_t *exclude_dev,
+                                             const uint32_t *want_dev, const float *radius_dev, uint64_t cap,
+                                             uint64_t *out_first_dev, uint32_t *out_ids_dev, float *out_d_dev,
+                                             uint32_t *status_dev, uint64_t *out_total_dev, void *stream);
+int phnsw_search_exact_radius_ranged(const phnsw_index *ix, const phnsw_attr *at, const float *queries, const uint64_t *qids,
+                                     uint64_t nq, const uint64_t *exclude, const uint32_t *lo, const uint32_t *hi,
+                                     const float *radius, uint64_t cap, uint64_t *out_first, uint64_t *out_ids, float *out_d,
+                                     uint64_t *out_total);
+int phnsw_search_exact_radius_ranged_device(const phnsw_index *ix, const phnsw_attr *at, const float *queries_dev, uint32_t ldq,
+                                            const uint32_t *qids_dev, uint64_t nq, const uint32_t *exclude_dev,
+                                            const uint32_t *lo_dev, const uint32_t *hi_dev, const float *radius_dev, uint64_t cap,
+                                            uint64_t *out_first_dev, uint32_t *out_ids_dev, float *out_d_dev,
+                                            uint32_t *status_dev, uint64_t *out_total_dev, void *stream);
 /* the graph walk by range: phnsw_search_batch_labeled with (at, lo, hi) in place of (lb, want) -- the search kernels'
  * range mode over attr_of, one 4-byte load and two compares per tested id.
  * ROW EQUALITY: rows, lengths, stats and statuses are those of phnsw_search_batch_filtered[_device] called with the

@@ -637,6 +637,29 @@ class Hnsw {
                                          uint64_t nq, const uint32_t *exclude_dev, const uint32_t *lo_dev, const uint32_t *hi_dev,
                                          uint64_t k, uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
                                          uint32_t *status_dev, void *stream) const;
+  // search_many_exact_radius with a filter PER QUERY (phnsw_search_exact_radius_labeled / _ranged): for query i the
+  // vectors `labels` lists under want[i] -- or `attr` lists with lo[i] <= key <= hi[i] -- with d < radius[i], ascending by
+  // (distance, id); the segments of search_many_exact_radius over the equivalent bitmap, bit for bit.  Two library calls
+  // at the most, as there
+  inline std::vector<SearchResult> search_many_exact_radius_labeled(const std::vector<const float *> &queries,
+                                                                    const std::vector<float> &radius, const Labels &labels,
+                                                                    const std::vector<uint32_t> &want) const;
+  inline std::vector<SearchResult> search_many_exact_radius_ranged(const std::vector<const float *> &queries,
+                                                                   const std::vector<float> &radius, const Attribute &attr,
+                                                                   const std::vector<uint32_t> &lo,
+                                                                   const std::vector<uint32_t> &hi) const;
+  // zero-copy forms (phnsw_search_exact_radius_labeled_device / _ranged_device): as search_exact_radius_device;
+  // synchronise `stream` once when cap > 0, never with cap == 0
+  inline void search_exact_radius_labeled_device(const Labels &labels, const float *queries_dev, uint32_t ldq,
+                                                 const uint32_t *qids_dev, uint64_t nq, const uint32_t *exclude_dev,
+                                                 const uint32_t *want_dev, const float *radius_dev, uint64_t cap,
+                                                 uint64_t *out_first_dev, uint32_t *out_ids_dev, float *out_d_dev,
+                                                 uint32_t *status_dev, uint64_t *out_total_dev, void *stream) const;
+  inline void search_exact_radius_ranged_device(const Attribute &attr, const float *queries_dev, uint32_t ldq,
+                                                const uint32_t *qids_dev, uint64_t nq, const uint32_t *exclude_dev,
+                                                const uint32_t *lo_dev, const uint32_t *hi_dev, const float *radius_dev,
+                                                uint64_t cap, uint64_t *out_first_dev, uint32_t *out_ids_dev, float *out_d_dev,
+                                                uint32_t *status_dev, uint64_t *out_total_dev, void *stream) const;
   // search_many_filtered by a numeric range (phnsw_search_batch_ranged): the graph walk restricted to the range; k 0 =
   // all number_of_candidates entries of a row
   inline std::vector<SearchResult> search_many_ranged(const std::vector<const float *> &queries, const SearchParameters &sp,
@@ -1226,6 +1249,71 @@ inline void Hnsw::search_exact_ranged_device(const Attribute &attr, const float 
                                              float *out_d_dev, uint32_t *out_len_dev, uint32_t *status_dev, void *stream) const {
   check(phnsw_search_exact_ranged_device(ix_, attr.handle(), queries_dev, ldq, qids_dev, nq, exclude_dev, lo_dev, hi_dev, k,
                                          out_ids_dev, out_d_dev, out_len_dev, status_dev, stream));
+}
+namespace detail {
+// the two calls of a radius search by list: room for 64 results per query, then exactly the total;
+// run(queries [nq][dim], room, first, ids, d, &total)
+template <class Run>
+std::vector<SearchResult> radius_segments(const std::vector<const float *> &queries, uint64_t dim, const std::vector<float> &radius,
+                                          const char *who, Run run) {
+  const uint64_t nq = queries.size();
+  if (radius.size() != nq) throw Error(PHNSW_E_INVALID, std::string(who) + ": one radius per query");
+  std::vector<float> q(nq * dim);
+  for (uint64_t i = 0; i < nq; i++) std::copy(queries[i], queries[i] + dim, q.begin() + i * dim);
+  std::vector<uint64_t> first(nq + 1), ids(std::max<uint64_t>(nq * 64, 1));
+  std::vector<float> d(ids.size());
+  uint64_t total = 0;
+  for (int round = 0; round < 2; round++) {
+    run(q.data(), (uint64_t)ids.size(), first.data(), ids.data(), d.data(), &total);
+    if (total <= ids.size()) break;
+    ids.resize(total), d.resize(total);
+  }
+  std::vector<SearchResult> out(nq);
+  for (uint64_t i = 0; i < nq; i++)
+    for (uint64_t j = first[i]; j < first[i + 1]; j++) out[i].push_back({ids[j], d[j]});
+  return out;
+}
+}  // namespace detail
+inline std::vector<SearchResult> Hnsw::search_many_exact_radius_labeled(const std::vector<const float *> &queries,
+                                                                        const std::vector<float> &radius, const Labels &labels,
+                                                                        const std::vector<uint32_t> &want) const {
+  const uint64_t nq = queries.size();
+  if (want.size() != nq) throw Error(PHNSW_E_INVALID, "search_many_exact_radius_labeled: one wanted label per query");
+  return detail::radius_segments(queries, c_->dim(), radius, "search_many_exact_radius_labeled",
+                                 [&](const float *q, uint64_t room, uint64_t *first, uint64_t *ids, float *d, uint64_t *total) {
+                                   check(phnsw_search_exact_radius_labeled(ix_, labels.handle(), q, nullptr, nq, nullptr, want.data(),
+                                                                           radius.data(), room, first, ids, d, total));
+                                 });
+}
+inline std::vector<SearchResult> Hnsw::search_many_exact_radius_ranged(const std::vector<const float *> &queries,
+                                                                       const std::vector<float> &radius, const Attribute &attr,
+                                                                       const std::vector<uint32_t> &lo,
+                                                                       const std::vector<uint32_t> &hi) const {
+  const uint64_t nq = queries.size();
+  if (lo.size() != nq || hi.size() != nq) throw Error(PHNSW_E_INVALID, "search_many_exact_radius_ranged: one lo and one hi per query");
+  return detail::radius_segments(queries, c_->dim(), radius, "search_many_exact_radius_ranged",
+                                 [&](const float *q, uint64_t room, uint64_t *first, uint64_t *ids, float *d, uint64_t *total) {
+                                   check(phnsw_search_exact_radius_ranged(ix_, attr.handle(), q, nullptr, nq, nullptr, lo.data(),
+                                                                          hi.data(), radius.data(), room, first, ids, d, total));
+                                 });
+}
+inline void Hnsw::search_exact_radius_labeled_device(const Labels &labels, const float *queries_dev, uint32_t ldq,
+                                                     const uint32_t *qids_dev, uint64_t nq, const uint32_t *exclude_dev,
+                                                     const uint32_t *want_dev, const float *radius_dev, uint64_t cap,
+                                                     uint64_t *out_first_dev, uint32_t *out_ids_dev, float *out_d_dev,
+                                                     uint32_t *status_dev, uint64_t *out_total_dev, void *stream) const {
+  check(phnsw_search_exact_radius_labeled_device(ix_, labels.handle(), queries_dev, ldq, qids_dev, nq, exclude_dev, want_dev,
+                                                 radius_dev, cap, out_first_dev, out_ids_dev, out_d_dev, status_dev, out_total_dev,
+                                                 stream));
+}
+inline void Hnsw::search_exact_radius_ranged_device(const Attribute &attr, const float *queries_dev, uint32_t ldq,
+                                                    const uint32_t *qids_dev, uint64_t nq, const uint32_t *exclude_dev,
+                                                    const uint32_t *lo_dev, const uint32_t *hi_dev, const float *radius_dev,
+                                                    uint64_t cap, uint64_t *out_first_dev, uint32_t *out_ids_dev, float *out_d_dev,
+                                                    uint32_t *status_dev, uint64_t *out_total_dev, void *stream) const {
+  check(phnsw_search_exact_radius_ranged_device(ix_, attr.handle(), queries_dev, ldq, qids_dev, nq, exclude_dev, lo_dev, hi_dev,
+                                                radius_dev, cap, out_first_dev, out_ids_dev, out_d_dev, status_dev, out_total_dev,
+                                                stream));
 }
 inline std::vector<SearchResult> Hnsw::search_many_ranged(const std::vector<const float *> &queries, const SearchParameters &sp,
                                                           uint64_t k, const Attribute &attr, const std::vector<uint32_t> &lo,

@@ -170,6 +170,12 @@ SYMBOLS = {
     "phnsw_attr_destroy": (None, [_vp]),
     "phnsw_search_exact_ranged": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp]),
     "phnsw_search_exact_ranged_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "phnsw_search_exact_radius_labeled": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "phnsw_search_exact_radius_labeled_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp,
+                                                        _vp, _vp]),
+    "phnsw_search_exact_radius_ranged": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "phnsw_search_exact_radius_ranged_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp,
+                                                       _vp, _vp, _vp]),
     "phnsw_search_batch_ranged": (_i32, [_vp, _vp, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _u32, _u64, _vp, _vp, _vp, _vp]),
     "phnsw_search_batch_ranged_device": (_i32, [_vp, _vp, _vp, _u32, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _u32, _vp, _vp, _vp,
                                                 _vp, _vp, _vp]),

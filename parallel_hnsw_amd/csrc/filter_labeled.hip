@@ -534,6 +534,14 @@ int ph_labeled_check(const phnsw_index *ix, const phnsw_labels *lb, uint64_t k, 
 
 const uint32_t *ph_labels_column(const phnsw_labels *lb) { return lb->label_of; }
 
+PhListView ph_labels_view(const phnsw_labels *lb) {
+  phnsw_labels *m = const_cast<phnsw_labels *>(lb);
+  PhListView v = {};
+  v.dev.values = lb->values, v.dev.first = lb->first, v.dev.nlabels = (uint32_t)lb->nlabels, v.dev.listed = (uint32_t)lb->listed;
+  v.dev.ids = lb->ids, v.longest = lb->longest, v.pool = &m->pool, v.resident = &m->resident;
+  return v;
+}
+
 namespace {
 
 // What both runs fill alike of the argument block: the store, the request, the posting lists and the grouping arrays of

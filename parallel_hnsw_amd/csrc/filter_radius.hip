@@ -13,7 +13,7 @@
 //                                the 64-bit cursor and adds them to count[q]; pass 2 writes (mkkey(d, id), q) records
 //                                by a ballot prefix per 64 entries.  Records at or past the pool's capacity are
 //                                dropped, but counted (radius_plan.h)
-//   4. the exclusive sum of count [nq + 1] into out_first; the cursor is the total
+//   4. (from here on: radius_tail.h) the exclusive sum of count [nq + 1] into out_first; the cursor is the total
 //      -- the host reads the total (the second synchronisation; the device form's count-only call skips it)
 //   5. total <= cap: two stable radix passes, by key and then by query, and ph_radius_unpack_kernel
 //
@@ -32,6 +32,7 @@
 #include "host_call.h"
 #include "phnsw_device.h"
 #include "radius_plan.h"
+#include "radius_tail.h"
 
 struct PhRadiusArgs {
   const float *D;            // [npos][stride]: the table of this (node chunk, position chunk)
@@ -48,14 +49,7 @@ struct PhRadiusArgs {
   uint64_t records;          // 0: count only
 };
 
-__global__ __launch_bounds__(256) void ph_radius_init_kernel(uint32_t *count, unsigned long long *cursor, const uint32_t *refuse,
-                                                             uint32_t *status, uint64_t nq) {
-  for (uint64_t q = (uint64_t)blockIdx.x * 256u + threadIdx.x; q <= nq; q += (uint64_t)gridDim.x * 256u) {
-    count[q] = 0u;
-    if (q < nq) status[q] = refuse ? refuse[q] : ST_OK;
-    if (q == 0) cursor[0] = 0ull;
-  }
-}
+// (ph_radius_init_kernel: radius_tail.h, shared with filter_list_radius.hip)
 
 // One wave64 per position.  Everything that decides a branch (the query, its radius, the row's count) is uniform over
 // the wave; count[q] is touched by this wave alone within a launch, and launches follow each other on one stream.
@@ -94,16 +88,7 @@ __global__ __launch_bounds__(64) void ph_radius_compact_kernel(PhRadiusArgs a) {
   }
 }
 
-// sorted record i is entry i of the CSR arrays: the records are in (query, key) order and out_first is the exclusive
-// sum of the queries' counts
-template <class Id>
-__global__ __launch_bounds__(256) void ph_radius_unpack_kernel(const uint64_t *keys, uint64_t total, Id *out_ids, float *out_d) {
-  for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < total; i += (uint64_t)gridDim.x * 256u) {
-    const uint64_t key = keys[i];
-    out_ids[i] = (Id)((uint32_t)key & IDM);
-    out_d[i] = unfkey((uint32_t)(key >> 32));
-  }
-}
+// (ph_radius_unpack_kernel, the tail from the exclusive sum on: radius_tail.h)
 
 // ------------------------------------------------------------------ a call's scratch
 
@@ -136,11 +121,6 @@ struct PhRadiusCall {
 };
 
 namespace {
-
-struct WidenCount {
-  __host__ __device__ uint64_t operator()(uint32_t v) const { return (uint64_t)v; }
-};
-typedef hipcub::TransformInputIterator<uint64_t, WidenCount, const uint32_t *> CountIter;
 
 // Steps 1 to 5 without the unpack: *total is exact (and 0 when it was not read back: the device form's count-only
 // call); *sorted is the (query, key) ordered records when ph_radius_emits(*total, cap), else nullptr
@@ -215,45 +195,18 @@ int radius_run(const phnsw_index *ix, const PhRadiusCall &c, PhRadiusSet &set, u
   }
 
   times.begin(4);
-  const int n1 = (int)(nq + 1u);  // nq <= 2^31 - 2 (checked by the entry points)
-  size_t scan_bytes = 0, sort1_bytes = 0, sort2_bytes = 0;
-  const CountIter counts(a.count, WidenCount());
-  PH_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, counts, c.out_first, n1, c.stream));
-  const int qbits = ph_radius_query_bits(nq);
-  if (records) {
-    PH_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort1_bytes, a.keys, keys_b, a.qs, qs_b, (int)records, 0, 64, c.stream));
-    PH_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, sort2_bytes, qs_b, a.qs, keys_b, a.keys, (int)records, 0, qbits, c.stream));
-  }
-  PH_TRY(set.block_ensure(&set.tmp, &set.tmp_bytes, std::max<size_t>(std::max(scan_bytes, std::max(sort1_bytes, sort2_bytes)), 16u),
-                          c.stream));
-  size_t bytes = scan_bytes;
-  PH_HIP(hipcub::DeviceScan::ExclusiveSum(set.tmp, bytes, counts, c.out_first, n1, c.stream));
-  if (c.out_total) PH_HIP(hipMemcpyAsync(c.out_total, a.cursor, 8, hipMemcpyDeviceToDevice, c.stream));
-  if (records || c.total_to_host) {
-    PH_HIP(hipMemcpyAsync(set.h_head + 2, a.cursor, 8, hipMemcpyDeviceToHost, c.stream));
-    PH_HIP(hipStreamSynchronize(c.stream));  // the second synchronisation: whether and how much to sort
-    *total = ((const uint64_t *)set.h_head)[1];
-  }
-  if (records && ph_radius_emits(*total, c.cap)) {  // total <= records: nothing was dropped
-    bytes = sort1_bytes;
-    PH_HIP(hipcub::DeviceRadixSort::SortPairs(set.tmp, bytes, a.keys, keys_b, a.qs, qs_b, (int)*total, 0, 64, c.stream));
-    bytes = sort2_bytes;
-    PH_HIP(hipcub::DeviceRadixSort::SortPairs(set.tmp, bytes, qs_b, a.qs, keys_b, a.keys, (int)*total, 0, qbits, c.stream));
-    *sorted = a.keys;
-  }
+  PhRadiusTail t = {};
+  t.nq = nq, t.cap = c.cap, t.records = records, t.cursor = a.cursor, t.count = a.count;
+  t.keys_a = a.keys, t.keys_b = keys_b, t.qs_a = a.qs, t.qs_b = qs_b;
+  t.out_first = c.out_first, t.out_total = c.out_total, t.total_to_host = c.total_to_host;
+  t.h_total = (uint64_t *)set.h_head + 1, t.set = &set, t.tmp = &set.tmp, t.tmp_bytes = &set.tmp_bytes, t.stream = c.stream;
+  PH_TRY(ph_radius_tail(t, total, sorted));  // the second synchronisation: whether and how much to sort
   times.end();
   float ms[5];
   if (times.collect(ms, 5))
     fprintf(stderr, "[phnsw] exact_radius: %llu queries x %llu candidates, %llu in radius: count %.3f ms, list %.3f ms, pack+table %.3f ms, "
             "compact %.3f ms, scan+sort %.3f ms\n", (unsigned long long)nq, (unsigned long long)cand, (unsigned long long)*total, ms[0],
             ms[1], ms[2], ms[3], ms[4]);
-  return 0;
-}
-
-template <class Id>
-int radius_unpack(const uint64_t *sorted, uint64_t total, Id *out_ids, float *out_d, hipStream_t stream) {
-  hipLaunchKernelGGL(ph_radius_unpack_kernel<Id>, dim3(grid1(total)), dim3(256), 0, stream, sorted, total, out_ids, out_d);
-  PH_HIP(hipGetLastError());
   return 0;
 }
 
@@ -308,7 +261,7 @@ extern "C" int phnsw_search_exact_radius_device(const phnsw_index *ix, const flo
   uint64_t total;
   const uint64_t *sorted;
   PH_TRY(radius_run(ix, c, *set, &total, &sorted));
-  if (sorted) PH_TRY(radius_unpack(sorted, total, out_ids_dev, out_d_dev, c.stream));
+  if (sorted) PH_TRY(ph_radius_unpack(sorted, total, out_ids_dev, out_d_dev, c.stream));
   return 0;
 } catch (...) { return ph_caught(); }
 
@@ -361,7 +314,7 @@ extern "C" int phnsw_search_exact_radius(const phnsw_index *ix, const float *que
     float *d = nullptr;
     PH_TRY(h.blocks.alloc(&ids, (size_t)total * 8u));
     PH_TRY(h.blocks.alloc(&d, (size_t)total * 4u));
-    PH_TRY(radius_unpack(sorted, total, ids, d, h.st));
+    PH_TRY(ph_radius_unpack(sorted, total, ids, d, h.st));
     PH_HIP(hipMemcpyAsync(out_ids, ids, (size_t)total * 8u, hipMemcpyDeviceToHost, h.st));
     PH_HIP(hipMemcpyAsync(out_d, d, (size_t)total * 4u, hipMemcpyDeviceToHost, h.st));
   }

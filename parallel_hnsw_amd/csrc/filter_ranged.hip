@@ -179,6 +179,14 @@ int ph_ranged_check(const phnsw_index *ix, const phnsw_attr *at, uint64_t k, con
 
 const uint32_t *ph_attr_column(const phnsw_attr *at) { return at->attr_of; }
 
+PhListView ph_attr_view(const phnsw_attr *at) {
+  phnsw_attr *m = const_cast<phnsw_attr *>(at);
+  PhListView v = {};
+  v.dev.skeys = at->skeys, v.dev.listed = (uint32_t)at->listed;
+  v.dev.ids = at->ids, v.longest = at->listed, v.pool = &m->pool, v.resident = &m->resident;
+  return v;
+}
+
 namespace {
 
 // the orchestration on a set the caller holds; c is checked, 0 < nq <= PH_LABEL_NQ_MAX (with a list: its length).

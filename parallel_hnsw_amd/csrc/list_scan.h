@@ -56,6 +56,11 @@ struct PhLabeledSet : PhCallSet {
   size_t pre_bytes = 0, tmp_bytes = 0, keys_bytes = 0;
   uint64_t tmp_nq = 0;  // the batch size tmp_need was asked of hipCUB for (0: none yet)
   size_t tmp_need = 0;
+  // the exact radius search over lists (filter_list_radius.hip): the record pool in radius_plan.h's layout, and the
+  // pinned word the total is read back into
+  void *post = nullptr;
+  size_t post_bytes = 0;
+  uint64_t *h_total = nullptr;
 };
 
 const size_t PH_LABEL_SETS = 4;  // scratch sets a handle makes before calls share one behind its event
@@ -98,6 +103,8 @@ static inline void ph_handle_sets_free(PhCallPool &pool) {
     if (s.pre) ph_pool_free(s.pre);
     if (s.tmp) ph_pool_free(s.tmp);
     if (s.keys) ph_pool_free(s.keys);
+    if (s.post) ph_pool_free(s.post);
+    if (s.h_total) hipHostFree(s.h_total);
   });
 }
 

@@ -693,6 +693,26 @@ const uint32_t *ph_attr_column(const phnsw_attr *at);
 // out_count_dev[q] = the length of the span of [lo_dev[q], hi_dev[q]] (phnsw_attr_count_device without its checks)
 int ph_attr_count(const phnsw_attr *at, const uint32_t *lo_dev, const uint32_t *hi_dev, uint64_t nq, uint32_t *out_count_dev,
                   hipStream_t stream);
+// What the exact radius search over lists (filter_list_radius.hip) reads of a handle -- a read-only view of its device
+// arrays (PhListArrays: what the kernels get), and what the launcher needs beside them; the structs stay private to
+// filter_labeled.hip and filter_ranged.hip.  A label handle fills values / first (nlabels), an attribute handle skeys (its
+// `listed` entries); both fill ids, and `longest`, the longest list a query of the handle can have (the longest posting
+// list; every listed row).  A later handle kind is a view of its own plus a lookup kernel.
+struct PhListArrays {
+  const uint32_t *values, *first;  // [nlabels] ascending, [nlabels + 1]; nullptr: not a label handle
+  uint32_t nlabels;
+  const uint32_t *skeys;  // [listed] ascending; nullptr: not an attribute handle
+  uint32_t listed;
+  const uint32_t *ids;  // the lists' ids: a list is ids + at, len
+};
+struct PhListView {
+  PhListArrays dev;
+  uint64_t longest;
+  PhCallPool *pool;  // where the scratch sets live: PhLabeledSet (list_scan.h)
+  PhResidentMemo *resident;  // under pool->mutex
+};
+PhListView ph_labels_view(const phnsw_labels *lb);  // filter_labeled.hip
+PhListView ph_attr_view(const phnsw_attr *at);      // filter_ranged.hip
 // The request of one exact top-k scan over the spans of a column sorted by (label, key) (ph_label_ranged_device,
 // filter_label_ranged.hip): PhRangedCall with the wanted label beside the bounds; list as there
 struct PhLabelRangedCall {

@@ -391,6 +391,26 @@ extern "C" {
                                             lo_dev: *const u32, hi_dev: *const u32, k: u64, out_ids_dev: *mut u32,
                                             out_d_dev: *mut c_float, out_len_dev: *mut u32, status_dev: *mut u32,
                                             stream: *mut c_void) -> c_int;
+    pub fn phnsw_search_exact_radius_labeled(ix: *const phnsw_index, lb: *const phnsw_labels, queries: *const c_float,
+                                             qids: *const u64, nq: u64, exclude: *const u64, want: *const u32,
+                                             radius: *const c_float, cap: u64, out_first: *mut u64, out_ids: *mut u64,
+                                             out_d: *mut c_float, out_total: *mut u64) -> c_int;
+    pub fn phnsw_search_exact_radius_labeled_device(ix: *const phnsw_index, lb: *const phnsw_labels,
+                                                    queries_dev: *const c_float, ldq: u32, qids_dev: *const u32, nq: u64,
+                                                    exclude_dev: *const u32, want_dev: *const u32,
+                                                    radius_dev: *const c_float, cap: u64, out_first_dev: *mut u64,
+                                                    out_ids_dev: *mut u32, out_d_dev: *mut c_float, status_dev: *mut u32,
+                                                    out_total_dev: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn phnsw_search_exact_radius_ranged(ix: *const phnsw_index, at: *const phnsw_attr, queries: *const c_float,
+                                            qids: *const u64, nq: u64, exclude: *const u64, lo: *const u32, hi: *const u32,
+                                            radius: *const c_float, cap: u64, out_first: *mut u64, out_ids: *mut u64,
+                                            out_d: *mut c_float, out_total: *mut u64) -> c_int;
+    pub fn phnsw_search_exact_radius_ranged_device(ix: *const phnsw_index, at: *const phnsw_attr,
+                                                   queries_dev: *const c_float, ldq: u32, qids_dev: *const u32, nq: u64,
+                                                   exclude_dev: *const u32, lo_dev: *const u32, hi_dev: *const u32,
+                                                   radius_dev: *const c_float, cap: u64, out_first_dev: *mut u64,
+                                                   out_ids_dev: *mut u32, out_d_dev: *mut c_float, status_dev: *mut u32,
+                                                   out_total_dev: *mut u64, stream: *mut c_void) -> c_int;
     pub fn phnsw_search_batch_ranged(ix: *const phnsw_index, at: *const phnsw_attr, queries: *const c_float,
                                      qids: *const u64, nq: u64, sp: *const phnsw_search_params, upto_layers: u32,
                                      exclude: *const u64, lo: *const u32, hi: *const u32, flags: u32, k: u64,
