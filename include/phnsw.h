@@ -1577,6 +1577,43 @@ int phnsw_i8q_search_batch_device(const phnsw_index *ix, const phnsw_store *full
                                   uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
                                   uint32_t *out_stats_dev, uint32_t *status_dev, void *stream);
 
+/* ---- 1-bit sign row store: Hamming distances, f32 re-rank (rowstore.hip) ----
+ * The rows of the f32 store `full` reduced to one bit per component by a device kernel: bit j of a row is
+ * rows[i][j] < 0.0f (+0, -0 and every non-negative value give 0); components past dim (padding) are bit 0 in every row
+ * and in every query.  96 bytes per stored 768-component vector instead of 3 072.  n, dim, ld, metric and device are
+ * those of `full` (phnsw_store_info; rows_dev NULL); all three metrics are accepted.  A source that is not an f32 store,
+ * or a NaN or infinite component, is PHNSW_E_INVALID; a row longer than 1536 floats is PHNSW_E_UNSUPPORTED.
+ * phnsw_store_read returns a row as +1.0f (bit 0) / -1.0f (bit 1), [count][dim].
+ * A distance is taken from h = popcount(row XOR query) over the row's words:
+ *   dot-product metrics: r = (float)(dim - 2 h);   Euclidean: r = (float)(4 h);   then the metric's own last step.
+ * A raw query is reduced to its sign bits by the rows' rule (q[j] < 0), a Stored query is its row as it is.  That is
+ * exactly the f32 search over the rows phnsw_store_read returns with the query where(q < 0, -1, +1): every partial sum
+ * is an integer below 2^24, so the f32 arithmetic reaches it in any summation order (tests/bits_reference.py restates
+ * it in numpy).  The distances of the plain calls are therefore in SIGN-VECTOR UNITS (COSINE_HALF runs from 1/2 down
+ * to (1 - dim) / 2, ONE_MINUS_DOT from 1 + dim to 1 - dim, L2 from 0 to 2 sqrt(dim)); a distance takes at most dim + 1
+ * values, ties are the normal case and the id decides, as everywhere.  phnsw_bits_search_batch[_device] return TRUE
+ * f32 distances: they recompute every candidate on `full`.
+ * Served: phnsw_distance_batch, phnsw_index_from_layers (adopt a graph built over the f32 store), phnsw_search_batch,
+ * _stored, _topk, _device (no dense tables, no split descent: every layer per hop), phnsw_index_layer_*, the
+ * phnsw_last_search_* queries, the destroy calls and the re-ranked pair below.  EVERY other entry point -- every filtered,
+ * labelled, ranged, collecting and radius walk, every exact scan and table, phnsw_bruteforce_topk, build / link / improve
+ * / promote / extend, phnsw_store_append, serialisation, the PQ constructors, knn / threshold_nn / search_instrumented --
+ * returns PHNSW_E_UNSUPPORTED on the host, before any launch, with a message that names the call and "bits". */
+int phnsw_store_create_bits(const phnsw_store *full, phnsw_store **out);
+/* the sign bits [n][ceil(dim / 32)] of a bits store: component j is bit j & 31 of word j >> 5 (the public layout,
+ * whatever the stride of the rows on the device) */
+int phnsw_bits_read(const phnsw_store *s, uint32_t *words);
+/* phnsw_i8q_search_batch / _device over an index on a bits store: walk with `sp` (Hamming distances), recompute all
+ * number_of_candidates returned ids on `full` (true f32 distances, the bits of phnsw_distance_batch on it), sort by
+ * (distance, id), keep the best k <= number_of_candidates; same outputs */
+int phnsw_bits_search_batch(const phnsw_index *ix, const phnsw_store *full, const float *queries, uint64_t nq,
+                            const phnsw_search_params *sp, uint64_t k, uint64_t *out_ids, float *out_d,
+                            uint64_t *out_len);
+int phnsw_bits_search_batch_device(const phnsw_index *ix, const phnsw_store *full, const float *queries_dev,
+                                   uint32_t ldq, uint64_t nq, const phnsw_search_params *sp, uint64_t k,
+                                   uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                   uint32_t *out_stats_dev, uint32_t *status_dev, void *stream);
+
 /* ---- on-disk interchange with the Rust crate: serialize_hnsw / deserialize_hnsw
  * (src/serialize.rs:33-209): <dir>/meta (JSON HNSWMeta), <dir>/comparator/ (this library's
  * store; a crate user substitutes their own Serializable comparator), layer.meta.N (JSON),

@@ -123,6 +123,18 @@ class Comparator {
     check(phnsw_store_create_i8q(s_, &h));
     return h;  // wrap it: Comparator q8q(full.make_i8q());
   }
+  // the same vectors as one sign bit per component (phnsw_store_create_bits): Hamming distances in sign-vector units,
+  // plain searches only; re-rank with Hnsw::search_many_reranked_bits(*this, ...) for true f32 distances
+  phnsw_store *make_bits() const {
+    phnsw_store *h = nullptr;
+    check(phnsw_store_create_bits(s_, &h));
+    return h;  // wrap it: Comparator qb(full.make_bits());
+  }
+  // the sign bits [n][ceil(dim / 32)] of a comparator made by make_bits (phnsw_bits_read)
+  void read_bits(std::vector<uint32_t> &words) const {
+    words.resize(n_ * ((dim_ + 31u) / 32u));
+    check(phnsw_bits_read(s_, words.data()));
+  }
   // codes [n][dim] and scales [n] of a comparator made by make_i8 or make_i8q (phnsw_i8_read)
   void read_i8(std::vector<int8_t> &codes, std::vector<float> &scales) const {
     codes.resize(n_ * dim_);
@@ -267,6 +279,25 @@ class Hnsw {
                                   uint32_t *out_len_dev, uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) const {
     check(phnsw_i8q_search_batch_device(ix_, full.handle(), queries_dev, ldq, nq, &sp, k, out_ids_dev, out_d_dev, out_len_dev,
                                         out_stats_dev, status_dev, stream));
+  }
+  // the same two over a bits comparator (phnsw_bits_search_batch / _device): the walk runs on Hamming distances, the
+  // returned distances are true f32 distances on `full`
+  std::vector<SearchResult> search_many_reranked_bits(const Comparator &full, const std::vector<float> &queries,
+                                                      const SearchParameters &sp, uint64_t k) const {
+    const uint64_t nq = queries.size() / c_->dim();
+    std::vector<uint64_t> ids(nq * k), len(nq);
+    std::vector<float> d(nq * k);
+    check(phnsw_bits_search_batch(ix_, full.handle(), queries.data(), nq, &sp, k, ids.data(), d.data(), len.data()));
+    std::vector<SearchResult> out(nq);
+    for (uint64_t i = 0; i < nq; i++)
+      for (uint64_t j = 0; j < len[i]; j++) out[i].push_back({ids[i * k + j], d[i * k + j]});
+    return out;
+  }
+  void search_reranked_bits_device(const Comparator &full, const float *queries_dev, uint32_t ldq, uint64_t nq,
+                                   const SearchParameters &sp, uint64_t k, uint32_t *out_ids_dev, float *out_d_dev,
+                                   uint32_t *out_len_dev, uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) const {
+    check(phnsw_bits_search_batch_device(ix_, full.handle(), queries_dev, ldq, nq, &sp, k, out_ids_dev, out_d_dev, out_len_dev,
+                                         out_stats_dev, status_dev, stream));
   }
   // the batched form every GPU caller should use
   std::vector<SearchResult> search_many(const std::vector<AbstractVector> &vs, const SearchParameters &sp,

@@ -287,6 +287,11 @@ SYMBOLS = {
     "phnsw_i8_search_batch": (_i32, [_vp, _vp, _vp, _u64, C.POINTER(SearchParams), _u64, _vp, _vp, _vp]),
     "phnsw_i8_search_batch_device": (_i32, [_vp, _vp, _vp, _u32, _u64, C.POINTER(SearchParams), _u64, _vp, _vp, _vp,
                                             _vp, _vp, _vp]),
+    "phnsw_store_create_bits": (_i32, [_vp, _pp]),
+    "phnsw_bits_read": (_i32, [_vp, _vp]),
+    "phnsw_bits_search_batch": (_i32, [_vp, _vp, _vp, _u64, C.POINTER(SearchParams), _u64, _vp, _vp, _vp]),
+    "phnsw_bits_search_batch_device": (_i32, [_vp, _vp, _vp, _u32, _u64, C.POINTER(SearchParams), _u64, _vp, _vp, _vp,
+                                              _vp, _vp, _vp]),
     "phnsw_store_create_i8q": (_i32, [_vp, _pp]),
     "phnsw_i8q_search_batch": (_i32, [_vp, _vp, _vp, _u64, C.POINTER(SearchParams), _u64, _vp, _vp, _vp]),
     "phnsw_i8q_search_batch_device": (_i32, [_vp, _vp, _vp, _u32, _u64, C.POINTER(SearchParams), _u64, _vp, _vp, _vp,

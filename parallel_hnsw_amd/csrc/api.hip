@@ -300,7 +300,7 @@ extern "C" int phnsw_store_info(const phnsw_store *s, uint64_t *n, uint32_t *dim
 } catch (...) { return ph_caught(); }
 
 extern "C" int phnsw_store_read(const phnsw_store *s, uint64_t first, uint64_t count, float *out) try {
-  if (s && out && ph_store_converted(s) && first + count <= s->n) {  // f16 / i8 store: the values the distance kernels see
+  if (s && out && (ph_store_converted(s) || ph_store_bits(s)) && first + count <= s->n) {  // f16 / i8 / bits store: the values the distance kernels see
     PH_HIP(hipSetDevice(s->device));
     if (!count) return 0;
     return ph_converted_store_read(s, first, count, out);
@@ -790,10 +790,15 @@ int ph_search_device(const phnsw_index *ix, const PhSearchCall &c) {
   const uint32_t knn_mode = c.knn_mode, out_stride = c.out_stride;
   uint32_t *const out_index = c.out_index;
   const hipStream_t stream = c.stream;
-  if (ph_store_converted(ix->store) && (knn_mode || out_index || c.hint || c.out_hit)) {
-    // an f16 / i8 store is searched, never built over: knn / threshold_nn / search_instrumented / the build's rounds
+  if ((ph_store_converted(ix->store) || ph_store_bits(ix->store)) && (knn_mode || out_index || c.hint || c.out_hit)) {
+    // an f16 / i8 / bits store is searched, never built over: knn / threshold_nn / search_instrumented / the build's rounds
     return ph_search_only_unsupported(ix->store, knn_mode ? "knn / threshold_nn" : (out_index ? "search_instrumented" : "build search"));
   }
+  // a bits store has the plain walk alone: no filter of any form, no collecting, no radius (their entry points have
+  // refused it by name; this is the one door every search launch comes through)
+  if (ph_store_bits(ix->store) && (c.filter.words || c.filter.label_of || c.filter.attr_of || c.filter.pair_of || c.filter.set_first ||
+                                   c.collect_k || c.radius))
+    return ph_bits_unsupported(ix->store, "filtered / labelled / ranged / collecting / radius search");
   PhSearchArgs a;
   fill_args(ix, c, a);
   if (ix->dbg_order && ix->dbg_order_n == nq) a.order = ix->dbg_order;
@@ -1031,6 +1036,8 @@ extern "C" int phnsw_search_batch_device(const phnsw_index *ix, const float *que
 // the argument checks the host and the device form share; *f = what the launch gets (nullptr words: no filter)
 int ph_filter_check(const phnsw_index *ix, const uint32_t *filter, uint32_t stride, uint32_t flags, const char *call,
                     PhFilter *f) {
+  if (ix)  // a bits store has the plain walk alone
+    if (int brc = ph_bits_unsupported(ix->store, call)) return brc;
   const uint64_t words = (ix->store->n + 31u) / 32u;
   if (flags & ~(uint32_t)PHNSW_FILTER_STRICT) {
     ph_set_error("%s: unknown flag bits 0x%x", call, flags);
@@ -1159,6 +1166,8 @@ extern "C" int phnsw_index_set_filter_device(phnsw_index *ix, const uint32_t *fi
 // ---- exact top-k over the allow-list (filter_exact.hip): the call for SELECTIVE filters
 
 int ph_exact_check(const phnsw_index *ix, uint64_t k, const char *call) {
+  if (ix)  // a bits store has the plain walk alone
+    if (int brc = ph_bits_unsupported(ix->store, call)) return brc;
   if (!ix || ix->layers.empty()) {
     ph_set_error("%s: null index or index without layers", call);
     return PHNSW_E_INVALID;

@@ -543,6 +543,7 @@ int ph_layer_anchor_pos(const phnsw_store *cs, PhLayerHost &L) {
 // the cells as the tests and the measuring scripts read them (made on first use, like everywhere): the store's anchors
 // [n_anchors][ld] and chain ranks [n_anchors] (either pointer may be NULL: the count alone), a layer's pos [n_nodes]
 extern "C" int phnsw_debug_store_cells(phnsw_store *s, float *anchors_out, uint32_t *rank_out, uint32_t *n_anchors_out) try {
+  if (int rc = ph_bits_unsupported(s, "phnsw_debug_store_cells")) return rc;  // the locality cells: no f32 view of a bit row
   if (!s || !n_anchors_out || !(ph_store_f32(s) || ph_store_converted(s)) || s->n < 16 || s->metric == PHNSW_METRIC_L2) {
     ph_set_error("phnsw_debug_store_cells: need an f32, f16 or i8 store with a dot-product metric");
     return PHNSW_E_INVALID;
@@ -560,6 +561,7 @@ extern "C" int phnsw_debug_layer_cells(phnsw_index *ix, uint32_t lft, uint32_t *
     ph_set_error("phnsw_debug_layer_cells: invalid argument");
     return PHNSW_E_INVALID;
   }
+  if (int rc = ph_bits_unsupported(ix->store, "phnsw_debug_layer_cells")) return rc;
   PH_HIP(hipSetDevice(ix->store->device));
   PhLayerHost &L = ix->layers[lft];
   if (int rc = ph_layer_anchor_pos(ix->store, L)) return rc;

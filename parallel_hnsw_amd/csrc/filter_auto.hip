@@ -351,6 +351,7 @@ int auto_run(const phnsw_index *ix, const PhAutoCall &c, PhAutoSet &set) {
 
 // the checks both entry points make before they look at a pointer: index, parameters, k, store kind
 int auto_check(const phnsw_index *ix, const phnsw_search_params *sp, uint64_t k, const char *call) {
+  if (ix) PH_TRY(ph_bits_unsupported(ix->store, call));  // a bits store has the plain walk alone
   PH_TRY(ph_check_sp(ix, sp));
   if (!ph_auto_k_valid(k, sp->number_of_candidates)) {
     ph_set_error("%s: k must be 1..number_of_candidates (got %llu, number_of_candidates %llu)", call, (unsigned long long)k,

@@ -320,6 +320,7 @@ int ph_table_run(const phnsw_index *ix, PhWorkspace &ws, const PhTableRun &r) {
 
 // the checks every entry point makes (filter_grouped.hip's too) before it looks at another argument: index, k, store kind and row length
 int ph_dense_check(const phnsw_index *ix, uint64_t k, const char *call) {
+  if (ix) PH_TRY(ph_bits_unsupported(ix->store, call));  // a bits store has the plain walk alone
   if (!ix || ix->layers.empty()) {
     ph_set_error("%s: null index or index without layers", call);
     return PHNSW_E_INVALID;

@@ -173,6 +173,8 @@ void ph_exact_free(phnsw_index *ix) {
 }
 
 int ph_exact_supported(const phnsw_index *ix, uint32_t k) {
+  if (ix)  // (the entry points have refused a bits store by name)
+    if (int brc = ph_bits_unsupported(ix->store, "exact scan")) return brc;
   const phnsw_store *s = ix->store;
   if (!exact_fn(s)) return ph_dim_unsupported(s->dim);
   const size_t pq_lds = (ph_pq_lds_bytes(s) + 15u) & ~(size_t)15u, own_lds = (size_t)ph_exact_own_lds(k);

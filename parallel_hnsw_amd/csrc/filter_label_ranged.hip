@@ -293,6 +293,7 @@ int ph_label_attr_fresh(const phnsw_index *ix, const phnsw_label_attr *h, const 
 
 // index, k, handle, store: ph_ranged_check's checks in its order
 int ph_label_ranged_check(const phnsw_index *ix, const phnsw_label_attr *h, uint64_t k, const char *call) {
+  if (ix) PH_TRY(ph_bits_unsupported(ix->store, call));  // a bits store has the plain walk alone
   if (!ix || ix->layers.empty()) {
     ph_set_error("%s: null index or index without layers", call);
     return PHNSW_E_INVALID;
@@ -539,6 +540,7 @@ int label_attr_create_check(const phnsw_index *ix, const void *labels, const voi
 
 // what both forms of the walk check before they look at a pointer: index and parameters, the handle, the flags
 int walk_check(const phnsw_index *ix, const phnsw_label_attr *h, const phnsw_search_params *sp, uint32_t flags, const char *call) {
+  if (ix) PH_TRY(ph_bits_unsupported(ix->store, call));  // a bits store has the plain walk alone
   PH_TRY(ph_check_sp(ix, sp));
   PH_TRY(ph_label_attr_fresh(ix, h, call));
   if (flags & ~(uint32_t)PHNSW_FILTER_STRICT) {

@@ -516,6 +516,7 @@ int ph_labels_fresh(const phnsw_index *ix, const phnsw_labels *lb, const char *c
 
 // index, k, handle, store: the checks every exact form makes before it looks at another argument, in this order
 int ph_labeled_check(const phnsw_index *ix, const phnsw_labels *lb, uint64_t k, const char *call) {
+  if (ix) PH_TRY(ph_bits_unsupported(ix->store, call));  // a bits store has the plain walk alone
   if (!ix || ix->layers.empty()) {
     ph_set_error("%s: null index or index without layers", call);
     return PHNSW_E_INVALID;
@@ -1073,6 +1074,7 @@ namespace {
 
 // what both forms of the walk check before they look at a pointer: index and parameters, the handle, the flags
 int walk_check(const phnsw_index *ix, const phnsw_labels *lb, const phnsw_search_params *sp, uint32_t flags, const char *call) {
+  if (ix) PH_TRY(ph_bits_unsupported(ix->store, call));  // a bits store has the plain walk alone
   PH_TRY(ph_check_sp(ix, sp));
   PH_TRY(ph_labels_fresh(ix, lb, call));
   if (flags & ~(uint32_t)PHNSW_FILTER_STRICT) {

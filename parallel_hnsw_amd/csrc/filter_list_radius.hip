@@ -275,6 +275,7 @@ int list_radius_run(const phnsw_index *ix, const PhListView &view, const PhListR
 
 // what every entry point checks first, in this order: the index, cap ...
 int list_radius_check(const phnsw_index *ix, uint64_t cap, const char *call) {
+  if (ix) PH_TRY(ph_bits_unsupported(ix->store, call));  // a bits store has the plain walk alone
   if (!ix || ix->layers.empty()) {
     ph_set_error("%s: null index or index without layers", call);
     return PHNSW_E_INVALID;

@@ -161,6 +161,7 @@ int ph_attr_fresh(const phnsw_index *ix, const phnsw_attr *at, const char *call)
 
 // index, k, handle, store: ph_labeled_check's checks in its order
 int ph_ranged_check(const phnsw_index *ix, const phnsw_attr *at, uint64_t k, const char *call) {
+  if (ix) PH_TRY(ph_bits_unsupported(ix->store, call));  // a bits store has the plain walk alone
   if (!ix || ix->layers.empty()) {
     ph_set_error("%s: null index or index without layers", call);
     return PHNSW_E_INVALID;
@@ -333,6 +334,7 @@ int attr_create_check(const phnsw_index *ix, const void *keys, uint64_t n, phnsw
 
 // what both forms of the walk check before they look at a pointer: index and parameters, the handle, the flags
 int walk_check(const phnsw_index *ix, const phnsw_attr *at, const phnsw_search_params *sp, uint32_t flags, const char *call) {
+  if (ix) PH_TRY(ph_bits_unsupported(ix->store, call));  // a bits store has the plain walk alone
   PH_TRY(ph_check_sp(ix, sp));
   PH_TRY(ph_attr_fresh(ix, at, call));
   if (flags & ~(uint32_t)PHNSW_FILTER_STRICT) {

@@ -557,6 +557,7 @@ extern "C" int phnsw_search_exact_filtered(const phnsw_index *ix, const float *q
 // what the four collecting entry points check first, in this order: index and parameters, the flags, k, the stride
 int ph_collect_check(const phnsw_index *ix, const phnsw_search_params *sp, uint32_t stride, uint32_t flags, uint64_t k,
                      const char *call) {
+  if (ix) PH_TRY(ph_bits_unsupported(ix->store, call));  // a bits store has the plain walk alone
   PH_TRY(ph_check_sp(ix, sp));
   if (flags & ~(uint32_t)PHNSW_COLLECT_EXTEND) {
     ph_set_error("%s: unknown flag bits 0x%x", call, flags);

@@ -48,6 +48,23 @@ static int distance_batch_rows(const phnsw_store *st, const PhDistArgs &da, cons
   return 0;
 }
 
+// a bits store: DistBits has one template argument
+static int distance_batch_bits(const phnsw_store *st, const PhDistArgs &da, const float *q_dev, uint32_t query_id,
+                               const uint32_t *ids_dev, uint32_t k, float *out_dev, hipStream_t s) {
+  const uint32_t blocks = std::min<uint32_t>((k + 63) / 64, 4096);
+#define PH_LAUNCH(NV)                                                                                                  \
+  hipLaunchKernelGGL((ph_distance_batch_kernel<DistBits<NV>>), dim3(blocks), dim3(64), 0, s, da, q_dev, query_id, ids_dev, \
+                     k, st->n, out_dev)
+  switch (ph_chunk_count(st->ld / 4)) {
+    case 1: PH_LAUNCH(1); break;
+    case 3: PH_LAUNCH(3); break;
+    case 6: PH_LAUNCH(6); break;
+    default: return ph_dim_unsupported(st->dim);
+  }
+#undef PH_LAUNCH
+  return 0;
+}
+
 int ph_dim_unsupported(uint32_t dim) {
   ph_set_error("dim %u unsupported (max 1536)", dim);
   return PHNSW_E_UNSUPPORTED;
@@ -75,6 +92,7 @@ int ph_distance_batch(const phnsw_store *st, const float *q_dev, uint32_t query_
       case PH_ROWS_F16: rc = distance_batch_rows<DistF16>(st, da, q_dev, query_id, ids_dev, k, out_dev, s); break;
       case PH_ROWS_I8: rc = distance_batch_rows<DistI8>(st, da, q_dev, query_id, ids_dev, k, out_dev, s); break;
       case PH_ROWS_I8Q: rc = distance_batch_rows<DistI8Q>(st, da, q_dev, query_id, ids_dev, k, out_dev, s); break;  // integer dots
+      case PH_ROWS_BITS: rc = distance_batch_bits(st, da, q_dev, query_id, ids_dev, k, out_dev, s); break;         // popcounts
       default: rc = distance_batch_rows<DistF32>(st, da, q_dev, query_id, ids_dev, k, out_dev, s); break;
     }
     if (rc) return rc;

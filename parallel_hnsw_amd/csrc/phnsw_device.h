@@ -3,6 +3,7 @@
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
+#include "bits_plan.h"
 #include "phnsw_internal.h"
 
 #define EXPF 0x80000000u
@@ -589,6 +590,73 @@ struct DistI8Q {
     }
     for (uint32_t base = 0; base < m; base += U) round(d, olo, ohi, m, base, cand, myrank, lane, myd);
     return myd;
+  }
+};
+
+// ------------------------------------------------------------------ bits: one sign bit per component, Hamming distance
+// THE distance of a bits store, from the popcount h of (row XOR query) over the row's words.  A sign vector has
+// components +-1, so dot = dim - 2 h and |q - x|^2 = 4 h: integers below 2^24, which the f32 chain over the rows
+// phnsw_store_read returns reaches exactly, in any summation order.  The per-hop policy below and the distance batch
+// (misc.hip) both call it.
+__device__ __forceinline__ float ph_bits_distance(uint32_t h, uint32_t dim, int metric) {
+  return finalize_metric(ph_bits_raw(h, dim, metric == PHNSW_METRIC_L2), metric);
+}
+// the sign bits of chunk c (four components) of a raw query, components >= dim cut: bit e = component 4 c + e
+__device__ __forceinline__ uint32_t ph_bits_nibble(const float4 &v, uint32_t c, uint32_t dim) {
+  const uint32_t j = 4u * c;
+  return (j + 0u < dim ? ph_bits_sign_of(__float_as_uint(v.x)) : 0u) | (j + 1u < dim ? ph_bits_sign_of(__float_as_uint(v.y)) << 1 : 0u) |
+         (j + 2u < dim ? ph_bits_sign_of(__float_as_uint(v.z)) << 2 : 0u) | (j + 3u < dim ? ph_bits_sign_of(__float_as_uint(v.w)) << 3 : 0u);
+}
+
+// DistBits<NV>: rows of 32 NV bytes (bits_plan.h), ONE LANE per candidate, as the PQ policies map them: batch() hands
+// each lane its own id and wants the result in that lane, so there is no compaction, no wave reduction and no
+// ds_bpermute.  The query's 8 NV words are the same in every lane: built once per query and held wave-uniform
+// (readfirstlane / readlane: SGPRs).  A flagged lane issues its row's 2 NV 16-byte loads before the first use, then
+// 8 NV XOR + popcount and one ph_bits_distance; a lane that is not flagged holds no valid id and issues no load.
+// d.m carries the rows' dim (ph_dist_args).  No ROW_STORE member: the visited sets stay in the HBM bitmap.
+template <int NV>
+struct DistBits {
+  static constexpr bool GLOBAL_TABLE = false;
+  static constexpr bool EARLY = false;
+  static constexpr int WORDS = 8 * NV;
+  uint32_t qw[WORDS];
+  // a raw query is reduced to its sign bits by the rows' rule: lane l's chunk l + 64 k gives a nibble, eight lanes'
+  // nibbles one word (an OR butterfly inside the groups of eight), and word w of block k is read from lane 8 w
+  __device__ __forceinline__ void prepare_raw(const PhDistArgs &d, const float *q, float *, uint32_t lane) {
+#pragma unroll
+    for (int k = 0; k < NV; k++) {
+      const uint32_t c = lane + 64u * k;
+      uint32_t v = 0u;
+      if (c < d.nv4) v = ph_bits_nibble(((const float4 *)q)[c], c, d.m) << (4u * (lane & 7u));
+      v |= (uint32_t)__shfl_xor((int)v, 1);
+      v |= (uint32_t)__shfl_xor((int)v, 2);
+      v |= (uint32_t)__shfl_xor((int)v, 4);
+#pragma unroll
+      for (int w = 0; w < 8; w++) qw[8 * k + w] = rl32(v, 8 * w);
+    }
+  }
+  // a stored query is its row as it is (same address in every lane: scalar loads)
+  __device__ __forceinline__ void prepare_stored(const PhDistArgs &d, uint32_t vid, float *, uint32_t) {
+    const uint32_t *row = (const uint32_t *)((const char *)d.rows.base + (uint64_t)rfl32(vid) * d.rows.stride);
+#pragma unroll
+    for (int w = 0; w < WORDS; w++) qw[w] = rfl32(row[w]);
+  }
+  __device__ __forceinline__ float batch(const PhDistArgs &d, uint64_t mask, uint32_t vid, uint32_t lane) const {
+    float r = 0.f;
+    if ((mask >> lane) & 1ull) {
+      const uint4 *row = (const uint4 *)((const char *)d.rows.base + (uint64_t)vid * d.rows.stride);  // 16-byte aligned
+      uint4 x[2 * NV];
+#pragma unroll
+      for (int i = 0; i < 2 * NV; i++) x[i] = row[i];
+      uint32_t h = 0;
+#pragma unroll
+      for (int i = 0; i < 2 * NV; i++) {
+        h += __popc(x[i].x ^ qw[4 * i]) + __popc(x[i].y ^ qw[4 * i + 1]) + __popc(x[i].z ^ qw[4 * i + 2]) +
+             __popc(x[i].w ^ qw[4 * i + 3]);
+      }
+      r = ph_bits_distance(h, d.m, d.metric);
+    }
+    return r;
   }
 };
 

@@ -68,11 +68,15 @@ enum PhRowKind : int {
   PH_ROWS_PQ,         // u8 codes over per-sub-space codebooks (pq.hip)
   PH_ROWS_PQ_SHARED,  // u16 codes over one shared codebook (pq.hip)
   PH_ROWS_I8Q,        // the bytes of PH_ROWS_I8; a distance quantises the query too and takes integer dot products (DistI8Q)
+  PH_ROWS_BITS,       // n rows of 32 * ph_chunk_count(ld / 4) bytes: one sign bit per component (bits_plan.h, DistBits)
 };
 static inline bool ph_rows_converted(int kind) { return kind == PH_ROWS_F16 || kind == PH_ROWS_I8 || kind == PH_ROWS_I8Q; }
+// the 1-bit sign store is NOT one of the converted kinds: it has no f32 view of a row in registers, so the dense tables,
+// the split descent, the cells and the filtered / exact kernels written over a row policy do not serve it
+static inline bool ph_rows_bits(int kind) { return kind == PH_ROWS_BITS; }
 static inline bool ph_rows_i8_layout(int kind) { return kind == PH_ROWS_I8 || kind == PH_ROWS_I8Q; }  // scale + int8 codes
 static inline const char *ph_rows_name(int kind) {
-  static const char *const names[] = {"f32", "f16", "i8", "product-quantised", "shared-codebook product-quantised", "i8q"};
+  static const char *const names[] = {"f32", "f16", "i8", "product-quantised", "shared-codebook product-quantised", "i8q", "bits"};
   return names[kind];
 }
 // float4 chunks a lane holds of a row of nv4 float4s: the three shapes the row kernels are instantiated for (0: none;
@@ -95,7 +99,7 @@ struct PhDistArgs {
   const uint8_t *codes;   // [n][m] u8 codes (PQ store)
   const uint16_t *codes16;  // [n][m] u16 codes over ONE shared codebook [ksub][dsub] (the reference's shape, pq.rs:19-27)
   const float *codebook;  // [m][ksub][dsub]
-  uint32_t m, ksub, dsub;
+  uint32_t m, ksub, dsub;  // (a bit store, which has no code rows, keeps the rows' dim in m: ph_bits_distance needs it)
   uint32_t table_f16;  // 1: the per-query table holds IEEE half values (2 bytes per entry)
 };
 
@@ -803,6 +807,7 @@ static inline bool ph_store_converted(const phnsw_store *s) { return ph_rows_con
 // the other kinds.  `rows` / `codes` / `codes16` are non-null exactly on an f32 / PQ / shared-codebook PQ store (every
 // creator allocates n > 0 rows); a pointer is still what a hipFree or an ownership rule asks
 static inline bool ph_store_f32(const phnsw_store *s) { return s->kind == PH_ROWS_F32; }
+static inline bool ph_store_bits(const phnsw_store *s) { return ph_rows_bits(s->kind); }  // the 1-bit sign store (rowstore.hip)
 static inline bool ph_store_pq(const phnsw_store *s) { return s->kind == PH_ROWS_PQ; }
 static inline bool ph_store_pq_shared(const phnsw_store *s) { return s->kind == PH_ROWS_PQ_SHARED; }
 // converted stores (rowstore.hip): rows of `ids_dev` (nullptr: rows first .. first + cnt) widened / dequantised into
@@ -845,8 +850,9 @@ void ph_workspace_free(PhWorkspace &ws);
 size_t ph_tiny_beside_lds(const phnsw_index *ix, const PhSearchArgs &a);  // LDS of one table block that runs beside a search (0: none)
 static inline PhRows ph_store_rows(const phnsw_store *s) {
   PhRows r;
-  r.base = ph_store_converted(s) ? (const void *)s->packed : (const void *)s->rows;
-  r.stride = ph_store_converted(s) ? s->packed_stride : s->ld * 4u;
+  const bool packed = ph_store_converted(s) || ph_store_bits(s);
+  r.base = packed ? (const void *)s->packed : (const void *)s->rows;
+  r.stride = packed ? s->packed_stride : s->ld * 4u;
   r.kind = s->kind;
   return r;
 }
@@ -859,7 +865,7 @@ static inline PhDistArgs ph_dist_args(const phnsw_store *s) {
   d.codes = s->codes;
   d.codes16 = s->codes16;
   d.codebook = s->codebook;
-  d.m = s->pq_m;
+  d.m = ph_store_bits(s) ? s->dim : s->pq_m;
   d.ksub = s->pq_ksub;
   d.dsub = s->pq_dsub;
   d.table_f16 = s->pq_table_f16;
@@ -867,11 +873,20 @@ static inline PhDistArgs ph_dist_args(const phnsw_store *s) {
 }
 // bytes of one stored row as the search gathers it
 static inline uint32_t ph_row_bytes(const phnsw_store *s) { return ph_store_rows(s).stride; }
-// an f16, i8 or i8q store serves searches only: every other entry point refuses it by name
+// an f16, i8, i8q or bits store serves searches only: every other entry point refuses it by name
 static inline int ph_search_only_unsupported(const phnsw_store *s, const char *call) {
-  if (!s || !ph_store_converted(s)) return 0;
+  if (!s || !(ph_store_converted(s) || ph_store_bits(s))) return 0;
   ph_set_error("%s: not supported on an %s store or an index over one (search-only; use the f32 store)", call,
                ph_rows_name(s->kind));
+  return PHNSW_E_UNSUPPORTED;
+}
+// a bits store serves the plain walk, the distance batch and the re-ranked search alone: every filtered, labelled,
+// ranged, collecting or radius walk, every exact scan and every table refuses it by name, on the host, before a launch
+// (their kernels read rows through an f32 / f16 / i8 row policy: a 96-byte bit row is none of those)
+static inline int ph_bits_unsupported(const phnsw_store *s, const char *call) {
+  if (!s || !ph_store_bits(s)) return 0;
+  ph_set_error("%s: not supported on a bits store or an index over one (plain search, distance batch and re-ranked "
+               "search only; use the f32 store)", call);
   return PHNSW_E_UNSUPPORTED;
 }
 // the batched search keeps PQ tables in global memory unless PHNSW_PQ_TABLE=lds

@@ -652,7 +652,7 @@ static bool rerank_check(uint32_t kinds, const phnsw_index *ix, const phnsw_stor
   if (!ix || !full || !sp) return false;
   const phnsw_store *s = ix->store;
   return ((kinds >> s->kind) & 1u) && ph_store_f32(full) && full->n == s->n && full->dim == s->dim &&
-         (!ph_store_converted(s) || (full->metric == s->metric && full->device == s->device)) && nq <= 0xFFFFFFFFull &&
+         (!(ph_store_converted(s) || ph_store_bits(s)) || (full->metric == s->metric && full->device == s->device)) && nq <= 0xFFFFFFFFull &&
          sp->number_of_candidates != 0 && sp->number_of_candidates <= 1024 && sp->probe_depth != 0 && k != 0 &&
          k <= sp->number_of_candidates;
 }
@@ -904,4 +904,17 @@ extern "C" int phnsw_i8q_search_batch(const phnsw_index *ix, const phnsw_store *
                                       const phnsw_search_params *sp, uint64_t k, uint64_t *out_ids, float *out_d,
                                       uint64_t *out_len) try {
   return converted_search_host("phnsw_i8q_search_batch", PH_ROWS_I8Q, ix, full, queries, nq, sp, k, out_ids, out_d, out_len);
+} catch (...) { return ph_caught(); }
+// ... and on a bits store: the walk's distances are in sign-vector units, the re-ranked rows hold true f32 distances
+extern "C" int phnsw_bits_search_batch_device(const phnsw_index *ix, const phnsw_store *full, const float *queries_dev,
+                                              uint32_t ldq, uint64_t nq, const phnsw_search_params *sp, uint64_t k,
+                                              uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                              uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) try {
+  return converted_search_device("phnsw_bits_search_batch_device", PH_ROWS_BITS, ix, full, queries_dev, ldq, nq, sp, k, out_ids_dev,
+                                out_d_dev, out_len_dev, out_stats_dev, status_dev, stream);
+} catch (...) { return ph_caught(); }
+extern "C" int phnsw_bits_search_batch(const phnsw_index *ix, const phnsw_store *full, const float *queries, uint64_t nq,
+                                       const phnsw_search_params *sp, uint64_t k, uint64_t *out_ids, float *out_d,
+                                       uint64_t *out_len) try {
+  return converted_search_host("phnsw_bits_search_batch", PH_ROWS_BITS, ix, full, queries, nq, sp, k, out_ids, out_d, out_len);
 } catch (...) { return ph_caught(); }

@@ -21,6 +21,12 @@
 // i8q: the rows of an i8 store, byte for byte (same kernel, same layout, same phnsw_i8_read and phnsw_store_read); what
 // differs is the distance, which quantises the query with the rows' own quantiser and takes integer dot products
 // (DistI8Q, phnsw_device.h).  Dot-product metrics only: the Euclidean distance would need the rows' norms.
+//
+// bits: one sign bit per component (bits_plan.h has the layout rules: bit j = the component is below zero, component j
+// in bit j & 31 of word j >> 5, rows of 32 * NV bytes, padding bits 0).  NOT a converted store in the sense above: no
+// row policy widens it in registers, a distance is a popcount (DistBits, phnsw_device.h), and only the plain walk, the
+// distance batch and the re-ranked search serve it (ph_bits_unsupported names everything else).  phnsw_store_read
+// returns its rows as +1 / -1, the values on which the f32 search gives the same distances, bit for bit.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -78,6 +84,45 @@ __global__ void ph_i8_convert_kernel(const float *__restrict__ rows, uint32_t ld
   if (mine) atomicOr(bad, 1u);
 }
 
+// one wave per row: 64 components at a time (coalesced), their sign bits by one ballot = two words of the row; lane w
+// keeps word w and the row's 8 NV words leave in one coalesced store (words past the row's components: 0).  A NaN or
+// an infinite component raises the flag.  stride_words <= 48 < 64.
+__global__ void ph_bits_convert_kernel(const float *__restrict__ rows, uint32_t ld, uint32_t dim, uint64_t n,
+                                       uint32_t *__restrict__ out, uint32_t stride_words, uint32_t *bad) {
+  const uint32_t lane = threadIdx.x & 63u, wpb = blockDim.x / 64u;
+  bool mine = false;
+  for (uint64_t r = (uint64_t)blockIdx.x * wpb + threadIdx.x / 64u; r < n; r += (uint64_t)gridDim.x * wpb) {
+    const float *src = rows + r * ld;
+    uint32_t word = 0u;
+    for (uint32_t b = 0; 64u * b < dim; b++) {
+      const uint32_t c = 64u * b + lane;
+      uint32_t neg = 0u;
+      if (c < dim) {
+        const uint32_t u = __float_as_uint(src[c]);
+        mine |= (u & 0x7F800000u) == 0x7F800000u;
+        neg = ph_bits_sign_of(u);
+      }
+      const uint64_t m = __ballot(neg != 0u);
+      if (lane == 2u * b) word = (uint32_t)m;
+      if (lane == 2u * b + 1u) word = (uint32_t)(m >> 32);
+    }
+    if (lane < stride_words) out[r * stride_words + lane] = word;
+  }
+  if (mine) atomicOr(bad, 1u);
+}
+
+// rows [first, first + count) of a bits store as a dense [count][dim] array of +1.0f (bit 0) / -1.0f (bit 1)
+__global__ void ph_bits_read_kernel(const uint32_t *__restrict__ words, uint32_t stride_words, uint32_t dim, uint64_t first,
+                                    uint64_t count, float *__restrict__ out) {
+  const uint64_t total = count * (uint64_t)dim;
+  for (uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; x < total; x += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t r = x / dim;
+    const uint32_t j = (uint32_t)(x - r * dim);
+    const uint32_t w = words[(first + r) * stride_words + ph_bits_word_of(j)];
+    out[x] = ((w >> ph_bits_bit_of(j)) & 1u) ? -1.0f : 1.0f;
+  }
+}
+
 // rows [first, first + count) converted into a dense [count][dim] f32 array: what the distance kernels see.  One
 // thread per chunk of four components (a row holds whole chunks: ld is a multiple of 4), the last one cut at dim.
 template <class R>
@@ -116,6 +161,7 @@ static int gather_rows(const phnsw_store *s, const uint32_t *ids_dev, uint32_t f
 }
 int ph_converted_gather_rows(const phnsw_store *s, const uint32_t *ids_dev, uint32_t first, uint32_t cnt, float *out_dev) {
   if (cnt == 0) return 0;
+  if (int rc = ph_bits_unsupported(s, "locality cells")) return rc;  // (ph_layer_wants_cells is false for the kind)
   return s->kind == PH_ROWS_F16 ? gather_rows<RowF16>(s, ids_dev, first, cnt, out_dev)
                                 : gather_rows<RowI8>(s, ids_dev, first, cnt, out_dev);
 }
@@ -139,7 +185,25 @@ static int store_read(const phnsw_store *s, uint64_t first, uint64_t count, floa
   hipFree(tmp);
   return rc;
 }
+static int bits_store_read(const phnsw_store *s, uint64_t first, uint64_t count, float *out) {
+  const uint64_t PIECE = 65536;
+  float *tmp = nullptr;
+  PH_HIP(hipMalloc(&tmp, (size_t)std::min(PIECE, count) * s->dim * 4));
+  int rc = 0;
+  for (uint64_t at = 0; at < count && !rc; at += PIECE) {
+    const uint64_t cnt = std::min(PIECE, count - at);
+    const uint64_t total = cnt * s->dim;
+    hipLaunchKernelGGL(ph_bits_read_kernel, dim3((uint32_t)std::min<uint64_t>((total + 255) / 256, 65536)), dim3(256), 0, 0,
+                       (const uint32_t *)s->packed, s->packed_stride / 4u, s->dim, first + at, cnt, tmp);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(out + at * s->dim, tmp, (size_t)total * 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = ph_hip_fail(e, "bits store read", __FILE__, __LINE__);
+  }
+  hipFree(tmp);
+  return rc;
+}
 int ph_converted_store_read(const phnsw_store *s, uint64_t first, uint64_t count, float *out) {
+  if (ph_store_bits(s)) return bits_store_read(s, first, count, out);
   return s->kind == PH_ROWS_F16 ? store_read<RowF16>(s, first, count, out) : store_read<RowI8>(s, first, count, out);
 }
 
@@ -163,6 +227,7 @@ static int create_converted(const char *name, const phnsw_store *full, int kind,
     ph_set_error("%s: the Euclidean metric is not supported on an i8q store (dot-product metrics only)", name);
     return PHNSW_E_UNSUPPORTED;
   }
+  if (kind == PH_ROWS_BITS && !ph_chunk_count(full->ld / 4)) return ph_dim_unsupported(full->dim);
   PH_HIP(hipSetDevice(full->device));
   phnsw_store *s = new phnsw_store();
   s->device = full->device;
@@ -170,7 +235,9 @@ static int create_converted(const char *name, const phnsw_store *full, int kind,
   s->n = full->n;
   s->dim = full->dim;
   s->ld = full->ld;
-  s->packed_stride = kind == PH_ROWS_F16 ? full->ld * 2u : ((4u + full->ld + 15u) & ~15u);
+  s->packed_stride = kind == PH_ROWS_BITS  ? ph_bits_stride(ph_chunk_count(full->ld / 4))
+                     : kind == PH_ROWS_F16 ? full->ld * 2u
+                                           : ((4u + full->ld + 15u) & ~15u);
   s->metric = full->metric;
   s->rows = nullptr;
   uint32_t *bad = nullptr;
@@ -183,6 +250,9 @@ static int create_converted(const char *name, const phnsw_store *full, int kind,
       const uint64_t total = s->n * (uint64_t)s->ld;
       hipLaunchKernelGGL(ph_f16_convert_kernel, dim3((uint32_t)std::min<uint64_t>((total + 255) / 256, 1u << 20)), dim3(256), 0,
                          0, full->rows, full->ld, full->dim, s->n, (uint16_t *)s->packed, s->ld, bad);
+    } else if (kind == PH_ROWS_BITS) {
+      hipLaunchKernelGGL(ph_bits_convert_kernel, dim3((uint32_t)std::min<uint64_t>((s->n + 3) / 4, 1u << 16)), dim3(256), 0, 0,
+                         full->rows, full->ld, full->dim, s->n, (uint32_t *)s->packed, s->packed_stride / 4u, bad);
     } else {
       hipLaunchKernelGGL(ph_i8_convert_kernel, dim3((uint32_t)std::min<uint64_t>((s->n + 3) / 4, 1u << 16)), dim3(256), 0, 0,
                          full->rows, full->ld, full->dim, s->n, (uint8_t *)s->packed, s->packed_stride, bad);
@@ -193,7 +263,8 @@ static int create_converted(const char *name, const phnsw_store *full, int kind,
   if (bad) hipFree(bad);
   int rc = 0;
   if (e != hipSuccess)
-    rc = ph_hip_fail(e, kind == PH_ROWS_F16 ? "f16 store conversion" : "i8 store conversion", __FILE__, __LINE__);
+    rc = ph_hip_fail(e, kind == PH_ROWS_F16 ? "f16 store conversion" : (kind == PH_ROWS_BITS ? "bits store conversion" : "i8 store conversion"),
+                     __FILE__, __LINE__);
   else if (h_bad) {
     if (kind == PH_ROWS_F16)
       ph_set_error("%s: a component is NaN or rounds to infinity in binary16 (|x| >= 65520)", name);
@@ -218,6 +289,23 @@ extern "C" int phnsw_store_create_i8(const phnsw_store *full, phnsw_store **out)
 } catch (...) { return ph_caught(); }
 extern "C" int phnsw_store_create_i8q(const phnsw_store *full, phnsw_store **out) try {
   return create_converted("phnsw_store_create_i8q", full, PH_ROWS_I8Q, out);
+} catch (...) { return ph_caught(); }
+
+extern "C" int phnsw_store_create_bits(const phnsw_store *full, phnsw_store **out) try {
+  return create_converted("phnsw_store_create_bits", full, PH_ROWS_BITS, out);
+} catch (...) { return ph_caught(); }
+
+// the sign bits [n][ceil(dim / 32)]: the public layout, whatever the device stride
+extern "C" int phnsw_bits_read(const phnsw_store *s, uint32_t *words) try {
+  if (!s || !ph_store_bits(s) || !words) {
+    ph_set_error("phnsw_bits_read: needs a bits store and the output");
+    return PHNSW_E_INVALID;
+  }
+  if (s->n == 0) return 0;
+  PH_HIP(hipSetDevice(s->device));
+  const size_t width = (size_t)ph_bits_words(s->dim) * 4u;
+  PH_HIP(hipMemcpy2D(words, width, s->packed, s->packed_stride, width, s->n, hipMemcpyDeviceToHost));
+  return 0;
 } catch (...) { return ph_caught(); }
 
 // the stored codes [n][dim] and scales [n], as they lie in the rows

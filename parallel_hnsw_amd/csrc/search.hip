@@ -123,6 +123,7 @@ struct PhKernelChoice {
   bool lat_shape = false;  // the shape has a latency kernel and the batch is small enough for it (the instrumented
                            // kernel overrides it, as it always has: after the latency path made its LDS arrangements)
 };
+// (not PH_KF_ROWS_BITS: no LDS visited table, no radius twin)
 static bool kf_rows(PhKernelFamily f) {
   return f == PH_KF_ROWS_F32 || f == PH_KF_ROWS_F16 || f == PH_KF_ROWS_I8 || f == PH_KF_ROWS_I8Q;
 }
@@ -150,6 +151,12 @@ static PhKernelChoice pick_unfiltered_kernel(const phnsw_store *s, uint32_t ef_m
       k.family = PH_KF_PQ_SHARED;
       k.nv = ph_chunk_count(nv4);
       k.fn = pick_kernel_pqs<false>(capc, k.nv);
+      return k;
+    case PH_ROWS_BITS:  // search_bits.hip: queues of 128 / 256 / 512 / 1024 slots, the one throughput kernel per shape
+      k.family = PH_KF_ROWS_BITS;
+      k.nv = ph_chunk_count(nv4);
+      k.capc = pick_capc_dense(ef_max);
+      k.fn = (instr || grows) ? nullptr : ph_pick_kernel_bits(k.capc, k.nv);
       return k;
     default: break;
   }
@@ -419,16 +426,21 @@ int ph_search_launch_big(const phnsw_index *ix, PhSearchArgs &a, uint32_t grid, 
 }
 
 int ph_search_launch(const phnsw_index *ix, PhWorkspace &ws, PhSearchArgs &a, hipStream_t stream, bool mark_end) {
-  if (a.dense_only) return search_launch_dense(ws, a, stream);
   const phnsw_store *st = ix->store;
+  // a bits store has no dense table (ph_tiny_layer_count is 0 for it): nothing but the per-hop walk may launch
+  if (ph_store_bits(st) && (a.tiny_layers || a.dense_only || a.after_dense))
+    return ph_bits_unsupported(st, "dense-table search launch");
+  if (a.dense_only) return search_launch_dense(ws, a, stream);
   const uint32_t ef_max = std::max(a.ef, a.cap_max);
-  if (ph_store_converted(st) && (a.knn_mode || a.out_index))
+  if ((ph_store_converted(st) || ph_store_bits(st)) && (a.knn_mode || a.out_index))
     return ph_search_only_unsupported(st, "knn / threshold_nn / search_instrumented");
   if (a.out_index && st->kind != PH_ROWS_F32) {
     ph_set_error("search_instrumented: f32 stores only");
     return PHNSW_E_UNSUPPORTED;
   }
   const int mode = ph_filter_mode(a);
+  // a bits store has no filtered, collecting or radius twin and no dense table (pick_kernel_family has no case for it)
+  if (ph_store_bits(st) && mode != PH_FM_NONE) return ph_bits_unsupported(st, "filtered / collecting / radius search launch");
   if (mode != PH_FM_NONE && (a.knn_mode || a.out_index)) {  // only the plain searches have filtered kernels
     ph_set_error("knn / threshold_nn / search_instrumented take no filter");
     return PHNSW_E_UNSUPPORTED;
@@ -496,6 +508,8 @@ int ph_search_launch(const phnsw_index *ix, PhWorkspace &ws, PhSearchArgs &a, hi
     ph_set_error("unsupported search shape: ef=%u nv4=%u", a.ef, a.dist.nv4);
     return PHNSW_E_UNSUPPORTED;
   }
+  if (k.family == PH_KF_ROWS_BITS && getenv("PHNSW_VERBOSE"))
+    fprintf(stderr, "[phnsw] search kernel: bits family, queue of %d slots, %d x 256 bits per row\n", k.capc * 64, k.nv);
   a.visited = ws.visited;
   a.visited_words = ws.visited_words;
   a.ovf = ws.ovf;

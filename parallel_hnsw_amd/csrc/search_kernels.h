@@ -1259,6 +1259,7 @@ enum PhKernelFamily {
   PH_KF_PQ_SHARED,  // shared-codebook PQ
   PH_KF_LATENCY,    // small batches over f32 rows
   PH_KF_INSTR,      // Hnsw::search_instrumented over f32 rows
+  PH_KF_ROWS_BITS,  // throughput kernels over 1-bit sign rows (search_bits.hip; no filtered, collecting or radius twin)
 };
 
 // the register-table PQ policy (pick_pqr): 32 / 64 / 96 / 128 sub-spaces, queues of up to 512 entries
@@ -1368,6 +1369,9 @@ ph_search_fn ph_pick_label_ranged_dense(int capc);
 // the radius twins (PH_FM_RADIUS, no filter): search_radius.hip.  Row stores and the 1024-slot queues only; nullptr for
 // every other family or shape
 ph_search_fn ph_pick_radius_kernel(int family, int nv);
+// the kernels of a bits store (search_bits.hip): queues of capc * 64 slots, capc in {2, 4, 8, 16}, nv in {1, 3, 6}; plain
+// searches only -- pick_kernel_family has no case for the family, so no FILT twin of them exists
+ph_search_fn ph_pick_kernel_bits(int capc, int nv);
 // the collecting twins (PH_FM_COLLECT over the bitmap and over the label column): search_collect.hip and
 // search_collect_labeled.hip.  No dense-only twin: a collecting kernel runs the last layer of a descent, and the
 // dense-only launch of a split descent never holds it (api.hip)

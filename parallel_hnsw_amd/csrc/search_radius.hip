@@ -39,6 +39,7 @@ ph_search_fn ph_pick_radius_kernel(int family, int nv) {
 // what both entry points check first, in this order: the index and the search parameters (as phnsw_search_batch), max_out,
 // the store
 static int radius_walk_check(const phnsw_index *ix, const phnsw_search_params *sp, uint64_t max_out, const char *call) {
+  if (ix) PH_TRY(ph_bits_unsupported(ix->store, call));  // a bits store has the plain walk alone
   PH_TRY(ph_check_sp(ix, sp));
   if (max_out < 1u || max_out > 1024u) {
     ph_set_error("%s: max_out must be 1..1024 (got %llu)", call, (unsigned long long)max_out);

@@ -788,6 +788,7 @@ static int tiny_table(const phnsw_index *ix, PhWorkspace &ws, const PhDistArgs &
   if (const char *e = getenv("PHNSW_TINY_DBG")) t.dbg = (uint32_t)atoi(e);
   const uint32_t nv4 = dist.nv4;
   const int nv = ph_chunk_count(nv4);  // 1, 3 or 6: ph_tiny_layer_count gives longer rows no dense layer
+  if (dist.rows.kind == PH_ROWS_BITS) return ph_bits_unsupported(ix->store, "dense distance table");  // no row policy reads bit rows
   if (dist.rows.kind == PH_ROWS_I8Q) return tiny_table_i8q(ix, ws, dist, queries, ldq, qids, order, npos, tnodes, tn, stride, D, stream, kept);
   // dot-product metrics over whole 64-chunk rows go to the matrix cores (same bits, see above); the Euclidean
   // chain (fma(d, d, acc) of a difference) is not a product of the two operands and stays on the vector units, as

@@ -808,8 +808,36 @@ class I8QStore(_Int8Rows):
     _create = "phnsw_store_create_i8q"
 
 
+class BitStore(VectorStore):
+    """one sign bit per component of an f32 VectorStore (phnsw_store_create_bits): bit j of a row is row[j] < 0, 96
+    bytes per 768-component vector.  A distance comes from the Hamming distance h of row and query (the query reduced
+    by the same rule): dim - 2 h for the dot-product metrics, 4 h for L2, then the metric's last step -- exactly the f32
+    search over read()'s +1 / -1 rows with the query where(q < 0, -1, +1); tests/bits_reference.py restates it.  The
+    plain searches return these sign-vector distances; Hnsw.search_batch_reranked returns true f32 distances.  All
+    three metrics.  Plain searches, distance batches and the re-ranked search only: every filtered, exact, radius or
+    build call refuses it.  Adopt a graph built over the f32 store with Hnsw.from_layers(bit_store, ...)"""
+
+    def __init__(self, full):
+        h = C.c_void_p()
+        check(lib().phnsw_store_create_bits(full._h, C.byref(h)))
+        VectorStore.__init__(self, _handle=h, device=full.device)
+        self.full = full
+
+    @classmethod
+    def from_full(cls, store):
+        return cls(store)
+
+    def words(self):
+        """the sign bits [n, ceil(dim / 32)] uint32: component j is bit j & 31 of word j >> 5"""
+        out = np.empty((self.n, (self.dim + 31) // 32), dtype=np.uint32)
+        check(lib().phnsw_bits_read(self._h, _p(out)))
+        return out
+
+
 def _reranked_kind(store):
     """the name a converted store's re-ranked search calls carry"""
+    if isinstance(store, BitStore):
+        return "bits"
     return "i8q" if isinstance(store, I8QStore) else ("i8" if isinstance(store, I8Store) else "f16")
 
 
@@ -2367,9 +2395,9 @@ class Hnsw:
             C.c_void_p(out_len), C.c_void_p(out_route or None), C.c_void_p(status), C.c_void_p(stream or None)))
 
     def search_batch_reranked(self, full, queries, sp=None, k=10):
-        """an index over an F16Store, I8Store or I8QStore: search it, recompute every result's distance on the f32 store
-        `full`, sort by (distance, id), keep the best k (phnsw_f16_search_batch / phnsw_i8_search_batch /
-        phnsw_i8q_search_batch)
+        """an index over an F16Store, I8Store, I8QStore or BitStore: search it, recompute every result's distance on the
+        f32 store `full`, sort by (distance, id), keep the best k (phnsw_f16_search_batch / phnsw_i8_search_batch /
+        phnsw_i8q_search_batch / phnsw_bits_search_batch)
         -> ids[nq, k] u64, d[nq, k] f32, len[nq]"""
         sp = sp or SearchParameters()
         q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)

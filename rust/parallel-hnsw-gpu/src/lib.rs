@@ -129,6 +129,22 @@ impl GpuComparator {
         GpuComparator { host: self.host.clone(), store: Arc::new(StoreHandle(s)) }
     }
 
+    /// The same vectors as one sign bit per component (`phnsw_store_create_bits`): Hamming distances in sign-vector
+    /// units, plain searches only.  Re-rank with `GpuHnsw::search_many_reranked_bits` for true f32 distances.
+    pub fn to_bits(&self) -> Self {
+        let mut s = std::ptr::null_mut();
+        check(unsafe { sys::phnsw_store_create_bits(self.store.0, &mut s) });
+        GpuComparator { host: self.host.clone(), store: Arc::new(StoreHandle(s)) }
+    }
+
+    /// the sign bits `[n][ceil(dim / 32)]` of a `to_bits()` comparator (`phnsw_bits_read`)
+    pub fn bits_words(&self) -> Vec<u32> {
+        let (n, dim) = (self.host.len(), self.host.first().map_or(0, |v| v.len()));
+        let mut words = vec![0u32; n * ((dim + 31) / 32)];
+        check(unsafe { sys::phnsw_bits_read(self.store.0, words.as_mut_ptr()) });
+        words
+    }
+
     /// codes `[n][dim]` and scales `[n]` of a `to_i8()` or `to_i8q()` comparator (`phnsw_i8_read`)
     pub fn i8_codes_and_scales(&self) -> (Vec<i8>, Vec<f32>) {
         let (n, dim) = (self.host.len(), self.host.first().map_or(0, |v| v.len()));
@@ -1118,6 +1134,38 @@ impl GpuHnsw {
         let psp = sp_c(sp);
         check(sys::phnsw_i8q_search_batch_device(self.ix, full.store.0, queries_dev, ldq, nq, &psp, k, out_ids_dev, out_d_dev,
                                                  out_len_dev, out_stats_dev, status_dev, stream));
+    }
+
+    /// `search_many_reranked` for an index over a `to_bits()` comparator (`phnsw_bits_search_batch`): the walk runs on
+    /// Hamming distances, the returned distances are true f32 distances on `full`
+    pub fn search_many_reranked_bits(&self, full: &GpuComparator, queries: &[Vec<f32>], sp: SearchParameters, k: usize)
+                                     -> Vec<Vec<(VectorId, f32)>> {
+        let nq = queries.len();
+        let psp = sp_c(sp);
+        let mut q: Vec<f32> = Vec::with_capacity(nq * queries.first().map_or(0, |x| x.len()));
+        for x in queries {
+            q.extend_from_slice(x);
+        }
+        let (mut ids, mut d, mut len) = (vec![0u64; nq * k], vec![0f32; nq * k], vec![0u64; nq]);
+        check(unsafe {
+            sys::phnsw_bits_search_batch(self.ix, full.store.0, q.as_ptr(), nq as u64, &psp, k as u64, ids.as_mut_ptr(),
+                                         d.as_mut_ptr(), len.as_mut_ptr())
+        });
+        (0..nq).map(|i| (0..len[i] as usize).map(|j| (VectorId(ids[i * k + j] as usize), d[i * k + j])).collect()).collect()
+    }
+
+    /// zero-copy form (`phnsw_bits_search_batch_device`), as `search_reranked_i8_device`
+    ///
+    /// # Safety
+    /// the pointers must be valid device allocations of the sizes `phnsw.h` documents for the call
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn search_reranked_bits_device(&self, full: &GpuComparator, queries_dev: *const f32, ldq: u32, nq: u64,
+                                              sp: SearchParameters, k: u64, out_ids_dev: *mut u32, out_d_dev: *mut f32,
+                                              out_len_dev: *mut u32, out_stats_dev: *mut u32, status_dev: *mut u32,
+                                              stream: *mut c_void) {
+        let psp = sp_c(sp);
+        check(sys::phnsw_bits_search_batch_device(self.ix, full.store.0, queries_dev, ldq, nq, &psp, k, out_ids_dev, out_d_dev,
+                                                  out_len_dev, out_stats_dev, status_dev, stream));
     }
 
     /// `Hnsw::search_instrumented(v, sp)`  lib.rs:667-673

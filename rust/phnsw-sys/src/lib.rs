@@ -674,6 +674,18 @@ extern "C" {
                                          out_d_dev: *mut c_float, out_len_dev: *mut u32, out_stats_dev: *mut u32,
                                          status_dev: *mut u32, stream: *mut c_void) -> c_int;
 
+    // ---- one sign bit per component: Hamming distances on the walk, re-rank on the f32 store
+    pub fn phnsw_store_create_bits(full: *const phnsw_store, out: *mut *mut phnsw_store) -> c_int;
+    pub fn phnsw_bits_read(s: *const phnsw_store, words: *mut u32) -> c_int;
+    pub fn phnsw_bits_search_batch(ix: *const phnsw_index, full: *const phnsw_store, queries: *const c_float,
+                                   nq: u64, sp: *const phnsw_search_params, k: u64, out_ids: *mut u64,
+                                   out_d: *mut c_float, out_len: *mut u64) -> c_int;
+    pub fn phnsw_bits_search_batch_device(ix: *const phnsw_index, full: *const phnsw_store,
+                                          queries_dev: *const c_float, ldq: u32, nq: u64,
+                                          sp: *const phnsw_search_params, k: u64, out_ids_dev: *mut u32,
+                                          out_d_dev: *mut c_float, out_len_dev: *mut u32, out_stats_dev: *mut u32,
+                                          status_dev: *mut u32, stream: *mut c_void) -> c_int;
+
     // ---- on-disk interchange (serialize.rs:33-209)
     pub fn phnsw_index_serialize(ix: *const phnsw_index, path: *const c_char) -> c_int;
     pub fn phnsw_index_deserialize(s: *mut phnsw_store, path: *const c_char, out: *mut *mut phnsw_index) -> c_int;
