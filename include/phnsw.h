@@ -1614,6 +1614,37 @@ int phnsw_bits_search_batch_device(const phnsw_index *ix, const phnsw_store *ful
                                    uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
                                    uint32_t *out_stats_dev, uint32_t *status_dev, void *stream);
 
+/* ---- MXFP4 row store: 4-bit codes, one power-of-two scale per 32 components (rowstore.hip) ----
+ * The rows of the f32 store `full` as OCP MXFP4, quantised block by block by a device kernel.  Block b of a row is
+ * components [32b, 32b + 32); components at or past dim count as 0.  With m = max |x| over the block:
+ *   e8 = clamp(floor(log2 m) - 2 + 127, 2, 252)  (from the f32 exponent field; m = 0 or a smaller exponent gives 2),
+ *   y = x * 2^-(e8 - 127), |y| rounded to the E2M1 grid {0, 0.5, 1, 1.5, 2, 3, 4, 6}: nearest, ties to the code with an
+ *   even mantissa bit (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4), saturating at 6,
+ *   code = sign << 3 | magnitude, and a magnitude of 0 always has sign 0 (no -0).
+ * A component decodes to +-grid[code & 7] * 2^(e8 - 127), which f32 holds exactly and which is zero or a normal number
+ * (tests/fp4_reference.py restates quantiser and decoder in numpy).  ld / 2 code bytes and 32 scale bytes per 1024
+ * components a row: 416 bytes per stored 768-component vector instead of 3 072.  n, dim, ld, metric and device are
+ * those of `full`; all three metrics are accepted.  A source that is not an f32 store, or a NaN or infinite component,
+ * is PHNSW_E_INVALID; a row longer than 1536 floats is PHNSW_E_UNSUPPORTED.
+ * A distance on the store decodes in registers and runs the f32 store's arithmetic, so every result equals, bit for
+ * bit, the f32 search over the decoded rows -- which phnsw_store_read returns (phnsw_store_info reports rows_dev
+ * NULL).  The store is SEARCH-ONLY with the supported list of the i8 store, every filtered, labelled, ranged, collecting,
+ * radius and exact call included; every other entry point returns PHNSW_E_UNSUPPORTED with a message that names the
+ * call and "fp4". */
+int phnsw_store_create_fp4(const phnsw_store *full, phnsw_store **out);
+/* the public layout of an fp4 store, whatever the rows look like on the device: codes [n][ceil(dim / 2)], component j
+ * in nibble j & 1 of byte j >> 1 (a last odd nibble is 0); scales [n][ceil(dim / 32)], the e8 byte of every block */
+int phnsw_fp4_read(const phnsw_store *s, uint8_t *codes, uint8_t *scales);
+/* phnsw_i8_search_batch / _device over an index on an fp4 store: search, recompute every returned id on `full`, sort
+ * by (distance, id), keep the best k <= number_of_candidates; same outputs */
+int phnsw_fp4_search_batch(const phnsw_index *ix, const phnsw_store *full, const float *queries, uint64_t nq,
+                           const phnsw_search_params *sp, uint64_t k, uint64_t *out_ids, float *out_d,
+                           uint64_t *out_len);
+int phnsw_fp4_search_batch_device(const phnsw_index *ix, const phnsw_store *full, const float *queries_dev,
+                                  uint32_t ldq, uint64_t nq, const phnsw_search_params *sp, uint64_t k,
+                                  uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                  uint32_t *out_stats_dev, uint32_t *status_dev, void *stream);
+
 /* ---- on-disk interchange with the Rust crate: serialize_hnsw / deserialize_hnsw
  * (src/serialize.rs:33-209): <dir>/meta (JSON HNSWMeta), <dir>/comparator/ (this library's
  * store; a crate user substitutes their own Serializable comparator), layer.meta.N (JSON),

@@ -135,6 +135,19 @@ class Comparator {
     words.resize(n_ * ((dim_ + 31u) / 32u));
     check(phnsw_bits_read(s_, words.data()));
   }
+  // the same vectors as MXFP4 rows, 4-bit codes with one power-of-two scale per 32 components (phnsw_store_create_fp4):
+  // search-only like make_i8, every filtered and exact call included; re-rank with Hnsw::search_many_reranked_fp4
+  phnsw_store *make_fp4() const {
+    phnsw_store *h = nullptr;
+    check(phnsw_store_create_fp4(s_, &h));
+    return h;  // wrap it: Comparator q4(full.make_fp4());
+  }
+  // codes [n][ceil(dim / 2)] and scale bytes [n][ceil(dim / 32)] of a comparator made by make_fp4 (phnsw_fp4_read)
+  void read_fp4(std::vector<uint8_t> &codes, std::vector<uint8_t> &scales) const {
+    codes.resize(n_ * ((dim_ + 1u) / 2u));
+    scales.resize(n_ * ((dim_ + 31u) / 32u));
+    check(phnsw_fp4_read(s_, codes.data(), scales.data()));
+  }
   // codes [n][dim] and scales [n] of a comparator made by make_i8 or make_i8q (phnsw_i8_read)
   void read_i8(std::vector<int8_t> &codes, std::vector<float> &scales) const {
     codes.resize(n_ * dim_);
@@ -298,6 +311,24 @@ class Hnsw {
                                    uint32_t *out_len_dev, uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) const {
     check(phnsw_bits_search_batch_device(ix_, full.handle(), queries_dev, ldq, nq, &sp, k, out_ids_dev, out_d_dev, out_len_dev,
                                          out_stats_dev, status_dev, stream));
+  }
+  // the same two over an fp4 comparator (phnsw_fp4_search_batch / _device)
+  std::vector<SearchResult> search_many_reranked_fp4(const Comparator &full, const std::vector<float> &queries,
+                                                     const SearchParameters &sp, uint64_t k) const {
+    const uint64_t nq = queries.size() / c_->dim();
+    std::vector<uint64_t> ids(nq * k), len(nq);
+    std::vector<float> d(nq * k);
+    check(phnsw_fp4_search_batch(ix_, full.handle(), queries.data(), nq, &sp, k, ids.data(), d.data(), len.data()));
+    std::vector<SearchResult> out(nq);
+    for (uint64_t i = 0; i < nq; i++)
+      for (uint64_t j = 0; j < len[i]; j++) out[i].push_back({ids[i * k + j], d[i * k + j]});
+    return out;
+  }
+  void search_reranked_fp4_device(const Comparator &full, const float *queries_dev, uint32_t ldq, uint64_t nq,
+                                  const SearchParameters &sp, uint64_t k, uint32_t *out_ids_dev, float *out_d_dev,
+                                  uint32_t *out_len_dev, uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) const {
+    check(phnsw_fp4_search_batch_device(ix_, full.handle(), queries_dev, ldq, nq, &sp, k, out_ids_dev, out_d_dev, out_len_dev,
+                                        out_stats_dev, status_dev, stream));
   }
   // the batched form every GPU caller should use
   std::vector<SearchResult> search_many(const std::vector<AbstractVector> &vs, const SearchParameters &sp,

@@ -190,6 +190,7 @@ static PhLabelRangedFn label_ranged_scan_fn(const phnsw_store *s, bool pairs = f
     case PH_ROWS_F16: return label_ranged_rows_fn<DistF16>(s->ld / 4, pairs);
     case PH_ROWS_I8: return label_ranged_rows_fn<DistI8>(s->ld / 4, pairs);
     case PH_ROWS_I8Q: return label_ranged_rows_fn<DistI8Q>(s->ld / 4, pairs);
+    case PH_ROWS_FP4: return label_ranged_rows_fn<DistFP4>(s->ld / 4, pairs);
     default: return label_ranged_rows_fn<DistF32>(s->ld / 4, pairs);
   }
 }

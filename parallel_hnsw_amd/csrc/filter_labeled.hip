@@ -466,6 +466,7 @@ static PhLabeledFn labeled_scan_fn(const phnsw_store *s, bool pairs) {
     case PH_ROWS_F16: return labeled_rows_fn<DistF16>(s->ld / 4, pairs);
     case PH_ROWS_I8: return labeled_rows_fn<DistI8>(s->ld / 4, pairs);
     case PH_ROWS_I8Q: return labeled_rows_fn<DistI8Q>(s->ld / 4, pairs);
+    case PH_ROWS_FP4: return labeled_rows_fn<DistFP4>(s->ld / 4, pairs);
     default: return labeled_rows_fn<DistF32>(s->ld / 4, pairs);
   }
 }
@@ -484,6 +485,7 @@ static PhLabeledFn labeled_tile_fn(const phnsw_store *s, bool pairs) {
     case PH_ROWS_F32: return labeled_tile_rows_fn<RowF32>(s->ld / 4, pairs);
     case PH_ROWS_F16: return labeled_tile_rows_fn<RowF16>(s->ld / 4, pairs);
     case PH_ROWS_I8: return labeled_tile_rows_fn<RowI8>(s->ld / 4, pairs);
+    case PH_ROWS_FP4: return labeled_tile_rows_fn<RowFP4>(s->ld / 4, pairs);
     default: return nullptr;
   }
 }

@@ -170,6 +170,7 @@ static PhListRadiusFn list_radius_scan_fn(const phnsw_store *s) {
     case PH_ROWS_F16: return list_radius_rows_fn<DistF16>(s->ld / 4);
     case PH_ROWS_I8: return list_radius_rows_fn<DistI8>(s->ld / 4);
     case PH_ROWS_I8Q: return list_radius_rows_fn<DistI8Q>(s->ld / 4);
+    case PH_ROWS_FP4: return list_radius_rows_fn<DistFP4>(s->ld / 4);
     default: return list_radius_rows_fn<DistF32>(s->ld / 4);
   }
 }

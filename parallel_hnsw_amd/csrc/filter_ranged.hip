@@ -151,6 +151,7 @@ static PhRangedFn ranged_scan_fn(const phnsw_store *s) {
     case PH_ROWS_F16: return ranged_rows_fn<DistF16>(s->ld / 4);
     case PH_ROWS_I8: return ranged_rows_fn<DistI8>(s->ld / 4);
     case PH_ROWS_I8Q: return ranged_rows_fn<DistI8Q>(s->ld / 4);
+    case PH_ROWS_FP4: return ranged_rows_fn<DistFP4>(s->ld / 4);
     default: return ranged_rows_fn<DistF32>(s->ld / 4);
   }
 }

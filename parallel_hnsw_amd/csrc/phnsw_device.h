@@ -118,7 +118,8 @@ __device__ __forceinline__ void chain_partial2(const float4 (&x)[NV], const ph_f
 }
 
 // How a stored row reaches the chain: a lane's chunk lane + 64k is four components -- 16 bytes of an f32 row, 8 bytes
-// of a half-precision row (f16 store), 4 bytes of an int8 row (i8 store).  Halves widen to f32 with v_cvt_f32_f16, which
+// of a half-precision row (f16 store), 4 bytes of an int8 row (i8 store), 2 code bytes and a scale byte of an MXFP4 row
+// (fp4 store).  Halves widen to f32 with v_cvt_f32_f16, which
 // is exact (subnormals included: the kernels run with f16 denormals on, the compiler's default); an int8 code becomes
 // scale * (float)code with the row's scale (ph_i8_dequant: one rounding, the value phnsw_store_read returns).  Either
 // way the chain sees the f32 values a row of the converted store would hold and everything behind the load is shared.
@@ -196,6 +197,60 @@ __device__ __forceinline__ float wave_max(float m) {
   for (int sft = 32; sft >= 1; sft >>= 1) m = fmaxf(m, __shfl_xor(m, sft));
   return m;
 }
+
+// ------------------------------------------------------------------ fp4: OCP MXFP4 rows
+// A component is a 4-bit E2M1 code (sign << 3 | magnitude, magnitudes 0, 0.5, 1, 1.5, 2, 3, 4, 6); block b of a row,
+// components [32b, 32b + 32), shares one E8M0 byte e8 and a component decodes to +-grid[code & 7] * 2^(e8 - 127), which
+// f32 holds exactly.  e8 stays in [2, 252], so every decoded value is zero or a normal f32.
+//
+// Device layout of a row (ph_fp4_stride bytes, a multiple of 16): sections of 256 chunks (1024 components), each 32
+// scale bytes followed by its code bytes in component order (512 in a full section).  A lane of the distance kernels
+// owns chunks lane + 64k; a block is the chunks of eight consecutive lanes of one k, so inside a section the scale of
+// chunk c sits at byte 4 * ((c & 63) >> 3) + ((c >> 6) & 3): the (up to) four scales a lane needs of a section are the
+// bytes of ONE aligned dword, eight lane groups one 32-byte run.  Neither offset depends on the row's length.
+__host__ __device__ __forceinline__ uint32_t ph_fp4_code_at(uint32_t c) { return 544u * (c >> 8) + 32u + 2u * (c & 255u); }
+__host__ __device__ __forceinline__ uint32_t ph_fp4_scale_at(uint32_t c) {
+  return 544u * (c >> 8) + 4u * ((c & 63u) >> 3) + ((c >> 6) & 3u);
+}
+// THE quantiser of the fp4 store, integer arithmetic alone (no rounding or denormal mode takes part).
+// maxabs_bits: the largest |x| of the block as f32 bits.  e8 = floor(log2 max) - 2 + 127, clamped to [2, 252].
+__device__ __forceinline__ uint32_t ph_fp4_e8(uint32_t maxabs_bits) {
+  return (uint32_t)min(max((int)(maxabs_bits >> 23) - 2, 2), 252);
+}
+// the code of x (f32 bits) under e8: |y| = |x| * 2^(127 - e8) rounded to the grid, nearest, ties to the code with an even
+// mantissa bit (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4), saturating at 6; no -0.
+// With |x| = M * 2^(E - 150), 4|y| = M / 2^sh, sh = e8 + 21 - E >= 19: z = twice its integer part plus a sticky bit
+// orders 4|y| against every threshold exactly.
+__device__ __forceinline__ uint32_t ph_fp4_quant(uint32_t xbits, uint32_t e8) {
+  const uint32_t ef = (xbits >> 23) & 0xFFu;
+  const uint32_t M = (xbits & 0x7FFFFFu) | (ef ? 0x800000u : 0u);
+  const uint32_t sh = min(e8 + 21u - max(ef, 1u), 31u);
+  const uint32_t z = 2u * (M >> sh) + ((M & ((1u << sh) - 1u)) ? 1u : 0u);
+  const uint32_t m = (z > 2u) + (z >= 6u) + (z > 10u) + (z >= 14u) + (z > 20u) + (z >= 28u) + (z > 40u);
+  return m ? ((xbits >> 28) & 8u) | m : 0u;
+}
+// THE decoded components of an fp4 store: byte `B` (0 / 1) of `codes` holds two codes, low nibble first; `scale` is
+// 2^(e8 - 127) as an f32.  One v_cvt_scalef32_pk_f32_fp4: the conversion and the block scale in one instruction.
+template <int B>
+__device__ __forceinline__ ph_f2 ph_fp4_decode2(uint32_t codes, float scale) {
+  return __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(codes, scale, B);
+}
+// A chunk of four components is two code bytes; the chunk word carries its block's scale byte above them (bits 16-23),
+// so widen needs nothing beside the word and the policy interface stays as it is.
+struct RowFP4 : RowBase<uint32_t> {
+  typedef RowNoAux aux;
+  static constexpr int KIND = PH_ROWS_FP4;
+  static __device__ __forceinline__ aux row_aux(const chunk *) { return aux(); }
+  static __device__ __forceinline__ chunk load(const chunk *row, uint32_t c) {
+    const uint8_t *b = (const uint8_t *)row;
+    return (uint32_t) * (const uint16_t *)(b + ph_fp4_code_at(c)) | ((uint32_t)b[ph_fp4_scale_at(c)] << 16);
+  }
+  static __device__ __forceinline__ float4 widen(const uint32_t &v, const aux &) {
+    const float s = __uint_as_float((v & 0x00FF0000u) << 7);  // e8 << 23
+    const ph_f2 lo = ph_fp4_decode2<0>(v, s), hi = ph_fp4_decode2<1>(v, s);
+    return make_float4(lo[0], lo[1], hi[0], hi[1]);
+  }
+};
 
 template <int NV, int U, bool EXACT, bool L2, class R>
 __device__ __forceinline__ void rows_partial_impl(const typename R::chunk *const (&row)[U], const float4 (&q)[NV],
@@ -399,7 +454,7 @@ __device__ __forceinline__ float batch_distances(const void *__restrict__ vecs, 
 
 // ------------------------------------------------------------------ distance policies
 // The traversal kernels are written once and instantiated per policy:
-//   DistF32 / DistF16 / DistI8<NV>: the query in registers, candidates = stored rows (wave per row, 4 in flight)
+//   DistF32 / DistF16 / DistI8 / DistFP4<NV>: the query in registers, candidates = stored rows (wave per row, 4 in flight)
 //   DistI8Q<NV>: the query as int8 codes in registers, candidates = int8 rows, integer dot products
 //   DistPQ:      product-quantised store: a per-query table T[m][ksub] in LDS
 //                (T[j][k] = <q_sub_j, c_jk> or |q_sub_j - c_jk|^2), candidates = u8 code
@@ -454,13 +509,15 @@ struct DistRows {
                                      lane);
   }
 };
-// the three row stores: derived structs, not aliases, so that the kernels keep the names they are profiled under
+// the row stores: derived structs, not aliases, so that the kernels keep the names they are profiled under
 template <int NV, int U = 4>
 struct DistF32 : DistRows<NV, U, RowF32> {};
 template <int NV, int U = 4>
 struct DistF16 : DistRows<NV, U, RowF16> {};
 template <int NV, int U = 4>
 struct DistI8 : DistRows<NV, U, RowI8> {};
+template <int NV, int U = 4>
+struct DistFP4 : DistRows<NV, U, RowFP4> {};
 
 // ------------------------------------------------------------------ i8q: int8 rows, int8 query, integer dot products
 // THE distance of an i8q store: the two scales multiplied first, then the exact integer dot product (converted with

@@ -60,7 +60,8 @@ struct PhLayerHost {
 };
 
 // How a store keeps its vectors.  The three row kinds are searched by the same kernels through a row policy
-// (RowF32 / RowF16 / RowI8, phnsw_device.h); f16, i8 and i8q are the converted, search-only stores of rowstore.hip.
+// (RowF32 / RowF16 / RowI8 / RowFP4, phnsw_device.h); f16, i8, i8q and fp4 are the converted, search-only stores of
+// rowstore.hip.
 enum PhRowKind : int {
   PH_ROWS_F32 = 0,    // [n][ld] f32
   PH_ROWS_F16,        // [n][ld] IEEE binary16 in component order: rows start on 8-byte boundaries
@@ -69,19 +70,24 @@ enum PhRowKind : int {
   PH_ROWS_PQ_SHARED,  // u16 codes over one shared codebook (pq.hip)
   PH_ROWS_I8Q,        // the bytes of PH_ROWS_I8; a distance quantises the query too and takes integer dot products (DistI8Q)
   PH_ROWS_BITS,       // n rows of 32 * ph_chunk_count(ld / 4) bytes: one sign bit per component (bits_plan.h, DistBits)
+  PH_ROWS_FP4,        // OCP MXFP4: E2M1 codes, one E8M0 scale per 32 components, in sections of 256 chunks (ph_fp4_stride)
 };
-static inline bool ph_rows_converted(int kind) { return kind == PH_ROWS_F16 || kind == PH_ROWS_I8 || kind == PH_ROWS_I8Q; }
+static inline bool ph_rows_converted(int kind) {
+  return kind == PH_ROWS_F16 || kind == PH_ROWS_I8 || kind == PH_ROWS_I8Q || kind == PH_ROWS_FP4;
+}
 // the 1-bit sign store is NOT one of the converted kinds: it has no f32 view of a row in registers, so the dense tables,
 // the split descent, the cells and the filtered / exact kernels written over a row policy do not serve it
 static inline bool ph_rows_bits(int kind) { return kind == PH_ROWS_BITS; }
 static inline bool ph_rows_i8_layout(int kind) { return kind == PH_ROWS_I8 || kind == PH_ROWS_I8Q; }  // scale + int8 codes
 static inline const char *ph_rows_name(int kind) {
-  static const char *const names[] = {"f32", "f16", "i8", "product-quantised", "shared-codebook product-quantised", "i8q", "bits"};
+  static const char *const names[] = {"f32", "f16", "i8", "product-quantised", "shared-codebook product-quantised", "i8q", "bits", "fp4"};
   return names[kind];
 }
 // float4 chunks a lane holds of a row of nv4 float4s: the three shapes the row kernels are instantiated for (0: none;
 // a launch switches on this value, one case per instance)
 static inline int ph_chunk_count(uint32_t nv4) { return nv4 <= 64 ? 1 : (nv4 <= 192 ? 3 : (nv4 <= 384 ? 6 : 0)); }
+// bytes of an fp4 row of ld components: per section of 1024 components 32 scale bytes and its codes (phnsw_device.h)
+static inline uint32_t ph_fp4_stride(uint32_t ld) { return (ld / 2u + 32u * ((ld / 4u + 255u) / 256u) + 15u) & ~15u; }
 int ph_dim_unsupported(uint32_t dim);  // sets "dim unsupported (max 1536)", returns PHNSW_E_UNSUPPORTED (misc.hip)
 // where the rows of a row kind are: one base pointer, one stride in bytes
 struct PhRows {
@@ -802,7 +808,7 @@ int ph_cell_order_device(const uint32_t *keys, uint32_t n, uint32_t bins, uint32
 // counting sort of the queries by it into ws.oorder; points b.order at it and sets b.table_by_query
 int ph_tiny_table_order(PhWorkspace &ws, PhSearchArgs &b, const uint32_t *pos, uint32_t bins, hipStream_t stream);
 
-// a search-only row store (f16, i8 or i8q): searched like the f32 store, its rows converted to f32 where a GEMM or a host reads them
+// a search-only row store (f16, i8, i8q or fp4): searched like the f32 store, its rows converted to f32 where a GEMM or a host reads them
 static inline bool ph_store_converted(const phnsw_store *s) { return ph_rows_converted(s->kind); }
 // the other kinds.  `rows` / `codes` / `codes16` are non-null exactly on an f32 / PQ / shared-codebook PQ store (every
 // creator allocates n > 0 rows); a pointer is still what a hipFree or an ownership rule asks
@@ -873,7 +879,7 @@ static inline PhDistArgs ph_dist_args(const phnsw_store *s) {
 }
 // bytes of one stored row as the search gathers it
 static inline uint32_t ph_row_bytes(const phnsw_store *s) { return ph_store_rows(s).stride; }
-// an f16, i8, i8q or bits store serves searches only: every other entry point refuses it by name
+// an f16, i8, i8q, fp4 or bits store serves searches only: every other entry point refuses it by name
 static inline int ph_search_only_unsupported(const phnsw_store *s, const char *call) {
   if (!s || !(ph_store_converted(s) || ph_store_bits(s))) return 0;
   ph_set_error("%s: not supported on an %s store or an index over one (search-only; use the f32 store)", call,

@@ -833,7 +833,7 @@ extern "C" int phnsw_pq_search_batch_device(const phnsw_index *ix, const phnsw_s
                                 status_dev, stream);
 } catch (...) { return ph_caught(); }
 
-// the f16 / i8 / i8q entry points: `kind` is the converted store the call serves
+// the f16 / i8 / i8q / fp4 / bits entry points: `kind` is the store the call serves
 static int converted_check(const char *call, int kind, const phnsw_index *ix, const phnsw_store *full,
                            const phnsw_search_params *sp, uint64_t nq, uint64_t k) {
   if (rerank_check(1u << kind, ix, full, sp, nq, k)) return 0;
@@ -917,4 +917,17 @@ extern "C" int phnsw_bits_search_batch(const phnsw_index *ix, const phnsw_store 
                                        const phnsw_search_params *sp, uint64_t k, uint64_t *out_ids, float *out_d,
                                        uint64_t *out_len) try {
   return converted_search_host("phnsw_bits_search_batch", PH_ROWS_BITS, ix, full, queries, nq, sp, k, out_ids, out_d, out_len);
+} catch (...) { return ph_caught(); }
+// ... and on an fp4 store
+extern "C" int phnsw_fp4_search_batch_device(const phnsw_index *ix, const phnsw_store *full, const float *queries_dev,
+                                             uint32_t ldq, uint64_t nq, const phnsw_search_params *sp, uint64_t k,
+                                             uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                             uint32_t *out_stats_dev, uint32_t *status_dev, void *stream) try {
+  return converted_search_device("phnsw_fp4_search_batch_device", PH_ROWS_FP4, ix, full, queries_dev, ldq, nq, sp, k, out_ids_dev,
+                                out_d_dev, out_len_dev, out_stats_dev, status_dev, stream);
+} catch (...) { return ph_caught(); }
+extern "C" int phnsw_fp4_search_batch(const phnsw_index *ix, const phnsw_store *full, const float *queries, uint64_t nq,
+                                      const phnsw_search_params *sp, uint64_t k, uint64_t *out_ids, float *out_d,
+                                      uint64_t *out_len) try {
+  return converted_search_host("phnsw_fp4_search_batch", PH_ROWS_FP4, ix, full, queries, nq, sp, k, out_ids, out_d, out_len);
 } catch (...) { return ph_caught(); }

@@ -1,10 +1,10 @@
-// Converted row stores: the rows of an f32 store in a narrower format, searched through a row policy (RowF16 / RowI8,
-// phnsw_device.h) by the kernels of the f32 store.
+// Converted row stores: the rows of an f32 store in a narrower format, searched through a row policy (RowF16 / RowI8 /
+// RowFP4, phnsw_device.h) by the kernels of the f32 store.
 //
 // The contract, whatever the format: a distance on a converted store is the f32 chain on the rows R::widen makes of
 // it, so a search equals, bit for bit, the f32 search over the store phnsw_store_read returns.  A converted store
 // serves searches and distance batches only (ph_search_only_unsupported names everything else).  Everything here but
-// the two conversion kernels is written once over the policy.
+// the conversion kernels is written once over the policy.
 //
 // f16: every component rounded to IEEE binary16 (round to nearest even, ph_f32_to_f16_bits), [n][ld] halves in
 // component order: a row starts on an 8-byte boundary and a lane's chunk of four components is one 8-byte load.
@@ -21,6 +21,11 @@
 // i8q: the rows of an i8 store, byte for byte (same kernel, same layout, same phnsw_i8_read and phnsw_store_read); what
 // differs is the distance, which quantises the query with the rows' own quantiser and takes integer dot products
 // (DistI8Q, phnsw_device.h).  Dot-product metrics only: the Euclidean distance would need the rows' norms.
+//
+// fp4: OCP MXFP4 -- every block of 32 components quantised on its own to 4-bit E2M1 codes under one E8M0 scale byte
+// (ph_fp4_e8 / ph_fp4_quant, phnsw_device.h, which also has the row layout); a component decodes to
+// +-grid[code & 7] * 2^(e8 - 127), exact in f32 (ph_fp4_decode2).  ld / 2 code bytes and 32 scale bytes per 1024
+// components a row, 416 bytes at 768 dimensions.
 //
 // bits: one sign bit per component (bits_plan.h has the layout rules: bit j = the component is below zero, component j
 // in bit j & 31 of word j >> 5, rows of 32 * NV bytes, padding bits 0).  NOT a converted store in the sense above: no
@@ -111,6 +116,49 @@ __global__ void ph_bits_convert_kernel(const float *__restrict__ rows, uint32_t 
   if (mine) atomicOr(bad, 1u);
 }
 
+// one wave per row, lane l takes chunks l + 64k as the distance kernels do: a block of 32 components is then the chunks
+// of the eight consecutive lanes of one k, and its maximum a three-step butterfly among them.  A k leaves as one 128-byte
+// run of code half-words; the four scale bytes of a lane group gather in a dword that its first lane stores, 32 bytes
+// a section.  Components at or past dim count as 0 (their block scale is that of the components before them, or 2).  A
+// NaN or an infinite component raises the flag.
+__global__ void ph_fp4_convert_kernel(const float *__restrict__ rows, uint32_t ld, uint32_t dim, uint64_t n,
+                                      uint8_t *__restrict__ out, uint32_t stride, uint32_t *bad) {
+  const uint32_t lane = threadIdx.x & 63u, wpb = blockDim.x / 64u, nv4 = ld / 4u;
+  bool mine = false;
+  for (uint64_t r = (uint64_t)blockIdx.x * wpb + threadIdx.x / 64u; r < n; r += (uint64_t)gridDim.x * wpb) {
+    const float4 *src = (const float4 *)(rows + r * ld);
+    uint8_t *dst = out + r * stride;
+    for (uint32_t s0 = 0; s0 < nv4; s0 += 256u) {  // a section
+      uint32_t sw = 0x02020202u;                   // a block without a component: e8 = 2, as a block of zeros
+      for (uint32_t k = 0; k < 4u && s0 + 64u * k < nv4; k++) {  // (wave-uniform bounds)
+        const uint32_t c = s0 + 64u * k + lane;
+        uint32_t x[4] = {0u, 0u, 0u, 0u};
+        if (c < nv4) {
+          const float4 v = src[c];
+          const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+          for (uint32_t j = 0; j < 4u; j++) x[j] = 4u * c + j < dim ? __float_as_uint(e[j]) : 0u;
+        }
+        uint32_t mb = 0u;
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; j++) {
+          mine |= (x[j] & 0x7F800000u) == 0x7F800000u;
+          mb = max(mb, x[j] & 0x7FFFFFFFu);  // non-negative floats order as their bits do
+        }
+#pragma unroll
+        for (int sft = 1; sft <= 4; sft <<= 1) mb = max(mb, (uint32_t)__shfl_xor((int)mb, sft));
+        const uint32_t e8 = ph_fp4_e8(mb);
+        const uint32_t w = ph_fp4_quant(x[0], e8) | (ph_fp4_quant(x[1], e8) << 4) | (ph_fp4_quant(x[2], e8) << 8) |
+                           (ph_fp4_quant(x[3], e8) << 12);
+        if (c < nv4) *(uint16_t *)(dst + ph_fp4_code_at(c)) = (uint16_t)w;
+        sw = (sw & ~(0xFFu << (8u * k))) | (e8 << (8u * k));
+      }
+      if ((lane & 7u) == 0u) *(uint32_t *)(dst + ph_fp4_scale_at(s0 + lane)) = sw;
+    }
+  }
+  if (mine) atomicOr(bad, 1u);
+}
+
 // rows [first, first + count) of a bits store as a dense [count][dim] array of +1.0f (bit 0) / -1.0f (bit 1)
 __global__ void ph_bits_read_kernel(const uint32_t *__restrict__ words, uint32_t stride_words, uint32_t dim, uint64_t first,
                                     uint64_t count, float *__restrict__ out) {
@@ -162,8 +210,11 @@ static int gather_rows(const phnsw_store *s, const uint32_t *ids_dev, uint32_t f
 int ph_converted_gather_rows(const phnsw_store *s, const uint32_t *ids_dev, uint32_t first, uint32_t cnt, float *out_dev) {
   if (cnt == 0) return 0;
   if (int rc = ph_bits_unsupported(s, "locality cells")) return rc;  // (ph_layer_wants_cells is false for the kind)
-  return s->kind == PH_ROWS_F16 ? gather_rows<RowF16>(s, ids_dev, first, cnt, out_dev)
-                                : gather_rows<RowI8>(s, ids_dev, first, cnt, out_dev);
+  switch (s->kind) {
+    case PH_ROWS_F16: return gather_rows<RowF16>(s, ids_dev, first, cnt, out_dev);
+    case PH_ROWS_FP4: return gather_rows<RowFP4>(s, ids_dev, first, cnt, out_dev);
+    default: return gather_rows<RowI8>(s, ids_dev, first, cnt, out_dev);
+  }
 }
 
 template <class R>
@@ -204,7 +255,11 @@ static int bits_store_read(const phnsw_store *s, uint64_t first, uint64_t count,
 }
 int ph_converted_store_read(const phnsw_store *s, uint64_t first, uint64_t count, float *out) {
   if (ph_store_bits(s)) return bits_store_read(s, first, count, out);
-  return s->kind == PH_ROWS_F16 ? store_read<RowF16>(s, first, count, out) : store_read<RowI8>(s, first, count, out);
+  switch (s->kind) {
+    case PH_ROWS_F16: return store_read<RowF16>(s, first, count, out);
+    case PH_ROWS_FP4: return store_read<RowFP4>(s, first, count, out);
+    default: return store_read<RowI8>(s, first, count, out);
+  }
 }
 
 // `name`: the entry point, for its messages.  The allocation holds at least one row, so that an empty store has a
@@ -227,7 +282,7 @@ static int create_converted(const char *name, const phnsw_store *full, int kind,
     ph_set_error("%s: the Euclidean metric is not supported on an i8q store (dot-product metrics only)", name);
     return PHNSW_E_UNSUPPORTED;
   }
-  if (kind == PH_ROWS_BITS && !ph_chunk_count(full->ld / 4)) return ph_dim_unsupported(full->dim);
+  if ((kind == PH_ROWS_BITS || kind == PH_ROWS_FP4) && !ph_chunk_count(full->ld / 4)) return ph_dim_unsupported(full->dim);
   PH_HIP(hipSetDevice(full->device));
   phnsw_store *s = new phnsw_store();
   s->device = full->device;
@@ -237,6 +292,7 @@ static int create_converted(const char *name, const phnsw_store *full, int kind,
   s->ld = full->ld;
   s->packed_stride = kind == PH_ROWS_BITS  ? ph_bits_stride(ph_chunk_count(full->ld / 4))
                      : kind == PH_ROWS_F16 ? full->ld * 2u
+                     : kind == PH_ROWS_FP4 ? ph_fp4_stride(full->ld)
                                            : ((4u + full->ld + 15u) & ~15u);
   s->metric = full->metric;
   s->rows = nullptr;
@@ -245,6 +301,8 @@ static int create_converted(const char *name, const phnsw_store *full, int kind,
   hipError_t e = hipMalloc(&s->packed, (size_t)std::max<uint64_t>(s->n, 1) * s->packed_stride);
   if (e == hipSuccess) e = hipMalloc(&bad, 4);
   if (e == hipSuccess) e = hipMemset(bad, 0, 4);
+  // (an fp4 row has bytes no lane writes: behind the codes of its last section)
+  if (e == hipSuccess && kind == PH_ROWS_FP4) e = hipMemset(s->packed, 0, (size_t)std::max<uint64_t>(s->n, 1) * s->packed_stride);
   if (e == hipSuccess && s->n) {
     if (kind == PH_ROWS_F16) {
       const uint64_t total = s->n * (uint64_t)s->ld;
@@ -253,6 +311,9 @@ static int create_converted(const char *name, const phnsw_store *full, int kind,
     } else if (kind == PH_ROWS_BITS) {
       hipLaunchKernelGGL(ph_bits_convert_kernel, dim3((uint32_t)std::min<uint64_t>((s->n + 3) / 4, 1u << 16)), dim3(256), 0, 0,
                          full->rows, full->ld, full->dim, s->n, (uint32_t *)s->packed, s->packed_stride / 4u, bad);
+    } else if (kind == PH_ROWS_FP4) {
+      hipLaunchKernelGGL(ph_fp4_convert_kernel, dim3((uint32_t)std::min<uint64_t>((s->n + 3) / 4, 1u << 16)), dim3(256), 0, 0,
+                         full->rows, full->ld, full->dim, s->n, (uint8_t *)s->packed, s->packed_stride, bad);
     } else {
       hipLaunchKernelGGL(ph_i8_convert_kernel, dim3((uint32_t)std::min<uint64_t>((s->n + 3) / 4, 1u << 16)), dim3(256), 0, 0,
                          full->rows, full->ld, full->dim, s->n, (uint8_t *)s->packed, s->packed_stride, bad);
@@ -263,7 +324,10 @@ static int create_converted(const char *name, const phnsw_store *full, int kind,
   if (bad) hipFree(bad);
   int rc = 0;
   if (e != hipSuccess)
-    rc = ph_hip_fail(e, kind == PH_ROWS_F16 ? "f16 store conversion" : (kind == PH_ROWS_BITS ? "bits store conversion" : "i8 store conversion"),
+    rc = ph_hip_fail(e, kind == PH_ROWS_F16    ? "f16 store conversion"
+                        : kind == PH_ROWS_BITS ? "bits store conversion"
+                        : kind == PH_ROWS_FP4  ? "fp4 store conversion"
+                                               : "i8 store conversion",
                      __FILE__, __LINE__);
   else if (h_bad) {
     if (kind == PH_ROWS_F16)
@@ -289,6 +353,10 @@ extern "C" int phnsw_store_create_i8(const phnsw_store *full, phnsw_store **out)
 } catch (...) { return ph_caught(); }
 extern "C" int phnsw_store_create_i8q(const phnsw_store *full, phnsw_store **out) try {
   return create_converted("phnsw_store_create_i8q", full, PH_ROWS_I8Q, out);
+} catch (...) { return ph_caught(); }
+
+extern "C" int phnsw_store_create_fp4(const phnsw_store *full, phnsw_store **out) try {
+  return create_converted("phnsw_store_create_fp4", full, PH_ROWS_FP4, out);
 } catch (...) { return ph_caught(); }
 
 extern "C" int phnsw_store_create_bits(const phnsw_store *full, phnsw_store **out) try {
@@ -319,5 +387,33 @@ extern "C" int phnsw_i8_read(const phnsw_store *s, int8_t *codes, float *scales)
   const uint8_t *rows = (const uint8_t *)s->packed;
   PH_HIP(hipMemcpy2D(scales, 4, rows, s->packed_stride, 4, s->n, hipMemcpyDeviceToHost));
   PH_HIP(hipMemcpy2D(codes, s->dim, rows + 4, s->packed_stride, s->dim, s->n, hipMemcpyDeviceToHost));
+  return 0;
+} catch (...) { return ph_caught(); }
+
+// the public layout of an fp4 store, whatever the device layout: codes [n][ceil(dim / 2)], component j in nibble j & 1
+// of byte j >> 1; scales [n][ceil(dim / 32)], the E8M0 byte of every block
+extern "C" int phnsw_fp4_read(const phnsw_store *s, uint8_t *codes, uint8_t *scales) try {
+  if (!s || s->kind != PH_ROWS_FP4 || !codes || !scales) {
+    ph_set_error("phnsw_fp4_read: needs an fp4 store and both outputs");
+    return PHNSW_E_INVALID;
+  }
+  if (s->n == 0) return 0;
+  PH_HIP(hipSetDevice(s->device));
+  const uint8_t *rows = (const uint8_t *)s->packed;
+  const uint32_t cb = (s->dim + 1u) / 2u, nb = (s->dim + 31u) / 32u, sections = (s->ld / 4u + 255u) / 256u;
+  std::vector<uint8_t> heads((size_t)s->n * 32u * sections);
+  for (uint32_t sec = 0; sec < sections; sec++) {
+    const uint32_t at = 256u * sec;  // the section's first chunk
+    if (512u * sec < cb)
+      PH_HIP(hipMemcpy2D(codes + 512u * sec, cb, rows + ph_fp4_code_at(at), s->packed_stride, std::min(512u, cb - 512u * sec), s->n,
+                         hipMemcpyDeviceToHost));
+    PH_HIP(hipMemcpy2D(heads.data() + 32u * sec, 32u * sections, rows + ph_fp4_scale_at(at), s->packed_stride, 32, s->n,
+                       hipMemcpyDeviceToHost));
+  }
+  for (uint64_t r = 0; r < s->n; r++)
+    for (uint32_t b = 0; b < nb; b++) {  // block b begins at chunk 8b
+      const uint32_t c = 8u * b, sec = c >> 8;
+      scales[r * nb + b] = heads[(r * sections + sec) * 32u + (ph_fp4_scale_at(c) - ph_fp4_scale_at(256u * sec))];
+    }
   return 0;
 } catch (...) { return ph_caught(); }

@@ -125,7 +125,7 @@ struct PhKernelChoice {
 };
 // (not PH_KF_ROWS_BITS: no LDS visited table, no radius twin)
 static bool kf_rows(PhKernelFamily f) {
-  return f == PH_KF_ROWS_F32 || f == PH_KF_ROWS_F16 || f == PH_KF_ROWS_I8 || f == PH_KF_ROWS_I8Q;
+  return f == PH_KF_ROWS_F32 || f == PH_KF_ROWS_F16 || f == PH_KF_ROWS_I8 || f == PH_KF_ROWS_I8Q || f == PH_KF_ROWS_FP4;
 }
 
 // grows: threshold_nn (the queue may double, so it keeps 512 slots at ef <= 256); instr: out_index is set.  Reads
@@ -179,6 +179,7 @@ static PhKernelChoice pick_unfiltered_kernel(const phnsw_store *s, uint32_t ef_m
     case PH_ROWS_F16: k.family = PH_KF_ROWS_F16; k.fn = pick_kernel_rows<DistF16, false>(k.capc, k.nv); break;
     case PH_ROWS_I8: k.family = PH_KF_ROWS_I8; k.fn = pick_kernel_rows<DistI8, false>(k.capc, k.nv); break;
     case PH_ROWS_I8Q: k.family = PH_KF_ROWS_I8Q; k.fn = pick_kernel_rows<DistI8Q, false>(k.capc, k.nv); break;
+    case PH_ROWS_FP4: k.family = PH_KF_ROWS_FP4; k.fn = pick_kernel_rows<DistFP4, false>(k.capc, k.nv); break;
     default: k.family = PH_KF_ROWS_F32; k.fn = pick_kernel_rows<DistF32, false>(k.capc, k.nv); break;
   }
   return k;

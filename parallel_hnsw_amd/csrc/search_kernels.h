@@ -1260,6 +1260,7 @@ enum PhKernelFamily {
   PH_KF_LATENCY,    // small batches over f32 rows
   PH_KF_INSTR,      // Hnsw::search_instrumented over f32 rows
   PH_KF_ROWS_BITS,  // throughput kernels over 1-bit sign rows (search_bits.hip; no filtered, collecting or radius twin)
+  PH_KF_ROWS_FP4,   // throughput kernels over MXFP4 rows, every twin the other row families have
 };
 
 // the register-table PQ policy (pick_pqr): 32 / 64 / 96 / 128 sub-spaces, queues of up to 512 entries
@@ -1303,7 +1304,7 @@ static ph_search_fn pick_kernel_lat(int capc, int nv) {
   return nullptr;
 }
 
-// The throughput kernels of a row store, D = DistF32 / DistF16 / DistI8 / DistI8Q: the same set shape for shape -- same
+// The throughput kernels of a row store, D = DistF32 / DistF16 / DistI8 / DistI8Q / DistFP4: the same set shape for shape -- same
 // queues, same LDS visited table, same rows in flight (DistI8Q too: 16 rows in flight would cost its headline kernel a
 // wave per SIMD, 144 VGPRs against 112, profiles/i8q).  (There are no latency (U == 0), instrumented or big-queue kernels over
 // converted rows: batches of any size run these, and the calls behind the others refuse a converted store.)
@@ -1340,6 +1341,7 @@ static ph_search_fn pick_kernel_family(int family, int capc, int nv, int pqr_m, 
     case PH_KF_ROWS_F16: return pick_kernel_rows<DistF16, FILT>(capc, nv);
     case PH_KF_ROWS_I8: return pick_kernel_rows<DistI8, FILT>(capc, nv);
     case PH_KF_ROWS_I8Q: return pick_kernel_rows<DistI8Q, FILT>(capc, nv);
+    case PH_KF_ROWS_FP4: return pick_kernel_rows<DistFP4, FILT>(capc, nv);
     case PH_KF_PQ_TABLE: return pick_kernel_pqt<FILT>(capc, pq_global);
     case PH_KF_PQ_REG: return pick_kernel_pqr<FILT>(capc, pqr_m);
     case PH_KF_PQ_SHARED: return pick_kernel_pqs<FILT>(capc, nv);

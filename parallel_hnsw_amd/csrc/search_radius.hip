@@ -32,6 +32,7 @@ ph_search_fn ph_pick_radius_kernel(int family, int nv) {
     case PH_KF_ROWS_F16: return pick_radius_rows<DistF16>(nv);
     case PH_KF_ROWS_I8: return pick_radius_rows<DistI8>(nv);
     case PH_KF_ROWS_I8Q: return pick_radius_rows<DistI8Q>(nv);
+    case PH_KF_ROWS_FP4: return pick_radius_rows<DistFP4>(nv);
     default: return nullptr;
   }
 }

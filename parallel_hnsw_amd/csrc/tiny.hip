@@ -157,8 +157,8 @@ __device__ __forceinline__ void tiny_tile(const float4 *lds, const ph_f2 (&qv)[Q
   if constexpr (QT == 4) V += __shfl_xor(V, 1);
 }
 
-// R: how the stored rows are read (RowF32, or RowF16 / RowI8: the halves of an f16 store widened, the codes of an i8
-// store dequantised, as they are staged, so the tile pass below sees the f32 operands it always saw)
+// R: how the stored rows are read (RowF32, or RowF16 / RowI8 / RowFP4: the halves of an f16 store widened, the codes of
+// an i8 or fp4 store dequantised, as they are staged, so the tile pass below sees the f32 operands it always saw)
 template <int NV, int QT, class R = RowF32>
 __global__ __launch_bounds__(256) void ph_tiny_table_kernel(PhTinyTableArgs a) {
   __shared__ float4 rows_lds[8 * NV * 64];
@@ -294,6 +294,20 @@ __global__ void ph_tiny_pack_kernel(PhTinyPackArgs p) {
   }
   const uint32_t t = ph_rev5(c & 31u), b = (c >> 5) & 1u, k = c >> 6;
   p.out[(((((uint64_t)(r >> 5) * 32u + t) * p.nv + k) * 2u + b) << 5) + (r & 31u)] = v;
+}
+// the stored rows of an fp4 store, packed the same way: a kernel of its own, so that the kind switch above -- and with it
+// the registers of the pack of every other kind -- stays as it was (raw queries go through the kernel above whatever the kind)
+__global__ void ph_tiny_pack_fp4_kernel(PhTinyPackArgs p) {
+  const uint32_t r = blockIdx.x * 32u + threadIdx.x;
+  const uint32_t c = blockIdx.y * 8u + threadIdx.y;  // < 64 * nv
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (r < p.n) v = tiny_pack_stored<RowFP4>(p.rows, p.ids[p.order ? p.order[r] : r], c);
+  const uint32_t t = ph_rev5(c & 31u), b = (c >> 5) & 1u, k = c >> 6;
+  p.out[(((((uint64_t)(r >> 5) * 32u + t) * p.nv + k) * 2u + b) << 5) + (r & 31u)] = v;
+}
+static void tiny_pack(const PhTinyPackArgs &k, hipStream_t stream) {
+  const bool fp4 = k.rows.kind == PH_ROWS_FP4 && !k.queries;
+  hipLaunchKernelGGL(fp4 ? ph_tiny_pack_fp4_kernel : ph_tiny_pack_kernel, dim3(k.n_pad / 32u, 8u * k.nv), dim3(32, 8), 0, stream, k);
 }
 
 struct PhTinyMfmaArgs {
@@ -829,14 +843,14 @@ static int tiny_table(const phnsw_index *ix, PhWorkspace &ws, const PhDistArgs &
     k.n = npos;
     k.n_pad = qtiles * 64u;
     k.out = ws.tiny_pq;
-    hipLaunchKernelGGL(ph_tiny_pack_kernel, dim3(k.n_pad / 32u, 8u * (uint32_t)nv), dim3(32, 8), 0, stream, k);
+    tiny_pack(k, stream);
     k.queries = nullptr;
     k.ids = tnodes;
     k.order = nullptr;
     k.n = tn;
     k.n_pad = ntiles * 64u;
     k.out = ws.tiny_pn;
-    if (!pn_kept) hipLaunchKernelGGL(ph_tiny_pack_kernel, dim3(k.n_pad / 32u, 8u * (uint32_t)nv), dim3(32, 8), 0, stream, k);
+    if (!pn_kept) tiny_pack(k, stream);
     PH_HIP(hipGetLastError());
     PhTinyMfmaArgs m;
     memset(&m, 0, sizeof(m));
@@ -881,6 +895,7 @@ static int tiny_table(const phnsw_index *ix, PhWorkspace &ws, const PhDistArgs &
     switch (dist.rows.kind) {
       case PH_ROWS_F16: tiny_table_valu<RowF16>(nv, grid, stream, t); break;
       case PH_ROWS_I8: tiny_table_valu<RowI8>(nv, grid, stream, t); break;
+      case PH_ROWS_FP4: tiny_table_valu<RowFP4>(nv, grid, stream, t); break;
       default: tiny_table_valu<RowF32>(nv, grid, stream, t); break;
     }
   }

@@ -834,10 +834,43 @@ class BitStore(VectorStore):
         return out
 
 
+class FP4Store(VectorStore):
+    """OCP MXFP4 view of an f32 VectorStore (phnsw_store_create_fp4): 4-bit E2M1 codes with one power-of-two scale
+    byte per block of 32 components, 416 bytes per 768-component vector.  Distances decode (grid[code] * 2^(e8 - 127),
+    exact in f32) and run the f32 arithmetic, so read() returns exactly the rows the searches see;
+    tests/fp4_reference.py restates quantiser and decoder.  All three metrics.  Search-only, like I8Store"""
+
+    def __init__(self, full):
+        h = C.c_void_p()
+        check(lib().phnsw_store_create_fp4(full._h, C.byref(h)))
+        VectorStore.__init__(self, _handle=h, device=full.device)
+        self.full = full
+
+    @classmethod
+    def from_full(cls, store):
+        return cls(store)
+
+    def _read_fp4(self):
+        codes = np.empty((self.n, (self.dim + 1) // 2), dtype=np.uint8)
+        scales = np.empty((self.n, (self.dim + 31) // 32), dtype=np.uint8)
+        check(lib().phnsw_fp4_read(self._h, _p(codes), _p(scales)))
+        return codes, scales
+
+    def codes(self):
+        """the stored codes [n, ceil(dim / 2)] uint8: component j in nibble j & 1 of byte j >> 1"""
+        return self._read_fp4()[0]
+
+    def scales(self):
+        """the blocks' E8M0 scale bytes [n, ceil(dim / 32)] uint8"""
+        return self._read_fp4()[1]
+
+
 def _reranked_kind(store):
     """the name a converted store's re-ranked search calls carry"""
     if isinstance(store, BitStore):
         return "bits"
+    if isinstance(store, FP4Store):
+        return "fp4"
     return "i8q" if isinstance(store, I8QStore) else ("i8" if isinstance(store, I8Store) else "f16")
 
 
@@ -2395,9 +2428,9 @@ class Hnsw:
             C.c_void_p(out_len), C.c_void_p(out_route or None), C.c_void_p(status), C.c_void_p(stream or None)))
 
     def search_batch_reranked(self, full, queries, sp=None, k=10):
-        """an index over an F16Store, I8Store, I8QStore or BitStore: search it, recompute every result's distance on the
-        f32 store `full`, sort by (distance, id), keep the best k (phnsw_f16_search_batch / phnsw_i8_search_batch /
-        phnsw_i8q_search_batch / phnsw_bits_search_batch)
+        """an index over an F16Store, I8Store, I8QStore, FP4Store or BitStore: search it, recompute every result's distance
+        on the f32 store `full`, sort by (distance, id), keep the best k (phnsw_f16_search_batch / phnsw_i8_search_batch /
+        phnsw_i8q_search_batch / phnsw_fp4_search_batch / phnsw_bits_search_batch)
         -> ids[nq, k] u64, d[nq, k] f32, len[nq]"""
         sp = sp or SearchParameters()
         q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
