@@ -1595,10 +1595,11 @@ int phnsw_i8q_search_batch_device(const phnsw_index *ix, const phnsw_store *full
  * f32 distances: they recompute every candidate on `full`.
  * Served: phnsw_distance_batch, phnsw_index_from_layers (adopt a graph built over the f32 store), phnsw_search_batch,
  * _stored, _topk, _device (no dense tables, no split descent: every layer per hop), phnsw_index_layer_*, the
- * phnsw_last_search_* queries, the destroy calls and the re-ranked pair below.  EVERY other entry point -- every filtered,
- * labelled, ranged, collecting and radius walk, every exact scan and table, phnsw_bruteforce_topk, build / link / improve
- * / promote / extend, phnsw_store_append, serialisation, the PQ constructors, knn / threshold_nn / search_instrumented --
- * returns PHNSW_E_UNSUPPORTED on the host, before any launch, with a message that names the call and "bits". */
+ * phnsw_last_search_* queries, the destroy calls, the re-ranked pair below and the exhaustive scans after it.  EVERY
+ * other entry point -- every filtered, labelled, ranged, collecting and radius walk, every exact scan and table,
+ * phnsw_bruteforce_topk, build / link / improve / promote / extend, phnsw_store_append, serialisation, the PQ
+ * constructors, knn / threshold_nn / search_instrumented -- returns PHNSW_E_UNSUPPORTED on the host, before any launch,
+ * with a message that names the call and "bits". */
 int phnsw_store_create_bits(const phnsw_store *full, phnsw_store **out);
 /* the sign bits [n][ceil(dim / 32)] of a bits store: component j is bit j & 31 of word j >> 5 (the public layout,
  * whatever the stride of the rows on the device) */
@@ -1613,6 +1614,35 @@ int phnsw_bits_search_batch_device(const phnsw_index *ix, const phnsw_store *ful
                                    uint32_t ldq, uint64_t nq, const phnsw_search_params *sp, uint64_t k,
                                    uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
                                    uint32_t *out_stats_dev, uint32_t *status_dev, void *stream);
+
+/* ---- exhaustive Hamming scan over a bits store, with f32 re-rank (scan_bits.hip) ----
+ * The usual use of sign codes: no graph, every row 0 .. n - 1 of the bits store is a candidate (no index, no filter, no
+ * exclude).  Queries are raw f32 rows only; each is reduced to sign bits by the rows' rule (negative and not a zero: bit
+ * 1; padding bits 0; a NaN component gives bit 0, an infinite one its sign -- a query is not refused for either).
+ * phnsw_bits_scan_topk: per query the min(r, n) rows with the smallest (h, id), ascending, h = popcount(row XOR query).
+ * out_d carries exactly the bits phnsw_distance_batch returns on the same bits store (sign-vector units), for all three
+ * metrics; every metric's map of h is strictly increasing, so (distance, id) order and (h, id) order are one order.
+ * Rows have r entries, padded with PHNSW_EMPTY / f32::MAX; out_len[q] = min(r, n).  The result is exact in Hamming space
+ * and does not depend on tile size, slice count or any knob (PHNSW_BITS_SCAN_TILE, PHNSW_BITS_SCAN_SLICES).
+ * phnsw_bits_scan_search: that scan for r candidates, then every candidate recomputed on `full` (true f32 distances, the
+ * bits of phnsw_distance_batch on it), sorted by (distance, id), the best k <= r kept.  Outputs are shaped like
+ * phnsw_bits_search_batch[_device]'s: host rows [nq][k] u64, out_len[q] = min(len, k); device rows keep stride r, u32
+ * ids, the first min(len, k) live, enqueued on `stream` without a synchronisation.
+ * The device forms read queries_dev [nq][ldq], ldq >= dim; the search form wants the re-rank's ldq >= ld, a multiple of 4,
+ * and a 16-byte base.
+ * A NULL store or one that is not a bits store is PHNSW_E_UNSUPPORTED, naming the kind.  r outside 1 .. 1024, k outside
+ * 1 .. r, a NULL query or output pointer, nq > 2^32 - 1, n > 2^31 - 1, or a `full` that is not the f32 store of the same
+ * n / dim / metric / device is PHNSW_E_INVALID; every message names the call, and all of it is checked on the host before
+ * any launch.  nq == 0 is a no-op.  phnsw_bruteforce_topk and the phnsw_search_exact_* calls keep refusing a bits store. */
+int phnsw_bits_scan_topk(const phnsw_store *bits, const float *queries, uint64_t nq, uint64_t r, uint64_t *out_ids,
+                         float *out_d, uint64_t *out_len);
+int phnsw_bits_scan_topk_device(const phnsw_store *bits, const float *queries_dev, uint32_t ldq, uint64_t nq, uint64_t r,
+                                uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev, void *stream);
+int phnsw_bits_scan_search(const phnsw_store *bits, const phnsw_store *full, const float *queries, uint64_t nq, uint64_t r,
+                           uint64_t k, uint64_t *out_ids, float *out_d, uint64_t *out_len);
+int phnsw_bits_scan_search_device(const phnsw_store *bits, const phnsw_store *full, const float *queries_dev, uint32_t ldq,
+                                  uint64_t nq, uint64_t r, uint64_t k, uint32_t *out_ids_dev, float *out_d_dev,
+                                  uint32_t *out_len_dev, void *stream);
 
 /* ---- MXFP4 row store: 4-bit codes, one power-of-two scale per 32 components (rowstore.hip) ----
  * The rows of the f32 store `full` as OCP MXFP4, quantised block by block by a device kernel.  Block b of a row is

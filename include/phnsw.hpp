@@ -135,6 +135,29 @@ class Comparator {
     words.resize(n_ * ((dim_ + 31u) / 32u));
     check(phnsw_bits_read(s_, words.data()));
   }
+  // a make_bits comparator scanned exhaustively (phnsw_bits_scan_topk): per query the min(r, n) rows with the smallest
+  // (Hamming distance, id), distances in sign-vector units; ids / d are [nq][r], len [nq]
+  void bits_scan(const std::vector<float> &queries, uint64_t r, std::vector<uint64_t> &ids, std::vector<float> &d,
+                 std::vector<uint64_t> &len) const {
+    const uint64_t nq = queries.size() / dim_;
+    ids.resize(nq * r), d.resize(nq * r), len.resize(nq);
+    check(phnsw_bits_scan_topk(s_, queries.data(), nq, r, ids.data(), d.data(), len.data()));
+  }
+  void bits_scan_device(const float *queries_dev, uint32_t ldq, uint64_t nq, uint64_t r, uint32_t *out_ids_dev,
+                        float *out_d_dev, uint32_t *out_len_dev, void *stream) const {
+    check(phnsw_bits_scan_topk_device(s_, queries_dev, ldq, nq, r, out_ids_dev, out_d_dev, out_len_dev, stream));
+  }
+  // ... and re-ranked on the f32 comparator `full` (phnsw_bits_scan_search): the best k <= r by true f32 distance, [nq][k]
+  void bits_scan_search(const Comparator &full, const std::vector<float> &queries, uint64_t r, uint64_t k,
+                        std::vector<uint64_t> &ids, std::vector<float> &d, std::vector<uint64_t> &len) const {
+    const uint64_t nq = queries.size() / dim_;
+    ids.resize(nq * k), d.resize(nq * k), len.resize(nq);
+    check(phnsw_bits_scan_search(s_, full.s_, queries.data(), nq, r, k, ids.data(), d.data(), len.data()));
+  }
+  void bits_scan_search_device(const Comparator &full, const float *queries_dev, uint32_t ldq, uint64_t nq, uint64_t r,
+                               uint64_t k, uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev, void *stream) const {
+    check(phnsw_bits_scan_search_device(s_, full.s_, queries_dev, ldq, nq, r, k, out_ids_dev, out_d_dev, out_len_dev, stream));
+  }
   // the same vectors as MXFP4 rows, 4-bit codes with one power-of-two scale per 32 components (phnsw_store_create_fp4):
   // search-only like make_i8, every filtered and exact call included; re-rank with Hnsw::search_many_reranked_fp4
   phnsw_store *make_fp4() const {

@@ -665,6 +665,27 @@ __device__ __forceinline__ uint32_t ph_bits_nibble(const float4 &v, uint32_t c, 
          (j + 2u < dim ? ph_bits_sign_of(__float_as_uint(v.z)) << 2 : 0u) | (j + 3u < dim ? ph_bits_sign_of(__float_as_uint(v.w)) << 3 : 0u);
 }
 
+// One f32 row of `dim` components reduced to its sign words by a whole wave: 64 components at a time (coalesced), their
+// sign bits by one ballot = two words of the row; lane w returns word w (lanes past the row's words: 0).  `nonfinite`
+// is raised in a lane that read a NaN or an infinite component.  The store's conversion (rowstore.hip) and the scan's
+// query reduction (scan_bits.hip) both call it, so a query's bits follow the rows' rule by construction.
+__device__ __forceinline__ uint32_t ph_bits_row_words(const float *src, uint32_t dim, uint32_t lane, bool &nonfinite) {
+  uint32_t word = 0u;
+  for (uint32_t b = 0; 64u * b < dim; b++) {
+    const uint32_t c = 64u * b + lane;
+    uint32_t neg = 0u;
+    if (c < dim) {
+      const uint32_t u = __float_as_uint(src[c]);
+      nonfinite |= (u & 0x7F800000u) == 0x7F800000u;
+      neg = ph_bits_sign_of(u);
+    }
+    const uint64_t m = __ballot(neg != 0u);
+    if (lane == 2u * b) word = (uint32_t)m;
+    if (lane == 2u * b + 1u) word = (uint32_t)(m >> 32);
+  }
+  return word;
+}
+
 // DistBits<NV>: rows of 32 NV bytes (bits_plan.h), ONE LANE per candidate, as the PQ policies map them: batch() hands
 // each lane its own id and wants the result in that lane, so there is no compaction, no wave reduction and no
 // ds_bpermute.  The query's 8 NV words are the same in every lane: built once per query and held wave-uniform

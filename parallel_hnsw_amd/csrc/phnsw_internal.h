@@ -921,6 +921,9 @@ int ph_fill_u32(uint32_t *p, uint32_t v, uint64_t n, hipStream_t s);
 // [n][k] (ph_take_kernel, hostpath.hip)
 int ph_take_launch(const uint32_t *ids, const float *d, uint32_t ef, uint32_t k, uint64_t n, uint64_t *ids64, float *dk,
                    hipStream_t s);
+// the f32 re-rank of rows [nq][ef] in place, sorted by (distance, id), then the cut to k (rerank_launch, pq.hip)
+int ph_rerank_launch(const phnsw_store *full, const float *queries_dev, uint32_t ldq, uint64_t nq, uint32_t ef, uint32_t k,
+                     uint32_t *len, uint32_t *ids, float *d, hipStream_t st);
 int ph_scatter_vec2node(const uint32_t *nodes, uint32_t n, uint32_t *vec2node, hipStream_t s);
 int ph_count_nan(const float *rows, uint64_t n_floats, uint32_t *out_count_dev, hipStream_t s);
 

@@ -681,6 +681,12 @@ static int rerank_launch(const phnsw_store *full, const float *queries_dev, uint
   return 0;
 }
 
+// ... for the exhaustive scan over a bits store (scan_bits.hip), whose candidates come from no index
+int ph_rerank_launch(const phnsw_store *full, const float *queries_dev, uint32_t ldq, uint64_t nq, uint32_t ef, uint32_t k,
+                     uint32_t *len, uint32_t *ids, float *d, hipStream_t st) {
+  return rerank_launch(full, queries_dev, ldq, nq, ef, k, len, ids, d, st);
+}
+
 // zero-copy form (arguments checked by the caller): the search launches, the re-rank and the cut to k enqueued on
 // `stream`, u32 ids, no synchronisation.  The result rows keep the search's stride (number_of_candidates entries per
 // query): the first min(len, k) are live.

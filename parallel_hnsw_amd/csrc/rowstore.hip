@@ -97,20 +97,7 @@ __global__ void ph_bits_convert_kernel(const float *__restrict__ rows, uint32_t 
   const uint32_t lane = threadIdx.x & 63u, wpb = blockDim.x / 64u;
   bool mine = false;
   for (uint64_t r = (uint64_t)blockIdx.x * wpb + threadIdx.x / 64u; r < n; r += (uint64_t)gridDim.x * wpb) {
-    const float *src = rows + r * ld;
-    uint32_t word = 0u;
-    for (uint32_t b = 0; 64u * b < dim; b++) {
-      const uint32_t c = 64u * b + lane;
-      uint32_t neg = 0u;
-      if (c < dim) {
-        const uint32_t u = __float_as_uint(src[c]);
-        mine |= (u & 0x7F800000u) == 0x7F800000u;
-        neg = ph_bits_sign_of(u);
-      }
-      const uint64_t m = __ballot(neg != 0u);
-      if (lane == 2u * b) word = (uint32_t)m;
-      if (lane == 2u * b + 1u) word = (uint32_t)(m >> 32);
-    }
+    const uint32_t word = ph_bits_row_words(rows + r * ld, dim, lane, mine);
     if (lane < stride_words) out[r * stride_words + lane] = word;
   }
   if (mine) atomicOr(bad, 1u);

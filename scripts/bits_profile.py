@@ -12,7 +12,13 @@ the script reports what it finds, "slower at equal recall" included.
   python scripts/bits_profile.py --resources [--parent DIR]
       needs only hipcc: the compiler's resource report of the 12 bits kernels (resource_usage_bits.txt) and, with
       --parent pointing at the csrc directory of the parent commit, resource_usage_existing_diff.txt: every kernel that
-      exists in both trees, translation unit by translation unit, and how many differ in a reported figure."""
+      exists in both trees, translation unit by translation unit, and how many differ in a reported figure.
+  python scripts/bits_profile.py --scan [--candidates 64,256,1024] [--steps 5 --warmup 2 --runs 3]
+      the exhaustive scan (phnsw_bits_scan_search_device: Hamming scan for r candidates + f32 re-rank) on the same
+      workload, r in place of number_of_candidates: ms per batch and recall@10, with the walk + re-rank at the same
+      number of candidates and the f32 search at ef 256 ALTERNATING inside every round as above.  Appends to
+      profiles/bits_scan/bits_scan_profile.jsonl.  With --resources it writes profiles/bits_scan/ instead: the report of
+      scan_bits.hip and the unchanged-kernels diff."""
 import argparse
 import json
 import os
@@ -50,9 +56,12 @@ def resource_report(csrc, unit):
 
 
 def resources(args):
+    global OUT
+    if args.scan:
+        OUT = OUT + "_scan"
     os.makedirs(OUT, exist_ok=True)
-    mine = resource_report(CSRC, "search_bits.hip")
-    with open(os.path.join(OUT, "resource_usage_bits.txt"), "w") as f:
+    mine = resource_report(CSRC, "scan_bits.hip" if args.scan else "search_bits.hip")
+    with open(os.path.join(OUT, "resource_usage_bits_scan.txt" if args.scan else "resource_usage_bits.txt"), "w") as f:
         f.write("kernel | VGPRs | SGPRs | scratch bytes/lane | waves/SIMD | static LDS\n")
         for k in sorted(mine):
             r = mine[k]
@@ -130,6 +139,9 @@ def measure(args):
     lines = []
     for ef in [int(x) for x in args.candidates.split(",")]:
         sp = ph.SearchParameters(ef, ef, args.probe_depth)
+        if args.scan:
+            lines.append(measure_scan(args, ef, sp, bits, bix, store, qs, ids, d, ln, status, stream, f32, timed, recall))
+            continue
 
         def walk():
             bix.search_batch_device(nq, sp, ids.data_ptr(), d.data_ptr(), ln.data_ptr(), status.data_ptr(), queries=qs.rows_dev,
@@ -157,15 +169,50 @@ def measure(args):
                 "spread_ms": {v: round(max(runs[v]) - min(runs[v]), 4) for v in runs}}
         print(json.dumps(line), flush=True)
         lines.append(line)
-    os.makedirs(OUT, exist_ok=True)
-    with open(os.path.join(OUT, "bits_profile.jsonl"), "a") as f:
+    out = OUT + "_scan" if args.scan else OUT
+    os.makedirs(out, exist_ok=True)
+    with open(os.path.join(out, "bits_scan_profile.jsonl" if args.scan else "bits_profile.jsonl"), "a") as f:
         f.write("\n".join(json.dumps(x) for x in lines) + "\n")
     return lines
+
+
+def measure_scan(args, r, sp, bits, bix, store, qs, ids, d, ln, status, stream, f32, timed, recall):
+    """one setting of r: the scan alone, scan + re-rank, the walk + re-rank with r candidates, the f32 search"""
+    nq, k = args.nq, 10
+    status.zero_()
+
+    def scan():
+        bits.scan_device(nq, r, qs.rows_dev, qs.ld, ids.data_ptr(), d.data_ptr(), ln.data_ptr(), stream=stream.cuda_stream)
+
+    def scan_search():
+        bits.scan_search_device(store, nq, r, k, qs.rows_dev, qs.ld, ids.data_ptr(), d.data_ptr(), ln.data_ptr(),
+                                stream=stream.cuda_stream)
+
+    def walk_reranked():
+        bix.search_batch_reranked_device(store, nq, sp, k, qs.rows_dev, qs.ld, ids.data_ptr(), d.data_ptr(), ln.data_ptr(),
+                                         status.data_ptr(), stream=stream.cuda_stream)
+
+    calls = (("f32", f32), ("scan", scan), ("scan_search", scan_search)) + ((("walk_reranked", walk_reranked),) if r >= 256 else ())
+    runs = {name: [] for name, _ in calls}
+    for _ in range(args.runs):  # alternating: a drift of the machine lands on all of them
+        for name, fn in calls:
+            runs[name].append(timed(fn))
+    rec = {}
+    for name, fn, stride in (("f32", f32, 256), ("scan_search", scan_search, r)) + ((("walk_reranked", walk_reranked, r),) if r >= 256 else ()):
+        fn()
+        stream.synchronize()
+        rec[name] = round(recall(stride), 4)
+    line = {"r": r, "probe_depth": args.probe_depth, "vectors": args.n, "dim": args.dim, "queries": nq, "rounds": runs,
+            "ms": {v: float(np.median(runs[v])) for v in runs}, "recall_at_10": rec,
+            "spread_ms": {v: round(max(runs[v]) - min(runs[v]), 4) for v in runs}}
+    print(json.dumps(line), flush=True)
+    return line
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--resources", action="store_true")
+    ap.add_argument("--scan", action="store_true", help="the exhaustive scan (profiles/bits_scan/) instead of the walk")
     ap.add_argument("--parent", default="", help="csrc directory of the parent commit, for the unchanged-kernels diff")
     ap.add_argument("--jobs", type=int, default=8)
     ap.add_argument("--candidates", default="256,512,1024")
@@ -179,6 +226,8 @@ def main():
     args = ap.parse_args()
     if args.resources:
         resources(args)
+    elif args.scan:
+        measure(args)
     else:
         for x in measure(args):
             print("%d candidates: bits walk %.2f ms, + re-rank %.2f ms, recall@10 %.4f; f32 at ef 256: %.2f ms, recall@10 %.4f"
