@@ -1675,6 +1675,46 @@ int phnsw_fp4_search_batch_device(const phnsw_index *ix, const phnsw_store *full
                                   uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
                                   uint32_t *out_stats_dev, uint32_t *status_dev, void *stream);
 
+/* ---- exhaustive MXFP4 scan over an fp4 store on the block-scaled matrix cores, with f32 re-rank (scan_fp4.hip) ----
+ * No graph: every row 0 .. n - 1 of the fp4 store is a candidate (no index, no filter, no exclude).  Queries are raw f32
+ * rows only.  ANOTHER CONTRACT than every other call on an fp4 store: the QUERY IS ROUNDED TOO.  Each query is
+ * quantised to MXFP4 by the store's own rule above (block scale, grid, ties), components at or past dim counting as 0.
+ * With q^ and x^ the decoded query and row, the score is
+ *   s = sum_j q^_j x^_j,
+ * computed by a chain of v_mfma_scale_f32_16x16x128_f8f6f4 over ascending k (128 components, four blocks, a step),
+ * accumulated in f32 from 0, and the distance is the metric's last step on s ((1 - s) / 2 or 1 - s, in f32).  The two
+ * dot-product metrics only: an L2 store is PHNSW_E_UNSUPPORTED, as in phnsw_bruteforce_topk.
+ * What is fixed and what is not: every product q^_j x^_j is exact in f32.  When every partial sum of a (query, row)
+ * pair is representable in f32 as well, s is the exact sum and the result is fixed bit for bit.  Otherwise s may differ
+ * from the exact sum by the rounding of the accumulation inside and between the instructions, which the hardware does
+ * not document; |s - exact| <= dim * 2^-24 * sum_j |q^_j x^_j| is the first-order bound of any f32 summation order and
+ * is what the tests hold it to.  A row's score never depends on the other rows or queries of its instruction, nor
+ * on tile size, slice count or any knob (PHNSW_FP4_SCAN_TILE, PHNSW_FP4_SCAN_SLICES): a row group is 16 consecutive
+ * rows and a step 128 consecutive components whatever the cut.
+ * phnsw_fp4_scan_topk: per query the min(r, n) rows with the smallest (distance, id) on the finalised f32 distance,
+ * ascending.  Rows have r entries, padded with PHNSW_EMPTY / f32::MAX; out_len[q] = min(r, n).
+ * phnsw_fp4_scan_search: that scan for r candidates, then every candidate recomputed on `full` (true f32 distances, the
+ * bits of phnsw_distance_batch on it), sorted by (distance, id), the best k <= r kept.  Outputs are shaped like
+ * phnsw_bits_scan_search[_device]'s: host rows [nq][k] u64, out_len[q] = min(len, k); device rows keep stride r, u32
+ * ids, the first min(len, k) live, enqueued on `stream` without a synchronisation.
+ * The device forms read queries_dev [nq][ldq], ldq >= dim; the search form wants the re-rank's ldq >= ld, a multiple of 4,
+ * and a 16-byte base.  They cannot see a NaN or infinite component: the rows of such a query are unspecified, every
+ * other query is unaffected.  The host forms refuse it (PHNSW_E_INVALID).
+ * A NULL store or one that is not an fp4 store is PHNSW_E_UNSUPPORTED, naming the kind.  r outside 1 .. 1024, k outside
+ * 1 .. r, a NULL query or output pointer, nq > 2^32 - 1, n > 2^31 - 1, or a `full` that is not the f32 store of the same
+ * n / dim / metric / device is PHNSW_E_INVALID; every message names the call, and all of it is checked on the host before
+ * any launch.  nq == 0 is a no-op.  Nothing else changes: phnsw_bruteforce_topk keeps refusing an fp4 store and the
+ * f32-query calls on it keep their bit-for-bit contract. */
+int phnsw_fp4_scan_topk(const phnsw_store *fp4, const float *queries, uint64_t nq, uint64_t r, uint64_t *out_ids,
+                        float *out_d, uint64_t *out_len);
+int phnsw_fp4_scan_topk_device(const phnsw_store *fp4, const float *queries_dev, uint32_t ldq, uint64_t nq, uint64_t r,
+                               uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev, void *stream);
+int phnsw_fp4_scan_search(const phnsw_store *fp4, const phnsw_store *full, const float *queries, uint64_t nq, uint64_t r,
+                          uint64_t k, uint64_t *out_ids, float *out_d, uint64_t *out_len);
+int phnsw_fp4_scan_search_device(const phnsw_store *fp4, const phnsw_store *full, const float *queries_dev, uint32_t ldq,
+                                 uint64_t nq, uint64_t r, uint64_t k, uint32_t *out_ids_dev, float *out_d_dev,
+                                 uint32_t *out_len_dev, void *stream);
+
 /* ---- on-disk interchange with the Rust crate: serialize_hnsw / deserialize_hnsw
  * (src/serialize.rs:33-209): <dir>/meta (JSON HNSWMeta), <dir>/comparator/ (this library's
  * store; a crate user substitutes their own Serializable comparator), layer.meta.N (JSON),

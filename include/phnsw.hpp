@@ -171,6 +171,29 @@ class Comparator {
     scales.resize(n_ * ((dim_ + 31u) / 32u));
     check(phnsw_fp4_read(s_, codes.data(), scales.data()));
   }
+  // a make_fp4 comparator scanned exhaustively on the block-scaled matrix cores (phnsw_fp4_scan_topk): the queries are
+  // quantised to MXFP4 too; per query the min(r, n) rows with the smallest (distance, id); ids / d are [nq][r], len [nq]
+  void fp4_scan(const std::vector<float> &queries, uint64_t r, std::vector<uint64_t> &ids, std::vector<float> &d,
+                std::vector<uint64_t> &len) const {
+    const uint64_t nq = queries.size() / dim_;
+    ids.resize(nq * r), d.resize(nq * r), len.resize(nq);
+    check(phnsw_fp4_scan_topk(s_, queries.data(), nq, r, ids.data(), d.data(), len.data()));
+  }
+  void fp4_scan_device(const float *queries_dev, uint32_t ldq, uint64_t nq, uint64_t r, uint32_t *out_ids_dev,
+                       float *out_d_dev, uint32_t *out_len_dev, void *stream) const {
+    check(phnsw_fp4_scan_topk_device(s_, queries_dev, ldq, nq, r, out_ids_dev, out_d_dev, out_len_dev, stream));
+  }
+  // ... and re-ranked on the f32 comparator `full` (phnsw_fp4_scan_search): the best k <= r by true f32 distance, [nq][k]
+  void fp4_scan_search(const Comparator &full, const std::vector<float> &queries, uint64_t r, uint64_t k,
+                       std::vector<uint64_t> &ids, std::vector<float> &d, std::vector<uint64_t> &len) const {
+    const uint64_t nq = queries.size() / dim_;
+    ids.resize(nq * k), d.resize(nq * k), len.resize(nq);
+    check(phnsw_fp4_scan_search(s_, full.s_, queries.data(), nq, r, k, ids.data(), d.data(), len.data()));
+  }
+  void fp4_scan_search_device(const Comparator &full, const float *queries_dev, uint32_t ldq, uint64_t nq, uint64_t r,
+                              uint64_t k, uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev, void *stream) const {
+    check(phnsw_fp4_scan_search_device(s_, full.s_, queries_dev, ldq, nq, r, k, out_ids_dev, out_d_dev, out_len_dev, stream));
+  }
   // codes [n][dim] and scales [n] of a comparator made by make_i8 or make_i8q (phnsw_i8_read)
   void read_i8(std::vector<int8_t> &codes, std::vector<float> &scales) const {
     codes.resize(n_ * dim_);

@@ -698,6 +698,18 @@ extern "C" {
                                          ldq: u32, nq: u64, r: u64, k: u64, out_ids_dev: *mut u32,
                                          out_d_dev: *mut c_float, out_len_dev: *mut u32, stream: *mut c_void) -> c_int;
 
+    // ---- exhaustive MXFP4 scan over an fp4 store (block-scaled MFMA), alone and with the re-rank on the f32 store
+    pub fn phnsw_fp4_scan_topk(fp4: *const phnsw_store, queries: *const c_float, nq: u64, r: u64, out_ids: *mut u64,
+                               out_d: *mut c_float, out_len: *mut u64) -> c_int;
+    pub fn phnsw_fp4_scan_topk_device(fp4: *const phnsw_store, queries_dev: *const c_float, ldq: u32, nq: u64, r: u64,
+                                      out_ids_dev: *mut u32, out_d_dev: *mut c_float, out_len_dev: *mut u32,
+                                      stream: *mut c_void) -> c_int;
+    pub fn phnsw_fp4_scan_search(fp4: *const phnsw_store, full: *const phnsw_store, queries: *const c_float, nq: u64,
+                                 r: u64, k: u64, out_ids: *mut u64, out_d: *mut c_float, out_len: *mut u64) -> c_int;
+    pub fn phnsw_fp4_scan_search_device(fp4: *const phnsw_store, full: *const phnsw_store, queries_dev: *const c_float,
+                                        ldq: u32, nq: u64, r: u64, k: u64, out_ids_dev: *mut u32,
+                                        out_d_dev: *mut c_float, out_len_dev: *mut u32, stream: *mut c_void) -> c_int;
+
     // ---- MXFP4 rows: 4-bit codes, one power-of-two scale per 32 components; re-rank on the f32 store
     pub fn phnsw_store_create_fp4(full: *const phnsw_store, out: *mut *mut phnsw_store) -> c_int;
     pub fn phnsw_fp4_read(s: *const phnsw_store, codes: *mut u8, scales: *mut u8) -> c_int;
