@@ -1715,6 +1715,37 @@ int phnsw_fp4_scan_search_device(const phnsw_store *fp4, const phnsw_store *full
                                  uint64_t nq, uint64_t r, uint64_t k, uint32_t *out_ids_dev, float *out_d_dev,
                                  uint32_t *out_len_dev, void *stream);
 
+/* ---- the same scan restricted to an allow-list of rows (scan_fp4_filtered.hip) ----
+ * The four calls above with (filter, filter_stride_words) of phnsw_search_exact_filtered: bit v % 32 of word v / 32 set =
+ * row v is allowed; filter_stride_words 0 = one bitmap of ceil(n / 32) words for the whole batch, else nq bitmaps that
+ * far apart (>= ceil(n / 32), the last a whole stride); bits at or past n are ignored.  No index, label or attribute
+ * handle and no exclude: the scan has only a store.
+ * Contract: the unfiltered scan's, restricted to the allowed rows.  The query is quantised the same way, s is the same
+ * chain of the same instruction and a score never depends on the rows beside it in the instruction, so every returned
+ * (id, distance) has exactly the bits the unfiltered scan computes for that pair.  Per query the min(r, allowed rows)
+ * allowed rows with the smallest (distance, id), ascending; a disallowed row is never returned; out_len[q] = min(r,
+ * allowed rows of q), rows padded as above.  The _search forms re-rank those candidates on `full` as above.
+ * How it runs: a shared bitmap is compacted on the device into an ascending row list and only listed rows are read
+ * (cost proportional to the allowed rows); per-query bitmaps scan every row and test a row's bit only when its score
+ * passes the query's threshold (cost that of the unfiltered scan, more while a selective filter keeps a list short).
+ * Neither form, nor PHNSW_FP4_SCAN_TILE / PHNSW_FP4_SCAN_SLICES, changes a result.
+ * Refusals as above, naming the call; in addition a NULL filter (the unfiltered calls exist for that) or a stride between
+ * 1 and ceil(n / 32) - 1 is PHNSW_E_INVALID.  The host forms read `filter` from host memory, the device forms from
+ * device memory (filter_dev must stay unchanged until the work enqueued on `stream` has run). */
+int phnsw_fp4_scan_topk_filtered(const phnsw_store *fp4, const float *queries, uint64_t nq, uint64_t r,
+                                 const uint32_t *filter, uint32_t filter_stride_words, uint64_t *out_ids, float *out_d,
+                                 uint64_t *out_len);
+int phnsw_fp4_scan_topk_filtered_device(const phnsw_store *fp4, const float *queries_dev, uint32_t ldq, uint64_t nq,
+                                        uint64_t r, const uint32_t *filter_dev, uint32_t filter_stride_words,
+                                        uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev, void *stream);
+int phnsw_fp4_scan_search_filtered(const phnsw_store *fp4, const phnsw_store *full, const float *queries, uint64_t nq,
+                                   uint64_t r, uint64_t k, const uint32_t *filter, uint32_t filter_stride_words,
+                                   uint64_t *out_ids, float *out_d, uint64_t *out_len);
+int phnsw_fp4_scan_search_filtered_device(const phnsw_store *fp4, const phnsw_store *full, const float *queries_dev,
+                                          uint32_t ldq, uint64_t nq, uint64_t r, uint64_t k, const uint32_t *filter_dev,
+                                          uint32_t filter_stride_words, uint32_t *out_ids_dev, float *out_d_dev,
+                                          uint32_t *out_len_dev, void *stream);
+
 /* ---- on-disk interchange with the Rust crate: serialize_hnsw / deserialize_hnsw
  * (src/serialize.rs:33-209): <dir>/meta (JSON HNSWMeta), <dir>/comparator/ (this library's
  * store; a crate user substitutes their own Serializable comparator), layer.meta.N (JSON),

@@ -1,7 +1,9 @@
 // The exhaustive MXFP4 scan over an fp4 store (PH_ROWS_FP4, rowstore.hip) on the block-scaled matrix cores:
 // phnsw_fp4_scan_topk[_device], the r rows nearest each query by the score s = sum q^_j x^_j of the MXFP4-quantised query
 // and the stored row, and phnsw_fp4_scan_search[_device], that scan followed by the f32 re-rank of pq.hip.  No index, no
-// filter, no exclude: every row 0 .. n - 1 is a candidate.  Dot-product metrics only.
+// filter, no exclude: every row 0 .. n - 1 is a candidate.  Dot-product metrics only.  The scan kernel's body is
+// scan_fp4_kernel.h's, instantiated here in its PLAIN form; the forms over an allow-list and their entry points are
+// scan_fp4_filtered.hip's, which run through this file's launcher, scratch, merge kernel and host staging.
 //
 //   result of a query = the min(r, n) rows with the smallest (finalize_metric(s), id), ascending.
 //   s                 = the chain of v_mfma_scale_f32_16x16x128_f8f6f4 over ascending k, f32 accumulation from 0.
@@ -30,37 +32,9 @@
 #include <cmath>
 #include <map>
 #include <mutex>
-#include <type_traits>
 #include <vector>
 
-#include "exact_topk.h"
-#include "fp4_scan_plan.h"
-#include "phnsw_device.h"
-
-#define PH_TRY(x)          \
-  do {                     \
-    int rc__ = (x);        \
-    if (rc__) return rc__; \
-  } while (0)
-
-typedef int ph_v8i __attribute__((ext_vector_type(8)));
-typedef float ph_v4f __attribute__((ext_vector_type(4)));
-
-struct PhFp4ScanArgs {
-  const uint8_t *rows;      // n rows of `stride` bytes, the device layout of phnsw_device.h
-  const uint8_t *qcodes;    // [nq][ph_fp4_scan_code_bytes(steps)]
-  const uint8_t *qscales;   // [nq][ph_fp4_scan_scale_bytes(steps)]
-  uint32_t stride, nb, steps;  // nb: blocks of a row that exist, ceil(ld / 32)
-  uint32_t nq, n, k;           // k: the r of the call (the name ph_exact_write_row reads)
-  int metric;
-  uint32_t tiles, slices, stage;
-  uint64_t groups;
-  uint64_t *lists;    // [tiles * slices][T][2 k]: the running top-r of every (query, slice)
-  uint64_t *scratch;  // slices > 1: [nq][slices][k] keys, each list ascending, KEY_NONE padded
-  uint32_t *out_ids;  // [nq][k]
-  float *out_d;
-  uint32_t *out_len, *status;  // [nq]
-};
+#include "scan_fp4_kernel.h"
 
 // one lane per block of 32 components: the block's scale by ph_fp4_e8, its codes by ph_fp4_quant, component j in nibble
 // j & 1 of byte j / 2 as in the store.  Components at or past dim count as 0; a block of zeros has e8 = 2 and zero codes.
@@ -89,161 +63,9 @@ __global__ __launch_bounds__(256) void ph_fp4_scan_query_kernel(const float *__r
   }
 }
 
-template <int I, int N, class F>
-__device__ __forceinline__ void ph_static_for(F &&f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>());
-    ph_static_for<I + 1, N>(f);
-  }
-}
-
-// one lane's operand of a row group: 16 code bytes a step; the scale dwords of (section, step parity)
-template <int S>
-struct PhFp4RowRegs {
-  uint4 c[S];
-  uint32_t sc[2 * ((S + 7) / 8)];
-};
-
-// the per-query state of a tile in LDS, four words
-struct PhFp4ScanState {
-  uint32_t staged, len, flip;
-  float smin;
-};
-
 template <int S, int G>
 __global__ __launch_bounds__(64) void ph_fp4_scan_kernel(PhFp4ScanArgs a) {
-  extern __shared__ uint64_t scan_lds[];
-  constexpr uint32_t T = 16u * G;
-  constexpr int SEC = (S + 7) / 8, QW = (S + 3) / 4;
-  const uint32_t lane = threadIdx.x, col = lane & 15u, kb = lane >> 4;
-  uint64_t *const stage = scan_lds;                     // [T][a.stage]
-  uint64_t *const sv = scan_lds + (uint64_t)T * a.stage;  // [64]
-  PhFp4ScanState *const state = (PhFp4ScanState *)(sv + 64);
-  const uint32_t tile = blockIdx.x % a.tiles, slice = blockIdx.x / a.tiles;
-  const uint32_t q0 = tile * T, tq = min(T, a.nq - q0);
-  uint64_t *const lists = a.lists + (uint64_t)blockIdx.x * T * 2u * a.k;
-  const bool half = a.metric == PHNSW_METRIC_COSINE_HALF;
-  for (uint32_t t = lane; t < T; t += 64u) state[t] = PhFp4ScanState{0u, 0u, 0u, t < tq ? -INFINITY : INFINITY};
-  __syncthreads();
-
-  // the tile's queries: lane's block 4 s + kb of query column `col` of every group; past the last query the last again
-  uint4 qc[G][S];
-  uint32_t qs[G][QW];
-#pragma unroll
-  for (int g = 0; g < G; g++) {
-    const uint32_t q = min(q0 + 16u * g + col, a.nq - 1u);
-    const uint8_t *cq = a.qcodes + (uint64_t)q * ph_fp4_scan_code_bytes(a.steps);
-    const uint8_t *sq = a.qscales + (uint64_t)q * ph_fp4_scan_scale_bytes(a.steps) + kb * ph_fp4_scan_scale_run(a.steps);
-#pragma unroll
-    for (int s = 0; s < S; s++) qc[g][s] = (uint32_t)s < a.steps ? *(const uint4 *)(cq + (4u * s + kb) * 16u) : make_uint4(0, 0, 0, 0);
-#pragma unroll
-    for (int w = 0; w < QW; w++) qs[g][w] = 4u * w < a.steps ? *(const uint32_t *)(sq + 4u * w) : 0x7F7F7F7Fu;
-  }
-  float smin[G];
-#pragma unroll
-  for (int g = 0; g < G; g++) smin[g] = 16u * g + col < tq ? -INFINITY : INFINITY;
-
-  uint64_t g0, g1;
-  ph_exact_slice_range(slice, a.slices, a.groups, &g0, &g1);
-
-  // lane's operand of row group `grp`
-  auto load = [&](PhFp4RowRegs<S> &x, uint64_t grp) {
-    const uint32_t row = min((uint32_t)(grp * 16u) + col, a.n - 1u);
-    const uint8_t *src = a.rows + (uint64_t)row * a.stride;
-#pragma unroll
-    for (int s = 0; s < S; s++) {
-      const uint32_t blk = 4u * s + kb;
-      x.c[s] = blk < a.nb ? *(const uint4 *)(src + 544u * (s >> 3) + 32u + 16u * (4u * (s & 7) + kb)) : make_uint4(0, 0, 0, 0);
-    }
-#pragma unroll
-    for (int w = 0; w < 2 * SEC; w++)  // a section that exists has its 32 scale bytes, every one a valid E8M0
-      x.sc[w] = 32u * (w >> 1) < a.nb ? *(const uint32_t *)(src + 544u * (w >> 1) + 16u * (w & 1) + 4u * kb) : 0x7F7F7F7Fu;
-  };
-
-  // the staged keys of query t into its running top-r; its threshold afterwards.  Whole wave, uniform control flow.
-  auto flush = [&](uint32_t t) {
-    PhFp4ScanState *const st = state + t;
-    const uint32_t staged = rfl32(st->staged);
-    const uint64_t key = lane < staged ? stage[t * a.stage + lane] : KEY_NONE;
-    PhExactTopK top;
-    top.init(lists + (uint64_t)t * 2u * a.k, a.k);
-    top.sv = sv;
-    if (rfl32(st->flip)) {
-      uint64_t *const c = top.cur;
-      top.cur = top.nxt, top.nxt = c;
-    }
-    top.len = rfl32(st->len);
-    __syncthreads();  // the state read above is rewritten below
-    top.insert(key, lane);
-    __syncthreads();  // (insert returns without one when nothing survived)
-    if (lane == 0) {
-      st->len = top.len;
-      st->flip = top.cur == lists + (uint64_t)t * 2u * a.k ? 0u : 1u;
-      st->staged = 0u;
-      st->smin = top.len == a.k ? ph_fp4_scan_smin(unfkey((uint32_t)(top.cur[a.k - 1u] >> 32)), half) : -INFINITY;
-    }
-    __syncthreads();
-  };
-
-  auto scan = [&](const PhFp4RowRegs<S> &x, uint64_t grp) {
-    ph_v4f acc[G];
-#pragma unroll
-    for (int g = 0; g < G; g++) acc[g] = ph_v4f{0.f, 0.f, 0.f, 0.f};
-    ph_static_for<0, S>([&](auto sc) {
-      constexpr int s = decltype(sc)::value;
-      if ((uint32_t)s < a.steps) {  // wave-uniform
-        const ph_v8i ra = {(int)x.c[s].x, (int)x.c[s].y, (int)x.c[s].z, (int)x.c[s].w, 0, 0, 0, 0};
-        const int sa = (int)x.sc[2 * (s >> 3) + (s & 1)];
-#pragma unroll
-        for (int g = 0; g < G; g++) {
-          const ph_v8i rb = {(int)qc[g][s].x, (int)qc[g][s].y, (int)qc[g][s].z, (int)qc[g][s].w, 0, 0, 0, 0};
-          acc[g] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(ra, rb, acc[g], 4, 4, (s & 7) >> 1, sa, s & 3, (int)qs[g][s >> 2]);
-        }
-      }
-    });
-    bool any = false;
-#pragma unroll
-    for (int g = 0; g < G; g++)
-      any |= acc[g][0] >= smin[g] || acc[g][1] >= smin[g] || acc[g][2] >= smin[g] || acc[g][3] >= smin[g];
-    if (!__ballot(any)) return;
-    const uint32_t row0 = (uint32_t)(grp * 16u) + 4u * kb;
-#pragma unroll
-    for (int g = 0; g < G; g++) {
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const uint32_t id = row0 + i;
-        if (id < a.n && acc[g][i] >= smin[g]) {  // (smin of a query past the last is +inf)
-          const uint32_t t = 16u * g + col;
-          const uint32_t slot = atomicAdd(&state[t].staged, 1u);  // < a.stage: at most 16 rows on top of stage - 16
-          stage[t * a.stage + slot] = mkkey(finalize_metric(acc[g][i], a.metric), id);
-        }
-      }
-    }
-    __syncthreads();
-    uint64_t full = __ballot(lane < T && state[lane < T ? lane : 0u].staged + 16u > a.stage);
-    if (!full) return;
-    for (; full; full &= full - 1ull) flush((uint32_t)__ffsll((unsigned long long)full) - 1u);
-#pragma unroll
-    for (int g = 0; g < G; g++) smin[g] = state[16u * g + col].smin;
-  };
-
-  if (g0 < g1) {
-    PhFp4RowRegs<S> xa, xb;
-    load(xa, g0);
-    for (uint64_t grp = g0; grp < g1; grp += 2u) {
-      if (grp + 1u < g1) load(xb, grp + 1u);
-      scan(xa, grp);
-      if (grp + 1u >= g1) break;
-      if (grp + 2u < g1) load(xa, grp + 2u);
-      scan(xb, grp + 1u);
-    }
-  }
-  for (uint32_t t = 0; t < tq; t++) {
-    PhFp4ScanState *const st = state + t;
-    if (rfl32(st->staged)) flush(t);
-    ph_exact_write_slice<false>(a, q0 + t, q0 + t, slice, lists + (uint64_t)t * 2u * a.k + (rfl32(st->flip) ? a.k : 0u), rfl32(st->len),
-                                false, lane);
-  }
+  ph_fp4_scan_body<S, G, PH_FP4_SCAN_PLAIN>(a);
 }
 
 // One wave per query: the slices' ascending lists merged through the same running top-r.
@@ -261,7 +83,6 @@ __global__ __launch_bounds__(64) void ph_fp4_scan_merge_kernel(PhFp4ScanArgs a) 
 
 // ------------------------------------------------------------------ launchers
 
-typedef void (*PhFp4ScanFn)(PhFp4ScanArgs);
 static PhFp4ScanFn scan_fn(int cls, uint32_t T) {
   switch (cls * 100 + (int)T) {
     case 216: return ph_fp4_scan_kernel<2, 1>;
@@ -316,16 +137,20 @@ int scratch_acquire(int device, size_t bytes, hipStream_t stream, ScanScratch **
 size_t up256(size_t b) { return (b + 255u) & ~(size_t)255u; }
 }  // namespace
 
-// the scan of nq device queries on `stream` (arguments checked by the caller): rows [nq][r] u32 ids and distances, len
-static int fp4_scan_device(const phnsw_store *s, const float *queries_dev, uint32_t ldq, uint64_t nq, uint32_t r,
-                           uint32_t *out_ids, float *out_d, uint32_t *out_len, hipStream_t stream) {
+// the scan of nq device queries on `stream` (arguments checked by the caller): rows [nq][r] u32 ids and distances, len.
+// filter_dev: nullptr = every row (the plain form); one bitmap (filter_stride 0: compacted here, the LIST form) or nq
+// bitmaps filter_stride words apart (the MASK form), scan_fp4_filtered.hip
+int ph_fp4_scan_enqueue(const phnsw_store *s, const float *queries_dev, uint32_t ldq, uint64_t nq, uint32_t r,
+                        const uint32_t *filter_dev, uint32_t filter_stride, uint32_t *out_ids, float *out_d, uint32_t *out_len,
+                        hipStream_t stream) {
   if (nq == 0) return 0;
   PH_HIP(hipSetDevice(s->device));
   const uint32_t steps = ph_fp4_scan_steps(s->ld);
   const int cls = ph_fp4_scan_class(steps);
   if (!cls) return ph_dim_unsupported(s->dim);
   const uint32_t T = ph_fp4_scan_tile(cls, env_ll("PHNSW_FP4_SCAN_TILE"));  // tests and tuning: neither changes a result
-  const PhFp4ScanFn fn = scan_fn(cls, T);
+  const int form = !filter_dev ? PH_FP4_SCAN_PLAIN : (filter_stride ? PH_FP4_SCAN_MASK : PH_FP4_SCAN_LIST);
+  const PhFp4ScanFn fn = form == PH_FP4_SCAN_PLAIN ? scan_fn(cls, T) : ph_fp4_scan_filtered_fn(cls, T, form);
   if (!fn) return ph_dim_unsupported(s->dim);
   const size_t lds = ph_fp4_scan_lds(r, T), merge_lds = ph_fp4_scan_merge_lds(r);
   uint64_t resident = 0;  // workgroups of the scan the device holds at once
@@ -344,7 +169,10 @@ static int fp4_scan_device(const phnsw_store *s, const float *queries_dev, uint3
   const size_t scales_bytes = up256((size_t)chunk * ph_fp4_scan_scale_bytes(steps)), status_bytes = up256((size_t)chunk * 4u);
   const size_t lists_bytes = up256((size_t)chunk_tiles * T * slices * 2u * r * 8u);
   const size_t merge_bytes = slices > 1u ? up256((size_t)chunk * slices * r * 8u) : 0u;  // together: ph_fp4_scan_scratch_bytes
-  const size_t bytes = codes_bytes + scales_bytes + status_bytes + lists_bytes + merge_bytes;
+  // LIST: the compaction's words behind everything else.  The slices were cut from all ceil(n / 16) groups, the kernel
+  // cuts the list's own; what is left over is empty slices
+  const size_t pre_bytes = form == PH_FP4_SCAN_LIST ? up256(ph_fp4_scan_pre_bytes(s->n)) : 0u;
+  const size_t bytes = codes_bytes + scales_bytes + status_bytes + lists_bytes + merge_bytes + pre_bytes;
 
   std::lock_guard<std::mutex> g(g_mutex);
   ScanScratch *x = nullptr;
@@ -357,10 +185,17 @@ static int fp4_scan_device(const phnsw_store *s, const float *queries_dev, uint3
   a.qscales = (const uint8_t *)at_mem, at_mem += scales_bytes;
   a.status = (uint32_t *)at_mem, at_mem += status_bytes;
   a.lists = (uint64_t *)at_mem, at_mem += lists_bytes;
-  a.scratch = (uint64_t *)at_mem;
+  a.scratch = (uint64_t *)at_mem, at_mem += merge_bytes;
+  if (form == PH_FP4_SCAN_LIST) {  // once for all chunks
+    uint32_t *const pre = (uint32_t *)at_mem;
+    PH_TRY(ph_fp4_scan_list_enqueue(filter_dev, s->n, pre, stream));
+    a.count = pre, a.cand = pre + ph_fp4_scan_pre_list(s->n);
+  }
+  a.filter_stride = filter_stride;
   for (uint64_t at = 0; at < nq; at += chunk) {
     const uint64_t cnt = std::min(chunk, nq - at);
     a.nq = (uint32_t)cnt, a.tiles = (uint32_t)ph_fp4_scan_tiles(cnt, T);
+    if (form == PH_FP4_SCAN_MASK) a.filter = filter_dev + at * filter_stride;
     a.out_ids = out_ids + at * r, a.out_d = out_d + at * r, a.out_len = out_len + at;
     hipLaunchKernelGGL(ph_fp4_scan_query_kernel, dim3((uint32_t)std::min<uint64_t>((cnt * 4u * steps + 255u) / 256u, 1u << 16)), dim3(256),
                        0, stream, queries_dev + at * ldq, ldq, s->dim, (uint32_t)cnt, steps, (uint8_t *)a.qcodes, (uint8_t *)a.qscales);
@@ -376,7 +211,7 @@ static int fp4_scan_device(const phnsw_store *s, const float *queries_dev, uint3
 // ------------------------------------------------------------------ entry points
 
 // what all four calls ask of the store and of r
-static int scan_check(const char *call, const phnsw_store *fp4, uint64_t nq, uint64_t r) {
+int ph_fp4_scan_check(const char *call, const phnsw_store *fp4, uint64_t nq, uint64_t r) {
   if (!fp4 || fp4->kind != PH_ROWS_FP4) {
     ph_set_error("%s: needs an fp4 store (phnsw_store_create_fp4), not %s", call, fp4 ? ph_rows_name(fp4->kind) : "NULL");
     return PHNSW_E_UNSUPPORTED;
@@ -392,8 +227,8 @@ static int scan_check(const char *call, const phnsw_store *fp4, uint64_t nq, uin
   return 0;
 }
 // ... and the searches of `full` and k: what rerank_check (pq.hip) demands of a converted store
-static int scan_search_check(const char *call, const phnsw_store *fp4, const phnsw_store *full, uint64_t nq, uint64_t r, uint64_t k) {
-  PH_TRY(scan_check(call, fp4, nq, r));
+int ph_fp4_scan_search_check(const char *call, const phnsw_store *fp4, const phnsw_store *full, uint64_t nq, uint64_t r, uint64_t k) {
+  PH_TRY(ph_fp4_scan_check(call, fp4, nq, r));
   if (!full || !ph_store_f32(full) || full->n != fp4->n || full->dim != fp4->dim || full->metric != fp4->metric ||
       full->device != fp4->device || k == 0 || k > r) {
     ph_set_error("%s: needs the f32 store of the same n / dim / metric / device and 1 <= k <= r", call);
@@ -401,7 +236,7 @@ static int scan_search_check(const char *call, const phnsw_store *fp4, const phn
   }
   return 0;
 }
-static int scan_device_check(const char *call, const float *queries_dev, uint32_t ldq, uint32_t ld_min, bool aligned,
+int ph_fp4_scan_device_check(const char *call, const float *queries_dev, uint32_t ldq, uint32_t ld_min, bool aligned,
                              const void *ids, const void *d, const void *len) {
   if (!queries_dev || !ids || !d || !len || ldq < ld_min || (aligned && ((ldq % 4) || ((uintptr_t)queries_dev % 16)))) {
     ph_set_error("%s: invalid argument (queries and outputs not NULL; ldq >= %u%s)", call, ld_min,
@@ -412,9 +247,10 @@ static int scan_device_check(const char *call, const float *queries_dev, uint32_
 }
 
 // the host forms: queries checked and up as rows of `ld` floats (zero padded), the device form on the null stream, the
-// leading `k` of each row of r down as u64 ids (ph_take_launch)
-static int scan_host(const char *call, const phnsw_store *fp4, const phnsw_store *full, const float *queries, uint64_t nq,
-                     uint32_t r, uint32_t k, uint64_t *out_ids, float *out_d, uint64_t *out_len) {
+// leading `k` of each row of r down as u64 ids (ph_take_launch).  filter: nullptr, or the host words of the filtered forms
+int ph_fp4_scan_host(const char *call, const phnsw_store *fp4, const phnsw_store *full, const float *queries, uint64_t nq,
+                     uint32_t r, uint32_t k, const uint32_t *filter, uint32_t filter_stride, uint64_t *out_ids, float *out_d,
+                     uint64_t *out_len) {
   if (!queries || !out_ids || !out_d || !out_len) {
     ph_set_error("%s: queries and outputs must not be NULL", call);
     return PHNSW_E_INVALID;
@@ -427,9 +263,11 @@ static int scan_host(const char *call, const phnsw_store *fp4, const phnsw_store
   PH_HIP(hipSetDevice(fp4->device));
   const uint32_t ld = fp4->ld;
   float *qd = nullptr, *od = nullptr, *dk = nullptr;
-  uint32_t *oid = nullptr, *olen = nullptr;
+  uint32_t *oid = nullptr, *olen = nullptr, *fd = nullptr;
   uint64_t *ids64 = nullptr;
   int rc = 0;
+  // the filter's words as the device form reads them: one bitmap, or nq whole strides
+  const size_t filter_bytes = filter ? (filter_stride ? (size_t)nq * filter_stride : (size_t)ph_exact_words(fp4->n)) * 4u : 0u;
   hipError_t e = hipMalloc(&qd, (size_t)nq * ld * 4);
   if (e == hipSuccess && ld != fp4->dim) e = hipMemset(qd, 0, (size_t)nq * ld * 4);
   if (e == hipSuccess)
@@ -439,8 +277,10 @@ static int scan_host(const char *call, const phnsw_store *fp4, const phnsw_store
   if (e == hipSuccess) e = hipMalloc(&olen, nq * 4);
   if (e == hipSuccess) e = hipMalloc(&ids64, (size_t)nq * k * 8);
   if (e == hipSuccess) e = hipMalloc(&dk, (size_t)nq * k * 4);
+  if (e == hipSuccess && filter_bytes) e = hipMalloc(&fd, filter_bytes);
+  if (e == hipSuccess && filter_bytes) e = hipMemcpy(fd, filter, filter_bytes, hipMemcpyHostToDevice);
   if (e != hipSuccess) rc = ph_hip_fail(e, "fp4 scan staging", __FILE__, __LINE__);
-  if (!rc) rc = fp4_scan_device(fp4, qd, ld, nq, r, oid, od, olen, 0);
+  if (!rc) rc = ph_fp4_scan_enqueue(fp4, qd, ld, nq, r, fd, filter_stride, oid, od, olen, 0);
   if (!rc && full) rc = ph_rerank_launch(full, qd, ld, nq, r, k, olen, oid, od, 0);
   if (!rc) rc = ph_take_launch(oid, od, r, k, nq, ids64, dk, 0);
   if (!rc) {
@@ -452,7 +292,7 @@ static int scan_host(const char *call, const phnsw_store *fp4, const phnsw_store
     if (e != hipSuccess) rc = ph_hip_fail(e, "fp4 scan", __FILE__, __LINE__);
     for (uint64_t i = 0; !rc && i < nq; i++) out_len[i] = std::min<uint64_t>(h_len[i], k);
   }
-  for (void *p : {(void *)qd, (void *)od, (void *)dk, (void *)oid, (void *)olen, (void *)ids64})
+  for (void *p : {(void *)qd, (void *)od, (void *)dk, (void *)oid, (void *)olen, (void *)ids64, (void *)fd})
     if (p) hipFree(p);
   return rc;
 }
@@ -461,35 +301,35 @@ extern "C" int phnsw_fp4_scan_topk_device(const phnsw_store *fp4, const float *q
                                           uint64_t r, uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
                                           void *stream) try {
   const char *const call = "phnsw_fp4_scan_topk_device";
-  PH_TRY(scan_check(call, fp4, nq, r));
+  PH_TRY(ph_fp4_scan_check(call, fp4, nq, r));
   if (nq == 0) return 0;
-  PH_TRY(scan_device_check(call, queries_dev, ldq, fp4->dim, false, out_ids_dev, out_d_dev, out_len_dev));
-  return fp4_scan_device(fp4, queries_dev, ldq, nq, (uint32_t)r, out_ids_dev, out_d_dev, out_len_dev, (hipStream_t)stream);
+  PH_TRY(ph_fp4_scan_device_check(call, queries_dev, ldq, fp4->dim, false, out_ids_dev, out_d_dev, out_len_dev));
+  return ph_fp4_scan_enqueue(fp4, queries_dev, ldq, nq, (uint32_t)r, nullptr, 0u, out_ids_dev, out_d_dev, out_len_dev, (hipStream_t)stream);
 } catch (...) { return ph_caught(); }
 
 extern "C" int phnsw_fp4_scan_topk(const phnsw_store *fp4, const float *queries, uint64_t nq, uint64_t r, uint64_t *out_ids,
                                    float *out_d, uint64_t *out_len) try {
   const char *const call = "phnsw_fp4_scan_topk";
-  PH_TRY(scan_check(call, fp4, nq, r));
+  PH_TRY(ph_fp4_scan_check(call, fp4, nq, r));
   if (nq == 0) return 0;
-  return scan_host(call, fp4, nullptr, queries, nq, (uint32_t)r, (uint32_t)r, out_ids, out_d, out_len);
+  return ph_fp4_scan_host(call, fp4, nullptr, queries, nq, (uint32_t)r, (uint32_t)r, nullptr, 0u, out_ids, out_d, out_len);
 } catch (...) { return ph_caught(); }
 
 extern "C" int phnsw_fp4_scan_search_device(const phnsw_store *fp4, const phnsw_store *full, const float *queries_dev,
                                             uint32_t ldq, uint64_t nq, uint64_t r, uint64_t k, uint32_t *out_ids_dev,
                                             float *out_d_dev, uint32_t *out_len_dev, void *stream) try {
   const char *const call = "phnsw_fp4_scan_search_device";
-  PH_TRY(scan_search_check(call, fp4, full, nq, r, k));
+  PH_TRY(ph_fp4_scan_search_check(call, fp4, full, nq, r, k));
   if (nq == 0) return 0;
-  PH_TRY(scan_device_check(call, queries_dev, ldq, full->ld, true, out_ids_dev, out_d_dev, out_len_dev));
-  PH_TRY(fp4_scan_device(fp4, queries_dev, ldq, nq, (uint32_t)r, out_ids_dev, out_d_dev, out_len_dev, (hipStream_t)stream));
+  PH_TRY(ph_fp4_scan_device_check(call, queries_dev, ldq, full->ld, true, out_ids_dev, out_d_dev, out_len_dev));
+  PH_TRY(ph_fp4_scan_enqueue(fp4, queries_dev, ldq, nq, (uint32_t)r, nullptr, 0u, out_ids_dev, out_d_dev, out_len_dev, (hipStream_t)stream));
   return ph_rerank_launch(full, queries_dev, ldq, nq, (uint32_t)r, (uint32_t)k, out_len_dev, out_ids_dev, out_d_dev, (hipStream_t)stream);
 } catch (...) { return ph_caught(); }
 
 extern "C" int phnsw_fp4_scan_search(const phnsw_store *fp4, const phnsw_store *full, const float *queries, uint64_t nq,
                                      uint64_t r, uint64_t k, uint64_t *out_ids, float *out_d, uint64_t *out_len) try {
   const char *const call = "phnsw_fp4_scan_search";
-  PH_TRY(scan_search_check(call, fp4, full, nq, r, k));
+  PH_TRY(ph_fp4_scan_search_check(call, fp4, full, nq, r, k));
   if (nq == 0) return 0;
-  return scan_host(call, fp4, full, queries, nq, (uint32_t)r, (uint32_t)k, out_ids, out_d, out_len);
+  return ph_fp4_scan_host(call, fp4, full, queries, nq, (uint32_t)r, (uint32_t)k, nullptr, 0u, out_ids, out_d, out_len);
 } catch (...) { return ph_caught(); }
