@@ -1715,7 +1715,38 @@ int phnsw_fp4_scan_search_device(const phnsw_store *fp4, const phnsw_store *full
                                  uint64_t nq, uint64_t r, uint64_t k, uint32_t *out_ids_dev, float *out_d_dev,
                                  uint32_t *out_len_dev, void *stream);
 
-/* ---- the same scan restricted to an allow-list of rows (scan_fp4_filtered.hip) ----
+/* ---- exhaustive int8 scan over an i8q store on the matrix cores (scan_i8q.hip) ----
+ * Every row 0 .. n - 1 of a store made by phnsw_store_create_i8q is a candidate: no index, no filter, no exclude.  A raw
+ * query is quantised the way the rows were (scale = maxabs / 127, codes by the rows' quantiser: the bits the i8q
+ * searches give it) and the distance of a row is the store's own, finalize_metric((sq * sr) * (float)idot) with idot
+ * the exact int32 dot product of the codes.  An integer sum has no order, so the result is defined bit for bit:
+ * tests/i8q_reference.py restates it and the tests hold the scan to it with no tolerance.  It does not depend on
+ * tile size, slice count, the batch around a query or any knob (PHNSW_I8Q_SCAN_TILE, PHNSW_I8Q_SCAN_SLICES).
+ * phnsw_i8q_scan_topk: per query the min(r, n) rows with the smallest (distance, id), ascending.  Rows have r entries,
+ * padded with PHNSW_EMPTY / f32::MAX; out_len[q] = min(r, n).
+ * phnsw_i8q_scan_search: that scan for r candidates, then every candidate recomputed on `full` (true f32 distances, the
+ * bits of phnsw_distance_batch on it), sorted by (distance, id), the best k <= r kept.  Outputs are shaped like
+ * phnsw_fp4_scan_search[_device]'s: host rows [nq][k] u64, out_len[q] = min(len, k); device rows keep stride r, u32
+ * ids, the first min(len, k) live, enqueued on `stream` without a synchronisation.
+ * The device forms read queries_dev [nq][ldq], ldq >= dim; the search form wants the re-rank's ldq >= ld, a multiple of 4,
+ * and a 16-byte base.  They cannot see a NaN or infinite component: the rows of such a query are unspecified, every
+ * other query is unaffected.  The host forms refuse it (PHNSW_E_INVALID).
+ * 1 <= r <= 1024, n <= 2^31 - 1, nq <= 2^32 - 1, rows up to 1536 components.  Any store that is not an i8q store -- an
+ * i8 store too: the same bytes under an f32-query contract -- is PHNSW_E_UNSUPPORTED; r out of range, a NULL pointer,
+ * k == 0, k > r or a `full` that is not the f32 store of the same n / dim / metric / device is PHNSW_E_INVALID; every
+ * message names the call, and all of it is checked on the host before any launch.  nq == 0 is a no-op.  An i8q store
+ * is never L2 (phnsw_store_create_i8q refuses it), so no metric is refused here. */
+int phnsw_i8q_scan_topk(const phnsw_store *i8q, const float *queries, uint64_t nq, uint64_t r, uint64_t *out_ids,
+                        float *out_d, uint64_t *out_len);
+int phnsw_i8q_scan_topk_device(const phnsw_store *i8q, const float *queries_dev, uint32_t ldq, uint64_t nq, uint64_t r,
+                               uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev, void *stream);
+int phnsw_i8q_scan_search(const phnsw_store *i8q, const phnsw_store *full, const float *queries, uint64_t nq, uint64_t r,
+                          uint64_t k, uint64_t *out_ids, float *out_d, uint64_t *out_len);
+int phnsw_i8q_scan_search_device(const phnsw_store *i8q, const phnsw_store *full, const float *queries_dev, uint32_t ldq,
+                                 uint64_t nq, uint64_t r, uint64_t k, uint32_t *out_ids_dev, float *out_d_dev,
+                                 uint32_t *out_len_dev, void *stream);
+
+/* ---- the fp4 scan restricted to an allow-list of rows (scan_fp4_filtered.hip) ----
  * The four calls above with (filter, filter_stride_words) of phnsw_search_exact_filtered: bit v % 32 of word v / 32 set =
  * row v is allowed; filter_stride_words 0 = one bitmap of ceil(n / 32) words for the whole batch, else nq bitmaps that
  * far apart (>= ceil(n / 32), the last a whole stride); bits at or past n are ignored.  No index, label or attribute

@@ -194,7 +194,31 @@ class Comparator {
                               uint64_t k, uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev, void *stream) const {
     check(phnsw_fp4_scan_search_device(s_, full.s_, queries_dev, ldq, nq, r, k, out_ids_dev, out_d_dev, out_len_dev, stream));
   }
-  // the same four over an allow-list (phnsw_fp4_scan_topk_filtered / _search_filtered): filter holds packed bitmap words,
+  // a make_i8q comparator scanned exhaustively on the int8 matrix cores (phnsw_i8q_scan_topk): the queries are quantised
+  // as the rows were, the distance is the store's own (exact integer dot products); per query the min(r, n) rows with the
+  // smallest (distance, id); ids / d are [nq][r], len [nq]
+  void i8q_scan(const std::vector<float> &queries, uint64_t r, std::vector<uint64_t> &ids, std::vector<float> &d,
+                std::vector<uint64_t> &len) const {
+    const uint64_t nq = queries.size() / dim_;
+    ids.resize(nq * r), d.resize(nq * r), len.resize(nq);
+    check(phnsw_i8q_scan_topk(s_, queries.data(), nq, r, ids.data(), d.data(), len.data()));
+  }
+  void i8q_scan_device(const float *queries_dev, uint32_t ldq, uint64_t nq, uint64_t r, uint32_t *out_ids_dev,
+                       float *out_d_dev, uint32_t *out_len_dev, void *stream) const {
+    check(phnsw_i8q_scan_topk_device(s_, queries_dev, ldq, nq, r, out_ids_dev, out_d_dev, out_len_dev, stream));
+  }
+  // ... and re-ranked on the f32 comparator `full` (phnsw_i8q_scan_search): the best k <= r by true f32 distance, [nq][k]
+  void i8q_scan_search(const Comparator &full, const std::vector<float> &queries, uint64_t r, uint64_t k,
+                       std::vector<uint64_t> &ids, std::vector<float> &d, std::vector<uint64_t> &len) const {
+    const uint64_t nq = queries.size() / dim_;
+    ids.resize(nq * k), d.resize(nq * k), len.resize(nq);
+    check(phnsw_i8q_scan_search(s_, full.s_, queries.data(), nq, r, k, ids.data(), d.data(), len.data()));
+  }
+  void i8q_scan_search_device(const Comparator &full, const float *queries_dev, uint32_t ldq, uint64_t nq, uint64_t r,
+                              uint64_t k, uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev, void *stream) const {
+    check(phnsw_i8q_scan_search_device(s_, full.s_, queries_dev, ldq, nq, r, k, out_ids_dev, out_d_dev, out_len_dev, stream));
+  }
+  // the fp4 four over an allow-list (phnsw_fp4_scan_topk_filtered / _search_filtered): filter holds packed bitmap words,
   // bit v % 32 of word v / 32 allows row v; stride_words 0 = one bitmap of ceil(n / 32) words for the batch (compacted on
   // the device, only allowed rows are read), else one bitmap per query that many words apart (the full scan, masked).
   // Per query the min(r, allowed rows) allowed rows, every pair with the bits fp4_scan gives it

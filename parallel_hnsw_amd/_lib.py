@@ -297,6 +297,10 @@ SYMBOLS = {
     "phnsw_fp4_scan_topk_device": (_i32, [_vp, _vp, _u32, _u64, _u64, _vp, _vp, _vp, _vp]),
     "phnsw_fp4_scan_search": (_i32, [_vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp]),
     "phnsw_fp4_scan_search_device": (_i32, [_vp, _vp, _vp, _u32, _u64, _u64, _u64, _vp, _vp, _vp, _vp]),
+    "phnsw_i8q_scan_topk": (_i32, [_vp, _vp, _u64, _u64, _vp, _vp, _vp]),
+    "phnsw_i8q_scan_topk_device": (_i32, [_vp, _vp, _u32, _u64, _u64, _vp, _vp, _vp, _vp]),
+    "phnsw_i8q_scan_search": (_i32, [_vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp]),
+    "phnsw_i8q_scan_search_device": (_i32, [_vp, _vp, _vp, _u32, _u64, _u64, _u64, _vp, _vp, _vp, _vp]),
     "phnsw_fp4_scan_topk_filtered": (_i32, [_vp, _vp, _u64, _u64, _vp, _u32, _vp, _vp, _vp]),
     "phnsw_fp4_scan_topk_filtered_device": (_i32, [_vp, _vp, _u32, _u64, _u64, _vp, _u32, _vp, _vp, _vp, _vp]),
     "phnsw_fp4_scan_search_filtered": (_i32, [_vp, _vp, _vp, _u64, _u64, _u64, _vp, _u32, _vp, _vp, _vp]),

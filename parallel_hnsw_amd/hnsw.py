@@ -807,6 +807,42 @@ class I8QStore(_Int8Rows):
 
     _create = "phnsw_store_create_i8q"
 
+    def scan(self, queries, r):
+        """the exhaustive scan on the int8 matrix cores (phnsw_i8q_scan_topk): the queries are quantised as the rows
+        were, the distance is the store's own; per query the min(r, n) rows with the smallest (distance, id), bit for
+        bit tests/i8q_reference.py's, no index -> ids[nq, r] u64, d[nq, r] f32, len[nq]"""
+        q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+        assert q.shape[1] == self.dim
+        nq, r = q.shape[0], int(r)
+        ids = np.empty((nq, max(r, 0)), dtype=np.uint64)
+        d = np.empty((nq, max(r, 0)), dtype=np.float32)
+        ln = np.zeros(nq, dtype=np.uint64)
+        check(lib().phnsw_i8q_scan_topk(self._h, _p(q), nq, r, _p(ids), _p(d), _p(ln)))
+        return ids, d, ln
+
+    def scan_device(self, nq, r, queries, ldq, out_ids, out_d, out_len, stream=0):
+        """zero-copy form of scan (device pointers as ints, u32 ids, rows of r)"""
+        check(lib().phnsw_i8q_scan_topk_device(self._h, C.c_void_p(queries), ldq, nq, int(r), C.c_void_p(out_ids),
+                                                C.c_void_p(out_d), C.c_void_p(out_len), C.c_void_p(stream or None)))
+
+    def scan_search(self, full, queries, r, k=10):
+        """scan for r candidates, recompute each on the f32 store `full`, sort by (distance, id), keep the best k <= r
+        (phnsw_i8q_scan_search) -> ids[nq, k] u64, true f32 distances d[nq, k], len[nq]"""
+        q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+        assert q.shape[1] == self.dim
+        nq, r, k = q.shape[0], int(r), int(k)
+        ids = np.empty((nq, max(k, 0)), dtype=np.uint64)
+        d = np.empty((nq, max(k, 0)), dtype=np.float32)
+        ln = np.zeros(nq, dtype=np.uint64)
+        check(lib().phnsw_i8q_scan_search(self._h, full._h, _p(q), nq, r, k, _p(ids), _p(d), _p(ln)))
+        return ids, d, ln
+
+    def scan_search_device(self, full, nq, r, k, queries, ldq, out_ids, out_d, out_len, stream=0):
+        """zero-copy form of scan_search (device pointers as ints, u32 ids, rows of r: the first min(len, k) live)"""
+        check(lib().phnsw_i8q_scan_search_device(self._h, full._h, C.c_void_p(queries), ldq, nq, int(r), int(k),
+                                                  C.c_void_p(out_ids), C.c_void_p(out_d), C.c_void_p(out_len),
+                                                  C.c_void_p(stream or None)))
+
 
 class BitStore(VectorStore):
     """one sign bit per component of an f32 VectorStore (phnsw_store_create_bits): bit j of a row is row[j] < 0, 96

@@ -245,6 +245,49 @@ impl GpuComparator {
         });
     }
 
+    /// A `to_i8q()` comparator scanned exhaustively on the int8 matrix cores (`phnsw_i8q_scan_topk`): the queries are
+    /// quantised as the rows were and the distance is the store's own, exact integer dot products; per query the
+    /// `min(r, n)` rows with the smallest (distance, id).  No index.
+    pub fn i8q_scan(&self, queries: &[Vec<f32>], r: usize) -> Vec<Vec<(VectorId, f32)>> {
+        let nq = queries.len();
+        let q: Vec<f32> = queries.iter().flatten().copied().collect();
+        let (mut ids, mut d, mut len) = (vec![0u64; nq * r], vec![0f32; nq * r], vec![0u64; nq]);
+        check(unsafe {
+            sys::phnsw_i8q_scan_topk(self.store.0, q.as_ptr(), nq as u64, r as u64, ids.as_mut_ptr(), d.as_mut_ptr(),
+                                      len.as_mut_ptr())
+        });
+        (0..nq).map(|i| (0..len[i] as usize).map(|j| (VectorId(ids[i * r + j] as usize), d[i * r + j])).collect()).collect()
+    }
+
+    /// `i8q_scan` for `r` candidates, re-ranked on the f32 comparator `full` (`phnsw_i8q_scan_search`): the best
+    /// `k <= r` by true f32 distance
+    pub fn i8q_scan_search(&self, full: &GpuComparator, queries: &[Vec<f32>], r: usize, k: usize) -> Vec<Vec<(VectorId, f32)>> {
+        let nq = queries.len();
+        let q: Vec<f32> = queries.iter().flatten().copied().collect();
+        let (mut ids, mut d, mut len) = (vec![0u64; nq * k], vec![0f32; nq * k], vec![0u64; nq]);
+        check(unsafe {
+            sys::phnsw_i8q_scan_search(self.store.0, full.store.0, q.as_ptr(), nq as u64, r as u64, k as u64,
+                                        ids.as_mut_ptr(), d.as_mut_ptr(), len.as_mut_ptr())
+        });
+        (0..nq).map(|i| (0..len[i] as usize).map(|j| (VectorId(ids[i * k + j] as usize), d[i * k + j])).collect()).collect()
+    }
+
+    /// zero-copy forms (`phnsw_i8q_scan_topk_device`; with `full`, `phnsw_i8q_scan_search_device` and its `k`)
+    ///
+    /// # Safety
+    /// the pointers must be valid device allocations of the sizes `phnsw.h` documents for the call
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn i8q_scan_device(&self, full: Option<(&GpuComparator, u64)>, queries_dev: *const f32, ldq: u32, nq: u64,
+                                   r: u64, out_ids_dev: *mut u32, out_d_dev: *mut f32, out_len_dev: *mut u32,
+                                   stream: *mut c_void) {
+        check(match full {
+            None => sys::phnsw_i8q_scan_topk_device(self.store.0, queries_dev, ldq, nq, r, out_ids_dev, out_d_dev, out_len_dev,
+                                                     stream),
+            Some((f, k)) => sys::phnsw_i8q_scan_search_device(self.store.0, f.store.0, queries_dev, ldq, nq, r, k, out_ids_dev,
+                                                               out_d_dev, out_len_dev, stream),
+        });
+    }
+
     /// `fp4_scan` over an allow-list (`phnsw_fp4_scan_topk_filtered`; with `full`, `phnsw_fp4_scan_search_filtered` and
     /// its `k`): `filter` holds packed bitmap words, bit `v % 32` of word `v / 32` allows row `v`; `stride_words` 0 = one
     /// bitmap of `ceil(n / 32)` words for the batch, else one per query that many words apart.  Per query the allowed rows

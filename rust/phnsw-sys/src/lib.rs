@@ -709,7 +709,18 @@ extern "C" {
     pub fn phnsw_fp4_scan_search_device(fp4: *const phnsw_store, full: *const phnsw_store, queries_dev: *const c_float,
                                         ldq: u32, nq: u64, r: u64, k: u64, out_ids_dev: *mut u32,
                                         out_d_dev: *mut c_float, out_len_dev: *mut u32, stream: *mut c_void) -> c_int;
-    // the same four over an allow-list: one packed bitmap (filter_stride_words 0) or one per query
+    // ---- exhaustive int8 scan over an i8q store (int8 MFMA, exact integer dots), alone and with the re-rank on the f32 store
+    pub fn phnsw_i8q_scan_topk(i8q: *const phnsw_store, queries: *const c_float, nq: u64, r: u64, out_ids: *mut u64,
+                               out_d: *mut c_float, out_len: *mut u64) -> c_int;
+    pub fn phnsw_i8q_scan_topk_device(i8q: *const phnsw_store, queries_dev: *const c_float, ldq: u32, nq: u64, r: u64,
+                                      out_ids_dev: *mut u32, out_d_dev: *mut c_float, out_len_dev: *mut u32,
+                                      stream: *mut c_void) -> c_int;
+    pub fn phnsw_i8q_scan_search(i8q: *const phnsw_store, full: *const phnsw_store, queries: *const c_float, nq: u64,
+                                 r: u64, k: u64, out_ids: *mut u64, out_d: *mut c_float, out_len: *mut u64) -> c_int;
+    pub fn phnsw_i8q_scan_search_device(i8q: *const phnsw_store, full: *const phnsw_store, queries_dev: *const c_float,
+                                        ldq: u32, nq: u64, r: u64, k: u64, out_ids_dev: *mut u32,
+                                        out_d_dev: *mut c_float, out_len_dev: *mut u32, stream: *mut c_void) -> c_int;
+    // the fp4 four over an allow-list: one packed bitmap (filter_stride_words 0) or one per query
     pub fn phnsw_fp4_scan_topk_filtered(fp4: *const phnsw_store, queries: *const c_float, nq: u64, r: u64,
                                         filter: *const u32, filter_stride_words: u32, out_ids: *mut u64,
                                         out_d: *mut c_float, out_len: *mut u64) -> c_int;
