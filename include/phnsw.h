@@ -1777,6 +1777,37 @@ int phnsw_fp4_scan_search_filtered_device(const phnsw_store *fp4, const phnsw_st
                                           uint32_t filter_stride_words, uint32_t *out_ids_dev, float *out_d_dev,
                                           uint32_t *out_len_dev, void *stream);
 
+/* ---- the int8 scan restricted to an allow-list of rows (scan_i8q_filtered.hip) ----
+ * The four phnsw_i8q_scan_* calls with the (filter, filter_stride_words) of the fp4 calls above, argument for argument:
+ * bit v % 32 of word v / 32 set = row v is allowed; filter_stride_words 0 = one bitmap of ceil(n / 32) words for the whole
+ * batch, else nq bitmaps that far apart (>= ceil(n / 32), the last a whole stride); bits at or past n are ignored.
+ * Contract: the unfiltered int8 scan's, restricted to the allowed rows.  The query is quantised the same way, idot is the
+ * exact int32 dot product and the distance ph_i8q_distance of it; an integer sum has no order, so every returned
+ * (id, distance) has exactly the bits the unfiltered scan computes for that pair, whatever the tile, the slices, the batch
+ * or the form.  Per query the min(r, allowed rows) allowed rows with the smallest (distance, id), ascending; a disallowed
+ * row is never returned; out_len[q] = min(r, allowed rows of q), rows padded as above.  The _search forms re-rank those
+ * candidates on `full` as above.
+ * How it runs: a shared bitmap is compacted on the device into an ascending row list and only listed rows are staged
+ * (cost proportional to the allowed rows); per-query bitmaps scan every row and test a row's bit only when its dot
+ * product passes the query's threshold.  Neither form, nor PHNSW_I8Q_SCAN_TILE / PHNSW_I8Q_SCAN_SLICES, changes a result.
+ * Refusals as for the unfiltered calls, naming the call; in addition a NULL filter (the unfiltered calls exist for that)
+ * or a stride between 1 and ceil(n / 32) - 1 is PHNSW_E_INVALID.  nq == 0 is a no-op.  The host forms read `filter` from
+ * host memory, the device forms from device memory (filter_dev must stay unchanged until the work enqueued on `stream`
+ * has run). */
+int phnsw_i8q_scan_topk_filtered(const phnsw_store *i8q, const float *queries, uint64_t nq, uint64_t r,
+                                 const uint32_t *filter, uint32_t filter_stride_words, uint64_t *out_ids, float *out_d,
+                                 uint64_t *out_len);
+int phnsw_i8q_scan_topk_filtered_device(const phnsw_store *i8q, const float *queries_dev, uint32_t ldq, uint64_t nq,
+                                        uint64_t r, const uint32_t *filter_dev, uint32_t filter_stride_words,
+                                        uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev, void *stream);
+int phnsw_i8q_scan_search_filtered(const phnsw_store *i8q, const phnsw_store *full, const float *queries, uint64_t nq,
+                                   uint64_t r, uint64_t k, const uint32_t *filter, uint32_t filter_stride_words,
+                                   uint64_t *out_ids, float *out_d, uint64_t *out_len);
+int phnsw_i8q_scan_search_filtered_device(const phnsw_store *i8q, const phnsw_store *full, const float *queries_dev,
+                                          uint32_t ldq, uint64_t nq, uint64_t r, uint64_t k, const uint32_t *filter_dev,
+                                          uint32_t filter_stride_words, uint32_t *out_ids_dev, float *out_d_dev,
+                                          uint32_t *out_len_dev, void *stream);
+
 /* ---- on-disk interchange with the Rust crate: serialize_hnsw / deserialize_hnsw
  * (src/serialize.rs:33-209): <dir>/meta (JSON HNSWMeta), <dir>/comparator/ (this library's
  * store; a crate user substitutes their own Serializable comparator), layer.meta.N (JSON),

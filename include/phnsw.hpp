@@ -248,6 +248,35 @@ class Comparator {
     check(phnsw_fp4_scan_search_filtered_device(s_, full.s_, queries_dev, ldq, nq, r, k, filter_dev, stride_words, out_ids_dev,
                                                 out_d_dev, out_len_dev, stream));
   }
+  // the i8q four over an allow-list (phnsw_i8q_scan_topk_filtered / _search_filtered): filter and stride_words as for
+  // fp4_scan_filtered (0 = one bitmap for the batch: only allowed rows are staged; else one per query: the full scan,
+  // masked).  Per query the min(r, allowed rows) allowed rows, every pair with the bits i8q_scan gives it
+  void i8q_scan_filtered(const std::vector<float> &queries, uint64_t r, const std::vector<uint32_t> &filter, uint32_t stride_words,
+                         std::vector<uint64_t> &ids, std::vector<float> &d, std::vector<uint64_t> &len) const {
+    const uint64_t nq = queries.size() / dim_;
+    ids.resize(nq * r), d.resize(nq * r), len.resize(nq);
+    check(phnsw_i8q_scan_topk_filtered(s_, queries.data(), nq, r, filter.data(), stride_words, ids.data(), d.data(), len.data()));
+  }
+  void i8q_scan_filtered_device(const float *queries_dev, uint32_t ldq, uint64_t nq, uint64_t r, const uint32_t *filter_dev,
+                                uint32_t stride_words, uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
+                                void *stream) const {
+    check(phnsw_i8q_scan_topk_filtered_device(s_, queries_dev, ldq, nq, r, filter_dev, stride_words, out_ids_dev, out_d_dev,
+                                              out_len_dev, stream));
+  }
+  void i8q_scan_search_filtered(const Comparator &full, const std::vector<float> &queries, uint64_t r, uint64_t k,
+                                const std::vector<uint32_t> &filter, uint32_t stride_words, std::vector<uint64_t> &ids,
+                                std::vector<float> &d, std::vector<uint64_t> &len) const {
+    const uint64_t nq = queries.size() / dim_;
+    ids.resize(nq * k), d.resize(nq * k), len.resize(nq);
+    check(phnsw_i8q_scan_search_filtered(s_, full.s_, queries.data(), nq, r, k, filter.data(), stride_words, ids.data(), d.data(),
+                                         len.data()));
+  }
+  void i8q_scan_search_filtered_device(const Comparator &full, const float *queries_dev, uint32_t ldq, uint64_t nq, uint64_t r,
+                                       uint64_t k, const uint32_t *filter_dev, uint32_t stride_words, uint32_t *out_ids_dev,
+                                       float *out_d_dev, uint32_t *out_len_dev, void *stream) const {
+    check(phnsw_i8q_scan_search_filtered_device(s_, full.s_, queries_dev, ldq, nq, r, k, filter_dev, stride_words, out_ids_dev,
+                                                out_d_dev, out_len_dev, stream));
+  }
   // codes [n][dim] and scales [n] of a comparator made by make_i8 or make_i8q (phnsw_i8_read)
   void read_i8(std::vector<int8_t> &codes, std::vector<float> &scales) const {
     codes.resize(n_ * dim_);

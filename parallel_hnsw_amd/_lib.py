@@ -305,6 +305,10 @@ SYMBOLS = {
     "phnsw_fp4_scan_topk_filtered_device": (_i32, [_vp, _vp, _u32, _u64, _u64, _vp, _u32, _vp, _vp, _vp, _vp]),
     "phnsw_fp4_scan_search_filtered": (_i32, [_vp, _vp, _vp, _u64, _u64, _u64, _vp, _u32, _vp, _vp, _vp]),
     "phnsw_fp4_scan_search_filtered_device": (_i32, [_vp, _vp, _vp, _u32, _u64, _u64, _u64, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "phnsw_i8q_scan_topk_filtered": (_i32, [_vp, _vp, _u64, _u64, _vp, _u32, _vp, _vp, _vp]),
+    "phnsw_i8q_scan_topk_filtered_device": (_i32, [_vp, _vp, _u32, _u64, _u64, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "phnsw_i8q_scan_search_filtered": (_i32, [_vp, _vp, _vp, _u64, _u64, _u64, _vp, _u32, _vp, _vp, _vp]),
+    "phnsw_i8q_scan_search_filtered_device": (_i32, [_vp, _vp, _vp, _u32, _u64, _u64, _u64, _vp, _u32, _vp, _vp, _vp, _vp]),
     "phnsw_bits_search_batch": (_i32, [_vp, _vp, _vp, _u64, C.POINTER(SearchParams), _u64, _vp, _vp, _vp]),
     "phnsw_bits_search_batch_device": (_i32, [_vp, _vp, _vp, _u32, _u64, C.POINTER(SearchParams), _u64, _vp, _vp, _vp,
                                               _vp, _vp, _vp]),

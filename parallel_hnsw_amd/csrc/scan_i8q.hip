@@ -1,7 +1,9 @@
 // The exhaustive int8 scan over an i8q store (PH_ROWS_I8Q, rowstore.hip) on the matrix cores:
 // phnsw_i8q_scan_topk[_device], the r rows nearest each query by the store's own distance, and
 // phnsw_i8q_scan_search[_device], that scan followed by the f32 re-rank of pq.hip.  No index, no filter, no exclude:
-// every row 0 .. n - 1 is a candidate.  An i8q store is never L2.
+// every row 0 .. n - 1 is a candidate.  An i8q store is never L2.  The scan kernel's body is scan_i8q_kernel.h's,
+// instantiated here in its PLAIN form; the forms over an allow-list and their entry points are scan_i8q_filtered.hip's,
+// which run through this file's launcher, scratch, merge kernel and host staging.
 //
 //   result of a query = the min(r, n) rows with the smallest (ph_i8q_distance(sq, sr, idot, metric), id), ascending.
 //   idot              = the exact int32 dot product of the query's codes (ph_i8_scale / ph_i8_quant, the bits of
@@ -41,49 +43,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "exact_topk_wave.h"
-#include "i8q_scan_plan.h"
-#include "phnsw_device.h"
-
-#ifndef PH_TRY
-#define PH_TRY(x)          \
-  do {                     \
-    int rc__ = (x);        \
-    if (rc__) return rc__; \
-  } while (0)
-#endif
-
-typedef int ph_v4i __attribute__((ext_vector_type(4)));
-
-struct PhI8qScanArgs {
-  const uint8_t *rows;   // n rows of `stride` bytes: f32 scale, codes (RowI8)
-  const uint8_t *qimg;   // [nq][ph_i8q_scan_query_bytes(steps)]
-  const float *qscale;   // [nq]
-  uint32_t stride, runs, steps, tile_groups;  // runs: 16-byte runs of a row that exist; stride >= 16 runs
-  uint32_t nq, n, k;     // k: the r of the call (the name ph_exact_write_row reads)
-  int metric;
-  uint32_t qtiles, slices, stage;
-  uint64_t row_tiles;
-  uint64_t *lists;    // [qtiles * slices][64][2 k]: the running top-r of every (query, slice)
-  uint64_t *scratch;  // slices > 1: [nq][slices][k] keys, each list ascending, KEY_NONE padded
-  uint32_t *out_ids;  // [nq][k]
-  float *out_d;
-  uint32_t *out_len, *status;  // [nq]
-};
-
-// the per-query state of a wave in LDS, four words
-struct PhI8qScanState {
-  uint32_t staged, len, flip;
-  float smin;
-};
-
-template <int I, int N, class F>
-__device__ __forceinline__ void ph_i8q_static_for(F &&f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>());
-    ph_i8q_static_for<I + 1, N>(f);
-  }
-}
+#include "scan_i8q_kernel.h"
 
 // one wave per query: the query's scale and its image -- four zero bytes, then the codes by the store's own quantiser
 // (component order = byte order, as ph_i8_convert_kernel writes a row), zeros to the end of the last step
@@ -111,134 +71,9 @@ __global__ __launch_bounds__(256) void ph_i8q_scan_query_kernel(const float *__r
   }
 }
 
-// S: the step class; RG: the largest row tile of the class, in groups (ph_i8q_scan_tile_cap)
 template <int S, int RG>
 __global__ __launch_bounds__(256) void ph_i8q_scan_kernel(PhI8qScanArgs a) {
-  extern __shared__ uint64_t scan_lds[];
-  constexpr int NL = (16 * RG * 4 * S + 255) / 256;  // ph_i8q_scan_loads
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6, col = lane & 15u, kb = lane >> 4;
-  const uint32_t pitch = ph_i8q_scan_pitch(a.steps), tile_bytes = 16u * a.tile_groups * pitch;
-  uint8_t *const tiles = (uint8_t *)scan_lds;  // [2][16 tile_groups][pitch]
-  uint64_t *const stage = scan_lds + (2u * tile_bytes + w * ph_i8q_scan_wave_bytes(a.k)) / 8u;  // [16][a.stage], this wave's
-  uint64_t *const sv = stage + 16u * a.stage;                                                   // [64]
-  PhI8qScanState *const state = (PhI8qScanState *)(sv + 64);                                    // [16]
-  const uint32_t qtile = blockIdx.x % a.qtiles, slice = blockIdx.x / a.qtiles;
-  const uint32_t q0 = qtile * PH_I8Q_SCAN_QTILE + 16u * w;  // this wave's first query
-  const uint32_t tq = q0 < a.nq ? min(16u, a.nq - q0) : 0u;
-  uint64_t *const lists = a.lists + ((uint64_t)blockIdx.x * PH_I8Q_SCAN_QTILE + 16u * w) * 2u * a.k;
-  const bool half = a.metric == PHNSW_METRIC_COSINE_HALF;
-  if (lane < 16u) state[lane] = PhI8qScanState{0u, 0u, 0u, lane < tq ? -INFINITY : INFINITY};
-  ph_wave_sync();
-
-  // the wave's queries: lane's run 4 s + kb of query column `col`; past the last query the last again
-  const uint32_t q = min(q0 + col, a.nq - 1u);
-  ph_v4i qc[S];
-#pragma unroll
-  for (int s = 0; s < S; s++)
-    qc[s] = (uint32_t)s < a.steps ? *(const ph_v4i *)(a.qimg + (uint64_t)q * ph_i8q_scan_query_bytes(a.steps) + 16u * (4u * s + kb))
-                                  : ph_v4i{0, 0, 0, 0};
-  const float sq = a.qscale[q];
-  float smin = col < tq ? -INFINITY : INFINITY;
-
-  // staging: the tile's 16 tile_groups x runs runs dealt to the threads in order, (row of the tile) << 16 | run; a
-  // thread with nothing to move in a round loads row 0's first run again and drops it (bit 31)
-  const uint32_t per_tile = 16u * a.tile_groups * a.runs;
-  uint32_t lpos[NL];
-#pragma unroll
-  for (int i = 0; i < NL; i++) {
-    const uint32_t idx = tid + 256u * i;
-    lpos[i] = idx < per_tile ? ((idx / a.runs) << 16) | (idx % a.runs) : 0x80000000u;
-  }
-  ph_v4i x[NL];
-  auto fetch = [&](uint64_t tile) {
-    const uint32_t base = (uint32_t)(tile * 16u * a.tile_groups);
-#pragma unroll
-    for (int i = 0; i < NL; i++)
-      x[i] = *(const ph_v4i *)(a.rows + (uint64_t)min(base + ((lpos[i] >> 16) & 0x7FFFu), a.n - 1u) * a.stride + 16u * (lpos[i] & 0xFFFFu));
-  };
-  auto put = [&](uint32_t buf) {
-#pragma unroll
-    for (int i = 0; i < NL; i++)
-      if (!(lpos[i] >> 31)) *(ph_v4i *)(tiles + buf * tile_bytes + (lpos[i] >> 16) * pitch + 16u * (lpos[i] & 0xFFFFu)) = x[i];
-  };
-
-  // the staged keys of query t into its running top-r; its threshold afterwards.  Whole wave, uniform control flow.
-  auto flush = [&](uint32_t t) {
-    PhI8qScanState *const st = state + t;
-    const uint32_t staged = rfl32(st->staged);
-    const uint64_t key = lane < staged ? stage[t * a.stage + lane] : KEY_NONE;
-    PhWaveTopK top;
-    top.cur = lists + (uint64_t)t * 2u * a.k, top.nxt = top.cur + a.k, top.sv = sv, top.k = a.k;
-    if (rfl32(st->flip)) {
-      uint64_t *const c = top.cur;
-      top.cur = top.nxt, top.nxt = c;
-    }
-    top.len = rfl32(st->len);
-    ph_wave_sync();  // the state read above is rewritten below
-    top.insert(key, lane);
-    ph_wave_sync();  // (insert returns without one when nothing survived)
-    if (lane == 0) {
-      st->len = top.len;
-      st->flip = top.cur == lists + (uint64_t)t * 2u * a.k ? 0u : 1u;
-      st->staged = 0u;
-      st->smin = top.len == a.k ? ph_fp4_scan_smin(unfkey((uint32_t)(top.cur[a.k - 1u] >> 32)), half) : -INFINITY;
-    }
-    ph_wave_sync();
-  };
-
-  // one row group of a staged tile: rows row0 .. row0 + 15 at `grp` in LDS
-  auto scan = [&](const uint8_t *grp, uint32_t row0) {
-    ph_v4i acc = {0, 0, 0, 0};
-    const uint8_t *src = grp + col * pitch + 16u * kb;
-    ph_i8q_static_for<0, S>([&](auto sc) {
-      constexpr int s = decltype(sc)::value;
-      if ((uint32_t)s < a.steps)  // wave-uniform
-        acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(*(const ph_v4i *)(src + 64u * s), qc[s], acc, 0, 0, 0);
-    });
-    float sr[4], dot[4];
-    bool any = false;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      sr[i] = *(const float *)(grp + (4u * kb + i) * pitch);  // the row's scale, staged with its codes
-      dot[i] = __fmul_rn(__fmul_rn(sq, sr[i]), (float)acc[i]);
-      any |= dot[i] >= smin;
-    }
-    if (!__ballot(any)) return;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const uint32_t id = row0 + 4u * kb + i;
-      if (id < a.n && dot[i] >= smin) {  // (smin of a query past the last is +inf)
-        const uint32_t slot = atomicAdd(&state[col].staged, 1u);  // < a.stage: at most 16 rows on top of stage - 16
-        stage[col * a.stage + slot] = mkkey(ph_i8q_distance(sq, sr[i], acc[i], a.metric), id);
-      }
-    }
-    ph_wave_sync();
-    uint64_t full = __ballot(lane < 16u && state[lane & 15u].staged + 16u > a.stage);
-    if (!full) return;
-    for (; full; full &= full - 1ull) flush((uint32_t)__ffsll((unsigned long long)full) - 1u);
-    smin = state[col].smin;
-  };
-
-  uint64_t t0, t1;
-  ph_exact_slice_range(slice, a.slices, a.row_tiles, &t0, &t1);
-  if (t0 < t1) {  // workgroup-uniform
-    fetch(t0);
-    uint32_t buf = 0u;
-    for (uint64_t t = t0; t < t1; t++, buf ^= 1u) {
-      put(buf);
-      __syncthreads();  // the tile is whole; and every wave is done with the buffer the NEXT put rewrites
-      if (t + 1u < t1) fetch(t + 1u);
-      if (tq)  // (a wave of a partial last query tile has no query: it only stages)
-        for (uint32_t g = 0; g < a.tile_groups; g++)
-          scan(tiles + buf * tile_bytes + g * 16u * pitch, (uint32_t)(t * a.tile_groups + g) * 16u);
-    }
-  }
-  for (uint32_t t = 0; t < tq; t++) {
-    PhI8qScanState *const st = state + t;
-    if (rfl32(st->staged)) flush(t);
-    ph_exact_write_slice<false>(a, q0 + t, q0 + t, slice, lists + (uint64_t)t * 2u * a.k + (rfl32(st->flip) ? a.k : 0u), rfl32(st->len),
-                                false, lane);
-  }
+  ph_i8q_scan_body<S, RG, PH_I8Q_SCAN_PLAIN>(a);
 }
 
 // One wave per query: the slices' ascending lists merged through the same running top-r.
@@ -256,7 +91,6 @@ __global__ __launch_bounds__(64) void ph_i8q_scan_merge_kernel(PhI8qScanArgs a) 
 
 // ------------------------------------------------------------------ launchers
 
-typedef void (*PhI8qScanFn)(PhI8qScanArgs);
 static PhI8qScanFn scan_fn(int cls) {  // the tile caps are ph_i8q_scan_tile_cap's
   switch (cls) {
     case 2: return ph_i8q_scan_kernel<2, 4>;
@@ -307,17 +141,22 @@ int scratch_acquire(int device, size_t bytes, hipStream_t stream, ScanScratch **
 size_t up256(size_t b) { return (b + 255u) & ~(size_t)255u; }
 }  // namespace
 
-// the scan of nq device queries on `stream` (arguments checked by the caller): rows [nq][r] u32 ids and distances, len
-static int i8q_scan_enqueue(const phnsw_store *s, const float *queries_dev, uint32_t ldq, uint64_t nq, uint32_t r,
-                            uint32_t *out_ids, float *out_d, uint32_t *out_len, hipStream_t stream) {
+// the scan of nq device queries on `stream` (arguments checked by the caller): rows [nq][r] u32 ids and distances, len.
+// filter_dev: nullptr = every row (the plain form); one bitmap (filter_stride 0: compacted here, the LIST form) or nq
+// bitmaps filter_stride words apart (the MASK form), scan_i8q_filtered.hip
+int ph_i8q_scan_enqueue(const phnsw_store *s, const float *queries_dev, uint32_t ldq, uint64_t nq, uint32_t r,
+                        const uint32_t *filter_dev, uint32_t filter_stride, uint32_t *out_ids, float *out_d, uint32_t *out_len,
+                        hipStream_t stream) {
   if (nq == 0) return 0;
   PH_HIP(hipSetDevice(s->device));
   const uint32_t steps = ph_i8q_scan_steps(s->ld), runs = ph_i8q_scan_runs(s->ld);
   const int cls = s->ld <= PH_I8Q_SCAN_LD_MAX ? ph_i8q_scan_class(steps) : 0;
-  const PhI8qScanFn fn = scan_fn(cls);
+  const int form = !filter_dev ? PH_I8Q_SCAN_PLAIN : (filter_stride ? PH_I8Q_SCAN_MASK : PH_I8Q_SCAN_LIST);
+  const PhI8qScanFn fn = form == PH_I8Q_SCAN_PLAIN ? scan_fn(cls) : ph_i8q_scan_filtered_fn(cls, form);
   if (!fn || s->packed_stride < 16u * runs || s->packed_stride % 16u) return ph_dim_unsupported(s->dim);
   const uint32_t tg = ph_i8q_scan_tile(cls, env_ll("PHNSW_I8Q_SCAN_TILE"));  // tests and tuning: neither changes a result
-  const size_t lds = ph_i8q_scan_lds(r, steps, tg), merge_lds = ph_i8q_scan_merge_lds(r);
+  const size_t lds = form == PH_I8Q_SCAN_LIST ? ph_i8q_scan_list_lds(r, steps, tg) : ph_i8q_scan_lds(r, steps, tg);
+  const size_t merge_lds = ph_i8q_scan_merge_lds(r);
   uint64_t resident = 0;  // workgroups of the scan the device holds at once (LDS decides, so the probe's block size does not)
   PhResidentMemo *memo;
   {
@@ -334,7 +173,10 @@ static int i8q_scan_enqueue(const phnsw_store *s, const float *queries_dev, uint
   const size_t scale_bytes = up256((size_t)chunk * 4u), status_bytes = up256((size_t)chunk * 4u);
   const size_t lists_bytes = up256((size_t)chunk_tiles * PH_I8Q_SCAN_QTILE * slices * 2u * r * 8u);
   const size_t merge_bytes = slices > 1u ? up256((size_t)chunk * slices * r * 8u) : 0u;  // together: ph_i8q_scan_scratch_bytes
-  const size_t bytes = img_bytes + scale_bytes + status_bytes + lists_bytes + merge_bytes;
+  // LIST: the compaction's words behind everything else.  The slices were cut from all the row tiles of n, the kernel
+  // cuts the list's own; what is left over is empty slices
+  const size_t pre_bytes = form == PH_I8Q_SCAN_LIST ? up256(ph_fp4_scan_pre_bytes(s->n)) : 0u;
+  const size_t bytes = img_bytes + scale_bytes + status_bytes + lists_bytes + merge_bytes + pre_bytes;
 
   std::lock_guard<std::mutex> g(g_mutex);
   ScanScratch *x = nullptr;
@@ -348,9 +190,16 @@ static int i8q_scan_enqueue(const phnsw_store *s, const float *queries_dev, uint
   a.status = (uint32_t *)at_mem, at_mem += status_bytes;
   a.lists = (uint64_t *)at_mem, at_mem += lists_bytes;
   a.scratch = (uint64_t *)at_mem, at_mem += merge_bytes;
+  if (form == PH_I8Q_SCAN_LIST) {  // once for all chunks
+    uint32_t *const pre = (uint32_t *)at_mem;
+    PH_TRY(ph_fp4_scan_list_enqueue(filter_dev, s->n, pre, stream));
+    a.count = pre, a.cand = pre + ph_fp4_scan_pre_list(s->n);
+  }
+  a.filter_stride = filter_stride;
   for (uint64_t at = 0; at < nq; at += chunk) {
     const uint64_t cnt = std::min(chunk, nq - at);
     a.nq = (uint32_t)cnt, a.qtiles = (uint32_t)ph_i8q_scan_qtiles(cnt);
+    if (form == PH_I8Q_SCAN_MASK) a.filter = filter_dev + at * filter_stride;
     a.out_ids = out_ids + at * r, a.out_d = out_d + at * r, a.out_len = out_len + at;
     hipLaunchKernelGGL(ph_i8q_scan_query_kernel, dim3((uint32_t)std::min<uint64_t>((cnt + 3u) / 4u, 1u << 16)), dim3(256), 0, stream,
                        queries_dev + at * ldq, ldq, s->dim, (uint32_t)cnt, steps, (uint32_t *)a.qimg, (float *)a.qscale);
@@ -366,7 +215,7 @@ static int i8q_scan_enqueue(const phnsw_store *s, const float *queries_dev, uint
 // ------------------------------------------------------------------ entry points
 
 // what all four calls ask of the store and of r (an i8q store is never L2: phnsw_store_create_i8q refuses it)
-static int i8q_scan_check(const char *call, const phnsw_store *i8q, uint64_t nq, uint64_t r) {
+int ph_i8q_scan_check(const char *call, const phnsw_store *i8q, uint64_t nq, uint64_t r) {
   if (!i8q || i8q->kind != PH_ROWS_I8Q) {
     ph_set_error("%s: needs an i8q store (phnsw_store_create_i8q), not %s", call, i8q ? ph_rows_name(i8q->kind) : "NULL");
     return PHNSW_E_UNSUPPORTED;
@@ -378,9 +227,8 @@ static int i8q_scan_check(const char *call, const phnsw_store *i8q, uint64_t nq,
   return 0;
 }
 // ... and the searches of `full` and k: what rerank_check (pq.hip) demands of a converted store
-static int i8q_scan_search_check(const char *call, const phnsw_store *i8q, const phnsw_store *full, uint64_t nq, uint64_t r,
-                                 uint64_t k) {
-  PH_TRY(i8q_scan_check(call, i8q, nq, r));
+int ph_i8q_scan_search_check(const char *call, const phnsw_store *i8q, const phnsw_store *full, uint64_t nq, uint64_t r, uint64_t k) {
+  PH_TRY(ph_i8q_scan_check(call, i8q, nq, r));
   if (!full || !ph_store_f32(full) || full->n != i8q->n || full->dim != i8q->dim || full->metric != i8q->metric ||
       full->device != i8q->device || k == 0 || k > r) {
     ph_set_error("%s: needs the f32 store of the same n / dim / metric / device and 1 <= k <= r", call);
@@ -388,8 +236,8 @@ static int i8q_scan_search_check(const char *call, const phnsw_store *i8q, const
   }
   return 0;
 }
-static int i8q_scan_device_check(const char *call, const float *queries_dev, uint32_t ldq, uint32_t ld_min, bool aligned,
-                                 const void *ids, const void *d, const void *len) {
+int ph_i8q_scan_device_check(const char *call, const float *queries_dev, uint32_t ldq, uint32_t ld_min, bool aligned,
+                             const void *ids, const void *d, const void *len) {
   if (!queries_dev || !ids || !d || !len || ldq < ld_min || (aligned && ((ldq % 4) || ((uintptr_t)queries_dev % 16)))) {
     ph_set_error("%s: invalid argument (queries and outputs not NULL; ldq >= %u%s)", call, ld_min,
                  aligned ? ", a multiple of 4, 16-byte base" : "");
@@ -399,9 +247,10 @@ static int i8q_scan_device_check(const char *call, const float *queries_dev, uin
 }
 
 // the host forms: queries checked and up as rows of `ld` floats (zero padded), the device form on the null stream, the
-// leading `k` of each row of r down as u64 ids (ph_take_launch)
-static int i8q_scan_host(const char *call, const phnsw_store *i8q, const phnsw_store *full, const float *queries, uint64_t nq,
-                         uint32_t r, uint32_t k, uint64_t *out_ids, float *out_d, uint64_t *out_len) {
+// leading `k` of each row of r down as u64 ids (ph_take_launch).  filter: nullptr, or the host words of the filtered forms
+int ph_i8q_scan_host(const char *call, const phnsw_store *i8q, const phnsw_store *full, const float *queries, uint64_t nq,
+                     uint32_t r, uint32_t k, const uint32_t *filter, uint32_t filter_stride, uint64_t *out_ids, float *out_d,
+                     uint64_t *out_len) {
   if (!queries || !out_ids || !out_d || !out_len) {
     ph_set_error("%s: queries and outputs must not be NULL", call);
     return PHNSW_E_INVALID;
@@ -414,9 +263,11 @@ static int i8q_scan_host(const char *call, const phnsw_store *i8q, const phnsw_s
   PH_HIP(hipSetDevice(i8q->device));
   const uint32_t ld = i8q->ld;
   float *qd = nullptr, *od = nullptr, *dk = nullptr;
-  uint32_t *oid = nullptr, *olen = nullptr;
+  uint32_t *oid = nullptr, *olen = nullptr, *fd = nullptr;
   uint64_t *ids64 = nullptr;
   int rc = 0;
+  // the filter's words as the device form reads them: one bitmap, or nq whole strides
+  const size_t filter_bytes = filter ? (filter_stride ? (size_t)nq * filter_stride : (size_t)ph_exact_words(i8q->n)) * 4u : 0u;
   hipError_t e = hipMalloc(&qd, (size_t)nq * ld * 4);
   if (e == hipSuccess && ld != i8q->dim) e = hipMemset(qd, 0, (size_t)nq * ld * 4);
   if (e == hipSuccess)
@@ -426,8 +277,10 @@ static int i8q_scan_host(const char *call, const phnsw_store *i8q, const phnsw_s
   if (e == hipSuccess) e = hipMalloc(&olen, nq * 4);
   if (e == hipSuccess) e = hipMalloc(&ids64, (size_t)nq * k * 8);
   if (e == hipSuccess) e = hipMalloc(&dk, (size_t)nq * k * 4);
+  if (e == hipSuccess && filter_bytes) e = hipMalloc(&fd, filter_bytes);
+  if (e == hipSuccess && filter_bytes) e = hipMemcpy(fd, filter, filter_bytes, hipMemcpyHostToDevice);
   if (e != hipSuccess) rc = ph_hip_fail(e, "i8q scan staging", __FILE__, __LINE__);
-  if (!rc) rc = i8q_scan_enqueue(i8q, qd, ld, nq, r, oid, od, olen, 0);
+  if (!rc) rc = ph_i8q_scan_enqueue(i8q, qd, ld, nq, r, fd, filter_stride, oid, od, olen, 0);
   if (!rc && full) rc = ph_rerank_launch(full, qd, ld, nq, r, k, olen, oid, od, 0);
   if (!rc) rc = ph_take_launch(oid, od, r, k, nq, ids64, dk, 0);
   if (!rc) {
@@ -439,7 +292,7 @@ static int i8q_scan_host(const char *call, const phnsw_store *i8q, const phnsw_s
     if (e != hipSuccess) rc = ph_hip_fail(e, "i8q scan", __FILE__, __LINE__);
     for (uint64_t i = 0; !rc && i < nq; i++) out_len[i] = std::min<uint64_t>(h_len[i], k);
   }
-  for (void *p : {(void *)qd, (void *)od, (void *)dk, (void *)oid, (void *)olen, (void *)ids64})
+  for (void *p : {(void *)qd, (void *)od, (void *)dk, (void *)oid, (void *)olen, (void *)ids64, (void *)fd})
     if (p) hipFree(p);
   return rc;
 }
@@ -448,35 +301,35 @@ extern "C" int phnsw_i8q_scan_topk_device(const phnsw_store *i8q, const float *q
                                           uint64_t r, uint32_t *out_ids_dev, float *out_d_dev, uint32_t *out_len_dev,
                                           void *stream) try {
   const char *const call = "phnsw_i8q_scan_topk_device";
-  PH_TRY(i8q_scan_check(call, i8q, nq, r));
+  PH_TRY(ph_i8q_scan_check(call, i8q, nq, r));
   if (nq == 0) return 0;
-  PH_TRY(i8q_scan_device_check(call, queries_dev, ldq, i8q->dim, false, out_ids_dev, out_d_dev, out_len_dev));
-  return i8q_scan_enqueue(i8q, queries_dev, ldq, nq, (uint32_t)r, out_ids_dev, out_d_dev, out_len_dev, (hipStream_t)stream);
+  PH_TRY(ph_i8q_scan_device_check(call, queries_dev, ldq, i8q->dim, false, out_ids_dev, out_d_dev, out_len_dev));
+  return ph_i8q_scan_enqueue(i8q, queries_dev, ldq, nq, (uint32_t)r, nullptr, 0u, out_ids_dev, out_d_dev, out_len_dev, (hipStream_t)stream);
 } catch (...) { return ph_caught(); }
 
 extern "C" int phnsw_i8q_scan_topk(const phnsw_store *i8q, const float *queries, uint64_t nq, uint64_t r, uint64_t *out_ids,
                                    float *out_d, uint64_t *out_len) try {
   const char *const call = "phnsw_i8q_scan_topk";
-  PH_TRY(i8q_scan_check(call, i8q, nq, r));
+  PH_TRY(ph_i8q_scan_check(call, i8q, nq, r));
   if (nq == 0) return 0;
-  return i8q_scan_host(call, i8q, nullptr, queries, nq, (uint32_t)r, (uint32_t)r, out_ids, out_d, out_len);
+  return ph_i8q_scan_host(call, i8q, nullptr, queries, nq, (uint32_t)r, (uint32_t)r, nullptr, 0u, out_ids, out_d, out_len);
 } catch (...) { return ph_caught(); }
 
 extern "C" int phnsw_i8q_scan_search_device(const phnsw_store *i8q, const phnsw_store *full, const float *queries_dev,
                                             uint32_t ldq, uint64_t nq, uint64_t r, uint64_t k, uint32_t *out_ids_dev,
                                             float *out_d_dev, uint32_t *out_len_dev, void *stream) try {
   const char *const call = "phnsw_i8q_scan_search_device";
-  PH_TRY(i8q_scan_search_check(call, i8q, full, nq, r, k));
+  PH_TRY(ph_i8q_scan_search_check(call, i8q, full, nq, r, k));
   if (nq == 0) return 0;
-  PH_TRY(i8q_scan_device_check(call, queries_dev, ldq, full->ld, true, out_ids_dev, out_d_dev, out_len_dev));
-  PH_TRY(i8q_scan_enqueue(i8q, queries_dev, ldq, nq, (uint32_t)r, out_ids_dev, out_d_dev, out_len_dev, (hipStream_t)stream));
+  PH_TRY(ph_i8q_scan_device_check(call, queries_dev, ldq, full->ld, true, out_ids_dev, out_d_dev, out_len_dev));
+  PH_TRY(ph_i8q_scan_enqueue(i8q, queries_dev, ldq, nq, (uint32_t)r, nullptr, 0u, out_ids_dev, out_d_dev, out_len_dev, (hipStream_t)stream));
   return ph_rerank_launch(full, queries_dev, ldq, nq, (uint32_t)r, (uint32_t)k, out_len_dev, out_ids_dev, out_d_dev, (hipStream_t)stream);
 } catch (...) { return ph_caught(); }
 
 extern "C" int phnsw_i8q_scan_search(const phnsw_store *i8q, const phnsw_store *full, const float *queries, uint64_t nq,
                                      uint64_t r, uint64_t k, uint64_t *out_ids, float *out_d, uint64_t *out_len) try {
   const char *const call = "phnsw_i8q_scan_search";
-  PH_TRY(i8q_scan_search_check(call, i8q, full, nq, r, k));
+  PH_TRY(ph_i8q_scan_search_check(call, i8q, full, nq, r, k));
   if (nq == 0) return 0;
-  return i8q_scan_host(call, i8q, full, queries, nq, (uint32_t)r, (uint32_t)k, out_ids, out_d, out_len);
+  return ph_i8q_scan_host(call, i8q, full, queries, nq, (uint32_t)r, (uint32_t)k, nullptr, 0u, out_ids, out_d, out_len);
 } catch (...) { return ph_caught(); }

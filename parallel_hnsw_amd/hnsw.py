@@ -843,6 +843,52 @@ class I8QStore(_Int8Rows):
                                                   C.c_void_p(out_ids), C.c_void_p(out_d), C.c_void_p(out_len),
                                                   C.c_void_p(stream or None)))
 
+    def scan_filtered(self, queries, r, allow):
+        """scan over the allowed rows only (phnsw_i8q_scan_topk_filtered): allow is a bool mask [n] or its packed u32
+        words (one list for the batch: compacted on the device, only allowed rows are staged) or [nq, n] / packed
+        [nq, stride] (one per query: the full scan, a row's bit tested when its dot product passes), packed as for
+        search_exact_filtered.  Per query the min(r, allowed rows) allowed rows with the smallest (distance, id), every
+        pair with the bits scan() gives it -> ids[nq, r] u64, d[nq, r] f32, len[nq]"""
+        q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+        assert q.shape[1] == self.dim
+        nq, r = q.shape[0], int(r)
+        if allow is None:
+            raise ValueError("allow: a mask is required (scan() scans every row)")
+        words, stride = pack_allow(allow, self.n, nq)
+        ids = np.empty((nq, max(r, 0)), dtype=np.uint64)
+        d = np.empty((nq, max(r, 0)), dtype=np.float32)
+        ln = np.zeros(nq, dtype=np.uint64)
+        check(lib().phnsw_i8q_scan_topk_filtered(self._h, _p(q), nq, r, _p(words), stride, _p(ids), _p(d), _p(ln)))
+        return ids, d, ln
+
+    def scan_filtered_device(self, nq, r, queries, ldq, allow, allow_stride, out_ids, out_d, out_len, stream=0):
+        """zero-copy form of scan_filtered (device pointers as ints; allow = one packed bitmap, allow_stride 0, or nq
+        bitmaps allow_stride words apart; u32 ids, rows of r)"""
+        check(lib().phnsw_i8q_scan_topk_filtered_device(self._h, C.c_void_p(queries), ldq, nq, int(r), C.c_void_p(allow or None),
+                                                         int(allow_stride), C.c_void_p(out_ids), C.c_void_p(out_d),
+                                                         C.c_void_p(out_len), C.c_void_p(stream or None)))
+
+    def scan_search_filtered(self, full, queries, r, k, allow):
+        """scan_filtered for r candidates, each recomputed on the f32 store `full`, sorted by (distance, id), the best
+        k <= r kept (phnsw_i8q_scan_search_filtered) -> ids[nq, k] u64, true f32 distances d[nq, k], len[nq]"""
+        q = np.ascontiguousarray(np.atleast_2d(queries), dtype=np.float32)
+        assert q.shape[1] == self.dim
+        nq, r, k = q.shape[0], int(r), int(k)
+        if allow is None:
+            raise ValueError("allow: a mask is required (scan_search() scans every row)")
+        words, stride = pack_allow(allow, self.n, nq)
+        ids = np.empty((nq, max(k, 0)), dtype=np.uint64)
+        d = np.empty((nq, max(k, 0)), dtype=np.float32)
+        ln = np.zeros(nq, dtype=np.uint64)
+        check(lib().phnsw_i8q_scan_search_filtered(self._h, full._h, _p(q), nq, r, k, _p(words), stride, _p(ids), _p(d), _p(ln)))
+        return ids, d, ln
+
+    def scan_search_filtered_device(self, full, nq, r, k, queries, ldq, allow, allow_stride, out_ids, out_d, out_len, stream=0):
+        """zero-copy form of scan_search_filtered (as scan_filtered_device; rows of r: the first min(len, k) live)"""
+        check(lib().phnsw_i8q_scan_search_filtered_device(self._h, full._h, C.c_void_p(queries), ldq, nq, int(r), int(k),
+                                                           C.c_void_p(allow or None), int(allow_stride), C.c_void_p(out_ids),
+                                                           C.c_void_p(out_d), C.c_void_p(out_len), C.c_void_p(stream or None)))
+
 
 class BitStore(VectorStore):
     """one sign bit per component of an f32 VectorStore (phnsw_store_create_bits): bit j of a row is row[j] < 0, 96

@@ -327,6 +327,44 @@ impl GpuComparator {
         });
     }
 
+    /// `i8q_scan` over an allow-list (`phnsw_i8q_scan_topk_filtered`; with `full`, `phnsw_i8q_scan_search_filtered` and
+    /// its `k`): `filter` and `stride_words` as for `fp4_scan_filtered`.  Per query the allowed rows with the smallest
+    /// (distance, id), at most `r` (`k`) of them, every pair with the bits `i8q_scan` gives it.
+    pub fn i8q_scan_filtered(&self, full: Option<(&GpuComparator, usize)>, queries: &[Vec<f32>], r: usize, filter: &[u32],
+                             stride_words: u32) -> Vec<Vec<(VectorId, f32)>> {
+        let nq = queries.len();
+        let q: Vec<f32> = queries.iter().flatten().copied().collect();
+        let w = full.map_or(r, |(_, k)| k);
+        let (mut ids, mut d, mut len) = (vec![0u64; nq * w], vec![0f32; nq * w], vec![0u64; nq]);
+        check(unsafe {
+            match full {
+                None => sys::phnsw_i8q_scan_topk_filtered(self.store.0, q.as_ptr(), nq as u64, r as u64, filter.as_ptr(),
+                                                          stride_words, ids.as_mut_ptr(), d.as_mut_ptr(), len.as_mut_ptr()),
+                Some((f, k)) => sys::phnsw_i8q_scan_search_filtered(self.store.0, f.store.0, q.as_ptr(), nq as u64, r as u64,
+                                                                    k as u64, filter.as_ptr(), stride_words, ids.as_mut_ptr(),
+                                                                    d.as_mut_ptr(), len.as_mut_ptr()),
+            }
+        });
+        (0..nq).map(|i| (0..len[i] as usize).map(|j| (VectorId(ids[i * w + j] as usize), d[i * w + j])).collect()).collect()
+    }
+
+    /// zero-copy forms (`phnsw_i8q_scan_topk_filtered_device`; with `full`, `phnsw_i8q_scan_search_filtered_device`)
+    ///
+    /// # Safety
+    /// the pointers must be valid device allocations of the sizes `phnsw.h` documents for the call
+    #[allow(clippy::too_many_arguments)]
+    pub unsafe fn i8q_scan_filtered_device(&self, full: Option<(&GpuComparator, u64)>, queries_dev: *const f32, ldq: u32,
+                                            nq: u64, r: u64, filter_dev: *const u32, stride_words: u32, out_ids_dev: *mut u32,
+                                            out_d_dev: *mut f32, out_len_dev: *mut u32, stream: *mut c_void) {
+        check(match full {
+            None => sys::phnsw_i8q_scan_topk_filtered_device(self.store.0, queries_dev, ldq, nq, r, filter_dev, stride_words,
+                                                              out_ids_dev, out_d_dev, out_len_dev, stream),
+            Some((f, k)) => sys::phnsw_i8q_scan_search_filtered_device(self.store.0, f.store.0, queries_dev, ldq, nq, r, k,
+                                                                        filter_dev, stride_words, out_ids_dev, out_d_dev,
+                                                                        out_len_dev, stream),
+        });
+    }
+
     /// codes `[n][dim]` and scales `[n]` of a `to_i8()` or `to_i8q()` comparator (`phnsw_i8_read`)
     pub fn i8_codes_and_scales(&self) -> (Vec<i8>, Vec<f32>) {
         let (n, dim) = (self.host.len(), self.host.first().map_or(0, |v| v.len()));

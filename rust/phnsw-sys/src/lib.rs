@@ -736,6 +736,22 @@ extern "C" {
                                                  filter_dev: *const u32, filter_stride_words: u32, out_ids_dev: *mut u32,
                                                  out_d_dev: *mut c_float, out_len_dev: *mut u32,
                                                  stream: *mut c_void) -> c_int;
+    // the i8q four over an allow-list: one packed bitmap (filter_stride_words 0) or one per query
+    pub fn phnsw_i8q_scan_topk_filtered(i8q: *const phnsw_store, queries: *const c_float, nq: u64, r: u64,
+                                        filter: *const u32, filter_stride_words: u32, out_ids: *mut u64,
+                                        out_d: *mut c_float, out_len: *mut u64) -> c_int;
+    pub fn phnsw_i8q_scan_topk_filtered_device(i8q: *const phnsw_store, queries_dev: *const c_float, ldq: u32, nq: u64,
+                                               r: u64, filter_dev: *const u32, filter_stride_words: u32,
+                                               out_ids_dev: *mut u32, out_d_dev: *mut c_float, out_len_dev: *mut u32,
+                                               stream: *mut c_void) -> c_int;
+    pub fn phnsw_i8q_scan_search_filtered(i8q: *const phnsw_store, full: *const phnsw_store, queries: *const c_float,
+                                          nq: u64, r: u64, k: u64, filter: *const u32, filter_stride_words: u32,
+                                          out_ids: *mut u64, out_d: *mut c_float, out_len: *mut u64) -> c_int;
+    pub fn phnsw_i8q_scan_search_filtered_device(i8q: *const phnsw_store, full: *const phnsw_store,
+                                                 queries_dev: *const c_float, ldq: u32, nq: u64, r: u64, k: u64,
+                                                 filter_dev: *const u32, filter_stride_words: u32, out_ids_dev: *mut u32,
+                                                 out_d_dev: *mut c_float, out_len_dev: *mut u32,
+                                                 stream: *mut c_void) -> c_int;
 
     // ---- MXFP4 rows: 4-bit codes, one power-of-two scale per 32 components; re-rank on the f32 store
     pub fn phnsw_store_create_fp4(full: *const phnsw_store, out: *mut *mut phnsw_store) -> c_int;
