@@ -96,7 +96,11 @@ const char *phnsw_last_error(void);
 int phnsw_device_count(void);
 
 /* ---- store: replaces BigComparator{data: Arc<Vec<Vec<f32>>>}  src/bigvec.rs:38-57 ----
- * rows are copied into one flat HBM array [n][ld], ld = dim rounded up to 4 floats. */
+ * rows are copied into one flat HBM array [n][ld], ld = dim rounded up to 4 floats.
+ * Supported dimensions: every call serves rows of at most 1536 floats.  An f32 store with rows of 1537 .. 4096 floats is
+ * served by phnsw_distance_batch, the plain searches (phnsw_search_batch, _device, _stored, _topk) and phnsw_build with
+ * the layer, link and improve calls; everything else returns PHNSW_E_UNSUPPORTED for it, as every call does past 4096
+ * floats. */
 int phnsw_store_create(const float *rows, uint64_t n, uint32_t dim, int metric, int device,
                        phnsw_store **out);
 /* append rows to a store that owns its array (ids continue at the old n; *out_first_id = first

@@ -799,6 +799,12 @@ int ph_search_device(const phnsw_index *ix, const PhSearchCall &c) {
   if (ph_store_bits(ix->store) && (c.filter.words || c.filter.label_of || c.filter.attr_of || c.filter.pair_of || c.filter.set_first ||
                                    c.collect_k || c.radius))
     return ph_bits_unsupported(ix->store, "filtered / labelled / ranged / collecting / radius search");
+  // f32 rows past 1536 floats have the plain walk alone too (search_wide.hip): every other search keeps the answer it
+  // gave before those rows were served at all
+  if (ph_store_f32(ix->store) && ph_wide_chunk_count(ix->store->ld / 4) &&
+      (knn_mode || out_index || c.filter.words || c.filter.label_of || c.filter.attr_of || c.filter.pair_of || c.filter.set_first ||
+       c.collect_k || c.radius))
+    return ph_dim_unsupported(ix->store->dim);
   PhSearchArgs a;
   fill_args(ix, c, a);
   if (ix->dbg_order && ix->dbg_order_n == nq) a.order = ix->dbg_order;

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "phnsw_device.h"
+#include "wide_rows.h"
 
 // group.hip (rocPRIM sort / scan)
 int ph_sort_u32_host(uint32_t *keys, uint32_t n);
@@ -218,8 +219,16 @@ __global__ __launch_bounds__(64) void ph_seed_rows_kernel(PhSeedArgs a) {
       uint32_t k = base + lane;
       bool act = k < picks;
       uint32_t member = 0, vm = 0;
-      if (act) {
-        uint64_t f = ph_feistel_perm(k, domain, rkey);
+      // The loop below reads psz / pst of the supers' lanes (rl32 on the lanes of pm), and a supers lane need not be a
+      // lane with a pick.  Inside a branch only the `act` lanes enter, the compiler may reload psz / pst from where it
+      // parked them under the branch's mask; the lanes outside it then hold stale values and the readlane returns them.
+      // The instances of DistF32Wide<12> and <16> did exactly that (v_accvgpr_read of pst under the mask of `act`, then
+      // v_readlane on a lane of pm) and seeded wrong rows.  For a wide policy every lane therefore runs the block, the
+      // idle ones on pick 0 (which exists: picks > 0 here), so the readlanes execute under the full mask.  The other
+      // policies' instances are left as compiled: at their register pressure psz / pst stay in VGPRs, but the hazard
+      // is in the source for them too
+      if (act || dist_is_wide<Dist>::value) {
+        uint64_t f = ph_feistel_perm(act ? k : 0u, domain, rkey);
         if (excl && f >= i) f += 1;
         uint32_t midx = 0;
         bool found = false;
@@ -451,7 +460,9 @@ __global__ void ph_link_targets_kernel(const uint32_t *nodes, uint32_t n, const 
 
 // ------------------------------------------------------------------ host: shared steps
 
-static bool store_supported(const phnsw_store *s) { return ph_store_pq(s) || ph_chunk_count(s->ld / 4) != 0; }
+// f32 rows of 1537 .. 4096 floats: the streaming policy (wide_rows.h)
+static int wide_class(const phnsw_store *s) { return ph_store_f32(s) ? ph_wide_chunk_count(s->ld / 4) : 0; }
+static bool store_supported(const phnsw_store *s) { return ph_store_pq(s) || ph_chunk_count(s->ld / 4) != 0 || wide_class(s) != 0; }
 // resident one-wave blocks a PQ kernel can have per chip: the lookup table dominates the LDS
 static uint32_t pq_grid(const phnsw_store *s, uint32_t want) {
   size_t per = ph_pq_lds_bytes(s) + 8 * 1024;
@@ -459,8 +470,11 @@ static uint32_t pq_grid(const phnsw_store *s, uint32_t want) {
   return std::min<uint32_t>(want, 256u * std::min<uint32_t>(per_cu, 16u));
 }
 
-template <typename K1, typename K3, typename K6, typename KQ, typename... Args>
-static int launch_by_policy(const phnsw_store *s, dim3 g, K1 k1, K3 k3, K6 k6, KQ kq, Args... args) {
+// the instances of a kernel template over the distance policies, in launch_by_policy's order
+#define PH_POLICY_KERNELS(K) \
+  K<DistF32<1>>, K<DistF32<3>>, K<DistF32<6>>, K<DistPQ>, K<DistF32Wide<8>>, K<DistF32Wide<12>>, K<DistF32Wide<16>>
+template <typename K1, typename K3, typename K6, typename KQ, typename KW8, typename KW12, typename KW16, typename... Args>
+static int launch_by_policy(const phnsw_store *s, dim3 g, K1 k1, K3 k3, K6 k6, KQ kq, KW8 kw8, KW12 kw12, KW16 kw16, Args... args) {
   if (ph_store_pq(s)) {
     size_t lds = ph_pq_lds_bytes(s);
     if (lds > 48 * 1024) {
@@ -468,6 +482,13 @@ static int launch_by_policy(const phnsw_store *s, dim3 g, K1 k1, K3 k3, K6 k6, K
       if (e != hipSuccess) return ph_hip_fail(e, "hipFuncSetAttribute(LDS)", __FILE__, __LINE__);
     }
     hipLaunchKernelGGL(kq, g, dim3(64), lds, 0, args...);
+  } else if (const int wide = wide_class(s)) {
+    if (wide == 8)
+      hipLaunchKernelGGL(kw8, g, dim3(64), 0, 0, args...);
+    else if (wide == 12)
+      hipLaunchKernelGGL(kw12, g, dim3(64), 0, 0, args...);
+    else  // 16: ph_wide_chunk_count has no other value
+      hipLaunchKernelGGL(kw16, g, dim3(64), 0, 0, args...);
   } else {
     switch (ph_chunk_count(s->ld / 4)) {
       case 1:
@@ -532,9 +553,8 @@ static int ensure_row_dist(phnsw_index *ix, PhLayerHost &L) {
   PH_HIP(hipMalloc(&L.nbr_dist, (size_t)L.n_nodes * L.W * 4));
   // a PQ table takes most of a CU's LDS: one resident wave per CU is all that fits
   dim3 g(ph_store_pq(s) ? pq_grid(s, L.n_nodes) : wave_grid(L.n_nodes));
-  return launch_by_policy(s, g, ph_row_dist_kernel<DistF32<1>>, ph_row_dist_kernel<DistF32<3>>,
-                          ph_row_dist_kernel<DistF32<6>>, ph_row_dist_kernel<DistPQ>, ph_dist_args(s), L.nodes, L.n_nodes,
-                          L.W, L.neighbors, L.nbr_dist);
+  return launch_by_policy(s, g, PH_POLICY_KERNELS(ph_row_dist_kernel), ph_dist_args(s), L.nodes, L.n_nodes, L.W, L.neighbors,
+                          L.nbr_dist);
 }
 
 // run the batched search for Stored queries and surface per-query failures
@@ -920,8 +940,7 @@ static int layer_seed_impl(phnsw_index *ix, const phnsw_build_params *bp, const 
   a.rows = out_rows;
   a.rows_d = out_rows_d;
   dim3 g(ph_store_pq(s) ? pq_grid(s, count) : wave_grid(count));
-  PH_TRY(launch_by_policy(s, g, ph_seed_rows_kernel<DistF32<1>>, ph_seed_rows_kernel<DistF32<3>>,
-                          ph_seed_rows_kernel<DistF32<6>>, ph_seed_rows_kernel<DistPQ>, a));
+  PH_TRY(launch_by_policy(s, g, PH_POLICY_KERNELS(ph_seed_rows_kernel), a));
   PH_HIP(hipDeviceSynchronize());
   return 0;
 }
@@ -1395,12 +1414,10 @@ static int filter_promotion_candidates_impl(phnsw_index *ix, uint32_t lft, const
     PH_TRY(search_stored(ix, cand_d.p + c0, bc, sp, lft, nullptr, r_id.p, r_d.p, r_len.p, 1, nullptr));
     dim3 g(ph_store_pq(s) ? pq_grid(s, bc) : wave_grid(bc));
     if (prev)
-      PH_TRY(launch_by_policy(s, g, ph_cover_kernel<DistF32<1>>, ph_cover_kernel<DistF32<3>>, ph_cover_kernel<DistF32<6>>,
-                              ph_cover_kernel<DistPQ>, ph_dist_args(s), cand_d.p + c0, bc, (const uint32_t *)sel_d.p,
-                              (uint32_t)prev, (const float *)rad_d.p, cov_d.p, (float *)nullptr));
-    PH_TRY(launch_by_policy(s, g, ph_cover_kernel<DistF32<1>>, ph_cover_kernel<DistF32<3>>, ph_cover_kernel<DistF32<6>>,
-                            ph_cover_kernel<DistPQ>, ph_dist_args(s), cand_d.p + c0, bc, (const uint32_t *)(cand_d.p + c0), bc,
-                            (const float *)nullptr, (uint32_t *)nullptr, table.p));
+      PH_TRY(launch_by_policy(s, g, PH_POLICY_KERNELS(ph_cover_kernel), ph_dist_args(s), cand_d.p + c0, bc,
+                              (const uint32_t *)sel_d.p, (uint32_t)prev, (const float *)rad_d.p, cov_d.p, (float *)nullptr));
+    PH_TRY(launch_by_policy(s, g, PH_POLICY_KERNELS(ph_cover_kernel), ph_dist_args(s), cand_d.p + c0, bc,
+                            (const uint32_t *)(cand_d.p + c0), bc, (const float *)nullptr, (uint32_t *)nullptr, table.p));
     hr.resize(bc);
     hl.resize(bc);
     hc.assign(bc, 0);

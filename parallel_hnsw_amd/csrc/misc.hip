@@ -8,6 +8,7 @@
 #include <chrono>
 
 #include "phnsw_device.h"
+#include "wide_rows.h"
 
 // ---- K1: out[i] = compare_vec(query, Stored(ids[i])); a wave takes 64 candidates at a time ----
 template <class Dist>
@@ -48,6 +49,23 @@ static int distance_batch_rows(const phnsw_store *st, const PhDistArgs &da, cons
   return 0;
 }
 
+// f32 rows past ph_chunk_count's classes: the streaming policy (wide_rows.h), up to 4096 floats
+static int distance_batch_wide(const phnsw_store *st, const PhDistArgs &da, const float *q_dev, uint32_t query_id,
+                               const uint32_t *ids_dev, uint32_t k, float *out_dev, hipStream_t s) {
+  const uint32_t blocks = std::min<uint32_t>((k + 63) / 64, 4096);
+#define PH_LAUNCH(NV)                                                                                                     \
+  hipLaunchKernelGGL((ph_distance_batch_kernel<DistF32Wide<NV>>), dim3(blocks), dim3(64), 0, s, da, q_dev, query_id, ids_dev, \
+                     k, st->n, out_dev)
+  switch (ph_wide_chunk_count(st->ld / 4)) {
+    case 8: PH_LAUNCH(8); break;
+    case 12: PH_LAUNCH(12); break;
+    case 16: PH_LAUNCH(16); break;
+    default: return ph_wide_dim_unsupported(st->dim);
+  }
+#undef PH_LAUNCH
+  return 0;
+}
+
 // a bits store: DistBits has one template argument
 static int distance_batch_bits(const phnsw_store *st, const PhDistArgs &da, const float *q_dev, uint32_t query_id,
                                const uint32_t *ids_dev, uint32_t k, float *out_dev, hipStream_t s) {
@@ -67,6 +85,12 @@ static int distance_batch_bits(const phnsw_store *st, const PhDistArgs &da, cons
 
 int ph_dim_unsupported(uint32_t dim) {
   ph_set_error("dim %u unsupported (max 1536)", dim);
+  return PHNSW_E_UNSUPPORTED;
+}
+
+// what the calls that serve wide f32 rows say past their last class
+int ph_wide_dim_unsupported(uint32_t dim) {
+  ph_set_error("dim %u unsupported (max 4096 over f32 rows for the distance batch, the plain search and the build; max 1536 elsewhere)", dim);
   return PHNSW_E_UNSUPPORTED;
 }
 
@@ -94,7 +118,10 @@ int ph_distance_batch(const phnsw_store *st, const float *q_dev, uint32_t query_
       case PH_ROWS_FP4: rc = distance_batch_rows<DistFP4>(st, da, q_dev, query_id, ids_dev, k, out_dev, s); break;
       case PH_ROWS_I8Q: rc = distance_batch_rows<DistI8Q>(st, da, q_dev, query_id, ids_dev, k, out_dev, s); break;  // integer dots
       case PH_ROWS_BITS: rc = distance_batch_bits(st, da, q_dev, query_id, ids_dev, k, out_dev, s); break;         // popcounts
-      default: rc = distance_batch_rows<DistF32>(st, da, q_dev, query_id, ids_dev, k, out_dev, s); break;
+      default:
+        rc = ph_chunk_count(st->ld / 4) ? distance_batch_rows<DistF32>(st, da, q_dev, query_id, ids_dev, k, out_dev, s)
+                                        : distance_batch_wide(st, da, q_dev, query_id, ids_dev, k, out_dev, s);
+        break;
     }
     if (rc) return rc;
   }

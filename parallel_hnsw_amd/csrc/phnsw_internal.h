@@ -86,6 +86,11 @@ static inline const char *ph_rows_name(int kind) {
 // float4 chunks a lane holds of a row of nv4 float4s: the three shapes the row kernels are instantiated for (0: none;
 // a launch switches on this value, one case per instance)
 static inline int ph_chunk_count(uint32_t nv4) { return nv4 <= 64 ? 1 : (nv4 <= 192 ? 3 : (nv4 <= 384 ? 6 : 0)); }
+// the same for the rows ph_chunk_count refuses, 1537 .. 4096 floats of an F32 store: the classes of the streaming
+// policy (DistF32Wide, wide_rows.h).  Asked only where that policy has instances: the distance batch, the plain walk
+// and the build; everything else keeps to ph_chunk_count and refuses
+static inline int ph_wide_chunk_count(uint32_t nv4) { return nv4 <= 384 ? 0 : (nv4 <= 512 ? 8 : (nv4 <= 768 ? 12 : (nv4 <= 1024 ? 16 : 0))); }
+int ph_wide_dim_unsupported(uint32_t dim);  // sets "dim unsupported (max 4096 ...)", returns PHNSW_E_UNSUPPORTED (misc.hip)
 // bytes of an fp4 row of ld components: per section of 1024 components 32 scale bytes and its codes (phnsw_device.h)
 static inline uint32_t ph_fp4_stride(uint32_t ld) { return (ld / 2u + 32u * ((ld / 4u + 255u) / 256u) + 15u) & ~15u; }
 int ph_dim_unsupported(uint32_t dim);  // sets "dim unsupported (max 1536)", returns PHNSW_E_UNSUPPORTED (misc.hip)

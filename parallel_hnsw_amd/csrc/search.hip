@@ -160,6 +160,13 @@ static PhKernelChoice pick_unfiltered_kernel(const phnsw_store *s, uint32_t ef_m
       return k;
     default: break;
   }
+  if (s->kind == PH_ROWS_F32 && ph_wide_chunk_count(nv4)) {  // search_wide.hip: the bits family's queues, batches of every size
+    k.family = PH_KF_ROWS_WIDE;
+    k.nv = ph_wide_chunk_count(nv4);
+    k.capc = pick_capc_dense(ef_max);
+    k.fn = (instr || grows) ? nullptr : ph_pick_kernel_wide(k.capc, k.nv);
+    return k;
+  }
   k.nv = ph_chunk_count(nv4);
   if (s->kind == PH_ROWS_F32 && !instr && nq <= PH_LATENCY_MAX && !getenv("PHNSW_NO_LAT") && pick_kernel_lat<false>(capc, k.nv)) {
     k.family = PH_KF_LATENCY;
@@ -277,6 +284,8 @@ int ph_workspace_ensure(const phnsw_index *ix, PhWorkspace &ws, uint32_t ef, uin
   }
   const bool pqg = family == PH_KF_PQ_REG || (family == PH_KF_PQ_TABLE && ph_pq_global_tables());  // table slots in global memory
   if (slots == 0) {
+    // f32 rows past every class, the wide ones included (search_wide.hip): the plain search's own limit
+    if (ph_store_f32(st) && !ph_chunk_count(st->ld / 4) && !ph_wide_chunk_count(st->ld / 4)) return ph_wide_dim_unsupported(st->dim);
     ph_set_error("unsupported search shape: ef=%u dim=%u (ef <= 1024, dim <= 1536; PQ table + queue <= 160 KB LDS)", ef,
                  ix->store->dim);
     return PHNSW_E_UNSUPPORTED;

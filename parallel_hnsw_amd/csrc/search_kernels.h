@@ -55,7 +55,7 @@ __device__ __forceinline__ void queue_sync() {
 // 4 -> 3 waves per SIMD).  The one-wave-per-SIMD latency kernels (U = 0) measured 2 % slower with the table for
 // batches of 1, 64 and 1024 and keep the bitmap too.
 __host__ __device__ constexpr bool vis_lds_shape(int capc, int nv) {
-  return capc == 2 || (capc == 4 && nv != 1) || (capc == 8 && nv == 6);
+  return nv <= 6 && (capc == 2 || (capc == 4 && nv != 1) || (capc == 8 && nv == 6));  // (nv > 6: search_wide.hip, the bitmap)
 }
 template <int CAPC, class D, class = void>
 struct vis_lds_policy : std::false_type {};
@@ -1261,6 +1261,7 @@ enum PhKernelFamily {
   PH_KF_INSTR,      // Hnsw::search_instrumented over f32 rows
   PH_KF_ROWS_BITS,  // throughput kernels over 1-bit sign rows (search_bits.hip; no filtered, collecting or radius twin)
   PH_KF_ROWS_FP4,   // throughput kernels over MXFP4 rows, every twin the other row families have
+  PH_KF_ROWS_WIDE,  // throughput kernels over f32 rows of 1537 .. 4096 floats (search_wide.hip; plain searches only)
 };
 
 // the register-table PQ policy (pick_pqr): 32 / 64 / 96 / 128 sub-spaces, queues of up to 512 entries
@@ -1374,6 +1375,9 @@ ph_search_fn ph_pick_radius_kernel(int family, int nv);
 // the kernels of a bits store (search_bits.hip): queues of capc * 64 slots, capc in {2, 4, 8, 16}, nv in {1, 3, 6}; plain
 // searches only -- pick_kernel_family has no case for the family, so no FILT twin of them exists
 ph_search_fn ph_pick_kernel_bits(int capc, int nv);
+// the kernels of f32 rows of 1537 .. 4096 floats (search_wide.hip): the same queues, nv in {8, 12, 16}
+// (ph_wide_chunk_count); plain searches only, like the bits family
+ph_search_fn ph_pick_kernel_wide(int capc, int nv);
 // the collecting twins (PH_FM_COLLECT over the bitmap and over the label column): search_collect.hip and
 // search_collect_labeled.hip.  No dense-only twin: a collecting kernel runs the last layer of a descent, and the
 // dense-only launch of a split descent never holds it (api.hip)

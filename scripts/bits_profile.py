@@ -38,9 +38,9 @@ FIGURES = ("TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "Dynamic 
            "SGPRs Spill", "VGPRs Spill", "LDS Size [bytes/block]")
 
 
-def resource_report(csrc, unit):
+def resource_report(csrc, unit, defines=()):
     """{kernel: {figure: value}} of one translation unit, from the compiler's remarks"""
-    extra = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"] if unit == "tiny.hip" else []
+    extra = (["-mllvm", "-amdgpu-mfma-vgpr-form=1"] if unit == "tiny.hip" else []) + ["-D" + d for d in defines]
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     err = subprocess.run([hipcc] + FLAGS + extra + [unit], cwd=csrc, capture_output=True, text=True).stderr
     out, cur = {}, None
